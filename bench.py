@@ -164,6 +164,37 @@ def launcher_command(gpus, argv, port):
     return cmd, env
 
 
+DUMP_BYTES = 48 << 20   # what --dump-outputs may write in all (it must stay below 64 MB)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(dirname, part, plan, lnl, lo, taxa, attrs):
+    """What a caller of the timed path holds after its last step, as DIR/<name>.npy in float64: the lnL
+    pll_compute_edge_loglikelihood returned, and the root edge's two CLVs and scale buffers it read, at a fixed
+    seeded sample of this partition's sites (the same sites for the same arguments; site_index.npy holds them as
+    global column numbers).  A CLV that is a tip's character row under PLL_ATTRIB_PATTERN_TIP has none to write."""
+    from libpll_amd.pllapi import ATTRIB_PATTERN_TIP
+    os.makedirs(dirname, exist_ok=True)
+    pclv, pscaler, cclv, cscaler = (int(x) for x in plan.root_edge[:4])
+    sites = part.sites_total
+    per_site = 0
+    sides = []
+    for name, clv, scaler in (("parent", pclv, pscaler), ("child", cclv, cscaler)):
+        has_clv = clv >= taxa or not (attrs & ATTRIB_PATTERN_TIP)
+        sides.append((name, clv if has_clv else None, scaler if scaler >= 0 else None))
+        per_site += (part.s.rate_cats * part.s.states if has_clv else 0) + (part.scaler_len // sites if scaler >= 0 else 0)
+    n = min(sites, DUMP_BYTES // (8 * max(per_site, 1)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(sites, size=n, replace=False))
+    arrays = {"lnl": np.array([lnl], dtype=np.float64), "site_index": (idx + lo).astype(np.float64)}
+    for name, clv, scaler in sides:
+        if clv is not None:
+            arrays["root_%s_clv" % name] = part.get_clv(clv)[idx].astype(np.float64)
+        if scaler is not None:
+            arrays["root_%s_scaler" % name] = part.get_scaler(scaler).reshape(sites, -1)[idx].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     t_process = time.perf_counter()
     sections = {}
@@ -213,7 +244,12 @@ def main():
     ap.add_argument("--newton", type=int, default=0,
                     help="also time pll_update_sumtable + N x pll_compute_likelihood_derivatives "
                          "at the root edge (BASELINE config 5's inner loop)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/*.npy (float64, rank 0): its lnL and, at a "
+                         "fixed seeded sample of sites, the two root-edge CLVs and their scale buffers")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -440,6 +476,9 @@ def main():
         elapsed = float(t.item())
 
     lnl_timed = lnl   # (the last timed step's value: at N > 1 the sum over the ranks, made by the library's all-reduce)
+    if args.dump_outputs and rank == 0:
+        # read back now, before any later leg runs other op lists over the same CLVs
+        dump_outputs(args.dump_outputs, part, plan, lnl_timed, lo, T, attrs)
     site_updates = float(ops_per_eval) * total_sites * args.steps
     value = site_updates / elapsed / 1e6
     untimed_steps = 1 + len(ramp_steps) + args.warmup   # what really ran before the timed region

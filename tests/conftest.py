@@ -47,6 +47,10 @@ def amd():
     """The product library.  Missing library = hard failure, never a skip."""
     if not os.path.exists(LIB):
         _make("lib")
+    # torch first, as in bench.py: it carries its own HIP runtime and RCCL.  Loaded after the library, a test that
+    # imports torch would map a second HIP runtime next to the library's, and the RCCL the library then binds (the
+    # copy already in the process: torch's) runs on the other one -- its communicator fails to initialise.
+    import torch  # noqa: F401
     import libpll_amd
     return libpll_amd.load()
 

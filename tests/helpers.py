@@ -37,18 +37,21 @@ def make_case(states=4, shape="balanced", tips=16, sites=200, rate_cats=4, seed=
 ALPHABET = b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789"
 
 
-def odd_state_case(states, tips=9, sites=30, seed=3, shape="random", **kw):
+def odd_state_case(states, tips=9, sites=30, seed=3, shape="random", observed=None, **kw):
     """Data with 2..32 states (other than 4 and 20) over the alphabet A.. with a
-    hand-made character map."""
+    hand-made character map.  observed: tip characters name only the first `observed`
+    states (more than 32 states: what 32-bit character masks can say; the gap is then
+    those states)."""
     case = make_case(states, shape, tips, sites, seed=seed, **kw)
     rng = np.random.default_rng(seed)
-    alphabet = ALPHABET[:states]
+    n = observed or states
+    alphabet = ALPHABET[:n]
     chars = np.frombuffer(alphabet, dtype=np.uint8)
-    case["seqs"] = [chars[rng.integers(0, states, sites)].tobytes() for _ in range(tips)]
+    case["seqs"] = [chars[rng.integers(0, n, sites)].tobytes() for _ in range(tips)]
     cmap = np.zeros(256, dtype=np.uint32)
     for i, ch in enumerate(alphabet):
         cmap[ch] = 1 << i
-    cmap[ord("-")] = (1 << states) - 1
+    cmap[ord("-")] = (1 << n) - 1
     for s in range(0, tips, 3):
         b = bytearray(case["seqs"][s])
         b[s % sites] = ord("-")

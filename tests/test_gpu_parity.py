@@ -56,8 +56,7 @@ def compare(p, o, case, R, exact=True):
 @pytest.mark.parametrize("rate_scalers", [0, ATTRIB_RATE_SCALERS])
 def test_evaluation_matches_oracle(gpu, orc, aa_mode, states, shape, tips, sites, pattern_tip,
                                    rate_scalers):
-    if states == 4 and aa_mode != "exact":
-        pytest.skip("mode only affects 20-state kernels")
+    # (4 states: the 20-state modes change nothing -- bit for bit in every one of them)
     exact = states == 4 or aa_mode == "exact"
     attrs = pattern_tip | rate_scalers
     case = make_case(states, shape, tips, sites, seed=sites)
@@ -82,8 +81,7 @@ def test_evaluation_matches_oracle(gpu, orc, aa_mode, states, shape, tips, sites
 @pytest.mark.parametrize("rate_scalers", [0, ATTRIB_RATE_SCALERS])
 def test_deep_tree_scaler_counts_bit_exact(gpu, orc, aa_mode, states, tips, expect_min, rate_scalers):
     """Pattern-tip caterpillar: tip-inner kernels all the way down."""
-    if states == 4 and aa_mode != "exact":
-        pytest.skip("mode only affects 20-state kernels")
+    # (4 states: the 20-state modes change nothing -- bit for bit in every one of them)
     exact = states == 4 or aa_mode == "exact"
     attrs = ATTRIB_PATTERN_TIP | rate_scalers
     case = make_case(states, "caterpillar", tips, 8, seed=5, alpha=0.5, branch=0.5, weights=False,
@@ -118,8 +116,7 @@ def test_deep_aa_inner_inner_scalers(gpu, orc, aa_mode, rate_scalers):
 @pytest.mark.parametrize("states", [4, 20])
 def test_rate_category_counts(gpu, orc, aa_mode, states, rate_cats):
     """1/2/8/16 use the lane-per-(site,rate) kernels, 3 the generic fallback."""
-    if states == 4 and aa_mode != "exact":
-        pytest.skip("mode only affects 20-state kernels")
+    # (4 states: the 20-state modes change nothing -- bit for bit in every one of them)
     exact = states == 4 or aa_mode == "exact"
     attrs = ATTRIB_PATTERN_TIP
     case = make_case(states, "random", 9, 101, rate_cats=rate_cats, seed=rate_cats)
@@ -144,11 +141,9 @@ def test_chunked_rate_categories_20_states(gpu, orc, aa_mode, monkeypatch, shape
     1, 7 = 4 + 2 + 1, 8 = 4 + 4, 12 = 4 + 4 + 4), the per-site scaling verdict of the chunks so far travelling in the
     parent's scale buffer -- or in a scratch array when the op scales in place (parent scale buffer = the inner
     child's, in_place).  CLVs and scaler counts bit for bit, with scaling events, in both scaling modes, with waves that
-    walk several tiles; the edge lnL (chunk by chunk too, likelihood_aa_mfma.hip) to the default path's tolerance."""
-    if in_place and shape != "caterpillar":
-        pytest.skip("one scale buffer all the way down needs a ladder")
-    if rate_cats in (3, 12) and shape in ("random", "balanced") and rate_scalers:
-        pytest.skip("covered by the other counts")
+    walk several tiles; the edge lnL (chunk by chunk too, likelihood_aa_mfma.hip) to the default path's tolerance.
+    In place on a ladder: one scale buffer all the way down; on other trees every op with an inner child scales in
+    that child's buffer (the first inner one), so that each buffer is rewritten along one path of the tree."""
     import dataclasses
     monkeypatch.setenv("PLLHIP_AA_GRID_CAP", "3")
     case = make_case(20, shape, tips, sites, rate_cats=rate_cats, seed=tips, alpha=0.5,
@@ -158,9 +153,27 @@ def test_chunked_rate_categories_20_states(gpu, orc, aa_mode, monkeypatch, shape
     if in_place:
         plan = case["plan"]
         ops = plan.ops.copy()
-        for f in ("parent_scaler_index", "child1_scaler_index", "child2_scaler_index"):
-            ops[f] = np.where(ops[f] >= 0, 0, ops[f])
-        edge = tuple(0 if (i in (1, 3) and v >= 0) else v for i, v in enumerate(plan.root_edge))
+        if shape == "caterpillar":
+            for f in ("parent_scaler_index", "child1_scaler_index", "child2_scaler_index"):
+                ops[f] = np.where(ops[f] >= 0, 0, ops[f])
+            edge = tuple(0 if (i in (1, 3) and v >= 0) else v for i, v in enumerate(plan.root_edge))
+        else:
+            buf = {}   # CLV index -> the scale buffer its op wrote
+            for op in ops:
+                for c in ("child1", "child2"):
+                    node = int(op[c + "_clv_index"])
+                    if node in buf:
+                        op[c + "_scaler_index"] = buf[node]
+                inner = [int(op[c + "_scaler_index"]) for c in ("child1", "child2")
+                         if int(op[c + "_clv_index"]) in buf and int(op[c + "_scaler_index"]) >= 0]
+                if inner and int(op["parent_scaler_index"]) >= 0:
+                    op["parent_scaler_index"] = inner[0]
+                buf[int(op["parent_clv_index"])] = int(op["parent_scaler_index"])
+            e = list(plan.root_edge)
+            for i in (0, 2):
+                if e[i] in buf:
+                    e[i + 1] = buf[e[i]]
+            edge = tuple(e)
         case["plan"] = dataclasses.replace(plan, ops=ops, root_edge=edge)
     attrs = pattern_tip | rate_scalers
     p = build_partition(gpu, case, attrs)
@@ -245,9 +258,10 @@ def test_generic_state_kernels(gpu, orc, states, rate_cats, pattern_tip, rate_sc
     """Several tiles / rounds per op, all three op kinds, both scaling modes; bit-exact
     against the plain-C order of the reference."""
     attrs = pattern_tip | rate_scalers
-    if states > 32:
-        if pattern_tip:
-            pytest.skip("tip characters are 32-bit state masks")
+    if states > 32 and pattern_tip:
+        # tip characters are 32-bit state masks: characters of the first 32 states only
+        case = odd_state_case(states, tips=7, sites=75, seed=states, rate_cats=rate_cats, observed=32)
+    elif states > 32:
         case = many_state_case(states, tips=7, sites=75, seed=states, rate_cats=rate_cats)
     else:
         case = odd_state_case(states, tips=10, sites=333, seed=states + rate_cats, rate_cats=rate_cats)
@@ -309,8 +323,7 @@ def test_ragged_site_counts(gpu, orc, sites):
 
 @pytest.mark.parametrize("states", [4, 20])
 def test_invariant_sites_model(gpu, orc, aa_mode, states):
-    if states == 4 and aa_mode != "exact":
-        pytest.skip("mode only affects 20-state kernels")
+    # (4 states: the 20-state modes change nothing -- bit for bit in every one of them)
     exact = states == 4 or aa_mode == "exact"
     attrs = ATTRIB_PATTERN_TIP
     case = make_case(states, "random", 7, 120, seed=9, gap_frac=0.0, ambiguity=False)
