@@ -98,6 +98,9 @@ extern "C" {
 #define PLL_ERROR_INVAR_NONEFOUND 120
 #define PLL_ERROR_AB_INVALIDMETHOD 121
 #define PLL_ERROR_AB_NOSUPPORT 122
+#define PLL_ERROR_STEPWISE_STRUCT 127
+#define PLL_ERROR_STEPWISE_TIPS 128
+#define PLL_ERROR_STEPWISE_UNSUPPORTED 129
 #define PLL_ERROR_EINVAL 130
 /* new codes of this library, outside the reference's range */
 #define PLL_ERROR_HIP_NODEVICE 200
@@ -253,6 +256,50 @@ typedef struct pll_rnode_s
   struct pll_rnode_s * parent;
   void * data;
 } pll_rnode_t;
+
+/* pll.h:327-335 */
+typedef struct pll_utree_s
+{
+  unsigned int tip_count;
+  unsigned int inner_count;
+  unsigned int edge_count;
+  pll_unode_t ** nodes;
+} pll_utree_t;
+
+/* Fitch parsimony (pll.h:391-423); layouts frozen.  Here packedvector[i] is NULL until
+ * pll_amd_sync_parsimony_vector(pars, i) fills it: the vectors live on the device.  The weighted
+ * (Sankoff) fields stay zero. */
+typedef struct pll_parsimony_s
+{
+  unsigned int tips;
+  unsigned int inner_nodes;
+  unsigned int sites;
+  unsigned int states;
+  unsigned int attributes;
+  size_t alignment;
+
+  /* fast unweighted parsimony */
+  unsigned int ** packedvector;
+  unsigned int * node_cost;
+  unsigned int packedvector_count;
+  unsigned int const_cost;
+  int * informative;
+  unsigned int informative_count;
+
+  /* weighted parsimony (not provided) */
+  unsigned int score_buffers;
+  unsigned int ancestral_buffers;
+  double * score_matrix;
+  double ** sbuffer;
+  unsigned int ** anc_states;
+} pll_parsimony_t;
+
+typedef struct pll_pars_buildop_s
+{
+  unsigned int parent_score_index;
+  unsigned int child1_score_index;
+  unsigned int child2_score_index;
+} pll_pars_buildop_t;
 
 /* ---- global data (pll.h:470-522) ---- */
 
@@ -612,6 +659,37 @@ PLL_EXPORT int pll_core_update_pmatrix(double ** pmatrix, unsigned int states, u
                                        unsigned int count, unsigned int attrib);   /* pll.h:1659, core_pmatrix.c:24 */
 PLL_EXPORT void pll_amd_core_release(void);
 
+/* ---- Fitch parsimony and stepwise addition (fast_parsimony.c, stepwise.c; pll.h:1801-1881) ----
+ * pll_fastparsimony_init classifies and packs the partition's tips on its device; the object owns its own device
+ * memory and stream and outlives the partition.  Every call below is synchronous: update_vectors returns with
+ * node_cost current on the host, edge_score with the score.  A partition sharded over several devices is refused
+ * (PLL_ERROR_HIP_UNSUPPORTED).  INTEGRATION.md section "Parsimony". */
+PLL_EXPORT pll_parsimony_t * pll_fastparsimony_init(const pll_partition_t * partition);
+PLL_EXPORT void pll_fastparsimony_update_vectors(pll_parsimony_t * parsimony, const pll_pars_buildop_t * ops,
+                                                 unsigned int count);
+PLL_EXPORT void pll_fastparsimony_update_vector(pll_parsimony_t * parsimony, const pll_pars_buildop_t * op);
+PLL_EXPORT void pll_fastparsimony_update_vector_4x4(pll_parsimony_t * parsimony, const pll_pars_buildop_t * op);
+PLL_EXPORT unsigned int pll_fastparsimony_root_score(const pll_parsimony_t * parsimony, unsigned int root_index);
+PLL_EXPORT unsigned int pll_fastparsimony_edge_score(const pll_parsimony_t * parsimony,
+                                                     unsigned int node1_score_index,
+                                                     unsigned int node2_score_index);
+PLL_EXPORT unsigned int pll_fastparsimony_edge_score_4x4(const pll_parsimony_t * parsimony,
+                                                         unsigned int node1_score_index,
+                                                         unsigned int node2_score_index);
+PLL_EXPORT pll_utree_t * pll_fastparsimony_stepwise(pll_parsimony_t ** list, char * const * labels,
+                                                    unsigned int * score, unsigned int count, unsigned int seed);
+PLL_EXPORT void pll_parsimony_destroy(pll_parsimony_t * parsimony);
+
+/* tree helpers of the parsimony path (utree.c:217,740, rtree.c:458, parse_utree.y:71,102,395) */
+PLL_EXPORT void pll_utree_create_pars_buildops(pll_unode_t * const * trav_buffer, unsigned int trav_buffer_size,
+                                               pll_pars_buildop_t * ops, unsigned int * ops_count);
+PLL_EXPORT void pll_rtree_create_pars_buildops(pll_rnode_t * const * trav_buffer, unsigned int trav_buffer_size,
+                                               pll_pars_buildop_t * ops, unsigned int * ops_count);
+PLL_EXPORT pll_utree_t * pll_utree_wraptree(pll_unode_t * root, unsigned int tip_count);
+PLL_EXPORT void pll_utree_destroy(pll_utree_t * tree, void (*cb_destroy)(void *));
+PLL_EXPORT void pll_utree_graph_destroy(pll_unode_t * root, void (*cb_destroy)(void *));
+PLL_EXPORT char * pll_utree_export_newick(const pll_unode_t * root, char * (*cb_serialize)(const pll_unode_t *));
+
 /* ---- additions of this library (no reference counterpart) ---- */
 
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
@@ -656,6 +734,10 @@ PLL_EXPORT int pll_amd_sync_clv(pll_partition_t * partition, unsigned int clv_in
 PLL_EXPORT int pll_amd_sync_scaler(pll_partition_t * partition, unsigned int scaler_index);
 PLL_EXPORT int pll_amd_sync_pmatrix(pll_partition_t * partition, unsigned int matrix_index);
 PLL_EXPORT int pll_amd_sync_sumtable(pll_partition_t * partition, double * sumtable);
+/* Host copy of node `index`'s parsimony vector in parsimony->packedvector[index] (allocated on first use, freed by
+ * pll_parsimony_destroy), in the reference's layout: `states` planes of packedvector_count 32-bit words, the partial
+ * last word and the padding words filled with ones. */
+PLL_EXPORT int pll_amd_sync_parsimony_vector(pll_parsimony_t * parsimony, unsigned int index);
 /* Outside mirror mode pll_update_sumtable does not fill the caller's buffer -- but it does MARK it: the entries of
  * the first site (states * rate_cats doubles) are set to this signalling NaN, so that a client which reads the
  * buffer without pll_amd_sync_sumtable finds NaNs that propagate (and trap under feenableexcept(FE_INVALID)), not

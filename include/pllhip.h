@@ -364,6 +364,42 @@ PLLHIP_EXPORT int pllhip_aa_list_kinds(pllhip_ctx_t * ctx, unsigned int * out8);
  * torch tensor wrapped around it); NULL if out of range */
 PLLHIP_EXPORT void * pllhip_dev_clv(pllhip_ctx_t * ctx, unsigned int clv_index);
 
+/* ---- Fitch parsimony (parsimony.hip; host side host/parsimony.c, host/stepwise.c) ----
+ * An object of its own: packed bit-vectors of `nodes` nodes (the tips first) on the context's device, with
+ * its own memory and stream, so that it outlives the context it was made from.  Not for sharded contexts. */
+typedef struct pllhip_pars pllhip_pars_t;
+/* replaces pll_set_informative + fill_parsimony_vectors (fast_parsimony.c:362-396, 192-360): classifies the
+ * first `sites` patterns from the context's tip characters (h_tipmap: 256 entries, pattern tips) or tip CLVs,
+ * scans the informative weights and packs the tips.  Out: *bits = informative bits, *const_cost,
+ * h_informative[sites] (0/1), *informative_count.  Returns -2 if the device lacks the memory. */
+PLLHIP_EXPORT int pllhip_pars_create(pllhip_ctx_t * ctx, unsigned int nodes, unsigned int sites,
+                                     const unsigned int * h_tipmap, const unsigned int * h_pattern_weights,
+                                     unsigned int * bits, unsigned int * const_cost, int * h_informative,
+                                     unsigned int * informative_count, pllhip_pars_t ** out);
+PLLHIP_EXPORT void pllhip_pars_destroy(pllhip_pars_t * pars);
+/* words per state plane on the device (a multiple of 8) */
+PLLHIP_EXPORT unsigned int pllhip_pars_words(const pllhip_pars_t * pars);
+/* the op loop of pll_fastparsimony_update_vectors (fast_parsimony.c:643-710) in one launch: h_ops = count
+ * triples (parent, child1, child2); h_counts[i] = sites of op i whose children do not intersect */
+PLLHIP_EXPORT int pllhip_pars_update(pllhip_pars_t * pars, const unsigned int * h_ops, unsigned int count,
+                                     unsigned int * h_counts);
+/* sites whose vectors at a and b do not intersect (fast_parsimony.c:604-641) */
+PLLHIP_EXPORT int pllhip_pars_edge_count(pllhip_pars_t * pars, unsigned int a, unsigned int b, unsigned int * count);
+/* the first `words` words of every state plane of node `index` into h (states * words) */
+PLLHIP_EXPORT int pllhip_pars_get_vector(pllhip_pars_t * pars, unsigned int index, unsigned int * h,
+                                         unsigned int words);
+/* Stepwise addition (host/stepwise.c).  Slots: 0..tips-1 are the tips' vectors, tips.. the `inner_slots` directed
+ * vectors of step_begin's arena.  step_enqueue: recompute the ops (triples of slots, in list order), then count for
+ * every edge i (h_pairs[2i], h_pairs[2i+1]) the sites where fitch(U, V) misses the vector of tip_slot; then either the
+ * counts are read back (want_counts) or their argmin, lowest index first.  step_wait completes it. */
+PLLHIP_EXPORT int pllhip_pars_step_begin(pllhip_pars_t * pars, unsigned int inner_slots, unsigned int max_edges);
+PLLHIP_EXPORT int pllhip_pars_step_enqueue(pllhip_pars_t * pars, const unsigned int * h_ops, unsigned int nops,
+                                           const unsigned int * h_pairs, unsigned int npairs, unsigned int tip_slot,
+                                           int want_counts);
+PLLHIP_EXPORT int pllhip_pars_step_wait(pllhip_pars_t * pars, unsigned int * h_counts, unsigned int npairs,
+                                        unsigned int * best_index, unsigned int * best_count);
+PLLHIP_EXPORT int pllhip_pars_step_end(pllhip_pars_t * pars);
+
 #ifdef __cplusplus
 }
 #endif

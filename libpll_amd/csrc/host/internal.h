@@ -69,6 +69,18 @@ static inline pll_amd_partition_t * pll_amd_priv(const pll_partition_t * p)
   return (pll_amd_partition_t *)p;
 }
 
+/* private view of a parsimony object (host/parsimony.c): the public struct first, as for partitions */
+#define PLL_AMD_PARS_MAGIC 0x504c4c5041525331ull /* "PLLPARS1" */
+typedef struct pll_amd_parsimony
+{
+  pll_parsimony_t pub;          /* MUST be first */
+  unsigned long long magic;
+  pllhip_pars_t * dev;
+} pll_amd_parsimony_t;
+
+/* the parsimony object behind `p`, or NULL (and pll_errno set) if it was not made by this library */
+pll_amd_parsimony_t * pll_amd_pars_priv(const pll_parsimony_t * p);
+
 /* sets pll_errno/pll_errmsg from the shim's last error; returns PLL_FAILURE */
 int pll_amd_fail_hip(int rc, const char * what);
 void pll_amd_set_error(int code, const char * fmt, ...);

@@ -77,7 +77,54 @@ OPS_DTYPE = np.dtype([
     ("child2_clv_index", "<u4"), ("child2_matrix_index", "<u4"),
     ("child2_scaler_index", "<i4")])
 
+class UNode(C.Structure):
+    """pll_unode_t, pll.h:312-324."""
+
+
+UNode._fields_ = [
+    ("label", C.c_void_p), ("length", C.c_double), ("node_index", C.c_uint),
+    ("clv_index", C.c_uint), ("scaler_index", C.c_int), ("pmatrix_index", C.c_uint),
+    ("next", C.POINTER(UNode)), ("back", C.POINTER(UNode)), ("data", C.c_void_p)]
+
+
+class RNode(C.Structure):
+    """pll_rnode_t, pll.h:336-349."""
+
+
+RNode._fields_ = [
+    ("label", C.c_void_p), ("length", C.c_double), ("node_index", C.c_uint),
+    ("clv_index", C.c_uint), ("scaler_index", C.c_int), ("pmatrix_index", C.c_uint),
+    ("left", C.POINTER(RNode)), ("right", C.POINTER(RNode)), ("parent", C.POINTER(RNode)),
+    ("data", C.c_void_p)]
+
+
+class UTree(C.Structure):
+    """pll_utree_t, pll.h:327-335."""
+    _fields_ = [("tip_count", C.c_uint), ("inner_count", C.c_uint), ("edge_count", C.c_uint),
+                ("nodes", C.POINTER(C.POINTER(UNode)))]
+
+
+class ParsimonyStruct(C.Structure):
+    """pll_parsimony_t, pll.h:391-415."""
+    _fields_ = [
+        ("tips", C.c_uint), ("inner_nodes", C.c_uint), ("sites", C.c_uint), ("states", C.c_uint),
+        ("attributes", C.c_uint), ("alignment", C.c_size_t),
+        ("packedvector", C.POINTER(C.POINTER(C.c_uint))), ("node_cost", C.POINTER(C.c_uint)),
+        ("packedvector_count", C.c_uint), ("const_cost", C.c_uint),
+        ("informative", C.POINTER(C.c_int)), ("informative_count", C.c_uint),
+        ("score_buffers", C.c_uint), ("ancestral_buffers", C.c_uint),
+        ("score_matrix", C.POINTER(C.c_double)), ("sbuffer", C.POINTER(C.POINTER(C.c_double))),
+        ("anc_states", C.POINTER(C.POINTER(C.c_uint)))]
+
+
+ERROR_STEPWISE_STRUCT = 127         # pll.h:164-166
+ERROR_STEPWISE_TIPS = 128
+ERROR_STEPWISE_UNSUPPORTED = 129
+ERROR_HIP_UNSUPPORTED = 202
+
 _PP = C.POINTER(PartitionStruct)
+_PARS = C.POINTER(ParsimonyStruct)
+_UN = C.POINTER(UNode)
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
 
@@ -140,6 +187,43 @@ class PllLibrary:
         lib.pll_aligned_alloc.argtypes = [C.c_size_t, C.c_size_t]
         lib.pll_aligned_free.restype = None
         lib.pll_aligned_free.argtypes = [C.c_void_p]
+        if hasattr(lib, "pll_fastparsimony_init"):
+            lib.pll_fastparsimony_init.restype = _PARS
+            lib.pll_fastparsimony_init.argtypes = [_PP]
+            for name in ("pll_fastparsimony_update_vectors",):
+                getattr(lib, name).restype = None
+                getattr(lib, name).argtypes = [_PARS, C.c_void_p, C.c_uint]
+            for name in ("pll_fastparsimony_update_vector", "pll_fastparsimony_update_vector_4x4"):
+                getattr(lib, name).restype = None
+                getattr(lib, name).argtypes = [_PARS, C.c_void_p]
+            lib.pll_fastparsimony_root_score.restype = C.c_uint
+            lib.pll_fastparsimony_root_score.argtypes = [_PARS, C.c_uint]
+            for name in ("pll_fastparsimony_edge_score", "pll_fastparsimony_edge_score_4x4"):
+                getattr(lib, name).restype = C.c_uint
+                getattr(lib, name).argtypes = [_PARS, C.c_uint, C.c_uint]
+            lib.pll_fastparsimony_stepwise.restype = C.POINTER(UTree)
+            lib.pll_fastparsimony_stepwise.argtypes = [C.POINTER(_PARS), C.POINTER(C.c_char_p), _up, C.c_uint,
+                                                       C.c_uint]
+            lib.pll_parsimony_destroy.restype = None
+            lib.pll_parsimony_destroy.argtypes = [_PARS]
+        if hasattr(lib, "pll_utree_export_newick"):
+            lib.pll_utree_export_newick.restype = C.c_void_p
+            lib.pll_utree_export_newick.argtypes = [_UN, C.c_void_p]
+        if hasattr(lib, "pll_utree_create_pars_buildops"):
+            lib.pll_utree_create_pars_buildops.restype = None
+            lib.pll_utree_create_pars_buildops.argtypes = [C.POINTER(_UN), C.c_uint, C.c_void_p, _up]
+        if hasattr(lib, "pll_rtree_create_pars_buildops"):
+            lib.pll_rtree_create_pars_buildops.restype = None
+            lib.pll_rtree_create_pars_buildops.argtypes = [C.POINTER(C.POINTER(RNode)), C.c_uint, C.c_void_p, _up]
+        if hasattr(lib, "pll_utree_wraptree"):
+            lib.pll_utree_wraptree.restype = C.POINTER(UTree)
+            lib.pll_utree_wraptree.argtypes = [_UN, C.c_uint]
+            lib.pll_utree_destroy.restype = None
+            lib.pll_utree_destroy.argtypes = [C.POINTER(UTree), C.c_void_p]
+            lib.pll_utree_graph_destroy.restype = None
+            lib.pll_utree_graph_destroy.argtypes = [_UN, C.c_void_p]
+        if hasattr(lib, "pll_amd_sync_parsimony_vector"):
+            lib.pll_amd_sync_parsimony_vector.argtypes = [_PARS, C.c_uint]
         if self.is_amd:
             lib.pll_amd_sync_clv.argtypes = [_PP, C.c_uint]
             lib.pll_amd_sync_scaler.argtypes = [_PP, C.c_uint]
@@ -200,6 +284,32 @@ class PllLibrary:
     def device_count(self):
         return self.lib.pll_amd_device_count() if self.is_amd else 0
 
+    # -- parsimony (pll.h:1801-1881) ------------------------------------------------
+    def fastparsimony_init(self, partition):
+        p = self.lib.pll_fastparsimony_init(partition.ptr)
+        if not p:
+            raise PllError("pll_fastparsimony_init failed (pll_errno=%d): %s" % (self.errno(), self.errmsg()))
+        return Parsimony(self, p)
+
+    def stepwise(self, pars_list, labels, seed):
+        """pll_fastparsimony_stepwise: (pointer to the pll_utree_t, score); raises on failure"""
+        arr = (_PARS * len(pars_list))(*[q.ptr for q in pars_list])
+        lab = (C.c_char_p * len(labels))(*[x.encode() if isinstance(x, str) else x for x in labels])
+        score = C.c_uint(0)
+        t = self.lib.pll_fastparsimony_stepwise(arr, lab, C.byref(score), len(pars_list), seed)
+        if not t:
+            raise PllError("pll_fastparsimony_stepwise failed (pll_errno=%d): %s" % (self.errno(), self.errmsg()))
+        return t, score.value
+
+    def export_newick(self, node):
+        """pll_utree_export_newick(node, NULL) as a str (the C string is freed)"""
+        r = self.lib.pll_utree_export_newick(node, None)
+        if not r:
+            raise PllError("pll_utree_export_newick failed: %s" % self.errmsg())
+        out = C.string_at(r).decode()
+        _libc.free(C.c_void_p(r))
+        return out
+
     def partition_create(self, tips, clv_buffers, states, sites, rate_matrices, prob_matrices,
                          rate_cats, scale_buffers, attributes):
         p = self.lib.pll_partition_create(tips, clv_buffers, states, sites, rate_matrices,
@@ -208,6 +318,64 @@ class PllLibrary:
             raise PllError("pll_partition_create failed (pll_errno=%d): %s"
                            % (self.errno(), self.errmsg()))
         return Partition(self, p)
+
+
+_libc = C.CDLL(None)
+_libc.free.argtypes = [C.c_void_p]
+_libc.free.restype = None
+
+
+class Parsimony:
+    """A pll_parsimony_t* (pll_fastparsimony_init) plus the calls that take it."""
+
+    def __init__(self, owner, ptr):
+        self.o = owner
+        self.lib = owner.lib
+        self.ptr = ptr
+        self.s = ptr.contents
+
+    def destroy(self):
+        if self.ptr:
+            self.lib.pll_parsimony_destroy(self.ptr)
+            self.ptr = None
+
+    @property
+    def nodes(self):
+        return self.s.tips + self.s.inner_nodes
+
+    def update_vectors(self, ops):
+        """ops: (n, 3) integers (parent, child1, child2)"""
+        a = np.ascontiguousarray(ops, dtype=np.uint32).reshape(-1, 3)
+        self.lib.pll_fastparsimony_update_vectors(self.ptr, a.ctypes.data, len(a))
+
+    def update_vector(self, op, four=False):
+        a = np.ascontiguousarray(op, dtype=np.uint32).reshape(3)
+        f = self.lib.pll_fastparsimony_update_vector_4x4 if four else self.lib.pll_fastparsimony_update_vector
+        f(self.ptr, a.ctypes.data)
+
+    def root_score(self, root):
+        return int(self.lib.pll_fastparsimony_root_score(self.ptr, root))
+
+    def edge_score(self, a, b, four=False):
+        f = self.lib.pll_fastparsimony_edge_score_4x4 if four else self.lib.pll_fastparsimony_edge_score
+        return int(f(self.ptr, a, b))
+
+    def node_cost(self):
+        return np.ctypeslib.as_array(self.s.node_cost, shape=(self.nodes,)).copy()
+
+    def informative(self):
+        return np.ctypeslib.as_array(self.s.informative, shape=(self.s.sites,)).copy()
+
+    def vector(self, index):
+        """node `index`'s packed vector as (states, packedvector_count) uint32 -- synced first on libpll_amd"""
+        n = self.s.packedvector_count
+        if hasattr(self.lib, "pll_amd_sync_parsimony_vector"):
+            if not self.lib.pll_amd_sync_parsimony_vector(self.ptr, index):
+                raise PllError("pll_amd_sync_parsimony_vector failed: %s" % self.o.errmsg())
+        if n == 0:
+            return np.zeros((self.s.states, 0), dtype=np.uint32)
+        v = self.s.packedvector[index]
+        return np.ctypeslib.as_array(v, shape=(self.s.states * n,)).copy().reshape(self.s.states, n)
 
 
 class Partition:
