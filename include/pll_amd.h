@@ -266,9 +266,13 @@ typedef struct pll_utree_s
   pll_unode_t ** nodes;
 } pll_utree_t;
 
-/* Fitch parsimony (pll.h:391-423); layouts frozen.  Here packedvector[i] is NULL until
- * pll_amd_sync_parsimony_vector(pars, i) fills it: the vectors live on the device.  The weighted
- * (Sankoff) fields stay zero. */
+/* Parsimony (pll.h:391-431); layouts frozen.  Fitch objects (pll_fastparsimony_init): packedvector[i] is NULL
+ * until pll_amd_sync_parsimony_vector(pars, i) fills it -- the vectors live on the device -- and the weighted fields
+ * stay zero.  Weighted objects (pll_parsimony_create): score_matrix is a host copy; sbuffer[0 .. tips +
+ * score_buffers - 1] and anc_states[tips .. tips + ancestral_buffers - 1] are the reference's layouts ([site][state]
+ * doubles, [site] characters), kept current by every call while the object's buffers stay below
+ * PLL_AMD_AUTO_MIRROR_MB (default 64 MB), NULL above it until pll_amd_sync_parsimony_scores /
+ * pll_amd_sync_parsimony_ancestral fills them; the Fitch fields stay zero. */
 typedef struct pll_parsimony_s
 {
   unsigned int tips;
@@ -286,7 +290,7 @@ typedef struct pll_parsimony_s
   int * informative;
   unsigned int informative_count;
 
-  /* weighted parsimony (not provided) */
+  /* weighted parsimony */
   unsigned int score_buffers;
   unsigned int ancestral_buffers;
   double * score_matrix;
@@ -300,6 +304,14 @@ typedef struct pll_pars_buildop_s
   unsigned int child1_score_index;
   unsigned int child2_score_index;
 } pll_pars_buildop_t;
+
+typedef struct pll_pars_recop_s
+{
+  unsigned int node_score_index;
+  unsigned int node_ancestral_index;
+  unsigned int parent_score_index;
+  unsigned int parent_ancestral_index;
+} pll_pars_recop_t;
 
 /* ---- global data (pll.h:470-522) ---- */
 
@@ -680,6 +692,28 @@ PLL_EXPORT pll_utree_t * pll_fastparsimony_stepwise(pll_parsimony_t ** list, cha
                                                     unsigned int * score, unsigned int count, unsigned int seed);
 PLL_EXPORT void pll_parsimony_destroy(pll_parsimony_t * parsimony);
 
+/* ---- weighted (Sankoff) parsimony (parsimony.c; pll.h:1801-1830) ----
+ * pll_parsimony_create puts the object on the device the calling thread's next pll_partition_create would use
+ * (pll_amd_get_device); it owns its memory and a stream of its own.  No device: NULL, PLL_ERROR_HIP_NODEVICE.  2 to 64
+ * states (a character map expresses at most 32).  Every call is synchronous.  Indices are checked before anything
+ * reaches the device (PLL_ERROR_PARAM_INVALID, nothing launched): a sequence goes to a tip; a build's parents are
+ * score buffers past the tips and not their own children; a reconstruct's node and parent indices are at or above
+ * `tips`; a map must give every state a single-bit character; count 0 is refused.  On such an error build and score
+ * return NaN.  pll_parsimony_destroy frees both kinds of object; a Fitch call given a weighted object, or the
+ * reverse, fails with PLL_ERROR_PARAM_INVALID.  INTEGRATION.md section "Parsimony". */
+PLL_EXPORT pll_parsimony_t * pll_parsimony_create(unsigned int tips, unsigned int states, unsigned int sites,
+                                                  const double * score_matrix, unsigned int score_buffers,
+                                                  unsigned int ancestral_buffers);
+PLL_EXPORT int pll_set_parsimony_sequence(pll_parsimony_t * pars, unsigned int tip_index, const unsigned int * map,
+                                          const char * sequence);
+PLL_EXPORT double pll_parsimony_build(pll_parsimony_t * pars, const pll_pars_buildop_t * operations,
+                                      unsigned int count);
+PLL_EXPORT double pll_parsimony_score(pll_parsimony_t * pars, unsigned int score_buffer_index);
+PLL_EXPORT void pll_parsimony_reconstruct(pll_parsimony_t * pars, const unsigned int * map,
+                                          const pll_pars_recop_t * operations, unsigned int count);
+PLL_EXPORT void pll_rtree_create_pars_recops(pll_rnode_t * const * trav_buffer, unsigned int trav_buffer_size,
+                                             pll_pars_recop_t * ops, unsigned int * ops_count);
+
 /* tree helpers of the parsimony path (utree.c:217,740, rtree.c:458, parse_utree.y:71,102,395) */
 PLL_EXPORT void pll_utree_create_pars_buildops(pll_unode_t * const * trav_buffer, unsigned int trav_buffer_size,
                                                pll_pars_buildop_t * ops, unsigned int * ops_count);
@@ -738,6 +772,14 @@ PLL_EXPORT int pll_amd_sync_sumtable(pll_partition_t * partition, double * sumta
  * pll_parsimony_destroy), in the reference's layout: `states` planes of packedvector_count 32-bit words, the partial
  * last word and the padding words filled with ones. */
 PLL_EXPORT int pll_amd_sync_parsimony_vector(pll_parsimony_t * parsimony, unsigned int index);
+/* Weighted objects: host copy of score buffer `index` in parsimony->sbuffer[index] / of ancestral buffer `index`
+ * (tips <= index < tips + ancestral_buffers) in parsimony->anc_states[index], in the reference's layout (allocated
+ * with malloc on first use, freed by pll_parsimony_destroy).  pll_amd_push_parsimony_scores is the other direction:
+ * a client that wrote sbuffer[index] itself (a tip with values other than 0 / inf, or more than 32 states) hands it
+ * to the device; the next build uses it. */
+PLL_EXPORT int pll_amd_sync_parsimony_scores(pll_parsimony_t * parsimony, unsigned int index);
+PLL_EXPORT int pll_amd_sync_parsimony_ancestral(pll_parsimony_t * parsimony, unsigned int index);
+PLL_EXPORT int pll_amd_push_parsimony_scores(pll_parsimony_t * parsimony, unsigned int index);
 /* Outside mirror mode pll_update_sumtable does not fill the caller's buffer -- but it does MARK it: the entries of
  * the first site (states * rate_cats doubles) are set to this signalling NaN, so that a client which reads the
  * buffer without pll_amd_sync_sumtable finds NaNs that propagate (and trap under feenableexcept(FE_INVALID)), not

@@ -400,6 +400,36 @@ PLLHIP_EXPORT int pllhip_pars_step_wait(pllhip_pars_t * pars, unsigned int * h_c
                                         unsigned int * best_index, unsigned int * best_count);
 PLLHIP_EXPORT int pllhip_pars_step_end(pllhip_pars_t * pars);
 
+/* ---- weighted (Sankoff) parsimony (sankoff.hip; host side host/sankoff.c) ----
+ * An object of its own on `device`: tips + score_buffers score buffers (indices below `tips` are the tips) and
+ * ancestral_buffers ancestral buffers (indices tips .. tips + ancestral_buffers - 1), with its own memory and stream.
+ * Every call is synchronous.  The host layer validates indices; these calls check them again and return -1.
+ * Buffers on the host side of these calls are in the reference's layout: [site][state] doubles, [site] characters. */
+typedef struct pllhip_sank pllhip_sank_t;
+/* inf: what pll_set_parsimony_sequence gives a state a character excludes (the largest matrix entry plus 1).
+ * Returns -2 if the device lacks the memory, -1 for a bad shape (states outside 2..64, no sites). */
+PLLHIP_EXPORT int pllhip_sank_create(int device, unsigned int tips, unsigned int states, unsigned int sites,
+                                     const double * h_matrix, double inf, unsigned int score_buffers,
+                                     unsigned int ancestral_buffers, pllhip_sank_t ** out);
+PLLHIP_EXPORT void pllhip_sank_destroy(pllhip_sank_t * sank);
+/* tip `tip` from per-site state masks (bit k: state k allowed; bits at or above states are ignored) */
+PLLHIP_EXPORT int pllhip_sank_set_tip_codes(pllhip_sank_t * sank, unsigned int tip, const unsigned int * h_codes);
+/* score buffer `index` (a tip or not) from / to sites * states doubles */
+PLLHIP_EXPORT int pllhip_sank_push(pllhip_sank_t * sank, unsigned int index, const double * h);
+PLLHIP_EXPORT int pllhip_sank_get(pllhip_sank_t * sank, unsigned int index, double * h);
+/* the op loop of pll_parsimony_build (parsimony.c) in one launch: h_ops = count triples (parent, child1, child2),
+ * parents not tips and not their own children; *score = pll_parsimony_score of the last parent */
+PLLHIP_EXPORT int pllhip_sank_build(pllhip_sank_t * sank, const unsigned int * h_ops, unsigned int count,
+                                    double * score);
+PLLHIP_EXPORT int pllhip_sank_score(pllhip_sank_t * sank, unsigned int index, double * score);
+/* pll_parsimony_reconstruct in one launch: h_recops = count quadruples (node score, node ancestral, parent score,
+ * parent ancestral), every index at or above tips (the first op's parent fields are not read); map and revmap are
+ * 256 entries each */
+PLLHIP_EXPORT int pllhip_sank_reconstruct(pllhip_sank_t * sank, const unsigned int * h_map,
+                                          const unsigned int * h_revmap, const unsigned int * h_recops,
+                                          unsigned int count);
+PLLHIP_EXPORT int pllhip_sank_get_ancestral(pllhip_sank_t * sank, unsigned int index, unsigned int * h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,15 +71,23 @@ static inline pll_amd_partition_t * pll_amd_priv(const pll_partition_t * p)
 
 /* private view of a parsimony object (host/parsimony.c): the public struct first, as for partitions */
 #define PLL_AMD_PARS_MAGIC 0x504c4c5041525331ull /* "PLLPARS1" */
+#define PLL_AMD_PARS_FITCH 0        /* pll_fastparsimony_init */
+#define PLL_AMD_PARS_WEIGHTED 1     /* pll_parsimony_create (host/sankoff.c) */
 typedef struct pll_amd_parsimony
 {
   pll_parsimony_t pub;          /* MUST be first */
   unsigned long long magic;
-  pllhip_pars_t * dev;
+  int kind;                     /* PLL_AMD_PARS_FITCH or PLL_AMD_PARS_WEIGHTED */
+  pllhip_pars_t * dev;          /* Fitch */
+  pllhip_sank_t * sank;         /* weighted */
+  int auto_mirror;              /* weighted: sbuffer / anc_states kept current by every call (PLL_AMD_AUTO_MIRROR_MB) */
 } pll_amd_parsimony_t;
 
-/* the parsimony object behind `p`, or NULL (and pll_errno set) if it was not made by this library */
-pll_amd_parsimony_t * pll_amd_pars_priv(const pll_parsimony_t * p);
+/* the parsimony object behind `p` if it was made by this library and is of `kind`; otherwise NULL, and pll_errno
+ * set to PLL_ERROR_PARAM_INVALID */
+pll_amd_parsimony_t * pll_amd_pars_priv(const pll_parsimony_t * p, int kind);
+/* frees a weighted object (host/sankoff.c; pll_parsimony_destroy frees both kinds) */
+void pll_amd_sankoff_free(pll_amd_parsimony_t * q);
 
 /* sets pll_errno/pll_errmsg from the shim's last error; returns PLL_FAILURE */
 int pll_amd_fail_hip(int rc, const char * what);

@@ -11,12 +11,20 @@
 
 #include "internal.h"
 
-pll_amd_parsimony_t * pll_amd_pars_priv(const pll_parsimony_t * p)
+pll_amd_parsimony_t * pll_amd_pars_priv(const pll_parsimony_t * p, int kind)
 {
   pll_amd_parsimony_t * q = (pll_amd_parsimony_t *)p;
-  if (!q || q->magic != PLL_AMD_PARS_MAGIC || !q->dev)
+  if (!q || q->magic != PLL_AMD_PARS_MAGIC || (q->kind == PLL_AMD_PARS_FITCH ? !q->dev : !q->sank))
   {
     pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "Not a parsimony object of this library.");
+    return NULL;
+  }
+  if (q->kind != kind)
+  {
+    pll_amd_set_error(PLL_ERROR_PARAM_INVALID,
+                      kind == PLL_AMD_PARS_FITCH
+                          ? "A weighted parsimony object (pll_parsimony_create) given to a fast-parsimony call."
+                          : "A fast-parsimony object (pll_fastparsimony_init) given to a weighted parsimony call.");
     return NULL;
   }
   return q;
@@ -72,6 +80,7 @@ pll_parsimony_t * pll_fastparsimony_init(const pll_partition_t * partition)
     return NULL;
   }
   q->magic = PLL_AMD_PARS_MAGIC;
+  q->kind = PLL_AMD_PARS_FITCH;
   p = &q->pub;
   p->tips = partition->tips;
   p->inner_nodes = partition->tips - 1;
@@ -115,17 +124,23 @@ pll_parsimony_t * pll_fastparsimony_init(const pll_partition_t * partition)
   return p;
 }
 
+/* both kinds of object: pll_fastparsimony_init's and pll_parsimony_create's */
 void pll_parsimony_destroy(pll_parsimony_t * parsimony)
 {
-  pll_amd_parsimony_t * q;
+  pll_amd_parsimony_t * q = (pll_amd_parsimony_t *)parsimony;
   if (!parsimony) return;
-  if (!(q = pll_amd_pars_priv(parsimony))) return;
+  if (q->magic == PLL_AMD_PARS_MAGIC && q->kind == PLL_AMD_PARS_WEIGHTED)
+  {
+    pll_amd_sankoff_free(q);
+    return;
+  }
+  if (!(q = pll_amd_pars_priv(parsimony, PLL_AMD_PARS_FITCH))) return;
   pars_free(q);
 }
 
 void pll_fastparsimony_update_vectors(pll_parsimony_t * parsimony, const pll_pars_buildop_t * ops, unsigned int count)
 {
-  pll_amd_parsimony_t * q = pll_amd_pars_priv(parsimony);
+  pll_amd_parsimony_t * q = pll_amd_pars_priv(parsimony, PLL_AMD_PARS_FITCH);
   unsigned int * counts, i;
   int rc;
   if (!q || !count) return;
@@ -162,13 +177,14 @@ void pll_fastparsimony_update_vector_4x4(pll_parsimony_t * parsimony, const pll_
 
 unsigned int pll_fastparsimony_root_score(const pll_parsimony_t * parsimony, unsigned int root_index)
 {
+  if (!pll_amd_pars_priv(parsimony, PLL_AMD_PARS_FITCH)) return 0;
   return parsimony->node_cost[root_index] + parsimony->const_cost;
 }
 
 unsigned int pll_fastparsimony_edge_score(const pll_parsimony_t * parsimony, unsigned int node1_score_index,
                                           unsigned int node2_score_index)
 {
-  pll_amd_parsimony_t * q = pll_amd_pars_priv(parsimony);
+  pll_amd_parsimony_t * q = pll_amd_pars_priv(parsimony, PLL_AMD_PARS_FITCH);
   unsigned int score = 0;
   int rc;
   if (!q) return 0;
@@ -189,7 +205,7 @@ unsigned int pll_fastparsimony_edge_score_4x4(const pll_parsimony_t * parsimony,
 
 int pll_amd_sync_parsimony_vector(pll_parsimony_t * parsimony, unsigned int index)
 {
-  pll_amd_parsimony_t * q = pll_amd_pars_priv(parsimony);
+  pll_amd_parsimony_t * q = pll_amd_pars_priv(parsimony, PLL_AMD_PARS_FITCH);
   const unsigned int n = parsimony ? parsimony->packedvector_count : 0;
   int rc;
   if (!q) return PLL_FAILURE;

@@ -164,7 +164,7 @@ pll_utree_t * pll_fastparsimony_stepwise(pll_parsimony_t ** list, char * const *
   }
   for (i = 0; i < count; ++i)
   {
-    if (!(dev[i] = pll_amd_pars_priv(list[i])))
+    if (!(dev[i] = pll_amd_pars_priv(list[i], PLL_AMD_PARS_FITCH)))
     {
       free(dev);
       return NULL;

@@ -211,3 +211,22 @@ void pll_rtree_create_operations(pll_rnode_t * const * trav, unsigned int trav_s
     }
   }
 }
+
+/* rtree.c:483-517: one recop per inner node of a preorder traversal; the root's parent fields are 0 (never read) */
+void pll_rtree_create_pars_recops(pll_rnode_t * const * trav_buffer, unsigned int trav_buffer_size,
+                                  pll_pars_recop_t * ops, unsigned int * ops_count)
+{
+  unsigned int i;
+  *ops_count = 0;
+  for (i = 0; i < trav_buffer_size; ++i)
+  {
+    const pll_rnode_t * n = trav_buffer[i];
+    pll_pars_recop_t * op;
+    if (!n->left) continue;
+    op = ops + (*ops_count)++;
+    op->node_score_index = n->clv_index;
+    op->node_ancestral_index = n->clv_index;
+    op->parent_score_index = n->parent ? n->parent->clv_index : 0;
+    op->parent_ancestral_index = n->parent ? n->parent->clv_index : 0;
+  }
+}

@@ -117,6 +117,12 @@ class ParsimonyStruct(C.Structure):
         ("anc_states", C.POINTER(C.POINTER(C.c_uint)))]
 
 
+class ParsRecop(C.Structure):
+    """pll_pars_recop_t, pll.h:425-431."""
+    _fields_ = [("node_score_index", C.c_uint), ("node_ancestral_index", C.c_uint),
+                ("parent_score_index", C.c_uint), ("parent_ancestral_index", C.c_uint)]
+
+
 ERROR_STEPWISE_STRUCT = 127         # pll.h:164-166
 ERROR_STEPWISE_TIPS = 128
 ERROR_STEPWISE_UNSUPPORTED = 129
@@ -224,6 +230,25 @@ class PllLibrary:
             lib.pll_utree_graph_destroy.argtypes = [_UN, C.c_void_p]
         if hasattr(lib, "pll_amd_sync_parsimony_vector"):
             lib.pll_amd_sync_parsimony_vector.argtypes = [_PARS, C.c_uint]
+        if hasattr(lib, "pll_parsimony_create"):
+            lib.pll_parsimony_create.restype = _PARS
+            lib.pll_parsimony_create.argtypes = [C.c_uint, C.c_uint, C.c_uint, _dp, C.c_uint, C.c_uint]
+            lib.pll_set_parsimony_sequence.argtypes = [_PARS, C.c_uint, _up, C.c_char_p]
+            lib.pll_parsimony_build.restype = C.c_double
+            lib.pll_parsimony_build.argtypes = [_PARS, C.c_void_p, C.c_uint]
+            lib.pll_parsimony_score.restype = C.c_double
+            lib.pll_parsimony_score.argtypes = [_PARS, C.c_uint]
+            lib.pll_parsimony_reconstruct.restype = None
+            lib.pll_parsimony_reconstruct.argtypes = [_PARS, _up, C.c_void_p, C.c_uint]
+            lib.pll_parsimony_destroy.restype = None
+            lib.pll_parsimony_destroy.argtypes = [_PARS]
+        if hasattr(lib, "pll_rtree_create_pars_recops"):
+            lib.pll_rtree_create_pars_recops.restype = None
+            lib.pll_rtree_create_pars_recops.argtypes = [C.POINTER(C.POINTER(RNode)), C.c_uint, C.c_void_p, _up]
+        for name in ("pll_amd_sync_parsimony_scores", "pll_amd_sync_parsimony_ancestral",
+                     "pll_amd_push_parsimony_scores"):
+            if hasattr(lib, name):
+                getattr(lib, name).argtypes = [_PARS, C.c_uint]
         if self.is_amd:
             lib.pll_amd_sync_clv.argtypes = [_PP, C.c_uint]
             lib.pll_amd_sync_scaler.argtypes = [_PP, C.c_uint]
@@ -290,6 +315,14 @@ class PllLibrary:
         if not p:
             raise PllError("pll_fastparsimony_init failed (pll_errno=%d): %s" % (self.errno(), self.errmsg()))
         return Parsimony(self, p)
+
+    def parsimony_create(self, tips, states, sites, matrix, score_buffers, ancestral_buffers):
+        """pll_parsimony_create: a WeightedParsimony; raises on failure"""
+        m = np.ascontiguousarray(matrix, dtype=np.float64).reshape(states * states)
+        p = self.lib.pll_parsimony_create(tips, states, sites, _d(m), score_buffers, ancestral_buffers)
+        if not p:
+            raise PllError("pll_parsimony_create failed (pll_errno=%d): %s" % (self.errno(), self.errmsg()))
+        return WeightedParsimony(self, p)
 
     def stepwise(self, pars_list, labels, seed):
         """pll_fastparsimony_stepwise: (pointer to the pll_utree_t, score); raises on failure"""
@@ -376,6 +409,80 @@ class Parsimony:
             return np.zeros((self.s.states, 0), dtype=np.uint32)
         v = self.s.packedvector[index]
         return np.ctypeslib.as_array(v, shape=(self.s.states * n,)).copy().reshape(self.s.states, n)
+
+
+class WeightedParsimony:
+    """A pll_parsimony_t* of pll_parsimony_create plus the weighted (Sankoff) calls that take it."""
+
+    def __init__(self, owner, ptr):
+        self.o = owner
+        self.lib = owner.lib
+        self.ptr = ptr
+        self.s = ptr.contents
+        self.amd = hasattr(self.lib, "pll_amd_sync_parsimony_scores")
+
+    def destroy(self):
+        if self.ptr:
+            self.lib.pll_parsimony_destroy(self.ptr)
+            self.ptr = None
+
+    def _check(self, ok, what):
+        if not ok:
+            raise PllError("%s failed (pll_errno=%d): %s" % (what, self.o.errno(), self.o.errmsg()))
+
+    def set_sequence(self, tip, cmap, seq):
+        """pll_set_parsimony_sequence; returns its status (PLL_SUCCESS / PLL_FAILURE) instead of raising"""
+        cmap = np.ascontiguousarray(cmap, dtype=np.uint32)
+        if isinstance(seq, str):
+            seq = seq.encode()
+        return self.lib.pll_set_parsimony_sequence(self.ptr, tip, _u(cmap), seq)
+
+    def build(self, ops):
+        """ops: (n, 3) integers (parent, child1, child2); the score pll_parsimony_build returns"""
+        a = np.ascontiguousarray(ops, dtype=np.uint32).reshape(-1, 3)
+        return self.lib.pll_parsimony_build(self.ptr, a.ctypes.data, len(a))
+
+    def score(self, index):
+        return self.lib.pll_parsimony_score(self.ptr, index)
+
+    def reconstruct(self, cmap, recops):
+        """recops: (n, 4) integers (node score, node ancestral, parent score, parent ancestral)"""
+        cmap = np.ascontiguousarray(cmap, dtype=np.uint32)
+        a = np.ascontiguousarray(recops, dtype=np.uint32).reshape(-1, 4)
+        self.lib.pll_parsimony_reconstruct(self.ptr, _u(cmap), a.ctypes.data, len(a))
+
+    def scores(self, index, sync=True):
+        """score buffer `index` as (sites, states) float64, synced first on libpll_amd unless sync=False (then the
+        host array as it stands; None if NULL)"""
+        if sync and self.amd:
+            self._check(self.lib.pll_amd_sync_parsimony_scores(self.ptr, index), "pll_amd_sync_parsimony_scores")
+        v = self.s.sbuffer[index]
+        if not v:
+            return None
+        return np.ctypeslib.as_array(v, shape=(self.s.sites * self.s.states,)).copy().reshape(self.s.sites,
+                                                                                             self.s.states)
+
+    def ancestral(self, index, sync=True):
+        """ancestral buffer `index` as uint32[sites] (synced as in scores())"""
+        if sync and self.amd:
+            self._check(self.lib.pll_amd_sync_parsimony_ancestral(self.ptr, index), "pll_amd_sync_parsimony_ancestral")
+        v = self.s.anc_states[index]
+        if not v:
+            return None
+        return np.ctypeslib.as_array(v, shape=(self.s.sites,)).copy()
+
+    def push_scores(self, index, values):
+        """write score buffer `index` (sites x states) into sbuffer[index] -- allocated with malloc if NULL, as the
+        library frees it -- and pll_amd_push_parsimony_scores it"""
+        vals = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        n = self.s.sites * self.s.states
+        assert vals.size == n
+        if not self.s.sbuffer[index]:
+            _libc.malloc.restype = C.c_void_p
+            _libc.malloc.argtypes = [C.c_size_t]
+            self.s.sbuffer[index] = C.cast(_libc.malloc(8 * n), _dp)
+        C.memmove(self.s.sbuffer[index], vals.ctypes.data, 8 * n)
+        self._check(self.lib.pll_amd_push_parsimony_scores(self.ptr, index), "pll_amd_push_parsimony_scores")
 
 
 class Partition:
