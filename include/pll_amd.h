@@ -726,6 +726,46 @@ PLL_EXPORT char * pll_utree_export_newick(const pll_unode_t * root, char * (*cb_
 
 /* ---- additions of this library (no reference counterpart) ---- */
 
+/* ---- batched insertion scoring: phylogenetic placement, lazy SPR (insertion.c, insertion.hip) ----
+ * One edge u -- v of a fixed tree, given by the CLVs of its two sides, each pointing away from the other (a tip or
+ * an inner CLV), their scale buffers, and the two lengths from the new node to u and to v. */
+typedef struct pll_amd_insertion_edge
+{
+  unsigned int proximal_clv_index;   /* u: the CLV of u's side, pointing away from v (a tip or an inner CLV) */
+  int          proximal_scaler_index;
+  unsigned int distal_clv_index;     /* v: the CLV of v's side, pointing away from u */
+  int          distal_scaler_index;
+  double       proximal_length;      /* u -- new node */
+  double       distal_length;        /* new node -- v */
+} pll_amd_insertion_edge_t;
+
+/* lnl[q * edge_count + e] = the log-likelihood of the tree in which query q hangs from a new node on edge e by a
+ * pendant branch of pendant_lengths[q]: what these three calls return on the same partition --
+ * pll_update_prob_matrices for the proximal, distal and pendant lengths with params_indices; pll_update_partials with
+ * one op, parent a spare node (its scaler a fresh buffer when scale_buffers > 0, else PLL_SCALE_BUFFER_NONE),
+ * children u and v; pll_compute_edge_loglikelihood(spare node, query, pendant matrix, freqs_indices =
+ * params_indices).  Queries are tips (placement) or inner CLVs with scalers (a pruned subtree, SPR);
+ * query_scaler_indices may be NULL (no scalers).  Both scaling modes, +I, a rate matrix per category, pattern tips or
+ * tip CLVs, pattern weights and partitions sharded over devices (pll_amd_set_devices: range sums added on the host in
+ * range order) behave as in those calls.
+ * What lives where: the insertion vectors, P-matrices and partial sums are scratch of the partition on its device,
+ * kept until it is destroyed; a call never changes a CLV, scale buffer, P-matrix, sumtable or host mirror.  Large
+ * batches are worked in chunks of at most about PLL_AMD_INSERTION_SCRATCH_MB (environment, default 2048) of scratch;
+ * the chunking never changes a result, and a pair's value is the same bits whatever else is in the batch, in
+ * whatever order.  The call is synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, lnl untouched): CLV, scaler and params indices in
+ * range, lengths non-negative and finite, edge_count and query_count not 0, no NULL array but query_scaler_indices.
+ * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
+ * or joined to an RCCL communicator (pll_amd_comm_init).  PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.
+ * INTEGRATION.md section "Insertion scoring". */
+PLL_EXPORT int pll_amd_insertion_loglikelihood(pll_partition_t * partition,
+                                               const pll_amd_insertion_edge_t * edges, unsigned int edge_count,
+                                               const unsigned int * query_clv_indices,
+                                               const int * query_scaler_indices,
+                                               const double * pendant_lengths, unsigned int query_count,
+                                               const unsigned int * params_indices,
+                                               double * lnl);
+
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets
  * threads create partitions concurrently -- WITH a process-wide default: a thread that has not set a device uses what

@@ -302,6 +302,29 @@ PLLHIP_EXPORT int pllhip_get_site_id(pllhip_ctx_t * ctx, unsigned int clv_index,
  * and reports *classes = 0 to the caller (its mirrors arrive expanded); this is the sum over its shards. */
 PLLHIP_EXPORT unsigned int pllhip_repeats_rows(pllhip_ctx_t * ctx, unsigned int clv_index);
 
+/* ---- batched insertion scoring (insertion.hip; host side host/insertion.c) ----
+ * lnl[q * edge_count + e] = what pllhip_update_pmatrices (the edge's two lengths and the pendant length),
+ * pllhip_update_partials (one op: a new node from the edge's two sides, its scaler a fresh buffer when the
+ * context has scale buffers) and pllhip_edge_loglikelihood (new node, query q, pendant matrix, freqs indices =
+ * params indices) would return.  Same layout as pll_amd_insertion_edge_t.  Nothing of the context changes;
+ * scratch (kept by the context) is at most about scratch_bytes per chunk, at least one pair's worth.  Returns
+ * -1 for a bad argument (nothing launched, lnl untouched), -2 if a chunk's scratch cannot be had, -3 for a
+ * context this call does not take (asc-bias, site repeats, RCCL). */
+typedef struct pllhip_insertion_edge
+{
+  unsigned int proximal_clv_index;
+  int proximal_scaler_index;
+  unsigned int distal_clv_index;
+  int distal_scaler_index;
+  double proximal_length;
+  double distal_length;
+} pllhip_insertion_edge_t;
+PLLHIP_EXPORT int pllhip_insertion_loglikelihood(pllhip_ctx_t * ctx, const pllhip_insertion_edge_t * h_edges,
+                                                 unsigned int edge_count, const unsigned int * h_query_clv,
+                                                 const int * h_query_scaler, const double * h_pendant,
+                                                 unsigned int query_count, const unsigned int * h_params_indices,
+                                                 size_t scratch_bytes, double * h_lnl);
+
 /* ---- multi-GPU: one process per GPU, RCCL sum of the scalar results ---- */
 PLLHIP_EXPORT int pllhip_comm_unique_id(void * id128);
 /* which RCCL the process uses: the file the collective symbols were bound to -- the copy already

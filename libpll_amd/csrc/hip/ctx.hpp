@@ -217,6 +217,11 @@ struct pllhip_ctx
   std::vector<pllhip_op_t> cert_ops;
   unsigned long long cert_stats[4] = {0, 0, 0, 0}; // lists launched with the test, trips, re-runs, uncertified
 
+  // insertion calls (insertion.hip): their scratch -- P-matrices, insertion vectors, query vectors, partial sums --,
+  // grown to what one chunk of a call needs and kept until the context goes
+  void * ins_scratch = nullptr;
+  size_t ins_scratch_bytes = 0;
+
   // optional per-launch timing (pllhip_profile_*): one event pair per launch
   bool profiling = false;
   std::vector<hipEvent_t> prof_events;   // pairs
@@ -487,6 +492,11 @@ static inline double pllhip_cert_err(const pllhip_ctx * c, unsigned int clv_inde
 {
   return (c->n_inexact && clv_index < c->clv_err.size()) ? c->clv_err[clv_index] : 0.0;
 }
+// partials.hip: `count` independent ops of one kind and mode, batched where the partition's kernels batch
+int pllhip_launch_partials_batch(pllhip_ctx * c, PartialsBatch & b, unsigned int count, int kind, int mode);
+// pmatrix.hip: P-matrices into `dst` (slots matrices of room) instead of the partition's array
+int pllhip_pmatrices_to(pllhip_ctx * c, double * dst, unsigned int slots, const unsigned int * h_params_indices,
+                        const unsigned int * h_matrix_indices, const double * h_branch_lengths, unsigned int count);
 // partials.hip: one op resolved into kernel arguments (kind 0 inner-inner, 1 tip-inner, 2 tip-tip)
 int pllhip_resolve_op(pllhip_ctx * c, const pllhip_op_t & op, PartialsArgs & a, int & kind, int & mode);
 void pllhip_aa_fused_free(pllhip_ctx * c);

@@ -404,6 +404,28 @@ int pllhip_launch_partials(pllhip_ctx * c, const PartialsArgs & a_in, int kind, 
   return 0;
 }
 
+// `count` mutually independent ops of one kind and scaling mode (the insertion calls' ops, insertion.hip): the batched
+// kernels of the per-level path where they cover the partition, else one launch per op -- the kernel each op would
+// get from pllhip_launch_partials either way
+int pllhip_launch_partials_batch(pllhip_ctx * c, PartialsBatch & b, unsigned int count, int kind, int mode)
+{
+  if (!count) return 0;
+  if (c->sh.states == 4 && fast_rc(c->sh.rate_cats))
+  {
+    pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II + kind);
+    HIP_TRY(pllhip_launch_dna_batch(c, b, count, kind, mode) ? hipErrorLaunchFailure : hipSuccess);
+    return 0;
+  }
+  if (c->sh.states == 20 && pllhip_aa_fast_covers(c, kind)) return pllhip_launch_aa_batch(c, b, count, kind, mode);
+  if (pllhip_gen_tile_covers(c)) return pllhip_launch_gen_batch(c, b, count, kind, mode);
+  for (unsigned int i = 0; i < count; ++i)
+  {
+    const int rc = pllhip_launch_partials(c, b.op[i], kind, mode, -1);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 // the plan of the previous per-level call of a context (see pllhip_update_partials)
 struct pllhip_planned_op
 {

@@ -108,17 +108,14 @@ __global__ __launch_bounds__(256) void k_update_pmatrix(PmatArgs a)
   }
 }
 
-extern "C" int pllhip_update_pmatrices(pllhip_ctx_t * c, const unsigned int * h_params_indices,
-                                       const unsigned int * h_matrix_indices,
-                                       const double * h_branch_lengths, unsigned int count)
+// matrices into `dst` (room for `slots` of them): the partition's own array, or scratch of the insertion calls
+// (insertion.hip) -- the same kernel either way, so a matrix there is bit for bit the one the partition would hold
+int pllhip_pmatrices_to(pllhip_ctx * c, double * dst, unsigned int slots, const unsigned int * h_params_indices,
+                        const unsigned int * h_matrix_indices, const double * h_branch_lengths, unsigned int count)
 {
-  PLLHIP_ALL_SHARDS_PAR(c, pllhip_update_pmatrices(s, h_params_indices, h_matrix_indices, h_branch_lengths, count));
-  if (!count) return 0;
-  HIP_TRY(hipSetDevice(c->sh.device));
-  PLLHIP_CERT_FIRST(c); // (a list that may have to run again must find the matrices it ran with)
   for (unsigned int i = 0; i < count; ++i)
   {
-    if (h_matrix_indices[i] >= c->sh.prob_matrices)
+    if (h_matrix_indices[i] >= slots)
     {
       pllhip_set_error("pllhip_update_pmatrices: matrix index %u out of range", h_matrix_indices[i]);
       return -1;
@@ -130,7 +127,7 @@ extern "C" int pllhip_update_pmatrices(pllhip_ctx_t * c, const unsigned int * h_
     }
   }
   PmatArgs a;
-  a.pmatrix = c->pmatrix;
+  a.pmatrix = dst;
   a.eigenvals = c->eigenvals;
   a.eigenvecs = c->eigenvecs;
   a.inv_eigenvecs = c->inv_eigenvecs;
@@ -190,4 +187,16 @@ extern "C" int pllhip_update_pmatrices(pllhip_ctx_t * c, const unsigned int * h_
     done += n;
   }
   return 0;
+}
+
+extern "C" int pllhip_update_pmatrices(pllhip_ctx_t * c, const unsigned int * h_params_indices,
+                                       const unsigned int * h_matrix_indices,
+                                       const double * h_branch_lengths, unsigned int count)
+{
+  PLLHIP_ALL_SHARDS_PAR(c, pllhip_update_pmatrices(s, h_params_indices, h_matrix_indices, h_branch_lengths, count));
+  if (!count) return 0;
+  HIP_TRY(hipSetDevice(c->sh.device));
+  PLLHIP_CERT_FIRST(c); // (a list that may have to run again must find the matrices it ran with)
+  return pllhip_pmatrices_to(c, c->pmatrix, c->sh.prob_matrices, h_params_indices, h_matrix_indices, h_branch_lengths,
+                             count);
 }

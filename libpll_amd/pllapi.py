@@ -280,6 +280,9 @@ class PllLibrary:
                                                       C.POINTER(C.c_double)]
                 lib.pll_amd_list_kinds.argtypes = [_PP, _up]
             lib.pll_amd_eigen_decompose.argtypes = [C.c_uint, _dp, _dp, _dp, _dp, _dp]
+            if hasattr(lib, "pll_amd_insertion_loglikelihood"):
+                lib.pll_amd_insertion_loglikelihood.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_void_p, _dp,
+                                                                C.c_uint, _up, _dp]
 
     # -- library-level helpers -------------------------------------------------
     def errno(self):
@@ -485,6 +488,12 @@ class WeightedParsimony:
         self._check(self.lib.pll_amd_push_parsimony_scores(self.ptr, index), "pll_amd_push_parsimony_scores")
 
 
+# pll_amd_insertion_edge_t (include/pll_amd.h)
+INSERTION_EDGE_DTYPE = np.dtype([("proximal_clv_index", np.uint32), ("proximal_scaler_index", np.int32),
+                                 ("distal_clv_index", np.uint32), ("distal_scaler_index", np.int32),
+                                 ("proximal_length", np.float64), ("distal_length", np.float64)])
+
+
 class Partition:
     """A pll_partition_t* plus the calls that take it as first argument."""
 
@@ -620,6 +629,27 @@ class Partition:
             self.ptr, pscaler, cscaler, t, _u(pi), _d(sumtable), C.byref(d), C.byref(dd)),
             "pll_compute_likelihood_derivatives")
         return d.value, dd.value
+
+    def insertion_loglikelihood(self, edges, queries, pendant_lengths, params_indices, query_scalers=None):
+        """pll_amd_insertion_loglikelihood: a (queries, edges) array of log-likelihoods.  edges: rows of
+        (proximal_clv, proximal_scaler, distal_clv, distal_scaler, proximal_length, distal_length) or an
+        INSERTION_EDGE_DTYPE array; queries: CLV indices; query_scalers: scaler indices or None."""
+        e = np.zeros(len(edges), dtype=INSERTION_EDGE_DTYPE)
+        if isinstance(edges, np.ndarray) and edges.dtype == INSERTION_EDGE_DTYPE:
+            e[:] = edges
+        else:
+            for i, row in enumerate(edges):
+                e[i] = tuple(row)
+        q = np.ascontiguousarray(queries, dtype=np.uint32)
+        pl = np.ascontiguousarray(pendant_lengths, dtype=np.float64)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        qs = None if query_scalers is None else np.ascontiguousarray(query_scalers, dtype=np.int32)
+        out = np.zeros((len(q), len(e)))
+        ok = self.lib.pll_amd_insertion_loglikelihood(
+            self.ptr, e.ctypes.data, len(e), _u(q), None if qs is None else qs.ctypes.data, _d(pl), len(q),
+            _u(pi), _d(out))
+        self._check(ok, "pll_amd_insertion_loglikelihood")
+        return out
 
     # -- reading results back ----------------------------------------------------------
     def get_clv(self, idx):
