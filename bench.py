@@ -50,6 +50,14 @@ stream and wall clock, median and minimum over the steps).
 `cpu_baseline` times the reference's AVX2-flag path (oracle/_ref, built from
 the reference sources in the dev container) on one host core over a bounded
 sample of the same workload.
+
+A plain run does only what the headline needs: it generates the alignment, sets the partition up,
+runs the first evaluation, the ramp and the --warmup steps, times the --steps steps, writes
+--dump-outputs if given and prints the line.  Everything else described above -- the reference's
+lnL of each rank's range and `lnl_rel_err_vs_reference`, `cpu_baseline`, `per_step_ms`, `roofline`
+(box ceiling and matrix cores included), `api_calls`, `kernels`, `varying_lists` and `c4_strong` --
+runs only with `--full`; in a plain run those fields are null.  `--newton N` and `--force-c4` are
+requests of their own and run with or without `--full`.
 """
 import argparse
 import json
@@ -244,6 +252,11 @@ def main():
     ap.add_argument("--newton", type=int, default=0,
                     help="also time pll_update_sumtable + N x pll_compute_likelihood_derivatives "
                          "at the root edge (BASELINE config 5's inner loop)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: CPU baseline and reference lnL checks, per-step "
+                         "spread, roofline and box ceiling, API-call and per-kernel times, varying lists and, at N > 1 "
+                         "or N = 1 with the default workload, BASELINE config 4 (the options above that shape these "
+                         "legs: --cpu-sites, --cpu-reps, --no-vary, --no-c4, --no-c4-one-gpu)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="write what the last timed step computed to DIR/*.npy (float64, rank 0): its lnL and, at a "
                          "fixed seeded sample of sites, the two root-edge CLVs and their scale buffers")
@@ -318,7 +331,7 @@ def main():
     # lnL the product's all-reduce returned (lnl_rel_err_vs_reference).  One evaluation of 62 ops x 1 M sites
     # is about half a second of one host core per rank.
     shard_ref_lnl = None
-    if (world > 1 or inproc > 1) and args.cpu_sites > 0 and ref is not None:
+    if args.full and (world > 1 or inproc > 1) and args.cpu_sites > 0 and ref is not None:
         shard_ref_lnl, _ = W.reference_lnl(ref, plan, seqs, S, R, attrs | ATTRIB_ARCH_AVX2)
 
     section("reference lnL of this rank's range")
@@ -328,7 +341,7 @@ def main():
     cpu = None
     cpu_sample = None
     cpu_ref_lnl = None
-    if rank == 0 and world == 1 and args.cpu_sites > 0 and ref is not None:
+    if args.full and rank == 0 and world == 1 and args.cpu_sites > 0 and ref is not None:
         n = min(args.cpu_sites, hi - lo)
         cpu_sample = [s[:n] for s in seqs]
         rp = W.setup_partition(ref, plan, cpu_sample, S, R, attrs | ATTRIB_ARCH_AVX2)
@@ -488,23 +501,25 @@ def main():
     # box by several per cent): every step synchronised and timed on its own, for at least 20 steps
     # and half a second.  (Each step then pays its own launch + completion latency: the median reads
     # a little above ms_per_step.)
-    per_step = []
-    t_spread = time.perf_counter()
-    while len(per_step) < 20 or time.perf_counter() - t_spread < 0.5:
-        t1 = time.perf_counter()
-        step()
-        sync()
-        per_step.append((time.perf_counter() - t1) * 1e3)
-        if use_comm:
-            # (a step is a collective: every rank runs the same number of them)
-            flag = torch.tensor([1.0 if (len(per_step) >= 20 and time.perf_counter() - t_spread >= 0.5) else 0.0],
-                                dtype=torch.float32, device="cuda")
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            if flag.item() >= 1.0:
-                break
-    ps = sorted(per_step)
-    per_step_ms = {"steps": len(ps), "median": round(ps[len(ps) // 2], 4), "p10": round(ps[len(ps) // 10], 4),
-                   "p90": round(ps[(9 * len(ps)) // 10], 4), "min": round(ps[0], 4), "max": round(ps[-1], 4)}
+    per_step_ms = None
+    if args.full:
+        per_step = []
+        t_spread = time.perf_counter()
+        while len(per_step) < 20 or time.perf_counter() - t_spread < 0.5:
+            t1 = time.perf_counter()
+            step()
+            sync()
+            per_step.append((time.perf_counter() - t1) * 1e3)
+            if use_comm:
+                # (a step is a collective: every rank runs the same number of them)
+                flag = torch.tensor([1.0 if (len(per_step) >= 20 and time.perf_counter() - t_spread >= 0.5) else 0.0],
+                                    dtype=torch.float32, device="cuda")
+                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+                if flag.item() >= 1.0:
+                    break
+        ps = sorted(per_step)
+        per_step_ms = {"steps": len(ps), "median": round(ps[len(ps) // 2], 4), "p10": round(ps[len(ps) // 10], 4),
+                       "p90": round(ps[(9 * len(ps)) // 10], 4), "min": round(ps[0], 4), "max": round(ps[-1], 4)}
     per_rank_ms = None
     if use_comm:
         # one figure per rank, so that a straggler GPU is visible
@@ -531,12 +546,14 @@ def main():
     # read per tip character -- NOT SURVEY 8(d)'s 396 / 265 / 134 B per site-update, which
     # describe the per-op algorithm and would put `frac` above 1; that equivalent is reported
     # next to it.
-    part.profile_enable(True)
-    part.update_partials(plan.ops)
-    prof_full = part.profile_read()
-    part.profile_enable(False)
-    full_launches = sum(v[0] for k, v in prof_full.items() if k.startswith("partials"))
-    if S in (4, 20) and full_launches == 1 and len(plan.ops) > 1:
+    full_launches = 0
+    if args.full:
+        part.profile_enable(True)
+        part.update_partials(plan.ops)
+        prof_full = part.profile_read()
+        part.profile_enable(False)
+        full_launches = sum(v[0] for k, v in prof_full.items() if k.startswith("partials"))
+    if args.full and S in (4, 20) and full_launches == 1 and len(plan.ops) > 1:
         n_ii = int((c1 & c2).sum()) if not args.tip_clv else len(plan.ops)
         n_tt = 0 if args.tip_clv else int((~c1 & ~c2).sum())
         n_ti = len(plan.ops) - n_ii - n_tt
@@ -623,7 +640,7 @@ def main():
                         "one gather, ops over tip-tip results a table lookup), and a matrix op runs at the wave's own "
                         "serial path (DESIGN.md 2.2c); mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 "
                         "SIMDs) of the list kernel from the rocprofv3 PMC pass named in mfma_busy_source"}
-    elif len(ii_ops):
+    elif args.full and len(ii_ops):
         # how many kernel launches the library makes for this op list (independent
         # ops of one tree level are batched into one launch, blockIdx.y = op)
         part.profile_enable(True)
@@ -670,19 +687,21 @@ def main():
     def spread(xs):
         xs = sorted(xs)
         return {"median": round(xs[len(xs) // 2], 4), "min": round(xs[0], 4)}
-    ev_up, wall_up, wall_lnl = [], [], []
-    for _ in range(max(args.steps, 5)):
-        part.wait()
-        t1 = time.perf_counter()
-        part.timer_start()
-        part.update_partials(plan.ops)
-        ev_up.append(part.timer_stop_ms())
-        wall_up.append((time.perf_counter() - t1) * 1e3)
-        t1 = time.perf_counter()
-        step_lnl = part.compute_edge_loglikelihood(*plan.root_edge, fi)
-        wall_lnl.append((time.perf_counter() - t1) * 1e3)
-    api = {"update_partials_ms_hip_events": spread(ev_up), "update_partials_ms_wall": spread(wall_up),
-           "edge_loglikelihood_ms_wall": spread(wall_lnl)}
+    api = None
+    if args.full:
+        ev_up, wall_up, wall_lnl = [], [], []
+        for _ in range(max(args.steps, 5)):
+            part.wait()
+            t1 = time.perf_counter()
+            part.timer_start()
+            part.update_partials(plan.ops)
+            ev_up.append(part.timer_stop_ms())
+            wall_up.append((time.perf_counter() - t1) * 1e3)
+            t1 = time.perf_counter()
+            step_lnl = part.compute_edge_loglikelihood(*plan.root_edge, fi)
+            wall_lnl.append((time.perf_counter() - t1) * 1e3)
+        api = {"update_partials_ms_hip_events": spread(ev_up), "update_partials_ms_wall": spread(wall_up),
+               "edge_loglikelihood_ms_wall": spread(wall_lnl)}
 
     section("spread, roofline and api legs")
     # ---- op lists that CHANGE from call to call: what the reference's real callers do (tree search:
@@ -693,7 +712,7 @@ def main():
     # branch-length changes (pll_update_prob_matrices for the changed branches is in the step) -- so
     # ordering the list, assigning slots, encoding and uploading the plan are inside the timed steps.
     varying = None
-    if not args.no_vary and not args.site_repeats:
+    if args.full and not args.no_vary and not args.site_repeats:
         view = W.UnrootedView(plan, use_scalers=not args.no_scalers)
         rng = W.SplitMix64(777)
         all_edges = view.edges()
@@ -781,13 +800,15 @@ def main():
 
     # per-class averages with one event pair per launch (diagnostic; each pair
     # adds ~2 us, so these read high)
-    part.profile_enable(True)
-    for _ in range(min(args.steps, 5)):
-        step()
-    prof = part.profile_read()
-    part.profile_enable(False)
-    per_kernel = {k: {"launches": v[0], "avg_us": round(v[1] / v[0] * 1e3, 2) if v[0] else None}
-                  for k, v in prof.items() if v[0]}
+    per_kernel = None
+    if args.full:
+        part.profile_enable(True)
+        for _ in range(min(args.steps, 5)):
+            step()
+        prof = part.profile_read()
+        part.profile_enable(False)
+        per_kernel = {k: {"launches": v[0], "avg_us": round(v[1] / v[0] * 1e3, 2) if v[0] else None}
+                      for k, v in prof.items() if v[0]}
 
     section("varying lists")
     # ---- optional: the branch-length optimisation inner loop at the root edge
@@ -829,7 +850,7 @@ def main():
     # otherwise leave the others waiting in the SUM: ADVICE r4) -- first a MIN over "I have one", as the config-4
     # section does.
     have_ref = shard_ref_lnl is not None
-    if world > 1:
+    if world > 1 and args.full:
         flag = torch.tensor([1.0 if have_ref else 0.0], dtype=torch.float64, device="cuda")
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         have_ref = flag.item() >= 1.0
@@ -856,7 +877,7 @@ def main():
                         not strong and not args.tip_clv and not args.site_repeats and not args.rate_scalers and
                         not args.no_scalers)
     c4_single = world * inproc == 1 and not args.force_c4
-    if (world * inproc > 1 or args.force_c4 or default_workload) and not args.no_c4 and S == 4:
+    if ((args.full and (world * inproc > 1 or default_workload)) or args.force_c4) and not args.no_c4 and S == 4:
         part.destroy()
         part = None
         c4_sites, c4_taxa = 8_000_000, 128
@@ -1039,6 +1060,7 @@ def main():
             "metric": "M CLV-site-updates/s (%dx%d states x rates)" % (S, R),
             "value": round(value, 2), "unit": "M CLV-site-updates/s",
             "n_gpus": world * inproc, "steps": args.steps, "warmup": untimed_steps, "warmup_flag": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "per_step_ms": per_step_ms, "per_rank_ms_per_step": per_rank_ms,
             "higher_is_better": True, "scaling": "strong" if strong else "weak",

@@ -11,7 +11,7 @@ print('%-44s %-28s step %7.3f ms  launch %8.3f ms  frac %.3f  value %.1f' % ('$1
 for shape in "$@"; do
   for rep in 1 2; do
     for v in $vals; do
-      env $var=$v python3 bench.py $shape --cpu-sites 0 --steps 20 --warmup 2 --no-vary --no-c4 2>/dev/null | line "$shape" "$var=$v"
+      env $var=$v python3 bench.py --full $shape --cpu-sites 0 --steps 20 --warmup 2 --no-vary --no-c4 2>/dev/null | line "$shape" "$var=$v"
     done
   done
 done

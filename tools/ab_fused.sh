@@ -5,7 +5,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 b() { # name, -- args
   local name=$1; shift; shift
-  env "${ENVS[@]}" python3 bench.py --cpu-sites 0 --steps 20 --warmup 3 "$@" > $out/$name.json 2> $out/$name.err
+  env "${ENVS[@]}" python3 bench.py --full --cpu-sites 0 --steps 20 --warmup 3 "$@" > $out/$name.json 2> $out/$name.err
   python3 - "$out/$name.json" "$name" <<'P'
 import json, sys
 try:

@@ -10,7 +10,7 @@ print('%-44s %-28s step %7.3f ms  launch %8.3f ms  frac %.3f  value %.1f' % ('$1
 for shape in "$@"; do
   for rep in 1 2 3; do
     for lib in $a $b; do
-      PLL_AMD_LIB=$lib python3 bench.py $shape --cpu-sites 0 --steps 20 --warmup 2 --no-vary --no-c4 2>/dev/null | line "$shape" $lib
+      PLL_AMD_LIB=$lib python3 bench.py --full $shape --cpu-sites 0 --steps 20 --warmup 2 --no-vary --no-c4 2>/dev/null | line "$shape" $lib
     done
   done
 done

@@ -13,7 +13,7 @@ if [ "$1" != pmc ]; then
   for shape in "--total-sites 8000000 --taxa 128" "--total-sites 2000000 --taxa 256"; do
     for b in 0 4000000 2000000 1000000 500000 auto; do
       if [ $b = auto ]; then unset PLLHIP_FUSED_BLOCK_SITES; else export PLLHIP_FUSED_BLOCK_SITES=$b; fi
-      python3 bench.py $shape --cpu-sites 0 --steps 5 --warmup 1 --no-vary 2>/dev/null | line "$shape" "block $b"
+      python3 bench.py --full $shape --cpu-sites 0 --steps 5 --warmup 1 --no-vary 2>/dev/null | line "$shape" "block $b"
     done
   done
   exit 0

@@ -10,7 +10,7 @@ export PLL_AMD_LIB=$PWD/build/wps4/libpll_amd.so
 for shape in "--sites 1000000" "--sites 1000000 --taxa 128" "--sites 500000 --taxa 200 --tree random" "--sites 125000"; do
   for rep in 1 2; do
     for w in 3 4; do
-      PLLHIP_FUSED_WGS=$w python3 bench.py $shape --cpu-sites 20000 --steps 20 --warmup 2 --no-vary --no-c4 2>/dev/null | python3 -c "
+      PLLHIP_FUSED_WGS=$w python3 bench.py --full $shape --cpu-sites 20000 --steps 20 --warmup 2 --no-vary --no-c4 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('%-44s workgroups per CU %d  step %7.3f ms  launch %8.1f us  frac %.3f  value %8.1f  lnL err %s  %s' % ('$shape', $w, d['ms_per_step'], r['avg_launch_us'], r['frac'], d['value'], d.get('lnl_rel_err_vs_reference'), r['kernel'][:40]))"

@@ -11,7 +11,7 @@ mkdir -p $out
 rm -f $out/lines_*.json
 for v in 1 0; do
  for shape in "--taxa 64" "--taxa 200 --tree random --sites 100000" "--taxa 64 --tip-clv"; do
-  (cd $R && PLLHIP_AA_CHUNKS=$v python3 bench.py --states 20 --rate-cats $RC --sites 200000 $shape --cpu-sites 20000 --no-vary --no-c4 --steps 10 2>/dev/null) | tee -a $out/lines_chunks_$v.json | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('CHUNKS=$v', 'R=$RC', '$shape', d['ms_per_step'], d.get('lnl_rel_err_vs_reference'), d['roofline']['frac'], d['kernels'])"
+  (cd $R && PLLHIP_AA_CHUNKS=$v python3 bench.py --full --states 20 --rate-cats $RC --sites 200000 $shape --cpu-sites 20000 --no-vary --no-c4 --steps 10 2>/dev/null) | tee -a $out/lines_chunks_$v.json | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('CHUNKS=$v', 'R=$RC', '$shape', d['ms_per_step'], d.get('lnl_rel_err_vs_reference'), d['roofline']['frac'], d['kernels'])"
  done
 done
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $R/bench.py --states 20 --rate-cats $RC --sites 200000 --cpu-sites 0 --no-vary --no-c4 --steps 10 > /dev/null 2> $out/trace.err

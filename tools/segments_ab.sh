@@ -12,7 +12,7 @@ for cfg in "$@"; do
   set -- $cfg
   for rep in 1 2; do
     for v in 0 8; do
-      PLLHIP_FUSED_SEGMENTS=$v python3 bench.py --states $1 --sites $2 --cpu-sites 0 --no-vary --no-c4 --steps 50 2>/dev/null | line $1 $2 "PLLHIP_FUSED_SEGMENTS=$v"
+      PLLHIP_FUSED_SEGMENTS=$v python3 bench.py --full --states $1 --sites $2 --cpu-sites 0 --no-vary --no-c4 --steps 50 2>/dev/null | line $1 $2 "PLLHIP_FUSED_SEGMENTS=$v"
     done
   done
 done

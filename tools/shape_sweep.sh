@@ -7,7 +7,7 @@ printf "%-8s" "taxa"; for s in 100000 250000 500000 1000000 2000000; do printf "
 for t in 16 32 64 128 256; do
   printf "%-8s" $t
   for s in 100000 250000 500000 1000000 2000000; do
-    python3 bench.py --cpu-sites 0 --no-c4 --steps 10 --warmup 2 --taxa $t --sites $s 2>/dev/null | python3 -c "
+    python3 bench.py --full --cpu-sites 0 --no-c4 --steps 10 --warmup 2 --taxa $t --sites $s 2>/dev/null | python3 -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
