@@ -44,7 +44,7 @@ HIPFLAGS_partials_aa_fused := -mllvm -amdgpu-mfma-vgpr-form -mllvm -amdgpu-spill
 $(BUILD)/hip_partials_aa_fused.o: libpll_amd/csrc/hip/partials_aa_fused.hip include/pllhip.h $(wildcard libpll_amd/csrc/hip/*.hpp) $(wildcard libpll_amd/csrc/hip/*.inc) tools/check_agprs.py | $(BUILD)
 	rm -rf $(BUILD)/aa_fused_tmp && mkdir -p $(BUILD)/aa_fused_tmp
 	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_partials_aa_fused) -save-temps=obj -c $< -o $(BUILD)/aa_fused_tmp/hip_partials_aa_fused.o
-	python3 tools/check_agprs.py $(AGPR_CHECK_FLAGS) $(BUILD)/aa_fused_tmp/partials_aa_fused-hip-amdgcn-amd-amdhsa-$(ARCH).s
+	python3 tools/check_agprs.py $(BUILD)/aa_fused_tmp/partials_aa_fused-hip-amdgcn-amd-amdhsa-$(ARCH).s
 	mv $(BUILD)/aa_fused_tmp/hip_partials_aa_fused.o $@
 
 $(OUT): $(HOST_OBJ) $(HIP_OBJ)

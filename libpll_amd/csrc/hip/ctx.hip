@@ -11,7 +11,6 @@
 //   tipchars      [tips][sites rounded up to 256 B] u8
 //   pmatrix       [prob_matrices][rate_cats][states][states] f64  (KBs; L2-resident)
 #include <dlfcn.h>
-#include <unistd.h>
 #include <sched.h>
 #include <time.h>
 #include <stdarg.h>
@@ -184,9 +183,7 @@ static int alloc_arena_placed(pllhip_ctx * c, char ** out, size_t bytes, size_t 
   c->placement_gbs.clear();
   int tries = 12; // (a fresh process has been handed six slow places in a row: profiles/r6_bench_driver_command.json)
   if (const char * e = pllhip_env("PLLHIP_PLACEMENT_TRIES")) tries = atoi(e);
-  size_t min_bytes = PLLHIP_PLACEMENT_MIN_BYTES;
-  if (const char * e = pllhip_env("PLLHIP_PLACEMENT_MIN_MB")) min_bytes = (size_t)atoi(e) << 20; // (tool switch)
-  if (bytes < min_bytes || tries <= 1) return dev_alloc(out, bytes, true, c->stream);
+  if (bytes < PLLHIP_PLACEMENT_MIN_BYTES || tries <= 1) return dev_alloc(out, bytes, true, c->stream);
   std::vector<void *> held;
   size_t best = 0;
   for (int t = 0; t < tries; ++t)
@@ -275,9 +272,7 @@ static void pllhip_fence_mark(void * flag)
 
 static void pllhip_stream_quiesce(hipStream_t stream)
 {
-  static const bool off = pllhip_env("PLLHIP_QUIESCE") && atoi(pllhip_env("PLLHIP_QUIESCE")) == 0; // (A/B of the crash hunt)
   (void)hipStreamSynchronize(stream);
-  if (off) return;
   // (the flag must outlive a callback that fires after the timeout: leaked on that path only)
   int * flag = new int(0);
   if (hipLaunchHostFunc(stream, pllhip_fence_mark, flag) != hipSuccess)
@@ -305,8 +300,6 @@ static void pllhip_stream_quiesce(hipStream_t stream)
 static void pllhip_exit_drain()
 {
   (void)hipDeviceSynchronize();
-  if (const char * e = pllhip_env("PLLHIP_EXIT_GRACE_US")) // (experiment knob of the crash hunt)
-    if (atoi(e) > 0) usleep((useconds_t)atoi(e));
 }
 
 extern "C" int pllhip_ctx_create(const pllhip_shape_t * shape, pllhip_ctx_t ** out)
@@ -355,16 +348,12 @@ extern "C" int pllhip_ctx_create(const pllhip_shape_t * shape, pllhip_ctx_t ** o
   if (const char * e = pllhip_env("PLLHIP_SPIN")) c->no_spin = atoi(e) == 0;
   if (const char * e = pllhip_env("PLLHIP_HOSTSUM")) c->no_hostsum = atoi(e) == 0;
   if (const char * e = pllhip_env("PLLHIP_FUSE_REDUCE")) c->fuse_forced = atoi(e) ? 1 : 0;
-  if (const char * e = pllhip_env("PLLHIP_FUSE_MAX_GRID")) c->fuse_max_grid = (unsigned int)atoi(e);
   if (const char * e = pllhip_env("PLLHIP_NT")) c->nt_override = atoi(e); // 0 / 1; 2: the whole-list kernel's counts too
-  if (const char * e = pllhip_env("PLLHIP_NO_BATCH")) c->no_batch = atoi(e) != 0;
   if (const char * e = pllhip_env("PLLHIP_FUSED"))
   {
     c->no_fused = atoi(e) == 0;
     c->force_fused = atoi(e) == 2;
   }
-  if (const char * e = pllhip_env("PLLHIP_BLOCKS_PER_CU"))
-    if (atoi(e) > 0) c->blocks_per_cu = atoi(e);
 
   HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   HIP_TRY(hipEventCreate(&c->ev0));
@@ -376,10 +365,6 @@ extern "C" int pllhip_ctx_create(const pllhip_shape_t * shape, pllhip_ctx_t ** o
   c->scaler_elems = shape->rate_scalers ? N * R : N;
   c->tip_stride = (N + 255) & ~(size_t)255;
   c->clv_stride = c->clv_elems + (size_t)PLLHIP_TAIL_SITES * c->span;
-  // (tool switch: extra sites of slack per CLV -- what the distance between the list kernels' output streams does to
-  // their stores, tools/ceiling_by_size.sh)
-  if (const char * e = pllhip_env("PLLHIP_CLV_PAD_SITES"))
-    if (atoi(e) > 0) c->clv_stride += (size_t)atoi(e) * c->span;
   c->scaler_stride = c->scaler_elems + (size_t)PLLHIP_TAIL_SITES * (shape->rate_scalers ? R : 1);
   c->pmat_elems = R * S * S;
 
@@ -622,8 +607,6 @@ extern "C" void pllhip_ctx_destroy(pllhip_ctx_t * c)
   for (hipEvent_t e : c->prof_events) (void)hipEventDestroy(e);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
-  if (const char * e = pllhip_env("PLLHIP_DESTROY_GRACE_US"))
-    if (atoi(e) > 0) usleep((useconds_t)atoi(e));
 }
 
 extern "C" int pllhip_wait(pllhip_ctx_t * c)

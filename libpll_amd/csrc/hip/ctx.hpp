@@ -136,7 +136,6 @@ struct pllhip_ctx
   bool no_spin = false;                // env PLLHIP_SPIN=0: wait for the stream instead (A/B measurements)
   bool no_hostsum = false;             // env PLLHIP_HOSTSUM=0: k_final_sum instead of the host's sum of workgroup sums
   int fuse_forced = -1;                // env PLLHIP_FUSE_REDUCE=0/1: the final sum never / always inside the reducing kernel
-  unsigned int fuse_max_grid = 128;    // env PLLHIP_FUSE_MAX_GRID (all read when the context is created)
   double * h_result_dev = nullptr;     // device address of h_result
   // workgroup sums of a result-returning kernel, written by the kernel straight into host memory and added by
   // the host (likelihood.hip: pllhip_result_wait_host): {value, sequence number} per workgroup and component
@@ -156,12 +155,6 @@ struct pllhip_ctx
 
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   int num_cus = 256;
-  // Grid cap of the streaming kernels (env PLLHIP_BLOCKS_PER_CU).  Measured on
-  // MI355X, 1,000,000 sites: one pass over the data with as many workgroups as
-  // it takes (3907) runs the 4-state CLV kernel in 65 us; capping the grid so
-  // that every wave makes 2 or 3 grid-stride passes costs 70-72 us.  So the cap
-  // is set where it only matters for alignments beyond ~16 M sites per GPU.
-  int blocks_per_cu = 256;
   int asc_type = 0;                      // PLL_ATTRIB_AB_* bits (0 = no correction)
   unsigned int asc_weight_sum = 0;
   double * d_asc = nullptr;              // [3] correction terms added by the final sum
@@ -186,7 +179,6 @@ struct pllhip_ctx
   size_t clv_arena_alloc_bytes = 0; // what was allocated for the arena (strides included)
   int placement_tries = 0, placement_best = 0; // where the CLV arena lies: places tried, the one kept (ctx.hip)
   std::vector<double> placement_gbs;          // GB/s of a zeroing pass over each place tried
-  bool no_batch = false;                 // PLLHIP_NO_BATCH=1: one launch per op (measurements)
   int nt_override = -1;                  // PLLHIP_NT=0/1 forces the cache policy (measurements); 2: and the whole-list
                                          // kernel's count stores, which follow the partition's size otherwise
   // 20 states: 1 = bit-exact vector kernels only (env PLLHIP_AA_EXACT=1);
@@ -243,10 +235,11 @@ struct pllhip_prof_scope
 void pllhip_set_error(const char * fmt, ...);
 
 // Environment switches.  The ones a client may rely on are the table in ctx.hip (pllhip_user_switches; INTEGRATION.md
-// section 6 documents each one); every other PLLHIP_* variable is a developer's knob -- tile shapes, grid caps,
-// experiments whose A/B results are in DESIGN.md -- and is read only under PLLHIP_DEVELOPER=1: a stray variable cannot
+// section 6 documents each one); every other PLLHIP_* variable is a developer's knob -- tile shapes, grid caps and the
+// alternative paths the tests compare against -- and is read only under PLLHIP_DEVELOPER=1: a stray variable cannot
 // move a production run off the configuration the test suite covers, and the library says so once on stderr when it
-// ignores one.  (forty switches, each a configuration nobody crosses with the others.)
+// ignores one.  (forty switches, each a configuration nobody crosses with the others.  The
+// experiments' switches that no test sets are gone; their A/B results are in DESIGN.md.)
 const char * pllhip_env(const char * name);
 
 // Run `expr` on every shard of a group context and return (inside `expr`: s = the shard, lo =
@@ -340,8 +333,15 @@ static inline bool pllhip_use_nt(const pllhip_ctx * c)
   return c->clv_arena_bytes >= PLLHIP_INFINITY_CACHE_BYTES;
 }
 
+// Grid cap of the streaming kernels, in workgroups per CU.  Measured on
+// MI355X, 1,000,000 sites: one pass over the data with as many workgroups as
+// it takes (3907) runs the 4-state CLV kernel in 65 us; capping the grid so
+// that every wave makes 2 or 3 grid-stride passes costs 70-72 us.  So the cap
+// is set where it only matters for alignments beyond ~16 M sites per GPU.
+#define PLLHIP_STREAM_BLOCKS_PER_CU 256
+
 // Grid size for a streaming kernel over `items` lanes-worth of work: all of it
-// in one pass if that fits the cap (blocks_per_cu x CUs), otherwise the smallest
+// in one pass if that fits the cap (PLLHIP_STREAM_BLOCKS_PER_CU x CUs), otherwise the smallest
 // whole number of grid-stride passes, with the grid shrunk so every block does
 // the SAME number of passes -- a last pass that only part of the grid takes
 // showed up as 7 % of the CLV kernel's time.
@@ -349,7 +349,7 @@ static inline unsigned int pllhip_stream_grid(const pllhip_ctx * c, size_t items
                                               unsigned int block)
 {
   size_t need = (items + block - 1) / block;
-  const size_t cap = (size_t)c->num_cus * c->blocks_per_cu;
+  const size_t cap = (size_t)c->num_cus * PLLHIP_STREAM_BLOCKS_PER_CU;
   if (need < 1) need = 1;
   if (need <= cap) return (unsigned int)need;
   const size_t passes = (need + cap - 1) / cap;
@@ -427,7 +427,6 @@ int pllhip_allreduce_result(pllhip_ctx * c, unsigned int count);
 // 20-state fast kernels (matrix cores / round-based tip-tip) for `count` mutually
 // independent ops of one kind and mode; returns 1 if the case is not covered
 bool pllhip_aa_fast_covers(const pllhip_ctx * c, int kind);
-bool pllhip_aa_chunks_enabled(); // 20 states, rate_cats other than 1, 2, 4 on the matrix-core kernels (PLLHIP_AA_CHUNKS)
 unsigned int pllhip_aa_lookup_budget(const pllhip_ctx * c);
 int pllhip_launch_aa_batch(pllhip_ctx * c, PartialsBatch & b, unsigned int count, int kind, int mode);
 bool pllhip_aa_cherry_covers(const pllhip_ctx * c, int mode);
@@ -451,11 +450,11 @@ struct AaLookupJob
   double * dst;
   unsigned int mode, pad;
 };
-// jobs == nullptr: the tables are built here and now (launches of the tabulating kernels); otherwise only their
-// places are assigned and jobs[2 i], jobs[2 i + 1] describe the two tables of op i
+// only their places are assigned here: jobs[2 i], jobs[2 i + 1] describe the two tables of op i, which the
+// whole-list kernel's prepare launch builds
 int pllhip_aa_lookup_tables(pllhip_ctx * c, const PartialsArgs * ops, const PartialsArgs * kid1,
                             const PartialsArgs * kid2, unsigned int count, AaLookupTables * out,
-                            AaLookupJob * jobs = nullptr);
+                            AaLookupJob * jobs);
 // partials_aa_fused.hip: a 20-state op list in one site-blocked launch; returns 1 if the list (or
 // the partition) is not one it takes -- the caller then launches per level
 int pllhip_aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count);

@@ -698,7 +698,7 @@ extern "C" int pllhip_likelihood_derivatives(pllhip_ctx_t * c, unsigned int slot
                             (c->asc_type & PLLHIP_AB_MASK) != PLLHIP_AB_STAMATAKIS;
   const bool aa_tile = (S == 20 && !c->aa_exact && (R == 1 || R == 2 || R == 4));
   // (other category counts: the tile walk chunk by chunk, its table staged; 150 KB of LDS at most)
-  const bool aa_chunks = (S == 20 && !c->aa_exact && !aa_tile && pllhip_aa_chunks_enabled() &&
+  const bool aa_chunks = (S == 20 && !c->aa_exact && !aa_tile &&
                           (size_t)R * 102 * sizeof(double) + 4 * 11 * 1024 <= 150 * 1024);
   DerivArgs a;
   if (dna || aa_tile) memcpy(a.diag_inline, h_diagptable, dbytes);
@@ -748,10 +748,9 @@ extern "C" int pllhip_likelihood_derivatives(pllhip_ctx_t * c, unsigned int slot
     if (grid > PLLHIP_REDUCE_BLOCKS) grid = PLLHIP_REDUCE_BLOCKS;
     // (a Newton iteration is a 17 us kernel: fewer, longer workgroups -- two per CU -- leave the final
     // sum 512 values instead of 1954 and the launch less to dispatch: 33.9 -> 28.8 us per call at
-    // 500 k sites; PLLHIP_DERIV_GRID for measurements)
+    // 500 k sites)
     {
-      const char * e = pllhip_env("PLLHIP_DERIV_GRID");
-      const unsigned int cap = e && atoi(e) > 0 ? (unsigned int)atoi(e) : (unsigned int)c->num_cus * 2;
+      const unsigned int cap = (unsigned int)c->num_cus * 2;
       if (grid > cap) grid = cap;
     }
     a.reduce = pllhip_reduce_out(c, grid, 2);
@@ -759,8 +758,7 @@ extern "C" int pllhip_likelihood_derivatives(pllhip_ctx_t * c, unsigned int slot
     // iteration from there: no streaming hint on its loads (the hint is for CLV-sized streams that
     // nothing will touch again)
     const size_t table_bytes = (size_t)c->sh.sites * R * S * sizeof(double);
-    bool nt = pllhip_use_nt(c) && table_bytes > ((size_t)128 << 20);
-    if (const char * e = pllhip_env("PLLHIP_DERIV_NT")) nt = atoi(e) != 0; // (measurements)
+    const bool nt = pllhip_use_nt(c) && table_bytes > ((size_t)128 << 20);
 #define DERIV_DNA(RCV)                                                        \
     do {                                                                      \
       if (nt) k_derivatives_dna<RCV, true><<<grid, 256, 0, c->stream>>>(a);   \

@@ -33,6 +33,9 @@
 #include "lnl_common.hpp"
 
 
+// the largest grid whose last-arriving workgroup finishes the sum itself (below)
+#define PLLHIP_FUSE_GRID_CAP 128u
+
 ReduceOut pllhip_reduce_out(pllhip_ctx * c, unsigned int grid, unsigned int ncomp, unsigned int block)
 {
   ReduceOut r;
@@ -46,19 +49,19 @@ ReduceOut pllhip_reduce_out(pllhip_ctx * c, unsigned int grid, unsigned int ncom
   r.extra = c->pending_extra; // set by the caller for exactly one launch
   c->pending_extra = nullptr;
   // The last-arriving workgroup finishes the sum in the same launch only for small grids
-  // (PLLHIP_FUSE_MAX_GRID workgroups, default 128; PLLHIP_FUSE_REDUCE=0/1 forces either way).  Measured
+  // (PLLHIP_FUSE_GRID_CAP workgroups; PLLHIP_FUSE_REDUCE=0/1 forces either way).  Measured
   // in round 3 with two levels of tickets (64 workgroups per counter, so that no counter serialises
   // thousands of atomics): every workgroup still ends with a write-through store, a wait for it and an
   // atomic round trip, and the finisher reads all partials past the L2 -- 45.8 us per derivative call
   // at 1954 workgroups against 33.9 us with the separate 6 us launch, 31.3 against 28.8 at 512
   // (tools/call_floor_ab.sh).  Small grids are latency-bound and save the launch.
-  r.fused = c->fuse_forced >= 0 ? c->fuse_forced : (grid <= c->fuse_max_grid ? 1 : 0);
+  r.fused = c->fuse_forced >= 0 ? c->fuse_forced : (grid <= PLLHIP_FUSE_GRID_CAP ? 1 : 0);
   // Round 5: small grids too hand their workgroup sums to the host when they can (below) -- a kernel of eight
   // workgroups spent its last microseconds on write-through stores, two ticket atomics, an acquire fence and the
   // finisher's reads: the edge lnL call of a 2,000-site partition 16.2 -> 12.6 us from C (tools/step_floor.c,
   // profiles/r5_step_floor_from_c.txt).  The host adds in the order the finishing workgroup used -- thread t of
   // `block` takes entries t, t + block, ...; then the tree -- so the bits are those of rounds 1-4.
-  const bool small = grid <= c->fuse_max_grid;
+  const bool small = grid <= PLLHIP_FUSE_GRID_CAP;
   const bool can_hostsum = !c->no_hostsum && !c->comm && !r.extra && (size_t)grid * ncomp <= PLLHIP_HOSTSUM_MAX;
   if (c->fuse_forced < 0 && small && can_hostsum) r.fused = 0;
   // Larger grids (round 4): the workgroup sums go straight to host-mapped memory and the host adds them -- in
@@ -1041,12 +1044,10 @@ static int run_lnl(pllhip_ctx * c, LnlArgs & a, int kind, double * h_persite, do
     // then walk several rounds each.  4 states: four workgroups per CU at most -- 1 M sites 54.7 -> 50.6 us for the
     // kernel and 64.9 -> 58.3 us for the call (a quarter of the sums for the host to wait for and add), 2 M sites 92 ->
     // 85 / 106 -> 95, 500 k 30.2 -> 27.5 / 39.1 -> 36.2, no difference at 8 M sites or below 250 k
-    // (profiles/r5_lnl_grid_cap_ab.txt).  PLLHIP_LNL_GRID: measurements.
+    // (profiles/r5_lnl_grid_cap_ab.txt).
     {
-      const char * e = pllhip_env("PLLHIP_LNL_GRID");
       unsigned int cap = (unsigned int)PLLHIP_HOSTSUM_MAX;
       if (s4 && (unsigned int)c->num_cus * 4u < cap) cap = (unsigned int)c->num_cus * 4u;
-      if (e && atoi(e) > 0) cap = (unsigned int)atoi(e);
       if (grid > cap) grid = cap;
     }
     a.reduce = pllhip_reduce_out(c, grid);

@@ -493,7 +493,6 @@ int pllhip_launch_lnl_aa_mfma(pllhip_ctx * c, LnlArgs & a, int kind, unsigned in
     case 4: return launch_lnl_rc<4>(c, a, kind, grid_out);
     default: break;
   }
-  if (!pllhip_aa_chunks_enabled()) return 1;
   if (a.rate_cats % 4 == 0) return launch_lnl_chunks<4>(c, a, kind, grid_out);
   if (a.rate_cats % 2 == 0) return launch_lnl_chunks<2>(c, a, kind, grid_out);
   return launch_lnl_chunks<1>(c, a, kind, grid_out);

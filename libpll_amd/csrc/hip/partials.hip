@@ -749,12 +749,11 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
   // tree gives one launch per tree level; a post-order list of a random 200-taxon
   // tree, where kinds alternate, gives 3 launches per level instead of one per run of
   // equal kinds (111 -> see DESIGN.md 2.1).
-  const bool no_batch = c->no_batch;
   const bool dna_fast = c->sh.states == 4 && fast_rc(c->sh.rate_cats);
   const bool aa_fast = c->sh.states == 20 && pllhip_aa_fast_covers(c, 0) &&
                        (!c->sh.pattern_tip || pllhip_aa_fast_covers(c, 2));
   const bool gen_fast = !dna_fast && !aa_fast && pllhip_gen_tile_covers(c);
-  const bool batchable = (dna_fast || aa_fast || gen_fast) && !no_batch;
+  const bool batchable = dna_fast || aa_fast || gen_fast;
   if (!batchable)
   {
     for (unsigned int i = 0; i < count; ++i)
@@ -775,13 +774,12 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
   // whole list vs per level: 8 k sites 74 vs 63 us, 16 k 78 vs 79, 24 k 84 vs 93, 33 k 100 vs 121,
   // 50 k 118 vs 164.  A property of the device -- tiles against SIMDs -- not a tuned number.)
   const size_t fused_tile_sites = (size_t)PLLHIP_FUSED_J * 64 / (2 * c->sh.rate_cats);
-  static const bool small_rule = !(pllhip_env("PLLHIP_FUSED_SMALL") && atoi(pllhip_env("PLLHIP_FUSED_SMALL")) == 0);
   const bool whole_list_kind = (dna_fast && (c->sh.rate_cats <= 4 || c->sh.rate_cats == 8)) || (aa_fast && c->sh.rate_cats == 4);
   // (asked only below the sizes from which the whole-list kernels always pay -- the two rules below, in THIS device's
   // compute units: 16,384 sites on an MI355X's 256; derived, not a constant of its own, so that no size falls
   // between the two rules on another part.  The cost constants of the estimate are this part's, measured.)
   const size_t always_pays_from = dna_fast ? fused_tile_sites * (size_t)c->num_cus * 4 : (size_t)32 * c->num_cus * 2;
-  const bool small_pays = small_rule && whole_list_kind && !c->no_fused && !c->force_fused && c->rows.empty() && count >= 2 &&
+  const bool small_pays = whole_list_kind && !c->no_fused && !c->force_fused && c->rows.empty() && count >= 2 &&
                           (size_t)c->sh.sites < always_pays_from && whole_list_pays_when_small(c, ops, count);
   const bool fused_pays = (size_t)c->sh.sites / fused_tile_sites >= (size_t)c->num_cus * 4 || c->force_fused || small_pays;
   // (8 rate categories: a tile is 8 sites, a P-matrix a whole 1 KB block per wave, a site's lanes a DPP row of 16.
@@ -817,10 +815,7 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
     // written together with their CLV -- runs per level.
     const FusedGeom geom = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
     // (PLLHIP_FUSED_WGS=2: the 8-wave, 7-slot configuration at once -- tests run both)
-    unsigned int first_wgs = pllhip_env("PLLHIP_FUSED_WGS") && atoi(pllhip_env("PLLHIP_FUSED_WGS")) == 2 ? 2u : 3u;
-#ifdef PLLHIP_FUSED_WPS4
-    if (pllhip_env("PLLHIP_FUSED_WGS") && atoi(pllhip_env("PLLHIP_FUSED_WGS")) == 4) first_wgs = 4u; // (tool build)
-#endif
+    const unsigned int first_wgs = pllhip_env("PLLHIP_FUSED_WGS") && atoi(pllhip_env("PLLHIP_FUSED_WGS")) == 2 ? 2u : 3u;
     // Round 5: independent sub-lists (the two sides of the root edge of a full traversal) as SEGMENTS of one launch
     // -- (tile, segment) work items -- while the tiles alone do not fill the chip's wave slots eight times over:
     // below that a launch's time is quantised by rounds of the list's length (partials_fused.hpp).

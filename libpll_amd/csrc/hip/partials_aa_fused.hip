@@ -109,11 +109,6 @@ constexpr unsigned int AF_LAST = 8192u;
 // the threshold (partials_aa_fused_op.inc); the segment's HEADER record carries what the rare path needs -- `parent`:
 // the address of the call's flag word (host memory), `pscaler`: the window as a double, 2^-256 x its relative half-width
 constexpr unsigned int AF_CERT = 32768u;
-// (round 6) a value that a later op of the SAME list copies back from HBM (the planner gave its slot away): stored with
-// the default cache policy instead of the non-temporal one, so that the copy -- which the reading op waits for with
-// everything else in flight -- comes out of L2 / the memory-side cache a few ops later instead of out of DRAM behind
-// the write stream (profiles/r6_replay_counters_c3.txt: a list with three such copies sees twice the read latency)
-constexpr unsigned int AF_KEEP = 65536u;
 constexpr unsigned int AF_NEXT_SHIFT = 17u;
 
 struct AfMatJob
@@ -258,7 +253,7 @@ __global__ __launch_bounds__(256) void k_af_prepare(const AfMatJob * __restrict_
     // A tip-tip op's pair table: row (c1 ms + c2) = left factor of c1 (.) right factor of c2 -- the two masked row
     // sums of k_aa_tip_tables / the branch above and the ONE multiplication of k_aa_tt_rounds (a masked sum = the
     // row's selected entries added in ascending order; adding +0.0 for the others changes no bit).
-    // Round 6, third form (profiles/r6_aa_prepare_ab.txt; tools/aa_prepare_parts.sh says what each kind of job costs):
+    // Round 6, third form (profiles/r6_aa_prepare_ab.txt, which also says what each kind of job costs):
     // a workgroup per (op, first character) that pulled its rows of both matrices straight into registers was bound
     // by those loads -- a lane per row is sixty-four cache lines per instruction, 23 workgroups per op each fetching
     // all of it.  Now AF_PAIR_WGS workgroups per op, each a range of first characters: the right matrix comes ONCE,
@@ -366,16 +361,6 @@ __global__ __launch_bounds__(256) void k_af_prepare(const AfMatJob * __restrict_
   }
 }
 
-#ifdef PLLHIP_AF_TIMING
-// (tool build: PLLHIP_AF_EXP=mask switches parts of the kernel off -- wrong results, for timing only:
-// 1 no matrix-core products, 2 no stores, 4 no gathers, 8 no block staging, 16 no barriers, 32 no wait for the
-// operands copied back from HBM, 64 no such copies at all)
-__device__ unsigned int af_exp_mask;
-#define AF_EXP(bit) (exp_mask & (bit))
-#else
-#define AF_EXP(bit) false
-#endif
-
 // ---- device helpers
 typedef const unsigned int __attribute__((address_space(4))) * af_words;
 // words [FIRST, FIRST + N) of record i, through the scalar cache
@@ -416,21 +401,14 @@ __device__ __forceinline__ af_gptr af_base(unsigned long long uniform_address)
 // M0 (the LDS address of an LDS-DMA) is a register the compiler reserves for itself, so an asm block may not simply
 // declare it clobbered: it is saved and put back around every run of DMA instructions -- two scalar instructions per
 // run, ~30 of the ~165 a wave executes per op.  The compiler never reads M0 in these kernels (tools/check_agprs.py
-// looks: no instruction outside these blocks mentions m0), so the assembly could simply OWN it
-// (-DPLLHIP_AF_SAVE_M0=0).  Measured late in round 4, three interleaved pairs on one box: C3 1.713-1.724 against
-// 1.710-1.713 ms, 200-taxon random tree 3.989 against 3.981 -- the scalar unit is not on the waves' critical path;
-// not worth leaning on a reserved register: the default saves.
-#ifndef PLLHIP_AF_PIPE
-#define PLLHIP_AF_PIPE 0
-#endif
-#ifndef PLLHIP_AF_SAVE_M0
-#define PLLHIP_AF_SAVE_M0 1
-#endif
+// looks: no instruction outside these blocks mentions m0), so the assembly could simply OWN it.  Measured late in
+// round 4 (a build that did), three interleaved pairs on one box: C3 1.713-1.724 against 1.710-1.713 ms, 200-taxon
+// random tree 3.989 against 3.981 -- the scalar unit is not on the waves' critical path; not worth leaning on a
+// reserved register: the assembly saves.
 template <int N>
 __device__ __forceinline__ void af_dma_run(unsigned int lds_b, unsigned long long uniform_src, unsigned int lane16)
 {
   static_assert(N == 1 || N == 4, "immediate offsets reach 4095");
-#if PLLHIP_AF_SAVE_M0
   unsigned int m0_saved;
   if (N == 1)
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
@@ -440,16 +418,6 @@ __device__ __forceinline__ void af_dma_run(unsigned int lds_b, unsigned long lon
                  "global_load_lds_dwordx4 %2, %3 offset:1024\n\tglobal_load_lds_dwordx4 %2, %3 offset:2048\n\t"
                  "global_load_lds_dwordx4 %2, %3 offset:3072\n\ts_mov_b32 m0, %0"
                  : "=&s"(m0_saved) : "s"(lds_b), "v"(lane16), "s"(uniform_src) : "memory");
-#else
-  if (N == 1)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                 : : "s"(lds_b), "v"(lane16), "s"(uniform_src) : "memory");
-  else
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:3072"
-                 : : "s"(lds_b), "v"(lane16), "s"(uniform_src) : "memory");
-#endif
 }
 // a gather: five KiB of LDS from five lane offsets each (voff[it] relative to table); the first four
 // share an M0 -- the immediate offset that advances the LDS address advances the global one as well,
@@ -457,7 +425,6 @@ __device__ __forceinline__ void af_dma_run(unsigned int lds_b, unsigned long lon
 __device__ __forceinline__ void af_dma_gather5(unsigned int lds_b, unsigned long long table, const unsigned int (&voff)[5])
 {
   const unsigned int v0 = voff[0] + 3072u, v1 = voff[1] + 2048u, v2 = voff[2] + 1024u;
-#if PLLHIP_AF_SAVE_M0
   unsigned int m0_saved;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %8\n\t"
                "global_load_lds_dwordx4 %4, %8 offset:1024\n\tglobal_load_lds_dwordx4 %5, %8 offset:2048\n\t"
@@ -466,15 +433,6 @@ __device__ __forceinline__ void af_dma_gather5(unsigned int lds_b, unsigned long
                : "=&s"(m0_saved)
                : "s"(lds_b), "s"(lds_b + 4096u), "v"(v0), "v"(v1), "v"(v2), "v"(voff[3]), "v"(voff[4]), "s"(table - 3072ull), "s"(table)
                : "memory");
-#else
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %7\n\t"
-               "global_load_lds_dwordx4 %3, %7 offset:1024\n\tglobal_load_lds_dwordx4 %4, %7 offset:2048\n\t"
-               "global_load_lds_dwordx4 %5, %7 offset:3072\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-               "global_load_lds_dwordx4 %6, %8"
-               :
-               : "s"(lds_b), "s"(lds_b + 4096u), "v"(v0), "v"(v1), "v"(v2), "v"(voff[3]), "v"(voff[4]), "s"(table - 3072ull), "s"(table)
-               : "memory");
-#endif
 }
 
 struct AfSlot
@@ -554,23 +512,6 @@ __device__ __forceinline__ void af_matvec(const char * mat_lane, const char * ma
   // operands of group t + 1 ahead of the MFMAs of group t and deferred the sums -- worth 1 % then, and 32 registers,
   // which the column tail and the wider fifth-step operands need now: the kernel must stay within 128, see the slots.)
   double c5[AF_J][4];
-#if (PLLHIP_AF_PIPE & 1)
-  // (round 5, PLLHIP_AF_PIPE bit 0: the A operands of row group t + 1 requested before the eight MFMAs of group t are
-  // issued -- with eight MFMAs per group instead of round 3's sixteen the LDS round trip is a third of a group's time)
-  AfAops a_cur, a_nxt;
-  af_fetch_a(mat_lane, mat_cls, 0, a_cur);
-  af_column_tail(b, lane, c5);
-#pragma unroll
-  for (int t = 0; t < 5; ++t)
-  {
-    double acc[AF_J][4];
-    if (t < 4) af_fetch_a(mat_lane, mat_cls, t + 1, a_nxt);
-    af_group(a_cur, b, c5, acc);
-    af_sum<MUL>(acc, t, x);
-    if (t < 4) a_cur = a_nxt;
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#else
   af_column_tail(b, lane, c5);
 #pragma unroll
   for (int t = 0; t < 5; ++t)
@@ -582,7 +523,6 @@ __device__ __forceinline__ void af_matvec(const char * mat_lane, const char * ma
     af_sum<MUL>(acc, t, x);
     __builtin_amdgcn_sched_barrier(0);
   }
-#endif
 }
 
 // x[j][t] = tip factor * (P . column)[state 4q + t | 16 + q] in the order of the reference's TIP-INNER kernel
@@ -783,9 +723,7 @@ static_assert(AF_J == 2 && AF_NSLOT == 5, "the slot macros spell out two sub-til
 // segment 0 first.  A workgroup that moves on to another segment starts cold -- everybody done with the blocks in
 // LDS, the new segment's first blocks requested -- which the segment-major order makes a once-per-launch event.
 // segtab: [segment] = {first record, ops}.
-// NT: 0 plain stores, 1 the tiles non-temporal, 2 non-temporal except the values a later op of the list copies back
-// (AF_KEEP).  An instance of its own: the branch around every store cost a list WITHOUT such values 3.5 % when all
-// non-temporal lists ran through it (config 3: 1,710 -> 1,767 us per call, profiles/r6_aa_keep_instance_ab.txt).
+// NT: 0 plain stores, 1 the tiles non-temporal.
 template <int MODE, int NT>
 __global__ __launch_bounds__(256, 2) void k_aa_fused(const AaRec * __restrict__ plan0, const unsigned int * __restrict__ segtab,
                                                      unsigned int nsegs, unsigned int sites,
@@ -828,13 +766,8 @@ __global__ __launch_bounds__(256, 2) void k_aa_fused(const AaRec * __restrict__ 
   const unsigned long long sink_a = (unsigned long long)(uintptr_t)(sink + ((size_t)blockIdx.x * 4u + wave) * 8u); // (128 bytes per wave)
   const unsigned long long aorder_a = (unsigned long long)(uintptr_t)aorder;
 
-
-#ifdef PLLHIP_AF_TIMING
-  const unsigned int exp_mask = __builtin_amdgcn_readfirstlane(af_exp_mask);
-#endif
   // a matrix block into LDS: 13 pieces of 1 KB over the four waves
   auto stage_matrix = [&](unsigned int buf_b, unsigned int off) __attribute__((always_inline)) {
-    if (AF_EXP(8u)) return;
     // (waves 0..2 four consecutive pieces each, wave 3 the thirteenth)
     const unsigned int w4 = wave * 4096u;
     if (wave < 3u) af_dma_run<4>(buf_b + w4, aorder_a + off + w4, lane16);
@@ -891,7 +824,6 @@ __global__ __launch_bounds__(256, 2) void k_aa_fused(const AaRec * __restrict__ 
 
     // an operand without a slot: from HBM through stage 1 into a slot (AF_RELOAD_TAKE)
     auto reload_issue = [&](unsigned long long src) __attribute__((always_inline)) {
-      if (AF_EXP(64u)) return; // (tool build, bit 64: nothing is copied back at all)
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // (the stage's last readers are done)
       af_dma_run<4>(st1_b, src + clv_off, lane16);
       af_dma_run<1>(st1_b + 4096u, src + clv_off + 4096u, lane16);
@@ -903,14 +835,14 @@ __global__ __launch_bounds__(256, 2) void k_aa_fused(const AaRec * __restrict__ 
         cj[j] = 0u;
         unsigned int o = MODE == SCALE_RATE ? ((4u * j + n) * 4u + rate) * 4u : (4u * j + n) * 4u;
         asm volatile("" : "+v"(o));
-        if (MODE != SCALE_NONE && cnt && !AF_EXP(64u)) cj[j] = *(const unsigned int PLL_GLOBAL *)(af_base(cnt + cnt_off) + o);
+        if (MODE != SCALE_NONE && cnt) cj[j] = *(const unsigned int PLL_GLOBAL *)(af_base(cnt + cnt_off) + o);
       }
     };
     // (a macro, not a lambda: a lambda would capture the slot variables by reference, and
     // variables whose address is taken anywhere stay in memory)
 #define AF_RELOAD_TAKE(slot, cj)                                   \
   {                                                                \
-    if (!AF_EXP(32u | 64u)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* (tool build, bit 32: no wait for a reload) */ \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               \
     AfSlot tmp;                                                    \
     af_read_tile(st1 + boff, st1 + boff5, tmp.v);                  \
     tmp.c[0] = cj[0];                                              \
@@ -966,7 +898,6 @@ __global__ __launch_bounds__(256, 2) void k_aa_fused(const AaRec * __restrict__ 
     // table entries -- LDS-DMA with one address per lane, straight into the two stages in the
     // layout of the stores --, a tip-inner op the tip's factor (a row of its table per site, into stage 1)
     auto next_gathers = [&](unsigned int nkind, bool one_table, unsigned long long tab_l, unsigned long long tab_r, unsigned int chars) __attribute__((always_inline)) {
-      if (AF_EXP(4u)) return;
       unsigned int o[5];
       if (nkind == 2u)
       {
@@ -1028,19 +959,6 @@ __global__ __launch_bounds__(256, 2) void k_aa_fused(const AaRec * __restrict__ 
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
-#ifdef PLLHIP_AF_TIMING
-    // (tool build, tools/aa_fused_timing.sh: where a wave's cycles go, by op kind and phase)
-    unsigned long long phase_cycles[3][11] = {};
-    unsigned int nkind_ops[3] = {};
-    unsigned long long t_last = __builtin_readcyclecounter();
-#ifdef PLLHIP_AF_NOTICKS
-#define AF_TICK(ph)
-#else
-#define AF_TICK(ph) { const unsigned long long t_now = __builtin_readcyclecounter(); phase_cycles[kind][ph] += t_now - t_last; t_last = t_now; }
-#endif
-#else
-#define AF_TICK(ph)
-#endif
     bool af_last;
     for (;;)
     {
@@ -1065,16 +983,6 @@ __global__ __launch_bounds__(256, 2) void k_aa_fused(const AaRec * __restrict__ 
 #undef AF_CH_USE
       if (af_last) break;
     }
-#if defined(PLLHIP_AF_TIMING) && !defined(PLLHIP_AF_NOTICKS)
-    if (lane == 0 && round == 2 && wave == 1 && (blockIdx.x == 0 || blockIdx.x == 101 || blockIdx.x == 202 || blockIdx.x == 303))
-      for (int kd = 0; kd < 3; ++kd)
-        if (nkind_ops[kd])
-          printf("kind %d: %u ops: first half %llu, wait A %llu, barrier A %llu, [slot read %llu, products %llu] rest of second half %llu, barrier B %llu, "
-                 "[lds wait %llu, blocks %llu, gathers %llu] characters + stores %llu cycles per op\n",
-                 kd, nkind_ops[kd], phase_cycles[kd][0] / nkind_ops[kd], phase_cycles[kd][1] / nkind_ops[kd], phase_cycles[kd][2] / nkind_ops[kd],
-                 phase_cycles[kd][6] / nkind_ops[kd], phase_cycles[kd][7] / nkind_ops[kd], phase_cycles[kd][3] / nkind_ops[kd], phase_cycles[kd][4] / nkind_ops[kd],
-                 phase_cycles[kd][8] / nkind_ops[kd], phase_cycles[kd][9] / nkind_ops[kd], phase_cycles[kd][10] / nkind_ops[kd], phase_cycles[kd][5] / nkind_ops[kd]);
-#endif
   }
 }
 } // namespace
@@ -1104,7 +1012,7 @@ struct pllhip_aa_fused_cache
   char * d_pairtab = nullptr;          // pair tables of the list's tip-tip ops (AfPairJob)
   size_t pairtab_cap = 0, off_pair = 0;
   unsigned int npair = 0;
-  size_t off_lk = 0;                   // lookup-table jobs (AaLookupJob; nlk == 0: the tables come from launches of their own)
+  size_t off_lk = 0;                   // lookup-table jobs (AaLookupJob)
   unsigned int nlk = 0;
   size_t off_seg = 0;                  // (round 5) the segment table: {first record, ops} per segment
   unsigned int nsegs = 1;
@@ -1118,7 +1026,6 @@ struct pllhip_aa_fused_cache
   // tip-tip in the list, lookups, inner-inner on the matrix cores, tip-inner on the matrix cores, tip-inner on the
   // vector unit, operands reloaded
   unsigned int kinds_of_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  bool any_keep = false; // some op's value is copied back by a later op of the list (AF_KEEP): the kernel instance that looks
 };
 
 void pllhip_aa_fused_free(pllhip_ctx * c)
@@ -1136,7 +1043,7 @@ void pllhip_aa_fused_free(pllhip_ctx * c)
 }
 
 // everything the kept plan describes, again: tip-tip ops, tables, matrices in operand order, the list
-static int aa_fused_launch(pllhip_ctx * c, bool tables_built)
+static int aa_fused_launch(pllhip_ctx * c)
 {
   pllhip_aa_fused_cache & k = *c->aa_fused;
   // tip-tip ops of one scaling mode per launch, PLLHIP_BATCH_MAX at a time
@@ -1149,26 +1056,13 @@ static int aa_fused_launch(pllhip_ctx * c, bool tables_built)
     const int rc = pllhip_launch_aa_batch(c, b, nb, 2, mode);
     if (rc) return rc;
   }
-  if (!k.lk_ops.empty() && !tables_built && !k.nlk)
-  {
-    // (same pool, same places: the records' addresses hold while the epoch does)
-    std::vector<AaLookupTables> tabs(k.lk_ops.size());
-    const int rc = pllhip_aa_lookup_tables(c, k.lk_ops.data(), k.lk_k1.data(), k.lk_k2.data(),
-                                           (unsigned int)k.lk_ops.size(), tabs.data());
-    if (rc) return rc;
-  }
   const char * plan = static_cast<const char *>(k.d_plan);
   if (k.nmat + k.ntip + k.npair + k.nlk)
   {
-    // (tool switch, wrong results: PLLHIP_AF_PREP_SKIP = 1 no matrix jobs | 2 no tip tables | 4 no pair tables |
-    // 8 no lookup tables -- what each kind of job costs the launch, tools/aa_prepare_ab.sh)
-    const unsigned int skip = pllhip_env("PLLHIP_AF_PREP_SKIP") ? (unsigned int)atoi(pllhip_env("PLLHIP_AF_PREP_SKIP")) : 0u;
-    const unsigned int nmat = (skip & 1u) ? 0u : k.nmat, ntip = (skip & 2u) ? 0u : k.ntip;
-    const unsigned int npair = (skip & 4u) ? 0u : k.npair, nlk = (skip & 8u) ? 0u : k.nlk;
-    k_af_prepare<<<std::max(1u, nmat + ntip + npair * AF_PAIR_WGS + nlk * c->maxstates), 256, 0, c->stream>>>(
-        (const AfMatJob *)(plan + k.off_mat), nmat, (const AfTipJob *)(plan + k.off_tip), ntip, k.d_aorder,
-        k.d_titab, c->tipmap, c->maxstates, c->d_tile_counter, (const AfPairJob *)(plan + k.off_pair), npair,
-        k.d_pairtab, (const AaLookupJob *)(plan + k.off_lk), nlk);
+    k_af_prepare<<<std::max(1u, k.nmat + k.ntip + k.npair * AF_PAIR_WGS + k.nlk * c->maxstates), 256, 0, c->stream>>>(
+        (const AfMatJob *)(plan + k.off_mat), k.nmat, (const AfTipJob *)(plan + k.off_tip), k.ntip, k.d_aorder,
+        k.d_titab, c->tipmap, c->maxstates, c->d_tile_counter, (const AfPairJob *)(plan + k.off_pair), k.npair,
+        k.d_pairtab, (const AaLookupJob *)(plan + k.off_lk), k.nlk);
     HIP_TRY(hipGetLastError());
   }
   else HIP_TRY(hipMemsetAsync(c->d_tile_counter, 0, sizeof(unsigned int), c->stream));
@@ -1177,16 +1071,8 @@ static int aa_fused_launch(pllhip_ctx * c, bool tables_built)
   const size_t cap = pllhip_env("PLLHIP_AA_GRID_CAP") ? (size_t)atoi(pllhip_env("PLLHIP_AA_GRID_CAP")) : (size_t)c->num_cus * 2; // (tests: many tiles per workgroup)
   if (grid > cap) grid = cap;
   const size_t rounds = tiles / grid;
-  const unsigned int dynamic_rounds = pllhip_env("PLLHIP_FUSED_DYNAMIC_ROUNDS") ? (unsigned int)atoi(pllhip_env("PLLHIP_FUSED_DYNAMIC_ROUNDS"))
-                                                                            : (unsigned int)std::max<size_t>(2, rounds / 3);
+  const unsigned int dynamic_rounds = (unsigned int)std::max<size_t>(2, rounds / 3);
   const unsigned int static_rounds = rounds > dynamic_rounds ? (unsigned int)(rounds - dynamic_rounds) : 1u;
-  unsigned int * counter = pllhip_env("PLLHIP_FUSED_STATIC_TILES") ? nullptr : c->d_tile_counter;
-#ifdef PLLHIP_AF_TIMING
-  {
-    const unsigned int m = pllhip_env("PLLHIP_AF_EXP") ? (unsigned int)atoi(pllhip_env("PLLHIP_AF_EXP")) : 0u;
-    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(af_exp_mask), &m, sizeof(m), 0, hipMemcpyHostToDevice, c->stream));
-  }
-#endif
   const bool nt = pllhip_use_nt(c);
 #define AF_LAUNCH(MODEV, NTV)                                                                                          \
   do {                                                                                                                 \
@@ -1194,15 +1080,12 @@ static int aa_fused_launch(pllhip_ctx * c, bool tables_built)
                                 hipFuncAttributeMaxDynamicSharedMemorySize, AF_LDS_B));                                \
     k_aa_fused<MODEV, NTV><<<(unsigned int)grid, 256, AF_LDS_B, c->stream>>>(                                          \
         (const AaRec *)k.d_plan, (const unsigned int *)(plan + k.off_seg), k.nsegs, c->sh.sites, k.d_aorder,           \
-        c->maxstates, (double2 *)c->d_sink, counter, static_rounds);                                                   \
+        c->maxstates, (double2 *)c->d_sink, c->d_tile_counter, static_rounds);                                                   \
   } while (0)
-  // (tool switch: every non-temporal list through the instance that looks for AF_KEEP, profiles/r6_aa_keep_instance_ab.txt)
-  const bool force_keep_instance = pllhip_env("PLLHIP_AA_KEEP_INSTANCE") && atoi(pllhip_env("PLLHIP_AA_KEEP_INSTANCE")) != 0;
 #define AF_LAUNCH_MODE(MODEV)                                                                                          \
   do {                                                                                                                 \
     if (!nt) AF_LAUNCH(MODEV, 0);                                                                                      \
-    else if (!k.any_keep && !force_keep_instance) AF_LAUNCH(MODEV, 1);                                                 \
-    else AF_LAUNCH(MODEV, 2);                                                                                          \
+    else AF_LAUNCH(MODEV, 1);                                                                                          \
   } while (0)
   if (k.mode == SCALE_NONE) AF_LAUNCH_MODE(SCALE_NONE);
   else if (k.mode == SCALE_RATE) AF_LAUNCH_MODE(SCALE_RATE);
@@ -1269,7 +1152,7 @@ static int aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int
   // Tip-inner mat-vecs on the matrix cores (the default, round 6) -- unless the list is being run again after its
   // certificate tripped, or could not be run again: a list that overwrites an operand it has read from an earlier
   // call (slot reuse across calls) is not idempotent, and keeps to the reference's order.
-  const bool ti_mfma = c->aa_ti_mfma && !c->cert_force_exact && !c->no_batch;
+  const bool ti_mfma = c->aa_ti_mfma && !c->cert_force_exact;
   if (k.last_ops.size() == count && k.epoch == c->layout_epoch && k.maxstates == c->maxstates && k.ti_mfma == ti_mfma &&
       !c->fused_debug && memcmp(k.last_ops.data(), ops, (size_t)count * sizeof(pllhip_op_t)) == 0)
   {
@@ -1278,7 +1161,7 @@ static int aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int
     if (same_marks)
     {
       if (k.cert_kind == 1) c->cert_ops.assign(ops, ops + count);
-      return aa_fused_launch(c, false);
+      return aa_fused_launch(c);
     }
   }
   k.last_ops.clear();
@@ -1417,7 +1300,6 @@ static int aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int
   std::vector<PartialsArgs> rargs;
   std::vector<int> rkinds, orig;
   k.tt_ops.clear();
-  k.any_keep = false;
   k.tt_modes.clear();
   for (int pass = 0; pass < 2; ++pass) // (tip-tip ops grouped by mode: without a scale buffer first)
     for (unsigned int i = 0; i < count; ++i)
@@ -1517,14 +1399,13 @@ static int aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int
   }
   // the lookup tables' addresses are needed in the records: build them now (their pool may move)
   std::vector<AaLookupTables> tabs(k.lk_ops.size());
-  // (round 4: the tables are made by k_af_prepare, AaLookupJob; PLLHIP_AA_LOOKUP_DIRECT=0: by launches of the
-  // tabulating kernels ahead of it, as in round 3)
-  const bool lk_direct = !(pllhip_env("PLLHIP_AA_LOOKUP_DIRECT") && atoi(pllhip_env("PLLHIP_AA_LOOKUP_DIRECT")) == 0);
-  std::vector<AaLookupJob> lj(lk_direct ? 2 * k.lk_ops.size() : 0);
+  // (round 4: the tables are made by k_af_prepare, AaLookupJob; in round 3 by launches of the tabulating kernels
+  // ahead of it)
+  std::vector<AaLookupJob> lj(2 * k.lk_ops.size());
   if (!k.lk_ops.empty())
   {
     rc = pllhip_aa_lookup_tables(c, k.lk_ops.data(), k.lk_k1.data(), k.lk_k2.data(), (unsigned int)k.lk_ops.size(),
-                                 tabs.data(), lk_direct ? lj.data() : nullptr);
+                                 tabs.data(), lj.data());
     // (the pool could not be allocated: once more, now without lookup ops -- the context remembers)
     if (rc == 1 && c->cherry_pool_failed) return aa_fused_update(c, ops, count, tt_wanted);
     if (rc) return rc;
@@ -1648,22 +1529,6 @@ static int aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int
     }
     if (pos + 1 < m) reloads_of(r, fplan[first + pos + 1]);
   }
-  // (opt-in since the end of round 6, PLLHIP_AA_KEEP=1: with the planner's walk fixed hardly a list copies a value of its
-  // own back any more -- one of 398 ops of a 400-taxon random tree -- and the kernel instance that looks for such values
-  // costs a list 1.9 %: 3,727-3,751 us with it against 3,686-3,692 without, profiles/r6_aa_keep_instance_ab.txt)
-  if (pllhip_env("PLLHIP_AA_KEEP") && atoi(pllhip_env("PLLHIP_AA_KEEP")) != 0)
-    for (unsigned int pos = 0; pos < m; ++pos)
-    {
-      // (the writer of a value that op `pos` reloads, if it is an earlier op of this segment)
-      const FusedOp & f = fplan[first + pos];
-      for (const double * src : {(f.dma_flags & 1) ? f.left_hbm : nullptr, (f.dma_flags & 2) ? f.right_hbm : nullptr})
-        for (unsigned int w = 0; src && w < pos; ++w)
-          if (fplan[first + w].parent == src)
-          {
-            R[w + 1].flags |= AF_KEEP;
-            k.any_keep = true;
-          }
-    }
   // The left block of op i is staged by the four waves, a part each, while they run op i - 2, and the barrier that
   // tells a wave that everybody's part has landed is barrier A of op i - 1 -- which a lookup does not have.  Until
   // the tip-tip ops joined the list (runs of tens of barrier-free ops, over which the waves drift apart by whole
@@ -1790,7 +1655,7 @@ static int aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int
             (size_t)n - k.lk_ops.size() - tt_inside_rec.size() - tt_pair_rec.size(), synced, reloads, nsegs);
   }
   lap("encode + upload");
-  rc = aa_fused_launch(c, true);
+  rc = aa_fused_launch(c);
   if (rc) return rc;
   lap("launches");
   k.last_ops.assign(ops, ops + count);

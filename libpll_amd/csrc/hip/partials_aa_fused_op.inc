@@ -57,12 +57,8 @@
     AF_SLOT_READ(slots & 15u, l)
 #pragma unroll
     for (int j = 0; j < AF_J; ++j) lc[j] = l.c[j];
-    if (!AF_EXP(1u))
-    {
-      const unsigned int lm = lane_again();
-      af_matvec<false>(xlane, xlane - lm * 8u + cls32_of(lm), lm, l.v, x);
-    }
-    else { for (int j = 0; j < AF_J; ++j) for (int t = 0; t < 5; ++t) x[j][t] = l.v[j][t]; }
+    const unsigned int lm = lane_again();
+    af_matvec<false>(xlane, xlane - lm * 8u + cls32_of(lm), lm, l.v, x);
   }
   else
   {
@@ -74,18 +70,15 @@
       for (int t = 0; t < 5; ++t) x[j][t] = 0.0;
   }
   if ((fl & AF_RELOAD_A) && kind == 0u) AF_RELOAD_TAKE((slots >> 12) & 15u, ra_cj)
-  AF_TICK(0)
 
   // ---- barrier A: all but my six stores have arrived (the right block with them, and a tip's factor)
-  if ((fl & AF_RELOAD_A) && kind == 0u && !AF_EXP(32u | 64u)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if ((fl & AF_RELOAD_A) && kind == 0u) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-  AF_TICK(1)
   // (a lookup multiplies by no block: it needs neither barrier and the waves may drift apart over
   // it -- which also keeps their requests from colliding.  What it requests for the ops ahead goes to
   // buffers whose last readers were through before a barrier every wave has passed.)
-  if (kind <= 1u && !AF_EXP(16u)) __builtin_amdgcn_s_barrier();
+  if (kind <= 1u) __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  AF_TICK(2)
   // the left block of op i + 2 into this op's left buffer, which everybody is done with: requested here,
   // not with the rest at the end -- the waves of a workgroup run in lock-step and their requests collide
   {
@@ -121,9 +114,7 @@
       AF_SLOT_READ((slots >> 4) & 15u, r)
 #pragma unroll
       for (int j = 0; j < AF_J; ++j) rcn[j] = r.c[j];
-      AF_TICK(6)
-      if (AF_EXP(1u)) {}
-      else if (kind == 1u && !(fl & AF_TI_MFMA))
+      if (kind == 1u && !(fl & AF_TI_MFMA))
       {
         // (yrows: the right block in row order, the lane's class x 16 bytes)
         const unsigned int lm = lane_again();
@@ -137,7 +128,6 @@
         const unsigned int lm = lane_again();
         af_matvec<true>(ylane, ylane - lm * 8u + cls32_of(lm), lm, r.v, x);
       }
-      AF_TICK(7)
     }
     // Round 6, the scaling certificate (AF_CERT: an op whose value may carry the matrix cores' rounding of a tip-inner
     // mat-vec from further down the tree -- 1e-15 relative per op -- and whose scaling decision must nevertheless be the
@@ -326,35 +316,20 @@
     }
   }
   if (fl & AF_RELOAD_B) AF_RELOAD_TAKE((slots >> 16) & 15u, rb_cj)
-  AF_TICK(3)
 
   // ---- barrier B: everybody is done with the right block (and with this op's left block)
-  if (kind <= 1u && !AF_EXP(16u)) __builtin_amdgcn_s_barrier();
+  if (kind <= 1u) __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  AF_TICK(4)
 
   // ---- requests for the ops ahead, all of them BEFORE this op's stores
   {
     const unsigned int nfl = __builtin_amdgcn_readfirstlane(AF_RN[18]);
     const unsigned int nkind = nfl & AF_KIND_MASK;
-#if (PLLHIP_AF_PIPE & 2)
-    // (round 5, PLLHIP_AF_PIPE bit 1: the next right block -- into the block buffer, which barrier B has just freed
-    // -- is requested BEFORE the wait for the stages' last readers: the tile's five reads out of stage 0 have only
-    // just been issued, and the block request does not touch a stage)
-    if (nkind <= 1u) stage_matrix(ybuf_b, AF_RN[17]);
-    AF_TICK(9)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    AF_TICK(8)
-#else
     // (the stages are free: their readers are done)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    AF_TICK(8)
     if (nkind <= 1u) stage_matrix(ybuf_b, AF_RN[17]);
-    AF_TICK(9)
-#endif
     // what op i + 1 gathers -- unless it belongs to the next tile (other sites: the prologue does it)
     if (!last && !early_gather) next_gathers(nkind, (nfl & AF_ONE_TABLE) != 0u, AF_RN.quad(4), AF_RN.quad(6), AF_CH_USE);
-    AF_TICK(10)
   }
   asm volatile("" ::: "memory");
   // the six stores (always six: barrier A of the next op counts on it): the counts -- to the wave's sink
@@ -383,38 +358,16 @@
     if (lane < (MODE == SCALE_RATE ? 4u : 1u) * (unsigned int)AF_WS) *(unsigned int PLL_GLOBAL *)(cdst + lane4) = mine;
     asm volatile("" ::: "memory");
     const af_gptr out = af_base(AF_RC.quad(0) + clv_off);
-    // (AF_KEEP, a value that a later op of this list copies back: the default cache policy.  In assembly: written as
-    // "if (keep) *dst = v; else nontemporal_store(v, dst)" the two stores are merged into ONE by the optimiser, which
-    // drops the non-temporal hint from all of them -- seen: no `nt` store left in the kernel, C3 1.70 -> 2.56 ms.  One
-    // branch per op, around the five stores, and only in the instance such lists run: NT == 2.)
-    if (NT == 2 && (fl & AF_KEEP))
-    {
 #pragma unroll
-      for (unsigned int it = 0; it < 5; ++it)
-      {
-        if (AF_EXP(2u)) break;
-        const pll_v2d v = {g[it].x, g[it].y};
-        asm volatile("global_store_dwordx4 %0, %1, %2" : : "v"(lane16s + it * 1024u), "v"(v), "s"(out) : "memory");
-      }
-    }
-    else
+    for (unsigned int it = 0; it < 5; ++it)
     {
-#pragma unroll
-      for (unsigned int it = 0; it < 5; ++it)
-      {
-        if (AF_EXP(2u)) break;
-        const pll_v2d v = {g[it].x, g[it].y};
-        pll_v2d PLL_GLOBAL * dst = (pll_v2d PLL_GLOBAL *)(out + (lane16s + it * 1024u));
-        if (NT) __builtin_nontemporal_store(v, dst);
-        else *dst = v;
-        asm volatile("" ::: "memory");
-      }
+      const pll_v2d v = {g[it].x, g[it].y};
+      pll_v2d PLL_GLOBAL * dst = (pll_v2d PLL_GLOBAL *)(out + (lane16s + it * 1024u));
+      if (NT) __builtin_nontemporal_store(v, dst);
+      else *dst = v;
+      asm volatile("" ::: "memory");
     }
   }
   xpar ^= 1u;
   af_last = last;
-  AF_TICK(5)
-#ifdef PLLHIP_AF_TIMING
-  nkind_ops[kind]++;
-#endif
 }

@@ -325,7 +325,6 @@ __global__ __launch_bounds__(256, 2) void k_aa_ii_mfma(PartialsBatch batch)
     // the matrix cores' rounding of a tip-inner op of the whole-list kernel; then a decision is the reference's for
     // certain only while no block's largest entry lies within rounding distance of the threshold.  Two integer
     // instructions on the high word per category (a window of 2^-20); the exact window only behind that.
-#ifndef PLLHIP_NO_II_CERT /* (tool build: what the test costs a launch that does not need it) */
     if (MODE != SCALE_NONE && SPLIT == 0 && a.cert)
     {
       bool wide = false, inside = false;
@@ -340,7 +339,6 @@ __global__ __launch_bounds__(256, 2) void k_aa_ii_mfma(PartialsBatch batch)
       if (__ballot(wide))
         if (__ballot(inside && site0 + s < sites) && lane == 0u) *a.cert = 1u;
     }
-#endif
     if (MODE == SCALE_SITE && (SPLIT == 1 || SPLIT == 3))
     {
       // not the last chunk of the categories: no decision yet -- the verdict so far goes to the verdict buffer (the
@@ -668,21 +666,12 @@ __global__ __launch_bounds__(256) void k_aa_cherry_rounds(CherryBatch batch)
   }
 }
 
-bool pllhip_aa_chunks_enabled()
-{
-  static const bool on = !(pllhip_env("PLLHIP_AA_CHUNKS") && atoi(pllhip_env("PLLHIP_AA_CHUNKS")) == 0) &&
-                         !(pllhip_env("PLLHIP_AA_RC8") && atoi(pllhip_env("PLLHIP_AA_RC8")) == 0);
-  return on;
-}
-
 bool pllhip_aa_fast_covers(const pllhip_ctx * c, int kind)
 {
   const unsigned int R = c->sh.rate_cats;
   // (category counts other than 1, 2, 4 -- round 4: several launches per op, each over a chunk of 4, 2 or 1 of the
-  // categories, k_aa_ii_mfma's SPLIT; PLLHIP_AA_CHUNKS=0: the all-vector kernels as before)
+  // categories, k_aa_ii_mfma's SPLIT; until then the all-vector kernels)
   if (c->aa_exact || c->sh.states != 20 || R == 0) return false;
-  const bool whole = R == 1 || R == 2 || R == 4;
-  if (!whole && !pllhip_aa_chunks_enabled()) return false;
   if (kind == 0) return true;
   // tip kinds: both tables of an op (of a chunk) must fit the workgroup's LDS next to its other data
   return c->maxstates > 0 && c->maxstates <= 32 &&
@@ -1097,8 +1086,8 @@ unsigned int pllhip_aa_lookup_budget(const pllhip_ctx * c)
 }
 
 // The tables of ALL `count` lookup ops of a list at once (the whole-list kernel,
-// partials_aa_fused.hip, walks a tile of sites through every op): same builders, a pool of
-// their own that grows with the list.
+// partials_aa_fused.hip, walks a tile of sites through every op): a pool of their own that
+// grows with the list; the whole-list kernel's prepare launch fills it.
 int pllhip_aa_lookup_tables(pllhip_ctx * c, const PartialsArgs * ops, const PartialsArgs * kid1,
                             const PartialsArgs * kid2, unsigned int count, AaLookupTables * out, AaLookupJob * jobs)
 {
@@ -1129,31 +1118,18 @@ int pllhip_aa_lookup_tables(pllhip_ctx * c, const PartialsArgs * ops, const Part
     c->cherry_pool_all_ops = (unsigned int)n;
     ++c->layout_epoch;
   }
-  if (jobs)
+  // places only (the same ones cherry_tables uses); the caller's prepare kernel fills them
+  for (unsigned int i = 0; i < count; ++i)
   {
-    // places only (the same ones cherry_tables uses); the caller's prepare kernel fills them
-    for (unsigned int i = 0; i < count; ++i)
-    {
-      double * base = c->cherry_pool_all + (size_t)i * per_op;
-      double * t0 = base + 2 * rows * row_elems, * t1 = base + 3 * rows * row_elems;
-      const PartialsArgs & op = ops[i];
-      const bool tip_left = kid1[i].lmat == nullptr; // a tip-inner lookup op: the left factor is the tip's own table
-      out[i] = AaLookupTables{t0, t1, tip_left ? op.ltip : kid1[i].ltip, tip_left ? c->cherry_zero : kid1[i].rtip,
-                              kid2[i].ltip, kid2[i].rtip};
-      jobs[2 * i] = tip_left ? AaLookupJob{nullptr, op.lmat, nullptr, t0, 2u, 0u}
-                             : AaLookupJob{op.lmat, kid1[i].lmat, kid1[i].rmat, t0, 0u, 0u};
-      jobs[2 * i + 1] = AaLookupJob{op.rmat, kid2[i].lmat, kid2[i].rmat, t1, tip_left ? 1u : 0u, 0u};
-    }
-    return 0;
-  }
-  for (unsigned int first = 0; first < count; first += chunk)
-  {
-    const unsigned int n = (count - first < chunk) ? count - first : chunk;
-    CherryBatch ch;
-    rc = cherry_tables(c, c->cherry_pool_all + (size_t)first * per_op, ops + first, kid1 + first, kid2 + first, n, ch);
-    if (rc) return rc;
-    for (unsigned int i = 0; i < n; ++i)
-      out[first + i] = AaLookupTables{ch.op[i].tl, ch.op[i].tr, ch.op[i].t1, ch.op[i].t2, ch.op[i].t3, ch.op[i].t4};
+    double * base = c->cherry_pool_all + (size_t)i * per_op;
+    double * t0 = base + 2 * rows * row_elems, * t1 = base + 3 * rows * row_elems;
+    const PartialsArgs & op = ops[i];
+    const bool tip_left = kid1[i].lmat == nullptr; // a tip-inner lookup op: the left factor is the tip's own table
+    out[i] = AaLookupTables{t0, t1, tip_left ? op.ltip : kid1[i].ltip, tip_left ? c->cherry_zero : kid1[i].rtip,
+                            kid2[i].ltip, kid2[i].rtip};
+    jobs[2 * i] = tip_left ? AaLookupJob{nullptr, op.lmat, nullptr, t0, 2u, 0u}
+                           : AaLookupJob{op.lmat, kid1[i].lmat, kid1[i].rmat, t0, 0u, 0u};
+    jobs[2 * i + 1] = AaLookupJob{op.rmat, kid2[i].lmat, kid2[i].rmat, t1, tip_left ? 1u : 0u, 0u};
   }
   return 0;
 }

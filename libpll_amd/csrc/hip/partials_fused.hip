@@ -292,9 +292,6 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       row_first = bases.rowtab[(size_t)sg[2] * 64u + lane];
     }
     const size_t site0 = (size_t)site_base + tile * TS; // (site_base: this launch's block of the alignment)
-#ifdef PLLHIP_FUSED_TIMING
-    const unsigned long long t_tile = __builtin_readcyclecounter();
-#endif
     unsigned int next_ticket = 0;
     const unsigned long long ticket_counter = (next_tile && round + 1 >= static_rounds) ? my_counter : no_counter;
     const size_t clv_off = site0 * (W * 16u);                             // bytes into a CLV
@@ -483,15 +480,6 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     sink_stores();
     stage_rows(fb, (rec_flags(h1) >> PLLHIP_FUSED_STAGE_SHIFT) & 3u, pl, pr);
 
-#ifdef PLLHIP_FUSED_TIMING
-    // (tool build, tools/fused_timing.sh: where a wave's cycles go, printed by a few waves)
-    unsigned long long seg[6] = {0, 0, 0, 0, 0, 0};
-#define PLLHIP_TICK(n) { const unsigned long long t_now = __builtin_readcyclecounter(); seg[n] += t_now - t_last; t_last = t_now; }
-    unsigned long long t_last = __builtin_readcyclecounter();
-    const unsigned long long t_prologue = t_last - t_tile;
-#else
-#define PLLHIP_TICK(n)
-#endif
     // One op.  r0: its record, r1: where the next one is loaded to; fu: the fetch of op i+1,
     // ff: where that of op i+2 goes; pu: its pair-table entries, pf: where those of op i+1 go.
     // The caller alternates the two of each, so that nothing loaded is ever copied (a copy
@@ -548,13 +536,11 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       // (the request last: what the next op waits for first is the youngest operation in flight)
       gather(pf, r0);
       request(ff, r0);
-      PLLHIP_TICK(0)
       // (every load is consumed on every path, needed or not: the registers of a load that
       // nobody waited for stay "pending" for the compiler, and it drains the queue -- this op's
       // predecessor's stores included -- when it next reuses them)
 #pragma unroll
       for (unsigned int j = 0; j < J; ++j) asm volatile("" ::"v"(pu[j].x), "v"(pu[j].y));
-      PLLHIP_TICK(1)
       unsigned long long scaled[J];
       double p0[J], p1[J];
       if (kind == 2)
@@ -608,13 +594,11 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       // (the arithmetic is done with pl, pr: their registers take the next op's rows, whose
       // LDS round trip runs while the stores below are issued)
       asm volatile("" ::"v"(p0[J - 1]), "v"(p1[J - 1]), "v"(fu.pm.x), "v"(fu.pm.y) : "memory");
-      PLLHIP_TICK(2)
       // the next record: a scalar load, and scalar loads return out of order -- while one is in
       // flight every wait for an LDS read or an earlier record field becomes a wait for
       // everything.  Here nothing of that kind is waited for until the next op begins.
       r1 = rec_load(plan, i + 3);
       stage_rows(fu, (fl >> PLLHIP_FUSED_STAGE_SHIFT) & 3u, pl, pr);
-      PLLHIP_TICK(5)
       // The stores are common to all kinds and under no branch: the compiler counts the memory
       // operations of the path with the FEWEST of them to decide how many may stay in flight at a
       // wait, and a path without this op's stores would make the next op wait for the stores of
@@ -633,7 +617,6 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
         asm volatile("s_mov_b64 exec, %0\n\tds_write_b128 %1, %2 offset:%3\n\ts_mov_b64 exec, -1"
                      :: "s"(slot_mask), "v"(lds_p_b), "v"(v), "n"(j * 1024u) : "memory");
       }
-      PLLHIP_TICK(3)
       // The tile's counts, once per op: inherited counts plus one if the sub-step that held the
       // entry scaled its group; all of them leave in ONE store (64 contiguous bytes per tile
       // with per-site counts).  (An op without a scale buffer stores to the sink.)
@@ -657,7 +640,6 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
         if (NTP == 2) __builtin_nontemporal_store(count, (unsigned int PLL_GLOBAL *)(cdst + t * 4u));
         else *(unsigned int PLL_GLOBAL *)(cdst + t * 4u) = count;
       }
-      PLLHIP_TICK(4)
     };
     for (unsigned int i = 0;;)
     {
@@ -666,12 +648,6 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       step(rb, ra, fb, fa, ptb, pta, i);
       if (++i == nops) break;
     }
-#ifdef PLLHIP_FUSED_TIMING
-    if (lane == 0 && round == 3 && (wave == 0 || wave == 1001 || wave == 2002 || wave == 3003))
-      printf("wave %u ops %u: tile %llu cycles, of which prologue %llu; per op: top (records, requests arrive, gather) %llu pair entries arrive %llu arithmetic %llu stores %llu counts %llu stage %llu\n",
-             (unsigned int)wave, nops, (unsigned long long)__builtin_readcyclecounter() - t_tile, t_prologue,
-             seg[0] / nops, seg[1] / nops, seg[2] / nops, seg[3] / nops, seg[4] / nops, seg[5] / nops);
-#endif
     if (++round < static_rounds)
     {
       item += nwaves;
@@ -713,7 +689,7 @@ unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int wgs)
   // (four workgroups -- 16 waves of 128 registers, four slots -- were measured for short lists in round 3 and are
   // slower than three at every list length: 2 / 3 / 5 / 7 / 15 ops 257 / 286 / 335 / 282 / 421 us against 226 / 260 /
   // 310 / 246 / 411; the variant spills seven registers)
-  const size_t budget = PLLHIP_FUSED_J == 1 ? 9472 : (wgs >= 4 ? 9984 : wgs >= 3 ? 13312 : 16384); // J = 1: four workgroups per CU
+  const size_t budget = wgs >= 3 ? 13312 : 16384;
   return (unsigned int)((budget - pmat) / per_slot);
 }
 
@@ -953,10 +929,8 @@ int pllhip_fused_plan(const FusedGeom & geom, const pllhip_op_t * ops, const Par
     // "heavier child first" rule below.  Until then every list with scale buffers was walked child 1 first, whatever the
     // subtrees' sizes: a traversal directed at a deep edge of a balanced 64-taxon tree needed 4 operands copied back
     // from HBM with five slots and ended in a run of seven matrix ops; now none, and at most three in a row.)
-    // (PLLHIP_FUSED_ORDER=0, a developer's switch: the old walk, for A/B measurements)
-    static const bool producers_are_no_hazards = !(pllhip_env("PLLHIP_FUSED_ORDER") && atoi(pllhip_env("PLLHIP_FUSED_ORDER")) == 0);
     auto hard = [&](int p) {
-      if (p >= 0 && (unsigned int)p != i && !(producers_are_no_hazards && (p == nd.raw[0] || p == nd.raw[1])))
+      if (p >= 0 && (unsigned int)p != i && p != nd.raw[0] && p != nd.raw[1])
         hard_of[i].push_back((unsigned int)p);
     };
     nd.sraw[0] = op.child1_scaler >= 0 ? sc_w[op.child1_scaler] : -1;
@@ -1118,16 +1092,9 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   // walks its share of the tiles
   const size_t nsegs = bases.nsegs; // (work items: (tile, segment) pairs)
   size_t grid = (tiles * nsegs + 3) / 4;
-#ifdef PLLHIP_FUSED_WPS4
-  // (tool build, tools/fused_wps4.sh: four workgroups per CU -- sixteen waves of 128 registers, four slots each)
-  const bool four = J != 1 && nslots <= pllhip_fused_slots(c, 4);
-#else
-  const bool four = false;
-#endif
-  const size_t cap = (size_t)c->num_cus * (J == 1 || four ? 4 : (nslots <= pllhip_fused_slots(c, 3) ? 3 : 2));
+  const size_t cap = (size_t)c->num_cus * (nslots <= pllhip_fused_slots(c, 3) ? 3 : 2);
   if (grid > cap) grid = cap;
   const bool nt = pllhip_use_nt(c);
-  const bool static_tiles = pllhip_env("PLLHIP_FUSED_STATIC_TILES") != nullptr;
   // Partitions beyond 8 GB (CLVs + scale buffers): the counts are stored non-temporally like the
   // tiles (see the kernel).  8 GB is what the address-translation caches reach (4096 pages of
   // 2 MB): every shape ran at 0.59-0.64 of the HBM peak up to there and at 0.46-0.50 beyond
@@ -1139,52 +1106,26 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   // (0.747 / 0.746, 0.688 / 0.689): the alternating walk is gone.
   const size_t footprint = c->clv_arena_bytes + (size_t)c->sh.scale_buffers * c->scaler_stride * sizeof(unsigned int);
   const bool beyond_reach = footprint > (size_t)4096 * ((size_t)2 << 20);
+  // (round 3: the alignment walked in BLOCKS of sites, one launch each, every launch taking its block through the
+  // whole list, was measured on the 133 GB partition (8 M sites x 128 taxa) with blocks of 4 M ... 500 k sites: 0.557 /
+  // 0.558 / 0.554 / 0.547 of the HBM peak against 0.555 in one launch -- what that partition lost it lost on the reads
+  // of the tip characters, not on the footprint of a launch (profiles/r3_footprint.txt).  One launch: site_base 0.)
+  // (the two sets of tile counters in turn: see the kernel)
+  unsigned int * const tile_counter = c->d_tile_counter + (size_t)c->tile_counter_phase * (PLLHIP_TILE_COUNTER_BYTES / 4);
+  unsigned int * const reset_tiles = c->d_tile_counter + (size_t)(c->tile_counter_phase ^ 1u) * (PLLHIP_TILE_COUNTER_BYTES / 4);
+  c->tile_counter_phase ^= 1u;
   // a third of a wave's rounds of tiles come from the counter (see the kernel: the XCDs' unequal
   // write rates): seven of the ~21 rounds of 1 M sites (the measured optimum there), and in proportion
   // for longer alignments (8 M sites x 128 taxa: 7 rounds 0.565, 30 0.584, 54 0.583 of the HBM peak;
   // 2 M sites: 7 rounds 0.652, 14 0.672); short lists two, see the kernel
-  // PLLHIP_FUSED_BLOCK_SITES (an experiment kept as a switch; default one launch): the alignment walked in
-  // BLOCKS of sites, one launch each, every launch taking its block through the whole list.  Measured on the
-  // 133 GB partition (8 M sites x 128 taxa) with blocks of 4 M ... 500 k sites: 0.557 / 0.558 / 0.554 / 0.547 of
-  // the HBM peak against 0.555 in one launch -- what that partition lost it lost on the reads of the tip
-  // characters, not on the footprint of a launch (profiles/r3_footprint.txt).
-  size_t block_sites = sites;
-  {
-    const char * e = pllhip_env("PLLHIP_FUSED_BLOCK_SITES");
-    if (e) block_sites = atoi(e) > 0 ? (size_t)atoi(e) : sites;
-    block_sites = (block_sites + 255) / 256 * 256; // (whole tiles, whole rounds)
-    if (block_sites > sites) block_sites = sites;
-  }
-  for (size_t base = 0; base < sites; base += block_sites)
-  {
-  const unsigned int bsites = (unsigned int)(sites - base < block_sites ? sites - base : block_sites);
-  const size_t btiles = (bsites + tile_sites - 1) / tile_sites;
-  size_t bgrid = (btiles * nsegs + 3) / 4;
-  if (bgrid > cap) bgrid = cap;
-  // (the two sets of tile counters in turn: see the kernel)
-  unsigned int * const tile_counter = static_tiles ? nullptr : c->d_tile_counter + (size_t)c->tile_counter_phase * (PLLHIP_TILE_COUNTER_BYTES / 4);
-  unsigned int * const reset_tiles = static_tiles ? nullptr : c->d_tile_counter + (size_t)(c->tile_counter_phase ^ 1u) * (PLLHIP_TILE_COUNTER_BYTES / 4);
-  c->tile_counter_phase ^= 1u;
-  const size_t rounds = btiles * nsegs / (bgrid * 4);
-  const unsigned int dynamic_rounds = pllhip_env("PLLHIP_FUSED_DYNAMIC_ROUNDS") ? (unsigned int)atoi(pllhip_env("PLLHIP_FUSED_DYNAMIC_ROUNDS"))
-                                      : (c->fused_last_longest >= 32 ? (unsigned int)std::max<size_t>(7, rounds / 3) : 2u);
-  // (eight counters, or what PLLHIP_FUSED_TILE_GROUPS says -- but never more than there are groups of eight
-  // workgroups, or a counter's tiles would have no takers; and no more than the counter buffer holds)
-  const size_t want_groups = pllhip_env("PLLHIP_FUSED_TILE_GROUPS") ? (size_t)std::max(1, atoi(pllhip_env("PLLHIP_FUSED_TILE_GROUPS"))) : 8;
-  const unsigned int tile_groups = (unsigned int)std::min<size_t>(std::min<size_t>(want_groups, PLLHIP_TILE_COUNTER_BYTES / 128),
-                                                                  std::max<size_t>(1, bgrid / 8));
-#define LAUNCH_FUSED_ARGS (unsigned int)bgrid, 256, lds, c->stream>>>( \
-      d_plan, bases, count, bsites, nslots, (double2 *)c->d_sink, tile_counter, dynamic_rounds, (unsigned int)base, tile_groups, \
-      reset_tiles)
-#ifdef PLLHIP_FUSED_WPS4
-#define LAUNCH_FUSED(MODEV, NTV)                                                      \
-  do {                                                                                \
-    if (four) k_dna_fused<RC, J, MODEV, NTV, 4><<<LAUNCH_FUSED_ARGS;                  \
-    else k_dna_fused<RC, J, MODEV, NTV, (J == 1 ? 4 : 3)><<<LAUNCH_FUSED_ARGS;        \
-  } while (0)
-#else
-#define LAUNCH_FUSED(MODEV, NTV) k_dna_fused<RC, J, MODEV, NTV, (J == 1 ? 4 : 3)><<<LAUNCH_FUSED_ARGS
-#endif
+  const size_t rounds = tiles * nsegs / (grid * 4);
+  const unsigned int dynamic_rounds = c->fused_last_longest >= 32 ? (unsigned int)std::max<size_t>(7, rounds / 3) : 2u;
+  // (eight counters -- but never more than there are groups of eight workgroups, or a counter's tiles would have no
+  // takers; and no more than the counter buffer holds)
+  const unsigned int tile_groups = (unsigned int)std::min<size_t>(std::min<size_t>(8, PLLHIP_TILE_COUNTER_BYTES / 128),
+                                                                  std::max<size_t>(1, grid / 8));
+#define LAUNCH_FUSED(MODEV, NTV) k_dna_fused<RC, J, MODEV, NTV, 3><<<(unsigned int)grid, 256, lds, c->stream>>>( \
+      d_plan, bases, count, sites, nslots, (double2 *)c->d_sink, tile_counter, dynamic_rounds, 0u, tile_groups, reset_tiles)
 #define LAUNCH_FUSED_MODE(NTV)                         \
   do {                                                  \
     if (mode == SCALE_NONE) LAUNCH_FUSED(0, NTV);       \
@@ -1196,8 +1137,6 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   else LAUNCH_FUSED_MODE(2);
 #undef LAUNCH_FUSED_MODE
 #undef LAUNCH_FUSED
-#undef LAUNCH_FUSED_ARGS
-  }
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -6,9 +6,7 @@
 
 #include "ctx.hpp"
 
-#ifndef PLLHIP_FUSED_J
-#define PLLHIP_FUSED_J 2 /* sub-steps (64 lanes x 16 B) per tile */
-#endif
+constexpr int PLLHIP_FUSED_J = 2; // sub-steps (64 lanes x 16 B) per tile
 
 // What the planner decides for one op (host side; the device gets FusedRec below).
 struct FusedOp
@@ -42,7 +40,7 @@ struct FusedOp
 //   - the op itself: parent, scale buffer, LDS places of operands, parent and counts.
 // Round 2 first had 32-byte records of 16-bit indices, decoded by the kernel; the counters say
 // a wave-op then cost 124 scalar + 124 vector instructions of which 30 were arithmetic, and that
-// the wave, not HBM, was the limit (tools/pmc_instmix.sh, tools/fused_timing.sh) -- so the
+// the wave, not HBM, was the limit (tools/pmc_instmix.sh) -- so the
 // host now does the decoding once per list.  The records hold addresses: they are rebuilt when an
 // arena moves (layout_epoch).
 struct FusedRec

@@ -475,7 +475,7 @@ def test_tip_character_batches_of_the_whole_list_kernel(amd, rate_cats):
             assert rows_in.get(b, 0) >= rpb - 1, "a batch was closed with room for a whole op left"
 
 
-def test_whole_list_kernel_keeps_out_of_the_slot_registers():
+def test_whole_list_kernel_instances_keep_out_of_the_slot_registers():
     """partials_aa_fused.hip keeps its values in the accumulation registers a0..a109 behind the
     compiler's back (inline assembly).  The generated code is checked: no instruction outside that
     assembly may touch them (without -mllvm -amdgpu-mfma-vgpr-form the compiler parks the matrix cores'
@@ -488,7 +488,7 @@ def test_whole_list_kernel_keeps_out_of_the_slot_registers():
     out = subprocess.run([sys.executable, os.path.join(root, "tools", "check_agprs.py")], capture_output=True, text=True,
                          timeout=900)
     assert out.returncode == 0, out.stdout + out.stderr
-    assert "9 kernels checked, 0 instructions" in out.stdout  # (three scaling modes x three cache policies)
+    assert "6 kernels checked, 0 instructions" in out.stdout  # (three scaling modes x two cache policies)
 
 
 def test_device_selection_per_thread_with_a_process_wide_default(amd):
@@ -663,7 +663,7 @@ def test_small_partition_path_choice(amd):
     assert _small_choice(amd, 4, 2000, bal64, ops=bad)[0] == -1
 
 
-def test_developer_switches_are_gated(amd, monkeypatch):
+def test_developer_switches_are_gated_and_listed_exactly(amd, monkeypatch):
     """Environment switches (round 5): the ones a client may set are a short table in the library (ctx.hip) and in
     INTEGRATION.md section 6; every other PLLHIP_* variable the sources read is a developer's knob, honoured only
     under PLLHIP_DEVELOPER=1 -- a stray variable cannot move a production run off the tested configuration."""
@@ -678,11 +678,14 @@ def test_developer_switches_are_gated(amd, monkeypatch):
         read |= set(re.findall(r'pllhip_env\("([A-Z_0-9]+)"', text))
         # nothing in the device layer reads a PLLHIP_ variable past the gate
         assert not [m for m in re.findall(r'[^_]getenv\("(PLLHIP_[A-Z_0-9]+)"', text) if m != "PLLHIP_DEVELOPER"], name
-    assert len(read) > 30
     user = {n for n in read if lib.pllhip_env_is_user_switch(n.encode())}
     assert user == {"PLLHIP_AA_EXACT", "PLLHIP_AA_TI_MFMA", "PLLHIP_FUSED", "PLLHIP_HOSTSUM", "PLLHIP_FUSE_REDUCE",
                     "PLLHIP_SPIN", "PLLHIP_SHARD_THREADS", "PLLHIP_SHARD_POLL", "PLLHIP_SHARD_PIN", "PLLHIP_PLACEMENT_TRIES", "PLLHIP_FUSED_DEBUG",
                     "PLLHIP_RCCL_DEBUG"}
+    # the developer's switches are the ones the tests set (the one-off experiments' switches are gone): a new one is a
+    # path nobody tests unless a test comes with it
+    assert read - user == {"PLLHIP_NT", "PLLHIP_FUSED_SEGMENTS", "PLLHIP_FUSED_WGS", "PLLHIP_AA_CHERRY", "PLLHIP_AA_LOOKUP_MB",
+                           "PLLHIP_AA_TT_INSIDE", "PLLHIP_AA_TT_PAIRS", "PLLHIP_AA_GRID_CAP"}, sorted(read - user)
     # the first table holds the client's switches, the second every developer's one
     doc = open(os.path.join(root, "INTEGRATION.md")).read()
     sec = doc[doc.index("## 6. Environment switches"):]
@@ -690,7 +693,7 @@ def test_developer_switches_are_gated(amd, monkeypatch):
     in_client = set(re.findall(r"`(PLLHIP_[A-Z_0-9]+)", "\n".join(l for l in client.splitlines() if l.startswith("| `"))))
     in_developer = set(re.findall(r"`(PLLHIP_[A-Z_0-9]+)", "\n".join(l for l in developer.splitlines() if l.startswith("| `"))))
     assert in_client - {"PLLHIP_DEVELOPER"} == user
-    assert read - user <= in_developer, sorted(read - user - in_developer)
+    assert read - user == in_developer, (sorted(read - user - in_developer), sorted(in_developer - (read - user)))
     assert not (in_developer & user)
     # the gate itself
     dev = sorted(read - user)[0]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """developer tool (round 6): does the speed of a partition's stores depend on WHERE in device memory it lies?
-(tools/clv_pad_sweep.sh on a fresh box: the first process stored BASELINE config 2's list at 5.7 TB/s and ran it in
+(profiles/r6_clv_pad_sweep.txt, on a fresh box: the first process stored BASELINE config 2's list at 5.7 TB/s and ran it in
 1,483 us, every later process -- same code, same sizes -- at 6.1-7.3 TB/s and 1,385-1,400 us.)  One process: N partitions
 of config 2 created one after the other and kept, each measured (list kernel by HIP events, bare stores of its list);
 then all destroyed and three more created.  PLLHIP_PLACEMENT_TRIES=1 shows the places as the allocator hands them
