@@ -1196,6 +1196,19 @@ extern "C" int pllhip_edge_loglikelihood(pllhip_ctx_t * c, unsigned int parent_c
   return run_lnl_certified(c, a, kind, h_persite_lnl, h_lnl);
 }
 
+// The reference's root kernel takes site n's count from ENTRY n of the scale buffer (core_likelihood.c:197-198): with
+// per-rate buffers ([sites][rate_cats]) that is the count of site n / rate_cats, category n % rate_cats.  A buffer
+// stored by class (PLL_ATTRIB_SITE_REPEATS) holds that entry in row site_id[n / rate_cats], not at index n: the
+// entries are gathered by site first, as shard.hip: gather_root_counts does for the shards of a partition.
+__global__ __launch_bounds__(256) void k_root_counts_by_site(unsigned int * __restrict__ out,
+                                                             const unsigned int * __restrict__ counts,
+                                                             const unsigned int * __restrict__ site_id,
+                                                             unsigned int sites, unsigned int R)
+{
+  for (size_t n = blockIdx.x * (size_t)blockDim.x + threadIdx.x; n < sites; n += (size_t)gridDim.x * blockDim.x)
+    out[n] = counts[(size_t)site_id[n / R] * R + n % R];
+}
+
 extern "C" int pllhip_root_loglikelihood(pllhip_ctx_t * c, unsigned int clv_index,
                                          int scaler_index, const unsigned int * h_freqs_indices,
                                          double * h_persite_lnl, double * h_lnl)
@@ -1215,5 +1228,28 @@ extern "C" int pllhip_root_loglikelihood(pllhip_ctx_t * c, unsigned int clv_inde
   a.pscaler = c->root_scaler_override ? c->root_scaler_override : pllhip_scaler_ptr(c, scaler_index);
   a.pscaler_by_site = c->root_scaler_override != nullptr;
   if (!c->rows.empty() && c->rows[clv_index].classes) a.pidx = c->rows[clv_index].site_id;
+  const int owner = (a.pscaler && !a.pscaler_by_site && c->sh.rate_scalers && !c->rows.empty() &&
+                     (size_t)scaler_index < c->scaler_owner.size()) ? c->scaler_owner[scaler_index] : -1;
+  if (owner >= 0 && (size_t)owner < c->rows.size() && c->rows[owner].classes)
+  {
+    HIP_TRY(hipSetDevice(c->sh.device));
+    // (the counts gathered must be final: the scaling certificate of the last list first)
+    if (c->cert_pending)
+    {
+      const int rc = pllhip_cert_resolve(c);
+      if (rc) return rc;
+    }
+    const size_t n = (size_t)c->sh.sites + PLLHIP_TAIL_SITES;
+    if (!c->root_counts)
+    {
+      HIP_TRY(hipMalloc((void **)&c->root_counts, n * sizeof(unsigned int)));
+      HIP_TRY(hipMemsetAsync(c->root_counts, 0, n * sizeof(unsigned int), c->stream));
+    }
+    k_root_counts_by_site<<<pllhip_stream_grid(c, c->sh.sites, 256), 256, 0, c->stream>>>(
+        c->root_counts, a.pscaler, c->rows[owner].site_id, c->sh.sites, c->sh.rate_cats);
+    HIP_TRY(hipGetLastError());
+    a.pscaler = c->root_counts;
+    a.pscaler_by_site = 1;
+  }
   return run_lnl_certified(c, a, ROOT, h_persite_lnl, h_lnl);
 }

@@ -106,6 +106,17 @@ double orc_edge_loglikelihood_ti(unsigned int states, unsigned int sites, unsign
                                  const double * prop_invar, const int * invariant,
                                  double * persite_lnl, int per_rate_scaling);
 
+/* pll_core_root_loglikelihood, core_likelihood.c:25 (4: core_likelihood_avx.c:114,
+ * 20: core_likelihood_avx2.c:25).  The count of site n is ENTRY n of the scale
+ * buffer in both scaling modes (core_likelihood.c:197-198): with per-rate buffers
+ * ([sites][rate_cats]) that is the first `sites` entries, not site n's counts.
+ * scaler, invariant and persite_lnl may be NULL. */
+double orc_root_loglikelihood(unsigned int states, unsigned int sites, unsigned int rate_cats,
+                              const double * clv, const unsigned int * scaler,
+                              const double * const * freqs, const double * rate_weights,
+                              const unsigned int * pattern_weights, const double * prop_invar,
+                              const int * invariant, double * persite_lnl);
+
 /* pll_core_update_sumtable_ii / _ti, core_derivatives.c:125,277 (plain-C
  * summation order; the SIMD variants differ in the last bits only) */
 void orc_update_sumtable_ii(unsigned int states, unsigned int sites, unsigned int rate_cats,

@@ -161,3 +161,40 @@ double orc_edge_loglikelihood_ti(unsigned int S, unsigned int sites, unsigned in
   }
   return logl;
 }
+
+double orc_root_loglikelihood(unsigned int S, unsigned int sites, unsigned int R,
+                              const double * clv, const unsigned int * scaler,
+                              const double * const * freqs, const double * w,
+                              const unsigned int * pw, const double * pinv, const int * invariant,
+                              double * persite)
+{
+  double logl = 0;
+  size_t n;
+  unsigned int k, j;
+  for (n = 0; n < sites; ++n)
+  {
+    double terma = 0;
+    for (k = 0; k < R; ++k)
+    {
+      const double * p = clv + (n * R + k) * S, * f = freqs[k];
+      double terma_r;
+      if (S == 4)
+        /* pi x clv, pairwise: core_likelihood_avx.c:145-156 */
+        terma_r = orc_pair4(f[0] * p[0], f[1] * p[1], f[2] * p[2], f[3] * p[3]);
+      else if (S == 20)
+        /* 4 accumulators strided by j mod 4, fused: core_likelihood_avx2.c:57-77 */
+        terma_r = orc_dot(f, p, 20, 1);
+      else
+      {
+        /* core_likelihood.c:170-174 */
+        terma_r = 0;
+        for (j = 0; j < S; ++j) terma_r += p[j] * f[j];
+      }
+      /* no test of terma_r > 0 here, unlike the 4-state edge kernels */
+      terma += weigh(terma_r, 0, w[k], pinv[k], f, invariant, n, 0);
+    }
+    /* entry n of the buffer whatever its layout: core_likelihood.c:197-198 */
+    logl += finish(terma, scaler ? scaler[n] : 0u, pw[n], persite, n);
+  }
+  return logl;
+}

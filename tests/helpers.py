@@ -71,6 +71,29 @@ def many_state_case(states, tips=9, sites=30, seed=3, shape="random", **kw):
     return case
 
 
+def constant_columns(case, every=3):
+    """Make every `every`-th column one character in every tip, so that invariant[] is populated (tip characters or,
+    for more than 32 states, tip state indices)."""
+    if case.get("tip_index") is not None:
+        case["tip_index"][:, ::every] = case["tip_index"][:1, ::every]
+        return
+    seqs = [bytearray(s) for s in case["seqs"]]
+    for col in range(0, case["sites"], every):
+        for s in seqs:
+            s[col] = seqs[0][col]
+    case["seqs"] = [bytes(s) for s in seqs]
+
+
+def repeat_columns(case, seed, distinct):
+    """Resample the alignment's columns from a pool of `distinct` of them, so that site repeats
+    (PLL_ATTRIB_SITE_REPEATS) find few classes per node, like real data."""
+    sites = case["sites"]
+    rng = np.random.default_rng(seed)
+    pool = rng.integers(0, sites, size=distinct)
+    pick = pool[rng.integers(0, len(pool), size=sites)]
+    case["seqs"] = [bytes(np.frombuffer(s, dtype=np.uint8)[pick]) for s in case["seqs"]]
+
+
 def index_tip_clvs(case):
     S, R = case["states"], case["rate_cats"]
     idx = case["tip_index"]
@@ -210,6 +233,41 @@ def sumtable_err(a, b):
     entries that are analytically zero (gap columns) carry only rounding noise."""
     scale = np.abs(b).max(axis=2, keepdims=True) + 1e-300
     return float(np.max(np.abs(a - b) / scale))
+
+
+def derivative_magnitudes(model, sumtable, t, pattern_weights=None, invariant=None):
+    """(sum_n w_n |L'/L|, sum_n w_n ((L'/L)^2 + |L''/L|)) from a sumtable [sites][R][S], in double: the size of the
+    site terms that pll_compute_likelihood_derivatives adds up (d_f = sum_n w_n (-L'/L), dd_f = sum_n w_n ((L'/L)^2 -
+    L''/L)).  The scale to judge a total by where its terms cancel: at a long branch (t = 50) every site's L'/L is
+    what is left of the eigenvalues that are zero in exact arithmetic, and (L'/L)^2 and L''/L agree to the last
+    bits -- a total near zero, against which rounding of the terms would look large."""
+    S, R = model["states"], model["rate_cats"]
+    pinv = float(model.get("pinv", 0.0))
+    x = np.asarray(model["eigenvals"])[None, :] * (np.asarray(model["rates"]) / (1.0 - pinv))[:, None]
+    e = np.exp(x * t)
+    st = np.asarray(sumtable, dtype=np.float64).reshape(-1, R, S)
+    w = np.asarray(model["rate_weights"])
+    fr = np.asarray(model["freqs"])
+    lk = [(st * (e * x ** i)[None]).sum(axis=2) for i in range(3)]
+    if pinv > 0:
+        inv = np.full(st.shape[0], -1) if invariant is None else np.asarray(invariant)
+        inv_lk = np.where(inv >= 0, fr[np.maximum(inv, 0)], 0.0) * pinv
+        lk = [lk[0] * (1 - pinv) + inv_lk[:, None], lk[1] * (1 - pinv), lk[2] * (1 - pinv)]
+    L0, L1, L2 = [(v * w[None, :]).sum(axis=1) for v in lk]
+    pw = np.ones(st.shape[0]) if pattern_weights is None else np.asarray(pattern_weights, dtype=np.float64)
+    d1, d2 = L1 / L0, L2 / L0
+    return float((np.abs(d1) * pw).sum()), float(((d1 * d1 + np.abs(d2)) * pw).sum())
+
+
+def deriv_errs(got, want, t, mags):
+    """errors of (d_f, dd_f) against `want`: relative to the totals, and at t >= 50 relative to the magnitudes of
+    their terms instead (`mags`, derivative_magnitudes or ExactRun.derivatives): there the totals are sums of terms
+    that cancel to near zero"""
+    out = []
+    for g, w_, m in zip(got, want, mags):
+        scale = float(m) if t >= 50 else abs(float(w_))
+        out.append(abs(float(g) - float(w_)) / max(scale, 1e-300))
+    return max(out)
 
 
 def random_op_sequence(rng, tips, inner, scalers, matrices, length):

@@ -42,6 +42,7 @@ class Oracle:
         self.lib = lib = C.CDLL(path, mode=C.RTLD_LOCAL)
         lib.orc_edge_loglikelihood_ii.restype = C.c_double
         lib.orc_edge_loglikelihood_ti.restype = C.c_double
+        lib.orc_root_loglikelihood.restype = C.c_double
         for name in ("orc_update_pmatrix", "orc_update_partial_ii", "orc_update_partial_ti",
                      "orc_update_partial_tt", "orc_update_sumtable_ii", "orc_update_sumtable_ti",
                      "orc_likelihood_derivatives", "orc_update_partials"):
@@ -127,6 +128,16 @@ class OracleRun:
             v = L.orc_edge_loglikelihood_ii(C.c_uint(self.S), C.c_uint(self.sites), C.c_uint(self.R),
                                             _d(self.clv[pclv]), _u(self._sc(pscaler)),
                                             _d(self.clv[cclv]), _u(self._sc(cscaler)), *common)
+        return (v, ps) if persite else v
+
+    def root_loglikelihood(self, clv, scaler, persite=False):
+        """lnL at CLV `clv` read as a root (pll_compute_root_loglikelihood); scaler: index
+        or -1.  Site n takes entry n of the scale buffer in either scaling mode."""
+        ps = np.zeros(self.sites) if persite else None
+        w = np.ascontiguousarray(self.m["rate_weights"], dtype=np.float64)
+        v = self.o.lib.orc_root_loglikelihood(C.c_uint(self.S), C.c_uint(self.sites), C.c_uint(self.R),
+                                              _d(self.clv[clv]), _u(self._sc(scaler)), _rows(self._fr),
+                                              _d(w), _u(self.pw), _d(self._pinv), _i(self.invariant), _d(ps))
         return (v, ps) if persite else v
 
     def sumtable(self, pclv, cclv, pscaler, cscaler):

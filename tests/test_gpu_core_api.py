@@ -46,7 +46,8 @@ def bind(lib):
     L.pll_core_edge_loglikelihood_ti_4x4.restype = C.c_double
     L.pll_core_root_loglikelihood.restype = C.c_double
     for name in ("pll_core_create_lookup", "pll_core_update_partial_tt", "pll_core_update_partial_ti",
-                 "pll_core_update_partial_ii", "pll_amd_core_release"):
+                 "pll_core_update_partial_ii", "pll_amd_core_release", "pll_core_create_lookup_4x4",
+                 "pll_core_update_partial_tt_4x4", "pll_core_update_partial_ti_4x4"):
         getattr(L, name).restype = None
     return L
 
@@ -130,6 +131,21 @@ def test_tree_through_core_api(gpu, orc, monkeypatch, states, shape, tips, sites
         assert bits_equal(clv[par], o.clv[par]), "CLV %d" % par
         if psc >= 0:
             assert (scal[psc] == o.scalers[psc]).all(), "scaler %d" % psc
+        if S == 4 and (t1 or t2):
+            # the same op through the 4-state forms (pll.h: pll_core_*_4x4), into a CLV and a scale buffer of its own
+            clv4 = np.zeros((sites, R, S))
+            sc4 = np.zeros(sc_len, dtype=np.uint32) if psc >= 0 else None
+            if t1 and t2:
+                lookup4 = np.zeros(table_rows * span)
+                L.pll_core_create_lookup_4x4(R, d(lookup4), d(pm[m1]), d(pm[m2]))
+                L.pll_core_update_partial_tt_4x4(sites, R, d(clv4), u(sc4), b(codes[c1]), b(codes[c2]), d(lookup4),
+                                                 attrib)
+            else:
+                L.pll_core_update_partial_ti_4x4(sites, R, d(clv4), u(sc4), b(codes[tip]), d(clv[inner]), d(pm[mt]),
+                                                 d(pm[mn]), u(sc(sn)), attrib)
+            assert bits_equal(clv4, o.clv[par]), "CLV %d (4x4 form)" % par
+            if psc >= 0:
+                assert (sc4 == o.scalers[psc]).all(), "scaler %d (4x4 form)" % psc
 
     # ---- edge log-likelihood at the root edge (likelihood.c:416-513)
     pc, ps_, cc, cs, m = plan.root_edge
@@ -171,6 +187,11 @@ def test_tree_through_core_api(gpu, orc, monkeypatch, states, shape, tips, sites
     assert ok == 1, gpu.errmsg()
     want_st = o.sumtable(pc, cc, ps_, cs)
     assert sumtable_err(st.reshape(want_st.shape), want_st) < 1e-12
+    if S == 4 and pattern_tip and (pc < tips or cc < tips):
+        st4 = np.zeros(sites * span)
+        assert L.pll_core_update_sumtable_ti_4x4(sites, R, d(clv[inner]), b(codes[tip]), u(sc(isc)), per_cat(vecs),
+                                                 per_cat(inv), per_cat(freqs), u(tipmap), d(st4), attrib) == 1
+        assert sumtable_err(st4.reshape(want_st.shape), want_st) < 1e-12
     df, ddf = C.c_double(), C.c_double()
     pinv_cat = np.zeros(R)
     for t in (0.03, 0.4):

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from helpers import (make_case, odd_state_case, build_partition, oracle_run, bits_equal, rel_err,
-                     sumtable_err)
+                     sumtable_err, constant_columns)
 from libpll_amd.pllapi import (ATTRIB_PATTERN_TIP, ATTRIB_RATE_SCALERS, ATTRIB_ARCH_AVX2,
                                ATTRIB_ARCH_CPU)
 
@@ -134,4 +134,69 @@ def test_random_op_sequences(ref, orc, seed):
         assert (p.get_scaler(sc) == o.scalers[sc]).all(), "scale buffer %d" % sc
         fired = max(fired, int(o.scalers[sc].max()))
     assert fired >= 4, "sequence no longer exercises scaling"
+    p.destroy()
+
+
+@pytest.mark.parametrize("states", [4, 20, 5])
+@pytest.mark.parametrize("pattern_tip", [0, ATTRIB_PATTERN_TIP])
+@pytest.mark.parametrize("pinv", [0.0, 0.3])
+def test_root_loglikelihood(ref, orc, states, pattern_tip, pinv):
+    """orc_root_loglikelihood against pll_compute_root_loglikelihood at every inner CLV of a tree, with pattern
+    weights and (pinv > 0) invariant columns: bit for bit (5 states: the CPU flag's plain-C order)."""
+    if states == 5:
+        attrs = pattern_tip | ATTRIB_ARCH_CPU
+        case = odd_state_case(5, tips=9, sites=61, seed=17)
+    else:
+        attrs = pattern_tip | ATTRIB_ARCH_AVX2
+        case = make_case(states, "random", 9, 61, seed=17 + states, gap_frac=0.0, ambiguity=False)
+        if states == 20:
+            case["rates"], case["freqs"] = ref.aa_model("wag")
+    constant_columns(case)
+    p = build_partition(ref, case, attrs, pinv=pinv)
+    o = oracle_run(orc, ref, p, case, attrs, pinv=pinv)
+    if pinv:
+        assert (o.invariant >= 0).sum() >= 15
+    plan = case["plan"]
+    p.update_partials(plan.ops)
+    o.update_partials()
+    for op in plan.ops:
+        node, sc = int(op["parent_clv_index"]), int(op["parent_scaler_index"])
+        lnl_r, ps_r = p.compute_root_loglikelihood(node, sc, [0] * 4, persite=True)
+        lnl_o, ps_o = o.root_loglikelihood(node, sc, persite=True)
+        assert bits_equal(ps_o, ps_r), "CLV %d" % node
+        assert lnl_o == lnl_r
+    p.destroy()
+
+
+@pytest.mark.parametrize("states,tips,rate_scalers", [(4, 700, 0), (20, 400, 0), (5, 500, 0),
+                                                     (4, 700, ATTRIB_RATE_SCALERS), (20, 400, ATTRIB_RATE_SCALERS)])
+def test_root_loglikelihood_deep(ref, orc, states, tips, rate_scalers):
+    """Deep caterpillars: the root call's scaler term.  Per-rate buffers: the reference takes site n's count from
+    ENTRY n of the [sites][rate_cats] buffer (core_likelihood.c:197-198); pinned where those entries are non-zero and
+    are not the sites' own counts."""
+    arch = ATTRIB_ARCH_CPU if states == 5 else ATTRIB_ARCH_AVX2
+    attrs = ATTRIB_PATTERN_TIP | rate_scalers | arch
+    kw = dict(alpha=0.3, branch=0.5, weights=False, seed=5)
+    if states == 5:
+        case = odd_state_case(5, tips=tips, sites=12, shape="caterpillar", **kw)
+    else:
+        case = make_case(states, "caterpillar", tips, 12, ambiguity=False, gap_frac=0.0, **kw)
+        if states == 20:
+            case["rates"], case["freqs"] = ref.aa_model("lg")
+    p = build_partition(ref, case, attrs)
+    o = oracle_run(orc, ref, p, case, attrs)
+    plan = case["plan"]
+    p.update_partials(plan.ops)
+    o.update_partials()
+    node, sc = int(plan.ops[-1]["parent_clv_index"]), int(plan.ops[-1]["parent_scaler_index"])
+    counts = o.scalers[sc]
+    assert (counts == p.get_scaler(sc)).all()
+    assert counts[:12].min() >= 2, "fixture no longer exercises scaling: %s" % counts
+    if rate_scalers:
+        own = counts.reshape(12, -1).min(axis=1)
+        assert (counts[:12] != own).any(), "the entries the root reads are the sites' own counts here"
+    lnl_r, ps_r = p.compute_root_loglikelihood(node, sc, [0] * 4, persite=True)
+    lnl_o, ps_o = o.root_loglikelihood(node, sc, persite=True)
+    assert bits_equal(ps_o, ps_r)
+    assert lnl_o == lnl_r
     p.destroy()
