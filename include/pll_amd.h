@@ -766,6 +766,68 @@ PLL_EXPORT int pll_amd_insertion_loglikelihood(pll_partition_t * partition,
                                                const unsigned int * params_indices,
                                                double * lnl);
 
+/* ---- batched branch-length optimisation (branch_opt.c, branch_opt.hip) ----
+ * One branch, given by its two sides in the same way as pll_update_sumtable: each side's CLV pointing away from the
+ * other (a tip or an inner CLV) and its scale buffer. */
+typedef struct pll_amd_branch
+{
+  unsigned int parent_clv_index;
+  int          parent_scaler_index;   /* PLL_SCALE_BUFFER_NONE allowed */
+  unsigned int child_clv_index;
+  int          child_scaler_index;
+} pll_amd_branch_t;
+
+#define PLL_AMD_BRANCH_CONVERGED 0
+#define PLL_AMD_BRANCH_MAX_ITERS 1
+#define PLL_AMD_BRANCH_NONFINITE 2
+
+/* The length of every branch optimised on its own, all CLVs held fixed, by a safeguarded Newton iteration that runs
+ * on the device.  D(t) = (f, g) is what pll_compute_likelihood_derivatives(partition, parent_scaler, child_scaler, t,
+ * params_indices, sumtable, &f, &g) returns after pll_update_sumtable(partition, parent_clv, child_clv,
+ * parent_scaler, child_scaler, params_indices, sumtable); f and g are the first and second derivatives of -lnL.
+ * For every branch, independently:
+ *
+ *   t  = min(max(lengths[b], min_length), max_length);  lo = min_length;  hi = max_length
+ *   (f, g) = D(t);  evals = 1;  status = MAX_ITERS
+ *   if f or g is not finite: status = NONFINITE, stop
+ *   for step = 1 .. max_iters:
+ *       if f < 0: lo = t  else: hi = t                    # the optimum stays inside [lo, hi]
+ *       tn = t - f / g                                    # Newton step ...
+ *       if not (g > 0 and lo <= tn <= hi):
+ *           tn = sqrt(lo * hi)                            # ... else geometric bisection (lengths are scales)
+ *       done = |tn - t| < tolerance
+ *       t = tn
+ *       if done: status = CONVERGED, stop
+ *       if step == max_iters: stop
+ *       (f, g) = D(t);  evals += 1
+ *       if f or g is not finite: status = NONFINITE, stop
+ *   lengths[b] = t;  evals[b] = evals;  status[b] = status
+ *   lnl[b] = pll_compute_edge_loglikelihood at length t (the tip, if any, as the child; freqs_indices = params_indices)
+ *
+ * The device's exp and its order of the site sums differ from the single calls': d and dd agree with them to about
+ * 1e-13 relative, not bit for bit, so a result lies within `tolerance` of the host loop's, not on it.  lnl, evals and
+ * status may be NULL.
+ * What lives where: the sumtables, Newton states and partial sums are scratch of the partition on its device, kept
+ * until it is destroyed; a call never changes a CLV, scale buffer, P-matrix, sumtable slot or host mirror, and
+ * `lengths` is the only input it overwrites.  Large batches are worked in chunks of at most about
+ * PLL_AMD_BRANCH_SCRATCH_MB (environment, read at call time, default 2048) of scratch; a branch's result is the same
+ * bits whatever else is in the batch, in whatever order, however the call chunks it.  The call is synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, outputs untouched): CLV, scaler and params indices in
+ * range, no tip-tip branch (pattern tips), 0 < min_length <= max_length and both finite, tolerance > 0 and finite,
+ * max_iters >= 1, count >= 1, start lengths finite, no NULL array but lnl, evals and status.
+ * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
+ * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
+ * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  INTEGRATION.md section 4c. */
+PLL_EXPORT int pll_amd_optimize_branch_lengths(pll_partition_t * partition,
+                                               const pll_amd_branch_t * branches, unsigned int count,
+                                               const unsigned int * params_indices,
+                                               double min_length, double max_length,
+                                               double tolerance, unsigned int max_iters,
+                                               double * lengths,        /* in: start; out: optimised */
+                                               double * lnl,            /* out, may be NULL */
+                                               unsigned int * evals,    /* out, may be NULL */
+                                               int * status);           /* out, may be NULL */
+
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets
  * threads create partitions concurrently -- WITH a process-wide default: a thread that has not set a device uses what

@@ -325,6 +325,30 @@ PLLHIP_EXPORT int pllhip_insertion_loglikelihood(pllhip_ctx_t * ctx, const pllhi
                                                  unsigned int query_count, const unsigned int * h_params_indices,
                                                  size_t scratch_bytes, double * h_lnl);
 
+/* ---- batched branch-length optimisation (branch_opt.hip; host side host/branch_opt.c) ----
+ * Every branch on its own, all CLVs fixed: the safeguarded Newton rule of pll_amd_optimize_branch_lengths
+ * (include/pll_amd.h) on what pllhip_update_sumtable and pllhip_likelihood_derivatives would return, the iteration
+ * on the device; lnl at the final length as pllhip_edge_loglikelihood would return it (freqs indices = params
+ * indices).  Same layout as pll_amd_branch_t; status codes PLLHIP_BRANCH_* = PLL_AMD_BRANCH_*.  Nothing of the
+ * context changes; scratch (kept by the context) is at most about scratch_bytes per chunk, at least one branch's
+ * worth.  Returns -1 for a bad argument (nothing launched, outputs untouched), -2 if a chunk's scratch cannot be
+ * had, -3 for a context this call does not take (asc-bias, site repeats, sharded, RCCL). */
+typedef struct pllhip_branch
+{
+  unsigned int parent_clv_index;
+  int parent_scaler_index;
+  unsigned int child_clv_index;
+  int child_scaler_index;
+} pllhip_branch_t;
+#define PLLHIP_BRANCH_CONVERGED 0
+#define PLLHIP_BRANCH_MAX_ITERS 1
+#define PLLHIP_BRANCH_NONFINITE 2
+PLLHIP_EXPORT int pllhip_optimize_branch_lengths(pllhip_ctx_t * ctx, const pllhip_branch_t * h_branches,
+                                                 unsigned int count, const unsigned int * h_params_indices,
+                                                 double min_length, double max_length, double tolerance,
+                                                 unsigned int max_iters, size_t scratch_bytes, double * h_lengths,
+                                                 double * h_lnl, unsigned int * h_evals, int * h_status);
+
 /* ---- multi-GPU: one process per GPU, RCCL sum of the scalar results ---- */
 PLLHIP_EXPORT int pllhip_comm_unique_id(void * id128);
 /* which RCCL the process uses: the file the collective symbols were bound to -- the copy already

@@ -213,6 +213,9 @@ struct pllhip_ctx
   // grown to what one chunk of a call needs and kept until the context goes
   void * ins_scratch = nullptr;
   size_t ins_scratch_bytes = 0;
+  // batched branch-length calls (branch_opt.hip): sumtables, Newton states and partial sums of one chunk, kept the same way
+  void * bo_scratch = nullptr;
+  size_t bo_scratch_bytes = 0;
 
   // optional per-launch timing (pllhip_profile_*): one event pair per launch
   bool profiling = false;
@@ -493,6 +496,8 @@ static inline double pllhip_cert_err(const pllhip_ctx * c, unsigned int clv_inde
 }
 // partials.hip: `count` independent ops of one kind and mode, batched where the partition's kernels batch
 int pllhip_launch_partials_batch(pllhip_ctx * c, PartialsBatch & b, unsigned int count, int kind, int mode);
+// derivatives.hip: a sumtable's two matrix sets for h_params_indices into `left` / `right` (pmat_elems doubles each)
+int pllhip_sumtable_mats_to(pllhip_ctx * c, const unsigned int * h_params_indices, double * left, double * right);
 // pmatrix.hip: P-matrices into `dst` (slots matrices of room) instead of the partition's array
 int pllhip_pmatrices_to(pllhip_ctx * c, double * dst, unsigned int slots, const unsigned int * h_params_indices,
                         const unsigned int * h_matrix_indices, const double * h_branch_lengths, unsigned int count);

@@ -81,6 +81,24 @@ __global__ __launch_bounds__(256) void k_sumtable_rescale(double * __restrict__ 
   }
 }
 
+// the two matrix sets of a sumtable (A_k at `left`, B_k at `right`, pmat_elems each) for params_indices, as
+// pllhip_update_sumtable makes them (the batched branch-length call, branch_opt.hip)
+int pllhip_sumtable_mats_to(pllhip_ctx * c, const unsigned int * h_params_indices, double * left, double * right)
+{
+  SumMatArgs m;
+  m.left = left;
+  m.right = right;
+  m.eigenvecs = c->eigenvecs;
+  m.inv_eigenvecs = c->inv_eigenvecs;
+  m.freqs = c->freqs;
+  m.states = c->sh.states;
+  m.rate_cats = c->sh.rate_cats;
+  for (unsigned int k = 0; k < m.rate_cats; ++k) m.params_indices[k] = h_params_indices[k];
+  k_build_sumtable_mats<<<(m.rate_cats * m.states * m.states + 255) / 256, 256, 0, c->stream>>>(m);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 extern "C" int pllhip_update_sumtable(pllhip_ctx_t * c, unsigned int parent_clv,
                                       int parent_scaler, unsigned int child_clv,
                                       int child_scaler, const unsigned int * h_params_indices,

@@ -283,6 +283,10 @@ class PllLibrary:
             if hasattr(lib, "pll_amd_insertion_loglikelihood"):
                 lib.pll_amd_insertion_loglikelihood.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_void_p, _dp,
                                                                 C.c_uint, _up, _dp]
+            if hasattr(lib, "pll_amd_optimize_branch_lengths"):
+                lib.pll_amd_optimize_branch_lengths.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_double,
+                                                                C.c_double, C.c_double, C.c_uint, _dp, _dp, _up,
+                                                                C.c_void_p]
 
     # -- library-level helpers -------------------------------------------------
     def errno(self):
@@ -493,6 +497,11 @@ INSERTION_EDGE_DTYPE = np.dtype([("proximal_clv_index", np.uint32), ("proximal_s
                                  ("distal_clv_index", np.uint32), ("distal_scaler_index", np.int32),
                                  ("proximal_length", np.float64), ("distal_length", np.float64)])
 
+# pll_amd_branch_t (include/pll_amd.h)
+BRANCH_DTYPE = np.dtype([("parent_clv_index", np.uint32), ("parent_scaler_index", np.int32),
+                         ("child_clv_index", np.uint32), ("child_scaler_index", np.int32)])
+BRANCH_CONVERGED, BRANCH_MAX_ITERS, BRANCH_NONFINITE = 0, 1, 2
+
 
 class Partition:
     """A pll_partition_t* plus the calls that take it as first argument."""
@@ -650,6 +659,29 @@ class Partition:
             _u(pi), _d(out))
         self._check(ok, "pll_amd_insertion_loglikelihood")
         return out
+
+    def optimize_branch_lengths(self, branches, lengths, params_indices, min_length=1e-6, max_length=100.0,
+                                tolerance=1e-7, max_iters=64):
+        """pll_amd_optimize_branch_lengths: (lengths, lnl, evals, status) as numpy arrays, one entry per branch.
+        branches: rows of (parent_clv, parent_scaler, child_clv, child_scaler) or a BRANCH_DTYPE array; lengths:
+        the start lengths (not changed: the result is a new array)."""
+        b = np.zeros(len(branches), dtype=BRANCH_DTYPE)
+        if isinstance(branches, np.ndarray) and branches.dtype == BRANCH_DTYPE:
+            b[:] = branches
+        else:
+            for i, row in enumerate(branches):
+                b[i] = tuple(row)
+        t = np.array(lengths, dtype=np.float64).reshape(-1)
+        assert len(t) == len(b)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        lnl = np.zeros(len(b))
+        evals = np.zeros(len(b), dtype=np.uint32)
+        status = np.zeros(len(b), dtype=np.int32)
+        ok = self.lib.pll_amd_optimize_branch_lengths(
+            self.ptr, b.ctypes.data if len(b) else None, len(b), _u(pi), min_length, max_length, tolerance,
+            max_iters, _d(t), _d(lnl), _u(evals), status.ctypes.data)
+        self._check(ok, "pll_amd_optimize_branch_lengths")
+        return t, lnl, evals, status
 
     # -- reading results back ----------------------------------------------------------
     def get_clv(self, idx):
