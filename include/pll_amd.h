@@ -828,6 +828,60 @@ PLL_EXPORT int pll_amd_optimize_branch_lengths(pll_partition_t * partition,
                                                unsigned int * evals,    /* out, may be NULL */
                                                int * status);           /* out, may be NULL */
 
+/* ---- batched per-site posteriors: ancestral states and rate categories (posteriors.c, posteriors.hip) ----
+ * One edge, given as pll_compute_edge_loglikelihood takes it; the node whose states are asked for is the parent. */
+typedef struct pll_amd_posterior_edge
+{
+  unsigned int parent_clv_index;     /* the node whose states are asked for: its CLV pointing away from the child */
+  int          parent_scaler_index;  /* PLL_SCALE_BUFFER_NONE allowed */
+  unsigned int child_clv_index;      /* the other side, pointing away from the parent (a tip or an inner CLV) */
+  int          child_scaler_index;
+  unsigned int matrix_index;         /* the P-matrix of the edge, as pll_compute_edge_loglikelihood takes it */
+} pll_amd_posterior_edge_t;
+
+/* For every edge and site, the shares of the site likelihood that pll_compute_edge_loglikelihood(partition, parent,
+ * parent scaler, child, child scaler, matrix_index, freqs_indices, persite_lnl) is made of (marginal ancestral
+ * states, rate-category posteriors, empirical-Bayes site rates).  For site n (core_likelihood.c:914-996, :348-403),
+ * with termb[i][j] = sum_k P_i[j][k] clvc[i][k], f_i the frequencies of category i (freqs_indices[i]), w_i its weight,
+ * p_i its invariant proportion, and m_i = PLL_SCALE_THRESHOLD to the capped difference between category i's scaler
+ * count and the site's smallest (PLL_ATTRIB_RATE_SCALERS; otherwise 1):
+ *
+ *   x[i][j] = w_i (1 - p_i) m_i clvp[i][j] f_i[j] termb[i][j]
+ *   v[i]    = w_i p_i f_i[invar_indices[n]]            (0 where p_i = 0 or the site is not invariant)
+ *   terma   = sum_i (sum_j x[i][j] + v[i])             (log(terma) + the scaler term is persite_lnl)
+ *
+ *   state_probs[j]        = (sum_i x[i][j] + [j == invar_indices[n]] sum_i v[i]) / terma
+ *   rate_probs[i]         = sum_j x[i][j] / terma      for i < rate_cats
+ *   rate_probs[rate_cats] = sum_i v[i] / terma         (the invariant class; 0 without +I)
+ *   best_state            = the lowest j with the largest state_probs[j] as returned;  best_prob = that entry
+ *   site_rates            = sum_i rate_probs[i] r_i,   r_i = rates[i] / (1 - p_i) where p_i > 0, else rates[i]
+ *
+ * All sums run left to right in index order; rows of state_probs and rate_probs add up to 1 only to rounding.
+ * Per-site scaler counts cancel and are not applied.  The invariant term is added to a scaled category sum without
+ * being rescaled, as the reference does: the shares add up to the terma the library's lnL is made of.
+ * Layout: state_probs [edge][site][states], best_state / best_prob / site_rates [edge][site], rate_probs
+ * [edge][site][rate_cats + 1]; each may be NULL, one at least is not.
+ * What lives where: the outputs of a chunk are scratch of the partition on its device, kept until it is destroyed; a
+ * call never changes a CLV, scale buffer, P-matrix, sumtable or host mirror.  Large batches are worked in chunks of
+ * at most about PLL_AMD_POSTERIOR_SCRATCH_MB (environment, read at call time, default 2048) of scratch; an edge's
+ * values are the same bits whatever else is in the batch, in whatever order, however the call chunks it and
+ * whichever outputs are NULL.  The call is synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, outputs untouched): CLV, scaler, matrix and freqs
+ * indices in range, edge_count >= 1, edges and freqs_indices not NULL, one output at least, and with
+ * PLL_ATTRIB_PATTERN_TIP the parent is not a tip (a tip's states are its characters).
+ * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
+ * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
+ * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: joint reconstruction, a builder of the
+ * pre-order op list, device-resident outputs.  INTEGRATION.md section 4d. */
+PLL_EXPORT int pll_amd_site_posteriors(pll_partition_t * partition,
+                                       const pll_amd_posterior_edge_t * edges, unsigned int edge_count,
+                                       const unsigned int * freqs_indices,
+                                       double * state_probs,        /* [edge][site][states]        or NULL */
+                                       unsigned char * best_state,  /* [edge][site]                or NULL */
+                                       double * best_prob,          /* [edge][site]                or NULL */
+                                       double * rate_probs,         /* [edge][site][rate_cats + 1] or NULL */
+                                       double * site_rates);        /* [edge][site]                or NULL */
+
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets
  * threads create partitions concurrently -- WITH a process-wide default: a thread that has not set a device uses what

@@ -349,6 +349,27 @@ PLLHIP_EXPORT int pllhip_optimize_branch_lengths(pllhip_ctx_t * ctx, const pllhi
                                                  unsigned int max_iters, size_t scratch_bytes, double * h_lengths,
                                                  double * h_lnl, unsigned int * h_evals, int * h_status);
 
+/* ---- batched per-site posteriors (posteriors.hip; host side host/posteriors.c) ----
+ * For every edge and site, how the site likelihood of pllhip_edge_loglikelihood (same five arguments) splits over the
+ * states of the parent side and over the rate categories: the definition is written out at pll_amd_site_posteriors
+ * (include/pll_amd.h).  Same layout as pll_amd_posterior_edge_t.  Outputs are host arrays, each may be NULL (one at
+ * least is not); nothing of the context changes; scratch (kept by the context) is at most about scratch_bytes per
+ * chunk, at least one edge's worth.  Returns -1 for a bad argument (nothing launched, outputs untouched), -2 if a
+ * chunk's scratch cannot be had, -3 for a context this call does not take (asc-bias, site repeats, sharded, RCCL). */
+typedef struct pllhip_posterior_edge
+{
+  unsigned int parent_clv_index;
+  int parent_scaler_index;
+  unsigned int child_clv_index;
+  int child_scaler_index;
+  unsigned int matrix_index;
+} pllhip_posterior_edge_t;
+PLLHIP_EXPORT int pllhip_site_posteriors(pllhip_ctx_t * ctx, const pllhip_posterior_edge_t * h_edges,
+                                         unsigned int edge_count, const unsigned int * h_freqs_indices,
+                                         size_t scratch_bytes, double * h_state_probs,
+                                         unsigned char * h_best_state, double * h_best_prob, double * h_rate_probs,
+                                         double * h_site_rates);
+
 /* ---- multi-GPU: one process per GPU, RCCL sum of the scalar results ---- */
 PLLHIP_EXPORT int pllhip_comm_unique_id(void * id128);
 /* which RCCL the process uses: the file the collective symbols were bound to -- the copy already

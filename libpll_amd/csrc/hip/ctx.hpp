@@ -216,6 +216,9 @@ struct pllhip_ctx
   // batched branch-length calls (branch_opt.hip): sumtables, Newton states and partial sums of one chunk, kept the same way
   void * bo_scratch = nullptr;
   size_t bo_scratch_bytes = 0;
+  // site-posterior calls (posteriors.hip): the edge descriptors and the outputs of one chunk, kept the same way
+  void * post_scratch = nullptr;
+  size_t post_scratch_bytes = 0;
 
   // optional per-launch timing (pllhip_profile_*): one event pair per launch
   bool profiling = false;

@@ -287,6 +287,9 @@ class PllLibrary:
                 lib.pll_amd_optimize_branch_lengths.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_double,
                                                                 C.c_double, C.c_double, C.c_uint, _dp, _dp, _up,
                                                                 C.c_void_p]
+            if hasattr(lib, "pll_amd_site_posteriors"):
+                lib.pll_amd_site_posteriors.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]
 
     # -- library-level helpers -------------------------------------------------
     def errno(self):
@@ -502,6 +505,11 @@ BRANCH_DTYPE = np.dtype([("parent_clv_index", np.uint32), ("parent_scaler_index"
                          ("child_clv_index", np.uint32), ("child_scaler_index", np.int32)])
 BRANCH_CONVERGED, BRANCH_MAX_ITERS, BRANCH_NONFINITE = 0, 1, 2
 
+# pll_amd_posterior_edge_t (include/pll_amd.h)
+POSTERIOR_EDGE_DTYPE = np.dtype([("parent_clv_index", np.uint32), ("parent_scaler_index", np.int32),
+                                 ("child_clv_index", np.uint32), ("child_scaler_index", np.int32),
+                                 ("matrix_index", np.uint32)])
+
 
 class Partition:
     """A pll_partition_t* plus the calls that take it as first argument."""
@@ -682,6 +690,44 @@ class Partition:
             max_iters, _d(t), _d(lnl), _u(evals), status.ctypes.data)
         self._check(ok, "pll_amd_optimize_branch_lengths")
         return t, lnl, evals, status
+
+    def site_posteriors(self, edges, freqs_indices, want=("state_probs", "best", "rate_probs", "site_rates")):
+        """pll_amd_site_posteriors: a dict of numpy arrays, first axis the edge -- state_probs [edges][sites][states],
+        best_state / best_prob [edges][sites] (want "best": both; "best_state" / "best_prob": one), rate_probs
+        [edges][sites][rate_cats + 1], site_rates [edges][sites].  edges: rows of (parent_clv, parent_scaler,
+        child_clv, child_scaler, matrix_index) or a POSTERIOR_EDGE_DTYPE array."""
+        if not hasattr(self.lib, "pll_amd_site_posteriors"):
+            raise PllError("this library has no pll_amd_site_posteriors")
+        e = np.zeros(len(edges), dtype=POSTERIOR_EDGE_DTYPE)
+        if isinstance(edges, np.ndarray) and edges.dtype == POSTERIOR_EDGE_DTYPE:
+            e[:] = edges
+        else:
+            for i, row in enumerate(edges):
+                e[i] = tuple(row)
+        fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+        n, sites, S, R = len(e), self.s.sites, self.s.states, self.s.rate_cats
+        want = set(want)
+        if "best" in want:
+            want |= {"best_state", "best_prob"}
+        out = {}
+        if "state_probs" in want:
+            out["state_probs"] = np.zeros((n, sites, S))
+        if "best_state" in want:
+            out["best_state"] = np.zeros((n, sites), dtype=np.uint8)
+        if "best_prob" in want:
+            out["best_prob"] = np.zeros((n, sites))
+        if "rate_probs" in want:
+            out["rate_probs"] = np.zeros((n, sites, R + 1))
+        if "site_rates" in want:
+            out["site_rates"] = np.zeros((n, sites))
+
+        def ptr(name):
+            return out[name].ctypes.data if name in out and out[name].size else None
+        ok = self.lib.pll_amd_site_posteriors(self.ptr, e.ctypes.data if n else None, n, _u(fi), ptr("state_probs"),
+                                              ptr("best_state"), ptr("best_prob"), ptr("rate_probs"),
+                                              ptr("site_rates"))
+        self._check(ok, "pll_amd_site_posteriors")
+        return out
 
     # -- reading results back ----------------------------------------------------------
     def get_clv(self, idx):
