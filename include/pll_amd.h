@@ -882,6 +882,74 @@ PLL_EXPORT int pll_amd_site_posteriors(pll_partition_t * partition,
                                        double * rate_probs,         /* [edge][site][rate_cats + 1] or NULL */
                                        double * site_rates);        /* [edge][site]                or NULL */
 
+/* ---- batched NNI scoring: every inner edge's three quartets in one call (nni.c, nni.hip) ----
+ * One inner edge u -- v with the subtrees A, B hanging from u and C, D from v.  A side is the subtree's CLV pointing
+ * towards the edge (a tip or an inner CLV), its scale buffer, and the subtree's branch to u or v, which moves with
+ * the subtree when it changes places. */
+typedef struct pll_amd_nni_side
+{
+  unsigned int clv_index;    /* the subtree's CLV pointing towards the edge (a tip or an inner CLV) */
+  int          scaler_index; /* PLL_SCALE_BUFFER_NONE allowed */
+  double       length;       /* the subtree's branch to u or v; it moves with the subtree */
+} pll_amd_nni_side_t;
+
+typedef struct pll_amd_nni_edge
+{
+  pll_amd_nni_side_t side[4]; /* A, B (at u), C, D (at v) */
+  double             length;  /* u -- v */
+} pll_amd_nni_edge_t;
+
+#define PLL_AMD_NNI_AB_CD 0   /* the tree as it is */
+#define PLL_AMD_NNI_AC_BD 1   /* B and C change places */
+#define PLL_AMD_NNI_AD_BC 2   /* B and D change places */
+
+/* Arrangement k of an edge names (X, Y | Z, W): k = 0: (A, B | C, D); k = 1: (A, C | B, D); k = 2: (A, D | C, B).
+ * lnl[3 e + k] = the log-likelihood of the tree in which edge e's subtrees are arranged that way: what this sequence
+ * returns on the same partition -- pll_update_prob_matrices for the five lengths (x, y, z, w of the sides and the
+ * edge's) with params_indices into five spare matrices; pll_update_partials with two ops, a spare node u' with
+ * children X and Y and a spare node v' with children Z and W, each with a fresh scale buffer where scale_buffers > 0
+ * (else PLL_SCALE_BUFFER_NONE); pll_compute_edge_loglikelihood(u', its scaler, v', its scaler, the edge's matrix,
+ * freqs_indices = params_indices).  Both scaling modes, +I, a rate matrix per category, pattern tips or tip CLVs and
+ * pattern weights behave as in those calls.
+ * What lives where: P-matrices, partial sums and -- for shapes the quartet kernel does not take (anything but 4
+ * states with 1 or 4 rate categories and no per-rate scale buffers) -- the candidates' CLVs and scale buffers are
+ * scratch of the partition on its device, kept until it is destroyed; a call never changes a CLV, scale buffer,
+ * P-matrix, sumtable or host mirror.  Large batches are worked in chunks of at most about PLL_AMD_NNI_SCRATCH_MB
+ * (environment, read at call time, default 2048) of scratch, one edge at least; an edge's values are the same bits
+ * whatever else is in the batch, in whatever order, however the call chunks it, and arrangement k of (A, B, C, D) is
+ * the same bits as arrangement 0 of the edge given with its sides in arrangement k's order.  The call is synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, lnl untouched): CLV, scaler and params indices in
+ * range, lengths non-negative and finite, edge_count >= 1, no NULL array.
+ * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
+ * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
+ * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: optimising the four outer branches,
+ * applying a move to a tree, a builder of the all-directions op list.  INTEGRATION.md section 4e. */
+PLL_EXPORT int pll_amd_nni_loglikelihood(pll_partition_t * partition,
+                                         const pll_amd_nni_edge_t * edges, unsigned int edge_count,
+                                         const unsigned int * params_indices,
+                                         double * lnl);              /* out [edge][3] */
+
+/* The same candidates with the central branch re-optimised: for every edge and arrangement, independently, the rule
+ * written out at pll_amd_optimize_branch_lengths on the branch (u', v') of the sequence above -- D(t) from
+ * pll_update_sumtable(u', v', their scalers) and pll_compute_likelihood_derivatives --, started from the edge's
+ * `length`, the four outer lengths fixed.  lengths[3 e + k], lnl[3 e + k] (pll_compute_edge_loglikelihood(u', v') at
+ * that length), evals and status (PLL_AMD_BRANCH_*) with that call's meaning and its closeness to the host loop (a
+ * result lies within `tolerance` of it, not on it); lnl, evals and status may be NULL.
+ * What lives where, chunking (PLL_AMD_NNI_SCRATCH_MB; the candidates' sumtables and Newton states are scratch too),
+ * the bits of an edge's values, limits and errors as for pll_amd_nni_loglikelihood; a call never changes a CLV, scale
+ * buffer, P-matrix, sumtable slot or host mirror.  Checked before anything is launched (PLL_ERROR_PARAM_INVALID,
+ * outputs untouched): what pll_amd_nni_loglikelihood checks, 0 < min_length <= max_length and both finite,
+ * tolerance > 0 and finite, max_iters >= 1, no NULL array but lnl, evals and status. */
+PLL_EXPORT int pll_amd_nni_optimize(pll_partition_t * partition,
+                                    const pll_amd_nni_edge_t * edges, unsigned int edge_count,
+                                    const unsigned int * params_indices,
+                                    double min_length, double max_length,
+                                    double tolerance, unsigned int max_iters,
+                                    double * lengths,        /* out [edge][3] */
+                                    double * lnl,            /* out [edge][3], may be NULL */
+                                    unsigned int * evals,    /* out [edge][3], may be NULL */
+                                    int * status);           /* out [edge][3], may be NULL */
+
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets
  * threads create partitions concurrently -- WITH a process-wide default: a thread that has not set a device uses what

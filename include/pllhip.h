@@ -370,6 +370,37 @@ PLLHIP_EXPORT int pllhip_site_posteriors(pllhip_ctx_t * ctx, const pllhip_poster
                                          unsigned char * h_best_state, double * h_best_prob, double * h_rate_probs,
                                          double * h_site_rates);
 
+/* ---- batched NNI scoring (nni.hip; host side host/nni.c) ----
+ * For every inner edge, given by its four sides A, B (at u), C, D (at v) with their lengths and its own length, the
+ * three arrangements 0 (A, B | C, D), 1 (A, C | B, D), 2 (A, D | C, B): lnl[3 e + k] = what pllhip_update_pmatrices
+ * (the five lengths), pllhip_update_partials (two ops: u' from X and Y, v' from Z and W, fresh scale buffers when the
+ * context has scale buffers) and pllhip_edge_loglikelihood (u', v', the edge's matrix, freqs indices = params
+ * indices) would return; pllhip_nni_optimize: the rule of pllhip_optimize_branch_lengths on the branch (u', v')
+ * started from the edge's length, outputs [edge][3].  Same layout as pll_amd_nni_edge_t.  route: -1 the library's
+ * choice (the quartet kernel for 4 states with 1 or 4 rate categories and no per-rate scale buffers, the general
+ * route otherwise), 0 the general route, 1 the quartet kernel where it covers the partition.  Nothing of the context
+ * changes; scratch (kept by the context) is at most about scratch_bytes per chunk, at least one edge's worth.
+ * Returns -1 for a bad argument (nothing launched, outputs untouched), -2 if a chunk's scratch cannot be had, -3 for
+ * a context this call does not take (asc-bias, site repeats, sharded, RCCL). */
+typedef struct pllhip_nni_side
+{
+  unsigned int clv_index;
+  int scaler_index;
+  double length;
+} pllhip_nni_side_t;
+typedef struct pllhip_nni_edge
+{
+  pllhip_nni_side_t side[4];
+  double length;
+} pllhip_nni_edge_t;
+PLLHIP_EXPORT int pllhip_nni_loglikelihood(pllhip_ctx_t * ctx, const pllhip_nni_edge_t * h_edges,
+                                           unsigned int edge_count, const unsigned int * h_params_indices, int route,
+                                           size_t scratch_bytes, double * h_lnl);
+PLLHIP_EXPORT int pllhip_nni_optimize(pllhip_ctx_t * ctx, const pllhip_nni_edge_t * h_edges, unsigned int edge_count,
+                                      const unsigned int * h_params_indices, double min_length, double max_length,
+                                      double tolerance, unsigned int max_iters, int route, size_t scratch_bytes,
+                                      double * h_lengths, double * h_lnl, unsigned int * h_evals, int * h_status);
+
 /* ---- multi-GPU: one process per GPU, RCCL sum of the scalar results ---- */
 PLLHIP_EXPORT int pllhip_comm_unique_id(void * id128);
 /* which RCCL the process uses: the file the collective symbols were bound to -- the copy already

@@ -22,52 +22,12 @@
 //
 // Determinism: tiles are BO_TILE sites, a branch's partial sums depend on nothing but its own table and length, and
 // every sum runs in a fixed order: a branch's result does not depend on the batch, its order or the chunking.
-#include "lnl_common.hpp"
+#include "branch_opt.hpp"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <vector>
-
-#define BO_TILE 256 // sites per workgroup of k_bo_pass (64 per wave); a branch's partial sums are per tile
-#define BO_CHECK 4   // Newton steps enqueued between two looks at the count of active branches
-
-struct BoState
-{
-  double t, lo, hi;
-  unsigned int evals;
-  int status;
-  int active;
-  int pad;
-};
-
-// the scale buffers a branch's table and lnL count (pllhip_update_sumtable / pllhip_edge_loglikelihood: with a
-// pattern tip on one side, only the inner side's)
-struct BoSides
-{
-  const unsigned int * ps;
-  const unsigned int * cs;
-};
-
-struct BoPassArgs
-{
-  const double * __restrict__ tables;      // [branches][table_stride]
-  const BoState * __restrict__ st;         // [branches]
-  const BoSides * __restrict__ sides;      // [branches]
-  const double * __restrict__ eigenvals;   // [rate_matrices][S]
-  const double * __restrict__ rates;       // [R]
-  const double * __restrict__ prop_invar;  // [rate_matrices]
-  const double * __restrict__ rate_weights;
-  const double * __restrict__ freqs;
-  const unsigned int * __restrict__ pattern_weights;
-  const int * __restrict__ invariant;      // nullptr = no +I
-  double * __restrict__ partial;           // [branches][tiles][2]
-  size_t table_stride;
-  unsigned int sites, states, rate_cats, tiles;
-  int lnl;          // 0: (d, dd) of the active branches; 1: lnL of every branch (one component)
-  int rate_scalers; // lnL pass: per-rate scale buffers
-  unsigned int params[PLLHIP_MAX_RATE_CATS];
-};
 
 // per-rate scaling of every table of a chunk: k_sumtable_rescale (derivatives.hip), one branch per blockIdx.y
 __global__ __launch_bounds__(256) void k_bo_rescale(double * __restrict__ tables, const BoSides * __restrict__ sides,
@@ -361,6 +321,57 @@ static int bo_launch_pass(pllhip_ctx * c, const BoPassArgs & a, unsigned int nb)
   return 0;
 }
 
+int pllhip_bo_rescale(pllhip_ctx * c, double * tables, const BoSides * sides, unsigned int nb)
+{
+  const size_t sites = c->sh.sites;
+  const unsigned int gx = (unsigned int)std::min<size_t>((sites + 255) / 256, 1024);
+  k_bo_rescale<<<dim3(gx, nb), 256, 0, c->stream>>>(tables, sides, c->clv_stride, (unsigned int)sites,
+                                                    c->sh.rate_cats, c->sh.states);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int pllhip_bo_newton(pllhip_ctx * c, BoPassArgs & pa, const BoBuffers & bf, unsigned int nb, double tolerance,
+                     unsigned int max_iters, BoState * h_state, double * h_lnl)
+{
+  int rc;
+  const unsigned int tiles = pa.tiles;
+  unsigned int * h_cnt = (unsigned int *)c->h_stage;
+  // ---- Newton steps: (pass, step) pairs back to back, a look at the active count every BO_CHECK steps
+  pa.lnl = 0;
+  for (unsigned int it = 0; it < max_iters;)
+  {
+    const unsigned int wn = std::min<unsigned int>(BO_CHECK, max_iters - it);
+    for (unsigned int j = 0; j < wn; ++j)
+    {
+      if ((rc = bo_launch_pass(c, pa, nb))) return rc;
+      const bool last = j + 1 == wn;
+      if (last) HIP_TRY(hipMemsetAsync(bf.count, 0, 4, c->stream));
+      k_bo_step<<<nb, 64, 0, c->stream>>>(bf.state, bf.partial, tiles, tolerance, max_iters,
+                                          last ? bf.count : nullptr);
+      HIP_TRY(hipGetLastError());
+    }
+    it += wn;
+    if (it >= max_iters) break;
+    HIP_TRY(hipMemcpyAsync(h_cnt, bf.count, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (*h_cnt == 0) break;
+  }
+
+  // ---- lnL at the final lengths
+  if (h_lnl)
+  {
+    pa.lnl = 1;
+    if ((rc = bo_launch_pass(c, pa, nb))) return rc;
+    k_bo_finish<<<nb, 64, 0, c->stream>>>(bf.partial, bf.lnl, tiles);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_lnl, bf.lnl, nb * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(h_state, bf.state, nb * sizeof(BoState), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_branch_t * B, unsigned int count,
                                               const unsigned int * params, double min_length, double max_length,
                                               double tolerance, unsigned int max_iters, size_t budget,
@@ -500,7 +511,7 @@ extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_bra
   std::vector<BoState> hs(nc);
   std::vector<BoSides> hsd(nc);
   std::vector<double> hl(nc);
-  unsigned int * h_cnt = (unsigned int *)c->h_stage;
+  const BoBuffers bf = {d_state, d_part, d_lnl, d_cnt};
   for (unsigned int b0 = 0; b0 < count; b0 += nc)
   {
     const unsigned int nb = std::min(nc, count - b0);
@@ -569,44 +580,9 @@ extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_bra
         }
       }
     }
-    if (c->sh.rate_scalers && nsc > 0)
-    {
-      const unsigned int gx = (unsigned int)std::min<size_t>((sites + 255) / 256, 1024);
-      k_bo_rescale<<<dim3(gx, nb), 256, 0, c->stream>>>(d_tab, d_sides, c->clv_stride, (unsigned int)sites, R, S);
-      HIP_TRY(hipGetLastError());
-    }
-
-    // ---- Newton steps: (pass, step) pairs back to back, a look at the active count every BO_CHECK steps
-    pa.lnl = 0;
-    for (unsigned int it = 0; it < max_iters;)
-    {
-      const unsigned int wn = std::min<unsigned int>(BO_CHECK, max_iters - it);
-      for (unsigned int j = 0; j < wn; ++j)
-      {
-        if ((rc = bo_launch_pass(c, pa, nb))) return rc;
-        const bool last = j + 1 == wn;
-        if (last) HIP_TRY(hipMemsetAsync(d_cnt, 0, 4, c->stream));
-        k_bo_step<<<nb, 64, 0, c->stream>>>(d_state, d_part, tiles, tolerance, max_iters, last ? d_cnt : nullptr);
-        HIP_TRY(hipGetLastError());
-      }
-      it += wn;
-      if (it >= max_iters) break;
-      HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, 4, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (*h_cnt == 0) break;
-    }
-
-    // ---- lnL at the final lengths
-    if (h_lnl)
-    {
-      pa.lnl = 1;
-      if ((rc = bo_launch_pass(c, pa, nb))) return rc;
-      k_bo_finish<<<nb, 64, 0, c->stream>>>(d_part, d_lnl, tiles);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(hl.data(), d_lnl, nb * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(hs.data(), d_state, nb * sizeof(BoState), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->sh.rate_scalers && nsc > 0 && (rc = pllhip_bo_rescale(c, d_tab, d_sides, nb))) return rc;
+    if ((rc = pllhip_bo_newton(c, pa, bf, nb, tolerance, max_iters, hs.data(), h_lnl ? hl.data() : nullptr)))
+      return rc;
     for (unsigned int i = 0; i < nb; ++i)
     {
       h_lengths[b0 + i] = hs[i].t;

@@ -1,0 +1,62 @@
+// branch_opt.hpp -- internal: what branch_opt.hip shares with the other batched Newton caller (nni.hip): the Newton
+// state of a branch, the argument block of k_bo_pass, and the part of a chunk's work that starts once the sumtables
+// and the per-site scaler counts are in scratch.
+#pragma once
+#include "lnl_common.hpp"
+
+#define BO_TILE 256 // sites per workgroup of k_bo_pass (64 per wave); a branch's partial sums are per tile
+#define BO_CHECK 4   // Newton steps enqueued between two looks at the count of active branches
+
+struct BoState
+{
+  double t, lo, hi;
+  unsigned int evals;
+  int status;
+  int active;
+  int pad;
+};
+
+// the scale buffers a branch's table and lnL count (pllhip_update_sumtable / pllhip_edge_loglikelihood: with a
+// pattern tip on one side, only the inner side's)
+struct BoSides
+{
+  const unsigned int * ps;
+  const unsigned int * cs;
+};
+
+struct BoPassArgs
+{
+  const double * __restrict__ tables;      // [branches][table_stride]
+  const BoState * __restrict__ st;         // [branches]
+  const BoSides * __restrict__ sides;      // [branches]
+  const double * __restrict__ eigenvals;   // [rate_matrices][S]
+  const double * __restrict__ rates;       // [R]
+  const double * __restrict__ prop_invar;  // [rate_matrices]
+  const double * __restrict__ rate_weights;
+  const double * __restrict__ freqs;
+  const unsigned int * __restrict__ pattern_weights;
+  const int * __restrict__ invariant;      // nullptr = no +I
+  double * __restrict__ partial;           // [branches][tiles][2]
+  size_t table_stride;
+  unsigned int sites, states, rate_cats, tiles;
+  int lnl;          // 0: (d, dd) of the active branches; 1: lnL of every branch (one component)
+  int rate_scalers; // lnL pass: per-rate scale buffers
+  unsigned int params[PLLHIP_MAX_RATE_CATS];
+};
+
+// the buffers of one chunk (device): Newton states, partial sums [branches][tiles][2], lnL [branches], one counter
+struct BoBuffers
+{
+  BoState * state;
+  double * partial;
+  double * lnl;
+  unsigned int * count;
+};
+
+// per-rate scale buffers: every table of the chunk brought to its sites' smallest counts (k_bo_rescale)
+int pllhip_bo_rescale(pllhip_ctx * c, double * tables, const BoSides * sides, unsigned int nb);
+// From "tables, sides and start states are in scratch" on: the (pass, step) pairs of the rule, the lnL pass at the
+// final lengths when h_lnl is not null, the states (and lnL) of the chunk's nb branches back on the host; waits for
+// the stream.  pa: everything but `lnl` filled in (tables, st, sides, partial point into the chunk's scratch).
+int pllhip_bo_newton(pllhip_ctx * c, BoPassArgs & pa, const BoBuffers & bf, unsigned int nb, double tolerance,
+                     unsigned int max_iters, BoState * h_state, double * h_lnl);

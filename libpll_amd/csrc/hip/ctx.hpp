@@ -219,6 +219,10 @@ struct pllhip_ctx
   // site-posterior calls (posteriors.hip): the edge descriptors and the outputs of one chunk, kept the same way
   void * post_scratch = nullptr;
   size_t post_scratch_bytes = 0;
+  // NNI calls (nni.hip): P-matrices, edge descriptors, partial sums and -- where a route needs them -- the
+  // candidates' CLVs, scale buffers and sumtables of one chunk, kept the same way
+  void * nni_scratch = nullptr;
+  size_t nni_scratch_bytes = 0;
 
   // optional per-launch timing (pllhip_profile_*): one event pair per launch
   bool profiling = false;

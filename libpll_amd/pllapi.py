@@ -287,6 +287,10 @@ class PllLibrary:
                 lib.pll_amd_optimize_branch_lengths.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_double,
                                                                 C.c_double, C.c_double, C.c_uint, _dp, _dp, _up,
                                                                 C.c_void_p]
+            if hasattr(lib, "pll_amd_nni_loglikelihood"):
+                lib.pll_amd_nni_loglikelihood.argtypes = [_PP, C.c_void_p, C.c_uint, _up, _dp]
+                lib.pll_amd_nni_optimize.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_double, C.c_double,
+                                                     C.c_double, C.c_uint, _dp, _dp, _up, C.c_void_p]
             if hasattr(lib, "pll_amd_site_posteriors"):
                 lib.pll_amd_site_posteriors.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p]
@@ -510,6 +514,24 @@ POSTERIOR_EDGE_DTYPE = np.dtype([("parent_clv_index", np.uint32), ("parent_scale
                                  ("child_clv_index", np.uint32), ("child_scaler_index", np.int32),
                                  ("matrix_index", np.uint32)])
 
+# pll_amd_nni_edge_t (include/pll_amd.h): the sides A, B (at u), C, D (at v), then the edge's own length
+NNI_SIDE_DTYPE = np.dtype([("clv_index", np.uint32), ("scaler_index", np.int32), ("length", np.float64)])
+NNI_EDGE_DTYPE = np.dtype([("side", NNI_SIDE_DTYPE, (4,)), ("length", np.float64)])
+NNI_AB_CD, NNI_AC_BD, NNI_AD_BC = 0, 1, 2
+
+
+def nni_edges(edges):
+    """an NNI_EDGE_DTYPE array from rows of ((clv, scaler, length) x 4, length), or from such an array"""
+    e = np.zeros(len(edges), dtype=NNI_EDGE_DTYPE)
+    if isinstance(edges, np.ndarray) and edges.dtype == NNI_EDGE_DTYPE:
+        e[:] = edges
+    else:
+        for i, (sides, length) in enumerate(edges):
+            for k, sd in enumerate(sides):
+                e[i]["side"][k] = tuple(sd)
+            e[i]["length"] = length
+    return e
+
 
 class Partition:
     """A pll_partition_t* plus the calls that take it as first argument."""
@@ -689,6 +711,31 @@ class Partition:
             self.ptr, b.ctypes.data if len(b) else None, len(b), _u(pi), min_length, max_length, tolerance,
             max_iters, _d(t), _d(lnl), _u(evals), status.ctypes.data)
         self._check(ok, "pll_amd_optimize_branch_lengths")
+        return t, lnl, evals, status
+
+    def nni_loglikelihood(self, edges, params_indices):
+        """pll_amd_nni_loglikelihood: an (edges, 3) array, column k the arrangement PLL_AMD_NNI_* = k.  edges: rows of
+        (((clv, scaler, length) of A, B, C, D), length) or an NNI_EDGE_DTYPE array."""
+        e = nni_edges(edges)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        out = np.zeros((len(e), 3))
+        ok = self.lib.pll_amd_nni_loglikelihood(self.ptr, e.ctypes.data if len(e) else None, len(e), _u(pi), _d(out))
+        self._check(ok, "pll_amd_nni_loglikelihood")
+        return out
+
+    def nni_optimize(self, edges, params_indices, min_length=1e-6, max_length=100.0, tolerance=1e-7, max_iters=64):
+        """pll_amd_nni_optimize: (lengths, lnl, evals, status), each an (edges, 3) array; edges as for
+        nni_loglikelihood."""
+        e = nni_edges(edges)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        t = np.zeros((len(e), 3))
+        lnl = np.zeros((len(e), 3))
+        evals = np.zeros((len(e), 3), dtype=np.uint32)
+        status = np.zeros((len(e), 3), dtype=np.int32)
+        ok = self.lib.pll_amd_nni_optimize(self.ptr, e.ctypes.data if len(e) else None, len(e), _u(pi), min_length,
+                                           max_length, tolerance, max_iters, _d(t), _d(lnl), _u(evals),
+                                           status.ctypes.data)
+        self._check(ok, "pll_amd_nni_optimize")
         return t, lnl, evals, status
 
     def site_posteriors(self, edges, freqs_indices, want=("state_probs", "best", "rate_probs", "site_rates")):
