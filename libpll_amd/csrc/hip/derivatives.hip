@@ -507,10 +507,11 @@ __global__ __launch_bounds__(256) void k_derivatives_dna(DerivArgs a)
       c0 += dpp_pair_swap(c0);
       c1 += dpp_pair_swap(c1);
       c2 += dpp_pair_swap(c2);
+      // held by the lane that owns the site; outside the per-lane branch below, so that every lane takes part
+      const int inv = has_inv ? __shfl(inv_own, (int)(grp0 + j), 64) : -1;
       if (pinv > 0.0)
       {
         // core_derivatives.c:481-491
-        const int inv = __shfl(inv_own, (int)(grp0 + j), 64); // held by the lane that owns the site
         const double inv_lk = (inv == -1) ? 0.0 : a.freqs[(size_t)pi * 4 + inv] * pinv;
         c0 = c0 * (1.0 - pinv) + inv_lk;
         c1 = c1 * (1.0 - pinv);

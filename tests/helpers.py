@@ -107,16 +107,89 @@ def case_map(lib, case):
     return lib.map("nt" if case["states"] == 4 else "aa")
 
 
+def params_of(case):
+    """params_indices of a case: the mixture's (`mixture`), or one rate matrix for every category"""
+    return list(case.get("params_indices") or [0] * case["rate_cats"])
+
+
+def freqs_of(case):
+    """freqs_indices of a case: its own where the mixture names them, its params_indices otherwise"""
+    return list(case.get("freqs_indices") or params_of(case))
+
+
+def case_pinvs(case, pinv=0.0):
+    """+I proportion of every rate matrix: the mixture's `pinvs`, or `pinv` for the one matrix"""
+    if case.get("models") is None:
+        return [float(pinv)]
+    assert not pinv, "a mixture case carries its own pinvs"
+    return [float(v) for v in (case.get("pinvs") or [0.0] * len(case["models"]))]
+
+
+def mixture(case, lib, seed, variant=0, pinv=False, params_indices=None):
+    """Decorate a case (make_case / odd_state_case / many_state_case) with a model that no kernel gets right by
+    accident: M = min(R, 3) rate matrices (2 at R = 1) of which the case's own is number 0, params_indices[k] =
+    M - 1 - k % M (never 0 first, never the identity, shared where R > M), category weights that are unequal and sum
+    to 1.3, and -- pinv -- distinct +I proportions, one of them 0.  variant 1: freqs_indices that differ from
+    params_indices (odd k: the next matrix's; R = 1: matrix 0's).  params_indices: a list to use instead (deep trees
+    of random data, where only the fastest category carries weight and ITS entry has to differ from 0 and from k)."""
+    S, R = case["states"], case["rate_cats"]
+    M = 2 if R == 1 else min(R, 3)
+    rng = np.random.default_rng(7000 + seed)
+    models = [(case["rates"], case["freqs"])]
+    for _ in range(M - 1):
+        models.append((rng.uniform(0.3, 4.0, S * (S - 1) // 2), rng.dirichlet(np.ones(S) * 6)))
+    case["models"] = models
+    case["params_indices"] = list(params_indices or [M - 1 - k % M for k in range(R)])
+    assert len(case["params_indices"]) == R and max(case["params_indices"]) == M - 1
+    if variant:
+        case["freqs_indices"] = ([0] if R == 1 else
+                                 [(i + k % 2) % M for k, i in enumerate(case["params_indices"])])
+        assert case["freqs_indices"] != case["params_indices"]
+    case["cat_weights"] = rng.dirichlet(np.ones(R)) * 1.3
+    if pinv:
+        case["pinvs"] = [0.0, 0.25] if M == 2 else [0.1, 0.0, 0.3]
+    return case
+
+
+def stale_freqs_defect(case, attrs, edge, plan):
+    """Does the genuine reference give a wrong value here?  Its 4-state tip-inner edge kernel (pattern tips) fills a
+    lookup table category by category and then, in its site loop, takes the invariant-site term of EVERY category from
+    the frequencies pointer the table loop left behind -- the last category's (core_likelihood_avx.c:274 and
+    :371).  With one frequency set, or without +I, that is the right pointer; in a mixture with +I it is not."""
+    return (case["states"] == 4 and bool(attrs & ATTRIB_PATTERN_TIP) and min(edge[0], edge[2]) < plan.tips
+            and len(set(freqs_of(case))) > 1 and max(case.get("pinvs") or [0.0]) > 0)
+
+
+def undo_stale_freqs_defect(case, model, invariant, per_site):
+    """The reference's per-site lnL of an edge under stale_freqs_defect, put right: at an invariant site its likelihood
+    is off by sum_k w_k pinv_k (f_last[i] - f_k[i]) -- the last category's frequency of the site's state i in place of
+    each category's own -- and nothing else.  model: model_of(the reference partition); for edges without scaling
+    (site likelihood = exp(lnl / pattern weight): the caller asserts the counts are 0)."""
+    fi, w = freqs_of(case), np.asarray(case["cat_weights"], dtype=np.float64)
+    fr, pinvs = model["freqs"], model["pinvs"]
+    pw = np.ones(len(per_site)) if case["pw"] is None else np.asarray(case["pw"], dtype=np.float64)
+    out = np.array(per_site, dtype=np.float64)
+    for n in np.flatnonzero(np.asarray(invariant) >= 0):
+        i = int(invariant[n])
+        delta = sum(w[k] * pinvs[fi[k]] * (fr[fi[-1]][i] - fr[fi[k]][i]) for k in range(len(fi)))
+        out[n] = np.log(np.exp(per_site[n] / pw[n]) - delta) * pw[n]
+    return out
+
+
 def build_partition(lib, case, attrs, pinv=0.0):
     """Create + fill a partition on `lib`; returns it with P-matrices computed."""
     plan, S, R = case["plan"], case["states"], case["rate_cats"]
     if lib.is_amd:
         attrs &= ~0xF
-    p = lib.partition_create(plan.tips, plan.clv_buffers, S, case["sites"], 1, plan.prob_matrices,
+    models = case.get("models") or [(case["rates"], case["freqs"])]
+    p = lib.partition_create(plan.tips, plan.clv_buffers, S, case["sites"], len(models), plan.prob_matrices,
                              R, plan.scale_buffers, attrs)
-    p.set_frequencies(0, case["freqs"])
-    p.set_subst_params(0, case["rates"])
+    for i, (rates, freqs) in enumerate(models):
+        p.set_frequencies(i, freqs)
+        p.set_subst_params(i, rates)
     p.set_category_rates(lib.compute_gamma_cats(case["alpha"], R))
+    if case.get("cat_weights") is not None:
+        p.set_category_weights(case["cat_weights"])
     if case.get("tip_index") is not None:
         for i, clv in enumerate(index_tip_clvs(case)):
             p.set_tip_clv(i, clv[:, 0, :].reshape(-1))   # [sites][states]; the call replicates over rates
@@ -126,17 +199,28 @@ def build_partition(lib, case, attrs, pinv=0.0):
             p.set_tip_states(i, cmap, s)
     if case["pw"] is not None:
         p.set_pattern_weights(case["pw"])
-    if pinv > 0:
-        p.update_invariant_sites_proportion(0, pinv)
-    p.update_prob_matrices([0] * R, plan.matrix_indices, plan.branch_lengths)
+    for i, v in enumerate(case_pinvs(case, pinv)):
+        if v > 0:
+            p.update_invariant_sites_proportion(i, v)
+    p.update_prob_matrices(params_of(case), plan.matrix_indices, plan.branch_lengths)
     return p
 
 
 def model_of(part, lib, case, pinv=0.0):
     """Model arrays as the partition holds them on the host (eigen system from
-    pll_update_eigen, category rates from pll_compute_gamma_cats)."""
-    vals, vecs, inv = part.get_eigen(0)
+    pll_update_eigen, category rates from pll_compute_gamma_cats).  A mixture case (`mixture`): eigen systems,
+    frequencies and pinvs are lists with one entry per rate matrix, next to the two index lists and the weights."""
     S, R = case["states"], case["rate_cats"]
+    if case.get("models") is not None:
+        eig = [part.get_eigen(i) for i in range(len(case["models"]))]
+        fr = [np.ctypeslib.as_array(part.s.frequencies[i], shape=(part.s.states_padded,)).copy()[:S]
+              for i in range(len(case["models"]))]
+        # (the case's own weights, not what the partition under test stored of them: the library does not touch them)
+        w = np.full(R, 1.0 / R) if case.get("cat_weights") is None else np.array(case["cat_weights"], dtype=np.float64)
+        return dict(states=S, rate_cats=R, rates=lib.compute_gamma_cats(case["alpha"], R), rate_weights=w,
+                    eigenvals=[e[0] for e in eig], eigenvecs=[e[1] for e in eig], inv_eigenvecs=[e[2] for e in eig],
+                    freqs=fr, pinvs=case_pinvs(case), params_indices=params_of(case), freqs_indices=freqs_of(case))
+    vals, vecs, inv = part.get_eigen(0)
     fr = np.ctypeslib.as_array(part.s.frequencies[0], shape=(part.s.states_padded,)).copy()[:S]
     return dict(states=S, rate_cats=R, rates=lib.compute_gamma_cats(case["alpha"], R),
                 rate_weights=np.full(R, 1.0 / R), eigenvals=vals, eigenvecs=vecs,
@@ -170,9 +254,11 @@ def invariant_of(part):
     return np.ctypeslib.as_array(s.invariant, shape=(s.sites,)).copy()
 
 
-def oracle_run(orc, lib, part, case, attrs, pinv=0.0):
+def oracle_run(orc, lib, part, case, attrs, pinv=0.0, override=None):
+    """override: entries of the model to replace (`model_variants`)"""
     model = model_of(part, lib, case, pinv)
-    inv = invariant_of(part) if pinv > 0 else None
+    model.update(override or {})
+    inv = invariant_of(part) if max(case_pinvs(case, pinv)) > 0 else None
     if attrs & ATTRIB_PATTERN_TIP:
         codes, tipmap = encode_tips(part)
         return OracleRun(orc, model, case["plan"], attrs, tipcodes=codes, tipmap=tipmap,
@@ -182,6 +268,52 @@ def oracle_run(orc, lib, part, case, attrs, pinv=0.0):
                          pattern_weights=case["pw"], invariant=inv)
     return OracleRun(orc, model, case["plan"], attrs, tipclvs=tip_clvs(case, case_map(lib, case)),
                      pattern_weights=case["pw"], invariant=inv)
+
+
+def model_variants(model):
+    """{name: entries to replace} -- the mistakes a kernel could make with a mixture's per-category inputs, as
+    changes to the ORACLE's model (oracle_run(..., override=)): the mean weight for every category, 1 / R for every
+    category, the identity for the indices (modulo the number of rate matrices), index 0 for every category, the
+    first matrix's +I proportion for every matrix.  Only those that change the model at all."""
+    R, M = model["rate_cats"], len(model["eigenvals"])
+    pi, fi, w = list(model["params_indices"]), list(model["freqs_indices"]), np.asarray(model["rate_weights"])
+    pinvs = list(model.get("pinvs") or [0.0] * M)
+    out = {}
+    if not np.allclose(w, w.mean(), rtol=1e-3):
+        out["mean-weight"] = dict(rate_weights=np.full(R, w.mean()))
+    if not np.allclose(w, 1.0 / R, rtol=1e-3):
+        out["weights-1/R"] = dict(rate_weights=np.full(R, 1.0 / R))
+    ident = [k % M for k in range(R)]
+    for name, idx in (("identity", ident), ("all-zero", [0] * R)):
+        if idx != pi or idx != fi:
+            out["indices-" + name] = dict(params_indices=idx, freqs_indices=idx)
+    if any(v != pinvs[0] for v in pinvs):
+        out["pinvs[0]"] = dict(pinvs=[pinvs[0]] * M)
+    return out
+
+
+def assert_discriminates(orc, lib, part, case, attrs, edge=None, floor=1e-6):
+    """On the oracle alone: every mistake of model_variants moves the edge lnL of this mixture case by more than
+    `floor` relative -- nine orders of magnitude above the bounds the product is held to -- so a kernel that made it
+    would fail.  The weights and indices variants must exist wherever the shape allows them (R > 1)."""
+    edge = tuple(edge or case["plan"].root_edge)
+    base = oracle_run(orc, lib, part, case, attrs)
+    base.update_partials()
+    want = base.edge_loglikelihood(*edge)
+    variants = model_variants(base.m)
+    need = {"weights-1/R", "indices-all-zero"}
+    if case["rate_cats"] > 1:
+        need |= {"mean-weight", "indices-identity"}
+    if case.get("pinvs"):
+        need.add("pinvs[0]")
+        assert base.invariant is not None and (base.invariant >= 0).any(), "no invariant site in the fixture"
+    assert need <= set(variants), "fixture is degenerate: %s" % sorted(need - set(variants))
+    for name, change in variants.items():
+        o = oracle_run(orc, lib, part, case, attrs, override=change)
+        o.update_partials()
+        got = o.edge_loglikelihood(*edge)
+        assert abs(got - want) > floor * abs(want), "fixture does not tell %s apart: %r %r" % (name, got, want)
+    return base
 
 
 def bits_equal(a, b):
@@ -242,17 +374,24 @@ def derivative_magnitudes(model, sumtable, t, pattern_weights=None, invariant=No
     what is left of the eigenvalues that are zero in exact arithmetic, and (L'/L)^2 and L''/L agree to the last
     bits -- a total near zero, against which rounding of the terms would look large."""
     S, R = model["states"], model["rate_cats"]
-    pinv = float(model.get("pinv", 0.0))
-    x = np.asarray(model["eigenvals"])[None, :] * (np.asarray(model["rates"]) / (1.0 - pinv))[:, None]
+    if model.get("params_indices") is None:
+        pinv = np.full(R, float(model.get("pinv", 0.0)))
+        vals = np.repeat(np.asarray(model["eigenvals"])[None, :], R, axis=0)
+        fr = np.repeat(np.asarray(model["freqs"])[None, :], R, axis=0)
+    else:   # a mixture: category k has the eigenvalues, frequencies and pinv of rate matrix params_indices[k]
+        pi = list(model["params_indices"])
+        pinv = np.asarray(model.get("pinvs") or [0.0] * len(model["eigenvals"]), dtype=np.float64)[pi]
+        vals = np.asarray(model["eigenvals"])[pi]
+        fr = np.asarray(model["freqs"])[pi]
+    x = vals * (np.asarray(model["rates"]) / (1.0 - pinv))[:, None]
     e = np.exp(x * t)
     st = np.asarray(sumtable, dtype=np.float64).reshape(-1, R, S)
     w = np.asarray(model["rate_weights"])
-    fr = np.asarray(model["freqs"])
     lk = [(st * (e * x ** i)[None]).sum(axis=2) for i in range(3)]
-    if pinv > 0:
+    if pinv.max() > 0:
         inv = np.full(st.shape[0], -1) if invariant is None else np.asarray(invariant)
-        inv_lk = np.where(inv >= 0, fr[np.maximum(inv, 0)], 0.0) * pinv
-        lk = [lk[0] * (1 - pinv) + inv_lk[:, None], lk[1] * (1 - pinv), lk[2] * (1 - pinv)]
+        inv_lk = np.where((inv >= 0)[:, None], fr[:, np.maximum(inv, 0)].T, 0.0) * pinv[None, :]
+        lk = [lk[0] * (1 - pinv)[None, :] + inv_lk, lk[1] * (1 - pinv)[None, :], lk[2] * (1 - pinv)[None, :]]
     L0, L1, L2 = [(v * w[None, :]).sum(axis=1) for v in lk]
     pw = np.ones(st.shape[0]) if pattern_weights is None else np.asarray(pattern_weights, dtype=np.float64)
     d1, d2 = L1 / L0, L2 / L0

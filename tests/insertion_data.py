@@ -40,7 +40,11 @@ class InsertionCase:
 
     def __init__(self, states=4, tips=12, sites=300, rate_cats=4, seed=1, tip_queries=3, inner_queries=1,
                  caterpillar=False, per_cat_models=False, pattern_tip=True, rate_scalers=False, scalers=True,
-                 pinv=0.0, weights=True):
+                 pinv=0.0, weights=True, params=None, cat_weights=False, constant=0):
+        """params="shared": min(R, 3) rate matrices (2 at R = 1) shared between the categories through
+        params[k] = M - 1 - k % M -- never 0 first, never the identity -- with +I proportions that differ between the
+        matrices (0 for one of them) where pinv > 0.  cat_weights: unequal category weights that sum to 1.3.
+        constant: every constant-th column shows one state in every tip, so that +I has sites to act on."""
         rng = np.random.default_rng(seed)
         self.states, self.sites, self.rate_cats, self.pinv = states, sites, rate_cats, pinv
         self.n = tips
@@ -76,7 +80,17 @@ class InsertionCase:
         self.pattern_tip = pattern_tip
         self.per_cat_models = per_cat_models
         self.params = [0, 1, 2, 3][:rate_cats] if per_cat_models else [0] * rate_cats
+        if params == "shared":
+            M = 2 if rate_cats == 1 else min(rate_cats, 3)
+            self.params = [M - 1 - k % M for k in range(rate_cats)]
+        else:
+            assert params is None
         self.nmodels = max(self.params) + 1
+        self.pinvs = [pinv] * self.nmodels
+        if params == "shared" and pinv > 0:
+            self.pinvs = [0.0, pinv] if self.nmodels == 2 else [pinv / 2, 0.0, pinv]
+        # (a generator of its own: the draws below stay what they were before these options existed)
+        self.cat_weights = np.random.default_rng(seed + 4000).dirichlet(np.ones(rate_cats)) * 1.3 if cat_weights else None
         self.rng = rng
         self.models = [(rng.uniform(0.5, 3.0, states * (states - 1) // 2), rng.dirichlet(np.ones(states) * 6))
                        for _ in range(self.nmodels)]
@@ -109,6 +123,13 @@ class InsertionCase:
             idx = rng.integers(0, states, size=(self.ntips, sites))
             idx[rng.random((self.ntips, sites)) < 0.03] = -1
             self.tip_index = idx
+        if constant:
+            alphabet = {4: NT, 20: b"ARNDCQEGHILKMFPSTWYV"}.get(states, b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdef")
+            seqs = [bytearray(q) for q in self.seqs]
+            for col in range(0, sites, constant):
+                for q in seqs:
+                    q[col] = alphabet[(col // constant) % states]
+            self.seqs = [bytes(q) for q in seqs]
 
     def _directed(self):
         n = self.n
@@ -185,9 +206,11 @@ def build(lib, case):
             p.set_tip_clv(i, clv.reshape(-1))
     if case.pw is not None:
         p.set_pattern_weights(case.pw)
-    if case.pinv > 0:
-        for i in range(case.nmodels):
-            p.update_invariant_sites_proportion(i, case.pinv)
+    if case.cat_weights is not None:
+        p.set_category_weights(case.cat_weights)
+    for i, v in enumerate(case.pinvs):
+        if v > 0:
+            p.update_invariant_sites_proportion(i, v)
     nm = len(case.lengths)
     p.update_prob_matrices(case.params, list(range(nm)), case.lengths)
     ops = np.zeros(len(case.ops), dtype=OPS_DTYPE)
@@ -216,3 +239,36 @@ def queries_of(case, rng=None):
     s = [-1] * len(case.query_tips) + list(case.query_inner_sc)
     pl = rng.uniform(0.02, 0.6, len(q))
     return q, s, pl
+
+
+def as_case(case):
+    """the case as tests/helpers.py describes one (a dict with a plan), so that helpers.oracle_run and
+    helpers.assert_discriminates take it: every directed CLV of the tree, the queries' subtrees included"""
+    import types
+    from libpll_amd.pllapi import OPS_DTYPE
+    ops = np.zeros(len(case.ops), dtype=OPS_DTYPE)
+    for i, op in enumerate(case.ops):
+        ops[i] = op
+    nm = len(case.lengths)
+    plan = types.SimpleNamespace(tips=case.ntips, nodes=case.ntips + case.nclv, scale_buffers=case.nscale,
+                                 prob_matrices=case.nmat, matrix_indices=list(range(nm)),
+                                 branch_lengths=case.lengths, ops=ops)
+    return dict(states=case.states, rate_cats=case.rate_cats, tips=case.ntips, sites=case.sites, seqs=case.seqs,
+                tip_index=getattr(case, "tip_index", None), cmap=getattr(case, "cmap", None), pw=case.pw, alpha=0.6, plan=plan,
+                models=case.models, params_indices=list(case.params), cat_weights=case.cat_weights,
+                pinvs=list(case.pinvs))
+
+
+def assert_discriminates(orc, lib, p, case):
+    """helpers.assert_discriminates for a case of this file, at an inner edge of its tree (both sides inner where the
+    tree has such an edge): on the oracle alone, the mean weight or 1 / R for every category, the identity or 0 for
+    every index and the first matrix's +I proportion for all of them each move the tree's lnL"""
+    import helpers
+    eid = max(range(len(case.edges)), key=lambda e: min(case.edges[e][0], case.edges[e][1]))
+    a, b, _ = case.edges[eid]
+    pc, ps = case.side(a, b)
+    cc, cs = case.side(b, a)
+    d = as_case(case)
+    if max(case.pinvs) == 0:
+        d["pinvs"] = None
+    return helpers.assert_discriminates(orc, lib, p, d, case.attrs, edge=(pc, ps, cc, cs, eid))

@@ -62,7 +62,10 @@ class OracleRun:
     """Full evaluation through the oracle with the same inputs a partition gets.
 
     model: dict(states, rate_cats, rates, rate_weights, eigenvals, eigenvecs,
-    inv_eigenvecs, freqs, pinv) -- one rate matrix shared by all categories.
+    inv_eigenvecs, freqs, pinv) -- one rate matrix shared by all categories; or, with a key params_indices, a mixture:
+    eigenvals / eigenvecs / inv_eigenvecs / freqs / pinvs are lists with one entry per rate matrix, and category k
+    takes entry params_indices[k] for P-matrices, sumtable and derivatives, entry freqs_indices[k] (default: the
+    same) of freqs and pinvs for the edge and root lnL -- as the reference's calls take their index arguments.
     tipcodes: uint8 [tips][sites] encoded tips (pattern-tip mode) or None;
     tipclvs: float64 [tips][sites][R][S] (CLV mode) or None.
     """
@@ -78,7 +81,7 @@ class OracleRun:
         self.per_rate = 1 if (attrs & ATTRIB_RATE_SCALERS) else 0
         self.sites = (tipcodes if self.pattern_tip else tipclvs).shape[1]
         self.tips = plan.tips
-        nodes = 2 * plan.tips - 2
+        nodes = getattr(plan, "nodes", 2 * plan.tips - 2)   # (a plan with more CLV slots than a tree's says so)
         self.clv = np.zeros((nodes, self.sites, R, S))
         if not self.pattern_tip:
             self.clv[:plan.tips] = tipclvs
@@ -90,11 +93,25 @@ class OracleRun:
                    else np.ascontiguousarray(pattern_weights, dtype=np.uint32))
         self.invariant = None if invariant is None else np.ascontiguousarray(invariant, dtype=np.int32)
         self.pmat = np.zeros((plan.prob_matrices, R, S, S))
-        self._ev = [np.ascontiguousarray(model["eigenvals"], dtype=np.float64)] * R
-        self._vc = [np.ascontiguousarray(model["eigenvecs"], dtype=np.float64)] * R
-        self._iv = [np.ascontiguousarray(model["inv_eigenvecs"], dtype=np.float64)] * R
-        self._fr = [np.ascontiguousarray(model["freqs"], dtype=np.float64)] * R
-        self._pinv = np.full(R, float(model.get("pinv", 0.0)))
+        if model.get("params_indices") is None:
+            self._ev = [np.ascontiguousarray(model["eigenvals"], dtype=np.float64)] * R
+            self._vc = [np.ascontiguousarray(model["eigenvecs"], dtype=np.float64)] * R
+            self._iv = [np.ascontiguousarray(model["inv_eigenvecs"], dtype=np.float64)] * R
+            self._fr = [np.ascontiguousarray(model["freqs"], dtype=np.float64)] * R
+            self._pinv = np.full(R, float(model.get("pinv", 0.0)))
+            self._fr_lnl, self._pinv_lnl = self._fr, self._pinv
+        else:
+            pi = [int(i) for i in model["params_indices"]]
+            fi = [int(i) for i in (model.get("freqs_indices") or pi)]
+            assert len(pi) == R and len(fi) == R
+
+            def per_matrix(key):
+                return [np.ascontiguousarray(a, dtype=np.float64) for a in model[key]]
+            ev, vc, iv, fr = (per_matrix(k) for k in ("eigenvals", "eigenvecs", "inv_eigenvecs", "freqs"))
+            pinvs = np.asarray(model.get("pinvs") or [0.0] * len(ev), dtype=np.float64)
+            self._ev, self._vc, self._iv = ([a[i] for i in pi] for a in (ev, vc, iv))
+            self._fr, self._pinv = [fr[i] for i in pi], np.ascontiguousarray(pinvs[pi])
+            self._fr_lnl, self._pinv_lnl = [fr[i] for i in fi], np.ascontiguousarray(pinvs[fi])
         for mi, t in zip(plan.matrix_indices, plan.branch_lengths):
             self.pmat[int(mi)] = orc.pmatrix(S, R, model["rates"], float(t), self._ev, self._vc,
                                              self._iv, self._pinv)
@@ -117,7 +134,7 @@ class OracleRun:
         w = np.ascontiguousarray(self.m["rate_weights"], dtype=np.float64)
         tp = self.pattern_tip and pclv < self.tips
         tc = self.pattern_tip and cclv < self.tips
-        common = (_d(self.pmat[matrix]), _rows(self._fr), _d(w), _u(self.pw), _d(self._pinv),
+        common = (_d(self.pmat[matrix]), _rows(self._fr_lnl), _d(w), _u(self.pw), _d(self._pinv_lnl),
                   _i(self.invariant), _d(ps), C.c_int(self.per_rate))
         if tp or tc:
             inner, isc, tip = (cclv, cscaler, pclv) if tp else (pclv, pscaler, cclv)
@@ -136,8 +153,8 @@ class OracleRun:
         ps = np.zeros(self.sites) if persite else None
         w = np.ascontiguousarray(self.m["rate_weights"], dtype=np.float64)
         v = self.o.lib.orc_root_loglikelihood(C.c_uint(self.S), C.c_uint(self.sites), C.c_uint(self.R),
-                                              _d(self.clv[clv]), _u(self._sc(scaler)), _rows(self._fr),
-                                              _d(w), _u(self.pw), _d(self._pinv), _i(self.invariant), _d(ps))
+                                              _d(self.clv[clv]), _u(self._sc(scaler)), _rows(self._fr_lnl),
+                                              _d(w), _u(self.pw), _d(self._pinv_lnl), _i(self.invariant), _d(ps))
         return (v, ps) if persite else v
 
     def sumtable(self, pclv, cclv, pscaler, cscaler):

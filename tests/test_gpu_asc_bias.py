@@ -176,3 +176,82 @@ def test_asc_bias_is_additive_over_site_shards(gpu, kind):
         parts += p.compute_edge_loglikelihood(*plan.root_edge, [0] * R)
         p.destroy()
     assert abs(parts - total) <= 1e-11 * abs(total), (kind, parts, total)
+
+
+@pytest.mark.parametrize("kind", sorted(TYPES))
+@pytest.mark.parametrize("states,pattern_tip,rate_scalers,R",
+                         [(4, True, False, 4), (4, False, True, 3), (20, False, False, 4), (5, False, False, 3)])
+def test_asc_bias_mixture_matches_reference(gpu, ref, orc, monkeypatch, kind, states, pattern_tip, rate_scalers, R):
+    """The correction kernels (asc_bias.hip) read the category weights and, through freqs_indices, the frequencies:
+    test_asc_bias_matches_reference under a mixture model (helpers.mixture without +I, which the correction does not
+    allow; freqs_indices that differ from params_indices) -- edge lnL per site and summed, a tip edge, the root form,
+    sumtable and derivatives against the genuine reference, to that test's bounds."""
+    from helpers import (odd_state_case, mixture, build_partition, assert_discriminates, params_of, freqs_of)
+    monkeypatch.delenv("PLLHIP_AA_EXACT", raising=False)
+    if states in (4, 20):
+        case = make_case(states, "random", 12, 157, seed=states + len(kind), rate_cats=R)
+    else:
+        case = odd_state_case(states, tips=9, sites=41, seed=5, rate_cats=R)
+        case["pw"] = np.ones(41, dtype=np.uint32)
+    mixture(case, gpu, seed=states + R, variant=1)
+    # the corrections take logarithms of 1 minus a sum of likelihoods of the extra sites (likelihood.c:24-119), which
+    # is a probability only with weights that sum to 1: unequal weights, but normalised (with mixture's factor 1.3
+    # the reference itself returns NaN at the tip edge and at the root form below)
+    case["cat_weights"] = case["cat_weights"] / case["cat_weights"].sum()
+    plan, pi, fi = case["plan"], params_of(case), freqs_of(case)
+    assert fi != pi
+    tips_scal = (ATTRIB_PATTERN_TIP if pattern_tip else 0) | (ATTRIB_RATE_SCALERS if rate_scalers else 0)
+    arch = ATTRIB_ARCH_AVX2 if states in (4, 20) else 0
+    # the fixture itself, on the oracle alone (which knows no correction: a partition without one)
+    plain = build_partition(ref, case, tips_scal | arch)
+    assert_discriminates(orc, ref, plain, case, tips_scal)
+    plain.destroy()
+    attrs = TYPES[kind] | tips_scal
+    sw = np.random.default_rng(3).integers(1, 40, size=states).astype(np.uint32) if kind != "lewis" else None
+    g, r = build_partition(gpu, case, attrs), build_partition(ref, case, attrs | arch)
+    if sw is not None:
+        g.set_asc_state_weights(sw)
+        r.set_asc_state_weights(sw)
+    assert g.s.asc_bias_alloc == 1 and g.sites_total == case["sites"] + states
+    g.update_partials(plan.ops)
+    r.update_partials(plan.ops)
+    for op in plan.ops:
+        node, sc = int(op["parent_clv_index"]), int(op["parent_scaler_index"])
+        assert bits_equal(g.get_clv(node), r.get_clv(node)), "CLV %d (with its extra sites)" % node
+        assert (g.get_scaler(sc) == r.get_scaler(sc)).all()
+    e = plan.root_edge
+    lg, psg = g.compute_edge_loglikelihood(*e, fi, persite=True)
+    lr, psr = r.compute_edge_loglikelihood(*e, fi, persite=True)
+    assert np.isfinite(lr) and np.isfinite(psr).all(), "fixture: the reference's value is not a number"
+    assert abs(lg - lr) <= 1e-11 * abs(lr), (lg, lr)
+    assert rel_err(psg, psr) < 1e-12
+    # the correction is part of the value, and the indices are its business too: with index 0 for every category the
+    # REFERENCE's correction (corrected minus plain lnL) moves
+    r.set_asc_bias_type(0)
+    corr = lr - r.compute_edge_loglikelihood(*e, fi)
+    zero = r.compute_edge_loglikelihood(*e, [0] * R)
+    r.set_asc_bias_type(TYPES[kind])
+    assert abs(corr) > 1e-6 * abs(lr)
+    assert abs((r.compute_edge_loglikelihood(*e, [0] * R) - zero) - corr) > 1e-6 * abs(corr)
+    if pattern_tip:
+        op = next(o for o in plan.ops if int(o["child1_clv_index"]) < plan.tips)
+        te = (int(op["parent_clv_index"]), int(op["parent_scaler_index"]), int(op["child1_clv_index"]),
+              -1, int(op["child1_matrix_index"]))
+        a, b = g.compute_edge_loglikelihood(*te, fi), r.compute_edge_loglikelihood(*te, fi)
+        assert np.isfinite(b), "fixture: the reference's value is not a number"
+        assert abs(a - b) <= 1e-11 * abs(b), (a, b)
+    a = g.compute_root_loglikelihood(e[0], e[1], fi)
+    b = r.compute_root_loglikelihood(e[0], e[1], fi)
+    assert np.isfinite(b), "fixture: the reference's value is not a number"
+    assert abs(a - b) <= 1e-11 * abs(b), (a, b)
+    stg, strf = g.alloc_sumtable(), r.alloc_sumtable()
+    g.update_sumtable(e[0], e[2], e[1], e[3], pi, stg)
+    r.update_sumtable(e[0], e[2], e[1], e[3], pi, strf)
+    assert sumtable_err(g.get_sumtable(stg), r.get_sumtable(strf)) < 1e-11
+    for t in (0.03, 0.4, 2.0):
+        dg = g.compute_likelihood_derivatives(e[1], e[3], t, pi, stg)
+        dr = r.compute_likelihood_derivatives(e[1], e[3], t, pi, strf)
+        assert np.isfinite(dr).all(), "fixture: the reference's value is not a number"
+        assert rel_err(np.array(dg), np.array(dr)) < 1e-9, (t, dg, dr)
+    g.destroy()
+    r.destroy()

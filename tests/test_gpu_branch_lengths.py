@@ -100,15 +100,29 @@ CONFIGS = {
     "s61-1rate": dict(states=61, rate_cats=1, tips=6, sites=60, pattern_tip=False),
     "dna-matrix-per-category": dict(states=4, per_cat_models=True, pinv=0.1),
 }
+# mixtures (insertion_data: shared, non-identity indices; unequal weights that sum to 1.3; distinct +I proportions)
+MIXTURES = {
+    "dna-mixture": dict(states=4, params="shared", cat_weights=True, pinv=0.2, constant=6),
+    "dna-mixture-1rate-index-1": dict(states=4, rate_cats=1, params="shared", cat_weights=True, pinv=0.2, constant=6),
+    "dna-mixture-tip-clvs-rate-scalers": dict(states=4, params="shared", cat_weights=True, pattern_tip=False,
+                                              rate_scalers=True),
+    "aa-mixture": dict(states=20, params="shared", cat_weights=True, pinv=0.2, constant=6),
+    "s5-mixture-3rates": dict(states=5, rate_cats=3, params="shared", cat_weights=True, pinv=0.2, constant=6),
+    "s61-mixture": dict(states=61, rate_cats=4, tips=5, sites=40, pattern_tip=False, params="shared",
+                        cat_weights=True),
+}
+CONFIGS.update(MIXTURES)
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))
-def test_equals_call_sequence(gpu, name):
+def test_equals_call_sequence(gpu, orc, name):
     case = D.make_case(seed=3, inner_queries=0, tip_queries=0, **CONFIGS[name])
     if case.states == 20:
         case.models[0] = gpu.aa_model("lg")
     p = D.build(gpu, case)
     try:
+        if case.cat_weights is not None:
+            D.assert_discriminates(orc, gpu, p, case)
         branches, starts = branches_of(case)
         got = p.optimize_branch_lengths(branches, starts, case.params)
         assert (got[3] == BRANCH_CONVERGED).any()
@@ -135,12 +149,19 @@ def test_deep_caterpillar_scales(gpu, rate_scalers):
         p.destroy()
 
 
-@pytest.mark.parametrize("kw", [dict(states=4, rate_scalers=True, pinv=0.2), dict(states=20)], ids=["dna", "aa"])
-def test_against_reference(gpu, ref, kw):
+REF_MIXTURES = ["dna-mixture", "dna-mixture-1rate-index-1", "dna-mixture-tip-clvs-rate-scalers", "aa-mixture",
+                "s5-mixture-3rates"]
+
+
+@pytest.mark.parametrize("kw", [dict(states=4, rate_scalers=True, pinv=0.2), dict(states=20)] +
+                         [MIXTURES[k] for k in REF_MIXTURES], ids=["dna", "aa"] + REF_MIXTURES)
+def test_against_reference(gpu, ref, orc, kw):
     case = D.make_case(seed=9, tips=8, sites=150, tip_queries=0, inner_queries=0, **kw)
     p = D.build(gpu, case)
     r = D.build(ref, case)
     try:
+        if case.cat_weights is not None:
+            D.assert_discriminates(orc, ref, r, case)
         branches, starts = branches_of(case)
         got = p.optimize_branch_lengths(branches, starts, case.params)
         check_against_rule(got, r, case, branches, starts)

@@ -267,3 +267,103 @@ def test_core_api_keeps_a_context_per_recent_shape(gpu):
     later = min(round_() for _ in range(3))
     assert later < 0.5 * first, (first, later)
     L.pll_amd_core_release()
+
+
+@pytest.mark.parametrize("states,sites,pattern_tip,rate_scalers,R",
+                         [(4, 333, True, False, 4), (4, 257, False, True, 3), (20, 150, True, False, 4),
+                          (20, 97, False, True, 5), (5, 120, True, False, 3)])
+def test_result_calls_with_per_category_pointers(gpu, orc, monkeypatch, states, sites, pattern_tip, rate_scalers, R):
+    """The result-returning entry points with a mixture model (helpers.mixture), given as the reference's callers
+    give it: pll_core_update_pmatrix with one eigen system and +I proportion per rate matrix and params_indices;
+    the lnL calls with the frequency sets and proportions per rate matrix and freqs_indices (which differ from
+    params_indices here); sumtable and derivatives with one pointer and proportion PER CATEGORY, distinct ones.
+    CLVs and scale buffers are the oracle's (the partial calls read none of these arrays)."""
+    from helpers import mixture, assert_discriminates, constant_columns, params_of, freqs_of
+    monkeypatch.delenv("PLLHIP_AA_EXACT", raising=False)
+    L = bind(gpu)
+    kw = dict(gap_frac=0.0, ambiguity=False) if states in (4, 20) else {}
+    case = (make_case(states, "random", 10, sites, seed=sites, rate_cats=R, **kw) if states in (4, 20) else
+            odd_state_case(states, tips=10, sites=sites, seed=9, rate_cats=R))
+    constant_columns(case)
+    mixture(case, gpu, seed=sites + R, variant=1, pinv=True)
+    plan, S, tips = case["plan"], states, case["tips"]
+    attrs = (ATTRIB_PATTERN_TIP if pattern_tip else 0) | (ATTRIB_RATE_SCALERS if rate_scalers else 0)
+    attrib = attrs | (ATTRIB_ARCH_AVX2 if states % 4 == 0 else 0)
+    p = build_partition(gpu, case, attrs)
+    o = assert_discriminates(orc, gpu, p, case, attrs)
+    m_ = o.m
+    c = lambda x: np.ascontiguousarray(x, dtype=np.float64)  # noqa: E731
+    vals, vecs, inv, freqs = ([c(a) for a in m_[k]] for k in ("eigenvals", "eigenvecs", "inv_eigenvecs", "freqs"))
+    pinvs = c(m_["pinvs"])
+    pi = np.ascontiguousarray(params_of(case), dtype=np.uint32)
+    fi = np.ascontiguousarray(freqs_of(case), dtype=np.uint32)
+    rates, w = c(m_["rates"]), c(m_["rate_weights"])
+    span = S * R
+
+    nm = plan.prob_matrices
+    pm = np.zeros((nm, R, S, S))
+    mi = np.ascontiguousarray(plan.matrix_indices, dtype=np.uint32)
+    bl = c(plan.branch_lengths)
+    assert L.pll_core_update_pmatrix(rows([pm[i] for i in range(nm)]), S, R, d(rates), d(bl), u(mi), u(pi), d(pinvs),
+                                     rows(vals), rows(vecs), rows(inv), len(mi), attrib) == 1, gpu.errmsg()
+    for m in plan.matrix_indices:
+        assert bits_equal(pm[int(m)], o.pmat[int(m)]), "P-matrix %d" % m
+
+    clv, scal, codes, tipmap = o.clv, o.scalers, o.tipcodes, o.tipmap
+    maxstates = int(p.s.maxstates) if pattern_tip else 0
+    pw = np.ascontiguousarray(o.pw, dtype=np.uint32)
+    invariant = np.ascontiguousarray(o.invariant, dtype=np.int32)
+    ip = invariant.ctypes.data_as(_ip)
+
+    def sc(idx):
+        return None if idx < 0 else scal[idx]
+
+    def tip_edge():
+        op = [q for q in plan.ops if int(q["child2_clv_index"]) < tips][-1]
+        return (int(op["parent_clv_index"]), int(op["parent_scaler_index"]), int(op["child2_clv_index"]), -1,
+                int(op["child2_matrix_index"]))
+    mfma = states == 20
+    for pc, ps_, cc, cs, m in (tuple(plan.root_edge), tip_edge()):
+        persite = np.zeros(sites)
+        ti = pattern_tip and (pc < tips or cc < tips)
+        if ti:
+            tip, inner, isc = (pc, cc, cs) if pc < tips else (cc, pc, ps_)
+            lnl = L.pll_core_edge_loglikelihood_ti(S, sites, R, d(clv[inner]), u(sc(isc)), b(codes[tip]), u(tipmap),
+                                                   maxstates, d(pm[m]), rows(freqs), d(w), u(pw), d(pinvs), ip,
+                                                   u(fi), d(persite), attrib)
+        else:
+            lnl = L.pll_core_edge_loglikelihood_ii(S, sites, R, d(clv[pc]), u(sc(ps_)), d(clv[cc]), u(sc(cs)),
+                                                   d(pm[m]), rows(freqs), d(w), u(pw), d(pinvs), ip, u(fi),
+                                                   d(persite), attrib)
+        want, want_ps = o.edge_loglikelihood(pc, ps_, cc, cs, m, persite=True)
+        assert rel_err(persite, want_ps) < (1e-11 if mfma else 1e-13)
+        assert abs(lnl - want) <= (1e-11 if mfma else 1e-12) * abs(want)
+        st = np.zeros(sites * span)
+        cat = lambda a: rows([a[int(k)] for k in pi])  # noqa: E731  (per category, through params_indices)
+        if ti:
+            ok = L.pll_core_update_sumtable_ti(S, sites, R, d(clv[inner]), b(codes[tip]), u(sc(isc)), cat(vecs),
+                                               cat(inv), cat(freqs), u(tipmap), maxstates, d(st), attrib)
+        else:
+            ok = L.pll_core_update_sumtable_ii(S, sites, R, d(clv[pc]), d(clv[cc]), u(sc(ps_)), u(sc(cs)),
+                                               cat(vecs), cat(inv), cat(freqs), d(st), attrib)
+        assert ok == 1, gpu.errmsg()
+        want_st = o.sumtable(pc, cc, ps_, cs)
+        assert sumtable_err(st.reshape(want_st.shape), want_st) < (1e-10 if mfma else 1e-12)
+        df, ddf = C.c_double(), C.c_double()
+        pinv_cat = c(pinvs[pi])
+        for t in (0.03, 0.4):
+            assert L.pll_core_likelihood_derivatives(S, sites, R, d(w), u(sc(ps_)), u(sc(cs)), ip, u(pw),
+                                                     C.c_double(t), d(pinv_cat), cat(freqs), d(rates),
+                                                     cat(vals), d(st), C.byref(df), C.byref(ddf), attrib) == 1
+            assert rel_err(np.array([df.value, ddf.value]), np.array(o.derivatives(want_st, t))) < 1e-10
+    if not rate_scalers:
+        top = plan.ops[-1]
+        tclv, tsc = int(top["parent_clv_index"]), int(top["parent_scaler_index"])
+        persite = np.zeros(sites)
+        ra = L.pll_core_root_loglikelihood(S, sites, R, d(clv[tclv]), u(sc(tsc)), rows(freqs), d(w), u(pw),
+                                           d(pinvs), ip, u(fi), d(persite), attrib)
+        want, want_ps = o.root_loglikelihood(tclv, tsc, persite=True)
+        assert rel_err(persite, want_ps) < (1e-11 if mfma else 1e-13)
+        assert abs(ra - want) <= (1e-11 if mfma else 1e-12) * abs(want)
+    p.destroy()
+    L.pll_amd_core_release()

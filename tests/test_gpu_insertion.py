@@ -39,6 +39,19 @@ def assert_close(got, want, states):
         assert abs(g - w) <= tol_of(states) * abs(w), (j, i, g, w)
 
 
+# Mixtures (insertion_data: params="shared", cat_weights): rate matrices shared through an index list that is neither 0
+# nor the identity, unequal category weights that sum to 1.3, +I proportions that differ between the matrices and
+# columns for them to act on.  Every device route the list below tells apart: 4 states with pattern tips and with tip
+# CLVs, R = 1 (index [1]), 20 states, a small and a large odd state count.
+MIXTURES = [
+    dict(states=4, params="shared", cat_weights=True, pinv=0.2, constant=6),
+    dict(states=4, rate_cats=1, params="shared", cat_weights=True, pinv=0.2, constant=6),
+    dict(states=4, params="shared", cat_weights=True, pattern_tip=False, rate_scalers=True),
+    dict(states=20, params="shared", cat_weights=True, pinv=0.2, constant=6),
+    dict(states=5, rate_cats=3, params="shared", cat_weights=True, pinv=0.2, constant=6),
+    dict(states=61, rate_cats=4, tips=5, sites=40, pattern_tip=False, params="shared", cat_weights=True),
+]
+
 CONFIGS = [
     dict(states=4),
     dict(states=4, rate_cats=1),
@@ -55,14 +68,16 @@ CONFIGS = [
     dict(states=5, pattern_tip=False, rate_scalers=True, pinv=0.2),
     dict(states=61, rate_cats=1, tips=6, sites=60, pattern_tip=False),
     dict(states=61, rate_cats=4, tips=5, sites=40, pattern_tip=False, rate_scalers=True),
-]
+] + MIXTURES
 
 
 @pytest.mark.parametrize("kw", CONFIGS, ids=lambda kw: "-".join("%s%s" % (k[:4], v) for k, v in kw.items()))
-def test_equals_three_call_sequence(gpu, kw):
+def test_equals_three_call_sequence(gpu, orc, kw):
     case = D.make_case(seed=3, **kw)
     p, got, want = batch_and_sequence(gpu, case)
     try:
+        if case.cat_weights is not None:
+            D.assert_discriminates(orc, gpu, p, case)
         assert got.shape == (case.tip_queries + case.inner_queries, len(case.edges))
         assert_close(got, want, case.states)
     finally:
@@ -90,13 +105,16 @@ def test_deep_caterpillar_scales(gpu, states, tips, rate_scalers):
 
 
 @pytest.mark.parametrize("kw", [dict(states=4), dict(states=4, rate_scalers=True, pinv=0.2),
-                                dict(states=20, rate_cats=1), dict(states=5, pattern_tip=False)],
-                         ids=["dna", "dna-rate-pinv", "aa", "s5"])
-def test_against_reference(gpu, ref, kw):
+                                dict(states=20, rate_cats=1), dict(states=5, pattern_tip=False)] + MIXTURES[:5],
+                         ids=["dna", "dna-rate-pinv", "aa", "s5", "dna-mixture", "dna-mixture-1-rate",
+                              "dna-mixture-tip-clvs-rate", "aa-mixture", "s5-mixture"])
+def test_against_reference(gpu, ref, orc, kw):
     case = D.make_case(seed=9, tips=8, sites=120, **kw)
     p = D.build(gpu, case)
     r = D.build(ref, case)
     try:
+        if case.cat_weights is not None:
+            D.assert_discriminates(orc, ref, r, case)
         q, s, pl = D.queries_of(case)
         e = case.edge_list()
         got = p.insertion_loglikelihood(e, q, pl, case.params, s)

@@ -11,8 +11,8 @@ import pytest
 import nni_data as N
 from libpll_amd.pllapi import (ATTRIB_AB_FLAG, ATTRIB_AB_LEWIS, ATTRIB_SITE_REPEATS, BRANCH_CONVERGED,
                                BRANCH_MAX_ITERS, ERROR_PARAM_INVALID, nni_edges)
-from test_gpu_branch_lengths import CONFIGS as OPT_CONFIGS, rule
-from test_gpu_insertion import CONFIGS
+from test_gpu_branch_lengths import CONFIGS as OPT_CONFIGS, MIXTURES as OPT_MIXTURES, REF_MIXTURES, rule
+from test_gpu_insertion import CONFIGS, MIXTURES
 
 pytestmark = pytest.mark.gpu
 
@@ -61,11 +61,13 @@ def check_lnl(got, p, case, edges):
 
 
 @pytest.mark.parametrize("kw", CONFIGS, ids=ids_of)
-def test_equals_call_sequence(gpu, monkeypatch, kw):
+def test_equals_call_sequence(gpu, orc, monkeypatch, kw):
     set_route(monkeypatch, "default")
     case = N.make_case(seed=3, **kw)
     p = N.build(gpu, case)
     try:
+        if case.cat_weights is not None:
+            N.D.assert_discriminates(orc, gpu, p, case)
         edges = N.nni_edges(case)
         assert len(edges) == case.n - 3
         got = p.nni_loglikelihood(edges, case.params)
@@ -84,17 +86,25 @@ def test_equals_call_sequence(gpu, monkeypatch, kw):
 
 
 @pytest.mark.parametrize("kw", [dict(states=4), dict(states=4, rate_scalers=True, pinv=0.2),
-                                dict(states=20, rate_cats=1), dict(states=5, pattern_tip=False)],
-                         ids=["dna", "dna-rate-pinv", "aa", "s5"])
-def test_against_reference(gpu, ref, monkeypatch, kw):
+                                dict(states=20, rate_cats=1), dict(states=5, pattern_tip=False)] + MIXTURES[:5],
+                         ids=["dna", "dna-rate-pinv", "aa", "s5", "dna-mixture", "dna-mixture-1-rate",
+                              "dna-mixture-tip-clvs-rate", "aa-mixture", "s5-mixture"])
+def test_against_reference(gpu, ref, orc, monkeypatch, kw):
     set_route(monkeypatch, "default")
     case = N.make_case(seed=9, tips=8, sites=120, **kw)
     p = N.build(gpu, case)
     r = N.build(ref, case)
     try:
+        if case.cat_weights is not None:
+            N.D.assert_discriminates(orc, ref, r, case)
         edges = N.nni_edges(case)
         got = p.nni_loglikelihood(edges, case.params)
         check_lnl(got, r, case, edges)
+        if case.states == 4 and case.cat_weights is not None:
+            # both routes against the reference (where the quartet kernel covers the shape, the default took it)
+            for route in ("general", "quartet"):
+                set_route(monkeypatch, route)
+                check_lnl(p.nni_loglikelihood(edges, case.params), r, case, edges)
     finally:
         p.destroy()
         r.destroy()
@@ -175,13 +185,15 @@ def check_optimum(got, p, case, edges, want_p=None, **kw):
 
 
 @pytest.mark.parametrize("name", list(OPT_CONFIGS))
-def test_optimize_equals_rule(gpu, monkeypatch, name):
+def test_optimize_equals_rule(gpu, orc, monkeypatch, name):
     set_route(monkeypatch, "default")
     case = N.make_case(seed=3, **OPT_CONFIGS[name])
     if case.states == 20:
         case.models[0] = gpu.aa_model("lg")
     p = N.build(gpu, case)
     try:
+        if case.cat_weights is not None:
+            N.D.assert_discriminates(orc, gpu, p, case)
         edges = N.nni_edges(case)
         got = p.nni_optimize(edges, case.params)
         assert got[0].shape == (len(edges), 3)
@@ -197,16 +209,21 @@ def test_optimize_equals_rule(gpu, monkeypatch, name):
         p.destroy()
 
 
-@pytest.mark.parametrize("kw", [dict(states=4, rate_scalers=True, pinv=0.2), dict(states=4), dict(states=20)],
-                         ids=["dna-rate-pinv", "dna", "aa"])
-def test_optimize_against_reference(gpu, ref, monkeypatch, kw):
+@pytest.mark.parametrize("kw", [dict(states=4, rate_scalers=True, pinv=0.2), dict(states=4), dict(states=20)] +
+                         [OPT_MIXTURES[k] for k in REF_MIXTURES], ids=["dna-rate-pinv", "dna", "aa"] + REF_MIXTURES)
+def test_optimize_against_reference(gpu, ref, orc, monkeypatch, kw):
     set_route(monkeypatch, "default")
     case = N.make_case(seed=9, tips=8, sites=150, **kw)
     p = N.build(gpu, case)
     r = N.build(ref, case)
     try:
+        if case.cat_weights is not None:
+            N.D.assert_discriminates(orc, ref, r, case)
         edges = N.nni_edges(case)
         check_optimum(p.nni_optimize(edges, case.params), p, case, edges, want_p=r)
+        if case.states == 4 and case.cat_weights is not None:
+            set_route(monkeypatch, "general")
+            check_optimum(p.nni_optimize(edges, case.params), p, case, edges, want_p=r)
     finally:
         p.destroy()
         r.destroy()

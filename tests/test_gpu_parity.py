@@ -556,3 +556,98 @@ def test_full_size_against_reference_sample(gpu, ref):
     assert abs(la - lr) <= 1e-10 * abs(lr)
     a.destroy()
     r.destroy()
+
+
+def test_rccl_allreduce_path_single_rank_mixture(gpu, orc):
+    """test_rccl_allreduce_path_single_rank under a mixture model (helpers.mixture): the kernels that feed the
+    all-reduce read the weights, frequencies and +I proportions by category; edge lnL, root lnL and derivatives of the
+    joined partition against the oracle"""
+    import ctypes
+    from helpers import mixture, assert_discriminates, constant_columns, params_of, freqs_of
+    case = make_case(4, "random", 9, 3000, seed=12, gap_frac=0.0, ambiguity=False)
+    constant_columns(case)
+    mixture(case, gpu, seed=12, variant=1, pinv=True)
+    plan, pi, fi = case["plan"], params_of(case), freqs_of(case)
+    p = build_partition(gpu, case, ATTRIB_PATTERN_TIP)
+    o = assert_discriminates(orc, gpu, p, case, ATTRIB_PATTERN_TIP)
+    p.update_partials(plan.ops)
+    uid = ctypes.create_string_buffer(128)
+    assert gpu.lib.pll_amd_comm_unique_id(uid), gpu.errmsg()
+    p.comm_init(0, 1, uid.raw)
+    e = plan.root_edge
+    lnl = p.compute_edge_loglikelihood(*e, fi)
+    want = o.edge_loglikelihood(*e)
+    assert abs(lnl - want) <= LNL_RTOL * abs(want)
+    root = p.compute_root_loglikelihood(e[0], e[1], fi)
+    want = o.root_loglikelihood(e[0], e[1])
+    assert abs(root - want) <= LNL_RTOL * abs(want)
+    st = p.alloc_sumtable()
+    p.update_sumtable(e[0], e[2], e[1], e[3], pi, st)
+    so = o.sumtable(e[0], e[2], e[1], e[3])
+    for t in (0.003, 0.13, 2.0):
+        assert rel_err(p.compute_likelihood_derivatives(e[1], e[3], t, pi, st), o.derivatives(so, t)) < DERIV_RTOL
+    p.destroy()
+
+
+@pytest.mark.parametrize("states,R,rate_scalers,aa_exact", [
+    pytest.param(4, 4, 0, None, id="4-states-R4"), pytest.param(4, 3, ATTRIB_RATE_SCALERS, None, id="4-states-R3-per-rate"),
+    pytest.param(20, 4, 0, "0", id="20-states-R4-matrix-cores"), pytest.param(20, 5, 0, "0", id="20-states-R5-matrix-cores"),
+    pytest.param(20, 4, 0, "1", id="20-states-R4-exact"), pytest.param(7, 4, 0, None, id="7-states-R4")])
+def test_model_change_on_a_live_partition(gpu, orc, monkeypatch, states, R, rate_scalers, aa_exact):
+    """After an evaluation: pll_set_category_weights, pll_set_frequencies(k) and
+    pll_update_invariant_sites_proportion(k) -- and, from 0 to a value, the proportion of a partition that had none
+    -- then everything again.  Whatever the device keeps of the model (weights, frequencies, +I proportions, whether
+    any is set, lookup tables, diagonal matrices) must follow: P-matrices, CLVs, scaler counts, per-site edge and root
+    lnL and the sumtable bit for bit those of a fresh partition with the new model, the sums too (same kernels, same
+    order), and the oracle's to the usual bounds."""
+    from helpers import mixture, assert_discriminates, constant_columns, params_of, freqs_of
+    from test_gpu_mixture_models import check_edge, check_roots
+    from test_gpu_result_calls import edges, tree_nodes, new_case
+    if aa_exact is not None:
+        monkeypatch.setenv("PLLHIP_AA_EXACT", aa_exact)
+    attrs = ATTRIB_PATTERN_TIP | rate_scalers
+    case = new_case(gpu, states, R, 333, tips=11, seed=states + R, pinv=True)
+    mixture(case, gpu, seed=5 * states + R, variant=1, pinv=False)       # no +I at first
+    plan, pi, fi = case["plan"], params_of(case), freqs_of(case)
+    M = len(case["models"])
+
+    def state(p):
+        p.update_partials(plan.ops)
+        out = [p.get_pmatrix(int(m)) for m in plan.matrix_indices]
+        out += [p.get_clv(n) for n, _ in tree_nodes(plan)] + [p.get_scaler(s) for _, s in tree_nodes(plan)]
+        for name, pc, ps, cc, cs, m in edges(plan, ATTRIB_PATTERN_TIP):
+            st = p.alloc_sumtable()
+            p.update_sumtable(pc, cc, ps, cs, pi, st)
+            lnl, per = p.compute_edge_loglikelihood(pc, ps, cc, cs, m, fi, persite=True)
+            out += [per, np.array([lnl]), p.get_sumtable(st),
+                    np.array([p.compute_likelihood_derivatives(ps, cs, t, pi, st) for t in (0.05, 0.7)])]
+        for node, sc in tree_nodes(plan)[-2:]:
+            lnl, per = p.compute_root_loglikelihood(node, sc, fi, persite=True)
+            out += [per, np.array([lnl])]
+        return out
+
+    live = build_partition(gpu, case, attrs)
+    before = state(live)
+    changed = dict(case, cat_weights=case["cat_weights"][::-1] * 0.8,
+                   models=[(r, f[::-1].copy()) if i == M - 1 else (r, f) for i, (r, f) in enumerate(case["models"])],
+                   pinvs=[0.0, 0.25] if M == 2 else [0.1, 0.0, 0.3])
+    live.set_category_weights(changed["cat_weights"])
+    live.set_frequencies(M - 1, changed["models"][M - 1][1])
+    for i, v in enumerate(changed["pinvs"]):
+        if v > 0:
+            live.update_invariant_sites_proportion(i, v)
+    live.update_prob_matrices(pi, plan.matrix_indices, plan.branch_lengths)
+    after = state(live)
+    fresh = build_partition(gpu, changed, attrs)
+    want = state(fresh)
+    assert not all(bits_equal(a, b) for a, b in zip(before, after))
+    for i, (a, b) in enumerate(zip(after, want)):
+        assert bits_equal(a, b), "item %d of the state differs from a fresh partition's" % i
+    o = assert_discriminates(orc, gpu, fresh, changed, attrs)
+    exact = states != 20 or aa_exact == "1"
+    tol, stol = (PERSITE_RTOL, 1e-12) if exact else (MFMA_LNL_RTOL, 1e-10)
+    for name, pc, ps, cc, cs, m in edges(plan, ATTRIB_PATTERN_TIP):
+        check_edge(live, o, changed, (pc, ps, cc, cs, m), name, tol, max(tol, LNL_RTOL), stol)
+    check_roots(live, o, changed, tree_nodes(plan), tol, max(tol, LNL_RTOL))
+    live.destroy()
+    fresh.destroy()

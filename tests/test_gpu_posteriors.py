@@ -15,7 +15,7 @@ import insertion_data as D
 import posterior_data as PD
 from libpll_amd.pllapi import (ATTRIB_AB_FLAG, ATTRIB_AB_LEWIS, ATTRIB_SITE_REPEATS, ERROR_HIP_UNSUPPORTED,
                                ERROR_PARAM_INVALID, POSTERIOR_EDGE_DTYPE as PD_EDGE)
-from test_gpu_branch_lengths import CONFIGS, lnl_tol
+from test_gpu_branch_lengths import CONFIGS, MIXTURES, REF_MIXTURES, lnl_tol
 
 pytestmark = pytest.mark.gpu
 
@@ -57,33 +57,62 @@ def check_against_definition(p, want_p, case, asks, what):
     for i, ask in enumerate(asks):
         worst = max(worst, check_edge(got, i, PD.definition(want_p, ask, case.params), lnl_tol(case.states),
                                       (what, ask)))
-    check_self_consistency(got, case.rate_cats, case.pinv)
+    check_self_consistency(got, case.rate_cats, max(case.pinvs))
     print("%s: %d edges x %d sites, largest relative error %.2e" % (what, len(asks), case.sites, worst))
     return got
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))
-def test_equals_definition(gpu, name):
+def test_equals_definition(gpu, orc, name):
+    """(the mixtures of CONFIGS carry category weights that sum to 1.3: the posteriors are shares of the site
+    likelihood, so a common factor of the weights cancels -- in the definition, posterior_data.definition, and in the
+    call alike; test_weights_need_not_sum_to_one says so of the call alone)"""
     case = D.make_case(seed=3, inner_queries=0, tip_queries=0, **CONFIGS[name])
     if case.states == 20:
         case.models[0] = gpu.aa_model("lg")
     p = D.build(gpu, case)
     try:
+        if case.cat_weights is not None:
+            D.assert_discriminates(orc, gpu, p, case)
         check_against_definition(p, p, case, PD.asks(case), name)
     finally:
         p.destroy()
 
 
-@pytest.mark.parametrize("kw", [dict(states=4, rate_scalers=True, pinv=0.2), dict(states=20)], ids=["dna", "aa"])
-def test_against_reference(gpu, ref, kw):
+@pytest.mark.parametrize("kw", [dict(states=4, rate_scalers=True, pinv=0.2), dict(states=20)] +
+                         [MIXTURES[k] for k in REF_MIXTURES], ids=["dna", "aa"] + REF_MIXTURES)
+def test_against_reference(gpu, ref, orc, kw):
     case = D.make_case(seed=9, tips=8, sites=150, tip_queries=0, inner_queries=0, **kw)
     p = D.build(gpu, case)
     r = D.build(ref, case)
     try:
+        if case.cat_weights is not None:
+            D.assert_discriminates(orc, ref, r, case)
         check_against_definition(p, r, case, PD.asks(case), "reference-%d" % case.states)
     finally:
         p.destroy()
         r.destroy()
+
+
+@pytest.mark.parametrize("name", ["dna-mixture", "aa-mixture"])
+def test_weights_need_not_sum_to_one(gpu, name):
+    """The call is defined for any positive category weights (include/pll_amd.h: every output is a share of terma, in
+    which a common factor of the weights cancels): weights that sum to 1.3 against the definition, and against the
+    same weights scaled to sum to 1 -- the same shares to the bound used against the definition."""
+    case = D.make_case(seed=3, inner_queries=0, tip_queries=0, **MIXTURES[name])
+    assert abs(case.cat_weights.sum() - 1.3) < 1e-12
+    p = D.build(gpu, case)
+    case.cat_weights = case.cat_weights / 1.3
+    q = D.build(gpu, case)
+    try:
+        asks = PD.asks(case)
+        got = check_against_definition(p, p, case, asks, name + "-sum-1.3")
+        one = check_against_definition(q, q, case, asks, name + "-sum-1")
+        for i in range(len(asks)):
+            check_edge(got, i, {k: one[k][i] for k in VALUES}, lnl_tol(case.states), (name, asks[i]))
+    finally:
+        p.destroy()
+        q.destroy()
 
 
 @pytest.mark.parametrize("rate_scalers", [False, True], ids=["site-scalers", "rate-scalers"])

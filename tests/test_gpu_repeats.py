@@ -324,3 +324,38 @@ def test_identification_on_every_sort_path(gpu, tips, sites):
     assert la[0] == lb[0] and bits_equal(la[1], lb[1]) and la[0] != a[0]
     plain.destroy()
     rep.destroy()
+
+
+@pytest.mark.parametrize("states,shape,tips,sites,rate_cats,rate_scalers",
+                         [(4, "random", 30, 911, 4, True), (4, "balanced", 16, 1200, 2, False),
+                          (4, "random", 20, 700, 8, False), (20, "random", 14, 400, 4, False)])
+def test_repeats_mixture_against_the_oracle(gpu, orc, monkeypatch, states, shape, tips, sites, rate_cats, rate_scalers):
+    """The GATHER instances of the result kernels (rows looked up through the class maps) under a mixture model
+    (helpers.mixture: shared, non-identity indices; unequal weights; distinct +I proportions): CLVs and scale buffers
+    bit for bit, edge lnL at an inner and at a tip edge, root lnL on a CLV stored by class, sumtable and derivatives,
+    with the checks and bounds of tests/test_gpu_mixture_models.py."""
+    from helpers import mixture, assert_discriminates, constant_columns, repeat_columns
+    from test_gpu_mixture_models import check_clvs, check_edge, check_roots
+    from test_gpu_result_calls import edges, tree_nodes, MFMA_RTOL, PERSITE_RTOL, LNL_RTOL
+    monkeypatch.setenv("PLLHIP_AA_EXACT", "0")
+    case = make_case(states, shape, tips, sites, rate_cats=rate_cats, seed=3 * tips + sites, gap_frac=0.0,
+                     ambiguity=False)
+    if states == 20:
+        case["rates"], case["freqs"] = gpu.aa_model("lg")
+    repeat_columns(case, sites + 1, sites // 5 + 1)
+    constant_columns(case)
+    mixture(case, gpu, seed=sites, variant=int(rate_scalers), pinv=True)
+    plan = case["plan"]
+    attrs = ATTRIB_PATTERN_TIP | (ATTRIB_RATE_SCALERS if rate_scalers else 0)
+    rep = build_partition(gpu, case, attrs | ATTRIB_SITE_REPEATS)
+    o = assert_discriminates(orc, gpu, rep, case, attrs)
+    check_clvs(rep, o, case)
+    by_class = sum(1 for op in plan.ops if rep.repeats_classes(int(op["parent_clv_index"])))
+    assert by_class >= len(plan.ops) // 2, "fixture no longer stores its CLVs by class"
+    tol, stol = (MFMA_RTOL, 1e-10) if states == 20 else (PERSITE_RTOL, 1e-12)
+    for name, pc, ps, cc, cs, m in edges(plan, ATTRIB_PATTERN_TIP):
+        check_edge(rep, o, case, (pc, ps, cc, cs, m), name, tol, max(tol, LNL_RTOL), stol)
+    top = tree_nodes(plan)[-1]
+    assert 0 < rep.repeats_classes(top[0]) < sites
+    check_roots(rep, o, case, [top], tol, max(tol, LNL_RTOL))
+    rep.destroy()

@@ -311,3 +311,83 @@ def test_sharded_with_site_repeats(gpu, monkeypatch, states, shape, tips, sites,
         assert bits_equal(a[1], b[1]) and abs(a[0] - b[0]) <= 1e-12 * abs(b[0])
         p.destroy()
         q.destroy()
+
+
+def mixture_state(p, case, plan):
+    """what a client sees of a mixture case: edge lnL (per site too) at an inner and a tip edge, root lnL per site,
+    sumtable and derivatives"""
+    from helpers import params_of, freqs_of
+    from test_gpu_result_calls import edges, tree_nodes
+    pi, fi = params_of(case), freqs_of(case)
+    p.update_partials(plan.ops)
+    out = {}
+    for name, pc, ps, cc, cs, m in edges(plan, ATTRIB_PATTERN_TIP)[:2]:
+        st = p.alloc_sumtable()
+        p.update_sumtable(pc, cc, ps, cs, pi, st)
+        out[name] = (p.compute_edge_loglikelihood(pc, ps, cc, cs, m, fi, persite=True), p.get_sumtable(st),
+                     [p.compute_likelihood_derivatives(ps, cs, t, pi, st) for t in (0.04, 0.3, 2.0)])
+    node, sc = tree_nodes(plan)[-1]
+    out["root"] = p.compute_root_loglikelihood(node, sc, fi, persite=True)
+    return out
+
+
+def assert_same_mixture_state(a, b):
+    for key in b:
+        if key == "root":
+            assert bits_equal(a[key][1], b[key][1]) and abs(a[key][0] - b[key][0]) <= 1e-12 * abs(b[key][0])
+            continue
+        (la, pa), ta, da = a[key]
+        (lb, pb), tb, db = b[key]
+        assert bits_equal(pa, pb) and abs(la - lb) <= 1e-12 * abs(lb), key
+        assert bits_equal(ta, tb), key
+        assert rel_err(np.array(da), np.array(db)) < 1e-11, key
+
+
+@pytest.mark.parametrize("states,R,rate_scalers", [(4, 4, 0), (4, 3, ATTRIB_RATE_SCALERS), (20, 4, 0)])
+def test_sharded_mixture(gpu, orc, monkeypatch, states, R, rate_scalers):
+    """PLL_AMD_DEVICES=0,0 under a mixture model (helpers.mixture): every shard must get every rate matrix, its
+    frequencies and +I proportion, and the category weights (pllhip_put_model, pllhip_put_rates) -- the shards exist
+    from pll_partition_create on, so every setter runs after them.  Edge lnL, root lnL, sumtable and derivatives
+    against the unsharded partition (as assert_same) and the oracle.  Then the model of the LIVE sharded partition is
+    changed -- weights, one matrix's frequencies, one +I proportion -- and everything must equal a fresh unsharded
+    partition with that model."""
+    from helpers import mixture, assert_discriminates, constant_columns
+    from test_gpu_mixture_models import check_edge, check_roots
+    from test_gpu_result_calls import edges, tree_nodes, MFMA_RTOL, PERSITE_RTOL, LNL_RTOL
+    monkeypatch.setenv("PLLHIP_AA_EXACT", "0")
+    attrs = ATTRIB_PATTERN_TIP | rate_scalers
+    case = make_case(states, "random", 14, 1500, seed=40 + states + R, rate_cats=R, gap_frac=0.0, ambiguity=False)
+    if states == 20:
+        case["rates"], case["freqs"] = gpu.aa_model("lg")
+    constant_columns(case)
+    mixture(case, gpu, seed=states + R, variant=int(rate_scalers > 0), pinv=True)
+    plan = case["plan"]
+    one = build_partition(gpu, case, attrs)
+    monkeypatch.setenv("PLL_AMD_DEVICES", "0,0")
+    two = build_partition(gpu, case, attrs)
+    monkeypatch.delenv("PLL_AMD_DEVICES")
+    assert gpu.lib.pll_amd_shard_count(one.ptr) == 1 and gpu.lib.pll_amd_shard_count(two.ptr) == 2
+    o = assert_discriminates(orc, gpu, one, case, attrs)
+    whole = mixture_state(one, case, plan)
+    assert_same_mixture_state(mixture_state(two, case, plan), whole)
+    tol, stol = (MFMA_RTOL, 1e-10) if states == 20 else (PERSITE_RTOL, 1e-12)
+    for name, pc, ps, cc, cs, m in edges(plan, ATTRIB_PATTERN_TIP)[:2]:
+        check_edge(two, o, case, (pc, ps, cc, cs, m), name, tol, max(tol, LNL_RTOL), stol)
+    check_roots(two, o, case, tree_nodes(plan)[-1:], tol, max(tol, LNL_RTOL))
+    one.destroy()
+    # a new model on the live sharded partition, against a fresh unsharded one
+    M = len(case["models"])
+    changed = dict(case, cat_weights=case["cat_weights"][::-1] * 0.8,
+                   models=[(r, f[::-1].copy()) if i == M - 1 else (r, f) for i, (r, f) in enumerate(case["models"])],
+                   pinvs=[0.15 if i == 0 else v for i, v in enumerate(case["pinvs"])])
+    two.set_category_weights(changed["cat_weights"])
+    two.set_frequencies(M - 1, changed["models"][M - 1][1])
+    two.update_invariant_sites_proportion(0, 0.15)
+    from helpers import params_of
+    two.update_prob_matrices(params_of(case), plan.matrix_indices, plan.branch_lengths)
+    fresh = build_partition(gpu, changed, attrs)
+    want = mixture_state(fresh, changed, plan)
+    assert_same_mixture_state(mixture_state(two, changed, plan), want)
+    assert abs(want["ii"][0][0] - whole["ii"][0][0]) > 1e-6 * abs(whole["ii"][0][0]), "the change changed nothing"
+    two.destroy()
+    fresh.destroy()

@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 
 from helpers import (make_case, odd_state_case, build_partition, oracle_run, bits_equal, rel_err,
-                     sumtable_err, constant_columns)
+                     sumtable_err, constant_columns, mixture, params_of, freqs_of, assert_discriminates,
+                     stale_freqs_defect)
 from libpll_amd.pllapi import (ATTRIB_PATTERN_TIP, ATTRIB_RATE_SCALERS, ATTRIB_ARCH_AVX2,
                                ATTRIB_ARCH_CPU)
 
@@ -199,4 +200,86 @@ def test_root_loglikelihood_deep(ref, orc, states, tips, rate_scalers):
     lnl_o, ps_o = o.root_loglikelihood(node, sc, persite=True)
     assert bits_equal(ps_o, ps_r)
     assert lnl_o == lnl_r
+    p.destroy()
+
+
+def check_stale_freqs_defect(o, case, ps_o, ps_r):
+    """the reference's per-site values under stale_freqs_defect: the oracle's bit for bit at sites that are not
+    invariant; at invariant ones, apart by exactly the term the defect swaps (no scaling on these shallow trees:
+    site likelihood = exp(lnl / pattern weight))"""
+    fi, w = freqs_of(case), o.m["rate_weights"]
+    fr, pinvs = o.m["freqs"], o.m["pinvs"]
+    inv = o.invariant
+    assert bits_equal(ps_o[inv < 0], ps_r[inv < 0])
+    assert (inv >= 0).any() and not bits_equal(ps_o[inv >= 0], ps_r[inv >= 0])
+    for n in np.flatnonzero(inv >= 0):
+        delta = sum(w[k] * pinvs[fi[k]] * (fr[fi[-1]][inv[n]] - fr[fi[k]][inv[n]]) for k in range(len(fi)))
+        lk_o, lk_r = np.exp(ps_o[n] / o.pw[n]), np.exp(ps_r[n] / o.pw[n])
+        assert abs(lk_r - lk_o - delta) < 1e-13 * lk_o, n
+
+
+def mixture_edges(plan):
+    """the root edge and the last op's edge to a tip child: (parent clv, parent scaler, child clv, child scaler,
+    matrix)"""
+    out = [tuple(plan.root_edge)]
+    for op in plan.ops:
+        if int(op["child2_clv_index"]) < plan.tips:
+            tip = (int(op["parent_clv_index"]), int(op["parent_scaler_index"]), int(op["child2_clv_index"]), -1,
+                   int(op["child2_matrix_index"]))
+    return out + [tip]
+
+
+@pytest.mark.parametrize("variant", [pytest.param(0, id="freqs=params"), pytest.param(1, id="freqs!=params")])
+@pytest.mark.parametrize("R", [1, 3, 4])
+@pytest.mark.parametrize("states,pattern_tip,rate_scalers",
+                         [(s, pt, rs) for s in (4, 20) for pt in (0, ATTRIB_PATTERN_TIP)
+                          for rs in (0, ATTRIB_RATE_SCALERS)] + [(5, 0, 0), (5, ATTRIB_PATTERN_TIP, 0)])
+def test_mixture_models(ref, orc, states, pattern_tip, rate_scalers, R, variant):
+    """OracleRun with per-category models (helpers.mixture: shared, non-identity params_indices, freqs_indices that
+    differ from them in variant 1, unequal weights that sum to 1.3, distinct +I proportions) against the genuine
+    reference: P-matrices, CLVs, scaler counts and the per-site edge and root lnL bit for bit, sumtable and
+    derivatives to this file's bounds.  And the fixture discriminates (helpers.assert_discriminates).  One
+    exception, a defect of the reference that these cases brought out: stale_freqs_defect."""
+    if states == 5:
+        attrs = pattern_tip | ATTRIB_ARCH_CPU
+        case = odd_state_case(5, tips=9, sites=61, seed=17, rate_cats=R)
+    else:
+        attrs = pattern_tip | rate_scalers | ATTRIB_ARCH_AVX2
+        case = make_case(states, "random", 9, 61, rate_cats=R, seed=17 + states, gap_frac=0.0, ambiguity=False)
+        if states == 20:
+            case["rates"], case["freqs"] = ref.aa_model("wag")
+    constant_columns(case)
+    mixture(case, ref, seed=states + R, variant=variant, pinv=True)
+    pi, fi = params_of(case), freqs_of(case)
+    assert pi[0] != 0 and (variant == 0 or fi != pi)
+    p = build_partition(ref, case, attrs)
+    o = assert_discriminates(orc, ref, p, case, attrs)
+    assert (o.invariant >= 0).sum() >= 15
+    plan = case["plan"]
+    for mi in plan.matrix_indices:
+        assert bits_equal(o.pmat[int(mi)], p.get_pmatrix(int(mi))), "P-matrix %d" % mi
+    p.update_partials(plan.ops)
+    for op in plan.ops:
+        node, sc = int(op["parent_clv_index"]), int(op["parent_scaler_index"])
+        assert bits_equal(o.clv[node], p.get_clv(node)), "CLV %d" % node
+        assert (o.scalers[sc] == p.get_scaler(sc)).all(), "scaler %d" % sc
+        lnl_r, ps_r = p.compute_root_loglikelihood(node, sc, fi, persite=True)
+        lnl_o, ps_o = o.root_loglikelihood(node, sc, persite=True)
+        assert bits_equal(ps_o, ps_r), "root at CLV %d" % node
+        assert lnl_o == lnl_r
+    for e in mixture_edges(plan):
+        lnl_r, ps_r = p.compute_edge_loglikelihood(*e, fi, persite=True)
+        lnl_o, ps_o = o.edge_loglikelihood(*e, persite=True)
+        if stale_freqs_defect(case, attrs, e, plan):
+            check_stale_freqs_defect(o, case, ps_o, ps_r)
+        else:
+            assert bits_equal(ps_o, ps_r), e
+            assert lnl_o == lnl_r
+        st = p.alloc_sumtable()
+        p.update_sumtable(e[0], e[2], e[1], e[3], pi, st)
+        so = o.sumtable(e[0], e[2], e[1], e[3])
+        assert sumtable_err(so, p.get_sumtable(st)) < 1e-12
+        for t in (0.01, 0.2, 1.5):
+            d_r = p.compute_likelihood_derivatives(e[1], e[3], t, pi, st)
+            assert rel_err(o.derivatives(so, t), d_r) < 1e-10, (e, t)
     p.destroy()
