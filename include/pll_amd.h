@@ -1069,6 +1069,15 @@ PLL_EXPORT int pll_amd_profile_read(pll_partition_t * partition, unsigned int * 
  * partition is the reference's.  PLLHIP_AA_TI_MFMA=0 (environment, read when a partition is created): reference
  * order everywhere, every CLV bit for bit. */
 PLL_EXPORT int pll_amd_scaling_certificate(pll_partition_t * partition, unsigned long long * stats4);
+/* Deferred cherries of 4-state partitions (pllhip.h: pllhip_deferred_stats): {CLVs deferred now, ops deferred in total,
+ * materialising launches, CLVs materialised}.  Partitions that mirror their CLVs on the host, use site repeats or keep
+ * tips as CLVs do not defer. */
+PLL_EXPORT int pll_amd_deferred_stats(pll_partition_t * partition, unsigned long long * stats4);
+/* 0: every op of this partition is run and stored from now on (deferred CLVs are stored first); 1: defer again. */
+PLL_EXPORT int pll_amd_set_deferral(pll_partition_t * partition, int on);
+/* The device address of a CLV (pllhip.h: pllhip_dev_clv; NULL for a partition over several devices or a bad index).  A
+ * deferred CLV is stored first and the index is never deferred again: the caller holds the address. */
+PLL_EXPORT void * pll_amd_dev_clv(pll_partition_t * partition, unsigned int clv_index);
 
 /* Measurement only (bench.py's roofline.box_ceiling; pllhip.h: pllhip_write_ceiling): nothing but the stores of an op
  * list with the whole-list kernels' own address pattern, `reps` times, timed with HIP events.  OVERWRITES the CLVs and

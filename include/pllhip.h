@@ -175,6 +175,23 @@ PLLHIP_EXPORT int pllhip_fused_plan_dry(unsigned int tips, unsigned int clv_buff
                                         unsigned int nslots, unsigned int * order_out,
                                         unsigned int * reloads_out, int * slots_out);
 
+/* The same with deferred cherries (pllhip_set_deferral): which tip-tip ops the list defers and how the kept ops are
+ * walked.  old_deferred / old_scaler / pinned: per CLV index (tips + clv_buffers entries), what earlier calls left
+ * deferred, with which scale buffer (-1 none), and which CLVs are never deferred; each may be NULL.  Out (any may be
+ * NULL): *nkept kept ops in walk order as positions in the caller's list (order_out), six numbers per kept op as
+ * pllhip_fused_plan_dry gives them (slots_out), two operand kinds per kept op (operands_out: 0 a slot, 1 a tip, 2 a
+ * deferred cherry), per list op whether it is deferred (deferred_out[count]), the CLVs deferred earlier that are
+ * stored before the list (materialise_out) or whose deferral the list ends by overwriting them (dropped_out). */
+PLLHIP_EXPORT int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                                 int pattern_tip, const pllhip_op_t * ops, unsigned int count,
+                                                 unsigned int nslots, const unsigned char * old_deferred,
+                                                 const int * old_scaler, const unsigned char * pinned,
+                                                 unsigned int * nkept, unsigned int * order_out, int * slots_out,
+                                                 int * operands_out, unsigned char * deferred_out,
+                                                 unsigned int * reloads_out, unsigned int * materialise_out,
+                                                 unsigned int * nmaterialise, unsigned int * dropped_out,
+                                                 unsigned int * ndropped);
+
 /* Host logic, no device (round 5): the op list as independent sub-lists ("segments": ops that share no buffer any of
  * them writes -- the two sides of the root edge of a full traversal), which the whole-list kernels hand out as
  * (tile of sites, segment) work items when the tiles alone do not fill the chip (partials_fused.hpp).  seg_out[i] =
@@ -211,6 +228,16 @@ PLLHIP_EXPORT int pllhip_small_partition_estimate(unsigned int states, unsigned 
  * out4[3] == 0 every scaler count of the partition is the reference's (core_partials_avx2.c:752-800).
  * PLLHIP_AA_TI_MFMA=0: reference order everywhere, every CLV bit for bit, nothing to certify. */
 PLLHIP_EXPORT int pllhip_cert_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+
+/* Deferred cherries (4 states, whole-list kernel).  A tip-tip op of a whole-list launch is not run: its
+ * parent CLV is one of 256 rows of the op's pair table at every site, and stays DEFERRED -- defined by its two tip rows
+ * and a kept copy of that table -- until anything but a list kernel reads or overwrites it; that entry point then
+ * stores it first, bit for bit what the op would have stored (one pass of 132 B per site), and zeroes the scale buffer
+ * the op would have cleared.  Any CLV or scale buffer is readable at any time with unchanged bits.
+ * pllhip_set_deferral(ctx, 0): every op is run (deferred CLVs are stored first); 1: the default.
+ * pllhip_deferred_stats: {CLVs deferred now, ops deferred in total, materialising launches, CLVs materialised}. */
+PLLHIP_EXPORT int pllhip_set_deferral(pllhip_ctx_t * ctx, int on);
+PLLHIP_EXPORT int pllhip_deferred_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
 
 /* Host logic of the same planner, no device: where the 4-state whole-list kernel keeps each op's tip characters.
  * tips[i]: bit 0 / 1 = op i (in the PLANNED order) has a left / right tip row.  chars_out[i]: bits 0-7 / 8-15 the
@@ -461,6 +488,7 @@ PLLHIP_EXPORT int pllhip_aa_list_kinds(pllhip_ctx_t * ctx, unsigned int * out8);
 
 /* raw device pointer of a CLV (for tools that share HBM buffers, e.g. a
  * torch tensor wrapped around it); NULL if out of range */
+/* (a deferred CLV is stored first, and the index is never deferred again: the caller holds the address) */
 PLLHIP_EXPORT void * pllhip_dev_clv(pllhip_ctx_t * ctx, unsigned int clv_index);
 
 /* ---- Fitch parsimony (parsimony.hip; host side host/parsimony.c, host/stepwise.c) ----

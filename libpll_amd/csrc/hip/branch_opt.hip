@@ -440,6 +440,7 @@ extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_bra
     return -3;
   }
   PLLHIP_CERT_FIRST(c); // (the CLVs and scaler counts read here are the reference's, or the list runs again first)
+  PLLHIP_DEFERRED_FLUSH(c); // (deferred cherries get their bytes before anything but a list kernel touches them)
 
   // ---- chunk size: everything one chunk needs within `budget` bytes (one branch at least)
   const size_t sites = c->sh.sites;

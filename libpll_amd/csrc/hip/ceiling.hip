@@ -122,6 +122,7 @@ extern "C" int pllhip_write_ceiling(pllhip_ctx_t * c, const pllhip_op_t * ops, u
   if (!count || !reps) { pllhip_set_error("pllhip_write_ceiling: nothing to do"); return -1; }
   HIP_TRY(hipSetDevice(c->sh.device));
   PLLHIP_CERT_FIRST(c);
+  PLLHIP_DEFERRED_FLUSH(c); // (deferred cherries get their bytes before anything but a list kernel touches them)
   // the tile of a wave: 2 KB of a 4-state CLV (16 sites x 4 categories), 5 KB of a 20-state one (8 sites) -- what the
   // list kernels store per wave and op; other shapes: the largest whole number of sites in about 4 KB
   const size_t site_b = c->span * sizeof(double);

@@ -159,6 +159,7 @@ extern "C" int pllhip_arena_fill_bandwidth(pllhip_ctx_t * c, double * gbs)
   if (!c->shards.empty()) { pllhip_set_error("pllhip_arena_fill_bandwidth: not for a sharded context"); return -1; }
   HIP_TRY(hipSetDevice(c->sh.device));
   PLLHIP_CERT_FIRST(c);
+  PLLHIP_DEFERRED_FLUSH(c); // (every CLV is overwritten: no deferral outlives it)
   HIP_TRY(hipStreamSynchronize(c->stream));
   const size_t bytes = (c->clv_arena_alloc_bytes / 16) * 16;
   return fill_bandwidth(c->clv_arena, bytes, c->stream, c->ev0, c->ev1, c->num_cus, gbs);
@@ -580,6 +581,7 @@ extern "C" void pllhip_ctx_destroy(pllhip_ctx_t * c)
   if (c->fused_zero_row) (void)hipFree(c->fused_zero_row);
   if (c->d_tile_counter) (void)hipFree(c->d_tile_counter);
   if (c->d_pairtab) (void)hipFree(c->d_pairtab);
+  if (c->defer_pool) (void)hipFree(c->defer_pool);
   if (c->cherry_pool) (void)hipFree(c->cherry_pool);
   if (c->cherry_codes) (void)hipFree(c->cherry_codes);
   if (c->cherry_zero) (void)hipFree(c->cherry_zero);
@@ -642,6 +644,7 @@ extern "C" int pllhip_put_tipchars(pllhip_ctx_t * c, unsigned int tip, const uns
 {
   PLLHIP_ALL_SHARDS(c, pllhip_put_tipchars(s, tip, h + lo));
   PLLHIP_CERT_FIRST(c);
+  PLLHIP_DEFERRED_FLUSH(c); // (a deferred cherry is indexed by its tips' rows: it gets its bytes before a row changes)
   if (!c->sh.pattern_tip || tip >= c->sh.tips)
   {
     pllhip_set_error("pllhip_put_tipchars: tip %u invalid", tip);
@@ -655,6 +658,7 @@ extern "C" int pllhip_put_tipmap(pllhip_ctx_t * c, const unsigned int * h, unsig
   if (!c->shards.empty()) c->maxstates = maxstates;
   PLLHIP_ALL_SHARDS(c, pllhip_put_tipmap(s, h, maxstates));
   PLLHIP_CERT_FIRST(c);
+  PLLHIP_DEFERRED_FLUSH(c);
   if (maxstates > 256) { pllhip_set_error("tipmap too large"); return -1; }
   c->maxstates = maxstates;
   return h2d(c, c->tipmap, h, maxstates * sizeof(unsigned int));
@@ -669,6 +673,7 @@ extern "C" int pllhip_put_clv(pllhip_ctx_t * c, unsigned int idx, const double *
     pllhip_set_error("pllhip_put_clv: index %u has no CLV", idx);
     return -1;
   }
+  PLLHIP_DEFERRED_NEED(c, idx, idx, -1, -1); // (its deferral ends; the scale buffer it cleared holds zeros)
   pllhip_cert_mark_clv(c, idx, 0.0); // (the caller's values: nothing of ours in them)
   return h2d(c, c->clv[idx], h, c->clv_elems * sizeof(double));
 }
@@ -697,6 +702,7 @@ extern "C" int pllhip_put_tip_clv_persite(pllhip_ctx_t * c, unsigned int idx,
     pllhip_set_error("pllhip_put_tip_clv_persite: index %u has no CLV", idx);
     return -1;
   }
+  PLLHIP_DEFERRED_NEED(c, idx, idx, -1, -1);
   pllhip_cert_mark_clv(c, idx, 0.0);
   const size_t S = c->sh.states, N = c->sh.sites;
   // stage the compact [sites][states] vectors in the tail of the parent CLV's
@@ -792,6 +798,7 @@ extern "C" int pllhip_put_scaler(pllhip_ctx_t * c, unsigned int idx, const unsig
   PLLHIP_ALL_SHARDS(c, pllhip_put_scaler(s, idx, h + lo * (c->sh.rate_scalers ? c->sh.rate_cats : 1)));
   PLLHIP_CERT_FIRST(c);
   if (idx >= c->sh.scale_buffers) { pllhip_set_error("pllhip_put_scaler: index %u", idx); return -1; }
+  PLLHIP_DEFERRED_NEED(c, ~0u, ~0u, idx, -1);
   return h2d(c, pllhip_scaler_ptr(c, (int)idx), h, c->scaler_elems * sizeof(unsigned int));
 }
 
@@ -827,6 +834,7 @@ extern "C" int pllhip_partial_tt_from_lookup(pllhip_ctx_t * c, unsigned int pare
   }
   pllhip_cert_mark_clv(c, parent_clv, 0.0);
   HIP_TRY(hipSetDevice(c->sh.device));
+  PLLHIP_DEFERRED_NEED(c, parent_clv, parent_clv, parent_scaler, -1);
   double * d_lookup = nullptr;
   HIP_TRY(hipMalloc((void **)&d_lookup, rows * c->span * sizeof(double)));
   int rc = h2d(c, d_lookup, h_lookup, rows * c->span * sizeof(double));
@@ -891,6 +899,7 @@ extern "C" int pllhip_get_clv(pllhip_ctx_t * c, unsigned int idx, double * h)
     pllhip_set_error("pllhip_get_clv: index %u has no CLV", idx);
     return -1;
   }
+  PLLHIP_DEFERRED_NEED(c, idx, idx, -1, -1);
   return d2h(c, h, c->clv[idx], c->clv_elems * sizeof(double));
 }
 
@@ -899,6 +908,7 @@ extern "C" int pllhip_get_scaler(pllhip_ctx_t * c, unsigned int idx, unsigned in
   PLLHIP_ALL_SHARDS(c, shard_scaler_per_site(s, idx, h + lo * (c->sh.rate_scalers ? c->sh.rate_cats : 1)));
   PLLHIP_CERT_FIRST(c);
   if (idx >= c->sh.scale_buffers) { pllhip_set_error("pllhip_get_scaler: index %u", idx); return -1; }
+  PLLHIP_DEFERRED_NEED(c, ~0u, ~0u, idx, -1);
   return d2h(c, h, pllhip_scaler_ptr(c, (int)idx), c->scaler_elems * sizeof(unsigned int));
 }
 
@@ -939,6 +949,7 @@ extern "C" int pllhip_mirror_batch(pllhip_ctx_t * c, const pllhip_mirror_job_t *
   if (!c->shards.empty()) { pllhip_set_error("pllhip_mirror_batch: not for a sharded context"); return -1; }
   HIP_TRY(hipSetDevice(c->sh.device));
   PLLHIP_CERT_FIRST(c);
+  PLLHIP_DEFERRED_FLUSH(c);
   for (unsigned int first = 0; first < count; first += PLLHIP_MIRROR_BATCH)
   {
     const unsigned int n = std::min<unsigned int>(PLLHIP_MIRROR_BATCH, count - first);
@@ -1054,7 +1065,16 @@ extern "C" void * pllhip_dev_clv(pllhip_ctx_t * c, unsigned int idx)
 {
   if (!c->shards.empty()) return nullptr; // (one CLV lives on several devices)
   if (c->cert_pending && pllhip_cert_resolve(c)) return nullptr;
-  return idx < c->clv.size() ? (void *)c->clv[idx] : nullptr;
+  if (idx >= c->clv.size()) return nullptr;
+  // (the caller holds a raw pointer from here on: the CLV gets its bytes now and is never deferred again)
+  if (c->n_deferred && pllhip_deferred_materialise(c, &idx, 1)) return nullptr;
+  if (c->clv_pinned.size() != c->clv.size()) c->clv_pinned.assign(c->clv.size(), 0);
+  if (!c->clv_pinned[idx])
+  {
+    c->clv_pinned[idx] = 1;
+    ++c->defer_epoch;
+  }
+  return (void *)c->clv[idx];
 }
 
 // ---- per-launch profiling ----

@@ -89,6 +89,7 @@ struct pllhip_ctx
   size_t fused_last_jobs_offset = 0; // pair-table jobs within d_plan
   size_t fused_last_rowtab_offset = 0;     // ... and of the tip-character row table (partials_fused.hip)
   size_t fused_last_segs_offset = 0, fused_last_srcs_offset = 0; // ... the segment table, the reload sources
+  unsigned int fused_last_ndeferred = 0;                          // tip-tip ops the kept plan defers (not walked)
   unsigned int fused_last_nsegs = 1, fused_last_longest = 0;      // segments of the kept plan; ops of its longest
   float last_timer_ms = 0.f;               // pllhip_timer_stop_ms's last result on this context's stream
   unsigned char * fused_zero_row = nullptr; // [sites + slack] zeros: the "tip" of an op without one
@@ -98,6 +99,27 @@ struct pllhip_ctx
   // layout_epoch; a kept plan is only reused while its epoch is the current one.
   unsigned int layout_epoch = 0, fused_last_epoch = 0;
   double * d_pairtab = nullptr; // pair tables of the tip-tip ops of the current op list
+  // ---- deferred cherries (deferred.hip): a tip-tip op of a 4-state whole-list launch is not run; its
+  // parent CLV is DEFINED by its two tip rows and a kept copy of its pair table T[c1][c2][rate][state] until somebody
+  // other than a list kernel needs the bytes -- every such entry point materialises what it touches first
+  // (PLLHIP_DEFERRED_* below).  deferred[i].on: CLV i is in that state; scaler: the scale buffer cleared with it.
+  struct deferred_clv
+  {
+    bool on = false;
+    unsigned int tip1 = 0, tip2 = 0;
+    int scaler = -1;
+  };
+  std::vector<deferred_clv> deferred;          // per CLV index (sized on first use)
+  std::vector<int> deferred_sc_owner;          // per scale buffer: the deferred CLV that owns its (zero) counts, or -1
+  std::vector<unsigned char> clv_pinned;       // per CLV index: pllhip_dev_clv handed its address out -- never deferred
+  unsigned int n_deferred = 0;
+  double * defer_pool = nullptr;               // [CLV index][256][span]: the kept tables, one place per CLV
+  bool defer_pool_failed = false;
+  bool cherry_deferral = true;                        // pllhip_set_deferral (0: the eager path, for A/B and tests)
+  unsigned int defer_epoch = 0;                // bumped whenever a deferral ends other than by the list that replaces it
+  unsigned int fused_last_defer_epoch = 0;     // ... as it was when the kept plan was launched
+  std::vector<unsigned int> fused_last_deferred; // the kept plan's deferred set: {clv, tip1, tip2, scaler + 1} each
+  unsigned long long defer_stats[4] = {0, 0, 0, 0}; // deferred now (filled on read), ops deferred, materialise launches, CLVs materialised
   // 20 states: scratch of the lookup ops (partials_aa_mfma.hip, k_aa_cherry_rounds)
   double * cherry_pool = nullptr;
   unsigned char * cherry_codes = nullptr;
@@ -494,6 +516,31 @@ int pllhip_cert_resolve(pllhip_ctx * c, bool * rerun = nullptr, bool drained = f
       const int rc_cert_ = pllhip_cert_resolve(c); \
       if (rc_cert_) return rc_cert_;               \
     }                                              \
+  } while (0)
+// Deferred cherries (pllhip_ctx::deferred, deferred.hip).  An entry point that is about to read or overwrite CLVs or
+// scale buffers outside a 4-state list kernel materialises them first -- bit for bit what the tip-tip op would have
+// stored, and zeros in the scale buffer it cleared.  n < 0 / PLLHIP_DEFERRED_FLUSH: every deferred CLV.
+int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * clv_indices, int n);
+int pllhip_deferred_materialise_scalers(pllhip_ctx * c, const int * scaler_indices, int n);
+void pllhip_deferred_drop(pllhip_ctx * c, unsigned int clv_index); // the deferral ends without the bytes (overwritten)
+double * pllhip_deferred_table(pllhip_ctx * c, unsigned int clv_index); // its place in the pool (nullptr: no pool)
+#define PLLHIP_DEFERRED_FLUSH(c)                                         \
+  do {                                                                   \
+    if ((c)->n_deferred) {                                               \
+      const int rc_def_ = pllhip_deferred_materialise(c, nullptr, -1);   \
+      if (rc_def_) return rc_def_;                                       \
+    }                                                                    \
+  } while (0)
+// (a, b: CLV indices; sa, sb: scale buffer indices, < 0 none)
+#define PLLHIP_DEFERRED_NEED(c, a, b, sa, sb)                                      \
+  do {                                                                             \
+    if ((c)->n_deferred) {                                                         \
+      const unsigned int clv_def_[2] = {(unsigned int)(a), (unsigned int)(b)};     \
+      const int sc_def_[2] = {(int)(sa), (int)(sb)};                               \
+      int rc_def_ = pllhip_deferred_materialise(c, clv_def_, 2);                   \
+      if (!rc_def_) rc_def_ = pllhip_deferred_materialise_scalers(c, sc_def_, 2);  \
+      if (rc_def_) return rc_def_;                                                 \
+    }                                                                              \
   } while (0)
 // per-level path (partials.hip) and whole-list kernel (partials_aa_fused.hip): marks after the list, which ops test
 void pllhip_cert_mark_clv(pllhip_ctx * c, unsigned int clv_index, double err);

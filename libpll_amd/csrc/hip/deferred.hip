@@ -1,0 +1,167 @@
+// deferred.hip -- deferred cherries: materialising a CLV that a 4-state whole-list launch did not store.
+//
+// A tip-tip op's parent at a site is row (c1, c2) of the op's pair table (partials_fused.hip: k_dna_pair_tables), one
+// of 256 values.  The whole-list kernel no longer runs such an op: its readers in the list take what they need from
+// tables, and the CLV is DEFERRED -- defined by its two tip rows and a kept copy T[c1][c2][rate][state] of the pair
+// table (pllhip_ctx::defer_pool; a snapshot: a later pll_update_prob_matrices does not change what the CLV is, just
+// as the reference's CLV keeps its value until an op rewrites it).  Every entry point that reads or overwrites a CLV
+// or a scale buffer outside a list kernel comes through here first (ctx.hpp: PLLHIP_DEFERRED_NEED / _FLUSH): one
+// launch gathers the rows of all the CLVs asked for, blockIdx.y = CLV, and zeroes the scale buffers the ops would
+// have cleared (core_partials_avx.c:598-599) -- the bytes the tip-tip op itself would have stored.
+#include <algorithm>
+
+#include "ctx.hpp"
+#include "numerics.hpp"
+
+#define PLLHIP_DEFER_BATCH 48
+struct DeferredJobs
+{
+  const pll_v2d * tab[PLLHIP_DEFER_BATCH];
+  const unsigned char * c1[PLLHIP_DEFER_BATCH];
+  const unsigned char * c2[PLLHIP_DEFER_BATCH];
+  pll_v2d * clv[PLLHIP_DEFER_BATCH];
+  unsigned int * counts[PLLHIP_DEFER_BATCH]; // nullptr: none
+};
+static_assert(sizeof(DeferredJobs) <= 3900, "the jobs travel as kernel arguments");
+
+// one lane per 16 bytes of the CLV: site n's row is T[(c1[n] & 15) << 4 | (c2[n] & 15)], span2 granules
+// (the list kernels' pair index: partials_fused.hip, gather())
+template <bool NT>
+__global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs, size_t sites, unsigned int span2,
+                                                              unsigned int count_words)
+{
+  const pll_v2d * __restrict__ tab = jobs.tab[blockIdx.y];
+  const unsigned char * __restrict__ c1 = jobs.c1[blockIdx.y];
+  const unsigned char * __restrict__ c2 = jobs.c2[blockIdx.y];
+  pll_v2d * __restrict__ clv = jobs.clv[blockIdx.y];
+  unsigned int * __restrict__ counts = jobs.counts[blockIdx.y];
+  const size_t total = sites * span2;
+  for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+  {
+    const size_t n = t / span2;
+    const unsigned int g = (unsigned int)(t - n * span2);
+    const unsigned int pair = ((unsigned int)(c1[n] & 15u) << 4) | (unsigned int)(c2[n] & 15u);
+    const pll_v2d v = tab[(size_t)pair * span2 + g];
+    if (NT) __builtin_nontemporal_store(v, clv + t);
+    else clv[t] = v;
+  }
+  if (counts)
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < sites * count_words; t += (size_t)gridDim.x * blockDim.x)
+      counts[t] = 0u;
+}
+
+double * pllhip_deferred_table(pllhip_ctx * c, unsigned int idx)
+{
+  if (!c->defer_pool)
+  {
+    if (c->defer_pool_failed) return nullptr;
+    const size_t bytes = c->clv.size() * 256 * c->span * sizeof(double);
+    if (bytes > ((size_t)512 << 20) || hipMalloc((void **)&c->defer_pool, bytes) != hipSuccess)
+    {
+      (void)hipGetLastError();
+      c->defer_pool = nullptr;
+      c->defer_pool_failed = true;
+      return nullptr;
+    }
+  }
+  return c->defer_pool + (size_t)idx * 256 * c->span;
+}
+
+static void deferred_clear(pllhip_ctx * c, unsigned int idx)
+{
+  pllhip_ctx::deferred_clv & d = c->deferred[idx];
+  if (!d.on) return;
+  if (d.scaler >= 0 && (size_t)d.scaler < c->deferred_sc_owner.size() && c->deferred_sc_owner[d.scaler] == (int)idx)
+    c->deferred_sc_owner[d.scaler] = -1;
+  d.on = false;
+  --c->n_deferred;
+  ++c->defer_epoch;
+}
+
+void pllhip_deferred_drop(pllhip_ctx * c, unsigned int idx)
+{
+  if (idx < c->deferred.size()) deferred_clear(c, idx);
+}
+
+int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
+{
+  if (!c->n_deferred) return 0;
+  std::vector<unsigned int> todo;
+  if (n < 0)
+  {
+    for (unsigned int i = 0; i < c->deferred.size(); ++i)
+      if (c->deferred[i].on) todo.push_back(i);
+  }
+  else
+    for (int k = 0; k < n; ++k)
+      if (idx[k] < c->deferred.size() && c->deferred[idx[k]].on &&
+          std::find(todo.begin(), todo.end(), idx[k]) == todo.end())
+        todo.push_back(idx[k]);
+  if (todo.empty()) return 0;
+  HIP_TRY(hipSetDevice(c->sh.device));
+  const unsigned int span2 = (unsigned int)(c->span / 2);
+  const size_t total = (size_t)c->sh.sites * span2;
+  const unsigned int gx = (unsigned int)std::min<size_t>(std::max<size_t>(1, (total + 255) / 256), (size_t)c->num_cus * 8);
+  const bool nt = pllhip_use_nt(c);
+  for (size_t first = 0; first < todo.size(); first += PLLHIP_DEFER_BATCH)
+  {
+    const unsigned int m = (unsigned int)std::min<size_t>(PLLHIP_DEFER_BATCH, todo.size() - first);
+    DeferredJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    for (unsigned int k = 0; k < m; ++k)
+    {
+      const unsigned int i = todo[first + k];
+      const pllhip_ctx::deferred_clv & d = c->deferred[i];
+      jobs.tab[k] = reinterpret_cast<const pll_v2d *>(pllhip_deferred_table(c, i));
+      jobs.c1[k] = pllhip_tip_ptr(c, d.tip1);
+      jobs.c2[k] = pllhip_tip_ptr(c, d.tip2);
+      jobs.clv[k] = reinterpret_cast<pll_v2d *>(c->clv[i]);
+      jobs.counts[k] = pllhip_scaler_ptr(c, d.scaler);
+    }
+    if (nt) k_deferred_materialise<true><<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, 1u);
+    else k_deferred_materialise<false><<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, 1u);
+    HIP_TRY(hipGetLastError());
+    ++c->defer_stats[2];
+  }
+  for (unsigned int i : todo) deferred_clear(c, i);
+  c->defer_stats[3] += todo.size();
+  return 0;
+}
+
+int pllhip_deferred_materialise_scalers(pllhip_ctx * c, const int * sc, int n)
+{
+  if (!c->n_deferred) return 0;
+  unsigned int owners[8];
+  int m = 0;
+  for (int k = 0; k < n && m < 8; ++k)
+    if (sc[k] >= 0 && (size_t)sc[k] < c->deferred_sc_owner.size() && c->deferred_sc_owner[sc[k]] >= 0)
+      owners[m++] = (unsigned int)c->deferred_sc_owner[sc[k]];
+  return m ? pllhip_deferred_materialise(c, owners, m) : 0;
+}
+
+extern "C" int pllhip_set_deferral(pllhip_ctx_t * c, int on)
+{
+  PLLHIP_ALL_SHARDS(c, pllhip_set_deferral(s, on));
+  if (c->cherry_deferral == (on != 0)) return 0;
+  if (!on) PLLHIP_DEFERRED_FLUSH(c);
+  c->cherry_deferral = on != 0;
+  ++c->defer_epoch;
+  return 0;
+}
+
+extern "C" int pllhip_deferred_stats(pllhip_ctx_t * c, unsigned long long * out4)
+{
+  for (int t = 0; t < 4; ++t) out4[t] = 0;
+  if (!c->shards.empty())
+  {
+    for (pllhip_ctx * s : c->shards)
+    {
+      out4[0] += s->n_deferred;
+      for (int t = 1; t < 4; ++t) out4[t] += s->defer_stats[t];
+    }
+    return 0;
+  }
+  out4[0] = c->n_deferred;
+  for (int t = 1; t < 4; ++t) out4[t] = c->defer_stats[t];
+  return 0;
+}

@@ -114,6 +114,7 @@ extern "C" int pllhip_update_sumtable(pllhip_ctx_t * c, unsigned int parent_clv,
     pllhip_set_error("pllhip_update_sumtable: index out of range");
     return -1;
   }
+  PLLHIP_DEFERRED_NEED(c, parent_clv, child_clv, parent_scaler, child_scaler);
   const bool tp = pllhip_is_tip(c, parent_clv), tc = pllhip_is_tip(c, child_clv);
   if (tp && tc)
   {
@@ -700,6 +701,7 @@ extern "C" int pllhip_likelihood_derivatives(pllhip_ctx_t * c, unsigned int slot
     return pllhip_group_likelihood_derivatives(c, slot, parent_scaler, child_scaler, h_params_indices, h_diagptable, h_d_f, h_dd_f);
   HIP_TRY(hipSetDevice(c->sh.device));
   if (!c->defer) PLLHIP_CERT_FIRST(c); // (reads scaler counts; the sumtable call before it has normally looked already.  A shard of a group: shard.hip looks)
+  PLLHIP_DEFERRED_NEED(c, ~0u, ~0u, parent_scaler, child_scaler);
   if (slot >= PLLHIP_SUMTABLE_MAX_SLOTS || !c->sumtable[slot])
   {
     pllhip_set_error("pllhip_likelihood_derivatives: sumtable slot %u empty", slot);

@@ -306,6 +306,7 @@ static int ins_run(pllhip_ctx * c, const pllhip_insertion_edge_t * E, unsigned i
     }
   }
   PLLHIP_CERT_FIRST(c); // (the CLVs read here are the reference's, or the list runs again first)
+  PLLHIP_DEFERRED_FLUSH(c); // (deferred cherries get their bytes before anything but a list kernel touches them)
 
   // ---- chunk sizes: everything one chunk needs within `budget` bytes (one pair at least)
   const size_t sites = c->sh.sites;

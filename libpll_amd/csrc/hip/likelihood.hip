@@ -1154,6 +1154,7 @@ extern "C" int pllhip_edge_loglikelihood(pllhip_ctx_t * c, unsigned int parent_c
     pllhip_set_error("pllhip_edge_loglikelihood: index out of range");
     return -1;
   }
+  PLLHIP_DEFERRED_NEED(c, parent_clv, child_clv, parent_scaler, child_scaler);
   LnlArgs a;
   memset(&a, 0, sizeof(a));
   if (fill_freqs_indices(c, a, h_freqs_indices)) return -1;
@@ -1221,6 +1222,7 @@ extern "C" int pllhip_root_loglikelihood(pllhip_ctx_t * c, unsigned int clv_inde
     pllhip_set_error("pllhip_root_loglikelihood: index out of range");
     return -1;
   }
+  PLLHIP_DEFERRED_NEED(c, clv_index, clv_index, scaler_index, -1);
   LnlArgs a;
   memset(&a, 0, sizeof(a));
   if (fill_freqs_indices(c, a, h_freqs_indices)) return -1;

@@ -551,6 +551,7 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
     return -3;
   }
   PLLHIP_CERT_FIRST(c); // (the CLVs and scaler counts read here are the reference's, or the list runs again first)
+  PLLHIP_DEFERRED_FLUSH(c); // (deferred cherries get their bytes before anything but a list kernel touches them)
 
   const bool scaled = nsc > 0;
   const bool covers = S == 4 && (R == 1 || R == 4) && !(scaled && c->sh.rate_scalers);

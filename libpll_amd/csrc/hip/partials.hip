@@ -792,14 +792,19 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
   // round 3 they lost -- 3 ops 260 vs 200 us -- to the tile counter, not to their reloads: see the kernel.)
   if (dna_fast && (c->sh.rate_cats <= 4 || c->sh.rate_cats == 8) && !c->no_fused && fused_pays && c->rows.empty() && count >= 2)
   {
+    // (deferred cherries: the kept plan stands for a set of deferred CLVs -- it is the same list only while none of
+    // them has been materialised, dropped or pinned since, defer_epoch; the launch then defers the same ones again)
     if (c->fused_last_ops.size() == count && !c->fused_debug &&
-        c->fused_last_epoch == c->layout_epoch &&
+        c->fused_last_epoch == c->layout_epoch && c->fused_last_defer_epoch == c->defer_epoch &&
         memcmp(c->fused_last_ops.data(), ops, (size_t)count * sizeof(pllhip_op_t)) == 0)
     {
       pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
+      c->defer_stats[1] += c->fused_last_deferred.size() / 4;
       return pllhip_relaunch_fused(c);
     }
     c->fused_last_ops.clear();
+    const unsigned int full_count = count;       // (the caller's list; `ops` / `count` below: the ops the kernel runs)
+    const pllhip_op_t * const full_ops = ops;
     std::vector<PartialsArgs> args(count);
     std::vector<int> kinds(count), modes(count);
     for (unsigned int i = 0; i < count; ++i)
@@ -807,13 +812,142 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
       int rc = resolve_op(c, ops[i], args[i], kinds[i], modes[i]);
       if (rc) return rc;
     }
+    // ---- deferred cherries (partials_fused.hpp: pllhip_fused_deferral).  The tip-tip ops of the list
+    // that a tree-like use allows are not run: their parents become deferred, their readers take a factor from a table.
+    FusedDeferral dd;
+    std::vector<pllhip_op_t> kept_ops;
+    std::vector<FusedExtra> extras;
+    std::vector<FusedPairJob> keep_jobs;
+    std::vector<unsigned int> new_deferred; // {clv, tip1, tip2, scaler + 1} per deferred op
+    const bool may_defer = c->cherry_deferral && c->sh.pattern_tip && !c->sh.rate_scalers && c->sh.rate_cats <= 4;
+    if (!may_defer) PLLHIP_DEFERRED_FLUSH(c);
+    if (may_defer)
+    {
+      if (c->deferred.size() != c->clv.size()) c->deferred.assign(c->clv.size(), pllhip_ctx::deferred_clv());
+      if (c->deferred_sc_owner.size() != c->sh.scale_buffers) c->deferred_sc_owner.assign(c->sh.scale_buffers, -1);
+      if (c->clv_pinned.size() != c->clv.size()) c->clv_pinned.assign(c->clv.size(), 0);
+      std::vector<unsigned char> oldf(c->clv.size(), 0);
+      std::vector<int> oldsc(c->clv.size(), -1);
+      for (size_t i = 0; c->n_deferred && i < c->clv.size(); ++i)
+        if (c->deferred[i].on)
+        {
+          oldf[i] = 1;
+          oldsc[i] = c->deferred[i].scaler;
+        }
+      const FusedGeom g0 = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
+      pllhip_fused_deferral(g0, ops, count, oldf.data(), oldsc.data(), c->clv_pinned.data(), dd);
+      unsigned int ndefer = 0;
+      for (unsigned int i = 0; i < count; ++i) ndefer += dd.defer[i];
+      bool any_kept_table = false;
+      for (size_t i = 0; i < c->clv.size(); ++i) any_kept_table = any_kept_table || (dd.as_tip[i] && oldf[i]);
+      if (count - ndefer < 2 || ((ndefer || any_kept_table) && !pllhip_deferred_table(c, 0)))
+      {
+        // (too little left for a list kernel, or no room for the tables: ordinary buffers, ordinary ops)
+        PLLHIP_DEFERRED_FLUSH(c);
+        dd.defer.assign(count, 0);
+        dd.as_tip.assign(c->clv.size(), 0);
+        dd.dropped.clear();
+      }
+      else
+      {
+        if (!dd.materialise.empty())
+        {
+          const int rc = pllhip_deferred_materialise(c, dd.materialise.data(), (int)dd.materialise.size());
+          if (rc) return rc;
+          for (unsigned int i : dd.materialise) dd.as_tip[i] = 0;
+        }
+        // one operand of a kept op as a gathered one: a tip, or a cherry deferred by this list / by an earlier call
+        std::vector<int> deferring_op(c->clv.size(), -1);
+        for (unsigned int i = 0; i < count; ++i)
+          if (dd.defer[i]) deferring_op[ops[i].parent_clv] = (int)i;
+        auto operand = [&](unsigned int clv, unsigned int matrix) {
+          FusedOperand g;
+          memset(&g, 0, sizeof(g));
+          g.mat = pllhip_pmat_ptr(c, matrix);
+          if (pllhip_is_tip(c, clv))
+          {
+            g.type = FUSED_G_TIP;
+            g.row1 = pllhip_tip_ptr(c, clv);
+          }
+          else if (deferring_op[clv] >= 0)
+          {
+            const pllhip_op_t & d = ops[deferring_op[clv]];
+            g.type = FUSED_G_CHERRY_NEW;
+            g.row1 = pllhip_tip_ptr(c, d.child1_clv);
+            g.row2 = pllhip_tip_ptr(c, d.child2_clv);
+            g.c_lmat = pllhip_pmat_ptr(c, d.child1_matrix);
+            g.c_rmat = pllhip_pmat_ptr(c, d.child2_matrix);
+          }
+          else
+          {
+            const pllhip_ctx::deferred_clv & d = c->deferred[clv];
+            g.type = FUSED_G_CHERRY_KEPT;
+            g.row1 = pllhip_tip_ptr(c, d.tip1);
+            g.row2 = pllhip_tip_ptr(c, d.tip2);
+            g.kept = pllhip_deferred_table(c, clv);
+          }
+          return g;
+        };
+        std::vector<PartialsArgs> kargs;
+        std::vector<int> kkinds;
+        for (unsigned int i = 0; i < count; ++i)
+        {
+          const pllhip_op_t & op = ops[i];
+          if (dd.defer[i])
+          {
+            keep_jobs.push_back(FusedPairJob{args[i].lmat, args[i].rmat, pllhip_deferred_table(c, op.parent_clv), 1ull, nullptr, nullptr});
+            new_deferred.insert(new_deferred.end(), {op.parent_clv, op.child1_clv, op.child2_clv, (unsigned int)(op.parent_scaler + 1)});
+            continue;
+          }
+          PartialsArgs a = args[i];
+          int kind = kinds[i];
+          FusedExtra x;
+          memset(&x, 0, sizeof(x));
+          const bool d1 = !pllhip_is_tip(c, op.child1_clv) && dd.as_tip[op.child1_clv];
+          const bool d2 = !pllhip_is_tip(c, op.child2_clv) && dd.as_tip[op.child2_clv];
+          if (d1 || d2)
+          {
+            const bool g1 = d1 || pllhip_is_tip(c, op.child1_clv), g2 = d2 || pllhip_is_tip(c, op.child2_clv);
+            a.left = a.right = nullptr;
+            a.ltip = a.rtip = nullptr;
+            a.lscaler = a.rscaler = nullptr;
+            if (g1 && g2)
+            {
+              kind = 3;
+              x.g[0] = operand(op.child1_clv, op.child1_matrix);
+              x.g[1] = operand(op.child2_clv, op.child2_matrix);
+            }
+            else
+            {
+              // the gathered operand plays the tip of a tip-inner op: "left"
+              kind = 1;
+              const unsigned int gathered = g1 ? op.child1_clv : op.child2_clv, inner = g1 ? op.child2_clv : op.child1_clv;
+              x.g[0] = operand(gathered, g1 ? op.child1_matrix : op.child2_matrix);
+              a.right = c->clv[inner];
+              a.lmat = pllhip_pmat_ptr(c, g1 ? op.child1_matrix : op.child2_matrix);
+              a.rmat = pllhip_pmat_ptr(c, g1 ? op.child2_matrix : op.child1_matrix);
+              a.rscaler = pllhip_scaler_ptr(c, g1 ? op.child2_scaler : op.child1_scaler);
+            }
+          }
+          kept_ops.push_back(op);
+          kargs.push_back(a);
+          kkinds.push_back(kind);
+          extras.push_back(x);
+        }
+        args.swap(kargs);
+        kinds.swap(kkinds);
+        ops = kept_ops.data();
+        count = (unsigned int)kept_ops.size();
+      }
+    }
     // Three workgroups per CU (12 waves) hide the per-op latencies better than two, but
     // leave one LDS slot less per wave (6 against 7 at 4 rate categories): the 12-wave
     // configuration whenever the planner can keep every operand in a slot with it (values
     // that give their slot up, and operands written by earlier calls, are copied back from
     // HBM by LDS-DMA one op ahead).  A list the planner does not take -- counts that were not
     // written together with their CLV -- runs per level.
-    const FusedGeom geom = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
+    FusedGeom geom = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
+    if (!extras.empty()) geom.as_tip = dd.as_tip.data();
     // (PLLHIP_FUSED_WGS=2: the 8-wave, 7-slot configuration at once -- tests run both)
     const unsigned int first_wgs = pllhip_env("PLLHIP_FUSED_WGS") && atoi(pllhip_env("PLLHIP_FUSED_WGS")) == 2 ? 2u : 3u;
     // Round 5: independent sub-lists (the two sides of the root edge of a full traversal) as SEGMENTS of one launch
@@ -839,11 +973,13 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
           unsigned int reloads = 0;
           if (nsegs == 1)
           {
-            rc = pllhip_fused_plan(geom, ops, args.data(), kinds.data(), count, nslots, fplans[0], &reloads);
+            rc = pllhip_fused_plan(geom, ops, args.data(), kinds.data(), count, nslots, fplans[0], &reloads,
+                                   extras.empty() ? nullptr : extras.data());
             continue;
           }
           std::vector<pllhip_op_t> sops;
           std::vector<PartialsArgs> sargs;
+          std::vector<FusedExtra> sextras;
           std::vector<int> skinds, where;
           for (unsigned int i = 0; i < count; ++i)
             if (seg_of[i] == sg)
@@ -851,9 +987,11 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
               sops.push_back(ops[i]);
               sargs.push_back(args[i]);
               skinds.push_back(kinds[i]);
+              if (!extras.empty()) sextras.push_back(extras[i]);
               where.push_back((int)i);
             }
-          rc = pllhip_fused_plan(geom, sops.data(), sargs.data(), skinds.data(), (unsigned int)sops.size(), nslots, fplans[sg], &reloads);
+          rc = pllhip_fused_plan(geom, sops.data(), sargs.data(), skinds.data(), (unsigned int)sops.size(), nslots, fplans[sg], &reloads,
+                                 sextras.empty() ? nullptr : sextras.data());
           for (FusedOp & f : fplans[sg]) f.list_pos = where[f.list_pos];
         }
       }
@@ -863,12 +1001,36 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
     if (rc == 0)
     {
       pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
-      rc = pllhip_launch_fused(c, fplans, nslots);
-      if (rc == 0) c->fused_last_ops.assign(ops, ops + count);
+      rc = pllhip_launch_fused(c, fplans, nslots, keep_jobs.empty() ? nullptr : &keep_jobs);
+      if (rc == 0)
+      {
+        // the deferrals this list ends and begins
+        for (unsigned int i : dd.dropped) pllhip_deferred_drop(c, i);
+        for (size_t t = 0; t < new_deferred.size(); t += 4)
+        {
+          const unsigned int clv = new_deferred[t];
+          const int sc = (int)new_deferred[t + 3] - 1;
+          pllhip_deferred_drop(c, clv);
+          pllhip_ctx::deferred_clv & d = c->deferred[clv];
+          d.on = true;
+          d.tip1 = new_deferred[t + 1];
+          d.tip2 = new_deferred[t + 2];
+          d.scaler = sc;
+          if (sc >= 0) c->deferred_sc_owner[sc] = (int)clv;
+          ++c->n_deferred;
+        }
+        c->defer_stats[1] += new_deferred.size() / 4;
+        c->fused_last_deferred = new_deferred;
+        c->fused_last_defer_epoch = c->defer_epoch;
+        c->fused_last_ops.assign(full_ops, full_ops + full_count);
+      }
       if (rc <= 0) return rc;
     }
-    // (a list shape the kernel does not take: per-level launches below)
+    // (a list shape the kernel does not take: per-level launches below, on ordinary buffers)
+    ops = full_ops;
+    count = full_count;
   }
+  PLLHIP_DEFERRED_FLUSH(c);
 
   // 20 states, 4 rate categories: the whole list in one site-blocked launch on the matrix cores
   // (partials_aa_fused.hip); from one workgroup tile (32 sites) per workgroup slot of the device on

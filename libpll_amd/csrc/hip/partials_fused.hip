@@ -40,6 +40,8 @@
 //             do not write at the same rate), the ticket requested two ops before it is needed
 //   plan      one 64-byte record per op, read through the scalar data cache one op ahead: absolute
 //             addresses and LDS offsets, decoded by the host (FusedRec in partials_fused.hpp)
+//   cherries  a tip-tip op is not run at all where the list allows it: its parent is DEFERRED (deferred.hip), and the ops
+//             that read it take their factor from a table -- gathered-inner (kind 1) and gathered-gathered (kind 3)
 //   limit     a wave's own serial path, not HBM: twelve waves per CU is all the slots allow, so
 //             the order within an op overlaps the wave's latencies with its own work (see step())
 //
@@ -94,6 +96,8 @@ __device__ __forceinline__ Rec rec_load(const FusedRec * plan, unsigned int i)
 }
 __device__ __forceinline__ unsigned long long rec_quad(const Rec & r, int t) { return (unsigned long long)r.w[t] | ((unsigned long long)r.w[t + 1] << 32); }
 __device__ __forceinline__ unsigned int rec_chars(const Rec & r) { return r.w[0]; }
+__device__ __forceinline__ unsigned int rec_chars2(const Rec & r) { return r.w[1]; }
+__device__ __forceinline__ unsigned int rec_gather2(const Rec & r) { return r.w[2]; }
 __device__ __forceinline__ unsigned int rec_req_lmat(const Rec & r) { return r.w[4]; }
 __device__ __forceinline__ unsigned int rec_req_rmat(const Rec & r) { return r.w[5]; }
 __device__ __forceinline__ unsigned int rec_gather(const Rec & r) { return r.w[6]; }
@@ -128,6 +132,57 @@ __global__ __launch_bounds__(256) void k_dna_pair_tables(const FusedPairJob * __
   const unsigned int i = blockIdx.x >> 2, quarter = blockIdx.x & 3u;
   if (blockIdx.x == 0 && tile_counters) tile_counters[threadIdx.x * 32u] = 0u;
   if (i >= njobs) return;
+  // Deferred cherries: the factor a READER with matrix P takes from a cherry that is not stored,
+  // F[c1][c2][rate][s] = dot4(P[rate][s], T[c1][c2][rate][.]) -- the bits pl.dot() / pr.dot() of the list kernel give
+  // from the stored cherry (separate products, (x0 + x1) + (x2 + x3); a lane with h = 1 adds the two halves the other
+  // way round, which is the same sum).  A cherry deferred by this very list: its T entries are formed here from its own
+  // two matrices, as the job that keeps T forms them (no waiting for another workgroup); one deferred earlier: read.
+  if (jobs[i].kind >= 2)
+  {
+    constexpr unsigned int ROW = RC * 4u, PER = 256u / ROW, ROUNDS = 64u / PER;
+    const unsigned int ki = threadIdx.x % ROW, sub = threadIdx.x / ROW, rate4 = (ki >> 2) * 4u;
+    const PLL_GLOBAL double * pm = (const PLL_GLOBAL double *)jobs[i].pmat;
+    double * tab = jobs[i].tab;
+    double p[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = pm[ki * 4u + k];
+    if (jobs[i].kind == 2)
+    {
+      const PLL_GLOBAL double * lm = (const PLL_GLOBAL double *)jobs[i].lmat, * rm = (const PLL_GLOBAL double *)jobs[i].rmat;
+      double l[4][4], r[4][4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+        {
+          l[k][m] = lm[(rate4 + k) * 4u + m];
+          r[k][m] = rm[(rate4 + k) * 4u + m];
+        }
+#pragma unroll
+      for (unsigned int round = 0; round < ROUNDS; ++round)
+      {
+        const unsigned int pair = quarter * 64u + round * PER + sub, c1 = pair >> 4, c2 = pair & 15u;
+        double t[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) t[k] = masksum4(l[k], c1) * masksum4(r[k], c2);
+        tab[pair * ROW + ki] = dot4(p, t[0], t[1], t[2], t[3]);
+      }
+    }
+    else
+    {
+      const PLL_GLOBAL double * kept = (const PLL_GLOBAL double *)jobs[i].kept;
+#pragma unroll
+      for (unsigned int round = 0; round < ROUNDS; ++round)
+      {
+        const unsigned int pair = quarter * 64u + round * PER + sub;
+        double t[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) t[k] = kept[pair * ROW + rate4 + k];
+        tab[pair * ROW + ki] = dot4(p, t[0], t[1], t[2], t[3]);
+      }
+    }
+    return;
+  }
   // Round 5: the table written in address order.  (A thread per character pair that
   // read its 2 x 16 rows of 4 straight from memory and wrote 128 contiguous bytes of its own took 10.6 us per launch
   // -- sixteen dependent trips to L1 per thread --, a fifth of pll_update_partials at 20,000 sites.)  Same products,
@@ -136,7 +191,7 @@ __global__ __launch_bounds__(256) void k_dna_pair_tables(const FusedPairJob * __
   double * tab = jobs[i].tab;
   // (tip-inner ops: the tip's factor alone, in the entries [code 1][0] the kernel's index
   // (code 1 << 4 | character of an absent tip = 0) reaches; x * 1.0 is x)
-  const bool tt = jobs[i].tip_tip != 0;
+  const bool tt = jobs[i].kind != 0;
   constexpr unsigned int ROW = RC * 4u;                 // entries of a pair: (rate, state)
   constexpr unsigned int PER = 256u / ROW;              // pairs a workgroup makes per round
   constexpr unsigned int ROUNDS = 64u / PER;            // rounds of its quarter (64 pairs)
@@ -327,15 +382,22 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     };
     // ... and ONE op ahead its entries of the pair table are gathered (table 0, all zeros, for an op
     // without a tip; an absent tip's character is 0)
-    auto gather = [&](double2 (&pt)[J], const Rec & r) {
-      const unsigned int ch = rec_chars(r);
+    // (deferred cherries: both characters of a pair may belong to ONE operand -- the cherry's two tips -- and an op
+    // whose two factors are both gathered, kind 3, takes the second one from a table of its own: every op issues that
+    // second gather too, from the table of zeros)
+    auto gather = [&](double2 (&pt)[J], double2 (&pt2)[J], const Rec & r) {
+      const unsigned int ch = rec_chars(r), ch2 = rec_chars2(r);
       const unsigned int lmask = (ch & PLLHIP_FUSED_CH_LTIP) ? 15u : 0u, rmask = (ch & PLLHIP_FUSED_CH_RTIP) ? 15u : 0u;
+      const unsigned int lmask2 = (ch2 & PLLHIP_FUSED_CH_LTIP) ? 15u : 0u, rmask2 = (ch2 & PLLHIP_FUSED_CH_RTIP) ? 15u : 0u;
 #pragma unroll
       for (unsigned int j = 0; j < J; ++j)
       {
         const unsigned int pair = ((row_code(PLLHIP_FUSED_CH_LPOS(ch), j) & lmask) << 4) | (row_code(PLLHIP_FUSED_CH_RPOS(ch), j) & rmask);
         const unsigned int off = pair * (W * 16u) + gat_lane + rec_gather(r);
         pt[j] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(bases.pairtab) + off);
+        const unsigned int pair2 = ((row_code(PLLHIP_FUSED_CH_LPOS(ch2), j) & lmask2) << 4) | (row_code(PLLHIP_FUSED_CH_RPOS(ch2), j) & rmask2);
+        const unsigned int off2 = pair2 * (W * 16u) + gat_lane + rec_gather2(r);
+        pt2[j] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(bases.pairtab) + off2);
       }
       // the list moves on to rows this batch does not hold (rare: every 1024 / TS tip operands): the lanes'
       // addresses of the next batch, then its rows.  Assembly, like reload(): the compiler counts no load
@@ -455,7 +517,7 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     Rec ra = rec_load(plan, 2), rb;
     FusedFetch<J> fa, fb;
     half_rows pl, pr;
-    double2 pta[J], ptb[J];
+    double2 pta[J], ptb[J], pta2[J], ptb2[J];
     // The prologue issues its memory operations in the order two ops would -- requests, gather,
     // stores (to the sink) -- because the compiler counts the operations issued after a load to
     // know how many may stay in flight when the load is consumed, and takes the minimum over
@@ -473,7 +535,7 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     request(fb, h0);
     sink_stores();
     if (rec_flags(h1) & PLLHIP_FUSED_RELOAD_NEXT) reload(rec_src(h1));
-    gather(pta, h1);
+    gather(pta, pta2, h1);
     request(fa, h1);
     asm volatile("" ::"v"(fb.pm.x), "v"(fb.pm.y) : "memory");
     if (RC == 8) asm volatile("" ::"v"(fb.pm2.x), "v"(fb.pm2.y) : "memory");
@@ -485,7 +547,7 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     // The caller alternates the two of each, so that nothing loaded is ever copied (a copy
     // would have to wait for the load).
     auto step = [&](const Rec & r0, Rec & r1, const FusedFetch<J> & fu, FusedFetch<J> & ff, const double2 (&pu)[J],
-                    double2 (&pf)[J], unsigned int i) __attribute__((always_inline)) {
+                    double2 (&pf)[J], const double2 (&pu2)[J], double2 (&pf2)[J], unsigned int i) __attribute__((always_inline)) {
       // A wave is the limit of this kernel, not HBM: with twelve waves per CU nothing hides
       // what a wave waits for itself (counters: ~2300 cycles per op of which ~500 issue
       // vector and ~270 scalar instructions).  So the order below overlaps the wave's own
@@ -534,13 +596,13 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
         asm volatile("s_mov_b64 exec, 1\n\tglobal_atomic_add %0, %1, %2, off sc0\n\ts_mov_b64 exec, -1"
                      : "=&v"(next_ticket) : "v"(ticket_counter), "v"(1u) : "memory");
       // (the request last: what the next op waits for first is the youngest operation in flight)
-      gather(pf, r0);
+      gather(pf, pf2, r0);
       request(ff, r0);
       // (every load is consumed on every path, needed or not: the registers of a load that
       // nobody waited for stay "pending" for the compiler, and it drains the queue -- this op's
       // predecessor's stores included -- when it next reuses them)
 #pragma unroll
-      for (unsigned int j = 0; j < J; ++j) asm volatile("" ::"v"(pu[j].x), "v"(pu[j].y));
+      for (unsigned int j = 0; j < J; ++j) asm volatile("" ::"v"(pu[j].x), "v"(pu[j].y), "v"(pu2[j].x), "v"(pu2[j].y));
       unsigned long long scaled[J];
       double p0[J], p1[J];
       if (kind == 2)
@@ -562,9 +624,9 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
         {
           const double2 rp = make_double2(dpp_pair_swap(ro[j].x), dpp_pair_swap(ro[j].y));
           double x0, x1;
-          if (kind == 1)
+          if (kind & 1u)
           {
-            // tip-inner: the tip's factor is its pair-table entry
+            // gathered-inner (a tip, or a deferred cherry) and gathered-gathered: the factor is the table entry
             x0 = pu[j].x;
             x1 = pu[j].y;
           }
@@ -574,7 +636,9 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
             x0 = pl.dot(0, lo[j], lp);
             x1 = pl.dot(1, lo[j], lp);
           }
-          double q0 = x0 * pr.dot(0, ro[j], rp), q1 = x1 * pr.dot(1, ro[j], rp);
+          // (kind 3: the second factor is gathered too -- no mat-vec at all)
+          const double y0 = kind == 3 ? pu2[j].x : pr.dot(0, ro[j], rp), y1 = kind == 3 ? pu2[j].y : pr.dot(1, ro[j], rp);
+          double q0 = x0 * y0, q1 = x1 * y1;
           // scaling rule of core_partials_avx.c:486-527: all entries of the site (of the rate,
           // with per-rate scalers) below the threshold; x * 1.0 is x
           scaled[j] = 0;
@@ -643,9 +707,9 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     };
     for (unsigned int i = 0;;)
     {
-      step(ra, rb, fa, fb, pta, ptb, i);
+      step(ra, rb, fa, fb, pta, ptb, pta2, ptb2, i);
       if (++i == nops) break;
-      step(rb, ra, fb, fa, ptb, pta, i);
+      step(rb, ra, fb, fa, ptb, pta, ptb2, pta2, i);
       if (++i == nops) break;
     }
     if (++round < static_rounds)
@@ -702,7 +766,7 @@ static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, 
                                const int * kinds, unsigned int count, unsigned int nslots,
                                const std::vector<unsigned int> & order, const std::vector<unsigned int> & pos_of,
                                const std::vector<Node> & node, std::vector<FusedOp> & plan,
-                               unsigned int * reloads_out, std::pmr::memory_resource * pool)
+                               unsigned int * reloads_out, std::pmr::memory_resource * pool, const FusedExtra * extra)
 {
   // inner operands of the op at each position: producing list op (-1: written by an earlier
   // call), its HBM address, the HBM address of the counts the reader passes with it, and the
@@ -820,6 +884,11 @@ static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, 
     f.kind = kinds[i];
     f.list_pos = (int)i;
     f.lslot = f.rslot = f.pslot = f.lsc_slot = f.rsc_slot = -1;
+    if (extra)
+    {
+      f.g[0] = extra[i].g[0];
+      f.g[1] = extra[i].g[1];
+    }
   }
   if (place_reloads(0, 0)) return 1;
   oneshot.swap(oneshot_next);
@@ -908,7 +977,7 @@ static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, 
 
 int pllhip_fused_plan(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args,
                       const int * kinds, unsigned int count, unsigned int nslots,
-                      std::vector<FusedOp> & plan, unsigned int * reloads_out)
+                      std::vector<FusedOp> & plan, unsigned int * reloads_out, const FusedExtra * extra)
 {
   static thread_local std::vector<char> arena(256 * 1024);
   std::pmr::monotonic_buffer_resource pool(arena.data(), arena.size()); // (beyond the buffer: the heap)
@@ -1003,7 +1072,7 @@ int pllhip_fused_plan(const FusedGeom & geom, const pllhip_op_t * ops, const Par
   std::vector<unsigned int> pos_of(count);
   for (unsigned int pos = 0; pos < count; ++pos) pos_of[order[pos]] = pos;
 
-  const int rc = assign_slots_reload(geom, ops, args, kinds, count, nslots, order, pos_of, node, plan, reloads_out, &pool);
+  const int rc = assign_slots_reload(geom, ops, args, kinds, count, nslots, order, pos_of, node, plan, reloads_out, &pool, extra);
   if (rc) return rc;
   if (pllhip_env("PLLHIP_FUSED_DEBUG"))
   {
@@ -1017,6 +1086,218 @@ int pllhip_fused_plan(const FusedGeom & geom, const pllhip_op_t * ops, const Par
                 (const void *)f.left_hbm, (const void *)f.right_hbm, (const void *)f.lsc_hbm, (const void *)f.rsc_hbm);
       }
   }
+  return 0;
+}
+
+// Which tip-tip ops a list defers (partials_fused.hpp).  A deferred CLV is served from tables only while the list
+// treats it the way a tree does: written once, by that op; read after it, with the scale buffer it was cleared with (or
+// none); that scale buffer written by nobody else and read with nobody else.  Anything else is materialised (a CLV
+// deferred earlier) or simply not deferred (an op of this list) -- the list then sees ordinary buffers.
+void pllhip_fused_deferral(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
+                           const unsigned char * old_deferred, const int * old_scaler, const unsigned char * pinned,
+                           FusedDeferral & out)
+{
+  const size_t nclv = geom.nclv, nsc = geom.nsc;
+  const unsigned int NONE = ~0u;
+  out.defer.assign(count, 0);
+  out.as_tip.assign(nclv, 0);
+  out.materialise.clear();
+  out.dropped.clear();
+  auto true_tip = [&](unsigned int i) { return geom.pattern_tip && i < geom.tips; };
+  std::vector<unsigned int> nwrites(nclv, 0), first_write(nclv, NONE), first_read(nclv, NONE);
+  std::vector<unsigned int> sc_nwrites(nsc, 0), sc_first_write(nsc, NONE), sc_first_read(nsc, NONE);
+  std::vector<int> cand_sc(nclv, -2);        // the scale buffer a deferred CLV i would own (-1 none, -2: no candidate)
+  std::vector<int> sc_reader(nsc, -1);       // the one CLV a scale buffer is read with (-1 nobody, -2 several)
+  std::vector<unsigned char> bad(nclv, 0);   // read with a scale buffer that is not its own
+  for (unsigned int k = 0; k < count; ++k)
+  {
+    const pllhip_op_t & op = ops[k];
+    ++nwrites[op.parent_clv];
+    if (first_write[op.parent_clv] == NONE) first_write[op.parent_clv] = k;
+    if (op.parent_scaler >= 0)
+    {
+      ++sc_nwrites[op.parent_scaler];
+      if (sc_first_write[op.parent_scaler] == NONE) sc_first_write[op.parent_scaler] = k;
+    }
+  }
+  for (size_t i = 0; i < nclv; ++i)
+  {
+    if (old_deferred && old_deferred[i]) cand_sc[i] = old_scaler ? old_scaler[i] : -1;
+    if (nwrites[i] == 1)
+    {
+      const pllhip_op_t & op = ops[first_write[i]];
+      if (true_tip(op.child1_clv) && true_tip(op.child2_clv) && !true_tip((unsigned int)i) && !(pinned && pinned[i]) &&
+          !(old_deferred && old_deferred[i]))
+        cand_sc[i] = op.parent_scaler;
+    }
+  }
+  for (unsigned int k = 0; k < count; ++k)
+  {
+    const pllhip_op_t & op = ops[k];
+    const unsigned int kid[2] = {op.child1_clv, op.child2_clv};
+    const int ksc[2] = {op.child1_scaler, op.child2_scaler};
+    for (int o = 0; o < 2; ++o)
+    {
+      if (first_read[kid[o]] == NONE) first_read[kid[o]] = k;
+      if (cand_sc[kid[o]] != -2 && ksc[o] != -1 && ksc[o] != cand_sc[kid[o]]) bad[kid[o]] = 1;
+      if (ksc[o] >= 0)
+      {
+        if (sc_first_read[ksc[o]] == NONE) sc_first_read[ksc[o]] = k;
+        if (sc_reader[ksc[o]] == -1) sc_reader[ksc[o]] = (int)kid[o];
+        else if (sc_reader[ksc[o]] != (int)kid[o]) sc_reader[ksc[o]] = -2;
+      }
+    }
+  }
+  // CLVs deferred by an earlier call
+  for (size_t i = 0; old_deferred && i < nclv; ++i)
+  {
+    if (!old_deferred[i]) continue;
+    const int s = cand_sc[i];
+    const bool sc_touched = s >= 0 && (sc_nwrites[s] || sc_first_read[s] != NONE);
+    if (nwrites[i] == 0 && first_read[i] == NONE && !sc_touched) continue; // (the list does not see it)
+    if (nwrites[i] == 0)
+    {
+      // read only: from its kept table, if its counts are its own
+      const bool ok = !bad[i] && (s < 0 || (sc_nwrites[s] == 0 && (sc_reader[s] == -1 || sc_reader[s] == (int)i)));
+      if (ok) out.as_tip[i] = 1;
+      else out.materialise.push_back((unsigned int)i);
+      continue;
+    }
+    // overwritten: the deferral ends without the bytes if nothing reads them first and its zero counts go with it
+    const unsigned int w = first_write[i];
+    const bool dead = (first_read[i] == NONE || first_read[i] > w) &&
+                      (s < 0 || (ops[w].parent_scaler == s && sc_first_write[s] == w &&
+                                 (sc_first_read[s] == NONE || sc_first_read[s] > w)));
+    if (dead) out.dropped.push_back((unsigned int)i);
+    else out.materialise.push_back((unsigned int)i);
+  }
+  // tip-tip ops of this list
+  for (unsigned int k = 0; k < count; ++k)
+  {
+    const pllhip_op_t & op = ops[k];
+    const unsigned int p = op.parent_clv;
+    const int s = op.parent_scaler;
+    if (!true_tip(op.child1_clv) || !true_tip(op.child2_clv) || true_tip(p) || (pinned && pinned[p])) continue;
+    if (nwrites[p] != 1 || bad[p] || (first_read[p] != NONE && first_read[p] <= k)) continue;
+    // (bad[] of a CLV deferred earlier was judged against its OLD scale buffer: against the new one here)
+    if (old_deferred && old_deferred[p])
+    {
+      bool wrong = false;
+      for (unsigned int r = k + 1; r < count && !wrong; ++r)
+        wrong = (ops[r].child1_clv == p && ops[r].child1_scaler != -1 && ops[r].child1_scaler != s) ||
+                (ops[r].child2_clv == p && ops[r].child2_scaler != -1 && ops[r].child2_scaler != s);
+      if (wrong) continue;
+    }
+    if (s >= 0 && (sc_nwrites[s] != 1 || (sc_reader[s] != -1 && sc_reader[s] != (int)p) ||
+                   (sc_first_read[s] != NONE && sc_first_read[s] <= k)))
+      continue;
+    out.defer[k] = 1;
+    out.as_tip[p] = 1;
+  }
+}
+
+// The planner with deferred cherries, without a device (tests/test_host_deferred_plan.py).  old_deferred / old_scaler /
+// pinned: per CLV index, may be NULL (pllhip_fused_deferral).  Out: *nkept kept ops in walk order as positions in
+// the caller's list (order_out), six numbers per kept op as pllhip_fused_plan_dry gives them (slots_out), two operand
+// kinds per kept op (operands_out: 0 a slot, 1 a tip, 2 a deferred cherry), per list op whether it is deferred
+// (deferred_out), and the CLVs deferred earlier that the list has materialised first / ends the deferral of
+// (materialise_out, dropped_out: at most clv indices each, counts in *nmaterialise, *ndropped).
+// Returns 0, 1 if the kernel does not take the list, < 0 on error.
+extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                              int pattern_tip, const pllhip_op_t * ops, unsigned int count, unsigned int nslots,
+                                              const unsigned char * old_deferred, const int * old_scaler,
+                                              const unsigned char * pinned, unsigned int * nkept, unsigned int * order_out,
+                                              int * slots_out, int * operands_out, unsigned char * deferred_out,
+                                              unsigned int * reloads_out, unsigned int * materialise_out,
+                                              unsigned int * nmaterialise, unsigned int * dropped_out, unsigned int * ndropped)
+{
+  FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
+  for (unsigned int i = 0; i < count; ++i)
+  {
+    const pllhip_op_t & op = ops[i];
+    if (op.parent_clv >= geom.nclv || op.child1_clv >= geom.nclv || op.child2_clv >= geom.nclv ||
+        op.parent_scaler >= (int)scale_buffers || op.child1_scaler >= (int)scale_buffers ||
+        op.child2_scaler >= (int)scale_buffers)
+    {
+      pllhip_set_error("pllhip_fused_plan_dry_deferred: index out of range in op %u", i);
+      return -1;
+    }
+  }
+  FusedDeferral d;
+  pllhip_fused_deferral(geom, ops, count, old_deferred, old_scaler, pinned, d);
+  std::vector<pllhip_op_t> kept;
+  std::vector<unsigned int> where;
+  for (unsigned int i = 0; i < count; ++i)
+  {
+    if (deferred_out) deferred_out[i] = d.defer[i];
+    if (!d.defer[i])
+    {
+      kept.push_back(ops[i]);
+      where.push_back(i);
+    }
+  }
+  if (nmaterialise) *nmaterialise = (unsigned int)d.materialise.size();
+  if (ndropped) *ndropped = (unsigned int)d.dropped.size();
+  for (size_t t = 0; materialise_out && t < d.materialise.size(); ++t) materialise_out[t] = d.materialise[t];
+  for (size_t t = 0; dropped_out && t < d.dropped.size(); ++t) dropped_out[t] = d.dropped[t];
+  // (what is materialised first is an ordinary buffer to the list)
+  for (unsigned int i : d.materialise) d.as_tip[i] = 0;
+  geom.as_tip = d.as_tip.data();
+  const unsigned int n = (unsigned int)kept.size();
+  if (nkept) *nkept = n;
+  std::vector<PartialsArgs> args(n);
+  std::vector<int> kinds(n);
+  for (unsigned int i = 0; i < n; ++i)
+  {
+    const pllhip_op_t & op = kept[i];
+    const bool t1 = geom.is_tip(op.child1_clv), t2 = geom.is_tip(op.child2_clv);
+    const bool tip1 = pattern_tip && op.child1_clv < tips, tip2 = pattern_tip && op.child2_clv < tips;
+    memset(&args[i], 0, sizeof(PartialsArgs));
+    kinds[i] = (tip1 && tip2) ? 2 : (t1 && t2) ? 3 : (t1 || t2) ? 1 : 0;
+    auto sc = [&](int idx) { return idx >= 0 ? reinterpret_cast<unsigned int *>((uintptr_t)4096 * (idx + 1)) : (unsigned int *)nullptr; };
+    auto clv = [&](unsigned int idx) { return reinterpret_cast<const double *>((uintptr_t)4096 * (idx + 1)); };
+    args[i].pscaler = sc(op.parent_scaler);
+    if (kinds[i] == 0)
+    {
+      args[i].left = clv(op.child1_clv);
+      args[i].right = clv(op.child2_clv);
+      args[i].lscaler = sc(op.child1_scaler);
+      args[i].rscaler = sc(op.child2_scaler);
+    }
+    else if (kinds[i] == 1)
+    {
+      args[i].right = clv(t1 ? op.child2_clv : op.child1_clv);
+      args[i].rscaler = sc(t1 ? op.child2_scaler : op.child1_scaler);
+    }
+    if (operands_out)
+    {
+      operands_out[2 * i] = tip1 ? 1 : t1 ? 2 : 0;
+      operands_out[2 * i + 1] = tip2 ? 1 : t2 ? 2 : 0;
+    }
+  }
+  if (reloads_out) *reloads_out = 0;
+  if (!n) return 0;
+  std::vector<FusedOp> plan;
+  unsigned int reloads = 0;
+  const int rc = pllhip_fused_plan(geom, kept.data(), args.data(), kinds.data(), n, nslots, plan, &reloads);
+  if (rc) return rc;
+  std::vector<int> opnd(operands_out ? operands_out : nullptr, operands_out ? operands_out + 2 * n : nullptr);
+  for (unsigned int pos = 0; pos < n; ++pos)
+  {
+    const FusedOp & f = plan[pos];
+    if (order_out) order_out[pos] = where[f.list_pos];
+    if (operands_out)
+    {
+      operands_out[2 * pos] = opnd[2 * f.list_pos];
+      operands_out[2 * pos + 1] = opnd[2 * f.list_pos + 1];
+    }
+    if (slots_out)
+    {
+      const int v[6] = {f.lslot, f.rslot, f.pslot, f.lsc_slot, f.rsc_slot, f.dma_flags};
+      for (int t = 0; t < 6; ++t) slots_out[pos * 6 + t] = v[t];
+    }
+  }
+  if (reloads_out) *reloads_out = reloads;
   return 0;
 }
 
@@ -1118,8 +1399,10 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   // write rates): seven of the ~21 rounds of 1 M sites (the measured optimum there), and in proportion
   // for longer alignments (8 M sites x 128 taxa: 7 rounds 0.565, 30 0.584, 54 0.583 of the HBM peak;
   // 2 M sites: 7 rounds 0.652, 14 0.672); short lists two, see the kernel
+  // (a list whose cherries are deferred is as long as the list the caller handed over: a full traversal walks 30 ops
+  // where it walked 62 and keeps the long list's share of tickets; lists that defer nothing are judged as before)
   const size_t rounds = tiles * nsegs / (grid * 4);
-  const unsigned int dynamic_rounds = c->fused_last_longest >= 32 ? (unsigned int)std::max<size_t>(7, rounds / 3) : 2u;
+  const unsigned int dynamic_rounds = c->fused_last_longest + c->fused_last_ndeferred >= 32 ? (unsigned int)std::max<size_t>(7, rounds / 3) : 2u;
   // (eight counters -- but never more than there are groups of eight workgroups, or a counter's tiles would have no
   // takers; and no more than the counter buffer holds)
   const unsigned int tile_groups = (unsigned int)std::min<size_t>(std::min<size_t>(8, PLLHIP_TILE_COUNTER_BYTES / 128),
@@ -1146,14 +1429,14 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
 // both rows of an op into the same batch.  tips[pos]: bit 0 / 1 = the op has a left / right tip.  Out, per op:
 // chars (PLLHIP_FUSED_CH_LPOS / RPOS = first lane of the row, CH_LTIP / CH_RTIP) and the batch its rows are in
 // (an op without tips: the batch current at that point).  Returns the number of batches.  Pure host logic.
-unsigned int pllhip_fused_char_batches(const unsigned int * tips, unsigned int count, unsigned int lpr,
-                                       unsigned int * chars_out, unsigned int * batch_out)
+unsigned int pllhip_fused_char_batches4(const unsigned int * tips, unsigned int count, unsigned int lpr,
+                                        unsigned int * chars_out, unsigned int * chars2_out, unsigned int * batch_out)
 {
   const unsigned int rpb = 64 / lpr; // rows per batch
   unsigned int batch = 0, q = 0;
   for (unsigned int pos = 0; pos < count; ++pos)
   {
-    const unsigned int n = (tips[pos] & 1u) + ((tips[pos] >> 1) & 1u);
+    const unsigned int n = (tips[pos] & 1u) + ((tips[pos] >> 1) & 1u) + ((tips[pos] >> 2) & 1u) + ((tips[pos] >> 3) & 1u);
     if (q + n > rpb)
     {
       ++batch;
@@ -1163,8 +1446,21 @@ unsigned int pllhip_fused_char_batches(const unsigned int * tips, unsigned int c
     chars_out[pos] = 0;
     if (tips[pos] & 1u) chars_out[pos] |= PLLHIP_FUSED_CH_LTIP | (q++ * lpr);
     if (tips[pos] & 2u) chars_out[pos] |= PLLHIP_FUSED_CH_RTIP | (q++ * lpr) << 8;
+    // (the rows of a second gather -- an op with two gathered operands -- lie in the same batch)
+    if (chars2_out)
+    {
+      chars2_out[pos] = 0;
+      if (tips[pos] & 4u) chars2_out[pos] |= PLLHIP_FUSED_CH_LTIP | (q++ * lpr);
+      if (tips[pos] & 8u) chars2_out[pos] |= PLLHIP_FUSED_CH_RTIP | (q++ * lpr) << 8;
+    }
   }
   return batch + 1;
+}
+
+unsigned int pllhip_fused_char_batches(const unsigned int * tips, unsigned int count, unsigned int lpr,
+                                       unsigned int * chars_out, unsigned int * batch_out)
+{
+  return pllhip_fused_char_batches4(tips, count, lpr, chars_out, nullptr, batch_out);
 }
 
 extern "C" unsigned int pllhip_fused_char_batches_dry(const unsigned int * tips, unsigned int count, unsigned int rate_cats,
@@ -1275,7 +1571,8 @@ extern "C" unsigned int pllhip_fused_segments_dry(unsigned int tips, unsigned in
 // stand for ops -2 and -1, one record per op, one of padding (the last op's look-ahead load) -- then the segment
 // table, the reload sources, the pair-table jobs, the character rows' addresses.  Returns 1 if the list is not one
 // the kernel takes.
-int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots)
+int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
+                        const std::vector<FusedPairJob> * keep_jobs)
 {
   const unsigned int nsegs = (unsigned int)plans.size();
   unsigned int count = 0, longest = 0;
@@ -1291,7 +1588,7 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   const size_t per = (size_t)256 * R * 4; // doubles per table
   size_t ntab = 1;
   for (const auto & plan : plans)
-    for (const FusedOp & f : plan) ntab += (f.kind >= 1);
+    for (const FusedOp & f : plan) ntab += (f.kind >= 1) + (f.kind == 3);
   if (ntab * per * sizeof(double) > 0xffffffffull ||
       (size_t)c->sh.prob_matrices * c->pmat_elems * sizeof(double) > 0xffffffffull)
     return 1;
@@ -1332,42 +1629,67 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   // Tip rows in the order the segment uses them, in batches of what a wave's 64 x 16 bytes hold of a tile
   // (pllhip_fused_char_batches).  rowtab[batch][lane]: the address the lane fetches from (+ the tile's first
   // site); lanes without a row fetch zeros.  Batches are numbered across the segments.
-  std::vector<unsigned int> chars_of(n, 0), batch_of(n, 0);
+  // every op's gathered operands (FusedOperand): what the planner was told about deferred cherries, else what the
+  // op's kind says -- the tip of a tip-inner op, the finished parent of a tip-tip op
+  std::vector<FusedExtra> gx(n);
+  for (unsigned int pos = 0; pos < n; ++pos)
+  {
+    const FusedOp & f = plan[pos];
+    gx[pos].g[0] = f.g[0];
+    gx[pos].g[1] = f.g[1];
+    if (f.g[0].type == FUSED_G_NONE && f.kind == 1) gx[pos].g[0] = FusedOperand{FUSED_G_TIP, f.ltip, nullptr, f.lmat, nullptr, nullptr, nullptr};
+    if (f.g[0].type == FUSED_G_NONE && f.kind == 2) gx[pos].g[0] = FusedOperand{FUSED_G_PAIR, f.ltip, f.rtip, nullptr, f.lmat, f.rmat, nullptr};
+    if (f.kind == 3 && (gx[pos].g[0].type == FUSED_G_NONE || gx[pos].g[1].type == FUSED_G_NONE)) return 1;
+  }
+  std::vector<unsigned int> chars_of(n, 0), chars2_of(n, 0), batch_of(n, 0);
   const unsigned int batch0 = (unsigned int)(rowtab.size() / 64);
   {
     std::vector<unsigned int> ntips(n);
-    for (unsigned int pos = 0; pos < n; ++pos) ntips[pos] = (plan[pos].ltip ? 1u : 0u) | (plan[pos].rtip ? 2u : 0u);
-    const unsigned int nbatches = pllhip_fused_char_batches(ntips.data(), n, lpr, chars_of.data(), batch_of.data());
-    if (batch0 + nbatches > 255) return 1;
+    for (unsigned int pos = 0; pos < n; ++pos)
+      ntips[pos] = (gx[pos].g[0].row1 ? 1u : 0u) | (gx[pos].g[0].row2 ? 2u : 0u) | (gx[pos].g[1].row1 ? 4u : 0u) | (gx[pos].g[1].row2 ? 8u : 0u);
+    const unsigned int nbatches = pllhip_fused_char_batches4(ntips.data(), n, lpr, chars_of.data(), chars2_of.data(), batch_of.data());
+    if (batch0 + nbatches > 255 || 4 * lpr > 64) return 1;
     rowtab.resize((size_t)(batch0 + nbatches) * 64, (unsigned long long)(uintptr_t)c->fused_zero_row);
     for (unsigned int pos = 0; pos < n; ++pos)
     {
       batch_of[pos] += batch0;
-      const unsigned char * rows[2] = {plan[pos].ltip, plan[pos].rtip};
-      const unsigned int lane0[2] = {PLLHIP_FUSED_CH_LPOS(chars_of[pos]), PLLHIP_FUSED_CH_RPOS(chars_of[pos])};
-      for (int o = 0; o < 2; ++o)
+      const unsigned char * rows[4] = {gx[pos].g[0].row1, gx[pos].g[0].row2, gx[pos].g[1].row1, gx[pos].g[1].row2};
+      const unsigned int lane0[4] = {PLLHIP_FUSED_CH_LPOS(chars_of[pos]), PLLHIP_FUSED_CH_RPOS(chars_of[pos]),
+                                     PLLHIP_FUSED_CH_LPOS(chars2_of[pos]), PLLHIP_FUSED_CH_RPOS(chars2_of[pos])};
+      for (int o = 0; o < 4; ++o)
         for (unsigned int l = 0; rows[o] && l < lpr; ++l)
           rowtab[(size_t)batch_of[pos] * 64 + lane0[o] + l] = (unsigned long long)(uintptr_t)rows[o] + l * 16u;
     }
   }
-  std::vector<unsigned int> table_of(n, 0); // byte offset of each op's pair table (0: zeros)
+  std::vector<unsigned int> table_of(n, 0), table2_of(n, 0); // byte offsets of each op's tables (0: zeros)
   for (unsigned int pos = 0; pos < n; ++pos)
   {
     const FusedOp & f = plan[pos];
-    if (f.kind >= 1)
+    for (int o = 0; o < 2; ++o)
     {
+      const FusedOperand & g = gx[pos].g[o];
+      if (g.type == FUSED_G_NONE) continue;
       const size_t index = jobs.size() + 1;
-      table_of[pos] = (unsigned int)(index * per * sizeof(double));
-      jobs.push_back(FusedPairJob{f.lmat, f.rmat, c->d_pairtab + index * per, f.kind == 2 ? 1ull : 0ull});
+      (o ? table2_of : table_of)[pos] = (unsigned int)(index * per * sizeof(double));
+      double * tab = c->d_pairtab + index * per;
+      if (g.type == FUSED_G_TIP) jobs.push_back(FusedPairJob{g.mat, nullptr, tab, 0ull, nullptr, nullptr});
+      else if (g.type == FUSED_G_PAIR) jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 1ull, nullptr, nullptr});
+      else if (g.type == FUSED_G_CHERRY_NEW) jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 2ull, g.mat, nullptr});
+      else jobs.push_back(FusedPairJob{nullptr, nullptr, tab, 3ull, g.mat, g.kept});
     }
     // every op with a parent scaler scales the partition's way
     if (f.pscaler) mode = c->sh.rate_scalers ? SCALE_RATE : SCALE_SITE;
   }
   // what record `r` says about the ops ahead of position `pos` (pos may be -2, -1: the headers)
   auto look_ahead = [&](FusedRec & r, long pos) -> int {
-    r.chars = 0;
+    r.chars = r.chars2 = r.gather_off2 = 0;
     r.req_lmat = r.req_rmat = 0;
-    if (pos + 1 >= 0 && pos + 1 < (long)n) r.chars = chars_of[pos + 1];
+    if (pos + 1 >= 0 && pos + 1 < (long)n)
+    {
+      r.chars = chars_of[pos + 1];
+      r.chars2 = chars2_of[pos + 1];
+      r.gather_off2 = table2_of[pos + 1];
+    }
     if (pos + 2 < (long)n)
     {
       const FusedOp & f = plan[pos + 2];
@@ -1430,6 +1752,8 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   rs[n + 2] = rs[n + 1]; // (loaded by the last op, never used)
   rs[n + 2].flags &= ~PLLHIP_FUSED_RELOAD_NEXT;
   } // segments
+  // the kept tables T of the cherries this list defers: written straight into their places in the pool
+  if (keep_jobs) jobs.insert(jobs.end(), keep_jobs->begin(), keep_jobs->end());
 
   const size_t rec_bytes = recs.size() * sizeof(FusedRec);
   const size_t seg_bytes = (size_t)PLLHIP_FUSED_MAX_SEGS * sizeof(FusedSeg);
@@ -1481,6 +1805,7 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   c->fused_last_jobs = (unsigned int)jobs.size();
   c->fused_last_count = plans[0].size();
   c->fused_last_longest = longest;
+  c->fused_last_ndeferred = keep_jobs ? (unsigned int)keep_jobs->size() : 0u;
   c->fused_last_nsegs = nsegs;
   c->fused_last_nslots = nslots;
   c->fused_last_mode = mode;

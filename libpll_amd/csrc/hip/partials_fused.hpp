@@ -8,6 +8,24 @@
 
 constexpr int PLLHIP_FUSED_J = 2; // sub-steps (64 lanes x 16 B) per tile
 
+// A GATHERED operand: a factor the list kernel takes from a small table by tip characters instead of computing it
+// from a CLV -- a tip, or a deferred cherry (deferred.hip: a tip-tip parent that is not stored).
+enum { FUSED_G_NONE = 0, FUSED_G_TIP = 1, FUSED_G_PAIR = 2, FUSED_G_CHERRY_NEW = 3, FUSED_G_CHERRY_KEPT = 4 };
+struct FusedOperand
+{
+  int type;                         // FUSED_G_*: TIP the tip's factor; PAIR the finished tip-tip parent (kind 2);
+                                    // CHERRY_NEW a cherry deferred by this list, CHERRY_KEPT by an earlier call
+  const unsigned char * row1;       // tip rows the table is indexed by: (row1 << 4) | row2; row2 nullptr: code 0
+  const unsigned char * row2;
+  const double * mat;               // the reader's P-matrix on this edge
+  const double * c_lmat, * c_rmat;  // CHERRY_NEW: the cherry's own two matrices (its T is built from them on the spot)
+  const double * kept;              // CHERRY_KEPT: its kept table T
+};
+struct FusedExtra
+{
+  FusedOperand g[2];
+};
+
 // What the planner decides for one op (host side; the device gets FusedRec below).
 struct FusedOp
 {
@@ -23,11 +41,12 @@ struct FusedOp
   const unsigned int * rsc_hbm;
   int lslot, rslot, pslot;         // LDS slots of the two inner children / the parent; -1 = none
   int lsc_slot, rsc_slot;          // LDS slots the inherited counts are taken from; -1 = none
-  int kind;                        // 0 inner-inner, 1 tip-inner, 2 tip-tip
+  int kind;                        // 0 inner-inner, 1 gathered-inner (tip or deferred cherry), 2 tip-tip, 3 gathered-gathered
   int list_pos;                    // position of the op in the caller's list (the plan is re-ordered)
   int dma_flags;                   // bit 0 / 1: left_hbm / right_hbm is copied into lslot / rslot by LDS-DMA
                                    // at the top of the op before this one
   const double * pair_tab;         // tip operands: [256 code pairs][rate][state] table, else nullptr
+  FusedOperand g[2];               // gathered operands over deferred cherries (type 0: the op's kind says it all)
 };
 
 // The plan as the kernel reads it, through the scalar data cache: ONE 64-byte record per op (one
@@ -46,7 +65,9 @@ struct FusedOp
 struct FusedRec
 {
   unsigned int chars;                    // tip characters of op + 1, PLLHIP_FUSED_CH_* below
-  unsigned int pad[3];
+  unsigned int chars2;                   // ... of its SECOND gather (kind 3), same layout (no CH_LOAD, no batch)
+  unsigned int gather_off2;              // byte offset of the second gather's table (0: the table of zeros)
+  unsigned int pad;
   unsigned int req_lmat, req_rmat;       // byte offsets of its P-matrices in the matrix arena
   unsigned int gather_off;               // byte offset of the pair table of op + 1 (0: the table of zeros)
   unsigned int flags;                    // PLLHIP_FUSED_* below
@@ -58,7 +79,7 @@ struct FusedRec
   unsigned short pcnt_b, list_pos;       //   counts are read from / the parent's are kept at
 };
 static_assert(sizeof(FusedRec) == 64, "sixteen words per op");
-#define PLLHIP_FUSED_KIND_MASK 3u      /* 0 inner-inner, 1 tip-inner, 2 tip-tip */
+#define PLLHIP_FUSED_KIND_MASK 3u      /* 0 inner-inner, 1 gathered-inner, 2 tip-tip, 3 gathered-gathered */
 #define PLLHIP_FUSED_HAS_PSLOT 4u      /* the parent is kept in a slot */
 #define PLLHIP_FUSED_SCALING 8u        /* the op has a scale buffer */
 #define PLLHIP_FUSED_LCNT 16u          /* counts are inherited from the left / right operand's slot */
@@ -87,16 +108,25 @@ struct FusedSrc
 };
 
 // one pair table to build (k_dna_pair_tables)
+// kind 0: [c1][0] = masksum4(lmat row, c1), a tip's factor; 1: [c1][c2] = masksum4(lmat) * masksum4(rmat), a tip-tip
+// parent (tab in d_pairtab: a kept tip-tip op; in the pool: a deferred cherry's kept table T); 2: the READER's factor
+// over a cherry, F[c1][c2][rate][s] = dot4(pmat[rate][s], T[c1][c2][rate][.]), T formed on the spot from lmat / rmat;
+// 3: the same from the kept table `kept`
 struct FusedPairJob
 {
   const double * lmat;
   const double * rmat;
   double * tab;
-  unsigned long long tip_tip;
+  unsigned long long kind;
+  const double * pmat;
+  const double * kept;
 };
 
 unsigned int pllhip_fused_char_batches(const unsigned int * tips, unsigned int count, unsigned int lpr,
                                        unsigned int * chars_out, unsigned int * batch_out);
+// the same for ops with up to four rows (bits 2 / 3 of tips[pos]: the rows of the second gather, into chars2_out)
+unsigned int pllhip_fused_char_batches4(const unsigned int * tips, unsigned int count, unsigned int lpr,
+                                        unsigned int * chars_out, unsigned int * chars2_out, unsigned int * batch_out);
 
 // Round 5: SEGMENTS.  Ops that share no buffer any of them writes are independent lists -- the two sides of the root
 // edge of a full traversal, above all -- and a tile of sites may be taken through each of them by a different wave at
@@ -134,7 +164,8 @@ struct FusedGeom
   size_t nsc;             // scale buffers
   unsigned int tips;
   bool pattern_tip;       // tips are character rows, not CLVs
-  bool is_tip(unsigned int clv_index) const { return pattern_tip && clv_index < tips; }
+  const unsigned char * as_tip = nullptr; // per CLV index: a deferred cherry -- an operand without a slot, like a tip
+  bool is_tip(unsigned int clv_index) const { return (pattern_tip && clv_index < tips) || (as_tip && as_tip[clv_index]); }
 };
 
 // Order the list, assign slots.  args/kinds are resolve_op's results per op.  Returns 0 and
@@ -143,7 +174,23 @@ struct FusedGeom
 // launches per level), < 0 on error.
 int pllhip_fused_plan(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args,
                       const int * kinds, unsigned int count, unsigned int nslots,
-                      std::vector<FusedOp> & plan, unsigned int * reloads);
+                      std::vector<FusedOp> & plan, unsigned int * reloads, const FusedExtra * extra = nullptr);
+
+// Which tip-tip ops of a list are DEFERRED (not run) and what must be materialised before the list.
+// Pure host logic on indices (tests/test_host_deferred_plan.py through pllhip_fused_plan_dry_deferred).
+//   old_deferred[i] / old_scaler[i]: CLV i is deferred by an earlier call, with that scale buffer (-1 none)
+//   pinned[i]: never deferred.  All three may be nullptr.
+// Out: defer[k] = 1: op k is deferred; as_tip[i] = 1: CLV i is a gathered operand of this list (deferred now or
+// before); materialise: CLVs deferred earlier that the list touches in a way a table cannot serve; dropped: CLVs
+// deferred earlier that the list overwrites before reading (their deferral ends without the bytes).
+struct FusedDeferral
+{
+  std::vector<unsigned char> defer, as_tip;
+  std::vector<unsigned int> materialise, dropped;
+};
+void pllhip_fused_deferral(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
+                           const unsigned char * old_deferred, const int * old_scaler, const unsigned char * pinned,
+                           FusedDeferral & out);
 unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int workgroups_per_cu);
 // The list as up to `max_segments` independent sub-lists of at least two ops each: seg_of[i] = segment of op i
 // (segment 0 the longest; ops keep their relative order within a segment).  Components -- ops connected through a
@@ -152,7 +199,8 @@ unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int workgroups_pe
 unsigned int pllhip_fused_segments(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
                                    unsigned int max_segments, std::vector<unsigned int> & seg_of);
 // one plan per segment (pllhip_fused_plan of its sub-list)
-int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots);
+int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
+                        const std::vector<FusedPairJob> * keep_jobs = nullptr);
 int pllhip_relaunch_fused(pllhip_ctx * c); // the same op list as in the previous whole-list call of this context
 
 #endif

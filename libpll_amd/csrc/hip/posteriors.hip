@@ -445,6 +445,7 @@ extern "C" int pllhip_site_posteriors(pllhip_ctx_t * c, const pllhip_posterior_e
     return -3;
   }
   PLLHIP_CERT_FIRST(c); // (the CLVs and counts read here are the reference's, or the list runs again first)
+  PLLHIP_DEFERRED_FLUSH(c); // (deferred cherries get their bytes before anything but a list kernel touches them)
 
   // ---- chunk size: the outputs of one chunk within `budget` bytes (one edge at least)
   const size_t sites = c->sh.sites;

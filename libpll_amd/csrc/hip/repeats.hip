@@ -370,6 +370,7 @@ extern "C" int pllhip_identify_repeats(pllhip_ctx_t * c, unsigned int parent, un
     return 0;
   }
   HIP_TRY(hipSetDevice(c->sh.device));
+  PLLHIP_DEFERRED_FLUSH(c);
   *classes_out = 0;
   const unsigned int nodes = (unsigned int)c->clv.size();
   if (parent >= nodes || child1 >= nodes || child2 >= nodes || !c->clv[parent])

@@ -441,6 +441,10 @@ pll_partition_t * pll_partition_create(unsigned int tips, unsigned int clv_buffe
     pll_partition_destroy(p);
     return NULL;
   }
+  /* deferred cherries (pllhip.h): not where every CLV is read back after each call (host mirrors), where the whole-list
+   * kernel never runs (site repeats), or where there are no tip-tip ops to defer (tips as CLVs) */
+  if (PLL_AMD_MIRRORS(p) || (attributes & PLL_ATTRIB_SITE_REPEATS) || !(attributes & PLL_ATTRIB_PATTERN_TIP))
+    (void)pllhip_set_deferral(q->ctx, 0);
   if ((attributes & PLL_ATTRIB_SITE_REPEATS) && !pll_amd_repeats_alloc(q))
   {
     pll_partition_destroy(p);
@@ -845,6 +849,25 @@ int pll_amd_scaling_certificate(pll_partition_t * p, unsigned long long * stats4
 {
   int rc = pllhip_cert_stats(pll_amd_priv(p)->ctx, stats4);
   if (rc) return pll_amd_fail_hip(rc, "scaling certificate");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_deferred_stats(pll_partition_t * p, unsigned long long * stats4)
+{
+  int rc = pllhip_deferred_stats(pll_amd_priv(p)->ctx, stats4);
+  if (rc) return pll_amd_fail_hip(rc, "deferred stats");
+  return PLL_SUCCESS;
+}
+
+void * pll_amd_dev_clv(pll_partition_t * p, unsigned int clv_index)
+{
+  return pllhip_dev_clv(pll_amd_priv(p)->ctx, clv_index);
+}
+
+int pll_amd_set_deferral(pll_partition_t * p, int on)
+{
+  int rc = pllhip_set_deferral(pll_amd_priv(p)->ctx, on);
+  if (rc) return pll_amd_fail_hip(rc, "set deferral");
   return PLL_SUCCESS;
 }
 

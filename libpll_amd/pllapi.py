@@ -275,6 +275,11 @@ class PllLibrary:
             lib.pll_amd_profile_read.argtypes = [_PP, _up, _dp]
             if hasattr(lib, "pll_amd_scaling_certificate"):
                 lib.pll_amd_scaling_certificate.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
+            if hasattr(lib, "pll_amd_deferred_stats"):
+                lib.pll_amd_deferred_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
+                lib.pll_amd_set_deferral.argtypes = [_PP, C.c_int]
+                lib.pll_amd_dev_clv.argtypes = [_PP, C.c_uint]
+                lib.pll_amd_dev_clv.restype = C.c_void_p
             if hasattr(lib, "pll_amd_write_ceiling"):   # (older builds under PLL_AMD_LIB: tools/list_time.py)
                 lib.pll_amd_write_ceiling.argtypes = [_PP, C.c_void_p, C.c_uint, C.c_uint, C.POINTER(C.c_float),
                                                       C.POINTER(C.c_double)]
@@ -846,6 +851,20 @@ class Partition:
         buf = (C.c_ulonglong * 4)()
         self._check(self.lib.pll_amd_scaling_certificate(self.ptr, buf), "pll_amd_scaling_certificate")
         return dict(zip(("lists", "raised", "rerun", "uncertified"), (int(v) for v in buf)))
+
+    def set_deferral(self, on):
+        """False: every tip-tip op of a 4-state whole-list launch is run and stored (the eager path)."""
+        self._check(self.lib.pll_amd_set_deferral(self.ptr, 1 if on else 0), "pll_amd_set_deferral")
+
+    def dev_clv(self, idx):
+        """device address of a CLV (pll_amd_dev_clv); the CLV is stored if deferred and pinned eager from then on"""
+        return self.lib.pll_amd_dev_clv(self.ptr, idx)
+
+    def deferred_stats(self):
+        """{deferred_now, ops_deferred, launches, materialised} of the 4-state deferred cherries (pll_amd.h)."""
+        buf = (C.c_ulonglong * 4)()
+        self._check(self.lib.pll_amd_deferred_stats(self.ptr, buf), "pll_amd_deferred_stats")
+        return dict(zip(("deferred_now", "ops_deferred", "launches", "materialised"), (int(v) for v in buf)))
 
     def write_ceiling(self, ops, reps):
         """(ms per pass, bytes per pass) of nothing but the stores of `ops` -- OVERWRITES their CLVs (pll_amd.h)."""
