@@ -950,6 +950,54 @@ PLL_EXPORT int pll_amd_nni_optimize(pll_partition_t * partition,
                                     unsigned int * evals,    /* out [edge][3], may be NULL */
                                     int * status);           /* out [edge][3], may be NULL */
 
+/* ---- batched tree scoring: op lists to log-likelihoods, no CLV written (tree_score.c, tree_score.hip) ----
+ * A candidate is an op list, the branch lengths it uses and the edge to evaluate at: a candidate topology, a candidate
+ * vector of branch lengths (a line search over all lengths at once), or the changed path to the root after a local
+ * move. */
+typedef struct pll_amd_tree_candidate
+{
+  const pll_operation_t * operations;      /* may be NULL when op_count == 0 */
+  unsigned int            op_count;
+  const unsigned int *    matrix_indices;  /* the matrices this candidate gives lengths of its own */
+  const double *          branch_lengths;
+  unsigned int            matrix_count;    /* may be 0 */
+  unsigned int            parent_clv_index;    /* the edge, as pll_compute_edge_loglikelihood takes it */
+  int                     parent_scaler_index;
+  unsigned int            child_clv_index;
+  int                     child_scaler_index;
+  unsigned int            matrix_index;
+} pll_amd_tree_candidate_t;
+
+/* lnl[c] = what this sequence returns on the same partition -- pll_update_prob_matrices(params_indices, the candidate's
+ * matrix_indices, branch_lengths, matrix_count); pll_update_partials(its operations, op_count);
+ * pll_compute_edge_loglikelihood(parent, parent scaler, child, child scaler, matrix_index, freqs_indices =
+ * params_indices) -- and the call itself changes no CLV, scale buffer, P-matrix, sumtable slot or host mirror.  A
+ * matrix index the candidate does not list means the partition's current matrix; a CLV or scale buffer its ops do not
+ * write means the partition's current content (tips, tip CLVs, results of earlier calls).  Candidates are independent
+ * of each other.  Per-site scalers, per-rate scalers or none, +I, a rate matrix per category, category weights,
+ * pattern tips or tip CLVs and pattern weights behave as in the three calls.
+ * What lives where: for 4 states with 1 or 4 rate categories and no per-rate scale buffers a candidate's intermediate
+ * CLVs live on the chip only (ops the edge does not depend on are not run at all); for every other shape, and for
+ * lists whose plan needs more than 16 live values per site, they are scratch of the partition on its device, as are
+ * the candidates' own P-matrices and partial sums, kept until the partition is destroyed.  Large batches are worked
+ * in chunks of whole candidates of at most about PLL_AMD_TREE_SCRATCH_MB (environment, read at call time, default
+ * 2048) of scratch, one candidate at least; a candidate's value is the same bits whatever else is in the batch, in
+ * whatever order, however the call chunks it, and on a repeated call.  The call is synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, lnl untouched): count >= 1 and no NULL array where a
+ * count is non-zero; every CLV, scaler, matrix and params index in range; op parents are inner CLVs; lengths finite and
+ * non-negative; with PLL_ATTRIB_PATTERN_TIP the edge's parent is not a tip; within one candidate no parent CLV index
+ * and no parent scaler index (other than PLL_SCALE_BUFFER_NONE) is written by two ops, and no op reads a CLV that the
+ * same or a later op of the candidate writes.
+ * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
+ * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
+ * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: per-candidate model parameters or category
+ * rates, per-site outputs, applying a candidate to the partition, and lists in which an op reads a CLV that a later op
+ * of the same candidate overwrites (they have a meaning in the sequence and no use here).  INTEGRATION.md section 4f. */
+PLL_EXPORT int pll_amd_tree_loglikelihood(pll_partition_t * partition,
+                                          const pll_amd_tree_candidate_t * candidates, unsigned int count,
+                                          const unsigned int * params_indices,
+                                          double * lnl);            /* out [count] */
+
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets
  * threads create partitions concurrently -- WITH a process-wide default: a thread that has not set a device uses what

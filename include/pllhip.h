@@ -428,6 +428,53 @@ PLLHIP_EXPORT int pllhip_nni_optimize(pllhip_ctx_t * ctx, const pllhip_nni_edge_
                                       double tolerance, unsigned int max_iters, int route, size_t scratch_bytes,
                                       double * h_lengths, double * h_lnl, unsigned int * h_evals, int * h_status);
 
+/* ---- batched tree scoring (tree_score.hip; host side host/tree_score.c) ----
+ * A candidate: an op list, the matrices it gives lengths of its own, the edge to evaluate at.  lnl[c] = what
+ * pllhip_update_pmatrices (the candidate's matrix indices and lengths), pllhip_update_partials (its ops) and
+ * pllhip_edge_loglikelihood (its edge, freqs indices = params indices) would return on this context -- and nothing of
+ * the context changes: every CLV, count and matrix a candidate makes lives in scratch or on the chip.  A matrix the
+ * candidate does not list, a CLV or scale buffer its ops do not write: the context's.  Same layout as
+ * pll_amd_tree_candidate_t.  route: -1 the library's choice (k_tree_score for 4 states with 1 or 4 rate categories and
+ * no per-rate scale buffers where the candidate's plan fits max_slots LDS slots per wave, the general route
+ * otherwise), 0 the general route, 1 as -1.  max_slots: <= 0 the default (16), at most 17.  Scratch (kept by the
+ * context) is at most about scratch_bytes per chunk of whole candidates, at least one candidate's worth.  Returns -1
+ * for a bad argument (nothing launched, lnl untouched), -2 if a chunk's scratch cannot be had, -3 for a context this
+ * call does not take (asc-bias, site repeats, sharded, RCCL). */
+typedef struct pllhip_tree_candidate
+{
+  const pllhip_op_t * operations;
+  unsigned int op_count;
+  const unsigned int * matrix_indices;
+  const double * branch_lengths;
+  unsigned int matrix_count;
+  unsigned int parent_clv_index;
+  int parent_scaler_index;
+  unsigned int child_clv_index;
+  int child_scaler_index;
+  unsigned int matrix_index;
+} pllhip_tree_candidate_t;
+PLLHIP_EXPORT int pllhip_tree_loglikelihood(pllhip_ctx_t * ctx, const pllhip_tree_candidate_t * h_candidates,
+                                            unsigned int count, const unsigned int * h_params_indices, int route,
+                                            int max_slots, size_t scratch_bytes, double * h_lnl);
+
+/* The planner of k_tree_score on its own -- host logic, no device needed.  The ops the edge (parent_clv, child_clv
+ * with their scaler indices) does not depend on are dropped; the rest are ordered depth-first from the edge, the
+ * operand that needs more live values first, and a parent takes the slot of one of its operands.  Tips (pattern_tip)
+ * and CLVs the list does not write need no slot.  need(op) = max(1, a == b ? a + 1 : a) for operand needs a >= b (0 for
+ * a tip or a CLV of an earlier call); the edge needs max(x, y + 1) for side needs x >= y > 0, max(x, 1) for y == 0.
+ * Out (any may be NULL): *nkept_out kept ops as positions in the list, in walk order (order_out); three numbers per
+ * kept op (slots_out): the slots of child 1, child 2 and the parent, -1: not a slot; *nslots_out: what the edge needs.
+ * Returns 0: the kernel takes the list; 1: the general route does -- it needs more than max_slots, an operand written
+ * by the list is read with a scaler index other than its writer's or none, or a value is read twice (order_out: the
+ * kept ops in list order, slots_out -1); -1: an invalid list -- an index out of range, a parent that is a tip, a
+ * parent CLV or scale buffer written twice, an op that reads a CLV the same or a later op writes, a pattern tip as the
+ * edge's parent. */
+PLLHIP_EXPORT int pllhip_tree_score_plan_dry(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                             int pattern_tip, const pllhip_op_t * ops, unsigned int count,
+                                             unsigned int parent_clv, int parent_scaler, unsigned int child_clv,
+                                             int child_scaler, unsigned int max_slots, unsigned int * order_out,
+                                             int * slots_out, unsigned int * nkept_out, unsigned int * nslots_out);
+
 /* ---- multi-GPU: one process per GPU, RCCL sum of the scalar results ---- */
 PLLHIP_EXPORT int pllhip_comm_unique_id(void * id128);
 /* which RCCL the process uses: the file the collective symbols were bound to -- the copy already

@@ -591,6 +591,7 @@ extern "C" void pllhip_ctx_destroy(pllhip_ctx_t * c)
   if (c->ins_scratch) (void)hipFree(c->ins_scratch);
   if (c->bo_scratch) (void)hipFree(c->bo_scratch);
   if (c->nni_scratch) (void)hipFree(c->nni_scratch);
+  if (c->tree_scratch) (void)hipFree(c->tree_scratch);
   if (c->post_scratch) (void)hipFree(c->post_scratch);
   pllhip_aa_fused_free(c);
   for (int b = 0; b < 2; ++b)

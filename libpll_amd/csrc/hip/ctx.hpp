@@ -245,6 +245,10 @@ struct pllhip_ctx
   // candidates' CLVs, scale buffers and sumtables of one chunk, kept the same way
   void * nni_scratch = nullptr;
   size_t nni_scratch_bytes = 0;
+  // tree-scoring calls (tree_score.hip): the candidates' P-matrices, records, partial sums and -- on the general
+  // route -- their CLVs and scale buffers of one chunk, kept the same way
+  void * tree_scratch = nullptr;
+  size_t tree_scratch_bytes = 0;
 
   // optional per-launch timing (pllhip_profile_*): one event pair per launch
   bool profiling = false;

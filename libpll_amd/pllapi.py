@@ -296,6 +296,11 @@ class PllLibrary:
                 lib.pll_amd_nni_loglikelihood.argtypes = [_PP, C.c_void_p, C.c_uint, _up, _dp]
                 lib.pll_amd_nni_optimize.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_double, C.c_double,
                                                      C.c_double, C.c_uint, _dp, _dp, _up, C.c_void_p]
+            if hasattr(lib, "pll_amd_tree_loglikelihood"):
+                lib.pll_amd_tree_loglikelihood.argtypes = [_PP, C.c_void_p, C.c_uint, _up, _dp]
+                lib.pllhip_tree_score_plan_dry.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_void_p, C.c_uint,
+                                                           C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, _up,
+                                                           C.POINTER(C.c_int), _up, _up]
             if hasattr(lib, "pll_amd_site_posteriors"):
                 lib.pll_amd_site_posteriors.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p]
@@ -538,6 +543,56 @@ def nni_edges(edges):
     return e
 
 
+class TreeCandidate(C.Structure):
+    """pll_amd_tree_candidate_t (include/pll_amd.h)"""
+    _fields_ = [("operations", C.c_void_p), ("op_count", C.c_uint), ("matrix_indices", C.c_void_p),
+                ("branch_lengths", C.c_void_p), ("matrix_count", C.c_uint), ("parent_clv_index", C.c_uint),
+                ("parent_scaler_index", C.c_int), ("child_clv_index", C.c_uint), ("child_scaler_index", C.c_int),
+                ("matrix_index", C.c_uint)]
+
+
+def tree_candidates(candidates):
+    """(a TreeCandidate array, the numpy arrays it points into) from rows of (ops, matrix_indices, lengths, parent,
+    parent_scaler, child, child_scaler, matrix); ops: an OPS_DTYPE array, rows of eight numbers, or None"""
+    arr = (TreeCandidate * max(len(candidates), 1))()
+    keep = []
+    for i, (ops, mi, bl, pc, ps, cc, cs, m) in enumerate(candidates):
+        if ops is None:
+            ops = []
+        if not (isinstance(ops, np.ndarray) and ops.dtype == OPS_DTYPE):
+            rows = ops
+            ops = np.zeros(len(rows), dtype=OPS_DTYPE)
+            for k, row in enumerate(rows):
+                ops[k] = tuple(row)
+        ops = np.ascontiguousarray(ops)
+        mi = np.ascontiguousarray(mi if mi is not None else [], dtype=np.uint32)
+        bl = np.ascontiguousarray(bl if bl is not None else [], dtype=np.float64)
+        assert len(mi) == len(bl)
+        keep += [ops, mi, bl]
+        arr[i] = TreeCandidate(ops.ctypes.data if len(ops) else None, len(ops), mi.ctypes.data if len(mi) else None,
+                               bl.ctypes.data if len(bl) else None, len(mi), pc, ps, cc, cs, m)
+    return arr, keep
+
+
+def tree_score_plan(lib, tips, clv_buffers, scale_buffers, pattern_tip, ops, parent, parent_scaler, child,
+                    child_scaler, max_slots=16):
+    """pllhip_tree_score_plan_dry (host logic, no device): (rc, order, slots [kept][3], nslots) -- the kept ops in walk
+    order as positions in `ops`, the slots of child 1, child 2 and the parent (-1: not a slot), the slots the edge
+    needs; rc 0: the kernel takes the list, 1: the general route, -1: an invalid list (order, slots, nslots None)"""
+    ops = np.ascontiguousarray(ops, dtype=OPS_DTYPE)
+    n = len(ops)
+    order = np.zeros(max(n, 1), dtype=np.uint32)
+    slots = np.zeros((max(n, 1), 3), dtype=np.int32)
+    nkept, nslots = C.c_uint(0), C.c_uint(0)
+    rc = lib.pllhip_tree_score_plan_dry(tips, clv_buffers, scale_buffers, 1 if pattern_tip else 0,
+                                        ops.ctypes.data if n else None, n, parent, parent_scaler, child, child_scaler,
+                                        max_slots, _u(order), slots.ctypes.data_as(C.POINTER(C.c_int)),
+                                        C.byref(nkept), C.byref(nslots))
+    if rc < 0:
+        return rc, None, None, None
+    return rc, order[:nkept.value].copy(), slots[:nkept.value].copy(), int(nslots.value)
+
+
 class Partition:
     """A pll_partition_t* plus the calls that take it as first argument."""
 
@@ -742,6 +797,21 @@ class Partition:
                                            status.ctypes.data)
         self._check(ok, "pll_amd_nni_optimize")
         return t, lnl, evals, status
+
+    def tree_loglikelihood(self, candidates, params_indices):
+        """pll_amd_tree_loglikelihood: one log-likelihood per candidate.  candidates: rows of (ops, matrix_indices,
+        lengths, parent, parent_scaler, child, child_scaler, matrix) -- ops an OPS_DTYPE array or rows of eight
+        numbers (None: no ops), matrix_indices / lengths the matrices the candidate gives lengths of its own."""
+        if not hasattr(self.lib, "pll_amd_tree_loglikelihood"):
+            raise PllError("this library has no pll_amd_tree_loglikelihood")
+        arr, keep = tree_candidates(candidates)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        out = np.zeros(len(candidates))
+        ok = self.lib.pll_amd_tree_loglikelihood(self.ptr, C.addressof(arr) if len(candidates) else None,
+                                                 len(candidates), _u(pi), _d(out))
+        del keep
+        self._check(ok, "pll_amd_tree_loglikelihood")
+        return out
 
     def site_posteriors(self, edges, freqs_indices, want=("state_probs", "best", "rate_probs", "site_rates")):
         """pll_amd_site_posteriors: a dict of numpy arrays, first axis the edge -- state_probs [edges][sites][states],
