@@ -1038,6 +1038,10 @@ PLL_EXPORT void pll_amd_set_mirror_mode(int on);
 
 PLL_EXPORT int pll_amd_sync_clv(pll_partition_t * partition, unsigned int clv_index);
 PLL_EXPORT int pll_amd_sync_scaler(pll_partition_t * partition, unsigned int scaler_index);
+/* The other direction: the host mirror partition->clv[clv_index] / ->scale_buffer[scaler_index] (allocated by the
+ * sync call, then changed by the client) replaces the device's copy.  Not for partitions with site repeats. */
+PLL_EXPORT int pll_amd_push_clv(pll_partition_t * partition, unsigned int clv_index);
+PLL_EXPORT int pll_amd_push_scaler(pll_partition_t * partition, unsigned int scaler_index);
 PLL_EXPORT int pll_amd_sync_pmatrix(pll_partition_t * partition, unsigned int matrix_index);
 PLL_EXPORT int pll_amd_sync_sumtable(pll_partition_t * partition, double * sumtable);
 /* Host copy of node `index`'s parsimony vector in parsimony->packedvector[index] (allocated on first use, freed by
@@ -1123,6 +1127,15 @@ PLL_EXPORT int pll_amd_scaling_certificate(pll_partition_t * partition, unsigned
 PLL_EXPORT int pll_amd_deferred_stats(pll_partition_t * partition, unsigned long long * stats4);
 /* 0: every op of this partition is run and stored from now on (deferred CLVs are stored first); 1: defer again. */
 PLL_EXPORT int pll_amd_set_deferral(pll_partition_t * partition, int on);
+/* Edge log-likelihood terms from the 4-state whole-list launch (pllhip.h: pllhip_set_edge_fold): after
+ * pll_compute_edge_loglikelihood at an inner-inner edge, the next pll_update_partials that writes one of the edge's two
+ * CLVs also forms the edge's per-site terms, and the same evaluation then only sums them -- bit for bit the value it
+ * returns without.  0: never; 1: the default.  Partitions that mirror their CLVs on the host never fold.
+ * stats[0] = op lists launched with the epilogue, [1] = evaluations served from terms, [2] = terms dropped unused,
+ * [3] = inner-inner edge evaluations of a 4-state partition that ran the lnL kernel (root and tip-inner ones are not
+ * counted). */
+PLL_EXPORT int pll_amd_set_edge_fold(pll_partition_t * partition, int on);
+PLL_EXPORT int pll_amd_edge_fold_stats(pll_partition_t * partition, unsigned long long * stats4);
 /* The device address of a CLV (pllhip.h: pllhip_dev_clv; NULL for a partition over several devices or a bad index).  A
  * deferred CLV is stored first and the index is never deferred again: the caller holds the address. */
 PLL_EXPORT void * pll_amd_dev_clv(pll_partition_t * partition, unsigned int clv_index);

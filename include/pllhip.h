@@ -239,6 +239,30 @@ PLLHIP_EXPORT int pllhip_cert_stats(pllhip_ctx_t * ctx, unsigned long long * out
 PLLHIP_EXPORT int pllhip_set_deferral(pllhip_ctx_t * ctx, int on);
 PLLHIP_EXPORT int pllhip_deferred_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
 
+/* Edge log-likelihood terms from the 4-state whole-list launch.  pllhip_edge_loglikelihood remembers an inner-inner
+ * request; the next pllhip_update_partials that runs as ONE whole-list launch and writes one of the edge's two CLVs
+ * also forms that edge's per-site terms from the CLVs it still holds on chip, and an evaluation of exactly that
+ * request then only sums them -- same grid, same order, the same bits as without.  The terms are dropped by every call
+ * that changes device state; dropped unused, they end the speculation until the next evaluation.  4 states, 1 / 2 / 4
+ * rate categories, per-site or no scale buffers, no site repeats, ascertainment correction or invariant sites; a
+ * sharded context never folds.  pllhip_set_edge_fold(ctx, 0): never; 1: the default.
+ * out4: lists launched with the epilogue, evaluations served from terms, terms dropped unused, inner-inner edge
+ * evaluations of a 4-state partition that ran the lnL kernel (root and tip-inner evaluations are not counted). */
+PLLHIP_EXPORT int pllhip_set_edge_fold(pllhip_ctx_t * ctx, int on);
+PLLHIP_EXPORT int pllhip_edge_fold_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+/* The planner with that evaluation as a pseudo-op behind the last op, without a device (tests): as
+ * pllhip_fused_plan_dry_deferred, for a partition with `rate_cats` (1, 2, 4) categories; edge4 = {parent_clv,
+ * parent_scaler, child_clv, child_scaler}.  edge_out[8]: folded (0: the outputs describe the unfolded plan), the
+ * pseudo-op's parent slot, child slot, parent count slot, child count slot, reload flags (bit 0 parent, bit 1 child),
+ * workgroups per CU of the unfolded plan, of the folded plan (0: not folded). */
+PLLHIP_EXPORT int pllhip_fused_plan_dry_edge(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                             int pattern_tip, unsigned int rate_cats, const pllhip_op_t * ops,
+                                             unsigned int count, const unsigned char * old_deferred,
+                                             const int * old_scaler, const unsigned char * pinned, const int * edge4,
+                                             unsigned int * nkept, unsigned int * order_out, int * slots_out,
+                                             int * operands_out, unsigned char * deferred_out,
+                                             unsigned int * reloads_out, int * edge_out);
+
 /* Host logic of the same planner, no device: where the 4-state whole-list kernel keeps each op's tip characters.
  * tips[i]: bit 0 / 1 = op i (in the PLANNED order) has a left / right tip row.  chars_out[i]: bits 0-7 / 8-15 the
  * first lane of the left / right row in the wave's character registers, bit 16 / 17 = has a left / right tip;

@@ -252,6 +252,7 @@ int pllhip_asc_derivatives(pllhip_ctx * c, const double * sumtable, const double
 
 extern "C" int pllhip_set_asc(pllhip_ctx_t * c, int asc_type, unsigned int pattern_weight_sum)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!c->shards.empty())
   {
     // the per-state sites live on the last shard; the correction is added to that shard's sum

@@ -378,6 +378,7 @@ extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_bra
                                               double * h_lengths, double * h_lnl, unsigned int * h_evals,
                                               int * h_status)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!B || !params || !h_lengths || !count)
   {
     pllhip_set_error("pllhip_optimize_branch_lengths: empty batch or NULL array");

@@ -118,6 +118,7 @@ int pllhip_probe_clv_streams(pllhip_ctx * c, char * base, size_t n, size_t strid
 extern "C" int pllhip_write_ceiling(pllhip_ctx_t * c, const pllhip_op_t * ops, unsigned int count, unsigned int reps,
                                     float * ms_per_pass, double * bytes_per_pass)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!c->shards.empty()) { pllhip_set_error("pllhip_write_ceiling: not for a sharded context"); return -1; }
   if (!count || !reps) { pllhip_set_error("pllhip_write_ceiling: nothing to do"); return -1; }
   HIP_TRY(hipSetDevice(c->sh.device));

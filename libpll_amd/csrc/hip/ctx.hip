@@ -156,6 +156,7 @@ static int fill_bandwidth(void * p, size_t bytes, hipStream_t s, hipEvent_t e0, 
 // (tool: the CLV arena zeroed once more, timed -- OVERWRITES every CLV; tools/placement_probe.py)
 extern "C" int pllhip_arena_fill_bandwidth(pllhip_ctx_t * c, double * gbs)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!c->shards.empty()) { pllhip_set_error("pllhip_arena_fill_bandwidth: not for a sharded context"); return -1; }
   HIP_TRY(hipSetDevice(c->sh.device));
   PLLHIP_CERT_FIRST(c);
@@ -579,6 +580,7 @@ extern "C" void pllhip_ctx_destroy(pllhip_ctx_t * c)
   if (c->d_plan) (void)hipFree(c->d_plan);
   if (c->d_sink) (void)hipFree(c->d_sink);
   if (c->fused_zero_row) (void)hipFree(c->fused_zero_row);
+  if (c->d_edge_terms) (void)hipFree(c->d_edge_terms);
   if (c->d_tile_counter) (void)hipFree(c->d_tile_counter);
   if (c->d_pairtab) (void)hipFree(c->d_pairtab);
   if (c->defer_pool) (void)hipFree(c->defer_pool);
@@ -643,6 +645,7 @@ static int d2h(pllhip_ctx * c, void * dst, const void * src, size_t bytes)
 
 extern "C" int pllhip_put_tipchars(pllhip_ctx_t * c, unsigned int tip, const unsigned char * h)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_tipchars(s, tip, h + lo));
   PLLHIP_CERT_FIRST(c);
   PLLHIP_DEFERRED_FLUSH(c); // (a deferred cherry is indexed by its tips' rows: it gets its bytes before a row changes)
@@ -656,6 +659,7 @@ extern "C" int pllhip_put_tipchars(pllhip_ctx_t * c, unsigned int tip, const uns
 
 extern "C" int pllhip_put_tipmap(pllhip_ctx_t * c, const unsigned int * h, unsigned int maxstates)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!c->shards.empty()) c->maxstates = maxstates;
   PLLHIP_ALL_SHARDS(c, pllhip_put_tipmap(s, h, maxstates));
   PLLHIP_CERT_FIRST(c);
@@ -667,6 +671,7 @@ extern "C" int pllhip_put_tipmap(pllhip_ctx_t * c, const unsigned int * h, unsig
 
 extern "C" int pllhip_put_clv(pllhip_ctx_t * c, unsigned int idx, const double * h)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_clv(s, idx, h + lo * c->span));
   PLLHIP_CERT_FIRST(c);
   if (idx >= c->clv.size() || !c->clv[idx])
@@ -696,6 +701,7 @@ __global__ void k_replicate_tip_clv(double * __restrict__ clv, const double * __
 extern "C" int pllhip_put_tip_clv_persite(pllhip_ctx_t * c, unsigned int idx,
                                           const double * h, unsigned int stride)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_tip_clv_persite(s, idx, h + lo * stride, stride));
   PLLHIP_CERT_FIRST(c);
   if (idx >= c->clv.size() || !c->clv[idx])
@@ -734,12 +740,14 @@ extern "C" int pllhip_put_tip_clv_persite(pllhip_ctx_t * c, unsigned int idx,
 
 extern "C" int pllhip_put_pattern_weights(pllhip_ctx_t * c, const unsigned int * h)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_pattern_weights(s, h + lo));
   return h2d(c, c->pattern_weights, h, (size_t)c->sh.sites * sizeof(unsigned int));
 }
 
 extern "C" int pllhip_put_invariant(pllhip_ctx_t * c, const int * h)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_invariant(s, h ? h + lo : nullptr));
   HIP_TRY(hipSetDevice(c->sh.device));
   if (!h)
@@ -759,6 +767,7 @@ extern "C" int pllhip_put_invariant(pllhip_ctx_t * c, const int * h)
 
 extern "C" int pllhip_put_rates(pllhip_ctx_t * c, const double * r, const double * w)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_rates(s, r, w));
   int rc = 0;
   if (r) rc = h2d(c, c->rates, r, c->sh.rate_cats * sizeof(double));
@@ -770,6 +779,7 @@ extern "C" int pllhip_put_model(pllhip_ctx_t * c, unsigned int pi, const double 
                                 const double * evecs, const double * inv_evecs,
                                 const double * freqs, double prop_invar)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_model(s, pi, evals, evecs, inv_evecs, freqs, prop_invar));
   if (pi >= c->sh.rate_matrices) { pllhip_set_error("pllhip_put_model: index %u", pi); return -1; }
   const size_t S = c->sh.states;
@@ -788,6 +798,7 @@ extern "C" int pllhip_put_model(pllhip_ctx_t * c, unsigned int pi, const double 
 
 extern "C" int pllhip_put_pmatrix(pllhip_ctx_t * c, unsigned int idx, const double * h)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_pmatrix(s, idx, h));
   PLLHIP_CERT_FIRST(c);
   if (idx >= c->sh.prob_matrices) { pllhip_set_error("pllhip_put_pmatrix: index %u", idx); return -1; }
@@ -796,6 +807,7 @@ extern "C" int pllhip_put_pmatrix(pllhip_ctx_t * c, unsigned int idx, const doub
 
 extern "C" int pllhip_put_scaler(pllhip_ctx_t * c, unsigned int idx, const unsigned int * h)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_scaler(s, idx, h + lo * (c->sh.rate_scalers ? c->sh.rate_cats : 1)));
   PLLHIP_CERT_FIRST(c);
   if (idx >= c->sh.scale_buffers) { pllhip_set_error("pllhip_put_scaler: index %u", idx); return -1; }
@@ -825,6 +837,7 @@ extern "C" int pllhip_partial_tt_from_lookup(pllhip_ctx_t * c, unsigned int pare
                                              unsigned int tip1, unsigned int tip2, const double * h_lookup,
                                              size_t rows, unsigned int log2_maxstates)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!c->shards.empty()) { pllhip_set_error("pllhip_partial_tt_from_lookup: not for a sharded context"); return -1; }
   PLLHIP_CERT_FIRST(c);
   if (parent_clv >= c->clv.size() || !c->clv[parent_clv] || !c->sh.pattern_tip || tip1 >= c->sh.tips ||
@@ -947,6 +960,7 @@ extern "C" void pllhip_host_free(void * p)
 
 extern "C" int pllhip_mirror_batch(pllhip_ctx_t * c, const pllhip_mirror_job_t * jobs, unsigned int count)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!c->shards.empty()) { pllhip_set_error("pllhip_mirror_batch: not for a sharded context"); return -1; }
   HIP_TRY(hipSetDevice(c->sh.device));
   PLLHIP_CERT_FIRST(c);
@@ -1009,6 +1023,7 @@ extern "C" int pllhip_get_pmatrices(pllhip_ctx_t * c, unsigned int first, unsign
 
 extern "C" int pllhip_put_sumtable(pllhip_ctx_t * c, unsigned int slot, const double * h)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_sumtable(s, slot, h + lo * c->span));
   if (slot >= PLLHIP_SUMTABLE_MAX_SLOTS) { pllhip_set_error("sumtable slot %u", slot); return -1; }
   HIP_TRY(hipSetDevice(c->sh.device));
@@ -1064,6 +1079,7 @@ extern "C" int pllhip_release_sumtable(pllhip_ctx_t * c, unsigned int slot)
 
 extern "C" void * pllhip_dev_clv(pllhip_ctx_t * c, unsigned int idx)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!c->shards.empty()) return nullptr; // (one CLV lives on several devices)
   if (c->cert_pending && pllhip_cert_resolve(c)) return nullptr;
   if (idx >= c->clv.size()) return nullptr;

@@ -120,6 +120,34 @@ struct pllhip_ctx
   unsigned int fused_last_defer_epoch = 0;     // ... as it was when the kept plan was launched
   std::vector<unsigned int> fused_last_deferred; // the kept plan's deferred set: {clv, tip1, tip2, scaler + 1} each
   unsigned long long defer_stats[4] = {0, 0, 0, 0}; // deferred now (filled on read), ops deferred, materialise launches, CLVs materialised
+  // ---- edge lnL terms from the 4-state whole-list launch (partials_fused.hip: EDGE, likelihood.hip)
+  // An EDGE_II evaluation is remembered (edge_hint); the next whole-list launch that writes one of its two CLVs also
+  // computes that edge's per-site terms (edge_terms), and an evaluation of exactly that request sums them instead of
+  // reading both CLVs back.  The terms are good while NOTHING else happened: every entry point that changes device
+  // state drops them (pllhip_edge_terms_drop); dropped without having been used, they end the speculation until the
+  // next evaluation.
+  struct edge_req
+  {
+    unsigned int parent_clv = 0, child_clv = 0, matrix_index = 0;
+    int parent_scaler = -1, child_scaler = -1;
+    unsigned int freqs_indices[4] = {0, 0, 0, 0};
+    bool operator==(const edge_req & o) const
+    {
+      return parent_clv == o.parent_clv && child_clv == o.child_clv && matrix_index == o.matrix_index &&
+             parent_scaler == o.parent_scaler && child_scaler == o.child_scaler &&
+             memcmp(freqs_indices, o.freqs_indices, sizeof(freqs_indices)) == 0;
+    }
+  };
+  bool edge_fold = true;                      // pllhip_set_edge_fold
+  bool is_shard = false;                      // a shard of a group never folds
+  bool edge_hint_on = false;
+  edge_req edge_hint;
+  bool edge_terms_valid = false, edge_terms_used = false;
+  edge_req edge_terms_req;
+  double * d_edge_terms = nullptr;            // [sites + PLLHIP_TAIL_SITES], allocated on first use
+  bool fused_last_hint_on = false, fused_last_edge = false; // the kept plan: the hint it was built for, whether it has the epilogue
+  edge_req fused_last_hint;
+  unsigned long long edge_stats[4] = {0, 0, 0, 0}; // lists with the epilogue, lnL from terms, terms dropped unused, lnL by k_lnl_dna
   // 20 states: scratch of the lookup ops (partials_aa_mfma.hip, k_aa_cherry_rounds)
   double * cherry_pool = nullptr;
   unsigned char * cherry_codes = nullptr;
@@ -521,6 +549,18 @@ int pllhip_cert_resolve(pllhip_ctx * c, bool * rerun = nullptr, bool drained = f
       if (rc_cert_) return rc_cert_;               \
     }                                              \
   } while (0)
+// Edge lnL terms of the last whole-list launch (pllhip_ctx::edge_terms_*): at the top of every entry point that changes
+// device state.  Terms nobody summed were a wrong guess: no epilogue again until an evaluation hints anew.
+static inline void pllhip_edge_terms_drop(pllhip_ctx * c)
+{
+  if (!c->edge_terms_valid) return;
+  c->edge_terms_valid = false;
+  if (!c->edge_terms_used)
+  {
+    ++c->edge_stats[2];
+    c->edge_hint_on = false;
+  }
+}
 // Deferred cherries (pllhip_ctx::deferred, deferred.hip).  An entry point that is about to read or overwrite CLVs or
 // scale buffers outside a 4-state list kernel materialises them first -- bit for bit what the tip-tip op would have
 // stored, and zeros in the scale buffer it cleared.  n < 0 / PLLHIP_DEFERRED_FLUSH: every deferred CLV.

@@ -141,6 +141,7 @@ int pllhip_deferred_materialise_scalers(pllhip_ctx * c, const int * sc, int n)
 
 extern "C" int pllhip_set_deferral(pllhip_ctx_t * c, int on)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_set_deferral(s, on));
   if (c->cherry_deferral == (on != 0)) return 0;
   if (!on) PLLHIP_DEFERRED_FLUSH(c);

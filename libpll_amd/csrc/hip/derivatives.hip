@@ -104,6 +104,7 @@ extern "C" int pllhip_update_sumtable(pllhip_ctx_t * c, unsigned int parent_clv,
                                       int child_scaler, const unsigned int * h_params_indices,
                                       unsigned int slot)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS_PAR(c, pllhip_update_sumtable(s, parent_clv, parent_scaler, child_clv, child_scaler, h_params_indices, slot));
   HIP_TRY(hipSetDevice(c->sh.device));
   PLLHIP_CERT_FIRST(c);

@@ -533,6 +533,7 @@ extern "C" int pllhip_insertion_loglikelihood(pllhip_ctx_t * c, const pllhip_ins
                                               unsigned int query_count, const unsigned int * h_params_indices,
                                               size_t scratch_bytes, double * h_lnl)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!h_edges || !h_query_clv || !h_pendant || !h_params_indices || !h_lnl || !edge_count || !query_count)
   {
     pllhip_set_error("pllhip_insertion_loglikelihood: empty batch or NULL array");

@@ -586,6 +586,28 @@ __global__ __launch_bounds__(256) void k_lnl_dna(LnlArgs a)
   block_sum_to_partials(acc, a.reduce);
 }
 
+// 4 states, the per-site terms already formed by the whole-list launch (partials_fused.hip: EDGE): what is left of
+// k_lnl_dna is its sum -- the same grid, the same rounds per wave, the same lane for every site, so that every
+// partial sum, and with them the result, has k_lnl_dna's bits.  (terms[n] is the `lk` k_lnl_dna adds for site n.)
+template <int RC>
+__global__ __launch_bounds__(256) void k_lnl_dna_terms(const double * __restrict__ terms, unsigned int sites, ReduceOut reduce)
+{
+  constexpr unsigned int W = 2 * RC, SPS = 64 / W;
+  const unsigned int lane = threadIdx.x & 63u;
+  double acc = 0.0;
+  const size_t rounds = ((size_t)sites + 63) / 64;
+  const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const size_t nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
+  const unsigned int own = (lane & (W - 1)) * SPS + (lane / W);
+  for (size_t r = wave; r < rounds; r += nwaves)
+  {
+    const size_t n_own = r * 64 + own;
+    const double lk = terms[n_own]; // (slack behind the last site: no clamping)
+    if (n_own < sites) acc += lk;
+  }
+  block_sum_to_partials(acc, reduce);
+}
+
 // any states / any rate_cats: one lane per site
 template <int KIND>
 __global__ __launch_bounds__(128) void k_lnl_gen(LnlArgs a)
@@ -1001,7 +1023,7 @@ static int launch_lnl_two_pass(pllhip_ctx * c, LnlArgs & a, int kind, unsigned i
     }                                             \
   } while (0)
 
-static int run_lnl(pllhip_ctx * c, LnlArgs & a, int kind, double * h_persite, double * h_lnl)
+static int run_lnl(pllhip_ctx * c, LnlArgs & a, int kind, double * h_persite, double * h_lnl, bool from_terms = false)
 {
   HIP_TRY(hipSetDevice(c->sh.device));
   const unsigned int S = c->sh.states, R = c->sh.rate_cats;
@@ -1054,7 +1076,21 @@ static int run_lnl(pllhip_ctx * c, LnlArgs & a, int kind, double * h_persite, do
     size_t lds = 0;
     if (kind == EDGE_II && !s4) lds = (size_t)R * S * S * sizeof(double);
     if (kind == EDGE_TI) lds = (size_t)(s4 ? 16u : c->maxstates) * R * S * sizeof(double);
-    if (kind == EDGE_II) LAUNCH_LNL_RC(EDGE_II);
+    // (the terms of exactly this request, formed by the list launch and untouched since: only their sum is left)
+    if (from_terms)
+    {
+      const double * terms = c->d_edge_terms;
+      switch (R)
+      {
+        case 1: k_lnl_dna_terms<1><<<grid, 256, 0, c->stream>>>(terms, a.sites, a.reduce); break;
+        case 2: k_lnl_dna_terms<2><<<grid, 256, 0, c->stream>>>(terms, a.sites, a.reduce); break;
+        default: k_lnl_dna_terms<4><<<grid, 256, 0, c->stream>>>(terms, a.sites, a.reduce); break;
+      }
+      c->edge_terms_used = true;
+      ++c->edge_stats[1];
+    }
+    else if (kind == EDGE_II) LAUNCH_LNL_RC(EDGE_II);
+    if (s4 && kind == EDGE_II && !from_terms) ++c->edge_stats[3];
     if (kind == EDGE_TI) LAUNCH_LNL_RC(EDGE_TI);
     if (kind == ROOT) LAUNCH_LNL_RC(ROOT);
   }
@@ -1118,7 +1154,8 @@ static int fill_freqs_indices(pllhip_ctx * c, LnlArgs & a, const unsigned int * 
 // list's flag is looked at when the result has arrived -- a word in host memory, written before the lnL kernel
 // started.  Raised (rare): the list runs again in the reference's order, and the evaluation once more.  A shard of a
 // group (defer) returns without waiting: its group looks at the flags when it has collected (shard.hip).
-static int run_lnl_certified(pllhip_ctx * c, LnlArgs & a, int kind, double * h_persite_lnl, double * h_lnl)
+static int run_lnl_certified(pllhip_ctx * c, LnlArgs & a, int kind, double * h_persite_lnl, double * h_lnl,
+                             const pllhip_ctx::edge_req * req = nullptr)
 {
   // One rank of several (pllhip_comm_init): the evaluation ends in an all-reduce that every rank must enter the same
   // number of times, and a flag is raised on ONE rank -- so the flag is looked at first (one wait for the stream, which
@@ -1131,7 +1168,9 @@ static int run_lnl_certified(pllhip_ctx * c, LnlArgs & a, int kind, double * h_p
   for (;;)
   {
     LnlArgs aa = a;
-    int rc = run_lnl(c, aa, kind, h_persite_lnl, h_lnl);
+    // (looked at on every trip: a list that runs again drops the terms)
+    const bool from_terms = req && !h_persite_lnl && c->edge_terms_valid && c->d_edge_terms && c->edge_terms_req == *req;
+    int rc = run_lnl(c, aa, kind, h_persite_lnl, h_lnl, from_terms);
     if (rc || c->defer || !c->cert_pending) return rc;
     bool again = false;
     rc = pllhip_cert_resolve(c, &again, h_persite_lnl == nullptr);
@@ -1194,7 +1233,53 @@ extern "C" int pllhip_edge_loglikelihood(pllhip_ctx_t * c, unsigned int parent_c
       if (c->rows[child_clv].classes) a.cidx = c->rows[child_clv].site_id;
     }
   }
-  return run_lnl_certified(c, a, kind, h_persite_lnl, h_lnl);
+  // The request as a hint for the next whole-list launch (ctx.hpp: edge_hint), and as what kept terms must match.
+  // Eligible: 4 states, 1 / 2 / 4 categories, per-site or no scale buffers, no site repeats, no ascertainment
+  // correction, no invariant sites, not a shard of a group.
+  pllhip_ctx::edge_req req;
+  const bool eligible = kind == EDGE_II && c->edge_fold && !c->is_shard && !c->comm && c->sh.states == 4 &&
+                        (c->sh.rate_cats == 1 || c->sh.rate_cats == 2 || c->sh.rate_cats == 4) && !c->sh.rate_scalers &&
+                        c->rows.empty() && !c->asc_type && !c->sh.asc_states && !c->any_prop_invar;
+  if (eligible)
+  {
+    req.parent_clv = parent_clv;
+    req.child_clv = child_clv;
+    req.matrix_index = matrix_index;
+    req.parent_scaler = parent_scaler;
+    req.child_scaler = child_scaler;
+    for (unsigned int k = 0; k < c->sh.rate_cats; ++k) req.freqs_indices[k] = h_freqs_indices[k];
+  }
+  const int rc = run_lnl_certified(c, a, kind, h_persite_lnl, h_lnl, eligible ? &req : nullptr);
+  if (rc == 0 && eligible)
+  {
+    // (terms kept for another request were a wrong guess: they go now, so that THIS request is what the next list sees)
+    if (c->edge_terms_valid && !(c->edge_terms_req == req)) pllhip_edge_terms_drop(c);
+    c->edge_hint_on = true;
+    c->edge_hint = req;
+  }
+  else if (rc == 0)
+    c->edge_hint_on = false;
+  return rc;
+}
+
+/* Edge lnL terms from the whole-list launch (pllhip.h). */
+extern "C" int pllhip_set_edge_fold(pllhip_ctx_t * c, int on)
+{
+  for (pllhip_ctx * s : c->shards) s->edge_fold = false; // (a group's shards never fold)
+  pllhip_edge_terms_drop(c);
+  c->edge_fold = on != 0;
+  if (!c->edge_fold) c->edge_hint_on = false;
+  return 0;
+}
+
+extern "C" int pllhip_edge_fold_stats(pllhip_ctx_t * c, unsigned long long * out4)
+{
+  for (int t = 0; t < 4; ++t) out4[t] = 0;
+  for (pllhip_ctx * s : c->shards)
+    for (int t = 0; t < 4; ++t) out4[t] += s->edge_stats[t];
+  if (c->shards.empty())
+    for (int t = 0; t < 4; ++t) out4[t] = c->edge_stats[t];
+  return 0;
 }
 
 // The reference's root kernel takes site n's count from ENTRY n of the scale buffer (core_likelihood.c:197-198): with

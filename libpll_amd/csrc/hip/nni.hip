@@ -831,6 +831,7 @@ extern "C" int pllhip_nni_loglikelihood(pllhip_ctx_t * c, const pllhip_nni_edge_
                                         const unsigned int * h_params_indices, int route, size_t scratch_bytes,
                                         double * h_lnl)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   return nni_run(c, h_edges, edge_count, h_params_indices, route, scratch_bytes, nullptr, h_lnl);
 }
 
@@ -839,6 +840,7 @@ extern "C" int pllhip_nni_optimize(pllhip_ctx_t * c, const pllhip_nni_edge_t * h
                                    double tolerance, unsigned int max_iters, int route, size_t scratch_bytes,
                                    double * h_lengths, double * h_lnl, unsigned int * h_evals, int * h_status)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   const NniOpt opt = {min_length, max_length, tolerance, max_iters, h_lengths, h_evals, h_status};
   return nni_run(c, h_edges, edge_count, h_params_indices, route, scratch_bytes, &opt, h_lnl);
 }

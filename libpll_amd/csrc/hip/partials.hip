@@ -725,6 +725,7 @@ extern "C" int pllhip_cert_stats(pllhip_ctx_t * c, unsigned long long * out4)
 extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops, unsigned int count)
 {
   PLLHIP_ALL_SHARDS_PAR(c, pllhip_update_partials(s, ops, count)); // (enqueued on every device; nothing waits)
+  pllhip_edge_terms_drop(c);
   HIP_TRY(hipSetDevice(c->sh.device));
   if (c->cert_pending)
   {
@@ -794,13 +795,25 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
   {
     // (deferred cherries: the kept plan stands for a set of deferred CLVs -- it is the same list only while none of
     // them has been materialised, dropped or pinned since, defer_epoch; the launch then defers the same ones again)
+    // (the edge epilogue, ctx.hpp: edge_hint -- the kept plan stands for the hint it was built for, folded or not)
+    const bool edge_wanted = c->edge_fold && c->edge_hint_on && !c->is_shard && c->sh.rate_cats <= 4 && !c->sh.rate_scalers &&
+                             !c->asc_type && !c->sh.asc_states && !c->any_prop_invar && !c->comm;
     if (c->fused_last_ops.size() == count && !c->fused_debug &&
         c->fused_last_epoch == c->layout_epoch && c->fused_last_defer_epoch == c->defer_epoch &&
+        c->fused_last_hint_on == edge_wanted && (!edge_wanted || c->fused_last_hint == c->edge_hint) &&
         memcmp(c->fused_last_ops.data(), ops, (size_t)count * sizeof(pllhip_op_t)) == 0)
     {
       pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
       c->defer_stats[1] += c->fused_last_deferred.size() / 4;
-      return pllhip_relaunch_fused(c);
+      const int rc = pllhip_relaunch_fused(c);
+      if (rc == 0 && c->fused_last_edge)
+      {
+        c->edge_terms_valid = true;
+        c->edge_terms_used = false;
+        c->edge_terms_req = c->fused_last_hint;
+        ++c->edge_stats[0];
+      }
+      return rc;
     }
     c->fused_last_ops.clear();
     const unsigned int full_count = count;       // (the caller's list; `ops` / `count` below: the ops the kernel runs)
@@ -998,12 +1011,65 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
       if (nsegs == 1) break;
     }
     if (rc < 0) return rc;
+    // The edge epilogue: the hinted evaluation as a pseudo-op behind the last op -- one segment only, at the
+    // configuration the unfolded plan has just taken (never fewer waves for its sake), both ends ordinary stored CLVs
+    // of which the list writes at least one.  A planner that refuses leaves the unfolded plan as it is.
+    FusedEdge fedge;
+    bool folded = false;
+    if (rc == 0 && edge_wanted && fplans.size() == 1) // (fplans: what was planned -- the loop above leaves nsegs at 1)
+    {
+      const pllhip_ctx::edge_req & q = c->edge_hint;
+      // (an end the list reads or leaves as a table is no CLV in HBM; one deferred earlier still is none unless this
+      // list overwrites it with an ordinary op)
+      // (partials_fused.hpp: the one rule, shared with the dry planner.  What the list materialised first is no
+      // longer deferred here; its address handed out: anybody may write it)
+      auto stored = [&](unsigned int i) {
+        return i < c->clv.size() && c->clv[i] &&
+               pllhip_fused_edge_end_stored(geom, dd, i, i < c->deferred.size() && c->deferred[i].on,
+                                            i < c->clv_pinned.size() && c->clv_pinned[i]);
+      };
+      bool list_scales = false;
+      for (unsigned int i = 0; i < count; ++i) list_scales = list_scales || args[i].pscaler != nullptr;
+      if (stored(q.parent_clv) && stored(q.child_clv) && q.matrix_index < c->sh.prob_matrices &&
+          q.parent_scaler < (int)c->sh.scale_buffers && q.child_scaler < (int)c->sh.scale_buffers &&
+          (list_scales || (q.parent_scaler < 0 && q.child_scaler < 0)))
+      {
+        memset(&fedge, 0, sizeof(fedge));
+        fedge.parent_clv = q.parent_clv;
+        fedge.child_clv = q.child_clv;
+        fedge.parent_scaler = q.parent_scaler;
+        fedge.child_scaler = q.child_scaler;
+        fedge.parent = c->clv[q.parent_clv];
+        fedge.child = c->clv[q.child_clv];
+        fedge.pscaler = pllhip_scaler_ptr(c, q.parent_scaler);
+        fedge.cscaler = pllhip_scaler_ptr(c, q.child_scaler);
+        fedge.pmat = pllhip_pmat_ptr(c, q.matrix_index);
+        std::vector<FusedOp> with_edge;
+        unsigned int reloads = 0;
+        if (pllhip_fused_plan(geom, ops, args.data(), kinds.data(), count, nslots, with_edge, &reloads,
+                              extras.empty() ? nullptr : extras.data(), &fedge) == 0)
+        {
+          fplans[0].swap(with_edge);
+          folded = true;
+        }
+      }
+    }
     if (rc == 0)
     {
       pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
-      rc = pllhip_launch_fused(c, fplans, nslots, keep_jobs.empty() ? nullptr : &keep_jobs);
+      // (the hint the plan stands for; the launch takes the frequencies' places from it)
+      c->fused_last_hint_on = edge_wanted;
+      c->fused_last_hint = c->edge_hint;
+      rc = pllhip_launch_fused(c, fplans, nslots, keep_jobs.empty() ? nullptr : &keep_jobs, folded ? &fedge : nullptr);
       if (rc == 0)
       {
+        if (folded)
+        {
+          c->edge_terms_valid = true;
+          c->edge_terms_used = false;
+          c->edge_terms_req = c->edge_hint;
+          ++c->edge_stats[0];
+        }
         // the deferrals this list ends and begins
         for (unsigned int i : dd.dropped) pllhip_deferred_drop(c, i);
         for (size_t t = 0; t < new_deferred.size(); t += 4)

@@ -232,15 +232,30 @@ __device__ __forceinline__ unsigned int group_and(unsigned int x)
   return x;
 }
 
+// The tail of k_lnl_dna for one site (likelihood.hip), statement for statement: logarithm, scaler term, pattern weight.
+// Not inlined into the list kernel: the logarithm's two dozen constants would be hoisted out of the tile loop and held
+// in registers through every op of the list (seen: 149 -> 168 registers and scratch).
+__device__ __attribute__((noinline)) double edge_site_loglk(double terma, unsigned int site_scalings, unsigned int weight)
+{
+  double lk = log(terma);
+  if (site_scalings) lk += (double)site_scalings * log(PLLHIP_SCALE_THRESHOLD);
+  lk *= (double)weight;
+  return lk;
+}
+
 // WPS: waves per SIMD the register budget is sized for (3 = 168 VGPRs: twelve waves per CU)
 // NTP: cache policy -- 0 plain stores, 1 the tiles non-temporal, 2 the counts as well
-template <int RC, int J, int MODE, int NTP, int WPS>
+// EDGE: when a tile's op loop has ended, the per-site terms of one edge log-likelihood are formed from the two CLVs
+//       in their slots and stored, 8 bytes per site (the epilogue below; one segment, 1 / 2 / 4 rate categories, per-site
+//       or no scale buffers).  Without it the kernel is what it was: every line the flag adds is under `if (EDGE)`.
+template <int RC, int J, int MODE, int NTP, int WPS, bool EDGE>
 __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restrict__ plan0, FusedBases bases,
                                                         unsigned int nops0, unsigned int sites, unsigned int nslots,
                                                         double2 * sink, unsigned int * next_tile, unsigned int dynamic_rounds,
                                                         unsigned int site_base, unsigned int tile_groups,
-                                                        unsigned int * reset_tiles)
+                                                        unsigned int * reset_tiles, FusedEdgeArgs edge)
 {
+  static_assert(!EDGE || (RC <= 4 && MODE != SCALE_RATE && J <= 2 * RC), "the edge epilogue: a lane of each site's group keeps one sub-step's site");
   // (round 5) Two sets of tile counters in turn: this launch hands out tiles from `next_tile` and zeroes the OTHER set
   // for the launch behind it (stream order separates the two) -- until then a list without tip operands, which has no
   // table launch to do it, was preceded by a 32 KB hipMemsetAsync: two fill kernels in front of every short
@@ -279,6 +294,18 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
   // behind its last site (ctx.hip), so the last tile is loaded and STORED whole: no lane
   // predicates, and every address is a wave-uniform tile base plus a lane offset that
   // never changes.
+  // (EDGE: the lane's two frequencies and its category's weight, as k_lnl_dna keeps them -- loaded once per wave, ahead
+  // of everything: the epilogue of a tile consumes no load of its own)
+  double2 edge_fr = make_double2(0.0, 0.0);
+  double edge_wk = 0.0;
+  if (EDGE)
+  {
+    const unsigned int fo = k == 0 ? edge.freqs_off[0] : k == 1 ? edge.freqs_off[1] : k == 2 ? edge.freqs_off[2] : edge.freqs_off[3];
+    const pll_v2d fr = *(const pll_v2d PLL_GLOBAL *)((unsigned long long)(uintptr_t)edge.freqs + fo + h * 16u);
+    edge_fr = make_double2(fr.x, fr.y);
+    edge_wk = *(const double PLL_GLOBAL *)((unsigned long long)(uintptr_t)edge.rate_weights + k * 8u);
+    asm volatile("" : "+v"(edge_fr.x), "+v"(edge_fr.y), "+v"(edge_wk)); // (waited for here, once per wave: plain registers from now on)
+  }
   const size_t tiles = ((size_t)sites + TS - 1) / TS;
   // (round 5) work items: (tile, segment) pairs, segment-major -- every tile of the longest segment first
   const unsigned int nsegs = bases.nsegs;
@@ -359,6 +386,12 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     // evicting -- with 8 M sites per row that cost the 133 GB partition a quarter of its speed; tool builds
     // that read every row from the first row's pages: 0.56 -> 0.76 of the HBM peak, profiles/r3_footprint.txt.
     // Sixty-four rows in one instruction wait for their translations together, long before they are used.)
+    // (EDGE: the pattern weight of the ONE site of this tile the lane finishes in the epilogue -- sub-step (lane % W) % J,
+    // site lane / W of it -- requested here, AHEAD of the characters: the first wait for those covers it, and the
+    // epilogue consumes no load of its own)
+    const unsigned int edge_sub = EDGE ? (lane & (W - 1)) % J : 0u, edge_own = EDGE ? edge_sub * SPS + lane / W : 0u;
+    unsigned int edge_pw = 0;
+    if (EDGE) edge_pw = *(const unsigned int PLL_GLOBAL *)((unsigned long long)(uintptr_t)edge.pattern_weights + (site0 + edge_own) * 4u);
     pll_v4u cs = *(const pll_v4u PLL_GLOBAL *)(row_first + site0);
     // What an op needs from memory besides is requested TWO ops ahead of it: its 16 bytes of [P_l | P_r].
     auto request = [&](FusedFetch<J> & f, const Rec & r) {
@@ -536,6 +569,7 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     sink_stores();
     if (rec_flags(h1) & PLLHIP_FUSED_RELOAD_NEXT) reload(rec_src(h1));
     gather(pta, pta2, h1);
+    if (EDGE) asm volatile("" : "+v"(edge_pw)); // (arrived with the characters the gather has just used: not a load any longer)
     request(fa, h1);
     asm volatile("" ::"v"(fb.pm.x), "v"(fb.pm.y) : "memory");
     if (RC == 8) asm volatile("" ::"v"(fb.pm2.x), "v"(fb.pm2.y) : "memory");
@@ -712,6 +746,62 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       step(rb, ra, fb, fa, ptb, pta, ptb2, pta2, i);
       if (++i == nops) break;
     }
+    if (EDGE)
+    {
+      // The edge epilogue (likelihood.hip: k_lnl_dna, EDGE_II, statement for statement).  The plan kept both CLVs of
+      // the edge in slots to the end of the list (the pseudo-op at position nops); the last op's look-ahead staged the
+      // edge's P-matrix rows in `pr`, and its reload -- issued ahead of that op's request -- has arrived once the
+      // request has: both fetches are consumed, whichever was the last (no wait for the last op's stores).
+      asm volatile("" ::"v"(fa.pm.x), "v"(fa.pm.y), "v"(fb.pm.x), "v"(fb.pm.y) : "memory");
+      const Rec re = rec_load(plan, nops + 2);
+      const unsigned int efl = rec_flags(re);
+      const char * lds_p = reinterpret_cast<const char *>(clv) + rec_lslot(re) + lane16;
+      const char * lds_c = reinterpret_cast<const char *>(clv) + rec_rslot(re) + lane16;
+      double2 pj[J], cj[J];
+#pragma unroll
+      for (unsigned int j = 0; j < J; ++j)
+      {
+        pj[j] = *reinterpret_cast<const double2 *>(lds_p + j * 1024u);
+        cj[j] = *reinterpret_cast<const double2 *>(lds_c + j * 1024u);
+      }
+      unsigned int ps_own = 0u, cs_own = 0u;
+      if (MODE != SCALE_NONE)
+      {
+        ps_own = *reinterpret_cast<const unsigned int *>(reinterpret_cast<const char *>(cnt) + rec_lcnt(re) + edge_own * 4u);
+        cs_own = *reinterpret_cast<const unsigned int *>(reinterpret_cast<const char *>(cnt) + rec_rcnt(re) + edge_own * 4u);
+        if (!(efl & PLLHIP_FUSED_LCNT)) ps_own = 0u;
+        if (!(efl & PLLHIP_FUSED_RCNT)) cs_own = 0u;
+      }
+      const double fr0 = edge_fr.x, fr1 = edge_fr.y, wk = edge_wk;
+      const unsigned int grp0 = lane & ~(W - 1);
+      double my_terma = 1.0;
+#pragma unroll
+      for (unsigned int j = 0; j < J; ++j)
+      {
+        const double2 p = pj[j], c = cj[j];
+        const double2 cp = make_double2(dpp_pair_swap(c.x), dpp_pair_swap(c.y));
+        // row dot, x pi, x parent (core_likelihood_avx.c:1175-1213)
+        const double t0 = (fr0 * pr.dot(0, c, cp)) * p.x;
+        const double t1 = (fr1 * pr.dot(1, c, cp)) * p.y;
+        // (t0 + t1) + (t2 + t3): own pair plus the partner's pair
+        const double s = t0 + t1;
+        const double terma_r = s + dpp_pair_swap(s);
+        // (the 4-state edge kernels skip non-positive terms; no invariant sites here: every prop_invar is 0)
+        double contrib;
+        if (!(terma_r > 0.0))
+          contrib = 0.0;
+        else
+          contrib = terma_r * wk;
+        double terma = 0.0;
+#pragma unroll
+        for (int i = 0; i < RC; ++i) terma += __shfl(contrib, (int)(grp0 + 2 * i), 64);
+        if (edge_sub == j) my_terma = terma;
+      }
+      // once per site: the lanes with lane % W < J own one each
+      const double lk = edge_site_loglk(my_terma, ps_own + cs_own, edge_pw);
+      // (tail tiles store whole, into the buffer's slack; the sum ignores sites past the end)
+      if ((lane & (W - 1)) < J) *(double PLL_GLOBAL *)((unsigned long long)(uintptr_t)edge.terms + (site0 + edge_own) * 8u) = lk;
+    }
     if (++round < static_rounds)
     {
       item += nwaves;
@@ -742,12 +832,17 @@ struct Node
 
 // slots per wave when `wgs` workgroups of four waves share a CU's LDS: 64 KB per workgroup
 // for two (8 waves per CU), 52 KB for three (12 waves: better latency hiding, one slot less)
+static unsigned int fused_slots_for(unsigned int R, bool rate_scalers, unsigned int wgs);
 unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int wgs)
 {
+  return fused_slots_for(c->sh.rate_cats, c->sh.rate_scalers != 0, wgs);
+}
+
+static unsigned int fused_slots_for(unsigned int R, bool rate_scalers, unsigned int wgs)
+{
   // 64 KB per workgroup of four waves: 16 KB per wave minus the matrix block
-  const unsigned int R = c->sh.rate_cats;
   const unsigned int sps = 64 / (2 * R);
-  const size_t cw = c->sh.rate_scalers ? 32 : (sps < 4 ? 4 : sps);
+  const size_t cw = rate_scalers ? 32 : (sps < 4 ? 4 : sps);
   const size_t per_slot = (size_t)PLLHIP_FUSED_J * (64 * 16 + cw * 4);
   const size_t pmat = (size_t)R * 16 * sizeof(double); // one matrix at a time (stage_rows)
   // (four workgroups -- 16 waves of 128 registers, four slots -- were measured for short lists in round 3 and are
@@ -766,15 +861,23 @@ static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, 
                                const int * kinds, unsigned int count, unsigned int nslots,
                                const std::vector<unsigned int> & order, const std::vector<unsigned int> & pos_of,
                                const std::vector<Node> & node, std::vector<FusedOp> & plan,
-                               unsigned int * reloads_out, std::pmr::memory_resource * pool, const FusedExtra * extra)
+                               unsigned int * reloads_out, std::pmr::memory_resource * pool, const FusedExtra * extra,
+                               FusedEdge * edge, const int * edge_raw, const int * edge_sraw)
 {
+  // the edge pseudo-op (FusedEdge): position `count`, list index `count` -- it reads two values and writes none
+  const unsigned int total = count + (edge ? 1u : 0u);
   // inner operands of the op at each position: producing list op (-1: written by an earlier
   // call), its HBM address, the HBM address of the counts the reader passes with it, and the
   // list op that wrote those counts
   struct Operand { int w; const double * hbm; const unsigned int * sc; int sw; };
   auto operands = [&](unsigned int i, Operand (&o)[2]) {
     o[0] = o[1] = Operand{-2, nullptr, nullptr, -1}; // -2: no such operand (a tip)
-    if (kinds[i] == 0)
+    if (i == count)
+    {
+      o[0] = Operand{edge_raw[0], edge->parent, edge->pscaler, edge_sraw[0]};
+      o[1] = Operand{edge_raw[1], edge->child, edge->cscaler, edge_sraw[1]};
+    }
+    else if (kinds[i] == 0)
     {
       o[0] = Operand{node[i].raw[0], args[i].left, args[i].lscaler, node[i].sraw[0]};
       o[1] = Operand{node[i].raw[1], args[i].right, args[i].rscaler, node[i].sraw[1]};
@@ -786,10 +889,10 @@ static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, 
     }
   };
   PlanLists uses(count, pool); // positions at which each list value is read
-  for (unsigned int pos = 0; pos < count; ++pos)
+  for (unsigned int pos = 0; pos < total; ++pos)
   {
     Operand o[2];
-    operands(order[pos], o);
+    operands(pos < count ? order[pos] : count, o);
     if (o[0].w >= 0) uses[o[0].w].push_back(pos);
     if (o[1].w >= 0 && o[1].w != o[0].w) uses[o[1].w].push_back(pos);
   }
@@ -832,8 +935,8 @@ static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, 
   // operands of the op at position `pos` that are not in a slot: reloaded at the top of
   // position pos - 1 (`at`; the kernel's prologue for pos 0)
   auto place_reloads = [&](unsigned int pos, unsigned int at) -> int {
-    const unsigned int i = order[pos];
-    FusedOp & f = plan[pos];
+    const unsigned int i = pos < count ? order[pos] : count;
+    FusedOp & f = pos < count ? plan[pos] : edge->op;
     Operand o[2];
     operands(i, o);
     for (int side = 0; side < 2; ++side)
@@ -890,14 +993,21 @@ static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, 
       f.g[1] = extra[i].g[1];
     }
   }
+  if (edge)
+  {
+    memset(&edge->op, 0, sizeof(edge->op));
+    edge->op.kind = PLLHIP_FUSED_KIND_EDGE;
+    edge->op.list_pos = (int)count;
+    edge->op.lslot = edge->op.rslot = edge->op.pslot = edge->op.lsc_slot = edge->op.rsc_slot = -1;
+  }
   if (place_reloads(0, 0)) return 1;
   oneshot.swap(oneshot_next);
-  for (unsigned int pos = 0; pos < count; ++pos)
+  for (unsigned int pos = 0; pos < total; ++pos)
   {
-    const unsigned int i = order[pos];
-    FusedOp & f = plan[pos];
+    const unsigned int i = pos < count ? order[pos] : count;
+    FusedOp & f = pos < count ? plan[pos] : edge->op;
     // top of the op: the next op's missing operands are requested into slots free NOW
-    if (pos + 1 < count && place_reloads(pos + 1, pos)) return 1;
+    if (pos + 1 < total && place_reloads(pos + 1, pos)) return 1;
     Operand o[2];
     operands(i, o);
     for (int side = 0; side < 2; ++side)
@@ -923,6 +1033,7 @@ static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, 
         if (x.sc) sc_slot = slot;
       }
     }
+    if (pos == count) break; // (the edge pseudo-op: nothing runs after it, and it writes no value)
     // operands read for the last time give their slots back
     for (int side = 0; side < 2; ++side)
     {
@@ -977,7 +1088,7 @@ static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, 
 
 int pllhip_fused_plan(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args,
                       const int * kinds, unsigned int count, unsigned int nslots,
-                      std::vector<FusedOp> & plan, unsigned int * reloads_out, const FusedExtra * extra)
+                      std::vector<FusedOp> & plan, unsigned int * reloads_out, const FusedExtra * extra, FusedEdge * edge)
 {
   static thread_local std::vector<char> arena(256 * 1024);
   std::pmr::monotonic_buffer_resource pool(arena.data(), arena.size()); // (beyond the buffer: the heap)
@@ -1072,7 +1183,23 @@ int pllhip_fused_plan(const FusedGeom & geom, const pllhip_op_t * ops, const Par
   std::vector<unsigned int> pos_of(count);
   for (unsigned int pos = 0; pos < count; ++pos) pos_of[order[pos]] = pos;
 
-  const int rc = assign_slots_reload(geom, ops, args, kinds, count, nslots, order, pos_of, node, plan, reloads_out, &pool, extra);
+  // the edge pseudo-op reads what the list leaves in the two CLVs and scale buffers: their LAST writers.  An end the
+  // list does not keep in HBM (a tip, a deferred cherry), the same CLV twice, or a list that writes neither end: no fold
+  int edge_raw[2] = {-1, -1}, edge_sraw[2] = {-1, -1};
+  if (edge)
+  {
+    if (edge->parent_clv >= nclv || edge->child_clv >= nclv || edge->parent_clv == edge->child_clv ||
+        geom.is_tip(edge->parent_clv) || geom.is_tip(edge->child_clv) ||
+        edge->parent_scaler >= (int)nsc || edge->child_scaler >= (int)nsc)
+      return 1;
+    edge_raw[0] = clv_w[edge->parent_clv];
+    edge_raw[1] = clv_w[edge->child_clv];
+    if (edge_raw[0] < 0 && edge_raw[1] < 0) return 1;
+    edge_sraw[0] = edge->parent_scaler >= 0 ? sc_w[edge->parent_scaler] : -1;
+    edge_sraw[1] = edge->child_scaler >= 0 ? sc_w[edge->child_scaler] : -1;
+  }
+  const int rc = assign_slots_reload(geom, ops, args, kinds, count, nslots, order, pos_of, node, plan, reloads_out, &pool, extra,
+                                     edge, edge_raw, edge_sraw);
   if (rc) return rc;
   if (pllhip_env("PLLHIP_FUSED_DEBUG"))
   {
@@ -1196,6 +1323,15 @@ void pllhip_fused_deferral(const FusedGeom & geom, const pllhip_op_t * ops, unsi
   }
 }
 
+bool pllhip_fused_edge_end_stored(const FusedGeom & geom, const FusedDeferral & dd, unsigned int clv,
+                                  bool deferred_before, bool pinned)
+{
+  if (clv >= geom.nclv || geom.is_tip(clv) || pinned) return false;
+  if (!deferred_before) return true;
+  return std::find(dd.materialise.begin(), dd.materialise.end(), clv) != dd.materialise.end() ||
+         std::find(dd.dropped.begin(), dd.dropped.end(), clv) != dd.dropped.end();
+}
+
 // The planner with deferred cherries, without a device (tests/test_host_deferred_plan.py).  old_deferred / old_scaler /
 // pinned: per CLV index, may be NULL (pllhip_fused_deferral).  Out: *nkept kept ops in walk order as positions in
 // the caller's list (order_out), six numbers per kept op as pllhip_fused_plan_dry gives them (slots_out), two operand
@@ -1203,13 +1339,16 @@ void pllhip_fused_deferral(const FusedGeom & geom, const pllhip_op_t * ops, unsi
 // (deferred_out), and the CLVs deferred earlier that the list has materialised first / ends the deferral of
 // (materialise_out, dropped_out: at most clv indices each, counts in *nmaterialise, *ndropped).
 // Returns 0, 1 if the kernel does not take the list, < 0 on error.
-extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
-                                              int pattern_tip, const pllhip_op_t * ops, unsigned int count, unsigned int nslots,
-                                              const unsigned char * old_deferred, const int * old_scaler,
-                                              const unsigned char * pinned, unsigned int * nkept, unsigned int * order_out,
-                                              int * slots_out, int * operands_out, unsigned char * deferred_out,
-                                              unsigned int * reloads_out, unsigned int * materialise_out,
-                                              unsigned int * nmaterialise, unsigned int * dropped_out, unsigned int * ndropped)
+// (edge4 not null: pllhip_fused_plan_dry_edge -- {parent_clv, parent_scaler, child_clv, child_scaler}; `nslots` is then
+// not used: the list is planned the way pllhip_update_partials plans a one-segment list, see there)
+static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                             int pattern_tip, const pllhip_op_t * ops, unsigned int count, unsigned int nslots,
+                             const unsigned char * old_deferred, const int * old_scaler,
+                             const unsigned char * pinned, unsigned int * nkept, unsigned int * order_out,
+                             int * slots_out, int * operands_out, unsigned char * deferred_out,
+                             unsigned int * reloads_out, unsigned int * materialise_out,
+                             unsigned int * nmaterialise, unsigned int * dropped_out, unsigned int * ndropped,
+                             const int * edge4, unsigned int rate_cats, int * edge_out)
 {
   FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
   for (unsigned int i = 0; i < count; ++i)
@@ -1222,6 +1361,13 @@ extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int cl
       pllhip_set_error("pllhip_fused_plan_dry_deferred: index out of range in op %u", i);
       return -1;
     }
+  }
+  if (edge4 && (edge4[0] < 0 || (size_t)edge4[0] >= geom.nclv || edge4[2] < 0 || (size_t)edge4[2] >= geom.nclv ||
+                edge4[1] >= (int)scale_buffers || edge4[3] >= (int)scale_buffers ||
+                !(rate_cats == 1 || rate_cats == 2 || rate_cats == 4)))
+  {
+    pllhip_set_error("pllhip_fused_plan_dry_edge: bad edge or rate_cats");
+    return -1;
   }
   FusedDeferral d;
   pllhip_fused_deferral(geom, ops, count, old_deferred, old_scaler, pinned, d);
@@ -1276,10 +1422,49 @@ extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int cl
     }
   }
   if (reloads_out) *reloads_out = 0;
+  for (int t = 0; edge_out && t < 8; ++t) edge_out[t] = t >= 1 && t <= 4 ? -1 : 0;
   if (!n) return 0;
   std::vector<FusedOp> plan;
   unsigned int reloads = 0;
-  const int rc = pllhip_fused_plan(geom, kept.data(), args.data(), kinds.data(), n, nslots, plan, &reloads);
+  int rc;
+  if (!edge4)
+    rc = pllhip_fused_plan(geom, kept.data(), args.data(), kinds.data(), n, nslots, plan, &reloads);
+  else
+  {
+    // the unfolded plan decides the configuration (12 waves per CU, else 8); the epilogue is then tried at that one
+    unsigned int wgs = 3;
+    for (rc = 1; rc > 0 && wgs >= 2u; --wgs)
+    {
+      nslots = fused_slots_for(rate_cats, false, wgs);
+      rc = pllhip_fused_plan(geom, kept.data(), args.data(), kinds.data(), n, nslots, plan, &reloads);
+    }
+    if (rc) return rc;
+    ++wgs;
+    edge_out[6] = (int)wgs;
+    FusedEdge e;
+    memset(&e, 0, sizeof(e));
+    e.parent_clv = (unsigned int)edge4[0];
+    e.parent_scaler = edge4[1];
+    e.child_clv = (unsigned int)edge4[2];
+    e.child_scaler = edge4[3];
+    e.parent = reinterpret_cast<const double *>((uintptr_t)4096 * (e.parent_clv + 1));
+    e.child = reinterpret_cast<const double *>((uintptr_t)4096 * (e.child_clv + 1));
+    e.pscaler = e.parent_scaler >= 0 ? reinterpret_cast<unsigned int *>((uintptr_t)4096 * (e.parent_scaler + 1)) : nullptr;
+    e.cscaler = e.child_scaler >= 0 ? reinterpret_cast<unsigned int *>((uintptr_t)4096 * (e.child_scaler + 1)) : nullptr;
+    // (the rule pllhip_update_partials applies: an end deferred by an earlier call that the list does not see is not in HBM)
+    auto stored = [&](unsigned int i) {
+      return pllhip_fused_edge_end_stored(geom, d, i, old_deferred && old_deferred[i], pinned && pinned[i]);
+    };
+    std::vector<FusedOp> folded;
+    unsigned int freloads = 0;
+    if (stored(e.parent_clv) && stored(e.child_clv) && pllhip_fused_plan(geom, kept.data(), args.data(), kinds.data(), n, nslots, folded, &freloads, nullptr, &e) == 0)
+    {
+      plan.swap(folded);
+      reloads = freloads;
+      const int v[8] = {1, e.op.lslot, e.op.rslot, e.op.lsc_slot, e.op.rsc_slot, e.op.dma_flags, (int)wgs, (int)wgs};
+      for (int t = 0; t < 8; ++t) edge_out[t] = v[t];
+    }
+  }
   if (rc) return rc;
   std::vector<int> opnd(operands_out ? operands_out : nullptr, operands_out ? operands_out + 2 * n : nullptr);
   for (unsigned int pos = 0; pos < n; ++pos)
@@ -1299,6 +1484,42 @@ extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int cl
   }
   if (reloads_out) *reloads_out = reloads;
   return 0;
+}
+
+extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                              int pattern_tip, const pllhip_op_t * ops, unsigned int count, unsigned int nslots,
+                                              const unsigned char * old_deferred, const int * old_scaler,
+                                              const unsigned char * pinned, unsigned int * nkept, unsigned int * order_out,
+                                              int * slots_out, int * operands_out, unsigned char * deferred_out,
+                                              unsigned int * reloads_out, unsigned int * materialise_out,
+                                              unsigned int * nmaterialise, unsigned int * dropped_out, unsigned int * ndropped)
+{
+  return plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, nslots, old_deferred, old_scaler, pinned,
+                           nkept, order_out, slots_out, operands_out, deferred_out, reloads_out, materialise_out, nmaterialise,
+                           dropped_out, ndropped, nullptr, 0, nullptr);
+}
+
+// The same with the edge epilogue (pllhip_ctx::edge_hint; tests/test_host_edge_fold_plan.py): the list planned as
+// pllhip_update_partials plans a one-segment list of a partition with `rate_cats` categories and per-site or no scale
+// buffers -- unfolded at 12 waves per CU, else 8; then once more at that configuration with the evaluation of
+// edge4 = {parent_clv, parent_scaler, child_clv, child_scaler} as a pseudo-op behind the last op.
+// edge_out[8]: folded (0: the unfolded plan is what the other outputs describe), the pseudo-op's lslot (parent), rslot
+// (child), lsc_slot, rsc_slot, dma_flags, workgroups per CU of the unfolded plan, of the folded one (0: not folded).
+extern "C" int pllhip_fused_plan_dry_edge(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                          int pattern_tip, unsigned int rate_cats, const pllhip_op_t * ops, unsigned int count,
+                                          const unsigned char * old_deferred, const int * old_scaler,
+                                          const unsigned char * pinned, const int * edge4, unsigned int * nkept,
+                                          unsigned int * order_out, int * slots_out, int * operands_out,
+                                          unsigned char * deferred_out, unsigned int * reloads_out, int * edge_out)
+{
+  if (!edge4 || !edge_out)
+  {
+    pllhip_set_error("pllhip_fused_plan_dry_edge: no edge");
+    return -1;
+  }
+  return plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, 0, old_deferred, old_scaler, pinned, nkept,
+                           order_out, slots_out, operands_out, deferred_out, reloads_out, nullptr, nullptr, nullptr, nullptr,
+                           edge4, rate_cats, edge_out);
 }
 
 // The planner without a device (tests/test_host.py, tools): which order and how many
@@ -1361,7 +1582,7 @@ extern "C" int pllhip_fused_plan_dry(unsigned int tips, unsigned int clv_buffers
 
 template <int RC>
 static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedBases & bases, unsigned int count,
-                           unsigned int nslots, int mode)
+                           unsigned int nslots, int mode, bool with_edge)
 {
   constexpr int J = PLLHIP_FUSED_J;
   const unsigned int sites = c->sh.sites;
@@ -1407,8 +1628,23 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   // takers; and no more than the counter buffer holds)
   const unsigned int tile_groups = (unsigned int)std::min<size_t>(std::min<size_t>(8, PLLHIP_TILE_COUNTER_BYTES / 128),
                                                                   std::max<size_t>(1, grid / 8));
-#define LAUNCH_FUSED(MODEV, NTV) k_dna_fused<RC, J, MODEV, NTV, 3><<<(unsigned int)grid, 256, lds, c->stream>>>( \
-      d_plan, bases, count, sites, nslots, (double2 *)c->d_sink, tile_counter, dynamic_rounds, 0u, tile_groups, reset_tiles)
+  // (the edge epilogue: pllhip_launch_fused has made sure of one segment, 1 / 2 / 4 categories, no per-rate scalers)
+  FusedEdgeArgs edge_args = {c->freqs, c->rate_weights, c->pattern_weights, c->d_edge_terms, {0u, 0u, 0u, 0u}};
+  for (int k = 0; with_edge && k < 4; ++k) edge_args.freqs_off[k] = c->fused_last_hint.freqs_indices[k] * 4u * (unsigned int)sizeof(double);
+  if (with_edge && (RC > 4 || mode == SCALE_RATE || nsegs != 1 || !c->d_edge_terms))
+  {
+    pllhip_set_error("whole-list launch: no edge epilogue for this shape");
+    return -1;
+  }
+#define LAUNCH_FUSED_E(MODEV, NTV, EDGEV) k_dna_fused<RC, J, MODEV, NTV, 3, EDGEV><<<(unsigned int)grid, 256, lds, c->stream>>>( \
+      d_plan, bases, count, sites, nslots, (double2 *)c->d_sink, tile_counter, dynamic_rounds, 0u, tile_groups, reset_tiles, edge_args)
+#define LAUNCH_FUSED(MODEV, NTV)                                                       \
+  do {                                                                                  \
+    if constexpr (RC <= 4 && MODEV != SCALE_RATE) {                                     \
+      if (with_edge) LAUNCH_FUSED_E(MODEV, NTV, true);                                  \
+      else LAUNCH_FUSED_E(MODEV, NTV, false);                                           \
+    } else LAUNCH_FUSED_E(MODEV, NTV, false);                                           \
+  } while (0)
 #define LAUNCH_FUSED_MODE(NTV)                         \
   do {                                                  \
     if (mode == SCALE_NONE) LAUNCH_FUSED(0, NTV);       \
@@ -1420,6 +1656,7 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   else LAUNCH_FUSED_MODE(2);
 #undef LAUNCH_FUSED_MODE
 #undef LAUNCH_FUSED
+#undef LAUNCH_FUSED_E
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1572,9 +1809,12 @@ extern "C" unsigned int pllhip_fused_segments_dry(unsigned int tips, unsigned in
 // table, the reload sources, the pair-table jobs, the character rows' addresses.  Returns 1 if the list is not one
 // the kernel takes.
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
-                        const std::vector<FusedPairJob> * keep_jobs)
+                        const std::vector<FusedPairJob> * keep_jobs, const FusedEdge * edge)
 {
   const unsigned int nsegs = (unsigned int)plans.size();
+  if (edge && (nsegs != 1 || plans[0].size() < 2 || c->sh.rate_cats > 4 || c->sh.rate_scalers)) return 1;
+  if (edge && !c->d_edge_terms)
+    HIP_TRY(hipMalloc((void **)&c->d_edge_terms, ((size_t)c->sh.sites + PLLHIP_TAIL_SITES) * sizeof(double)));
   unsigned int count = 0, longest = 0;
   for (const auto & plan : plans)
   {
@@ -1690,6 +1930,8 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
       r.chars2 = chars2_of[pos + 1];
       r.gather_off2 = table2_of[pos + 1];
     }
+    // (the edge pseudo-op at position n: its matrix is requested and staged as a right-hand one, like a tip-inner op's)
+    if (edge && pos + 2 == (long)n) r.req_rmat = (unsigned int)((edge->pmat - c->pmatrix) * sizeof(double));
     if (pos + 2 < (long)n)
     {
       const FusedOp & f = plan[pos + 2];
@@ -1700,11 +1942,11 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
       r.req_rmat = (unsigned int)((f.rmat - c->pmatrix) * sizeof(double));
     }
     r.src = 0;
-    if (pos + 1 >= 0 && pos + 1 < (long)n)
+    if (pos + 1 >= 0 && pos + 1 < (long)n + (edge ? 1 : 0))
     {
-      const FusedOp & f = plan[pos + 1];
-      r.gather_off = table_of[pos + 1];
-      r.flags |= (f.kind == 0 ? 2u : f.kind == 1 ? 1u : 0u) << PLLHIP_FUSED_STAGE_SHIFT;
+      const FusedOp & f = pos + 1 < (long)n ? plan[pos + 1] : edge->op;
+      r.gather_off = pos + 1 < (long)n ? table_of[pos + 1] : 0u;
+      r.flags |= (f.kind == 0 ? 2u : (f.kind == 1 || f.kind == PLLHIP_FUSED_KIND_EDGE) ? 1u : 0u) << PLLHIP_FUSED_STAGE_SHIFT;
       if (f.dma_flags)
       {
         if (srcs.size() >= 0xffffu) return 1;
@@ -1751,6 +1993,20 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   }
   rs[n + 2] = rs[n + 1]; // (loaded by the last op, never used)
   rs[n + 2].flags &= ~PLLHIP_FUSED_RELOAD_NEXT;
+  if (edge)
+  {
+    // ... but by the edge epilogue: where the two CLVs and their counts are
+    FusedRec & e = rs[n + 2];
+    const FusedOp & f = edge->op;
+    if (f.lslot < 0 || f.rslot < 0) return 1;
+    memset(&e, 0, sizeof(e));
+    if (f.lsc_slot >= 0) e.flags |= PLLHIP_FUSED_LCNT;
+    if (f.rsc_slot >= 0) e.flags |= PLLHIP_FUSED_RCNT;
+    e.lslot_b = (unsigned short)(f.lslot * slot_bytes);
+    e.rslot_b = (unsigned short)(f.rslot * slot_bytes);
+    e.lcnt_b = (unsigned short)((f.lsc_slot > 0 ? f.lsc_slot : 0) * count_bytes);
+    e.rcnt_b = (unsigned short)((f.rsc_slot > 0 ? f.rsc_slot : 0) * count_bytes);
+  }
   } // segments
   // the kept tables T of the cherries this list defers: written straight into their places in the pool
   if (keep_jobs) jobs.insert(jobs.end(), keep_jobs->begin(), keep_jobs->end());
@@ -1810,6 +2066,7 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   c->fused_last_nslots = nslots;
   c->fused_last_mode = mode;
   c->fused_last_epoch = c->layout_epoch;
+  c->fused_last_edge = edge != nullptr;
   return pllhip_relaunch_fused(c);
 }
 
@@ -1841,9 +2098,9 @@ int pllhip_relaunch_fused(pllhip_ctx * c)
   }
   switch (c->sh.rate_cats)
   {
-    case 1: return launch_fused_rc<1>(c, d_plan, bases, count, nslots, mode);
-    case 2: return launch_fused_rc<2>(c, d_plan, bases, count, nslots, mode);
-    case 8: return launch_fused_rc<8>(c, d_plan, bases, count, nslots, mode);
-    default: return launch_fused_rc<4>(c, d_plan, bases, count, nslots, mode);
+    case 1: return launch_fused_rc<1>(c, d_plan, bases, count, nslots, mode, c->fused_last_edge);
+    case 2: return launch_fused_rc<2>(c, d_plan, bases, count, nslots, mode, c->fused_last_edge);
+    case 8: return launch_fused_rc<8>(c, d_plan, bases, count, nslots, mode, c->fused_last_edge);
+    default: return launch_fused_rc<4>(c, d_plan, bases, count, nslots, mode, c->fused_last_edge);
   }
 }

@@ -86,6 +86,7 @@ static_assert(sizeof(FusedRec) == 64, "sixteen words per op");
 #define PLLHIP_FUSED_RCNT 32u
 #define PLLHIP_FUSED_STAGE_SHIFT 6     /* two bits: matrices op + 1 needs (2 both, 1 right only, 0 none) */
 #define PLLHIP_FUSED_RELOAD_NEXT 256u  /* op + 1 reloads operands: FusedSrc number `src` */
+#define PLLHIP_FUSED_KIND_EDGE 4        /* FusedOp::kind of the edge pseudo-op (never in a record's kind bits) */
 #define PLLHIP_FUSED_MAX_OPS 60000u    /* longer lists run per level */
 // FusedRec::chars -- a wave holds the characters of up to 1024 / (tile sites) tip rows at its tile, 16 bytes per
 // lane, fetched with ONE load per tile (rows in the order the list uses them; lists with more tip operands fetch
@@ -156,6 +157,15 @@ struct FusedBases
   const FusedSeg * segs;             // [nsegs] (nsegs == 1: not read, the kernel's own arguments say it all)
   unsigned int nsegs;
 };
+// what the edge epilogue of the list kernel reads and writes (EDGE instantiations only)
+struct FusedEdgeArgs
+{
+  const double * freqs;                  // [rate_matrices][4]
+  const double * rate_weights;           // [rate_cats]
+  const unsigned int * pattern_weights;  // [sites + slack]
+  double * terms;                        // [sites + PLLHIP_TAIL_SITES]: weighted per-site lnL of the edge
+  unsigned int freqs_off[4];             // byte offsets of each category's frequencies in `freqs`
+};
 
 // (The planner is host logic and needs no device: what it must know of the partition is here.)
 struct FusedGeom
@@ -168,13 +178,27 @@ struct FusedGeom
   bool is_tip(unsigned int clv_index) const { return (pattern_tip && clv_index < tips) || (as_tip && as_tip[clv_index]); }
 };
 
+// The edge evaluation a list launch also computes the per-site terms of (pllhip_ctx::edge_hint): a pseudo-op at
+// position `count` that reads the two CLVs and their counts and writes no CLV.  In: the request resolved into
+// addresses.  Out (pllhip_fused_plan): where the kernel finds the operands when the op loop has ended.
+struct FusedEdge
+{
+  unsigned int parent_clv, child_clv;
+  int parent_scaler, child_scaler;
+  const double * parent, * child;          // the two CLVs in HBM
+  const unsigned int * pscaler, * cscaler; // their scale buffers, nullptr none
+  const double * pmat;                     // the edge's P-matrix
+  FusedOp op;                              // out: lslot / rslot, lsc_slot / rsc_slot, what is reloaded (parent "left", child "right")
+};
+
 // Order the list, assign slots.  args/kinds are resolve_op's results per op.  Returns 0 and
 // fills plan (one entry per op, in the order the kernel runs them) and *reloads (operands copied
 // back from HBM), 1 if the list is of a shape the kernel does not take (the caller then
 // launches per level), < 0 on error.
 int pllhip_fused_plan(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args,
                       const int * kinds, unsigned int count, unsigned int nslots,
-                      std::vector<FusedOp> & plan, unsigned int * reloads, const FusedExtra * extra = nullptr);
+                      std::vector<FusedOp> & plan, unsigned int * reloads, const FusedExtra * extra = nullptr,
+                      FusedEdge * edge = nullptr);
 
 // Which tip-tip ops of a list are DEFERRED (not run) and what must be materialised before the list.
 // Pure host logic on indices (tests/test_host_deferred_plan.py through pllhip_fused_plan_dry_deferred).
@@ -191,6 +215,12 @@ struct FusedDeferral
 void pllhip_fused_deferral(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
                            const unsigned char * old_deferred, const int * old_scaler, const unsigned char * pinned,
                            FusedDeferral & out);
+// May CLV `clv` be an end of the edge a list launch forms the terms of?  Only an ordinary CLV whose bytes are in HBM
+// when the list has run: no tip, no cherry the list defers or reads from a table (geom.as_tip), no CLV whose address
+// was handed out, and none that an earlier call left deferred -- unless this list stores it first (dd.materialise) or
+// overwrites it with an ordinary op (dd.dropped).  ONE rule for pllhip_update_partials and pllhip_fused_plan_dry_edge.
+bool pllhip_fused_edge_end_stored(const FusedGeom & geom, const FusedDeferral & dd, unsigned int clv,
+                                  bool deferred_before, bool pinned);
 unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int workgroups_per_cu);
 // The list as up to `max_segments` independent sub-lists of at least two ops each: seg_of[i] = segment of op i
 // (segment 0 the longest; ops keep their relative order within a segment).  Components -- ops connected through a
@@ -200,7 +230,7 @@ unsigned int pllhip_fused_segments(const FusedGeom & geom, const pllhip_op_t * o
                                    unsigned int max_segments, std::vector<unsigned int> & seg_of);
 // one plan per segment (pllhip_fused_plan of its sub-list)
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
-                        const std::vector<FusedPairJob> * keep_jobs = nullptr);
+                        const std::vector<FusedPairJob> * keep_jobs = nullptr, const FusedEdge * edge = nullptr);
 int pllhip_relaunch_fused(pllhip_ctx * c); // the same op list as in the previous whole-list call of this context
 
 #endif

@@ -193,6 +193,7 @@ extern "C" int pllhip_update_pmatrices(pllhip_ctx_t * c, const unsigned int * h_
                                        const unsigned int * h_matrix_indices,
                                        const double * h_branch_lengths, unsigned int count)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS_PAR(c, pllhip_update_pmatrices(s, h_params_indices, h_matrix_indices, h_branch_lengths, count));
   if (!count) return 0;
   HIP_TRY(hipSetDevice(c->sh.device));

@@ -390,6 +390,7 @@ extern "C" int pllhip_site_posteriors(pllhip_ctx_t * c, const pllhip_posterior_e
                                       unsigned char * h_best_state, double * h_best_prob, double * h_rate_probs,
                                       double * h_site_rates)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!E || !h_freqs_indices || !count ||
       !(h_state_probs || h_best_state || h_best_prob || h_rate_probs || h_site_rates))
   {

@@ -353,6 +353,7 @@ extern "C" int pllhip_identify_repeats(pllhip_ctx_t * c, unsigned int parent, un
                                        unsigned int child2, unsigned int max_classes,
                                        unsigned int * classes_out)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   if (!c->shards.empty())
   {
     // One partition over several devices (round 4): every shard identifies the classes of ITS site range -- two

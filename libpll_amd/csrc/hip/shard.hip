@@ -273,6 +273,7 @@ extern "C" int pllhip_ctx_create_sharded(const pllhip_shape_t * shape, const int
       return rc;
     }
     s->shard_poll = shard_poll;
+    s->is_shard = true; // (no edge epilogue on a shard: ctx.hpp, edge_hint)
     g->shards.push_back(s);
     g->shard_lo.push_back(lo[i]);
   }

@@ -761,6 +761,7 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
                                          const unsigned int * params, int route, int max_slots, size_t budget,
                                          double * h_lnl)
 {
+  pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   const char * what = "pllhip_tree_loglikelihood";
   if (!C || !params || !count || !h_lnl)
   {

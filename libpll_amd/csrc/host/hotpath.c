@@ -24,6 +24,7 @@ void pll_update_partials(pll_partition_t * p, const pll_operation_t * ops, unsig
   /* (mirror mode switched on after the partition was created: every CLV is read back after each call, so deferring
      the cherries would only add a launch -- a no-op once it is off) */
   if (pll_amd_mirror_mode) (void)pllhip_set_deferral(q->ctx, 0);
+  if (pll_amd_mirror_mode) (void)pllhip_set_edge_fold(q->ctx, 0);
   if (q->rep)
   {
     /* site repeats: identification and execution interleave (repeats.c) */

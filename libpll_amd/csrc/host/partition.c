@@ -445,6 +445,8 @@ pll_partition_t * pll_partition_create(unsigned int tips, unsigned int clv_buffe
    * kernel never runs (site repeats), or where there are no tip-tip ops to defer (tips as CLVs) */
   if (PLL_AMD_MIRRORS(p) || (attributes & PLL_ATTRIB_SITE_REPEATS) || !(attributes & PLL_ATTRIB_PATTERN_TIP))
     (void)pllhip_set_deferral(q->ctx, 0);
+  /* the edge epilogue of the whole-list launch (pllhip.h): not on a host-mirroring partition */
+  if (PLL_AMD_MIRRORS(p)) (void)pllhip_set_edge_fold(q->ctx, 0);
   if ((attributes & PLL_ATTRIB_SITE_REPEATS) && !pll_amd_repeats_alloc(q))
   {
     pll_partition_destroy(p);
@@ -781,6 +783,33 @@ int pll_amd_sync_scaler(pll_partition_t * p, unsigned int idx)
   return PLL_SUCCESS;
 }
 
+int pll_amd_push_clv(pll_partition_t * p, unsigned int idx)
+{
+  pll_amd_partition_t * q = pll_amd_priv(p);
+  int rc;
+  if (idx >= p->tips + p->clv_buffers || ((p->attributes & PLL_ATTRIB_PATTERN_TIP) && idx < p->tips) ||
+      !p->clv[idx] || q->rep)
+  {
+    pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "CLV index %u has no host mirror to upload", idx);
+    return PLL_FAILURE;
+  }
+  if ((rc = pllhip_put_clv(q->ctx, idx, p->clv[idx]))) return pll_amd_fail_hip(rc, "CLV upload");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_push_scaler(pll_partition_t * p, unsigned int idx)
+{
+  pll_amd_partition_t * q = pll_amd_priv(p);
+  int rc;
+  if (idx >= p->scale_buffers || !p->scale_buffer[idx] || q->rep)
+  {
+    pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "Scaler index %u has no host mirror to upload", idx);
+    return PLL_FAILURE;
+  }
+  if ((rc = pllhip_put_scaler(q->ctx, idx, p->scale_buffer[idx]))) return pll_amd_fail_hip(rc, "scaler upload");
+  return PLL_SUCCESS;
+}
+
 int pll_amd_sync_pmatrix(pll_partition_t * p, unsigned int idx)
 {
   int rc;
@@ -868,6 +897,21 @@ int pll_amd_set_deferral(pll_partition_t * p, int on)
 {
   int rc = pllhip_set_deferral(pll_amd_priv(p)->ctx, on);
   if (rc) return pll_amd_fail_hip(rc, "set deferral");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_set_edge_fold(pll_partition_t * p, int on)
+{
+  /* (host mirrors: every CLV is read back after each call, and the mirrors are what clients read) */
+  int rc = pllhip_set_edge_fold(pll_amd_priv(p)->ctx, (on && !PLL_AMD_MIRRORS(p) && !pll_amd_mirror_mode) ? 1 : 0);
+  if (rc) return pll_amd_fail_hip(rc, "set edge fold");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_edge_fold_stats(pll_partition_t * p, unsigned long long * stats4)
+{
+  int rc = pllhip_edge_fold_stats(pll_amd_priv(p)->ctx, stats4);
+  if (rc) return pll_amd_fail_hip(rc, "edge fold stats");
   return PLL_SUCCESS;
 }
 

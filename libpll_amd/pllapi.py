@@ -280,6 +280,11 @@ class PllLibrary:
                 lib.pll_amd_set_deferral.argtypes = [_PP, C.c_int]
                 lib.pll_amd_dev_clv.argtypes = [_PP, C.c_uint]
                 lib.pll_amd_dev_clv.restype = C.c_void_p
+            if hasattr(lib, "pll_amd_set_edge_fold"):
+                lib.pll_amd_set_edge_fold.argtypes = [_PP, C.c_int]
+                lib.pll_amd_edge_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
+                lib.pll_amd_push_clv.argtypes = [_PP, C.c_uint]
+                lib.pll_amd_push_scaler.argtypes = [_PP, C.c_uint]
             if hasattr(lib, "pll_amd_write_ceiling"):   # (older builds under PLL_AMD_LIB: tools/list_time.py)
                 lib.pll_amd_write_ceiling.argtypes = [_PP, C.c_void_p, C.c_uint, C.c_uint, C.POINTER(C.c_float),
                                                       C.POINTER(C.c_double)]
@@ -864,6 +869,19 @@ class Partition:
             self._check(self.lib.pll_amd_sync_scaler(self.ptr, idx), "pll_amd_sync_scaler")
         return np.ctypeslib.as_array(self.s.scale_buffer[idx], shape=(self.scaler_len,)).copy()
 
+    def put_clv(self, idx, values):
+        """overwrite a CLV on the device with `values` (flat, the layout get_clv's mirror has; pll_amd_push_clv)"""
+        self._check(self.lib.pll_amd_sync_clv(self.ptr, idx), "pll_amd_sync_clv")
+        n = self.sites_total * self.s.rate_cats * self.s.states_padded
+        np.ctypeslib.as_array(self.s.clv[idx], shape=(n,))[:] = np.asarray(values, dtype=np.float64).reshape(-1)
+        self._check(self.lib.pll_amd_push_clv(self.ptr, idx), "pll_amd_push_clv")
+
+    def put_scaler(self, idx, values):
+        """overwrite a scale buffer on the device (pll_amd_push_scaler)"""
+        self._check(self.lib.pll_amd_sync_scaler(self.ptr, idx), "pll_amd_sync_scaler")
+        np.ctypeslib.as_array(self.s.scale_buffer[idx], shape=(self.scaler_len,))[:] = np.asarray(values, dtype=np.uint32)
+        self._check(self.lib.pll_amd_push_scaler(self.ptr, idx), "pll_amd_push_scaler")
+
     def get_pmatrix(self, idx):
         if self.o.is_amd:
             self._check(self.lib.pll_amd_sync_pmatrix(self.ptr, idx), "pll_amd_sync_pmatrix")
@@ -925,6 +943,16 @@ class Partition:
     def set_deferral(self, on):
         """False: every tip-tip op of a 4-state whole-list launch is run and stored (the eager path)."""
         self._check(self.lib.pll_amd_set_deferral(self.ptr, 1 if on else 0), "pll_amd_set_deferral")
+
+    def set_edge_fold(self, on):
+        """False: the whole-list launch never forms edge lnL terms; every evaluation reads both CLVs (pll_amd.h)."""
+        self._check(self.lib.pll_amd_set_edge_fold(self.ptr, 1 if on else 0), "pll_amd_set_edge_fold")
+
+    def edge_fold_stats(self):
+        """[lists with the epilogue, evaluations from terms, terms dropped unused, evaluations by the lnL kernel]"""
+        buf = (C.c_ulonglong * 4)()
+        self._check(self.lib.pll_amd_edge_fold_stats(self.ptr, buf), "pll_amd_edge_fold_stats")
+        return [int(v) for v in buf]
 
     def dev_clv(self, idx):
         """device address of a CLV (pll_amd_dev_clv); the CLV is stored if deferred and pinned eager from then on"""
