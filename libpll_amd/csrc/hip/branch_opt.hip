@@ -5,7 +5,7 @@
 // (the rule is written out in include/pll_amd.h).  Per chunk of branches:
 //
 //   sumtables    k_build_sumtable_mats once (the matrices depend on params_indices only), then every branch's table
-//                through the partition's own batched CLV kernels (pllhip_launch_partials_batch) into scratch, in the
+//                through the partition's own batched CLV kernels (pllhip_batch_run_ops) into scratch, in the
 //                arrangement of pllhip_update_sumtable (derivatives.hip) -- the table the single call would build;
 //                per-rate scale buffers: k_bo_rescale, k_sumtable_rescale's arithmetic for every table of the chunk;
 //   pass         k_bo_pass: per (site tile, branch) the branch's [R][S] exponentials and their two t-derivatives in
@@ -20,8 +20,8 @@
 // The (pass, step) pairs are plain launches back to back on the partition's stream; the host looks at a device count
 // of the branches still active every BO_CHECK steps, never per step or branch.
 //
-// Determinism: tiles are BO_TILE sites, a branch's partial sums depend on nothing but its own table and length, and
-// every sum runs in a fixed order: a branch's result does not depend on the batch, its order or the chunking.
+// Determinism: tiles are PLLHIP_BATCH_TILE sites, a branch's partial sums depend on nothing but its own table and
+// length, and every sum runs in a fixed order: a branch's result does not depend on the batch, its order or the chunking.
 #include "branch_opt.hpp"
 
 #include <algorithm>
@@ -73,9 +73,9 @@ __global__ __launch_bounds__(256) void k_bo_pass(BoPassArgs a)
     const double t = sb->t;
     for (unsigned int i = tid; i < R * S; i += 256u)
     {
-      const unsigned int k = i / S, j = i - k * S, pi = a.params[k];
+      const unsigned int k = i / S, j = i - k * S, pi = a.m.params[k];
       const double ev = a.eigenvals[(size_t)pi * S + j];
-      const double ki = a.rates[k] / (1.0 - a.prop_invar[pi]);
+      const double ki = a.rates[k] / (1.0 - a.m.prop_invar[pi]);
       const double x = exp(ev * ki * t);
       double * d = s_diag + k * DP + j * 3u;
       d[0] = x;
@@ -91,14 +91,14 @@ __global__ __launch_bounds__(256) void k_bo_pass(BoPassArgs a)
   const unsigned int g = lane / R, k = lane - g * R, grp0 = g * R;
   const unsigned int own_round = lane / spr;
   const int own_src = (int)((lane - own_round * spr) * R);
-  const unsigned int pi = a.params[k];
-  const double pinv = a.prop_invar[pi];
-  const double w = a.rate_weights[k];
-  const size_t first = (size_t)tile * BO_TILE;
-  const size_t end = std::min<size_t>(first + BO_TILE, a.sites);
+  const unsigned int pi = a.m.params[k];
+  const double pinv = a.m.prop_invar[pi];
+  const double w = a.m.rate_weights[k];
+  const size_t first = (size_t)tile * PLLHIP_BATCH_TILE;
+  const size_t end = std::min<size_t>(first + PLLHIP_BATCH_TILE, a.sites);
   const BoSides sd = a.sides[b];
   double acc0 = 0.0, acc1 = 0.0;
-  for (unsigned int blk = wave; blk < BO_TILE / 64u; blk += 4u)
+  for (unsigned int blk = wave; blk < PLLHIP_BATCH_TILE / 64u; blk += 4u)
   {
     const size_t sbase = first + (size_t)blk * 64u;
     if (sbase >= end) break;
@@ -153,8 +153,8 @@ __global__ __launch_bounds__(256) void k_bo_pass(BoPassArgs a)
       if (pinv > 0.0)
       {
         // core_derivatives.c:481-491
-        const int inv = a.invariant ? a.invariant[n] : -1;
-        const double inv_lk = (inv == -1) ? 0.0 : a.freqs[(size_t)pi * S + inv] * pinv;
+        const int inv = a.m.invariant ? a.m.invariant[n] : -1;
+        const double inv_lk = (inv == -1) ? 0.0 : a.m.freqs[(size_t)pi * S + inv] * pinv;
         c0 = c0 * (1.0 - pinv) + inv_lk;
         c1 = c1 * (1.0 - pinv);
         c2 = c2 * (1.0 - pinv);
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void k_bo_pass(BoPassArgs a)
     const size_t n = sbase + lane;
     if (n < end)
     {
-      const double pw = (double)a.pattern_weights[n];
+      const double pw = (double)a.m.pattern_weights[n];
       if (a.lnl)
       {
         // the scaler term of the edge-lnL kernels: per site the two counts; per rate the smallest sum of the
@@ -301,11 +301,6 @@ __global__ __launch_bounds__(64) void k_bo_finish(const double * __restrict__ pa
   if (threadIdx.x == 0) lnl[b] = f;
 }
 
-static size_t bo_align(size_t b)
-{
-  return (b + 255) & ~(size_t)255;
-}
-
 static int bo_launch_pass(pllhip_ctx * c, const BoPassArgs & a, unsigned int nb)
 {
   const dim3 grid(a.tiles, nb);
@@ -329,6 +324,32 @@ int pllhip_bo_rescale(pllhip_ctx * c, double * tables, const BoSides * sides, un
                                                     c->sh.rate_cats, c->sh.states);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+
+void pllhip_bo_pass_args(const pllhip_ctx * c, const unsigned int * params, BoPassArgs & pa)
+{
+  memset(&pa, 0, sizeof(pa));
+  pa.eigenvals = c->eigenvals;
+  pa.rates = c->rates;
+  pllhip_batch_model(c, params, pa.m);
+  pa.table_stride = c->clv_stride;
+  pa.sites = (unsigned int)c->sh.sites;
+  pa.states = c->sh.states;
+  pa.rate_cats = c->sh.rate_cats;
+  pa.tiles = pllhip_batch_tiles(c);
+}
+
+BoState pllhip_bo_start(double length, double min_length, double max_length)
+{
+  BoState s;
+  s.t = std::min(std::max(length, min_length), max_length);
+  s.lo = min_length;
+  s.hi = max_length;
+  s.evals = 1;
+  s.status = PLLHIP_BRANCH_MAX_ITERS;
+  s.active = 1;
+  s.pad = 0;
+  return s;
 }
 
 int pllhip_bo_newton(pllhip_ctx * c, BoPassArgs & pa, const BoBuffers & bf, unsigned int nb, double tolerance,
@@ -384,13 +405,9 @@ extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_bra
     pllhip_set_error("pllhip_optimize_branch_lengths: empty batch or NULL array");
     return -1;
   }
-  if (!c->shards.empty() || c->comm || c->asc_type || !c->rows.empty())
-  {
-    pllhip_set_error("pllhip_optimize_branch_lengths: not for sharded, RCCL-joined, asc-bias or site-repeat "
-                     "partitions");
-    return -3;
-  }
-  HIP_TRY(hipSetDevice(c->sh.device));
+  const char * what = "pllhip_optimize_branch_lengths";
+  int rc = pllhip_batch_open(c, what, BATCH_PLAIN_ONLY, params);
+  if (rc) return rc;
   const unsigned int nodes = (unsigned int)c->clv.size();
   const int nsc = (int)c->sh.scale_buffers;
   const unsigned int S = c->sh.states, R = c->sh.rate_cats;
@@ -401,12 +418,6 @@ extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_bra
     pllhip_set_error("pllhip_optimize_branch_lengths: bounds, tolerance or max_iters out of range");
     return -1;
   }
-  for (unsigned int k = 0; k < R; ++k)
-    if (params[k] >= c->sh.rate_matrices)
-    {
-      pllhip_set_error("pllhip_optimize_branch_lengths: params index %u out of range", params[k]);
-      return -1;
-    }
   for (unsigned int i = 0; i < count; ++i)
   {
     const pllhip_branch_t & e = B[i];
@@ -429,11 +440,6 @@ extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_bra
       return -1;
     }
   }
-  if (S != 4 && c->maxstates == 0 && c->sh.pattern_tip)
-  {
-    pllhip_set_error("pllhip_optimize_branch_lengths: tipmap not uploaded");
-    return -1;
-  }
   if ((size_t)R * (3u * S + 1u) * sizeof(double) > 65536 - 64)
   {
     pllhip_set_error("pllhip_optimize_branch_lengths: %u states x %u rate categories: the exponentials of a branch "
@@ -444,40 +450,27 @@ extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_bra
   PLLHIP_DEFERRED_FLUSH(c); // (deferred cherries get their bytes before anything but a list kernel touches them)
 
   // ---- chunk size: everything one chunk needs within `budget` bytes (one branch at least)
-  const size_t sites = c->sh.sites;
-  const unsigned int tiles = (unsigned int)((sites + BO_TILE - 1) / BO_TILE);
+  const unsigned int tiles = pllhip_batch_tiles(c);
   const size_t per_branch = c->clv_stride * 8 + sizeof(BoState) + sizeof(BoSides) + (size_t)tiles * 16 + 8 + 4 * 256;
   const size_t fixed = 2 * c->pmat_elems * 8 + 4096;
   size_t room = budget > fixed ? (budget - fixed) / per_branch : 0;
   const unsigned int nc = (unsigned int)std::min<size_t>(std::max<size_t>(room, 1), std::min<size_t>(count, 65535));
 
   // ---- scratch layout
-  size_t off = 0;
-  const size_t o_mats = off;   off += bo_align(2 * c->pmat_elems * 8);
-  const size_t o_tab = off;    off += bo_align((size_t)nc * c->clv_stride * 8);
-  const size_t o_state = off;  off += bo_align((size_t)nc * sizeof(BoState));
-  const size_t o_sides = off;  off += bo_align((size_t)nc * sizeof(BoSides));
-  const size_t o_part = off;   off += bo_align((size_t)nc * tiles * 16);
-  const size_t o_lnl = off;    off += bo_align((size_t)nc * 8);
-  const size_t o_cnt = off;    off += bo_align(4);
-  if (off > c->bo_scratch_bytes)
-  {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->bo_scratch) HIP_TRY(hipFree(c->bo_scratch));
-    c->bo_scratch = nullptr;
-    c->bo_scratch_bytes = 0;
-    if (hipMalloc(&c->bo_scratch, off) != hipSuccess)
-    {
-      (void)hipGetLastError();
-      c->bo_scratch = nullptr;
-      pllhip_set_error("pllhip_optimize_branch_lengths: no device memory for a chunk (%zu bytes)", off);
-      return -2;
-    }
-    // zeros: the slack behind every scratch table, as behind the partition's own (PLLHIP_TAIL_SITES)
-    HIP_TRY(hipMemsetAsync(c->bo_scratch, 0, off, c->stream));
-    c->bo_scratch_bytes = off;
-  }
-  char * base = (char *)c->bo_scratch;
+  BatchLayout L;
+  const size_t o_mats = L.take(2 * c->pmat_elems * 8);
+  const size_t o_tab = L.take((size_t)nc * c->clv_stride * 8);
+  const size_t o_state = L.take((size_t)nc * sizeof(BoState));
+  const size_t o_sides = L.take((size_t)nc * sizeof(BoSides));
+  const size_t o_part = L.take((size_t)nc * tiles * 16);
+  const size_t o_lnl = L.take((size_t)nc * 8);
+  const size_t o_cnt = L.take(4);
+  BatchScratch & scratch = c->batch_scratch[BATCH_BRANCH_OPT];
+  bool grew;
+  if ((rc = pllhip_batch_scratch_grow(c, scratch, L.off, what, &grew))) return rc;
+  // zeros: the slack behind every scratch table, as behind the partition's own (PLLHIP_TAIL_SITES)
+  if (grew) HIP_TRY(hipMemsetAsync(scratch.p, 0, L.off, c->stream));
+  char * base = (char *)scratch.p;
   double * d_left = (double *)(base + o_mats), * d_right = d_left + c->pmat_elems;
   double * d_tab = (double *)(base + o_tab);
   BoState * d_state = (BoState *)(base + o_state);
@@ -486,38 +479,25 @@ extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_bra
   double * d_lnl = (double *)(base + o_lnl);
   unsigned int * d_cnt = (unsigned int *)(base + o_cnt);
 
-  int rc = pllhip_sumtable_mats_to(c, params, d_left, d_right);
-  if (rc) return rc;
+  if ((rc = pllhip_sumtable_mats_to(c, params, d_left, d_right))) return rc;
 
   BoPassArgs pa;
-  memset(&pa, 0, sizeof(pa));
+  pllhip_bo_pass_args(c, params, pa);
   pa.tables = d_tab;
   pa.st = d_state;
   pa.sides = d_sides;
-  pa.eigenvals = c->eigenvals;
-  pa.rates = c->rates;
-  pa.prop_invar = c->prop_invar;
-  pa.rate_weights = c->rate_weights;
-  pa.freqs = c->freqs;
-  pa.pattern_weights = c->pattern_weights;
-  pa.invariant = c->any_prop_invar ? c->invariant : nullptr;
   pa.partial = d_part;
-  pa.table_stride = c->clv_stride;
-  pa.sites = (unsigned int)sites;
-  pa.states = S;
-  pa.rate_cats = R;
-  pa.tiles = tiles;
   pa.rate_scalers = c->sh.rate_scalers;
-  for (unsigned int k = 0; k < R; ++k) pa.params[k] = params[k];
 
   std::vector<BoState> hs(nc);
   std::vector<BoSides> hsd(nc);
   std::vector<double> hl(nc);
+  std::vector<BatchOp> ops(nc);
   const BoBuffers bf = {d_state, d_part, d_lnl, d_cnt};
   for (unsigned int b0 = 0; b0 < count; b0 += nc)
   {
     const unsigned int nb = std::min(nc, count - b0);
-    // ---- the chunk's sumtables, batched by kind (pllhip_update_sumtable's arrangement)
+    // ---- the chunk's sumtables (pllhip_update_sumtable's arrangement)
     for (unsigned int i = 0; i < nb; ++i)
     {
       const pllhip_branch_t & e = B[b0 + i];
@@ -532,56 +512,15 @@ extern "C" int pllhip_optimize_branch_lengths(pllhip_ctx_t * c, const pllhip_bra
         hsd[i].ps = pllhip_scaler_ptr(c, e.parent_scaler_index);
         hsd[i].cs = pllhip_scaler_ptr(c, e.child_scaler_index);
       }
-      BoState & s = hs[i];
-      s.t = std::min(std::max(h_lengths[b0 + i], min_length), max_length);
-      s.lo = min_length;
-      s.hi = max_length;
-      s.evals = 1;
-      s.status = PLLHIP_BRANCH_MAX_ITERS;
-      s.active = 1;
-      s.pad = 0;
+      hs[i] = pllhip_bo_start(h_lengths[b0 + i], min_length, max_length);
+      ops[i].kind = pllhip_batch_fill_sumtable(c, ops[i].a, pllhip_batch_operand(c, e.parent_clv_index, -1, nullptr),
+                                               pllhip_batch_operand(c, e.child_clv_index, -1, nullptr), d_left, d_right,
+                                               d_tab + (size_t)i * c->clv_stride);
+      ops[i].mode = SCALE_NONE;
     }
     HIP_TRY(hipMemcpyAsync(d_sides, hsd.data(), nb * sizeof(BoSides), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_state, hs.data(), nb * sizeof(BoState), hipMemcpyHostToDevice, c->stream));
-    for (int kind = 0; kind < 2; ++kind)
-    {
-      PartialsBatch b;
-      unsigned int cnt = 0;
-      for (unsigned int i = 0; i <= nb; ++i)
-      {
-        if (i == nb || cnt == PLLHIP_BATCH_MAX)
-        {
-          if (cnt && (rc = pllhip_launch_partials_batch(c, b, cnt, kind, SCALE_NONE))) return rc;
-          cnt = 0;
-          if (i == nb) break;
-        }
-        const pllhip_branch_t & e = B[b0 + i];
-        const bool tp = pllhip_is_tip(c, e.parent_clv_index), tc = pllhip_is_tip(c, e.child_clv_index);
-        if ((tp || tc) != (kind == 1)) continue;
-        PartialsArgs & a = b.op[cnt++];
-        memset(&a, 0, sizeof(a));
-        a.parent = d_tab + (size_t)i * c->clv_stride;
-        a.tipmap = c->tipmap;
-        a.zero = c->d_zero;
-        a.sites = c->sh.sites;
-        a.rate_cats = R;
-        a.states = S;
-        a.maxstates = c->maxstates;
-        a.lmat = d_left;
-        a.rmat = d_right;
-        if (kind == 1)
-        {
-          // the tip supplies the pi-weighted left factor whichever side it is on (derivatives.hip)
-          a.ltip = pllhip_tip_ptr(c, tp ? e.parent_clv_index : e.child_clv_index);
-          a.right = c->clv[tp ? e.child_clv_index : e.parent_clv_index];
-        }
-        else
-        {
-          a.left = c->clv[e.parent_clv_index];
-          a.right = c->clv[e.child_clv_index];
-        }
-      }
-    }
+    if ((rc = pllhip_batch_run_ops(c, ops.data(), nb))) return rc;
     if (c->sh.rate_scalers && nsc > 0 && (rc = pllhip_bo_rescale(c, d_tab, d_sides, nb))) return rc;
     if ((rc = pllhip_bo_newton(c, pa, bf, nb, tolerance, max_iters, hs.data(), h_lnl ? hl.data() : nullptr)))
       return rc;

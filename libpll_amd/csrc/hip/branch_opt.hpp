@@ -2,9 +2,8 @@
 // state of a branch, the argument block of k_bo_pass, and the part of a chunk's work that starts once the sumtables
 // and the per-site scaler counts are in scratch.
 #pragma once
-#include "lnl_common.hpp"
+#include "batched.hpp"
 
-#define BO_TILE 256 // sites per workgroup of k_bo_pass (64 per wave); a branch's partial sums are per tile
 #define BO_CHECK 4   // Newton steps enqueued between two looks at the count of active branches
 
 struct BoState
@@ -31,17 +30,12 @@ struct BoPassArgs
   const BoSides * __restrict__ sides;      // [branches]
   const double * __restrict__ eigenvals;   // [rate_matrices][S]
   const double * __restrict__ rates;       // [R]
-  const double * __restrict__ prop_invar;  // [rate_matrices]
-  const double * __restrict__ rate_weights;
-  const double * __restrict__ freqs;
-  const unsigned int * __restrict__ pattern_weights;
-  const int * __restrict__ invariant;      // nullptr = no +I
+  BatchModel m;
   double * __restrict__ partial;           // [branches][tiles][2]
   size_t table_stride;
   unsigned int sites, states, rate_cats, tiles;
   int lnl;          // 0: (d, dd) of the active branches; 1: lnL of every branch (one component)
   int rate_scalers; // lnL pass: per-rate scale buffers
-  unsigned int params[PLLHIP_MAX_RATE_CATS];
 };
 
 // the buffers of one chunk (device): Newton states, partial sums [branches][tiles][2], lnL [branches], one counter
@@ -55,6 +49,10 @@ struct BoBuffers
 
 // per-rate scale buffers: every table of the chunk brought to its sites' smallest counts (k_bo_rescale)
 int pllhip_bo_rescale(pllhip_ctx * c, double * tables, const BoSides * sides, unsigned int nb);
+// everything of `pa` that does not depend on the chunk's scratch or the caller: the model, the shape, the tiles
+void pllhip_bo_pass_args(const pllhip_ctx * c, const unsigned int * params, BoPassArgs & pa);
+// the start state of a branch: its length clamped into the bounds
+BoState pllhip_bo_start(double length, double min_length, double max_length);
 // From "tables, sides and start states are in scratch" on: the (pass, step) pairs of the rule, the lnL pass at the
 // final lengths when h_lnl is not null, the states (and lnL) of the chunk's nb branches back on the host; waits for
 // the stream.  pa: everything but `lnl` filled in (tables, st, sides, partial point into the chunk's scratch).

@@ -590,11 +590,8 @@ extern "C" void pllhip_ctx_destroy(pllhip_ctx_t * c)
   if (c->cherry_pool_all) (void)hipFree(c->cherry_pool_all);
   if (c->split_verdicts) (void)hipFree(c->split_verdicts);
   if (c->root_counts) (void)hipFree(c->root_counts);
-  if (c->ins_scratch) (void)hipFree(c->ins_scratch);
-  if (c->bo_scratch) (void)hipFree(c->bo_scratch);
-  if (c->nni_scratch) (void)hipFree(c->nni_scratch);
-  if (c->tree_scratch) (void)hipFree(c->tree_scratch);
-  if (c->post_scratch) (void)hipFree(c->post_scratch);
+  for (BatchScratch & bs : c->batch_scratch)
+    if (bs.p) (void)hipFree(bs.p);
   pllhip_aa_fused_free(c);
   for (int b = 0; b < 2; ++b)
   {

@@ -18,6 +18,16 @@ struct ncclComm;
 
 struct pllhip_rep_work;
 
+// scratch of a batched call (batched.hpp): insertion -- P-matrices, insertion vectors, query vectors, partial sums;
+// branch lengths -- sumtables, Newton states, partial sums; posteriors -- edge descriptors and outputs; NNI and tree
+// scoring -- P-matrices, descriptors, partial sums and, where a route needs them, candidate CLVs, scale buffers, sumtables
+struct BatchScratch
+{
+  void * p = nullptr;
+  size_t bytes = 0;
+};
+enum { BATCH_INSERTION, BATCH_BRANCH_OPT, BATCH_POSTERIORS, BATCH_NNI, BATCH_TREE_SCORE, BATCH_FAMILIES };
+
 struct pllhip_ctx
 {
   pllhip_shape_t sh;
@@ -259,24 +269,9 @@ struct pllhip_ctx
   std::vector<pllhip_op_t> cert_ops;
   unsigned long long cert_stats[4] = {0, 0, 0, 0}; // lists launched with the test, trips, re-runs, uncertified
 
-  // insertion calls (insertion.hip): their scratch -- P-matrices, insertion vectors, query vectors, partial sums --,
-  // grown to what one chunk of a call needs and kept until the context goes
-  void * ins_scratch = nullptr;
-  size_t ins_scratch_bytes = 0;
-  // batched branch-length calls (branch_opt.hip): sumtables, Newton states and partial sums of one chunk, kept the same way
-  void * bo_scratch = nullptr;
-  size_t bo_scratch_bytes = 0;
-  // site-posterior calls (posteriors.hip): the edge descriptors and the outputs of one chunk, kept the same way
-  void * post_scratch = nullptr;
-  size_t post_scratch_bytes = 0;
-  // NNI calls (nni.hip): P-matrices, edge descriptors, partial sums and -- where a route needs them -- the
-  // candidates' CLVs, scale buffers and sumtables of one chunk, kept the same way
-  void * nni_scratch = nullptr;
-  size_t nni_scratch_bytes = 0;
-  // tree-scoring calls (tree_score.hip): the candidates' P-matrices, records, partial sums and -- on the general
-  // route -- their CLVs and scale buffers of one chunk, kept the same way
-  void * tree_scratch = nullptr;
-  size_t tree_scratch_bytes = 0;
+  // the batched calls (batched.hpp): one scratch per call family, grown to what one chunk of a call needs and kept
+  // until the context goes.  Apart on purpose: two families zero theirs only when it grows
+  BatchScratch batch_scratch[BATCH_FAMILIES];
 
   // optional per-launch timing (pllhip_profile_*): one event pair per launch
   bool profiling = false;

@@ -16,18 +16,17 @@
 //                its site and walks the queries -- a dot product of rates x states, the +I term, one log, the scaler
 //                term and the weight per pair-site (k_lnl_gen's arithmetic, likelihood.hip) -- and the workgroup adds
 //                its 256 sites per query in a fixed tree;
-//   reduction    k_ins_reduce adds a pair's tile sums in tile order.
+//   reduction    k_batch_reduce (batched.hip) adds a pair's tile sums in tile order.
 //
-// Determinism: the tiles are fixed by the site count (INS_TILE sites each), a pair's partial sums depend on nothing
-// but the pair, and every sum runs in a fixed order: a pair's value does not depend on the batch, its order or the
+// Determinism: the tiles (PLLHIP_BATCH_TILE sites) are fixed by the site count, a pair's partial sums depend on
+// nothing but the pair, and every sum runs in a fixed order: a pair's value does not depend on the batch, its order or the
 // chunking.  No atomics.
-#include "lnl_common.hpp"
+#include "batched.hpp"
 
 #include <algorithm>
 #include <cfloat>
 #include <vector>
 
-#define INS_TILE 256 // sites per workgroup of k_ins_score: a pair's partial sums are per tile of this many sites
 #define INS_QB 8     // queries per workgroup of k_ins_score
 
 struct InsQuery
@@ -42,17 +41,12 @@ struct InsScoreArgs
   const double * __restrict__ cvec;        // [edges][clv_stride]
   const unsigned int * __restrict__ cscal; // [edges][scaler_stride] or nullptr
   const InsQuery * __restrict__ queries;   // [nq]
-  const double * __restrict__ freqs;
-  const double * __restrict__ prop_invar;
-  const double * __restrict__ rate_weights;
-  const unsigned int * __restrict__ pattern_weights;
-  const int * __restrict__ invariant;
+  BatchModel m;
   double * __restrict__ partial;           // [nq][edges][tiles]
   size_t clv_stride, scaler_stride;
   unsigned int sites, states, rate_cats, rows;
   unsigned int nq, edges, tiles;
   int rate_scalers;
-  unsigned int freqs_indices[PLLHIP_MAX_RATE_CATS];
 };
 
 // table of a pattern-tip query: T[row][k][j] = sum over the states s of row's mask of P[k][j][s], in state order
@@ -109,13 +103,13 @@ __device__ __forceinline__ double ins_category(const InsScoreArgs & a, double t,
                                                unsigned int rel)
 {
   if (rel > 0) t *= scale_minlh(rel);
-  const unsigned int fi = a.freqs_indices[k];
-  const double pinv = a.prop_invar[fi];
-  const double w = a.rate_weights[k];
+  const unsigned int fi = a.m.params[k];
+  const double pinv = a.m.prop_invar[fi];
+  const double w = a.m.rate_weights[k];
   if (pinv > 0.0)
   {
-    const int inv = a.invariant ? a.invariant[n] : -1;
-    const double inv_lk = (inv == -1) ? 0.0 : a.freqs[(size_t)fi * a.states + inv];
+    const int inv = a.m.invariant ? a.m.invariant[n] : -1;
+    const double inv_lk = (inv == -1) ? 0.0 : a.m.freqs[(size_t)fi * a.states + inv];
     return w * (t * (1.0 - pinv) + inv_lk * pinv);
   }
   return t * w;
@@ -123,13 +117,13 @@ __device__ __forceinline__ double ins_category(const InsScoreArgs & a, double t,
 
 // ST / RT: compile-time states / rate categories (C_e (.) pi of the site in registers), 0 = read at run time
 template <int ST, int RT>
-__global__ __launch_bounds__(INS_TILE) void k_ins_score(InsScoreArgs a)
+__global__ __launch_bounds__(PLLHIP_BATCH_TILE) void k_ins_score(InsScoreArgs a)
 {
   constexpr bool FIXED = ST > 0 && RT > 0;
   constexpr int NREG = FIXED ? ST * RT : 1;
   const unsigned int S = FIXED ? (unsigned int)ST : a.states, R = FIXED ? (unsigned int)RT : a.rate_cats;
   const unsigned int tile = blockIdx.x, e = blockIdx.y, q0 = blockIdx.z * INS_QB;
-  const unsigned int n = tile * INS_TILE + threadIdx.x;
+  const unsigned int n = tile * PLLHIP_BATCH_TILE + threadIdx.x;
   const bool valid = n < a.sites;
   const double * ce = a.cvec + (size_t)e * a.clv_stride + (size_t)n * R * S;
   const unsigned int * es = a.cscal ? a.cscal + (size_t)e * a.scaler_stride : nullptr;
@@ -140,11 +134,12 @@ __global__ __launch_bounds__(INS_TILE) void k_ins_score(InsScoreArgs a)
 #pragma unroll
     for (int k = 0; k < RT; ++k)
 #pragma unroll
-      for (int j = 0; j < ST; ++j) cv[k * ST + j] = ce[k * ST + j] * a.freqs[(size_t)a.freqs_indices[k] * ST + j];
+      for (int j = 0; j < ST; ++j) cv[k * ST + j] = ce[k * ST + j] * a.m.freqs[(size_t)a.m.params[k] * ST + j];
   }
 
-  // per query: the lane's site, then the workgroup's sum -- wave trees, then the four waves in order
-  __shared__ double s_wave[INS_QB][INS_TILE / 64];
+  // per query: the lane's site, then the workgroup's sum -- wave trees, then the four waves in order (its own lines,
+  // not batch_tile_sum: INS_QB sums share one barrier, and a query's four waves are added by a loop from 0.0)
+  __shared__ double s_wave[INS_QB][PLLHIP_BATCH_TILE / 64];
   const unsigned int wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   for (unsigned int qi = 0; qi < INS_QB; ++qi)
   {
@@ -206,53 +201,36 @@ __global__ __launch_bounds__(INS_TILE) void k_ins_score(InsScoreArgs a)
       else
         for (unsigned int k = 0; k < R; ++k)
         {
-          const double * fr = a.freqs + (size_t)a.freqs_indices[k] * S;
+          const double * fr = a.m.freqs + (size_t)a.m.params[k] * S;
           double terma_r = 0.0;
           for (unsigned int j = 0; j < S; ++j) terma_r += ce[k * S + j] * fr[j] * vq[k * S + j];
           terma += ins_category(a, terma_r, k, n, rs[k]);
         }
       double lk = log(terma);
       if (site_scalings) lk += (double)site_scalings * log(PLLHIP_SCALE_THRESHOLD);
-      v = lk * (double)a.pattern_weights[n];
+      v = lk * (double)a.m.pattern_weights[n];
     }
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    v = batch_wave_sum(v);
     if (lane == 0) s_wave[qi][wave] = v;
   }
   __syncthreads();
   if (threadIdx.x < INS_QB && q0 + threadIdx.x < a.nq)
   {
     double t = 0.0;
-    for (unsigned int w = 0; w < INS_TILE / 64; ++w) t += s_wave[threadIdx.x][w];
+    for (unsigned int w = 0; w < PLLHIP_BATCH_TILE / 64; ++w) t += s_wave[threadIdx.x][w];
     a.partial[((size_t)(q0 + threadIdx.x) * a.edges + e) * a.tiles + tile] = t;
   }
-}
-
-// a pair's tile sums in tile order
-__global__ __launch_bounds__(256) void k_ins_reduce(const double * __restrict__ partial, double * __restrict__ out,
-                                                    size_t pairs, unsigned int tiles)
-{
-  const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  if (p >= pairs) return;
-  const double * t = partial + p * tiles;
-  double s = 0.0;
-  for (unsigned int i = 0; i < tiles; ++i) s += t[i];
-  out[p] = s;
-}
-
-static size_t ins_align(size_t b)
-{
-  return (b + 255) & ~(size_t)255;
 }
 
 static int ins_launch_score(pllhip_ctx * c, const InsScoreArgs & a, unsigned int qblocks)
 {
   const dim3 grid(a.tiles, a.edges, qblocks);
   const unsigned int S = c->sh.states, R = c->sh.rate_cats;
-  if (S == 4 && R == 4) k_ins_score<4, 4><<<grid, INS_TILE, 0, c->stream>>>(a);
-  else if (S == 4 && R == 1) k_ins_score<4, 1><<<grid, INS_TILE, 0, c->stream>>>(a);
-  else if (S == 20 && R == 4) k_ins_score<20, 4><<<grid, INS_TILE, 0, c->stream>>>(a);
-  else if (S == 20 && R == 1) k_ins_score<20, 1><<<grid, INS_TILE, 0, c->stream>>>(a);
-  else k_ins_score<0, 0><<<grid, INS_TILE, 0, c->stream>>>(a);
+  if (S == 4 && R == 4) k_ins_score<4, 4><<<grid, PLLHIP_BATCH_TILE, 0, c->stream>>>(a);
+  else if (S == 4 && R == 1) k_ins_score<4, 1><<<grid, PLLHIP_BATCH_TILE, 0, c->stream>>>(a);
+  else if (S == 20 && R == 4) k_ins_score<20, 4><<<grid, PLLHIP_BATCH_TILE, 0, c->stream>>>(a);
+  else if (S == 20 && R == 1) k_ins_score<20, 1><<<grid, PLLHIP_BATCH_TILE, 0, c->stream>>>(a);
+  else k_ins_score<0, 0><<<grid, PLLHIP_BATCH_TILE, 0, c->stream>>>(a);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -262,27 +240,13 @@ static int ins_run(pllhip_ctx * c, const pllhip_insertion_edge_t * E, unsigned i
                    const int * qsc, const double * plen, unsigned int nq, const unsigned int * params,
                    size_t budget, double * h_lnl)
 {
-  HIP_TRY(hipSetDevice(c->sh.device));
+  // everything again (the shim's own rule: a binding may call it directly); a shard of a group is served
+  const char * what = "pllhip_insertion_loglikelihood";
+  int rc = pllhip_batch_open(c, what, BATCH_PLAIN_ONLY & ~BATCH_NO_SHARDS, params);
+  if (rc) return rc;
   const unsigned int nodes = (unsigned int)c->clv.size();
   const int nsc = (int)c->sh.scale_buffers;
   const unsigned int S = c->sh.states, R = c->sh.rate_cats;
-  // everything again (the shim's own rule: a binding may call it directly)
-  if (c->asc_type || !c->rows.empty() || c->comm)
-  {
-    pllhip_set_error("pllhip_insertion_loglikelihood: not for asc-bias, site-repeat or RCCL-joined partitions");
-    return -3;
-  }
-  if (S != 4 && c->maxstates == 0 && c->sh.pattern_tip)
-  {
-    pllhip_set_error("pllhip_insertion_loglikelihood: tipmap not uploaded");
-    return -1;
-  }
-  for (unsigned int k = 0; k < R; ++k)
-    if (params[k] >= c->sh.rate_matrices)
-    {
-      pllhip_set_error("pllhip_insertion_loglikelihood: params index %u out of range", params[k]);
-      return -1;
-    }
   bool any_tipq = false, any_clvq = false;
   for (unsigned int i = 0; i < nq; ++i)
   {
@@ -310,7 +274,7 @@ static int ins_run(pllhip_ctx * c, const pllhip_insertion_edge_t * E, unsigned i
 
   // ---- chunk sizes: everything one chunk needs within `budget` bytes (one pair at least)
   const size_t sites = c->sh.sites;
-  const unsigned int tiles = (unsigned int)((sites + INS_TILE - 1) / INS_TILE);
+  const unsigned int tiles = pllhip_batch_tiles(c);
   const unsigned int rows = (S == 4) ? 16u : (c->maxstates ? c->maxstates : 1u);
   const size_t table_elems = (size_t)rows * R * S;
   const size_t qslot = std::max(any_tipq ? table_elems : (size_t)0, any_clvq ? c->clv_stride : (size_t)0);
@@ -332,34 +296,22 @@ static int ins_run(pllhip_ctx * c, const pllhip_insertion_edge_t * E, unsigned i
   }
 
   // ---- scratch layout
-  size_t off = 0;
-  const size_t o_pm = off;     off += ins_align(((size_t)2 * ec + qc) * c->pmat_elems * 8);
-  const size_t o_cvec = off;   off += ins_align((size_t)ec * c->clv_stride * 8);
-  const size_t o_cscal = off;  off += scaled ? ins_align((size_t)ec * c->scaler_stride * 4) : 0;
-  const size_t o_qvec = off;   off += ins_align((size_t)qc * qslot * 8 + 8);
-  const size_t o_qdesc = off;  off += ins_align((size_t)qc * sizeof(InsQuery));
-  const size_t o_qsrc = off;   off += ins_align((size_t)qc * sizeof(double *));
-  const size_t o_slots = off;  off += ins_align((size_t)qc * 4);
-  const size_t o_part = off;   off += ins_align((size_t)qc * ec * tiles * 8);
-  const size_t o_out = off;    off += ins_align((size_t)qc * ec * 8);
-  if (off > c->ins_scratch_bytes)
-  {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->ins_scratch) HIP_TRY(hipFree(c->ins_scratch));
-    c->ins_scratch = nullptr;
-    c->ins_scratch_bytes = 0;
-    if (hipMalloc(&c->ins_scratch, off) != hipSuccess)
-    {
-      (void)hipGetLastError();
-      c->ins_scratch = nullptr;
-      pllhip_set_error("pllhip_insertion_loglikelihood: no device memory for a chunk (%zu bytes)", off);
-      return -2;
-    }
-    // zeros: the slack behind every scratch CLV, as behind the partition's own (PLLHIP_TAIL_SITES)
-    HIP_TRY(hipMemsetAsync(c->ins_scratch, 0, off, c->stream));
-    c->ins_scratch_bytes = off;
-  }
-  char * base = (char *)c->ins_scratch;
+  BatchLayout L;
+  const size_t o_pm = L.take(((size_t)2 * ec + qc) * c->pmat_elems * 8);
+  const size_t o_cvec = L.take((size_t)ec * c->clv_stride * 8);
+  const size_t o_cscal = L.take(scaled ? (size_t)ec * c->scaler_stride * 4 : 0);
+  const size_t o_qvec = L.take((size_t)qc * qslot * 8 + 8);
+  const size_t o_qdesc = L.take((size_t)qc * sizeof(InsQuery));
+  const size_t o_qsrc = L.take((size_t)qc * sizeof(double *));
+  const size_t o_slots = L.take((size_t)qc * 4);
+  const size_t o_part = L.take((size_t)qc * ec * tiles * 8);
+  const size_t o_out = L.take((size_t)qc * ec * 8);
+  BatchScratch & scratch = c->batch_scratch[BATCH_INSERTION];
+  bool grew;
+  if ((rc = pllhip_batch_scratch_grow(c, scratch, L.off, what, &grew))) return rc;
+  // zeros: the slack behind every scratch CLV, as behind the partition's own (PLLHIP_TAIL_SITES)
+  if (grew) HIP_TRY(hipMemsetAsync(scratch.p, 0, L.off, c->stream));
+  char * base = (char *)scratch.p;
   double * d_pm = (double *)(base + o_pm);
   double * d_cvec = (double *)(base + o_cvec);
   unsigned int * d_cscal = scaled ? (unsigned int *)(base + o_cscal) : nullptr;
@@ -377,6 +329,7 @@ static int ins_run(pllhip_ctx * c, const pllhip_insertion_edge_t * E, unsigned i
   std::vector<const double *> hsrc(qc);
   std::vector<unsigned int> hslots(qc);
   std::vector<double> hout((size_t)qc * ec);
+  std::vector<BatchOp> ops;
 
   for (unsigned int e0 = 0; e0 < ne; e0 += ec)
   {
@@ -391,64 +344,21 @@ static int ins_run(pllhip_ctx * c, const pllhip_insertion_edge_t * E, unsigned i
       bl[2 * i] = E[e0 + i].proximal_length;
       bl[2 * i + 1] = E[e0 + i].distal_length;
     }
-    int rc = pllhip_pmatrices_to(c, d_pm, 2 * ec + qc, params, mi.data(), bl.data(), 2 * en);
-    if (rc) return rc;
+    if ((rc = pllhip_pmatrices_to(c, d_pm, 2 * ec + qc, params, mi.data(), bl.data(), 2 * en))) return rc;
 
-    // phase 1: the op of every edge, batched by kind
-    for (int kind = 0; kind < 3; ++kind)
+    // phase 1: the op of every edge
+    ops.resize(en);
+    for (unsigned int i = 0; i < en; ++i)
     {
-      PartialsBatch b;
-      unsigned int cnt = 0;
-      for (unsigned int i = 0; i <= en; ++i)
-      {
-        if (i == en || cnt == PLLHIP_BATCH_MAX)
-        {
-          if (cnt && (rc = pllhip_launch_partials_batch(c, b, cnt, kind, mode))) return rc;
-          cnt = 0;
-          if (i == en) break;
-        }
-        const pllhip_insertion_edge_t & ed = E[e0 + i];
-        const bool tu = pllhip_is_tip(c, ed.proximal_clv_index), tv = pllhip_is_tip(c, ed.distal_clv_index);
-        const int k = (tu && tv) ? 2 : (tu || tv) ? 1 : 0;
-        if (k != kind) continue;
-        PartialsArgs & a = b.op[cnt++];
-        memset(&a, 0, sizeof(a));
-        a.parent = d_cvec + (size_t)i * c->clv_stride;
-        a.pscaler = scaled ? d_cscal + (size_t)i * c->scaler_stride : nullptr;
-        a.tipmap = c->tipmap;
-        a.zero = c->d_zero;
-        a.sites = c->sh.sites;
-        a.rate_cats = R;
-        a.states = S;
-        a.maxstates = c->maxstates;
-        double * pp = d_pm + (size_t)(2 * i) * c->pmat_elems, * pd = pp + c->pmat_elems;
-        if (kind == 2)
-        {
-          a.ltip = pllhip_tip_ptr(c, ed.proximal_clv_index);
-          a.rtip = pllhip_tip_ptr(c, ed.distal_clv_index);
-          a.lmat = pp;
-          a.rmat = pd;
-        }
-        else if (kind == 1)
-        {
-          // the tip is presented as the left child (partials.c:91-112), as resolve_op does
-          a.ltip = pllhip_tip_ptr(c, tu ? ed.proximal_clv_index : ed.distal_clv_index);
-          a.right = c->clv[tu ? ed.distal_clv_index : ed.proximal_clv_index];
-          a.lmat = tu ? pp : pd;
-          a.rmat = tu ? pd : pp;
-          a.rscaler = pllhip_scaler_ptr(c, tu ? ed.distal_scaler_index : ed.proximal_scaler_index);
-        }
-        else
-        {
-          a.left = c->clv[ed.proximal_clv_index];
-          a.right = c->clv[ed.distal_clv_index];
-          a.lmat = pp;
-          a.rmat = pd;
-          a.lscaler = pllhip_scaler_ptr(c, ed.proximal_scaler_index);
-          a.rscaler = pllhip_scaler_ptr(c, ed.distal_scaler_index);
-        }
-      }
+      const pllhip_insertion_edge_t & ed = E[e0 + i];
+      double * pp = d_pm + (size_t)(2 * i) * c->pmat_elems;
+      ops[i].kind = pllhip_batch_fill_op(
+          c, ops[i].a, pllhip_batch_operand(c, ed.proximal_clv_index, ed.proximal_scaler_index, pp),
+          pllhip_batch_operand(c, ed.distal_clv_index, ed.distal_scaler_index, pp + c->pmat_elems),
+          d_cvec + (size_t)i * c->clv_stride, scaled ? d_cscal + (size_t)i * c->scaler_stride : nullptr);
+      ops[i].mode = mode;
     }
+    if ((rc = pllhip_batch_run_ops(c, ops.data(), en))) return rc;
 
     for (unsigned int qs = 0; qs < nq; qs += qc)
     {
@@ -497,11 +407,7 @@ static int ins_run(pllhip_ctx * c, const pllhip_insertion_edge_t * E, unsigned i
       a.cvec = d_cvec;
       a.cscal = d_cscal;
       a.queries = d_qdesc;
-      a.freqs = c->freqs;
-      a.prop_invar = c->prop_invar;
-      a.rate_weights = c->rate_weights;
-      a.pattern_weights = c->pattern_weights;
-      a.invariant = c->any_prop_invar ? c->invariant : nullptr;
+      pllhip_batch_model(c, params, a.m);
       a.partial = d_part;
       a.clv_stride = c->clv_stride;
       a.scaler_stride = c->scaler_stride;
@@ -513,11 +419,9 @@ static int ins_run(pllhip_ctx * c, const pllhip_insertion_edge_t * E, unsigned i
       a.edges = en;
       a.tiles = tiles;
       a.rate_scalers = c->sh.rate_scalers;
-      for (unsigned int k = 0; k < R; ++k) a.freqs_indices[k] = params[k];
       if ((rc = ins_launch_score(c, a, (qn + INS_QB - 1) / INS_QB))) return rc;
       const size_t pairs = (size_t)qn * en;
-      k_ins_reduce<<<(unsigned int)((pairs + 255) / 256), 256, 0, c->stream>>>(d_part, d_out, pairs, tiles);
-      HIP_TRY(hipGetLastError());
+      if ((rc = pllhip_batch_reduce(c, d_part, d_out, pairs, tiles))) return rc;
       HIP_TRY(hipMemcpyAsync(hout.data(), d_out, pairs * 8, hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
       for (unsigned int i = 0; i < qn; ++i)

@@ -14,13 +14,13 @@
 //                 log-likelihood term (per-tile sums, nothing per site leaves the chip) or writes the pairing's
 //                 sumtable row and combined scaler count into the optimiser's scratch.  No candidate CLV is written;
 //   general route every other shape: u' and v' of every candidate by the partition's own CLV kernels
-//                 (pllhip_launch_partials_batch) into scratch CLVs and scale buffers, then k_nni_edge_lnl (k_lnl_gen's
-//                 arithmetic per (tile, candidate)), or the candidates' sumtables as branch_opt.hip builds them;
+//                 (pllhip_batch_run_ops) into scratch CLVs and scale buffers, then k_batch_edge_lnl (batched.hip:
+//                 k_lnl_gen's arithmetic per (tile, candidate)), or the candidates' sumtables as branch_opt.hip builds them;
 //   optimiser     the pass / step / finish kernels of branch_opt.hip (pllhip_bo_newton), one "branch" per candidate;
-//   reduction     k_nni_reduce adds a candidate's tile sums in tile order.
+//   reduction     k_batch_reduce (batched.hip) adds a candidate's tile sums in tile order.
 //
-// Determinism: tiles are NNI_TILE sites fixed by the site count; what a candidate's partial sums are made of depends
-// on its own four sides, five lengths and pairing only; every sum runs in a fixed order.  A candidate's value does
+// Determinism: tiles are PLLHIP_BATCH_TILE sites fixed by the site count; what a candidate's partial sums are made of
+// depends on its own four sides, five lengths and pairing only; every sum runs in a fixed order.  A candidate's value does
 // not depend on the batch, its order or the chunking, and arrangement k of (A, B, C, D) is arrangement 0 of the edge
 // given with its sides in arrangement k's order: the pairing is one function of (X, Y, Z, W).  No atomics.
 #include "branch_opt.hpp"
@@ -30,7 +30,6 @@
 #include <cmath>
 #include <vector>
 
-#define NNI_TILE 256 // sites per workgroup (64 per wave); equal to BO_TILE: the optimiser's tiles are the same
 
 // arrangement k: which of the edge's sides are X, Y (children of u') and Z, W (children of v')
 static const unsigned int nni_perm[3][4] = {{0, 1, 2, 3}, {0, 2, 1, 3}, {0, 3, 2, 1}};
@@ -53,18 +52,13 @@ struct NniQuartetArgs
   const double * __restrict__ pm;         // [edges][5][R][4][4]: sides A..D, then the edge
   const double * __restrict__ sum_left;   // optimiser: the sumtable's two matrix sets [R][4][4]
   const double * __restrict__ sum_right;
-  const double * __restrict__ freqs;
-  const double * __restrict__ prop_invar;
-  const double * __restrict__ rate_weights;
-  const unsigned int * __restrict__ pattern_weights;
-  const int * __restrict__ invariant;     // nullptr = no +I
+  BatchModel m;
   double * __restrict__ partial;          // lnL: [edges][3][tiles]
   double * __restrict__ tables;           // optimiser: [edges][3][table_stride]
   unsigned int * __restrict__ counts;     // optimiser: [edges][3][count_stride] (scaled partitions)
   size_t table_stride, count_stride;
   unsigned int sites, tiles;
   int scaled;                             // the partition has scale buffers: u' and v' take the op's scaling rule
-  unsigned int params[4];
 };
 
 // One pairing of a site's four products, for one rate category (the lane's): u' = x (.) y, v' = z (.) w, the
@@ -154,7 +148,7 @@ __global__ __launch_bounds__(256) void k_nni_quartet(NniQuartetArgs a)
     }
   else
     for (unsigned int i = tid; i < R * 16u; i += 256u) (&s_e[0][0][0])[i] = pm[4u * R * 16u + i];
-  for (unsigned int i = tid; i < R * 4u; i += 256u) s_fr[i / 4u][i % 4u] = a.freqs[(size_t)a.params[i / 4u] * 4u + i % 4u];
+  for (unsigned int i = tid; i < R * 4u; i += 256u) s_fr[i / 4u][i % 4u] = a.m.freqs[(size_t)a.m.params[i / 4u] * 4u + i % 4u];
   for (unsigned int i = tid; i < 4u * 16u * R * 4u; i += 256u)
   {
     const unsigned int j = i % 4u, k = (i / 4u) % R, code = (i / (4u * R)) % 16u, x = i / (64u * R);
@@ -173,11 +167,11 @@ __global__ __launch_bounds__(256) void k_nni_quartet(NniQuartetArgs a)
   const unsigned int g = lane / R, k = lane - g * R, grp0 = g * R;
   const unsigned int own_round = lane / SPR;
   const int own_src = (int)((lane - own_round * SPR) * R);
-  const unsigned int pi = a.params[k];
-  const double pinv = a.prop_invar[pi];
-  const double wk = a.rate_weights[k];
-  const size_t first = (size_t)tile * NNI_TILE;
-  const size_t end = std::min<size_t>(first + NNI_TILE, a.sites);
+  const unsigned int pi = a.m.params[k];
+  const double pinv = a.m.prop_invar[pi];
+  const double wk = a.m.rate_weights[k];
+  const size_t first = (size_t)tile * PLLHIP_BATCH_TILE;
+  const size_t end = std::min<size_t>(first + PLLHIP_BATCH_TILE, a.sites);
   const size_t sbase = first + (size_t)wave * 64u;
   double o_t[3] = {1.0, 1.0, 1.0};
   unsigned int o_c[3] = {0u, 0u, 0u};
@@ -216,7 +210,7 @@ __global__ __launch_bounds__(256) void k_nni_quartet(NniQuartetArgs a)
         cnt[sd] = (a.scaled && S.scaler) ? S.scaler[n] : 0u;
       }
       int inv = -1;
-      if (!OPT && pinv > 0.0 && a.invariant) inv = a.invariant[n];
+      if (!OPT && pinv > 0.0 && a.m.invariant) inv = a.m.invariant[n];
 #pragma unroll
       for (int arr = 0; arr < 3; ++arr)
       {
@@ -278,7 +272,7 @@ __global__ __launch_bounds__(256) void k_nni_quartet(NniQuartetArgs a)
   const size_t n_own = sbase + lane;
   if (n_own < end)
   {
-    const double pw = (double)a.pattern_weights[n_own];
+    const double pw = (double)a.m.pattern_weights[n_own];
 #pragma unroll
     for (int arr = 0; arr < 3; ++arr)
     {
@@ -290,125 +284,12 @@ __global__ __launch_bounds__(256) void k_nni_quartet(NniQuartetArgs a)
 #pragma unroll
   for (int arr = 0; arr < 3; ++arr)
   {
-    double t = acc[arr];
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+    const double t = batch_wave_sum(acc[arr]);
     if (lane == 0) s_wave[arr][wave] = t;
   }
   __syncthreads();
   if (tid < 3)
-    a.partial[((size_t)e * 3u + tid) * a.tiles + tile] = ((s_wave[tid][0] + s_wave[tid][1]) + s_wave[tid][2]) + s_wave[tid][3];
-}
-
-struct NniGenArgs
-{
-  const double * __restrict__ clv;          // [candidates][2][clv_stride]: u', v'
-  const unsigned int * __restrict__ scal;   // [candidates][2][scaler_stride] or nullptr
-  const double * __restrict__ pm;           // [edges][5][pmat_elems]
-  const double * __restrict__ freqs;
-  const double * __restrict__ prop_invar;
-  const double * __restrict__ rate_weights;
-  const unsigned int * __restrict__ pattern_weights;
-  const int * __restrict__ invariant;
-  double * __restrict__ partial;            // [candidates][tiles]
-  size_t clv_stride, scaler_stride, pmat_elems;
-  unsigned int sites, states, rate_cats, tiles;
-  int rate_scalers;
-  unsigned int freqs_indices[PLLHIP_MAX_RATE_CATS];
-};
-
-// the edge log-likelihood of every (u', v') pair of a chunk: k_lnl_gen's arithmetic (likelihood.hip, EDGE_II), one
-// lane per site, per (tile, candidate); the tile's sum: wave trees, then the four waves in order
-__global__ __launch_bounds__(NNI_TILE) void k_nni_edge_lnl(NniGenArgs a)
-{
-  const unsigned int S = a.states, R = a.rate_cats;
-  const unsigned int tile = blockIdx.x, cand = blockIdx.y;
-  const size_t n = (size_t)tile * NNI_TILE + threadIdx.x;
-  const double * up = a.clv + (size_t)cand * 2u * a.clv_stride;
-  const double * vp = up + a.clv_stride;
-  const unsigned int * us = a.scal ? a.scal + (size_t)cand * 2u * a.scaler_stride : nullptr;
-  const unsigned int * vs = us ? us + a.scaler_stride : nullptr;
-  const double * pmat = a.pm + ((size_t)(cand / 3u) * 5u + 4u) * a.pmat_elems;
-  double lk = 0.0;
-  if (n < a.sites)
-  {
-    unsigned int rs[PLLHIP_MAX_RATE_CATS];
-    unsigned int site_scalings = 0;
-    if (a.rate_scalers && us)
-    {
-      unsigned int mn = 0xffffffffu;
-      for (unsigned int k = 0; k < R; ++k)
-      {
-        const unsigned int v = us[n * R + k] + vs[n * R + k];
-        rs[k] = v;
-        mn = v < mn ? v : mn;
-      }
-      site_scalings = mn;
-      for (unsigned int k = 0; k < R; ++k)
-      {
-        const unsigned int d = rs[k] - mn;
-        rs[k] = d > PLLHIP_SCALE_RATE_MAXDIFF ? PLLHIP_SCALE_RATE_MAXDIFF : d;
-      }
-    }
-    else
-    {
-      for (unsigned int k = 0; k < R; ++k) rs[k] = 0;
-      if (us) site_scalings = us[n] + vs[n];
-    }
-    double terma = 0.0;
-    for (unsigned int k = 0; k < R; ++k)
-    {
-      const unsigned int fi = a.freqs_indices[k];
-      const double * fr = a.freqs + (size_t)fi * S;
-      const double * pc = up + (n * R + k) * S;
-      const double * cc = vp + (n * R + k) * S;
-      const double * m = pmat + (size_t)k * S * S;
-      double terma_r = 0.0;
-      for (unsigned int j = 0; j < S; ++j)
-      {
-        double termb = 0.0;
-        for (unsigned int q = 0; q < S; ++q) termb += m[j * S + q] * cc[q];
-        terma_r += pc[j] * fr[j] * termb; // core_likelihood.c:955
-      }
-      if (rs[k] > 0) terma_r *= scale_minlh(rs[k]);
-      const double pinv = a.prop_invar[fi];
-      const double w = a.rate_weights[k];
-      if (pinv > 0.0)
-      {
-        const int inv = a.invariant ? a.invariant[n] : -1;
-        const double inv_lk = (inv == -1) ? 0.0 : fr[inv];
-        terma += w * (terma_r * (1.0 - pinv) + inv_lk * pinv);
-      }
-      else
-        terma += terma_r * w;
-    }
-    lk = log(terma);
-    if (site_scalings) lk += (double)site_scalings * log(PLLHIP_SCALE_THRESHOLD);
-    lk *= (double)a.pattern_weights[n];
-  }
-  __shared__ double s_wave[NNI_TILE / 64];
-  const unsigned int wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  for (int off = 32; off > 0; off >>= 1) lk += __shfl_down(lk, off, 64);
-  if (lane == 0) s_wave[wave] = lk;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    a.partial[(size_t)cand * a.tiles + tile] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-}
-
-// a candidate's tile sums in tile order
-__global__ __launch_bounds__(256) void k_nni_reduce(const double * __restrict__ partial, double * __restrict__ out,
-                                                    size_t cands, unsigned int tiles)
-{
-  const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  if (p >= cands) return;
-  const double * t = partial + p * tiles;
-  double s = 0.0;
-  for (unsigned int i = 0; i < tiles; ++i) s += t[i];
-  out[p] = s;
-}
-
-static size_t nni_align(size_t b)
-{
-  return (b + 255) & ~(size_t)255;
+    a.partial[((size_t)e * 3u + tid) * a.tiles + tile] = batch_waves_sum(s_wave[tid]);
 }
 
 struct NniOpt
@@ -420,70 +301,6 @@ struct NniOpt
   int * status;
 };
 
-// one op of the general route: parent (scratch CLV and scale buffer) from the sides x and y of an edge
-static int nni_fill_op(pllhip_ctx * c, PartialsArgs & a, const pllhip_nni_side_t & x, double * mx,
-                       const pllhip_nni_side_t & y, double * my, double * parent, unsigned int * pscaler)
-{
-  const bool tx = pllhip_is_tip(c, x.clv_index), ty = pllhip_is_tip(c, y.clv_index);
-  memset(&a, 0, sizeof(a));
-  a.parent = parent;
-  a.pscaler = pscaler;
-  a.tipmap = c->tipmap;
-  a.zero = c->d_zero;
-  a.sites = c->sh.sites;
-  a.rate_cats = c->sh.rate_cats;
-  a.states = c->sh.states;
-  a.maxstates = c->maxstates;
-  if (tx && ty)
-  {
-    a.ltip = pllhip_tip_ptr(c, x.clv_index);
-    a.rtip = pllhip_tip_ptr(c, y.clv_index);
-    a.lmat = mx;
-    a.rmat = my;
-    return 2;
-  }
-  if (tx || ty)
-  {
-    // the tip is presented as the left child (partials.c:91-112), as resolve_op does
-    const pllhip_nni_side_t & t = tx ? x : y, & in = tx ? y : x;
-    a.ltip = pllhip_tip_ptr(c, t.clv_index);
-    a.right = c->clv[in.clv_index];
-    a.lmat = tx ? mx : my;
-    a.rmat = tx ? my : mx;
-    a.rscaler = pllhip_scaler_ptr(c, in.scaler_index);
-    return 1;
-  }
-  a.left = c->clv[x.clv_index];
-  a.right = c->clv[y.clv_index];
-  a.lmat = mx;
-  a.rmat = my;
-  a.lscaler = pllhip_scaler_ptr(c, x.scaler_index);
-  a.rscaler = pllhip_scaler_ptr(c, y.scaler_index);
-  return 0;
-}
-
-// `count` ops of mixed kinds, batched by kind
-static int nni_run_ops(pllhip_ctx * c, const std::vector<PartialsArgs> & ops, const std::vector<int> & kinds, int mode)
-{
-  for (int kind = 0; kind < 3; ++kind)
-  {
-    PartialsBatch b;
-    unsigned int cnt = 0;
-    for (size_t i = 0; i <= ops.size(); ++i)
-    {
-      if (i == ops.size() || cnt == PLLHIP_BATCH_MAX)
-      {
-        int rc;
-        if (cnt && (rc = pllhip_launch_partials_batch(c, b, cnt, kind, mode))) return rc;
-        cnt = 0;
-        if (i == ops.size()) break;
-      }
-      if (kinds[i] == kind) b.op[cnt++] = ops[i];
-    }
-  }
-  return 0;
-}
-
 // route: -1 the library's choice, 0 the general route, 1 the quartet kernel where it covers the partition
 static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne, const unsigned int * params,
                    int route, size_t budget, const NniOpt * opt, double * h_lnl)
@@ -494,12 +311,8 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
     pllhip_set_error("%s: empty batch or NULL array", what);
     return -1;
   }
-  if (!c->shards.empty() || c->comm || c->asc_type || !c->rows.empty())
-  {
-    pllhip_set_error("%s: not for sharded, RCCL-joined, asc-bias or site-repeat partitions", what);
-    return -3;
-  }
-  HIP_TRY(hipSetDevice(c->sh.device));
+  int rc = pllhip_batch_open(c, what, BATCH_PLAIN_ONLY, params);
+  if (rc) return rc;
   const unsigned int nodes = (unsigned int)c->clv.size();
   const int nsc = (int)c->sh.scale_buffers;
   const unsigned int S = c->sh.states, R = c->sh.rate_cats;
@@ -510,12 +323,6 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
     pllhip_set_error("%s: bounds, tolerance or max_iters out of range", what);
     return -1;
   }
-  for (unsigned int k = 0; k < R; ++k)
-    if (params[k] >= c->sh.rate_matrices)
-    {
-      pllhip_set_error("%s: params index %u out of range", what, params[k]);
-      return -1;
-    }
   for (unsigned int i = 0; i < ne; ++i)
   {
     if (!(E[i].length >= 0.0 && E[i].length <= DBL_MAX))
@@ -539,11 +346,6 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
       }
     }
   }
-  if (S != 4 && c->maxstates == 0 && c->sh.pattern_tip)
-  {
-    pllhip_set_error("%s: tipmap not uploaded", what);
-    return -1;
-  }
   if (opt && (size_t)R * (3u * S + 1u) * sizeof(double) > 65536 - 64)
   {
     pllhip_set_error("%s: %u states x %u rate categories: the exponentials of a branch exceed 64 KB of LDS", what, S,
@@ -560,11 +362,11 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
 
   // ---- chunk size in edges: everything one chunk needs within `budget` bytes (one edge at least)
   const size_t sites = c->sh.sites;
-  const unsigned int tiles = (unsigned int)((sites + NNI_TILE - 1) / NNI_TILE);
+  const unsigned int tiles = pllhip_batch_tiles(c);
   const size_t count_stride = sites + PLLHIP_TAIL_SITES;
   const size_t sc_b = scaled ? c->scaler_stride * 4 : 0;
   size_t per_edge = 5 * c->pmat_elems * 8 + sizeof(NniEdge) + 3 * ((size_t)tiles * 8 + 8) + 4 * 256;
-  if (!quartet) per_edge += 6 * (c->clv_stride * 8 + sc_b);
+  if (!quartet) per_edge += 6 * (c->clv_stride * 8 + sc_b) + 3 * sizeof(BatchEdge);
   if (opt)
     per_edge += 3 * (c->clv_stride * 8 + (quartet && scaled ? count_stride * 4 : 0) + sizeof(BoState) +
                      sizeof(BoSides) + (size_t)tiles * 16 + 8);
@@ -574,38 +376,26 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
   const unsigned int nc = 3 * ec; // candidates of a chunk (the grid's y of the optimiser's kernels: at most 65535)
 
   // ---- scratch layout
-  size_t off = 0;
-  const size_t o_mats = off;   off += nni_align(2 * c->pmat_elems * 8);
-  const size_t o_pm = off;     off += nni_align((size_t)5 * ec * c->pmat_elems * 8);
-  const size_t o_desc = off;   off += nni_align((size_t)ec * sizeof(NniEdge));
-  const size_t o_part = off;   off += nni_align((size_t)nc * tiles * (opt ? 16 : 8));
-  const size_t o_out = off;    off += nni_align((size_t)nc * 8);
-  const size_t o_clv = off;    off += quartet ? 0 : nni_align((size_t)2 * nc * c->clv_stride * 8);
-  const size_t o_scal = off;   off += (quartet || !scaled) ? 0 : nni_align((size_t)2 * nc * c->scaler_stride * 4);
-  const size_t o_tab = off;    off += opt ? nni_align((size_t)nc * c->clv_stride * 8) : 0;
-  const size_t o_cnts = off;   off += (opt && quartet && scaled) ? nni_align((size_t)nc * count_stride * 4) : 0;
-  const size_t o_state = off;  off += opt ? nni_align((size_t)nc * sizeof(BoState)) : 0;
-  const size_t o_sides = off;  off += opt ? nni_align((size_t)nc * sizeof(BoSides)) : 0;
-  const size_t o_cnt = off;    off += nni_align(4);
-  if (off > c->nni_scratch_bytes)
-  {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->nni_scratch) HIP_TRY(hipFree(c->nni_scratch));
-    c->nni_scratch = nullptr;
-    c->nni_scratch_bytes = 0;
-    if (hipMalloc(&c->nni_scratch, off) != hipSuccess)
-    {
-      (void)hipGetLastError();
-      c->nni_scratch = nullptr;
-      pllhip_set_error("%s: no device memory for a chunk (%zu bytes)", what, off);
-      return -2;
-    }
-    c->nni_scratch_bytes = off;
-  }
+  BatchLayout L;
+  const size_t o_mats = L.take(2 * c->pmat_elems * 8);
+  const size_t o_pm = L.take((size_t)5 * ec * c->pmat_elems * 8);
+  const size_t o_desc = L.take((size_t)ec * sizeof(NniEdge));
+  const size_t o_part = L.take((size_t)nc * tiles * (opt ? 16 : 8));
+  const size_t o_out = L.take((size_t)nc * 8);
+  const size_t o_clv = L.take(quartet ? 0 : (size_t)2 * nc * c->clv_stride * 8);
+  const size_t o_scal = L.take((quartet || !scaled) ? 0 : (size_t)2 * nc * c->scaler_stride * 4);
+  const size_t o_tab = L.take(opt ? (size_t)nc * c->clv_stride * 8 : 0);
+  const size_t o_cnts = L.take((opt && quartet && scaled) ? (size_t)nc * count_stride * 4 : 0);
+  const size_t o_state = L.take(opt ? (size_t)nc * sizeof(BoState) : 0);
+  const size_t o_sides = L.take(opt ? (size_t)nc * sizeof(BoSides) : 0);
+  const size_t o_cnt = L.take(4);
+  const size_t o_gedge = L.take((quartet || opt) ? 0 : (size_t)nc * sizeof(BatchEdge));
+  BatchScratch & scratch = c->batch_scratch[BATCH_NNI];
+  if ((rc = pllhip_batch_scratch_grow(c, scratch, L.off, what))) return rc;
   // zeros: the slack behind every scratch CLV and table, as behind the partition's own (PLLHIP_TAIL_SITES) -- on
   // every call: the same scratch serves both routes and both calls with different layouts
-  HIP_TRY(hipMemsetAsync(c->nni_scratch, 0, off, c->stream));
-  char * base = (char *)c->nni_scratch;
+  HIP_TRY(hipMemsetAsync(scratch.p, 0, L.off, c->stream));
+  char * base = (char *)scratch.p;
   double * d_left = (double *)(base + o_mats), * d_right = d_left + c->pmat_elems;
   double * d_pm = (double *)(base + o_pm);
   NniEdge * d_desc = (NniEdge *)(base + o_desc);
@@ -618,30 +408,17 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
   BoState * d_state = (BoState *)(base + o_state);
   BoSides * d_sides = (BoSides *)(base + o_sides);
   unsigned int * d_cnt = (unsigned int *)(base + o_cnt);
+  BatchEdge * d_gedge = (BatchEdge *)(base + o_gedge);
 
-  int rc;
   if (opt && (rc = pllhip_sumtable_mats_to(c, params, d_left, d_right))) return rc;
 
   BoPassArgs pa;
-  memset(&pa, 0, sizeof(pa));
+  pllhip_bo_pass_args(c, params, pa);
   pa.tables = d_tab;
   pa.st = d_state;
   pa.sides = d_sides;
-  pa.eigenvals = c->eigenvals;
-  pa.rates = c->rates;
-  pa.prop_invar = c->prop_invar;
-  pa.rate_weights = c->rate_weights;
-  pa.freqs = c->freqs;
-  pa.pattern_weights = c->pattern_weights;
-  pa.invariant = c->any_prop_invar ? c->invariant : nullptr;
   pa.partial = d_part;
-  pa.table_stride = c->clv_stride;
-  pa.sites = (unsigned int)sites;
-  pa.states = S;
-  pa.rate_cats = R;
-  pa.tiles = tiles;
   pa.rate_scalers = quartet ? 0 : c->sh.rate_scalers;
-  for (unsigned int k = 0; k < R; ++k) pa.params[k] = params[k];
   const BoBuffers bf = {d_state, d_part, d_out, d_cnt};
 
   std::vector<unsigned int> mi(5 * (size_t)ec);
@@ -650,8 +427,8 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
   std::vector<double> hout(nc);
   std::vector<BoState> hs(opt ? nc : 0);
   std::vector<BoSides> hsd(opt ? nc : 0);
-  std::vector<PartialsArgs> ops;
-  std::vector<int> kinds;
+  std::vector<BatchOp> ops;
+  std::vector<BatchEdge> hge((quartet || opt) ? 0 : nc);
 
   for (unsigned int e0 = 0; e0 < ne; e0 += ec)
   {
@@ -687,11 +464,7 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
       q.pm = d_pm;
       q.sum_left = d_left;
       q.sum_right = d_right;
-      q.freqs = c->freqs;
-      q.prop_invar = c->prop_invar;
-      q.rate_weights = c->rate_weights;
-      q.pattern_weights = c->pattern_weights;
-      q.invariant = c->any_prop_invar ? c->invariant : nullptr;
+      pllhip_batch_model(c, params, q.m);
       q.partial = d_part;
       q.tables = d_tab;
       q.counts = d_cnts;
@@ -700,7 +473,6 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
       q.sites = (unsigned int)sites;
       q.tiles = tiles;
       q.scaled = scaled ? 1 : 0;
-      for (unsigned int k = 0; k < R; ++k) q.params[k] = params[k];
       const dim3 grid(tiles, en);
       if (R == 4 && opt) k_nni_quartet<4, 1><<<grid, 256, 0, c->stream>>>(q);
       else if (R == 4) k_nni_quartet<4, 0><<<grid, 256, 0, c->stream>>>(q);
@@ -711,77 +483,58 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
     else
     {
       // u' and v' of every candidate: the ops themselves, by the partition's own CLV kernels
-      ops.clear();
-      kinds.clear();
+      ops.resize(2 * (size_t)cn);
       for (unsigned int i = 0; i < en; ++i)
         for (unsigned int k = 0; k < 3; ++k)
           for (unsigned int h = 0; h < 2; ++h)
           {
             const unsigned int x = nni_perm[k][2 * h], y = nni_perm[k][2 * h + 1];
             const size_t slot = ((size_t)i * 3 + k) * 2 + h;
-            ops.emplace_back();
-            kinds.push_back(nni_fill_op(c, ops.back(), E[e0 + i].side[x], d_pm + (size_t)(5 * i + x) * c->pmat_elems,
-                                        E[e0 + i].side[y], d_pm + (size_t)(5 * i + y) * c->pmat_elems,
-                                        d_clv + slot * c->clv_stride,
-                                        d_scal ? d_scal + slot * c->scaler_stride : nullptr));
+            const pllhip_nni_side_t & sx = E[e0 + i].side[x], & sy = E[e0 + i].side[y];
+            ops[slot].kind = pllhip_batch_fill_op(
+                c, ops[slot].a,
+                pllhip_batch_operand(c, sx.clv_index, sx.scaler_index, d_pm + (size_t)(5 * i + x) * c->pmat_elems),
+                pllhip_batch_operand(c, sy.clv_index, sy.scaler_index, d_pm + (size_t)(5 * i + y) * c->pmat_elems),
+                d_clv + slot * c->clv_stride, d_scal ? d_scal + slot * c->scaler_stride : nullptr);
+            ops[slot].mode = mode;
           }
-      if ((rc = nni_run_ops(c, ops, kinds, mode))) return rc;
+      if ((rc = pllhip_batch_run_ops(c, ops.data(), ops.size()))) return rc;
       if (opt)
       {
         // the candidates' sumtables, as pllhip_update_sumtable arranges an inner-inner branch (u' the parent)
-        ops.clear();
-        kinds.clear();
+        ops.resize(cn);
         for (unsigned int i = 0; i < cn; ++i)
         {
-          ops.emplace_back();
-          PartialsArgs & a = ops.back();
-          memset(&a, 0, sizeof(a));
-          a.parent = d_tab + (size_t)i * c->clv_stride;
-          a.tipmap = c->tipmap;
-          a.zero = c->d_zero;
-          a.sites = c->sh.sites;
-          a.rate_cats = R;
-          a.states = S;
-          a.maxstates = c->maxstates;
-          a.lmat = d_left;
-          a.rmat = d_right;
-          a.left = d_clv + (size_t)(2 * i) * c->clv_stride;
-          a.right = d_clv + (size_t)(2 * i + 1) * c->clv_stride;
-          kinds.push_back(0);
+          const BatchOperand u = {nullptr, d_clv + (size_t)(2 * i) * c->clv_stride, nullptr, nullptr};
+          const BatchOperand v = {nullptr, d_clv + (size_t)(2 * i + 1) * c->clv_stride, nullptr, nullptr};
+          ops[i].kind = pllhip_batch_fill_sumtable(c, ops[i].a, u, v, d_left, d_right, d_tab + (size_t)i * c->clv_stride);
+          ops[i].mode = SCALE_NONE;
         }
-        if ((rc = nni_run_ops(c, ops, kinds, SCALE_NONE))) return rc;
+        if ((rc = pllhip_batch_run_ops(c, ops.data(), cn))) return rc;
       }
       else
       {
-        NniGenArgs g;
-        memset(&g, 0, sizeof(g));
-        g.clv = d_clv;
-        g.scal = d_scal;
-        g.pm = d_pm;
-        g.freqs = c->freqs;
-        g.prop_invar = c->prop_invar;
-        g.rate_weights = c->rate_weights;
-        g.pattern_weights = c->pattern_weights;
-        g.invariant = c->any_prop_invar ? c->invariant : nullptr;
-        g.partial = d_part;
-        g.clv_stride = c->clv_stride;
-        g.scaler_stride = c->scaler_stride;
-        g.pmat_elems = c->pmat_elems;
-        g.sites = (unsigned int)sites;
-        g.states = S;
-        g.rate_cats = R;
-        g.tiles = tiles;
-        g.rate_scalers = c->sh.rate_scalers;
-        for (unsigned int k = 0; k < R; ++k) g.freqs_indices[k] = params[k];
-        k_nni_edge_lnl<<<dim3(tiles, cn), NNI_TILE, 0, c->stream>>>(g);
-        HIP_TRY(hipGetLastError());
+        // the edge of every candidate: u', v', the edge's matrix
+        for (unsigned int i = 0; i < cn; ++i)
+        {
+          BatchEdge & g = hge[i];
+          memset(&g, 0, sizeof(g));
+          g.pclv = d_clv + (size_t)(2 * i) * c->clv_stride;
+          g.cclv = g.pclv + c->clv_stride;
+          g.pscal = d_scal ? d_scal + (size_t)(2 * i) * c->scaler_stride : nullptr;
+          g.cscal = d_scal ? g.pscal + c->scaler_stride : nullptr;
+          g.pmat = d_pm + (size_t)(5 * (i / 3) + 4) * c->pmat_elems;
+          g.out = i;
+        }
+        // (the stream orders this copy behind the previous chunk's kernel; hge is rewritten only after the wait below)
+        HIP_TRY(hipMemcpyAsync(d_gedge, hge.data(), cn * sizeof(BatchEdge), hipMemcpyHostToDevice, c->stream));
+        if ((rc = pllhip_batch_edge_lnl(c, d_gedge, cn, params, d_part, tiles))) return rc;
       }
     }
 
     if (!opt)
     {
-      k_nni_reduce<<<(cn + 255) / 256, 256, 0, c->stream>>>(d_part, d_out, cn, tiles);
-      HIP_TRY(hipGetLastError());
+      if ((rc = pllhip_batch_reduce(c, d_part, d_out, cn, tiles))) return rc;
       HIP_TRY(hipMemcpyAsync(hout.data(), d_out, (size_t)cn * 8, hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
       memcpy(h_lnl + (size_t)3 * e0, hout.data(), (size_t)cn * 8);
@@ -801,14 +554,7 @@ static int nni_run(pllhip_ctx * c, const pllhip_nni_edge_t * E, unsigned int ne,
         hsd[i].ps = d_scal ? d_scal + (size_t)(2 * i) * c->scaler_stride : nullptr;
         hsd[i].cs = d_scal ? d_scal + (size_t)(2 * i + 1) * c->scaler_stride : nullptr;
       }
-      BoState & s = hs[i];
-      s.t = std::min(std::max(E[e0 + i / 3].length, opt->min_length), opt->max_length);
-      s.lo = opt->min_length;
-      s.hi = opt->max_length;
-      s.evals = 1;
-      s.status = PLLHIP_BRANCH_MAX_ITERS;
-      s.active = 1;
-      s.pad = 0;
+      hs[i] = pllhip_bo_start(E[e0 + i / 3].length, opt->min_length, opt->max_length);
     }
     HIP_TRY(hipMemcpyAsync(d_sides, hsd.data(), cn * sizeof(BoSides), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_state, hs.data(), cn * sizeof(BoState), hipMemcpyHostToDevice, c->stream));

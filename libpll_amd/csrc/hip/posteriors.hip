@@ -25,7 +25,7 @@
 // staged or stored.
 //
 // Determinism: a site's values depend on its two rows, its counts and the edge's matrix only.
-#include "lnl_common.hpp"
+#include "batched.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -45,11 +45,8 @@ struct PostEdge
 struct PostArgs
 {
   const PostEdge * __restrict__ edges; // [gridDim.y]
-  const double * __restrict__ freqs;
-  const double * __restrict__ prop_invar;
-  const double * __restrict__ rate_weights;
+  BatchModel m;                        // (the pattern weights are not read; params: the freqs indices)
   const double * __restrict__ rates;
-  const int * __restrict__ invariant;  // nullable
   const unsigned int * __restrict__ tipmap;
   double * state_probs;        // [edges][sites][S] or nullptr
   unsigned char * best_state;  // [edges][sites]
@@ -59,7 +56,6 @@ struct PostArgs
   unsigned int sites, states, rate_cats, maxstates;
   int rate_scalers;
   unsigned int mat_in_lds;     // general instance: the matrix fits next to the rows
-  unsigned int freqs_indices[PLLHIP_MAX_RATE_CATS];
 };
 
 __host__ __device__ constexpr unsigned int post_pad(unsigned int n)
@@ -88,7 +84,7 @@ __device__ __forceinline__ void post_factors(const PostArgs & a, unsigned int R,
 {
   for (unsigned int i = threadIdx.x; i < R; i += blockDim.x)
   {
-    const double p = a.prop_invar[a.freqs_indices[i]], w = a.rate_weights[i];
+    const double p = a.m.prop_invar[a.m.params[i]], w = a.m.rate_weights[i];
     s_c[i] = w * (1.0 - p);
     s_wp[i] = w * p;
     s_r[i] = p > 0.0 ? a.rates[i] / (1.0 - p) : a.rates[i];
@@ -114,7 +110,7 @@ __global__ __launch_bounds__(ST > 0 ? POST_TILE : 64) void k_post(PostArgs a)
     __shared__ double s_stage[POST_TILE * SPAD];
     for (unsigned int t = threadIdx.x; t < R * S * S; t += POST_TILE) s_mat[t] = E.pmat[t];
     for (unsigned int t = threadIdx.x; t < R * S; t += POST_TILE)
-      s_fr[t] = a.freqs[(size_t)a.freqs_indices[t / S] * S + t % S];
+      s_fr[t] = a.m.freqs[(size_t)a.m.params[t / S] * S + t % S];
     post_factors(a, R, s_c, s_wp, s_r);
     __syncthreads();
 
@@ -146,7 +142,7 @@ __global__ __launch_bounds__(ST > 0 ? POST_TILE : 64) void k_post(PostArgs a)
           rel[i] = d > PLLHIP_SCALE_RATE_MAXDIFF ? PLLHIP_SCALE_RATE_MAXDIFF : d;
         }
       }
-      const int inv = a.invariant ? a.invariant[n] : -1;
+      const int inv = a.m.invariant ? a.m.invariant[n] : -1;
       unsigned int mask = 0;
       if (E.tip)
       {
@@ -251,7 +247,7 @@ __global__ __launch_bounds__(ST > 0 ? POST_TILE : 64) void k_post(PostArgs a)
     double * s_sp = s_r + R;           // [64][SPAD]
     double * s_rs = s_sp + 64 * SPAD;  // [64][RPAD]
     double * s_mat = s_rs + 64 * RPAD; // [R][S][S] if it fits
-    for (unsigned int t = threadIdx.x; t < R * S; t += 64) s_fr[t] = a.freqs[(size_t)a.freqs_indices[t / S] * S + t % S];
+    for (unsigned int t = threadIdx.x; t < R * S; t += 64) s_fr[t] = a.m.freqs[(size_t)a.m.params[t / S] * S + t % S];
     post_factors(a, R, s_c, s_wp, s_r);
     if (a.mat_in_lds)
       for (unsigned int t = threadIdx.x; t < R * S * S; t += 64) s_mat[t] = E.pmat[t];
@@ -279,7 +275,7 @@ __global__ __launch_bounds__(ST > 0 ? POST_TILE : 64) void k_post(PostArgs a)
             mn = x < mn ? x : mn;
           }
         }
-        const int inv = a.invariant ? a.invariant[n] : -1;
+        const int inv = a.m.invariant ? a.m.invariant[n] : -1;
         unsigned int mask = 0;
         if (E.tip)
         {
@@ -354,11 +350,6 @@ __global__ __launch_bounds__(ST > 0 ? POST_TILE : 64) void k_post(PostArgs a)
   }
 }
 
-static size_t post_align(size_t b)
-{
-  return (b + 255) & ~(size_t)255;
-}
-
 // LDS of the general instance without / with the edge's matrix
 static size_t post_gen_lds(unsigned int S, unsigned int R, bool with_mat)
 {
@@ -397,22 +388,13 @@ extern "C" int pllhip_site_posteriors(pllhip_ctx_t * c, const pllhip_posterior_e
     pllhip_set_error("pllhip_site_posteriors: empty batch, NULL array or no output");
     return -1;
   }
-  if (!c->shards.empty() || c->comm || c->asc_type || !c->rows.empty())
-  {
-    pllhip_set_error("pllhip_site_posteriors: not for sharded, RCCL-joined, asc-bias or site-repeat partitions");
-    return -3;
-  }
-  HIP_TRY(hipSetDevice(c->sh.device));
+  const char * what = "pllhip_site_posteriors";
+  int rc = pllhip_batch_open(c, what, BATCH_PLAIN_ONLY, h_freqs_indices);
+  if (rc) return rc;
   const unsigned int nodes = (unsigned int)c->clv.size();
   const int nsc = (int)c->sh.scale_buffers;
   const unsigned int S = c->sh.states, R = c->sh.rate_cats;
   // everything again (the shim's own rule: a binding may call it directly)
-  for (unsigned int k = 0; k < R; ++k)
-    if (h_freqs_indices[k] >= c->sh.rate_matrices)
-    {
-      pllhip_set_error("pllhip_site_posteriors: freqs index %u out of range", h_freqs_indices[k]);
-      return -1;
-    }
   for (unsigned int i = 0; i < count; ++i)
   {
     const pllhip_posterior_edge_t & e = E[i];
@@ -434,11 +416,6 @@ extern "C" int pllhip_site_posteriors(pllhip_ctx_t * c, const pllhip_posterior_e
       return -1;
     }
   }
-  if (S != 4 && c->maxstates == 0 && c->sh.pattern_tip)
-  {
-    pllhip_set_error("pllhip_site_posteriors: tipmap not uploaded");
-    return -1;
-  }
   const bool fixed = (S == 4 || S == 20) && (R == 1 || R == 4);
   if (!fixed && (S > 64 || R > PLLHIP_MAX_RATE_CATS || post_gen_lds(S, R, false) > 65536 - 64))
   {
@@ -451,47 +428,32 @@ extern "C" int pllhip_site_posteriors(pllhip_ctx_t * c, const pllhip_posterior_e
   // ---- chunk size: the outputs of one chunk within `budget` bytes (one edge at least)
   const size_t sites = c->sh.sites;
   const unsigned int tiles = (unsigned int)((sites + POST_TILE - 1) / POST_TILE);
-  const size_t b_sp = h_state_probs ? post_align(sites * S * 8) : 0, b_bs = h_best_state ? post_align(sites) : 0;
-  const size_t b_bp = h_best_prob ? post_align(sites * 8) : 0, b_rp = h_rate_probs ? post_align(sites * (R + 1) * 8) : 0;
-  const size_t b_sr = h_site_rates ? post_align(sites * 8) : 0;
+  const size_t b_sp = h_state_probs ? pllhip_batch_align(sites * S * 8) : 0, b_bs = h_best_state ? pllhip_batch_align(sites) : 0;
+  const size_t b_bp = h_best_prob ? pllhip_batch_align(sites * 8) : 0, b_rp = h_rate_probs ? pllhip_batch_align(sites * (R + 1) * 8) : 0;
+  const size_t b_sr = h_site_rates ? pllhip_batch_align(sites * 8) : 0;
   const size_t per_edge = b_sp + b_bs + b_bp + b_rp + b_sr + sizeof(PostEdge);
   const size_t room = budget > 4096 ? (budget - 4096) / per_edge : 0;
   const unsigned int nc = (unsigned int)std::min<size_t>(std::max<size_t>(room, 1), std::min<size_t>(count, 65535));
 
   // ---- scratch layout (an output's rows of a chunk lie back to back, as in the caller's array)
-  size_t off = 0;
-  const size_t o_edges = off; off += post_align((size_t)nc * sizeof(PostEdge));
-  const size_t o_sp = off;    off += h_state_probs ? post_align((size_t)nc * sites * S * 8) : 0;
-  const size_t o_rp = off;    off += h_rate_probs ? post_align((size_t)nc * sites * (R + 1) * 8) : 0;
-  const size_t o_bp = off;    off += h_best_prob ? post_align((size_t)nc * sites * 8) : 0;
-  const size_t o_sr = off;    off += h_site_rates ? post_align((size_t)nc * sites * 8) : 0;
-  const size_t o_bs = off;    off += h_best_state ? post_align((size_t)nc * sites) : 0;
-  if (off > c->post_scratch_bytes)
-  {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->post_scratch) HIP_TRY(hipFree(c->post_scratch));
-    c->post_scratch = nullptr;
-    c->post_scratch_bytes = 0;
-    if (hipMalloc(&c->post_scratch, off) != hipSuccess)
-    {
-      (void)hipGetLastError();
-      c->post_scratch = nullptr;
-      pllhip_set_error("pllhip_site_posteriors: no device memory for a chunk (%zu bytes)", off);
-      return -2;
-    }
-    c->post_scratch_bytes = off;
-  }
-  char * base = (char *)c->post_scratch;
+  BatchLayout L;
+  const size_t o_edges = L.take((size_t)nc * sizeof(PostEdge));
+  const size_t o_sp = L.take(h_state_probs ? (size_t)nc * sites * S * 8 : 0);
+  const size_t o_rp = L.take(h_rate_probs ? (size_t)nc * sites * (R + 1) * 8 : 0);
+  const size_t o_bp = L.take(h_best_prob ? (size_t)nc * sites * 8 : 0);
+  const size_t o_sr = L.take(h_site_rates ? (size_t)nc * sites * 8 : 0);
+  const size_t o_bs = L.take(h_best_state ? (size_t)nc * sites : 0);
+  BatchScratch & scratch = c->batch_scratch[BATCH_POSTERIORS];
+  // (never zeroed: every byte read was written by the same chunk)
+  if ((rc = pllhip_batch_scratch_grow(c, scratch, L.off, what))) return rc;
+  char * base = (char *)scratch.p;
   PostEdge * d_edges = (PostEdge *)(base + o_edges);
 
   PostArgs a;
   memset(&a, 0, sizeof(a));
   a.edges = d_edges;
-  a.freqs = c->freqs;
-  a.prop_invar = c->prop_invar;
-  a.rate_weights = c->rate_weights;
+  pllhip_batch_model(c, h_freqs_indices, a.m);
   a.rates = c->rates;
-  a.invariant = c->any_prop_invar ? c->invariant : nullptr;
   a.tipmap = c->tipmap;
   a.state_probs = h_state_probs ? (double *)(base + o_sp) : nullptr;
   a.rate_probs = h_rate_probs ? (double *)(base + o_rp) : nullptr;
@@ -503,7 +465,6 @@ extern "C" int pllhip_site_posteriors(pllhip_ctx_t * c, const pllhip_posterior_e
   a.rate_cats = R;
   a.maxstates = c->maxstates;
   a.rate_scalers = (c->sh.rate_scalers && nsc > 0) ? 1 : 0;
-  for (unsigned int k = 0; k < R; ++k) a.freqs_indices[k] = h_freqs_indices[k];
 
   std::vector<PostEdge> he(nc);
   for (unsigned int e0 = 0; e0 < count; e0 += nc)
@@ -524,8 +485,7 @@ extern "C" int pllhip_site_posteriors(pllhip_ctx_t * c, const pllhip_posterior_e
     }
     // (the stream orders this copy behind the previous chunk's kernel; he is rewritten only after the wait below)
     HIP_TRY(hipMemcpyAsync(d_edges, he.data(), en * sizeof(PostEdge), hipMemcpyHostToDevice, c->stream));
-    const int rc = post_launch(c, a, tiles, en);
-    if (rc) return rc;
+    if ((rc = post_launch(c, a, tiles, en))) return rc;
     const size_t es = (size_t)en * sites, e0s = (size_t)e0 * sites;
     if (h_state_probs)
       HIP_TRY(hipMemcpyAsync(h_state_probs + e0s * S, a.state_probs, es * S * 8, hipMemcpyDeviceToHost, c->stream));

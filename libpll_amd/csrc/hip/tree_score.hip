@@ -18,23 +18,20 @@
 //                 log-likelihood term itself (k_lnl_dna's arithmetic).  Per-tile sums; nothing per site leaves the chip;
 //   general route every other shape, and lists that need more slots than the cap: the kept ops of the chunk's
 //                 candidates, levelled by their dependencies, by the context's own CLV kernels
-//                 (pllhip_launch_partials_batch) into scratch CLVs and scale buffers, then k_tree_edge_lnl (k_lnl_gen's
-//                 arithmetic per (tile, candidate));
-//   reduction     k_tree_reduce adds a candidate's tile sums in tile order.
+//                 (pllhip_batch_run_ops) into scratch CLVs and scale buffers, then k_batch_edge_lnl (batched.hip:
+//                 k_lnl_gen's arithmetic per (tile, candidate));
+//   reduction     k_batch_reduce (batched.hip) adds a candidate's tile sums in tile order.
 //
-// Determinism: tiles are TS_TILE sites fixed by the site count; a candidate's plan, records and partial sums depend on
-// the candidate alone, every sum runs in a fixed order.  A candidate's value does not depend on the batch, its order or
+// Determinism: tiles are PLLHIP_BATCH_TILE sites fixed by the site count; a candidate's plan, records and partial sums
+// depend on the candidate alone, every sum runs in a fixed order.  A candidate's value does not depend on the batch, its order or
 // the chunking.  No atomics, no barrier inside the walk, no traffic between waves.
-#include "ctx.hpp"
-#include "numerics.hpp"
-#include "lnl_common.hpp"
+#include "batched.hpp"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <vector>
 
-#define TS_TILE 256          // sites per workgroup
 #define TS_SLOT_BYTES 2304   // a slot of one wave: 64 lanes x 32 B (two planes of 16 B per lane), then 64 counts
 #define TS_HEAD_BYTES 64     // the four wave sums, in front of everything (all LDS is dynamic: the base stays 16-aligned)
 #define TS_STAGE_ROW 144     // the staged matrices of an op: 128 B per (matrix, rate), 144 apart
@@ -314,14 +311,9 @@ struct TsArgs
 {
   const TsCand * __restrict__ cands;
   const TsOp * __restrict__ ops;
-  const double * __restrict__ freqs;
-  const double * __restrict__ prop_invar;
-  const double * __restrict__ rate_weights;
-  const unsigned int * __restrict__ pattern_weights;
-  const int * __restrict__ invariant; // nullptr = no +I
+  BatchModel m;
   double * __restrict__ partial;      // [chunk's candidates][tiles]
   unsigned int sites, tiles, nslots;
-  unsigned int params[4];
 };
 
 // A record is the same for every lane: read through the constant address space it is loaded by the scalar unit into
@@ -461,13 +453,13 @@ __global__ __launch_bounds__(256) void k_tree_score(TsArgs a)
   char * wbase = ts_lds + TS_HEAD_BYTES + 4u * TS_STAGE_BYTES + (size_t)wave * a.nslots * TS_SLOT_BYTES;
   const unsigned int g = lane / R, k = lane - g * R, grp0 = g * R;
   const char * lrow = stage + k * TS_STAGE_ROW, * rrow = stage + (R + k) * TS_STAGE_ROW;
-  const unsigned int pi = a.params[k];
-  const double pinv = a.prop_invar[pi];
-  const double wk = a.rate_weights[k];
-  const double * __restrict__ frk = a.freqs + (size_t)pi * 4u;
+  const unsigned int pi = a.m.params[k];
+  const double pinv = a.m.prop_invar[pi];
+  const double wk = a.m.rate_weights[k];
+  const double * __restrict__ frk = a.m.freqs + (size_t)pi * 4u;
   const double fr[4] = {frk[0], frk[1], frk[2], frk[3]};
-  const size_t first = (size_t)tile * TS_TILE;
-  const size_t end = std::min<size_t>(first + TS_TILE, a.sites);
+  const size_t first = (size_t)tile * PLLHIP_BATCH_TILE;
+  const size_t end = std::min<size_t>(first + PLLHIP_BATCH_TILE, a.sites);
   const size_t sbase = first + (size_t)wave * 64u;
   const TsOp * __restrict__ ops = a.ops + cd.first;
   const unsigned int nops = cd.nops;
@@ -478,8 +470,8 @@ __global__ __launch_bounds__(256) void k_tree_score(TsArgs a)
   const int own_src = (int)((lane - own_round * SPR) * R);
   // (the invariant index is requested unconditionally, an absent array reads site 0 of the weights: a load under the
   // divergent +I branch would be waited for there, with everything else in flight)
-  const bool has_inv = a.invariant != nullptr;
-  const int * inv_site = has_inv ? a.invariant : reinterpret_cast<const int *>(a.pattern_weights);
+  const bool has_inv = a.m.invariant != nullptr;
+  const int * inv_site = has_inv ? a.m.invariant : reinterpret_cast<const int *>(a.m.pattern_weights);
   double o_t = 1.0;
   unsigned int o_c = 0u;
   if (sbase < end)
@@ -583,178 +575,13 @@ __global__ __launch_bounds__(256) void k_tree_score(TsArgs a)
   {
     double lk = log(o_t);
     if (o_c) lk += (double)o_c * log(PLLHIP_SCALE_THRESHOLD);
-    acc = lk * (double)a.pattern_weights[n_own];
+    acc = lk * (double)a.m.pattern_weights[n_own];
   }
   // the tile's sum: wave trees, then the four waves in order
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if (lane == 0) s_wave[wave] = acc;
-  __syncthreads();
-  if (tid == 0) a.partial[(size_t)cd.out * a.tiles + tile] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-}
-
-// ------------------------------------------------------------------------------------------------ the general route
-
-struct TsEdge
-{
-  const double * pclv;         // the parent side's CLV (the context's or scratch)
-  const double * cclv;         // the child side's, or nullptr: a pattern tip
-  const unsigned char * ctip;
-  const unsigned int * pscal, * cscal;
-  const double * pmat;
-  unsigned int out, pad;
-};
-
-struct TsGenArgs
-{
-  const TsEdge * __restrict__ edges;
-  const double * __restrict__ freqs;
-  const double * __restrict__ prop_invar;
-  const double * __restrict__ rate_weights;
-  const unsigned int * __restrict__ pattern_weights;
-  const int * __restrict__ invariant;
-  const unsigned int * __restrict__ tipmap;
-  double * __restrict__ partial;
-  unsigned int sites, states, rate_cats, tiles;
-  int rate_scalers;
-  unsigned int freqs_indices[PLLHIP_MAX_RATE_CATS];
-};
-
-// the edge log-likelihood of every general-route candidate of a chunk: k_lnl_gen's arithmetic (likelihood.hip), one lane
-// per site, per (tile, candidate); the tile's sum: wave trees, then the four waves in order
-__global__ __launch_bounds__(TS_TILE) void k_tree_edge_lnl(TsGenArgs a)
-{
-  const unsigned int S = a.states, R = a.rate_cats;
-  const unsigned int tile = blockIdx.x;
-  const TsEdge & e = a.edges[blockIdx.y];
-  const size_t n = (size_t)tile * TS_TILE + threadIdx.x;
-  double lk = 0.0;
-  if (n < a.sites)
-  {
-    unsigned int rs[PLLHIP_MAX_RATE_CATS];
-    unsigned int site_scalings = 0;
-    if (a.rate_scalers)
-    {
-      unsigned int mn = 0xffffffffu;
-      for (unsigned int k = 0; k < R; ++k)
-      {
-        unsigned int v = e.pscal ? e.pscal[n * R + k] : 0u;
-        if (e.cscal) v += e.cscal[n * R + k];
-        rs[k] = v;
-        mn = v < mn ? v : mn;
-      }
-      site_scalings = mn;
-      for (unsigned int k = 0; k < R; ++k)
-      {
-        const unsigned int d = rs[k] - mn;
-        rs[k] = d > PLLHIP_SCALE_RATE_MAXDIFF ? PLLHIP_SCALE_RATE_MAXDIFF : d;
-      }
-    }
-    else
-    {
-      for (unsigned int k = 0; k < R; ++k) rs[k] = 0;
-      if (e.pscal) site_scalings += e.pscal[n];
-      if (e.cscal) site_scalings += e.cscal[n];
-    }
-    unsigned int mask = 0;
-    if (!e.cclv)
-    {
-      const unsigned int c = e.ctip[n];
-      mask = (S == 4) ? c : a.tipmap[c];
-    }
-    double terma = 0.0;
-    for (unsigned int k = 0; k < R; ++k)
-    {
-      const unsigned int fi = a.freqs_indices[k];
-      const double * fr = a.freqs + (size_t)fi * S;
-      const double * pc = e.pclv + (n * R + k) * S;
-      const double * cc = e.cclv ? e.cclv + (n * R + k) * S : nullptr;
-      const double * m = e.pmat + (size_t)k * S * S;
-      double terma_r = 0.0;
-      for (unsigned int j = 0; j < S; ++j)
-      {
-        double termb = 0.0;
-        if (cc)
-          for (unsigned int q = 0; q < S; ++q) termb += m[j * S + q] * cc[q];
-        else
-          for (unsigned int q = 0; q < S; ++q)
-            if ((mask >> q) & 1u) termb += m[j * S + q];
-        terma_r += pc[j] * fr[j] * termb; // core_likelihood.c:955
-      }
-      if (rs[k] > 0) terma_r *= scale_minlh(rs[k]);
-      const double pinv = a.prop_invar[fi];
-      const double w = a.rate_weights[k];
-      if (pinv > 0.0)
-      {
-        const int inv = a.invariant ? a.invariant[n] : -1;
-        const double inv_lk = (inv == -1) ? 0.0 : fr[inv];
-        terma += w * (terma_r * (1.0 - pinv) + inv_lk * pinv);
-      }
-      else
-        terma += terma_r * w;
-    }
-    lk = log(terma);
-    if (site_scalings) lk += (double)site_scalings * log(PLLHIP_SCALE_THRESHOLD);
-    lk *= (double)a.pattern_weights[n];
-  }
-  __shared__ double s_wave[TS_TILE / 64];
-  const unsigned int wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  for (int off = 32; off > 0; off >>= 1) lk += __shfl_down(lk, off, 64);
-  if (lane == 0) s_wave[wave] = lk;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    a.partial[(size_t)e.out * a.tiles + tile] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-}
-
-// a candidate's tile sums in tile order
-__global__ __launch_bounds__(256) void k_tree_reduce(const double * __restrict__ partial, double * __restrict__ out,
-                                                     size_t cands, unsigned int tiles)
-{
-  const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  if (p >= cands) return;
-  const double * t = partial + p * tiles;
-  double s = 0.0;
-  for (unsigned int i = 0; i < tiles; ++i) s += t[i];
-  out[p] = s;
+  batch_tile_sum(acc, s_wave, a.partial + (size_t)cd.out * a.tiles + tile);
 }
 
 // ------------------------------------------------------------------------------------------------ the call
-
-static size_t ts_align(size_t b)
-{
-  return (b + 255) & ~(size_t)255;
-}
-
-// one general-route op: its arguments, its kind, its scaling mode and its dependency level
-struct TsGenOp
-{
-  PartialsArgs a;
-  int kind, mode;
-  unsigned int level;
-};
-
-// `ops` of one level, batched by kind and mode
-static int ts_run_level(pllhip_ctx * c, const std::vector<TsGenOp> & ops, const std::vector<unsigned int> & ids)
-{
-  for (int kind = 0; kind < 3; ++kind)
-    for (int mode = 0; mode < 3; ++mode)
-    {
-      PartialsBatch b;
-      unsigned int cnt = 0;
-      for (size_t i = 0; i <= ids.size(); ++i)
-      {
-        if (i == ids.size() || cnt == PLLHIP_BATCH_MAX)
-        {
-          int rc;
-          if (cnt && (rc = pllhip_launch_partials_batch(c, b, cnt, kind, mode))) return rc;
-          cnt = 0;
-          if (i == ids.size()) break;
-        }
-        const TsGenOp & o = ops[ids[i]];
-        if (o.kind == kind && o.mode == mode) b.op[cnt++] = o.a;
-      }
-    }
-  return 0;
-}
 
 // route: -1 the library's choice, 0 the general route, 1 the kernel where it covers the candidate
 extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_candidate_t * C, unsigned int count,
@@ -768,26 +595,11 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
     pllhip_set_error("%s: empty batch or NULL array", what);
     return -1;
   }
-  if (!c->shards.empty() || c->comm || c->asc_type || !c->rows.empty())
-  {
-    pllhip_set_error("%s: not for sharded, RCCL-joined, asc-bias or site-repeat partitions", what);
-    return -3;
-  }
-  HIP_TRY(hipSetDevice(c->sh.device));
+  int rc = pllhip_batch_open(c, what, BATCH_PLAIN_ONLY, params);
+  if (rc) return rc;
   const unsigned int nodes = (unsigned int)c->clv.size();
   const unsigned int S = c->sh.states, R = c->sh.rate_cats;
   const TsGeom geom = {c->sh.tips, nodes, c->sh.scale_buffers, c->sh.pattern_tip != 0};
-  for (unsigned int k = 0; k < R; ++k)
-    if (params[k] >= c->sh.rate_matrices)
-    {
-      pllhip_set_error("%s: params index %u out of range", what, params[k]);
-      return -1;
-    }
-  if (S != 4 && c->maxstates == 0 && c->sh.pattern_tip)
-  {
-    pllhip_set_error("%s: tipmap not uploaded", what);
-    return -1;
-  }
   const bool scaled = c->sh.scale_buffers > 0;
   const bool covers = S == 4 && (R == 1 || R == 4) && !(scaled && c->sh.rate_scalers);
   const bool use_kernel = covers && route != 0;
@@ -828,10 +640,10 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
         pllhip_set_error("%s: candidate %u, op %u: matrix index out of range", what, i, o);
         return -1;
       }
-    const int rc = ts_plan(geom, cd.operations, cd.op_count, cd.parent_clv_index, cd.parent_scaler_index,
-                           cd.child_clv_index, cd.child_scaler_index, cap, plans[i]);
-    if (rc < 0) return -1;
-    by_kernel[i] = rc == 0;
+    const int route_of = ts_plan(geom, cd.operations, cd.op_count, cd.parent_clv_index, cd.parent_scaler_index,
+                                 cd.child_clv_index, cd.child_scaler_index, cap, plans[i]);
+    if (route_of < 0) return -1;
+    by_kernel[i] = route_of == 0;
     // what the candidate reads of earlier calls
     for (unsigned int o : plans[i].order) written[cd.operations[o].parent_clv] = i + 1;
     auto ext = [&](unsigned int clv, int sc) -> bool {
@@ -860,7 +672,7 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
     ext_clv.erase(std::unique(ext_clv.begin(), ext_clv.end()), ext_clv.end());
     std::sort(ext_sc.begin(), ext_sc.end());
     ext_sc.erase(std::unique(ext_sc.begin(), ext_sc.end()), ext_sc.end());
-    int rc = ext_clv.empty() ? 0 : pllhip_deferred_materialise(c, ext_clv.data(), (int)ext_clv.size());
+    rc = ext_clv.empty() ? 0 : pllhip_deferred_materialise(c, ext_clv.data(), (int)ext_clv.size());
     // (the helper takes an edge's worth of indices: eight at a time)
     for (size_t at = 0; !rc && at < ext_sc.size(); at += 8)
       rc = pllhip_deferred_materialise_scalers(c, ext_sc.data() + at, (int)std::min<size_t>(8, ext_sc.size() - at));
@@ -868,13 +680,13 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
   }
 
   const size_t sites = c->sh.sites;
-  const unsigned int tiles = (unsigned int)((sites + TS_TILE - 1) / TS_TILE);
+  const unsigned int tiles = pllhip_batch_tiles(c);
   const size_t clv_b = c->clv_stride * 8, sc_b = scaled ? c->scaler_stride * 4 : 0;
   // what a candidate takes of a chunk's scratch
   auto bytes_of = [&](unsigned int i) -> size_t {
     const size_t nk = plans[i].order.size();
     size_t b = (size_t)C[i].matrix_count * c->pmat_elems * 8 + (size_t)tiles * 8 + 8 + 512;
-    b += by_kernel[i] ? nk * sizeof(TsOp) + sizeof(TsCand) : nk * (clv_b + sc_b + 512) + sizeof(TsEdge);
+    b += by_kernel[i] ? nk * sizeof(TsOp) + sizeof(TsCand) : nk * (clv_b + sc_b + 512) + sizeof(BatchEdge);
     return b;
   };
 
@@ -884,8 +696,9 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
   std::vector<int> clv_at(nodes, -1), sc_at(c->sh.scale_buffers, -1);
   std::vector<TsOp> h_ops;
   std::vector<TsCand> h_cands;
-  std::vector<TsEdge> h_edges;
-  std::vector<TsGenOp> gen;
+  std::vector<BatchEdge> h_edges;
+  std::vector<BatchOp> gen, level_ops;
+  std::vector<unsigned int> level_of; // per op of gen: its dependency level
   std::vector<double> hout;
 
   for (unsigned int c0 = 0; c0 < count;)
@@ -915,37 +728,24 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
       ++cn;
     }
     // ---- scratch layout
-    size_t off = 0;
-    const size_t o_pm = off;    off += ts_align(nmat * c->pmat_elems * 8);
-    const size_t o_ops = off;   off += ts_align(nrec * sizeof(TsOp));
-    const size_t o_cand = off;  off += ts_align(nkc * sizeof(TsCand));
-    const size_t o_edge = off;  off += ts_align(ngc * sizeof(TsEdge));
-    const size_t o_part = off;  off += ts_align((size_t)cn * tiles * 8);
-    const size_t o_out = off;   off += ts_align((size_t)cn * 8);
-    const size_t o_zero = off; // from here: zeroed on every chunk (the slack behind every scratch CLV reads as zeros)
-    const size_t o_clv = off;   off += ts_align(ngen * clv_b);
-    const size_t o_scal = off;  off += ts_align(ngen * sc_b);
-    if (off > c->tree_scratch_bytes)
-    {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (c->tree_scratch) HIP_TRY(hipFree(c->tree_scratch));
-      c->tree_scratch = nullptr;
-      c->tree_scratch_bytes = 0;
-      if (hipMalloc(&c->tree_scratch, off) != hipSuccess)
-      {
-        (void)hipGetLastError();
-        c->tree_scratch = nullptr;
-        pllhip_set_error("%s: no device memory for a chunk (%zu bytes)", what, off);
-        return -2;
-      }
-      c->tree_scratch_bytes = off;
-    }
-    char * base = (char *)c->tree_scratch;
-    if (off > o_zero) HIP_TRY(hipMemsetAsync(base + o_zero, 0, off - o_zero, c->stream));
+    BatchLayout L;
+    const size_t o_pm = L.take(nmat * c->pmat_elems * 8);
+    const size_t o_ops = L.take(nrec * sizeof(TsOp));
+    const size_t o_cand = L.take(nkc * sizeof(TsCand));
+    const size_t o_edge = L.take(ngc * sizeof(BatchEdge));
+    const size_t o_part = L.take((size_t)cn * tiles * 8);
+    const size_t o_out = L.take((size_t)cn * 8);
+    const size_t o_zero = L.off; // from here: zeroed on every chunk (the slack behind every scratch CLV reads as zeros)
+    const size_t o_clv = L.take(ngen * clv_b);
+    const size_t o_scal = L.take(ngen * sc_b);
+    BatchScratch & scratch = c->batch_scratch[BATCH_TREE_SCORE];
+    if ((rc = pllhip_batch_scratch_grow(c, scratch, L.off, what))) return rc;
+    char * base = (char *)scratch.p;
+    if (L.off > o_zero) HIP_TRY(hipMemsetAsync(base + o_zero, 0, L.off - o_zero, c->stream));
     double * d_pm = (double *)(base + o_pm);
     TsOp * d_ops = (TsOp *)(base + o_ops);
     TsCand * d_cands = (TsCand *)(base + o_cand);
-    TsEdge * d_edges = (TsEdge *)(base + o_edge);
+    BatchEdge * d_edges = (BatchEdge *)(base + o_edge);
     double * d_part = (double *)(base + o_part);
     double * d_out = (double *)(base + o_out);
     double * d_clv = (double *)(base + o_clv);
@@ -960,7 +760,6 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
         mi.push_back((unsigned int)mi.size());
         bl.push_back(C[c0 + j].branch_lengths[m]);
       }
-    int rc;
     if (nmat && (rc = pllhip_pmatrices_to(c, d_pm, (unsigned int)nmat, params, mi.data(), bl.data(), (unsigned int)nmat)))
       return rc;
 
@@ -969,6 +768,7 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
     h_cands.clear();
     h_edges.clear();
     gen.clear();
+    level_of.clear();
     size_t mat0 = 0, gen0 = 0;
     unsigned int max_level = 0;
     for (unsigned int j = 0; j < cn; ++j)
@@ -1026,66 +826,35 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
         {
           const pllhip_op_t & op = cd.operations[pl.order[q]];
           const size_t at = gen0 + q;
-          TsGenOp go;
-          PartialsArgs & a = go.a;
-          memset(&a, 0, sizeof(a));
+          BatchOp go;
           unsigned int level = 0;
           auto clv_of = [&](unsigned int clv) -> const double * {
             if (clv_at[clv] < 0) return c->clv[clv];
-            level = std::max(level, gen[clv_at[clv]].level + 1);
+            level = std::max(level, level_of[clv_at[clv]] + 1);
             return d_clv + (size_t)clv_at[clv] * c->clv_stride;
           };
           auto sc_of = [&](int sc) -> const unsigned int * {
             if (sc < 0) return nullptr;
             if (sc_at[sc] < 0) return pllhip_scaler_ptr(c, sc);
-            level = std::max(level, gen[sc_at[sc]].level + 1);
+            level = std::max(level, level_of[sc_at[sc]] + 1);
             return d_scal + (size_t)sc_at[sc] * c->scaler_stride;
           };
-          const bool t1 = geom.is_tip(op.child1_clv), t2 = geom.is_tip(op.child2_clv);
-          a.parent = d_clv + at * c->clv_stride;
-          a.pscaler = op.parent_scaler >= 0 ? d_scal + at * c->scaler_stride : nullptr;
-          a.tipmap = c->tipmap;
-          a.zero = c->d_zero;
-          a.sites = c->sh.sites;
-          a.rate_cats = R;
-          a.states = S;
-          a.maxstates = c->maxstates;
-          if (t1 && t2)
-          {
-            go.kind = 2;
-            a.ltip = pllhip_tip_ptr(c, op.child1_clv);
-            a.rtip = pllhip_tip_ptr(c, op.child2_clv);
-            a.lmat = mat(op.child1_matrix);
-            a.rmat = mat(op.child2_matrix);
-          }
-          else if (t1 || t2)
-          {
-            // the tip is presented as the left child (partials.c:91-112), as resolve_op does
-            go.kind = 1;
-            a.ltip = pllhip_tip_ptr(c, t1 ? op.child1_clv : op.child2_clv);
-            a.right = clv_of(t1 ? op.child2_clv : op.child1_clv);
-            a.lmat = mat(t1 ? op.child1_matrix : op.child2_matrix);
-            a.rmat = mat(t1 ? op.child2_matrix : op.child1_matrix);
-            a.rscaler = sc_of(t1 ? op.child2_scaler : op.child1_scaler);
-          }
-          else
-          {
-            go.kind = 0;
-            a.left = clv_of(op.child1_clv);
-            a.right = clv_of(op.child2_clv);
-            a.lmat = mat(op.child1_matrix);
-            a.rmat = mat(op.child2_matrix);
-            a.lscaler = sc_of(op.child1_scaler);
-            a.rscaler = sc_of(op.child2_scaler);
-          }
-          go.mode = !a.pscaler ? SCALE_NONE : (c->sh.rate_scalers ? SCALE_RATE : SCALE_SITE);
-          go.level = level;
+          auto operand = [&](unsigned int clv, int sc, unsigned int m) -> BatchOperand {
+            if (geom.is_tip(clv)) return {pllhip_tip_ptr(c, clv), nullptr, nullptr, mat(m)};
+            return {nullptr, clv_of(clv), sc_of(sc), mat(m)};
+          };
+          unsigned int * pscaler = op.parent_scaler >= 0 ? d_scal + at * c->scaler_stride : nullptr;
+          go.kind = pllhip_batch_fill_op(c, go.a, operand(op.child1_clv, op.child1_scaler, op.child1_matrix),
+                                         operand(op.child2_clv, op.child2_scaler, op.child2_matrix),
+                                         d_clv + at * c->clv_stride, pscaler);
+          go.mode = !pscaler ? SCALE_NONE : (c->sh.rate_scalers ? SCALE_RATE : SCALE_SITE);
           max_level = std::max(max_level, level);
           gen.push_back(go);
+          level_of.push_back(level);
           clv_at[op.parent_clv] = (int)at;
           if (op.parent_scaler >= 0) sc_at[op.parent_scaler] = (int)at;
         }
-        TsEdge he;
+        BatchEdge he;
         memset(&he, 0, sizeof(he));
         const unsigned int pc = cd.parent_clv_index, cc = cd.child_clv_index;
         const int ps = cd.parent_scaler_index, cs = cd.child_scaler_index;
@@ -1117,16 +886,11 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
       memset(&q, 0, sizeof(q));
       q.cands = d_cands;
       q.ops = d_ops;
-      q.freqs = c->freqs;
-      q.prop_invar = c->prop_invar;
-      q.rate_weights = c->rate_weights;
-      q.pattern_weights = c->pattern_weights;
-      q.invariant = c->any_prop_invar ? c->invariant : nullptr;
+      pllhip_batch_model(c, params, q.m);
       q.partial = d_part;
       q.sites = (unsigned int)sites;
       q.tiles = tiles;
       q.nslots = chunk_slots;
-      for (unsigned int k = 0; k < R; ++k) q.params[k] = params[k];
       const size_t lds = TS_HEAD_BYTES + 4u * TS_STAGE_BYTES + (size_t)chunk_slots * 4u * TS_SLOT_BYTES;
       const dim3 grid(tiles, (unsigned int)nkc);
       if (lds > 65536)
@@ -1140,37 +904,18 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
     }
     if (ngc)
     {
-      std::vector<unsigned int> ids;
       for (unsigned int level = 0; level <= max_level && !gen.empty(); ++level)
       {
-        ids.clear();
+        level_ops.clear();
         for (size_t q = 0; q < gen.size(); ++q)
-          if (gen[q].level == level) ids.push_back((unsigned int)q);
-        if ((rc = ts_run_level(c, gen, ids))) return rc;
+          if (level_of[q] == level) level_ops.push_back(gen[q]);
+        if ((rc = pllhip_batch_run_ops(c, level_ops.data(), level_ops.size()))) return rc;
       }
-      HIP_TRY(hipMemcpyAsync(d_edges, h_edges.data(), ngc * sizeof(TsEdge), hipMemcpyHostToDevice, c->stream));
-      TsGenArgs g;
-      memset(&g, 0, sizeof(g));
-      g.edges = d_edges;
-      g.freqs = c->freqs;
-      g.prop_invar = c->prop_invar;
-      g.rate_weights = c->rate_weights;
-      g.pattern_weights = c->pattern_weights;
-      g.invariant = c->any_prop_invar ? c->invariant : nullptr;
-      g.tipmap = c->tipmap;
-      g.partial = d_part;
-      g.sites = (unsigned int)sites;
-      g.states = S;
-      g.rate_cats = R;
-      g.tiles = tiles;
-      g.rate_scalers = (scaled && c->sh.rate_scalers) ? 1 : 0;
-      for (unsigned int k = 0; k < R; ++k) g.freqs_indices[k] = params[k];
+      HIP_TRY(hipMemcpyAsync(d_edges, h_edges.data(), ngc * sizeof(BatchEdge), hipMemcpyHostToDevice, c->stream));
       pllhip_prof_scope prof(c, PLLHIP_PROF_LNL);
-      k_tree_edge_lnl<<<dim3(tiles, (unsigned int)ngc), TS_TILE, 0, c->stream>>>(g);
-      HIP_TRY(hipGetLastError());
+      if ((rc = pllhip_batch_edge_lnl(c, d_edges, (unsigned int)ngc, params, d_part, tiles))) return rc;
     }
-    k_tree_reduce<<<(cn + 255) / 256, 256, 0, c->stream>>>(d_part, d_out, cn, tiles);
-    HIP_TRY(hipGetLastError());
+    if ((rc = pllhip_batch_reduce(c, d_part, d_out, cn, tiles))) return rc;
     hout.resize(cn);
     HIP_TRY(hipMemcpyAsync(hout.data(), d_out, (size_t)cn * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream)); // (the host vectors above are reused by the next chunk)
