@@ -31,8 +31,9 @@
 //   look-ahead  vector-memory loads and stores retire in ONE in-order queue, so a load
 //             issued after a store cannot be consumed before that store is acknowledged.
 //             Everything an op needs from memory (its two P-matrices) is therefore requested
-//             during the op two before it, ahead of that op's stores, with unconditional loads,
-//             and its pair-table entries are gathered during the op before it.
+//             during the op two before it, ahead of that op's stores, with an unconditional load,
+//             and its pair-table entries are gathered during the op before it -- only if it has a
+//             gathered factor, by loads the compiler does not count (see gather())
 //   characters  the tile's characters of up to 64 tip rows are fetched with ONE load at the top of
 //             the tile and kept in four registers; an op takes its own with v_readlane (round 3:
 //             per-op requests of two rows each were what held partitions beyond 33 GB at 0.5-0.57)
@@ -117,8 +118,8 @@ __device__ __forceinline__ unsigned int rec_pcnt(const Rec & r) { return r.w[15]
 // masksum4(P_r row, code 2) -- the very product the kernel would form per site (30 VALU
 // instructions per tip operand and sub-step) -- built by one small launch ahead of the
 // list and read back by the list kernel with one 16-byte gather per lane and sub-step
-// (32 KB per op at 4 rate categories: L2-resident).  Table 0 is all zeros: what ops without a
-// tip gather from (every op issues the same loads).
+// (32 KB per op at 4 rate categories: L2-resident).  An op without a gathered factor gathers
+// nothing and has no table.
 // (round 4: the launch also reset the tile counters of the list kernel behind it -- counter g is word 32 g, one
 // 128-byte line each -- which used to be a fill kernel of its own per call, 4.3 us; round 5: the list kernel resets
 // the set of counters of the launch BEHIND it, two sets in turn, and this launch no longer does)
@@ -413,25 +414,40 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       }
       return (word >> ((tip_lane & 3u) * 8u)) & 255u;
     };
-    // ... and ONE op ahead its entries of the pair table are gathered (table 0, all zeros, for an op
-    // without a tip; an absent tip's character is 0)
+    // ... and ONE op ahead its entries of the pair table are gathered -- by an op that HAS a gathered factor only (an
+    // absent tip's character is 0).  The characters' readlanes, the address arithmetic and the loads of a factor sit
+    // behind a wave-uniform branch on the record's CH_LTIP | CH_RTIP bits: an inner-inner op ahead costs a scalar test.
     // (deferred cherries: both characters of a pair may belong to ONE operand -- the cherry's two tips -- and an op
-    // whose two factors are both gathered, kind 3, takes the second one from a table of its own: every op issues that
-    // second gather too, from the table of zeros)
-    auto gather = [&](double2 (&pt)[J], double2 (&pt2)[J], const Rec & r) {
-      const unsigned int ch = rec_chars(r), ch2 = rec_chars2(r);
+    // whose two factors are both gathered, kind 3, takes the second one from a table of its own, behind a branch of
+    // its own; the instances that never defer -- 8 categories, per-rate scalers -- have no second gather at all)
+    // The loads are assembly, like reload(): a counted load under a branch would make the compiler drain the queue on
+    // every path.  Why nothing reads an entry before it is there: (1) the loads write the very registers the next op
+    // computes with (`+v`: no copy, which would read the register early) and the compiler, which sees no load, puts no
+    // instruction of its own on them before that op's arithmetic; (2) they are issued AHEAD of this op's request(),
+    // which is an ordinary counted load on every path; (3) vector-memory operations return in order, and the next op's
+    // first statement consumes that request -- a wait that leaves only what was issued after it in flight (this op's
+    // stores), so whatever was issued before it has arrived.  Uncounted operations can only make a counted wait
+    // stricter, never weaker.  An op whose factor is NOT gathered leaves the registers as they are; no kind reads them.
+    // (1) is the compiler's doing, not a guarantee of the language: after any change to step() or to the arrays read the
+    // assembly of an instance again -- between a gather and the next op's vmcnt wait nothing may move, copy or spill its
+    // destination registers (seen once: the arrays kept as one transposed 8-register value and re-packed right behind
+    // the loads, until both ends of their life were made whole 16-byte operands of an empty asm statement).
+    constexpr bool SECOND = RC <= 4 && MODE != SCALE_RATE; // (partials.hip: what may defer a cherry; checked by the launch)
+    auto gather_factor = [&](pll_v2d (&pt)[J], unsigned int ch, unsigned int table_off) {
       const unsigned int lmask = (ch & PLLHIP_FUSED_CH_LTIP) ? 15u : 0u, rmask = (ch & PLLHIP_FUSED_CH_RTIP) ? 15u : 0u;
-      const unsigned int lmask2 = (ch2 & PLLHIP_FUSED_CH_LTIP) ? 15u : 0u, rmask2 = (ch2 & PLLHIP_FUSED_CH_RTIP) ? 15u : 0u;
+      const unsigned long long tab = (unsigned long long)(uintptr_t)bases.pairtab + table_off; // (uniform)
 #pragma unroll
       for (unsigned int j = 0; j < J; ++j)
       {
         const unsigned int pair = ((row_code(PLLHIP_FUSED_CH_LPOS(ch), j) & lmask) << 4) | (row_code(PLLHIP_FUSED_CH_RPOS(ch), j) & rmask);
-        const unsigned int off = pair * (W * 16u) + gat_lane + rec_gather(r);
-        pt[j] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(bases.pairtab) + off);
-        const unsigned int pair2 = ((row_code(PLLHIP_FUSED_CH_LPOS(ch2), j) & lmask2) << 4) | (row_code(PLLHIP_FUSED_CH_RPOS(ch2), j) & rmask2);
-        const unsigned int off2 = pair2 * (W * 16u) + gat_lane + rec_gather2(r);
-        pt2[j] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(bases.pairtab) + off2);
+        const unsigned int off = pair * (W * 16u) + gat_lane;
+        asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pt[j]) : "v"(off), "s"(tab) : "memory");
       }
+    };
+    auto gather = [&](pll_v2d (&pt)[J], pll_v2d (&pt2)[J], const Rec & r) {
+      const unsigned int ch = rec_chars(r), ch2 = rec_chars2(r);
+      if (ch & (PLLHIP_FUSED_CH_LTIP | PLLHIP_FUSED_CH_RTIP)) gather_factor(pt, ch, rec_gather(r));
+      if (SECOND && (ch2 & (PLLHIP_FUSED_CH_LTIP | PLLHIP_FUSED_CH_RTIP))) gather_factor(pt2, ch2, rec_gather2(r));
       // the list moves on to rows this batch does not hold (rare: every 1024 / TS tip operands): the lanes'
       // addresses of the next batch, then its rows.  Assembly, like reload(): the compiler counts no load
       // here (a load inside a branch makes it wait for everything in flight on every path), the next op's
@@ -550,7 +566,16 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     Rec ra = rec_load(plan, 2), rb;
     FusedFetch<J> fa, fb;
     half_rows pl, pr;
-    double2 pta[J], ptb[J], pta2[J], ptb2[J];
+    // (the gathered entries: registers the assembly loads of gather() write in place -- zero once per tile, so that
+    // they are defined before the first gather; the previous tile's last op gathers nothing: nothing is in flight)
+    pll_v2d pta[J], ptb[J], pta2[J], ptb2[J];
+#pragma unroll
+    for (unsigned int j = 0; j < J; ++j)
+    {
+      pta[j] = ptb[j] = pta2[j] = ptb2[j] = pll_v2d{0.0, 0.0};
+      // (each a register pair of its own from here on, not a constant the compiler may form again wherever it likes)
+      asm volatile("" : "+v"(pta[j]), "+v"(ptb[j]), "+v"(pta2[j]), "+v"(ptb2[j]));
+    }
     // The prologue issues its memory operations in the order two ops would -- requests, gather,
     // stores (to the sink) -- because the compiler counts the operations issued after a load to
     // know how many may stay in flight when the load is consumed, and takes the minimum over
@@ -568,8 +593,9 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     request(fb, h0);
     sink_stores();
     if (rec_flags(h1) & PLLHIP_FUSED_RELOAD_NEXT) reload(rec_src(h1));
+    asm volatile("" ::"v"(cs)); // (the characters are waited for HERE on every path, whether op 0 gathers or not)
     gather(pta, pta2, h1);
-    if (EDGE) asm volatile("" : "+v"(edge_pw)); // (arrived with the characters the gather has just used: not a load any longer)
+    if (EDGE) asm volatile("" : "+v"(edge_pw)); // (arrived with the characters, requested ahead of them: not a load any longer)
     request(fa, h1);
     asm volatile("" ::"v"(fb.pm.x), "v"(fb.pm.y) : "memory");
     if (RC == 8) asm volatile("" ::"v"(fb.pm2.x), "v"(fb.pm2.y) : "memory");
@@ -580,8 +606,8 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     // ff: where that of op i+2 goes; pu: its pair-table entries, pf: where those of op i+1 go.
     // The caller alternates the two of each, so that nothing loaded is ever copied (a copy
     // would have to wait for the load).
-    auto step = [&](const Rec & r0, Rec & r1, const FusedFetch<J> & fu, FusedFetch<J> & ff, const double2 (&pu)[J],
-                    double2 (&pf)[J], const double2 (&pu2)[J], double2 (&pf2)[J], unsigned int i) __attribute__((always_inline)) {
+    auto step = [&](const Rec & r0, Rec & r1, const FusedFetch<J> & fu, FusedFetch<J> & ff, pll_v2d (&pu)[J],
+                    pll_v2d (&pf)[J], pll_v2d (&pu2)[J], pll_v2d (&pf2)[J], unsigned int i) __attribute__((always_inline)) {
       // A wave is the limit of this kernel, not HBM: with twelve waves per CU nothing hides
       // what a wave waits for itself (counters: ~2300 cycles per op of which ~500 issue
       // vector and ~270 scalar instructions).  So the order below overlaps the wave's own
@@ -632,11 +658,10 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       // (the request last: what the next op waits for first is the youngest operation in flight)
       gather(pf, pf2, r0);
       request(ff, r0);
-      // (every load is consumed on every path, needed or not: the registers of a load that
-      // nobody waited for stay "pending" for the compiler, and it drains the queue -- this op's
-      // predecessor's stores included -- when it next reuses them)
+      // (this op's gathered entries, as the registers they arrived in: whole 16-byte values on every path, so that the
+      // compiler has nothing to re-pack between the op that loaded them and here -- see gather())
 #pragma unroll
-      for (unsigned int j = 0; j < J; ++j) asm volatile("" ::"v"(pu[j].x), "v"(pu[j].y), "v"(pu2[j].x), "v"(pu2[j].y));
+      for (unsigned int j = 0; j < J; ++j) asm volatile("" : "+v"(pu[j]), "+v"(pu2[j]));
       unsigned long long scaled[J];
       double p0[J], p1[J];
       if (kind == 2)
@@ -1823,12 +1848,16 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   }
   const unsigned int R = c->sh.rate_cats;
   if (count > PLLHIP_FUSED_MAX_OPS || nsegs < 1 || nsegs > PLLHIP_FUSED_MAX_SEGS) return 1;
-  // pair tables of the ops with a tip (k_dna_pair_tables), carved from one device buffer behind a
-  // table of zeros
+  // pair tables of the ops with a gathered factor (k_dna_pair_tables), carved from one device buffer
+  // (the kernel instances of 8 categories and of per-rate scalers have no second gather: partials.hip defers nothing there)
   const size_t per = (size_t)256 * R * 4; // doubles per table
-  size_t ntab = 1;
+  size_t ntab = 0;
   for (const auto & plan : plans)
-    for (const FusedOp & f : plan) ntab += (f.kind >= 1) + (f.kind == 3);
+    for (const FusedOp & f : plan)
+    {
+      if (f.kind == 3 && (R > 4 || c->sh.rate_scalers)) return 1;
+      ntab += (f.kind >= 1) + (f.kind == 3);
+    }
   if (ntab * per * sizeof(double) > 0xffffffffull ||
       (size_t)c->sh.prob_matrices * c->pmat_elems * sizeof(double) > 0xffffffffull)
     return 1;
@@ -1838,7 +1867,6 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
     if (c->d_pairtab) HIP_TRY(hipFree(c->d_pairtab));
     c->d_pairtab = nullptr;
     HIP_TRY(hipMalloc((void **)&c->d_pairtab, ntab * per * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(c->d_pairtab, 0, per * sizeof(double), c->stream));
     c->pairtab_elems = ntab * per;
     ++c->layout_epoch;
   }
@@ -1901,7 +1929,7 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
           rowtab[(size_t)batch_of[pos] * 64 + lane0[o] + l] = (unsigned long long)(uintptr_t)rows[o] + l * 16u;
     }
   }
-  std::vector<unsigned int> table_of(n, 0), table2_of(n, 0); // byte offsets of each op's tables (0: zeros)
+  std::vector<unsigned int> table_of(n, 0), table2_of(n, 0); // byte offsets of each op's tables (read only where the op's chars say it gathers)
   for (unsigned int pos = 0; pos < n; ++pos)
   {
     const FusedOp & f = plan[pos];
@@ -1909,7 +1937,7 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
     {
       const FusedOperand & g = gx[pos].g[o];
       if (g.type == FUSED_G_NONE) continue;
-      const size_t index = jobs.size() + 1;
+      const size_t index = jobs.size();
       (o ? table2_of : table_of)[pos] = (unsigned int)(index * per * sizeof(double));
       double * tab = c->d_pairtab + index * per;
       if (g.type == FUSED_G_TIP) jobs.push_back(FusedPairJob{g.mat, nullptr, tab, 0ull, nullptr, nullptr});

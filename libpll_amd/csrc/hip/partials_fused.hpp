@@ -66,10 +66,10 @@ struct FusedRec
 {
   unsigned int chars;                    // tip characters of op + 1, PLLHIP_FUSED_CH_* below
   unsigned int chars2;                   // ... of its SECOND gather (kind 3), same layout (no CH_LOAD, no batch)
-  unsigned int gather_off2;              // byte offset of the second gather's table (0: the table of zeros)
+  unsigned int gather_off2;              // byte offset of the second gather's table (read only if chars2 has CH_LTIP | CH_RTIP)
   unsigned int pad;
   unsigned int req_lmat, req_rmat;       // byte offsets of its P-matrices in the matrix arena
-  unsigned int gather_off;               // byte offset of the pair table of op + 1 (0: the table of zeros)
+  unsigned int gather_off;               // byte offset of the pair table of op + 1 (read only if chars has CH_LTIP | CH_RTIP)
   unsigned int flags;                    // PLLHIP_FUSED_* below
   unsigned long long parent;             // CLV the op writes
   unsigned long long pscaler;            // its scale buffer (0: none)
