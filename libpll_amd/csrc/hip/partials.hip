@@ -722,6 +722,275 @@ extern "C" int pllhip_cert_stats(pllhip_ctx_t * c, unsigned long long * out4)
   return 0;
 }
 
+// ---- the 4-state whole-list path of pllhip_update_partials (kernel: partials_fused.hip; planner: fused_plan.hip) ----
+
+// What deferring cherries makes of a list (partials_fused.hpp: pllhip_fused_deferral).  The tip-tip ops
+// that a tree-like use allows are not run: their parents become deferred, their readers take a factor from a table.
+struct DnaListKept
+{
+  FusedDeferral dd;
+  std::vector<pllhip_op_t> ops;            // the ops the kernel runs (empty: the caller's list as it is)
+  std::vector<FusedExtra> extras;          // their gathered operands (empty: none -- nothing deferred, now or before)
+  std::vector<FusedPairJob> keep_jobs;     // the tables of the cherries this list defers
+  std::vector<unsigned int> new_deferred;  // {clv, tip1, tip2, scaler + 1} per deferred op
+};
+// args / kinds: resolve_op's of the caller's list in, of k.ops out (where k.ops is not empty).  Materialises what the
+// list cannot read from a table; every deferred CLV where nothing may be deferred.
+static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count, std::vector<PartialsArgs> & args,
+                          std::vector<int> & kinds, DnaListKept & k)
+{
+  FusedDeferral & dd = k.dd;
+  const bool may_defer = c->cherry_deferral && c->sh.pattern_tip && !c->sh.rate_scalers && c->sh.rate_cats <= 4;
+  if (!may_defer)
+  {
+    PLLHIP_DEFERRED_FLUSH(c);
+    return 0;
+  }
+  if (c->deferred.size() != c->clv.size()) c->deferred.assign(c->clv.size(), pllhip_ctx::deferred_clv());
+  if (c->deferred_sc_owner.size() != c->sh.scale_buffers) c->deferred_sc_owner.assign(c->sh.scale_buffers, -1);
+  if (c->clv_pinned.size() != c->clv.size()) c->clv_pinned.assign(c->clv.size(), 0);
+  std::vector<unsigned char> oldf(c->clv.size(), 0);
+  std::vector<int> oldsc(c->clv.size(), -1);
+  for (size_t i = 0; c->n_deferred && i < c->clv.size(); ++i)
+    if (c->deferred[i].on)
+    {
+      oldf[i] = 1;
+      oldsc[i] = c->deferred[i].scaler;
+    }
+  const FusedGeom g0 = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
+  pllhip_fused_deferral(g0, ops, count, oldf.data(), oldsc.data(), c->clv_pinned.data(), dd);
+  unsigned int ndefer = 0;
+  for (unsigned int i = 0; i < count; ++i) ndefer += dd.defer[i];
+  bool any_kept_table = false;
+  for (size_t i = 0; i < c->clv.size(); ++i) any_kept_table = any_kept_table || (dd.as_tip[i] && oldf[i]);
+  if (count - ndefer < 2 || ((ndefer || any_kept_table) && !pllhip_deferred_table(c, 0)))
+  {
+    // (too little left for a list kernel, or no room for the tables: ordinary buffers, ordinary ops)
+    PLLHIP_DEFERRED_FLUSH(c);
+    dd.defer.assign(count, 0);
+    dd.as_tip.assign(c->clv.size(), 0);
+    dd.dropped.clear();
+    return 0;
+  }
+  if (!dd.materialise.empty())
+  {
+    const int rc = pllhip_deferred_materialise(c, dd.materialise.data(), (int)dd.materialise.size());
+    if (rc) return rc;
+    for (unsigned int i : dd.materialise) dd.as_tip[i] = 0;
+  }
+  // one operand of a kept op as a gathered one: a tip, or a cherry deferred by this list / by an earlier call
+  std::vector<int> deferring_op(c->clv.size(), -1);
+  for (unsigned int i = 0; i < count; ++i)
+    if (dd.defer[i]) deferring_op[ops[i].parent_clv] = (int)i;
+  auto operand = [&](unsigned int clv, unsigned int matrix) {
+    FusedOperand g;
+    memset(&g, 0, sizeof(g));
+    g.mat = pllhip_pmat_ptr(c, matrix);
+    if (pllhip_is_tip(c, clv))
+    {
+      g.type = FUSED_G_TIP;
+      g.row1 = pllhip_tip_ptr(c, clv);
+    }
+    else if (deferring_op[clv] >= 0)
+    {
+      const pllhip_op_t & d = ops[deferring_op[clv]];
+      g.type = FUSED_G_CHERRY_NEW;
+      g.row1 = pllhip_tip_ptr(c, d.child1_clv);
+      g.row2 = pllhip_tip_ptr(c, d.child2_clv);
+      g.c_lmat = pllhip_pmat_ptr(c, d.child1_matrix);
+      g.c_rmat = pllhip_pmat_ptr(c, d.child2_matrix);
+    }
+    else
+    {
+      const pllhip_ctx::deferred_clv & d = c->deferred[clv];
+      g.type = FUSED_G_CHERRY_KEPT;
+      g.row1 = pllhip_tip_ptr(c, d.tip1);
+      g.row2 = pllhip_tip_ptr(c, d.tip2);
+      g.kept = pllhip_deferred_table(c, clv);
+    }
+    return g;
+  };
+  std::vector<PartialsArgs> kargs;
+  std::vector<int> kkinds;
+  for (unsigned int i = 0; i < count; ++i)
+  {
+    const pllhip_op_t & op = ops[i];
+    if (dd.defer[i])
+    {
+      k.keep_jobs.push_back(FusedPairJob{args[i].lmat, args[i].rmat, pllhip_deferred_table(c, op.parent_clv), 1ull, nullptr, nullptr});
+      k.new_deferred.insert(k.new_deferred.end(), {op.parent_clv, op.child1_clv, op.child2_clv, (unsigned int)(op.parent_scaler + 1)});
+      continue;
+    }
+    PartialsArgs a = args[i];
+    int kind = kinds[i];
+    FusedExtra x;
+    memset(&x, 0, sizeof(x));
+    const bool d1 = !pllhip_is_tip(c, op.child1_clv) && dd.as_tip[op.child1_clv];
+    const bool d2 = !pllhip_is_tip(c, op.child2_clv) && dd.as_tip[op.child2_clv];
+    if (d1 || d2)
+    {
+      const bool g1 = d1 || pllhip_is_tip(c, op.child1_clv), g2 = d2 || pllhip_is_tip(c, op.child2_clv);
+      a.left = a.right = nullptr;
+      a.ltip = a.rtip = nullptr;
+      a.lscaler = a.rscaler = nullptr;
+      if (g1 && g2)
+      {
+        kind = 3;
+        x.g[0] = operand(op.child1_clv, op.child1_matrix);
+        x.g[1] = operand(op.child2_clv, op.child2_matrix);
+      }
+      else
+      {
+        // the gathered operand plays the tip of a tip-inner op: "left"
+        kind = 1;
+        const unsigned int gathered = g1 ? op.child1_clv : op.child2_clv, inner = g1 ? op.child2_clv : op.child1_clv;
+        x.g[0] = operand(gathered, g1 ? op.child1_matrix : op.child2_matrix);
+        a.right = c->clv[inner];
+        a.lmat = pllhip_pmat_ptr(c, g1 ? op.child1_matrix : op.child2_matrix);
+        a.rmat = pllhip_pmat_ptr(c, g1 ? op.child2_matrix : op.child1_matrix);
+        a.rscaler = pllhip_scaler_ptr(c, g1 ? op.child2_scaler : op.child1_scaler);
+      }
+    }
+    k.ops.push_back(op);
+    kargs.push_back(a);
+    kkinds.push_back(kind);
+    k.extras.push_back(x);
+  }
+  args.swap(kargs);
+  kinds.swap(kkinds);
+  return 0;
+}
+
+// 4 states, more than one op, no site repeats: the whole list in one site-blocked launch.  *per_level = true: a list
+// shape the kernel does not take -- the per-level launches follow, on the caller's list with every deferral flushed;
+// else the call is over and the value returned is its result (0, or an error: HIP's are positive numbers).
+static int update_partials_dna_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsigned int full_count,
+                                    size_t fused_tile_sites, bool * per_level)
+{
+  *per_level = false;
+  // (deferred cherries: the kept plan stands for a set of deferred CLVs -- it is the same list only while none of
+  // them has been materialised, dropped or pinned since, defer_epoch; the launch then defers the same ones again)
+  // (the edge epilogue, ctx.hpp: edge_hint -- the kept plan stands for the hint it was built for, folded or not)
+  const bool edge_wanted = c->edge_fold && c->edge_hint_on && !c->is_shard && c->sh.rate_cats <= 4 && !c->sh.rate_scalers &&
+                           !c->asc_type && !c->sh.asc_states && !c->any_prop_invar && !c->comm;
+  if (c->fused_last_ops.size() == full_count && !c->fused_debug &&
+      c->fused_last_epoch == c->layout_epoch && c->fused_last_defer_epoch == c->defer_epoch &&
+      c->fused_last_hint_on == edge_wanted && (!edge_wanted || c->fused_last_hint == c->edge_hint) &&
+      memcmp(c->fused_last_ops.data(), full_ops, (size_t)full_count * sizeof(pllhip_op_t)) == 0)
+  {
+    pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
+    c->defer_stats[1] += c->fused_last_deferred.size() / 4;
+    const int rc = pllhip_relaunch_fused(c);
+    if (rc == 0 && c->fused_last_edge)
+    {
+      c->edge_terms_valid = true;
+      c->edge_terms_used = false;
+      c->edge_terms_req = c->fused_last_hint;
+      ++c->edge_stats[0];
+    }
+    return rc;
+  }
+  c->fused_last_ops.clear();
+  std::vector<PartialsArgs> args(full_count);
+  std::vector<int> kinds(full_count), modes(full_count);
+  for (unsigned int i = 0; i < full_count; ++i)
+  {
+    int rc = resolve_op(c, full_ops[i], args[i], kinds[i], modes[i]);
+    if (rc) return rc;
+  }
+  DnaListKept k;
+  int rc = defer_cherries(c, full_ops, full_count, args, kinds, k);
+  if (rc) return rc;
+  // (the caller's list: full_ops; the ops the kernel runs: ops)
+  const pllhip_op_t * const ops = k.ops.empty() ? full_ops : k.ops.data();
+  const unsigned int count = k.ops.empty() ? full_count : (unsigned int)k.ops.size();
+  const FusedExtra * const extras = k.extras.empty() ? nullptr : k.extras.data();
+  FusedGeom geom = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
+  if (extras) geom.as_tip = k.dd.as_tip.data();
+  // 12 waves per CU, else 8 (PLLHIP_FUSED_WGS=2: the 8-wave, 7-slot configuration at once -- tests run both)
+  const unsigned int slot_counts[2] = {pllhip_fused_slots(c, 3), pllhip_fused_slots(c, 2)};
+  const unsigned int skip = pllhip_env("PLLHIP_FUSED_WGS") && atoi(pllhip_env("PLLHIP_FUSED_WGS")) == 2 ? 1u : 0u;
+  // Round 5: independent sub-lists (the two sides of the root edge of a full traversal) as SEGMENTS of one launch
+  // -- (tile, segment) work items -- while the tiles alone do not fill the chip's wave slots eight times over:
+  // below that a launch's time is quantised by rounds of the list's length (partials_fused.hpp).
+  // PLLHIP_FUSED_SEGMENTS=0 / n: never / up to n whatever the size.
+  unsigned int max_segs = (size_t)c->sh.sites / fused_tile_sites < (size_t)c->num_cus * 12 * 8 ? PLLHIP_FUSED_MAX_SEGS : 1u;
+  if (const char * e = pllhip_env("PLLHIP_FUSED_SEGMENTS")) max_segs = (unsigned int)std::max(1, atoi(e));
+  // The edge epilogue (pllhip_fused_plan_list): the hinted evaluation, where the context has both ends as CLVs.  (What
+  // the list materialised first is no longer deferred here; its address handed out: anybody may write it.)
+  FusedEdge fedge;
+  memset(&fedge, 0, sizeof(fedge));
+  const pllhip_ctx::edge_req & q = c->edge_hint;
+  bool list_scales = false;
+  for (unsigned int i = 0; i < count; ++i) list_scales = list_scales || args[i].pscaler != nullptr;
+  const bool edge_ok = edge_wanted && q.parent_clv < c->clv.size() && q.child_clv < c->clv.size() && c->clv[q.parent_clv] &&
+                       c->clv[q.child_clv] && q.matrix_index < c->sh.prob_matrices && q.parent_scaler < (int)c->sh.scale_buffers &&
+                       q.child_scaler < (int)c->sh.scale_buffers && (list_scales || (q.parent_scaler < 0 && q.child_scaler < 0));
+  if (edge_ok)
+  {
+    const unsigned int ends[2] = {q.parent_clv, q.child_clv};
+    for (int t = 0; t < 2; ++t)
+    {
+      fedge.deferred_before[t] = ends[t] < c->deferred.size() && c->deferred[ends[t]].on;
+      fedge.pinned[t] = ends[t] < c->clv_pinned.size() && c->clv_pinned[ends[t]];
+    }
+    fedge.parent_clv = q.parent_clv;
+    fedge.child_clv = q.child_clv;
+    fedge.parent_scaler = q.parent_scaler;
+    fedge.child_scaler = q.child_scaler;
+    fedge.parent = c->clv[q.parent_clv];
+    fedge.child = c->clv[q.child_clv];
+    fedge.pscaler = pllhip_scaler_ptr(c, q.parent_scaler);
+    fedge.cscaler = pllhip_scaler_ptr(c, q.child_scaler);
+    fedge.pmat = pllhip_pmat_ptr(c, q.matrix_index);
+  }
+  FusedListPlan lp;
+  rc = pllhip_fused_plan_list(geom, ops, args.data(), kinds.data(), extras, count, max_segs, slot_counts + skip, 2u - skip,
+                              edge_ok ? &fedge : nullptr, k.dd, lp);
+  if (rc < 0) return rc;
+  if (rc == 0)
+  {
+    pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
+    // (the hint the plan stands for; the launch takes the frequencies' places from it)
+    c->fused_last_hint_on = edge_wanted;
+    c->fused_last_hint = c->edge_hint;
+    rc = pllhip_launch_fused(c, lp.plans, lp.nslots, k.keep_jobs.empty() ? nullptr : &k.keep_jobs, lp.folded ? &fedge : nullptr);
+    if (rc == 0)
+    {
+      if (lp.folded)
+      {
+        c->edge_terms_valid = true;
+        c->edge_terms_used = false;
+        c->edge_terms_req = c->edge_hint;
+        ++c->edge_stats[0];
+      }
+      // the deferrals this list ends and begins
+      for (unsigned int i : k.dd.dropped) pllhip_deferred_drop(c, i);
+      for (size_t t = 0; t < k.new_deferred.size(); t += 4)
+      {
+        const unsigned int clv = k.new_deferred[t];
+        const int sc = (int)k.new_deferred[t + 3] - 1;
+        pllhip_deferred_drop(c, clv);
+        pllhip_ctx::deferred_clv & d = c->deferred[clv];
+        d.on = true;
+        d.tip1 = k.new_deferred[t + 1];
+        d.tip2 = k.new_deferred[t + 2];
+        d.scaler = sc;
+        if (sc >= 0) c->deferred_sc_owner[sc] = (int)clv;
+        ++c->n_deferred;
+      }
+      c->defer_stats[1] += k.new_deferred.size() / 4;
+      c->fused_last_deferred = k.new_deferred;
+      c->fused_last_defer_epoch = c->defer_epoch;
+      c->fused_last_ops.assign(full_ops, full_ops + full_count);
+    }
+    if (rc <= 0) return rc;
+  }
+  *per_level = true;
+  return 0;
+}
+
+static int launch_levels(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count, bool dna_fast, bool aa_fast);
 extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops, unsigned int count)
 {
   PLLHIP_ALL_SHARDS_PAR(c, pllhip_update_partials(s, ops, count)); // (enqueued on every device; nothing waits)
@@ -793,308 +1062,9 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
   // round 3 they lost -- 3 ops 260 vs 200 us -- to the tile counter, not to their reloads: see the kernel.)
   if (dna_fast && (c->sh.rate_cats <= 4 || c->sh.rate_cats == 8) && !c->no_fused && fused_pays && c->rows.empty() && count >= 2)
   {
-    // (deferred cherries: the kept plan stands for a set of deferred CLVs -- it is the same list only while none of
-    // them has been materialised, dropped or pinned since, defer_epoch; the launch then defers the same ones again)
-    // (the edge epilogue, ctx.hpp: edge_hint -- the kept plan stands for the hint it was built for, folded or not)
-    const bool edge_wanted = c->edge_fold && c->edge_hint_on && !c->is_shard && c->sh.rate_cats <= 4 && !c->sh.rate_scalers &&
-                             !c->asc_type && !c->sh.asc_states && !c->any_prop_invar && !c->comm;
-    if (c->fused_last_ops.size() == count && !c->fused_debug &&
-        c->fused_last_epoch == c->layout_epoch && c->fused_last_defer_epoch == c->defer_epoch &&
-        c->fused_last_hint_on == edge_wanted && (!edge_wanted || c->fused_last_hint == c->edge_hint) &&
-        memcmp(c->fused_last_ops.data(), ops, (size_t)count * sizeof(pllhip_op_t)) == 0)
-    {
-      pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
-      c->defer_stats[1] += c->fused_last_deferred.size() / 4;
-      const int rc = pllhip_relaunch_fused(c);
-      if (rc == 0 && c->fused_last_edge)
-      {
-        c->edge_terms_valid = true;
-        c->edge_terms_used = false;
-        c->edge_terms_req = c->fused_last_hint;
-        ++c->edge_stats[0];
-      }
-      return rc;
-    }
-    c->fused_last_ops.clear();
-    const unsigned int full_count = count;       // (the caller's list; `ops` / `count` below: the ops the kernel runs)
-    const pllhip_op_t * const full_ops = ops;
-    std::vector<PartialsArgs> args(count);
-    std::vector<int> kinds(count), modes(count);
-    for (unsigned int i = 0; i < count; ++i)
-    {
-      int rc = resolve_op(c, ops[i], args[i], kinds[i], modes[i]);
-      if (rc) return rc;
-    }
-    // ---- deferred cherries (partials_fused.hpp: pllhip_fused_deferral).  The tip-tip ops of the list
-    // that a tree-like use allows are not run: their parents become deferred, their readers take a factor from a table.
-    FusedDeferral dd;
-    std::vector<pllhip_op_t> kept_ops;
-    std::vector<FusedExtra> extras;
-    std::vector<FusedPairJob> keep_jobs;
-    std::vector<unsigned int> new_deferred; // {clv, tip1, tip2, scaler + 1} per deferred op
-    const bool may_defer = c->cherry_deferral && c->sh.pattern_tip && !c->sh.rate_scalers && c->sh.rate_cats <= 4;
-    if (!may_defer) PLLHIP_DEFERRED_FLUSH(c);
-    if (may_defer)
-    {
-      if (c->deferred.size() != c->clv.size()) c->deferred.assign(c->clv.size(), pllhip_ctx::deferred_clv());
-      if (c->deferred_sc_owner.size() != c->sh.scale_buffers) c->deferred_sc_owner.assign(c->sh.scale_buffers, -1);
-      if (c->clv_pinned.size() != c->clv.size()) c->clv_pinned.assign(c->clv.size(), 0);
-      std::vector<unsigned char> oldf(c->clv.size(), 0);
-      std::vector<int> oldsc(c->clv.size(), -1);
-      for (size_t i = 0; c->n_deferred && i < c->clv.size(); ++i)
-        if (c->deferred[i].on)
-        {
-          oldf[i] = 1;
-          oldsc[i] = c->deferred[i].scaler;
-        }
-      const FusedGeom g0 = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
-      pllhip_fused_deferral(g0, ops, count, oldf.data(), oldsc.data(), c->clv_pinned.data(), dd);
-      unsigned int ndefer = 0;
-      for (unsigned int i = 0; i < count; ++i) ndefer += dd.defer[i];
-      bool any_kept_table = false;
-      for (size_t i = 0; i < c->clv.size(); ++i) any_kept_table = any_kept_table || (dd.as_tip[i] && oldf[i]);
-      if (count - ndefer < 2 || ((ndefer || any_kept_table) && !pllhip_deferred_table(c, 0)))
-      {
-        // (too little left for a list kernel, or no room for the tables: ordinary buffers, ordinary ops)
-        PLLHIP_DEFERRED_FLUSH(c);
-        dd.defer.assign(count, 0);
-        dd.as_tip.assign(c->clv.size(), 0);
-        dd.dropped.clear();
-      }
-      else
-      {
-        if (!dd.materialise.empty())
-        {
-          const int rc = pllhip_deferred_materialise(c, dd.materialise.data(), (int)dd.materialise.size());
-          if (rc) return rc;
-          for (unsigned int i : dd.materialise) dd.as_tip[i] = 0;
-        }
-        // one operand of a kept op as a gathered one: a tip, or a cherry deferred by this list / by an earlier call
-        std::vector<int> deferring_op(c->clv.size(), -1);
-        for (unsigned int i = 0; i < count; ++i)
-          if (dd.defer[i]) deferring_op[ops[i].parent_clv] = (int)i;
-        auto operand = [&](unsigned int clv, unsigned int matrix) {
-          FusedOperand g;
-          memset(&g, 0, sizeof(g));
-          g.mat = pllhip_pmat_ptr(c, matrix);
-          if (pllhip_is_tip(c, clv))
-          {
-            g.type = FUSED_G_TIP;
-            g.row1 = pllhip_tip_ptr(c, clv);
-          }
-          else if (deferring_op[clv] >= 0)
-          {
-            const pllhip_op_t & d = ops[deferring_op[clv]];
-            g.type = FUSED_G_CHERRY_NEW;
-            g.row1 = pllhip_tip_ptr(c, d.child1_clv);
-            g.row2 = pllhip_tip_ptr(c, d.child2_clv);
-            g.c_lmat = pllhip_pmat_ptr(c, d.child1_matrix);
-            g.c_rmat = pllhip_pmat_ptr(c, d.child2_matrix);
-          }
-          else
-          {
-            const pllhip_ctx::deferred_clv & d = c->deferred[clv];
-            g.type = FUSED_G_CHERRY_KEPT;
-            g.row1 = pllhip_tip_ptr(c, d.tip1);
-            g.row2 = pllhip_tip_ptr(c, d.tip2);
-            g.kept = pllhip_deferred_table(c, clv);
-          }
-          return g;
-        };
-        std::vector<PartialsArgs> kargs;
-        std::vector<int> kkinds;
-        for (unsigned int i = 0; i < count; ++i)
-        {
-          const pllhip_op_t & op = ops[i];
-          if (dd.defer[i])
-          {
-            keep_jobs.push_back(FusedPairJob{args[i].lmat, args[i].rmat, pllhip_deferred_table(c, op.parent_clv), 1ull, nullptr, nullptr});
-            new_deferred.insert(new_deferred.end(), {op.parent_clv, op.child1_clv, op.child2_clv, (unsigned int)(op.parent_scaler + 1)});
-            continue;
-          }
-          PartialsArgs a = args[i];
-          int kind = kinds[i];
-          FusedExtra x;
-          memset(&x, 0, sizeof(x));
-          const bool d1 = !pllhip_is_tip(c, op.child1_clv) && dd.as_tip[op.child1_clv];
-          const bool d2 = !pllhip_is_tip(c, op.child2_clv) && dd.as_tip[op.child2_clv];
-          if (d1 || d2)
-          {
-            const bool g1 = d1 || pllhip_is_tip(c, op.child1_clv), g2 = d2 || pllhip_is_tip(c, op.child2_clv);
-            a.left = a.right = nullptr;
-            a.ltip = a.rtip = nullptr;
-            a.lscaler = a.rscaler = nullptr;
-            if (g1 && g2)
-            {
-              kind = 3;
-              x.g[0] = operand(op.child1_clv, op.child1_matrix);
-              x.g[1] = operand(op.child2_clv, op.child2_matrix);
-            }
-            else
-            {
-              // the gathered operand plays the tip of a tip-inner op: "left"
-              kind = 1;
-              const unsigned int gathered = g1 ? op.child1_clv : op.child2_clv, inner = g1 ? op.child2_clv : op.child1_clv;
-              x.g[0] = operand(gathered, g1 ? op.child1_matrix : op.child2_matrix);
-              a.right = c->clv[inner];
-              a.lmat = pllhip_pmat_ptr(c, g1 ? op.child1_matrix : op.child2_matrix);
-              a.rmat = pllhip_pmat_ptr(c, g1 ? op.child2_matrix : op.child1_matrix);
-              a.rscaler = pllhip_scaler_ptr(c, g1 ? op.child2_scaler : op.child1_scaler);
-            }
-          }
-          kept_ops.push_back(op);
-          kargs.push_back(a);
-          kkinds.push_back(kind);
-          extras.push_back(x);
-        }
-        args.swap(kargs);
-        kinds.swap(kkinds);
-        ops = kept_ops.data();
-        count = (unsigned int)kept_ops.size();
-      }
-    }
-    // Three workgroups per CU (12 waves) hide the per-op latencies better than two, but
-    // leave one LDS slot less per wave (6 against 7 at 4 rate categories): the 12-wave
-    // configuration whenever the planner can keep every operand in a slot with it (values
-    // that give their slot up, and operands written by earlier calls, are copied back from
-    // HBM by LDS-DMA one op ahead).  A list the planner does not take -- counts that were not
-    // written together with their CLV -- runs per level.
-    FusedGeom geom = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
-    if (!extras.empty()) geom.as_tip = dd.as_tip.data();
-    // (PLLHIP_FUSED_WGS=2: the 8-wave, 7-slot configuration at once -- tests run both)
-    const unsigned int first_wgs = pllhip_env("PLLHIP_FUSED_WGS") && atoi(pllhip_env("PLLHIP_FUSED_WGS")) == 2 ? 2u : 3u;
-    // Round 5: independent sub-lists (the two sides of the root edge of a full traversal) as SEGMENTS of one launch
-    // -- (tile, segment) work items -- while the tiles alone do not fill the chip's wave slots eight times over:
-    // below that a launch's time is quantised by rounds of the list's length (partials_fused.hpp).
-    // PLLHIP_FUSED_SEGMENTS=0 / n: never / up to n whatever the size.
-    unsigned int max_segs = (size_t)c->sh.sites / fused_tile_sites < (size_t)c->num_cus * 12 * 8 ? PLLHIP_FUSED_MAX_SEGS : 1u;
-    if (const char * e = pllhip_env("PLLHIP_FUSED_SEGMENTS")) max_segs = (unsigned int)std::max(1, atoi(e));
-    std::vector<unsigned int> seg_of;
-    unsigned int nsegs = pllhip_fused_segments(geom, ops, count, max_segs, seg_of);
-    std::vector<std::vector<FusedOp>> fplans;
-    unsigned int nslots = 0;
-    int rc = 1;
-    for (; rc > 0; nsegs = 1) // (segments the planner does not take: once more as one list)
-    {
-      for (unsigned int wgs = first_wgs; rc > 0 && wgs >= 2u; --wgs)
-      {
-        nslots = pllhip_fused_slots(c, wgs);
-        fplans.assign(nsegs, std::vector<FusedOp>());
-        rc = 0;
-        for (unsigned int sg = 0; sg < nsegs && rc == 0; ++sg)
-        {
-          unsigned int reloads = 0;
-          if (nsegs == 1)
-          {
-            rc = pllhip_fused_plan(geom, ops, args.data(), kinds.data(), count, nslots, fplans[0], &reloads,
-                                   extras.empty() ? nullptr : extras.data());
-            continue;
-          }
-          std::vector<pllhip_op_t> sops;
-          std::vector<PartialsArgs> sargs;
-          std::vector<FusedExtra> sextras;
-          std::vector<int> skinds, where;
-          for (unsigned int i = 0; i < count; ++i)
-            if (seg_of[i] == sg)
-            {
-              sops.push_back(ops[i]);
-              sargs.push_back(args[i]);
-              skinds.push_back(kinds[i]);
-              if (!extras.empty()) sextras.push_back(extras[i]);
-              where.push_back((int)i);
-            }
-          rc = pllhip_fused_plan(geom, sops.data(), sargs.data(), skinds.data(), (unsigned int)sops.size(), nslots, fplans[sg], &reloads,
-                                 sextras.empty() ? nullptr : sextras.data());
-          for (FusedOp & f : fplans[sg]) f.list_pos = where[f.list_pos];
-        }
-      }
-      if (nsegs == 1) break;
-    }
-    if (rc < 0) return rc;
-    // The edge epilogue: the hinted evaluation as a pseudo-op behind the last op -- one segment only, at the
-    // configuration the unfolded plan has just taken (never fewer waves for its sake), both ends ordinary stored CLVs
-    // of which the list writes at least one.  A planner that refuses leaves the unfolded plan as it is.
-    FusedEdge fedge;
-    bool folded = false;
-    if (rc == 0 && edge_wanted && fplans.size() == 1) // (fplans: what was planned -- the loop above leaves nsegs at 1)
-    {
-      const pllhip_ctx::edge_req & q = c->edge_hint;
-      // (an end the list reads or leaves as a table is no CLV in HBM; one deferred earlier still is none unless this
-      // list overwrites it with an ordinary op)
-      // (partials_fused.hpp: the one rule, shared with the dry planner.  What the list materialised first is no
-      // longer deferred here; its address handed out: anybody may write it)
-      auto stored = [&](unsigned int i) {
-        return i < c->clv.size() && c->clv[i] &&
-               pllhip_fused_edge_end_stored(geom, dd, i, i < c->deferred.size() && c->deferred[i].on,
-                                            i < c->clv_pinned.size() && c->clv_pinned[i]);
-      };
-      bool list_scales = false;
-      for (unsigned int i = 0; i < count; ++i) list_scales = list_scales || args[i].pscaler != nullptr;
-      if (stored(q.parent_clv) && stored(q.child_clv) && q.matrix_index < c->sh.prob_matrices &&
-          q.parent_scaler < (int)c->sh.scale_buffers && q.child_scaler < (int)c->sh.scale_buffers &&
-          (list_scales || (q.parent_scaler < 0 && q.child_scaler < 0)))
-      {
-        memset(&fedge, 0, sizeof(fedge));
-        fedge.parent_clv = q.parent_clv;
-        fedge.child_clv = q.child_clv;
-        fedge.parent_scaler = q.parent_scaler;
-        fedge.child_scaler = q.child_scaler;
-        fedge.parent = c->clv[q.parent_clv];
-        fedge.child = c->clv[q.child_clv];
-        fedge.pscaler = pllhip_scaler_ptr(c, q.parent_scaler);
-        fedge.cscaler = pllhip_scaler_ptr(c, q.child_scaler);
-        fedge.pmat = pllhip_pmat_ptr(c, q.matrix_index);
-        std::vector<FusedOp> with_edge;
-        unsigned int reloads = 0;
-        if (pllhip_fused_plan(geom, ops, args.data(), kinds.data(), count, nslots, with_edge, &reloads,
-                              extras.empty() ? nullptr : extras.data(), &fedge) == 0)
-        {
-          fplans[0].swap(with_edge);
-          folded = true;
-        }
-      }
-    }
-    if (rc == 0)
-    {
-      pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
-      // (the hint the plan stands for; the launch takes the frequencies' places from it)
-      c->fused_last_hint_on = edge_wanted;
-      c->fused_last_hint = c->edge_hint;
-      rc = pllhip_launch_fused(c, fplans, nslots, keep_jobs.empty() ? nullptr : &keep_jobs, folded ? &fedge : nullptr);
-      if (rc == 0)
-      {
-        if (folded)
-        {
-          c->edge_terms_valid = true;
-          c->edge_terms_used = false;
-          c->edge_terms_req = c->edge_hint;
-          ++c->edge_stats[0];
-        }
-        // the deferrals this list ends and begins
-        for (unsigned int i : dd.dropped) pllhip_deferred_drop(c, i);
-        for (size_t t = 0; t < new_deferred.size(); t += 4)
-        {
-          const unsigned int clv = new_deferred[t];
-          const int sc = (int)new_deferred[t + 3] - 1;
-          pllhip_deferred_drop(c, clv);
-          pllhip_ctx::deferred_clv & d = c->deferred[clv];
-          d.on = true;
-          d.tip1 = new_deferred[t + 1];
-          d.tip2 = new_deferred[t + 2];
-          d.scaler = sc;
-          if (sc >= 0) c->deferred_sc_owner[sc] = (int)clv;
-          ++c->n_deferred;
-        }
-        c->defer_stats[1] += new_deferred.size() / 4;
-        c->fused_last_deferred = new_deferred;
-        c->fused_last_defer_epoch = c->defer_epoch;
-        c->fused_last_ops.assign(full_ops, full_ops + full_count);
-      }
-      if (rc <= 0) return rc;
-    }
-    // (a list shape the kernel does not take: per-level launches below, on ordinary buffers)
-    ops = full_ops;
-    count = full_count;
+    bool per_level = false;
+    const int rc = update_partials_dna_list(c, ops, count, fused_tile_sites, &per_level);
+    if (!per_level) return rc;
   }
   PLLHIP_DEFERRED_FLUSH(c);
 
@@ -1222,6 +1192,15 @@ extern "C" int pllhip_update_partials(pllhip_ctx_t * c, const pllhip_op_t * ops,
     lc.epoch = c->layout_epoch;
   }
   } // !plan_kept
+  return launch_levels(c, ops, count, dna_fast, aa_fast);
+}
+
+// The launches of pllhip_update_partials' per-level path, from the plan in the level cache.
+static int launch_levels(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count, bool dna_fast, bool aa_fast)
+{
+  const std::vector<pllhip_planned_op> & plan = c->level_cache->plan;
+  const std::vector<PartialsArgs> & by_pos = c->level_cache->by_pos;
+  const std::vector<std::pair<int, int>> & cherry_kids = c->level_cache->cherry;
 
   // The scaling certificate on this path: its kernels work in the reference's order, so a value is marked only when
   // an operand is; the marks are walked in list order, and an op that scales a marked value tests (k_aa_ii_mfma).

@@ -1334,37 +1334,15 @@ static int aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int
   if (const char * e = pllhip_env("PLLHIP_FUSED_SEGMENTS")) max_segs = (unsigned int)std::max(1, atoi(e));
   std::vector<unsigned int> seg_of, seg_first, seg_n;
   const unsigned int nsegs = pllhip_fused_segments(geom, rops.data(), n, max_segs, seg_of);
-  int rc = 0;
-  if (nsegs == 1)
+  std::vector<std::vector<FusedOp>> seg_plans;
+  int rc = pllhip_fused_plan_segments(geom, rops.data(), rargs.data(), rkinds.data(), nullptr, n, seg_of.data(), nsegs, AF_NSLOT,
+                                      seg_plans, &reloads);
+  for (unsigned int sg = 0; rc == 0 && sg < nsegs; ++sg)
   {
-    rc = pllhip_fused_plan(geom, rops.data(), rargs.data(), rkinds.data(), n, AF_NSLOT, fplan, &reloads);
-    seg_first.push_back(0u);
-    seg_n.push_back(n);
-  }
-  for (unsigned int sg = 0; nsegs > 1 && sg < nsegs && rc == 0; ++sg)
-  {
-    std::vector<pllhip_op_t> sops;
-    std::vector<PartialsArgs> sargs;
-    std::vector<int> skinds, where;
-    for (unsigned int i = 0; i < n; ++i)
-      if (seg_of[i] == sg)
-      {
-        sops.push_back(rops[i]);
-        sargs.push_back(rargs[i]);
-        skinds.push_back(rkinds[i]);
-        where.push_back((int)i);
-      }
-    std::vector<FusedOp> part;
-    unsigned int r = 0;
-    rc = pllhip_fused_plan(geom, sops.data(), sargs.data(), skinds.data(), (unsigned int)sops.size(), AF_NSLOT, part, &r);
-    reloads += r;
     seg_first.push_back((unsigned int)fplan.size());
-    seg_n.push_back((unsigned int)part.size());
-    for (FusedOp & f : part)
-    {
-      f.list_pos = where[f.list_pos];
-      fplan.push_back(f);
-    }
+    seg_n.push_back((unsigned int)seg_plans[sg].size());
+    if (sg == 0) fplan.swap(seg_plans[0]); // (one segment: no copy)
+    else fplan.insert(fplan.end(), seg_plans[sg].begin(), seg_plans[sg].end());
   }
   if (rc) return rc;
   lap("plan (order, slots)");

@@ -18,12 +18,7 @@
 //
 //   tile      J sub-steps of 64 lanes x 16 B (J x 64 / (2 rate_cats) sites)
 //   slots     tiles per wave in LDS (6 x 2.1 KB for 4 rate categories on 12 waves per CU, 7 on 8); the
-//             host assigns them: a value keeps its slot until its last reader in the list has run
-//   op order  any order that respects the list's read/write hazards on CLV and scale
-//             buffer indices is equivalent; the host re-orders the list depth-first,
-//             heavier subtree first (Sethi-Ullman), which bounds the number of live
-//             values by the tree's Strahler number (5 for a balanced 64-taxon tree, 6 for 128
-//             taxa, not the 32 / 64 of a level-by-level list)
+//             host assigns them, and orders the ops so that few suffice (fused_plan.hip: the planner)
 //   reload    EVERY inner operand is read from a slot.  A value that had to give its slot up
 //             (random trees: a handful per list), and every operand written by an earlier call
 //             (partial traversals; tip CLVs), is copied from HBM into a slot by LDS-DMA
@@ -58,7 +53,6 @@
 #include <algorithm>
 #include <stdio.h>
 #include <stdlib.h>
-#include <memory_resource>
 #include <vector>
 
 #include "ctx.hpp"
@@ -837,772 +831,12 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
   }
 }
 
-// ---------------------------------------------------------------- host: order, slots, launch
+// ---------------------------------------------------------------- host: encode, launch
+// (order and slots: fused_plan.hip)
 
-namespace
-{
-// (round 4) The planner's many small lists -- hazard predecessors, readers per buffer, uses per value -- come from a
-// bump allocator over a per-thread buffer: as std::vectors on the heap they were most of its time (0.32 us per op,
-// 20 us for BASELINE config 2's 62-op list, 75 us for a 198-op list; VERDICT r3 Weak 6: tree search hands over a new
-// list almost every call).
-typedef std::pmr::vector<unsigned int> PlanList;
-typedef std::pmr::vector<PlanList> PlanLists;
-struct Node
-{
-  int raw[2] = {-1, -1};          // producers of the two children within the list (-1: outside)
-  int sraw[2] = {-1, -1};         // writers of the two child scale buffers within the list
-  unsigned int need = 1;          // Sethi-Ullman number of the subtree rooted here
-};
-}
-
-// slots per wave when `wgs` workgroups of four waves share a CU's LDS: 64 KB per workgroup
-// for two (8 waves per CU), 52 KB for three (12 waves: better latency hiding, one slot less)
-static unsigned int fused_slots_for(unsigned int R, bool rate_scalers, unsigned int wgs);
 unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int wgs)
 {
-  return fused_slots_for(c->sh.rate_cats, c->sh.rate_scalers != 0, wgs);
-}
-
-static unsigned int fused_slots_for(unsigned int R, bool rate_scalers, unsigned int wgs)
-{
-  // 64 KB per workgroup of four waves: 16 KB per wave minus the matrix block
-  const unsigned int sps = 64 / (2 * R);
-  const size_t cw = rate_scalers ? 32 : (sps < 4 ? 4 : sps);
-  const size_t per_slot = (size_t)PLLHIP_FUSED_J * (64 * 16 + cw * 4);
-  const size_t pmat = (size_t)R * 16 * sizeof(double); // one matrix at a time (stage_rows)
-  // (four workgroups -- 16 waves of 128 registers, four slots -- were measured for short lists in round 3 and are
-  // slower than three at every list length: 2 / 3 / 5 / 7 / 15 ops 257 / 286 / 335 / 282 / 421 us against 226 / 260 /
-  // 310 / 246 / 411; the variant spills seven registers)
-  const size_t budget = wgs >= 3 ? 13312 : 16384;
-  return (unsigned int)((budget - pmat) / per_slot);
-}
-
-// Slot assignment: every inner operand is read from a slot.  A value whose
-// slot was taken away (or that an earlier call wrote) is copied back from HBM into a slot by
-// the kernel's reload() at the top of the op BEFORE its reader; that slot must be free from
-// then on (not read by that op, not its parent's).  Belady's rule decides who gives a slot up:
-// the live value whose next reader is farthest away.
-static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args,
-                               const int * kinds, unsigned int count, unsigned int nslots,
-                               const std::vector<unsigned int> & order, const std::vector<unsigned int> & pos_of,
-                               const std::vector<Node> & node, std::vector<FusedOp> & plan,
-                               unsigned int * reloads_out, std::pmr::memory_resource * pool, const FusedExtra * extra,
-                               FusedEdge * edge, const int * edge_raw, const int * edge_sraw)
-{
-  // the edge pseudo-op (FusedEdge): position `count`, list index `count` -- it reads two values and writes none
-  const unsigned int total = count + (edge ? 1u : 0u);
-  // inner operands of the op at each position: producing list op (-1: written by an earlier
-  // call), its HBM address, the HBM address of the counts the reader passes with it, and the
-  // list op that wrote those counts
-  struct Operand { int w; const double * hbm; const unsigned int * sc; int sw; };
-  auto operands = [&](unsigned int i, Operand (&o)[2]) {
-    o[0] = o[1] = Operand{-2, nullptr, nullptr, -1}; // -2: no such operand (a tip)
-    if (i == count)
-    {
-      o[0] = Operand{edge_raw[0], edge->parent, edge->pscaler, edge_sraw[0]};
-      o[1] = Operand{edge_raw[1], edge->child, edge->cscaler, edge_sraw[1]};
-    }
-    else if (kinds[i] == 0)
-    {
-      o[0] = Operand{node[i].raw[0], args[i].left, args[i].lscaler, node[i].sraw[0]};
-      o[1] = Operand{node[i].raw[1], args[i].right, args[i].rscaler, node[i].sraw[1]};
-    }
-    else if (kinds[i] == 1)
-    {
-      const int inner = geom.is_tip(ops[i].child1_clv) ? 1 : 0;
-      o[1] = Operand{node[i].raw[inner], args[i].right, args[i].rscaler, node[i].sraw[inner]};
-    }
-  };
-  PlanLists uses(count, pool); // positions at which each list value is read
-  for (unsigned int pos = 0; pos < total; ++pos)
-  {
-    Operand o[2];
-    operands(pos < count ? order[pos] : count, o);
-    if (o[0].w >= 0) uses[o[0].w].push_back(pos);
-    if (o[1].w >= 0 && o[1].w != o[0].w) uses[o[1].w].push_back(pos);
-  }
-  std::vector<unsigned int> next_use(count, 0);
-  std::vector<int> slot_of(count, -1);
-  std::vector<int> free_slots;
-  for (int s = (int)nslots - 1; s >= 0; --s) free_slots.push_back(s);
-  std::vector<unsigned int> live;          // list values that hold a slot
-  std::vector<int> oneshot, oneshot_next;  // slots of operands from earlier calls (of this op / the next): free after their one reader
-  unsigned int reloads = 0;
-  const unsigned int NEVER = ~0u;
-  auto next_read = [&](unsigned int v) { return next_use[v] < uses[v].size() ? uses[v][next_use[v]] : NEVER; };
-  // a slot that may be written from position `pos` on: a free one, else that of the live
-  // value read farthest in the future -- but not before pos + 2 (its own reload is issued at
-  // the top of the op before its reader and needs a slot free by then)
-  auto take_slot = [&](unsigned int pos) -> int {
-    if (!free_slots.empty())
-    {
-      const int s = free_slots.back();
-      free_slots.pop_back();
-      return s;
-    }
-    int victim = -1;
-    unsigned int far = 0;
-    for (unsigned int v : live)
-    {
-      const unsigned int u = next_read(v);
-      if (u != NEVER && u >= pos + 2 && u >= far)
-      {
-        far = u;
-        victim = (int)v;
-      }
-    }
-    if (victim < 0) return -1;
-    const int s = slot_of[victim];
-    slot_of[victim] = -1;
-    live.erase(std::find(live.begin(), live.end(), (unsigned int)victim));
-    return s;
-  };
-  // operands of the op at position `pos` that are not in a slot: reloaded at the top of
-  // position pos - 1 (`at`; the kernel's prologue for pos 0)
-  auto place_reloads = [&](unsigned int pos, unsigned int at) -> int {
-    const unsigned int i = pos < count ? order[pos] : count;
-    FusedOp & f = pos < count ? plan[pos] : edge->op;
-    Operand o[2];
-    operands(i, o);
-    for (int side = 0; side < 2; ++side)
-    {
-      const Operand & x = o[side];
-      if (x.w == -2) continue;
-      if (side == 1 && x.w >= 0 && x.w == o[0].w) continue; // the same value twice: one slot
-      if (x.w >= 0 && (pos_of[x.w] >= at || slot_of[x.w] >= 0)) continue; // still to come, or in a slot
-      if (x.w >= 0 && pos_of[x.w] + 2 >= pos) return 1; // (cannot happen: evicted values are read later)
-      const int s = take_slot(at);
-      if (s < 0) return 1;
-      ++reloads;
-      const unsigned int * counts = nullptr;
-      if (x.w >= 0)
-      {
-        // a value of this list: its counts are those its producer wrote, whoever reads it
-        counts = args[x.w].pscaler;
-        slot_of[x.w] = s;
-        live.push_back((unsigned int)x.w);
-      }
-      else
-      {
-        // written by an earlier call: the counts the reader passes, which no op of this list
-        // may have rewritten shortly before
-        if (x.sc && x.sw >= 0 && pos_of[x.sw] + 2 >= pos) return 1;
-        counts = x.sc;
-        oneshot_next.push_back(s);
-      }
-      if (side == 0) { f.left_hbm = x.hbm; f.lsc_hbm = counts; f.lslot = s; f.dma_flags |= 1; }
-      else { f.right_hbm = x.hbm; f.rsc_hbm = counts; f.rslot = s; f.dma_flags |= 2; }
-    }
-    return 0;
-  };
-
-  plan.resize(count);
-  for (unsigned int pos = 0; pos < count; ++pos)
-  {
-    const unsigned int i = order[pos];
-    const PartialsArgs & a = args[i];
-    FusedOp & f = plan[pos];
-    memset(&f, 0, sizeof(f));
-    f.parent = a.parent;
-    f.ltip = a.ltip;
-    f.rtip = a.rtip;
-    f.lmat = a.lmat;
-    f.rmat = a.rmat;
-    f.pscaler = a.pscaler;
-    f.kind = kinds[i];
-    f.list_pos = (int)i;
-    f.lslot = f.rslot = f.pslot = f.lsc_slot = f.rsc_slot = -1;
-    if (extra)
-    {
-      f.g[0] = extra[i].g[0];
-      f.g[1] = extra[i].g[1];
-    }
-  }
-  if (edge)
-  {
-    memset(&edge->op, 0, sizeof(edge->op));
-    edge->op.kind = PLLHIP_FUSED_KIND_EDGE;
-    edge->op.list_pos = (int)count;
-    edge->op.lslot = edge->op.rslot = edge->op.pslot = edge->op.lsc_slot = edge->op.rsc_slot = -1;
-  }
-  if (place_reloads(0, 0)) return 1;
-  oneshot.swap(oneshot_next);
-  for (unsigned int pos = 0; pos < total; ++pos)
-  {
-    const unsigned int i = pos < count ? order[pos] : count;
-    FusedOp & f = pos < count ? plan[pos] : edge->op;
-    // top of the op: the next op's missing operands are requested into slots free NOW
-    if (pos + 1 < total && place_reloads(pos + 1, pos)) return 1;
-    Operand o[2];
-    operands(i, o);
-    for (int side = 0; side < 2; ++side)
-    {
-      const Operand & x = o[side];
-      if (x.w == -2) continue;
-      int & slot = side == 0 ? f.lslot : f.rslot;
-      int & sc_slot = side == 0 ? f.lsc_slot : f.rsc_slot;
-      if (x.w >= 0)
-      {
-        if (slot < 0) slot = slot_of[x.w];
-        if (slot < 0) return 1;
-        // counts: only those written together with the value live in its slot
-        if (x.sc)
-        {
-          if (x.sw != x.w || x.sc != args[x.w].pscaler) return 1;
-          sc_slot = slot;
-        }
-      }
-      else
-      {
-        if (slot < 0) return 1; // (placed by place_reloads)
-        if (x.sc) sc_slot = slot;
-      }
-    }
-    if (pos == count) break; // (the edge pseudo-op: nothing runs after it, and it writes no value)
-    // operands read for the last time give their slots back
-    for (int side = 0; side < 2; ++side)
-    {
-      const int w = o[side].w;
-      if (w < 0 || (side == 1 && w == o[0].w)) continue;
-      if (next_use[w] < uses[w].size() && uses[w][next_use[w]] == pos) next_use[w]++;
-      if (next_use[w] >= uses[w].size() && slot_of[w] >= 0)
-      {
-        free_slots.push_back(slot_of[w]);
-        slot_of[w] = -1;
-        live.erase(std::find(live.begin(), live.end(), (unsigned int)w));
-      }
-    }
-    for (int s : oneshot) free_slots.push_back(s);
-    oneshot.clear();
-    oneshot.swap(oneshot_next);
-    // the parent: a slot if it has readers -- unless its first reader is far enough away for a
-    // reload (three ops: its stores must have left) and farther than every live value's next
-    if (!uses[i].empty())
-    {
-      const unsigned int first = uses[i][0];
-      bool wants = true;
-      if (free_slots.empty() && first >= pos + 3)
-      {
-        unsigned int far = 0;
-        for (unsigned int v : live)
-        {
-          const unsigned int u = next_read(v);
-          if (u != NEVER && u >= pos + 2 && u > far) far = u;
-        }
-        if (first >= far) wants = false;
-      }
-      if (wants)
-      {
-        const int s = take_slot(pos);
-        if (s < 0)
-        {
-          if (first < pos + 3) return 1;
-        }
-        else
-        {
-          f.pslot = s;
-          slot_of[i] = s;
-          live.push_back(i);
-        }
-      }
-    }
-  }
-  *reloads_out = reloads;
-  return 0;
-}
-
-int pllhip_fused_plan(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args,
-                      const int * kinds, unsigned int count, unsigned int nslots,
-                      std::vector<FusedOp> & plan, unsigned int * reloads_out, const FusedExtra * extra, FusedEdge * edge)
-{
-  static thread_local std::vector<char> arena(256 * 1024);
-  std::pmr::monotonic_buffer_resource pool(arena.data(), arena.size()); // (beyond the buffer: the heap)
-  std::vector<Node> node(count);
-  PlanLists hard_of(count, &pool); // WAW / WAR predecessors (and scaler hazards) of each op: must run before it
-  const size_t nclv = geom.nclv, nsc = geom.nsc;
-  // last writer and readers-since of every CLV / scale buffer, in list order
-  std::pmr::vector<int> clv_w(nclv, -1, &pool), sc_w(nsc, -1, &pool);
-  PlanLists clv_r(nclv, &pool), sc_r(nsc, &pool);
-  for (unsigned int i = 0; i < count; ++i)
-  {
-    const pllhip_op_t & op = ops[i];
-    Node & nd = node[i];
-    nd.raw[0] = clv_w[op.child1_clv];
-    nd.raw[1] = clv_w[op.child2_clv];
-    // (round 6: a predecessor that is one of the op's two PRODUCERS is no hazard of its own -- the usual case: a
-    // child's scale buffer was written by the op that wrote the child -- and must not be walked ahead of the
-    // "heavier child first" rule below.  Until then every list with scale buffers was walked child 1 first, whatever the
-    // subtrees' sizes: a traversal directed at a deep edge of a balanced 64-taxon tree needed 4 operands copied back
-    // from HBM with five slots and ended in a run of seven matrix ops; now none, and at most three in a row.)
-    auto hard = [&](int p) {
-      if (p >= 0 && (unsigned int)p != i && p != nd.raw[0] && p != nd.raw[1])
-        hard_of[i].push_back((unsigned int)p);
-    };
-    nd.sraw[0] = op.child1_scaler >= 0 ? sc_w[op.child1_scaler] : -1;
-    nd.sraw[1] = op.child2_scaler >= 0 ? sc_w[op.child2_scaler] : -1;
-    hard(clv_w[op.parent_clv]);
-    for (unsigned int r : clv_r[op.parent_clv]) hard((int)r);
-    hard(nd.sraw[0]);
-    hard(nd.sraw[1]);
-    if (op.parent_scaler >= 0)
-    {
-      hard(sc_w[op.parent_scaler]);
-      for (unsigned int r : sc_r[op.parent_scaler]) hard((int)r);
-    }
-    clv_w[op.parent_clv] = (int)i;
-    clv_r[op.parent_clv].clear();
-    clv_r[op.child1_clv].push_back(i);
-    clv_r[op.child2_clv].push_back(i);
-    if (op.parent_scaler >= 0)
-    {
-      sc_w[op.parent_scaler] = (int)i;
-      sc_r[op.parent_scaler].clear();
-    }
-    if (op.child1_scaler >= 0) sc_r[op.child1_scaler].push_back(i);
-    if (op.child2_scaler >= 0) sc_r[op.child2_scaler].push_back(i);
-    const unsigned int a = nd.raw[0] >= 0 ? node[nd.raw[0]].need : 0;
-    const unsigned int b = nd.raw[1] >= 0 ? node[nd.raw[1]].need : 0;
-    nd.need = std::max(1u, a == b ? a + (a ? 1u : 0u) : std::max(a, b));
-  }
-
-  // depth-first order from the end of the list: hazards first, then the heavier child
-  std::vector<unsigned int> order;
-  order.reserve(count);
-  {
-    std::vector<unsigned char> state(count, 0); // 0 new, 1 open, 2 emitted
-    std::vector<std::pair<unsigned int, unsigned int>> stack; // (op, next predecessor to look at)
-    PlanLists & preds = hard_of; // (the two producers are appended: hazards first, then the heavier child)
-    for (unsigned int i = 0; i < count; ++i)
-    {
-      int r0 = node[i].raw[0], r1 = node[i].raw[1];
-      if (r0 >= 0 && r1 >= 0 && node[r1].need > node[r0].need) std::swap(r0, r1);
-      if (r0 >= 0) preds[i].push_back((unsigned int)r0);
-      if (r1 >= 0 && r1 != r0) preds[i].push_back((unsigned int)r1);
-    }
-    for (unsigned int root = count; root-- > 0;)
-    {
-      if (state[root]) continue;
-      stack.push_back({root, 0});
-      state[root] = 1;
-      while (!stack.empty())
-      {
-        auto & top = stack.back();
-        if (top.second < preds[top.first].size())
-        {
-          const unsigned int p = preds[top.first][top.second++];
-          if (!state[p])
-          {
-            state[p] = 1;
-            stack.push_back({p, 0});
-          }
-        }
-        else
-        {
-          state[top.first] = 2;
-          order.push_back(top.first);
-          stack.pop_back();
-        }
-      }
-    }
-  }
-  std::vector<unsigned int> pos_of(count);
-  for (unsigned int pos = 0; pos < count; ++pos) pos_of[order[pos]] = pos;
-
-  // the edge pseudo-op reads what the list leaves in the two CLVs and scale buffers: their LAST writers.  An end the
-  // list does not keep in HBM (a tip, a deferred cherry), the same CLV twice, or a list that writes neither end: no fold
-  int edge_raw[2] = {-1, -1}, edge_sraw[2] = {-1, -1};
-  if (edge)
-  {
-    if (edge->parent_clv >= nclv || edge->child_clv >= nclv || edge->parent_clv == edge->child_clv ||
-        geom.is_tip(edge->parent_clv) || geom.is_tip(edge->child_clv) ||
-        edge->parent_scaler >= (int)nsc || edge->child_scaler >= (int)nsc)
-      return 1;
-    edge_raw[0] = clv_w[edge->parent_clv];
-    edge_raw[1] = clv_w[edge->child_clv];
-    if (edge_raw[0] < 0 && edge_raw[1] < 0) return 1;
-    edge_sraw[0] = edge->parent_scaler >= 0 ? sc_w[edge->parent_scaler] : -1;
-    edge_sraw[1] = edge->child_scaler >= 0 ? sc_w[edge->child_scaler] : -1;
-  }
-  const int rc = assign_slots_reload(geom, ops, args, kinds, count, nslots, order, pos_of, node, plan, reloads_out, &pool, extra,
-                                     edge, edge_raw, edge_sraw);
-  if (rc) return rc;
-  if (pllhip_env("PLLHIP_FUSED_DEBUG"))
-  {
-    fprintf(stderr, "pllhip fused plan: %u ops, %u slots, %u operands reloaded from HBM\n", count, nslots, *reloads_out);
-    if (atoi(pllhip_env("PLLHIP_FUSED_DEBUG")) > 1)
-      for (unsigned int pos = 0; pos < count; ++pos)
-      {
-        const FusedOp & f = plan[pos];
-        fprintf(stderr, "  %3u: op %3d kind %d  l %2d r %2d p %2d  lsc %2d rsc %2d  dma %d  hbm %p %p counts %p %p\n", pos,
-                f.list_pos, f.kind, f.lslot, f.rslot, f.pslot, f.lsc_slot, f.rsc_slot, f.dma_flags,
-                (const void *)f.left_hbm, (const void *)f.right_hbm, (const void *)f.lsc_hbm, (const void *)f.rsc_hbm);
-      }
-  }
-  return 0;
-}
-
-// Which tip-tip ops a list defers (partials_fused.hpp).  A deferred CLV is served from tables only while the list
-// treats it the way a tree does: written once, by that op; read after it, with the scale buffer it was cleared with (or
-// none); that scale buffer written by nobody else and read with nobody else.  Anything else is materialised (a CLV
-// deferred earlier) or simply not deferred (an op of this list) -- the list then sees ordinary buffers.
-void pllhip_fused_deferral(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
-                           const unsigned char * old_deferred, const int * old_scaler, const unsigned char * pinned,
-                           FusedDeferral & out)
-{
-  const size_t nclv = geom.nclv, nsc = geom.nsc;
-  const unsigned int NONE = ~0u;
-  out.defer.assign(count, 0);
-  out.as_tip.assign(nclv, 0);
-  out.materialise.clear();
-  out.dropped.clear();
-  auto true_tip = [&](unsigned int i) { return geom.pattern_tip && i < geom.tips; };
-  std::vector<unsigned int> nwrites(nclv, 0), first_write(nclv, NONE), first_read(nclv, NONE);
-  std::vector<unsigned int> sc_nwrites(nsc, 0), sc_first_write(nsc, NONE), sc_first_read(nsc, NONE);
-  std::vector<int> cand_sc(nclv, -2);        // the scale buffer a deferred CLV i would own (-1 none, -2: no candidate)
-  std::vector<int> sc_reader(nsc, -1);       // the one CLV a scale buffer is read with (-1 nobody, -2 several)
-  std::vector<unsigned char> bad(nclv, 0);   // read with a scale buffer that is not its own
-  for (unsigned int k = 0; k < count; ++k)
-  {
-    const pllhip_op_t & op = ops[k];
-    ++nwrites[op.parent_clv];
-    if (first_write[op.parent_clv] == NONE) first_write[op.parent_clv] = k;
-    if (op.parent_scaler >= 0)
-    {
-      ++sc_nwrites[op.parent_scaler];
-      if (sc_first_write[op.parent_scaler] == NONE) sc_first_write[op.parent_scaler] = k;
-    }
-  }
-  for (size_t i = 0; i < nclv; ++i)
-  {
-    if (old_deferred && old_deferred[i]) cand_sc[i] = old_scaler ? old_scaler[i] : -1;
-    if (nwrites[i] == 1)
-    {
-      const pllhip_op_t & op = ops[first_write[i]];
-      if (true_tip(op.child1_clv) && true_tip(op.child2_clv) && !true_tip((unsigned int)i) && !(pinned && pinned[i]) &&
-          !(old_deferred && old_deferred[i]))
-        cand_sc[i] = op.parent_scaler;
-    }
-  }
-  for (unsigned int k = 0; k < count; ++k)
-  {
-    const pllhip_op_t & op = ops[k];
-    const unsigned int kid[2] = {op.child1_clv, op.child2_clv};
-    const int ksc[2] = {op.child1_scaler, op.child2_scaler};
-    for (int o = 0; o < 2; ++o)
-    {
-      if (first_read[kid[o]] == NONE) first_read[kid[o]] = k;
-      if (cand_sc[kid[o]] != -2 && ksc[o] != -1 && ksc[o] != cand_sc[kid[o]]) bad[kid[o]] = 1;
-      if (ksc[o] >= 0)
-      {
-        if (sc_first_read[ksc[o]] == NONE) sc_first_read[ksc[o]] = k;
-        if (sc_reader[ksc[o]] == -1) sc_reader[ksc[o]] = (int)kid[o];
-        else if (sc_reader[ksc[o]] != (int)kid[o]) sc_reader[ksc[o]] = -2;
-      }
-    }
-  }
-  // CLVs deferred by an earlier call
-  for (size_t i = 0; old_deferred && i < nclv; ++i)
-  {
-    if (!old_deferred[i]) continue;
-    const int s = cand_sc[i];
-    const bool sc_touched = s >= 0 && (sc_nwrites[s] || sc_first_read[s] != NONE);
-    if (nwrites[i] == 0 && first_read[i] == NONE && !sc_touched) continue; // (the list does not see it)
-    if (nwrites[i] == 0)
-    {
-      // read only: from its kept table, if its counts are its own
-      const bool ok = !bad[i] && (s < 0 || (sc_nwrites[s] == 0 && (sc_reader[s] == -1 || sc_reader[s] == (int)i)));
-      if (ok) out.as_tip[i] = 1;
-      else out.materialise.push_back((unsigned int)i);
-      continue;
-    }
-    // overwritten: the deferral ends without the bytes if nothing reads them first and its zero counts go with it
-    const unsigned int w = first_write[i];
-    const bool dead = (first_read[i] == NONE || first_read[i] > w) &&
-                      (s < 0 || (ops[w].parent_scaler == s && sc_first_write[s] == w &&
-                                 (sc_first_read[s] == NONE || sc_first_read[s] > w)));
-    if (dead) out.dropped.push_back((unsigned int)i);
-    else out.materialise.push_back((unsigned int)i);
-  }
-  // tip-tip ops of this list
-  for (unsigned int k = 0; k < count; ++k)
-  {
-    const pllhip_op_t & op = ops[k];
-    const unsigned int p = op.parent_clv;
-    const int s = op.parent_scaler;
-    if (!true_tip(op.child1_clv) || !true_tip(op.child2_clv) || true_tip(p) || (pinned && pinned[p])) continue;
-    if (nwrites[p] != 1 || bad[p] || (first_read[p] != NONE && first_read[p] <= k)) continue;
-    // (bad[] of a CLV deferred earlier was judged against its OLD scale buffer: against the new one here)
-    if (old_deferred && old_deferred[p])
-    {
-      bool wrong = false;
-      for (unsigned int r = k + 1; r < count && !wrong; ++r)
-        wrong = (ops[r].child1_clv == p && ops[r].child1_scaler != -1 && ops[r].child1_scaler != s) ||
-                (ops[r].child2_clv == p && ops[r].child2_scaler != -1 && ops[r].child2_scaler != s);
-      if (wrong) continue;
-    }
-    if (s >= 0 && (sc_nwrites[s] != 1 || (sc_reader[s] != -1 && sc_reader[s] != (int)p) ||
-                   (sc_first_read[s] != NONE && sc_first_read[s] <= k)))
-      continue;
-    out.defer[k] = 1;
-    out.as_tip[p] = 1;
-  }
-}
-
-bool pllhip_fused_edge_end_stored(const FusedGeom & geom, const FusedDeferral & dd, unsigned int clv,
-                                  bool deferred_before, bool pinned)
-{
-  if (clv >= geom.nclv || geom.is_tip(clv) || pinned) return false;
-  if (!deferred_before) return true;
-  return std::find(dd.materialise.begin(), dd.materialise.end(), clv) != dd.materialise.end() ||
-         std::find(dd.dropped.begin(), dd.dropped.end(), clv) != dd.dropped.end();
-}
-
-// The planner with deferred cherries, without a device (tests/test_host_deferred_plan.py).  old_deferred / old_scaler /
-// pinned: per CLV index, may be NULL (pllhip_fused_deferral).  Out: *nkept kept ops in walk order as positions in
-// the caller's list (order_out), six numbers per kept op as pllhip_fused_plan_dry gives them (slots_out), two operand
-// kinds per kept op (operands_out: 0 a slot, 1 a tip, 2 a deferred cherry), per list op whether it is deferred
-// (deferred_out), and the CLVs deferred earlier that the list has materialised first / ends the deferral of
-// (materialise_out, dropped_out: at most clv indices each, counts in *nmaterialise, *ndropped).
-// Returns 0, 1 if the kernel does not take the list, < 0 on error.
-// (edge4 not null: pllhip_fused_plan_dry_edge -- {parent_clv, parent_scaler, child_clv, child_scaler}; `nslots` is then
-// not used: the list is planned the way pllhip_update_partials plans a one-segment list, see there)
-static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
-                             int pattern_tip, const pllhip_op_t * ops, unsigned int count, unsigned int nslots,
-                             const unsigned char * old_deferred, const int * old_scaler,
-                             const unsigned char * pinned, unsigned int * nkept, unsigned int * order_out,
-                             int * slots_out, int * operands_out, unsigned char * deferred_out,
-                             unsigned int * reloads_out, unsigned int * materialise_out,
-                             unsigned int * nmaterialise, unsigned int * dropped_out, unsigned int * ndropped,
-                             const int * edge4, unsigned int rate_cats, int * edge_out)
-{
-  FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
-  for (unsigned int i = 0; i < count; ++i)
-  {
-    const pllhip_op_t & op = ops[i];
-    if (op.parent_clv >= geom.nclv || op.child1_clv >= geom.nclv || op.child2_clv >= geom.nclv ||
-        op.parent_scaler >= (int)scale_buffers || op.child1_scaler >= (int)scale_buffers ||
-        op.child2_scaler >= (int)scale_buffers)
-    {
-      pllhip_set_error("pllhip_fused_plan_dry_deferred: index out of range in op %u", i);
-      return -1;
-    }
-  }
-  if (edge4 && (edge4[0] < 0 || (size_t)edge4[0] >= geom.nclv || edge4[2] < 0 || (size_t)edge4[2] >= geom.nclv ||
-                edge4[1] >= (int)scale_buffers || edge4[3] >= (int)scale_buffers ||
-                !(rate_cats == 1 || rate_cats == 2 || rate_cats == 4)))
-  {
-    pllhip_set_error("pllhip_fused_plan_dry_edge: bad edge or rate_cats");
-    return -1;
-  }
-  FusedDeferral d;
-  pllhip_fused_deferral(geom, ops, count, old_deferred, old_scaler, pinned, d);
-  std::vector<pllhip_op_t> kept;
-  std::vector<unsigned int> where;
-  for (unsigned int i = 0; i < count; ++i)
-  {
-    if (deferred_out) deferred_out[i] = d.defer[i];
-    if (!d.defer[i])
-    {
-      kept.push_back(ops[i]);
-      where.push_back(i);
-    }
-  }
-  if (nmaterialise) *nmaterialise = (unsigned int)d.materialise.size();
-  if (ndropped) *ndropped = (unsigned int)d.dropped.size();
-  for (size_t t = 0; materialise_out && t < d.materialise.size(); ++t) materialise_out[t] = d.materialise[t];
-  for (size_t t = 0; dropped_out && t < d.dropped.size(); ++t) dropped_out[t] = d.dropped[t];
-  // (what is materialised first is an ordinary buffer to the list)
-  for (unsigned int i : d.materialise) d.as_tip[i] = 0;
-  geom.as_tip = d.as_tip.data();
-  const unsigned int n = (unsigned int)kept.size();
-  if (nkept) *nkept = n;
-  std::vector<PartialsArgs> args(n);
-  std::vector<int> kinds(n);
-  for (unsigned int i = 0; i < n; ++i)
-  {
-    const pllhip_op_t & op = kept[i];
-    const bool t1 = geom.is_tip(op.child1_clv), t2 = geom.is_tip(op.child2_clv);
-    const bool tip1 = pattern_tip && op.child1_clv < tips, tip2 = pattern_tip && op.child2_clv < tips;
-    memset(&args[i], 0, sizeof(PartialsArgs));
-    kinds[i] = (tip1 && tip2) ? 2 : (t1 && t2) ? 3 : (t1 || t2) ? 1 : 0;
-    auto sc = [&](int idx) { return idx >= 0 ? reinterpret_cast<unsigned int *>((uintptr_t)4096 * (idx + 1)) : (unsigned int *)nullptr; };
-    auto clv = [&](unsigned int idx) { return reinterpret_cast<const double *>((uintptr_t)4096 * (idx + 1)); };
-    args[i].pscaler = sc(op.parent_scaler);
-    if (kinds[i] == 0)
-    {
-      args[i].left = clv(op.child1_clv);
-      args[i].right = clv(op.child2_clv);
-      args[i].lscaler = sc(op.child1_scaler);
-      args[i].rscaler = sc(op.child2_scaler);
-    }
-    else if (kinds[i] == 1)
-    {
-      args[i].right = clv(t1 ? op.child2_clv : op.child1_clv);
-      args[i].rscaler = sc(t1 ? op.child2_scaler : op.child1_scaler);
-    }
-    if (operands_out)
-    {
-      operands_out[2 * i] = tip1 ? 1 : t1 ? 2 : 0;
-      operands_out[2 * i + 1] = tip2 ? 1 : t2 ? 2 : 0;
-    }
-  }
-  if (reloads_out) *reloads_out = 0;
-  for (int t = 0; edge_out && t < 8; ++t) edge_out[t] = t >= 1 && t <= 4 ? -1 : 0;
-  if (!n) return 0;
-  std::vector<FusedOp> plan;
-  unsigned int reloads = 0;
-  int rc;
-  if (!edge4)
-    rc = pllhip_fused_plan(geom, kept.data(), args.data(), kinds.data(), n, nslots, plan, &reloads);
-  else
-  {
-    // the unfolded plan decides the configuration (12 waves per CU, else 8); the epilogue is then tried at that one
-    unsigned int wgs = 3;
-    for (rc = 1; rc > 0 && wgs >= 2u; --wgs)
-    {
-      nslots = fused_slots_for(rate_cats, false, wgs);
-      rc = pllhip_fused_plan(geom, kept.data(), args.data(), kinds.data(), n, nslots, plan, &reloads);
-    }
-    if (rc) return rc;
-    ++wgs;
-    edge_out[6] = (int)wgs;
-    FusedEdge e;
-    memset(&e, 0, sizeof(e));
-    e.parent_clv = (unsigned int)edge4[0];
-    e.parent_scaler = edge4[1];
-    e.child_clv = (unsigned int)edge4[2];
-    e.child_scaler = edge4[3];
-    e.parent = reinterpret_cast<const double *>((uintptr_t)4096 * (e.parent_clv + 1));
-    e.child = reinterpret_cast<const double *>((uintptr_t)4096 * (e.child_clv + 1));
-    e.pscaler = e.parent_scaler >= 0 ? reinterpret_cast<unsigned int *>((uintptr_t)4096 * (e.parent_scaler + 1)) : nullptr;
-    e.cscaler = e.child_scaler >= 0 ? reinterpret_cast<unsigned int *>((uintptr_t)4096 * (e.child_scaler + 1)) : nullptr;
-    // (the rule pllhip_update_partials applies: an end deferred by an earlier call that the list does not see is not in HBM)
-    auto stored = [&](unsigned int i) {
-      return pllhip_fused_edge_end_stored(geom, d, i, old_deferred && old_deferred[i], pinned && pinned[i]);
-    };
-    std::vector<FusedOp> folded;
-    unsigned int freloads = 0;
-    if (stored(e.parent_clv) && stored(e.child_clv) && pllhip_fused_plan(geom, kept.data(), args.data(), kinds.data(), n, nslots, folded, &freloads, nullptr, &e) == 0)
-    {
-      plan.swap(folded);
-      reloads = freloads;
-      const int v[8] = {1, e.op.lslot, e.op.rslot, e.op.lsc_slot, e.op.rsc_slot, e.op.dma_flags, (int)wgs, (int)wgs};
-      for (int t = 0; t < 8; ++t) edge_out[t] = v[t];
-    }
-  }
-  if (rc) return rc;
-  std::vector<int> opnd(operands_out ? operands_out : nullptr, operands_out ? operands_out + 2 * n : nullptr);
-  for (unsigned int pos = 0; pos < n; ++pos)
-  {
-    const FusedOp & f = plan[pos];
-    if (order_out) order_out[pos] = where[f.list_pos];
-    if (operands_out)
-    {
-      operands_out[2 * pos] = opnd[2 * f.list_pos];
-      operands_out[2 * pos + 1] = opnd[2 * f.list_pos + 1];
-    }
-    if (slots_out)
-    {
-      const int v[6] = {f.lslot, f.rslot, f.pslot, f.lsc_slot, f.rsc_slot, f.dma_flags};
-      for (int t = 0; t < 6; ++t) slots_out[pos * 6 + t] = v[t];
-    }
-  }
-  if (reloads_out) *reloads_out = reloads;
-  return 0;
-}
-
-extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
-                                              int pattern_tip, const pllhip_op_t * ops, unsigned int count, unsigned int nslots,
-                                              const unsigned char * old_deferred, const int * old_scaler,
-                                              const unsigned char * pinned, unsigned int * nkept, unsigned int * order_out,
-                                              int * slots_out, int * operands_out, unsigned char * deferred_out,
-                                              unsigned int * reloads_out, unsigned int * materialise_out,
-                                              unsigned int * nmaterialise, unsigned int * dropped_out, unsigned int * ndropped)
-{
-  return plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, nslots, old_deferred, old_scaler, pinned,
-                           nkept, order_out, slots_out, operands_out, deferred_out, reloads_out, materialise_out, nmaterialise,
-                           dropped_out, ndropped, nullptr, 0, nullptr);
-}
-
-// The same with the edge epilogue (pllhip_ctx::edge_hint; tests/test_host_edge_fold_plan.py): the list planned as
-// pllhip_update_partials plans a one-segment list of a partition with `rate_cats` categories and per-site or no scale
-// buffers -- unfolded at 12 waves per CU, else 8; then once more at that configuration with the evaluation of
-// edge4 = {parent_clv, parent_scaler, child_clv, child_scaler} as a pseudo-op behind the last op.
-// edge_out[8]: folded (0: the unfolded plan is what the other outputs describe), the pseudo-op's lslot (parent), rslot
-// (child), lsc_slot, rsc_slot, dma_flags, workgroups per CU of the unfolded plan, of the folded one (0: not folded).
-extern "C" int pllhip_fused_plan_dry_edge(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
-                                          int pattern_tip, unsigned int rate_cats, const pllhip_op_t * ops, unsigned int count,
-                                          const unsigned char * old_deferred, const int * old_scaler,
-                                          const unsigned char * pinned, const int * edge4, unsigned int * nkept,
-                                          unsigned int * order_out, int * slots_out, int * operands_out,
-                                          unsigned char * deferred_out, unsigned int * reloads_out, int * edge_out)
-{
-  if (!edge4 || !edge_out)
-  {
-    pllhip_set_error("pllhip_fused_plan_dry_edge: no edge");
-    return -1;
-  }
-  return plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, 0, old_deferred, old_scaler, pinned, nkept,
-                           order_out, slots_out, operands_out, deferred_out, reloads_out, nullptr, nullptr, nullptr, nullptr,
-                           edge4, rate_cats, edge_out);
-}
-
-// The planner without a device (tests/test_host.py, tools): which order and how many
-// operands without a slot a list gets with `nslots` slots per wave.
-extern "C" int pllhip_fused_plan_dry(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
-                                     int pattern_tip, const pllhip_op_t * ops, unsigned int count,
-                                     unsigned int nslots, unsigned int * order_out,
-                                     unsigned int * reloads_out, int * slots_out)
-{
-  const FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
-  std::vector<PartialsArgs> args(count);
-  std::vector<int> kinds(count);
-  for (unsigned int i = 0; i < count; ++i)
-  {
-    const pllhip_op_t & op = ops[i];
-    if (op.parent_clv >= geom.nclv || op.child1_clv >= geom.nclv || op.child2_clv >= geom.nclv ||
-        op.parent_scaler >= (int)scale_buffers || op.child1_scaler >= (int)scale_buffers ||
-        op.child2_scaler >= (int)scale_buffers)
-    {
-      pllhip_set_error("pllhip_fused_plan_dry: index out of range in op %u", i);
-      return -1;
-    }
-    const bool t1 = geom.is_tip(op.child1_clv), t2 = geom.is_tip(op.child2_clv);
-    memset(&args[i], 0, sizeof(PartialsArgs));
-    kinds[i] = (t1 && t2) ? 2 : (t1 || t2) ? 1 : 0;
-    // (distinct fake addresses per scale buffer: the reload plan compares them)
-    auto sc = [&](int idx) { return idx >= 0 ? reinterpret_cast<unsigned int *>((uintptr_t)4096 * (idx + 1)) : (unsigned int *)nullptr; };
-    args[i].pscaler = sc(op.parent_scaler);
-    auto clv = [&](unsigned int idx) { return reinterpret_cast<const double *>((uintptr_t)4096 * (idx + 1)); };
-    if (kinds[i] == 0)
-    {
-      args[i].left = clv(op.child1_clv);
-      args[i].right = clv(op.child2_clv);
-      args[i].lscaler = sc(op.child1_scaler);
-      args[i].rscaler = sc(op.child2_scaler);
-    }
-    else if (kinds[i] == 1)
-    {
-      args[i].right = clv(t1 ? op.child2_clv : op.child1_clv);
-      args[i].rscaler = sc(t1 ? op.child2_scaler : op.child1_scaler);
-    }
-  }
-  std::vector<FusedOp> plan;
-  unsigned int reloads = 0;
-  const int rc = pllhip_fused_plan(geom, ops, args.data(), kinds.data(), count, nslots, plan, &reloads);
-  if (rc) return rc;
-  for (unsigned int pos = 0; pos < count; ++pos)
-  {
-    if (order_out) order_out[pos] = (unsigned int)plan[pos].list_pos;
-    if (slots_out)
-    {
-      const FusedOp & f = plan[pos];
-      const int v[6] = {f.lslot, f.rslot, f.pslot, f.lsc_slot, f.rsc_slot, f.dma_flags};
-      for (int t = 0; t < 6; ++t) slots_out[pos * 6 + t] = v[t];
-    }
-  }
-  if (reloads_out) *reloads_out = reloads;
-  return 0;
+  return pllhip_fused_slots_for(c->sh.rate_cats, c->sh.rate_scalers != 0, wgs);
 }
 
 template <int RC>
@@ -1613,8 +847,7 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   const unsigned int sites = c->sh.sites;
   const size_t tile_sites = (size_t)J * (64 / (2 * RC));
   const size_t tiles = (sites + tile_sites - 1) / tile_sites;
-  const size_t cw = c->sh.rate_scalers ? 32 : ((64 / (2 * RC)) < 4 ? 4 : (64 / (2 * RC)));
-  const size_t lds = 4 * ((size_t)nslots * J * (64 * 16 + cw * 4) + (size_t)RC * 16 * sizeof(double));
+  const size_t lds = 4 * ((size_t)nslots * pllhip_fused_slot_size(RC, c->sh.rate_scalers != 0).bytes() + (size_t)RC * 16 * sizeof(double));
   // three workgroups (12 waves) per CU when the slots leave room for them, else two; each wave
   // walks its share of the tiles
   const size_t nsegs = bases.nsegs; // (work items: (tile, segment) pairs)
@@ -1686,149 +919,6 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   return 0;
 }
 
-// Where each op's tip characters sit in a wave's character registers.  A wave holds the characters of 64 / lpr tip
-// rows of its tile at a time (lpr lanes of 16 bytes per row); the rows are dealt in the order the list uses them,
-// both rows of an op into the same batch.  tips[pos]: bit 0 / 1 = the op has a left / right tip.  Out, per op:
-// chars (PLLHIP_FUSED_CH_LPOS / RPOS = first lane of the row, CH_LTIP / CH_RTIP) and the batch its rows are in
-// (an op without tips: the batch current at that point).  Returns the number of batches.  Pure host logic.
-unsigned int pllhip_fused_char_batches4(const unsigned int * tips, unsigned int count, unsigned int lpr,
-                                        unsigned int * chars_out, unsigned int * chars2_out, unsigned int * batch_out)
-{
-  const unsigned int rpb = 64 / lpr; // rows per batch
-  unsigned int batch = 0, q = 0;
-  for (unsigned int pos = 0; pos < count; ++pos)
-  {
-    const unsigned int n = (tips[pos] & 1u) + ((tips[pos] >> 1) & 1u) + ((tips[pos] >> 2) & 1u) + ((tips[pos] >> 3) & 1u);
-    if (q + n > rpb)
-    {
-      ++batch;
-      q = 0;
-    }
-    batch_out[pos] = batch;
-    chars_out[pos] = 0;
-    if (tips[pos] & 1u) chars_out[pos] |= PLLHIP_FUSED_CH_LTIP | (q++ * lpr);
-    if (tips[pos] & 2u) chars_out[pos] |= PLLHIP_FUSED_CH_RTIP | (q++ * lpr) << 8;
-    // (the rows of a second gather -- an op with two gathered operands -- lie in the same batch)
-    if (chars2_out)
-    {
-      chars2_out[pos] = 0;
-      if (tips[pos] & 4u) chars2_out[pos] |= PLLHIP_FUSED_CH_LTIP | (q++ * lpr);
-      if (tips[pos] & 8u) chars2_out[pos] |= PLLHIP_FUSED_CH_RTIP | (q++ * lpr) << 8;
-    }
-  }
-  return batch + 1;
-}
-
-unsigned int pllhip_fused_char_batches(const unsigned int * tips, unsigned int count, unsigned int lpr,
-                                       unsigned int * chars_out, unsigned int * batch_out)
-{
-  return pllhip_fused_char_batches4(tips, count, lpr, chars_out, nullptr, batch_out);
-}
-
-extern "C" unsigned int pllhip_fused_char_batches_dry(const unsigned int * tips, unsigned int count, unsigned int rate_cats,
-                                                      unsigned int * chars_out, unsigned int * batch_out)
-{
-  const unsigned int ts = PLLHIP_FUSED_J * (64 / (2 * rate_cats));
-  return pllhip_fused_char_batches(tips, count, ts >= 16 ? ts / 16 : 1, chars_out, batch_out);
-}
-
-// Independent sub-lists (FusedSeg in partials_fused.hpp).  Two ops belong together when one of them writes a
-// buffer -- CLV or scale buffer -- the other reads or writes; buffers nobody in the list writes (tips, operands of
-// earlier calls) tie nothing.  Union-find over the ops, then the components dealt longest first.
-unsigned int pllhip_fused_segments(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
-                                   unsigned int max_segments, std::vector<unsigned int> & seg_of)
-{
-  seg_of.assign(count, 0u);
-  if (max_segments > PLLHIP_FUSED_MAX_SEGS) max_segments = PLLHIP_FUSED_MAX_SEGS;
-  if (count < 4 || max_segments < 2) return 1;
-  // (every new list passes here: the work arrays are the thread's, not the heap's)
-  static thread_local std::vector<unsigned int> parent, size, roots, load, seg_of_root;
-  static thread_local std::vector<int> clv_first, sc_first;
-  parent.resize(count);
-  for (unsigned int i = 0; i < count; ++i) parent[i] = i;
-  auto find = [&](unsigned int x) {
-    while (parent[x] != x) x = parent[x] = parent[parent[x]];
-    return x;
-  };
-  auto join = [&](unsigned int a, unsigned int b) {
-    a = find(a);
-    b = find(b);
-    if (a != b) parent[a > b ? a : b] = a < b ? a : b;
-  };
-  // first op that touches each WRITTEN buffer (-1: not written in this list, -2: written, nobody met yet)
-  clv_first.assign(geom.nclv, -1);
-  sc_first.assign(geom.nsc, -1);
-  for (unsigned int i = 0; i < count; ++i)
-  {
-    if (ops[i].parent_clv >= geom.nclv || ops[i].child1_clv >= geom.nclv || ops[i].child2_clv >= geom.nclv ||
-        ops[i].parent_scaler >= (int)geom.nsc || ops[i].child1_scaler >= (int)geom.nsc || ops[i].child2_scaler >= (int)geom.nsc)
-      return 1; // (the path taken reports it)
-    clv_first[ops[i].parent_clv] = -2;
-    if (ops[i].parent_scaler >= 0) sc_first[ops[i].parent_scaler] = -2;
-  }
-  for (unsigned int i = 0; i < count; ++i)
-  {
-    auto touch = [&](std::vector<int> & first, int idx) {
-      if (idx < 0 || first[idx] == -1) return;
-      if (first[idx] == -2) first[idx] = (int)i;
-      else join((unsigned int)first[idx], i);
-    };
-    touch(clv_first, (int)ops[i].parent_clv);
-    touch(clv_first, (int)ops[i].child1_clv);
-    touch(clv_first, (int)ops[i].child2_clv);
-    touch(sc_first, ops[i].parent_scaler);
-    touch(sc_first, ops[i].child1_scaler);
-    touch(sc_first, ops[i].child2_scaler);
-  }
-  // components by size, longest first (ties: the one that begins first)
-  size.assign(count, 0u);
-  for (unsigned int i = 0; i < count; ++i) ++size[find(i)];
-  roots.clear();
-  for (unsigned int i = 0; i < count; ++i)
-    if (size[i]) roots.push_back(i);
-  if (roots.size() < 2) return 1;
-  std::stable_sort(roots.begin(), roots.end(), [&](unsigned int a, unsigned int b) { return size[a] > size[b]; });
-  // as many segments as have two ops each at least, and no more than shorten the longest
-  unsigned int nsegs = (unsigned int)std::min<size_t>(max_segments, roots.size());
-  seg_of_root.assign(count, 0u);
-  for (;; --nsegs)
-  {
-    load.assign(nsegs, 0u);
-    for (unsigned int r : roots)
-    {
-      const unsigned int k = (unsigned int)(std::min_element(load.begin(), load.end()) - load.begin());
-      seg_of_root[r] = k;
-      load[k] += size[r];
-    }
-    if (nsegs == 1 || *std::min_element(load.begin(), load.end()) >= 2) break;
-  }
-  if (nsegs == 1) return 1;
-  // segment 0 the longest, as the header says and the kernels' segment-major order wants (every tile of the longest
-  // segment first): the greedy dealing above does not give that by itself once components outnumber segments --
-  // components of 5, 4 and 4 ops over two segments are loads of 5 and 8 -- so the segments are numbered by
-  // descending load afterwards (tests/test_host.py)
-  std::vector<unsigned int> rank_of(nsegs);
-  {
-    std::vector<unsigned int> by_load(nsegs);
-    for (unsigned int k = 0; k < nsegs; ++k) by_load[k] = k;
-    std::stable_sort(by_load.begin(), by_load.end(), [&](unsigned int a, unsigned int b) { return load[a] > load[b]; });
-    for (unsigned int r = 0; r < nsegs; ++r) rank_of[by_load[r]] = r;
-  }
-  for (unsigned int i = 0; i < count; ++i) seg_of[i] = rank_of[seg_of_root[find(i)]];
-  return nsegs;
-}
-
-extern "C" unsigned int pllhip_fused_segments_dry(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
-                                                  int pattern_tip, const pllhip_op_t * ops, unsigned int count,
-                                                  unsigned int max_segments, unsigned int * seg_out)
-{
-  const FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
-  std::vector<unsigned int> seg_of;
-  const unsigned int n = pllhip_fused_segments(geom, ops, count, max_segments, seg_of);
-  for (unsigned int i = 0; i < count && seg_out; ++i) seg_out[i] = seg_of[i];
-  return n;
-}
-
 // Encode the plans for the device (FusedRec in partials_fused.hpp) -- one per segment: two header records that
 // stand for ops -2 and -1, one record per op, one of padding (the last op's look-ahead load) -- then the segment
 // table, the reload sources, the pair-table jobs, the character rows' addresses.  Returns 1 if the list is not one
@@ -1879,8 +969,8 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   }
   const unsigned int J = PLLHIP_FUSED_J;
   const unsigned int sps = 64 / (2 * R);
-  const unsigned int cw = c->sh.rate_scalers ? 32 : (sps < 4 ? 4 : sps);
-  const unsigned int slot_bytes = J * 1024u, count_bytes = J * cw * 4u;
+  const FusedSlotSize slot = pllhip_fused_slot_size(R, c->sh.rate_scalers != 0);
+  const unsigned int slot_bytes = slot.tile_bytes, count_bytes = slot.count_bytes;
   if ((size_t)nslots * slot_bytes > 0xffffu) return 1;
 
   std::vector<FusedRec> recs;

@@ -1,4 +1,4 @@
-// partials_fused.hpp -- plan of the site-blocked whole-list kernel (partials_fused.hip)
+// partials_fused.hpp -- plan of the site-blocked whole-list kernel: planner (fused_plan.hip), kernels (partials_fused.hip)
 #ifndef PLLHIP_PARTIALS_FUSED_HPP_
 #define PLLHIP_PARTIALS_FUSED_HPP_
 
@@ -7,6 +7,20 @@
 #include "ctx.hpp"
 
 constexpr int PLLHIP_FUSED_J = 2; // sub-steps (64 lanes x 16 B) per tile
+
+// One LDS slot of a wave: a tile and its scaler counts -- `count_words` per sub-step: one per site (four at least),
+// 32 with per-rate scalers.  (Slots per wave, the launch's LDS and the records' byte offsets all come from here.)
+struct FusedSlotSize
+{
+  unsigned int count_words, tile_bytes, count_bytes;
+  unsigned int bytes() const { return tile_bytes + count_bytes; }
+};
+inline FusedSlotSize pllhip_fused_slot_size(unsigned int rate_cats, bool rate_scalers)
+{
+  const unsigned int sps = 64 / (2 * rate_cats); // sites per sub-step
+  const unsigned int cw = rate_scalers ? 32 : (sps < 4 ? 4 : sps);
+  return {cw, PLLHIP_FUSED_J * 64u * 16u, PLLHIP_FUSED_J * cw * 4u};
+}
 
 // A GATHERED operand: a factor the list kernel takes from a small table by tip characters instead of computing it
 // from a CLV -- a tip, or a deferred cherry (deferred.hip: a tip-tip parent that is not stored).
@@ -188,6 +202,7 @@ struct FusedEdge
   const double * parent, * child;          // the two CLVs in HBM
   const unsigned int * pscaler, * cscaler; // their scale buffers, nullptr none
   const double * pmat;                     // the edge's P-matrix
+  bool deferred_before[2], pinned[2];      // {parent, child}: what pllhip_fused_edge_end_stored asks of an end
   FusedOp op;                              // out: lslot / rslot, lsc_slot / rsc_slot, what is reloaded (parent "left", child "right")
 };
 
@@ -221,6 +236,8 @@ void pllhip_fused_deferral(const FusedGeom & geom, const pllhip_op_t * ops, unsi
 // overwrites it with an ordinary op (dd.dropped).  ONE rule for pllhip_update_partials and pllhip_fused_plan_dry_edge.
 bool pllhip_fused_edge_end_stored(const FusedGeom & geom, const FusedDeferral & dd, unsigned int clv,
                                   bool deferred_before, bool pinned);
+// slots per wave with 2 (8 waves per CU) or 3 (12 waves) workgroups per CU
+unsigned int pllhip_fused_slots_for(unsigned int rate_cats, bool rate_scalers, unsigned int workgroups_per_cu);
 unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int workgroups_per_cu);
 // The list as up to `max_segments` independent sub-lists of at least two ops each: seg_of[i] = segment of op i
 // (segment 0 the longest; ops keep their relative order within a segment).  Components -- ops connected through a
@@ -228,7 +245,30 @@ unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int workgroups_pe
 // Returns the number of segments (1: the list does not split).
 unsigned int pllhip_fused_segments(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
                                    unsigned int max_segments, std::vector<unsigned int> & seg_of);
-// one plan per segment (pllhip_fused_plan of its sub-list)
+// One plan per segment (both whole-list kernels): pllhip_fused_plan of the sub-list seg_of marks -- nsegs == 1: of the
+// list itself, in place --, list_pos in the caller's numbering, *reloads summed.  Ends at the first plan that is not 0.
+int pllhip_fused_plan_segments(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
+                               const FusedExtra * extra, unsigned int count, const unsigned int * seg_of, unsigned int nsegs,
+                               unsigned int nslots, std::vector<std::vector<FusedOp>> & plans, unsigned int * reloads);
+
+// The 4-state list driver: ONE rule for pllhip_update_partials (real addresses) and pllhip_fused_plan_dry_deferred /
+// _edge (fake ones).  The list is segmented and planned at each of slot_counts[] in turn until one is taken -- 12 waves
+// per CU, else 8; segments refused at every slot count: once more as one list.  Then, with an `edge` and one segment:
+// once more at the slot count taken with the edge as a pseudo-op, if both ends pass pllhip_fused_edge_end_stored; a
+// fold the planner refuses leaves the unfolded plan.  Returns pllhip_fused_plan's codes.
+struct FusedListPlan
+{
+  std::vector<std::vector<FusedOp>> plans; // one per segment
+  unsigned int nslots = 0, taken = 0;      // the slot count taken and its position in slot_counts[]
+  unsigned int reloads = 0;
+  bool folded = false;                     // plans[0] ends in the edge pseudo-op: edge->op says where its operands are
+};
+int pllhip_fused_plan_list(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
+                           const FusedExtra * extra, unsigned int count, unsigned int max_segments,
+                           const unsigned int * slot_counts, unsigned int nslot_counts, FusedEdge * edge,
+                           const FusedDeferral & dd, FusedListPlan & out);
+
+// encode and launch: one plan per segment
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
                         const std::vector<FusedPairJob> * keep_jobs = nullptr, const FusedEdge * edge = nullptr);
 int pllhip_relaunch_fused(pllhip_ctx * c); // the same op list as in the previous whole-list call of this context
