@@ -271,6 +271,29 @@ PLLHIP_EXPORT unsigned int pllhip_fused_char_batches_dry(const unsigned int * ti
                                                          unsigned int rate_cats, unsigned int * chars_out,
                                                          unsigned int * batch_out);
 
+/* The 20-state whole-list kernel's list logic without a device (partials_aa_fused.hip plans every new list with the same
+ * three functions of fused_plan.hip): what each op is to the kernel, what the scaling certificate (above) makes of the
+ * list, and how the list is walked.  Geometry as for pllhip_fused_plan_dry.  lookups_max: the lookup budget
+ * (PLLHIP_AA_LOOKUP_MB in table sets); tt_inside / ti_mfma: PLLHIP_AA_TT_INSIDE / PLLHIP_AA_TI_MFMA; max_segments:
+ * at most so many segments (8 on a small partition, PLLHIP_FUSED_SEGMENTS); incoming: the bound an earlier call left
+ * on each CLV (tips + clv_buffers doubles; NULL: none).  Out, each may be NULL:
+ *   op_out[7 * count], per op: class (0 inner-inner, 1 tip-inner, 2 tip-tip ahead of the list, 3 lookup, 4 tip-tip in
+ *     the list); the two ops that wrote a lookup's children (-1: no lookup; first -2: a tip-inner lookup); whether its
+ *     scaling test looks for the certificate's window; its segment and its position in that segment's walk (-1, -1:
+ *     ahead of the list); whether it begins with a barrier of its own (an inner-inner op behind a barrier-free one);
+ *   list_out[14]: tip-inner mat-vecs on the matrix cores (0: the list could not be run again, or its bounds outgrow
+ *     every window with them), cert_kind (0 nothing tests, 1 a trip runs the list again, 2 inherited bounds only),
+ *     cert_too_wide, operands reloaded, segments, ops walked, then pllhip_aa_list_kinds' eight numbers;
+ *   *window_out: the certificate's window (relative half-width); bounds_out[tips + clv_buffers]: `incoming` with
+ *     what the list leaves marked.
+ * Returns 0, 1 if the kernel does not take the list (a tip-tip op whose parent or scale buffer an earlier op of the
+ * list touched; nothing but tip-tip ops ahead; a shape the planner refuses), -1 on an index out of range. */
+PLLHIP_EXPORT int pllhip_aa_list_plan_dry(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                          int pattern_tip, const pllhip_op_t * ops, unsigned int count,
+                                          unsigned int lookups_max, int tt_inside, int ti_mfma,
+                                          unsigned int max_segments, const double * incoming, int * op_out,
+                                          int * list_out, double * window_out, double * bounds_out);
+
 /* replaces pll_core_update_partial_tt proper (core_partials.c:82-200): the parent CLV of a tip-tip
  * node is, per site, row ((code1 << log2_maxstates) + code2) of the lookup table the caller built
  * with pll_core_create_lookup -- a gather on the device from the uploaded table (h_lookup:

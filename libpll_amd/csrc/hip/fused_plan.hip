@@ -7,6 +7,9 @@
 //             of a level-by-level list)
 //   slots     a value keeps its LDS slot until its last reader in the list has run (assign_slots_reload)
 //   driver    cherries deferred, segments, 12 waves per CU or 8, the edge pseudo-op: pllhip_fused_plan_list
+//   20 states what comes before the planner there: every op's class (pllhip_aa_list_classify), the scaling certificate's
+//             bounds (pllhip_aa_list_cert), the list the kernel walks and its barriers (pllhip_aa_list_walk);
+//             pllhip_aa_list_plan_dry runs the three (tests/test_host_aa_list_plan.py, test_gpu_aa_list_plan.py)
 #include <algorithm>
 #include <stdint.h>
 #include <stdio.h>
@@ -605,6 +608,182 @@ int pllhip_fused_plan_list(const FusedGeom & geom, const pllhip_op_t * ops, cons
   return 0;
 }
 
+// ---- the 20-state list (partials_fused.hpp): classes, certificate bounds, the walk
+
+int pllhip_aa_list_classify(const FusedGeom & geom, const pllhip_op_t * ops, const int * kinds, const int * scales,
+                            unsigned int count, unsigned int lookups_max, bool tt_inside, AaListClasses & out)
+{
+  std::vector<unsigned char> clv_touched(geom.nclv, 0), sc_touched(geom.nsc, 0);
+  std::vector<int> tt_writer(geom.nclv, -1); // the tip-tip op of this list that wrote each CLV last
+  out.cls.assign(count, AA_OP_II);
+  out.lk_kids.assign(count, {-1, -1});
+  out.lookups = 0;
+  out.any_scaler = false;
+  for (unsigned int i = 0; i < count; ++i)
+  {
+    const pllhip_op_t & op = ops[i];
+    const int plain = kinds[i];
+    if (plain == 2 && (clv_touched[op.parent_clv] || (op.parent_scaler >= 0 && sc_touched[op.parent_scaler]))) return 1;
+    out.any_scaler = out.any_scaler || scales[i] != 0;
+    out.cls[i] = plain == 2 ? (tt_inside ? AA_OP_TT_LIST : AA_OP_TT_AHEAD) : plain;
+    if (out.lookups < lookups_max && plain == 0 && tt_writer[op.child1_clv] >= 0 && tt_writer[op.child2_clv] >= 0)
+    {
+      out.lk_kids[i] = {tt_writer[op.child1_clv], tt_writer[op.child2_clv]};
+      out.cls[i] = AA_OP_LOOKUP;
+      ++out.lookups;
+    }
+    else if (out.lookups < lookups_max && plain == 1)
+    {
+      const unsigned int inner = geom.is_tip(op.child1_clv) ? op.child2_clv : op.child1_clv;
+      if (tt_writer[inner] >= 0)
+      {
+        out.lk_kids[i] = {-2, tt_writer[inner]};
+        out.cls[i] = AA_OP_LOOKUP;
+        ++out.lookups;
+      }
+    }
+    tt_writer[op.parent_clv] = plain == 2 ? (int)i : -1;
+    clv_touched[op.parent_clv] = clv_touched[op.child1_clv] = clv_touched[op.child2_clv] = 1;
+    if (op.parent_scaler >= 0) sc_touched[op.parent_scaler] = 1;
+    if (op.child1_scaler >= 0) sc_touched[op.child1_scaler] = 1;
+    if (op.child2_scaler >= 0) sc_touched[op.child2_scaler] = 1;
+  }
+  return 0;
+}
+
+void pllhip_aa_list_cert(const FusedGeom & geom, const pllhip_op_t * ops, const int * cls, unsigned int count,
+                         const double * incoming, bool ti_mfma, AaListCert & out)
+{
+  const size_t nclv = geom.nclv, nsc = geom.nsc;
+  // a list that overwrites an operand it has read from an earlier call (slot reuse across calls) is not idempotent:
+  // it could not be run again after a trip, and keeps to the reference's order
+  bool rerunnable = true;
+  {
+    std::vector<unsigned char> written(nclv, 0), sc_written(nsc, 0), ext_read(nclv, 0), sc_ext_read(nsc, 0);
+    for (unsigned int i = 0; i < count && ti_mfma; ++i)
+    {
+      const pllhip_op_t & op = ops[i];
+      for (unsigned int ch : {op.child1_clv, op.child2_clv})
+        if (!written[ch]) ext_read[ch] = 1;
+      for (int sc : {op.child1_scaler, op.child2_scaler})
+        if (sc >= 0 && !sc_written[sc]) sc_ext_read[sc] = 1;
+      if (ext_read[op.parent_clv] || (op.parent_scaler >= 0 && sc_ext_read[op.parent_scaler])) rerunnable = false;
+      written[op.parent_clv] = 1;
+      if (op.parent_scaler >= 0) sc_written[op.parent_scaler] = 1;
+    }
+  }
+  out.list_ti_mfma = ti_mfma && rerunnable;
+  out.op_inexact.assign(count, 0);
+  out.out_marks.clear();
+  std::vector<double> err(nclv, 0.0);
+  std::vector<unsigned char> local(nclv, 0);
+  bool any_ti = false;
+  double worst = 0.0;
+  for (int attempt = 0; attempt < 2; ++attempt)
+  {
+    // (first with the tip-inner mat-vecs on the matrix cores; if the bounds then outgrow every window -- operands
+    // that earlier calls left with large bounds -- once more with every op in the reference's order)
+    std::fill(local.begin(), local.end(), 0);
+    out.ext_marks.clear();
+    any_ti = false;
+    worst = 0.0;
+    for (unsigned int i = 0; i < count; ++i)
+    {
+      const pllhip_op_t & op = ops[i];
+      const bool source = cls[i] == AA_OP_TI && out.list_ti_mfma;
+      any_ti = any_ti || source;
+      double in = 0.0;
+      for (unsigned int ch : {op.child1_clv, op.child2_clv})
+      {
+        if (geom.is_tip(ch)) continue;
+        if (!local[ch])
+        {
+          // an operand from an earlier call: the plan holds for THIS bound of it
+          const double m = incoming ? incoming[ch] : 0.0;
+          bool seen = false;
+          for (const auto & e : out.ext_marks) seen = seen || e.first == ch;
+          if (!seen) out.ext_marks.push_back({ch, m});
+          in += m;
+        }
+        else in += err[ch];
+      }
+      const double bound = (source || in > 0.0) ? in + PLLHIP_CERT_OP_ERR : 0.0;
+      err[op.parent_clv] = bound;
+      local[op.parent_clv] = 1;
+      out.op_inexact[i] = bound > 0.0 && op.parent_scaler >= 0;
+      if (out.op_inexact[i] && bound > worst) worst = bound;
+    }
+    if (!(out.list_ti_mfma && 8.0 * worst > PLLHIP_CERT_WINDOW_MAX)) break;
+    out.list_ti_mfma = false;
+  }
+  for (unsigned int i = 0; i < nclv; ++i)
+    if (local[i]) out.out_marks.push_back({i, err[i]});
+  out.cert_kind = !(worst > 0.0) ? 0 : (any_ti ? 1 : 2);
+  out.too_wide = 8.0 * worst > PLLHIP_CERT_WINDOW_MAX;
+  out.window = std::min(std::max(8.0 * worst, PLLHIP_CERT_WINDOW_MIN), PLLHIP_CERT_WINDOW_MAX);
+}
+
+int pllhip_aa_list_walk(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * cls,
+                        const int * scales, unsigned int count, unsigned int max_segments, unsigned int nslots,
+                        AaListWalk & out)
+{
+  std::vector<pllhip_op_t> rops;
+  std::vector<PartialsArgs> rargs;
+  std::vector<int> rkinds;
+  out.ahead.clear();
+  out.orig.clear();
+  out.plan.clear();
+  out.seg_first.clear();
+  out.seg_n.clear();
+  out.sync_left.clear();
+  out.reloads = 0;
+  for (int pass = 0; pass < 2; ++pass) // (tip-tip ops grouped by mode: without a scale buffer first)
+    for (unsigned int i = 0; i < count; ++i)
+      if (cls[i] == AA_OP_TT_AHEAD && (scales[i] != 0) == (pass == 1)) out.ahead.push_back(i);
+  for (unsigned int i = 0; i < count; ++i)
+    if (cls[i] != AA_OP_TT_AHEAD)
+    {
+      rops.push_back(ops[i]);
+      rargs.push_back(args[i]);
+      rkinds.push_back(pllhip_aa_walk_kind(cls[i]));
+      out.orig.push_back((int)i);
+    }
+  const unsigned int n = (unsigned int)rops.size();
+  if (n == 0) return 1; // nothing but tip-tip ops
+  std::vector<unsigned int> seg_of;
+  out.nsegs = pllhip_fused_segments(geom, rops.data(), n, max_segments, seg_of);
+  std::vector<std::vector<FusedOp>> seg_plans;
+  const int rc = pllhip_fused_plan_segments(geom, rops.data(), rargs.data(), rkinds.data(), nullptr, n, seg_of.data(), out.nsegs,
+                                            nslots, seg_plans, &out.reloads);
+  if (rc) return rc;
+  for (unsigned int sg = 0; sg < out.nsegs; ++sg)
+  {
+    out.seg_first.push_back((unsigned int)out.plan.size());
+    out.seg_n.push_back((unsigned int)seg_plans[sg].size());
+    if (sg == 0) out.plan.swap(seg_plans[0]); // (one segment: no copy)
+    else out.plan.insert(out.plan.end(), seg_plans[sg].begin(), seg_plans[sg].end());
+  }
+  out.sync_left.assign(n, 0);
+  for (unsigned int sg = 0; sg < out.nsegs; ++sg)
+  {
+    const FusedOp * f = out.plan.data() + out.seg_first[sg];
+    const unsigned int m = out.seg_n[sg];
+    for (unsigned int pos = 0; pos < m; ++pos)
+      out.sync_left[out.seg_first[sg] + pos] = f[pos].kind == 0 && f[(pos + m - 1) % m].kind == 2;
+  }
+  return 0;
+}
+
+void pllhip_aa_list_kinds_of(const int * cls, unsigned int count, bool list_ti_mfma, unsigned int reloads,
+                             unsigned int * out8)
+{
+  unsigned int n[5] = {0, 0, 0, 0, 0};
+  for (unsigned int i = 0; i < count; ++i) ++n[cls[i]];
+  const unsigned int v[8] = {count, n[AA_OP_TT_AHEAD], n[AA_OP_TT_LIST], n[AA_OP_LOOKUP], n[AA_OP_II],
+                             list_ti_mfma ? n[AA_OP_TI] : 0u, list_ti_mfma ? 0u : n[AA_OP_TI], reloads};
+  for (int t = 0; t < 8; ++t) out8[t] = v[t];
+}
+
 // ---- the planner without a device (tests, tools): fake addresses, the same code
 
 static int dry_ops_in_range(const char * who, const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count)
@@ -825,6 +1004,69 @@ extern "C" int pllhip_fused_plan_dry(unsigned int tips, unsigned int clv_buffers
     if (slots_out) dry_slots_out(plan[pos], slots_out + (size_t)pos * 6);
   }
   if (reloads_out) *reloads_out = reloads;
+  return 0;
+}
+
+// The 20-state list without a device (tests/test_host_aa_list_plan.py, test_gpu_aa_list_plan.py): the three steps
+// pllhip_aa_fused_update takes before it encodes anything, on fake addresses.  incoming: the bound an earlier call left
+// on each CLV (tips + clv_buffers entries; NULL: none).
+// op_out[7 i ..]: op i's class (AaOpClass), its two lookup kids, whether its scaling test looks for the window, its
+// segment, its position in that segment's walk and the sync-left flag (-1 / -1 / 0: ahead of the list).
+// list_out[14]: list_ti_mfma, cert_kind, cert_too_wide, reloads, segments, ops walked, pllhip_aa_list_kinds' eight.
+// bounds_out (tips + clv_buffers): `incoming` with what the list leaves marked.  Any output may be NULL.
+// Returns 0, 1 if the kernel does not take the list (op_out holds the classes if it got that far), -1 on bad indices.
+extern "C" int pllhip_aa_list_plan_dry(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                       int pattern_tip, const pllhip_op_t * ops, unsigned int count,
+                                       unsigned int lookups_max, int tt_inside, int ti_mfma, unsigned int max_segments,
+                                       const double * incoming, int * op_out, int * list_out, double * window_out,
+                                       double * bounds_out)
+{
+  const FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
+  if (dry_ops_in_range("pllhip_aa_list_plan_dry", geom, ops, count)) return -1;
+  std::vector<PartialsArgs> args(count);
+  std::vector<int> kinds(count), scales(count);
+  for (unsigned int i = 0; i < count; ++i)
+  {
+    dry_resolve(geom, ops[i], args[i], kinds[i], nullptr);
+    scales[i] = ops[i].parent_scaler >= 0;
+  }
+  for (unsigned int t = 0; list_out && t < 14; ++t) list_out[t] = 0;
+  for (unsigned int t = 0; op_out && t < 7 * count; ++t) op_out[t] = t % 7 == 0 || t % 7 == 3 || t % 7 == 6 ? 0 : -1;
+  AaListClasses lc;
+  if (pllhip_aa_list_classify(geom, ops, kinds.data(), scales.data(), count, lookups_max, tt_inside != 0 && pattern_tip, lc)) return 1;
+  AaListCert cert;
+  pllhip_aa_list_cert(geom, ops, lc.cls.data(), count, incoming, ti_mfma != 0, cert);
+  for (unsigned int i = 0; op_out && i < count; ++i)
+  {
+    const int v[4] = {lc.cls[i], lc.lk_kids[i].first, lc.lk_kids[i].second, cert.op_inexact[i]};
+    memcpy(op_out + 7 * (size_t)i, v, sizeof(v));
+  }
+  if (window_out) *window_out = cert.window;
+  for (size_t i = 0; bounds_out && i < geom.nclv; ++i) bounds_out[i] = incoming ? incoming[i] : 0.0;
+  for (const auto & m : cert.out_marks)
+    if (bounds_out) bounds_out[m.first] = m.second;
+  AaListWalk walk;
+  const int rc = pllhip_aa_list_walk(geom, ops, args.data(), lc.cls.data(), scales.data(), count, max_segments,
+                                     PLLHIP_AA_FUSED_SLOTS, walk);
+  if (list_out)
+  {
+    const int v[6] = {cert.list_ti_mfma, cert.cert_kind, cert.too_wide, (int)walk.reloads, rc ? 0 : (int)walk.nsegs,
+                      rc ? 0 : (int)walk.plan.size()};
+    memcpy(list_out, v, sizeof(v));
+    unsigned int k8[8];
+    pllhip_aa_list_kinds_of(lc.cls.data(), count, cert.list_ti_mfma, walk.reloads, k8);
+    for (int t = 0; t < 8; ++t) list_out[6 + t] = (int)k8[t];
+  }
+  if (rc) return rc;
+  for (unsigned int sg = 0; op_out && sg < walk.nsegs; ++sg)
+    for (unsigned int pos = 0; pos < walk.seg_n[sg]; ++pos)
+    {
+      const unsigned int at = walk.seg_first[sg] + pos;
+      int * o = op_out + 7 * (size_t)walk.orig[walk.plan[at].list_pos];
+      o[4] = (int)sg;
+      o[5] = (int)pos;
+      o[6] = walk.sync_left[at];
+    }
   return 0;
 }
 

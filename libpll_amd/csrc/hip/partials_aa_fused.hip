@@ -40,8 +40,9 @@
 //   stores    a finished tile goes through a per-wave LDS stage into the 16-bytes-per-lane
 //             layout: 5 KB contiguous per wave and op.
 //
-// The order of the list and the slots come from the planner of partials_fused.hip (depth
-// first, heavier subtree first; Belady for evictions).
+// What a list is to this kernel -- each op's class, the scaling certificate's bounds, the order, segments and slots
+// (depth first, heavier subtree first; Belady for evictions) -- is decided in fused_plan.hip, on indices alone
+// (partials_fused.hpp); the host part of this file encodes that into records and jobs, keeps the buffers, launches.
 //
 // Roofline: HBM writes, 644 B per site-update (640 B CLV + 4 B scaler count) + tip
 // characters; the matrix cores run 80 MFMAs per 16 columns and child (16 cycles each):
@@ -66,7 +67,7 @@ constexpr int AF_J = 2;                    // sub-tiles per wave
 constexpr int AF_WS = 4 * AF_J;            // sites of a wave's tile
 constexpr int AF_WGS = 4 * AF_WS;          // sites of a workgroup's tile (four waves)
 constexpr int AF_TILE_B = AF_WS * 640;     // bytes of a wave's tile of a CLV
-constexpr int AF_NSLOT = 5;                // values a wave keeps in registers
+constexpr int AF_NSLOT = PLLHIP_AA_FUSED_SLOTS; // values a wave keeps in registers
 constexpr int AF_MAT_PIECES = 13;          // 1 KB pieces of a matrix block in operand order (12.5, padded)
 constexpr int AF_MAT_B = AF_MAT_PIECES * 1024;
 constexpr int AF_LDS_B = 3 * AF_MAT_B + 4 * 2 * AF_TILE_B + 16; // two workgroups per CU: 158 of its 160 KB
@@ -988,56 +989,63 @@ __global__ __launch_bounds__(256, 2) void k_aa_fused(const AaRec * __restrict__ 
 } // namespace
 
 // ---------------------------------------------------------------- host
+//
+// pllhip_aa_fused_update reads as: gate, replay, classify, bounds, plan, tables, encode, upload, launch, keep.
+// What a list IS -- the class of every op, the scaling certificate's bounds, the order and segments it is walked in,
+// which op needs a barrier of its own -- is decided by fused_plan.hip on indices (partials_fused.hpp: the device-less
+// pllhip_aa_list_plan_dry runs the same three functions); what is here turns that into records and jobs with
+// addresses in them, keeps the buffers, and launches.
 
+// The kept plan of the last list.
 struct pllhip_aa_fused_cache
 {
-  std::vector<pllhip_op_t> last_ops;
-  unsigned int epoch = 0, maxstates = 0;
-  // what runs ahead of the list kernel
-  std::vector<PartialsArgs> tt_ops;   // tip-tip ops, grouped by scaling mode
-  std::vector<int> tt_modes;
-  std::vector<PartialsArgs> lk_ops, lk_k1, lk_k2; // lookup ops and the tip-tip ops that made their children
-  unsigned int nops = 0, nmat = 0, ntip = 0;
-  int mode = SCALE_NONE;
-  size_t off_mat = 0, off_tip = 0;    // job arrays within d_plan
-  void * d_plan = nullptr;
-  void * h_plan = nullptr;
-  size_t plan_cap = 0;
-  hipEvent_t done = nullptr;
-  bool pending = false;
-  char * d_aorder = nullptr;
-  size_t aorder_cap = 0;
-  char * d_titab = nullptr;
-  size_t titab_cap = 0;
-  char * d_pairtab = nullptr;          // pair tables of the list's tip-tip ops (AfPairJob)
-  size_t pairtab_cap = 0, off_pair = 0;
-  unsigned int npair = 0;
-  size_t off_lk = 0;                   // lookup-table jobs (AaLookupJob)
-  unsigned int nlk = 0;
-  size_t off_seg = 0;                  // (round 5) the segment table: {first record, ops} per segment
-  unsigned int nsegs = 1;
-  // (round 6) the scaling certificate: the plan was made for these marks of the operands it reads from earlier calls
-  // (index, mark) and in this mode; what it leaves marked; whether any op tests, and what a trip means (ctx.hpp)
-  bool ti_mfma = false;
-  std::vector<std::pair<unsigned int, double>> ext_marks, out_marks;
-  int cert_kind = 0;
-  bool cert_too_wide = false; // the bounds outgrew the widest window: every launch counts as uncertified
-  // what the kept plan is made of (pllhip_aa_list_kinds: bench.py's flop count): ops, tip-tip ahead of the list,
-  // tip-tip in the list, lookups, inner-inner on the matrix cores, tip-inner on the matrix cores, tip-inner on the
-  // vector unit, operands reloaded
-  unsigned int kinds_of_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // what identifies it: a call with these ops, under this layout, with the tip-inner mat-vecs wanted where this plan
+  // was made with them, whose operands from earlier calls carry these certificate marks (index, mark), runs it again
+  struct
+  {
+    std::vector<pllhip_op_t> last_ops;
+    unsigned int epoch = 0, maxstates = 0;
+    bool ti_mfma = false;
+    std::vector<std::pair<unsigned int, double>> ext_marks;
+  } key;
+  // what a relaunch needs
+  struct
+  {
+    std::vector<PartialsArgs> tt_ops;   // tip-tip ops ahead of the list kernel, grouped by scaling mode
+    std::vector<int> tt_modes;
+    int mode = SCALE_NONE;
+    unsigned int nmat = 0, ntip = 0, npair = 0, nlk = 0, nsegs = 1; // jobs of k_af_prepare: matrices, tip tables, pair
+                                                                    // tables (AfPairJob), lookup tables (AaLookupJob)
+    size_t off_mat = 0, off_tip = 0, off_pair = 0, off_lk = 0, off_seg = 0; // within d_plan, behind the records; the
+                                                                            // segment table: {first record, ops} each
+    // the scaling certificate: what the list leaves marked; whether any op tests, and what a trip means (ctx.hpp)
+    std::vector<std::pair<unsigned int, double>> out_marks;
+    int cert_kind = 0;
+    bool cert_too_wide = false; // the bounds outgrew the widest window: every launch counts as uncertified
+    unsigned int kinds_of_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // pllhip_aa_list_kinds (pllhip_aa_list_kinds_of)
+  } run;
+  // the buffers it owns
+  struct
+  {
+    void * d_plan = nullptr, * h_plan = nullptr; // records, jobs, segment table; its pinned staging copy
+    size_t plan_cap = 0;
+    hipEvent_t done = nullptr;                   // the staging copy has been read
+    bool pending = false;
+    char * d_aorder = nullptr, * d_titab = nullptr, * d_pairtab = nullptr; // matrices in operand order, tip tables,
+    size_t aorder_cap = 0, titab_cap = 0, pairtab_cap = 0;                 // pair tables of the list's tip-tip ops
+  } buf;
 };
 
 void pllhip_aa_fused_free(pllhip_ctx * c)
 {
   pllhip_aa_fused_cache * k = c->aa_fused;
   if (!k) return;
-  if (k->d_plan) (void)hipFree(k->d_plan);
-  if (k->h_plan) (void)hipHostFree(k->h_plan);
-  if (k->done) (void)hipEventDestroy(k->done);
-  if (k->d_aorder) (void)hipFree(k->d_aorder);
-  if (k->d_titab) (void)hipFree(k->d_titab);
-  if (k->d_pairtab) (void)hipFree(k->d_pairtab);
+  if (k->buf.d_plan) (void)hipFree(k->buf.d_plan);
+  if (k->buf.h_plan) (void)hipHostFree(k->buf.h_plan);
+  if (k->buf.done) (void)hipEventDestroy(k->buf.done);
+  if (k->buf.d_aorder) (void)hipFree(k->buf.d_aorder);
+  if (k->buf.d_titab) (void)hipFree(k->buf.d_titab);
+  if (k->buf.d_pairtab) (void)hipFree(k->buf.d_pairtab);
   delete k;
   c->aa_fused = nullptr;
 }
@@ -1045,7 +1053,8 @@ void pllhip_aa_fused_free(pllhip_ctx * c)
 // everything the kept plan describes, again: tip-tip ops, tables, matrices in operand order, the list
 static int aa_fused_launch(pllhip_ctx * c)
 {
-  pllhip_aa_fused_cache & k = *c->aa_fused;
+  const auto & k = c->aa_fused->run;
+  const auto & buf = c->aa_fused->buf;
   // tip-tip ops of one scaling mode per launch, PLLHIP_BATCH_MAX at a time
   for (size_t first = 0; first < k.tt_ops.size();)
   {
@@ -1056,13 +1065,13 @@ static int aa_fused_launch(pllhip_ctx * c)
     const int rc = pllhip_launch_aa_batch(c, b, nb, 2, mode);
     if (rc) return rc;
   }
-  const char * plan = static_cast<const char *>(k.d_plan);
+  const char * plan = static_cast<const char *>(buf.d_plan);
   if (k.nmat + k.ntip + k.npair + k.nlk)
   {
     k_af_prepare<<<std::max(1u, k.nmat + k.ntip + k.npair * AF_PAIR_WGS + k.nlk * c->maxstates), 256, 0, c->stream>>>(
-        (const AfMatJob *)(plan + k.off_mat), k.nmat, (const AfTipJob *)(plan + k.off_tip), k.ntip, k.d_aorder,
-        k.d_titab, c->tipmap, c->maxstates, c->d_tile_counter, (const AfPairJob *)(plan + k.off_pair), k.npair,
-        k.d_pairtab, (const AaLookupJob *)(plan + k.off_lk), k.nlk);
+        (const AfMatJob *)(plan + k.off_mat), k.nmat, (const AfTipJob *)(plan + k.off_tip), k.ntip, buf.d_aorder,
+        buf.d_titab, c->tipmap, c->maxstates, c->d_tile_counter, (const AfPairJob *)(plan + k.off_pair), k.npair,
+        buf.d_pairtab, (const AaLookupJob *)(plan + k.off_lk), k.nlk);
     HIP_TRY(hipGetLastError());
   }
   else HIP_TRY(hipMemsetAsync(c->d_tile_counter, 0, sizeof(unsigned int), c->stream));
@@ -1079,7 +1088,7 @@ static int aa_fused_launch(pllhip_ctx * c)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_aa_fused<MODEV, NTV>),                               \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, AF_LDS_B));                                \
     k_aa_fused<MODEV, NTV><<<(unsigned int)grid, 256, AF_LDS_B, c->stream>>>(                                          \
-        (const AaRec *)k.d_plan, (const unsigned int *)(plan + k.off_seg), k.nsegs, c->sh.sites, k.d_aorder,           \
+        (const AaRec *)buf.d_plan, (const unsigned int *)(plan + k.off_seg), k.nsegs, c->sh.sites, buf.d_aorder,       \
         c->maxstates, (double2 *)c->d_sink, c->d_tile_counter, static_rounds);                                                   \
   } while (0)
 #define AF_LAUNCH_MODE(MODEV)                                                                                          \
@@ -1110,243 +1119,394 @@ extern "C" int pllhip_aa_list_kinds(pllhip_ctx_t * c, unsigned int * out8)
 {
   for (int t = 0; t < 8; ++t) out8[t] = 0;
   pllhip_ctx * s = c->shards.empty() ? c : c->shards[0];
-  if (!s->aa_fused || s->aa_fused->last_ops.empty()) return 0;
-  memcpy(out8, s->aa_fused->kinds_of_plan, 8 * sizeof(unsigned int));
+  if (!s->aa_fused || s->aa_fused->key.last_ops.empty()) return 0;
+  memcpy(out8, s->aa_fused->run.kinds_of_plan, 8 * sizeof(unsigned int));
+  return 0;
+}
+
+namespace
+{
+// (PLLHIP_FUSED_DEBUG=3: where the host's time goes when a list is new)
+struct AaHostLaps
+{
+  bool on;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void operator()(const char * what)
+  {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "pllhip 20-state list, host: %-28s %7.1f us\n", what, std::chrono::duration<double, std::micro>(now - t).count());
+    t = now;
+  }
+};
+
+// the ops as resolve_op sees them: `resolved` of them (the first that fails ends it, with `rc`)
+struct AaResolved
+{
+  std::vector<PartialsArgs> args;
+  std::vector<int> kinds, modes;
+  unsigned int resolved = 0;
+  int rc = 0;
+};
+
+// a new list, as far as it is decided before a byte is encoded
+struct AaPlanned
+{
+  AaListClasses lc;
+  AaListCert cert;
+  AaListWalk walk;
+  unsigned int lookups_max = 0;
+  std::vector<int> lk_index;          // per position of the walk: the number of its lookup's table set, -1 none
+  std::vector<AaLookupTables> tabs;   // the lookups' tables, in walk order, and the jobs that fill them (two each)
+  std::vector<AaLookupJob> lj;
+};
+
+// records and jobs of a list, addresses of the cache's own tables still relative (aa_upload makes them absolute)
+struct AaEncoded
+{
+  std::vector<AaRec> recs; // per segment: the header, one record per op, the record that names op 0 again
+  std::vector<unsigned int> segtab;
+  std::vector<AfMatJob> mj;
+  std::vector<AfTipJob> tj;
+  std::vector<AfPairJob> pj;
+  std::vector<size_t> tt_pair_rec, tt_inside_rec, op_rec; // (absolute record numbers: whose tab_l / tab_r are relative)
+  unsigned int synced = 0;
+};
+struct AaEncodeIn
+{
+  const AaPlanned & p;
+  const PartialsArgs * args;
+  unsigned int maxstates;
+  size_t pair_budget_b;               // what the lookups of this list left of their pool's budget, for pair tables
+  unsigned long long zero_row, cert_flag; // a row of zero characters; the address of the call's flag word
+  size_t tip_tab_b() const { return (size_t)maxstates * 80 * sizeof(double); }
+  size_t pair_tab_b() const { return (size_t)maxstates * tip_tab_b(); }
+};
+} // namespace
+
+// classify, bounds, plan, tables.  Returns 0, 1 if the list is not one this path takes, < 0 on error.
+static int aa_plan_list(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count, const AaResolved & r, bool ti_mfma,
+                        AaHostLaps & lap, AaPlanned & p)
+{
+  pllhip_aa_fused_cache & k = *c->aa_fused;
+  const FusedGeom geom = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
+  // Tip-tip ops run INSIDE the list: parent = tip table of the left matrix [character 1] (.) tip table of the right
+  // matrix [character 2] is what a lookup op does with two other tables, so a tip-tip op is a lookup op whose tables
+  // are the two tip tables k_af_prepare builds anyway -- or, within the pool's budget, ONE gather from its pair table
+  // (AfPairJob) -- and its stores interleave with the matrix ops of the other workgroup on the CU instead of
+  // preceding the list as a launch of their own.  Round 3 put them ahead of a list seen for the first time; round 4:
+  // inside, always (profiles/r4_aa_tt_inside_ab.txt, ahead / inside: C3 2.10 / 1.80 ms, 64-taxon random tree 2.68 /
+  // 2.47, 200-taxon random tree 4.49 / 4.35).  PLLHIP_AA_TT_INSIDE=0 puts them ahead again (k_aa_tt_rounds).
+  const char * tt_env = pllhip_env("PLLHIP_AA_TT_INSIDE");
+  const bool tt_inside = c->sh.pattern_tip && !(tt_env && atoi(tt_env) == 0);
+  p.lookups_max = pllhip_aa_cherry_covers(c, SCALE_SITE) ? pllhip_aa_lookup_budget(c) : 0u; // (their tables' pool is bounded)
+  if (pllhip_aa_list_classify(geom, ops, r.kinds.data(), r.modes.data(), r.resolved, p.lookups_max, tt_inside, p.lc)) return 1;
+  if (r.rc) return r.rc;
+  // Tip-inner mat-vecs on the matrix cores (the default, round 6) -- unless the list is being run again after its
+  // certificate tripped (ti_mfma), or could not be run again, or its bounds outgrow every window (pllhip_aa_list_cert)
+  const double * incoming = (c->n_inexact && c->clv_err.size() == geom.nclv) ? c->clv_err.data() : nullptr;
+  pllhip_aa_list_cert(geom, ops, p.lc.cls.data(), count, incoming, ti_mfma, p.cert);
+  k.key.ext_marks = p.cert.ext_marks;
+  k.key.ti_mfma = ti_mfma;
+  k.run.out_marks = p.cert.out_marks;
+  k.run.cert_kind = p.cert.cert_kind;
+  k.run.cert_too_wide = p.cert.too_wide;
+  if (p.cert.cert_kind == 1) c->cert_ops.assign(ops, ops + count);
+  lap("resolve + classify");
+  // Round 5: independent sub-lists as segments of the launch, (tile, segment) work items, while the tiles alone do
+  // not fill the device's workgroup slots eight times over (partials_fused.hpp); PLLHIP_FUSED_SEGMENTS=0 / n: never /
+  // up to n whatever the size.
+  unsigned int max_segs = ((size_t)c->sh.sites + AF_WGS - 1) / AF_WGS < (size_t)c->num_cus * 2 * 8 ? PLLHIP_FUSED_MAX_SEGS : 1u;
+  if (const char * e = pllhip_env("PLLHIP_FUSED_SEGMENTS")) max_segs = (unsigned int)std::max(1, atoi(e));
+  int rc = pllhip_aa_list_walk(geom, ops, r.args.data(), p.lc.cls.data(), r.modes.data(), count, max_segs, AF_NSLOT, p.walk);
+  k.run.tt_ops.clear();
+  k.run.tt_modes.clear();
+  for (unsigned int i : p.walk.ahead)
+  {
+    k.run.tt_ops.push_back(r.args[i]);
+    k.run.tt_modes.push_back(r.modes[i]);
+  }
+  if (rc) return rc;
+  lap("plan (order, slots)");
+  // the lookup tables' addresses are needed in the records: their places now (their pool may move); k_af_prepare
+  // fills them (AaLookupJob)
+  const unsigned int n = (unsigned int)p.walk.plan.size();
+  std::vector<PartialsArgs> lk_ops, lk_k1, lk_k2; // lookup ops and the tip-tip ops that made their children
+  lk_ops.reserve(p.lc.lookups);
+  lk_k1.reserve(p.lc.lookups);
+  lk_k2.reserve(p.lc.lookups);
+  p.lk_index.assign(n, -1);
+  for (unsigned int pos = 0; pos < n; ++pos)
+  {
+    const int oi = p.walk.orig[p.walk.plan[pos].list_pos];
+    if (p.lc.cls[oi] != AA_OP_LOOKUP) continue; // (a tip-tip op of the list needs no lookup tables)
+    p.lk_index[pos] = (int)lk_ops.size();
+    lk_ops.push_back(r.args[oi]);
+    PartialsArgs none; // marks a tip-inner lookup op (no producing op on the tip's side)
+    memset(&none, 0, sizeof(none));
+    lk_k1.push_back(p.lc.lk_kids[oi].first >= 0 ? r.args[p.lc.lk_kids[oi].first] : none);
+    lk_k2.push_back(r.args[p.lc.lk_kids[oi].second]);
+  }
+  p.tabs.resize(lk_ops.size());
+  p.lj.resize(2 * lk_ops.size());
+  if (!lk_ops.empty())
+    rc = pllhip_aa_lookup_tables(c, lk_ops.data(), lk_k1.data(), lk_k2.data(), (unsigned int)lk_ops.size(), p.tabs.data(), p.lj.data());
+  if (!rc) lap("lookup tables (launches)");
+  return rc;
+}
+
+static unsigned int slot4(int s) { return (unsigned int)(s > 0 ? s : 0) & 15u; }
+
+// what the op BEFORE the one `f` plans does for it: its reloads
+static void aa_encode_reloads(AaRec & r, const FusedOp & f)
+{
+  if (f.dma_flags & 1)
+  {
+    r.flags |= AF_RELOAD_A;
+    r.ra_src = (unsigned long long)(uintptr_t)f.left_hbm;
+    r.ra_cnt = (unsigned long long)(uintptr_t)f.lsc_hbm;
+    r.slots |= slot4(f.lslot) << 12;
+  }
+  if (f.dma_flags & 2)
+  {
+    r.flags |= AF_RELOAD_B;
+    r.rb_src = (unsigned long long)(uintptr_t)f.right_hbm;
+    r.rb_cnt = (unsigned long long)(uintptr_t)f.rsc_hbm;
+    r.slots |= slot4(f.rslot) << 16;
+  }
+}
+
+// One op: `r` its record (absolute number rec_no), `o` what it brings along itself -- its rows, its left block, its
+// kind --, which aa_encode records with the ops before it.  `at`: its position in the walk.
+static void aa_encode_op(const AaEncodeIn & in, unsigned int at, size_t rec_no, AaRec & r, AaRec & o, AaEncoded & e)
+{
+  const FusedOp & f = in.p.walk.plan[at];
+  const int oi = in.p.walk.orig[f.list_pos];
+  const PartialsArgs & a = in.args[oi];
+  const bool tt_op = in.p.lc.cls[oi] == AA_OP_TT_LIST, list_ti_mfma = in.p.cert.list_ti_mfma;
+  const int kind = pllhip_aa_walk_kind(in.p.lc.cls[oi]);
+  const size_t tip_tab_b = in.tip_tab_b(), pair_tab_b = in.pair_tab_b();
+  e.op_rec.push_back(rec_no);
+  r.parent = (unsigned long long)(uintptr_t)f.parent;
+  r.pscaler = (unsigned long long)(uintptr_t)f.pscaler;
+  r.flags = (unsigned int)kind;
+  o.flags = (unsigned int)kind;
+  if (f.pslot >= 0) r.flags |= AF_HAS_PSLOT;
+  if (f.pscaler) r.flags |= tt_op ? AF_ZERO_COUNTS : AF_SCALING;
+  if (f.pscaler && in.p.cert.op_inexact[oi] && kind <= 1) r.flags |= AF_CERT;
+  if (kind == 0 && f.lsc_slot >= 0) r.flags |= AF_LCNT;
+  if (kind <= 1 && f.rsc_slot >= 0) r.flags |= AF_RCNT;
+  if (in.p.walk.sync_left[at])
+  {
+    r.flags |= AF_SYNC_LEFT; // (AaListWalk::sync_left: an inner-inner op behind a barrier-free one)
+    ++e.synced;
+  }
+  r.slots = slot4(f.lslot) | slot4(f.rslot) << 4 | slot4(f.pslot) << 8;
+  for (int t = 0; t < 4; ++t) o.row[t] = in.zero_row;
+  if (kind == 0)
+  {
+    o.xoff = (unsigned int)(e.mj.size() * AF_MAT_B);
+    e.mj.push_back(AfMatJob{f.lmat, (unsigned long long)o.xoff, 0ull});
+  }
+  if (kind <= 1)
+  {
+    r.yoff = (unsigned int)(e.mj.size() * AF_MAT_B);
+    e.mj.push_back(AfMatJob{f.rmat, (unsigned long long)r.yoff, (kind == 1 && !list_ti_mfma) ? 1ull : 0ull});
+    if (kind == 1 && list_ti_mfma) r.flags |= AF_TI_MFMA;
+  }
+  if (kind == 1)
+  {
+    o.row[0] = (unsigned long long)(uintptr_t)f.ltip;
+    r.tab_l = (unsigned long long)(e.tj.size() * tip_tab_b); // (relative: aa_upload)
+    e.tj.push_back(AfTipJob{f.lmat, (unsigned long long)(e.tj.size() * tip_tab_b)});
+  }
+  if (tt_op && (e.pj.size() + 1) * pair_tab_b <= in.pair_budget_b)
+  {
+    // ONE table over the character pairs (AfPairJob; offset relative): row c1 ms + c2
+    r.tab_l = (unsigned long long)(e.pj.size() * pair_tab_b);
+    e.pj.push_back(AfPairJob{a.lmat, a.rmat, (unsigned long long)(e.pj.size() * pair_tab_b)});
+    r.flags |= AF_ONE_TABLE;
+    o.row[0] = (unsigned long long)(uintptr_t)a.ltip;
+    o.row[1] = (unsigned long long)(uintptr_t)a.rtip;
+    e.tt_pair_rec.push_back(rec_no);
+  }
+  else if (tt_op)
+  {
+    // (beyond the pool's budget: the two tip tables, multiplied per site.  Offsets into the tip tables, relative;
+    // "pair" (0, character) is row `character`)
+    r.tab_l = (unsigned long long)(e.tj.size() * tip_tab_b);
+    e.tj.push_back(AfTipJob{a.lmat, (unsigned long long)(e.tj.size() * tip_tab_b)});
+    r.tab_r = (unsigned long long)(e.tj.size() * tip_tab_b);
+    e.tj.push_back(AfTipJob{a.rmat, (unsigned long long)(e.tj.size() * tip_tab_b)});
+    o.row[1] = (unsigned long long)(uintptr_t)a.ltip;
+    o.row[3] = (unsigned long long)(uintptr_t)a.rtip;
+    e.tt_inside_rec.push_back(rec_no);
+  }
+  else if (kind == 2)
+  {
+    const AaLookupTables & t = in.p.tabs[in.p.lk_index[at]];
+    r.tab_l = (unsigned long long)(uintptr_t)t.tl;
+    r.tab_r = (unsigned long long)(uintptr_t)t.tr;
+    o.row[0] = (unsigned long long)(uintptr_t)t.t1;
+    o.row[1] = (unsigned long long)(uintptr_t)t.t2;
+    o.row[2] = (unsigned long long)(uintptr_t)t.t3;
+    o.row[3] = (unsigned long long)(uintptr_t)t.t4;
+  }
+}
+
+// plan + classes + arguments + table addresses -> records, segment table, jobs, fix-up lists.  No HIP call.
+static void aa_encode(const AaEncodeIn & in, AaEncoded & e)
+{
+  const AaListWalk & w = in.p.walk;
+  for (unsigned int sg = 0; sg < w.nsegs; ++sg)
+  {
+    const unsigned int first = w.seg_first[sg], m = w.seg_n[sg];
+    const size_t base = e.recs.size();
+    e.segtab.push_back((unsigned int)base);
+    e.segtab.push_back(m);
+    e.recs.resize(base + m + 2);
+    AaRec * const R = e.recs.data() + base;
+    memset(R, 0, (m + 2) * sizeof(AaRec));
+    aa_encode_reloads(R[0], w.plan[first]);
+    // what each op brings along itself is recorded with the op BEFORE it (the header for op 0; the last op names
+    // op 0 again: the segment is walked tile after tile)
+    std::vector<AaRec> own(m);
+    memset(own.data(), 0, m * sizeof(AaRec));
+    for (unsigned int pos = 0; pos < m; ++pos)
+    {
+      aa_encode_op(in, first + pos, base + pos + 1, R[pos + 1], own[pos], e);
+      if (pos + 1 < m) aa_encode_reloads(R[pos + 1], w.plan[first + pos + 1]);
+    }
+    for (unsigned int pos = 0; pos <= m; ++pos)
+    {
+      // R[pos] is the record before op `pos` (R[0]: the header; R[m] names op 0 again)
+      const AaRec & o = own[pos == m ? 0 : pos];
+      AaRec & r = R[pos];
+      r.xoff = o.xoff;
+      r.flags |= (o.flags & AF_KIND_MASK) << 8;
+      // (rows: those of the op after next -- the header names op 0's)
+      const AaRec & o2 = pos == 0 ? own[0] : own[(pos + 1) % m];
+      for (int t = 0; t < 4; ++t) r.row[t] = o2.row[t];
+      // the link: the record of the op that runs after this record's (the header's: op 0's; the last op's: op 0's again)
+      r.flags |= (unsigned int)(base + (pos == m ? 1u : pos + 1u)) << AF_NEXT_SHIFT;
+      if (pos == m) r.flags |= AF_LAST;
+    }
+    R[0].yoff = (unsigned int)(base + m); // (the segment's last record: the prologue takes op 1's rows from it)
+    // (the scaling certificate's rare path reads these two from the header: the flag's address, the window)
+    R[0].parent = in.cert_flag;
+    const double win = PLLHIP_SCALE_THRESHOLD * in.p.cert.window;
+    memcpy(&R[0].pscaler, &win, sizeof(win));
+  }
+}
+
+// a device buffer of the cache with room for `need` bytes (what it held is not kept: the plan is being rebuilt)
+template <typename T>
+static int aa_grow(pllhip_ctx * c, T *& buf, size_t & cap, size_t need, size_t new_cap)
+{
+  if (cap >= need) return 0;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (buf) HIP_TRY(hipFree(buf));
+  buf = nullptr;
+  cap = new_cap;
+  HIP_TRY(hipMalloc((void **)&buf, cap));
+  return 0;
+}
+
+// room for the tables, their addresses into the records, the plan laid out and on its way to the device
+static int aa_upload(pllhip_ctx * c, const AaEncodeIn & in, AaEncoded & e, const std::vector<AaLookupJob> & lj)
+{
+  auto & run = c->aa_fused->run;
+  auto & buf = c->aa_fused->buf;
+  const size_t mats_b = (e.mj.size() + 1) * (size_t)AF_MAT_B, tips_b = (e.tj.size() + 1) * in.tip_tab_b(),
+               pairs_b = (e.pj.size() + 1) * in.pair_tab_b();
+  int rc = aa_grow(c, buf.d_aorder, buf.aorder_cap, mats_b, mats_b * 2);
+  if (!rc) rc = aa_grow(c, buf.d_titab, buf.titab_cap, tips_b, tips_b * 2);
+  if (!rc) rc = aa_grow(c, buf.d_pairtab, buf.pairtab_cap, pairs_b, pairs_b);
+  if (rc) return rc;
+  for (size_t ri : e.tt_pair_rec) e.recs[ri].tab_l += (unsigned long long)(uintptr_t)buf.d_pairtab;
+  for (size_t ri : e.op_rec)
+    if ((e.recs[ri].flags & AF_KIND_MASK) == 1u) e.recs[ri].tab_l += (unsigned long long)(uintptr_t)buf.d_titab;
+  for (size_t ri : e.tt_inside_rec)
+  {
+    e.recs[ri].tab_l += (unsigned long long)(uintptr_t)buf.d_titab;
+    e.recs[ri].tab_r += (unsigned long long)(uintptr_t)buf.d_titab;
+  }
+  // the plan: records, then the four job arrays (one spare entry each), then the segment table
+  run.off_mat = e.recs.size() * sizeof(AaRec);
+  run.off_tip = run.off_mat + (e.mj.size() + 1) * sizeof(AfMatJob);
+  run.off_pair = run.off_tip + (e.tj.size() + 1) * sizeof(AfTipJob);
+  run.off_lk = run.off_pair + (e.pj.size() + 1) * sizeof(AfPairJob);
+  run.off_seg = run.off_lk + (lj.size() + 1) * sizeof(AaLookupJob);
+  const size_t bytes = run.off_seg + 2 * PLLHIP_FUSED_MAX_SEGS * sizeof(unsigned int);
+  if (buf.plan_cap < bytes)
+  {
+    rc = aa_grow(c, buf.d_plan, buf.plan_cap, bytes, bytes * 2);
+    if (rc) return rc;
+    if (buf.h_plan) HIP_TRY(hipHostFree(buf.h_plan));
+    buf.h_plan = nullptr;
+    HIP_TRY(hipHostMalloc(&buf.h_plan, buf.plan_cap, hipHostMallocDefault));
+    if (!buf.done) HIP_TRY(hipEventCreateWithFlags(&buf.done, hipEventDisableTiming));
+    buf.pending = false;
+  }
+  if (buf.pending) HIP_TRY(hipEventSynchronize(buf.done));
+  char * stage = static_cast<char *>(buf.h_plan);
+  memcpy(stage, e.recs.data(), run.off_mat);
+  if (!e.mj.empty()) memcpy(stage + run.off_mat, e.mj.data(), e.mj.size() * sizeof(AfMatJob));
+  if (!e.tj.empty()) memcpy(stage + run.off_tip, e.tj.data(), e.tj.size() * sizeof(AfTipJob));
+  if (!e.pj.empty()) memcpy(stage + run.off_pair, e.pj.data(), e.pj.size() * sizeof(AfPairJob));
+  if (!lj.empty()) memcpy(stage + run.off_lk, lj.data(), lj.size() * sizeof(AaLookupJob));
+  memcpy(stage + run.off_seg, e.segtab.data(), e.segtab.size() * sizeof(unsigned int));
+  HIP_TRY(hipMemcpyAsync(buf.d_plan, buf.h_plan, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(buf.done, c->stream));
+  buf.pending = true;
+  run.nlk = (unsigned int)lj.size();
+  run.npair = (unsigned int)e.pj.size();
+  run.nmat = (unsigned int)e.mj.size();
+  run.ntip = (unsigned int)e.tj.size();
   return 0;
 }
 
 // Returns 0 when the list has been enqueued, 1 when it is not one this path takes (the caller
 // launches per level), < 0 on error.
-static int aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count, bool tt_wanted);
-
-// Where a list's tip-tip ops run.  Round 3: AHEAD of the list kernel (a launch of k_aa_tt_rounds) for a list seen
-// for the first time -- the cheaper plan then, 30 ops instead of 62 for BASELINE config 3 -- and INSIDE the list, as
-// lookups over the two tip tables, once the very same list came again, unless that plan reloaded more than one
-// operand.  Round 4: inside, always.  A tip-tip op of the list is ONE gather from its pair table now (AfPairJob) and
-// the planner takes a third of the time (bump-allocated lists): measured with the tip-tip ops ahead / inside
-// (profiles/r4_aa_tt_inside_ab.txt, one box): C3 2.10 / 1.80 ms, 64-taxon random tree 2.68 / 2.47, 200-taxon random
-// tree (26 operands reloaded with the tip-tip ops ahead: every tip-tip result a matrix op consumes) 4.49 / 4.35.
-// PLLHIP_AA_TT_INSIDE=0 puts them ahead again.
 int pllhip_aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count)
 {
-  return aa_fused_update(c, ops, count, true);
-}
-
-static int aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count, bool tt_wanted)
-{
+  // ---- gate
   if (c->sh.states != 20 || c->sh.rate_cats != 4 || c->sh.asc_states || !c->rows.empty() ||
       c->aa_exact || count > PLLHIP_FUSED_MAX_OPS)
     return 1;
   if (c->sh.pattern_tip && (c->maxstates < 1 || c->maxstates > 32)) return 1;
   if (!c->aa_fused) c->aa_fused = new pllhip_aa_fused_cache();
   pllhip_aa_fused_cache & k = *c->aa_fused;
-  // (PLLHIP_FUSED_DEBUG=3: where the host's time goes when a list is new)
-  const bool host_times = c->fused_debug == 3;
-  auto t_host = std::chrono::steady_clock::now();
-  auto lap = [&](const char * what) {
-    if (!host_times) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "pllhip 20-state list, host: %-28s %7.1f us\n", what, std::chrono::duration<double, std::micro>(now - t_host).count());
-    t_host = now;
-  };
-  // Tip-inner mat-vecs on the matrix cores (the default, round 6) -- unless the list is being run again after its
-  // certificate tripped, or could not be run again: a list that overwrites an operand it has read from an earlier
-  // call (slot reuse across calls) is not idempotent, and keeps to the reference's order.
+  AaHostLaps lap{c->fused_debug == 3};
+  // ---- replay: the kept plan, if it was made for this list, this layout, this mode and these marks
   const bool ti_mfma = c->aa_ti_mfma && !c->cert_force_exact;
-  if (k.last_ops.size() == count && k.epoch == c->layout_epoch && k.maxstates == c->maxstates && k.ti_mfma == ti_mfma &&
-      !c->fused_debug && memcmp(k.last_ops.data(), ops, (size_t)count * sizeof(pllhip_op_t)) == 0)
+  if (k.key.last_ops.size() == count && k.key.epoch == c->layout_epoch && k.key.maxstates == c->maxstates &&
+      k.key.ti_mfma == ti_mfma && !c->fused_debug && memcmp(k.key.last_ops.data(), ops, (size_t)count * sizeof(pllhip_op_t)) == 0)
   {
     bool same_marks = true;
-    for (const auto & m : k.ext_marks) same_marks = same_marks && pllhip_cert_err(c, m.first) == m.second;
+    for (const auto & m : k.key.ext_marks) same_marks = same_marks && pllhip_cert_err(c, m.first) == m.second;
     if (same_marks)
     {
-      if (k.cert_kind == 1) c->cert_ops.assign(ops, ops + count);
+      if (k.run.cert_kind == 1) c->cert_ops.assign(ops, ops + count);
       return aa_fused_launch(c);
     }
   }
-  k.last_ops.clear();
-
-  // ---- classify.  Tip-tip ops run ahead of the list: allowed only if nothing earlier in the list
-  // wrote or read what they write (they read tips only).  An inner-inner op over two tip-tip
-  // results of this list, or a tip-inner op over one, is a lookup.
-  std::vector<PartialsArgs> args(count);
-  std::vector<int> kinds(count), modes(count);
-  const size_t nclv = c->clv.size(), nsc = c->sh.scale_buffers;
-  std::vector<int> clv_touched(nclv, 0), sc_touched(nsc, 0), tt_writer(nclv, -1);
-  std::vector<std::pair<int, int>> lk_kids(count, {-1, -1});
-  bool any_scaler = false;
-  const bool lookups_ok = pllhip_aa_cherry_covers(c, SCALE_SITE);
-  const unsigned int lookups_max = lookups_ok ? pllhip_aa_lookup_budget(c) : 0u; // (their tables' pool is bounded)
-  unsigned int lookups = 0;
-  // Tip-tip ops INSIDE the list (kind 4 below): parent = tip table of the left matrix [character 1] (.) tip table of
-  // the right matrix [character 2] is what a lookup op does with two other tables, so a tip-tip op is a lookup op
-  // whose tables are the two tip tables k_af_prepare builds anyway and whose "pairs" are (0, character): no code of
-  // its own in the kernel.  Its stores then interleave with the matrix ops of the other workgroup on the CU
-  // instead of preceding the list as a launch of their own.  Measured (C3's partition, lists directed at five
-  // edges): a list with no or one operand reloaded from HBM gains 4-5 % (2.09-2.11 against 2.19 ms), the two
-  // lists with three reloads lose 10 % (2.47 against 2.25) -- so a list with more than one reload is planned again
-  // with the tip-tip ops ahead of it (a rule from five lists, not a law).  PLLHIP_AA_TT_INSIDE=0 / 1: never / always.
-  const char * tt_env = pllhip_env("PLLHIP_AA_TT_INSIDE");
-  const bool tt_inside = c->sh.pattern_tip && (tt_env ? atoi(tt_env) != 0 : tt_wanted);
-  for (unsigned int i = 0; i < count; ++i)
-  {
-    const int rc = pllhip_resolve_op(c, ops[i], args[i], kinds[i], modes[i]);
-    if (rc) return rc;
-    const pllhip_op_t & op = ops[i];
-    if (kinds[i] == 2 && (clv_touched[op.parent_clv] || (op.parent_scaler >= 0 && sc_touched[op.parent_scaler]))) return 1;
-    any_scaler = any_scaler || modes[i] != SCALE_NONE;
-    const int plain = kinds[i];
-    if (lookups < lookups_max && plain == 0 && tt_writer[op.child1_clv] >= 0 && tt_writer[op.child2_clv] >= 0)
-    {
-      lk_kids[i] = {tt_writer[op.child1_clv], tt_writer[op.child2_clv]};
-      kinds[i] = 3;
-      ++lookups;
-    }
-    else if (lookups < lookups_max && plain == 1)
-    {
-      const unsigned int inner = pllhip_is_tip(c, op.child1_clv) ? op.child2_clv : op.child1_clv;
-      if (tt_writer[inner] >= 0)
-      {
-        lk_kids[i] = {-2, tt_writer[inner]};
-        kinds[i] = 3;
-        ++lookups;
-      }
-    }
-    tt_writer[op.parent_clv] = plain == 2 ? (int)i : -1;
-    clv_touched[op.parent_clv] = clv_touched[op.child1_clv] = clv_touched[op.child2_clv] = 1;
-    if (op.parent_scaler >= 0) sc_touched[op.parent_scaler] = 1;
-    if (op.child1_scaler >= 0) sc_touched[op.child1_scaler] = 1;
-    if (op.child2_scaler >= 0) sc_touched[op.child2_scaler] = 1;
-  }
-
-  // ---- the scaling certificate (ctx.hpp): a bound on every op's relative difference from the reference's value --
-  // its operands' bounds plus PLLHIP_CERT_OP_ERR when anything below it ran on the matrix cores' tip-inner path --, which
-  // ops therefore test, and the window they test with
-  std::vector<unsigned char> op_inexact(count, 0);
-  bool list_ti_mfma = ti_mfma;
-  double cert_window = PLLHIP_CERT_WINDOW_MIN;
-  bool cert_too_wide = false;
-  k.ext_marks.clear();
-  k.out_marks.clear();
-  {
-    bool rerunnable = true;
-    std::vector<unsigned char> written(nclv, 0), sc_written(nsc, 0), ext_read(nclv, 0), sc_ext_read(nsc, 0);
-    for (unsigned int i = 0; i < count && ti_mfma; ++i)
-    {
-      const pllhip_op_t & op = ops[i];
-      for (unsigned int ch : {op.child1_clv, op.child2_clv})
-        if (!written[ch]) ext_read[ch] = 1;
-      for (int sc : {op.child1_scaler, op.child2_scaler})
-        if (sc >= 0 && !sc_written[sc]) sc_ext_read[sc] = 1;
-      if (ext_read[op.parent_clv] || (op.parent_scaler >= 0 && sc_ext_read[op.parent_scaler])) rerunnable = false;
-      written[op.parent_clv] = 1;
-      if (op.parent_scaler >= 0) sc_written[op.parent_scaler] = 1;
-    }
-    list_ti_mfma = ti_mfma && rerunnable;
-    std::vector<double> err(nclv, 0.0);
-    std::vector<unsigned char> local(nclv, 0);
-    bool any_ti = false;
-    double worst = 0.0;
-    for (int attempt = 0; attempt < 2; ++attempt)
-    {
-      // (first with the tip-inner mat-vecs on the matrix cores; if the bounds then outgrow every window -- operands
-      // that earlier calls left with large bounds -- once more with every op in the reference's order)
-      std::fill(local.begin(), local.end(), 0);
-      k.ext_marks.clear();
-      any_ti = false;
-      worst = 0.0;
-      for (unsigned int i = 0; i < count; ++i)
-      {
-        const pllhip_op_t & op = ops[i];
-        const bool source = kinds[i] == 1 && list_ti_mfma;
-        any_ti = any_ti || source;
-        double in = 0.0;
-        for (unsigned int ch : {op.child1_clv, op.child2_clv})
-        {
-          if (pllhip_is_tip(c, ch)) continue;
-          if (!local[ch])
-          {
-            // an operand from an earlier call: the plan holds for THIS bound of it
-            const double m = pllhip_cert_err(c, ch);
-            bool seen = false;
-            for (const auto & e : k.ext_marks) seen = seen || e.first == ch;
-            if (!seen) k.ext_marks.push_back({ch, m});
-            in += m;
-          }
-          else in += err[ch];
-        }
-        const double out = (source || in > 0.0) ? in + PLLHIP_CERT_OP_ERR : 0.0;
-        err[op.parent_clv] = out;
-        local[op.parent_clv] = 1;
-        op_inexact[i] = out > 0.0 && op.parent_scaler >= 0;
-        if (op_inexact[i] && out > worst) worst = out;
-      }
-      if (!(list_ti_mfma && 8.0 * worst > PLLHIP_CERT_WINDOW_MAX)) break;
-      list_ti_mfma = false;
-    }
-    for (unsigned int i = 0; i < nclv; ++i)
-      if (local[i]) k.out_marks.push_back({i, err[i]});
-    k.cert_kind = !(worst > 0.0) ? 0 : (any_ti ? 1 : 2);
-    cert_too_wide = 8.0 * worst > PLLHIP_CERT_WINDOW_MAX;
-    cert_window = std::min(std::max(8.0 * worst, PLLHIP_CERT_WINDOW_MIN), PLLHIP_CERT_WINDOW_MAX);
-    k.cert_too_wide = cert_too_wide;
-    if (k.cert_kind == 1) c->cert_ops.assign(ops, ops + count);
-  }
-  k.ti_mfma = ti_mfma;
-  lap("resolve + classify");
-  // ---- the list the kernel walks: everything but the tip-tip ops, ordered and given slots by the
-  // planner of the 4-state kernel (a lookup has no inner operands: a "tip-tip" op to the planner)
-  std::vector<pllhip_op_t> rops;
-  std::vector<PartialsArgs> rargs;
-  std::vector<int> rkinds, orig;
-  k.tt_ops.clear();
-  k.tt_modes.clear();
-  for (int pass = 0; pass < 2; ++pass) // (tip-tip ops grouped by mode: without a scale buffer first)
-    for (unsigned int i = 0; i < count; ++i)
-      if (kinds[i] == 2 && !tt_inside && (modes[i] != SCALE_NONE) == (pass == 1))
-      {
-        k.tt_ops.push_back(args[i]);
-        k.tt_modes.push_back(modes[i]);
-      }
-  for (unsigned int i = 0; i < count; ++i)
-    if (kinds[i] != 2 || tt_inside)
-    {
-      if (kinds[i] == 2) kinds[i] = 4; // (a tip-tip op of the list)
-      rops.push_back(ops[i]);
-      rargs.push_back(args[i]);
-      rkinds.push_back(kinds[i] >= 3 ? 2 : kinds[i]);
-      orig.push_back((int)i);
-    }
-  const unsigned int n = (unsigned int)rops.size();
-  if (n == 0)
-  {
-    // nothing but tip-tip ops
-    k.nops = 0;
-    return 1;
-  }
-  std::vector<FusedOp> fplan; // (the segments' plans one after the other; list_pos: position in rops)
-  unsigned int reloads = 0;
-  const FusedGeom geom = {nclv, nsc, c->sh.tips, c->sh.pattern_tip != 0};
-  // Round 5: independent sub-lists as segments of the launch, (tile, segment) work items, while the tiles alone do
-  // not fill the device's workgroup slots eight times over (partials_fused.hpp); PLLHIP_FUSED_SEGMENTS=0 / n: never /
-  // up to n whatever the size.
-  unsigned int max_segs = ((size_t)c->sh.sites + AF_WGS - 1) / AF_WGS < (size_t)c->num_cus * 2 * 8 ? PLLHIP_FUSED_MAX_SEGS : 1u;
-  if (const char * e = pllhip_env("PLLHIP_FUSED_SEGMENTS")) max_segs = (unsigned int)std::max(1, atoi(e));
-  std::vector<unsigned int> seg_of, seg_first, seg_n;
-  const unsigned int nsegs = pllhip_fused_segments(geom, rops.data(), n, max_segs, seg_of);
-  std::vector<std::vector<FusedOp>> seg_plans;
-  int rc = pllhip_fused_plan_segments(geom, rops.data(), rargs.data(), rkinds.data(), nullptr, n, seg_of.data(), nsegs, AF_NSLOT,
-                                      seg_plans, &reloads);
-  for (unsigned int sg = 0; rc == 0 && sg < nsegs; ++sg)
-  {
-    seg_first.push_back((unsigned int)fplan.size());
-    seg_n.push_back((unsigned int)seg_plans[sg].size());
-    if (sg == 0) fplan.swap(seg_plans[0]); // (one segment: no copy)
-    else fplan.insert(fplan.end(), seg_plans[sg].begin(), seg_plans[sg].end());
-  }
+  k.key.last_ops.clear();
+  // ---- classify, bounds, plan, tables
+  AaResolved r;
+  r.args.resize(count);
+  r.kinds.resize(count);
+  r.modes.resize(count);
+  while (r.resolved < count &&
+         !(r.rc = pllhip_resolve_op(c, ops[r.resolved], r.args[r.resolved], r.kinds[r.resolved], r.modes[r.resolved])))
+    ++r.resolved;
+  AaPlanned p;
+  const bool pool_failed_before = c->cherry_pool_failed;
+  int rc = aa_plan_list(c, ops, count, r, ti_mfma, lap, p);
+  // (the lookup tables' pool could not be allocated: the list is planned again, now without lookup ops -- the
+  // context remembers, pllhip_aa_cherry_covers)
+  if (rc == 1 && c->cherry_pool_failed && !pool_failed_before) rc = aa_plan_list(c, ops, count, r, ti_mfma, lap, p);
   if (rc) return rc;
-  lap("plan (order, slots)");
-
   // ---- encode
   if (!c->fused_zero_row)
   {
@@ -1356,288 +1516,36 @@ static int aa_fused_update(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int
   }
   if (!c->d_sink) HIP_TRY(hipMalloc(&c->d_sink, (size_t)c->num_cus * 16 * 80 * sizeof(double2)));
   if (!c->d_tile_counter) HIP_TRY(hipMalloc((void **)&c->d_tile_counter, 2 * PLLHIP_TILE_COUNTER_BYTES));
-  k.lk_ops.clear();
-  k.lk_k1.clear();
-  k.lk_k2.clear();
-  std::vector<int> lk_index(n, -1);
-  for (unsigned int pos = 0; pos < n; ++pos)
-  {
-    const int ri = fplan[pos].list_pos, oi = orig[ri];
-    if (kinds[oi] != 3) continue; // (a tip-tip op of the list needs no pair tables)
-    lk_index[pos] = (int)k.lk_ops.size();
-    k.lk_ops.push_back(args[oi]);
-    if (lk_kids[oi].first >= 0) k.lk_k1.push_back(args[lk_kids[oi].first]);
-    else
-    {
-      PartialsArgs none; // marks a tip-inner lookup op (no producing op on the tip's side)
-      memset(&none, 0, sizeof(none));
-      k.lk_k1.push_back(none);
-    }
-    k.lk_k2.push_back(args[lk_kids[oi].second]);
-  }
-  // the lookup tables' addresses are needed in the records: build them now (their pool may move)
-  std::vector<AaLookupTables> tabs(k.lk_ops.size());
-  // (round 4: the tables are made by k_af_prepare, AaLookupJob; in round 3 by launches of the tabulating kernels
-  // ahead of it)
-  std::vector<AaLookupJob> lj(2 * k.lk_ops.size());
-  if (!k.lk_ops.empty())
-  {
-    rc = pllhip_aa_lookup_tables(c, k.lk_ops.data(), k.lk_k1.data(), k.lk_k2.data(), (unsigned int)k.lk_ops.size(),
-                                 tabs.data(), lj.data());
-    // (the pool could not be allocated: once more, now without lookup ops -- the context remembers)
-    if (rc == 1 && c->cherry_pool_failed) return aa_fused_update(c, ops, count, tt_wanted);
-    if (rc) return rc;
-  }
-  lap("lookup tables (launches)");
-  std::vector<AaRec> recs; // per segment: the header, one record per op, the record that names op 0 again
-  std::vector<unsigned int> segtab;
-  std::vector<AfMatJob> mj;
-  std::vector<AfTipJob> tj;
-  std::vector<AfPairJob> pj;
-  std::vector<size_t> tt_pair_rec, tt_inside_rec, op_rec; // (absolute record numbers)
-  unsigned int synced = 0;
-  const size_t tip_tab_b = (size_t)c->maxstates * 80 * sizeof(double);
-  const size_t pair_tab_b = (size_t)c->maxstates * tip_tab_b;
   // (the pool of the pair tables shares the lookup tables' budget: what the lookups of this list left of it)
   const bool pairs_on = !(pllhip_env("PLLHIP_AA_TT_PAIRS") && atoi(pllhip_env("PLLHIP_AA_TT_PAIRS")) == 0);
   const size_t lookup_tab_b = 4 * ((size_t)c->maxstates * c->maxstates + PLLHIP_TAIL_SITES) * 80 * sizeof(double);
-  const size_t pair_budget_b = !pairs_on ? 0 : (size_t)(lookups_max > lookups ? lookups_max - lookups : 0) * lookup_tab_b;
-  const unsigned long long zero_row = (unsigned long long)(uintptr_t)c->fused_zero_row;
-  k.mode = !any_scaler ? SCALE_NONE : (c->sh.rate_scalers ? SCALE_RATE : SCALE_SITE);
-  auto slot4 = [](int s) { return (unsigned int)(s > 0 ? s : 0) & 15u; };
-  auto reloads_of = [&](AaRec & r, const FusedOp & f) {
-    // what is done during the op before `f` for it
-    if (f.dma_flags & 1)
-    {
-      r.flags |= AF_RELOAD_A;
-      r.ra_src = (unsigned long long)(uintptr_t)f.left_hbm;
-      r.ra_cnt = (unsigned long long)(uintptr_t)f.lsc_hbm;
-      r.slots |= slot4(f.lslot) << 12;
-    }
-    if (f.dma_flags & 2)
-    {
-      r.flags |= AF_RELOAD_B;
-      r.rb_src = (unsigned long long)(uintptr_t)f.right_hbm;
-      r.rb_cnt = (unsigned long long)(uintptr_t)f.rsc_hbm;
-      r.slots |= slot4(f.rslot) << 16;
-    }
-  };
-  for (unsigned int sg = 0; sg < nsegs; ++sg)
-  {
-  const unsigned int first = seg_first[sg], m = seg_n[sg];
-  const size_t base = recs.size();
-  segtab.push_back((unsigned int)base);
-  segtab.push_back(m);
-  recs.resize(base + m + 2);
-  AaRec * const R = recs.data() + base;
-  memset(R, 0, (m + 2) * sizeof(AaRec));
-  reloads_of(R[0], fplan[first]);
-  // what each op brings along itself: its rows, its left block, its kind -- recorded with the op BEFORE
-  // it (the header for op 0; the last op names op 0 again: the segment is walked tile after tile)
-  std::vector<AaRec> own(m);
-  memset(own.data(), 0, m * sizeof(AaRec));
-  for (unsigned int pos = 0; pos < m; ++pos)
-  {
-    const FusedOp & f = fplan[first + pos];
-    const int oi = orig[f.list_pos];
-    const bool tt_op = kinds[oi] == 4;
-    const int kind = kinds[oi] >= 3 ? 2 : kinds[oi];
-    AaRec & r = R[pos + 1];
-    AaRec & o = own[pos];
-    op_rec.push_back(base + pos + 1);
-    r.parent = (unsigned long long)(uintptr_t)f.parent;
-    r.pscaler = (unsigned long long)(uintptr_t)f.pscaler;
-    r.flags = (unsigned int)kind;
-    o.flags = (unsigned int)kind;
-    if (f.pslot >= 0) r.flags |= AF_HAS_PSLOT;
-    if (f.pscaler) r.flags |= tt_op ? AF_ZERO_COUNTS : AF_SCALING;
-    if (f.pscaler && op_inexact[oi] && kind <= 1) r.flags |= AF_CERT;
-    if (kind == 0 && f.lsc_slot >= 0) r.flags |= AF_LCNT;
-    if (kind <= 1 && f.rsc_slot >= 0) r.flags |= AF_RCNT;
-    r.slots = slot4(f.lslot) | slot4(f.rslot) << 4 | slot4(f.pslot) << 8;
-    for (int t = 0; t < 4; ++t) o.row[t] = zero_row;
-    if (kind == 0)
-    {
-      o.xoff = (unsigned int)(mj.size() * AF_MAT_B);
-      mj.push_back(AfMatJob{f.lmat, (unsigned long long)o.xoff, 0ull});
-    }
-    if (kind <= 1)
-    {
-      r.yoff = (unsigned int)(mj.size() * AF_MAT_B);
-      mj.push_back(AfMatJob{f.rmat, (unsigned long long)r.yoff, (kind == 1 && !list_ti_mfma) ? 1ull : 0ull});
-      if (kind == 1 && list_ti_mfma) r.flags |= AF_TI_MFMA;
-    }
-    if (kind == 1)
-    {
-      o.row[0] = (unsigned long long)(uintptr_t)f.ltip;
-      r.tab_l = (unsigned long long)(tj.size() * tip_tab_b); // (made absolute below)
-      tj.push_back(AfTipJob{f.lmat, (unsigned long long)(tj.size() * tip_tab_b)});
-    }
-    if (tt_op && (pj.size() + 1) * pair_tab_b <= pair_budget_b)
-    {
-      // ONE table over the character pairs (AfPairJob; offset made absolute below): row c1 ms + c2
-      r.tab_l = (unsigned long long)(pj.size() * pair_tab_b);
-      pj.push_back(AfPairJob{args[oi].lmat, args[oi].rmat, (unsigned long long)(pj.size() * pair_tab_b)});
-      r.flags |= AF_ONE_TABLE;
-      o.row[0] = (unsigned long long)(uintptr_t)args[oi].ltip;
-      o.row[1] = (unsigned long long)(uintptr_t)args[oi].rtip;
-      tt_pair_rec.push_back(base + pos + 1);
-    }
-    else if (tt_op)
-    {
-      // (beyond the pool's budget: the two tip tables, multiplied per site.  Offsets into the tip tables, made
-      // absolute below; "pair" (0, character) is row `character`)
-      r.tab_l = (unsigned long long)(tj.size() * tip_tab_b);
-      tj.push_back(AfTipJob{args[oi].lmat, (unsigned long long)(tj.size() * tip_tab_b)});
-      r.tab_r = (unsigned long long)(tj.size() * tip_tab_b);
-      tj.push_back(AfTipJob{args[oi].rmat, (unsigned long long)(tj.size() * tip_tab_b)});
-      o.row[1] = (unsigned long long)(uintptr_t)args[oi].ltip;
-      o.row[3] = (unsigned long long)(uintptr_t)args[oi].rtip;
-      tt_inside_rec.push_back(base + pos + 1);
-    }
-    else if (kind == 2)
-    {
-      const AaLookupTables & t = tabs[lk_index[first + pos]];
-      r.tab_l = (unsigned long long)(uintptr_t)t.tl;
-      r.tab_r = (unsigned long long)(uintptr_t)t.tr;
-      o.row[0] = (unsigned long long)(uintptr_t)t.t1;
-      o.row[1] = (unsigned long long)(uintptr_t)t.t2;
-      o.row[2] = (unsigned long long)(uintptr_t)t.t3;
-      o.row[3] = (unsigned long long)(uintptr_t)t.t4;
-    }
-    if (pos + 1 < m) reloads_of(r, fplan[first + pos + 1]);
-  }
-  // The left block of op i is staged by the four waves, a part each, while they run op i - 2, and the barrier that
-  // tells a wave that everybody's part has landed is barrier A of op i - 1 -- which a lookup does not have.  Until
-  // the tip-tip ops joined the list (runs of tens of barrier-free ops, over which the waves drift apart by whole
-  // ops) this went unnoticed: an inner-inner op behind a lookup then read its left block a few hundred cycles
-  // after the waves had last met.  Such an op now begins with a barrier of its own.
-  for (unsigned int pos = 0; pos < m; ++pos)
-    if ((own[pos].flags & AF_KIND_MASK) == 0u && (own[(pos + m - 1) % m].flags & AF_KIND_MASK) == 2u)
-    {
-      R[pos + 1].flags |= AF_SYNC_LEFT;
-      ++synced;
-    }
-  for (unsigned int pos = 0; pos <= m; ++pos)
-  {
-    // R[pos] is the record before op `pos` (R[0]: the header; R[m] names op 0 again)
-    const AaRec & o = own[pos == m ? 0 : pos];
-    AaRec & r = R[pos];
-    r.xoff = o.xoff;
-    r.flags |= (o.flags & AF_KIND_MASK) << 8;
-    // (rows: those of the op after next -- the header names op 0's)
-    const AaRec & o2 = pos == 0 ? own[0] : own[(pos + 1) % m];
-    for (int t = 0; t < 4; ++t) r.row[t] = o2.row[t];
-    // the link: the record of the op that runs after this record's (the header's: op 0's; the last op's: op 0's again)
-    r.flags |= (unsigned int)(base + (pos == m ? 1u : pos + 1u)) << AF_NEXT_SHIFT;
-    if (pos == m) r.flags |= AF_LAST;
-  }
-  R[0].yoff = (unsigned int)(base + m); // (the segment's last record: the prologue takes op 1's rows from it)
-  // (the scaling certificate's rare path reads these two from the header: the flag's address, the window)
-  R[0].parent = (unsigned long long)(uintptr_t)c->h_cert_dev;
-  {
-    const double w = PLLHIP_SCALE_THRESHOLD * cert_window;
-    memcpy(&R[0].pscaler, &w, sizeof(w));
-  }
-  } // segments
-  if (recs.size() >= (1u << (32 - AF_NEXT_SHIFT))) return 1;
-  if ((mj.size() + 1) * (size_t)AF_MAT_B > 0xffffffffull) return 1;
-  // buffers: matrices in operand order, tip tables
-  if (k.aorder_cap < (mj.size() + 1) * (size_t)AF_MAT_B)
-  {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (k.d_aorder) HIP_TRY(hipFree(k.d_aorder));
-    k.d_aorder = nullptr;
-    k.aorder_cap = (mj.size() + 1) * (size_t)AF_MAT_B * 2;
-    HIP_TRY(hipMalloc((void **)&k.d_aorder, k.aorder_cap));
-  }
-  if (k.titab_cap < (tj.size() + 1) * tip_tab_b)
-  {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (k.d_titab) HIP_TRY(hipFree(k.d_titab));
-    k.d_titab = nullptr;
-    k.titab_cap = (tj.size() + 1) * tip_tab_b * 2;
-    HIP_TRY(hipMalloc((void **)&k.d_titab, k.titab_cap));
-  }
-  if (k.pairtab_cap < (pj.size() + 1) * pair_tab_b)
-  {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (k.d_pairtab) HIP_TRY(hipFree(k.d_pairtab));
-    k.d_pairtab = nullptr;
-    k.pairtab_cap = (pj.size() + 1) * pair_tab_b;
-    HIP_TRY(hipMalloc((void **)&k.d_pairtab, k.pairtab_cap));
-  }
-  for (size_t ri : tt_pair_rec) recs[ri].tab_l += (unsigned long long)(uintptr_t)k.d_pairtab;
-  for (size_t ri : op_rec)
-    if ((recs[ri].flags & AF_KIND_MASK) == 1u) recs[ri].tab_l += (unsigned long long)(uintptr_t)k.d_titab;
-  for (size_t ri : tt_inside_rec)
-  {
-    recs[ri].tab_l += (unsigned long long)(uintptr_t)k.d_titab;
-    recs[ri].tab_r += (unsigned long long)(uintptr_t)k.d_titab;
-  }
-
-  const size_t rec_b = recs.size() * sizeof(AaRec), mat_b = (mj.size() + 1) * sizeof(AfMatJob),
-               tip_b = (tj.size() + 1) * sizeof(AfTipJob), pair_b = (pj.size() + 1) * sizeof(AfPairJob),
-               lk_b = (lj.size() + 1) * sizeof(AaLookupJob), seg_b = 2 * PLLHIP_FUSED_MAX_SEGS * sizeof(unsigned int);
-  const size_t bytes = rec_b + mat_b + tip_b + pair_b + lk_b + seg_b;
-  if (k.plan_cap < bytes)
-  {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (k.d_plan) HIP_TRY(hipFree(k.d_plan));
-    if (k.h_plan) HIP_TRY(hipHostFree(k.h_plan));
-    k.d_plan = k.h_plan = nullptr;
-    k.plan_cap = bytes * 2;
-    HIP_TRY(hipMalloc(&k.d_plan, k.plan_cap));
-    HIP_TRY(hipHostMalloc(&k.h_plan, k.plan_cap, hipHostMallocDefault));
-    if (!k.done) HIP_TRY(hipEventCreateWithFlags(&k.done, hipEventDisableTiming));
-    k.pending = false;
-  }
-  if (k.pending) HIP_TRY(hipEventSynchronize(k.done));
-  char * stage = static_cast<char *>(k.h_plan);
-  memcpy(stage, recs.data(), rec_b);
-  if (!mj.empty()) memcpy(stage + rec_b, mj.data(), mj.size() * sizeof(AfMatJob));
-  if (!tj.empty()) memcpy(stage + rec_b + mat_b, tj.data(), tj.size() * sizeof(AfTipJob));
-  if (!pj.empty()) memcpy(stage + rec_b + mat_b + tip_b, pj.data(), pj.size() * sizeof(AfPairJob));
-  if (!lj.empty()) memcpy(stage + rec_b + mat_b + tip_b + pair_b, lj.data(), lj.size() * sizeof(AaLookupJob));
-  memcpy(stage + rec_b + mat_b + tip_b + pair_b + lk_b, segtab.data(), segtab.size() * sizeof(unsigned int));
-  HIP_TRY(hipMemcpyAsync(k.d_plan, k.h_plan, bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipEventRecord(k.done, c->stream));
-  k.pending = true;
-  k.off_mat = rec_b;
-  k.off_tip = rec_b + mat_b;
-  k.off_pair = rec_b + mat_b + tip_b;
-  k.off_lk = rec_b + mat_b + tip_b + pair_b;
-  k.off_seg = rec_b + mat_b + tip_b + pair_b + lk_b;
-  k.nsegs = nsegs;
-  k.nlk = (unsigned int)lj.size();
-  k.npair = (unsigned int)pj.size();
-  k.nmat = (unsigned int)mj.size();
-  k.ntip = (unsigned int)tj.size();
-  k.nops = n;
-  {
-    unsigned int n_ii = 0, n_ti = 0;
-    for (unsigned int i = 0; i < count; ++i)
-    {
-      n_ii += kinds[i] == 0;
-      n_ti += kinds[i] == 1;
-    }
-    const unsigned int v[8] = {count, (unsigned int)k.tt_ops.size(), (unsigned int)(tt_inside_rec.size() + tt_pair_rec.size()),
-                               (unsigned int)k.lk_ops.size(), n_ii, list_ti_mfma ? n_ti : 0u, list_ti_mfma ? 0u : n_ti, reloads};
-    memcpy(k.kinds_of_plan, v, sizeof(v));
-  }
+  const size_t pair_budget_b = !pairs_on ? 0 : (size_t)(p.lookups_max > p.lc.lookups ? p.lookups_max - p.lc.lookups : 0) * lookup_tab_b;
+  const AaEncodeIn in = {p, r.args.data(), c->maxstates, pair_budget_b, (unsigned long long)(uintptr_t)c->fused_zero_row,
+                         (unsigned long long)(uintptr_t)c->h_cert_dev};
+  AaEncoded e;
+  aa_encode(in, e);
+  if (e.recs.size() >= (1u << (32 - AF_NEXT_SHIFT))) return 1;
+  if ((e.mj.size() + 1) * (size_t)AF_MAT_B > 0xffffffffull) return 1;
+  // ---- upload
+  rc = aa_upload(c, in, e, p.lj);
+  if (rc) return rc;
+  k.run.mode = !p.lc.any_scaler ? SCALE_NONE : (c->sh.rate_scalers ? SCALE_RATE : SCALE_SITE);
+  k.run.nsegs = p.walk.nsegs;
+  pllhip_aa_list_kinds_of(p.lc.cls.data(), count, p.cert.list_ti_mfma, p.walk.reloads, k.run.kinds_of_plan);
   if (c->fused_debug)
   {
-    fprintf(stderr, "pllhip 20-state list kernel: %u ops = %zu tip-tip ahead + %zu tip-tip in the list + %zu lookups + %zu on the matrix cores "
+    const unsigned int * v = k.run.kinds_of_plan;
+    fprintf(stderr, "pllhip 20-state list kernel: %u ops = %u tip-tip ahead + %u tip-tip in the list + %u lookups + %u on the matrix cores "
                     "(%u of them behind a lookup: a barrier more), %u operands reloaded, %u segment(s)\n",
-            count, k.tt_ops.size(), tt_inside_rec.size() + tt_pair_rec.size(), k.lk_ops.size(),
-            (size_t)n - k.lk_ops.size() - tt_inside_rec.size() - tt_pair_rec.size(), synced, reloads, nsegs);
+            count, v[1], v[2], v[3], count - v[1] - v[2] - v[3], e.synced, p.walk.reloads, p.walk.nsegs);
   }
   lap("encode + upload");
+  // ---- launch, keep
   rc = aa_fused_launch(c);
   if (rc) return rc;
   lap("launches");
-  k.last_ops.assign(ops, ops + count);
-  k.epoch = c->layout_epoch;
-  k.maxstates = c->maxstates;
+  k.key.last_ops.assign(ops, ops + count);
+  k.key.epoch = c->layout_epoch;
+  k.key.maxstates = c->maxstates;
   return 0;
 }

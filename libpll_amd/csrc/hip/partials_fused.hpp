@@ -1,7 +1,9 @@
-// partials_fused.hpp -- plan of the site-blocked whole-list kernel: planner (fused_plan.hip), kernels (partials_fused.hip)
+// partials_fused.hpp -- plan of the site-blocked whole-list kernels: planner and the 20-state list's classes, certificate
+// bounds and walk (fused_plan.hip), kernels (partials_fused.hip, 4 states; partials_aa_fused.hip, 20)
 #ifndef PLLHIP_PARTIALS_FUSED_HPP_
 #define PLLHIP_PARTIALS_FUSED_HPP_
 
+#include <utility>
 #include <vector>
 
 #include "ctx.hpp"
@@ -267,6 +269,75 @@ int pllhip_fused_plan_list(const FusedGeom & geom, const pllhip_op_t * ops, cons
                            const FusedExtra * extra, unsigned int count, unsigned int max_segments,
                            const unsigned int * slot_counts, unsigned int nslot_counts, FusedEdge * edge,
                            const FusedDeferral & dd, FusedListPlan & out);
+
+// ---- The 20-state list (partials_aa_fused.hip) before anything is encoded: what each op is to the kernel, what the
+// scaling certificate makes of it, the list the kernel walks.  Indices and numbers only -- ONE rule for
+// pllhip_aa_fused_update (real addresses) and pllhip_aa_list_plan_dry (fake ones; tests/test_host_aa_list_plan.py).
+constexpr unsigned int PLLHIP_AA_FUSED_SLOTS = 5; // values a wave of k_aa_fused keeps in registers
+enum AaOpClass
+{
+  AA_OP_II = 0,       // inner-inner, on the matrix cores
+  AA_OP_TI = 1,       // tip-inner
+  AA_OP_TT_AHEAD = 2, // tip-tip, run ahead of the list kernel (PLLHIP_AA_TT_INSIDE=0)
+  AA_OP_LOOKUP = 3,   // an inner-inner op over two tip-tip results of this list, or a tip-inner op over one: two table rows
+  AA_OP_TT_LIST = 4   // tip-tip, in the list: a lookup over the two tip tables, or one row of its pair table
+};
+// what the planner and the kernel take a walked op for: 0 inner-inner, 1 tip-inner, 2 no inner operand (a "lookup")
+inline int pllhip_aa_walk_kind(int cls) { return cls >= AA_OP_TT_AHEAD ? 2 : cls; }
+struct AaListClasses
+{
+  std::vector<int> cls;                     // AaOpClass per op
+  std::vector<std::pair<int, int>> lk_kids; // a lookup's producing ops {of child 1 (-2: a tip-inner lookup, no producer), of the inner child}
+  unsigned int lookups = 0;
+  bool any_scaler = false;
+};
+// kinds[i]: resolve_op's plain kind (0 / 1 / 2); scales[i] != 0: op i has a scale buffer.  At most `lookups_max`
+// lookups, the first eligible ops in list order.  Returns 1 -- the list runs per level -- for a tip-tip op whose parent
+// or scale buffer an earlier op of the list touched (tip-tip ops read tips only: they may run ahead of everything
+// only if nothing before them wrote or read what they write).
+int pllhip_aa_list_classify(const FusedGeom & geom, const pllhip_op_t * ops, const int * kinds, const int * scales,
+                            unsigned int count, unsigned int lookups_max, bool tt_inside, AaListClasses & out);
+// The scaling certificate's bounds (ctx.hpp): a bound on every op's relative difference from the
+// reference's value -- its operands' bounds plus PLLHIP_CERT_OP_ERR when anything at or below it is a tip-inner op on
+// the matrix cores --, which ops therefore test, and the window they test with.  incoming: the bound an earlier call
+// left on each CLV (nullptr: none anywhere).  ti_mfma: tip-inner mat-vecs on the matrix cores are wanted; list_ti_mfma:
+// and had -- not by a list that overwrites an operand it read from an earlier call (it could not be run again), nor,
+// second attempt, when the bounds would outgrow the widest window.
+struct AaListCert
+{
+  std::vector<unsigned char> op_inexact; // per op: its scaling test also looks for the window
+  bool list_ti_mfma = false, too_wide = false;
+  int cert_kind = 0;                     // 0 nothing tests; 1 a trip runs the list again; 2 the bounds are inherited only
+  double window = 0.0;
+  std::vector<std::pair<unsigned int, double>> ext_marks, out_marks; // (CLV, bound): read from earlier calls, in the
+                                                                     // order first read; left by the list, by index
+};
+void pllhip_aa_list_cert(const FusedGeom & geom, const pllhip_op_t * ops, const int * cls, unsigned int count,
+                         const double * incoming, bool ti_mfma, AaListCert & out);
+// The list the kernel walks: every op but the tip-tip ops ahead of it, segmented (pllhip_fused_segments), ordered and
+// given slots by the planner (a lookup or a tip-tip op has no inner operand: "tip-tip" to the planner).
+struct AaListWalk
+{
+  std::vector<unsigned int> ahead;           // the tip-tip ops ahead of the list, grouped: without a scale buffer first
+  std::vector<int> orig;                     // walked op -> op of the caller's list
+  std::vector<FusedOp> plan;                 // the segments' plans one after the other; list_pos: the walked op
+  std::vector<unsigned int> seg_first, seg_n;
+  // The left block of op i is staged by the four waves, a part each, while they run op i - 2, and the barrier that
+  // tells a wave that everybody's part has landed is barrier A of op i - 1 -- which a lookup does not have.  An
+  // inner-inner op whose predecessor in its segment's cyclic walk is a lookup or a tip-tip op therefore begins with
+  // a barrier of its own (AF_SYNC_LEFT): without it, over runs of tens of barrier-free ops the waves drift apart by
+  // whole ops, and the op read its left block a few hundred cycles after the waves had last met.
+  std::vector<unsigned char> sync_left;      // per position of `plan`
+  unsigned int nsegs = 1, reloads = 0;
+};
+// Returns 0; 1 for a list of nothing but tip-tip ops ahead, or one the planner does not take; < 0 on error.
+int pllhip_aa_list_walk(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * cls,
+                        const int * scales, unsigned int count, unsigned int max_segments, unsigned int nslots,
+                        AaListWalk & out);
+// pllhip_aa_list_kinds' eight numbers: ops, tip-tip ahead of the list, tip-tip in the list, lookups, inner-inner on the
+// matrix cores, tip-inner on the matrix cores, tip-inner on the vector unit, operands reloaded
+void pllhip_aa_list_kinds_of(const int * cls, unsigned int count, bool list_ti_mfma, unsigned int reloads,
+                             unsigned int * out8);
 
 // encode and launch: one plan per segment
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,

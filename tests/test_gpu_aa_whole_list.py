@@ -68,9 +68,9 @@ def _evaluate(gpu, case, attrs, monkeypatch, fused, partial=True, ti_mfma="0"):
 @pytest.mark.parametrize("attrs", [ATTRIB_PATTERN_TIP, 0])
 @pytest.mark.parametrize("tt", [None, "1", "0"])
 def test_whole_list_equals_per_level_and_oracle(gpu, orc, monkeypatch, shape, tips, sites, attrs, tt):
-    """tt: where the list's tip-tip ops run -- None: ahead of the list when it is new, inside it when it comes again
-    (the partial traversals of _evaluate make the full list come once only); "1": always inside, as lookups over the
-    two tip tables; "0": always ahead.  (Without pattern tips there are no tip-tip ops: the switch must change nothing.)"""
+    """tt: where the list's tip-tip ops run (PLLHIP_AA_TT_INSIDE) -- None, the default since round 4, and "1": inside
+    the list, each one row of its pair table per site (two tip tables beyond the pool's budget); "0": ahead of it, as a
+    launch of their own.  (Without pattern tips there are no tip-tip ops: the switch must change nothing.)"""
     if tt is not None:
         monkeypatch.setenv("PLLHIP_AA_TT_INSIDE", tt)
     case = _case(gpu, shape, tips, sites)

@@ -12,10 +12,18 @@ PLLHIP_FUSED=2 (the whole-list kernels take small partitions):
     PLLHIP_FUSED_WGS unset / 2; PLLHIP_FUSED_SEGMENTS unset / 0; deferral on / off; the edge fold on / off -- the
     last two only where the switch is live (deferral: character rows, up to 4 categories, no per-rate scalers; the
     fold: up to 4 categories, no per-rate scalers), elsewhere off.
-  20 states, 4 categories: 12 tips x 500 sites; PLLHIP_AA_TT_INSIDE 0 / 1; segments unset / 0.
+  20 states, 4 categories (profiles/aa_list_steps_bits.txt): random 12 tips x 500 sites, caterpillar 12 x 40 (a
+    tip-inner chain, a tip-inner lookup), balanced 16 x 40 (lookups over two cherries), random 40 x 33 (operands
+    reloaded); tips as character rows or CLVs; scale buffers none / per site / per rate; PLLHIP_AA_TI_MFMA 0 / 1;
+    PLLHIP_AA_TT_INSIDE unset / 0 / 1; PLLHIP_AA_TT_PAIRS unset / 0; segments unset / 0; PLLHIP_AA_LOOKUP_MB unset /
+    0 / 3 (the protein map's 23 codes make a table set 1,518,080 B: 3 MB allow two lookups).
 Every case: the list (a full traversal directed at an inner edge), the edge lnL (which leaves the hint); the list
 again (planned anew where the hint is new), the lnL; the list again (relaunched), the lnL; the list with one op
-changed, the lnL.
+changed, the lnL.  20 states: then a partial traversal of the last three ops, whose operands carry the scaling
+certificate's marks of the call before; pll_amd_list_kinds after every list and the certificate's counters at the
+end are part of the digest.
+
+    python3 tools/plan_driver_gpu_bits.py <parent> <this> aa     the 20-state cases only (dna: the 4-state ones)
 """
 import hashlib
 import itertools
@@ -64,9 +72,14 @@ def _run_case(lib, W, H, case, attrs, use_scalers, deferral, fold):
     last["child1_matrix_index"], last["child2_matrix_index"] = int(last["child2_matrix_index"]), int(last["child1_matrix_index"])
     fi = [0] * case["rate_cats"]
     h = hashlib.sha256()
-    for lst in (ops, ops, ops, changed):
+    aa = case["states"] == 20
+    for lst in (ops, ops, ops, changed) + ((changed[-3:],) if aa else ()):
         p.update_partials(lst)
         h.update(struct.pack("<d", p.compute_edge_loglikelihood(*edge, fi)))
+        if aa:
+            h.update(repr(sorted(p.list_kinds().items())).encode())
+    if aa:
+        h.update(repr(sorted(p.scaling_certificate().items())).encode())
     for node in range(plan.tips, plan.tips + plan.clv_buffers):
         h.update(p.get_clv(node).tobytes())
     if use_scalers:
@@ -76,7 +89,7 @@ def _run_case(lib, W, H, case, attrs, use_scalers, deferral, fold):
     return h.hexdigest()
 
 
-def worker():
+def worker(which):
     import libpll_amd
     from libpll_amd import workload as W
     from libpll_amd.pllapi import ATTRIB_PATTERN_TIP, ATTRIB_RATE_SCALERS
@@ -84,7 +97,7 @@ def worker():
     lib = libpll_amd.load()
     assert lib.device_count() > 0, "no device"
     lib.lib.pll_amd_set_device(0)
-    trees = (("random", 17, 1000), ("balanced", 8, 21))
+    trees = (("random", 17, 1000), ("balanced", 8, 21)) if which != "aa" else ()
     for (shape, tips, sites), rc, scale, pt, wgs, segs, deferral, fold in itertools.product(
             trees, (1, 2, 4, 8), ("none", "site", "rate"), (1, 0), (None, "2"), (None, "0"), (True, False), (True, False)):
         live = rc <= 4 and scale != "rate"
@@ -99,23 +112,31 @@ def worker():
         print("dna %s-%dx%d rc%d scale-%s %s wgs-%s segs-%s defer-%d fold-%d %s" %
               (shape, tips, sites, rc, scale, "rows" if pt else "clvs", wgs or "x", segs or "x", deferral, fold, digest), flush=True)
     _setenv("PLLHIP_FUSED_WGS", None)
-    for inside, segs in itertools.product(("0", "1"), (None, "0")):
-        _setenv("PLLHIP_AA_TT_INSIDE", inside)
-        _setenv("PLLHIP_FUSED_SEGMENTS", segs)
-        case = H.make_case(20, "random", 12, 500, rate_cats=4, seed=5)
-        digest = _run_case(lib, W, H, case, ATTRIB_PATTERN_TIP, True, False, False)
-        print("aa random-12x500 rc4 tt-inside-%s segs-%s %s" % (inside, segs or "x", digest), flush=True)
+    trees = (("random", 12, 500), ("caterpillar", 12, 40), ("balanced", 16, 40), ("random", 40, 33)) if which != "dna" else ()
+    for (shape, tips, sites), pt, scale, ti, inside, pairs, segs, mb in itertools.product(
+            trees, (1, 0), ("none", "site", "rate"), ("0", "1"), (None, "0", "1"), (None, "0"), (None, "0"), (None, "0", "3")):
+        for name, value in (("PLLHIP_AA_TI_MFMA", ti), ("PLLHIP_AA_TT_INSIDE", inside), ("PLLHIP_AA_TT_PAIRS", pairs),
+                            ("PLLHIP_FUSED_SEGMENTS", segs), ("PLLHIP_AA_LOOKUP_MB", mb)):
+            _setenv(name, value)
+        case = H.make_case(20, shape, tips, sites, rate_cats=4, seed=5)
+        case["plan"] = H.TREES[shape](tips, seed=5, use_scalers=scale != "none")
+        attrs = (ATTRIB_PATTERN_TIP if pt else 0) | (ATTRIB_RATE_SCALERS if scale == "rate" else 0)
+        digest = _run_case(lib, W, H, case, attrs, scale != "none", False, False)
+        print("aa %s-%dx%d scale-%s %s ti-mfma-%s tt-inside-%s pairs-%s segs-%s lookup-mb-%s %s" %
+              (shape, tips, sites, scale, "rows" if pt else "clvs", ti, inside or "x", pairs or "x", segs or "x", mb or "x",
+               digest), flush=True)
 
 
 def main():
-    if len(sys.argv) == 2 and sys.argv[1] == "--worker":
-        return worker()
-    if len(sys.argv) != 3:
+    if len(sys.argv) == 3 and sys.argv[1] == "--worker":
+        return worker(sys.argv[2])
+    if len(sys.argv) not in (3, 4) or sys.argv[3:] not in ([], ["aa"], ["dna"]):
         sys.exit(__doc__)
+    which = (sys.argv[3:] + ["all"])[0]
     out = []
     for name, path in zip("AB", sys.argv[1:3]):
         env = dict(os.environ, PLL_AMD_LIB=os.path.abspath(path))
-        r = subprocess.run([sys.executable, __file__, "--worker"], env=env, capture_output=True, text=True, timeout=420)
+        r = subprocess.run([sys.executable, __file__, "--worker", which], env=env, capture_output=True, text=True, timeout=420)
         if r.returncode:
             sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
             sys.exit("library %s (%s) ended with status %d: nothing more is run" % (name, path, r.returncode))
