@@ -20,7 +20,7 @@ CFLAGS   := -std=gnu11 -O2 -fPIC -g -Wall -Wextra -ffp-contract=off -fvisibility
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -ffp-contract=off -fvisibility=hidden \
             -Wall -Iinclude -Ilibpll_amd/csrc/hip $(EXTRA_HIPFLAGS)
 
-.PHONY: lib oracle all clean asan
+.PHONY: lib oracle all clean asan asan-model-score
 lib: $(OUT)
 all: lib oracle
 
@@ -77,7 +77,17 @@ $(ASAN_DIR)/liboracle.so: $(wildcard oracle/*.c) oracle/oracle.h | $(ASAN_DIR)
 	gcc -std=c99 -fPIC -g -Wall -Wextra -ffp-contract=off -mfma -mavx2 -D_GNU_SOURCE $(ASAN_FLAGS) \
 	    -shared -Wl,-Bsymbolic -o $@ $(wildcard oracle/*.c) -lm
 
-asan: $(ASAN_DIR)/libpll_amd.so $(ASAN_DIR)/liboracle.so
+# pll_amd_model_loglikelihood's argument checks through a stand-alone program (its own main, no Python, no device):
+# the sanitized host objects linked with the ordinary HIP objects
+$(ASAN_DIR)/model_score_args: tools/model_score_args.c $(ASAN_OBJ) $(HIP_OBJ)
+	gcc $(filter-out -O2,$(CFLAGS)) $(ASAN_FLAGS) -c $< -o $(ASAN_DIR)/model_score_args.o
+	g++ $(ASAN_FLAGS) -Wl,-rpath,/opt/rocm/lib -o $@ $(ASAN_DIR)/model_score_args.o $(ASAN_OBJ) $(HIP_OBJ) \
+	    -L/opt/rocm/lib -lamdhip64 -lm -ldl
+
+asan-model-score: $(ASAN_DIR)/model_score_args
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/model_score_args
+
+asan: asan-model-score $(ASAN_DIR)/libpll_amd.so $(ASAN_DIR)/liboracle.so
 	LD_PRELOAD="$$(gcc -print-file-name=libasan.so) $$(gcc -print-file-name=libubsan.so)" \
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1:allocator_may_return_null=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
 	PLL_AMD_LIB=$(abspath $(ASAN_DIR)/libpll_amd.so) PLL_ORACLE_LIB=$(abspath $(ASAN_DIR)/liboracle.so) \

@@ -991,12 +991,60 @@ typedef struct pll_amd_tree_candidate
  * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
  * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
  * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: per-candidate model parameters or category
- * rates, per-site outputs, applying a candidate to the partition, and lists in which an op reads a CLV that a later op
+ * rates (pll_amd_model_loglikelihood below scores models on one tree), per-site outputs, applying a candidate to the partition, and lists in which an op reads a CLV that a later op
  * of the same candidate overwrites (they have a meaning in the sequence and no use here).  INTEGRATION.md section 4f. */
 PLL_EXPORT int pll_amd_tree_loglikelihood(pll_partition_t * partition,
                                           const pll_amd_tree_candidate_t * candidates, unsigned int count,
                                           const unsigned int * params_indices,
                                           double * lnl);            /* out [count] */
+
+/* ---- batched model scoring: candidate model parameters on a fixed tree (model_score.c, model_score.hip) ----
+ * A candidate is a set of model parameters: what a line search on the Gamma shape, or one finite-difference gradient
+ * over exchangeabilities, frequencies, +I and free category rates and weights, evaluates -- many of them, independent
+ * of each other, on one tree.  A field that is NULL (for the two arrays of pointers: also an entry that is NULL) means
+ * the partition's current value. */
+typedef struct pll_amd_model_candidate
+{
+  const double * const * subst_params;     /* [rate_matrices] pointers to states (states - 1) / 2 exchangeabilities */
+  const double * const * frequencies;      /* [rate_matrices] pointers to states frequencies */
+  const double *         prop_invar;       /* [rate_matrices] */
+  const double *         category_rates;   /* [rate_cats] */
+  const double *         category_weights; /* [rate_cats] */
+} pll_amd_model_candidate_t;
+
+/* lnl[m] = what this sequence returns on a copy of the partition -- for every rate-matrix set i that candidate m gives:
+ * pll_set_subst_params(i) / pll_set_frequencies(i), then pll_update_eigen(i);
+ * pll_update_invariant_sites_proportion(i, prop_invar[i]) where given; pll_set_category_rates /
+ * pll_set_category_weights where given; then the three calls that define pll_amd_tree_loglikelihood for `tree`:
+ * pll_update_prob_matrices(params_indices, its matrix_indices, branch_lengths, matrix_count),
+ * pll_update_partials(its operations, op_count), pll_compute_edge_loglikelihood(its edge, freqs_indices =
+ * params_indices).  A matrix the tree does not list is the partition's current matrix; a CLV its ops do not write is
+ * the partition's current CLV, MADE UNDER THE PARTITION'S OWN MODEL: for a whole-model evaluation the tree lists every
+ * matrix and computes every CLV from the tips.  A candidate's eigen systems are made by pll_amd_eigen_decompose, the
+ * routine behind pll_update_eigen, and its P-matrices by the arithmetic of pll_update_prob_matrices: they are the
+ * values the partition would hold.
+ * The call changes no CLV, scale buffer, P-matrix, eigen system, frequency, rate, weight, +I proportion, sumtable slot
+ * or host mirror -- but for the eigen systems of the partition's own sets that params_indices uses and that were
+ * waiting to be made (the lazy pll_update_eigen of pll_update_prob_matrices).  Candidates are independent: a
+ * candidate's value is the same bits whatever else is in the batch, in whatever order, however the call chunks it,
+ * and on a repeated call; a candidate with every field NULL has the bits of pll_amd_tree_loglikelihood(tree).  Large
+ * batches are worked in chunks of whole candidates of at most about PLL_AMD_MODEL_SCRATCH_MB (environment, read at
+ * call time, default 2048) of scratch, one candidate at least.  What lives where: as for pll_amd_tree_loglikelihood,
+ * with every candidate's P-matrices and model block in scratch.  The call is synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, lnl untouched): what pll_amd_tree_loglikelihood
+ * checks for the tree; count >= 1 and no NULL among tree, models, params_indices, lnl; exchangeabilities finite and
+ * non-negative; frequencies finite and positive; category rates and weights finite and non-negative; proportions in
+ * [0, 1); a positive proportion on a partition whose invariant sites were never computed (partition->invariant ==
+ * NULL: the sequence would compute them, which changes the partition -- call pll_update_invariant_sites first); a
+ * candidate whose eigen decomposition does not converge (the message names the candidate).
+ * Limits (PLL_ERROR_HIP_UNSUPPORTED) and PLL_ERROR_MEM_ALLOC: as for pll_amd_tree_loglikelihood.  Not offered:
+ * per-candidate trees in the same call, derivatives with respect to model parameters, applying a candidate to the
+ * partition, building Gamma rates from a shape (pll_compute_gamma_cats does).  INTEGRATION.md section 4g. */
+PLL_EXPORT int pll_amd_model_loglikelihood(pll_partition_t * partition,
+                                           const pll_amd_tree_candidate_t * tree,   /* ONE tree */
+                                           const pll_amd_model_candidate_t * models, unsigned int count,
+                                           const unsigned int * params_indices,
+                                           double * lnl);           /* out [count] */
 
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets

@@ -504,6 +504,24 @@ PLLHIP_EXPORT int pllhip_tree_loglikelihood(pllhip_ctx_t * ctx, const pllhip_tre
                                             unsigned int count, const unsigned int * h_params_indices, int route,
                                             int max_slots, size_t scratch_bytes, double * h_lnl);
 
+/* ---- batched model scoring (model_score.hip; host side host/model_score.c) ----
+ * `count` candidate models on ONE tree (a pllhip_tree_candidate_t): lnl[m] = what pllhip_tree_loglikelihood would
+ * return for the tree after model m was put into the context (pllhip_put_model for every rate matrix,
+ * pllhip_put_rates) -- and nothing of the context changes, its model included.  A model is a packed block of
+ * block_doubles doubles, the blocks back to back in h_blocks; for S states, M rate matrices and R rate categories:
+ *   [M][S] eigenvalues, [M][S*S] eigenvectors, [M][S*S] inverse eigenvectors, [M][S] frequencies, [M] +I proportions,
+ *   [R] category rates, [R] category weights, padded to an even number of doubles
+ * (every entry filled: what a candidate leaves as it is comes from the caller).  The matrices of every (model, listed
+ * branch) are made in one launch per chunk by the arithmetic of pllhip_update_pmatrices; the tree is planned once; the
+ * routes, route, max_slots and the return codes are pllhip_tree_loglikelihood's.  A CLV the tree's ops do not write is
+ * the context's, made under the context's own model.  -1 also for a block size other than the shape's, a proportion
+ * outside [0, 1) or positive on a context without an invariant index (pllhip_put_invariant), a negative or non-finite
+ * category rate or weight. */
+PLLHIP_EXPORT int pllhip_model_loglikelihood(pllhip_ctx_t * ctx, const pllhip_tree_candidate_t * h_tree,
+                                             const double * h_blocks, size_t block_doubles, unsigned int count,
+                                             const unsigned int * h_params_indices, int route, int max_slots,
+                                             size_t scratch_bytes, double * h_lnl);
+
 /* The planner of k_tree_score on its own -- host logic, no device needed.  The ops the edge (parent_clv, child_clv
  * with their scaler indices) does not depend on are dropped; the rest are ordered depth-first from the edge, the
  * operand that needs more live values first, and a parent takes the slot of one of its operands.  Tips (pattern_tip)

@@ -161,15 +161,22 @@ struct BatchEdgeArgs
   double * __restrict__ partial;
   unsigned int sites, states, rate_cats, tiles;
   int rate_scalers;
+  BatchModelBlocks mb; // (MODEL only)
 };
 
 // the edge log-likelihood of every descriptor: k_lnl_gen's arithmetic (likelihood.hip), one lane per site, per (tile,
-// descriptor); the tile's sum: wave trees, then the four waves in order
+// descriptor); the tile's sum: wave trees, then the four waves in order.  MODEL: frequencies, +I proportions and
+// category weights are those of the descriptor's model block
+template <bool MODEL>
 __global__ __launch_bounds__(PLLHIP_BATCH_TILE) void k_batch_edge_lnl(BatchEdgeArgs a)
 {
   const unsigned int S = a.states, R = a.rate_cats;
   const unsigned int tile = blockIdx.x;
   const BatchEdge & e = a.edges[blockIdx.y];
+  const double * __restrict__ blk = MODEL ? a.mb.p + (size_t)e.model * a.mb.stride : nullptr;
+  const double * __restrict__ freqs = MODEL ? blk + a.mb.freqs : a.m.freqs;
+  const double * __restrict__ prop_invar = MODEL ? blk + a.mb.pinv : a.m.prop_invar;
+  const double * __restrict__ rate_weights = MODEL ? blk + a.mb.weights : a.m.rate_weights;
   const size_t n = (size_t)tile * PLLHIP_BATCH_TILE + threadIdx.x;
   double lk = 0.0;
   if (n < a.sites)
@@ -209,7 +216,7 @@ __global__ __launch_bounds__(PLLHIP_BATCH_TILE) void k_batch_edge_lnl(BatchEdgeA
     for (unsigned int k = 0; k < R; ++k)
     {
       const unsigned int fi = a.m.params[k];
-      const double * fr = a.m.freqs + (size_t)fi * S;
+      const double * fr = freqs + (size_t)fi * S;
       const double * pc = e.pclv + (n * R + k) * S;
       const double * cc = e.cclv ? e.cclv + (n * R + k) * S : nullptr;
       const double * m = e.pmat + (size_t)k * S * S;
@@ -225,8 +232,8 @@ __global__ __launch_bounds__(PLLHIP_BATCH_TILE) void k_batch_edge_lnl(BatchEdgeA
         terma_r += pc[j] * fr[j] * termb; // core_likelihood.c:955
       }
       if (rs[k] > 0) terma_r *= scale_minlh(rs[k]);
-      const double pinv = a.m.prop_invar[fi];
-      const double w = a.m.rate_weights[k];
+      const double pinv = prop_invar[fi];
+      const double w = rate_weights[k];
       if (pinv > 0.0)
       {
         const int inv = a.m.invariant ? a.m.invariant[n] : -1;
@@ -245,7 +252,7 @@ __global__ __launch_bounds__(PLLHIP_BATCH_TILE) void k_batch_edge_lnl(BatchEdgeA
 }
 
 int pllhip_batch_edge_lnl(pllhip_ctx * c, const BatchEdge * d_edges, unsigned int n, const unsigned int * params,
-                          double * partial, unsigned int tiles)
+                          double * partial, unsigned int tiles, const BatchModelBlocks * blocks)
 {
   BatchEdgeArgs g;
   memset(&g, 0, sizeof(g));
@@ -258,7 +265,15 @@ int pllhip_batch_edge_lnl(pllhip_ctx * c, const BatchEdge * d_edges, unsigned in
   g.rate_cats = c->sh.rate_cats;
   g.tiles = tiles;
   g.rate_scalers = (c->sh.scale_buffers > 0 && c->sh.rate_scalers) ? 1 : 0;
-  k_batch_edge_lnl<<<dim3(tiles, n), PLLHIP_BATCH_TILE, 0, c->stream>>>(g);
+  if (blocks)
+  {
+    g.mb = *blocks;
+    // (a candidate's proportion may be positive where none of the partition's is)
+    g.m.invariant = c->invariant;
+    k_batch_edge_lnl<true><<<dim3(tiles, n), PLLHIP_BATCH_TILE, 0, c->stream>>>(g);
+  }
+  else
+    k_batch_edge_lnl<false><<<dim3(tiles, n), PLLHIP_BATCH_TILE, 0, c->stream>>>(g);
   HIP_TRY(hipGetLastError());
   return 0;
 }

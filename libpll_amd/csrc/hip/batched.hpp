@@ -1,5 +1,5 @@
 // batched.hpp -- internal: the device plumbing the batched calls share (insertion.hip, branch_opt.hip, posteriors.hip,
-// nni.hip, tree_score.hip; the code is in batched.hip).  A new batched call starts from these pieces:
+// nni.hip, tree_score.hip, model_score.hip; the code is in batched.hip).  A new batched call starts from these pieces:
 //
 //   opening   pllhip_batch_open: the checks every batched call begins with;
 //   scratch   one BatchScratch per call family in the context (ctx.hpp), grown by pllhip_batch_scratch_grow and laid
@@ -7,6 +7,7 @@
 //   ops       BatchOp lists -- CLV ops (pllhip_batch_fill_op) and sumtable ops (pllhip_batch_fill_sumtable) -- run by
 //             the partition's own CLV kernels (pllhip_batch_run_ops);
 //   model     BatchModel: the model block of a batched kernel's arguments (pllhip_batch_model fills it);
+//             BatchModelBlocks: per-item models of a call that scores models, packed as BatchModelLayout says;
 //   sums      per (PLLHIP_BATCH_TILE-site tile, item) partial sums in a fixed order (batch_wave_sum, batch_waves_sum,
 //             batch_tile_sum), added per item in tile order (pllhip_batch_reduce);
 //   edge lnL  k_batch_edge_lnl: the log-likelihood at one edge per item, any shape (pllhip_batch_edge_lnl).
@@ -91,6 +92,35 @@ struct BatchModel
   unsigned int params[PLLHIP_MAX_RATE_CATS];
 };
 void pllhip_batch_model(const pllhip_ctx * c, const unsigned int * params, BatchModel & m);
+// Model blocks: a batched call whose items carry models of their own (model_score.hip) keeps one packed block of
+// doubles per item in scratch, in the layout of pllhip_model_loglikelihood (pllhip.h).  A kernel's model variant
+// takes an item's frequencies, +I proportions and category weights from its block instead of BatchModel's arrays
+// (pattern weights, the invariant index and params stay BatchModel's).  p == nullptr: no blocks, the plain variant.
+struct BatchModelBlocks
+{
+  const double * __restrict__ p;
+  unsigned int stride;                  // doubles from one item's block to the next
+  unsigned int freqs, pinv, weights;    // where [rate_matrices][states], [rate_matrices] and [rate_cats] begin
+};
+// the layout for the context's shape: the offsets of every piece and the doubles of a block (an even number)
+struct BatchModelLayout
+{
+  unsigned int eigenvals, eigenvecs, inv_eigenvecs, freqs, pinv, rates, weights, doubles;
+};
+static inline BatchModelLayout pllhip_batch_model_layout(const pllhip_ctx * c)
+{
+  const unsigned int S = c->sh.states, M = c->sh.rate_matrices, R = c->sh.rate_cats;
+  BatchModelLayout l;
+  l.eigenvals = 0;
+  l.eigenvecs = M * S;
+  l.inv_eigenvecs = l.eigenvecs + M * S * S;
+  l.freqs = l.inv_eigenvecs + M * S * S;
+  l.pinv = l.freqs + M * S;
+  l.rates = l.pinv + M;
+  l.weights = l.rates + R;
+  l.doubles = (l.weights + R + 1u) & ~1u;
+  return l;
+}
 
 // ---- sums
 // the wave's sum of v, in lane 0: a tree of __shfl_down
@@ -123,8 +153,10 @@ struct BatchEdge
   const unsigned char * ctip;
   const unsigned int * pscal, * cscal;
   const double * pmat;
-  unsigned int out, pad;       // the item: its tile sums go to partial[out][tiles]
+  unsigned int out, model;     // the item: its tile sums go to partial[out][tiles]; its model block, where the
+                               // call has blocks (otherwise not read)
 };
-// k_batch_edge_lnl over n descriptors (device) x tiles; the caller brackets it with a pllhip_prof_scope if it counts
+// k_batch_edge_lnl over n descriptors (device) x tiles; the caller brackets it with a pllhip_prof_scope if it counts.
+// blocks: the model variant -- descriptor i takes the model of block d_edges[i].model
 int pllhip_batch_edge_lnl(pllhip_ctx * c, const BatchEdge * d_edges, unsigned int n, const unsigned int * params,
-                          double * partial, unsigned int tiles);
+                          double * partial, unsigned int tiles, const BatchModelBlocks * blocks = nullptr);

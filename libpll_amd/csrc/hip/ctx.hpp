@@ -21,6 +21,7 @@ struct pllhip_rep_work;
 // scratch of a batched call (batched.hpp): insertion -- P-matrices, insertion vectors, query vectors, partial sums;
 // branch lengths -- sumtables, Newton states, partial sums; posteriors -- edge descriptors and outputs; NNI and tree
 // scoring -- P-matrices, descriptors, partial sums and, where a route needs them, candidate CLVs, scale buffers, sumtables
+// (model scoring shares tree scoring's: the same pieces, plus a model block per item and the tree's lengths)
 struct BatchScratch
 {
   void * p = nullptr;

@@ -10,6 +10,7 @@
 // Traffic is a few KB per branch: launch-latency bound, not HBM bound.
 #include "ctx.hpp"
 #include "numerics.hpp"
+#include "pmatrix_entry.hpp"
 
 #define PMAT_INLINE 256
 
@@ -46,66 +47,8 @@ __global__ __launch_bounds__(256) void k_update_pmatrix(PmatArgs a)
   const bool inl = a.matrix_indices == nullptr;
   const double t = inl ? a.bl_inline[b] : a.branch_lengths[b];
   double * const pm = a.pmatrix + (size_t)(inl ? a.mi_inline[b] : a.matrix_indices[b]) * R * S * S;
-
-  if (t == 0.0)
-  {
-    // zero-length branch: exact identity (core_pmatrix.c:174-179)
-    for (unsigned int e = e_lo * S * S + threadIdx.x; e < (e_lo + e_n) * S * S; e += blockDim.x)
-    {
-      const unsigned int j = (e / S) % S, k = e % S;
-      pm[e] = (j == k) ? 1.0 : 0.0;
-    }
-    return;
-  }
-
-  for (unsigned int e = e_lo * S + threadIdx.x; e < (e_lo + e_n) * S; e += blockDim.x)
-  {
-    const unsigned int n = e / S, m = e % S;
-    const unsigned int pi = a.params_indices[n];
-    const double pinv = a.prop_invar[pi];
-    // ((lambda * rate) * t) [/ (1 - pinv)]: core_pmatrix_avx.c:117-130
-    double arg = (a.eigenvals[pi * S + m] * a.rates[n]) * t;
-    if (pinv > 1e-8) arg = arg / (1.0 - pinv);
-    s_expd[e] = pll_expm1(arg);
-  }
-  __syncthreads();
-
-  for (unsigned int e = e_lo * S * S + threadIdx.x; e < (e_lo + e_n) * S * S; e += blockDim.x)
-  {
-    const unsigned int n = e / (S * S), j = (e / S) % S, k = e % S;
-    const unsigned int pi = a.params_indices[n];
-    const double * __restrict__ inv = a.inv_eigenvecs + (size_t)pi * S * S + j * S;
-    const double * __restrict__ vec = a.eigenvecs + (size_t)pi * S * S + k;
-    const double * __restrict__ ex = s_expd + n * S;
-    double p;
-    if (S == 4)
-    {
-      // core_pmatrix_avx.c:200-222: four products, pairwise tree, then + I
-      p = pairsum4((inv[0] * ex[0]) * vec[0], (inv[1] * ex[1]) * vec[4],
-                   (inv[2] * ex[2]) * vec[8], (inv[3] * ex[3]) * vec[12]);
-      p = p + ((j == k) ? 1.0 : 0.0);
-    }
-    else if (S == 20)
-    {
-      // core_pmatrix_avx2.c:24-37 (ONESTEP) and :236-271: accumulators strided
-      // by m mod 4, first step a product, the rest fused, pairwise tree, + 1 on
-      // the diagonal
-      double acc[4];
-      for (unsigned int l = 0; l < 4; ++l) acc[l] = (inv[l] * ex[l]) * vec[l * S];
-      for (unsigned int m = 4; m < 20; m += 4)
-        for (unsigned int l = 0; l < 4; ++l)
-          acc[l] = fma(inv[m + l] * ex[m + l], vec[(m + l) * S], acc[l]);
-      p = pairsum4(acc[0], acc[1], acc[2], acc[3]);
-      if (j == k) p += 1.0;
-    }
-    else
-    {
-      // core_pmatrix.c:226-237: start from I, accumulate left to right
-      p = (j == k) ? 1.0 : 0.0;
-      for (unsigned int m = 0; m < S; ++m) p += (inv[m] * ex[m]) * vec[m * S];
-    }
-    pm[e] = p;
-  }
+  pmat_branch(pm, t, a.eigenvals, a.eigenvecs, a.inv_eigenvecs, a.prop_invar, a.rates, a.params_indices, S, e_lo, e_n,
+              s_expd);
 }
 
 // matrices into `dst` (room for `slots` of them): the partition's own array, or scratch of the insertion calls

@@ -22,10 +22,14 @@
 //                 k_lnl_gen's arithmetic per (tile, candidate));
 //   reduction     k_batch_reduce (batched.hip) adds a candidate's tile sums in tile order.
 //
+// The same driver scores many MODELS on one tree (pllhip_tree_score_run with models; model_score.hip): the tree is
+// planned once, every item has its own matrices, records and model block, and the kernel's and the edge kernel's
+// model variants take the edge term's frequencies, weights and +I proportions from the item's block.
+//
 // Determinism: tiles are PLLHIP_BATCH_TILE sites fixed by the site count; a candidate's plan, records and partial sums
 // depend on the candidate alone, every sum runs in a fixed order.  A candidate's value does not depend on the batch, its order or
 // the chunking.  No atomics, no barrier inside the walk, no traffic between waves.
-#include "batched.hpp"
+#include "tree_score.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -304,7 +308,7 @@ struct TsMats
 struct TsCand
 {
   TsSide p, c;
-  unsigned int first, nops, out, pad;
+  unsigned int first, nops, out, model; // (model: the item's model block, where the call has blocks)
 };
 
 struct TsArgs
@@ -314,6 +318,7 @@ struct TsArgs
   BatchModel m;
   double * __restrict__ partial;      // [chunk's candidates][tiles]
   unsigned int sites, tiles, nslots;
+  BatchModelBlocks mb; // (MODEL only)
 };
 
 // A record is the same for every lane: read through the constant address space it is loaded by the scalar unit into
@@ -440,7 +445,10 @@ __device__ __forceinline__ void ts_product(const TsSide & s, const char * mrow, 
 // One lane per (site, rate) row, the R lanes of a site neighbours.  A wave takes its 64 sites in R rounds of 64 / R
 // whole sites and walks the candidate's records once per round; the slots and the matrix staging area are the wave's
 // own, and a lane reads and writes its own 36 bytes of a slot only.
-template <int R>
+// MODEL: the edge term's frequencies, category weights and +I proportions are those of the candidate's model block
+// (pllhip_tree_score_run with models).  They are the same for every lane: read through the constant address space, as
+// the records are, every category's values arrive in scalar registers and a lane keeps its own category's.
+template <int R, bool MODEL>
 __global__ __launch_bounds__(256) void k_tree_score(TsArgs a)
 {
   extern __shared__ __attribute__((aligned(16))) char ts_lds[];
@@ -453,11 +461,41 @@ __global__ __launch_bounds__(256) void k_tree_score(TsArgs a)
   char * wbase = ts_lds + TS_HEAD_BYTES + 4u * TS_STAGE_BYTES + (size_t)wave * a.nslots * TS_SLOT_BYTES;
   const unsigned int g = lane / R, k = lane - g * R, grp0 = g * R;
   const char * lrow = stage + k * TS_STAGE_ROW, * rrow = stage + (R + k) * TS_STAGE_ROW;
-  const unsigned int pi = a.m.params[k];
-  const double pinv = a.m.prop_invar[pi];
-  const double wk = a.m.rate_weights[k];
-  const double * __restrict__ frk = a.m.freqs + (size_t)pi * 4u;
-  const double fr[4] = {frk[0], frk[1], frk[2], frk[3]};
+  double pinv, wk, fr[4];
+  if constexpr (MODEL)
+  {
+    typedef const double __attribute__((address_space(4))) * ts_cd;
+    const ts_cd blk = (ts_cd)(uintptr_t)(a.mb.p + (size_t)cd.model * a.mb.stride);
+    pinv = wk = fr[0] = fr[1] = fr[2] = fr[3] = 0.0;
+#pragma unroll
+    for (unsigned int q = 0; q < (unsigned int)R; ++q)
+    {
+      const unsigned int pq = a.m.params[q];
+      const double pv = blk[a.mb.pinv + pq], wq = blk[a.mb.weights + q];
+      const double f0 = blk[a.mb.freqs + pq * 4u], f1 = blk[a.mb.freqs + pq * 4u + 1u];
+      const double f2 = blk[a.mb.freqs + pq * 4u + 2u], f3 = blk[a.mb.freqs + pq * 4u + 3u];
+      if (k == q)
+      {
+        pinv = pv;
+        wk = wq;
+        fr[0] = f0;
+        fr[1] = f1;
+        fr[2] = f2;
+        fr[3] = f3;
+      }
+    }
+  }
+  else
+  {
+    const unsigned int pi = a.m.params[k];
+    const double * __restrict__ frk = a.m.freqs + (size_t)pi * 4u;
+    pinv = a.m.prop_invar[pi];
+    wk = a.m.rate_weights[k];
+    fr[0] = frk[0];
+    fr[1] = frk[1];
+    fr[2] = frk[2];
+    fr[3] = frk[3];
+  }
   const size_t first = (size_t)tile * PLLHIP_BATCH_TILE;
   const size_t end = std::min<size_t>(first + PLLHIP_BATCH_TILE, a.sites);
   const size_t sbase = first + (size_t)wave * 64u;
@@ -583,14 +621,15 @@ __global__ __launch_bounds__(256) void k_tree_score(TsArgs a)
 
 // ------------------------------------------------------------------------------------------------ the call
 
-// route: -1 the library's choice, 0 the general route, 1 the kernel where it covers the candidate
-extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_candidate_t * C, unsigned int count,
-                                         const unsigned int * params, int route, int max_slots, size_t budget,
-                                         double * h_lnl)
+// route: -1 the library's choice, 0 the general route, 1 the kernel where it covers the candidate.
+// models (tree_score.hpp): the items are the models, every one on the tree C[0] -- one plan, every item its own
+// matrices (pllhip_model_pmatrices), records and model block
+int pllhip_tree_score_run(pllhip_ctx * c, const char * what, const pllhip_tree_candidate_t * C, unsigned int count,
+                          const unsigned int * params, int route, int max_slots, size_t budget, double * h_lnl,
+                          const TsModels * models)
 {
   pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
-  const char * what = "pllhip_tree_loglikelihood";
-  if (!C || !params || !count || !h_lnl)
+  if (!C || !params || !count || !h_lnl || (models && (count != 1 || !models->count || !models->h_blocks)))
   {
     pllhip_set_error("%s: empty batch or NULL array", what);
     return -1;
@@ -599,6 +638,9 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
   if (rc) return rc;
   const unsigned int nodes = (unsigned int)c->clv.size();
   const unsigned int S = c->sh.states, R = c->sh.rate_cats;
+  const unsigned int items = models ? models->count : count;
+  auto tree_of = [&](unsigned int item) { return models ? 0u : item; };
+  const BatchModelLayout ml = pllhip_batch_model_layout(c);
   const TsGeom geom = {c->sh.tips, nodes, c->sh.scale_buffers, c->sh.pattern_tip != 0};
   const bool scaled = c->sh.scale_buffers > 0;
   const bool covers = S == 4 && (R == 1 || R == 4) && !(scaled && c->sh.rate_scalers);
@@ -683,10 +725,12 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
   const unsigned int tiles = pllhip_batch_tiles(c);
   const size_t clv_b = c->clv_stride * 8, sc_b = scaled ? c->scaler_stride * 4 : 0;
   // what a candidate takes of a chunk's scratch
-  auto bytes_of = [&](unsigned int i) -> size_t {
+  auto bytes_of = [&](unsigned int item) -> size_t {
+    const unsigned int i = tree_of(item);
     const size_t nk = plans[i].order.size();
     size_t b = (size_t)C[i].matrix_count * c->pmat_elems * 8 + (size_t)tiles * 8 + 8 + 512;
     b += by_kernel[i] ? nk * sizeof(TsOp) + sizeof(TsCand) : nk * (clv_b + sc_b + 512) + sizeof(BatchEdge);
+    if (models) b += (size_t)ml.doubles * 8;
     return b;
   };
 
@@ -701,18 +745,19 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
   std::vector<unsigned int> level_of; // per op of gen: its dependency level
   std::vector<double> hout;
 
-  for (unsigned int c0 = 0; c0 < count;)
+  const size_t len_b = models ? (size_t)C[0].matrix_count * 8 : 0; // (the tree's lengths: once per chunk)
+  for (unsigned int c0 = 0; c0 < items;)
   {
     // ---- the chunk: whole candidates within `budget` bytes, one at least
     unsigned int cn = 0;
-    size_t used = 8192, nmat = 0, nrec = 0, nkc = 0, ngc = 0, ngen = 0;
+    size_t used = 8192 + pllhip_batch_align(len_b), nmat = 0, nrec = 0, nkc = 0, ngc = 0, ngen = 0;
     unsigned int chunk_slots = 1;
-    while (c0 + cn < count && cn < 65535u)
+    while (c0 + cn < items && cn < 65535u)
     {
       const size_t b = bytes_of(c0 + cn);
       if (cn && used + b > budget) break;
       used += b;
-      const unsigned int i = c0 + cn;
+      const unsigned int i = tree_of(c0 + cn);
       nmat += C[i].matrix_count;
       if (by_kernel[i])
       {
@@ -735,6 +780,8 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
     const size_t o_edge = L.take(ngc * sizeof(BatchEdge));
     const size_t o_part = L.take((size_t)cn * tiles * 8);
     const size_t o_out = L.take((size_t)cn * 8);
+    const size_t o_blk = L.take(models ? (size_t)cn * ml.doubles * 8 : 0);
+    const size_t o_len = L.take(len_b);
     const size_t o_zero = L.off; // from here: zeroed on every chunk (the slack behind every scratch CLV reads as zeros)
     const size_t o_clv = L.take(ngen * clv_b);
     const size_t o_scal = L.take(ngen * sc_b);
@@ -750,18 +797,36 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
     double * d_out = (double *)(base + o_out);
     double * d_clv = (double *)(base + o_clv);
     unsigned int * d_scal = (unsigned int *)(base + o_scal);
+    const BatchModelBlocks mb = {(const double *)(base + o_blk), ml.doubles, ml.freqs, ml.pinv, ml.weights};
 
     // ---- the candidates' own matrices
-    mi.clear();
-    bl.clear();
-    for (unsigned int j = 0; j < cn; ++j)
-      for (unsigned int m = 0; m < C[c0 + j].matrix_count; ++m)
+    if (models)
+    {
+      // the chunk's model blocks and the tree's lengths go up; every (item, listed matrix) in one launch
+      HIP_TRY(hipMemcpyAsync(base + o_blk, models->h_blocks + (size_t)c0 * ml.doubles, (size_t)cn * ml.doubles * 8,
+                             hipMemcpyHostToDevice, c->stream));
+      if (len_b)
       {
-        mi.push_back((unsigned int)mi.size());
-        bl.push_back(C[c0 + j].branch_lengths[m]);
+        HIP_TRY(hipMemcpyAsync(base + o_len, C[0].branch_lengths, len_b, hipMemcpyHostToDevice, c->stream));
+        if ((rc = pllhip_model_pmatrices(c, d_pm, mb.p, ml, (const double *)(base + o_len), C[0].matrix_count, cn,
+                                         params)))
+          return rc;
       }
-    if (nmat && (rc = pllhip_pmatrices_to(c, d_pm, (unsigned int)nmat, params, mi.data(), bl.data(), (unsigned int)nmat)))
-      return rc;
+    }
+    else
+    {
+      mi.clear();
+      bl.clear();
+      for (unsigned int j = 0; j < cn; ++j)
+        for (unsigned int m = 0; m < C[c0 + j].matrix_count; ++m)
+        {
+          mi.push_back((unsigned int)mi.size());
+          bl.push_back(C[c0 + j].branch_lengths[m]);
+        }
+      if (nmat &&
+          (rc = pllhip_pmatrices_to(c, d_pm, (unsigned int)nmat, params, mi.data(), bl.data(), (unsigned int)nmat)))
+        return rc;
+    }
 
     // ---- records and descriptors
     h_ops.clear();
@@ -773,14 +838,14 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
     unsigned int max_level = 0;
     for (unsigned int j = 0; j < cn; ++j)
     {
-      const pllhip_tree_candidate_t & cd = C[c0 + j];
-      const TsPlan & pl = plans[c0 + j];
+      const pllhip_tree_candidate_t & cd = C[tree_of(c0 + j)];
+      const TsPlan & pl = plans[tree_of(c0 + j)];
       // (a matrix listed twice: the later length, as in the sequence)
       for (unsigned int m = 0; m < cd.matrix_count; ++m) matmap[cd.matrix_indices[m]] = (int)(mat0 + m);
       auto mat = [&](unsigned int m) -> const double * {
         return matmap[m] >= 0 ? d_pm + (size_t)matmap[m] * c->pmat_elems : pllhip_pmat_ptr(c, m);
       };
-      if (by_kernel[c0 + j])
+      if (by_kernel[tree_of(c0 + j)])
       {
         auto side = [&](unsigned int clv, int sc, unsigned int m, int slot) {
           TsSide s;
@@ -801,6 +866,7 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
         hc.first = (unsigned int)h_ops.size();
         hc.nops = (unsigned int)pl.order.size();
         hc.out = j;
+        hc.model = j;
         hc.p = side(cd.parent_clv_index, cd.parent_scaler_index, cd.matrix_index, pl.pslot);
         hc.c = side(cd.child_clv_index, cd.child_scaler_index, cd.matrix_index, pl.cslot);
         h_cands.push_back(hc);
@@ -866,6 +932,7 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
                                        : sc_at[cs] >= 0 ? d_scal + (size_t)sc_at[cs] * c->scaler_stride : pllhip_scaler_ptr(c, cs);
         he.pmat = mat(cd.matrix_index);
         he.out = j;
+        he.model = j;
         h_edges.push_back(he);
         for (unsigned int o : pl.order)
         {
@@ -891,15 +958,20 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
       q.sites = (unsigned int)sites;
       q.tiles = tiles;
       q.nslots = chunk_slots;
+      if (models)
+      {
+        q.mb = mb;
+        q.m.invariant = c->invariant; // (a candidate's proportion may be positive where none of the partition's is)
+      }
       const size_t lds = TS_HEAD_BYTES + 4u * TS_STAGE_BYTES + (size_t)chunk_slots * 4u * TS_SLOT_BYTES;
       const dim3 grid(tiles, (unsigned int)nkc);
+      void (*const kernel)(TsArgs) = models ? (R == 4 ? &k_tree_score<4, true> : &k_tree_score<1, true>)
+                                            : (R == 4 ? &k_tree_score<4, false> : &k_tree_score<1, false>);
       if (lds > 65536)
-        HIP_TRY(hipFuncSetAttribute(R == 4 ? reinterpret_cast<const void *>(&k_tree_score<4>)
-                                           : reinterpret_cast<const void *>(&k_tree_score<1>),
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       pllhip_prof_scope prof(c, PLLHIP_PROF_LNL);
-      if (R == 4) k_tree_score<4><<<grid, 256, lds, c->stream>>>(q);
-      else k_tree_score<1><<<grid, 256, lds, c->stream>>>(q);
+      kernel<<<grid, 256, lds, c->stream>>>(q);
       HIP_TRY(hipGetLastError());
     }
     if (ngc)
@@ -913,7 +985,8 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
       }
       HIP_TRY(hipMemcpyAsync(d_edges, h_edges.data(), ngc * sizeof(BatchEdge), hipMemcpyHostToDevice, c->stream));
       pllhip_prof_scope prof(c, PLLHIP_PROF_LNL);
-      if ((rc = pllhip_batch_edge_lnl(c, d_edges, (unsigned int)ngc, params, d_part, tiles))) return rc;
+      if ((rc = pllhip_batch_edge_lnl(c, d_edges, (unsigned int)ngc, params, d_part, tiles, models ? &mb : nullptr)))
+        return rc;
     }
     if ((rc = pllhip_batch_reduce(c, d_part, d_out, cn, tiles))) return rc;
     hout.resize(cn);
@@ -923,4 +996,12 @@ extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_can
     c0 += cn;
   }
   return 0;
+}
+
+extern "C" int pllhip_tree_loglikelihood(pllhip_ctx_t * c, const pllhip_tree_candidate_t * C, unsigned int count,
+                                         const unsigned int * params, int route, int max_slots, size_t budget,
+                                         double * h_lnl)
+{
+  return pllhip_tree_score_run(c, "pllhip_tree_loglikelihood", C, count, params, route, max_slots, budget, h_lnl,
+                               nullptr);
 }

@@ -98,6 +98,25 @@ int pll_amd_flush_model(pll_partition_t * partition);
 
 extern int pll_amd_mirror_mode;
 
+/* tree_score.c: the argument check of one candidate tree, shared with model_score.c.  clv_writer / sc_writer:
+ * [tips + clv_buffers] / [scale_buffers] entries of -1, left so.  Sets PLL_ERROR_PARAM_INVALID on failure. */
+int pll_amd_check_tree_candidate(const pll_partition_t * p, const pll_amd_tree_candidate_t * cd, unsigned int i,
+                                 int * clv_writer, int * sc_writer);
+/* ... and the whole of it for `count` candidates with their params indices (allocates the tables) */
+int pll_amd_check_tree_candidates(const pll_partition_t * p, const char * what,
+                                  const pll_amd_tree_candidate_t * candidates, unsigned int count,
+                                  const unsigned int * params_indices);
+/* PLL_ERROR_HIP_UNSUPPORTED for the partition kinds the tree- and model-scoring calls refuse on the host side */
+int pll_amd_tree_score_supported(const pll_partition_t * p, const char * what);
+/* the developer's switches PLLHIP_TREE_SCORE_ROUTE / PLLHIP_TREE_SCORE_SLOTS through the device layer's gate */
+void pll_amd_tree_score_switches(int * route, int * slots);
+/* model_score.c: the values of `count` candidate models (host logic: reads the partition's shape and whether it has
+ * an invariant index, nothing of the device).  Sets PLL_ERROR_PARAM_INVALID on failure. */
+int pll_amd_check_model_candidates(const pll_partition_t * p, const pll_amd_model_candidate_t * models,
+                                   unsigned int count);
+/* a device-layer return code of these calls as pll_errno; returns PLL_SUCCESS for 0 */
+int pll_amd_tree_score_result(int rc, const char * what);
+
 /* repeats.c */
 int pll_amd_repeats_alloc(pll_amd_partition_t * q);
 void pll_amd_repeats_free(pll_amd_partition_t * q);

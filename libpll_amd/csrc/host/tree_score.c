@@ -34,8 +34,8 @@ static int fail(const char * fmt, unsigned int a, unsigned int b)
 }
 
 /* one candidate: indices, lengths, and what its ops write and read */
-static int check_candidate(const pll_partition_t * p, const pll_amd_tree_candidate_t * cd, unsigned int i,
-                           int * clv_writer, int * sc_writer)
+int pll_amd_check_tree_candidate(const pll_partition_t * p, const pll_amd_tree_candidate_t * cd, unsigned int i,
+                                 int * clv_writer, int * sc_writer)
 {
   const unsigned int nodes = p->tips + p->clv_buffers;
   unsigned int o, m;
@@ -90,6 +90,66 @@ static int check_candidate(const pll_partition_t * p, const pll_amd_tree_candida
   return ok;
 }
 
+int pll_amd_check_tree_candidates(const pll_partition_t * p, const char * what,
+                                  const pll_amd_tree_candidate_t * candidates, unsigned int count,
+                                  const unsigned int * params_indices)
+{
+  const size_t nodes = (size_t)p->tips + p->clv_buffers, n = nodes + p->scale_buffers;
+  size_t k;
+  unsigned int i;
+  int rc = PLL_SUCCESS, * writers;
+  for (i = 0; i < p->rate_cats; ++i)
+    if (params_indices[i] >= p->rate_matrices)
+    {
+      pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "params index %u out of range", params_indices[i]);
+      return PLL_FAILURE;
+    }
+  writers = (int *)malloc((n ? n : 1) * sizeof(int));
+  if (!writers)
+  {
+    pll_amd_set_error(PLL_ERROR_MEM_ALLOC, "%s: no memory for the argument check", what);
+    return PLL_FAILURE;
+  }
+  for (k = 0; k < n; ++k) writers[k] = -1;
+  for (i = 0; i < count && rc; ++i) rc = pll_amd_check_tree_candidate(p, &candidates[i], i, writers, writers + nodes);
+  free(writers);
+  return rc;
+}
+
+int pll_amd_tree_score_supported(const pll_partition_t * p, const char * what)
+{
+  if (pll_amd_priv(p)->rep || (p->attributes & PLL_ATTRIB_SITE_REPEATS))
+  {
+    pll_amd_set_error(PLL_ERROR_HIP_UNSUPPORTED, "%s: not for site-repeat partitions", what);
+    return PLL_FAILURE;
+  }
+  if ((p->attributes & PLL_ATTRIB_AB_FLAG) || p->asc_bias_alloc)
+  {
+    pll_amd_set_error(PLL_ERROR_HIP_UNSUPPORTED, "%s: not for ascertainment-bias partitions", what);
+    return PLL_FAILURE;
+  }
+  return PLL_SUCCESS;
+}
+
+void pll_amd_tree_score_switches(int * route, int * slots)
+{
+  /* through the device layer's gate: without PLLHIP_DEVELOPER=1 the variables are not looked at */
+  const char * env = pllhip_env_is_honoured("PLLHIP_TREE_SCORE_ROUTE") ? getenv("PLLHIP_TREE_SCORE_ROUTE") : NULL;
+  *route = env ? (atoi(env) != 0) : -1;
+  env = pllhip_env_is_honoured("PLLHIP_TREE_SCORE_SLOTS") ? getenv("PLLHIP_TREE_SCORE_SLOTS") : NULL;
+  *slots = env ? atoi(env) : 0;
+}
+
+int pll_amd_tree_score_result(int rc, const char * what)
+{
+  if (!rc) return PLL_SUCCESS;
+  if (rc == -1) pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "%s", pllhip_last_error());
+  else if (rc == -2) pll_amd_set_error(PLL_ERROR_MEM_ALLOC, "%s", pllhip_last_error());
+  else if (rc == -3) pll_amd_set_error(PLL_ERROR_HIP_UNSUPPORTED, "%s", pllhip_last_error());
+  else return pll_amd_fail_hip(rc, what);
+  return PLL_FAILURE;
+}
+
 int pll_amd_tree_loglikelihood(pll_partition_t * p, const pll_amd_tree_candidate_t * candidates, unsigned int count,
                                const unsigned int * params_indices, double * lnl)
 {
@@ -97,7 +157,7 @@ int pll_amd_tree_loglikelihood(pll_partition_t * p, const pll_amd_tree_candidate
   const char * what = "pll_amd_tree_loglikelihood";
   unsigned int i;
   size_t budget;
-  int route, slots, rc, * writers;
+  int route, slots, rc;
   if (!p || !candidates || !params_indices || !lnl)
   {
     pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "%s: NULL argument", what);
@@ -109,37 +169,8 @@ int pll_amd_tree_loglikelihood(pll_partition_t * p, const pll_amd_tree_candidate
     return PLL_FAILURE;
   }
   q = pll_amd_priv(p);
-  for (i = 0; i < p->rate_cats; ++i)
-    if (params_indices[i] >= p->rate_matrices)
-    {
-      pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "params index %u out of range", params_indices[i]);
-      return PLL_FAILURE;
-    }
-  {
-    const size_t nodes = (size_t)p->tips + p->clv_buffers, n = nodes + p->scale_buffers;
-    size_t k;
-    writers = (int *)malloc((n ? n : 1) * sizeof(int));
-    if (!writers)
-    {
-      pll_amd_set_error(PLL_ERROR_MEM_ALLOC, "%s: no memory for the argument check", what);
-      return PLL_FAILURE;
-    }
-    for (k = 0; k < n; ++k) writers[k] = -1;
-    rc = PLL_SUCCESS;
-    for (i = 0; i < count && rc; ++i) rc = check_candidate(p, &candidates[i], i, writers, writers + nodes);
-    free(writers);
-    if (!rc) return PLL_FAILURE;
-  }
-  if (q->rep || (p->attributes & PLL_ATTRIB_SITE_REPEATS))
-  {
-    pll_amd_set_error(PLL_ERROR_HIP_UNSUPPORTED, "%s: not for site-repeat partitions", what);
-    return PLL_FAILURE;
-  }
-  if ((p->attributes & PLL_ATTRIB_AB_FLAG) || p->asc_bias_alloc)
-  {
-    pll_amd_set_error(PLL_ERROR_HIP_UNSUPPORTED, "%s: not for ascertainment-bias partitions", what);
-    return PLL_FAILURE;
-  }
+  if (!pll_amd_check_tree_candidates(p, what, candidates, count, params_indices)) return PLL_FAILURE;
+  if (!pll_amd_tree_score_supported(p, what)) return PLL_FAILURE;
   /* the eigen systems the P-matrices are made from, as pll_update_prob_matrices would (models.c) */
   for (i = 0; i < p->rate_cats; ++i)
     if (!p->eigen_decomp_valid[params_indices[i]])
@@ -150,30 +181,8 @@ int pll_amd_tree_loglikelihood(pll_partition_t * p, const pll_amd_tree_candidate
     const double mb = env ? atof(env) : 2048.0;
     budget = mb > 0.0 ? (size_t)(mb * 1024.0 * 1024.0) : 0;
   }
-  {
-    /* through the device layer's gate: without PLLHIP_DEVELOPER=1 the variables are not looked at */
-    const char * env = pllhip_env_is_honoured("PLLHIP_TREE_SCORE_ROUTE") ? getenv("PLLHIP_TREE_SCORE_ROUTE") : NULL;
-    route = env ? (atoi(env) != 0) : -1;
-    env = pllhip_env_is_honoured("PLLHIP_TREE_SCORE_SLOTS") ? getenv("PLLHIP_TREE_SCORE_SLOTS") : NULL;
-    slots = env ? atoi(env) : 0;
-  }
+  pll_amd_tree_score_switches(&route, &slots);
   rc = pllhip_tree_loglikelihood(q->ctx, (const pllhip_tree_candidate_t *)candidates, count, params_indices, route,
                                  slots, budget, lnl);
-  if (rc == -1)
-  {
-    pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "%s", pllhip_last_error());
-    return PLL_FAILURE;
-  }
-  if (rc == -2)
-  {
-    pll_amd_set_error(PLL_ERROR_MEM_ALLOC, "%s", pllhip_last_error());
-    return PLL_FAILURE;
-  }
-  if (rc == -3)
-  {
-    pll_amd_set_error(PLL_ERROR_HIP_UNSUPPORTED, "%s", pllhip_last_error());
-    return PLL_FAILURE;
-  }
-  if (rc) return pll_amd_fail_hip(rc, "tree log-likelihood");
-  return PLL_SUCCESS;
+  return pll_amd_tree_score_result(rc, "tree log-likelihood");
 }

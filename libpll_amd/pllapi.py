@@ -306,6 +306,8 @@ class PllLibrary:
                 lib.pllhip_tree_score_plan_dry.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_void_p, C.c_uint,
                                                            C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, _up,
                                                            C.POINTER(C.c_int), _up, _up]
+            if hasattr(lib, "pll_amd_model_loglikelihood"):
+                lib.pll_amd_model_loglikelihood.argtypes = [_PP, C.c_void_p, C.c_void_p, C.c_uint, _up, _dp]
             if hasattr(lib, "pll_amd_site_posteriors"):
                 lib.pll_amd_site_posteriors.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p]
@@ -579,6 +581,39 @@ def tree_candidates(candidates):
     return arr, keep
 
 
+class ModelCandidate(C.Structure):
+    """pll_amd_model_candidate_t (include/pll_amd.h): five pointers, NULL = the partition's current value"""
+    _fields_ = [("subst_params", C.c_void_p), ("frequencies", C.c_void_p), ("prop_invar", C.c_void_p),
+                ("category_rates", C.c_void_p), ("category_weights", C.c_void_p)]
+
+
+MODEL_FIELDS = tuple(name for name, _ in ModelCandidate._fields_)
+
+
+def model_candidates(models):
+    """(a ModelCandidate array, what it points into) from dicts with any of the keys subst_params / frequencies (one
+    entry per rate-matrix set: an array, or None for the partition's), prop_invar (one number per set),
+    category_rates, category_weights (one number per category).  A key that is missing or None: the partition's."""
+    arr = (ModelCandidate * max(len(models), 1))()
+    keep = []
+    for i, m in enumerate(models):
+        assert set(m) <= set(MODEL_FIELDS), sorted(set(m) - set(MODEL_FIELDS))
+        for name in MODEL_FIELDS:
+            v = m.get(name)
+            if v is None:
+                continue
+            if name in ("subst_params", "frequencies"):
+                rows = [None if r is None else np.ascontiguousarray(r, dtype=np.float64) for r in v]
+                ptrs = (C.c_void_p * len(rows))(*[None if r is None else r.ctypes.data for r in rows])
+                keep += [rows, ptrs]
+                setattr(arr[i], name, C.addressof(ptrs))
+            else:
+                a = np.ascontiguousarray(v, dtype=np.float64)
+                keep.append(a)
+                setattr(arr[i], name, a.ctypes.data)
+    return arr, keep
+
+
 def tree_score_plan(lib, tips, clv_buffers, scale_buffers, pattern_tip, ops, parent, parent_scaler, child,
                     child_scaler, max_slots=16):
     """pllhip_tree_score_plan_dry (host logic, no device): (rc, order, slots [kept][3], nslots) -- the kept ops in walk
@@ -816,6 +851,26 @@ class Partition:
                                                  len(candidates), _u(pi), _d(out))
         del keep
         self._check(ok, "pll_amd_tree_loglikelihood")
+        return out
+
+    def model_loglikelihood(self, tree, models, params_indices):
+        """pll_amd_model_loglikelihood: one log-likelihood per candidate model on ONE tree, the partition's own model
+        left as it is.  tree: a row as tree_loglikelihood takes it; models: dicts as model_candidates takes them."""
+        if not hasattr(self.lib, "pll_amd_model_loglikelihood"):
+            raise PllError("this library has no pll_amd_model_loglikelihood")
+        tarr, tkeep = tree_candidates([tree])
+        marr, mkeep = model_candidates(models)
+        for m in models:
+            for name in ("subst_params", "frequencies", "prop_invar"):
+                assert m.get(name) is None or len(m[name]) == self.s.rate_matrices, name
+            for name in ("category_rates", "category_weights"):
+                assert m.get(name) is None or len(m[name]) == self.s.rate_cats, name
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        out = np.zeros(len(models))
+        ok = self.lib.pll_amd_model_loglikelihood(self.ptr, C.addressof(tarr), C.addressof(marr) if len(models) else None,
+                                                  len(models), _u(pi), _d(out))
+        del tkeep, mkeep
+        self._check(ok, "pll_amd_model_loglikelihood")
         return out
 
     def site_posteriors(self, edges, freqs_indices, want=("state_probs", "best", "rate_probs", "site_rates")):
