@@ -1175,6 +1175,13 @@ PLL_EXPORT int pll_amd_scaling_certificate(pll_partition_t * partition, unsigned
 PLL_EXPORT int pll_amd_deferred_stats(pll_partition_t * partition, unsigned long long * stats4);
 /* 0: every op of this partition is run and stored from now on (deferred CLVs are stored first); 1: defer again. */
 PLL_EXPORT int pll_amd_set_deferral(pll_partition_t * partition, int on);
+/* Pair products of 4-state partitions (pllhip.h: pllhip_set_unstored_pairs): the parent of an op over two tips or
+ * deferred cherries is walked by the whole-list launch but not stored where the list allows it, and stored on demand,
+ * bit for bit.  0: such parents are stored from now on (those unstored first); 1: the default.  Off with
+ * pll_amd_set_deferral(partition, 0).  stats4: {CLVs unstored now, ops left unstored in total, materialising
+ * launches, CLVs materialised}. */
+PLL_EXPORT int pll_amd_set_unstored_pairs(pll_partition_t * partition, int on);
+PLL_EXPORT int pll_amd_unstored_stats(pll_partition_t * partition, unsigned long long * stats4);
 /* Edge log-likelihood terms from the 4-state whole-list launch (pllhip.h: pllhip_set_edge_fold): after
  * pll_compute_edge_loglikelihood at an inner-inner edge, the next pll_update_partials that writes one of the edge's two
  * CLVs also forms the edge's per-site terms, and the same evaluation then only sums them -- bit for bit the value it

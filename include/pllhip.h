@@ -175,6 +175,19 @@ PLLHIP_EXPORT int pllhip_fused_plan_dry(unsigned int tips, unsigned int clv_buff
                                         unsigned int nslots, unsigned int * order_out,
                                         unsigned int * reloads_out, int * slots_out);
 
+/* The deferred-cherry planner below with pair products (pllhip_set_unstored_pairs): the list of a partition with
+ * pattern tips, `rate_cats` (1, 2, 4) categories and no or per-site scale buffers, planned as one segment with `nslots`
+ * slots per wave -- 0: at 12 waves per CU, else 8 -- and the rule the live path applies to the finished plan.
+ * edge4 (may be NULL): the hinted evaluation {parent_clv, parent_scaler, child_clv, child_scaler} (the slot counts are
+ * then always the derived ones).  unstored_out[i] = 1: op i of the list is walked and its parent is not stored; the
+ * other outputs are pllhip_fused_plan_dry_deferred's. */
+PLLHIP_EXPORT int pllhip_fused_plan_dry_unstored(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                                 int pattern_tip, unsigned int rate_cats, const pllhip_op_t * ops,
+                                                 unsigned int count, unsigned int nslots, const unsigned char * pinned,
+                                                 const int * edge4, unsigned int * nkept, unsigned int * order_out,
+                                                 int * slots_out, int * operands_out, unsigned char * deferred_out,
+                                                 unsigned int * reloads_out, unsigned char * unstored_out);
+
 /* The same with deferred cherries (pllhip_set_deferral): which tip-tip ops the list defers and how the kept ops are
  * walked.  old_deferred / old_scaler / pinned: per CLV index (tips + clv_buffers entries), what earlier calls left
  * deferred, with which scale buffer (-1 none), and which CLVs are never deferred; each may be NULL.  Out (any may be
@@ -238,6 +251,19 @@ PLLHIP_EXPORT int pllhip_cert_stats(pllhip_ctx_t * ctx, unsigned long long * out
  * pllhip_deferred_stats: {CLVs deferred now, ops deferred in total, materialising launches, CLVs materialised}. */
 PLLHIP_EXPORT int pllhip_set_deferral(pllhip_ctx_t * ctx, int on);
 PLLHIP_EXPORT int pllhip_deferred_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+
+/* Unstored pair products.  A list that defers its cherries walks the ops right above them as gathered-gathered ops:
+ * parent = Fa[tip rows] * Fb[tip rows], two 256-entry factor tables, times 2^256 where the scaling test fired.  Where
+ * the list treats such a parent the way a tree does, the plan keeps it in a slot for its reader, nothing reloads it
+ * and it is no end of the hinted edge, the launch does not store the CLV (its counts it does): the context keeps the
+ * two tables instead -- snapshots, as for cherries -- and every entry point that reads or overwrites the CLV or its
+ * scale buffer outside a list kernel stores it first, bit for bit what the op would have stored.
+ * pllhip_set_unstored_pairs(ctx, 0): such parents are stored (those unstored now first); 1: the default; per shard,
+ * like pllhip_set_deferral, and off whenever that is off.  No environment switch.
+ * pllhip_unstored_stats: {CLVs unstored now, ops left unstored in total, materialising launches, CLVs materialised};
+ * pllhip_deferred_stats keeps counting cherries only. */
+PLLHIP_EXPORT int pllhip_set_unstored_pairs(pllhip_ctx_t * ctx, int on);
+PLLHIP_EXPORT int pllhip_unstored_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
 
 /* Edge log-likelihood terms from the 4-state whole-list launch.  pllhip_edge_loglikelihood remembers an inner-inner
  * request; the next pllhip_update_partials that runs as ONE whole-list launch and writes one of the edge's two CLVs

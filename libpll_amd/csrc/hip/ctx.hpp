@@ -87,7 +87,7 @@ struct pllhip_ctx
   double * lnl_scratch = nullptr; // CLV-sized: per-state lnL terms of the two-pass kernels (likelihood.hip)
   // whole-list kernel (partials_fused.hip): the plan's device copy and two pinned staging buffers
   void * d_plan = nullptr;
-  void * d_sink = nullptr; // 1 KB that the stores of lanes past the last site go to
+  void * d_sink = nullptr; // the whole-list kernels' sinks, one per wave: stores that must be issued and whose bytes nobody wants
   unsigned int tile_counter_phase = 0;     // (4 states: which of the two sets of tile counters the next launch hands out from)
   unsigned int * d_tile_counter = nullptr; // whole-list kernels: next tile to hand out (PLLHIP_TILE_COUNTER_BYTES: one per
                                            // group of eight workgroups, 128 bytes apart -- partials_fused.hip)
@@ -114,18 +114,28 @@ struct pllhip_ctx
   // parent CLV is DEFINED by its two tip rows and a kept copy of its pair table T[c1][c2][rate][state] until somebody
   // other than a list kernel needs the bytes -- every such entry point materialises what it touches first
   // (PLLHIP_DEFERRED_* below).  deferred[i].on: CLV i is in that state; scaler: the scale buffer cleared with it.
+  // A second kind, the PAIR PRODUCT ("Unstored pair products"): the parent of a gathered-gathered op
+  // that the list kernel walked but did not store -- Fa[rows 0, 1] * Fb[rows 2, 3], the two factor tables the op
+  // gathered from, kept in the pool as well, times 2^256 where the op's count (in HBM, in `scaler`) is not 0.
   struct deferred_clv
   {
     bool on = false;
+    bool pair = false;                   // a pair product: rows[] and the pool's two tables; else a cherry: tip1, tip2
     unsigned int tip1 = 0, tip2 = 0;
+    unsigned int rows[4] = {0, 0, 0, 0}; // tip index + 1 of each table's two rows (0: none -- code 0)
     int scaler = -1;
   };
   std::vector<deferred_clv> deferred;          // per CLV index (sized on first use)
   std::vector<int> deferred_sc_owner;          // per scale buffer: the deferred CLV that owns its (zero) counts, or -1
   std::vector<unsigned char> clv_pinned;       // per CLV index: pllhip_dev_clv handed its address out -- never deferred
-  unsigned int n_deferred = 0;
-  double * defer_pool = nullptr;               // [CLV index][256][span]: the kept tables, one place per CLV
+  unsigned int n_deferred = 0;                 // cherries and pair products
+  unsigned int n_unstored = 0;                 // ... the pair products among them
+  double * defer_pool = nullptr;               // [CLV index][defer_pool_tables][256][span]: the kept tables
+  unsigned int defer_pool_tables = 0;          // 2: a cherry's T or a pair product's Fa, Fb; 1 (no room for two): cherries only
   bool defer_pool_failed = false;
+  bool unstored_pairs = true;                  // pllhip_set_unstored_pairs
+  std::vector<unsigned int> fused_last_unstored; // the kept plan's pair products: {clv, scaler + 1, rows[4]} each
+  unsigned long long unstored_stats[4] = {0, 0, 0, 0}; // the same four numbers for pair products
   bool cherry_deferral = true;                        // pllhip_set_deferral (0: the eager path, for A/B and tests)
   unsigned int defer_epoch = 0;                // bumped whenever a deferral ends other than by the list that replaces it
   unsigned int fused_last_defer_epoch = 0;     // ... as it was when the kept plan was launched
@@ -563,7 +573,7 @@ static inline void pllhip_edge_terms_drop(pllhip_ctx * c)
 int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * clv_indices, int n);
 int pllhip_deferred_materialise_scalers(pllhip_ctx * c, const int * scaler_indices, int n);
 void pllhip_deferred_drop(pllhip_ctx * c, unsigned int clv_index); // the deferral ends without the bytes (overwritten)
-double * pllhip_deferred_table(pllhip_ctx * c, unsigned int clv_index); // its place in the pool (nullptr: no pool)
+double * pllhip_deferred_table(pllhip_ctx * c, unsigned int clv_index, unsigned int which = 0); // its place in the pool (nullptr: no pool, or no second table)
 #define PLLHIP_DEFERRED_FLUSH(c)                                         \
   do {                                                                   \
     if ((c)->n_deferred) {                                               \

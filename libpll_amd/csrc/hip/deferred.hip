@@ -8,6 +8,14 @@
 // or a scale buffer outside a list kernel comes through here first (ctx.hpp: PLLHIP_DEFERRED_NEED / _FLUSH): one
 // launch gathers the rows of all the CLVs asked for, blockIdx.y = CLV, and zeroes the scale buffers the ops would
 // have cleared (core_partials_avx.c:598-599) -- the bytes the tip-tip op itself would have stored.
+//
+// Pair products ("Unstored pair products"): the parent of a gathered-gathered op is Fa[rows] * Fb[rows],
+// times 2^256 where the scaling test fired.  The list kernel walks the op -- its reader takes the value from the
+// wave's slot, its counts are stored -- but where nothing else in the list needs the bytes it does not store the CLV
+// (fused_plan.hip: pllhip_fused_unstored).  The CLV is then defined by kept copies of the two factor tables (the
+// table launch writes them next to the ones the kernel gathers from: the same values), their tip rows and the op's
+// counts, which ARE in HBM: a gathered operand inherits none, so a count is 0 or 1 and is the scale bit.  The same
+// launch as for cherries forms it on demand with the kernel's own two multiplications.
 #include <algorithm>
 
 #include "ctx.hpp"
@@ -21,6 +29,11 @@ struct DeferredJobs
   const unsigned char * c2[PLLHIP_DEFER_BATCH];
   pll_v2d * clv[PLLHIP_DEFER_BATCH];
   unsigned int * counts[PLLHIP_DEFER_BATCH]; // nullptr: none
+  // a pair product (tab2 not nullptr): tab = Fa by (c1, c2), tab2 = Fb by (c3, c4); a row that is nullptr: code 0;
+  // counts are READ (the scale bits), not cleared
+  const pll_v2d * tab2[PLLHIP_DEFER_BATCH];
+  const unsigned char * c3[PLLHIP_DEFER_BATCH];
+  const unsigned char * c4[PLLHIP_DEFER_BATCH];
 };
 static_assert(sizeof(DeferredJobs) <= 3900, "the jobs travel as kernel arguments");
 
@@ -36,6 +49,27 @@ __global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs,
   pll_v2d * __restrict__ clv = jobs.clv[blockIdx.y];
   unsigned int * __restrict__ counts = jobs.counts[blockIdx.y];
   const size_t total = sites * span2;
+  if (const pll_v2d * __restrict__ tab2 = jobs.tab2[blockIdx.y])
+  {
+    const unsigned char * __restrict__ c3 = jobs.c3[blockIdx.y];
+    const unsigned char * __restrict__ c4 = jobs.c4[blockIdx.y];
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+    {
+      const size_t n = t / span2;
+      const unsigned int g = (unsigned int)(t - n * span2);
+      const unsigned int pa = ((c1 ? (unsigned int)(c1[n] & 15u) : 0u) << 4) | (c2 ? (unsigned int)(c2[n] & 15u) : 0u);
+      const unsigned int pb = ((c3 ? (unsigned int)(c3[n] & 15u) : 0u) << 4) | (c4 ? (unsigned int)(c4[n] & 15u) : 0u);
+      const pll_v2d a = tab[(size_t)pa * span2 + g], b = tab2[(size_t)pb * span2 + g];
+      // (partials_fused.hip, step(): q = x * y, then q *= 2^256 or 1.0)
+      const double factor = __hiloint2double((counts && counts[n * count_words]) ? 0x4ff00000 : 0x3ff00000, 0);
+      pll_v2d v = {a.x * b.x, a.y * b.y};
+      v.x *= factor;
+      v.y *= factor;
+      if (NT) __builtin_nontemporal_store(v, clv + t);
+      else clv[t] = v;
+    }
+    return;
+  }
   for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
   {
     const size_t n = t / span2;
@@ -50,13 +84,16 @@ __global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs,
       counts[t] = 0u;
 }
 
-double * pllhip_deferred_table(pllhip_ctx * c, unsigned int idx)
+double * pllhip_deferred_table(pllhip_ctx * c, unsigned int idx, unsigned int which)
 {
   if (!c->defer_pool)
   {
     if (c->defer_pool_failed) return nullptr;
-    const size_t bytes = c->clv.size() * 256 * c->span * sizeof(double);
-    if (bytes > ((size_t)512 << 20) || hipMalloc((void **)&c->defer_pool, bytes) != hipSuccess)
+    // two tables per CLV index (an index is a cherry or a pair product, never both) where 512 MB hold them, else the
+    // cherries' one: pair products are then stored as before
+    const size_t one = c->clv.size() * 256 * c->span * sizeof(double);
+    c->defer_pool_tables = 2 * one <= ((size_t)512 << 20) ? 2u : 1u;
+    if (one > ((size_t)512 << 20) || hipMalloc((void **)&c->defer_pool, one * c->defer_pool_tables) != hipSuccess)
     {
       (void)hipGetLastError();
       c->defer_pool = nullptr;
@@ -64,7 +101,8 @@ double * pllhip_deferred_table(pllhip_ctx * c, unsigned int idx)
       return nullptr;
     }
   }
-  return c->defer_pool + (size_t)idx * 256 * c->span;
+  if (which >= c->defer_pool_tables) return nullptr;
+  return c->defer_pool + ((size_t)idx * c->defer_pool_tables + which) * 256 * c->span;
 }
 
 static void deferred_clear(pllhip_ctx * c, unsigned int idx)
@@ -75,6 +113,8 @@ static void deferred_clear(pllhip_ctx * c, unsigned int idx)
     c->deferred_sc_owner[d.scaler] = -1;
   d.on = false;
   --c->n_deferred;
+  if (d.pair) --c->n_unstored;
+  d.pair = false;
   ++c->defer_epoch;
 }
 
@@ -103,9 +143,11 @@ int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
   const size_t total = (size_t)c->sh.sites * span2;
   const unsigned int gx = (unsigned int)std::min<size_t>(std::max<size_t>(1, (total + 255) / 256), (size_t)c->num_cus * 8);
   const bool nt = pllhip_use_nt(c);
+  size_t npairs = 0;
   for (size_t first = 0; first < todo.size(); first += PLLHIP_DEFER_BATCH)
   {
     const unsigned int m = (unsigned int)std::min<size_t>(PLLHIP_DEFER_BATCH, todo.size() - first);
+    const size_t pairs_before = npairs;
     DeferredJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
     for (unsigned int k = 0; k < m; ++k)
@@ -113,18 +155,33 @@ int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
       const unsigned int i = todo[first + k];
       const pllhip_ctx::deferred_clv & d = c->deferred[i];
       jobs.tab[k] = reinterpret_cast<const pll_v2d *>(pllhip_deferred_table(c, i));
-      jobs.c1[k] = pllhip_tip_ptr(c, d.tip1);
-      jobs.c2[k] = pllhip_tip_ptr(c, d.tip2);
       jobs.clv[k] = reinterpret_cast<pll_v2d *>(c->clv[i]);
       jobs.counts[k] = pllhip_scaler_ptr(c, d.scaler);
+      if (d.pair)
+      {
+        jobs.tab2[k] = reinterpret_cast<const pll_v2d *>(pllhip_deferred_table(c, i, 1));
+        const unsigned char * rows[4];
+        for (int r = 0; r < 4; ++r) rows[r] = d.rows[r] ? pllhip_tip_ptr(c, d.rows[r] - 1) : nullptr;
+        jobs.c1[k] = rows[0];
+        jobs.c2[k] = rows[1];
+        jobs.c3[k] = rows[2];
+        jobs.c4[k] = rows[3];
+        ++npairs;
+        continue;
+      }
+      jobs.c1[k] = pllhip_tip_ptr(c, d.tip1);
+      jobs.c2[k] = pllhip_tip_ptr(c, d.tip2);
     }
     if (nt) k_deferred_materialise<true><<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, 1u);
     else k_deferred_materialise<false><<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, 1u);
     HIP_TRY(hipGetLastError());
-    ++c->defer_stats[2];
+    // (a launch counts for each kind it serves)
+    if (npairs - pairs_before < m) ++c->defer_stats[2];
+    if (npairs > pairs_before) ++c->unstored_stats[2];
   }
   for (unsigned int i : todo) deferred_clear(c, i);
-  c->defer_stats[3] += todo.size();
+  c->defer_stats[3] += todo.size() - npairs;
+  c->unstored_stats[3] += npairs;
   return 0;
 }
 
@@ -150,6 +207,26 @@ extern "C" int pllhip_set_deferral(pllhip_ctx_t * c, int on)
   return 0;
 }
 
+// Pair products (see the top of the file) on or off; off stores those there are.  pllhip_set_deferral(ctx, 0) turns
+// both off: a list that defers no cherry has no gathered-gathered op over one.
+extern "C" int pllhip_set_unstored_pairs(pllhip_ctx_t * c, int on)
+{
+  pllhip_edge_terms_drop(c);
+  PLLHIP_ALL_SHARDS(c, pllhip_set_unstored_pairs(s, on));
+  if (c->unstored_pairs == (on != 0)) return 0;
+  if (!on && c->n_unstored)
+  {
+    std::vector<unsigned int> pairs;
+    for (unsigned int i = 0; i < c->deferred.size(); ++i)
+      if (c->deferred[i].on && c->deferred[i].pair) pairs.push_back(i);
+    const int rc = pllhip_deferred_materialise(c, pairs.data(), (int)pairs.size());
+    if (rc) return rc;
+  }
+  c->unstored_pairs = on != 0;
+  ++c->defer_epoch;
+  return 0;
+}
+
 extern "C" int pllhip_deferred_stats(pllhip_ctx_t * c, unsigned long long * out4)
 {
   for (int t = 0; t < 4; ++t) out4[t] = 0;
@@ -157,12 +234,29 @@ extern "C" int pllhip_deferred_stats(pllhip_ctx_t * c, unsigned long long * out4
   {
     for (pllhip_ctx * s : c->shards)
     {
-      out4[0] += s->n_deferred;
+      out4[0] += s->n_deferred - s->n_unstored;
       for (int t = 1; t < 4; ++t) out4[t] += s->defer_stats[t];
     }
     return 0;
   }
-  out4[0] = c->n_deferred;
+  out4[0] = c->n_deferred - c->n_unstored;
   for (int t = 1; t < 4; ++t) out4[t] = c->defer_stats[t];
+  return 0;
+}
+
+extern "C" int pllhip_unstored_stats(pllhip_ctx_t * c, unsigned long long * out4)
+{
+  for (int t = 0; t < 4; ++t) out4[t] = 0;
+  if (!c->shards.empty())
+  {
+    for (pllhip_ctx * s : c->shards)
+    {
+      out4[0] += s->n_unstored;
+      for (int t = 1; t < 4; ++t) out4[t] += s->unstored_stats[t];
+    }
+    return 0;
+  }
+  out4[0] = c->n_unstored;
+  for (int t = 1; t < 4; ++t) out4[t] = c->unstored_stats[t];
   return 0;
 }

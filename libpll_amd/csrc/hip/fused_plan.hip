@@ -531,6 +531,73 @@ bool pllhip_fused_edge_end_stored(const FusedGeom & geom, const FusedDeferral & 
          std::find(dd.dropped.begin(), dd.dropped.end(), clv) != dd.dropped.end();
 }
 
+// Which gathered-gathered parents of a planned list are left unstored (partials_fused.hpp).
+unsigned int pllhip_fused_unstored(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
+                                   std::vector<std::vector<FusedOp>> & plans, const FusedEdge * edge,
+                                   const unsigned char * pinned)
+{
+  const size_t nclv = geom.nclv, nsc = geom.nsc;
+  const unsigned int NONE = ~0u;
+  // how the list treats every CLV and scale buffer (the cherries' rule: pllhip_fused_deferral)
+  std::vector<unsigned int> nwrites(nclv, 0), first_read(nclv, NONE), sc_nwrites(nsc, 0), sc_first_read(nsc, NONE);
+  std::vector<int> sc_reader(nsc, -1); // the one CLV a scale buffer is read with (-1 nobody, -2 several)
+  for (unsigned int k = 0; k < count; ++k)
+  {
+    const pllhip_op_t & op = ops[k];
+    ++nwrites[op.parent_clv];
+    if (op.parent_scaler >= 0) ++sc_nwrites[op.parent_scaler];
+    const unsigned int kid[2] = {op.child1_clv, op.child2_clv};
+    const int ksc[2] = {op.child1_scaler, op.child2_scaler};
+    for (int o = 0; o < 2; ++o)
+    {
+      if (first_read[kid[o]] == NONE) first_read[kid[o]] = k;
+      if (ksc[o] < 0) continue;
+      if (sc_first_read[ksc[o]] == NONE) sc_first_read[ksc[o]] = k;
+      if (sc_reader[ksc[o]] == -1) sc_reader[ksc[o]] = (int)kid[o];
+      else if (sc_reader[ksc[o]] != (int)kid[o]) sc_reader[ksc[o]] = -2;
+    }
+  }
+  // what some op of the plan copies back from HBM
+  std::vector<const double *> reloaded;
+  for (const auto & plan : plans)
+    for (const FusedOp & f : plan)
+    {
+      if ((f.dma_flags & 1) && f.left_hbm) reloaded.push_back(f.left_hbm);
+      if ((f.dma_flags & 2) && f.right_hbm) reloaded.push_back(f.right_hbm);
+    }
+  if (edge)
+  {
+    if ((edge->op.dma_flags & 1) && edge->op.left_hbm) reloaded.push_back(edge->op.left_hbm);
+    if ((edge->op.dma_flags & 2) && edge->op.right_hbm) reloaded.push_back(edge->op.right_hbm);
+  }
+  unsigned int n = 0;
+  for (auto & plan : plans)
+    for (FusedOp & f : plan)
+    {
+      f.unstored = 0;
+      if (f.kind != 3 || f.pslot < 0 || f.list_pos < 0 || (unsigned int)f.list_pos >= count) continue;
+      const unsigned int k = (unsigned int)f.list_pos;
+      const pllhip_op_t & op = ops[k];
+      const unsigned int p = op.parent_clv;
+      const int s = op.parent_scaler;
+      if (geom.is_tip(p) || (pinned && pinned[p])) continue;
+      if (edge && (p == edge->parent_clv || p == edge->child_clv)) continue;
+      if (nwrites[p] != 1 || first_read[p] == NONE || first_read[p] <= k) continue;
+      bool foreign = false; // read with counts that are not its own
+      for (unsigned int r = k + 1; r < count && !foreign; ++r)
+        foreign = (ops[r].child1_clv == p && ops[r].child1_scaler != -1 && ops[r].child1_scaler != s) ||
+                  (ops[r].child2_clv == p && ops[r].child2_scaler != -1 && ops[r].child2_scaler != s);
+      if (foreign) continue;
+      if (s >= 0 && (sc_nwrites[s] != 1 || (sc_reader[s] != -1 && sc_reader[s] != (int)p) ||
+                     (sc_first_read[s] != NONE && sc_first_read[s] <= k)))
+        continue;
+      if (std::find(reloaded.begin(), reloaded.end(), (const double *)f.parent) != reloaded.end()) continue;
+      f.unstored = 1;
+      ++n;
+    }
+  return n;
+}
+
 int pllhip_fused_plan_segments(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
                                const FusedExtra * extra, unsigned int count, const unsigned int * seg_of, unsigned int nsegs,
                                unsigned int nslots, std::vector<std::vector<FusedOp>> & plans, unsigned int * reloads)
@@ -813,6 +880,7 @@ static void dry_resolve(const FusedGeom & geom, const pllhip_op_t & op, Partials
   memset(&a, 0, sizeof(PartialsArgs));
   kind = (tip1 && tip2) ? 2 : (t1 && t2) ? 3 : (t1 || t2) ? 1 : 0;
   a.pscaler = dry_scaler(op.parent_scaler);
+  a.parent = const_cast<double *>(dry_clv(op.parent_clv));
   if (kind == 0)
   {
     a.left = dry_clv(op.child1_clv);
@@ -853,10 +921,12 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
                              int * slots_out, int * operands_out, unsigned char * deferred_out,
                              unsigned int * reloads_out, unsigned int * materialise_out,
                              unsigned int * nmaterialise, unsigned int * dropped_out, unsigned int * ndropped,
-                             const int * edge4, unsigned int rate_cats, int * edge_out)
+                             const int * edge4, unsigned int rate_cats, int * edge_out,
+                             unsigned char * unstored_out = nullptr)
 {
   FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
   if (dry_ops_in_range("pllhip_fused_plan_dry_deferred", geom, ops, count)) return -1;
+  for (unsigned int i = 0; unstored_out && i < count; ++i) unstored_out[i] = 0;
   if (edge4 && (edge4[0] < 0 || (size_t)edge4[0] >= geom.nclv || edge4[2] < 0 || (size_t)edge4[2] >= geom.nclv ||
                 edge4[1] >= (int)scale_buffers || edge4[3] >= (int)scale_buffers ||
                 !(rate_cats == 1 || rate_cats == 2 || rate_cats == 4)))
@@ -894,8 +964,10 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
   for (int t = 0; edge_out && t < 8; ++t) edge_out[t] = t >= 1 && t <= 4 ? -1 : 0;
   if (!n) return 0;
   // one segment; with an edge the slot counts of a partition with per-site or no scale buffers
-  const unsigned int slot_counts[2] = {edge4 ? pllhip_fused_slots_for(rate_cats, false, 3) : nslots,
-                                       edge4 ? pllhip_fused_slots_for(rate_cats, false, 2) : 0u};
+  // (pllhip_fused_plan_dry_unstored with nslots 0: the same two)
+  const bool derived = edge4 || (!nslots && rate_cats);
+  const unsigned int slot_counts[2] = {derived ? pllhip_fused_slots_for(rate_cats, false, 3) : nslots,
+                                       derived ? pllhip_fused_slots_for(rate_cats, false, 2) : 0u};
   FusedEdge e;
   memset(&e, 0, sizeof(e));
   if (edge4)
@@ -917,9 +989,15 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
     }
   }
   FusedListPlan lp;
-  const int rc = pllhip_fused_plan_list(geom, kept.data(), args.data(), kinds.data(), nullptr, n, 1, slot_counts, edge4 ? 2u : 1u,
+  const int rc = pllhip_fused_plan_list(geom, kept.data(), args.data(), kinds.data(), nullptr, n, 1, slot_counts, derived ? 2u : 1u,
                                         edge4 ? &e : nullptr, d, lp);
   if (rc) return rc;
+  if (unstored_out)
+  {
+    pllhip_fused_unstored(geom, kept.data(), n, lp.plans, edge4 ? &e : nullptr, pinned);
+    for (const FusedOp & f : lp.plans[0])
+      if (f.unstored) unstored_out[where[f.list_pos]] = 1;
+  }
   if (edge4)
   {
     const int wgs = 3 - (int)lp.taken; // workgroups per CU of the slot count taken
@@ -980,6 +1058,30 @@ extern "C" int pllhip_fused_plan_dry_edge(unsigned int tips, unsigned int clv_bu
   return plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, 0, old_deferred, old_scaler, pinned, nkept,
                            order_out, slots_out, operands_out, deferred_out, reloads_out, nullptr, nullptr, nullptr, nullptr,
                            edge4, rate_cats, edge_out);
+}
+
+// The same with pair products (pllhip_set_unstored_pairs; tests/test_host_unstored_plan.py): the list of a partition
+// that may defer (pattern tips, `rate_cats` categories, no or per-site scale buffers), planned by the driver
+// pllhip_update_partials plans with as one segment -- with `nslots` slots per wave, or (nslots 0) at 12 waves per CU,
+// else 8 -- then pllhip_fused_unstored, the rule the live path applies.  edge4 (may be NULL): the hinted evaluation,
+// as for pllhip_fused_plan_dry_edge.  unstored_out[i] = 1: op i of the caller's list is walked and its parent is not
+// stored.  The other outputs are pllhip_fused_plan_dry_deferred's.
+extern "C" int pllhip_fused_plan_dry_unstored(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                              int pattern_tip, unsigned int rate_cats, const pllhip_op_t * ops, unsigned int count,
+                                              unsigned int nslots, const unsigned char * pinned, const int * edge4,
+                                              unsigned int * nkept, unsigned int * order_out, int * slots_out,
+                                              int * operands_out, unsigned char * deferred_out, unsigned int * reloads_out,
+                                              unsigned char * unstored_out)
+{
+  if (!(rate_cats == 1 || rate_cats == 2 || rate_cats == 4) || !unstored_out)
+  {
+    pllhip_set_error("pllhip_fused_plan_dry_unstored: rate_cats of an instance that defers, and unstored_out");
+    return -1;
+  }
+  int edge_out[8];
+  return plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, nslots, nullptr, nullptr, pinned, nkept,
+                           order_out, slots_out, operands_out, deferred_out, reloads_out, nullptr, nullptr, nullptr, nullptr,
+                           edge4, rate_cats, edge_out, unstored_out);
 }
 
 // The planner alone (tests/test_host.py, tools): which order and how many

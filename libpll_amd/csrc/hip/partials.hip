@@ -733,6 +733,9 @@ struct DnaListKept
   std::vector<FusedExtra> extras;          // their gathered operands (empty: none -- nothing deferred, now or before)
   std::vector<FusedPairJob> keep_jobs;     // the tables of the cherries this list defers
   std::vector<unsigned int> new_deferred;  // {clv, tip1, tip2, scaler + 1} per deferred op
+  std::vector<unsigned int> rows;          // per op of `ops`, four: tip index + 1 of the rows its two gathered factors are
+                                           // indexed by (0 none) -- what an unstored pair product is kept with
+  std::vector<unsigned int> new_unstored;  // {clv, scaler + 1, rows[4]} per op whose parent this list leaves unstored
 };
 // args / kinds: resolve_op's of the caller's list in, of k.ops out (where k.ops is not empty).  Materialises what the
 // list cannot read from a table; every deferred CLV where nothing may be deferred.
@@ -759,6 +762,20 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
     }
   const FusedGeom g0 = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
   pllhip_fused_deferral(g0, ops, count, oldf.data(), oldsc.data(), c->clv_pinned.data(), dd);
+  // (a pair product left unstored by an earlier call has no table a reader could gather from: where a cherry would
+  // be read from its kept table, it is stored first -- an ordinary buffer to this list)
+  // (read, not written: an index the list writes is a gathered operand because the list defers the cherry it becomes)
+  if (c->n_unstored)
+  {
+    std::vector<unsigned char> written(c->clv.size(), 0);
+    for (unsigned int i = 0; i < count; ++i) written[ops[i].parent_clv] = 1;
+    for (size_t i = 0; i < c->clv.size(); ++i)
+      if (oldf[i] && c->deferred[i].pair && dd.as_tip[i] && !written[i])
+      {
+        dd.as_tip[i] = 0;
+        dd.materialise.push_back((unsigned int)i);
+      }
+  }
   unsigned int ndefer = 0;
   for (unsigned int i = 0; i < count; ++i) ndefer += dd.defer[i];
   bool any_kept_table = false;
@@ -782,21 +799,23 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
   std::vector<int> deferring_op(c->clv.size(), -1);
   for (unsigned int i = 0; i < count; ++i)
     if (dd.defer[i]) deferring_op[ops[i].parent_clv] = (int)i;
-  auto operand = [&](unsigned int clv, unsigned int matrix) {
+  // (rows2: tip index + 1 of row1 / row2, 0 none)
+  auto operand = [&](unsigned int clv, unsigned int matrix, unsigned int * rows2) {
     FusedOperand g;
     memset(&g, 0, sizeof(g));
     g.mat = pllhip_pmat_ptr(c, matrix);
+    unsigned int t1, t2 = ~0u;
     if (pllhip_is_tip(c, clv))
     {
       g.type = FUSED_G_TIP;
-      g.row1 = pllhip_tip_ptr(c, clv);
+      t1 = clv;
     }
     else if (deferring_op[clv] >= 0)
     {
       const pllhip_op_t & d = ops[deferring_op[clv]];
       g.type = FUSED_G_CHERRY_NEW;
-      g.row1 = pllhip_tip_ptr(c, d.child1_clv);
-      g.row2 = pllhip_tip_ptr(c, d.child2_clv);
+      t1 = d.child1_clv;
+      t2 = d.child2_clv;
       g.c_lmat = pllhip_pmat_ptr(c, d.child1_matrix);
       g.c_rmat = pllhip_pmat_ptr(c, d.child2_matrix);
     }
@@ -804,10 +823,14 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
     {
       const pllhip_ctx::deferred_clv & d = c->deferred[clv];
       g.type = FUSED_G_CHERRY_KEPT;
-      g.row1 = pllhip_tip_ptr(c, d.tip1);
-      g.row2 = pllhip_tip_ptr(c, d.tip2);
+      t1 = d.tip1;
+      t2 = d.tip2;
       g.kept = pllhip_deferred_table(c, clv);
     }
+    g.row1 = pllhip_tip_ptr(c, t1);
+    if (t2 != ~0u) g.row2 = pllhip_tip_ptr(c, t2);
+    rows2[0] = t1 + 1;
+    rows2[1] = t2 + 1;
     return g;
   };
   std::vector<PartialsArgs> kargs;
@@ -825,6 +848,7 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
     int kind = kinds[i];
     FusedExtra x;
     memset(&x, 0, sizeof(x));
+    unsigned int rows[4] = {0, 0, 0, 0};
     const bool d1 = !pllhip_is_tip(c, op.child1_clv) && dd.as_tip[op.child1_clv];
     const bool d2 = !pllhip_is_tip(c, op.child2_clv) && dd.as_tip[op.child2_clv];
     if (d1 || d2)
@@ -836,15 +860,15 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
       if (g1 && g2)
       {
         kind = 3;
-        x.g[0] = operand(op.child1_clv, op.child1_matrix);
-        x.g[1] = operand(op.child2_clv, op.child2_matrix);
+        x.g[0] = operand(op.child1_clv, op.child1_matrix, rows);
+        x.g[1] = operand(op.child2_clv, op.child2_matrix, rows + 2);
       }
       else
       {
         // the gathered operand plays the tip of a tip-inner op: "left"
         kind = 1;
         const unsigned int gathered = g1 ? op.child1_clv : op.child2_clv, inner = g1 ? op.child2_clv : op.child1_clv;
-        x.g[0] = operand(gathered, g1 ? op.child1_matrix : op.child2_matrix);
+        x.g[0] = operand(gathered, g1 ? op.child1_matrix : op.child2_matrix, rows);
         a.right = c->clv[inner];
         a.lmat = pllhip_pmat_ptr(c, g1 ? op.child1_matrix : op.child2_matrix);
         a.rmat = pllhip_pmat_ptr(c, g1 ? op.child2_matrix : op.child1_matrix);
@@ -855,6 +879,7 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
     kargs.push_back(a);
     kkinds.push_back(kind);
     k.extras.push_back(x);
+    k.rows.insert(k.rows.end(), rows, rows + 4);
   }
   args.swap(kargs);
   kinds.swap(kkinds);
@@ -880,6 +905,7 @@ static int update_partials_dna_list(pllhip_ctx * c, const pllhip_op_t * full_ops
   {
     pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
     c->defer_stats[1] += c->fused_last_deferred.size() / 4;
+    c->unstored_stats[1] += c->fused_last_unstored.size() / 6;
     const int rc = pllhip_relaunch_fused(c);
     if (rc == 0 && c->fused_last_edge)
     {
@@ -948,6 +974,20 @@ static int update_partials_dna_list(pllhip_ctx * c, const pllhip_op_t * full_ops
   rc = pllhip_fused_plan_list(geom, ops, args.data(), kinds.data(), extras, count, max_segs, slot_counts + skip, 2u - skip,
                               edge_ok ? &fedge : nullptr, k.dd, lp);
   if (rc < 0) return rc;
+  // Pair products (deferred.hip): the gathered-gathered parents the finished plan lets go unstored, where the instance
+  // defers at all (a kind-3 op exists only then) and the pool has the two tables each needs.
+  if (rc == 0 && extras && c->unstored_pairs && c->cherry_deferral && pllhip_deferred_table(c, 0, 1) &&
+      pllhip_fused_unstored(geom, ops, count, lp.plans, edge_ok ? &fedge : nullptr, c->clv_pinned.data()))
+    for (auto & plan : lp.plans)
+      for (FusedOp & f : plan)
+        if (f.unstored)
+        {
+          const pllhip_op_t & op = ops[f.list_pos];
+          f.keep[0] = pllhip_deferred_table(c, op.parent_clv, 0);
+          f.keep[1] = pllhip_deferred_table(c, op.parent_clv, 1);
+          const unsigned int * rows = &k.rows[4 * (size_t)f.list_pos];
+          k.new_unstored.insert(k.new_unstored.end(), {op.parent_clv, (unsigned int)(op.parent_scaler + 1), rows[0], rows[1], rows[2], rows[3]});
+        }
   if (rc == 0)
   {
     pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
@@ -979,7 +1019,23 @@ static int update_partials_dna_list(pllhip_ctx * c, const pllhip_op_t * full_ops
         if (sc >= 0) c->deferred_sc_owner[sc] = (int)clv;
         ++c->n_deferred;
       }
+      for (size_t t = 0; t < k.new_unstored.size(); t += 6)
+      {
+        const unsigned int clv = k.new_unstored[t];
+        const int sc = (int)k.new_unstored[t + 1] - 1;
+        pllhip_deferred_drop(c, clv);
+        pllhip_ctx::deferred_clv & d = c->deferred[clv];
+        d.on = d.pair = true;
+        for (int r = 0; r < 4; ++r) d.rows[r] = k.new_unstored[t + 2 + r];
+        d.scaler = sc;
+        // (its counts are in HBM, but they define the CLV: whoever touches them stores it first)
+        if (sc >= 0) c->deferred_sc_owner[sc] = (int)clv;
+        ++c->n_deferred;
+        ++c->n_unstored;
+      }
       c->defer_stats[1] += k.new_deferred.size() / 4;
+      c->unstored_stats[1] += k.new_unstored.size() / 6;
+      c->fused_last_unstored = k.new_unstored;
       c->fused_last_deferred = k.new_deferred;
       c->fused_last_defer_epoch = c->defer_epoch;
       c->fused_last_ops.assign(full_ops, full_ops + full_count);

@@ -38,6 +38,8 @@
 //             addresses and LDS offsets, decoded by the host (FusedRec in partials_fused.hpp)
 //   cherries  a tip-tip op is not run at all where the list allows it: its parent is DEFERRED (deferred.hip), and the ops
 //             that read it take their factor from a table -- gathered-inner (kind 1) and gathered-gathered (kind 3)
+//   pairs     the parent of a gathered-gathered op that nothing reads from HBM is walked but not stored: its tile stores
+//             go to the wave's sink, and deferred.hip stores the CLV on demand (PLLHIP_FUSED_UNSTORED, see step())
 //   limit     a wave's own serial path, not HBM: twelve waves per CU is all the slots allow, so
 //             the order within an op overlaps the wave's latencies with its own work (see step())
 //
@@ -138,6 +140,7 @@ __global__ __launch_bounds__(256) void k_dna_pair_tables(const FusedPairJob * __
     const unsigned int ki = threadIdx.x % ROW, sub = threadIdx.x / ROW, rate4 = (ki >> 2) * 4u;
     const PLL_GLOBAL double * pm = (const PLL_GLOBAL double *)jobs[i].pmat;
     double * tab = jobs[i].tab;
+    double * copy = jobs[i].copy; // (an unstored pair product's kept factor: the same values, deferred.hip)
     double p[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) p[k] = pm[ki * 4u + k];
@@ -160,7 +163,9 @@ __global__ __launch_bounds__(256) void k_dna_pair_tables(const FusedPairJob * __
         double t[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) t[k] = masksum4(l[k], c1) * masksum4(r[k], c2);
-        tab[pair * ROW + ki] = dot4(p, t[0], t[1], t[2], t[3]);
+        const double f = dot4(p, t[0], t[1], t[2], t[3]);
+        tab[pair * ROW + ki] = f;
+        if (copy) copy[pair * ROW + ki] = f;
       }
     }
     else
@@ -173,7 +178,9 @@ __global__ __launch_bounds__(256) void k_dna_pair_tables(const FusedPairJob * __
         double t[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) t[k] = kept[pair * ROW + rate4 + k];
-        tab[pair * ROW + ki] = dot4(p, t[0], t[1], t[2], t[3]);
+        const double f = dot4(p, t[0], t[1], t[2], t[3]);
+        tab[pair * ROW + ki] = f;
+        if (copy) copy[pair * ROW + ki] = f;
       }
     }
     return;
@@ -184,6 +191,7 @@ __global__ __launch_bounds__(256) void k_dna_pair_tables(const FusedPairJob * __
   // same order: masksum4 of a row, times masksum4 of a row.
   const PLL_GLOBAL double * lm = (const PLL_GLOBAL double *)jobs[i].lmat, * rm = (const PLL_GLOBAL double *)jobs[i].rmat;
   double * tab = jobs[i].tab;
+  double * copy = jobs[i].copy;
   // (tip-inner ops: the tip's factor alone, in the entries [code 1][0] the kernel's index
   // (code 1 << 4 | character of an absent tip = 0) reaches; x * 1.0 is x)
   const bool tt = jobs[i].kind != 0;
@@ -202,7 +210,9 @@ __global__ __launch_bounds__(256) void k_dna_pair_tables(const FusedPairJob * __
   for (unsigned int round = 0; round < ROUNDS; ++round)
   {
     const unsigned int pair = quarter * 64u + round * PER + sub, c1 = pair >> 4, c2 = pair & 15u;
-    tab[pair * ROW + ki] = masksum4(l, c1) * (tt ? masksum4(r, c2) : 1.0);
+    const double f = masksum4(l, c1) * (tt ? masksum4(r, c2) : 1.0);
+    tab[pair * ROW + ki] = f;
+    if (copy) copy[pair * ROW + ki] = f;
   }
 }
 
@@ -215,6 +225,8 @@ struct FusedFetch
 };
 
 typedef unsigned int pll_v4u __attribute__((ext_vector_type(4)));
+// a wave's sink in 16-byte granules: PLLHIP_FUSED_J KB of tile, 256 bytes of counts, the ticket word's line
+#define PLLHIP_FUSED_SINK_GRANULES (PLLHIP_FUSED_J * 64 + 32)
 
 // all lanes of a group of W (2, 4 or 8: a site's lanes, or a rate's) hold x != 0?  DPP, no ballot
 template <int W>
@@ -314,11 +326,13 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
   // with 1024 (profiles/r2_xcd_tile_mapping.txt).
   const size_t wave = (size_t)blockIdx.x * 4u + wave_in_wg;
   const size_t nwaves = (size_t)gridDim.x * 4u;
-  // every wave has 1280 bytes of sink of its own: thousands of waves storing to ONE block
+  // every wave has 2304 bytes of sink of its own: thousands of waves storing to ONE block
   // serialise on its cache lines (measured: ~0.7 ms per launch at 1 M sites, hidden behind a
   // 62-op list but not behind a 5-op one)
-  sink += wave * 96;
-  unsigned int * sink_cnt = reinterpret_cast<unsigned int *>(sink + 64);
+  // (J KB for the tile of an op whose parent is not stored -- PLLHIP_FUSED_UNSTORED, see step() --, 256 bytes of
+  // counts, the ticket word)
+  sink += wave * PLLHIP_FUSED_SINK_GRANULES;
+  unsigned int * sink_cnt = reinterpret_cast<unsigned int *>(sink + J * 64);
   // Tiles of the last rounds come from `tile_groups` counters (eight): groups of eight consecutive workgroups --
   // one on each XCD -- take the counters in turn, counter g hands out tiles g, g + 8, ... of that region.  (One
   // counter for everybody serialised its atomics at ~12 ns: 37 us per round of 3072 waves, which a 62-op list
@@ -329,7 +343,7 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
   // tile it only begins a whole list later); static rounds ask a word of the wave's own sink instead.
   const unsigned int tile_group = (blockIdx.x / 8u) % tile_groups;
   const unsigned long long my_counter = (unsigned long long)(uintptr_t)(next_tile + (size_t)tile_group * 32u);
-  const unsigned long long no_counter = (unsigned long long)(uintptr_t)(sink + 80);
+  const unsigned long long no_counter = (unsigned long long)(uintptr_t)(sink + J * 64 + 16);
   // where this lane's 16 bytes of tip characters of the first batch of rows begin (+ the tile's first site)
   const unsigned long long row0 = bases.rowtab[lane];
   // (8 rate categories: a tile is 8 sites -- a lane fetches 16 bytes all the same and uses the first 8)
@@ -612,7 +626,16 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       const unsigned int kind = fl & PLLHIP_FUSED_KIND_MASK;
       const bool has_slot = fl & PLLHIP_FUSED_HAS_PSLOT;
       const bool scaling = MODE != SCALE_NONE && (fl & PLLHIP_FUSED_SCALING);
-      const unsigned long long out = rec_parent(r0) + clv_off; // (uniform)
+      // (a pair product that nobody reads from HBM, deferred.hip: the SAME stores, to the wave's sink -- a uniform
+      // select of the address, no branch and no mask: every store the compiler counts is issued on every path, or the
+      // next op's wait would leave one operation more in flight than it thinks; the instances that never defer
+      // compile to what they were)
+      // (... and all 64 lanes to the SAME 16 bytes of it: the tiles' stores are non-temporal, and a non-temporal store
+      // to the sink leaves L2 for memory like any other -- measured: a whole redirected tile per op wrote as many bytes
+      // as before and the launch was no faster; 64 lanes on one address are one 64-byte request)
+      const bool unstored = SECOND && (fl & PLLHIP_FUSED_UNSTORED);
+      const unsigned long long out = unstored ? (unsigned long long)(uintptr_t)sink : rec_parent(r0) + clv_off; // (uniform)
+      const unsigned int st_lane16 = lane16 & (unstored ? 0u : ~0u);
       char * lds_l = reinterpret_cast<char *>(clv) + rec_lslot(r0) + lane16;
       char * lds_r = reinterpret_cast<char *>(clv) + rec_rslot(r0) + lane16;
       constexpr unsigned int GW = (MODE == SCALE_RATE) ? 2u : W; // lanes that share a count
@@ -729,7 +752,7 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
 #pragma unroll
       for (unsigned int j = 0; j < J; ++j)
       {
-        st16g<NT>(out, j * 1024u + lane16, p0[j], p1[j]);
+        st16g<NT>(out, j * 1024u + (SECOND ? st_lane16 : lane16), p0[j], p1[j]);
         const pll_v2d v = {p0[j], p1[j]};
         asm volatile("s_mov_b64 exec, %0\n\tds_write_b128 %1, %2 offset:%3\n\ts_mov_b64 exec, -1"
                      :: "s"(slot_mask), "v"(lds_p_b), "v"(v), "n"(j * 1024u) : "memory");
@@ -1030,10 +1053,11 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
       const size_t index = jobs.size();
       (o ? table2_of : table_of)[pos] = (unsigned int)(index * per * sizeof(double));
       double * tab = c->d_pairtab + index * per;
-      if (g.type == FUSED_G_TIP) jobs.push_back(FusedPairJob{g.mat, nullptr, tab, 0ull, nullptr, nullptr});
-      else if (g.type == FUSED_G_PAIR) jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 1ull, nullptr, nullptr});
-      else if (g.type == FUSED_G_CHERRY_NEW) jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 2ull, g.mat, nullptr});
-      else jobs.push_back(FusedPairJob{nullptr, nullptr, tab, 3ull, g.mat, g.kept});
+      double * copy = f.unstored ? f.keep[o] : nullptr; // (an unstored pair product: its factors are kept, deferred.hip)
+      if (g.type == FUSED_G_TIP) jobs.push_back(FusedPairJob{g.mat, nullptr, tab, 0ull, nullptr, nullptr, copy, 0ull});
+      else if (g.type == FUSED_G_PAIR) jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 1ull, nullptr, nullptr, copy, 0ull});
+      else if (g.type == FUSED_G_CHERRY_NEW) jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 2ull, g.mat, nullptr, copy, 0ull});
+      else jobs.push_back(FusedPairJob{nullptr, nullptr, tab, 3ull, g.mat, g.kept, copy, 0ull});
     }
     // every op with a parent scaler scales the partition's way
     if (f.pscaler) mode = c->sh.rate_scalers ? SCALE_RATE : SCALE_SITE;
@@ -1096,6 +1120,12 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
     r.flags = (unsigned int)f.kind & PLLHIP_FUSED_KIND_MASK;
     if (f.pslot >= 0) r.flags |= PLLHIP_FUSED_HAS_PSLOT;
     if (f.pscaler) r.flags |= PLLHIP_FUSED_SCALING;
+    if (f.unstored)
+    {
+      // (only what the kernel can redirect and the planner marked: a reader without the slot would find nothing)
+      if (f.kind != 3 || f.pslot < 0 || R > 4 || c->sh.rate_scalers || !f.keep[0] || !f.keep[1]) return 1;
+      r.flags |= PLLHIP_FUSED_UNSTORED;
+    }
     if (f.kind == 0 && f.lsc_slot >= 0) r.flags |= PLLHIP_FUSED_LCNT;
     if (f.kind != 2 && f.rsc_slot >= 0) r.flags |= PLLHIP_FUSED_RCNT;
     r.parent = (unsigned long long)(uintptr_t)f.parent;
@@ -1165,7 +1195,7 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   HIP_TRY(hipMemcpyAsync(c->d_plan, c->h_plan[b], bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipEventRecord(c->plan_done[b], c->stream));
   c->plan_pending[b] = true;
-  if (!c->d_sink) HIP_TRY(hipMalloc(&c->d_sink, (size_t)c->num_cus * 16 * 96 * sizeof(double2))); // 1536 B per wave
+  if (!c->d_sink) HIP_TRY(hipMalloc(&c->d_sink, (size_t)c->num_cus * 16 * PLLHIP_FUSED_SINK_GRANULES * sizeof(double2)));
   if (!c->d_tile_counter)
   {
     HIP_TRY(hipMalloc((void **)&c->d_tile_counter, 2 * PLLHIP_TILE_COUNTER_BYTES));

@@ -63,6 +63,8 @@ struct FusedOp
                                    // at the top of the op before this one
   const double * pair_tab;         // tip operands: [256 code pairs][rate][state] table, else nullptr
   FusedOperand g[2];               // gathered operands over deferred cherries (type 0: the op's kind says it all)
+  int unstored;                    // kind 3: the parent is not stored (pllhip_fused_unstored) -- its CLV stores go to the sink
+  double * keep[2];                // ... and its two factor tables are also written here (the pool: deferred.hip)
 };
 
 // The plan as the kernel reads it, through the scalar data cache: ONE 64-byte record per op (one
@@ -102,6 +104,7 @@ static_assert(sizeof(FusedRec) == 64, "sixteen words per op");
 #define PLLHIP_FUSED_RCNT 32u
 #define PLLHIP_FUSED_STAGE_SHIFT 6     /* two bits: matrices op + 1 needs (2 both, 1 right only, 0 none) */
 #define PLLHIP_FUSED_RELOAD_NEXT 256u  /* op + 1 reloads operands: FusedSrc number `src` */
+#define PLLHIP_FUSED_UNSTORED 512u     /* the parent's CLV stores go to the wave's sink (a pair product: deferred.hip) */
 #define PLLHIP_FUSED_KIND_EDGE 4        /* FusedOp::kind of the edge pseudo-op (never in a record's kind bits) */
 #define PLLHIP_FUSED_MAX_OPS 60000u    /* longer lists run per level */
 // FusedRec::chars -- a wave holds the characters of up to 1024 / (tile sites) tip rows at its tile, 16 bytes per
@@ -137,6 +140,8 @@ struct FusedPairJob
   unsigned long long kind;
   const double * pmat;
   const double * kept;
+  double * copy;                   // not nullptr: every entry is written here as well (an unstored pair product's factor)
+  unsigned long long pad;
 };
 
 unsigned int pllhip_fused_char_batches(const unsigned int * tips, unsigned int count, unsigned int lpr,
@@ -238,6 +243,20 @@ void pllhip_fused_deferral(const FusedGeom & geom, const pllhip_op_t * ops, unsi
 // overwrites it with an ordinary op (dd.dropped).  ONE rule for pllhip_update_partials and pllhip_fused_plan_dry_edge.
 bool pllhip_fused_edge_end_stored(const FusedGeom & geom, const FusedDeferral & dd, unsigned int clv,
                                   bool deferred_before, bool pinned);
+// Which gathered-gathered (kind 3) parents of a planned list are left UNSTORED (pair products: deferred.hip).  The
+// value needs no other CLV -- two factor tables, tip rows, the op's own counts -- so it can be formed later, and in a
+// full traversal nothing reads the bytes: the one reader takes the value from the wave's slot.  An op qualifies if
+//   - the list treats its parent the way a tree does (the cherries' rule): written once, read only afterwards and with
+//     the op's own scale buffer or none, that buffer written by no other op and read with no other CLV, not pinned;
+//   - the finished plan keeps the parent in a slot, and no op of the plan reloads it from HBM;
+//   - it is read by at least one op of the list (a last op, a root, is stored);
+//   - it is not an end of `edge` (the hinted evaluation, folded or not: pllhip_fused_edge_end_stored wants bytes).
+// `ops` / `count`: the list the plans were made of (FusedOp::list_pos).  Sets FusedOp::unstored in `plans`, returns how
+// many.  ONE rule for pllhip_update_partials and pllhip_fused_plan_dry_unstored; the caller decides whether the
+// instance may leave anything unstored at all.
+unsigned int pllhip_fused_unstored(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
+                                   std::vector<std::vector<FusedOp>> & plans, const FusedEdge * edge,
+                                   const unsigned char * pinned);
 // slots per wave with 2 (8 waves per CU) or 3 (12 waves) workgroups per CU
 unsigned int pllhip_fused_slots_for(unsigned int rate_cats, bool rate_scalers, unsigned int workgroups_per_cu);
 unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int workgroups_per_cu);

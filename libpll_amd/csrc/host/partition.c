@@ -893,6 +893,20 @@ void * pll_amd_dev_clv(pll_partition_t * p, unsigned int clv_index)
   return pllhip_dev_clv(pll_amd_priv(p)->ctx, clv_index);
 }
 
+int pll_amd_unstored_stats(pll_partition_t * p, unsigned long long * stats4)
+{
+  int rc = pllhip_unstored_stats(pll_amd_priv(p)->ctx, stats4);
+  if (rc) return pll_amd_fail_hip(rc, "unstored stats");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_set_unstored_pairs(pll_partition_t * p, int on)
+{
+  int rc = pllhip_set_unstored_pairs(pll_amd_priv(p)->ctx, on);
+  if (rc) return pll_amd_fail_hip(rc, "set unstored pairs");
+  return PLL_SUCCESS;
+}
+
 int pll_amd_set_deferral(pll_partition_t * p, int on)
 {
   int rc = pllhip_set_deferral(pll_amd_priv(p)->ctx, on);

@@ -278,6 +278,9 @@ class PllLibrary:
             if hasattr(lib, "pll_amd_deferred_stats"):
                 lib.pll_amd_deferred_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
                 lib.pll_amd_set_deferral.argtypes = [_PP, C.c_int]
+            if hasattr(lib, "pll_amd_set_unstored_pairs"):
+                lib.pll_amd_set_unstored_pairs.argtypes = [_PP, C.c_int]
+                lib.pll_amd_unstored_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
                 lib.pll_amd_dev_clv.argtypes = [_PP, C.c_uint]
                 lib.pll_amd_dev_clv.restype = C.c_void_p
             if hasattr(lib, "pll_amd_set_edge_fold"):
@@ -998,6 +1001,16 @@ class Partition:
     def set_deferral(self, on):
         """False: every tip-tip op of a 4-state whole-list launch is run and stored (the eager path)."""
         self._check(self.lib.pll_amd_set_deferral(self.ptr, 1 if on else 0), "pll_amd_set_deferral")
+
+    def set_unstored_pairs(self, on):
+        """False: the parent of every gathered-gathered op of a 4-state whole-list launch is stored (pll_amd.h)."""
+        self._check(self.lib.pll_amd_set_unstored_pairs(self.ptr, 1 if on else 0), "pll_amd_set_unstored_pairs")
+
+    def unstored_stats(self):
+        """{unstored_now, ops_unstored, launches, materialised} of the 4-state pair products (pll_amd.h)."""
+        buf = (C.c_ulonglong * 4)()
+        self._check(self.lib.pll_amd_unstored_stats(self.ptr, buf), "pll_amd_unstored_stats")
+        return dict(zip(("unstored_now", "ops_unstored", "launches", "materialised"), (int(v) for v in buf)))
 
     def set_edge_fold(self, on):
         """False: the whole-list launch never forms edge lnL terms; every evaluation reads both CLVs (pll_amd.h)."""
