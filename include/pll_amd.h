@@ -1182,6 +1182,12 @@ PLL_EXPORT int pll_amd_set_deferral(pll_partition_t * partition, int on);
  * launches, CLVs materialised}. */
 PLL_EXPORT int pll_amd_set_unstored_pairs(pll_partition_t * partition, int on);
 PLL_EXPORT int pll_amd_unstored_stats(pll_partition_t * partition, unsigned long long * stats4);
+/* Folded pair products (pllhip.h: pllhip_set_pair_fold): an unstored parent with exactly one reader, an inner-inner op,
+ * is not walked by the whole-list launch at all; its reader forms it from the two gathered factors.  0: such parents
+ * are walked again; 1: the default.  stats4: {CLVs folded now, ops folded in total, lists planned a second time,
+ * folded CLVs materialised}. */
+PLL_EXPORT int pll_amd_set_pair_fold(pll_partition_t * partition, int on);
+PLL_EXPORT int pll_amd_pair_fold_stats(pll_partition_t * partition, unsigned long long * stats4);
 /* Edge log-likelihood terms from the 4-state whole-list launch (pllhip.h: pllhip_set_edge_fold): after
  * pll_compute_edge_loglikelihood at an inner-inner edge, the next pll_update_partials that writes one of the edge's two
  * CLVs also forms the edge's per-site terms, and the same evaluation then only sums them -- bit for bit the value it

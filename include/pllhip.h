@@ -264,6 +264,26 @@ PLLHIP_EXPORT int pllhip_deferred_stats(pllhip_ctx_t * ctx, unsigned long long *
  * pllhip_deferred_stats keeps counting cherries only. */
 PLLHIP_EXPORT int pllhip_set_unstored_pairs(pllhip_ctx_t * ctx, int on);
 PLLHIP_EXPORT int pllhip_unstored_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+/* Folded pair products.  An unstored parent that exactly one op of the list reads, an inner-inner op, is not walked at
+ * all: the list is planned once more without it, and its reader forms the product -- the same two multiplications and
+ * the same scaling test -- from the two gathered factors at the top of its own op.  Such a parent is an unstored pair
+ * product like the others (pllhip_unstored_stats counts it) whose counts are not in HBM either: the launch that stores
+ * it on demand forms the scale bits and writes them.  A reader whose other operand is a single gathered factor is not
+ * folded into.  pllhip_set_pair_fold(ctx, 0): every unstored parent is walked again; 1: the default; off whenever
+ * pllhip_set_unstored_pairs or pllhip_set_deferral is.  pllhip_pair_fold_stats: {CLVs folded now, ops folded in total,
+ * lists planned a second time, folded CLVs materialised}. */
+PLLHIP_EXPORT int pllhip_set_pair_fold(pllhip_ctx_t * ctx, int on);
+PLLHIP_EXPORT int pllhip_pair_fold_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+/* pllhip_fused_plan_dry_unstored followed by the fold (pllhip_set_pair_fold): the outputs describe the FINAL walk.
+ * folded_out[i] = 1: op i of the list is not walked, its reader forms the product; operands_out: 0 a slot, 1 a tip, 2 a
+ * deferred cherry, 3 a folded product; unstored_out: walked ops whose parent is not stored. */
+PLLHIP_EXPORT int pllhip_fused_plan_dry_folded(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                               int pattern_tip, unsigned int rate_cats, const pllhip_op_t * ops,
+                                               unsigned int count, unsigned int nslots, const unsigned char * pinned,
+                                               const int * edge4, unsigned int * nkept, unsigned int * order_out,
+                                               int * slots_out, int * operands_out, unsigned char * deferred_out,
+                                               unsigned int * reloads_out, unsigned char * unstored_out,
+                                               unsigned char * folded_out);
 
 /* Edge log-likelihood terms from the 4-state whole-list launch.  pllhip_edge_loglikelihood remembers an inner-inner
  * request; the next pllhip_update_partials that runs as ONE whole-list launch and writes one of the edge's two CLVs

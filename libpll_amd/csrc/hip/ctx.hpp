@@ -121,6 +121,8 @@ struct pllhip_ctx
   {
     bool on = false;
     bool pair = false;                   // a pair product: rows[] and the pool's two tables; else a cherry: tip1, tip2
+    bool folded = false;                 // a pair product FOLDED into its reader (not walked): its counts are not in HBM
+                                         // either -- the materialising launch forms the scale bits and writes them
     unsigned int tip1 = 0, tip2 = 0;
     unsigned int rows[4] = {0, 0, 0, 0}; // tip index + 1 of each table's two rows (0: none -- code 0)
     int scaler = -1;
@@ -134,6 +136,10 @@ struct pllhip_ctx
   unsigned int defer_pool_tables = 0;          // 2: a cherry's T or a pair product's Fa, Fb; 1 (no room for two): cherries only
   bool defer_pool_failed = false;
   bool unstored_pairs = true;                  // pllhip_set_unstored_pairs
+  bool pair_fold = true;                       // pllhip_set_pair_fold: unstored parents with one reader are not walked
+  unsigned int n_folded = 0;                   // ... the folded ones among the pair products
+  unsigned int fused_last_nfolded = 0;         // ops the kept plan folds (not walked)
+  unsigned long long fold_stats[4] = {0, 0, 0, 0}; // folded now (filled on read), ops folded, lists planned twice, CLVs materialised
   std::vector<unsigned int> fused_last_unstored; // the kept plan's pair products: {clv, scaler + 1, rows[4]} each
   unsigned long long unstored_stats[4] = {0, 0, 0, 0}; // the same four numbers for pair products
   bool cherry_deferral = true;                        // pllhip_set_deferral (0: the eager path, for A/B and tests)

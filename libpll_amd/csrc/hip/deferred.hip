@@ -16,6 +16,11 @@
 // table launch writes them next to the ones the kernel gathers from: the same values), their tip rows and the op's
 // counts, which ARE in HBM: a gathered operand inherits none, so a count is 0 or 1 and is the scale bit.  The same
 // launch as for cherries forms it on demand with the kernel's own two multiplications.
+//
+// Folded pair products (pllhip_set_pair_fold): such a parent with exactly one reader is not even walked --
+// the reader forms the product in registers (partials_fused.hip, step()).  Its counts were never stored either, so the
+// launch here runs the scaling test itself -- every entry of the site below the threshold, the op's own scale buffer
+// permitting -- and WRITES the counts with the CLV.
 #include <algorithm>
 
 #include "ctx.hpp"
@@ -34,6 +39,7 @@ struct DeferredJobs
   const pll_v2d * tab2[PLLHIP_DEFER_BATCH];
   const unsigned char * c3[PLLHIP_DEFER_BATCH];
   const unsigned char * c4[PLLHIP_DEFER_BATCH];
+  unsigned char folded[PLLHIP_DEFER_BATCH]; // a pair product whose counts are FORMED and written (never walked)
 };
 static_assert(sizeof(DeferredJobs) <= 3900, "the jobs travel as kernel arguments");
 
@@ -53,6 +59,7 @@ __global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs,
   {
     const unsigned char * __restrict__ c3 = jobs.c3[blockIdx.y];
     const unsigned char * __restrict__ c4 = jobs.c4[blockIdx.y];
+    const bool folded = jobs.folded[blockIdx.y] != 0;
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
     {
       const size_t n = t / span2;
@@ -60,8 +67,20 @@ __global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs,
       const unsigned int pa = ((c1 ? (unsigned int)(c1[n] & 15u) : 0u) << 4) | (c2 ? (unsigned int)(c2[n] & 15u) : 0u);
       const unsigned int pb = ((c3 ? (unsigned int)(c3[n] & 15u) : 0u) << 4) | (c4 ? (unsigned int)(c4[n] & 15u) : 0u);
       const pll_v2d a = tab[(size_t)pa * span2 + g], b = tab2[(size_t)pb * span2 + g];
+      bool scale = counts && !folded && counts[n * count_words];
+      if (folded && counts)
+      {
+        // (partials_fused.hip, step(): all 2 x span2 entries of the site below the threshold.  The span2 lanes of a site
+        // are neighbours in a wave, aligned -- span2 is 2, 4 or 8, t = n * span2 + g, the stride a multiple of 256 --
+        // and run this loop together: each judges its own two products, a butterfly joins them; lane 0 of the site
+        // stores the count)
+        int small = (a.x * b.x < PLLHIP_SCALE_THRESHOLD) && (a.y * b.y < PLLHIP_SCALE_THRESHOLD) ? 1 : 0;
+        for (unsigned int m = 1; m < span2; m <<= 1) small &= __shfl_xor(small, (int)m, 64);
+        scale = small != 0;
+        if (g == 0) counts[n * count_words] = scale ? 1u : 0u;
+      }
       // (partials_fused.hip, step(): q = x * y, then q *= 2^256 or 1.0)
-      const double factor = __hiloint2double((counts && counts[n * count_words]) ? 0x4ff00000 : 0x3ff00000, 0);
+      const double factor = __hiloint2double(scale ? 0x4ff00000 : 0x3ff00000, 0);
       pll_v2d v = {a.x * b.x, a.y * b.y};
       v.x *= factor;
       v.y *= factor;
@@ -114,7 +133,8 @@ static void deferred_clear(pllhip_ctx * c, unsigned int idx)
   d.on = false;
   --c->n_deferred;
   if (d.pair) --c->n_unstored;
-  d.pair = false;
+  if (d.folded) --c->n_folded;
+  d.pair = d.folded = false;
   ++c->defer_epoch;
 }
 
@@ -143,7 +163,7 @@ int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
   const size_t total = (size_t)c->sh.sites * span2;
   const unsigned int gx = (unsigned int)std::min<size_t>(std::max<size_t>(1, (total + 255) / 256), (size_t)c->num_cus * 8);
   const bool nt = pllhip_use_nt(c);
-  size_t npairs = 0;
+  size_t npairs = 0, nfolded = 0;
   for (size_t first = 0; first < todo.size(); first += PLLHIP_DEFER_BATCH)
   {
     const unsigned int m = (unsigned int)std::min<size_t>(PLLHIP_DEFER_BATCH, todo.size() - first);
@@ -166,6 +186,8 @@ int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
         jobs.c2[k] = rows[1];
         jobs.c3[k] = rows[2];
         jobs.c4[k] = rows[3];
+        jobs.folded[k] = d.folded ? 1 : 0;
+        if (d.folded) ++nfolded;
         ++npairs;
         continue;
       }
@@ -182,6 +204,7 @@ int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
   for (unsigned int i : todo) deferred_clear(c, i);
   c->defer_stats[3] += todo.size() - npairs;
   c->unstored_stats[3] += npairs;
+  c->fold_stats[3] += nfolded;
   return 0;
 }
 
@@ -224,6 +247,36 @@ extern "C" int pllhip_set_unstored_pairs(pllhip_ctx_t * c, int on)
   }
   c->unstored_pairs = on != 0;
   ++c->defer_epoch;
+  return 0;
+}
+
+// Folding pair products into their readers on or off (A/B, tests); off stores no CLV -- a folded parent stays what
+// it is, an unstored pair product whose counts the materialising launch writes -- but ends the kept plan.
+extern "C" int pllhip_set_pair_fold(pllhip_ctx_t * c, int on)
+{
+  pllhip_edge_terms_drop(c);
+  PLLHIP_ALL_SHARDS(c, pllhip_set_pair_fold(s, on));
+  if (c->pair_fold == (on != 0)) return 0;
+  c->pair_fold = on != 0;
+  ++c->defer_epoch;
+  return 0;
+}
+
+// {CLVs folded now, ops folded in total, lists planned a second time, folded CLVs materialised}
+extern "C" int pllhip_pair_fold_stats(pllhip_ctx_t * c, unsigned long long * out4)
+{
+  for (int t = 0; t < 4; ++t) out4[t] = 0;
+  if (!c->shards.empty())
+  {
+    for (pllhip_ctx * s : c->shards)
+    {
+      out4[0] += s->n_folded;
+      for (int t = 1; t < 4; ++t) out4[t] += s->fold_stats[t];
+    }
+    return 0;
+  }
+  out4[0] = c->n_folded;
+  for (int t = 1; t < 4; ++t) out4[t] = c->fold_stats[t];
   return 0;
 }
 

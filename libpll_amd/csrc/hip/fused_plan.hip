@@ -190,6 +190,13 @@ static int assign_slots_reload(const FusedGeom & geom, const pllhip_op_t * ops, 
     {
       f.g[0] = extra[i].g[0];
       f.g[1] = extra[i].g[1];
+      for (int s = 0; s < 2; ++s)
+      {
+        f.g2[s] = extra[i].g2[s];
+        f.prod[s] = extra[i].prod[s];
+        f.pkeep[s][0] = extra[i].pkeep[s][0];
+        f.pkeep[s][1] = extra[i].pkeep[s][1];
+      }
     }
   }
   if (edge)
@@ -576,6 +583,7 @@ unsigned int pllhip_fused_unstored(const FusedGeom & geom, const pllhip_op_t * o
     {
       f.unstored = 0;
       if (f.kind != 3 || f.pslot < 0 || f.list_pos < 0 || (unsigned int)f.list_pos >= count) continue;
+      if (f.prod[0] || f.prod[1]) continue; // (a reader of folded products: its value needs the whole mat-vec)
       const unsigned int k = (unsigned int)f.list_pos;
       const pllhip_op_t & op = ops[k];
       const unsigned int p = op.parent_clv;
@@ -596,6 +604,124 @@ unsigned int pllhip_fused_unstored(const FusedGeom & geom, const pllhip_op_t * o
       ++n;
     }
   return n;
+}
+
+// Which unstored pair products are folded into their reader (partials_fused.hpp).
+unsigned int pllhip_fused_fold(const pllhip_op_t * ops, const int * kinds, unsigned int count,
+                               const std::vector<std::vector<FusedOp>> & plans, std::vector<unsigned char> & fold)
+{
+  fold.assign(count, 0);
+  // how often each CLV is read in the list, and by whom last: one pass
+  unsigned int nclv = 0;
+  for (unsigned int r = 0; r < count; ++r)
+    nclv = std::max(nclv, std::max(ops[r].parent_clv, std::max(ops[r].child1_clv, ops[r].child2_clv)) + 1u);
+  std::vector<unsigned int> reads(nclv, 0);
+  std::vector<int> reader(nclv, -1);
+  for (unsigned int r = 0; r < count; ++r)
+  {
+    ++reads[ops[r].child1_clv];
+    ++reads[ops[r].child2_clv];
+    reader[ops[r].child1_clv] = reader[ops[r].child2_clv] = (int)r;
+  }
+  unsigned int n = 0;
+  for (const auto & plan : plans)
+    for (const FusedOp & f : plan)
+    {
+      if (!f.unstored || f.kind != 3 || f.list_pos < 0 || (unsigned int)f.list_pos >= count) continue;
+      const unsigned int k = (unsigned int)f.list_pos, p = ops[k].parent_clv;
+      // (pllhip_fused_unstored: written once, read only behind op k)
+      if (reads[p] != 1 || reader[p] <= (int)k || kinds[reader[p]] != 0) continue;
+      fold[k] = 1;
+      ++n;
+    }
+  // (a list kernel walks at least two ops)
+  if (n && count - n < 2)
+  {
+    fold.assign(count, 0);
+    n = 0;
+  }
+  return n;
+}
+
+void pllhip_fused_fold_list(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
+                            const FusedExtra * extras, const unsigned int * rows4, unsigned int count,
+                            const std::vector<unsigned char> & fold, FusedFoldList & out)
+{
+  out.where.clear();
+  out.ops.clear();
+  out.args.clear();
+  out.kinds.clear();
+  out.extras.clear();
+  out.rows8.clear();
+  out.prod_op.clear();
+  out.as_tip.assign(geom.nclv, 0);
+  for (size_t i = 0; geom.as_tip && i < geom.nclv; ++i) out.as_tip[i] = geom.as_tip[i];
+  std::vector<int> folded_by(geom.nclv, -1); // per CLV: the folded op that forms it
+  for (unsigned int k = 0; k < count; ++k)
+    if (fold[k])
+    {
+      folded_by[ops[k].parent_clv] = (int)k;
+      out.as_tip[ops[k].parent_clv] = 1;
+    }
+  for (unsigned int i = 0; i < count; ++i)
+  {
+    if (fold[i]) continue;
+    const pllhip_op_t & op = ops[i];
+    PartialsArgs a = args[i];
+    int kind = kinds[i];
+    FusedExtra x;
+    memset(&x, 0, sizeof(x));
+    if (extras)
+    {
+      x.g[0] = extras[i].g[0];
+      x.g[1] = extras[i].g[1];
+    }
+    unsigned int rows[8] = {0, 0, 0, 0, 0, 0, 0, 0}, from[2] = {0, 0};
+    for (int t = 0; rows4 && t < 4; ++t) rows[t] = rows4[4 * (size_t)i + t];
+    const int f1 = kind == 0 ? folded_by[op.child1_clv] : -1, f2 = kind == 0 ? folded_by[op.child2_clv] : -1;
+    // side `to` of the reader becomes the product op f forms; sc: the scale buffer the reader passes with it
+    auto product = [&](int to, int f, int sc) {
+      if (extras)
+      {
+        x.g[to] = extras[f].g[0];
+        x.g2[to] = extras[f].g[1];
+      }
+      x.prod[to] = 1 | (ops[f].parent_scaler >= 0 ? 2 : 0) | (sc >= 0 ? 4 : 0);
+      from[to] = (unsigned int)f + 1;
+      for (int t = 0; rows4 && t < 4; ++t) rows[4 * to + t] = rows4[4 * (size_t)f + t];
+    };
+    if (f1 >= 0 && f2 >= 0)
+    {
+      // both operands are products: no inner operand at all -- gathered-gathered to the planner
+      kind = 3;
+      product(0, f1, op.child1_scaler);
+      product(1, f2, op.child2_scaler);
+      a.left = a.right = nullptr;
+      a.lscaler = a.rscaler = nullptr;
+    }
+    else if (f1 >= 0 || f2 >= 0)
+    {
+      // the product plays the tip of a tip-inner op: "left" (x * y is y * x bit for bit)
+      kind = 1;
+      product(0, f1 >= 0 ? f1 : f2, f1 >= 0 ? op.child1_scaler : op.child2_scaler);
+      if (f1 < 0)
+      {
+        a.right = args[i].left;
+        a.rscaler = args[i].lscaler;
+        a.lmat = args[i].rmat;
+        a.rmat = args[i].lmat;
+      }
+      a.left = nullptr;
+      a.lscaler = nullptr;
+    }
+    out.where.push_back(i);
+    out.ops.push_back(op);
+    out.args.push_back(a);
+    out.kinds.push_back(kind);
+    out.extras.push_back(x);
+    out.rows8.insert(out.rows8.end(), rows, rows + 8);
+    out.prod_op.insert(out.prod_op.end(), from, from + 2);
+  }
 }
 
 int pllhip_fused_plan_segments(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
@@ -922,7 +1048,7 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
                              unsigned int * reloads_out, unsigned int * materialise_out,
                              unsigned int * nmaterialise, unsigned int * dropped_out, unsigned int * ndropped,
                              const int * edge4, unsigned int rate_cats, int * edge_out,
-                             unsigned char * unstored_out = nullptr)
+                             unsigned char * unstored_out = nullptr, unsigned char * folded_out = nullptr)
 {
   FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
   if (dry_ops_in_range("pllhip_fused_plan_dry_deferred", geom, ops, count)) return -1;
@@ -954,8 +1080,9 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
   // (what is materialised first is an ordinary buffer to the list)
   for (unsigned int i : d.materialise) d.as_tip[i] = 0;
   geom.as_tip = d.as_tip.data();
-  const unsigned int n = (unsigned int)kept.size();
+  unsigned int n = (unsigned int)kept.size();
   if (nkept) *nkept = n;
+  for (unsigned int i = 0; folded_out && i < count; ++i) folded_out[i] = 0;
   std::vector<PartialsArgs> args(n);
   std::vector<int> kinds(n), opnd(2 * (size_t)n);
   for (unsigned int i = 0; i < n; ++i) dry_resolve(geom, kept[i], args[i], kinds[i], &opnd[2 * i]);
@@ -995,6 +1122,44 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
   if (unstored_out)
   {
     pllhip_fused_unstored(geom, kept.data(), n, lp.plans, edge4 ? &e : nullptr, pinned);
+    // Folded pair products (pllhip_fused_plan_dry_folded): the live path's steps -- the fold rule on the finished plan,
+    // the list without the folded ops planned once more by the same driver, the unstored rule on what is left.  A
+    // second plan the planner refuses leaves the first.
+    std::vector<unsigned char> fold;
+    FusedFoldList fl;
+    if (folded_out && pllhip_fused_fold(kept.data(), kinds.data(), n, lp.plans, fold))
+    {
+      pllhip_fused_fold_list(geom, kept.data(), args.data(), kinds.data(), nullptr, nullptr, n, fold, fl);
+      FusedGeom geom2 = geom;
+      geom2.as_tip = fl.as_tip.data();
+      FusedListPlan lp2;
+      const unsigned int n2 = (unsigned int)fl.ops.size();
+      if (pllhip_fused_plan_list(geom2, fl.ops.data(), fl.args.data(), fl.kinds.data(), fl.extras.data(), n2, 1, slot_counts,
+                                 derived ? 2u : 1u, edge4 ? &e : nullptr, d, lp2) == 0)
+      {
+        pllhip_fused_unstored(geom2, fl.ops.data(), n2, lp2.plans, edge4 ? &e : nullptr, pinned);
+        std::vector<unsigned int> where2(n2);
+        std::vector<int> opnd2(2 * (size_t)n2);
+        for (unsigned int j = 0; j < n2; ++j)
+        {
+          const unsigned int o = fl.where[j];
+          where2[j] = where[o];
+          opnd2[2 * j] = fl.as_tip[kept[o].child1_clv] && !geom.is_tip(kept[o].child1_clv) ? 3 : opnd[2 * o];
+          opnd2[2 * j + 1] = fl.as_tip[kept[o].child2_clv] && !geom.is_tip(kept[o].child2_clv) ? 3 : opnd[2 * o + 1];
+        }
+        for (unsigned int k = 0; k < n; ++k)
+          if (fold[k]) folded_out[where[k]] = 1;
+        lp.plans.swap(lp2.plans);
+        lp.nslots = lp2.nslots;
+        lp.taken = lp2.taken;
+        lp.reloads = lp2.reloads;
+        lp.folded = lp2.folded;
+        where.swap(where2);
+        opnd.swap(opnd2);
+        n = n2;
+        if (nkept) *nkept = n;
+      }
+    }
     for (const FusedOp & f : lp.plans[0])
       if (f.unstored) unstored_out[where[f.list_pos]] = 1;
   }
@@ -1082,6 +1247,29 @@ extern "C" int pllhip_fused_plan_dry_unstored(unsigned int tips, unsigned int cl
   return plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, nslots, nullptr, nullptr, pinned, nkept,
                            order_out, slots_out, operands_out, deferred_out, reloads_out, nullptr, nullptr, nullptr, nullptr,
                            edge4, rate_cats, edge_out, unstored_out);
+}
+
+// The same with folded pair products (pllhip_set_pair_fold; tests/test_host_pair_fold_plan.py): after the steps of
+// pllhip_fused_plan_dry_unstored, pllhip_fused_fold picks the unstored parents with exactly one reader, an inner-inner
+// op, and the list is planned once more without them.  The outputs describe that final walk: folded_out[i] = 1: op i of
+// the caller's list is not walked, its reader forms the product; operands_out: 0 a slot, 1 a tip, 2 a deferred cherry,
+// 3 a folded product; unstored_out: the walked ops whose parent is not stored.
+extern "C" int pllhip_fused_plan_dry_folded(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                            int pattern_tip, unsigned int rate_cats, const pllhip_op_t * ops, unsigned int count,
+                                            unsigned int nslots, const unsigned char * pinned, const int * edge4,
+                                            unsigned int * nkept, unsigned int * order_out, int * slots_out,
+                                            int * operands_out, unsigned char * deferred_out, unsigned int * reloads_out,
+                                            unsigned char * unstored_out, unsigned char * folded_out)
+{
+  if (!(rate_cats == 1 || rate_cats == 2 || rate_cats == 4) || !unstored_out || !folded_out)
+  {
+    pllhip_set_error("pllhip_fused_plan_dry_folded: rate_cats of an instance that defers, unstored_out and folded_out");
+    return -1;
+  }
+  int edge_out[8];
+  return plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, nslots, nullptr, nullptr, pinned, nkept,
+                           order_out, slots_out, operands_out, deferred_out, reloads_out, nullptr, nullptr, nullptr, nullptr,
+                           edge4, rate_cats, edge_out, unstored_out, folded_out);
 }
 
 // The planner alone (tests/test_host.py, tools): which order and how many
@@ -1177,29 +1365,27 @@ extern "C" int pllhip_aa_list_plan_dry(unsigned int tips, unsigned int clv_buffe
 // both rows of an op into the same batch.  tips[pos]: bit 0 / 1 = the op has a left / right tip.  Out, per op:
 // chars (PLLHIP_FUSED_CH_LPOS / RPOS = first lane of the row, CH_LTIP / CH_RTIP) and the batch its rows are in
 // (an op without tips: the batch current at that point).  Returns the number of batches.  Pure host logic.
-unsigned int pllhip_fused_char_batches4(const unsigned int * tips, unsigned int count, unsigned int lpr,
-                                        unsigned int * chars_out, unsigned int * chars2_out, unsigned int * batch_out)
+unsigned int pllhip_fused_char_batches8(const unsigned int * tips, unsigned int count, unsigned int lpr,
+                                        unsigned int * const chars_out[4], unsigned int * batch_out)
 {
   const unsigned int rpb = 64 / lpr; // rows per batch
   unsigned int batch = 0, q = 0;
   for (unsigned int pos = 0; pos < count; ++pos)
   {
-    const unsigned int n = (tips[pos] & 1u) + ((tips[pos] >> 1) & 1u) + ((tips[pos] >> 2) & 1u) + ((tips[pos] >> 3) & 1u);
+    unsigned int n = 0;
+    for (int b = 0; b < 8; ++b) n += (tips[pos] >> b) & 1u;
     if (q + n > rpb)
     {
       ++batch;
       q = 0;
     }
     batch_out[pos] = batch;
-    chars_out[pos] = 0;
-    if (tips[pos] & 1u) chars_out[pos] |= PLLHIP_FUSED_CH_LTIP | (q++ * lpr);
-    if (tips[pos] & 2u) chars_out[pos] |= PLLHIP_FUSED_CH_RTIP | (q++ * lpr) << 8;
-    // (the rows of a second gather -- an op with two gathered operands -- lie in the same batch)
-    if (chars2_out)
+    // (all the rows of an op lie in one batch, in the order of its gathers)
+    for (int k = 0; k < 4 && chars_out[k]; ++k)
     {
-      chars2_out[pos] = 0;
-      if (tips[pos] & 4u) chars2_out[pos] |= PLLHIP_FUSED_CH_LTIP | (q++ * lpr);
-      if (tips[pos] & 8u) chars2_out[pos] |= PLLHIP_FUSED_CH_RTIP | (q++ * lpr) << 8;
+      chars_out[k][pos] = 0;
+      if (tips[pos] & (1u << (2 * k))) chars_out[k][pos] |= PLLHIP_FUSED_CH_LTIP | (q++ * lpr);
+      if (tips[pos] & (2u << (2 * k))) chars_out[k][pos] |= PLLHIP_FUSED_CH_RTIP | (q++ * lpr) << 8;
     }
   }
   return batch + 1;
@@ -1208,7 +1394,11 @@ unsigned int pllhip_fused_char_batches4(const unsigned int * tips, unsigned int 
 unsigned int pllhip_fused_char_batches(const unsigned int * tips, unsigned int count, unsigned int lpr,
                                        unsigned int * chars_out, unsigned int * batch_out)
 {
-  return pllhip_fused_char_batches4(tips, count, lpr, chars_out, nullptr, batch_out);
+  // (two rows per op: bits 0 / 1 of tips[pos] only)
+  std::vector<unsigned int> two(tips, tips + count);
+  for (unsigned int & t : two) t &= 3u;
+  unsigned int * const out[4] = {chars_out, nullptr, nullptr, nullptr};
+  return pllhip_fused_char_batches8(two.data(), count, lpr, out, batch_out);
 }
 
 extern "C" unsigned int pllhip_fused_char_batches_dry(const unsigned int * tips, unsigned int count, unsigned int rate_cats,

@@ -906,6 +906,7 @@ static int update_partials_dna_list(pllhip_ctx * c, const pllhip_op_t * full_ops
     pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
     c->defer_stats[1] += c->fused_last_deferred.size() / 4;
     c->unstored_stats[1] += c->fused_last_unstored.size() / 6;
+    c->fold_stats[1] += c->fused_last_nfolded;
     const int rc = pllhip_relaunch_fused(c);
     if (rc == 0 && c->fused_last_edge)
     {
@@ -976,25 +977,106 @@ static int update_partials_dna_list(pllhip_ctx * c, const pllhip_op_t * full_ops
   if (rc < 0) return rc;
   // Pair products (deferred.hip): the gathered-gathered parents the finished plan lets go unstored, where the instance
   // defers at all (a kind-3 op exists only then) and the pool has the two tables each needs.
-  if (rc == 0 && extras && c->unstored_pairs && c->cherry_deferral && pllhip_deferred_table(c, 0, 1) &&
-      pllhip_fused_unstored(geom, ops, count, lp.plans, edge_ok ? &fedge : nullptr, c->clv_pinned.data()))
+  unsigned int nunstored = 0, nfolded = 0;
+  if (rc == 0 && extras && c->unstored_pairs && c->cherry_deferral && pllhip_deferred_table(c, 0, 1))
+    nunstored = pllhip_fused_unstored(geom, ops, count, lp.plans, edge_ok ? &fedge : nullptr, c->clv_pinned.data());
+  // Folded pair products (pllhip_set_pair_fold; partials_fused.hpp: pllhip_fused_fold): an unstored parent with one
+  // reader, an inner-inner op, is not walked at all -- the list is planned once more without those ops, their readers'
+  // operands on that side products of two gathered factors, and the unstored rule applied to what is left.  A second
+  // plan the planner refuses, or one of fewer than two ops, leaves the first.
+  std::vector<unsigned char> fold;
+  FusedFoldList fl;
+  FusedListPlan first_lp;
+  FusedEdge first_edge = fedge;
+  const pllhip_op_t * wops = ops;      // the ops the plan was made of, and their rows (stride wstride)
+  const unsigned int * wrows = k.rows.data();
+  size_t wstride = 4;
+  if (nunstored && c->pair_fold && pllhip_fused_fold(ops, kinds.data(), count, lp.plans, fold))
+  {
+    pllhip_fused_fold_list(geom, ops, args.data(), kinds.data(), extras, k.rows.data(), count, fold, fl);
+    const unsigned int n2 = (unsigned int)fl.ops.size();
+    for (unsigned int j = 0; j < n2; ++j)
+      for (int s = 0; s < 2; ++s)
+        if (fl.prod_op[2 * (size_t)j + s])
+        {
+          const unsigned int clv = ops[fl.prod_op[2 * (size_t)j + s] - 1].parent_clv;
+          fl.extras[j].pkeep[s][0] = pllhip_deferred_table(c, clv, 0);
+          fl.extras[j].pkeep[s][1] = pllhip_deferred_table(c, clv, 1);
+        }
+    FusedGeom geom2 = geom;
+    geom2.as_tip = fl.as_tip.data();
+    FusedListPlan lp2;
+    FusedEdge fedge2 = fedge;
+    // (the edge epilogue where the first plan was offered it: a list in segments stays without, however short its
+    // segments have become)
+    const bool edge2 = edge_ok && lp.plans.size() == 1;
+    const int rc2 = n2 < 2 ? 1 : pllhip_fused_plan_list(geom2, fl.ops.data(), fl.args.data(), fl.kinds.data(), fl.extras.data(), n2,
+                                                        max_segs, slot_counts + skip, 2u - skip, edge2 ? &fedge2 : nullptr, k.dd, lp2);
+    if (rc2 < 0) return rc2;
+    if (rc2 == 0)
+    {
+      // (the first plan is kept: should the launch not take the second -- more character batches or tables than it
+      // encodes --, the list runs as it would have without folding)
+      first_lp = lp;
+      first_edge = fedge;
+      lp.plans.swap(lp2.plans);
+      lp.nslots = lp2.nslots;
+      lp.taken = lp2.taken;
+      lp.reloads = lp2.reloads;
+      lp.folded = lp2.folded;
+      fedge = fedge2;
+      wops = fl.ops.data();
+      wrows = fl.rows8.data();
+      wstride = 8;
+      nunstored = pllhip_fused_unstored(geom2, wops, n2, lp.plans, edge_ok ? &fedge : nullptr, c->clv_pinned.data());
+      for (unsigned int i = 0; i < count; ++i)
+        if (fold[i])
+        {
+          // (a folded parent is an unstored pair product whose counts are not in HBM either: bit 31 of the scaler word)
+          const pllhip_op_t & op = ops[i];
+          const unsigned int * rows = &k.rows[4 * (size_t)i];
+          k.new_unstored.insert(k.new_unstored.end(), {op.parent_clv, (unsigned int)(op.parent_scaler + 1) | 0x80000000u, rows[0], rows[1], rows[2], rows[3]});
+          ++nfolded;
+        }
+    }
+  }
+  // the walked parents the plan leaves unstored: where their tables are kept, and what the context remembers of them
+  auto keep_unstored = [&]() {
     for (auto & plan : lp.plans)
       for (FusedOp & f : plan)
         if (f.unstored)
         {
-          const pllhip_op_t & op = ops[f.list_pos];
+          const pllhip_op_t & op = wops[f.list_pos];
           f.keep[0] = pllhip_deferred_table(c, op.parent_clv, 0);
           f.keep[1] = pllhip_deferred_table(c, op.parent_clv, 1);
-          const unsigned int * rows = &k.rows[4 * (size_t)f.list_pos];
+          const unsigned int * rows = &wrows[wstride * (size_t)f.list_pos];
           k.new_unstored.insert(k.new_unstored.end(), {op.parent_clv, (unsigned int)(op.parent_scaler + 1), rows[0], rows[1], rows[2], rows[3]});
         }
+  };
+  if (nunstored) keep_unstored();
   if (rc == 0)
   {
     pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
     // (the hint the plan stands for; the launch takes the frequencies' places from it)
     c->fused_last_hint_on = edge_wanted;
     c->fused_last_hint = c->edge_hint;
+    c->fused_last_nfolded = nfolded; // (the launch sizes its share of counter tiles by the list the caller handed over)
     rc = pllhip_launch_fused(c, lp.plans, lp.nslots, k.keep_jobs.empty() ? nullptr : &k.keep_jobs, lp.folded ? &fedge : nullptr);
+    if (rc == 1 && nfolded)
+    {
+      // the launch does not take the folded plan: the first one, whose unstored marks still stand
+      lp = first_lp;
+      fedge = first_edge;
+      wops = ops;
+      wrows = k.rows.data();
+      wstride = 4;
+      nfolded = 0;
+      k.new_unstored.clear();
+      keep_unstored();
+      c->fused_last_nfolded = 0;
+      rc = pllhip_launch_fused(c, lp.plans, lp.nslots, k.keep_jobs.empty() ? nullptr : &k.keep_jobs, lp.folded ? &fedge : nullptr);
+    }
+    if (rc != 0) c->fused_last_nfolded = 0;
     if (rc == 0)
     {
       if (lp.folded)
@@ -1022,19 +1104,24 @@ static int update_partials_dna_list(pllhip_ctx * c, const pllhip_op_t * full_ops
       for (size_t t = 0; t < k.new_unstored.size(); t += 6)
       {
         const unsigned int clv = k.new_unstored[t];
-        const int sc = (int)k.new_unstored[t + 1] - 1;
+        const int sc = (int)(k.new_unstored[t + 1] & 0x7fffffffu) - 1;
         pllhip_deferred_drop(c, clv);
         pllhip_ctx::deferred_clv & d = c->deferred[clv];
         d.on = d.pair = true;
+        d.folded = (k.new_unstored[t + 1] >> 31) != 0;
+        if (d.folded) ++c->n_folded;
         for (int r = 0; r < 4; ++r) d.rows[r] = k.new_unstored[t + 2 + r];
         d.scaler = sc;
-        // (its counts are in HBM, but they define the CLV: whoever touches them stores it first)
+        // (its counts are in HBM -- a folded product's are not --, but they define the CLV: whoever touches them stores
+        // it first)
         if (sc >= 0) c->deferred_sc_owner[sc] = (int)clv;
         ++c->n_deferred;
         ++c->n_unstored;
       }
       c->defer_stats[1] += k.new_deferred.size() / 4;
       c->unstored_stats[1] += k.new_unstored.size() / 6;
+      c->fold_stats[1] += nfolded;
+      if (nfolded) ++c->fold_stats[2];
       c->fused_last_unstored = k.new_unstored;
       c->fused_last_deferred = k.new_deferred;
       c->fused_last_defer_epoch = c->defer_epoch;

@@ -94,7 +94,8 @@ __device__ __forceinline__ Rec rec_load(const FusedRec * plan, unsigned int i)
 __device__ __forceinline__ unsigned long long rec_quad(const Rec & r, int t) { return (unsigned long long)r.w[t] | ((unsigned long long)r.w[t + 1] << 32); }
 __device__ __forceinline__ unsigned int rec_chars(const Rec & r) { return r.w[0]; }
 __device__ __forceinline__ unsigned int rec_chars2(const Rec & r) { return r.w[1]; }
-__device__ __forceinline__ unsigned int rec_gather2(const Rec & r) { return r.w[2]; }
+__device__ __forceinline__ unsigned int rec_chars3(const Rec & r) { return r.w[2]; }
+__device__ __forceinline__ unsigned int rec_chars4(const Rec & r) { return r.w[3]; }
 __device__ __forceinline__ unsigned int rec_req_lmat(const Rec & r) { return r.w[4]; }
 __device__ __forceinline__ unsigned int rec_req_rmat(const Rec & r) { return r.w[5]; }
 __device__ __forceinline__ unsigned int rec_gather(const Rec & r) { return r.w[6]; }
@@ -452,10 +453,18 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
         asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pt[j]) : "v"(off), "s"(tab) : "memory");
       }
     };
-    auto gather = [&](pll_v2d (&pt)[J], pll_v2d (&pt2)[J], const Rec & r) {
+    // (the tables of one op follow each other in the table buffer: gather k reads k tables behind the first; a third
+    // and a fourth factor -- a right-hand operand that is a folded product, see step() -- always come together)
+    constexpr unsigned int TB = 256u * W * 16u; // bytes of a table
+    auto gather = [&](pll_v2d (&pt)[J], pll_v2d (&pt2)[J], pll_v2d (&pt3)[J], pll_v2d (&pt4)[J], const Rec & r) {
       const unsigned int ch = rec_chars(r), ch2 = rec_chars2(r);
       if (ch & (PLLHIP_FUSED_CH_LTIP | PLLHIP_FUSED_CH_RTIP)) gather_factor(pt, ch, rec_gather(r));
-      if (SECOND && (ch2 & (PLLHIP_FUSED_CH_LTIP | PLLHIP_FUSED_CH_RTIP))) gather_factor(pt2, ch2, rec_gather2(r));
+      if (SECOND && (ch2 & (PLLHIP_FUSED_CH_LTIP | PLLHIP_FUSED_CH_RTIP))) gather_factor(pt2, ch2, rec_gather(r) + TB);
+      if (SECOND && (rec_chars3(r) & (PLLHIP_FUSED_CH_LTIP | PLLHIP_FUSED_CH_RTIP)))
+      {
+        gather_factor(pt3, rec_chars3(r), rec_gather(r) + 2u * TB);
+        gather_factor(pt4, rec_chars4(r), rec_gather(r) + 3u * TB);
+      }
       // the list moves on to rows this batch does not hold (rare: every 1024 / TS tip operands): the lanes'
       // addresses of the next batch, then its rows.  Assembly, like reload(): the compiler counts no load
       // here (a load inside a branch makes it wait for everything in flight on every path), the next op's
@@ -602,7 +611,7 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     sink_stores();
     if (rec_flags(h1) & PLLHIP_FUSED_RELOAD_NEXT) reload(rec_src(h1));
     asm volatile("" ::"v"(cs)); // (the characters are waited for HERE on every path, whether op 0 gathers or not)
-    gather(pta, pta2, h1);
+    gather(pta, pta2, ptb, ptb2, h1);
     if (EDGE) asm volatile("" : "+v"(edge_pw)); // (arrived with the characters, requested ahead of them: not a load any longer)
     request(fa, h1);
     asm volatile("" ::"v"(fb.pm.x), "v"(fb.pm.y) : "memory");
@@ -614,8 +623,12 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     // ff: where that of op i+2 goes; pu: its pair-table entries, pf: where those of op i+1 go.
     // The caller alternates the two of each, so that nothing loaded is ever copied (a copy
     // would have to wait for the load).
+    // (the instances that defer, SECOND: pu and pf are the SAME registers, and so are pu2 and pf2 -- every gathered set
+    // is consumed at the top of the op, before the next op's gathers are issued, so four sets pu, pu2, p3, p4 need no
+    // more registers than two alternating pairs did)
     auto step = [&](const Rec & r0, Rec & r1, const FusedFetch<J> & fu, FusedFetch<J> & ff, pll_v2d (&pu)[J],
-                    pll_v2d (&pf)[J], pll_v2d (&pu2)[J], pll_v2d (&pf2)[J], unsigned int i) __attribute__((always_inline)) {
+                    pll_v2d (&pf)[J], pll_v2d (&pu2)[J], pll_v2d (&pf2)[J], pll_v2d (&p3)[J], pll_v2d (&p4)[J],
+                    unsigned int i) __attribute__((always_inline)) {
       // A wave is the limit of this kernel, not HBM: with twelve waves per CU nothing hides
       // what a wave waits for itself (counters: ~2300 cycles per op of which ~500 issue
       // vector and ~270 scalar instructions).  So the order below overlaps the wave's own
@@ -652,17 +665,92 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       // with per-rate scalers -- is lane t's); every kind reads both operands (a tip-tip op reads
       // slot 0 for nothing: no branch)
       double2 lo[J], ro[J];
-#pragma unroll
-      for (unsigned int j = 0; j < J; ++j)
+      if (!SECOND)
       {
-        lo[j] = *reinterpret_cast<const double2 *>(lds_l + j * 1024u);
-        ro[j] = *reinterpret_cast<const double2 *>(lds_r + j * 1024u);
+#pragma unroll
+        for (unsigned int j = 0; j < J; ++j)
+        {
+          lo[j] = *reinterpret_cast<const double2 *>(lds_l + j * 1024u);
+          ro[j] = *reinterpret_cast<const double2 *>(lds_r + j * 1024u);
+        }
       }
       unsigned int lc = 0u, rc = 0u;
       if (MODE != SCALE_NONE)
       {
         lc = *reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(cnt) + rec_lcnt(r0) + t * 4u);
         rc = *reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(cnt) + rec_rcnt(r0) + t * 4u);
+      }
+      if (SECOND)
+      {
+        // The instances that defer: an operand is read from its slot, or taken HERE from the registers the previous op's
+        // gathers wrote (arrived: the wait above) -- a gathered factor as it is, or, a FOLDED pair product
+        // (PLLHIP_FUSED_LPROD / _RPROD: a gathered-gathered parent with this one reader, fused_plan.hip), the product
+        // of two of them with the scaling test of the gathered-gathered op that is no longer walked, statement for
+        // statement; the count this op inherits on that side is the product's own scale bit.  Wave-uniform branches.
+        // Nothing below this block reads pu, pu2, p3, p4: the gathers behind it may write them again.
+#pragma unroll
+        for (unsigned int j = 0; j < J; ++j) asm volatile("" : "+v"(pu[j]), "+v"(pu2[j]), "+v"(p3[j]), "+v"(p4[j]));
+        auto product = [&](pll_v2d (&a)[J], pll_v2d (&b)[J], bool pscale, double2 (&out)[J], unsigned int & own) {
+          unsigned long long fired[J];
+#pragma unroll
+          for (unsigned int j = 0; j < J; ++j)
+          {
+            double q0 = a[j].x * b[j].x, q1 = a[j].y * b[j].y;
+            fired[j] = 0;
+            if (MODE != SCALE_NONE)
+            {
+              const unsigned int small = ((q0 < PLLHIP_SCALE_THRESHOLD) & (q1 < PLLHIP_SCALE_THRESHOLD)) ? 1u : 0u;
+              const bool scale = pscale && group_and<(int)GW>(small) != 0u;
+              const double factor = __hiloint2double(scale ? 0x4ff00000 : 0x3ff00000, 0); // 2^256 : 1.0
+              q0 *= factor;
+              q1 *= factor;
+              fired[j] = __ballot(scale);
+            }
+            out[j] = make_double2(q0, q1);
+          }
+          if (MODE != SCALE_NONE)
+          {
+            unsigned long long mine = fired[0];
+#pragma unroll
+            for (unsigned int j = 1; j < J; ++j) mine = (t / EPS == j) ? fired[j] : mine;
+            own = (unsigned int)(mine >> ((t % EPS) * GW)) & 1u;
+          }
+        };
+        // (the common op first: a plain inner-inner op costs one scalar test here)
+        if ((fl & (PLLHIP_FUSED_KIND_MASK | PLLHIP_FUSED_LPROD | PLLHIP_FUSED_RPROD)) == 0u)
+        {
+#pragma unroll
+          for (unsigned int j = 0; j < J; ++j)
+          {
+            lo[j] = *reinterpret_cast<const double2 *>(lds_l + j * 1024u);
+            ro[j] = *reinterpret_cast<const double2 *>(lds_r + j * 1024u);
+          }
+        }
+        else
+        {
+        if (fl & PLLHIP_FUSED_LPROD) product(pu, pu2, MODE != SCALE_NONE && (fl & PLLHIP_FUSED_LPSCALE), lo, lc);
+        else if (kind != 0)
+        {
+#pragma unroll
+          for (unsigned int j = 0; j < J; ++j) lo[j] = make_double2(pu[j].x, pu[j].y);
+        }
+        else
+        {
+#pragma unroll
+          for (unsigned int j = 0; j < J; ++j) lo[j] = *reinterpret_cast<const double2 *>(lds_l + j * 1024u);
+        }
+        if (fl & PLLHIP_FUSED_RPROD) product(p3, p4, MODE != SCALE_NONE && (fl & PLLHIP_FUSED_RPSCALE), ro, rc);
+        else if (kind == 3)
+        {
+#pragma unroll
+          for (unsigned int j = 0; j < J; ++j) ro[j] = make_double2(pu2[j].x, pu2[j].y);
+        }
+        else
+        {
+#pragma unroll
+          for (unsigned int j = 0; j < J; ++j) ro[j] = *reinterpret_cast<const double2 *>(lds_r + j * 1024u);
+        }
+        }
       }
       asm volatile("" ::: "memory"); // (the reads above are issued before what follows)
       // (rare, wave-uniform: the sources of the reload are read on the spot)
@@ -673,12 +761,16 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
         asm volatile("s_mov_b64 exec, 1\n\tglobal_atomic_add %0, %1, %2, off sc0\n\ts_mov_b64 exec, -1"
                      : "=&v"(next_ticket) : "v"(ticket_counter), "v"(1u) : "memory");
       // (the request last: what the next op waits for first is the youngest operation in flight)
-      gather(pf, pf2, r0);
+      gather(pf, pf2, p3, p4, r0);
       request(ff, r0);
       // (this op's gathered entries, as the registers they arrived in: whole 16-byte values on every path, so that the
-      // compiler has nothing to re-pack between the op that loaded them and here -- see gather())
+      // compiler has nothing to re-pack between the op that loaded them and here -- see gather(); the instances that
+      // defer took theirs at the top of the op)
+      if (!SECOND)
+      {
 #pragma unroll
-      for (unsigned int j = 0; j < J; ++j) asm volatile("" : "+v"(pu[j]), "+v"(pu2[j]));
+        for (unsigned int j = 0; j < J; ++j) asm volatile("" : "+v"(pu[j]), "+v"(pu2[j]));
+      }
       unsigned long long scaled[J];
       double p0[J], p1[J];
       if (kind == 2)
@@ -689,8 +781,8 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
         for (unsigned int j = 0; j < J; ++j)
         {
           scaled[j] = 0;
-          p0[j] = pu[j].x;
-          p1[j] = pu[j].y;
+          p0[j] = SECOND ? lo[j].x : pu[j].x;
+          p1[j] = SECOND ? lo[j].y : pu[j].y;
         }
       }
       else
@@ -703,8 +795,8 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
           if (kind & 1u)
           {
             // gathered-inner (a tip, or a deferred cherry) and gathered-gathered: the factor is the table entry
-            x0 = pu[j].x;
-            x1 = pu[j].y;
+            x0 = SECOND ? lo[j].x : pu[j].x;
+            x1 = SECOND ? lo[j].y : pu[j].y;
           }
           else
           {
@@ -713,7 +805,8 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
             x1 = pl.dot(1, lo[j], lp);
           }
           // (kind 3: the second factor is gathered too -- no mat-vec at all)
-          const double y0 = kind == 3 ? pu2[j].x : pr.dot(0, ro[j], rp), y1 = kind == 3 ? pu2[j].y : pr.dot(1, ro[j], rp);
+          const double y0 = kind == 3 ? (SECOND ? ro[j].x : pu2[j].x) : pr.dot(0, ro[j], rp);
+          const double y1 = kind == 3 ? (SECOND ? ro[j].y : pu2[j].y) : pr.dot(1, ro[j], rp);
           double q0 = x0 * y0, q1 = x1 * y1;
           // scaling rule of core_partials_avx.c:486-527: all entries of the site (of the rate,
           // with per-rate scalers) below the threshold; x * 1.0 is x
@@ -783,10 +876,20 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     };
     for (unsigned int i = 0;;)
     {
-      step(ra, rb, fa, fb, pta, ptb, pta2, ptb2, i);
-      if (++i == nops) break;
-      step(rb, ra, fb, fa, ptb, pta, ptb2, pta2, i);
-      if (++i == nops) break;
+      if constexpr (SECOND)
+      {
+        step(ra, rb, fa, fb, pta, pta, pta2, pta2, ptb, ptb2, i);
+        if (++i == nops) break;
+        step(rb, ra, fb, fa, pta, pta, pta2, pta2, ptb, ptb2, i);
+        if (++i == nops) break;
+      }
+      else
+      {
+        step(ra, rb, fa, fb, pta, ptb, pta2, ptb2, ptb, ptb2, i);
+        if (++i == nops) break;
+        step(rb, ra, fb, fa, ptb, pta, ptb2, pta2, ptb, ptb2, i);
+        if (++i == nops) break;
+      }
     }
     if (EDGE)
     {
@@ -904,7 +1007,8 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   // (a list whose cherries are deferred is as long as the list the caller handed over: a full traversal walks 30 ops
   // where it walked 62 and keeps the long list's share of tickets; lists that defer nothing are judged as before)
   const size_t rounds = tiles * nsegs / (grid * 4);
-  const unsigned int dynamic_rounds = c->fused_last_longest + c->fused_last_ndeferred >= 32 ? (unsigned int)std::max<size_t>(7, rounds / 3) : 2u;
+  // (... and so does one that folds pair products into their readers: 14 ops walked of 62)
+  const unsigned int dynamic_rounds = c->fused_last_longest + c->fused_last_ndeferred + c->fused_last_nfolded >= 32 ? (unsigned int)std::max<size_t>(7, rounds / 3) : 2u;
   // (eight counters -- but never more than there are groups of eight workgroups, or a counter's tiles would have no
   // takers; and no more than the counter buffer holds)
   const unsigned int tile_groups = (unsigned int)std::min<size_t>(std::min<size_t>(8, PLLHIP_TILE_COUNTER_BYTES / 128),
@@ -968,8 +1072,10 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   for (const auto & plan : plans)
     for (const FusedOp & f : plan)
     {
-      if (f.kind == 3 && (R > 4 || c->sh.rate_scalers)) return 1;
-      ntab += (f.kind >= 1) + (f.kind == 3);
+      if ((f.kind == 3 || f.prod[0] || f.prod[1]) && (R > 4 || c->sh.rate_scalers)) return 1;
+      // (a folded product is two factors; one on the right only does not exist: fused_plan.hip presents it "left")
+      if (f.prod[1] && !f.prod[0]) return 1;
+      ntab += f.prod[1] ? 4 : f.prod[0] ? 2 : (f.kind >= 1) + (f.kind == 3);
     }
   if (ntab * per * sizeof(double) > 0xffffffffull ||
       (size_t)c->sh.prob_matrices * c->pmat_elems * sizeof(double) > 0xffffffffull)
@@ -1012,65 +1118,102 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   // site); lanes without a row fetch zeros.  Batches are numbered across the segments.
   // every op's gathered operands (FusedOperand): what the planner was told about deferred cherries, else what the
   // op's kind says -- the tip of a tip-inner op, the finished parent of a tip-tip op
-  std::vector<FusedExtra> gx(n);
+  // (up to four per op, in the order the kernel gathers them: one or two factors of the op itself, or the two factors
+  // of a folded product on the left, then those of one on the right)
+  struct GatherSets { FusedOperand g[4]; double * copy[4]; };
+  std::vector<GatherSets> gx(n);
   for (unsigned int pos = 0; pos < n; ++pos)
   {
     const FusedOp & f = plan[pos];
-    gx[pos].g[0] = f.g[0];
-    gx[pos].g[1] = f.g[1];
-    if (f.g[0].type == FUSED_G_NONE && f.kind == 1) gx[pos].g[0] = FusedOperand{FUSED_G_TIP, f.ltip, nullptr, f.lmat, nullptr, nullptr, nullptr};
-    if (f.g[0].type == FUSED_G_NONE && f.kind == 2) gx[pos].g[0] = FusedOperand{FUSED_G_PAIR, f.ltip, f.rtip, nullptr, f.lmat, f.rmat, nullptr};
-    if (f.kind == 3 && (gx[pos].g[0].type == FUSED_G_NONE || gx[pos].g[1].type == FUSED_G_NONE)) return 1;
+    GatherSets & x = gx[pos];
+    memset(&x, 0, sizeof(x));
+    if (f.prod[0] || f.prod[1])
+    {
+      // (only what the planner folds: an inner-inner reader, presented as gathered-inner or gathered-gathered)
+      if (!f.prod[0] || (f.kind != 1 && f.kind != 3) || (f.kind == 3) != (f.prod[1] != 0) || f.unstored) return 1;
+      for (int s = 0; s < (f.prod[1] ? 2 : 1); ++s)
+      {
+        if (f.g[s].type == FUSED_G_NONE || f.g2[s].type == FUSED_G_NONE || !f.pkeep[s][0] || !f.pkeep[s][1]) return 1;
+        x.g[2 * s] = f.g[s];
+        x.g[2 * s + 1] = f.g2[s];
+        x.copy[2 * s] = f.pkeep[s][0];
+        x.copy[2 * s + 1] = f.pkeep[s][1];
+      }
+      continue;
+    }
+    x.g[0] = f.g[0];
+    x.g[1] = f.g[1];
+    if (f.g[0].type == FUSED_G_NONE && f.kind == 1) x.g[0] = FusedOperand{FUSED_G_TIP, f.ltip, nullptr, f.lmat, nullptr, nullptr, nullptr};
+    if (f.g[0].type == FUSED_G_NONE && f.kind == 2) x.g[0] = FusedOperand{FUSED_G_PAIR, f.ltip, f.rtip, nullptr, f.lmat, f.rmat, nullptr};
+    if (f.kind == 3 && (x.g[0].type == FUSED_G_NONE || x.g[1].type == FUSED_G_NONE)) return 1;
+    // (an unstored pair product: its factors are kept, deferred.hip)
+    for (int o = 0; f.unstored && o < 2; ++o) x.copy[o] = f.keep[o];
   }
-  std::vector<unsigned int> chars_of(n, 0), chars2_of(n, 0), batch_of(n, 0);
+  std::vector<unsigned int> chars_of[4] = {std::vector<unsigned int>(n, 0), std::vector<unsigned int>(n, 0),
+                                           std::vector<unsigned int>(n, 0), std::vector<unsigned int>(n, 0)};
+  std::vector<unsigned int> batch_of(n, 0);
   const unsigned int batch0 = (unsigned int)(rowtab.size() / 64);
   {
-    std::vector<unsigned int> ntips(n);
+    std::vector<unsigned int> ntips(n, 0);
     for (unsigned int pos = 0; pos < n; ++pos)
-      ntips[pos] = (gx[pos].g[0].row1 ? 1u : 0u) | (gx[pos].g[0].row2 ? 2u : 0u) | (gx[pos].g[1].row1 ? 4u : 0u) | (gx[pos].g[1].row2 ? 8u : 0u);
-    const unsigned int nbatches = pllhip_fused_char_batches4(ntips.data(), n, lpr, chars_of.data(), chars2_of.data(), batch_of.data());
-    if (batch0 + nbatches > 255 || 4 * lpr > 64) return 1;
+      for (int k = 0; k < 4; ++k) ntips[pos] |= (gx[pos].g[k].row1 ? 1u : 0u) << (2 * k) | (gx[pos].g[k].row2 ? 2u : 0u) << (2 * k);
+    unsigned int * const chars_out[4] = {chars_of[0].data(), chars_of[1].data(), chars_of[2].data(), chars_of[3].data()};
+    const unsigned int nbatches = pllhip_fused_char_batches8(ntips.data(), n, lpr, chars_out, batch_of.data());
+    if (batch0 + nbatches > 255 || 8 * lpr > 64) return 1;
     rowtab.resize((size_t)(batch0 + nbatches) * 64, (unsigned long long)(uintptr_t)c->fused_zero_row);
     for (unsigned int pos = 0; pos < n; ++pos)
     {
       batch_of[pos] += batch0;
-      const unsigned char * rows[4] = {gx[pos].g[0].row1, gx[pos].g[0].row2, gx[pos].g[1].row1, gx[pos].g[1].row2};
-      const unsigned int lane0[4] = {PLLHIP_FUSED_CH_LPOS(chars_of[pos]), PLLHIP_FUSED_CH_RPOS(chars_of[pos]),
-                                     PLLHIP_FUSED_CH_LPOS(chars2_of[pos]), PLLHIP_FUSED_CH_RPOS(chars2_of[pos])};
-      for (int o = 0; o < 4; ++o)
-        for (unsigned int l = 0; rows[o] && l < lpr; ++l)
-          rowtab[(size_t)batch_of[pos] * 64 + lane0[o] + l] = (unsigned long long)(uintptr_t)rows[o] + l * 16u;
+      for (int k = 0; k < 4; ++k)
+      {
+        const unsigned char * rows[2] = {gx[pos].g[k].row1, gx[pos].g[k].row2};
+        const unsigned int lane0[2] = {PLLHIP_FUSED_CH_LPOS(chars_of[k][pos]), PLLHIP_FUSED_CH_RPOS(chars_of[k][pos])};
+        for (int o = 0; o < 2; ++o)
+          for (unsigned int l = 0; rows[o] && l < lpr; ++l)
+          {
+            if (lane0[o] + l >= 64) return 1;
+            rowtab[(size_t)batch_of[pos] * 64 + lane0[o] + l] = (unsigned long long)(uintptr_t)rows[o] + l * 16u;
+          }
+      }
     }
   }
-  std::vector<unsigned int> table_of(n, 0), table2_of(n, 0); // byte offsets of each op's tables (read only where the op's chars say it gathers)
+  std::vector<unsigned int> table_of(n, 0); // byte offset of each op's first table: its tables follow each other (read only where the op's chars say it gathers)
   for (unsigned int pos = 0; pos < n; ++pos)
   {
     const FusedOp & f = plan[pos];
-    for (int o = 0; o < 2; ++o)
+    for (int o = 0; o < 4; ++o)
     {
       const FusedOperand & g = gx[pos].g[o];
-      if (g.type == FUSED_G_NONE) continue;
+      // (gathers are numbered without gaps: the kernel finds table k at k tables behind the first)
+      if (g.type == FUSED_G_NONE)
+      {
+        for (int later = o + 1; later < 4; ++later)
+          if (gx[pos].g[later].type != FUSED_G_NONE) return 1;
+        break;
+      }
       const size_t index = jobs.size();
-      (o ? table2_of : table_of)[pos] = (unsigned int)(index * per * sizeof(double));
+      if (index >= ntab) return 1;
+      if (o == 0) table_of[pos] = (unsigned int)(index * per * sizeof(double));
       double * tab = c->d_pairtab + index * per;
-      double * copy = f.unstored ? f.keep[o] : nullptr; // (an unstored pair product: its factors are kept, deferred.hip)
+      double * copy = gx[pos].copy[o];
       if (g.type == FUSED_G_TIP) jobs.push_back(FusedPairJob{g.mat, nullptr, tab, 0ull, nullptr, nullptr, copy, 0ull});
       else if (g.type == FUSED_G_PAIR) jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 1ull, nullptr, nullptr, copy, 0ull});
       else if (g.type == FUSED_G_CHERRY_NEW) jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 2ull, g.mat, nullptr, copy, 0ull});
       else jobs.push_back(FusedPairJob{nullptr, nullptr, tab, 3ull, g.mat, g.kept, copy, 0ull});
     }
-    // every op with a parent scaler scales the partition's way
-    if (f.pscaler) mode = c->sh.rate_scalers ? SCALE_RATE : SCALE_SITE;
+    // every op with a parent scaler scales the partition's way (and so does a folded product's test)
+    if (f.pscaler || (f.prod[0] & 2) || (f.prod[1] & 2)) mode = c->sh.rate_scalers ? SCALE_RATE : SCALE_SITE;
   }
   // what record `r` says about the ops ahead of position `pos` (pos may be -2, -1: the headers)
   auto look_ahead = [&](FusedRec & r, long pos) -> int {
-    r.chars = r.chars2 = r.gather_off2 = 0;
+    r.chars = r.chars2 = r.chars3 = r.chars4 = 0;
     r.req_lmat = r.req_rmat = 0;
     if (pos + 1 >= 0 && pos + 1 < (long)n)
     {
-      r.chars = chars_of[pos + 1];
-      r.chars2 = chars2_of[pos + 1];
-      r.gather_off2 = table2_of[pos + 1];
+      r.chars = chars_of[0][pos + 1];
+      r.chars2 = chars_of[1][pos + 1];
+      r.chars3 = chars_of[2][pos + 1];
+      r.chars4 = chars_of[3][pos + 1];
     }
     // (the edge pseudo-op at position n: its matrix is requested and staged as a right-hand one, like a tip-inner op's)
     if (edge && pos + 2 == (long)n) r.req_rmat = (unsigned int)((edge->pmat - c->pmatrix) * sizeof(double));
@@ -1088,7 +1231,8 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
     {
       const FusedOp & f = pos + 1 < (long)n ? plan[pos + 1] : edge->op;
       r.gather_off = pos + 1 < (long)n ? table_of[pos + 1] : 0u;
-      r.flags |= (f.kind == 0 ? 2u : (f.kind == 1 || f.kind == PLLHIP_FUSED_KIND_EDGE) ? 1u : 0u) << PLLHIP_FUSED_STAGE_SHIFT;
+      // (a reader of folded products runs as an inner-inner op: both matrices)
+      r.flags |= (f.kind == 0 || f.prod[0] ? 2u : (f.kind == 1 || f.kind == PLLHIP_FUSED_KIND_EDGE) ? 1u : 0u) << PLLHIP_FUSED_STAGE_SHIFT;
       if (f.dma_flags)
       {
         if (srcs.size() >= 0xffffu) return 1;
@@ -1118,6 +1262,14 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
     const FusedOp & f = plan[pos];
     FusedRec & r = rs[pos + 2];
     r.flags = (unsigned int)f.kind & PLLHIP_FUSED_KIND_MASK;
+    if (f.prod[0])
+    {
+      // folded products: the kernel's inner-inner arithmetic, that side's operand formed from the gathered factors;
+      // the count inherited on that side is the product's own scale bit, where the reader passes its scale buffer
+      r.flags = PLLHIP_FUSED_LPROD | ((f.prod[0] & 2) ? PLLHIP_FUSED_LPSCALE : 0u) | ((f.prod[0] & 4) ? PLLHIP_FUSED_LCNT : 0u);
+      if (f.prod[1])
+        r.flags |= PLLHIP_FUSED_RPROD | ((f.prod[1] & 2) ? PLLHIP_FUSED_RPSCALE : 0u) | ((f.prod[1] & 4) ? PLLHIP_FUSED_RCNT : 0u);
+    }
     if (f.pslot >= 0) r.flags |= PLLHIP_FUSED_HAS_PSLOT;
     if (f.pscaler) r.flags |= PLLHIP_FUSED_SCALING;
     if (f.unstored)
@@ -1127,7 +1279,7 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
       r.flags |= PLLHIP_FUSED_UNSTORED;
     }
     if (f.kind == 0 && f.lsc_slot >= 0) r.flags |= PLLHIP_FUSED_LCNT;
-    if (f.kind != 2 && f.rsc_slot >= 0) r.flags |= PLLHIP_FUSED_RCNT;
+    if (f.kind != 2 && !f.prod[1] && f.rsc_slot >= 0) r.flags |= PLLHIP_FUSED_RCNT;
     r.parent = (unsigned long long)(uintptr_t)f.parent;
     r.pscaler = (unsigned long long)(uintptr_t)f.pscaler;
     r.lslot_b = (unsigned short)((f.lslot > 0 ? f.lslot : 0) * slot_bytes);

@@ -37,9 +37,17 @@ struct FusedOperand
   const double * c_lmat, * c_rmat;  // CHERRY_NEW: the cherry's own two matrices (its T is built from them on the spot)
   const double * kept;              // CHERRY_KEPT: its kept table T
 };
+// A side of an op may also be the PRODUCT of two gathered factors (prod[side] != 0): a gathered-gathered parent with one
+// reader that is not walked at all but formed by that reader (pllhip_fused_fold).  g[side] and g2[side] are then its
+// two factors; prod[side] is a bit set: 1 a product, | 2 the folded op has a scale buffer (its scaling test can fire),
+// | 4 the reader passes its scale buffer on that side (it inherits the product's scale bit); pkeep[side]: where the two
+// factor tables are kept (the pool: deferred.hip).
 struct FusedExtra
 {
   FusedOperand g[2];
+  FusedOperand g2[2];
+  int prod[2];
+  double * pkeep[2][2];
 };
 
 // What the planner decides for one op (host side; the device gets FusedRec below).
@@ -65,6 +73,12 @@ struct FusedOp
   FusedOperand g[2];               // gathered operands over deferred cherries (type 0: the op's kind says it all)
   int unstored;                    // kind 3: the parent is not stored (pllhip_fused_unstored) -- its CLV stores go to the sink
   double * keep[2];                // ... and its two factor tables are also written here (the pool: deferred.hip)
+  // folded pair products (pllhip_fused_fold): side s is the product of the gathered factors g[s] and g2[s].  To the
+  // planner the op is then gathered-inner (kind 1, the product "left") or gathered-gathered (kind 3); the kernel runs
+  // it as an inner-inner op whose operand on that side is formed from registers instead of read from a slot.
+  FusedOperand g2[2];
+  int prod[2];                     // 0 no product; else bits: 1 a product, 2 its op has a scale buffer, 4 the reader inherits its count
+  double * pkeep[2][2];            // the pool's places of the two factor tables of side s
 };
 
 // The plan as the kernel reads it, through the scalar data cache: ONE 64-byte record per op (one
@@ -83,9 +97,9 @@ struct FusedOp
 struct FusedRec
 {
   unsigned int chars;                    // tip characters of op + 1, PLLHIP_FUSED_CH_* below
-  unsigned int chars2;                   // ... of its SECOND gather (kind 3), same layout (no CH_LOAD, no batch)
-  unsigned int gather_off2;              // byte offset of the second gather's table (read only if chars2 has CH_LTIP | CH_RTIP)
-  unsigned int pad;
+  unsigned int chars2;                   // ... of its SECOND gather (kind 3, a product), same layout (no CH_LOAD, no batch)
+  unsigned int chars3, chars4;           // ... of a third and fourth one (a reader of folded products: up to four factors)
+                                         // (the tables of one op follow each other: gather k reads at gather_off + k tables)
   unsigned int req_lmat, req_rmat;       // byte offsets of its P-matrices in the matrix arena
   unsigned int gather_off;               // byte offset of the pair table of op + 1 (read only if chars has CH_LTIP | CH_RTIP)
   unsigned int flags;                    // PLLHIP_FUSED_* below
@@ -105,6 +119,10 @@ static_assert(sizeof(FusedRec) == 64, "sixteen words per op");
 #define PLLHIP_FUSED_STAGE_SHIFT 6     /* two bits: matrices op + 1 needs (2 both, 1 right only, 0 none) */
 #define PLLHIP_FUSED_RELOAD_NEXT 256u  /* op + 1 reloads operands: FusedSrc number `src` */
 #define PLLHIP_FUSED_UNSTORED 512u     /* the parent's CLV stores go to the wave's sink (a pair product: deferred.hip) */
+#define PLLHIP_FUSED_LPROD 1024u       /* the left / right operand is the product of two gathered factors (sets 1, 2 / */
+#define PLLHIP_FUSED_RPROD 2048u       /* 3, 4), formed at the top of the op instead of read from a slot               */
+#define PLLHIP_FUSED_LPSCALE 4096u     /* ... and the folded op has a scale buffer: its scaling test runs              */
+#define PLLHIP_FUSED_RPSCALE 8192u
 #define PLLHIP_FUSED_KIND_EDGE 4        /* FusedOp::kind of the edge pseudo-op (never in a record's kind bits) */
 #define PLLHIP_FUSED_MAX_OPS 60000u    /* longer lists run per level */
 // FusedRec::chars -- a wave holds the characters of up to 1024 / (tile sites) tip rows at its tile, 16 bytes per
@@ -146,9 +164,10 @@ struct FusedPairJob
 
 unsigned int pllhip_fused_char_batches(const unsigned int * tips, unsigned int count, unsigned int lpr,
                                        unsigned int * chars_out, unsigned int * batch_out);
-// the same for ops with up to four rows (bits 2 / 3 of tips[pos]: the rows of the second gather, into chars2_out)
-unsigned int pllhip_fused_char_batches4(const unsigned int * tips, unsigned int count, unsigned int lpr,
-                                        unsigned int * chars_out, unsigned int * chars2_out, unsigned int * batch_out);
+// the same for ops with up to eight rows, the ONE batching rule (bits 2 k / 2 k + 1 of tips[pos]: the rows of gather k,
+// into chars_out[k]; null outputs from the first unused)
+unsigned int pllhip_fused_char_batches8(const unsigned int * tips, unsigned int count, unsigned int lpr,
+                                        unsigned int * const chars_out[4], unsigned int * batch_out);
 
 // Round 5: SEGMENTS.  Ops that share no buffer any of them writes are independent lists -- the two sides of the root
 // edge of a full traversal, above all -- and a tile of sites may be taken through each of them by a different wave at
@@ -257,6 +276,34 @@ bool pllhip_fused_edge_end_stored(const FusedGeom & geom, const FusedDeferral & 
 unsigned int pllhip_fused_unstored(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
                                    std::vector<std::vector<FusedOp>> & plans, const FusedEdge * edge,
                                    const unsigned char * pinned);
+// Which unstored pair products of a planned list are FOLDED into their reader: not walked at all, the reader forms the
+// product from the two gathered factors itself.  A parent pllhip_fused_unstored marked is folded if
+//   - exactly one op of the list reads it, on one side only;
+//   - that reader is an inner-inner op of the list (kinds[] 0): its other side is another folded product, or a slot.
+// (A reader whose other side is a single gathered factor keeps today's treatment: its product is walked, unstored.)
+// Sets fold[k] = 1 per op of the list to fold, returns how many -- 0 also where fewer than two ops would be left to
+// walk (a list kernel wants two).  ONE rule for pllhip_update_partials and pllhip_fused_plan_dry_folded; the caller
+// plans the list once more without the folded ops (pllhip_fused_fold_list).
+unsigned int pllhip_fused_fold(const pllhip_op_t * ops, const int * kinds, unsigned int count,
+                               const std::vector<std::vector<FusedOp>> & plans, std::vector<unsigned char> & fold);
+// The list without the ops fold[] marks, as the planner is to see it: `where` (kept op -> op of the list), the kept
+// ops, their args / kinds / extras with every reader's folded side turned into a product operand (FusedExtra::prod --
+// to the planner a gathered side: as_tip[parent] is set for every folded parent), and rows (4 per kept op -> 8: tip
+// index + 1 of the rows of its up to four factors).  extras / rows: of the list (rows may be nullptr: dry).
+struct FusedFoldList
+{
+  std::vector<unsigned int> where;
+  std::vector<pllhip_op_t> ops;
+  std::vector<PartialsArgs> args;
+  std::vector<int> kinds;
+  std::vector<FusedExtra> extras;
+  std::vector<unsigned char> as_tip;
+  std::vector<unsigned int> rows8;
+  std::vector<unsigned int> prod_op; // 2 per kept op: the op of the list folded into side 0 / 1 of it, + 1 (0: none)
+};
+void pllhip_fused_fold_list(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
+                            const FusedExtra * extras, const unsigned int * rows4, unsigned int count,
+                            const std::vector<unsigned char> & fold, FusedFoldList & out);
 // slots per wave with 2 (8 waves per CU) or 3 (12 waves) workgroups per CU
 unsigned int pllhip_fused_slots_for(unsigned int rate_cats, bool rate_scalers, unsigned int workgroups_per_cu);
 unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int workgroups_per_cu);

@@ -907,6 +907,20 @@ int pll_amd_set_unstored_pairs(pll_partition_t * p, int on)
   return PLL_SUCCESS;
 }
 
+int pll_amd_pair_fold_stats(pll_partition_t * p, unsigned long long * stats4)
+{
+  int rc = pllhip_pair_fold_stats(pll_amd_priv(p)->ctx, stats4);
+  if (rc) return pll_amd_fail_hip(rc, "pair fold stats");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_set_pair_fold(pll_partition_t * p, int on)
+{
+  int rc = pllhip_set_pair_fold(pll_amd_priv(p)->ctx, on);
+  if (rc) return pll_amd_fail_hip(rc, "set pair fold");
+  return PLL_SUCCESS;
+}
+
 int pll_amd_set_deferral(pll_partition_t * p, int on)
 {
   int rc = pllhip_set_deferral(pll_amd_priv(p)->ctx, on);

@@ -283,6 +283,9 @@ class PllLibrary:
                 lib.pll_amd_unstored_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
                 lib.pll_amd_dev_clv.argtypes = [_PP, C.c_uint]
                 lib.pll_amd_dev_clv.restype = C.c_void_p
+            if hasattr(lib, "pll_amd_set_pair_fold"):
+                lib.pll_amd_set_pair_fold.argtypes = [_PP, C.c_int]
+                lib.pll_amd_pair_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
             if hasattr(lib, "pll_amd_set_edge_fold"):
                 lib.pll_amd_set_edge_fold.argtypes = [_PP, C.c_int]
                 lib.pll_amd_edge_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
@@ -1005,6 +1008,16 @@ class Partition:
     def set_unstored_pairs(self, on):
         """False: the parent of every gathered-gathered op of a 4-state whole-list launch is stored (pll_amd.h)."""
         self._check(self.lib.pll_amd_set_unstored_pairs(self.ptr, 1 if on else 0), "pll_amd_set_unstored_pairs")
+
+    def set_pair_fold(self, on):
+        """Fold unstored pair products with one reader into that reader (pll_amd.h); on by default."""
+        self._check(self.lib.pll_amd_set_pair_fold(self.ptr, 1 if on else 0), "pll_amd_set_pair_fold")
+
+    def pair_fold_stats(self):
+        """{folded_now, ops_folded, lists_replanned, materialised} of the folded pair products (pll_amd.h)."""
+        buf = (C.c_ulonglong * 4)()
+        self._check(self.lib.pll_amd_pair_fold_stats(self.ptr, buf), "pll_amd_pair_fold_stats")
+        return dict(zip(("folded_now", "ops_folded", "lists_replanned", "materialised"), (int(v) for v in buf)))
 
     def unstored_stats(self):
         """{unstored_now, ops_unstored, launches, materialised} of the 4-state pair products (pll_amd.h)."""
