@@ -637,9 +637,9 @@ def test_second_grid_stride_round(gpu, orc, monkeypatch, tree, which, nt):
 
 # ---- D. a root that moves
 
-def _walk_case(shape, tips, seed, rate_cats, scalers, branch):
+def _walk_case(shape, tips, seed, rate_cats, scalers, branch, sites=SITES):
     plan, view, moves = U.walk_moves(shape, tips, seed, scalers=scalers, branch=branch)
-    case = make_case(4, "random", tips, SITES, rate_cats=rate_cats, seed=seed)
+    case = make_case(4, "random", tips, sites, rate_cats=rate_cats, seed=seed)
     case["plan"] = plan
     return case, plan, view, moves
 
@@ -714,13 +714,15 @@ def test_moving_root_scaling(gpu, orc):
 
 
 def test_moving_root_two_shards(gpu, monkeypatch):
-    """the 20-tip walk on two shards of one device against the unsharded partition"""
+    """the 20-tip walk on two shards of one device against the unsharded partition.  A shard begins on a multiple of 256
+    sites (shard.hip) -- at 40 sites the group had ONE shard --: 256 + 40 sites, the second shard the other cases' size."""
     shape, tips, seed = U.WALKS[1]
-    case, plan, view, moves = _walk_case(shape, tips, seed, 4, True, None)
+    case, plan, view, moves = _walk_case(shape, tips, seed, 4, True, None, sites=256 + SITES)
     whole = build_partition(gpu, case, ATTRS)
     monkeypatch.setenv("PLL_AMD_DEVICES", "0,0")
     split = build_partition(gpu, case, ATTRS)
     monkeypatch.delenv("PLL_AMD_DEVICES")
+    assert gpu.lib.pll_amd_shard_count(whole.ptr) == 1 and gpu.lib.pll_amd_shard_count(split.ptr) == 2
     began_folded = 0
     for mv in moves:
         for p in (whole, split):

@@ -1,5 +1,5 @@
-"""Shared data of tests/test_gpu_unstored_state.py and tests/test_unstored_state_lists.py: the trees and seeded walks of
-a root that moves, and the list builder that turns a new root edge into the op list a tree search would hand
+"""Shared data of tests/test_gpu_unstored_state.py, tests/test_unstored_state_lists.py and tests/moving_root.py (the
+walks of tests/test_gpu_moving_root_routes.py): the trees and seeded walks of a root that moves, and the list builder that turns a new root edge into the op list a tree search would hand
 pll_update_partials -- a partial traversal (the reference's pll_utree_traverse with a callback that stops at a node
 whose CLV is valid and points the right way).
 
@@ -88,19 +88,35 @@ class Orientation:
         return ops, (a, sc(a), b, sc(b), self.view.matrix[frozenset((a, b))])
 
 
-def walk_moves(shape, tips, seed, scalers=True, change_branches=True, branch=None):
-    """The walk over one tree, as plain data: (plan, view, [move]) with move = dict(root, ops, edge, changed) --
-    `changed` the (matrix index, new length) given to the previous root branch before the list, or None.  The first
-    entry of the list is the full traversal at the plan's own root (move 0); MOVES drawn moves follow."""
+def walk_moves(shape, tips, seed, scalers=True, change_branches=True, branch=None, replay_every=0):
+    """The walk over one tree, as plain data: (plan, view, [move]) with move = dict(root, ops, edge, changed, replay)
+    -- `changed` the (matrix index, new length) given to the previous root branch before the list, or None.  The first
+    entry of the list is the full traversal at the plan's own root (move 0); MOVES drawn moves follow.
+
+    replay_every = n > 0: every n-th move with a non-empty list (move 0 included) is followed by a replay -- the first
+    branch its last op reads gets a new length and the SAME list is to be run once more.  `replay` is that (matrix
+    index, new length), None elsewhere.  The tracker is told of the branch, so later lists recompute what lies above
+    it (the list's own nodes among them, which the replay left current: that costs ops, not correctness).  The roots
+    drawn and the lengths of `changed` are the same with and without replays."""
     plan = walk_plan(shape, tips, seed, scalers, branch)
     view = W.UnrootedView(plan, use_scalers=scalers)
     track = Orientation(view)
     edges = sorted(view.edges())
     rng = np.random.default_rng(WALK_SEED)
     lengths = np.random.default_rng(WALK_SEED + 1000)
+    replay_lengths = np.random.default_rng(WALK_SEED + 2000)
+
+    def replay_of(k, ops):
+        if not replay_every or k % replay_every or not len(ops):
+            return None
+        top, kid = int(ops[-1]["parent_clv_index"]), int(ops[-1]["child1_clv_index"])
+        track.change((top, kid))
+        t = float(replay_lengths.uniform(0.01, 0.3)) if branch is None else float(branch) * float(replay_lengths.uniform(0.5, 2.0))
+        return int(ops[-1]["child1_matrix_index"]), t
+
     root = tuple(view.root)
     ops, edge = track.move(root)
-    moves = [dict(root=root, ops=ops, edge=edge, changed=None)]
+    moves = [dict(root=root, ops=ops, edge=edge, changed=None, replay=replay_of(0, ops))]
     for k in range(1, MOVES + 1):
         new = edges[int(rng.integers(len(edges)))]
         changed = None
@@ -110,7 +126,7 @@ def walk_moves(shape, tips, seed, scalers=True, change_branches=True, branch=Non
             changed = (int(view.matrix[frozenset(root)]), t)
         root = new
         ops, edge = track.move(root)
-        moves.append(dict(root=root, ops=ops, edge=edge, changed=changed))
+        moves.append(dict(root=root, ops=ops, edge=edge, changed=changed, replay=replay_of(k, ops)))
     return plan, view, moves
 
 
