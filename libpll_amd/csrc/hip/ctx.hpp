@@ -140,12 +140,14 @@ struct pllhip_ctx
   unsigned int n_folded = 0;                   // ... the folded ones among the pair products
   unsigned int fused_last_nfolded = 0;         // ops the kept plan folds (not walked)
   unsigned long long fold_stats[4] = {0, 0, 0, 0}; // folded now (filled on read), ops folded, lists planned twice, CLVs materialised
-  std::vector<unsigned int> fused_last_unstored; // the kept plan's pair products: {clv, scaler + 1, rows[4]} each
+  struct unstored_product { unsigned int clv; int scaler; unsigned int rows[4]; bool folded; }; // (deferred_clv's fields)
+  std::vector<unstored_product> fused_last_unstored; // the kept plan's pair products
   unsigned long long unstored_stats[4] = {0, 0, 0, 0}; // the same four numbers for pair products
   bool cherry_deferral = true;                        // pllhip_set_deferral (0: the eager path, for A/B and tests)
   unsigned int defer_epoch = 0;                // bumped whenever a deferral ends other than by the list that replaces it
   unsigned int fused_last_defer_epoch = 0;     // ... as it was when the kept plan was launched
-  std::vector<unsigned int> fused_last_deferred; // the kept plan's deferred set: {clv, tip1, tip2, scaler + 1} each
+  struct deferred_cherry { unsigned int clv, tip1, tip2; int scaler; };
+  std::vector<deferred_cherry> fused_last_deferred; // the kept plan's deferred set
   unsigned long long defer_stats[4] = {0, 0, 0, 0}; // deferred now (filled on read), ops deferred, materialise launches, CLVs materialised
   // ---- edge lnL terms from the 4-state whole-list launch (partials_fused.hip: EDGE, likelihood.hip)
   // An EDGE_II evaluation is remembered (edge_hint); the next whole-list launch that writes one of its two CLVs also

@@ -801,6 +801,50 @@ int pllhip_fused_plan_list(const FusedGeom & geom, const pllhip_op_t * ops, cons
   return 0;
 }
 
+// Plan, unstored, fold, plan once more, unstored (partials_fused.hpp).
+int pllhip_fused_plan_walk(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
+                           const FusedExtra * extras, const unsigned int * rows4, unsigned int count,
+                           unsigned int max_segments, const unsigned int * slot_counts, unsigned int nslot_counts,
+                           const FusedEdge * edge, const FusedDeferral & dd, const unsigned char * pinned,
+                           bool may_unstore, bool may_fold, FusedWalk & out)
+{
+  out.replanned = false;
+  out.nunstored = out.nfolded = out.first_nunstored = 0;
+  out.fold.assign(count, 0);
+  out.list_ops = ops;
+  out.list_rows4 = rows4;
+  memset(&out.edge, 0, sizeof(out.edge));
+  if (edge) out.edge = *edge;
+  FusedEdge * const e = edge ? &out.edge : nullptr;
+  const int rc = pllhip_fused_plan_list(geom, ops, args, kinds, extras, count, max_segments, slot_counts, nslot_counts, e, dd, out.plan);
+  if (rc || !may_unstore) return rc;
+  out.nunstored = pllhip_fused_unstored(geom, ops, count, out.plan.plans, e, pinned);
+  if (!out.nunstored || !may_fold || !pllhip_fused_fold(ops, kinds, count, out.plan.plans, out.fold)) return 0;
+  pllhip_fused_fold_list(geom, ops, args, kinds, extras, rows4, count, out.fold, out.fl);
+  const unsigned int n2 = (unsigned int)out.fl.ops.size();
+  FusedGeom geom2 = geom;
+  geom2.as_tip = out.fl.as_tip.data();
+  FusedListPlan second;
+  FusedEdge edge2 = out.edge;
+  const bool offer2 = edge && out.plan.plans.size() == 1;
+  const int rc2 = n2 < 2 ? 1 : pllhip_fused_plan_list(geom2, out.fl.ops.data(), out.fl.args.data(), out.fl.kinds.data(), out.fl.extras.data(),
+                                                      n2, max_segments, slot_counts, nslot_counts, offer2 ? &edge2 : nullptr, dd, second);
+  if (rc2)
+  {
+    out.fold.assign(count, 0);
+    return rc2 < 0 ? rc2 : 0;
+  }
+  out.first_plan = std::move(out.plan);
+  out.first_edge = out.edge;
+  out.first_nunstored = out.nunstored;
+  out.plan = std::move(second);
+  out.edge = edge2;
+  out.replanned = true;
+  for (unsigned int i = 0; i < count; ++i) out.nfolded += out.fold[i];
+  out.nunstored = pllhip_fused_unstored(geom2, out.fl.ops.data(), n2, out.plan.plans, e, pinned);
+  return 0;
+}
+
 // ---- the 20-state list (partials_fused.hpp): classes, certificate bounds, the walk
 
 int pllhip_aa_list_classify(const FusedGeom & geom, const pllhip_op_t * ops, const int * kinds, const int * scales,
@@ -1115,76 +1159,43 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
       e.pinned[t] = pinned && pinned[ends[t]];
     }
   }
-  FusedListPlan lp;
-  const int rc = pllhip_fused_plan_list(geom, kept.data(), args.data(), kinds.data(), nullptr, n, 1, slot_counts, derived ? 2u : 1u,
-                                        edge4 ? &e : nullptr, d, lp);
+  // the live path's steps: pllhip_fused_plan_walk
+  FusedWalk w;
+  const int rc = pllhip_fused_plan_walk(geom, kept.data(), args.data(), kinds.data(), nullptr, nullptr, n, 1, slot_counts, derived ? 2u : 1u,
+                                        edge4 ? &e : nullptr, d, pinned, unstored_out != nullptr, folded_out != nullptr, w);
   if (rc) return rc;
-  if (unstored_out)
-  {
-    pllhip_fused_unstored(geom, kept.data(), n, lp.plans, edge4 ? &e : nullptr, pinned);
-    // Folded pair products (pllhip_fused_plan_dry_folded): the live path's steps -- the fold rule on the finished plan,
-    // the list without the folded ops planned once more by the same driver, the unstored rule on what is left.  A
-    // second plan the planner refuses leaves the first.
-    std::vector<unsigned char> fold;
-    FusedFoldList fl;
-    if (folded_out && pllhip_fused_fold(kept.data(), kinds.data(), n, lp.plans, fold))
-    {
-      pllhip_fused_fold_list(geom, kept.data(), args.data(), kinds.data(), nullptr, nullptr, n, fold, fl);
-      FusedGeom geom2 = geom;
-      geom2.as_tip = fl.as_tip.data();
-      FusedListPlan lp2;
-      const unsigned int n2 = (unsigned int)fl.ops.size();
-      if (pllhip_fused_plan_list(geom2, fl.ops.data(), fl.args.data(), fl.kinds.data(), fl.extras.data(), n2, 1, slot_counts,
-                                 derived ? 2u : 1u, edge4 ? &e : nullptr, d, lp2) == 0)
-      {
-        pllhip_fused_unstored(geom2, fl.ops.data(), n2, lp2.plans, edge4 ? &e : nullptr, pinned);
-        std::vector<unsigned int> where2(n2);
-        std::vector<int> opnd2(2 * (size_t)n2);
-        for (unsigned int j = 0; j < n2; ++j)
-        {
-          const unsigned int o = fl.where[j];
-          where2[j] = where[o];
-          opnd2[2 * j] = fl.as_tip[kept[o].child1_clv] && !geom.is_tip(kept[o].child1_clv) ? 3 : opnd[2 * o];
-          opnd2[2 * j + 1] = fl.as_tip[kept[o].child2_clv] && !geom.is_tip(kept[o].child2_clv) ? 3 : opnd[2 * o + 1];
-        }
-        for (unsigned int k = 0; k < n; ++k)
-          if (fold[k]) folded_out[where[k]] = 1;
-        lp.plans.swap(lp2.plans);
-        lp.nslots = lp2.nslots;
-        lp.taken = lp2.taken;
-        lp.reloads = lp2.reloads;
-        lp.folded = lp2.folded;
-        where.swap(where2);
-        opnd.swap(opnd2);
-        n = n2;
-        if (nkept) *nkept = n;
-      }
-    }
-    for (const FusedOp & f : lp.plans[0])
-      if (f.unstored) unstored_out[where[f.list_pos]] = 1;
-  }
+  const std::vector<FusedOp> & plan = w.plan.plans[0];
+  n = (unsigned int)plan.size();
+  if (nkept) *nkept = n;
+  for (unsigned int k = 0; folded_out && k < (unsigned int)kept.size(); ++k)
+    if (w.fold[k]) folded_out[where[k]] = 1;
   if (edge4)
   {
-    const int wgs = 3 - (int)lp.taken; // workgroups per CU of the slot count taken
+    const int wgs = 3 - (int)w.plan.taken; // workgroups per CU of the slot count taken
     edge_out[6] = wgs;
-    if (lp.folded)
+    if (w.plan.folded)
     {
-      const int v[8] = {1, e.op.lslot, e.op.rslot, e.op.lsc_slot, e.op.rsc_slot, e.op.dma_flags, wgs, wgs};
+      const FusedOp & eo = w.edge.op;
+      const int v[8] = {1, eo.lslot, eo.rslot, eo.lsc_slot, eo.rsc_slot, eo.dma_flags, wgs, wgs};
       for (int t = 0; t < 8; ++t) edge_out[t] = v[t];
     }
   }
   for (unsigned int pos = 0; pos < n; ++pos)
   {
-    const FusedOp & f = lp.plans[0][pos];
-    if (order_out) order_out[pos] = where[f.list_pos];
+    const FusedOp & f = plan[pos];
+    const unsigned int o = w.pos_in_list(f);
+    if (unstored_out && f.unstored) unstored_out[where[o]] = 1;
+    if (order_out) order_out[pos] = where[o];
     if (operands_out)
     {
-      operands_out[2 * pos] = opnd[2 * f.list_pos];
-      operands_out[2 * pos + 1] = opnd[2 * f.list_pos + 1];
+      // (3: a product folded into that side)
+      const unsigned int kid[2] = {kept[o].child1_clv, kept[o].child2_clv};
+      for (int t = 0; t < 2; ++t)
+        operands_out[2 * pos + t] = w.replanned && w.fl.as_tip[kid[t]] && !geom.is_tip(kid[t]) ? 3 : opnd[2 * o + t];
     }
     if (slots_out) dry_slots_out(f, slots_out + (size_t)pos * 6);
   }
-  if (reloads_out) *reloads_out = lp.reloads;
+  if (reloads_out) *reloads_out = w.plan.reloads;
   return 0;
 }
 

@@ -732,17 +732,25 @@ struct DnaListKept
   std::vector<pllhip_op_t> ops;            // the ops the kernel runs (empty: the caller's list as it is)
   std::vector<FusedExtra> extras;          // their gathered operands (empty: none -- nothing deferred, now or before)
   std::vector<FusedPairJob> keep_jobs;     // the tables of the cherries this list defers
-  std::vector<unsigned int> new_deferred;  // {clv, tip1, tip2, scaler + 1} per deferred op
+  std::vector<pllhip_ctx::deferred_cherry> new_deferred; // per deferred op
   std::vector<unsigned int> rows;          // per op of `ops`, four: tip index + 1 of the rows its two gathered factors are
                                            // indexed by (0 none) -- what an unstored pair product is kept with
-  std::vector<unsigned int> new_unstored;  // {clv, scaler + 1, rows[4]} per op whose parent this list leaves unstored
+  std::vector<pllhip_ctx::unstored_product> new_unstored; // per op whose parent the plan being launched leaves unstored
+  // the list's further state, step by step (update_partials_dna_list)
+  std::vector<PartialsArgs> args;          // resolve_op's of the ops the kernel runs
+  std::vector<int> kinds;
+  const pllhip_op_t * run_ops = nullptr;   // the ops the kernel runs: `ops`, or the caller's list
+  unsigned int run_count = 0;
+  bool edge_wanted = false, edge_ok = false; // the hinted evaluation: asked for by the instance; resolved into `edge`
+  FusedEdge edge;
+  FusedWalk walk;                          // the plan, what it leaves unstored and folds
 };
-// args / kinds: resolve_op's of the caller's list in, of k.ops out (where k.ops is not empty).  Materialises what the
-// list cannot read from a table; every deferred CLV where nothing may be deferred.
-static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count, std::vector<PartialsArgs> & args,
-                          std::vector<int> & kinds, DnaListKept & k)
+// Which cherries the list defers (k.dd), with what it cannot read from a table materialised first -- every deferred
+// CLV where nothing may be deferred.  *any = false: the list runs as it is, ordinary buffers, ordinary ops.
+static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count, DnaListKept & k, bool * any)
 {
   FusedDeferral & dd = k.dd;
+  *any = false;
   const bool may_defer = c->cherry_deferral && c->sh.pattern_tip && !c->sh.rate_scalers && c->sh.rate_cats <= 4;
   if (!may_defer)
   {
@@ -795,43 +803,60 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
     if (rc) return rc;
     for (unsigned int i : dd.materialise) dd.as_tip[i] = 0;
   }
-  // one operand of a kept op as a gathered one: a tip, or a cherry deferred by this list / by an earlier call
+  *any = true;
+  return 0;
+}
+
+// One operand of a kept op as a gathered one: a tip, a cherry deferred by this list (deferring_op[clv]: the op, else
+// -1) or by an earlier call.  rows2: tip index + 1 of row1 / row2, 0 none.
+static FusedOperand gathered_operand(pllhip_ctx * c, const pllhip_op_t * ops, const std::vector<int> & deferring_op,
+                                     unsigned int clv, unsigned int matrix, unsigned int * rows2)
+{
+  FusedOperand g;
+  memset(&g, 0, sizeof(g));
+  g.mat = pllhip_pmat_ptr(c, matrix);
+  unsigned int t1, t2 = ~0u;
+  if (pllhip_is_tip(c, clv))
+  {
+    g.type = FUSED_G_TIP;
+    t1 = clv;
+  }
+  else if (deferring_op[clv] >= 0)
+  {
+    const pllhip_op_t & d = ops[deferring_op[clv]];
+    g.type = FUSED_G_CHERRY_NEW;
+    t1 = d.child1_clv;
+    t2 = d.child2_clv;
+    g.c_lmat = pllhip_pmat_ptr(c, d.child1_matrix);
+    g.c_rmat = pllhip_pmat_ptr(c, d.child2_matrix);
+  }
+  else
+  {
+    const pllhip_ctx::deferred_clv & d = c->deferred[clv];
+    g.type = FUSED_G_CHERRY_KEPT;
+    t1 = d.tip1;
+    t2 = d.tip2;
+    g.kept = pllhip_deferred_table(c, clv);
+  }
+  g.row1 = pllhip_tip_ptr(c, t1);
+  if (t2 != ~0u) g.row2 = pllhip_tip_ptr(c, t2);
+  rows2[0] = t1 + 1;
+  rows2[1] = t2 + 1;
+  return g;
+}
+
+// The ops the kernel runs where the list defers (k.dd): k.ops, their extras and rows; k.args / k.kinds, resolve_op's of
+// the caller's list in, theirs out; and the deferred ops' table jobs and records.
+static void keep_undeferred_ops(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int count, DnaListKept & k)
+{
+  const FusedDeferral & dd = k.dd;
+  std::vector<PartialsArgs> & args = k.args;
+  std::vector<int> & kinds = k.kinds;
   std::vector<int> deferring_op(c->clv.size(), -1);
   for (unsigned int i = 0; i < count; ++i)
     if (dd.defer[i]) deferring_op[ops[i].parent_clv] = (int)i;
-  // (rows2: tip index + 1 of row1 / row2, 0 none)
   auto operand = [&](unsigned int clv, unsigned int matrix, unsigned int * rows2) {
-    FusedOperand g;
-    memset(&g, 0, sizeof(g));
-    g.mat = pllhip_pmat_ptr(c, matrix);
-    unsigned int t1, t2 = ~0u;
-    if (pllhip_is_tip(c, clv))
-    {
-      g.type = FUSED_G_TIP;
-      t1 = clv;
-    }
-    else if (deferring_op[clv] >= 0)
-    {
-      const pllhip_op_t & d = ops[deferring_op[clv]];
-      g.type = FUSED_G_CHERRY_NEW;
-      t1 = d.child1_clv;
-      t2 = d.child2_clv;
-      g.c_lmat = pllhip_pmat_ptr(c, d.child1_matrix);
-      g.c_rmat = pllhip_pmat_ptr(c, d.child2_matrix);
-    }
-    else
-    {
-      const pllhip_ctx::deferred_clv & d = c->deferred[clv];
-      g.type = FUSED_G_CHERRY_KEPT;
-      t1 = d.tip1;
-      t2 = d.tip2;
-      g.kept = pllhip_deferred_table(c, clv);
-    }
-    g.row1 = pllhip_tip_ptr(c, t1);
-    if (t2 != ~0u) g.row2 = pllhip_tip_ptr(c, t2);
-    rows2[0] = t1 + 1;
-    rows2[1] = t2 + 1;
-    return g;
+    return gathered_operand(c, ops, deferring_op, clv, matrix, rows2);
   };
   std::vector<PartialsArgs> kargs;
   std::vector<int> kkinds;
@@ -841,7 +866,7 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
     if (dd.defer[i])
     {
       k.keep_jobs.push_back(FusedPairJob{args[i].lmat, args[i].rmat, pllhip_deferred_table(c, op.parent_clv), 1ull, nullptr, nullptr});
-      k.new_deferred.insert(k.new_deferred.end(), {op.parent_clv, op.child1_clv, op.child2_clv, (unsigned int)(op.parent_scaler + 1)});
+      k.new_deferred.push_back({op.parent_clv, op.child1_clv, op.child2_clv, op.parent_scaler});
       continue;
     }
     PartialsArgs a = args[i];
@@ -883,54 +908,87 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
   }
   args.swap(kargs);
   kinds.swap(kkinds);
+}
+
+// The kept plan (ctx.hpp: fused_last_*) stands for a list, a set of deferred CLVs -- the same list only while none of
+// them has been materialised, dropped or pinned since, defer_epoch; the launch then defers the same ones again -- and
+// the edge hint it was built for, folded or not.  Returns true where it stood for this call: *rc is the call's result.
+static bool replay_kept_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsigned int full_count, bool edge_wanted, int * rc)
+{
+  if (c->fused_last_ops.size() != full_count || c->fused_debug || c->fused_last_epoch != c->layout_epoch ||
+      c->fused_last_defer_epoch != c->defer_epoch || c->fused_last_hint_on != edge_wanted ||
+      (edge_wanted && !(c->fused_last_hint == c->edge_hint)) ||
+      memcmp(c->fused_last_ops.data(), full_ops, (size_t)full_count * sizeof(pllhip_op_t)) != 0)
+    return false;
+  pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
+  c->defer_stats[1] += c->fused_last_deferred.size();
+  c->unstored_stats[1] += c->fused_last_unstored.size();
+  c->fold_stats[1] += c->fused_last_nfolded;
+  *rc = pllhip_relaunch_fused(c);
+  if (*rc == 0 && c->fused_last_edge)
+  {
+    c->edge_terms_valid = true;
+    c->edge_terms_used = false;
+    c->edge_terms_req = c->fused_last_hint;
+    ++c->edge_stats[0];
+  }
+  return true;
+}
+
+// resolve_op of every op of the caller's list, then the deferral: k.run_ops / args / kinds are what the kernel runs
+static int resolve_and_defer(pllhip_ctx * c, const pllhip_op_t * full_ops, unsigned int full_count, DnaListKept & k)
+{
+  k.args.resize(full_count);
+  k.kinds.resize(full_count);
+  for (unsigned int i = 0; i < full_count; ++i)
+  {
+    int mode;
+    const int rc = resolve_op(c, full_ops[i], k.args[i], k.kinds[i], mode);
+    if (rc) return rc;
+  }
+  bool any = false;
+  const int rc = defer_cherries(c, full_ops, full_count, k, &any);
+  if (rc) return rc;
+  if (any) keep_undeferred_ops(c, full_ops, full_count, k);
+  // (the caller's list: full_ops; the ops the kernel runs: run_ops)
+  k.run_ops = k.ops.empty() ? full_ops : k.ops.data();
+  k.run_count = k.ops.empty() ? full_count : (unsigned int)k.ops.size();
   return 0;
 }
 
-// 4 states, more than one op, no site repeats: the whole list in one site-blocked launch.  *per_level = true: a list
-// shape the kernel does not take -- the per-level launches follow, on the caller's list with every deferral flushed;
-// else the call is over and the value returned is its result (0, or an error: HIP's are positive numbers).
-static int update_partials_dna_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsigned int full_count,
-                                    size_t fused_tile_sites, bool * per_level)
+// The edge epilogue (pllhip_fused_plan_list): the hinted evaluation, where the context has both ends as CLVs.  (What
+// the list materialised first is no longer deferred here; its address handed out: anybody may write it.)
+static void resolve_edge(pllhip_ctx * c, DnaListKept & k)
 {
-  *per_level = false;
-  // (deferred cherries: the kept plan stands for a set of deferred CLVs -- it is the same list only while none of
-  // them has been materialised, dropped or pinned since, defer_epoch; the launch then defers the same ones again)
-  // (the edge epilogue, ctx.hpp: edge_hint -- the kept plan stands for the hint it was built for, folded or not)
-  const bool edge_wanted = c->edge_fold && c->edge_hint_on && !c->is_shard && c->sh.rate_cats <= 4 && !c->sh.rate_scalers &&
-                           !c->asc_type && !c->sh.asc_states && !c->any_prop_invar && !c->comm;
-  if (c->fused_last_ops.size() == full_count && !c->fused_debug &&
-      c->fused_last_epoch == c->layout_epoch && c->fused_last_defer_epoch == c->defer_epoch &&
-      c->fused_last_hint_on == edge_wanted && (!edge_wanted || c->fused_last_hint == c->edge_hint) &&
-      memcmp(c->fused_last_ops.data(), full_ops, (size_t)full_count * sizeof(pllhip_op_t)) == 0)
+  FusedEdge & fedge = k.edge;
+  memset(&fedge, 0, sizeof(fedge));
+  const pllhip_ctx::edge_req & q = c->edge_hint;
+  bool list_scales = false;
+  for (unsigned int i = 0; i < k.run_count; ++i) list_scales = list_scales || k.args[i].pscaler != nullptr;
+  k.edge_ok = k.edge_wanted && q.parent_clv < c->clv.size() && q.child_clv < c->clv.size() && c->clv[q.parent_clv] &&
+              c->clv[q.child_clv] && q.matrix_index < c->sh.prob_matrices && q.parent_scaler < (int)c->sh.scale_buffers &&
+              q.child_scaler < (int)c->sh.scale_buffers && (list_scales || (q.parent_scaler < 0 && q.child_scaler < 0));
+  if (!k.edge_ok) return;
+  const unsigned int ends[2] = {q.parent_clv, q.child_clv};
+  for (int t = 0; t < 2; ++t)
   {
-    pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
-    c->defer_stats[1] += c->fused_last_deferred.size() / 4;
-    c->unstored_stats[1] += c->fused_last_unstored.size() / 6;
-    c->fold_stats[1] += c->fused_last_nfolded;
-    const int rc = pllhip_relaunch_fused(c);
-    if (rc == 0 && c->fused_last_edge)
-    {
-      c->edge_terms_valid = true;
-      c->edge_terms_used = false;
-      c->edge_terms_req = c->fused_last_hint;
-      ++c->edge_stats[0];
-    }
-    return rc;
+    fedge.deferred_before[t] = ends[t] < c->deferred.size() && c->deferred[ends[t]].on;
+    fedge.pinned[t] = ends[t] < c->clv_pinned.size() && c->clv_pinned[ends[t]];
   }
-  c->fused_last_ops.clear();
-  std::vector<PartialsArgs> args(full_count);
-  std::vector<int> kinds(full_count), modes(full_count);
-  for (unsigned int i = 0; i < full_count; ++i)
-  {
-    int rc = resolve_op(c, full_ops[i], args[i], kinds[i], modes[i]);
-    if (rc) return rc;
-  }
-  DnaListKept k;
-  int rc = defer_cherries(c, full_ops, full_count, args, kinds, k);
-  if (rc) return rc;
-  // (the caller's list: full_ops; the ops the kernel runs: ops)
-  const pllhip_op_t * const ops = k.ops.empty() ? full_ops : k.ops.data();
-  const unsigned int count = k.ops.empty() ? full_count : (unsigned int)k.ops.size();
+  fedge.parent_clv = q.parent_clv;
+  fedge.child_clv = q.child_clv;
+  fedge.parent_scaler = q.parent_scaler;
+  fedge.child_scaler = q.child_scaler;
+  fedge.parent = c->clv[q.parent_clv];
+  fedge.child = c->clv[q.child_clv];
+  fedge.pscaler = pllhip_scaler_ptr(c, q.parent_scaler);
+  fedge.cscaler = pllhip_scaler_ptr(c, q.child_scaler);
+  fedge.pmat = pllhip_pmat_ptr(c, q.matrix_index);
+}
+
+// The planner's whole sequence (partials_fused.hpp: pllhip_fused_plan_walk) with this instance's configuration.
+static int plan_list(pllhip_ctx * c, size_t fused_tile_sites, DnaListKept & k)
+{
   const FusedExtra * const extras = k.extras.empty() ? nullptr : k.extras.data();
   FusedGeom geom = {c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0};
   if (extras) geom.as_tip = k.dd.as_tip.data();
@@ -943,190 +1001,135 @@ static int update_partials_dna_list(pllhip_ctx * c, const pllhip_op_t * full_ops
   // PLLHIP_FUSED_SEGMENTS=0 / n: never / up to n whatever the size.
   unsigned int max_segs = (size_t)c->sh.sites / fused_tile_sites < (size_t)c->num_cus * 12 * 8 ? PLLHIP_FUSED_MAX_SEGS : 1u;
   if (const char * e = pllhip_env("PLLHIP_FUSED_SEGMENTS")) max_segs = (unsigned int)std::max(1, atoi(e));
-  // The edge epilogue (pllhip_fused_plan_list): the hinted evaluation, where the context has both ends as CLVs.  (What
-  // the list materialised first is no longer deferred here; its address handed out: anybody may write it.)
-  FusedEdge fedge;
-  memset(&fedge, 0, sizeof(fedge));
-  const pllhip_ctx::edge_req & q = c->edge_hint;
-  bool list_scales = false;
-  for (unsigned int i = 0; i < count; ++i) list_scales = list_scales || args[i].pscaler != nullptr;
-  const bool edge_ok = edge_wanted && q.parent_clv < c->clv.size() && q.child_clv < c->clv.size() && c->clv[q.parent_clv] &&
-                       c->clv[q.child_clv] && q.matrix_index < c->sh.prob_matrices && q.parent_scaler < (int)c->sh.scale_buffers &&
-                       q.child_scaler < (int)c->sh.scale_buffers && (list_scales || (q.parent_scaler < 0 && q.child_scaler < 0));
-  if (edge_ok)
-  {
-    const unsigned int ends[2] = {q.parent_clv, q.child_clv};
-    for (int t = 0; t < 2; ++t)
-    {
-      fedge.deferred_before[t] = ends[t] < c->deferred.size() && c->deferred[ends[t]].on;
-      fedge.pinned[t] = ends[t] < c->clv_pinned.size() && c->clv_pinned[ends[t]];
-    }
-    fedge.parent_clv = q.parent_clv;
-    fedge.child_clv = q.child_clv;
-    fedge.parent_scaler = q.parent_scaler;
-    fedge.child_scaler = q.child_scaler;
-    fedge.parent = c->clv[q.parent_clv];
-    fedge.child = c->clv[q.child_clv];
-    fedge.pscaler = pllhip_scaler_ptr(c, q.parent_scaler);
-    fedge.cscaler = pllhip_scaler_ptr(c, q.child_scaler);
-    fedge.pmat = pllhip_pmat_ptr(c, q.matrix_index);
-  }
-  FusedListPlan lp;
-  rc = pllhip_fused_plan_list(geom, ops, args.data(), kinds.data(), extras, count, max_segs, slot_counts + skip, 2u - skip,
-                              edge_ok ? &fedge : nullptr, k.dd, lp);
-  if (rc < 0) return rc;
-  // Pair products (deferred.hip): the gathered-gathered parents the finished plan lets go unstored, where the instance
-  // defers at all (a kind-3 op exists only then) and the pool has the two tables each needs.
-  unsigned int nunstored = 0, nfolded = 0;
-  if (rc == 0 && extras && c->unstored_pairs && c->cherry_deferral && pllhip_deferred_table(c, 0, 1))
-    nunstored = pllhip_fused_unstored(geom, ops, count, lp.plans, edge_ok ? &fedge : nullptr, c->clv_pinned.data());
-  // Folded pair products (pllhip_set_pair_fold; partials_fused.hpp: pllhip_fused_fold): an unstored parent with one
-  // reader, an inner-inner op, is not walked at all -- the list is planned once more without those ops, their readers'
-  // operands on that side products of two gathered factors, and the unstored rule applied to what is left.  A second
-  // plan the planner refuses, or one of fewer than two ops, leaves the first.
-  std::vector<unsigned char> fold;
-  FusedFoldList fl;
-  FusedListPlan first_lp;
-  FusedEdge first_edge = fedge;
-  const pllhip_op_t * wops = ops;      // the ops the plan was made of, and their rows (stride wstride)
-  const unsigned int * wrows = k.rows.data();
-  size_t wstride = 4;
-  if (nunstored && c->pair_fold && pllhip_fused_fold(ops, kinds.data(), count, lp.plans, fold))
-  {
-    pllhip_fused_fold_list(geom, ops, args.data(), kinds.data(), extras, k.rows.data(), count, fold, fl);
-    const unsigned int n2 = (unsigned int)fl.ops.size();
-    for (unsigned int j = 0; j < n2; ++j)
-      for (int s = 0; s < 2; ++s)
-        if (fl.prod_op[2 * (size_t)j + s])
-        {
-          const unsigned int clv = ops[fl.prod_op[2 * (size_t)j + s] - 1].parent_clv;
-          fl.extras[j].pkeep[s][0] = pllhip_deferred_table(c, clv, 0);
-          fl.extras[j].pkeep[s][1] = pllhip_deferred_table(c, clv, 1);
-        }
-    FusedGeom geom2 = geom;
-    geom2.as_tip = fl.as_tip.data();
-    FusedListPlan lp2;
-    FusedEdge fedge2 = fedge;
-    // (the edge epilogue where the first plan was offered it: a list in segments stays without, however short its
-    // segments have become)
-    const bool edge2 = edge_ok && lp.plans.size() == 1;
-    const int rc2 = n2 < 2 ? 1 : pllhip_fused_plan_list(geom2, fl.ops.data(), fl.args.data(), fl.kinds.data(), fl.extras.data(), n2,
-                                                        max_segs, slot_counts + skip, 2u - skip, edge2 ? &fedge2 : nullptr, k.dd, lp2);
-    if (rc2 < 0) return rc2;
-    if (rc2 == 0)
-    {
-      // (the first plan is kept: should the launch not take the second -- more character batches or tables than it
-      // encodes --, the list runs as it would have without folding)
-      first_lp = lp;
-      first_edge = fedge;
-      lp.plans.swap(lp2.plans);
-      lp.nslots = lp2.nslots;
-      lp.taken = lp2.taken;
-      lp.reloads = lp2.reloads;
-      lp.folded = lp2.folded;
-      fedge = fedge2;
-      wops = fl.ops.data();
-      wrows = fl.rows8.data();
-      wstride = 8;
-      nunstored = pllhip_fused_unstored(geom2, wops, n2, lp.plans, edge_ok ? &fedge : nullptr, c->clv_pinned.data());
-      for (unsigned int i = 0; i < count; ++i)
-        if (fold[i])
-        {
-          // (a folded parent is an unstored pair product whose counts are not in HBM either: bit 31 of the scaler word)
-          const pllhip_op_t & op = ops[i];
-          const unsigned int * rows = &k.rows[4 * (size_t)i];
-          k.new_unstored.insert(k.new_unstored.end(), {op.parent_clv, (unsigned int)(op.parent_scaler + 1) | 0x80000000u, rows[0], rows[1], rows[2], rows[3]});
-          ++nfolded;
-        }
-    }
-  }
-  // the walked parents the plan leaves unstored: where their tables are kept, and what the context remembers of them
-  auto keep_unstored = [&]() {
-    for (auto & plan : lp.plans)
-      for (FusedOp & f : plan)
-        if (f.unstored)
-        {
-          const pllhip_op_t & op = wops[f.list_pos];
-          f.keep[0] = pllhip_deferred_table(c, op.parent_clv, 0);
-          f.keep[1] = pllhip_deferred_table(c, op.parent_clv, 1);
-          const unsigned int * rows = &wrows[wstride * (size_t)f.list_pos];
-          k.new_unstored.insert(k.new_unstored.end(), {op.parent_clv, (unsigned int)(op.parent_scaler + 1), rows[0], rows[1], rows[2], rows[3]});
-        }
+  // Pair products (deferred.hip): gathered-gathered parents may go unstored where the instance defers at all (a kind-3
+  // op exists only then) and the pool has the two tables each needs; folded into their reader: pllhip_set_pair_fold.
+  const bool may_unstore = extras && c->unstored_pairs && c->cherry_deferral && pllhip_deferred_table(c, 0, 1);
+  return pllhip_fused_plan_walk(geom, k.run_ops, k.args.data(), k.kinds.data(), extras, k.rows.data(), k.run_count, max_segs,
+                                slot_counts + skip, 2u - skip, k.edge_ok ? &k.edge : nullptr, k.dd, c->clv_pinned.data(),
+                                may_unstore, c->pair_fold, k.walk);
+}
+
+// The pool's tables of the plan about to be launched -- where a walked unstored parent's two factor tables are kept,
+// and those of a product folded into a reader -- and what the context is to remember of both.
+static void attach_tables(pllhip_ctx * c, DnaListKept & k)
+{
+  FusedWalk & w = k.walk;
+  k.new_unstored.clear();
+  auto remember = [&](const pllhip_op_t & op, const unsigned int * rows, bool folded) {
+    k.new_unstored.push_back({op.parent_clv, op.parent_scaler, {rows[0], rows[1], rows[2], rows[3]}, folded});
   };
-  if (nunstored) keep_unstored();
+  // (a folded parent is an unstored pair product whose counts are not in HBM either)
+  for (unsigned int i = 0; w.nfolded && i < k.run_count; ++i)
+    if (w.fold[i]) remember(k.run_ops[i], &k.rows[4 * (size_t)i], true);
+  if (!w.nunstored && !w.nfolded) return;
+  for (auto & plan : w.plan.plans)
+    for (FusedOp & f : plan)
+    {
+      for (int s = 0; s < 2; ++s)
+        if (const pllhip_op_t * from = w.folded_into(f, s))
+          for (int t = 0; t < 2; ++t) f.pkeep[s][t] = pllhip_deferred_table(c, from->parent_clv, t);
+      if (!f.unstored) continue;
+      const pllhip_op_t & op = w.op_of(f);
+      for (int t = 0; t < 2; ++t) f.keep[t] = pllhip_deferred_table(c, op.parent_clv, t);
+      remember(op, w.rows_of(f), false);
+    }
+}
+
+// Returns pllhip_launch_fused's codes.  A folded plan the launch does not take -- more character batches or tables
+// than it encodes -- gives way to the first one: the list runs as it would have without folding.
+static int launch_list(pllhip_ctx * c, DnaListKept & k)
+{
+  FusedWalk & w = k.walk;
+  // (the hint the plan stands for; the launch takes the frequencies' places from it)
+  c->fused_last_hint_on = k.edge_wanted;
+  c->fused_last_hint = c->edge_hint;
+  const std::vector<FusedPairJob> * const keep_jobs = k.keep_jobs.empty() ? nullptr : &k.keep_jobs;
+  int rc = 1;
+  for (int attempt = 0; attempt < 2 && rc == 1; ++attempt)
+  {
+    if (attempt == 1)
+    {
+      if (!w.replanned) break;
+      w.take_first();
+    }
+    attach_tables(c, k);
+    c->fused_last_nfolded = w.nfolded; // (the launch sizes its share of counter tiles by the list the caller handed over)
+    rc = pllhip_launch_fused(c, w.plan.plans, w.plan.nslots, keep_jobs, w.plan.folded ? &w.edge : nullptr);
+  }
+  if (rc != 0) c->fused_last_nfolded = 0;
+  return rc;
+}
+
+// The list has run: the deferrals it ends and begins, the pair products it leaves unstored, the kept plan.
+static void commit_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsigned int full_count, const DnaListKept & k)
+{
+  if (k.walk.plan.folded)
+  {
+    c->edge_terms_valid = true;
+    c->edge_terms_used = false;
+    c->edge_terms_req = c->edge_hint;
+    ++c->edge_stats[0];
+  }
+  for (unsigned int i : k.dd.dropped) pllhip_deferred_drop(c, i);
+  for (const pllhip_ctx::deferred_cherry & n : k.new_deferred)
+  {
+    pllhip_deferred_drop(c, n.clv);
+    pllhip_ctx::deferred_clv & d = c->deferred[n.clv];
+    d.on = true;
+    d.tip1 = n.tip1;
+    d.tip2 = n.tip2;
+    d.scaler = n.scaler;
+    if (n.scaler >= 0) c->deferred_sc_owner[n.scaler] = (int)n.clv;
+    ++c->n_deferred;
+  }
+  for (const pllhip_ctx::unstored_product & n : k.new_unstored)
+  {
+    pllhip_deferred_drop(c, n.clv);
+    pllhip_ctx::deferred_clv & d = c->deferred[n.clv];
+    d.on = d.pair = true;
+    d.folded = n.folded;
+    if (d.folded) ++c->n_folded;
+    for (int r = 0; r < 4; ++r) d.rows[r] = n.rows[r];
+    d.scaler = n.scaler;
+    // (its counts are in HBM -- a folded product's are not --, but they define the CLV: whoever touches them stores
+    // it first)
+    if (n.scaler >= 0) c->deferred_sc_owner[n.scaler] = (int)n.clv;
+    ++c->n_deferred;
+    ++c->n_unstored;
+  }
+  c->defer_stats[1] += k.new_deferred.size();
+  c->unstored_stats[1] += k.new_unstored.size();
+  c->fold_stats[1] += k.walk.nfolded;
+  if (k.walk.nfolded) ++c->fold_stats[2];
+  c->fused_last_unstored = k.new_unstored;
+  c->fused_last_deferred = k.new_deferred;
+  c->fused_last_defer_epoch = c->defer_epoch;
+  c->fused_last_ops.assign(full_ops, full_ops + full_count);
+}
+
+// 4 states, more than one op, no site repeats: the whole list in one site-blocked launch.  *per_level = true: a list
+// shape the kernel does not take -- the per-level launches follow, on the caller's list with every deferral flushed;
+// else the call is over and the value returned is its result (0, or an error: HIP's are positive numbers).
+static int update_partials_dna_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsigned int full_count,
+                                    size_t fused_tile_sites, bool * per_level)
+{
+  *per_level = false;
+  // (the edge epilogue, ctx.hpp: edge_hint)
+  const bool edge_wanted = c->edge_fold && c->edge_hint_on && !c->is_shard && c->sh.rate_cats <= 4 && !c->sh.rate_scalers &&
+                           !c->asc_type && !c->sh.asc_states && !c->any_prop_invar && !c->comm;
+  int rc = 0;
+  if (replay_kept_list(c, full_ops, full_count, edge_wanted, &rc)) return rc;
+  c->fused_last_ops.clear();
+  DnaListKept k;
+  k.edge_wanted = edge_wanted;
+  if ((rc = resolve_and_defer(c, full_ops, full_count, k))) return rc;
+  resolve_edge(c, k);
+  if ((rc = plan_list(c, fused_tile_sites, k)) < 0) return rc;
   if (rc == 0)
   {
     pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
-    // (the hint the plan stands for; the launch takes the frequencies' places from it)
-    c->fused_last_hint_on = edge_wanted;
-    c->fused_last_hint = c->edge_hint;
-    c->fused_last_nfolded = nfolded; // (the launch sizes its share of counter tiles by the list the caller handed over)
-    rc = pllhip_launch_fused(c, lp.plans, lp.nslots, k.keep_jobs.empty() ? nullptr : &k.keep_jobs, lp.folded ? &fedge : nullptr);
-    if (rc == 1 && nfolded)
-    {
-      // the launch does not take the folded plan: the first one, whose unstored marks still stand
-      lp = first_lp;
-      fedge = first_edge;
-      wops = ops;
-      wrows = k.rows.data();
-      wstride = 4;
-      nfolded = 0;
-      k.new_unstored.clear();
-      keep_unstored();
-      c->fused_last_nfolded = 0;
-      rc = pllhip_launch_fused(c, lp.plans, lp.nslots, k.keep_jobs.empty() ? nullptr : &k.keep_jobs, lp.folded ? &fedge : nullptr);
-    }
-    if (rc != 0) c->fused_last_nfolded = 0;
-    if (rc == 0)
-    {
-      if (lp.folded)
-      {
-        c->edge_terms_valid = true;
-        c->edge_terms_used = false;
-        c->edge_terms_req = c->edge_hint;
-        ++c->edge_stats[0];
-      }
-      // the deferrals this list ends and begins
-      for (unsigned int i : k.dd.dropped) pllhip_deferred_drop(c, i);
-      for (size_t t = 0; t < k.new_deferred.size(); t += 4)
-      {
-        const unsigned int clv = k.new_deferred[t];
-        const int sc = (int)k.new_deferred[t + 3] - 1;
-        pllhip_deferred_drop(c, clv);
-        pllhip_ctx::deferred_clv & d = c->deferred[clv];
-        d.on = true;
-        d.tip1 = k.new_deferred[t + 1];
-        d.tip2 = k.new_deferred[t + 2];
-        d.scaler = sc;
-        if (sc >= 0) c->deferred_sc_owner[sc] = (int)clv;
-        ++c->n_deferred;
-      }
-      for (size_t t = 0; t < k.new_unstored.size(); t += 6)
-      {
-        const unsigned int clv = k.new_unstored[t];
-        const int sc = (int)(k.new_unstored[t + 1] & 0x7fffffffu) - 1;
-        pllhip_deferred_drop(c, clv);
-        pllhip_ctx::deferred_clv & d = c->deferred[clv];
-        d.on = d.pair = true;
-        d.folded = (k.new_unstored[t + 1] >> 31) != 0;
-        if (d.folded) ++c->n_folded;
-        for (int r = 0; r < 4; ++r) d.rows[r] = k.new_unstored[t + 2 + r];
-        d.scaler = sc;
-        // (its counts are in HBM -- a folded product's are not --, but they define the CLV: whoever touches them stores
-        // it first)
-        if (sc >= 0) c->deferred_sc_owner[sc] = (int)clv;
-        ++c->n_deferred;
-        ++c->n_unstored;
-      }
-      c->defer_stats[1] += k.new_deferred.size() / 4;
-      c->unstored_stats[1] += k.new_unstored.size() / 6;
-      c->fold_stats[1] += nfolded;
-      if (nfolded) ++c->fold_stats[2];
-      c->fused_last_unstored = k.new_unstored;
-      c->fused_last_deferred = k.new_deferred;
-      c->fused_last_defer_epoch = c->defer_epoch;
-      c->fused_last_ops.assign(full_ops, full_ops + full_count);
-    }
+    rc = launch_list(c, k);
+    if (rc == 0) commit_list(c, full_ops, full_count, k);
     if (rc <= 0) return rc;
   }
   *per_level = true;

@@ -1046,87 +1046,58 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   return 0;
 }
 
-// Encode the plans for the device (FusedRec in partials_fused.hpp) -- one per segment: two header records that
-// stand for ops -2 and -1, one record per op, one of padding (the last op's look-ahead load) -- then the segment
-// table, the reload sources, the pair-table jobs, the character rows' addresses.  Returns 1 if the list is not one
-// the kernel takes.
-int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
-                        const std::vector<FusedPairJob> * keep_jobs, const FusedEdge * edge)
-{
-  const unsigned int nsegs = (unsigned int)plans.size();
-  if (edge && (nsegs != 1 || plans[0].size() < 2 || c->sh.rate_cats > 4 || c->sh.rate_scalers)) return 1;
-  if (edge && !c->d_edge_terms)
-    HIP_TRY(hipMalloc((void **)&c->d_edge_terms, ((size_t)c->sh.sites + PLLHIP_TAIL_SITES) * sizeof(double)));
-  unsigned int count = 0, longest = 0;
-  for (const auto & plan : plans)
-  {
-    count += (unsigned int)plan.size();
-    longest = std::max(longest, (unsigned int)plan.size());
-  }
-  const unsigned int R = c->sh.rate_cats;
-  if (count > PLLHIP_FUSED_MAX_OPS || nsegs < 1 || nsegs > PLLHIP_FUSED_MAX_SEGS) return 1;
-  // pair tables of the ops with a gathered factor (k_dna_pair_tables), carved from one device buffer
-  // (the kernel instances of 8 categories and of per-rate scalers have no second gather: partials.hip defers nothing there)
-  const size_t per = (size_t)256 * R * 4; // doubles per table
-  size_t ntab = 0;
-  for (const auto & plan : plans)
-    for (const FusedOp & f : plan)
-    {
-      if ((f.kind == 3 || f.prod[0] || f.prod[1]) && (R > 4 || c->sh.rate_scalers)) return 1;
-      // (a folded product is two factors; one on the right only does not exist: fused_plan.hip presents it "left")
-      if (f.prod[1] && !f.prod[0]) return 1;
-      ntab += f.prod[1] ? 4 : f.prod[0] ? 2 : (f.kind >= 1) + (f.kind == 3);
-    }
-  if (ntab * per * sizeof(double) > 0xffffffffull ||
-      (size_t)c->sh.prob_matrices * c->pmat_elems * sizeof(double) > 0xffffffffull)
-    return 1;
-  if (c->pairtab_elems < ntab * per)
-  {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_pairtab) HIP_TRY(hipFree(c->d_pairtab));
-    c->d_pairtab = nullptr;
-    HIP_TRY(hipMalloc((void **)&c->d_pairtab, ntab * per * sizeof(double)));
-    c->pairtab_elems = ntab * per;
-    ++c->layout_epoch;
-  }
-  // the row of zeros that lanes without a tip row fetch their "characters" from
-  if (!c->fused_zero_row)
-  {
-    const size_t bytes = (size_t)c->sh.sites + PLLHIP_TAIL_SITES + 256;
-    HIP_TRY(hipMalloc((void **)&c->fused_zero_row, bytes));
-    HIP_TRY(hipMemsetAsync(c->fused_zero_row, 0, bytes, c->stream));
-  }
-  const unsigned int J = PLLHIP_FUSED_J;
-  const unsigned int sps = 64 / (2 * R);
-  const FusedSlotSize slot = pllhip_fused_slot_size(R, c->sh.rate_scalers != 0);
-  const unsigned int slot_bytes = slot.tile_bytes, count_bytes = slot.count_bytes;
-  if ((size_t)nslots * slot_bytes > 0xffffu) return 1;
+// ---- A planned list on its way to the device: admission, encoding, upload, launch (pllhip_launch_fused below) ----
 
-  std::vector<FusedRec> recs;
-  std::vector<FusedSeg> segs(nsegs);
-  std::vector<FusedSrc> srcs;
-  std::vector<FusedPairJob> jobs;
-  std::vector<unsigned long long> rowtab;
-  int mode = SCALE_NONE;
-  const unsigned int lpr = J * sps >= 16 ? J * sps / 16 : 1; // lanes per row
-  for (unsigned int sg = 0; sg < nsegs; ++sg)
-  {
-  const std::vector<FusedOp> & plan = plans[sg];
-  const unsigned int n = (unsigned int)plan.size();
-  // Tip rows in the order the segment uses them, in batches of what a wave's 64 x 16 bytes hold of a tile
-  // (pllhip_fused_char_batches).  rowtab[batch][lane]: the address the lane fetches from (+ the tile's first
-  // site); lanes without a row fetch zeros.  Batches are numbered across the segments.
-  // every op's gathered operands (FusedOperand): what the planner was told about deferred cherries, else what the
-  // op's kind says -- the tip of a tip-inner op, the finished parent of a tip-tip op
-  // (up to four per op, in the order the kernel gathers them: one or two factors of the op itself, or the two factors
-  // of a folded product on the left, then those of one on the right)
-  struct GatherSets { FusedOperand g[4]; double * copy[4]; };
-  std::vector<GatherSets> gx(n);
+// Every op's gathered operands (FusedOperand): what the planner was told about deferred cherries, else what the op's
+// kind says -- the tip of a tip-inner op, the finished parent of a tip-tip op.  Up to four per op, in the order the
+// kernel gathers them: one or two factors of the op itself, or the two factors of a folded product on the left, then
+// those of one on the right.  copy: where a factor table is written as well (the pool: an unstored or folded product's).
+struct FusedGatherSets
+{
+  FusedOperand g[4];
+  double * copy[4];
+};
+// One segment's gathers and where a wave finds their tip characters: rows in the order the segment uses them, in
+// batches of what a wave's 64 x 16 bytes hold of a tile (pllhip_fused_char_batches), numbered across the segments.
+struct FusedSegGathers
+{
+  std::vector<FusedGatherSets> gx;       // per position of the plan
+  std::vector<unsigned int> chars_of[4]; // FusedRec::chars .. chars4 of that op
+  std::vector<unsigned int> batch_of;
+  std::vector<unsigned int> table_of;    // byte offset of the op's first table: its tables follow each other (read only
+                                         // where the op's chars say it gathers)
+  unsigned int batch0 = 0, nbatches = 0;
+};
+// What the admission pass hands the encoder.
+struct FusedAdmitted
+{
+  std::vector<FusedSegGathers> segs;
+  size_t ntab = 0;                       // pair tables of the ops with a gathered factor (k_dna_pair_tables)
+  unsigned int count = 0, longest = 0;   // ops of all segments, of the longest
+};
+static size_t fused_table_doubles(unsigned int R) { return (size_t)256 * R * 4; }
+static unsigned int fused_lanes_per_row(unsigned int R)
+{
+  const unsigned int tile_sites = PLLHIP_FUSED_J * (64 / (2 * R));
+  return tile_sites >= 16 ? tile_sites / 16 : 1;
+}
+
+// The gathers of one segment, the first of its batches being batch0, of its tables *ntables (counted on).  Returns 1
+// for an op that is not what the planner makes (a malformed product or unstored op, gathers with a gap) or rows the
+// kernel cannot address: more than 255 batches, a row beyond lane 63.
+static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, bool rate_scalers, unsigned int batch0,
+                             size_t * ntables, FusedSegGathers & out)
+{
+  const unsigned int n = (unsigned int)plan.size(), lpr = fused_lanes_per_row(R);
+  out.gx.resize(n);
+  out.table_of.assign(n, 0);
   for (unsigned int pos = 0; pos < n; ++pos)
   {
     const FusedOp & f = plan[pos];
-    GatherSets & x = gx[pos];
+    FusedGatherSets & x = out.gx[pos];
     memset(&x, 0, sizeof(x));
+    // (only what the kernel can redirect and the planner marked: a reader without the slot would find nothing)
+    if (f.unstored && (f.kind != 3 || f.pslot < 0 || R > 4 || rate_scalers || !f.keep[0] || !f.keep[1])) return 1;
     if (f.prod[0] || f.prod[1])
     {
       // (only what the planner folds: an inner-inner reader, presented as gathered-inner or gathered-gathered)
@@ -1146,177 +1117,253 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
     if (f.g[0].type == FUSED_G_NONE && f.kind == 1) x.g[0] = FusedOperand{FUSED_G_TIP, f.ltip, nullptr, f.lmat, nullptr, nullptr, nullptr};
     if (f.g[0].type == FUSED_G_NONE && f.kind == 2) x.g[0] = FusedOperand{FUSED_G_PAIR, f.ltip, f.rtip, nullptr, f.lmat, f.rmat, nullptr};
     if (f.kind == 3 && (x.g[0].type == FUSED_G_NONE || x.g[1].type == FUSED_G_NONE)) return 1;
+    // (gathers are numbered without gaps: the kernel finds table k at k tables behind the first)
+    if (x.g[0].type == FUSED_G_NONE && x.g[1].type != FUSED_G_NONE) return 1;
     // (an unstored pair product: its factors are kept, deferred.hip)
     for (int o = 0; f.unstored && o < 2; ++o) x.copy[o] = f.keep[o];
   }
-  std::vector<unsigned int> chars_of[4] = {std::vector<unsigned int>(n, 0), std::vector<unsigned int>(n, 0),
-                                           std::vector<unsigned int>(n, 0), std::vector<unsigned int>(n, 0)};
-  std::vector<unsigned int> batch_of(n, 0);
-  const unsigned int batch0 = (unsigned int)(rowtab.size() / 64);
+  for (int k = 0; k < 4; ++k) out.chars_of[k].assign(n, 0);
+  out.batch_of.assign(n, 0);
+  out.batch0 = batch0;
+  std::vector<unsigned int> ntips(n, 0);
+  for (unsigned int pos = 0; pos < n; ++pos)
+    for (int k = 0; k < 4; ++k)
+      ntips[pos] |= (out.gx[pos].g[k].row1 ? 1u : 0u) << (2 * k) | (out.gx[pos].g[k].row2 ? 2u : 0u) << (2 * k);
+  unsigned int * const chars_out[4] = {out.chars_of[0].data(), out.chars_of[1].data(), out.chars_of[2].data(), out.chars_of[3].data()};
+  out.nbatches = pllhip_fused_char_batches8(ntips.data(), n, lpr, chars_out, out.batch_of.data());
+  if (batch0 + out.nbatches > 255 || 8 * lpr > 64) return 1;
+  for (unsigned int pos = 0; pos < n; ++pos)
   {
-    std::vector<unsigned int> ntips(n, 0);
-    for (unsigned int pos = 0; pos < n; ++pos)
-      for (int k = 0; k < 4; ++k) ntips[pos] |= (gx[pos].g[k].row1 ? 1u : 0u) << (2 * k) | (gx[pos].g[k].row2 ? 2u : 0u) << (2 * k);
-    unsigned int * const chars_out[4] = {chars_of[0].data(), chars_of[1].data(), chars_of[2].data(), chars_of[3].data()};
-    const unsigned int nbatches = pllhip_fused_char_batches8(ntips.data(), n, lpr, chars_out, batch_of.data());
-    if (batch0 + nbatches > 255 || 8 * lpr > 64) return 1;
-    rowtab.resize((size_t)(batch0 + nbatches) * 64, (unsigned long long)(uintptr_t)c->fused_zero_row);
-    for (unsigned int pos = 0; pos < n; ++pos)
+    out.batch_of[pos] += batch0;
+    if (out.gx[pos].g[0].type != FUSED_G_NONE) out.table_of[pos] = (unsigned int)(*ntables * fused_table_doubles(R) * sizeof(double));
+    for (int k = 0; k < 4; ++k)
     {
-      batch_of[pos] += batch0;
-      for (int k = 0; k < 4; ++k)
-      {
-        const unsigned char * rows[2] = {gx[pos].g[k].row1, gx[pos].g[k].row2};
-        const unsigned int lane0[2] = {PLLHIP_FUSED_CH_LPOS(chars_of[k][pos]), PLLHIP_FUSED_CH_RPOS(chars_of[k][pos])};
-        for (int o = 0; o < 2; ++o)
-          for (unsigned int l = 0; rows[o] && l < lpr; ++l)
-          {
-            if (lane0[o] + l >= 64) return 1;
-            rowtab[(size_t)batch_of[pos] * 64 + lane0[o] + l] = (unsigned long long)(uintptr_t)rows[o] + l * 16u;
-          }
-      }
+      const FusedOperand & g = out.gx[pos].g[k];
+      *ntables += g.type != FUSED_G_NONE;
+      if ((g.row1 && PLLHIP_FUSED_CH_LPOS(out.chars_of[k][pos]) + lpr > 64) || (g.row2 && PLLHIP_FUSED_CH_RPOS(out.chars_of[k][pos]) + lpr > 64))
+        return 1;
     }
   }
-  std::vector<unsigned int> table_of(n, 0); // byte offset of each op's first table: its tables follow each other (read only where the op's chars say it gathers)
+  return 0;
+}
+
+// (a) Admission: is this a list the kernel takes?  No HIP call, nothing of the context changed: returns 1 for every
+// shape the kernel or its records do not take, else 0 and what the encoder needs of the plans.
+static int fused_admit(const pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
+                       const FusedEdge * edge, FusedAdmitted & out)
+{
+  const unsigned int nsegs = (unsigned int)plans.size(), R = c->sh.rate_cats;
+  const bool rate_scalers = c->sh.rate_scalers != 0;
+  if (nsegs < 1 || nsegs > PLLHIP_FUSED_MAX_SEGS) return 1;
+  if (edge && (nsegs != 1 || plans[0].size() < 2 || R > 4 || rate_scalers || edge->op.lslot < 0 || edge->op.rslot < 0)) return 1;
+  size_t nsrcs = edge && edge->op.dma_flags ? 1 : 0;
+  for (const auto & plan : plans)
+  {
+    out.count += (unsigned int)plan.size();
+    out.longest = std::max(out.longest, (unsigned int)plan.size());
+    for (const FusedOp & f : plan)
+    {
+      // (the kernel instances of 8 categories and of per-rate scalers have no second gather: partials.hip defers nothing there)
+      if ((f.kind == 3 || f.prod[0] || f.prod[1]) && (R > 4 || rate_scalers)) return 1;
+      // (a folded product is two factors; one on the right only does not exist: fused_plan.hip presents it "left")
+      if (f.prod[1] && !f.prod[0]) return 1;
+      out.ntab += f.prod[1] ? 4 : f.prod[0] ? 2 : (f.kind >= 1) + (f.kind == 3);
+      nsrcs += f.dma_flags ? 1 : 0;
+    }
+  }
+  // (a record holds 32-bit offsets into the tables and the matrix arena, 16-bit ones into a wave's slots and a 16-bit
+  // number of the reload source)
+  if (out.count > PLLHIP_FUSED_MAX_OPS || nsrcs > 0xffffu) return 1;
+  if (out.ntab * fused_table_doubles(R) * sizeof(double) > 0xffffffffull ||
+      (size_t)c->sh.prob_matrices * c->pmat_elems * sizeof(double) > 0xffffffffull)
+    return 1;
+  if ((size_t)nslots * pllhip_fused_slot_size(R, rate_scalers).tile_bytes > 0xffffu) return 1;
+  out.segs.resize(nsegs);
+  unsigned int batch0 = 0;
+  size_t ngathers = 0;
+  for (unsigned int sg = 0; sg < nsegs; ++sg)
+  {
+    if (fused_seg_gathers(plans[sg], R, rate_scalers, batch0, &ngathers, out.segs[sg])) return 1;
+    batch0 += out.segs[sg].nbatches;
+  }
+  return ngathers > out.ntab ? 1 : 0;
+}
+
+// (b) The encoder: no HIP call either, every address it needs in FusedEncodeIn.
+struct FusedEncodeIn
+{
+  const double * pmatrix;         // the matrix arena
+  double * pairtab;               // room for FusedAdmitted::ntab tables
+  const unsigned char * zero_row; // what lanes without a tip row fetch their "characters" from
+  FusedSlotSize slot;
+  unsigned int rate_cats;
+  bool rate_scalers;
+};
+// The plans as the device reads them (FusedRec in partials_fused.hpp) -- per segment two header records that stand for
+// ops -2 and -1, one record per op, one of padding (the last op's look-ahead load) -- then the segment table, the
+// reload sources, the pair-table jobs, the character rows' addresses.
+struct FusedEncoded
+{
+  std::vector<FusedRec> recs;
+  std::vector<FusedSeg> segs;
+  std::vector<FusedSrc> srcs;
+  std::vector<FusedPairJob> jobs;
+  std::vector<unsigned long long> rowtab; // [batch][lane]: the address the lane fetches from (+ the tile's first site)
+  int mode = SCALE_NONE;
+  unsigned int longest = 0;
+};
+// what record `r` says about the ops ahead of position `pos` (pos may be -2, -1: the headers)
+static void fused_look_ahead(const FusedEncodeIn & in, const std::vector<FusedOp> & plan, const FusedSegGathers & ga,
+                             const FusedEdge * edge, FusedRec & r, long pos, std::vector<FusedSrc> & srcs)
+{
+  const long n = (long)plan.size();
+  const unsigned int slot_bytes = in.slot.tile_bytes, count_bytes = in.slot.count_bytes;
+  r.chars = r.chars2 = r.chars3 = r.chars4 = 0;
+  r.req_lmat = r.req_rmat = 0;
+  if (pos + 1 >= 0 && pos + 1 < n)
+  {
+    r.chars = ga.chars_of[0][pos + 1];
+    r.chars2 = ga.chars_of[1][pos + 1];
+    r.chars3 = ga.chars_of[2][pos + 1];
+    r.chars4 = ga.chars_of[3][pos + 1];
+  }
+  // (the edge pseudo-op at position n: its matrix is requested and staged as a right-hand one, like a tip-inner op's)
+  if (edge && pos + 2 == n) r.req_rmat = (unsigned int)((edge->pmat - in.pmatrix) * sizeof(double));
+  if (pos + 2 < n)
+  {
+    const FusedOp & f = plan[pos + 2];
+    // (the rows of op + 2 are fetched once op + 1's characters have been taken from the registers)
+    const unsigned int now = pos + 1 >= 0 ? ga.batch_of[pos + 1] : ga.batch0;
+    if (ga.batch_of[pos + 2] != now) r.chars |= PLLHIP_FUSED_CH_LOAD | ga.batch_of[pos + 2] << 24;
+    r.req_lmat = (unsigned int)((f.lmat - in.pmatrix) * sizeof(double));
+    r.req_rmat = (unsigned int)((f.rmat - in.pmatrix) * sizeof(double));
+  }
+  r.src = 0;
+  if (pos + 1 < 0 || pos + 1 >= n + (edge ? 1 : 0)) return;
+  const FusedOp & f = pos + 1 < n ? plan[pos + 1] : edge->op;
+  r.gather_off = pos + 1 < n ? ga.table_of[pos + 1] : 0u;
+  // (a reader of folded products runs as an inner-inner op: both matrices)
+  r.flags |= (f.kind == 0 || f.prod[0] ? 2u : (f.kind == 1 || f.kind == PLLHIP_FUSED_KIND_EDGE) ? 1u : 0u) << PLLHIP_FUSED_STAGE_SHIFT;
+  if (!f.dma_flags) return;
+  r.flags |= PLLHIP_FUSED_RELOAD_NEXT;
+  r.src = (unsigned short)srcs.size();
+  FusedSrc s;
+  memset(&s, 0, sizeof(s));
+  if (f.dma_flags & 1) { s.left_hbm = f.left_hbm; s.lsc_hbm = f.lsc_hbm; }
+  if (f.dma_flags & 2) { s.right_hbm = f.right_hbm; s.rsc_hbm = f.rsc_hbm; }
+  s.where = (unsigned long long)((f.lslot > 0 ? f.lslot : 0) * slot_bytes) |
+            (unsigned long long)((f.rslot > 0 ? f.rslot : 0) * slot_bytes) << 16 |
+            (unsigned long long)((f.lslot > 0 ? f.lslot : 0) * count_bytes) << 32 |
+            (unsigned long long)((f.rslot > 0 ? f.rslot : 0) * count_bytes) << 48;
+  srcs.push_back(s);
+}
+
+// the record of op f itself (its look-ahead part: fused_look_ahead)
+static void fused_fill_record(const FusedEncodeIn & in, const FusedOp & f, FusedRec & r)
+{
+  const unsigned int slot_bytes = in.slot.tile_bytes, count_bytes = in.slot.count_bytes;
+  r.flags = (unsigned int)f.kind & PLLHIP_FUSED_KIND_MASK;
+  if (f.prod[0])
+  {
+    // folded products: the kernel's inner-inner arithmetic, that side's operand formed from the gathered factors;
+    // the count inherited on that side is the product's own scale bit, where the reader passes its scale buffer
+    r.flags = PLLHIP_FUSED_LPROD | ((f.prod[0] & 2) ? PLLHIP_FUSED_LPSCALE : 0u) | ((f.prod[0] & 4) ? PLLHIP_FUSED_LCNT : 0u);
+    if (f.prod[1])
+      r.flags |= PLLHIP_FUSED_RPROD | ((f.prod[1] & 2) ? PLLHIP_FUSED_RPSCALE : 0u) | ((f.prod[1] & 4) ? PLLHIP_FUSED_RCNT : 0u);
+  }
+  if (f.pslot >= 0) r.flags |= PLLHIP_FUSED_HAS_PSLOT;
+  if (f.pscaler) r.flags |= PLLHIP_FUSED_SCALING;
+  if (f.unstored) r.flags |= PLLHIP_FUSED_UNSTORED;
+  if (f.kind == 0 && f.lsc_slot >= 0) r.flags |= PLLHIP_FUSED_LCNT;
+  if (f.kind != 2 && !f.prod[1] && f.rsc_slot >= 0) r.flags |= PLLHIP_FUSED_RCNT;
+  r.parent = (unsigned long long)(uintptr_t)f.parent;
+  r.pscaler = (unsigned long long)(uintptr_t)f.pscaler;
+  r.lslot_b = (unsigned short)((f.lslot > 0 ? f.lslot : 0) * slot_bytes);
+  r.rslot_b = (unsigned short)((f.rslot > 0 ? f.rslot : 0) * slot_bytes);
+  r.pslot_b = (unsigned short)((f.pslot > 0 ? f.pslot : 0) * slot_bytes);
+  r.lcnt_b = (unsigned short)((f.lsc_slot > 0 ? f.lsc_slot : 0) * count_bytes);
+  r.rcnt_b = (unsigned short)((f.rsc_slot > 0 ? f.rsc_slot : 0) * count_bytes);
+  r.pcnt_b = (unsigned short)((f.pslot > 0 ? f.pslot : 0) * count_bytes);
+  r.list_pos = (unsigned short)f.list_pos;
+}
+
+// one segment: its rows' addresses, its pair-table jobs, its records
+static void fused_encode_segment(const FusedEncodeIn & in, const std::vector<FusedOp> & plan, const FusedSegGathers & ga,
+                                 const FusedEdge * edge, FusedEncoded & out)
+{
+  const unsigned int n = (unsigned int)plan.size(), lpr = fused_lanes_per_row(in.rate_cats);
+  const size_t per = fused_table_doubles(in.rate_cats);
+  // lanes without a row fetch zeros
+  out.rowtab.resize((size_t)(ga.batch0 + ga.nbatches) * 64, (unsigned long long)(uintptr_t)in.zero_row);
   for (unsigned int pos = 0; pos < n; ++pos)
   {
     const FusedOp & f = plan[pos];
-    for (int o = 0; o < 4; ++o)
+    for (int k = 0; k < 4; ++k)
     {
-      const FusedOperand & g = gx[pos].g[o];
-      // (gathers are numbered without gaps: the kernel finds table k at k tables behind the first)
-      if (g.type == FUSED_G_NONE)
-      {
-        for (int later = o + 1; later < 4; ++later)
-          if (gx[pos].g[later].type != FUSED_G_NONE) return 1;
-        break;
-      }
-      const size_t index = jobs.size();
-      if (index >= ntab) return 1;
-      if (o == 0) table_of[pos] = (unsigned int)(index * per * sizeof(double));
-      double * tab = c->d_pairtab + index * per;
-      double * copy = gx[pos].copy[o];
-      if (g.type == FUSED_G_TIP) jobs.push_back(FusedPairJob{g.mat, nullptr, tab, 0ull, nullptr, nullptr, copy, 0ull});
-      else if (g.type == FUSED_G_PAIR) jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 1ull, nullptr, nullptr, copy, 0ull});
-      else if (g.type == FUSED_G_CHERRY_NEW) jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 2ull, g.mat, nullptr, copy, 0ull});
-      else jobs.push_back(FusedPairJob{nullptr, nullptr, tab, 3ull, g.mat, g.kept, copy, 0ull});
+      const FusedOperand & g = ga.gx[pos].g[k];
+      if (g.type == FUSED_G_NONE) break;
+      const unsigned char * rows[2] = {g.row1, g.row2};
+      const unsigned int lane0[2] = {PLLHIP_FUSED_CH_LPOS(ga.chars_of[k][pos]), PLLHIP_FUSED_CH_RPOS(ga.chars_of[k][pos])};
+      for (int o = 0; o < 2; ++o)
+        for (unsigned int l = 0; rows[o] && l < lpr; ++l)
+          out.rowtab[(size_t)ga.batch_of[pos] * 64 + lane0[o] + l] = (unsigned long long)(uintptr_t)rows[o] + l * 16u;
+      double * tab = in.pairtab + out.jobs.size() * per;
+      double * copy = ga.gx[pos].copy[k];
+      if (g.type == FUSED_G_TIP) out.jobs.push_back(FusedPairJob{g.mat, nullptr, tab, 0ull, nullptr, nullptr, copy, 0ull});
+      else if (g.type == FUSED_G_PAIR) out.jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 1ull, nullptr, nullptr, copy, 0ull});
+      else if (g.type == FUSED_G_CHERRY_NEW) out.jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 2ull, g.mat, nullptr, copy, 0ull});
+      else out.jobs.push_back(FusedPairJob{nullptr, nullptr, tab, 3ull, g.mat, g.kept, copy, 0ull});
     }
     // every op with a parent scaler scales the partition's way (and so does a folded product's test)
-    if (f.pscaler || (f.prod[0] & 2) || (f.prod[1] & 2)) mode = c->sh.rate_scalers ? SCALE_RATE : SCALE_SITE;
+    if (f.pscaler || (f.prod[0] & 2) || (f.prod[1] & 2)) out.mode = in.rate_scalers ? SCALE_RATE : SCALE_SITE;
   }
-  // what record `r` says about the ops ahead of position `pos` (pos may be -2, -1: the headers)
-  auto look_ahead = [&](FusedRec & r, long pos) -> int {
-    r.chars = r.chars2 = r.chars3 = r.chars4 = 0;
-    r.req_lmat = r.req_rmat = 0;
-    if (pos + 1 >= 0 && pos + 1 < (long)n)
-    {
-      r.chars = chars_of[0][pos + 1];
-      r.chars2 = chars_of[1][pos + 1];
-      r.chars3 = chars_of[2][pos + 1];
-      r.chars4 = chars_of[3][pos + 1];
-    }
-    // (the edge pseudo-op at position n: its matrix is requested and staged as a right-hand one, like a tip-inner op's)
-    if (edge && pos + 2 == (long)n) r.req_rmat = (unsigned int)((edge->pmat - c->pmatrix) * sizeof(double));
-    if (pos + 2 < (long)n)
-    {
-      const FusedOp & f = plan[pos + 2];
-      // (the rows of op + 2 are fetched once op + 1's characters have been taken from the registers)
-      const unsigned int now = pos + 1 >= 0 ? batch_of[pos + 1] : batch0;
-      if (batch_of[pos + 2] != now) r.chars |= PLLHIP_FUSED_CH_LOAD | batch_of[pos + 2] << 24;
-      r.req_lmat = (unsigned int)((f.lmat - c->pmatrix) * sizeof(double));
-      r.req_rmat = (unsigned int)((f.rmat - c->pmatrix) * sizeof(double));
-    }
-    r.src = 0;
-    if (pos + 1 >= 0 && pos + 1 < (long)n + (edge ? 1 : 0))
-    {
-      const FusedOp & f = pos + 1 < (long)n ? plan[pos + 1] : edge->op;
-      r.gather_off = pos + 1 < (long)n ? table_of[pos + 1] : 0u;
-      // (a reader of folded products runs as an inner-inner op: both matrices)
-      r.flags |= (f.kind == 0 || f.prod[0] ? 2u : (f.kind == 1 || f.kind == PLLHIP_FUSED_KIND_EDGE) ? 1u : 0u) << PLLHIP_FUSED_STAGE_SHIFT;
-      if (f.dma_flags)
-      {
-        if (srcs.size() >= 0xffffu) return 1;
-        r.flags |= PLLHIP_FUSED_RELOAD_NEXT;
-        r.src = (unsigned short)srcs.size();
-        FusedSrc s;
-        memset(&s, 0, sizeof(s));
-        if (f.dma_flags & 1) { s.left_hbm = f.left_hbm; s.lsc_hbm = f.lsc_hbm; }
-        if (f.dma_flags & 2) { s.right_hbm = f.right_hbm; s.rsc_hbm = f.rsc_hbm; }
-        s.where = (unsigned long long)((f.lslot > 0 ? f.lslot : 0) * slot_bytes) |
-                  (unsigned long long)((f.rslot > 0 ? f.rslot : 0) * slot_bytes) << 16 |
-                  (unsigned long long)((f.lslot > 0 ? f.lslot : 0) * count_bytes) << 32 |
-                  (unsigned long long)((f.rslot > 0 ? f.rslot : 0) * count_bytes) << 48;
-        srcs.push_back(s);
-      }
-    }
-    return 0;
-  };
-  const size_t first = recs.size();
-  segs[sg] = FusedSeg{(unsigned int)first, n, batch0, 0u};
-  recs.resize(first + n + 3);
-  FusedRec * rs = recs.data() + first;
+  const size_t first = out.recs.size();
+  out.segs.push_back(FusedSeg{(unsigned int)first, n, ga.batch0, 0u});
+  out.recs.resize(first + n + 3);
+  FusedRec * rs = out.recs.data() + first;
   memset(rs, 0, (n + 3) * sizeof(FusedRec));
-  if (look_ahead(rs[0], -2) || look_ahead(rs[1], -1)) return 1;
+  fused_look_ahead(in, plan, ga, edge, rs[0], -2, out.srcs);
+  fused_look_ahead(in, plan, ga, edge, rs[1], -1, out.srcs);
   for (unsigned int pos = 0; pos < n; ++pos)
   {
-    const FusedOp & f = plan[pos];
-    FusedRec & r = rs[pos + 2];
-    r.flags = (unsigned int)f.kind & PLLHIP_FUSED_KIND_MASK;
-    if (f.prod[0])
-    {
-      // folded products: the kernel's inner-inner arithmetic, that side's operand formed from the gathered factors;
-      // the count inherited on that side is the product's own scale bit, where the reader passes its scale buffer
-      r.flags = PLLHIP_FUSED_LPROD | ((f.prod[0] & 2) ? PLLHIP_FUSED_LPSCALE : 0u) | ((f.prod[0] & 4) ? PLLHIP_FUSED_LCNT : 0u);
-      if (f.prod[1])
-        r.flags |= PLLHIP_FUSED_RPROD | ((f.prod[1] & 2) ? PLLHIP_FUSED_RPSCALE : 0u) | ((f.prod[1] & 4) ? PLLHIP_FUSED_RCNT : 0u);
-    }
-    if (f.pslot >= 0) r.flags |= PLLHIP_FUSED_HAS_PSLOT;
-    if (f.pscaler) r.flags |= PLLHIP_FUSED_SCALING;
-    if (f.unstored)
-    {
-      // (only what the kernel can redirect and the planner marked: a reader without the slot would find nothing)
-      if (f.kind != 3 || f.pslot < 0 || R > 4 || c->sh.rate_scalers || !f.keep[0] || !f.keep[1]) return 1;
-      r.flags |= PLLHIP_FUSED_UNSTORED;
-    }
-    if (f.kind == 0 && f.lsc_slot >= 0) r.flags |= PLLHIP_FUSED_LCNT;
-    if (f.kind != 2 && !f.prod[1] && f.rsc_slot >= 0) r.flags |= PLLHIP_FUSED_RCNT;
-    r.parent = (unsigned long long)(uintptr_t)f.parent;
-    r.pscaler = (unsigned long long)(uintptr_t)f.pscaler;
-    r.lslot_b = (unsigned short)((f.lslot > 0 ? f.lslot : 0) * slot_bytes);
-    r.rslot_b = (unsigned short)((f.rslot > 0 ? f.rslot : 0) * slot_bytes);
-    r.pslot_b = (unsigned short)((f.pslot > 0 ? f.pslot : 0) * slot_bytes);
-    r.lcnt_b = (unsigned short)((f.lsc_slot > 0 ? f.lsc_slot : 0) * count_bytes);
-    r.rcnt_b = (unsigned short)((f.rsc_slot > 0 ? f.rsc_slot : 0) * count_bytes);
-    r.pcnt_b = (unsigned short)((f.pslot > 0 ? f.pslot : 0) * count_bytes);
-    r.list_pos = (unsigned short)f.list_pos;
-    if (look_ahead(r, (long)pos)) return 1;
+    fused_fill_record(in, plan[pos], rs[pos + 2]);
+    fused_look_ahead(in, plan, ga, edge, rs[pos + 2], (long)pos, out.srcs);
   }
   rs[n + 2] = rs[n + 1]; // (loaded by the last op, never used)
   rs[n + 2].flags &= ~PLLHIP_FUSED_RELOAD_NEXT;
-  if (edge)
-  {
-    // ... but by the edge epilogue: where the two CLVs and their counts are
-    FusedRec & e = rs[n + 2];
-    const FusedOp & f = edge->op;
-    if (f.lslot < 0 || f.rslot < 0) return 1;
-    memset(&e, 0, sizeof(e));
-    if (f.lsc_slot >= 0) e.flags |= PLLHIP_FUSED_LCNT;
-    if (f.rsc_slot >= 0) e.flags |= PLLHIP_FUSED_RCNT;
-    e.lslot_b = (unsigned short)(f.lslot * slot_bytes);
-    e.rslot_b = (unsigned short)(f.rslot * slot_bytes);
-    e.lcnt_b = (unsigned short)((f.lsc_slot > 0 ? f.lsc_slot : 0) * count_bytes);
-    e.rcnt_b = (unsigned short)((f.rsc_slot > 0 ? f.rsc_slot : 0) * count_bytes);
-  }
-  } // segments
-  // the kept tables T of the cherries this list defers: written straight into their places in the pool
-  if (keep_jobs) jobs.insert(jobs.end(), keep_jobs->begin(), keep_jobs->end());
+  if (!edge) return;
+  // ... but by the edge epilogue: where the two CLVs and their counts are
+  FusedRec & e = rs[n + 2];
+  const FusedOp & f = edge->op;
+  memset(&e, 0, sizeof(e));
+  if (f.lsc_slot >= 0) e.flags |= PLLHIP_FUSED_LCNT;
+  if (f.rsc_slot >= 0) e.flags |= PLLHIP_FUSED_RCNT;
+  e.lslot_b = (unsigned short)(f.lslot * in.slot.tile_bytes);
+  e.rslot_b = (unsigned short)(f.rslot * in.slot.tile_bytes);
+  e.lcnt_b = (unsigned short)((f.lsc_slot > 0 ? f.lsc_slot : 0) * in.slot.count_bytes);
+  e.rcnt_b = (unsigned short)((f.rsc_slot > 0 ? f.rsc_slot : 0) * in.slot.count_bytes);
+}
 
-  const size_t rec_bytes = recs.size() * sizeof(FusedRec);
+static void fused_encode(const FusedEncodeIn & in, const std::vector<std::vector<FusedOp>> & plans, const FusedAdmitted & adm,
+                         const std::vector<FusedPairJob> * keep_jobs, const FusedEdge * edge, FusedEncoded & out)
+{
+  out.longest = adm.longest;
+  for (size_t sg = 0; sg < plans.size(); ++sg) fused_encode_segment(in, plans[sg], adm.segs[sg], edge, out);
+  // the kept tables T of the cherries this list defers: written straight into their places in the pool
+  if (keep_jobs) out.jobs.insert(out.jobs.end(), keep_jobs->begin(), keep_jobs->end());
+}
+
+// (c) Upload: the staging and device buffers grown where they must be, the five arrays at their offsets, and what a
+// repeated call with the same op list needs (pllhip_relaunch_fused).
+static int fused_upload(pllhip_ctx * c, const FusedEncoded & enc)
+{
+  const size_t rec_bytes = enc.recs.size() * sizeof(FusedRec);
   const size_t seg_bytes = (size_t)PLLHIP_FUSED_MAX_SEGS * sizeof(FusedSeg);
-  const size_t src_bytes = (srcs.size() + 1) * sizeof(FusedSrc);
-  const size_t job_bytes = (jobs.size() + 1) * sizeof(FusedPairJob);
-  const size_t tab_bytes = rowtab.size() * sizeof(unsigned long long);
-  const size_t bytes = rec_bytes + seg_bytes + src_bytes + job_bytes + tab_bytes;
+  const size_t src_bytes = (enc.srcs.size() + 1) * sizeof(FusedSrc);
+  const size_t job_bytes = (enc.jobs.size() + 1) * sizeof(FusedPairJob);
+  const size_t tab_bytes = enc.rowtab.size() * sizeof(unsigned long long);
+  const size_t segs_at = rec_bytes, srcs_at = segs_at + seg_bytes, jobs_at = srcs_at + src_bytes, rowtab_at = jobs_at + job_bytes;
+  const size_t bytes = rowtab_at + tab_bytes;
   if (c->plan_cap < bytes)
   {
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1339,33 +1386,73 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   c->plan_next ^= 1;
   if (c->plan_pending[b]) HIP_TRY(hipEventSynchronize(c->plan_done[b]));
   char * stage = static_cast<char *>(c->h_plan[b]);
-  memcpy(stage, recs.data(), rec_bytes);
-  memcpy(stage + rec_bytes, segs.data(), segs.size() * sizeof(FusedSeg));
-  if (!srcs.empty()) memcpy(stage + rec_bytes + seg_bytes, srcs.data(), srcs.size() * sizeof(FusedSrc));
-  if (!jobs.empty()) memcpy(stage + rec_bytes + seg_bytes + src_bytes, jobs.data(), jobs.size() * sizeof(FusedPairJob));
-  memcpy(stage + rec_bytes + seg_bytes + src_bytes + job_bytes, rowtab.data(), tab_bytes);
+  memcpy(stage, enc.recs.data(), rec_bytes);
+  memcpy(stage + segs_at, enc.segs.data(), enc.segs.size() * sizeof(FusedSeg));
+  if (!enc.srcs.empty()) memcpy(stage + srcs_at, enc.srcs.data(), enc.srcs.size() * sizeof(FusedSrc));
+  if (!enc.jobs.empty()) memcpy(stage + jobs_at, enc.jobs.data(), enc.jobs.size() * sizeof(FusedPairJob));
+  memcpy(stage + rowtab_at, enc.rowtab.data(), tab_bytes);
   HIP_TRY(hipMemcpyAsync(c->d_plan, c->h_plan[b], bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipEventRecord(c->plan_done[b], c->stream));
   c->plan_pending[b] = true;
+  c->fused_last_segs_offset = segs_at;
+  c->fused_last_srcs_offset = srcs_at;
+  c->fused_last_jobs_offset = jobs_at;
+  c->fused_last_rowtab_offset = rowtab_at;
+  c->fused_last_jobs = (unsigned int)enc.jobs.size();
+  c->fused_last_longest = enc.longest;
+  c->fused_last_nsegs = (unsigned int)enc.segs.size();
+  c->fused_last_mode = enc.mode;
+  c->fused_last_epoch = c->layout_epoch;
+  return 0;
+}
+
+// The buffers a launch needs besides the plan, on first use or where this list needs more: the edge terms, the pair
+// tables (carved from one device buffer), the row of zeros, the waves' sinks, the tile counters.
+static int fused_device_buffers(pllhip_ctx * c, size_t pairtab_elems, bool edge)
+{
+  if (edge && !c->d_edge_terms)
+    HIP_TRY(hipMalloc((void **)&c->d_edge_terms, ((size_t)c->sh.sites + PLLHIP_TAIL_SITES) * sizeof(double)));
+  if (c->pairtab_elems < pairtab_elems)
+  {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_pairtab) HIP_TRY(hipFree(c->d_pairtab));
+    c->d_pairtab = nullptr;
+    HIP_TRY(hipMalloc((void **)&c->d_pairtab, pairtab_elems * sizeof(double)));
+    c->pairtab_elems = pairtab_elems;
+    ++c->layout_epoch;
+  }
+  if (!c->fused_zero_row)
+  {
+    const size_t bytes = (size_t)c->sh.sites + PLLHIP_TAIL_SITES + 256;
+    HIP_TRY(hipMalloc((void **)&c->fused_zero_row, bytes));
+    HIP_TRY(hipMemsetAsync(c->fused_zero_row, 0, bytes, c->stream));
+  }
   if (!c->d_sink) HIP_TRY(hipMalloc(&c->d_sink, (size_t)c->num_cus * 16 * PLLHIP_FUSED_SINK_GRANULES * sizeof(double2)));
   if (!c->d_tile_counter)
   {
     HIP_TRY(hipMalloc((void **)&c->d_tile_counter, 2 * PLLHIP_TILE_COUNTER_BYTES));
     HIP_TRY(hipMemsetAsync(c->d_tile_counter, 0, 2 * PLLHIP_TILE_COUNTER_BYTES, c->stream));
   }
-  // what a repeated call with the same op list needs (pllhip_relaunch_fused)
-  c->fused_last_segs_offset = rec_bytes;
-  c->fused_last_srcs_offset = rec_bytes + seg_bytes;
-  c->fused_last_jobs_offset = rec_bytes + seg_bytes + src_bytes;
-  c->fused_last_rowtab_offset = rec_bytes + seg_bytes + src_bytes + job_bytes;
-  c->fused_last_jobs = (unsigned int)jobs.size();
+  return 0;
+}
+
+// A planned list: admitted, then -- and only then is anything of the device or the context touched -- its buffers,
+// the encoding, the upload, the launch.  Returns 1 if the list is not one the kernel takes.
+int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
+                        const std::vector<FusedPairJob> * keep_jobs, const FusedEdge * edge)
+{
+  FusedAdmitted adm;
+  if (fused_admit(c, plans, nslots, edge, adm)) return 1;
+  int rc = fused_device_buffers(c, adm.ntab * fused_table_doubles(c->sh.rate_cats), edge != nullptr);
+  if (rc) return rc;
+  const FusedEncodeIn in = {c->pmatrix, c->d_pairtab, c->fused_zero_row, pllhip_fused_slot_size(c->sh.rate_cats, c->sh.rate_scalers != 0),
+                            c->sh.rate_cats, c->sh.rate_scalers != 0};
+  FusedEncoded enc;
+  fused_encode(in, plans, adm, keep_jobs, edge, enc);
+  if ((rc = fused_upload(c, enc))) return rc;
   c->fused_last_count = plans[0].size();
-  c->fused_last_longest = longest;
   c->fused_last_ndeferred = keep_jobs ? (unsigned int)keep_jobs->size() : 0u;
-  c->fused_last_nsegs = nsegs;
   c->fused_last_nslots = nslots;
-  c->fused_last_mode = mode;
-  c->fused_last_epoch = c->layout_epoch;
   c->fused_last_edge = edge != nullptr;
   return pllhip_relaunch_fused(c);
 }

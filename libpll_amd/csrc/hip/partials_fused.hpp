@@ -271,8 +271,8 @@ bool pllhip_fused_edge_end_stored(const FusedGeom & geom, const FusedDeferral & 
 //   - it is read by at least one op of the list (a last op, a root, is stored);
 //   - it is not an end of `edge` (the hinted evaluation, folded or not: pllhip_fused_edge_end_stored wants bytes).
 // `ops` / `count`: the list the plans were made of (FusedOp::list_pos).  Sets FusedOp::unstored in `plans`, returns how
-// many.  ONE rule for pllhip_update_partials and pllhip_fused_plan_dry_unstored; the caller decides whether the
-// instance may leave anything unstored at all.
+// many.  ONE rule, applied by pllhip_fused_plan_walk alone; its caller decides whether the instance may leave anything
+// unstored at all.
 unsigned int pllhip_fused_unstored(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
                                    std::vector<std::vector<FusedOp>> & plans, const FusedEdge * edge,
                                    const unsigned char * pinned);
@@ -282,8 +282,8 @@ unsigned int pllhip_fused_unstored(const FusedGeom & geom, const pllhip_op_t * o
 //   - that reader is an inner-inner op of the list (kinds[] 0): its other side is another folded product, or a slot.
 // (A reader whose other side is a single gathered factor keeps today's treatment: its product is walked, unstored.)
 // Sets fold[k] = 1 per op of the list to fold, returns how many -- 0 also where fewer than two ops would be left to
-// walk (a list kernel wants two).  ONE rule for pllhip_update_partials and pllhip_fused_plan_dry_folded; the caller
-// plans the list once more without the folded ops (pllhip_fused_fold_list).
+// walk (a list kernel wants two).  ONE rule, applied by pllhip_fused_plan_walk alone, which then plans the list once
+// more without the folded ops (pllhip_fused_fold_list).
 unsigned int pllhip_fused_fold(const pllhip_op_t * ops, const int * kinds, unsigned int count,
                                const std::vector<std::vector<FusedOp>> & plans, std::vector<unsigned char> & fold);
 // The list without the ops fold[] marks, as the planner is to see it: `where` (kept op -> op of the list), the kept
@@ -319,11 +319,11 @@ int pllhip_fused_plan_segments(const FusedGeom & geom, const pllhip_op_t * ops, 
                                const FusedExtra * extra, unsigned int count, const unsigned int * seg_of, unsigned int nsegs,
                                unsigned int nslots, std::vector<std::vector<FusedOp>> & plans, unsigned int * reloads);
 
-// The 4-state list driver: ONE rule for pllhip_update_partials (real addresses) and pllhip_fused_plan_dry_deferred /
-// _edge (fake ones).  The list is segmented and planned at each of slot_counts[] in turn until one is taken -- 12 waves
-// per CU, else 8; segments refused at every slot count: once more as one list.  Then, with an `edge` and one segment:
-// once more at the slot count taken with the edge as a pseudo-op, if both ends pass pllhip_fused_edge_end_stored; a
-// fold the planner refuses leaves the unfolded plan.  Returns pllhip_fused_plan's codes.
+// The 4-state list driver: ONE rule, called by pllhip_fused_plan_walk alone.  The list is segmented and planned at each
+// of slot_counts[] in turn until one is taken -- 12 waves per CU, else 8; segments refused at every slot count: once
+// more as one list.  Then, with an `edge` and one segment: once more at the slot count taken with the edge as a
+// pseudo-op, if both ends pass pllhip_fused_edge_end_stored; a fold the planner refuses leaves the unfolded plan.
+// Returns pllhip_fused_plan's codes.
 struct FusedListPlan
 {
   std::vector<std::vector<FusedOp>> plans; // one per segment
@@ -335,6 +335,62 @@ int pllhip_fused_plan_list(const FusedGeom & geom, const pllhip_op_t * ops, cons
                            const FusedExtra * extra, unsigned int count, unsigned int max_segments,
                            const unsigned int * slot_counts, unsigned int nslot_counts, FusedEdge * edge,
                            const FusedDeferral & dd, FusedListPlan & out);
+
+// The whole preparation of a 4-state list, ONE sequence for pllhip_update_partials (real addresses) and the dry entry
+// points pllhip_fused_plan_dry_deferred / _edge / _unstored / _folded (fake ones; no device, no callback):
+//   1. the list is planned (pllhip_fused_plan_list, `edge` offered where given);
+//   2. may_unstore: pllhip_fused_unstored marks the parents that stay unstored;
+//   3. may_fold, and something is unstored: pllhip_fused_fold picks those its reader forms, pllhip_fused_fold_list builds
+//      the list without them, and that list is planned once more -- the edge offered only where the first plan had one
+//      segment (a list in segments stays without, however short its segments have become).  A second plan the planner
+//      refuses, or one of fewer than two ops, leaves the first;
+//   4. a second plan taken: pllhip_fused_unstored once more, on what is left.
+// ops / args / kinds / extras (may be nullptr) / rows4 (four per op: tip index + 1 of the rows of its two gathered
+// factors; may be nullptr: dry): the ops the kernel is to run, after deferral.  The arrays must outlive the result,
+// which refers to them.  Returns the first plan's code (pllhip_fused_plan's); < 0 also for an error of the second.
+struct FusedWalk
+{
+  FusedListPlan plan; // the plan to launch, and its edge (plan.folded: edge.op says where the epilogue's operands are)
+  FusedEdge edge;
+  // a folded plan replaced the first: the first is kept, its unstored marks standing, should the launch not take the
+  // second (more character batches or tables than it encodes) -- take_first()
+  bool replanned = false;
+  FusedListPlan first_plan;
+  FusedEdge first_edge;
+  std::vector<unsigned char> fold; // per op of the list: folded, not walked (all 0 unless replanned)
+  FusedFoldList fl;                // replanned: the list `plan` was made of
+  unsigned int nunstored = 0;      // walked parents `plan` leaves unstored
+  unsigned int nfolded = 0;        // folded ones (not walked, unstored too)
+  unsigned int first_nunstored = 0;
+  const pllhip_op_t * list_ops = nullptr;
+  const unsigned int * list_rows4 = nullptr;
+
+  // What an op of `plan` stands for: its position in the list handed over, the op itself, the four rows its parent is
+  // kept with where it stays unstored (nullptr: dry), and the op of the list folded into side s of it (nullptr: none).
+  unsigned int pos_in_list(const FusedOp & f) const { return replanned ? fl.where[f.list_pos] : (unsigned int)f.list_pos; }
+  const pllhip_op_t & op_of(const FusedOp & f) const { return list_ops[pos_in_list(f)]; }
+  const unsigned int * rows_of(const FusedOp & f) const { return list_rows4 ? list_rows4 + 4 * (size_t)pos_in_list(f) : nullptr; }
+  const pllhip_op_t * folded_into(const FusedOp & f, int s) const
+  {
+    const unsigned int from = replanned && f.prod[s] ? fl.prod_op[2 * (size_t)f.list_pos + s] : 0u;
+    return from ? list_ops + (from - 1) : nullptr;
+  }
+  // the launch did not take the folded plan: the first one again
+  void take_first()
+  {
+    plan = std::move(first_plan);
+    edge = first_edge;
+    replanned = false;
+    fold.assign(fold.size(), 0);
+    nunstored = first_nunstored;
+    nfolded = 0;
+  }
+};
+int pllhip_fused_plan_walk(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
+                           const FusedExtra * extras, const unsigned int * rows4, unsigned int count,
+                           unsigned int max_segments, const unsigned int * slot_counts, unsigned int nslot_counts,
+                           const FusedEdge * edge, const FusedDeferral & dd, const unsigned char * pinned,
+                           bool may_unstore, bool may_fold, FusedWalk & out);
 
 // ---- The 20-state list (partials_aa_fused.hip) before anything is encoded: what each op is to the kernel, what the
 // scaling certificate makes of it, the list the kernel walks.  Indices and numbers only -- ONE rule for

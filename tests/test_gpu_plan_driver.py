@@ -1,4 +1,4 @@
-"""The 4-state list driver, live and dry: ONE (fused_plan.hip: pllhip_fused_plan_list).
+"""The 4-state list driver, live and dry: ONE (fused_plan.hip: pllhip_fused_plan_walk over pllhip_fused_plan_list).
 
 pllhip_update_partials plans a list with the driver the device-less entry point pllhip_fused_plan_dry_edge plans it with,
 so what the dry call says of a list -- which ops are deferred, whether the hinted edge is folded into the launch -- is
@@ -10,6 +10,9 @@ pll_amd_edge_fold_stats (lists launched with the epilogue).
 plans one segment, so the live call is held to one too (PLLHIP_FUSED_SEGMENTS=1, as in test_gpu_edge_fold.py): a list
 of two segments is never folded.  The second traversal is the one compared: it meets the first one's deferred cherries
 (the dry call's old_deferred / old_scaler) and the hint the edge evaluation left.
+
+The steps behind the plan -- parents left unstored, parents folded into their reader, the list planned once more -- are
+held to pllhip_fused_plan_dry_folded by the last test, through pll_amd_unstored_stats and pll_amd_pair_fold_stats.
 """
 import numpy as np
 import pytest
@@ -18,6 +21,7 @@ from helpers import make_case, build_partition
 from libpll_amd import workload as W
 from libpll_amd.pllapi import ATTRIB_PATTERN_TIP
 from test_host_edge_fold_plan import _dry_edge
+from test_host_pair_fold_plan import _call as _dry_folded
 
 pytestmark = pytest.mark.gpu
 
@@ -90,3 +94,52 @@ def test_live_call_does_what_the_dry_call_says(gpu, shape, tips, cherry_end):
     assert p.compute_edge_loglikelihood(*edge, fi) == lnl
     assert dry_deferred and dry["edge"][0] == (0 if cherry_end else 1), "the case is meant to defer, and to fold or not"
     p.destroy()
+
+
+@pytest.mark.parametrize("shape,tips", [("random", 17), ("balanced", 16)])
+def test_live_call_leaves_unstored_and_folds_what_the_dry_call_says(gpu, shape, tips):
+    """ONE driver (fused_plan.hip: pllhip_fused_plan_walk) takes a list through plan, unstored, fold, plan once more and
+    unstored again, for pllhip_update_partials and for pllhip_fused_plan_dry_folded alike: the parents the dry call
+    says are deferred, left unstored and folded are the ones the live call does not have in HBM, each for that reason.
+    40 sites (three tiles of 16 at 4 categories, the last ragged), per-site scale buffers, one full traversal."""
+    case = make_case(4, shape, tips, 40, rate_cats=4, seed=5)
+    plan = case["plan"]
+    ops, fi = plan.ops, [0] * 4
+    p = build_partition(gpu, case, ATTRIB_PATTERN_TIP)
+    p.set_deferral(True)
+    p.set_unstored_pairs(True)
+    p.set_pair_fold(True)
+    dry = _dry_folded(gpu, "pllhip_fused_plan_dry_folded", ops, plan.tips, plan.clv_buffers, plan.scale_buffers, 4, 0, None,
+                      None, True)
+    assert dry["rc"] == 0
+    print("%s %d: %d ops, dry defers %r, folds %r, leaves unstored %r" %
+          (shape, tips, len(ops), dry["deferred"], dry["folded"], dry["unstored"]))
+    assert dry["deferred"] and dry["folded"], "the case is meant to defer and to fold"
+    assert dry["unstored"] or shape != "random", "the random tree is meant to leave walked parents unstored"
+    p.update_partials(ops)
+    assert p.deferred_stats()["ops_deferred"] == len(dry["deferred"])
+    assert p.pair_fold_stats()["folded_now"] == len(dry["folded"])
+    # (a folded parent is an unstored pair product as well)
+    assert p.unstored_stats()["unstored_now"] == len(dry["unstored"]) + len(dry["folded"])
+    # which CLVs: reading one back materialises it, and counts it, exactly if it was not in HBM
+    live = {"deferred": set(), "unstored": set(), "folded": set()}
+    for op in ops:
+        node = int(op["parent_clv_index"])
+        before = (p.deferred_stats()["materialised"], p.unstored_stats()["materialised"], p.pair_fold_stats()["materialised"])
+        p.get_clv(node)
+        after = (p.deferred_stats()["materialised"], p.unstored_stats()["materialised"], p.pair_fold_stats()["materialised"])
+        rose = tuple(a - b for a, b in zip(after, before))
+        assert rose in ((0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 1, 1)), (node, rose)
+        if rose != (0, 0, 0):
+            live["deferred" if rose[0] else "folded" if rose[2] else "unstored"].add(node)
+    for what in live:
+        assert live[what] == {int(ops[i]["parent_clv_index"]) for i in dry[what]}, what
+    # the same bits as a partition that defers, leaves unstored and folds nothing
+    q = build_partition(gpu, case, ATTRIB_PATTERN_TIP)
+    q.set_deferral(False)
+    q.set_unstored_pairs(False)
+    q.set_pair_fold(False)
+    q.update_partials(ops)
+    assert p.compute_edge_loglikelihood(*plan.root_edge, fi) == q.compute_edge_loglikelihood(*plan.root_edge, fi)
+    p.destroy()
+    q.destroy()

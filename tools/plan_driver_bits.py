@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Two builds of the library, one planner?  Drives the five device-less planner entry points
+"""Two builds of the library, one planner?  Drives the seven device-less planner entry points
 
     pllhip_fused_plan_dry  pllhip_fused_plan_dry_deferred  pllhip_fused_plan_dry_edge
+    pllhip_fused_plan_dry_unstored  pllhip_fused_plan_dry_folded
     pllhip_fused_char_batches_dry  pllhip_fused_segments_dry
 
 of both libraries from this one process with the same seeded inputs and compares the return code and every byte of
@@ -14,7 +15,8 @@ Inputs (the generators of the host tests): full and partial traversals of balanc
 CLVs; the same with one operand's counts taken from another CLV's scale buffer (refused at any slot count); random op
 sequences with reused CLV and scale buffers (tests/helpers.py: random_op_sequence); lists with an index out of range.
 nslots 3..7, max_segments 1 / 2 / 8, rate_cats 1 / 2 / 4 and every kind of edge for the edge entry point, random
-old_deferred / pinned masks for the deferred one.  One line per entry point and input family: cases compared,
+old_deferred / pinned masks for the deferred one; nslots 0 and 3..7, rate_cats 1 / 2 / 4 (and a bad one), with and
+without an edge and random pinned masks for the unstored and the folded one.  One line per entry point and input family: cases compared,
 how many were identical, and the parent's return values (0 taken, 1 refused -- for the two entry points that return a
 count: one batch / one segment --, -1 error, anything else `more`).  Exit status 1 if anything differs.
 """
@@ -78,6 +80,20 @@ def call_edge(lib, g, ops, rate_cats, old, old_sc, pinned, edge4):
     f.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_uint, VP, C.c_uint] + [VP] * 11
     rc = f(g[0], g[1], g[2], g[3], rate_cats, _ptr(ops), n, _ptr(old), _ptr(old_sc), _ptr(pinned), _ptr(e4), o.p("nkept"),
            o.p("order"), o.p("slots"), o.p("opnd"), o.p("deferred"), o.p("reloads"), o.p("edge"))
+    return rc, o.blob()
+
+
+def call_unstored(lib, g, ops, rate_cats, nslots, pinned, edge4, folded):
+    n = len(ops)
+    sizes = dict(nkept=4, order=4 * n, slots=24 * n, opnd=8 * n, deferred=n, reloads=4, unstored=n)
+    if folded:
+        sizes["folded"] = n
+    o = Out(**sizes)
+    e4 = None if edge4 is None else np.array(edge4, dtype=np.int32)
+    f = lib.pllhip_fused_plan_dry_folded if folded else lib.pllhip_fused_plan_dry_unstored
+    f.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_uint, VP, C.c_uint, C.c_uint] + [VP] * (10 if folded else 9)
+    rc = f(g[0], g[1], g[2], g[3], rate_cats, _ptr(ops), n, nslots, _ptr(pinned), _ptr(e4), o.p("nkept"), o.p("order"),
+           o.p("slots"), o.p("opnd"), o.p("deferred"), o.p("reloads"), o.p("unstored"), *([o.p("folded")] if folded else []))
     return rc, o.blob()
 
 
@@ -196,6 +212,12 @@ def main():
             for rate_cats in (1, 2, 4):
                 for k, e in enumerate(picks):
                     both("plan_dry_edge", fam, call_edge, g, ops, rate_cats, *masks[k % len(masks)], e)
+            for folded, entry in ((False, "plan_dry_unstored"), (True, "plan_dry_folded")):
+                for nslots in [0] + [int(x) for x in rng.permutation(np.arange(3, 8))[:2]]:
+                    rate_cats = (1, 2, 4)[int(rng.integers(3))]
+                    e = None if rng.random() < 0.5 else cand[int(rng.integers(len(cand)))]
+                    both(entry, fam, call_unstored, g, ops, rate_cats, nslots, masks[int(rng.integers(2))][2], e, folded)
+                both(entry, "out-of-range-pt%d" % pt, call_unstored, g, bad, 4, 0, None, None, folded)
             # an index out of range: refused, nothing read
             both("plan_dry", "out-of-range-pt%d" % pt, call_plan, g, bad, 5)
             both("plan_dry_deferred", "out-of-range-pt%d" % pt, call_deferred, g, bad, 5, None, None, None)
@@ -203,13 +225,15 @@ def main():
             both("segments_dry", "out-of-range-pt%d" % pt, call_segments, g, bad, 8)
         both("plan_dry_edge", "bad-edge-or-rate-cats", call_edge, (tips, clvb, scb, 1), ops, 3 if nlists % 2 else 4, None, None, None,
              cand[0] if nlists % 2 else (nclv, -1, tips, -1))
+        for folded, entry in ((False, "plan_dry_unstored"), (True, "plan_dry_folded")):
+            both(entry, "bad-rate-cats", call_unstored, (tips, clvb, scb, 1), ops, 3 if nlists % 2 else 8, 0, None, None, folded)
     for rate_cats in (1, 2, 4, 8):
         for count in (1, 2, 3, 7, 30, 62, 126, 198, 1000) * 12:
             nlists += 1
             tips = rng.integers(0, 4, size=count).astype(np.uint32)
             both("char_batches_dry", "random-rate-cats-%d" % rate_cats, call_chars, tips, rate_cats)
 
-    print("The planner's five device-less entry points, parent commit against this commit: %d lists, one process,\n"
+    print("The planner's seven device-less entry points, parent commit against this commit: %d lists, one process,\n"
           "both libraries loaded side by side (tools/plan_driver_bits.py).  Per line: cases compared, cases whose return\n"
           "value and output bytes are all identical, and the parent's return values." % nlists)
     print("%-24s %-32s %8s %9s %7s %7s %7s %7s" % ("entry point", "family", "compared", "identical", "rc 0", "rc 1", "rc -1", "more"))

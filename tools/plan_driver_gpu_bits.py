@@ -7,11 +7,12 @@ Each library runs every case in a process of its own, one after the other, under
 fails ends the run.  One SHA-256 per case over the edge log-likelihood after every list, and every inner CLV and every
 scale buffer at the end.  The cases are the smallest at which each branch of the list planner is live, all with
 PLLHIP_FUSED=2 (the whole-list kernels take small partitions):
-  4 states: 17 random tips x 1,000 sites (several tiles, the last ragged) and 8 balanced tips x 21 sites (less than a
-    tile); rate_cats 1 / 2 / 4 / 8; scale buffers none / per site / per rate; tips as character rows or CLVs;
+  4 states: 17 random tips x 1,000 sites (several tiles, the last ragged), 8 balanced tips x 21 sites (less than a
+    tile) and 16 balanced tips x 40 sites (the smallest balanced tree that folds pair products); rate_cats 1 / 2 / 4 / 8; scale buffers none / per site / per rate; tips as character rows or CLVs;
     PLLHIP_FUSED_WGS unset / 2; PLLHIP_FUSED_SEGMENTS unset / 0; deferral on / off; the edge fold on / off -- the
     last two only where the switch is live (deferral: character rows, up to 4 categories, no per-rate scalers; the
-    fold: up to 4 categories, no per-rate scalers), elsewhere off.
+    fold: up to 4 categories, no per-rate scalers), elsewhere off; where deferral is on, unstored pair products
+    (set_unstored_pairs) and their folding (set_pair_fold) on / off.
   20 states, 4 categories (profiles/aa_list_steps_bits.txt): random 12 tips x 500 sites, caterpillar 12 x 40 (a
     tip-inner chain, a tip-inner lookup), balanced 16 x 40 (lookups over two cherries), random 40 x 33 (operands
     reloaded); tips as character rows or CLVs; scale buffers none / per site / per rate; PLLHIP_AA_TI_MFMA 0 / 1;
@@ -60,12 +61,14 @@ def _inner_root(W, plan, use_scalers):
     return view.traversal(view.root)
 
 
-def _run_case(lib, W, H, case, attrs, use_scalers, deferral, fold):
+def _run_case(lib, W, H, case, attrs, use_scalers, deferral, fold, unstored=True, pair_fold=True):
     plan = case["plan"]
     p = H.build_partition(lib, case, attrs)
     if case["states"] == 4:
         p.set_deferral(deferral)
         p.set_edge_fold(fold)
+        p.set_unstored_pairs(unstored)
+        p.set_pair_fold(pair_fold)
     ops, edge = _inner_root(W, plan, use_scalers)
     changed = ops.copy()
     last = changed[len(changed) - 1]
@@ -97,20 +100,25 @@ def worker(which):
     lib = libpll_amd.load()
     assert lib.device_count() > 0, "no device"
     lib.lib.pll_amd_set_device(0)
-    trees = (("random", 17, 1000), ("balanced", 8, 21)) if which != "aa" else ()
-    for (shape, tips, sites), rc, scale, pt, wgs, segs, deferral, fold in itertools.product(
-            trees, (1, 2, 4, 8), ("none", "site", "rate"), (1, 0), (None, "2"), (None, "0"), (True, False), (True, False)):
+    trees = (("random", 17, 1000), ("balanced", 8, 21), ("balanced", 16, 40)) if which != "aa" else ()
+    for (shape, tips, sites), rc, scale, pt, wgs, segs, deferral, fold, unstored, pair_fold in itertools.product(
+            trees, (1, 2, 4, 8), ("none", "site", "rate"), (1, 0), (None, "2"), (None, "0"), (True, False), (True, False),
+            (True, False), (True, False)):
         live = rc <= 4 and scale != "rate"
         if (fold and not live) or (deferral and not (live and pt)):
+            continue
+        # (the two pair-product switches: only where deferral is on, elsewhere as they stand)
+        if not deferral and not (unstored and pair_fold):
             continue
         _setenv("PLLHIP_FUSED_WGS", wgs)
         _setenv("PLLHIP_FUSED_SEGMENTS", segs)
         case = H.make_case(4, shape, tips, sites, rate_cats=rc, seed=5)
         case["plan"] = H.TREES[shape](tips, seed=5, use_scalers=scale != "none")
         attrs = (ATTRIB_PATTERN_TIP if pt else 0) | (ATTRIB_RATE_SCALERS if scale == "rate" else 0)
-        digest = _run_case(lib, W, H, case, attrs, scale != "none", deferral, fold)
-        print("dna %s-%dx%d rc%d scale-%s %s wgs-%s segs-%s defer-%d fold-%d %s" %
-              (shape, tips, sites, rc, scale, "rows" if pt else "clvs", wgs or "x", segs or "x", deferral, fold, digest), flush=True)
+        digest = _run_case(lib, W, H, case, attrs, scale != "none", deferral, fold, unstored, pair_fold)
+        print("dna %s-%dx%d rc%d scale-%s %s wgs-%s segs-%s defer-%d fold-%d unstored-%d pair-fold-%d %s" %
+              (shape, tips, sites, rc, scale, "rows" if pt else "clvs", wgs or "x", segs or "x", deferral, fold, unstored,
+               pair_fold, digest), flush=True)
     _setenv("PLLHIP_FUSED_WGS", None)
     trees = (("random", 12, 500), ("caterpillar", 12, 40), ("balanced", 16, 40), ("random", 40, 33)) if which != "dna" else ()
     for (shape, tips, sites), pt, scale, ti, inside, pairs, segs, mb in itertools.product(
