@@ -991,7 +991,8 @@ typedef struct pll_amd_tree_candidate
  * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
  * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
  * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: per-candidate model parameters or category
- * rates (pll_amd_model_loglikelihood below scores models on one tree), per-site outputs, applying a candidate to the partition, and lists in which an op reads a CLV that a later op
+ * rates (pll_amd_model_loglikelihood below scores models on one tree), per-site outputs (pll_amd_replicate_loglikelihood
+ * below returns those of the partition's own edges), applying a candidate to the partition, and lists in which an op reads a CLV that a later op
  * of the same candidate overwrites (they have a meaning in the sequence and no use here).  INTEGRATION.md section 4f. */
 PLL_EXPORT int pll_amd_tree_loglikelihood(pll_partition_t * partition,
                                           const pll_amd_tree_candidate_t * candidates, unsigned int count,
@@ -1045,6 +1046,68 @@ PLL_EXPORT int pll_amd_model_loglikelihood(pll_partition_t * partition,
                                            const pll_amd_model_candidate_t * models, unsigned int count,
                                            const unsigned int * params_indices,
                                            double * lnl);           /* out [count] */
+
+/* ---- batched replicate scoring: bootstrap weight sets kept on the device (replicates.c, replicates.hip) ----
+ * One tree scored under many site-weight vectors: a non-parametric bootstrap by RELL, UFBoot-style support (B fixed
+ * replicates, every tree of a search scored against all of them), the resampling step of the KH / SH / AU tests.  The
+ * weights of a search are fixed, so they are uploaded once, as a set; an edge is given as
+ * pll_compute_edge_loglikelihood takes it. */
+typedef pll_amd_posterior_edge_t pll_amd_lnl_edge_t;   /* parent, its scaler, child, its scaler, matrix */
+typedef struct pll_amd_replicates pll_amd_replicates_t; /* opaque: a set of weight vectors on the partition's device */
+
+/* A set of `count` weight vectors, weights[r * sites + n] the weight of site n in replicate r (sites =
+ * partition->sites), copied to the partition's device; `weights` is not kept.  Storage: the narrowest of 8, 16 or 32
+ * bits per weight that holds the set's largest weight -- the pass over the weights is bound by their bytes, and
+ * bootstrap weights of uncompressed alignments are almost always below 256; results do not depend on the width (the
+ * conversion to double is exact).  A set belongs to the partition it was created on (its device, its site count);
+ * any number of sets may be alive; pll_partition_destroy destroys those that still are, after which their handles are
+ * dead.  pll_amd_replicates_destroy(NULL) is a no-op.  NULL on failure: PLL_ERROR_PARAM_INVALID (count == 0, weights
+ * NULL), PLL_ERROR_HIP_UNSUPPORTED (the limits below), PLL_ERROR_MEM_ALLOC (the set's device memory). */
+PLL_EXPORT pll_amd_replicates_t * pll_amd_replicates_create(pll_partition_t * partition,
+                                                            const unsigned int * weights, /* [count][sites] */
+                                                            unsigned int count);
+PLL_EXPORT void pll_amd_replicates_destroy(pll_amd_replicates_t * set);
+PLL_EXPORT unsigned int pll_amd_replicates_count(const pll_amd_replicates_t * set);
+
+/* lnl[e * count + r] = what this sequence returns on the same partition -- pll_set_pattern_weights(partition, weights
+ * + r * sites); pll_compute_edge_loglikelihood(partition, edge e's parent, parent scaler, child, child scaler, matrix,
+ * freqs_indices, NULL) -- with count = pll_amd_replicates_count(set).  persite_lnl[e * sites + n] = that call's
+ * per-site output with every pattern weight set to 1, log(terma) + scalings * log(2^-256): the unweighted site
+ * log-likelihoods s_e[n] that lnl[e][r] = sum_n (double)w_r[n] * s_e[n] is made of.  Per-site scalers, per-rate scalers
+ * or none, +I, a rate matrix per category, category weights, pattern tips or tip CLVs behave as in that call.
+ * Every term (double)w_r[n] * s_e[n] is formed as the reference forms it -- a rounded product, added afterwards, no
+ * fused multiply-add; only the order of the sum over the sites differs from the single call's, so a value agrees with
+ * the sequence to about 1e-12 relative (1e-11 for 20 states), not bit for bit.  The order: the sites are cut into
+ * spans of 2048; within a span the terms are added one by one in site order, starting from +0; the spans' sums are
+ * added one by one in span order, starting from +0.  It is fixed by compile-time constants, therefore lnl[e][r] is
+ * the same bits whatever else is in the batch of edges, in whatever order, however the call chunks the batch, on a
+ * repeated call, whatever else is in the set (a set made of replicate r alone, or of the replicates in another order,
+ * gives replicate r the same bits) and however the set stores its weights; a replicate with weight 1 at one site and 0
+ * elsewhere returns that site's persite_lnl bit for bit, an all-zero replicate 0.  persite_lnl of an edge is the same
+ * bits whether or not lnl is asked for.
+ * set may be NULL: then lnl is NULL and only persite_lnl is computed (the unweighted site log-likelihoods of many
+ * edges in one call).  With a set, lnl is required and persite_lnl may be NULL.
+ * What lives where: the set on the partition's device until it or the partition is destroyed; the site terms and
+ * partial sums of a chunk are scratch of the partition on its device, kept until it is destroyed.  The call changes
+ * nothing of the partition: not its own pattern weights (which it never reads), no CLV, scale buffer, P-matrix,
+ * sumtable slot or host mirror.  Large batches are worked in chunks of whole edges -- at most 4 with a set, each chunk
+ * reading every weight once -- of at most about PLL_AMD_REPLICATE_SCRATCH_MB (environment, read at call time, default
+ * 2048) of scratch, one edge at least.  The call is synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, outputs untouched): the set belongs to this
+ * partition; edge_count >= 1, edges and freqs_indices not NULL; at least one of lnl and persite_lnl, lnl given exactly
+ * when set is; CLV, scaler, matrix and freqs indices in range; with PLL_ATTRIB_PATTERN_TIP the parent is not a tip
+ * (give the tip as the child).
+ * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
+ * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
+ * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: generating the resampled weights (the
+ * client's random number generator defines them), candidate op lists in the same call (run the list, then ask at its
+ * edge), weights of type double.  INTEGRATION.md section 4h. */
+PLL_EXPORT int pll_amd_replicate_loglikelihood(pll_partition_t * partition,
+                                               const pll_amd_replicates_t * set,   /* may be NULL */
+                                               const pll_amd_lnl_edge_t * edges, unsigned int edge_count,
+                                               const unsigned int * freqs_indices,
+                                               double * lnl,           /* out [edge][count], NULL iff set is NULL */
+                                               double * persite_lnl);  /* out [edge][sites], unweighted; may be NULL */
 
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets

@@ -568,6 +568,29 @@ PLLHIP_EXPORT int pllhip_model_loglikelihood(pllhip_ctx_t * ctx, const pllhip_tr
                                              const unsigned int * h_params_indices, int route, int max_slots,
                                              size_t scratch_bytes, double * h_lnl);
 
+/* ---- batched replicate scoring (replicates.hip; host side host/replicates.c) ----
+ * A set is `count` weight vectors of the context's site count, kept on the context's device in `width` bytes per
+ * weight (1, 2 or 4: the caller has checked that every weight fits).  It belongs to the context, which frees the sets
+ * still alive when it goes.  pllhip_replicates_create: 0, -1 (bad argument), -2 (no device memory), -3 (a context the
+ * call does not take: asc-bias, site repeats, sharded, RCCL).  pllhip_replicates_owner: the context of a set.
+ * pllhip_replicate_loglikelihood: for every edge (pllhip_edge_loglikelihood's five arguments, a pllhip_posterior_edge_t)
+ * h_lnl[e][count] = sum over the sites of (double)w_r[n] * s_e[n], s_e[n] the unweighted per-site log-likelihood of
+ * the edge, and / or h_persite[e][sites] = s_e; the definition and the order of the sum are written out at
+ * pll_amd_replicate_loglikelihood (include/pll_amd.h) and in DESIGN.md section 7i.  set may be NULL (h_lnl is then
+ * NULL too).  Nothing of the context changes; scratch (kept by the context) is at most about scratch_bytes per chunk,
+ * at least one edge's worth.  Return codes as pllhip_site_posteriors. */
+typedef struct pllhip_replicates pllhip_replicates_t;
+PLLHIP_EXPORT int pllhip_replicates_create(pllhip_ctx_t * ctx, const unsigned int * h_weights, unsigned int count,
+                                           unsigned int width, pllhip_replicates_t ** out);
+PLLHIP_EXPORT void pllhip_replicates_destroy(pllhip_replicates_t * set);
+PLLHIP_EXPORT unsigned int pllhip_replicates_count(const pllhip_replicates_t * set);
+PLLHIP_EXPORT unsigned int pllhip_replicates_width(const pllhip_replicates_t * set);
+PLLHIP_EXPORT pllhip_ctx_t * pllhip_replicates_owner(const pllhip_replicates_t * set);
+PLLHIP_EXPORT int pllhip_replicate_loglikelihood(pllhip_ctx_t * ctx, const pllhip_replicates_t * set,
+                                                 const pllhip_posterior_edge_t * h_edges, unsigned int edge_count,
+                                                 const unsigned int * h_freqs_indices, size_t scratch_bytes,
+                                                 double * h_lnl, double * h_persite);
+
 /* The planner of k_tree_score on its own -- host logic, no device needed.  The ops the edge (parent_clv, child_clv
  * with their scaler indices) does not depend on are dropped; the rest are ordered depth-first from the edge, the
  * operand that needs more live values first, and a parent takes the slot of one of its operands.  Tips (pattern_tip)

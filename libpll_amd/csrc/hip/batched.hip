@@ -153,24 +153,12 @@ int pllhip_batch_reduce(pllhip_ctx * c, const double * partial, double * out, si
   return 0;
 }
 
-struct BatchEdgeArgs
-{
-  const BatchEdge * __restrict__ edges;
-  BatchModel m;
-  const unsigned int * __restrict__ tipmap;
-  double * __restrict__ partial;
-  unsigned int sites, states, rate_cats, tiles;
-  int rate_scalers;
-  BatchModelBlocks mb; // (MODEL only)
-};
-
 // the edge log-likelihood of every descriptor: k_lnl_gen's arithmetic (likelihood.hip), one lane per site, per (tile,
-// descriptor); the tile's sum: wave trees, then the four waves in order.  MODEL: frequencies, +I proportions and
-// category weights are those of the descriptor's model block
+// descriptor), the site's term by batch_edge_site_lnl (batched.hpp); the tile's sum: wave trees, then the four waves
+// in order.  MODEL: frequencies, +I proportions and category weights are those of the descriptor's model block
 template <bool MODEL>
 __global__ __launch_bounds__(PLLHIP_BATCH_TILE) void k_batch_edge_lnl(BatchEdgeArgs a)
 {
-  const unsigned int S = a.states, R = a.rate_cats;
   const unsigned int tile = blockIdx.x;
   const BatchEdge & e = a.edges[blockIdx.y];
   const double * __restrict__ blk = MODEL ? a.mb.p + (size_t)e.model * a.mb.stride : nullptr;
@@ -181,70 +169,7 @@ __global__ __launch_bounds__(PLLHIP_BATCH_TILE) void k_batch_edge_lnl(BatchEdgeA
   double lk = 0.0;
   if (n < a.sites)
   {
-    unsigned int rs[PLLHIP_MAX_RATE_CATS];
-    unsigned int site_scalings = 0;
-    if (a.rate_scalers)
-    {
-      unsigned int mn = 0xffffffffu;
-      for (unsigned int k = 0; k < R; ++k)
-      {
-        unsigned int v = e.pscal ? e.pscal[n * R + k] : 0u;
-        if (e.cscal) v += e.cscal[n * R + k];
-        rs[k] = v;
-        mn = v < mn ? v : mn;
-      }
-      site_scalings = mn;
-      for (unsigned int k = 0; k < R; ++k)
-      {
-        const unsigned int d = rs[k] - mn;
-        rs[k] = d > PLLHIP_SCALE_RATE_MAXDIFF ? PLLHIP_SCALE_RATE_MAXDIFF : d;
-      }
-    }
-    else
-    {
-      for (unsigned int k = 0; k < R; ++k) rs[k] = 0;
-      if (e.pscal) site_scalings += e.pscal[n];
-      if (e.cscal) site_scalings += e.cscal[n];
-    }
-    unsigned int mask = 0;
-    if (!e.cclv)
-    {
-      const unsigned int c = e.ctip[n];
-      mask = (S == 4) ? c : a.tipmap[c];
-    }
-    double terma = 0.0;
-    for (unsigned int k = 0; k < R; ++k)
-    {
-      const unsigned int fi = a.m.params[k];
-      const double * fr = freqs + (size_t)fi * S;
-      const double * pc = e.pclv + (n * R + k) * S;
-      const double * cc = e.cclv ? e.cclv + (n * R + k) * S : nullptr;
-      const double * m = e.pmat + (size_t)k * S * S;
-      double terma_r = 0.0;
-      for (unsigned int j = 0; j < S; ++j)
-      {
-        double termb = 0.0;
-        if (cc)
-          for (unsigned int q = 0; q < S; ++q) termb += m[j * S + q] * cc[q];
-        else
-          for (unsigned int q = 0; q < S; ++q)
-            if ((mask >> q) & 1u) termb += m[j * S + q];
-        terma_r += pc[j] * fr[j] * termb; // core_likelihood.c:955
-      }
-      if (rs[k] > 0) terma_r *= scale_minlh(rs[k]);
-      const double pinv = prop_invar[fi];
-      const double w = rate_weights[k];
-      if (pinv > 0.0)
-      {
-        const int inv = a.m.invariant ? a.m.invariant[n] : -1;
-        const double inv_lk = (inv == -1) ? 0.0 : fr[inv];
-        terma += w * (terma_r * (1.0 - pinv) + inv_lk * pinv);
-      }
-      else
-        terma += terma_r * w;
-    }
-    lk = log(terma);
-    if (site_scalings) lk += (double)site_scalings * log(PLLHIP_SCALE_THRESHOLD);
+    lk = batch_edge_site_lnl(a, e, freqs, prop_invar, rate_weights, n);
     lk *= (double)a.m.pattern_weights[n];
   }
   __shared__ double s_wave[PLLHIP_BATCH_TILE / 64];

@@ -1,5 +1,6 @@
 // batched.hpp -- internal: the device plumbing the batched calls share (insertion.hip, branch_opt.hip, posteriors.hip,
-// nni.hip, tree_score.hip, model_score.hip; the code is in batched.hip).  A new batched call starts from these pieces:
+// nni.hip, tree_score.hip, model_score.hip, replicates.hip; the code is in batched.hip).  A new batched call starts
+// from these pieces:
 //
 //   opening   pllhip_batch_open: the checks every batched call begins with;
 //   scratch   one BatchScratch per call family in the context (ctx.hpp), grown by pllhip_batch_scratch_grow and laid
@@ -10,7 +11,8 @@
 //             BatchModelBlocks: per-item models of a call that scores models, packed as BatchModelLayout says;
 //   sums      per (PLLHIP_BATCH_TILE-site tile, item) partial sums in a fixed order (batch_wave_sum, batch_waves_sum,
 //             batch_tile_sum), added per item in tile order (pllhip_batch_reduce);
-//   edge lnL  k_batch_edge_lnl: the log-likelihood at one edge per item, any shape (pllhip_batch_edge_lnl).
+//   edge lnL  k_batch_edge_lnl: the log-likelihood at one edge per item, any shape (pllhip_batch_edge_lnl); its per-site
+//             body, batch_edge_site_lnl, for kernels that keep the site terms apart.
 #pragma once
 #include "lnl_common.hpp"
 
@@ -156,6 +158,96 @@ struct BatchEdge
   unsigned int out, model;     // the item: its tile sums go to partial[out][tiles]; its model block, where the
                                // call has blocks (otherwise not read)
 };
+// what the kernel is given: the descriptors, the model, where the tile sums go
+struct BatchEdgeArgs
+{
+  const BatchEdge * __restrict__ edges;
+  BatchModel m;
+  const unsigned int * __restrict__ tipmap;
+  double * __restrict__ partial;
+  unsigned int sites, states, rate_cats, tiles;
+  int rate_scalers;
+  BatchModelBlocks mb; // (MODEL only)
+};
+// The unweighted log-likelihood of site n at descriptor e -- log(terma) + scalings * log(2^-256), k_lnl_gen's
+// arithmetic (likelihood.hip) -- with the frequencies, +I proportions and category weights given (BatchModel's or a
+// model block's).  The one copy of the per-site body: k_batch_edge_lnl multiplies it by the pattern weight and sums a
+// tile, the replicate call (replicates.hip) keeps it per site.  <ST, RT>: the state and category counts as
+// compile-time constants (0, 0: those of `a`) -- the same operations in the same order, so the same bits, with the
+// loops unrolled and the per-category counts in registers.
+template <int ST = 0, int RT = 0>
+__device__ __forceinline__ double batch_edge_site_lnl(const BatchEdgeArgs & a, const BatchEdge & e,
+                                                      const double * __restrict__ freqs,
+                                                      const double * __restrict__ prop_invar,
+                                                      const double * __restrict__ rate_weights, size_t n)
+{
+  const unsigned int S = ST > 0 ? (unsigned int)ST : a.states, R = RT > 0 ? (unsigned int)RT : a.rate_cats;
+  unsigned int rs[RT > 0 ? RT : PLLHIP_MAX_RATE_CATS];
+  unsigned int site_scalings = 0;
+  if (a.rate_scalers)
+  {
+    unsigned int mn = 0xffffffffu;
+    for (unsigned int k = 0; k < R; ++k)
+    {
+      unsigned int v = e.pscal ? e.pscal[n * R + k] : 0u;
+      if (e.cscal) v += e.cscal[n * R + k];
+      rs[k] = v;
+      mn = v < mn ? v : mn;
+    }
+    site_scalings = mn;
+    for (unsigned int k = 0; k < R; ++k)
+    {
+      const unsigned int d = rs[k] - mn;
+      rs[k] = d > PLLHIP_SCALE_RATE_MAXDIFF ? PLLHIP_SCALE_RATE_MAXDIFF : d;
+    }
+  }
+  else
+  {
+    for (unsigned int k = 0; k < R; ++k) rs[k] = 0;
+    if (e.pscal) site_scalings += e.pscal[n];
+    if (e.cscal) site_scalings += e.cscal[n];
+  }
+  unsigned int mask = 0;
+  if (!e.cclv)
+  {
+    const unsigned int c = e.ctip[n];
+    mask = (S == 4) ? c : a.tipmap[c];
+  }
+  double terma = 0.0;
+  for (unsigned int k = 0; k < R; ++k)
+  {
+    const unsigned int fi = a.m.params[k];
+    const double * fr = freqs + (size_t)fi * S;
+    const double * pc = e.pclv + (n * R + k) * S;
+    const double * cc = e.cclv ? e.cclv + (n * R + k) * S : nullptr;
+    const double * m = e.pmat + (size_t)k * S * S;
+    double terma_r = 0.0;
+    for (unsigned int j = 0; j < S; ++j)
+    {
+      double termb = 0.0;
+      if (cc)
+        for (unsigned int q = 0; q < S; ++q) termb += m[j * S + q] * cc[q];
+      else
+        for (unsigned int q = 0; q < S; ++q)
+          if ((mask >> q) & 1u) termb += m[j * S + q];
+      terma_r += pc[j] * fr[j] * termb; // core_likelihood.c:955
+    }
+    if (rs[k] > 0) terma_r *= scale_minlh(rs[k]);
+    const double pinv = prop_invar[fi];
+    const double w = rate_weights[k];
+    if (pinv > 0.0)
+    {
+      const int inv = a.m.invariant ? a.m.invariant[n] : -1;
+      const double inv_lk = (inv == -1) ? 0.0 : fr[inv];
+      terma += w * (terma_r * (1.0 - pinv) + inv_lk * pinv);
+    }
+    else
+      terma += terma_r * w;
+  }
+  double lk = log(terma);
+  if (site_scalings) lk += (double)site_scalings * log(PLLHIP_SCALE_THRESHOLD);
+  return lk;
+}
 // k_batch_edge_lnl over n descriptors (device) x tiles; the caller brackets it with a pllhip_prof_scope if it counts.
 // blocks: the model variant -- descriptor i takes the model of block d_edges[i].model
 int pllhip_batch_edge_lnl(pllhip_ctx * c, const BatchEdge * d_edges, unsigned int n, const unsigned int * params,

@@ -592,6 +592,11 @@ extern "C" void pllhip_ctx_destroy(pllhip_ctx_t * c)
   if (c->root_counts) (void)hipFree(c->root_counts);
   for (BatchScratch & bs : c->batch_scratch)
     if (bs.p) (void)hipFree(bs.p);
+  for (pllhip_replicates * r : c->replicate_sets)
+  {
+    if (r->d_weights) (void)hipFree(r->d_weights);
+    delete r;
+  }
   pllhip_aa_fused_free(c);
   for (int b = 0; b < 2; ++b)
   {

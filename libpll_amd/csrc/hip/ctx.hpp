@@ -21,13 +21,33 @@ struct pllhip_rep_work;
 // scratch of a batched call (batched.hpp): insertion -- P-matrices, insertion vectors, query vectors, partial sums;
 // branch lengths -- sumtables, Newton states, partial sums; posteriors -- edge descriptors and outputs; NNI and tree
 // scoring -- P-matrices, descriptors, partial sums and, where a route needs them, candidate CLVs, scale buffers, sumtables
-// (model scoring shares tree scoring's: the same pieces, plus a model block per item and the tree's lengths)
+// (model scoring shares tree scoring's: the same pieces, plus a model block per item and the tree's lengths); replicates
+// -- edge descriptors, the chunk's per-site terms and its per-span partial sums
 struct BatchScratch
 {
   void * p = nullptr;
   size_t bytes = 0;
 };
-enum { BATCH_INSERTION, BATCH_BRANCH_OPT, BATCH_POSTERIORS, BATCH_NNI, BATCH_TREE_SCORE, BATCH_FAMILIES };
+enum
+{
+  BATCH_INSERTION,
+  BATCH_BRANCH_OPT,
+  BATCH_POSTERIORS,
+  BATCH_NNI,
+  BATCH_TREE_SCORE,
+  BATCH_REPLICATES,
+  BATCH_FAMILIES
+};
+
+// a set of replicate weight vectors on a context's device (replicates.hip): `count` rows of `pitch` bytes, the weights
+// of a row `width` bytes each in site order, the bytes past the last site zero.  Owned by the context's list
+struct pllhip_replicates
+{
+  pllhip_ctx * ctx;
+  void * d_weights;
+  size_t pitch;
+  unsigned int count, width;
+};
 
 struct pllhip_ctx
 {
@@ -291,6 +311,8 @@ struct pllhip_ctx
   // the batched calls (batched.hpp): one scratch per call family, grown to what one chunk of a call needs and kept
   // until the context goes.  Apart on purpose: two families zero theirs only when it grows
   BatchScratch batch_scratch[BATCH_FAMILIES];
+  // the replicate sets that are alive (pllhip_replicates_create / _destroy); the context's end is theirs
+  std::vector<pllhip_replicates *> replicate_sets;
 
   // optional per-launch timing (pllhip_profile_*): one event pair per launch
   bool profiling = false;

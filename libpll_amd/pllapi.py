@@ -317,6 +317,15 @@ class PllLibrary:
             if hasattr(lib, "pll_amd_site_posteriors"):
                 lib.pll_amd_site_posteriors.argtypes = [_PP, C.c_void_p, C.c_uint, _up, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p]
+            if hasattr(lib, "pll_amd_replicate_loglikelihood"):
+                lib.pll_amd_replicates_create.restype = C.c_void_p
+                lib.pll_amd_replicates_create.argtypes = [_PP, C.c_void_p, C.c_uint]
+                lib.pll_amd_replicates_destroy.restype = None
+                lib.pll_amd_replicates_destroy.argtypes = [C.c_void_p]
+                lib.pll_amd_replicates_count.restype = C.c_uint
+                lib.pll_amd_replicates_count.argtypes = [C.c_void_p]
+                lib.pll_amd_replicate_loglikelihood.argtypes = [_PP, C.c_void_p, C.c_void_p, C.c_uint, _up,
+                                                                C.c_void_p, C.c_void_p]
 
     # -- library-level helpers -------------------------------------------------
     def errno(self):
@@ -536,6 +545,54 @@ BRANCH_CONVERGED, BRANCH_MAX_ITERS, BRANCH_NONFINITE = 0, 1, 2
 POSTERIOR_EDGE_DTYPE = np.dtype([("parent_clv_index", np.uint32), ("parent_scaler_index", np.int32),
                                  ("child_clv_index", np.uint32), ("child_scaler_index", np.int32),
                                  ("matrix_index", np.uint32)])
+
+# pll_amd_lnl_edge_t (include/pll_amd.h): the same five fields
+LNL_EDGE_DTYPE = POSTERIOR_EDGE_DTYPE
+
+
+def lnl_edges(edges):
+    """an LNL_EDGE_DTYPE array from rows of (parent_clv, parent_scaler, child_clv, child_scaler, matrix_index), or from
+    such an array"""
+    e = np.zeros(len(edges), dtype=LNL_EDGE_DTYPE)
+    if isinstance(edges, np.ndarray) and edges.dtype == LNL_EDGE_DTYPE:
+        e[:] = edges
+    else:
+        for i, row in enumerate(edges):
+            e[i] = tuple(row)
+    return e
+
+
+class Replicates:
+    """pll_amd_replicates_t (include/pll_amd.h): a set of site-weight vectors on a partition's device.  It dies with its
+    partition: after partition.destroy() a set must not be used, and destroy() on it must not be called."""
+
+    def __init__(self, partition, ptr):
+        self.partition = partition
+        self.lib = partition.lib
+        self.ptr = ptr
+
+    @classmethod
+    def create(cls, partition, weights):
+        """weights: [count][sites] non-negative integers below 2^32"""
+        if not hasattr(partition.lib, "pll_amd_replicate_loglikelihood"):
+            raise PllError("this library has no pll_amd_replicate_loglikelihood")
+        w = np.ascontiguousarray(weights, dtype=np.uint32)
+        if w.ndim == 1:
+            w = w.reshape(1, -1)
+        assert w.ndim == 2 and w.shape[1] == partition.s.sites, w.shape
+        ptr = partition.lib.pll_amd_replicates_create(partition.ptr, w.ctypes.data if w.size else None, w.shape[0])
+        partition._check(bool(ptr), "pll_amd_replicates_create")
+        return cls(partition, ptr)
+
+    def destroy(self):
+        if self.ptr:
+            self.lib.pll_amd_replicates_destroy(self.ptr)
+            self.ptr = None
+
+    @property
+    def count(self):
+        return int(self.lib.pll_amd_replicates_count(self.ptr))
+
 
 # pll_amd_nni_edge_t (include/pll_amd.h): the sides A, B (at u), C, D (at v), then the edge's own length
 NNI_SIDE_DTYPE = np.dtype([("clv_index", np.uint32), ("scaler_index", np.int32), ("length", np.float64)])
@@ -916,6 +973,24 @@ class Partition:
                                               ptr("site_rates"))
         self._check(ok, "pll_amd_site_posteriors")
         return out
+
+    def replicate_loglikelihood(self, rset, edges, freqs_indices, want_persite=False):
+        """pll_amd_replicate_loglikelihood: (lnl [edges][count] or None, persite [edges][sites] or None).  rset: a
+        Replicates of this partition, or None (then only the unweighted per-site log-likelihoods are computed);
+        edges: rows of (parent_clv, parent_scaler, child_clv, child_scaler, matrix_index) or an LNL_EDGE_DTYPE array."""
+        if not hasattr(self.lib, "pll_amd_replicate_loglikelihood"):
+            raise PllError("this library has no pll_amd_replicate_loglikelihood")
+        e = lnl_edges(edges)
+        fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+        n = len(e)
+        lnl = np.zeros((n, rset.count)) if rset is not None else None
+        persite = np.zeros((n, self.s.sites)) if (want_persite or rset is None) else None
+        ok = self.lib.pll_amd_replicate_loglikelihood(self.ptr, rset.ptr if rset is not None else None,
+                                                      e.ctypes.data if n else None, n, _u(fi),
+                                                      lnl.ctypes.data if lnl is not None and lnl.size else None,
+                                                      persite.ctypes.data if persite is not None and persite.size else None)
+        self._check(ok, "pll_amd_replicate_loglikelihood")
+        return lnl, persite
 
     # -- reading results back ----------------------------------------------------------
     def get_clv(self, idx):
