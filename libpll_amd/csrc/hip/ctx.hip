@@ -936,7 +936,10 @@ struct MirrorCopies
   unsigned int * dst[PLLHIP_MIRROR_BATCH];
   unsigned int words[PLLHIP_MIRROR_BATCH];
 };
-// blockIdx.y = buffer; 16 bytes per lane where the alignment allows, words for the tail
+// blockIdx.y = buffer; 16 bytes per lane whatever the addresses, words for the tail.  The source is cast to uint4 without
+// a test: a CLV is 8-byte aligned only where states * rate_cats * (sites + 64) is odd, a scale buffer 4-byte aligned
+// only where its stride is, and global loads of gfx9 take any dword-aligned address (unaligned access mode); the
+// destination is pinned host memory of pllhip_host_alloc.  tests/test_gpu_default_mirrors.py holds it to that.
 __global__ __launch_bounds__(256) void k_mirror_copy(MirrorCopies m)
 {
   const unsigned int * __restrict__ src = m.src[blockIdx.y];
@@ -963,6 +966,13 @@ extern "C" void pllhip_host_free(void * p)
 extern "C" int pllhip_mirror_batch(pllhip_ctx_t * c, const pllhip_mirror_job_t * jobs, unsigned int count)
 {
   pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
+  // (a group of ONE range -- a device list on a partition of at most 256 sites -- answers pllhip_shard_count with 1 like
+  // an ordinary context, and its range holds every site: the range's buffers are the partition's)
+  if (c->shards.size() == 1)
+  {
+    pllhip_device_guard guard;
+    return pllhip_mirror_batch(c->shards[0], jobs, count);
+  }
   if (!c->shards.empty()) { pllhip_set_error("pllhip_mirror_batch: not for a sharded context"); return -1; }
   HIP_TRY(hipSetDevice(c->sh.device));
   PLLHIP_CERT_FIRST(c);
