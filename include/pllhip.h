@@ -317,6 +317,23 @@ PLLHIP_EXPORT unsigned int pllhip_fused_char_batches_dry(const unsigned int * ti
                                                          unsigned int rate_cats, unsigned int * chars_out,
                                                          unsigned int * batch_out);
 
+/* What the 4-state whole-list kernel does in scalar registers, run on the host (the kernel's own functions, no device).
+ * pllhip_fused_group_mask_dry: gw = 2, 4, 8, 16 lanes per group; mask: bit l = both entries of lane l are below the
+ * scaling threshold.  Returns the mask of the groups whose lanes are ALL set, every lane of such a group set (0 for
+ * another gw).
+ * pllhip_fused_pair_index_dry: row_a / row_b: the characters of one tile of the left / right tip row as 32-bit words
+ * (2 * sps / 4 of them, four characters each, little-endian); lmask4 / rmask4: 0x0f0f0f0f where the factor has that
+ * row, else 0; sps = 4, 8, 16, 32 sites per sub-step; sub_step 0 or 1; lane 0..63.  Returns the pair-table index of
+ * that lane's site, (a & lmask) << 4 | (b & rmask), or ~0 for arguments out of range. */
+PLLHIP_EXPORT unsigned long long pllhip_fused_group_mask_dry(unsigned int gw, unsigned long long mask);
+/* The scale bit lane t of the kernel takes for entry t of a tile (t < 2 * 64 / gw: group t % (64 / gw) of sub-step
+ * t / (64 / gw)) from the two sub-steps' group masks (pllhip_fused_group_mask_dry's results); ~0 out of range. */
+PLLHIP_EXPORT unsigned int pllhip_fused_entry_bit_dry(unsigned int gw, unsigned long long groups0,
+                                                      unsigned long long groups1, unsigned int t);
+PLLHIP_EXPORT unsigned int pllhip_fused_pair_index_dry(const unsigned int * row_a, const unsigned int * row_b,
+                                                       unsigned int lmask4, unsigned int rmask4, unsigned int sps,
+                                                       unsigned int sub_step, unsigned int lane);
+
 /* The 20-state whole-list kernel's list logic without a device (partials_aa_fused.hip plans every new list with the same
  * three functions of fused_plan.hip): what each op is to the kernel, what the scaling certificate (above) makes of the
  * list, and how the list is walked.  Geometry as for pllhip_fused_plan_dry.  lookups_max: the lookup budget

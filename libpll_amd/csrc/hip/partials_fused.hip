@@ -41,7 +41,15 @@
 //   pairs     the parent of a gathered-gathered op that nothing reads from HBM is walked but not stored: its tile stores
 //             go to the wave's sink, and deferred.hip stores the CLV on demand (PLLHIP_FUSED_UNSTORED, see step())
 //   limit     a wave's own serial path, not HBM: twelve waves per CU is all the slots allow, so
-//             the order within an op overlaps the wave's latencies with its own work (see step())
+//             the order within an op overlaps the wave's latencies with its own work (see step()).
+//             Measured: the vector unit was busy 93 % of the time with three waves per SIMD, but
+//             moving a third of the vector instructions to the scalar unit one for one bought 6 % -- what a wave
+//             pays for is every instruction it issues, vector or scalar; taking instructions OUT (the scaling
+//             test's early exit) bought the rest
+//   scalar    what is wave-uniform, or already a wave mask, stays in scalar registers: the scaling decision is
+//             made on the compares' own 64-bit masks (scale_groups()), the two tip rows' characters are joined
+//             word by word before a lane picks its byte (gather_factor()) -- partials_fused.hpp has the
+//             integer code, which the host runs as well (tests/test_host_scalar_masks.py)
 //
 // The arithmetic per site is that of k_dna_partials, statement for statement (dot4 /
 // masksum4 order, scaling rule of core_partials_avx.c:486-527), so results are
@@ -229,15 +237,26 @@ typedef unsigned int pll_v4u __attribute__((ext_vector_type(4)));
 // a wave's sink in 16-byte granules: PLLHIP_FUSED_J KB of tile, 256 bytes of counts, the ticket word's line
 #define PLLHIP_FUSED_SINK_GRANULES (PLLHIP_FUSED_J * 64 + 32)
 
-// all lanes of a group of W (2, 4 or 8: a site's lanes, or a rate's) hold x != 0?  DPP, no ballot
-template <int W>
-__device__ __forceinline__ unsigned int group_and(unsigned int x)
+// The scaling rule of core_partials_avx.c:486-527 for a lane's two entries of a group of GW lanes (2 ... 16: a site's
+// lanes, or a rate's): all of the group's entries below the threshold -> times 2^256; x * 1.0 is x.  The two compares
+// deliver 64-bit wave masks; the decision is made on those, in scalar registers (pllhip_fused_group_mask,
+// partials_fused.hpp), and comes back to the lanes only as the select mask of the factor.  `on`: all ones where the op
+// has a scale buffer, else 0 (wave-uniform).  Returns the groups that scaled, every lane of a group set.
+// (The branch is wave-uniform and holds no memory operation: the compiler's count of loads and stores in flight is the
+// same on both paths.)
+template <unsigned int GW>
+__device__ __forceinline__ unsigned long long scale_groups(unsigned long long on, double & q0, double & q1)
 {
-  x &= (unsigned int)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true);                // lane ^ 1
-  if (W >= 4) x &= (unsigned int)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xF, 0xF, true);    // lane ^ 2
-  if (W >= 8) x &= (unsigned int)__builtin_amdgcn_mov_dpp((int)x, 0x141, 0xF, 0xF, true);   // lane <-> 7 - lane
-  if (W >= 16) x &= (unsigned int)__builtin_amdgcn_mov_dpp((int)x, 0x128, 0xF, 0xF, true);  // row_ror:8 = lane ^ 8
-  return x;
+  const unsigned long long below = __builtin_amdgcn_fcmp(q0, PLLHIP_SCALE_THRESHOLD, 4) & // (4: ordered "less than")
+                                   __builtin_amdgcn_fcmp(q1, PLLHIP_SCALE_THRESHOLD, 4) & on;
+  // (no lane of the wave below the threshold, the usual case, or no scale buffer: one scalar test, and nothing is
+  // multiplied by 1.0)
+  if (below == 0ull) return 0ull;
+  const unsigned long long groups = pllhip_fused_group_mask<GW>(below);
+  const double factor = __hiloint2double(__builtin_amdgcn_inverse_ballot_w64(groups) ? 0x4ff00000 : 0x3ff00000, 0); // 2^256 : 1.0
+  q0 *= factor;
+  q1 *= factor;
+  return groups;
 }
 
 // The tail of k_lnl_dna for one site (likelihood.hip), statement for statement: logarithm, scaler term, pattern weight.
@@ -409,19 +428,16 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       f.pm = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(bases.pmat) + off);
       if (RC == 8) f.pm2 = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(bases.pmat) + rec_req_rmat(r) + pm_lane);
     };
-    // A lane's characters of sub-step j of a row: byte j * SPS + tip_lane of the row's TS bytes, i.e. one of
-    // the SPS / 4 words that `readlane` brings from the lane(s) holding them (wave-uniform positions).
-    auto row_code = [&](unsigned int pos, unsigned int j) -> unsigned int {
-      unsigned int word = 0;
+    // The characters of sub-step j of a row: bytes j * SPS ... of the row's TS bytes, i.e. the SPS / 4 words that
+    // `readlane` brings from the lane(s) holding them (wave-uniform positions, wave-uniform results: scalar registers).
+    auto row_words = [&](unsigned int pos, unsigned int j, unsigned int (&out)[SPS / 4]) {
 #pragma unroll
       for (unsigned int m = 0; m < SPS / 4; ++m)
       {
         const unsigned int w = j * (SPS / 4) + m; // word of the row
         const unsigned int v = (w & 3u) == 0 ? cs.x : (w & 3u) == 1 ? cs.y : (w & 3u) == 2 ? cs.z : cs.w;
-        const unsigned int sw = (unsigned int)__builtin_amdgcn_readlane((int)v, (int)(pos + w / 4));
-        word = ((tip_lane >> 2) == m) ? sw : word;
+        out[m] = (unsigned int)__builtin_amdgcn_readlane((int)v, (int)(pos + w / 4));
       }
-      return (word >> ((tip_lane & 3u) * 8u)) & 255u;
     };
     // ... and ONE op ahead its entries of the pair table are gathered -- by an op that HAS a gathered factor only (an
     // absent tip's character is 0).  The characters' readlanes, the address arithmetic and the loads of a factor sit
@@ -443,12 +459,17 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     // the loads, until both ends of their life were made whole 16-byte operands of an empty asm statement).
     constexpr bool SECOND = RC <= 4 && MODE != SCALE_RATE; // (partials.hip: what may defer a cherry; checked by the launch)
     auto gather_factor = [&](pll_v2d (&pt)[J], unsigned int ch, unsigned int table_off) {
-      const unsigned int lmask = (ch & PLLHIP_FUSED_CH_LTIP) ? 15u : 0u, rmask = (ch & PLLHIP_FUSED_CH_RTIP) ? 15u : 0u;
+      // (the two rows' words are joined in scalar registers -- four characters at a time --, and a lane picks its word
+      // and byte once, for the pair: pllhip_fused_pair_index, partials_fused.hpp; then one shift-add)
+      const unsigned int lmask = (ch & PLLHIP_FUSED_CH_LTIP) ? 0x0f0f0f0fu : 0u, rmask = (ch & PLLHIP_FUSED_CH_RTIP) ? 0x0f0f0f0fu : 0u;
       const unsigned long long tab = (unsigned long long)(uintptr_t)bases.pairtab + table_off; // (uniform)
 #pragma unroll
       for (unsigned int j = 0; j < J; ++j)
       {
-        const unsigned int pair = ((row_code(PLLHIP_FUSED_CH_LPOS(ch), j) & lmask) << 4) | (row_code(PLLHIP_FUSED_CH_RPOS(ch), j) & rmask);
+        unsigned int lw[SPS / 4], rw[SPS / 4];
+        row_words(PLLHIP_FUSED_CH_LPOS(ch), j, lw);
+        row_words(PLLHIP_FUSED_CH_RPOS(ch), j, rw);
+        const unsigned int pair = pllhip_fused_pair_index<SPS>(lw, rw, lmask, rmask, tip_lane);
         const unsigned int off = pair * (W * 16u) + gat_lane;
         asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pt[j]) : "v"(off), "s"(tab) : "memory");
       }
@@ -655,6 +676,7 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       constexpr unsigned int EPS = 64u / GW, E = J * EPS;        // entries per sub-step / per tile
       static_assert(MODE == SCALE_NONE || CW == EPS, "one count word per entry of a sub-step");
       const unsigned int t = lane % E; // (lanes beyond the entries repeat them: same values to the same addresses)
+      const unsigned int t_shift = pllhip_fused_entry_shift<GW>(t); // (where entry t's scale bit is in the tile's mask)
 
       // Everything requested one op ago has arrived once fu's matrix block is used -- and with
       // it what that iteration's reload() copied into this op's slots (issued ahead of those
@@ -697,24 +719,10 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
           {
             double q0 = a[j].x * b[j].x, q1 = a[j].y * b[j].y;
             fired[j] = 0;
-            if (MODE != SCALE_NONE)
-            {
-              const unsigned int small = ((q0 < PLLHIP_SCALE_THRESHOLD) & (q1 < PLLHIP_SCALE_THRESHOLD)) ? 1u : 0u;
-              const bool scale = pscale && group_and<(int)GW>(small) != 0u;
-              const double factor = __hiloint2double(scale ? 0x4ff00000 : 0x3ff00000, 0); // 2^256 : 1.0
-              q0 *= factor;
-              q1 *= factor;
-              fired[j] = __ballot(scale);
-            }
+            if (MODE != SCALE_NONE) fired[j] = scale_groups<GW>(pscale ? ~0ull : 0ull, q0, q1);
             out[j] = make_double2(q0, q1);
           }
-          if (MODE != SCALE_NONE)
-          {
-            unsigned long long mine = fired[0];
-#pragma unroll
-            for (unsigned int j = 1; j < J; ++j) mine = (t / EPS == j) ? fired[j] : mine;
-            own = (unsigned int)(mine >> ((t % EPS) * GW)) & 1u;
-          }
+          if (MODE != SCALE_NONE) own = (unsigned int)(pllhip_fused_entry_bits<GW, J>(fired) >> t_shift) & 1u;
         };
         // (the common op first: a plain inner-inner op costs one scalar test here)
         if ((fl & (PLLHIP_FUSED_KIND_MASK | PLLHIP_FUSED_LPROD | PLLHIP_FUSED_RPROD)) == 0u)
@@ -811,15 +819,8 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
           // scaling rule of core_partials_avx.c:486-527: all entries of the site (of the rate,
           // with per-rate scalers) below the threshold; x * 1.0 is x
           scaled[j] = 0;
-          if (MODE != SCALE_NONE)
-          {
-            const unsigned int small = ((q0 < PLLHIP_SCALE_THRESHOLD) & (q1 < PLLHIP_SCALE_THRESHOLD)) ? 1u : 0u;
-            const bool scale = scaling && group_and<(int)GW>(small) != 0u;
-            const double factor = __hiloint2double(scale ? 0x4ff00000 : 0x3ff00000, 0); // 2^256 : 1.0
-            q0 *= factor;
-            q1 *= factor;
-            scaled[j] = __ballot(scale); // (wave-uniform: which groups of this sub-step were scaled)
-          }
+          // (wave-uniform: which groups of this sub-step were scaled -- scale_groups(), on the compares' own masks)
+          if (MODE != SCALE_NONE) scaled[j] = scale_groups<GW>(scaling ? ~0ull : 0ull, q0, q1);
           p0[j] = q0;
           p1[j] = q1;
         }
@@ -855,10 +856,8 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       // with per-site counts).  (An op without a scale buffer stores to the sink.)
       if (MODE != SCALE_NONE)
       {
-        unsigned long long mine = scaled[0];
-#pragma unroll
-        for (unsigned int j = 1; j < J; ++j) mine = (t / EPS == j) ? scaled[j] : mine;
-        const unsigned int bit = (unsigned int)(mine >> ((t % EPS) * GW)) & 1u;
+        // (the sub-steps' masks joined in scalar registers, one shift per lane: pllhip_fused_entry_bits)
+        const unsigned int bit = (unsigned int)(pllhip_fused_entry_bits<GW, J>(scaled) >> t_shift) & 1u;
         // (tip operands inherit nothing)
         if (!(fl & PLLHIP_FUSED_LCNT)) lc = 0u;
         if (!(fl & PLLHIP_FUSED_RCNT)) rc = 0u;
@@ -1489,5 +1488,65 @@ int pllhip_relaunch_fused(pllhip_ctx * c)
     case 2: return launch_fused_rc<2>(c, d_plan, bases, count, nslots, mode, c->fused_last_edge);
     case 8: return launch_fused_rc<8>(c, d_plan, bases, count, nslots, mode, c->fused_last_edge);
     default: return launch_fused_rc<4>(c, d_plan, bases, count, nslots, mode, c->fused_last_edge);
+  }
+}
+
+// ---------------------------------------------------------------- host: the kernel's scalar-side helpers without a device
+// (partials_fused.hpp: the functions the kernel calls; tests/test_host_scalar_masks.py)
+
+extern "C" unsigned long long pllhip_fused_group_mask_dry(unsigned int gw, unsigned long long mask)
+{
+  switch (gw)
+  {
+    case 2: return pllhip_fused_group_mask<2>(mask);
+    case 4: return pllhip_fused_group_mask<4>(mask);
+    case 8: return pllhip_fused_group_mask<8>(mask);
+    case 16: return pllhip_fused_group_mask<16>(mask);
+    default: return 0;
+  }
+}
+
+// the count bit of entry t of a tile, from its two sub-steps' group masks, as the kernel's lane t takes it
+extern "C" unsigned int pllhip_fused_entry_bit_dry(unsigned int gw, unsigned long long groups0, unsigned long long groups1,
+                                                   unsigned int t)
+{
+  static_assert(PLLHIP_FUSED_J == 2, "two sub-steps' masks");
+  const unsigned long long groups[2] = {groups0, groups1};
+  if (gw < 2u || gw > 16u || t >= 2u * (64u / gw)) return ~0u;
+  switch (gw)
+  {
+    case 2: return (unsigned int)(pllhip_fused_entry_bits<2, 2>(groups) >> pllhip_fused_entry_shift<2>(t)) & 1u;
+    case 4: return (unsigned int)(pllhip_fused_entry_bits<4, 2>(groups) >> pllhip_fused_entry_shift<4>(t)) & 1u;
+    case 8: return (unsigned int)(pllhip_fused_entry_bits<8, 2>(groups) >> pllhip_fused_entry_shift<8>(t)) & 1u;
+    case 16: return (unsigned int)(pllhip_fused_entry_bits<16, 2>(groups) >> pllhip_fused_entry_shift<16>(t)) & 1u;
+    default: return ~0u;
+  }
+}
+
+template <unsigned int SPS>
+static unsigned int pair_index_dry(const unsigned int * row_a, const unsigned int * row_b, unsigned int lmask4, unsigned int rmask4,
+                                   unsigned int sub_step, unsigned int lane)
+{
+  // as gather_factor() takes them: words sub_step * (SPS / 4) ... of each row, the lane's site lane / W of the sub-step
+  unsigned int a[SPS / 4], b[SPS / 4];
+  for (unsigned int m = 0; m < SPS / 4; ++m)
+  {
+    a[m] = row_a[sub_step * (SPS / 4) + m];
+    b[m] = row_b[sub_step * (SPS / 4) + m];
+  }
+  return pllhip_fused_pair_index<SPS>(a, b, lmask4, rmask4, lane / (64u / SPS));
+}
+
+extern "C" unsigned int pllhip_fused_pair_index_dry(const unsigned int * row_a, const unsigned int * row_b, unsigned int lmask4,
+                                                    unsigned int rmask4, unsigned int sps, unsigned int sub_step, unsigned int lane)
+{
+  if (!row_a || !row_b || lane >= 64u || sub_step >= (unsigned int)PLLHIP_FUSED_J) return ~0u;
+  switch (sps)
+  {
+    case 4: return pair_index_dry<4>(row_a, row_b, lmask4, rmask4, sub_step, lane);
+    case 8: return pair_index_dry<8>(row_a, row_b, lmask4, rmask4, sub_step, lane);
+    case 16: return pair_index_dry<16>(row_a, row_b, lmask4, rmask4, sub_step, lane);
+    case 32: return pair_index_dry<32>(row_a, row_b, lmask4, rmask4, sub_step, lane);
+    default: return ~0u;
   }
 }

@@ -134,6 +134,77 @@ static_assert(sizeof(FusedRec) == 64, "sixteen words per op");
 #define PLLHIP_FUSED_CH_RTIP (1u << 17)
 #define PLLHIP_FUSED_CH_LOAD (1u << 18)                /* op + 2's rows are in another batch: fetch batch (x >> 24) */
 
+// ---- What k_dna_fused does on the scalar side: integer code on wave masks and on wave-uniform words, no lane values.
+// Plain C++, so the host runs the very functions (pllhip_fused_group_mask_dry, pllhip_fused_pair_index_dry;
+// tests/test_host_scalar_masks.py).
+
+// The scaling rule's "all entries of the site (of the rate) are below the threshold" as mask arithmetic.  `below`: bit
+// l set = both entries of lane l are below it (the two compares' own 64-bit results, and-ed).  Returns the mask in which
+// all GW lanes of a group are set exactly where all GW of them were set in `below`: the and of the mask with itself
+// shifted by 1, 2, 4, 8 as far as GW needs has, at a group's base lane, the and over the group; those bits alone are
+// kept and spread over their groups (groups do not overlap: the multiplication by 2^GW - 1 carries nothing).
+template <unsigned int GW>
+__host__ __device__ constexpr unsigned long long pllhip_fused_group_base()
+{
+  static_assert(GW == 2 || GW == 4 || GW == 8 || GW == 16, "a site's lanes, or a rate's");
+  return GW == 2 ? 0x5555555555555555ull : GW == 4 ? 0x1111111111111111ull : GW == 8 ? 0x0101010101010101ull : 0x0001000100010001ull;
+}
+template <unsigned int GW>
+__host__ __device__ constexpr unsigned long long pllhip_fused_group_mask(unsigned long long below)
+{
+  unsigned long long m = below;
+  m &= m >> 1;
+  if (GW >= 4) m &= m >> 2;
+  if (GW >= 8) m &= m >> 4;
+  if (GW >= 16) m &= m >> 8;
+  m &= pllhip_fused_group_base<GW>();
+  return (m << GW) - m;
+}
+// The count bits of a tile's entries out of its sub-steps' group masks.  Entry t of the tile (lane t's: t < J * 64 / GW)
+// is group t % EPS of sub-step t / EPS (EPS = 64 / GW groups per sub-step).  The sub-steps' base bits are laid side by
+// side in ONE mask -- sub-step j's in bit j of each group, J <= GW -- so that a lane finds its entry's bit with one shift
+// by a number that never changes, (t % EPS) * GW + t / EPS, whichever sub-step holds it.
+template <unsigned int GW, unsigned int J>
+__host__ __device__ constexpr unsigned long long pllhip_fused_entry_bits(const unsigned long long (&groups)[J])
+{
+  static_assert(J <= GW, "a group has a bit for every sub-step");
+  unsigned long long bits = 0;
+  for (unsigned int j = 0; j < J; ++j) bits |= (groups[j] & pllhip_fused_group_base<GW>()) << j;
+  return bits;
+}
+template <unsigned int GW>
+__host__ __device__ constexpr unsigned int pllhip_fused_entry_shift(unsigned int t)
+{
+  return (t % (64u / GW)) * GW + t / (64u / GW);
+}
+
+// The pair-table index of one site of a sub-step.  a[], b[]: the SPS / 4 words of the sub-step in the left and the
+// right tip row, four characters each (wave-uniform: v_readlane results); lmask4 / rmask4: 0x0f0f0f0f where the factor
+// has that row, else 0 (an absent tip's character is 0).  The two rows are joined word by word BEFORE anything depends
+// on the lane -- codes are below 16, so no byte carries into its neighbour --, then the site picks its word and byte
+// ONCE, for the pair.
+template <unsigned int SPS>
+__host__ __device__ constexpr unsigned int pllhip_fused_pair_index(const unsigned int (&a)[SPS / 4], const unsigned int (&b)[SPS / 4],
+                                                                   unsigned int lmask4, unsigned int rmask4, unsigned int site)
+{
+  static_assert(SPS == 4 || SPS == 8 || SPS == 16 || SPS == 32, "sites per sub-step");
+  unsigned int joined[SPS / 4] = {};
+  for (unsigned int m = 0; m < SPS / 4; ++m)
+    joined[m] = ((a[m] & lmask4) << 4) + (b[m] & rmask4); // (no common bit: + is |, and one shift-add)
+  if constexpr (SPS == 4) return (joined[0] >> (site * 8u)) & 255u;
+  else
+  {
+    // two words at a time, a scalar register pair: eight sites are one 64-bit shift by the lane's own amount
+    unsigned long long two = 0;
+    for (unsigned int m = 0; m < SPS / 8; ++m)
+    {
+      const unsigned long long d = (unsigned long long)joined[2 * m] | ((unsigned long long)joined[2 * m + 1] << 32);
+      two = (SPS == 8 || (site >> 3) == m) ? d : two;
+    }
+    return (unsigned int)(two >> ((site & 7u) * 8u)) & 255u;
+  }
+}
+
 // sources and LDS destinations of the operands an op reloads (few ops have any: kept out of the records)
 struct FusedSrc
 {
