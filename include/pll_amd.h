@@ -1251,6 +1251,12 @@ PLL_EXPORT int pll_amd_unstored_stats(pll_partition_t * partition, unsigned long
  * folded CLVs materialised}. */
 PLL_EXPORT int pll_amd_set_pair_fold(pll_partition_t * partition, int on);
 PLL_EXPORT int pll_amd_pair_fold_stats(pll_partition_t * partition, unsigned long long * stats4);
+/* Pair rows of 4-state partitions with PLL_ATTRIB_PATTERN_TIP (pllhip.h: pllhip_set_pair_row_capacity): the whole-list
+ * launch reads a cherry's table index from one cached row per ordered tip pair.  rows: capacity of the pool (0: the
+ * default, one row per tip -- as much memory as the tip rows, allocated on first use).  stats4: {rows live now, rows
+ * built in total, build launches, evictions}. */
+PLL_EXPORT int pll_amd_set_pair_row_capacity(pll_partition_t * partition, unsigned int rows);
+PLL_EXPORT int pll_amd_pair_row_stats(pll_partition_t * partition, unsigned long long * stats4);
 /* Edge log-likelihood terms from the 4-state whole-list launch (pllhip.h: pllhip_set_edge_fold): after
  * pll_compute_edge_loglikelihood at an inner-inner edge, the next pll_update_partials that writes one of the edge's two
  * CLVs also forms the edge's per-site terms, and the same evaluation then only sums them -- bit for bit the value it

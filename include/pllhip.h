@@ -285,6 +285,30 @@ PLLHIP_EXPORT int pllhip_fused_plan_dry_folded(unsigned int tips, unsigned int c
                                                unsigned int * reloads_out, unsigned char * unstored_out,
                                                unsigned char * folded_out);
 
+/* Pair rows (4 states, whole-list kernel; DESIGN.md 2.0 "Tips").  For an ordered pair of tips (a, b) of a partition
+ * with PLL_ATTRIB_PATTERN_TIP the context caches one row of bytes ((row_a[n] & 15) << 4) | (row_b[n] & 15): the index a
+ * list kernel gathers a cherry's factor by, formed once instead of on every tile of every call.  The pool is one
+ * allocation made on first use -- `tips` rows by default, as much memory as the tip rows --, a row is evicted only for a
+ * list that does not name it (least recently used first), the pool grows where a list names more pairs than it holds,
+ * and pllhip_put_tipchars has the tip's rows rebuilt in place before the next list launch.  Each shard has its own.
+ * pllhip_set_pair_row_capacity(ctx, n): n rows (0: the default); the pool is dropped and built again on demand.
+ * pllhip_pair_row_stats: {rows live now, rows built in total, build launches, evictions}. */
+PLLHIP_EXPORT int pllhip_set_pair_row_capacity(pllhip_ctx_t * ctx, unsigned int n);
+PLLHIP_EXPORT int pllhip_pair_row_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+/* Host logic, no device (tests/test_host_pair_rows.py): the pair row's byte; the index gather_factor() of the list
+ * kernel takes from ONE row's words of a tile (kind 0 a pair row, 1 a single tip that is the table's first character,
+ * 2 one that is its second); and the rows every walked op's gathers name, on top of pllhip_fused_plan_dry_folded's
+ * walk: gathers_out[12] per walked op = four gathers x {first tip + 1, second tip + 1, chars word}. */
+PLLHIP_EXPORT unsigned int pllhip_pair_row_byte_dry(unsigned int a, unsigned int b);
+PLLHIP_EXPORT unsigned int pllhip_fused_row_index_dry(const unsigned int * row, unsigned int kind, unsigned int sps,
+                                                      unsigned int sub_step, unsigned int lane);
+PLLHIP_EXPORT int pllhip_fused_plan_dry_rows(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                             int pattern_tip, unsigned int rate_cats, const pllhip_op_t * ops,
+                                             unsigned int count, unsigned int nslots, unsigned int * nkept,
+                                             unsigned int * order_out, unsigned char * deferred_out,
+                                             unsigned char * folded_out, unsigned int * gathers_out,
+                                             unsigned int * batch_out, unsigned int * nbatches_out);
+
 /* Edge log-likelihood terms from the 4-state whole-list launch.  pllhip_edge_loglikelihood remembers an inner-inner
  * request; the next pllhip_update_partials that runs as ONE whole-list launch and writes one of the edge's two CLVs
  * also forms that edge's per-site terms from the CLVs it still holds on chip, and an evaluation of exactly that

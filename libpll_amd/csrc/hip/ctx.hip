@@ -583,6 +583,7 @@ extern "C" void pllhip_ctx_destroy(pllhip_ctx_t * c)
   if (c->d_edge_terms) (void)hipFree(c->d_edge_terms);
   if (c->d_tile_counter) (void)hipFree(c->d_tile_counter);
   if (c->d_pairtab) (void)hipFree(c->d_pairtab);
+  pllhip_pair_rows_free(c);
   if (c->defer_pool) (void)hipFree(c->defer_pool);
   if (c->cherry_pool) (void)hipFree(c->cherry_pool);
   if (c->cherry_codes) (void)hipFree(c->cherry_codes);
@@ -656,6 +657,7 @@ extern "C" int pllhip_put_tipchars(pllhip_ctx_t * c, unsigned int tip, const uns
     pllhip_set_error("pllhip_put_tipchars: tip %u invalid", tip);
     return -1;
   }
+  pllhip_pair_rows_tip_written(c, tip); // (pair_rows.hip: rebuilt in place before the next list launch reads them)
   return h2d(c, c->tipchars + (size_t)tip * c->tip_stride, h, c->sh.sites);
 }
 

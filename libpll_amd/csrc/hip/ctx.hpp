@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <utility>
 #include <vector>
 
 #include "pllhip.h"
@@ -130,6 +131,25 @@ struct pllhip_ctx
   // layout_epoch; a kept plan is only reused while its epoch is the current one.
   unsigned int layout_epoch = 0, fused_last_epoch = 0;
   double * d_pairtab = nullptr; // pair tables of the tip-tip ops of the current op list
+  // ---- pair rows (pair_rows.hip, DESIGN.md 2.0 "Tips"): per ordered tip pair (a, b) one cached row of bytes
+  // ((row_a[n] & 15) << 4) | (row_b[n] & 15) -- the pair-table index a 4-state list kernel gathers a cherry's factor by.
+  // ONE allocation of `cap` rows of the tip rows' stride, made on first use; a row lives until a list that does not
+  // name it needs its place (least recently used first) and is rebuilt in place when one of its tips' rows changes.
+  struct pair_row
+  {
+    unsigned int a = 0, b = 0;
+    bool live = false, stale = false;      // stale: a tip row of it was written since it was built
+    unsigned long long used = 0;           // pair_rows.clock of the last list that named it
+  };
+  struct pair_row_pool
+  {
+    unsigned char * d = nullptr;           // [cap][tip_stride] + PLLHIP_TAIL_SITES
+    std::vector<pair_row> rows;            // [cap]
+    unsigned int want = 0;                 // pllhip_set_pair_row_capacity (0: `tips` rows)
+    unsigned int nstale = 0;
+    unsigned long long clock = 0;
+    unsigned long long stats[4] = {0, 0, 0, 0}; // rows live (filled on read), rows built, build launches, evictions
+  } pair_rows;
   // ---- deferred cherries (deferred.hip): a tip-tip op of a 4-state whole-list launch is not run; its
   // parent CLV is DEFINED by its two tip rows and a kept copy of its pair table T[c1][c2][rate][state] until somebody
   // other than a list kernel needs the bytes -- every such entry point materialises what it touches first
@@ -399,6 +419,13 @@ void pllhip_group_destroy(pllhip_ctx * c);
       return (int)e_;                                                         \
     }                                                                         \
   } while (0)
+
+// pair_rows.hip: the cached pair rows of a context (pllhip_ctx::pair_rows)
+int pllhip_pair_rows_resolve(pllhip_ctx * c, const std::vector<std::pair<unsigned int, unsigned int>> & need,
+                             std::vector<const unsigned char *> & rows);
+int pllhip_pair_rows_refresh(pllhip_ctx * c);                       // stale rows rebuilt in place, on the stream
+void pllhip_pair_rows_tip_written(pllhip_ctx * c, unsigned int tip); // a tip row's bytes change: its pair rows are stale
+void pllhip_pair_rows_free(pllhip_ctx * c);
 
 static inline bool pllhip_is_tip(const pllhip_ctx * c, unsigned int clv_index)
 {

@@ -1092,7 +1092,9 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
                              unsigned int * reloads_out, unsigned int * materialise_out,
                              unsigned int * nmaterialise, unsigned int * dropped_out, unsigned int * ndropped,
                              const int * edge4, unsigned int rate_cats, int * edge_out,
-                             unsigned char * unstored_out = nullptr, unsigned char * folded_out = nullptr)
+                             unsigned char * unstored_out = nullptr, unsigned char * folded_out = nullptr,
+                             unsigned int * gathers_out = nullptr, unsigned int * batch_out = nullptr,
+                             unsigned int * nbatches_out = nullptr)
 {
   FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
   if (dry_ops_in_range("pllhip_fused_plan_dry_deferred", geom, ops, count)) return -1;
@@ -1159,9 +1161,37 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
       e.pinned[t] = pinned && pinned[ends[t]];
     }
   }
+  // (pllhip_fused_plan_dry_rows) the tip rows of every kept op's gathered factors, tip index + 1, as the live path
+  // hands them over: a gathered child's one or two rows -- a tip's own, a cherry's two tips (deferred by this list) --,
+  // the first gathered child's at [0, 1], the second's at [2, 3]; a tip-tip op's two tips at [0, 1]
+  std::vector<unsigned int> rows4;
+  if (gathers_out)
+  {
+    std::vector<int> deferring_op(geom.nclv, -1);
+    for (unsigned int i = 0; i < count; ++i)
+      if (d.defer[i]) deferring_op[ops[i].parent_clv] = (int)i;
+    rows4.assign(4 * (size_t)n, 0u);
+    for (unsigned int i = 0; i < n; ++i)
+    {
+      const unsigned int kid[2] = {kept[i].child1_clv, kept[i].child2_clv};
+      unsigned int at = 0;
+      for (int t = 0; t < 2 && kinds[i] != 0; ++t)
+      {
+        if (!geom.is_tip(kid[t])) continue;
+        unsigned int * r = &rows4[4 * (size_t)i + (kinds[i] == 2 ? 0 : 2 * at)];
+        if (geom.pattern_tip && kid[t] < geom.tips) r[kinds[i] == 2 ? t : 0] = kid[t] + 1;
+        else if (deferring_op[kid[t]] >= 0)
+        {
+          r[0] = ops[deferring_op[kid[t]]].child1_clv + 1;
+          r[1] = ops[deferring_op[kid[t]]].child2_clv + 1;
+        }
+        ++at;
+      }
+    }
+  }
   // the live path's steps: pllhip_fused_plan_walk
   FusedWalk w;
-  const int rc = pllhip_fused_plan_walk(geom, kept.data(), args.data(), kinds.data(), nullptr, nullptr, n, 1, slot_counts, derived ? 2u : 1u,
+  const int rc = pllhip_fused_plan_walk(geom, kept.data(), args.data(), kinds.data(), nullptr, gathers_out ? rows4.data() : nullptr, n, 1, slot_counts, derived ? 2u : 1u,
                                         edge4 ? &e : nullptr, d, pinned, unstored_out != nullptr, folded_out != nullptr, w);
   if (rc) return rc;
   const std::vector<FusedOp> & plan = w.plan.plans[0];
@@ -1196,7 +1226,64 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
     if (slots_out) dry_slots_out(f, slots_out + (size_t)pos * 6);
   }
   if (reloads_out) *reloads_out = w.plan.reloads;
+  if (gathers_out)
+  {
+    // What each walked op gathers, in the order the kernel does (partials_fused.hip: fused_seg_gathers): a reader of
+    // folded products the two factors of the product on its left, then of the one on its right; else the op's own one
+    // or two.  Every factor names ONE row (pllhip_fused_gather_rows / _bits), dealt to batches by the one rule.
+    std::vector<unsigned int> ntips(n, 0u);
+    for (unsigned int pos = 0; pos < n; ++pos)
+    {
+      const FusedOp & f = plan[pos];
+      unsigned int r8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (w.replanned) memcpy(r8, &w.fl.rows8[8 * (size_t)f.list_pos], sizeof(r8));
+      else memcpy(r8, &rows4[4 * (size_t)f.list_pos], 4 * sizeof(unsigned int));
+      unsigned int * g = gathers_out + 12 * (size_t)pos;
+      for (int k = 0; k < 4; ++k)
+      {
+        g[3 * k] = r8[2 * k];
+        g[3 * k + 1] = r8[2 * k + 1];
+        g[3 * k + 2] = 0;
+        ntips[pos] |= pllhip_fused_gather_rows(r8[2 * k] != 0, r8[2 * k + 1] != 0) << (2 * k);
+      }
+    }
+    const unsigned int ts = PLLHIP_FUSED_J * (64 / (2 * (rate_cats ? rate_cats : 4u)));
+    std::vector<unsigned int> ch[4], batch(n, 0u);
+    for (int k = 0; k < 4; ++k) ch[k].assign(n, 0u);
+    unsigned int * const chars_out[4] = {ch[0].data(), ch[1].data(), ch[2].data(), ch[3].data()};
+    const unsigned int nb = pllhip_fused_char_batches8(ntips.data(), n, ts >= 16 ? ts / 16 : 1, chars_out, batch.data());
+    for (unsigned int pos = 0; pos < n; ++pos)
+    {
+      unsigned int * g = gathers_out + 12 * (size_t)pos;
+      for (int k = 0; k < 4; ++k) g[3 * k + 2] = ch[k][pos] | pllhip_fused_gather_bits(g[3 * k] != 0, g[3 * k + 1] != 0);
+      if (batch_out) batch_out[pos] = batch[pos];
+    }
+    if (nbatches_out) *nbatches_out = nb;
+  }
   return 0;
+}
+
+// The rows the kernel's gathers name, without a device or a pool (tests/test_host_pair_rows.py): the final walk of
+// pllhip_fused_plan_dry_folded, and per walked op gathers_out[12] = four gathers x {first tip + 1, second tip + 1 (both
+// set: the pair row of that ordered pair; one: that tip's own row; neither: no gather), the record's chars word:
+// PLLHIP_FUSED_CH_LPOS the row's first lane in its batch, CH_LTIP, CH_SHIFT4, CH_NIBBLE}; batch_out per walked op,
+// *nbatches_out in all.
+extern "C" int pllhip_fused_plan_dry_rows(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                          int pattern_tip, unsigned int rate_cats, const pllhip_op_t * ops, unsigned int count,
+                                          unsigned int nslots, unsigned int * nkept, unsigned int * order_out,
+                                          unsigned char * deferred_out, unsigned char * folded_out,
+                                          unsigned int * gathers_out, unsigned int * batch_out, unsigned int * nbatches_out)
+{
+  if (!(rate_cats == 1 || rate_cats == 2 || rate_cats == 4) || !folded_out || !gathers_out)
+  {
+    pllhip_set_error("pllhip_fused_plan_dry_rows: rate_cats of an instance that defers, folded_out and gathers_out");
+    return -1;
+  }
+  int edge_out[8];
+  std::vector<unsigned char> unstored(count, 0);
+  return plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, nslots, nullptr, nullptr, nullptr, nkept,
+                           order_out, nullptr, nullptr, deferred_out, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, rate_cats, edge_out, unstored.data(), folded_out, gathers_out, batch_out, nbatches_out);
 }
 
 extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,

@@ -47,9 +47,11 @@
 //             pays for is every instruction it issues, vector or scalar; taking instructions OUT (the scaling
 //             test's early exit) bought the rest
 //   scalar    what is wave-uniform, or already a wave mask, stays in scalar registers: the scaling decision is
-//             made on the compares' own 64-bit masks (scale_groups()), the two tip rows' characters are joined
-//             word by word before a lane picks its byte (gather_factor()) -- partials_fused.hpp has the
-//             integer code, which the host runs as well (tests/test_host_scalar_masks.py)
+//             made on the compares' own 64-bit masks (scale_groups()), the words of the ONE row a gathered factor
+//             names are masked and shifted before a lane picks its byte (gather_factor()) -- partials_fused.hpp has
+//             the integer code, which the host runs as well (tests/test_host_scalar_masks.py, test_host_pair_rows.py)
+//   pair rows a cherry's table index (c1 << 4) | c2 depends on its two tip rows only: it is cached, one row of bytes per
+//             ordered tip pair (pair_rows.hip), and a factor over a cherry reads that row instead of joining two
 //
 // The arithmetic per site is that of k_dna_partials, statement for statement (dot4 /
 // masksum4 order, scaling rule of core_partials_avx.c:486-527), so results are
@@ -459,17 +461,18 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     // the loads, until both ends of their life were made whole 16-byte operands of an empty asm statement).
     constexpr bool SECOND = RC <= 4 && MODE != SCALE_RATE; // (partials.hip: what may defer a cherry; checked by the launch)
     auto gather_factor = [&](pll_v2d (&pt)[J], unsigned int ch, unsigned int table_off) {
-      // (the two rows' words are joined in scalar registers -- four characters at a time --, and a lane picks its word
-      // and byte once, for the pair: pllhip_fused_pair_index, partials_fused.hpp; then one shift-add)
-      const unsigned int lmask = (ch & PLLHIP_FUSED_CH_LTIP) ? 0x0f0f0f0fu : 0u, rmask = (ch & PLLHIP_FUSED_CH_RTIP) ? 0x0f0f0f0fu : 0u;
+      // (ONE row per factor: a cherry's cached pair row, whose bytes already are the table's index -- pair_rows.hip --, or
+      // a single tip's row, masked and shifted to its place in scalar registers, four characters at a time; a lane then
+      // picks its word and byte: pllhip_fused_row_index, partials_fused.hpp; then one shift-add)
+      const unsigned int mask = (ch & PLLHIP_FUSED_CH_NIBBLE) ? 0x0f0f0f0fu : 0xffffffffu;
+      const unsigned int shift = (ch / (PLLHIP_FUSED_CH_SHIFT4 / 4u)) & 4u;
       const unsigned long long tab = (unsigned long long)(uintptr_t)bases.pairtab + table_off; // (uniform)
 #pragma unroll
       for (unsigned int j = 0; j < J; ++j)
       {
-        unsigned int lw[SPS / 4], rw[SPS / 4];
-        row_words(PLLHIP_FUSED_CH_LPOS(ch), j, lw);
-        row_words(PLLHIP_FUSED_CH_RPOS(ch), j, rw);
-        const unsigned int pair = pllhip_fused_pair_index<SPS>(lw, rw, lmask, rmask, tip_lane);
+        unsigned int w[SPS / 4];
+        row_words(PLLHIP_FUSED_CH_LPOS(ch), j, w);
+        const unsigned int pair = pllhip_fused_row_index<SPS>(w, mask, shift, tip_lane);
         const unsigned int off = pair * (W * 16u) + gat_lane;
         asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pt[j]) : "v"(off), "s"(tab) : "memory");
       }
@@ -479,9 +482,9 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     constexpr unsigned int TB = 256u * W * 16u; // bytes of a table
     auto gather = [&](pll_v2d (&pt)[J], pll_v2d (&pt2)[J], pll_v2d (&pt3)[J], pll_v2d (&pt4)[J], const Rec & r) {
       const unsigned int ch = rec_chars(r), ch2 = rec_chars2(r);
-      if (ch & (PLLHIP_FUSED_CH_LTIP | PLLHIP_FUSED_CH_RTIP)) gather_factor(pt, ch, rec_gather(r));
-      if (SECOND && (ch2 & (PLLHIP_FUSED_CH_LTIP | PLLHIP_FUSED_CH_RTIP))) gather_factor(pt2, ch2, rec_gather(r) + TB);
-      if (SECOND && (rec_chars3(r) & (PLLHIP_FUSED_CH_LTIP | PLLHIP_FUSED_CH_RTIP)))
+      if (ch & PLLHIP_FUSED_CH_LTIP) gather_factor(pt, ch, rec_gather(r));
+      if (SECOND && (ch2 & PLLHIP_FUSED_CH_LTIP)) gather_factor(pt2, ch2, rec_gather(r) + TB);
+      if (SECOND && (rec_chars3(r) & PLLHIP_FUSED_CH_LTIP))
       {
         gather_factor(pt3, rec_chars3(r), rec_gather(r) + 2u * TB);
         gather_factor(pt4, rec_chars4(r), rec_gather(r) + 3u * TB);
@@ -1127,7 +1130,7 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
   std::vector<unsigned int> ntips(n, 0);
   for (unsigned int pos = 0; pos < n; ++pos)
     for (int k = 0; k < 4; ++k)
-      ntips[pos] |= (out.gx[pos].g[k].row1 ? 1u : 0u) << (2 * k) | (out.gx[pos].g[k].row2 ? 2u : 0u) << (2 * k);
+      ntips[pos] |= pllhip_fused_gather_rows(out.gx[pos].g[k].row1 != nullptr, out.gx[pos].g[k].row2 != nullptr) << (2 * k);
   unsigned int * const chars_out[4] = {out.chars_of[0].data(), out.chars_of[1].data(), out.chars_of[2].data(), out.chars_of[3].data()};
   out.nbatches = pllhip_fused_char_batches8(ntips.data(), n, lpr, chars_out, out.batch_of.data());
   if (batch0 + out.nbatches > 255 || 8 * lpr > 64) return 1;
@@ -1139,8 +1142,8 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
     {
       const FusedOperand & g = out.gx[pos].g[k];
       *ntables += g.type != FUSED_G_NONE;
-      if ((g.row1 && PLLHIP_FUSED_CH_LPOS(out.chars_of[k][pos]) + lpr > 64) || (g.row2 && PLLHIP_FUSED_CH_RPOS(out.chars_of[k][pos]) + lpr > 64))
-        return 1;
+      out.chars_of[k][pos] |= pllhip_fused_gather_bits(g.row1 != nullptr, g.row2 != nullptr);
+      if ((g.row1 || g.row2) && PLLHIP_FUSED_CH_LPOS(out.chars_of[k][pos]) + lpr > 64) return 1;
     }
   }
   return 0;
@@ -1301,11 +1304,10 @@ static void fused_encode_segment(const FusedEncodeIn & in, const std::vector<Fus
     {
       const FusedOperand & g = ga.gx[pos].g[k];
       if (g.type == FUSED_G_NONE) break;
-      const unsigned char * rows[2] = {g.row1, g.row2};
-      const unsigned int lane0[2] = {PLLHIP_FUSED_CH_LPOS(ga.chars_of[k][pos]), PLLHIP_FUSED_CH_RPOS(ga.chars_of[k][pos])};
-      for (int o = 0; o < 2; ++o)
-        for (unsigned int l = 0; rows[o] && l < lpr; ++l)
-          out.rowtab[(size_t)ga.batch_of[pos] * 64 + lane0[o] + l] = (unsigned long long)(uintptr_t)rows[o] + l * 16u;
+      // (the one row the factor names: a cherry's pair row, or the tip's own)
+      const unsigned int lane0 = PLLHIP_FUSED_CH_LPOS(ga.chars_of[k][pos]);
+      for (unsigned int l = 0; g.row && l < lpr; ++l)
+        out.rowtab[(size_t)ga.batch_of[pos] * 64 + lane0 + l] = (unsigned long long)(uintptr_t)g.row + l * 16u;
       double * tab = in.pairtab + out.jobs.size() * per;
       double * copy = ga.gx[pos].copy[k];
       if (g.type == FUSED_G_TIP) out.jobs.push_back(FusedPairJob{g.mat, nullptr, tab, 0ull, nullptr, nullptr, copy, 0ull});
@@ -1435,6 +1437,31 @@ static int fused_device_buffers(pllhip_ctx * c, size_t pairtab_elems, bool edge)
   return 0;
 }
 
+// The ONE row every gathered factor of the admitted list names (FusedOperand::row): a single tip's own row, a cherry's
+// pair row from the context's pool (pair_rows.hip) -- all the list's pairs resolved together, so that none of them is
+// evicted for another, and those the pool does not have built by one launch ahead of the table launch.
+static int fused_name_rows(pllhip_ctx * c, FusedAdmitted & adm)
+{
+  std::vector<std::pair<unsigned int, unsigned int>> need;
+  std::vector<FusedOperand *> who;
+  auto tip_of = [&](const unsigned char * row) { return (unsigned int)((size_t)(row - c->tipchars) / c->tip_stride); };
+  for (FusedSegGathers & sg : adm.segs)
+    for (FusedGatherSets & x : sg.gx)
+      for (FusedOperand & g : x.g)
+      {
+        if (g.type == FUSED_G_NONE) continue;
+        g.row = g.row1 ? g.row1 : g.row2;
+        if (!g.row1 || !g.row2) continue;
+        need.push_back(std::make_pair(tip_of(g.row1), tip_of(g.row2)));
+        who.push_back(&g);
+      }
+  std::vector<const unsigned char *> rows;
+  const int rc = pllhip_pair_rows_resolve(c, need, rows);
+  if (rc) return rc;
+  for (size_t i = 0; i < who.size(); ++i) who[i]->row = rows[i];
+  return 0;
+}
+
 // A planned list: admitted, then -- and only then is anything of the device or the context touched -- its buffers,
 // the encoding, the upload, the launch.  Returns 1 if the list is not one the kernel takes.
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
@@ -1444,6 +1471,7 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   if (fused_admit(c, plans, nslots, edge, adm)) return 1;
   int rc = fused_device_buffers(c, adm.ntab * fused_table_doubles(c->sh.rate_cats), edge != nullptr);
   if (rc) return rc;
+  if ((rc = fused_name_rows(c, adm))) return rc;
   const FusedEncodeIn in = {c->pmatrix, c->d_pairtab, c->fused_zero_row, pllhip_fused_slot_size(c->sh.rate_cats, c->sh.rate_scalers != 0),
                             c->sh.rate_cats, c->sh.rate_scalers != 0};
   FusedEncoded enc;
@@ -1464,6 +1492,8 @@ int pllhip_relaunch_fused(pllhip_ctx * c)
   const unsigned int count = c->fused_last_count, nslots = c->fused_last_nslots, njobs = c->fused_last_jobs; // (count: segment 0's)
   const int mode = c->fused_last_mode;
   static_assert(PLLHIP_TILE_COUNTER_BYTES == 256 * 128, "one counter per thread of k_dna_pair_tables' first workgroup");
+  // (pair rows whose tip rows were written since: rebuilt in place before this launch reads them)
+  if (const int rc = pllhip_pair_rows_refresh(c)) return rc;
   const FusedRec * d_plan = (const FusedRec *)c->d_plan;
   const FusedPairJob * d_jobs = (const FusedPairJob *)(static_cast<const char *>(c->d_plan) + c->fused_last_jobs_offset);
   const FusedBases bases = {c->pmatrix, c->d_pairtab,

@@ -36,6 +36,8 @@ struct FusedOperand
   const double * mat;               // the reader's P-matrix on this edge
   const double * c_lmat, * c_rmat;  // CHERRY_NEW: the cherry's own two matrices (its T is built from them on the spot)
   const double * kept;              // CHERRY_KEPT: its kept table T
+  const unsigned char * row;        // the ONE row the kernel reads the table index from (pllhip_fused_gather_row): the
+                                    // cached pair row of (row1, row2) -- set by the launch, pair_rows.hip --, else the tip row
 };
 // A side of an op may also be the PRODUCT of two gathered factors (prod[side] != 0): a gathered-gathered parent with one
 // reader that is not walked at all but formed by that reader (pllhip_fused_fold).  g[side] and g2[side] are then its
@@ -101,7 +103,7 @@ struct FusedRec
   unsigned int chars3, chars4;           // ... of a third and fourth one (a reader of folded products: up to four factors)
                                          // (the tables of one op follow each other: gather k reads at gather_off + k tables)
   unsigned int req_lmat, req_rmat;       // byte offsets of its P-matrices in the matrix arena
-  unsigned int gather_off;               // byte offset of the pair table of op + 1 (read only if chars has CH_LTIP | CH_RTIP)
+  unsigned int gather_off;               // byte offset of the pair table of op + 1 (read only if chars has CH_LTIP)
   unsigned int flags;                    // PLLHIP_FUSED_* below
   unsigned long long parent;             // CLV the op writes
   unsigned long long pscaler;            // its scale buffer (0: none)
@@ -133,6 +135,32 @@ static_assert(sizeof(FusedRec) == 64, "sixteen words per op");
 #define PLLHIP_FUSED_CH_LTIP (1u << 16)                /* op + 1 has a left / right tip */
 #define PLLHIP_FUSED_CH_RTIP (1u << 17)
 #define PLLHIP_FUSED_CH_LOAD (1u << 18)                /* op + 2's rows are in another batch: fetch batch (x >> 24) */
+// A record's gathers name ONE row each (pair rows: pair_rows.hip): CH_LPOS is its first lane, CH_LTIP says that the
+// factor is gathered at all, and
+#define PLLHIP_FUSED_CH_SHIFT4 (1u << 19)              /* the row is a single tip's and the table's FIRST character: (code & 15) << 4 */
+#define PLLHIP_FUSED_CH_NIBBLE (1u << 20)              /* the row is a single tip's: only the low nibble of a byte counts */
+// The ONE rule for what a gathered factor with a first and / or a second tip row names (the encoder and
+// pllhip_fused_plan_dry_rows): one row of a batch -- bit 0 of its pair of bits for pllhip_fused_char_batches8 --, and
+// the bits of its chars word: none for a cherry's pair row (shift 0, every bit of a byte counts), the nibble mask and
+// shift 4 for a single tip that is the table's first character, the mask and shift 0 for one that is its second.
+inline unsigned int pllhip_fused_gather_rows(bool first, bool second) { return first || second ? 1u : 0u; }
+inline unsigned int pllhip_fused_gather_bits(bool first, bool second)
+{
+  return first && second ? 0u : first ? (PLLHIP_FUSED_CH_SHIFT4 | PLLHIP_FUSED_CH_NIBBLE) : second ? PLLHIP_FUSED_CH_NIBBLE : 0u;
+}
+
+// ---- Pair rows.  Byte n of the pair row of the ordered tip pair (a, b) is the pair-table index of site n: what
+// pllhip_fused_pair_index joins from the two tip rows.  ONE definition for the kernel that builds the rows
+// (pair_rows.hip), the list kernel's tests and the host (tests/test_host_pair_rows.py).
+__host__ __device__ constexpr unsigned char pllhip_pair_row_byte(unsigned char a, unsigned char b)
+{
+  return (unsigned char)(((a & 15u) << 4) | (b & 15u));
+}
+// ... four sites at a time, as the builder forms them (no byte carries into its neighbour)
+__host__ __device__ constexpr unsigned int pllhip_pair_row_word(unsigned int a4, unsigned int b4)
+{
+  return ((a4 & 0x0f0f0f0fu) << 4) | (b4 & 0x0f0f0f0fu);
+}
 
 // ---- What k_dna_fused does on the scalar side: integer code on wave masks and on wave-uniform words, no lane values.
 // Plain C++, so the host runs the very functions (pllhip_fused_group_mask_dry, pllhip_fused_pair_index_dry;
@@ -178,6 +206,25 @@ __host__ __device__ constexpr unsigned int pllhip_fused_entry_shift(unsigned int
   return (t % (64u / GW)) * GW + t / (64u / GW);
 }
 
+// A site's byte of the SPS / 4 words that hold a sub-step's pair-table indices (wave-uniform words; `site` the lane's).
+template <unsigned int SPS>
+__host__ __device__ constexpr unsigned int pllhip_fused_pick_index(const unsigned int (&joined)[SPS / 4], unsigned int site)
+{
+  static_assert(SPS == 4 || SPS == 8 || SPS == 16 || SPS == 32, "sites per sub-step");
+  if constexpr (SPS == 4) return (joined[0] >> (site * 8u)) & 255u;
+  else
+  {
+    // two words at a time, a scalar register pair: eight sites are one 64-bit shift by the lane's own amount
+    unsigned long long two = 0;
+    for (unsigned int m = 0; m < SPS / 8; ++m)
+    {
+      const unsigned long long d = (unsigned long long)joined[2 * m] | ((unsigned long long)joined[2 * m + 1] << 32);
+      two = (SPS == 8 || (site >> 3) == m) ? d : two;
+    }
+    return (unsigned int)(two >> ((site & 7u) * 8u)) & 255u;
+  }
+}
+
 // The pair-table index of one site of a sub-step.  a[], b[]: the SPS / 4 words of the sub-step in the left and the
 // right tip row, four characters each (wave-uniform: v_readlane results); lmask4 / rmask4: 0x0f0f0f0f where the factor
 // has that row, else 0 (an absent tip's character is 0).  The two rows are joined word by word BEFORE anything depends
@@ -191,18 +238,20 @@ __host__ __device__ constexpr unsigned int pllhip_fused_pair_index(const unsigne
   unsigned int joined[SPS / 4] = {};
   for (unsigned int m = 0; m < SPS / 4; ++m)
     joined[m] = ((a[m] & lmask4) << 4) + (b[m] & rmask4); // (no common bit: + is |, and one shift-add)
-  if constexpr (SPS == 4) return (joined[0] >> (site * 8u)) & 255u;
-  else
-  {
-    // two words at a time, a scalar register pair: eight sites are one 64-bit shift by the lane's own amount
-    unsigned long long two = 0;
-    for (unsigned int m = 0; m < SPS / 8; ++m)
-    {
-      const unsigned long long d = (unsigned long long)joined[2 * m] | ((unsigned long long)joined[2 * m + 1] << 32);
-      two = (SPS == 8 || (site >> 3) == m) ? d : two;
-    }
-    return (unsigned int)(two >> ((site & 7u) * 8u)) & 255u;
-  }
+  return pllhip_fused_pick_index<SPS>(joined, site);
+}
+
+// The same index from ONE row, as gather_factor() of k_dna_fused takes it since the pair rows (pair_rows.hip): w[] the
+// SPS / 4 words of the sub-step in the row the record names (wave-uniform), mask4 / shift the record's -- 0xffffffff / 0
+// for a pair row, whose bytes already are what the join above gives; 0x0f0f0f0f / 4 for a single tip that is the
+// table's first character, 0x0f0f0f0f / 0 for one that is its second.  All of it before anything depends on the lane.
+template <unsigned int SPS>
+__host__ __device__ constexpr unsigned int pllhip_fused_row_index(const unsigned int (&w)[SPS / 4], unsigned int mask4,
+                                                                  unsigned int shift, unsigned int site)
+{
+  unsigned int shifted[SPS / 4] = {};
+  for (unsigned int m = 0; m < SPS / 4; ++m) shifted[m] = (w[m] & mask4) << shift;
+  return pllhip_fused_pick_index<SPS>(shifted, site);
 }
 
 // sources and LDS destinations of the operands an op reloads (few ops have any: kept out of the records)

@@ -921,6 +921,20 @@ int pll_amd_set_pair_fold(pll_partition_t * p, int on)
   return PLL_SUCCESS;
 }
 
+int pll_amd_set_pair_row_capacity(pll_partition_t * p, unsigned int rows)
+{
+  int rc = pllhip_set_pair_row_capacity(pll_amd_priv(p)->ctx, rows);
+  if (rc) return pll_amd_fail_hip(rc, "set pair row capacity");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_pair_row_stats(pll_partition_t * p, unsigned long long * stats4)
+{
+  int rc = pllhip_pair_row_stats(pll_amd_priv(p)->ctx, stats4);
+  if (rc) return pll_amd_fail_hip(rc, "pair row stats");
+  return PLL_SUCCESS;
+}
+
 int pll_amd_set_deferral(pll_partition_t * p, int on)
 {
   int rc = pllhip_set_deferral(pll_amd_priv(p)->ctx, on);

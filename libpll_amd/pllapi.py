@@ -286,6 +286,9 @@ class PllLibrary:
             if hasattr(lib, "pll_amd_set_pair_fold"):
                 lib.pll_amd_set_pair_fold.argtypes = [_PP, C.c_int]
                 lib.pll_amd_pair_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
+            if hasattr(lib, "pll_amd_set_pair_row_capacity"):
+                lib.pll_amd_set_pair_row_capacity.argtypes = [_PP, C.c_uint]
+                lib.pll_amd_pair_row_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
             if hasattr(lib, "pll_amd_set_edge_fold"):
                 lib.pll_amd_set_edge_fold.argtypes = [_PP, C.c_int]
                 lib.pll_amd_edge_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
@@ -1093,6 +1096,16 @@ class Partition:
         buf = (C.c_ulonglong * 4)()
         self._check(self.lib.pll_amd_pair_fold_stats(self.ptr, buf), "pll_amd_pair_fold_stats")
         return dict(zip(("folded_now", "ops_folded", "lists_replanned", "materialised"), (int(v) for v in buf)))
+
+    def set_pair_row_capacity(self, rows):
+        """Capacity of the pool of cached pair rows (pll_amd.h); 0: the default, one row per tip."""
+        self._check(self.lib.pll_amd_set_pair_row_capacity(self.ptr, int(rows)), "pll_amd_set_pair_row_capacity")
+
+    def pair_row_stats(self):
+        """{live, built, launches, evictions} of the cached pair rows (pll_amd.h)."""
+        buf = (C.c_ulonglong * 4)()
+        self._check(self.lib.pll_amd_pair_row_stats(self.ptr, buf), "pll_amd_pair_row_stats")
+        return dict(zip(("live", "built", "launches", "evictions"), (int(v) for v in buf)))
 
     def unstored_stats(self):
         """{unstored_now, ops_unstored, launches, materialised} of the 4-state pair products (pll_amd.h)."""
