@@ -20,17 +20,17 @@ CFLAGS   := -std=gnu11 -O2 -fPIC -g -Wall -Wextra -ffp-contract=off -fvisibility
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -ffp-contract=off -fvisibility=hidden \
             -Wall -Iinclude -Ilibpll_amd/csrc/hip $(EXTRA_HIPFLAGS)
 
-.PHONY: lib oracle all clean asan asan-model-score
+.PHONY: lib oracle all clean asan asan-model-score asan-nni-support
 lib: $(OUT)
 all: lib oracle
 
 $(BUILD):
 	mkdir -p $@
 
-$(BUILD)/host_%.o: libpll_amd/csrc/host/%.c include/pll_amd.h include/pllhip.h libpll_amd/csrc/host/internal.h | $(BUILD)
+$(BUILD)/host_%.o: libpll_amd/csrc/host/%.c include/pll_amd.h include/pllhip.h libpll_amd/csrc/host/internal.h libpll_amd/csrc/hip/support_rule.h | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(BUILD)/hip_%.o: libpll_amd/csrc/hip/%.hip include/pllhip.h $(wildcard libpll_amd/csrc/hip/*.hpp) $(wildcard libpll_amd/csrc/hip/*.inc) | $(BUILD)
+$(BUILD)/hip_%.o: libpll_amd/csrc/hip/%.hip include/pllhip.h $(wildcard libpll_amd/csrc/hip/*.hpp) $(wildcard libpll_amd/csrc/hip/*.h) $(wildcard libpll_amd/csrc/hip/*.inc) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_$*) -c $< -o $@
 
 # partials_aa_fused.hip keeps its values in the accumulation registers a0..a109 behind the compiler's
@@ -66,7 +66,7 @@ ASAN_OBJ   := $(patsubst libpll_amd/csrc/host/%.c,$(ASAN_DIR)/host_%.o,$(HOST_SR
 $(ASAN_DIR):
 	mkdir -p $@
 
-$(ASAN_DIR)/host_%.o: libpll_amd/csrc/host/%.c include/pll_amd.h include/pllhip.h libpll_amd/csrc/host/internal.h | $(ASAN_DIR)
+$(ASAN_DIR)/host_%.o: libpll_amd/csrc/host/%.c include/pll_amd.h include/pllhip.h libpll_amd/csrc/host/internal.h libpll_amd/csrc/hip/support_rule.h | $(ASAN_DIR)
 	gcc $(filter-out -O2,$(CFLAGS)) $(ASAN_FLAGS) -c $< -o $@
 
 $(ASAN_DIR)/libpll_amd.so: $(ASAN_OBJ) $(HIP_OBJ)
@@ -87,7 +87,16 @@ $(ASAN_DIR)/model_score_args: tools/model_score_args.c $(ASAN_OBJ) $(HIP_OBJ)
 asan-model-score: $(ASAN_DIR)/model_score_args
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/model_score_args
 
-asan: asan-model-score $(ASAN_DIR)/libpll_amd.so $(ASAN_DIR)/liboracle.so
+# pll_amd_nni_support_counts and the early refusals of pll_amd_nni_support, the same way
+$(ASAN_DIR)/nni_support_args: tools/nni_support_args.c $(ASAN_OBJ) $(HIP_OBJ)
+	gcc $(filter-out -O2,$(CFLAGS)) $(ASAN_FLAGS) -c $< -o $(ASAN_DIR)/nni_support_args.o
+	g++ $(ASAN_FLAGS) -Wl,-rpath,/opt/rocm/lib -o $@ $(ASAN_DIR)/nni_support_args.o $(ASAN_OBJ) $(HIP_OBJ) \
+	    -L/opt/rocm/lib -lamdhip64 -lm -ldl
+
+asan-nni-support: $(ASAN_DIR)/nni_support_args
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/nni_support_args
+
+asan: asan-model-score asan-nni-support $(ASAN_DIR)/libpll_amd.so $(ASAN_DIR)/liboracle.so
 	LD_PRELOAD="$$(gcc -print-file-name=libasan.so) $$(gcc -print-file-name=libubsan.so)" \
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1:allocator_may_return_null=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
 	PLL_AMD_LIB=$(abspath $(ASAN_DIR)/libpll_amd.so) PLL_ORACLE_LIB=$(abspath $(ASAN_DIR)/liboracle.so) \

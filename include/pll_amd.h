@@ -1109,6 +1109,74 @@ PLL_EXPORT int pll_amd_replicate_loglikelihood(pll_partition_t * partition,
                                                double * lnl,           /* out [edge][count], NULL iff set is NULL */
                                                double * persite_lnl);  /* out [edge][sites], unweighted; may be NULL */
 
+/* ---- batched branch support: aLRT, aBayes, SH-aLRT and local bootstrap of many inner edges (nni_support.c,
+ * nni_support.hip) ----
+ * The fast supports of an inner branch are functions of the three NNI arrangements around it, scored per site and
+ * resampled by RELL.  One call takes all inner edges (pll_amd_nni_edge_t, arrangements numbered as for
+ * pll_amd_nni_loglikelihood) and one replicate set, and returns a handful of numbers per edge.
+ * Per-site terms: s[e][k][n] = the per-site output of pll_amd_nni_loglikelihood's defining sequence for candidate
+ * (e, k) under unit pattern weights -- the five P-matrices, two ops into spare nodes u' and v' with fresh scale buffers
+ * where scale_buffers > 0, pll_compute_edge_loglikelihood(u', v', the edge's matrix, persite) --, the central branch
+ * central_lengths[3 e + k] long where central_lengths is given (what pll_amd_nni_optimize returned, say), else the
+ * edge's `length`.  persite_lnl[(3 e + k) * sites + n] = s[e][k][n].
+ * Sums: replicate_lnl[(3 e + k) * count + r] = sum_n (double)w_r[n] * s[e][k][n] with count =
+ * pll_amd_replicates_count(set), and the centres lnl[3 e + k] = c_k = sum_n (double)pattern_weights[n] * s[e][k][n]:
+ * the partition's own weights are one more replicate.  Both in the term formation and the sum order of
+ * pll_amd_replicate_loglikelihood, verbatim: a rounded product, added afterwards, no fused multiply-add; spans of 2048
+ * sites, each added one by one in site order from +0; the spans' sums added one by one in span order from +0.
+ * lnl[3 e + k] therefore agrees with pll_amd_nni_loglikelihood to about 1e-12 relative (1e-11 for 20 states), not bit
+ * for bit: that call sums in tiles of 256 sites.
+ * Statistics, formed on the host from the three centres (the device never evaluates them):
+ *   delta[e]  = c_0 - max(c_1, c_2): half the aLRT statistic; negative where the tree is not NNI-optimal at e;
+ *   abayes[e] = 1 / (1 + exp(c_1 - c_0) + exp(c_2 - c_0)), with the C library's exp.
+ * Counts, per replicate r: cs_k = replicate_lnl[k][r] - c_k; m1 >= m2 the two largest of the three cs_k (a tie gives
+ * m1 - m2 = 0); the replicate adds 1 to sh_count[e] iff delta > (m1 - m2) + epsilon, and 1 to lbp_count[e] iff
+ * replicate_lnl[0][r] > replicate_lnl[1][r] and replicate_lnl[0][r] > replicate_lnl[2][r].  Plain IEEE double
+ * operations without contraction; a NaN anywhere makes a comparison false.  The supports are sh_count / count
+ * (SH-aLRT) and lbp_count / count (local bootstrap): the division is the client's.  pll_amd_nni_support_counts is this
+ * rule on a table -- host only, no device, no partition --, and the device's counts equal it exactly on the table the
+ * same call returns.
+ * With set == NULL only lnl, delta, abayes and persite_lnl are computed (sh_count, lbp_count and replicate_lnl are
+ * then NULL); with a set sh_count is required.  With replicate_lnl == NULL the table never leaves the device.
+ * Bits: an edge's outputs are the same bits whatever else is in the batch, in whatever order, however the call chunks
+ * it, on a repeated call, whatever else is in the set and however the set stores its weights, and whichever optional
+ * outputs are NULL; arrangement k of (A, B, C, D) is the same bits as arrangement 0 of the edge given with its sides
+ * in arrangement k's order; central_lengths equal to the edges' lengths gives the bits of NULL; a replicate with
+ * weight 1 at one site and 0 elsewhere returns that site's persite_lnl bit for bit, an all-zero replicate 0, a
+ * replicate equal to the partition's own pattern weights lnl[3 e + k] bit for bit.
+ * What lives where: P-matrices, the site terms, partial sums, the table and -- for shapes the quartet kernel does
+ * not take -- the candidates' CLVs and scale buffers are scratch of the partition on its device, kept until it is
+ * destroyed; the call changes nothing of the partition or of the set.  Large batches are worked in chunks of whole
+ * edges of at most about PLL_AMD_NNI_SCRATCH_MB (environment, read at call time, default 2048) of scratch, one edge at
+ * least.  The call is synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, outputs untouched): what pll_amd_nni_loglikelihood
+ * checks; the set belongs to this partition; epsilon finite and >= 0; central_lengths finite and >= 0; sh_count given
+ * exactly when set is; lbp_count and replicate_lnl only with a set.
+ * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
+ * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
+ * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: the parametric aLRT p-value (a chi-square
+ * mixture of 2 delta: the client's), generating the weights.  INTEGRATION.md section 4i. */
+PLL_EXPORT int pll_amd_nni_support(pll_partition_t * partition,
+                                   const pll_amd_replicates_t * set,      /* may be NULL */
+                                   const pll_amd_nni_edge_t * edges, unsigned int edge_count,
+                                   const unsigned int * params_indices,
+                                   const double * central_lengths,        /* [edge][3] or NULL: the edge's `length` */
+                                   double epsilon,
+                                   double * lnl,                /* out [edge][3]: the centres c_k            */
+                                   double * delta,              /* out [edge], may be NULL                    */
+                                   double * abayes,             /* out [edge], may be NULL                    */
+                                   unsigned int * sh_count,     /* out [edge]; NULL iff set is NULL           */
+                                   unsigned int * lbp_count,    /* out [edge], may be NULL; NULL if set NULL  */
+                                   double * replicate_lnl,      /* out [edge][3][count], may be NULL          */
+                                   double * persite_lnl);       /* out [edge][3][sites], may be NULL          */
+
+/* The rule of the counts on one edge's table: centre3 = c_0, c_1, c_2; replicate_lnl[k * count + r].  Host only: no
+ * device, no partition.  One of sh_count and lbp_count may be NULL.  PLL_ERROR_PARAM_INVALID: a NULL table,
+ * count == 0, epsilon negative or not finite. */
+PLL_EXPORT int pll_amd_nni_support_counts(const double * centre3, const double * replicate_lnl /* [3][count] */,
+                                          unsigned int count, double epsilon,
+                                          unsigned int * sh_count, unsigned int * lbp_count);
+
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets
  * threads create partitions concurrently -- WITH a process-wide default: a thread that has not set a device uses what

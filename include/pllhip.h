@@ -632,6 +632,24 @@ PLLHIP_EXPORT int pllhip_replicate_loglikelihood(pllhip_ctx_t * ctx, const pllhi
                                                  const unsigned int * h_freqs_indices, size_t scratch_bytes,
                                                  double * h_lnl, double * h_persite);
 
+/* ---- batched branch support (nni_support.hip; host side host/nni_support.c) ----
+ * The three arrangements of pllhip_nni_loglikelihood around every edge, per site and resampled: s[e][k][n] the
+ * unweighted per-site log-likelihood of candidate (e, k) -- the central branch h_central[3 e + k] long where
+ * h_central is given, else the edge's length --, h_table[e][k][r] = sum_n (double)w_r[n] * s[e][k][n] over the set,
+ * h_centres[e][k] the same sum under the context's own pattern weights (one more replicate, 32 bits wide), in the
+ * term formation and sum order of pllhip_replicate_loglikelihood.  h_sh[e] / h_lbp[e]: how many replicates pass the
+ * rule written out at pll_amd_nni_support (include/pll_amd.h), counted on the device over the table.  h_persite
+ * [e][3][sites] = s.  set may be NULL: then h_sh, h_lbp and h_table are NULL too; with a set h_sh is required;
+ * h_lbp, h_table and h_persite may always be NULL.  route and scratch_bytes as for pllhip_nni_loglikelihood (chunks of
+ * whole edges).  Nothing of the context or of the set changes.  Returns -1 for a bad argument (nothing launched,
+ * outputs untouched), -2 if a chunk's scratch cannot be had, -3 for a context this call does not take (asc-bias, site
+ * repeats, sharded, RCCL). */
+PLLHIP_EXPORT int pllhip_nni_support(pllhip_ctx_t * ctx, const pllhip_replicates_t * set,
+                                     const pllhip_nni_edge_t * h_edges, unsigned int edge_count,
+                                     const unsigned int * h_params_indices, const double * h_central, double epsilon,
+                                     int route, size_t scratch_bytes, double * h_centres, unsigned int * h_sh,
+                                     unsigned int * h_lbp, double * h_table, double * h_persite);
+
 /* The planner of k_tree_score on its own -- host logic, no device needed.  The ops the edge (parent_clv, child_clv
  * with their scaler indices) does not depend on are dropped; the rest are ordered depth-first from the edge, the
  * operand that needs more live values first, and a parent takes the slot of one of its operands.  Tips (pattern_tip)

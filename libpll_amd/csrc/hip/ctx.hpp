@@ -23,7 +23,9 @@ struct pllhip_rep_work;
 // branch lengths -- sumtables, Newton states, partial sums; posteriors -- edge descriptors and outputs; NNI and tree
 // scoring -- P-matrices, descriptors, partial sums and, where a route needs them, candidate CLVs, scale buffers, sumtables
 // (model scoring shares tree scoring's: the same pieces, plus a model block per item and the tree's lengths); replicates
-// -- edge descriptors, the chunk's per-site terms and its per-span partial sums
+// -- edge descriptors, the chunk's per-site terms and its per-span partial sums; NNI support -- P-matrices, descriptors,
+// the candidates' per-site terms, per-span partial sums, the replicate table, centres and counts and, on the general
+// route, candidate CLVs and scale buffers
 struct BatchScratch
 {
   void * p = nullptr;
@@ -37,6 +39,7 @@ enum
   BATCH_NNI,
   BATCH_TREE_SCORE,
   BATCH_REPLICATES,
+  BATCH_NNI_SUPPORT,
   BATCH_FAMILIES
 };
 

@@ -96,6 +96,14 @@ void pll_amd_set_error(int code, const char * fmt, ...);
 /* push host-side model state that changed since the last kernel launch */
 int pll_amd_flush_model(pll_partition_t * partition);
 
+/* nni.c: what the calls on NNI edges (pll_amd_nni_loglikelihood, pll_amd_nni_optimize, pll_amd_nni_support) check and
+ * prepare -- edge_count, params indices, every index and length of every edge, the partition kinds they refuse; the
+ * eigen systems and the model flushed.  PLL_SUCCESS: *budget (PLL_AMD_NNI_SCRATCH_MB) and *route (PLLHIP_NNI_QUARTET)
+ * are set.  pll_amd_nni_result: a device-layer return code as pll_errno; PLL_SUCCESS for 0 */
+int pll_amd_nni_prepare(pll_partition_t * p, const pll_amd_nni_edge_t * edges, unsigned int edge_count,
+                        const unsigned int * params_indices, const char * what, size_t * budget, int * route);
+int pll_amd_nni_result(int rc, const char * what);
+
 extern int pll_amd_mirror_mode;
 
 /* tree_score.c: the argument check of one candidate tree, shared with model_score.c.  clv_writer / sc_writer:

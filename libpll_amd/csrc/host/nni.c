@@ -28,9 +28,9 @@ static int bad_scaler(const pll_partition_t * p, int s)
   return s != PLL_SCALE_BUFFER_NONE && (s < 0 || (unsigned int)s >= p->scale_buffers);
 }
 
-/* what both calls check and prepare; PLL_SUCCESS: *budget and *route are set */
-static int nni_prepare(pll_partition_t * p, const pll_amd_nni_edge_t * edges, unsigned int edge_count,
-                       const unsigned int * params_indices, const char * what, size_t * budget, int * route)
+/* what the calls on NNI edges check and prepare (internal.h); PLL_SUCCESS: *budget and *route are set */
+int pll_amd_nni_prepare(pll_partition_t * p, const pll_amd_nni_edge_t * edges, unsigned int edge_count,
+                        const unsigned int * params_indices, const char * what, size_t * budget, int * route)
 {
   pll_amd_partition_t * q = pll_amd_priv(p);
   const unsigned int nodes = p->tips + p->clv_buffers;
@@ -97,7 +97,7 @@ static int nni_prepare(pll_partition_t * p, const pll_amd_nni_edge_t * edges, un
   return PLL_SUCCESS;
 }
 
-static int nni_result(int rc, const char * what)
+int pll_amd_nni_result(int rc, const char * what)
 {
   if (rc == -1)
   {
@@ -128,11 +128,11 @@ int pll_amd_nni_loglikelihood(pll_partition_t * p, const pll_amd_nni_edge_t * ed
     pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "pll_amd_nni_loglikelihood: NULL argument");
     return PLL_FAILURE;
   }
-  if (!nni_prepare(p, edges, edge_count, params_indices, "pll_amd_nni_loglikelihood", &budget, &route))
+  if (!pll_amd_nni_prepare(p, edges, edge_count, params_indices, "pll_amd_nni_loglikelihood", &budget, &route))
     return PLL_FAILURE;
-  return nni_result(pllhip_nni_loglikelihood(pll_amd_priv(p)->ctx, (const pllhip_nni_edge_t *)edges, edge_count,
-                                             params_indices, route, budget, lnl),
-                    "NNI log-likelihood");
+  return pll_amd_nni_result(pllhip_nni_loglikelihood(pll_amd_priv(p)->ctx, (const pllhip_nni_edge_t *)edges,
+                                                     edge_count, params_indices, route, budget, lnl),
+                            "NNI log-likelihood");
 }
 
 int pll_amd_nni_optimize(pll_partition_t * p, const pll_amd_nni_edge_t * edges, unsigned int edge_count,
@@ -161,9 +161,10 @@ int pll_amd_nni_optimize(pll_partition_t * p, const pll_amd_nni_edge_t * edges, 
     pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "pll_amd_nni_optimize: tolerance must be > 0 and finite");
     return PLL_FAILURE;
   }
-  if (!nni_prepare(p, edges, edge_count, params_indices, "pll_amd_nni_optimize", &budget, &route)) return PLL_FAILURE;
-  return nni_result(pllhip_nni_optimize(pll_amd_priv(p)->ctx, (const pllhip_nni_edge_t *)edges, edge_count,
-                                        params_indices, min_length, max_length, tolerance, max_iters, route, budget,
-                                        lengths, lnl, evals, status),
-                    "NNI optimisation");
+  if (!pll_amd_nni_prepare(p, edges, edge_count, params_indices, "pll_amd_nni_optimize", &budget, &route))
+    return PLL_FAILURE;
+  return pll_amd_nni_result(pllhip_nni_optimize(pll_amd_priv(p)->ctx, (const pllhip_nni_edge_t *)edges, edge_count,
+                                                params_indices, min_length, max_length, tolerance, max_iters, route,
+                                                budget, lengths, lnl, evals, status),
+                            "NNI optimisation");
 }

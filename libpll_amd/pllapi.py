@@ -329,6 +329,23 @@ class PllLibrary:
                 lib.pll_amd_replicates_count.argtypes = [C.c_void_p]
                 lib.pll_amd_replicate_loglikelihood.argtypes = [_PP, C.c_void_p, C.c_void_p, C.c_uint, _up,
                                                                 C.c_void_p, C.c_void_p]
+            if hasattr(lib, "pll_amd_nni_support"):
+                lib.pll_amd_nni_support.argtypes = [_PP, C.c_void_p, C.c_void_p, C.c_uint, _up, C.c_void_p,
+                                                    C.c_double] + [C.c_void_p] * 7
+                lib.pll_amd_nni_support_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_double,
+                                                           C.c_void_p, C.c_void_p]
+
+    def nni_support_counts(self, centre3, replicate_lnl, epsilon=0.0):
+        """pll_amd_nni_support_counts (host only): (sh_count, lbp_count) of one edge's table -- centre3 the three
+        centres, replicate_lnl [3][count]."""
+        c = np.ascontiguousarray(centre3, dtype=np.float64).reshape(3)
+        t = np.ascontiguousarray(replicate_lnl, dtype=np.float64).reshape(3, -1)
+        out = np.zeros(2, dtype=np.uint32)
+        ok = self.lib.pll_amd_nni_support_counts(c.ctypes.data, t.ctypes.data if t.size else None, t.shape[1],
+                                                 epsilon, out[:1].ctypes.data, out[1:].ctypes.data)
+        if not ok:
+            raise PllError("pll_amd_nni_support_counts: errno %d: %s" % (self.errno(), self.errmsg()))
+        return int(out[0]), int(out[1])
 
     # -- library-level helpers -------------------------------------------------
     def errno(self):
@@ -903,6 +920,46 @@ class Partition:
                                            status.ctypes.data)
         self._check(ok, "pll_amd_nni_optimize")
         return t, lnl, evals, status
+
+    def nni_support(self, rset, edges, params_indices, central_lengths=None, epsilon=0.0,
+                    want=("delta", "abayes", "lbp_count")):
+        """pll_amd_nni_support: a dict of numpy arrays, first axis the edge -- lnl [edges][3] (the centres) always,
+        sh_count [edges] whenever rset is given, and what `want` names of delta, abayes [edges], lbp_count [edges],
+        replicate_lnl [edges][3][count] (the last two need rset) and persite_lnl [edges][3][sites].  rset: a Replicates
+        of this partition or None; edges as for nni_loglikelihood; central_lengths: [edges][3] (what nni_optimize
+        returned) or None for the edges' own lengths."""
+        if not hasattr(self.lib, "pll_amd_nni_support"):
+            raise PllError("this library has no pll_amd_nni_support")
+        e = nni_edges(edges)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        n, want = len(e), set(want)
+        cl = None
+        if central_lengths is not None:
+            cl = np.ascontiguousarray(central_lengths, dtype=np.float64)
+            assert cl.shape == (n, 3), cl.shape
+        out = {"lnl": np.zeros((n, 3))}
+        if "delta" in want:
+            out["delta"] = np.zeros(n)
+        if "abayes" in want:
+            out["abayes"] = np.zeros(n)
+        if rset is not None:
+            out["sh_count"] = np.zeros(n, dtype=np.uint32)
+            if "lbp_count" in want:
+                out["lbp_count"] = np.zeros(n, dtype=np.uint32)
+            if "replicate_lnl" in want:
+                out["replicate_lnl"] = np.zeros((n, 3, rset.count))
+        if "persite_lnl" in want:
+            out["persite_lnl"] = np.zeros((n, 3, self.s.sites))
+
+        def ptr(name):
+            return out[name].ctypes.data if name in out and out[name].size else None
+        ok = self.lib.pll_amd_nni_support(self.ptr, rset.ptr if rset is not None else None,
+                                          e.ctypes.data if n else None, n, _u(pi),
+                                          cl.ctypes.data if cl is not None and cl.size else None, epsilon,
+                                          ptr("lnl"), ptr("delta"), ptr("abayes"), ptr("sh_count"), ptr("lbp_count"),
+                                          ptr("replicate_lnl"), ptr("persite_lnl"))
+        self._check(ok, "pll_amd_nni_support")
+        return out
 
     def tree_loglikelihood(self, candidates, params_indices):
         """pll_amd_tree_loglikelihood: one log-likelihood per candidate.  candidates: rows of (ops, matrix_indices,
