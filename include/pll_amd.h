@@ -813,7 +813,8 @@ typedef struct pll_amd_branch
  * PLL_AMD_BRANCH_SCRATCH_MB (environment, read at call time, default 2048) of scratch; a branch's result is the same
  * bits whatever else is in the batch, in whatever order, however the call chunks it.  The call is synchronous.
  * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, outputs untouched): CLV, scaler and params indices in
- * range, no tip-tip branch (pattern tips), 0 < min_length <= max_length and both finite, tolerance > 0 and finite,
+ * range, no tip-tip branch (pattern tips: pll_amd_pairwise_distances is the call for two tips; a partition without
+ * PLL_ATTRIB_PATTERN_TIP takes tip-tip branches here), 0 < min_length <= max_length and both finite, tolerance > 0 and finite,
  * max_iters >= 1, count >= 1, start lengths finite, no NULL array but lnl, evals and status.
  * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
  * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
@@ -1176,6 +1177,91 @@ PLL_EXPORT int pll_amd_nni_support(pll_partition_t * partition,
 PLL_EXPORT int pll_amd_nni_support_counts(const double * centre3, const double * replicate_lnl /* [3][count] */,
                                           unsigned int count, double epsilon,
                                           unsigned int * sh_count, unsigned int * lbp_count);
+
+/* ---- batched pairwise ML distances between tips (distance.c, distance.hip) ----
+ * The maximum-likelihood distance of two sequences under the partition's model, for many pairs of tips in one call:
+ * the matrix a distance method (NJ, BIONJ, FastME), distance-based placement or clustering starts from.  The
+ * log-likelihood of a two-sequence tree depends on the data only through a table of counts, so the device counts that
+ * table for every pair (integers, exact in any order) and runs the safeguarded Newton rule of
+ * pll_amd_optimize_branch_lengths on it; no CLV and no sumtable of `sites` entries is ever built.
+ * Codes and masks: codes = 16 for 4 states, where a tip character is its ambiguity mask, else partition->maxstates,
+ * where it is a charmap code; mask(c) = c for 4 states and tipmap[c] otherwise.
+ * Counts, for row tip x and column tip y: N[a * codes + b] = sum_n pattern_weights[n] [char_x(n) = a] [char_y(n) = b],
+ * unsigned int sums.
+ * The distance of (x, y) is defined by the reference's calls on a partition Q built from the table:
+ *   1. Q has two tips, no inner CLV and no PLL_ATTRIB_PATTERN_TIP; the partition's states, rate categories and rate
+ *      matrices with the same exchangeabilities, frequencies, category rates and weights and +I proportions; one site
+ *      per bin with N > 0, in bin order, with pattern weight N; tip 0 the 0/1 vectors of mask(a) and tip 1 those of
+ *      mask(b), both set with pll_set_tip_clv; pll_update_invariant_sites where a +I proportion is > 0 -- a bin is then
+ *      invariant exactly when mask(a) & mask(b) has a single bit: the pairwise +I model, not the partition's invariant[];
+ *   2. D(t) = (f, g) of pll_compute_likelihood_derivatives(Q, NONE, NONE, t, params_indices, st, &f, &g) after
+ *      pll_update_sumtable(Q, 0, 1, NONE, NONE, params_indices, st);
+ *   3. distances[x][y], evals and status (PLL_AMD_BRANCH_*) are the results of the rule written out at
+ *      pll_amd_optimize_branch_lengths applied to this D, started at start_lengths[x][y] or, where start_lengths is NULL,
+ *      at sum N[a][b] [mask(a) & mask(b) == 0] / sum N[a][b] -- exact integer sums divided in double, min_length for a
+ *      table of zeros --, clamped by the rule's first line;
+ *   4. lnl = pll_compute_edge_loglikelihood(Q, 0, NONE, 1, NONE, a matrix at that length, params_indices).
+ * The device forms lnl in the eigen form -- sum of N log(L), L the site likelihood the derivative pass divides by --,
+ * not from P-matrix entries.  Closeness is that of pll_amd_optimize_branch_lengths: the device's exp and the order of
+ * the bin sums differ from the single calls', so a distance lies within `tolerance` of the host loop's, not on it; lnl
+ * agrees to about 1e-12 relative (1e-11 for 20 states).
+ * Pairing: the row tip is the parent, the column tip the child.  With col_tips == NULL (col_count 0) the pairs are those
+ * among row_tips and the outputs are [row_count][row_count]: only x < y is computed and then copied to [y][x] --
+ * distances, lnl, evals and status as they are, counts with a and b swapped, so that the copy is [y][x]'s own table;
+ * on the diagonal distance is 0, lnl NaN, evals 0, status CONVERGED and counts the diagonal's own table.  A tip may
+ * appear twice in a list.
+ * Bits: a pair's values are the same bits whatever else is in the batch, whatever the order of the lists, whether the
+ * pair is reached in all-pairs or in rows x columns mode with the same tip as the row, however the call is chunked,
+ * whichever outputs are NULL, and on a repeated call.
+ * What lives where: the count tables, the two factors of the bin table, Newton states and results are scratch of the
+ * partition on its device, kept until it is destroyed; the call changes nothing of the partition.  It is worked in
+ * chunks of whole pairs of at most about PLL_AMD_DISTANCE_SCRATCH_MB (environment, read at call time, default 2048)
+ * of scratch, 64 pairs at least.  The call is synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, outputs untouched): tip indices below `tips`; every
+ * listed tip's sequence has been set (pll_set_tip_states); params indices in range; 0 < min_length <= max_length and
+ * both finite, tolerance > 0 and finite, max_iters >= 1; start lengths finite; row_count >= 1; col_count >= 1 exactly
+ * where col_tips is given; the pattern weights sum to less than 2^32 (counts are 32 bits); no NULL array but col_tips,
+ * start_lengths, lnl, evals, status and counts.
+ * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions without PLL_ATTRIB_PATTERN_TIP -- their tip CLVs are arbitrary
+ * doubles, and pll_amd_optimize_branch_lengths takes tip-tip branches there --; codes > 64; partitions with
+ * PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction, sharded over devices (pll_amd_set_devices) or joined to
+ * an RCCL communicator (pll_amd_comm_init).  PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.
+ * Not offered: building a tree from the matrix, variances, per-pair models, device-resident outputs.
+ * INTEGRATION.md section 4j. */
+PLL_EXPORT int pll_amd_pairwise_distances(pll_partition_t * partition,
+                                          const unsigned int * row_tips, unsigned int row_count,
+                                          const unsigned int * col_tips, unsigned int col_count, /* NULL, 0: all pairs among row_tips */
+                                          const unsigned int * params_indices,
+                                          double min_length, double max_length,
+                                          double tolerance, unsigned int max_iters,
+                                          const double * start_lengths, /* [row][col] or NULL */
+                                          double * distances,           /* out [row][col] */
+                                          double * lnl,                 /* out [row][col] or NULL */
+                                          unsigned int * evals,         /* out [row][col] or NULL */
+                                          int * status,                 /* out [row][col] or NULL, PLL_AMD_BRANCH_* */
+                                          unsigned int * counts);       /* out [row][col][codes*codes] or NULL */
+
+/* The same rule on one count table in plain C.  Host only: no device, no partition -- for a client that keeps count
+ * tables and wants distances under another model.  code_masks[c] = mask(c); category i's arrays are eigenvecs[i],
+ * inv_eigenvecs[i] (states x states, row-major), eigenvals[i] and freqs[i], its rate, weight and +I proportion
+ * rates[i], rate_weights[i] and prop_invar[i].  start_length NaN: the default start above.  The bins are summed in
+ * index order with the C library's exp and log.  lnl, evals and status may be NULL.  PLL_ERROR_PARAM_INVALID: a NULL
+ * array, states outside 1..32, rate_cats or codes 0, the rule's bounds, an infinite start length, a +I proportion
+ * outside [0, 1). */
+PLL_EXPORT int pll_amd_distance_from_counts(unsigned int states, unsigned int rate_cats, unsigned int codes,
+                                            const unsigned int * code_masks /* [codes] */,
+                                            const unsigned int * counts /* [codes*codes] */,
+                                            double * const * eigenvecs, double * const * inv_eigenvecs,
+                                            double * const * eigenvals, double * const * freqs, /* each [rate_cats] */
+                                            const double * rates, const double * rate_weights,
+                                            const double * prop_invar, /* [rate_cats] */
+                                            double min_length, double max_length,
+                                            double tolerance, unsigned int max_iters,
+                                            double start_length /* NaN: the default start */,
+                                            double * distance, double * lnl, unsigned int * evals, int * status);
+/* Measurement (tools/distance_bench.py): while pll_amd_profile_enable is on, the milliseconds the counting kernel
+ * (ms2[0]) and the Newton kernel (ms2[1]) of the partition's last pll_amd_pairwise_distances took, over all chunks. */
+PLL_EXPORT int pll_amd_distance_kernel_ms(pll_partition_t * partition, float * ms2);
 
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets

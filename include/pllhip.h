@@ -650,6 +650,30 @@ PLLHIP_EXPORT int pllhip_nni_support(pllhip_ctx_t * ctx, const pllhip_replicates
                                      int route, size_t scratch_bytes, double * h_centres, unsigned int * h_sh,
                                      unsigned int * h_lbp, double * h_table, double * h_persite);
 
+/* ---- batched pairwise distances between tips (distance.hip; host side host/distance.c) ----
+ * Per pair (row tip x, column tip y) the count table N[a * codes + b] of the columns where x shows character code a and
+ * y code b, weighted by the pattern weights (codes = 16 for 4 states, else the tipmap's code count), and on that table
+ * the distance written out at pll_amd_pairwise_distances (include/pll_amd.h): the rule of
+ * pllhip_optimize_branch_lengths on the two-tip tree, the iteration on the device.  h_col_tips == NULL (col_count 0):
+ * the pairs x < y among h_row_tips; only those entries of the [row_count][row_count] outputs are written (the diagonal
+ * and the mirrored half are the host's).  Otherwise every entry of the [row_count][col_count] outputs.  h_start (same
+ * shape) may be NULL: the share of columns whose two masks exclude each other.  h_lnl, h_evals, h_status and h_counts
+ * ([..][codes * codes]) may be NULL.  Whether a tip's characters were ever uploaded is the caller's to know.  Nothing
+ * of the context changes; scratch (kept by the context) is at most about scratch_bytes per chunk of whole pairs, 64
+ * pairs' worth at least.  Returns -1 for a bad argument (nothing launched, outputs untouched), -2 if a chunk's scratch
+ * cannot be had, -3 for a context this call does not take (tips kept as CLVs, more than 64 codes, asc-bias, site
+ * repeats, sharded, RCCL).
+ * pllhip_distance_kernel_ms: while profiling is on (pllhip_profile_enable), what the counting kernel (ms2[0]) and the
+ * Newton kernel (ms2[1]) of the last call took, over all its chunks. */
+PLLHIP_EXPORT int pllhip_pairwise_distances(pllhip_ctx_t * ctx, const unsigned int * h_row_tips,
+                                            unsigned int row_count, const unsigned int * h_col_tips,
+                                            unsigned int col_count, const unsigned int * h_params_indices,
+                                            double min_length, double max_length, double tolerance,
+                                            unsigned int max_iters, size_t scratch_bytes, const double * h_start,
+                                            double * h_distances, double * h_lnl, unsigned int * h_evals,
+                                            int * h_status, unsigned int * h_counts);
+PLLHIP_EXPORT int pllhip_distance_kernel_ms(pllhip_ctx_t * ctx, float * ms2);
+
 /* The planner of k_tree_score on its own -- host logic, no device needed.  The ops the edge (parent_clv, child_clv
  * with their scaler indices) does not depend on are dropped; the rest are ordered depth-first from the edge, the
  * operand that needs more live values first, and a parent takes the slot of one of its operands.  Tips (pattern_tip)

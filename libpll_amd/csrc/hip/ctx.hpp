@@ -25,7 +25,8 @@ struct pllhip_rep_work;
 // (model scoring shares tree scoring's: the same pieces, plus a model block per item and the tree's lengths); replicates
 // -- edge descriptors, the chunk's per-site terms and its per-span partial sums; NNI support -- P-matrices, descriptors,
 // the candidates' per-site terms, per-span partial sums, the replicate table, centres and counts and, on the general
-// route, candidate CLVs and scale buffers
+// route, candidate CLVs and scale buffers; distances -- the two factors of the bin table, the chunk's count tables, Newton
+// states, start lengths and results, its jobs and the pairs' tips
 struct BatchScratch
 {
   void * p = nullptr;
@@ -40,6 +41,7 @@ enum
   BATCH_TREE_SCORE,
   BATCH_REPLICATES,
   BATCH_NNI_SUPPORT,
+  BATCH_DISTANCE,
   BATCH_FAMILIES
 };
 
@@ -334,6 +336,7 @@ struct pllhip_ctx
   // the batched calls (batched.hpp): one scratch per call family, grown to what one chunk of a call needs and kept
   // until the context goes.  Apart on purpose: two families zero theirs only when it grows
   BatchScratch batch_scratch[BATCH_FAMILIES];
+  float distance_ms[2] = {0.f, 0.f}; // distance.hip: the counting and Newton kernels of the last call, timed while profiling is on
   // the replicate sets that are alive (pllhip_replicates_create / _destroy); the context's end is theirs
   std::vector<pllhip_replicates *> replicate_sets;
 

@@ -61,6 +61,9 @@ typedef struct pll_amd_partition
   /* which mirrors are pinned memory of the device layer's (pllhip_host_alloc: the batched copy writes them over the
      bus) rather than the C library's: [tips + clv_buffers] and [scale_buffers] flags, NULL until the first one */
   unsigned char * clv_pinned, * scaler_pinned;
+  /* PLL_ATTRIB_PATTERN_TIP: [tips] flags, 1 once pll_set_tip_states has stored the tip's characters (a row that was
+     never set holds code 0, which is a character of its own wherever states != 4); NULL until the first one */
+  unsigned char * tip_set;
 } pll_amd_partition_t;
 #define PLL_AMD_MIRRORS(p) (pll_amd_mirror_mode || pll_amd_priv(p)->auto_mirror)
 

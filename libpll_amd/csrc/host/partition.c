@@ -231,6 +231,7 @@ void pll_partition_destroy(pll_partition_t * p)
       if (q->scaler_pinned[i]) { pllhip_host_free(p->scale_buffer[i]); p->scale_buffer[i] = NULL; }
     free(q->clv_pinned);
     free(q->scaler_pinned);
+    free(q->tip_set);
   }
   free_ptr_array((void **)p->clv, nodes);
   if (p->pmatrix)
@@ -586,6 +587,8 @@ int pll_set_tip_states(pll_partition_t * p, unsigned int tip_index, const unsign
       for (i = 0; i < p->states; ++i) codes[p->sites + i] = (unsigned char)(1u << i);
     if ((rc = pllhip_put_tipchars(q->ctx, tip_index, codes)))
       return pll_amd_fail_hip(rc, "upload of tip characters");
+    if (!q->tip_set) q->tip_set = (unsigned char *)calloc(p->tips, 1);
+    if (q->tip_set) q->tip_set[tip_index] = 1;
     pll_amd_repeats_tip_changed(q, tip_index);
     return PLL_SUCCESS;
   }

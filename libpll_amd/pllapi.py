@@ -334,6 +334,47 @@ class PllLibrary:
                                                     C.c_double] + [C.c_void_p] * 7
                 lib.pll_amd_nni_support_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_double,
                                                            C.c_void_p, C.c_void_p]
+            if hasattr(lib, "pll_amd_pairwise_distances"):
+                lib.pll_amd_pairwise_distances.argtypes = [_PP, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p,
+                                                           C.c_double, C.c_double, C.c_double, C.c_uint] + \
+                                                          [C.c_void_p] * 6
+                lib.pll_amd_distance_from_counts.argtypes = [C.c_uint, C.c_uint, C.c_uint] + [C.c_void_p] * 9 + \
+                                                            [C.c_double, C.c_double, C.c_double, C.c_uint,
+                                                             C.c_double] + [C.c_void_p] * 4
+                lib.pll_amd_distance_kernel_ms.argtypes = [_PP, C.POINTER(C.c_float)]
+
+    def distance_from_counts(self, states, code_masks, counts, eigenvecs, inv_eigenvecs, eigenvals, freqs, rates,
+                             rate_weights, prop_invar, min_length=1e-6, max_length=100.0, tolerance=1e-7,
+                             max_iters=64, start_length=float("nan")):
+        """pll_amd_distance_from_counts (host only): (distance, lnl, evals, status) of one count table.  code_masks
+        [codes]; counts [codes * codes]; eigenvecs, inv_eigenvecs, eigenvals, freqs: one array per rate category;
+        rates, rate_weights, prop_invar [rate_cats]."""
+        if not hasattr(self.lib, "pll_amd_distance_from_counts"):
+            raise PllError("this library has no pll_amd_distance_from_counts")
+        masks = np.ascontiguousarray(code_masks, dtype=np.uint32)
+        n = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        assert n.size == masks.size * masks.size, (n.size, masks.size)
+        rates = np.ascontiguousarray(rates, dtype=np.float64)
+        w = np.ascontiguousarray(rate_weights, dtype=np.float64)
+        pinv = np.ascontiguousarray(prop_invar, dtype=np.float64)
+        R = len(rates)
+        assert len(w) == R and len(pinv) == R
+        keep, rows = [], []
+        for arrs in (eigenvecs, inv_eigenvecs, eigenvals, freqs):
+            assert len(arrs) == R
+            a = [np.ascontiguousarray(x, dtype=np.float64) for x in arrs]
+            keep.append(a)
+            rows.append((_dp * R)(*[x.ctypes.data_as(_dp) for x in a]))
+        d, lnl = C.c_double(), C.c_double()
+        ev, st = C.c_uint(), C.c_int()
+        ok = self.lib.pll_amd_distance_from_counts(
+            states, R, masks.size, masks.ctypes.data, n.ctypes.data, C.addressof(rows[0]), C.addressof(rows[1]),
+            C.addressof(rows[2]), C.addressof(rows[3]), rates.ctypes.data, w.ctypes.data, pinv.ctypes.data,
+            min_length, max_length, tolerance, max_iters, start_length, C.addressof(d), C.addressof(lnl),
+            C.addressof(ev), C.addressof(st))
+        if not ok:
+            raise PllError("pll_amd_distance_from_counts: errno %d: %s" % (self.errno(), self.errmsg()))
+        return d.value, lnl.value, ev.value, st.value
 
     def nni_support_counts(self, centre3, replicate_lnl, epsilon=0.0):
         """pll_amd_nni_support_counts (host only): (sh_count, lbp_count) of one edge's table -- centre3 the three
@@ -960,6 +1001,55 @@ class Partition:
                                           ptr("replicate_lnl"), ptr("persite_lnl"))
         self._check(ok, "pll_amd_nni_support")
         return out
+
+    @property
+    def distance_codes(self):
+        """character codes of pll_amd_pairwise_distances' count tables: 16 for 4 states, else maxstates"""
+        return 16 if self.s.states == 4 else int(self.s.maxstates)
+
+    def pairwise_distances(self, row_tips, col_tips=None, params_indices=None, min_length=1e-6, max_length=100.0,
+                           tolerance=1e-7, max_iters=64, start_lengths=None,
+                           want=("lnl", "evals", "status", "counts")):
+        """pll_amd_pairwise_distances: a dict of numpy arrays [rows][cols] -- distances always, and what `want`
+        names of lnl, evals, status and counts ([rows][cols][codes * codes]).  col_tips None: all pairs among
+        row_tips ([rows][rows]).  start_lengths: [rows][cols] or None for the default start."""
+        if not hasattr(self.lib, "pll_amd_pairwise_distances"):
+            raise PllError("this library has no pll_amd_pairwise_distances")
+        rows = np.ascontiguousarray(row_tips, dtype=np.uint32).reshape(-1)
+        cols = None if col_tips is None else np.ascontiguousarray(col_tips, dtype=np.uint32).reshape(-1)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        shape = (len(rows), len(rows) if cols is None else len(cols))
+        start = None
+        if start_lengths is not None:
+            start = np.ascontiguousarray(start_lengths, dtype=np.float64)
+            assert start.shape == shape, start.shape
+        want = set(want)
+        out = {"distances": np.zeros(shape)}
+        if "lnl" in want:
+            out["lnl"] = np.zeros(shape)
+        if "evals" in want:
+            out["evals"] = np.zeros(shape, dtype=np.uint32)
+        if "status" in want:
+            out["status"] = np.zeros(shape, dtype=np.int32)
+        if "counts" in want:
+            out["counts"] = np.zeros(shape + (self.distance_codes ** 2,), dtype=np.uint32)
+
+        def ptr(name):
+            return out[name].ctypes.data if name in out and out[name].size else None
+        ok = self.lib.pll_amd_pairwise_distances(
+            self.ptr, rows.ctypes.data if len(rows) else None, len(rows),
+            cols.ctypes.data if cols is not None and len(cols) else None, 0 if cols is None else len(cols),
+            pi.ctypes.data, min_length, max_length, tolerance, max_iters,
+            start.ctypes.data if start is not None and start.size else None, ptr("distances"), ptr("lnl"),
+            ptr("evals"), ptr("status"), ptr("counts"))
+        self._check(ok, "pll_amd_pairwise_distances")
+        return out
+
+    def distance_kernel_ms(self):
+        """(counting ms, Newton ms) of the last pairwise_distances call made with profile_enable on"""
+        ms = (C.c_float * 2)()
+        self._check(self.lib.pll_amd_distance_kernel_ms(self.ptr, ms), "pll_amd_distance_kernel_ms")
+        return float(ms[0]), float(ms[1])
 
     def tree_loglikelihood(self, candidates, params_indices):
         """pll_amd_tree_loglikelihood: one log-likelihood per candidate.  candidates: rows of (ops, matrix_indices,
