@@ -1226,7 +1226,8 @@ PLL_EXPORT int pll_amd_nni_support_counts(const double * centre3, const double *
  * doubles, and pll_amd_optimize_branch_lengths takes tip-tip branches there --; codes > 64; partitions with
  * PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction, sharded over devices (pll_amd_set_devices) or joined to
  * an RCCL communicator (pll_amd_comm_init).  PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.
- * Not offered: building a tree from the matrix, variances, per-pair models, device-resident outputs.
+ * Not offered: variances, per-pair models, device-resident outputs (pll_amd_distance_tree builds the tree from the
+ * matrix without the matrix leaving the device).
  * INTEGRATION.md section 4j. */
 PLL_EXPORT int pll_amd_pairwise_distances(pll_partition_t * partition,
                                           const unsigned int * row_tips, unsigned int row_count,
@@ -1262,6 +1263,96 @@ PLL_EXPORT int pll_amd_distance_from_counts(unsigned int states, unsigned int ra
 /* Measurement (tools/distance_bench.py): while pll_amd_profile_enable is on, the milliseconds the counting kernel
  * (ms2[0]) and the Newton kernel (ms2[1]) of the partition's last pll_amd_pairwise_distances took, over all chunks. */
 PLL_EXPORT int pll_amd_distance_kernel_ms(pll_partition_t * partition, float * ms2);
+
+/* ---- neighbour-joining and BIONJ start trees from a distance matrix (joining.c, joining.hip) ----
+ * The other standard entry into a tree search besides stepwise addition: a tree joined from the matrix of
+ * pll_amd_pairwise_distances.  pll_amd_joins_from_matrix is the rule below in plain C, host only; pll_amd_matrix_joins
+ * runs it on the partition's device and returns the same bits in every field; pll_amd_tree_from_joins makes the
+ * pll_utree_t of a join list; pll_amd_distance_tree goes from the alignment to the tree in one call.
+ * Numbering: the n rows of the matrix are nodes 0 .. n - 1, the tips; step s = 0 .. n - 4 creates node n + s.
+ * The rule.  All arithmetic is IEEE double, every operation rounded once, nothing fused, evaluated exactly as
+ * parenthesised here.  R_x = ((0 + d[x][0]) + d[x][1]) + ... + d[x][n-1], the sequential sum in ascending order, and
+ * RV_x the same of V (BIONJ; V = variances, or d where variances is NULL; NJ ignores variances).  With r active nodes,
+ * m = (double)(r - 2):
+ *   Q(x, y) = (m * d_xy - R_lo) - R_hi, lo the lower and hi the higher of the two node numbers.  The pair with the
+ *     smallest Q is joined; equal Q: the pair with the smaller lower number, then the smaller higher number.  (At r = 4
+ *     the two complementary pairs have mathematically equal Q every time.)  i is the pair's lower number, j the higher.
+ *   b_i = 0.5 * d_ij + (R_i - R_j) / (2.0 * m);  b_j = d_ij - b_i    -- joins[s] = {i, j, b_i, b_j}
+ *   L = 0.5 for NJ, and for BIONJ where V_ij == 0; otherwise L = 0.5 + (RV_j - RV_i) / ((2.0 * m) * V_ij), then 0 where
+ *     L < 0 and 1 where L > 1;  M = 1.0 - L
+ *   for every other active k:  d_uk = L * (d_ik - b_i) + M * (d_jk - b_j)
+ *                              V_uk = (L * V_ik + M * V_jk) - (L * M) * V_ij
+ *                              R_k  = ((R_k - d_ik) - d_jk) + d_uk        RV_k = ((RV_k - V_ik) - V_jk) + V_uk
+ *   R_u  = L * ((R_i - d_ij) - m * b_i) + M * ((R_j - d_ij) - m * b_j)
+ *   RV_u = (L * (RV_i - V_ij) + M * (RV_j - V_ij)) - m * ((L * M) * V_ij)
+ * Only the initial row sums are sums; every later one is the closed form above.  The last three nodes x < y < z get
+ *   0.5 * ((d_xy + d_xz) - d_yz),  0.5 * ((d_xy + d_yz) - d_xz),  0.5 * ((d_xz + d_yz) - d_xy)
+ * and go to `last` in ascending node number.  n = 3: no join at all.  Negative lengths are returned as they come;
+ * pll_amd_tree_from_joins copies them into the tree, and clamping them before pll_update_prob_matrices is the client's
+ * decision.  (Should every Q of a step be NaN -- an overflow of finite entries -- the pair stored first is joined, on
+ * the host and on the device alike.)  At r = 4 it is rounding that makes one of the two complementary pairs' Q the
+ * smaller: the topology and NJ's lengths are the same either way, BIONJ's lengths around the last inner edge are not
+ * (lambda differs); the host function and the device call take the same pair.
+ * Checked before anything runs (PLL_ERROR_PARAM_INVALID, outputs untouched): n >= 3; every entry finite; d[x][y] and
+ * d[y][x] the same bits and the diagonal 0 (the same for V where BIONJ reads it); a known method; no NULL array but
+ * variances (and joins where n = 3). */
+#define PLL_AMD_JOIN_NJ    0
+#define PLL_AMD_JOIN_BIONJ 1
+typedef struct pll_amd_join { unsigned int a, b; double length_a, length_b; } pll_amd_join_t;
+typedef struct pll_amd_join_last { unsigned int node[3]; double length[3]; } pll_amd_join_last_t;
+
+/* host only: no device, no partition */
+PLL_EXPORT int pll_amd_joins_from_matrix(const double * distances /* [n][n] */,
+                                         const double * variances /* [n][n] or NULL */,
+                                         unsigned int n, int method,
+                                         pll_amd_join_t * joins /* out [n - 3] */,
+                                         pll_amd_join_last_t * last /* out */);
+
+/* The same on the device the partition lives on, with the same bits.  The partition is the device context only: its
+ * model, tips and CLVs are neither read nor changed, and any partition will do but one sharded over devices or joined
+ * to an RCCL communicator (PLL_ERROR_HIP_UNSUPPORTED).  The n - 3 steps are enqueued without a host synchronisation
+ * between them and the joins copied back once; the call is synchronous.  The matrices (n^2 doubles; two of them for
+ * BIONJ) are scratch of the partition on its device, kept until it is destroyed; there is no chunking, the matrix is
+ * the working set: PLL_ERROR_MEM_ALLOC where it does not fit. */
+PLL_EXPORT int pll_amd_matrix_joins(pll_partition_t * partition,
+                                    const double * distances, const double * variances,
+                                    unsigned int n, int method,
+                                    pll_amd_join_t * joins, pll_amd_join_last_t * last);
+
+/* Host only: the tree of a join list.  Tip k is a node with clv_index k, scaler_index PLL_SCALE_BUFFER_NONE and a copy
+ * of labels[k] (labels NULL: no labels); node n + s, s = 0 .. n - 4, is a ring with clv_index n + s and scaler_index s,
+ * whose second and third node lead to joins[s].a and joins[s].b; the ring that joins the last three has clv_index
+ * 2n - 3 and scaler_index n - 3.  The edge above node v (v = 0 .. 2n - 4) has pmatrix_index v and the join's length at
+ * both ends.  node_index is left as pll_fastparsimony_stepwise leaves it (0).  The tree is wrapped with
+ * pll_utree_wraptree and freed with pll_utree_destroy; pll_utree_traverse, pll_utree_create_operations and
+ * pll_utree_export_newick take it as they take any tree.  PLL_ERROR_PARAM_INVALID: a NULL array, n < 3, a join that
+ * names a node that does not exist yet or was joined already. */
+PLL_EXPORT pll_utree_t * pll_amd_tree_from_joins(const pll_amd_join_t * joins, const pll_amd_join_last_t * last,
+                                                 unsigned int n, char * const * labels /* [n] or NULL */);
+
+/* Alignment to tree in one call: the distances of all pairs among `tips` as pll_amd_pairwise_distances computes them
+ * (default starts), left on the device as the mirrored matrix with a zero diagonal, joined there, and the tree of the
+ * joins.  Node k of the rule is tips[k]: tip k of the tree has clv_index tips[k] and label labels[k]; the inner nodes
+ * are count + s as above -- a client that lists fewer than the partition's tips renumbers them before it uses them as
+ * CLV indices.  The result is that of pll_amd_pairwise_distances(tips, count, NULL, 0, ...) followed by
+ * pll_amd_matrix_joins (variances NULL) and pll_amd_tree_from_joins, bit for bit.  distances ([count][count]), status
+ * ([count][count], PLL_AMD_BRANCH_*), joins ([count - 3]) and last may each be NULL; the matrix is copied to the host
+ * only where distances asks for it.  Returns NULL and sets pll_errno for: whatever pll_amd_pairwise_distances rejects or
+ * refuses, count < 3, a tip listed twice, an unknown method (PLL_ERROR_PARAM_INVALID / PLL_ERROR_HIP_UNSUPPORTED,
+ * outputs untouched); PLL_ERROR_MEM_ALLOC where the matrix does not fit.  INTEGRATION.md section 4k. */
+PLL_EXPORT pll_utree_t * pll_amd_distance_tree(pll_partition_t * partition,
+                                               const unsigned int * tips, unsigned int count,
+                                               const unsigned int * params_indices,
+                                               double min_length, double max_length,
+                                               double tolerance, unsigned int max_iters,
+                                               int method, char * const * labels /* [count] or NULL */,
+                                               double * distances /* out [count][count] or NULL */,
+                                               int * status /* out [count][count] or NULL */,
+                                               pll_amd_join_t * joins /* out [count - 3] or NULL */,
+                                               pll_amd_join_last_t * last /* out or NULL */);
+/* Measurement (tools/joining_bench.py): while pll_amd_profile_enable is on, the milliseconds the joining kernels of the
+ * partition's last pll_amd_matrix_joins or pll_amd_distance_tree took, first row sum to last join. */
+PLL_EXPORT int pll_amd_joining_kernel_ms(pll_partition_t * partition, float * ms);
 
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets

@@ -674,6 +674,32 @@ PLLHIP_EXPORT int pllhip_pairwise_distances(pllhip_ctx_t * ctx, const unsigned i
                                             int * h_status, unsigned int * h_counts);
 PLLHIP_EXPORT int pllhip_distance_kernel_ms(pllhip_ctx_t * ctx, float * ms2);
 
+/* ---- neighbour joining and BIONJ on a distance matrix (joining.hip; host side host/joining.c) ----
+ * The joining rule written out at pll_amd_joins_from_matrix (include/pll_amd.h) on the context's device: the n - 3 steps
+ * are enqueued on the context's stream without a host synchronisation between them -- per step a scan kernel (one
+ * candidate per workgroup), a kernel that reduces the candidates under (Q, lower number, higher number) and records the
+ * join, and an update kernel for the new node's row and column and the row sums, over the compact active set -- and the
+ * joins are copied back once.  method: 0 NJ, 1 BIONJ (h_variances NULL: V = d); the structs are pll_amd_join_t and
+ * pll_amd_join_last_t.  The matrices were checked by the caller (finite, symmetric in bits, zero diagonal, n >= 3).
+ * The context is the device context only: nothing of it is read or changed but the scratch.  Returns -2 if the
+ * matrices do not fit in device memory, -3 for sharded and RCCL-joined contexts.
+ * pllhip_distance_joins: all pairs among h_tips by the kernels of distance.hip, the matrix left on the device
+ * (distance.hpp) and joined there; h_distances ([count][count], mirrored, diagonal 0) and h_status (likewise, diagonal
+ * PLLHIP_BRANCH_CONVERGED) may be NULL and are written only once everything has run.  Returns what
+ * pllhip_pairwise_distances returns.
+ * pllhip_joining_kernel_ms: while profiling is on, what the joining kernels of the last call took. */
+typedef struct pllhip_join { unsigned int a, b; double length_a, length_b; } pllhip_join_t;
+typedef struct pllhip_join_last { unsigned int node[3]; double length[3]; } pllhip_join_last_t;
+PLLHIP_EXPORT int pllhip_matrix_joins(pllhip_ctx_t * ctx, const double * h_distances, const double * h_variances,
+                                      unsigned int n, int method, pllhip_join_t * h_joins,
+                                      pllhip_join_last_t * h_last);
+PLLHIP_EXPORT int pllhip_distance_joins(pllhip_ctx_t * ctx, const unsigned int * h_tips, unsigned int count,
+                                        const unsigned int * h_params_indices, double min_length, double max_length,
+                                        double tolerance, unsigned int max_iters, size_t scratch_bytes, int method,
+                                        double * h_distances, int * h_status, pllhip_join_t * h_joins,
+                                        pllhip_join_last_t * h_last);
+PLLHIP_EXPORT int pllhip_joining_kernel_ms(pllhip_ctx_t * ctx, float * ms);
+
 /* The planner of k_tree_score on its own -- host logic, no device needed.  The ops the edge (parent_clv, child_clv
  * with their scaler indices) does not depend on are dropped; the rest are ordered depth-first from the edge, the
  * operand that needs more live values first, and a parent takes the slot of one of its operands.  Tips (pattern_tip)

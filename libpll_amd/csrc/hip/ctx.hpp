@@ -26,7 +26,8 @@ struct pllhip_rep_work;
 // -- edge descriptors, the chunk's per-site terms and its per-span partial sums; NNI support -- P-matrices, descriptors,
 // the candidates' per-site terms, per-span partial sums, the replicate table, centres and counts and, on the general
 // route, candidate CLVs and scale buffers; distances -- the two factors of the bin table, the chunk's count tables, Newton
-// states, start lengths and results, its jobs and the pairs' tips
+// states, start lengths and results, its jobs and the pairs' tips; joining -- the working distance and variance matrices,
+// the row sums, the slots' node numbers, the scan's candidates, the step record and the joins
 struct BatchScratch
 {
   void * p = nullptr;
@@ -42,6 +43,7 @@ enum
   BATCH_REPLICATES,
   BATCH_NNI_SUPPORT,
   BATCH_DISTANCE,
+  BATCH_JOINING,
   BATCH_FAMILIES
 };
 
@@ -337,6 +339,7 @@ struct pllhip_ctx
   // until the context goes.  Apart on purpose: two families zero theirs only when it grows
   BatchScratch batch_scratch[BATCH_FAMILIES];
   float distance_ms[2] = {0.f, 0.f}; // distance.hip: the counting and Newton kernels of the last call, timed while profiling is on
+  float joining_ms = 0.f;            // joining.hip: the kernels of the last call, first row sum to last join, likewise
   // the replicate sets that are alive (pllhip_replicates_create / _destroy); the context's end is theirs
   std::vector<pllhip_replicates *> replicate_sets;
 

@@ -31,6 +31,7 @@
 // Determinism: a pair's table is an exact integer sum, and its Newton wave reads nothing but that table and the model,
 // in a fixed order: a pair's outputs do not depend on the batch, its order, the mode or the chunking.
 #include "branch_opt.hpp"
+#include "distance.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -379,6 +380,20 @@ __global__ __launch_bounds__(64) void k_dist_newton(DistNewtonArgs a)
   }
 }
 
+// the device-resident route (distance.hpp): a chunk's distances into the square matrix, both halves
+__global__ __launch_bounds__(256) void k_dist_scatter(const BoState * __restrict__ st,
+                                                      const unsigned long long * __restrict__ at, unsigned int pairs,
+                                                      unsigned int n, double * __restrict__ matrix)
+{
+  const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= pairs) return;
+  const unsigned long long o = at[i];
+  const unsigned long long x = o / n, y = o % n;
+  const double t = st[i].t;
+  matrix[o] = t;
+  matrix[y * n + x] = t;
+}
+
 extern "C" int pllhip_distance_kernel_ms(pllhip_ctx_t * c, float * ms2)
 {
   if (!c || !ms2) return -1;
@@ -394,8 +409,24 @@ extern "C" int pllhip_pairwise_distances(pllhip_ctx_t * c, const unsigned int * 
                                          const double * h_start, double * h_dist, double * h_lnl,
                                          unsigned int * h_evals, int * h_status, unsigned int * h_counts)
 {
-  const char * what = "pllhip_pairwise_distances";
-  if (!c || !row_tips || !params || !h_dist || !row_count || (col_tips && !col_count) || (!col_tips && col_count))
+  if (!h_dist)
+  {
+    pllhip_set_error("pllhip_pairwise_distances: empty batch or NULL array");
+    return -1;
+  }
+  return pllhip_distances_run(c, "pllhip_pairwise_distances", row_tips, row_count, col_tips, col_count, params,
+                              min_length, max_length, tolerance, max_iters, budget, h_start, h_dist, h_lnl, h_evals,
+                              h_status, h_counts, nullptr);
+}
+
+int pllhip_distances_run(pllhip_ctx * c, const char * what, const unsigned int * row_tips, unsigned int row_count,
+                         const unsigned int * col_tips, unsigned int col_count, const unsigned int * params,
+                         double min_length, double max_length, double tolerance, unsigned int max_iters, size_t budget,
+                         const double * h_start, double * h_dist, double * h_lnl, unsigned int * h_evals,
+                         int * h_status, unsigned int * h_counts, double * d_matrix)
+{
+  if (!c || !row_tips || !params || (!h_dist && !d_matrix) || !row_count || (col_tips && !col_count) ||
+      (!col_tips && col_count) || (d_matrix && col_tips))
   {
     pllhip_set_error("%s: empty batch or NULL array", what);
     return -1;
@@ -468,7 +499,7 @@ extern "C" int pllhip_pairwise_distances(pllhip_ctx_t * c, const unsigned int * 
   if (jobs.empty()) return 0; // (one tip against itself: the diagonal is the host's)
 
   // ---- chunk size in whole jobs: everything one chunk needs within `budget` bytes (one job at least)
-  const size_t per_pair = (size_t)C2 * 4 + sizeof(BoState) + 8 + 8 + 4 + 4;
+  const size_t per_pair = (size_t)C2 * 4 + sizeof(BoState) + 8 + 8 + 4 + 4 + (d_matrix ? 8 : 0);
   const size_t per_job = DIST_LANES * per_pair + sizeof(DistJob) + 7 * 256;
   const size_t fixed = 2 * (size_t)C * R * S * 8 + 4096;
   const size_t room = budget > fixed ? (budget - fixed) / per_job : 0;
@@ -485,6 +516,7 @@ extern "C" int pllhip_pairwise_distances(pllhip_ctx_t * c, const unsigned int * 
   const size_t o_col = L.take(ncp * 4);
   const size_t o_row = L.take(ncp * 4);
   const size_t o_jobs = L.take(ncj * sizeof(DistJob));
+  const size_t o_at = d_matrix ? L.take(ncp * 8) : 0;
   BatchScratch & scratch = c->batch_scratch[BATCH_DISTANCE];
   if ((rc = pllhip_batch_scratch_grow(c, scratch, L.off, what))) return rc;
   char * base = (char *)scratch.p;
@@ -494,6 +526,8 @@ extern "C" int pllhip_pairwise_distances(pllhip_ctx_t * c, const unsigned int * 
   double * d_lnl = (double *)(base + o_lnl), * d_start = (double *)(base + o_start);
   unsigned int * d_col = (unsigned int *)(base + o_col), * d_row = (unsigned int *)(base + o_row);
   DistJob * d_jobs = (DistJob *)(base + o_jobs);
+  unsigned long long * d_at = (unsigned long long *)(base + o_at); // (d_matrix only)
+  const bool to_host = h_dist || h_lnl || h_evals || h_status || h_counts;
 
   DistNewtonArgs na;
   memset(&na, 0, sizeof(na));
@@ -543,6 +577,7 @@ extern "C" int pllhip_pairwise_distances(pllhip_ctx_t * c, const unsigned int * 
   std::vector<double> hl(ncp), hstart(h_start ? ncp : 0);
   std::vector<unsigned int> hc(h_counts ? ncp * C2 : 0);
   std::vector<DistJob> hj(ncj);
+  std::vector<unsigned long long> hat(d_matrix ? ncp : 0);
   for (size_t j0 = 0; j0 < jobs.size(); j0 += ncj)
   {
     const size_t nj = std::min(ncj, jobs.size() - j0);
@@ -592,7 +627,15 @@ extern "C" int pllhip_pairwise_distances(pllhip_ctx_t * c, const unsigned int * 
     k_dist_newton<<<np, 64, lds_newton, c->stream>>>(na);
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(ev[2], c->stream));
-    HIP_TRY(hipMemcpyAsync(hs.data(), d_state, (size_t)np * sizeof(BoState), hipMemcpyDeviceToHost, c->stream));
+    if (d_matrix)
+    {
+      for (unsigned int i = 0; i < np; ++i) hat[i] = pair_out[p0 + i];
+      HIP_TRY(hipMemcpyAsync(d_at, hat.data(), (size_t)np * 8, hipMemcpyHostToDevice, c->stream));
+      k_dist_scatter<<<(np + 255u) / 256u, 256, 0, c->stream>>>(d_state, d_at, np, row_count, d_matrix);
+      HIP_TRY(hipGetLastError());
+    }
+    if (to_host)
+      HIP_TRY(hipMemcpyAsync(hs.data(), d_state, (size_t)np * sizeof(BoState), hipMemcpyDeviceToHost, c->stream));
     if (h_lnl) HIP_TRY(hipMemcpyAsync(hl.data(), d_lnl, (size_t)np * 8, hipMemcpyDeviceToHost, c->stream));
     if (h_counts)
       HIP_TRY(hipMemcpyAsync(hc.data(), d_counts, (size_t)np * C2 * 4, hipMemcpyDeviceToHost, c->stream));
@@ -605,10 +648,10 @@ extern "C" int pllhip_pairwise_distances(pllhip_ctx_t * c, const unsigned int * 
       HIP_TRY(hipEventElapsedTime(&ms, ev[1], ev[2]));
       c->distance_ms[1] += ms;
     }
-    for (unsigned int i = 0; i < np; ++i)
+    for (unsigned int i = 0; to_host && i < np; ++i)
     {
       const size_t o = pair_out[p0 + i];
-      h_dist[o] = hs[i].t;
+      if (h_dist) h_dist[o] = hs[i].t;
       if (h_lnl) h_lnl[o] = hl[i];
       if (h_evals) h_evals[o] = hs[i].evals;
       if (h_status) h_status[o] = hs[i].status;

@@ -269,20 +269,18 @@ static void diagonal_counts(const pll_partition_t * p, unsigned int tip, unsigne
     if (row[n] < codes) out[(size_t)row[n] * codes + row[n]] += p->pattern_weights ? p->pattern_weights[n] : 1u;
 }
 
-int pll_amd_pairwise_distances(pll_partition_t * p, const unsigned int * row_tips, unsigned int row_count,
-                               const unsigned int * col_tips, unsigned int col_count,
-                               const unsigned int * params_indices, double min_length, double max_length,
-                               double tolerance, unsigned int max_iters, const double * start_lengths,
-                               double * distances, double * lnl, unsigned int * evals, int * status,
-                               unsigned int * counts)
+/* Everything pll_amd_pairwise_distances checks and prepares before the device is asked (pll_amd_distance_tree,
+   joining.c, begins the same way): the arguments, the partition kinds refused, the eigen systems made current and the
+   model flushed; *budget is the scratch of a chunk. */
+int pll_amd_distance_prepare(pll_partition_t * p, const char * what, const unsigned int * row_tips,
+                             unsigned int row_count, const unsigned int * col_tips, unsigned int col_count,
+                             const unsigned int * params_indices, double min_length, double max_length,
+                             double tolerance, unsigned int max_iters, const double * start_lengths, size_t * budget)
 {
-  const char * what = "pll_amd_pairwise_distances";
   pll_amd_partition_t * q;
   unsigned int i, x, y, codes, width;
   unsigned long long wsum = 0;
-  size_t budget, c2;
-  int rc;
-  if (!p || !row_tips || !params_indices || !distances)
+  if (!p || !row_tips || !params_indices)
   {
     pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "%s: NULL argument", what);
     return PLL_FAILURE;
@@ -363,8 +361,34 @@ int pll_amd_pairwise_distances(pll_partition_t * p, const unsigned int * row_tip
   {
     const char * env = getenv("PLL_AMD_DISTANCE_SCRATCH_MB");
     const double mb = env ? atof(env) : 2048.0;
-    budget = mb > 0.0 ? (size_t)(mb * 1024.0 * 1024.0) : 0;
+    *budget = mb > 0.0 ? (size_t)(mb * 1024.0 * 1024.0) : 0;
   }
+  return PLL_SUCCESS;
+}
+
+int pll_amd_pairwise_distances(pll_partition_t * p, const unsigned int * row_tips, unsigned int row_count,
+                               const unsigned int * col_tips, unsigned int col_count,
+                               const unsigned int * params_indices, double min_length, double max_length,
+                               double tolerance, unsigned int max_iters, const double * start_lengths,
+                               double * distances, double * lnl, unsigned int * evals, int * status,
+                               unsigned int * counts)
+{
+  const char * what = "pll_amd_pairwise_distances";
+  pll_amd_partition_t * q;
+  unsigned int x, y, codes, width;
+  size_t budget, c2;
+  int rc;
+  if (!distances)
+  {
+    pll_amd_set_error(PLL_ERROR_PARAM_INVALID, "%s: NULL argument", what);
+    return PLL_FAILURE;
+  }
+  if (!pll_amd_distance_prepare(p, what, row_tips, row_count, col_tips, col_count, params_indices, min_length,
+                                max_length, tolerance, max_iters, start_lengths, &budget))
+    return PLL_FAILURE;
+  q = pll_amd_priv(p);
+  width = col_tips ? col_count : row_count;
+  codes = p->states == 4 ? 16u : p->maxstates;
   rc = pllhip_pairwise_distances(q->ctx, row_tips, row_count, col_tips, col_count, params_indices, min_length,
                                  max_length, tolerance, max_iters, budget, start_lengths, distances, lnl, evals,
                                  status, counts);

@@ -128,6 +128,13 @@ int pll_amd_check_model_candidates(const pll_partition_t * p, const pll_amd_mode
 /* a device-layer return code of these calls as pll_errno; returns PLL_SUCCESS for 0 */
 int pll_amd_tree_score_result(int rc, const char * what);
 
+/* distance.c: the checks and preparations of pll_amd_pairwise_distances, which pll_amd_distance_tree (joining.c) shares.
+ * PLL_SUCCESS: *budget (PLL_AMD_DISTANCE_SCRATCH_MB) is set; otherwise pll_errno is. */
+int pll_amd_distance_prepare(pll_partition_t * p, const char * what, const unsigned int * row_tips,
+                             unsigned int row_count, const unsigned int * col_tips, unsigned int col_count,
+                             const unsigned int * params_indices, double min_length, double max_length,
+                             double tolerance, unsigned int max_iters, const double * start_lengths, size_t * budget);
+
 /* repeats.c */
 int pll_amd_repeats_alloc(pll_amd_partition_t * q);
 void pll_amd_repeats_free(pll_amd_partition_t * q);

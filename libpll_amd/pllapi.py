@@ -123,6 +123,10 @@ class ParsRecop(C.Structure):
                 ("parent_score_index", C.c_uint), ("parent_ancestral_index", C.c_uint)]
 
 
+JOIN_NJ, JOIN_BIONJ = 0, 1          # pll_amd.h: PLL_AMD_JOIN_*
+JOIN_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("length_a", np.float64), ("length_b", np.float64)])
+JOIN_LAST_DTYPE = np.dtype([("node", np.uint32, 3), ("length", np.float64, 3)], align=True)
+
 ERROR_STEPWISE_STRUCT = 127         # pll.h:164-166
 ERROR_STEPWISE_TIPS = 128
 ERROR_STEPWISE_UNSUPPORTED = 129
@@ -342,6 +346,42 @@ class PllLibrary:
                                                             [C.c_double, C.c_double, C.c_double, C.c_uint,
                                                              C.c_double] + [C.c_void_p] * 4
                 lib.pll_amd_distance_kernel_ms.argtypes = [_PP, C.POINTER(C.c_float)]
+            if hasattr(lib, "pll_amd_matrix_joins"):
+                lib.pll_amd_joins_from_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_void_p,
+                                                          C.c_void_p]
+                lib.pll_amd_matrix_joins.argtypes = [_PP, C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_void_p,
+                                                     C.c_void_p]
+                lib.pll_amd_tree_from_joins.restype = C.POINTER(UTree)
+                lib.pll_amd_tree_from_joins.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]
+                lib.pll_amd_distance_tree.restype = C.POINTER(UTree)
+                lib.pll_amd_distance_tree.argtypes = [_PP, C.c_void_p, C.c_uint, C.c_void_p, C.c_double, C.c_double,
+                                                      C.c_double, C.c_uint, C.c_int] + [C.c_void_p] * 5
+                lib.pll_amd_joining_kernel_ms.argtypes = [_PP, C.POINTER(C.c_float)]
+
+    def joins_from_matrix(self, distances, variances=None, method=JOIN_NJ):
+        """pll_amd_joins_from_matrix (host only): (joins, last) -- a JOIN_DTYPE array [n - 3] and a JOIN_LAST_DTYPE
+        record -- of the square matrix `distances` (and `variances`, BIONJ only; None: V = d)"""
+        if not hasattr(self.lib, "pll_amd_joins_from_matrix"):
+            raise PllError("this library has no pll_amd_joins_from_matrix")
+        d, v, joins, last = _join_buffers(distances, variances)
+        ok = self.lib.pll_amd_joins_from_matrix(d.ctypes.data, None if v is None else v.ctypes.data, len(d), method,
+                                                joins.ctypes.data, last.ctypes.data)
+        if not ok:
+            raise PllError("pll_amd_joins_from_matrix: errno %d: %s" % (self.errno(), self.errmsg()))
+        return joins[:max(len(d), 3) - 3], last[0]
+
+    def tree_from_joins(self, joins, last, n, labels=None):
+        """pll_amd_tree_from_joins (host only): the pointer to the pll_utree_t; raises on failure"""
+        if not hasattr(self.lib, "pll_amd_tree_from_joins"):
+            raise PllError("this library has no pll_amd_tree_from_joins")
+        j = np.ascontiguousarray(joins, dtype=JOIN_DTYPE).reshape(-1)
+        l = np.ascontiguousarray(last, dtype=JOIN_LAST_DTYPE).reshape(1)
+        lab = _label_array(labels)
+        t = self.lib.pll_amd_tree_from_joins(j.ctypes.data if len(j) else None, l.ctypes.data, n,
+                                             None if lab is None else C.addressof(lab))
+        if not t:
+            raise PllError("pll_amd_tree_from_joins failed (pll_errno=%d): %s" % (self.errno(), self.errmsg()))
+        return t
 
     def distance_from_counts(self, states, code_masks, counts, eigenvecs, inv_eigenvecs, eigenvals, freqs, rates,
                              rate_weights, prop_invar, min_length=1e-6, max_length=100.0, tolerance=1e-7,
@@ -458,6 +498,22 @@ class PllLibrary:
             raise PllError("pll_partition_create failed (pll_errno=%d): %s"
                            % (self.errno(), self.errmsg()))
         return Partition(self, p)
+
+
+def _join_buffers(distances, variances):
+    d = np.ascontiguousarray(distances, dtype=np.float64)
+    assert d.ndim == 2 and d.shape[0] == d.shape[1], d.shape
+    v = None
+    if variances is not None:
+        v = np.ascontiguousarray(variances, dtype=np.float64)
+        assert v.shape == d.shape, v.shape
+    return d, v, np.zeros(max(len(d), 4) - 3, dtype=JOIN_DTYPE), np.zeros(1, dtype=JOIN_LAST_DTYPE)
+
+
+def _label_array(labels):
+    if labels is None:
+        return None
+    return (C.c_char_p * len(labels))(*[x.encode() if isinstance(x, str) else x for x in labels])
 
 
 _libc = C.CDLL(None)
@@ -1044,6 +1100,52 @@ class Partition:
             ptr("evals"), ptr("status"), ptr("counts"))
         self._check(ok, "pll_amd_pairwise_distances")
         return out
+
+    def matrix_joins(self, distances, variances=None, method=JOIN_NJ):
+        """pll_amd_matrix_joins: (joins, last) as PllLibrary.joins_from_matrix returns them, from the device"""
+        if not hasattr(self.lib, "pll_amd_matrix_joins"):
+            raise PllError("this library has no pll_amd_matrix_joins")
+        d, v, joins, last = _join_buffers(distances, variances)
+        ok = self.lib.pll_amd_matrix_joins(self.ptr, d.ctypes.data, None if v is None else v.ctypes.data, len(d),
+                                           method, joins.ctypes.data, last.ctypes.data)
+        self._check(ok, "pll_amd_matrix_joins")
+        return joins[:max(len(d), 3) - 3], last[0]
+
+    def distance_tree(self, tips, params_indices, method=JOIN_NJ, labels=None, min_length=1e-6, max_length=100.0,
+                      tolerance=1e-7, max_iters=64, want=("distances", "status", "joins")):
+        """pll_amd_distance_tree: (pointer to the pll_utree_t, dict) -- the dict holds what `want` names of distances
+        and status ([count][count]) and joins (then also last); raises on failure"""
+        if not hasattr(self.lib, "pll_amd_distance_tree"):
+            raise PllError("this library has no pll_amd_distance_tree")
+        t = np.ascontiguousarray(tips, dtype=np.uint32).reshape(-1)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        n = len(t)
+        out = {}
+        if "distances" in want:
+            out["distances"] = np.zeros((n, n))
+        if "status" in want:
+            out["status"] = np.zeros((n, n), dtype=np.int32)
+        joins = np.zeros(max(n, 4) - 3, dtype=JOIN_DTYPE)
+        last = np.zeros(1, dtype=JOIN_LAST_DTYPE)
+        lab = _label_array(labels)
+
+        def ptr(name):
+            return out[name].ctypes.data if name in out and out[name].size else None
+        tree = self.lib.pll_amd_distance_tree(
+            self.ptr, t.ctypes.data if n else None, n, pi.ctypes.data, min_length, max_length, tolerance, max_iters,
+            method, None if lab is None else C.addressof(lab), ptr("distances"), ptr("status"),
+            joins.ctypes.data if "joins" in want else None, last.ctypes.data if "joins" in want else None)
+        if not tree:
+            raise PllError("pll_amd_distance_tree failed (pll_errno=%d): %s" % (self.o.errno(), self.o.errmsg()))
+        if "joins" in want:
+            out["joins"], out["last"] = joins[:max(n, 3) - 3], last[0]
+        return tree, out
+
+    def joining_kernel_ms(self):
+        """ms of the joining kernels of the last matrix_joins / distance_tree call made with profile_enable on"""
+        ms = C.c_float()
+        self._check(self.lib.pll_amd_joining_kernel_ms(self.ptr, C.byref(ms)), "pll_amd_joining_kernel_ms")
+        return float(ms.value)
 
     def distance_kernel_ms(self):
         """(counting ms, Newton ms) of the last pairwise_distances call made with profile_enable on"""
