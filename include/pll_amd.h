@@ -1502,6 +1502,16 @@ PLL_EXPORT int pll_amd_pair_fold_stats(pll_partition_t * partition, unsigned lon
  * built in total, build launches, evictions}. */
 PLL_EXPORT int pll_amd_set_pair_row_capacity(pll_partition_t * partition, unsigned int rows);
 PLL_EXPORT int pll_amd_pair_row_stats(pll_partition_t * partition, unsigned long long * stats4);
+/* Quad rows of the same partitions (pllhip.h: pllhip_set_quad_rows): a folded pair product over two cherries is read
+ * from a per-call table of one entry per distinct pattern of its four tips' characters, by a cached row of 16-bit class
+ * numbers.  On by default; min_sites_per_class: the fewest sites per class a quad is taken at (0: the default, 64).
+ * rows: capacity of the pool (0: the default, a row per four tips; 2 bytes per site and row).  stats5: {rows live now,
+ * rows built in total, build launches, evictions, quads refused}.  Results are bit for bit the same either way. */
+PLL_EXPORT int pll_amd_set_quad_rows(pll_partition_t * partition, int on, unsigned int min_sites_per_class);
+PLL_EXPORT int pll_amd_set_quad_row_capacity(pll_partition_t * partition, unsigned int rows);
+PLL_EXPORT int pll_amd_quad_row_stats(pll_partition_t * partition, unsigned long long * stats5);
+/* {quads read as tables in the list planned last, its wide gathers, quads read as tables by all planned lists} */
+PLL_EXPORT int pll_amd_quad_list_stats(pll_partition_t * partition, unsigned long long * stats3);
 /* Edge log-likelihood terms from the 4-state whole-list launch (pllhip.h: pllhip_set_edge_fold): after
  * pll_compute_edge_loglikelihood at an inner-inner edge, the next pll_update_partials that writes one of the edge's two
  * CLVs also forms the edge's per-site terms, and the same evaluation then only sums them -- bit for bit the value it

@@ -295,6 +295,45 @@ PLLHIP_EXPORT int pllhip_fused_plan_dry_folded(unsigned int tips, unsigned int c
  * pllhip_pair_row_stats: {rows live now, rows built in total, build launches, evictions}. */
 PLLHIP_EXPORT int pllhip_set_pair_row_capacity(pllhip_ctx_t * ctx, unsigned int n);
 PLLHIP_EXPORT int pllhip_pair_row_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+/* Quad rows (quad_rows.hip): a folded pair product whose two factors are both cherries takes one value
+ * per distinct pattern of its four tips' characters.  Per ordered pair of ordered tip pairs the context caches the
+ * patterns in ascending order -- the classes, at most 1024 -- and a row of 16-bit class numbers per site, and the
+ * product's reader gathers its factor from a per-call table of one entry per class.  A pool of its own, run by the pair
+ * rows' rules (tips / 4 rows by default, 2 bytes per site and row); finding a new quad's classes waits for the device
+ * once.  A quad is taken only at min_sites_per_class sites per class or more (0: the default, 64) and, where the folded
+ * op has a scale buffer, only where the host's bounds of the matrices prove that the product cannot scale.
+ * pllhip_quad_row_stats: {rows live now, rows built in total, build launches, evictions, quads refused}. */
+PLLHIP_EXPORT int pllhip_set_quad_rows(pllhip_ctx_t * ctx, int on, unsigned int min_sites_per_class);
+PLLHIP_EXPORT int pllhip_set_quad_row_capacity(pllhip_ctx_t * ctx, unsigned int n);
+PLLHIP_EXPORT int pllhip_quad_row_stats(pllhip_ctx_t * ctx, unsigned long long * out5);
+/* {quads read as tables in the list planned last, its wide gathers, quads read as tables by all planned lists}. */
+PLLHIP_EXPORT int pllhip_quad_list_stats(pllhip_ctx_t * ctx, unsigned long long * out3);
+/* Host logic, no device (tests/test_host_quad_rows.py): the classes and the row of two pair rows' bytes as the device
+ * builder makes them (row_out: two planes of `stride` bytes; returns 1 beyond the cap, the row then all zero); where a
+ * site's 16 bits lie in a row; the class gather_factor() of the list kernel picks from the character registers of the
+ * lanes that hold a row's tile (four words per lane, plane 0's lanes first); the rule a quad is taken by (0: taken,
+ * else the reason: 1 not two cherries, 2 the instance, 3 the class cap, 4 sites per class, 5 no bound, 6 mixed reader). */
+PLLHIP_EXPORT int pllhip_quad_row_build_dry(const unsigned char * pa, const unsigned char * pb, unsigned int sites,
+                                            unsigned int stride, unsigned int * n_out, unsigned short * patterns_out,
+                                            unsigned char * row_out);
+PLLHIP_EXPORT unsigned long long pllhip_quad_row_offset_dry(unsigned long long site, unsigned long long stride);
+PLLHIP_EXPORT unsigned int pllhip_fused_quad_pick_dry(const unsigned int * lanes, unsigned int sps, unsigned int sub_step,
+                                                      unsigned int lane);
+/* The quads of a planned list without a device (fused_plan.hip): the final walk of pllhip_fused_plan_dry_rows, then
+ * the rule the live path applies.  classes[i] / bounds[i]: the class count of the quad row (0: beyond the cap) and the
+ * host's lower bound of the table (NULL, <= 0: none) of op i where it is a folded product.  ops_out[3 pos ..]: kind,
+ * gathers, wide gathers of walked op pos; quads_out[i]: -1 no folded product, 0 read as a quad, else the reason
+ * (pllhip_fused_quad_rule_dry); counts_out[2]: quads taken, refused. */
+PLLHIP_EXPORT int pllhip_fused_plan_dry_quads(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                              int pattern_tip, unsigned int rate_cats, int rate_scalers, const pllhip_op_t * ops,
+                                              unsigned int count, unsigned int nslots, const unsigned char * pinned,
+                                              const int * edge4, unsigned int sites, int quads_on,
+                                              unsigned int min_sites_per_class, const unsigned int * classes,
+                                              const double * bounds, unsigned int * nkept, unsigned int * order_out,
+                                              unsigned char * folded_out, int * ops_out, int * quads_out,
+                                              unsigned int * counts_out);
+PLLHIP_EXPORT int pllhip_fused_quad_rule_dry(int cherries, int instance, unsigned int n, unsigned int sites,
+                                             unsigned int min_sites_per_class, int scales, double bound);
 /* Host logic, no device (tests/test_host_pair_rows.py): the pair row's byte; the index gather_factor() of the list
  * kernel takes from ONE row's words of a tile (kind 0 a pair row, 1 a single tip that is the table's first character,
  * 2 one that is its second); and the rows every walked op's gathers name, on top of pllhip_fused_plan_dry_folded's

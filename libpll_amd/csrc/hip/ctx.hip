@@ -584,6 +584,7 @@ extern "C" void pllhip_ctx_destroy(pllhip_ctx_t * c)
   if (c->d_tile_counter) (void)hipFree(c->d_tile_counter);
   if (c->d_pairtab) (void)hipFree(c->d_pairtab);
   pllhip_pair_rows_free(c);
+  pllhip_quad_rows_free(c);
   if (c->defer_pool) (void)hipFree(c->defer_pool);
   if (c->cherry_pool) (void)hipFree(c->cherry_pool);
   if (c->cherry_codes) (void)hipFree(c->cherry_codes);
@@ -658,6 +659,7 @@ extern "C" int pllhip_put_tipchars(pllhip_ctx_t * c, unsigned int tip, const uns
     return -1;
   }
   pllhip_pair_rows_tip_written(c, tip); // (pair_rows.hip: rebuilt in place before the next list launch reads them)
+  pllhip_quad_rows_tip_written(c, tip); // (quad_rows.hip: counted again, and the kept plan ends)
   return h2d(c, c->tipchars + (size_t)tip * c->tip_stride, h, c->sh.sites);
 }
 
@@ -774,6 +776,7 @@ extern "C" int pllhip_put_rates(pllhip_ctx_t * c, const double * r, const double
   pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
   PLLHIP_ALL_SHARDS(c, pllhip_put_rates(s, r, w));
   int rc = 0;
+  if (r && c->sh.states == 4) c->h_rates.assign(r, r + c->sh.rate_cats); // (the host's copy: pllhip_pmat_bounds_update)
   if (r) rc = h2d(c, c->rates, r, c->sh.rate_cats * sizeof(double));
   if (!rc && w) rc = h2d(c, c->rate_weights, w, c->sh.rate_cats * sizeof(double));
   return rc;
@@ -788,6 +791,17 @@ extern "C" int pllhip_put_model(pllhip_ctx_t * c, unsigned int pi, const double 
   if (pi >= c->sh.rate_matrices) { pllhip_set_error("pllhip_put_model: index %u", pi); return -1; }
   const size_t S = c->sh.states;
   int rc = 0;
+  if (S == 4)
+  {
+    // (the host's copy of the model: what pllhip_pmat_bounds_update forms its bounds from)
+    const size_t M = c->sh.rate_matrices;
+    if (c->h_eigenvals.size() != M * S) c->h_eigenvals.assign(M * S, 0.0);
+    if (c->h_eigenvecs.size() != M * S * S) c->h_eigenvecs.assign(M * S * S, 0.0);
+    if (c->h_inv_eigenvecs.size() != M * S * S) c->h_inv_eigenvecs.assign(M * S * S, 0.0);
+    if (evals) memcpy(&c->h_eigenvals[pi * S], evals, S * sizeof(double));
+    if (evecs) memcpy(&c->h_eigenvecs[pi * S * S], evecs, S * S * sizeof(double));
+    if (inv_evecs) memcpy(&c->h_inv_eigenvecs[pi * S * S], inv_evecs, S * S * sizeof(double));
+  }
   if (evals) rc = h2d(c, c->eigenvals + pi * S, evals, S * sizeof(double));
   if (!rc && evecs) rc = h2d(c, c->eigenvecs + pi * S * S, evecs, S * S * sizeof(double));
   if (!rc && inv_evecs) rc = h2d(c, c->inv_eigenvecs + pi * S * S, inv_evecs, S * S * sizeof(double));
@@ -806,6 +820,12 @@ extern "C" int pllhip_put_pmatrix(pllhip_ctx_t * c, unsigned int idx, const doub
   PLLHIP_ALL_SHARDS(c, pllhip_put_pmatrix(s, idx, h));
   PLLHIP_CERT_FIRST(c);
   if (idx >= c->sh.prob_matrices) { pllhip_set_error("pllhip_put_pmatrix: index %u", idx); return -1; }
+  // (a matrix written by this route: the host claims no bound for it -- no quad stands on it, quad_rows.hip)
+  if (idx < c->pmat_min_entry.size() && c->pmat_min_entry[idx] != 0.0)
+  {
+    c->pmat_min_entry[idx] = c->pmat_min_rowsum[idx] = 0.0;
+    ++c->layout_epoch;
+  }
   return h2d(c, pllhip_pmat_ptr(c, idx), h, c->pmat_elems * sizeof(double));
 }
 

@@ -157,6 +157,43 @@ struct pllhip_ctx
     unsigned long long clock = 0;
     unsigned long long stats[4] = {0, 0, 0, 0}; // rows live (filled on read), rows built, build launches, evictions
   } pair_rows;
+  // ---- quad rows (quad_rows.hip, DESIGN.md 2.0 "Quad rows"): per ordered pair of ordered tip pairs ((a, b), (c, d)) the
+  // distinct patterns (pair-row byte of (a, b)) << 8 | (pair-row byte of (c, d)) of the alignment in ascending order --
+  // the classes -- and one cached row of 16-bit class numbers per site, by which a 4-state list kernel gathers the
+  // factor of a folded pair product over two cherries.  A pool of its own, run by the pair rows' rules.
+  struct quad_row
+  {
+    unsigned int t[4] = {0, 0, 0, 0};
+    bool live = false, stale = false;
+    unsigned int n = 0;                    // classes; 0: more than PLLHIP_QUAD_MAX_CLASSES (no row, no list: refused)
+    bool has_zero = false;                 // a site has a character code 0 at one of the four tips
+    unsigned long long used = 0;
+  };
+  struct quad_row_pool
+  {
+    unsigned char * d = nullptr;           // [cap][2 planes][tip_stride] + PLLHIP_TAIL_SITES
+    unsigned short * d_patterns = nullptr; // [cap][PLLHIP_QUAD_MAX_CLASSES]
+    unsigned int * d_counts = nullptr;     // [cap] class counts as the device found them
+    unsigned int * d_work = nullptr;       // the builder's maps: [jobs of a launch][65536]
+    unsigned int * h_counts = nullptr;     // pinned, [cap]
+    std::vector<quad_row> rows;
+    unsigned int want = 0;                 // pllhip_set_quad_row_capacity (0: tips / 4 rows)
+    unsigned int nstale = 0;
+    unsigned long long clock = 0;
+    unsigned long long stats[5] = {0, 0, 0, 0, 0}; // rows live (filled on read), rows built, build launches, evictions, refused
+  } quad_rows;
+  bool quad_rows_on = true;                    // pllhip_set_quad_rows
+  unsigned int quad_min_sites_per_class = 64;
+  // What the host knows of each P-matrix without waiting for the device (pmatrix.hip): a lower bound on its entries
+  // and on its row sums, formed from the host's copy of the model when pllhip_update_pmatrices writes it; 0: none
+  // (never written, a branch of length 0, a model the host has no copy of).  A quad is taken for a product with a
+  // scale buffer only where these prove that it cannot scale.
+  std::vector<double> pmat_min_entry, pmat_min_rowsum; // per matrix index
+  std::vector<double> h_eigenvals, h_eigenvecs, h_inv_eigenvecs, h_rates; // the model as last set (4 states only)
+  std::vector<unsigned int> fused_last_quad_mats; // matrices whose bounds the kept plan's quads stand on
+  unsigned int fused_last_quads_refused_by_bound = 0; // quads the kept plan lost to a bound: a better one plans again
+  unsigned int fused_last_quad_jobs = 0;       // table jobs of kind 4 in the kept plan (0: no k_dna_quad_tables launch)
+  unsigned long long quad_list_stats[3] = {0, 0, 0}; // quads read as tables: in the last planned list, its wide gathers, in all
   // ---- deferred cherries (deferred.hip): a tip-tip op of a 4-state whole-list launch is not run; its
   // parent CLV is DEFINED by its two tip rows and a kept copy of its pair table T[c1][c2][rate][state] until somebody
   // other than a list kernel needs the bytes -- every such entry point materialises what it touches first
@@ -435,6 +472,27 @@ int pllhip_pair_rows_resolve(pllhip_ctx * c, const std::vector<std::pair<unsigne
 int pllhip_pair_rows_refresh(pllhip_ctx * c);                       // stale rows rebuilt in place, on the stream
 void pllhip_pair_rows_tip_written(pllhip_ctx * c, unsigned int tip); // a tip row's bytes change: its pair rows are stale
 void pllhip_pair_rows_free(pllhip_ctx * c);
+// quad_rows.hip: the cached quad rows of a context (pllhip_ctx::quad_rows)
+struct QuadRowRef
+{
+  unsigned int n = 0;                        // classes (0: beyond the cap -- no row)
+  bool has_zero = false;                     // a pattern has a character code 0: its entry is 0, no lower bound holds
+  const unsigned char * row = nullptr;       // plane 0; plane 1 is tip_stride bytes behind
+  const unsigned short * patterns = nullptr; // [n] on the device, ascending
+};
+struct QuadKey
+{
+  unsigned int t[4];
+  bool operator<(const QuadKey & o) const { return memcmp(t, o.t, sizeof(t)) < 0; }
+};
+// need[i] = ((a, b), (c, d)) -> out[i]; rows the pool lacks are built on the stream and the host waits for their
+// class counts once; a list whose quads are all in the pool waits for nothing
+int pllhip_quad_rows_resolve(pllhip_ctx * c, const std::vector<QuadKey> & need, std::vector<QuadRowRef> & out);
+void pllhip_quad_rows_tip_written(pllhip_ctx * c, unsigned int tip); // its quad rows are stale, and the kept plan ends
+void pllhip_quad_rows_free(pllhip_ctx * c);
+// pmatrix.hip: the host's bounds of the matrices about to be written (pllhip_ctx::pmat_min_entry)
+void pllhip_pmat_bounds_update(pllhip_ctx * c, const unsigned int * h_params_indices, const unsigned int * h_matrix_indices,
+                               const double * h_branch_lengths, unsigned int count);
 
 static inline bool pllhip_is_tip(const pllhip_ctx * c, unsigned int clv_index)
 {

@@ -1094,7 +1094,7 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
                              const int * edge4, unsigned int rate_cats, int * edge_out,
                              unsigned char * unstored_out = nullptr, unsigned char * folded_out = nullptr,
                              unsigned int * gathers_out = nullptr, unsigned int * batch_out = nullptr,
-                             unsigned int * nbatches_out = nullptr)
+                             unsigned int * nbatches_out = nullptr, int * kinds_out = nullptr)
 {
   FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
   if (dry_ops_in_range("pllhip_fused_plan_dry_deferred", geom, ops, count)) return -1;
@@ -1224,6 +1224,13 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
         operands_out[2 * pos + t] = w.replanned && w.fl.as_tip[kid[t]] && !geom.is_tip(kid[t]) ? 3 : opnd[2 * o + t];
     }
     if (slots_out) dry_slots_out(f, slots_out + (size_t)pos * 6);
+    // (pllhip_fused_plan_dry_quads: the kind the kernel runs and the folded products on its two sides)
+    if (kinds_out)
+    {
+      kinds_out[3 * pos] = f.kind;
+      kinds_out[3 * pos + 1] = f.prod[0];
+      kinds_out[3 * pos + 2] = f.prod[1];
+    }
   }
   if (reloads_out) *reloads_out = w.plan.reloads;
   if (gathers_out)
@@ -1284,6 +1291,105 @@ extern "C" int pllhip_fused_plan_dry_rows(unsigned int tips, unsigned int clv_bu
   return plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, nslots, nullptr, nullptr, nullptr, nkept,
                            order_out, nullptr, nullptr, deferred_out, nullptr, nullptr, nullptr, nullptr, nullptr,
                            nullptr, rate_cats, edge_out, unstored.data(), folded_out, gathers_out, batch_out, nbatches_out);
+}
+
+// Which folded products are read as quads (quad_rows.hip; tests/test_host_quad_rows.py): the final walk of
+// pllhip_fused_plan_dry_rows, then the rule the live path applies (pllhip_fused_quad_decide) -- to a partition of `sites`
+// sites with quad rows `quads_on` at `min_sites_per_class`.  What the live path finds on the device or in the context is
+// handed in per op of the caller's list, read where the op is a folded product: classes[i] the class count of its quad
+// row (0: beyond the cap), bounds[i] the lower bound the host can prove for its table (NULL or <= 0: none).
+// ops_out[3 pos ..]: walked op pos's kind, its gathers and how many of them are wide.  quads_out[i]: -1 where op i is no
+// folded product, else the rule's answer (0: read as a quad; else the reason, pllhip.h).  counts_out[2]: quads taken,
+// and refused (of the products over two cherries, as pllhip_quad_row_stats counts them).
+extern "C" int pllhip_fused_plan_dry_quads(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                           int pattern_tip, unsigned int rate_cats, int rate_scalers, const pllhip_op_t * ops,
+                                           unsigned int count, unsigned int nslots, const unsigned char * pinned, const int * edge4,
+                                           unsigned int sites, int quads_on, unsigned int min_sites_per_class,
+                                           const unsigned int * classes, const double * bounds, unsigned int * nkept,
+                                           unsigned int * order_out, unsigned char * folded_out, int * ops_out, int * quads_out,
+                                           unsigned int * counts_out)
+{
+  if (!(rate_cats == 1 || rate_cats == 2 || rate_cats == 4) || !classes || !nkept || !order_out || !folded_out || !ops_out || !quads_out ||
+      !counts_out)
+  {
+    pllhip_set_error("pllhip_fused_plan_dry_quads: rate_cats of an instance that defers, and every output");
+    return -1;
+  }
+  int edge_out[8];
+  std::vector<unsigned char> unstored(count, 0), deferred(count, 0);
+  std::vector<unsigned int> gathers(12 * (size_t)count + 12, 0u);
+  std::vector<int> kinds(3 * (size_t)count + 3, 0);
+  const int rc = plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, nslots, nullptr, nullptr, pinned, nkept,
+                                   order_out, nullptr, nullptr, deferred.data(), nullptr, nullptr, nullptr, nullptr, nullptr, edge4,
+                                   rate_cats, edge_out, unstored.data(), folded_out, gathers.data(), nullptr, nullptr, kinds.data());
+  if (rc) return rc;
+  for (unsigned int i = 0; i < count; ++i) quads_out[i] = -1;
+  counts_out[0] = counts_out[1] = 0;
+  // the tips under a child of a folded op: itself, or the two of the cherry this list defers
+  auto tips_of = [&](unsigned int clv, unsigned int (&t)[2]) {
+    t[0] = t[1] = 0;
+    if (clv < tips) { t[0] = clv + 1; return; }
+    for (unsigned int i = 0; i < count; ++i)
+      if (deferred[i] && ops[i].parent_clv == clv) { t[0] = ops[i].child1_clv + 1; t[1] = ops[i].child2_clv + 1; }
+  };
+  std::vector<FusedQuadCand> cands;
+  std::vector<unsigned int> op_of;
+  for (unsigned int pos = 0; pos < *nkept; ++pos)
+  {
+    const pllhip_op_t & reader = ops[order_out[pos]];
+    const unsigned int * g = &gathers[12 * (size_t)pos];
+    for (int s = 0; s < 2; ++s)
+    {
+      const int prod = kinds[3 * pos + 1 + s];
+      if (!prod) continue;
+      // the folded op on this side: the child of the reader whose factors' rows the side's two gathers name
+      unsigned int found = count;
+      for (unsigned int j = 0; j < count && found == count; ++j)
+      {
+        if (!folded_out[j] || (ops[j].parent_clv != reader.child1_clv && ops[j].parent_clv != reader.child2_clv)) continue;
+        unsigned int a[2], b[2];
+        tips_of(ops[j].child1_clv, a);
+        tips_of(ops[j].child2_clv, b);
+        const unsigned int * ga = g + 6 * s, * gb = g + 6 * s + 3;
+        auto same = [](const unsigned int (&t)[2], const unsigned int * r) {
+          return (t[0] == r[0] && t[1] == r[1]) || (t[1] == 0 && r[0] == 0 && t[0] == r[1]);
+        };
+        if ((same(a, ga) && same(b, gb)) || (same(b, ga) && same(a, gb))) found = j;
+      }
+      if (found == count)
+      {
+        pllhip_set_error("pllhip_fused_plan_dry_quads: op %u's folded operand is not in the list", order_out[pos]);
+        return -1;
+      }
+      const bool cherries = g[6 * s] && g[6 * s + 1] && g[6 * s + 3] && g[6 * s + 4];
+      cands.push_back(FusedQuadCand{0u, pos, s, kinds[3 * pos + 1] && kinds[3 * pos + 2], cherries, classes[found], (prod & 2) != 0,
+                                    bounds ? bounds[found] : 0.0, 0});
+      op_of.push_back(found);
+    }
+  }
+  const bool instance = quads_on && pattern_tip && rate_cats <= 4 && !rate_scalers;
+  counts_out[0] = pllhip_fused_quad_decide(cands.data(), cands.size(), instance, sites, min_sites_per_class ? min_sites_per_class : 64u);
+  std::vector<unsigned char> taken(2 * (size_t)*nkept + 2, 0);
+  for (size_t i = 0; i < cands.size(); ++i)
+  {
+    quads_out[op_of[i]] = cands[i].reason;
+    taken[2 * (size_t)cands[i].pos + cands[i].side] = cands[i].reason == FUSED_QUAD_TAKEN;
+    counts_out[1] += cands[i].cherries && cands[i].reason != FUSED_QUAD_TAKEN;
+  }
+  for (unsigned int pos = 0; pos < *nkept; ++pos)
+  {
+    const unsigned int * g = &gathers[12 * (size_t)pos];
+    int ng = 0, wide = 0;
+    if (taken[2 * pos] || taken[2 * pos + 1])
+      // (a reader of quads: one wide gather per product -- both, or the only one)
+      ng = wide = (kinds[3 * pos + 1] != 0) + (kinds[3 * pos + 2] != 0);
+    else
+      for (int k = 0; k < 4; ++k) ng += g[3 * k] || g[3 * k + 1];
+    ops_out[3 * pos] = kinds[3 * pos];
+    ops_out[3 * pos + 1] = ng;
+    ops_out[3 * pos + 2] = wide;
+  }
+  return 0;
 }
 
 extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,

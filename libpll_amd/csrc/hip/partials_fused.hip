@@ -65,6 +65,7 @@
 #include <algorithm>
 #include <stdio.h>
 #include <stdlib.h>
+#include <type_traits>
 #include <vector>
 
 #include "ctx.hpp"
@@ -120,6 +121,67 @@ __device__ __forceinline__ unsigned int rec_lcnt(const Rec & r) { return r.w[14]
 __device__ __forceinline__ unsigned int rec_rcnt(const Rec & r) { return r.w[14] >> 16; }
 __device__ __forceinline__ unsigned int rec_pcnt(const Rec & r) { return r.w[15] & 0xffffu; }
 
+// Quad rows (quad_rows.hip): the factor a reader with matrix P takes from a folded pair product over
+// two cherries, one entry per CLASS of the quad's row: F4[class][rate][s] = dot4(P[rate][s], T4[rate][.]), T4[rate][k] =
+// Fa[pa][rate][k] * Fb[pb][rate][k] -- (pa, pb) the class's pattern; Fa, Fb the two cherries' factors as the jobs of
+// kind 2 / 3 below form them, the multiplication the list kernel's product() does, the dot product its pl.dot() /
+// pr.dot().  Self-contained like kind 2: every factor is formed here from the matrices (or the kept table).  The job
+// takes two records: this one {lmat, rmat: cherry a's tip matrices, pmat: P, kept: the patterns, pad: the classes} and
+// the next, kind 5 {lmat, rmat: cherry b's, pmat / kept: the matrices Fa / Fb are read with, copy / pad: the kept
+// tables of a / b where they were deferred by an earlier call, else null}.
+// A launch of its own behind k_dna_pair_tables, made only for a list that reads a quad: the lists without one keep
+// their table launch as it was, registers and all.  One thread per (rate, state) of a class, PLLHIP_QUAD_TABLE_WGS
+// workgroups per job over the same job array; a workgroup of any other job ends at once.
+constexpr unsigned int PLLHIP_QUAD_TABLE_WGS = 16;
+template <int RC>
+__global__ __launch_bounds__(256) void k_dna_quad_tables(const FusedPairJob * __restrict__ jobs, unsigned int njobs)
+{
+  const unsigned int i = blockIdx.x / PLLHIP_QUAD_TABLE_WGS, part = blockIdx.x % PLLHIP_QUAD_TABLE_WGS;
+  if (i + 1 >= njobs || jobs[i].kind != 4) return;
+  constexpr unsigned int ROW = RC * 4u, PER = 256u / ROW;
+  const unsigned int ki = threadIdx.x % ROW, sub = threadIdx.x / ROW, rate4 = (ki >> 2) * 4u;
+  const FusedPairJob & ja = jobs[i], & jb = jobs[i + 1];
+  const PLL_GLOBAL double * pm = (const PLL_GLOBAL double *)ja.pmat;
+  const PLL_GLOBAL unsigned short * patterns = (const PLL_GLOBAL unsigned short *)ja.kept;
+  const unsigned int n = (unsigned int)ja.pad;
+  const PLL_GLOBAL double * side_l[2] = {(const PLL_GLOBAL double *)ja.lmat, (const PLL_GLOBAL double *)jb.lmat};
+  const PLL_GLOBAL double * side_r[2] = {(const PLL_GLOBAL double *)ja.rmat, (const PLL_GLOBAL double *)jb.rmat};
+  const PLL_GLOBAL double * side_p[2] = {(const PLL_GLOBAL double *)jb.pmat, (const PLL_GLOBAL double *)jb.kept};
+  const PLL_GLOBAL double * side_kept[2] = {(const PLL_GLOBAL double *)jb.copy, (const PLL_GLOBAL double *)jb.pad};
+  double * tab = ja.tab;
+  double p[4], pf[2][4][4], l[2][4][4], r[2][4][4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) p[k] = pm[ki * 4u + k];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+      {
+        pf[s][k][m] = side_p[s][(rate4 + k) * 4u + m];
+        l[s][k][m] = side_kept[s] ? 0.0 : side_l[s][(rate4 + k) * 4u + m];
+        r[s][k][m] = side_kept[s] ? 0.0 : side_r[s][(rate4 + k) * 4u + m];
+      }
+  for (unsigned int cls = part * PER + sub; cls < n; cls += PLLHIP_QUAD_TABLE_WGS * PER)
+  {
+    const unsigned int pattern = patterns[cls];
+    double f[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+    {
+      const unsigned int pair = s == 0 ? pattern >> 8 : pattern & 255u, c1 = pair >> 4, c2 = pair & 15u;
+      double t[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        t[k] = side_kept[s] ? side_kept[s][pair * ROW + rate4 + k] : masksum4(l[s][k], c1) * masksum4(r[s][k], c2);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) f[s][k] = dot4(pf[s][k], t[0], t[1], t[2], t[3]);
+    }
+    tab[cls * ROW + ki] = dot4(p, f[0][0] * f[1][0], f[0][1] * f[1][1], f[0][2] * f[1][2], f[0][3] * f[1][3]);
+  }
+}
+
 // Tip operands: the parent entry of a tip-tip op depends on its two tip characters only, 16 x 16
 // pairs.  One table per op with a tip, [pair][rate][state] = masksum4(P_l row, code 1) *
 // masksum4(P_r row, code 2) -- the very product the kernel would form per site (30 VALU
@@ -140,6 +202,8 @@ __global__ __launch_bounds__(256) void k_dna_pair_tables(const FusedPairJob * __
   const unsigned int i = blockIdx.x >> 2, quarter = blockIdx.x & 3u;
   if (blockIdx.x == 0 && tile_counters) tile_counters[threadIdx.x * 32u] = 0u;
   if (i >= njobs) return;
+  // (kinds 4 and 5, a quad's table: k_dna_quad_tables above)
+  if (jobs[i].kind >= 4) return;
   // Deferred cherries: the factor a READER with matrix P takes from a cherry that is not stored,
   // F[c1][c2][rate][s] = dot4(P[rate][s], T[c1][c2][rate][.]) -- the bits pl.dot() / pr.dot() of the list kernel give
   // from the stored cherry (separate products, (x0 + x1) + (x2 + x3); a lane with h = 1 adds the two halves the other
@@ -460,34 +524,64 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     // destination registers (seen once: the arrays kept as one transposed 8-register value and re-packed right behind
     // the loads, until both ends of their life were made whole 16-byte operands of an empty asm statement).
     constexpr bool SECOND = RC <= 4 && MODE != SCALE_RATE; // (partials.hip: what may defer a cherry; checked by the launch)
-    auto gather_factor = [&](pll_v2d (&pt)[J], unsigned int ch, unsigned int table_off) {
+    constexpr unsigned int TB = 256u * W * 16u; // bytes of a table
+    auto gather_factor = [&](pll_v2d (&pt)[J], unsigned int ch, unsigned int table_off, auto may_be_wide, bool displaced) {
       // (ONE row per factor: a cherry's cached pair row, whose bytes already are the table's index -- pair_rows.hip --, or
       // a single tip's row, masked and shifted to its place in scalar registers, four characters at a time; a lane then
       // picks its word and byte: pllhip_fused_row_index, partials_fused.hpp; then one shift-add)
       const unsigned int mask = (ch & PLLHIP_FUSED_CH_NIBBLE) ? 0x0f0f0f0fu : 0xffffffffu;
       const unsigned int shift = (ch / (PLLHIP_FUSED_CH_SHIFT4 / 4u)) & 4u;
       const unsigned long long tab = (unsigned long long)(uintptr_t)bases.pairtab + table_off; // (uniform)
+      // The WIDE form (quad rows, quad_rows.hip; only an op's first two gathers: a reader of quads has no more): the row
+      // holds a 16-bit class per site -- two lane positions per granule of a byte row, pllhip_quad_word_lane --, the table
+      // one entry per class and may be several tables long: a second gather finds its own behind the first's, displaced
+      // by the tables the word's top byte counts.  The same words-then-pick on the scalar side; the two forms differ in
+      // the OFFSET only, an ordinary lane value -- the load is ONE statement for both, so that the gathered registers
+      // have one writer per sub-step and nothing to merge behind it (see gather() below, point 1).
+      bool wide = false;
+      unsigned long long base = tab;
+      if constexpr (SECOND && decltype(may_be_wide)::value)
+      {
+        wide = (ch & PLLHIP_FUSED_CH_WIDE) != 0u;
+        if (wide && displaced) base = tab + (unsigned long long)(ch >> 24) * TB;
+      }
 #pragma unroll
       for (unsigned int j = 0; j < J; ++j)
       {
-        unsigned int w[SPS / 4];
-        row_words(PLLHIP_FUSED_CH_LPOS(ch), j, w);
-        const unsigned int pair = pllhip_fused_row_index<SPS>(w, mask, shift, tip_lane);
-        const unsigned int off = pair * (W * 16u) + gat_lane;
-        asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pt[j]) : "v"(off), "s"(tab) : "memory");
+        unsigned int off;
+        if (wide)
+        {
+          constexpr unsigned int LPR = TS >= 16 ? TS / 16 : 1;
+          const unsigned int pos = PLLHIP_FUSED_CH_LPOS(ch);
+          unsigned int w[SPS / 2];
+#pragma unroll
+          for (unsigned int m = 0; m < SPS / 2; ++m)
+          {
+            const unsigned int wl = pllhip_quad_word_of_lane<SPS>(j, m);
+            const unsigned int v = wl == 0 ? cs.x : wl == 1 ? cs.y : wl == 2 ? cs.z : cs.w;
+            w[m] = (unsigned int)__builtin_amdgcn_readlane((int)v, (int)(pos + pllhip_quad_word_lane<SPS>(j, m, LPR)));
+          }
+          off = pllhip_quad_pick<SPS>(w, tip_lane) * (W * 16u) + gat_lane;
+        }
+        else
+        {
+          unsigned int w[SPS / 4];
+          row_words(PLLHIP_FUSED_CH_LPOS(ch), j, w);
+          off = pllhip_fused_row_index<SPS>(w, mask, shift, tip_lane) * (W * 16u) + gat_lane;
+        }
+        asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pt[j]) : "v"(off), "s"(base) : "memory");
       }
     };
     // (the tables of one op follow each other in the table buffer: gather k reads k tables behind the first; a third
     // and a fourth factor -- a right-hand operand that is a folded product, see step() -- always come together)
-    constexpr unsigned int TB = 256u * W * 16u; // bytes of a table
     auto gather = [&](pll_v2d (&pt)[J], pll_v2d (&pt2)[J], pll_v2d (&pt3)[J], pll_v2d (&pt4)[J], const Rec & r) {
       const unsigned int ch = rec_chars(r), ch2 = rec_chars2(r);
-      if (ch & PLLHIP_FUSED_CH_LTIP) gather_factor(pt, ch, rec_gather(r));
-      if (SECOND && (ch2 & PLLHIP_FUSED_CH_LTIP)) gather_factor(pt2, ch2, rec_gather(r) + TB);
+      if (ch & PLLHIP_FUSED_CH_LTIP) gather_factor(pt, ch, rec_gather(r), std::true_type(), false);
+      if (SECOND && (ch2 & PLLHIP_FUSED_CH_LTIP)) gather_factor(pt2, ch2, rec_gather(r) + TB, std::true_type(), true);
       if (SECOND && (rec_chars3(r) & PLLHIP_FUSED_CH_LTIP))
       {
-        gather_factor(pt3, rec_chars3(r), rec_gather(r) + 2u * TB);
-        gather_factor(pt4, rec_chars4(r), rec_gather(r) + 3u * TB);
+        gather_factor(pt3, rec_chars3(r), rec_gather(r) + 2u * TB, std::false_type(), false);
+        gather_factor(pt4, rec_chars4(r), rec_gather(r) + 3u * TB, std::false_type(), false);
       }
       // the list moves on to rows this batch does not hold (rare: every 1024 / TS tip operands): the lanes'
       // addresses of the next batch, then its rows.  Assembly, like reload(): the compiler counts no load
@@ -1054,11 +1148,27 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
 // kind says -- the tip of a tip-inner op, the finished parent of a tip-tip op.  Up to four per op, in the order the
 // kernel gathers them: one or two factors of the op itself, or the two factors of a folded product on the left, then
 // those of one on the right.  copy: where a factor table is written as well (the pool: an unstored or folded product's).
+// A product side read as a QUAD (quad_rows.hip): ONE wide gather from a table of one entry per class of the quad's row,
+// `units` tables long, in place of the product's two.  Decided by the launch (fused_pick_quads), after the plan.
+struct FusedQuadSide
+{
+  bool taken = false;
+  QuadRowRef ref;
+  unsigned int units = 0;
+};
+typedef std::vector<FusedQuadSide> FusedQuadMarks; // two per position of a plan: its sides
 struct FusedGatherSets
 {
   FusedOperand g[4];
   double * copy[4];
+  // g[k] is a quad (type FUSED_G_QUAD; `mat` the reader's matrix on that side): its mark, and the product's two
+  // factors, whose tables are still written into the pool -- jobs with no reader in this launch (deferred.hip
+  // materialises from them)
+  const FusedQuadSide * quad[2];
+  FusedOperand qa[2], qb[2];
+  double * qkeep[2][2];
 };
+enum { FUSED_G_QUAD = 5 };
 // One segment's gathers and where a wave finds their tip characters: rows in the order the segment uses them, in
 // batches of what a wave's 64 x 16 bytes hold of a tile (pllhip_fused_char_batches), numbered across the segments.
 struct FusedSegGathers
@@ -1088,7 +1198,7 @@ static unsigned int fused_lanes_per_row(unsigned int R)
 // for an op that is not what the planner makes (a malformed product or unstored op, gathers with a gap) or rows the
 // kernel cannot address: more than 255 batches, a row beyond lane 63.
 static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, bool rate_scalers, unsigned int batch0,
-                             size_t * ntables, FusedSegGathers & out)
+                             size_t * ntables, FusedSegGathers & out, const FusedQuadMarks * quads)
 {
   const unsigned int n = (unsigned int)plan.size(), lpr = fused_lanes_per_row(R);
   out.gx.resize(n);
@@ -1104,9 +1214,24 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
     {
       // (only what the planner folds: an inner-inner reader, presented as gathered-inner or gathered-gathered)
       if (!f.prod[0] || (f.kind != 1 && f.kind != 3) || (f.kind == 3) != (f.prod[1] != 0) || f.unstored) return 1;
+      // (quads: every product side of the op, or none -- a reader of a quad and a plain product is not built)
+      const bool quad = quads && (*quads)[2 * (size_t)pos].taken && (!f.prod[1] || (*quads)[2 * (size_t)pos + 1].taken);
       for (int s = 0; s < (f.prod[1] ? 2 : 1); ++s)
       {
         if (f.g[s].type == FUSED_G_NONE || f.g2[s].type == FUSED_G_NONE || !f.pkeep[s][0] || !f.pkeep[s][1]) return 1;
+        if (quad)
+        {
+          memset(&x.g[s], 0, sizeof(x.g[s]));
+          x.g[s].type = FUSED_G_QUAD;
+          x.g[s].mat = s == 0 ? f.lmat : f.rmat;
+          x.quad[s] = &(*quads)[2 * (size_t)pos + s];
+          x.g[s].row = x.quad[s]->ref.row;
+          x.qa[s] = f.g[s];
+          x.qb[s] = f.g2[s];
+          x.qkeep[s][0] = f.pkeep[s][0];
+          x.qkeep[s][1] = f.pkeep[s][1];
+          continue;
+        }
         x.g[2 * s] = f.g[s];
         x.g[2 * s + 1] = f.g2[s];
         x.copy[2 * s] = f.pkeep[s][0];
@@ -1130,7 +1255,9 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
   std::vector<unsigned int> ntips(n, 0);
   for (unsigned int pos = 0; pos < n; ++pos)
     for (int k = 0; k < 4; ++k)
-      ntips[pos] |= pllhip_fused_gather_rows(out.gx[pos].g[k].row1 != nullptr, out.gx[pos].g[k].row2 != nullptr) << (2 * k);
+      // (a quad row is two planes: two rows of the batch, one behind the other)
+      ntips[pos] |= (out.gx[pos].g[k].type == FUSED_G_QUAD ? 3u : pllhip_fused_gather_rows(out.gx[pos].g[k].row1 != nullptr, out.gx[pos].g[k].row2 != nullptr))
+                    << (2 * k);
   unsigned int * const chars_out[4] = {out.chars_of[0].data(), out.chars_of[1].data(), out.chars_of[2].data(), out.chars_of[3].data()};
   out.nbatches = pllhip_fused_char_batches8(ntips.data(), n, lpr, chars_out, out.batch_of.data());
   if (batch0 + out.nbatches > 255 || 8 * lpr > 64) return 1;
@@ -1138,13 +1265,29 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
   {
     out.batch_of[pos] += batch0;
     if (out.gx[pos].g[0].type != FUSED_G_NONE) out.table_of[pos] = (unsigned int)(*ntables * fused_table_doubles(R) * sizeof(double));
+    unsigned int first_units = 1;
     for (int k = 0; k < 4; ++k)
     {
       const FusedOperand & g = out.gx[pos].g[k];
+      if (g.type == FUSED_G_QUAD)
+      {
+        // (the wide form: one row position, the planes lpr lanes apart; a second gather's table lies behind ALL of the
+        // first's tables -- the word's top byte says how many more than one)
+        const unsigned int units = out.gx[pos].quad[k]->units;
+        if (k == 0) first_units = units;
+        *ntables += units;
+        unsigned int & ch = out.chars_of[k][pos];
+        ch = (ch & ~(PLLHIP_FUSED_CH_RTIP | 0xff00u)) | PLLHIP_FUSED_CH_WIDE | (k == 1 ? (first_units - 1u) << 24 : 0u);
+        if (PLLHIP_FUSED_CH_LPOS(ch) + 2 * lpr > 64) return 1;
+        continue;
+      }
       *ntables += g.type != FUSED_G_NONE;
       out.chars_of[k][pos] |= pllhip_fused_gather_bits(g.row1 != nullptr, g.row2 != nullptr);
       if ((g.row1 || g.row2) && PLLHIP_FUSED_CH_LPOS(out.chars_of[k][pos]) + lpr > 64) return 1;
     }
+    // (the tables of a quad's two factors, written for the pool's sake: behind the op's own)
+    for (int s = 0; s < 2; ++s)
+      if (out.gx[pos].quad[s]) *ntables += 2;
   }
   return 0;
 }
@@ -1152,7 +1295,7 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
 // (a) Admission: is this a list the kernel takes?  No HIP call, nothing of the context changed: returns 1 for every
 // shape the kernel or its records do not take, else 0 and what the encoder needs of the plans.
 static int fused_admit(const pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
-                       const FusedEdge * edge, FusedAdmitted & out)
+                       const FusedEdge * edge, FusedAdmitted & out, const std::vector<FusedQuadMarks> * quads = nullptr)
 {
   const unsigned int nsegs = (unsigned int)plans.size(), R = c->sh.rate_cats;
   const bool rate_scalers = c->sh.rate_scalers != 0;
@@ -1185,10 +1328,13 @@ static int fused_admit(const pllhip_ctx * c, const std::vector<std::vector<Fused
   size_t ngathers = 0;
   for (unsigned int sg = 0; sg < nsegs; ++sg)
   {
-    if (fused_seg_gathers(plans[sg], R, rate_scalers, batch0, &ngathers, out.segs[sg])) return 1;
+    if (fused_seg_gathers(plans[sg], R, rate_scalers, batch0, &ngathers, out.segs[sg], quads ? &(*quads)[sg] : nullptr)) return 1;
     batch0 += out.segs[sg].nbatches;
   }
-  return ngathers > out.ntab ? 1 : 0;
+  if (!quads) return ngathers > out.ntab ? 1 : 0;
+  // (quads: their tables are as long as their rows have classes -- counted by the gathers themselves)
+  out.ntab = ngathers;
+  return out.ntab * fused_table_doubles(R) * sizeof(double) > 0xffffffffull ? 1 : 0;
 }
 
 // (b) The encoder: no HIP call either, every address it needs in FusedEncodeIn.
@@ -1200,6 +1346,7 @@ struct FusedEncodeIn
   FusedSlotSize slot;
   unsigned int rate_cats;
   bool rate_scalers;
+  size_t tip_stride;              // bytes between the two planes of a quad row
 };
 // The plans as the device reads them (FusedRec in partials_fused.hpp) -- per segment two header records that stand for
 // ops -2 and -1, one record per op, one of padding (the last op's look-ahead load) -- then the segment table, the
@@ -1213,6 +1360,7 @@ struct FusedEncoded
   std::vector<unsigned long long> rowtab; // [batch][lane]: the address the lane fetches from (+ the tile's first site)
   int mode = SCALE_NONE;
   unsigned int longest = 0;
+  size_t units = 0;                       // tables handed out so far (a quad's table takes several)
 };
 // what record `r` says about the ops ahead of position `pos` (pos may be -2, -1: the headers)
 static void fused_look_ahead(const FusedEncodeIn & in, const std::vector<FusedOp> & plan, const FusedSegGathers & ga,
@@ -1245,7 +1393,9 @@ static void fused_look_ahead(const FusedEncodeIn & in, const std::vector<FusedOp
   const FusedOp & f = pos + 1 < n ? plan[pos + 1] : edge->op;
   r.gather_off = pos + 1 < n ? ga.table_of[pos + 1] : 0u;
   // (a reader of folded products runs as an inner-inner op: both matrices)
-  r.flags |= (f.kind == 0 || f.prod[0] ? 2u : (f.kind == 1 || f.kind == PLLHIP_FUSED_KIND_EDGE) ? 1u : 0u) << PLLHIP_FUSED_STAGE_SHIFT;
+  // (... unless its products are quads: a gathered operand needs no matrix)
+  const bool quad = pos + 1 < n && ga.gx[pos + 1].quad[0] != nullptr;
+  r.flags |= (f.kind == 0 || (f.prod[0] && !quad) ? 2u : (f.kind == 1 || f.kind == PLLHIP_FUSED_KIND_EDGE) ? 1u : 0u) << PLLHIP_FUSED_STAGE_SHIFT;
   if (!f.dma_flags) return;
   r.flags |= PLLHIP_FUSED_RELOAD_NEXT;
   r.src = (unsigned short)srcs.size();
@@ -1261,11 +1411,13 @@ static void fused_look_ahead(const FusedEncodeIn & in, const std::vector<FusedOp
 }
 
 // the record of op f itself (its look-ahead part: fused_look_ahead)
-static void fused_fill_record(const FusedEncodeIn & in, const FusedOp & f, FusedRec & r)
+static void fused_fill_record(const FusedEncodeIn & in, const FusedOp & f, FusedRec & r, bool quad)
 {
   const unsigned int slot_bytes = in.slot.tile_bytes, count_bytes = in.slot.count_bytes;
   r.flags = (unsigned int)f.kind & PLLHIP_FUSED_KIND_MASK;
-  if (f.prod[0])
+  // (products read as quads: the op is what the planner took it for, gathered-inner or gathered-gathered -- the factor
+  // holds the reader's matrix already, and a gathered operand brings no count: the quad's rule made sure it has none)
+  if (f.prod[0] && !quad)
   {
     // folded products: the kernel's inner-inner arithmetic, that side's operand formed from the gathered factors;
     // the count inherited on that side is the product's own scale bit, where the reader passes its scale buffer
@@ -1308,12 +1460,42 @@ static void fused_encode_segment(const FusedEncodeIn & in, const std::vector<Fus
       const unsigned int lane0 = PLLHIP_FUSED_CH_LPOS(ga.chars_of[k][pos]);
       for (unsigned int l = 0; g.row && l < lpr; ++l)
         out.rowtab[(size_t)ga.batch_of[pos] * 64 + lane0 + l] = (unsigned long long)(uintptr_t)g.row + l * 16u;
-      double * tab = in.pairtab + out.jobs.size() * per;
+      double * tab = in.pairtab + out.units * per;
+      if (g.type == FUSED_G_QUAD)
+      {
+        // (plane 1 of the row: the next lpr lanes; the table job and its second record: k_dna_pair_tables, kind 4)
+        const FusedQuadSide & q = *ga.gx[pos].quad[k];
+        const FusedOperand & a = ga.gx[pos].qa[k], & b = ga.gx[pos].qb[k];
+        for (unsigned int l = 0; l < lpr; ++l)
+          out.rowtab[(size_t)ga.batch_of[pos] * 64 + lane0 + lpr + l] = (unsigned long long)(uintptr_t)g.row + in.tip_stride + l * 16u;
+        out.jobs.push_back(FusedPairJob{a.c_lmat, a.c_rmat, tab, 4ull, g.mat, (const double *)q.ref.patterns, nullptr, (unsigned long long)q.ref.n});
+        out.jobs.push_back(FusedPairJob{b.c_lmat, b.c_rmat, nullptr, 5ull, a.mat, b.mat,
+                                        a.type == FUSED_G_CHERRY_KEPT ? const_cast<double *>(a.kept) : nullptr,
+                                        b.type == FUSED_G_CHERRY_KEPT ? (unsigned long long)(uintptr_t)b.kept : 0ull});
+        out.units += q.units;
+        continue;
+      }
+      out.units += 1;
       double * copy = ga.gx[pos].copy[k];
       if (g.type == FUSED_G_TIP) out.jobs.push_back(FusedPairJob{g.mat, nullptr, tab, 0ull, nullptr, nullptr, copy, 0ull});
       else if (g.type == FUSED_G_PAIR) out.jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 1ull, nullptr, nullptr, copy, 0ull});
       else if (g.type == FUSED_G_CHERRY_NEW) out.jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 2ull, g.mat, nullptr, copy, 0ull});
       else out.jobs.push_back(FusedPairJob{nullptr, nullptr, tab, 3ull, g.mat, g.kept, copy, 0ull});
+    }
+    // (a quad's two factor tables, as the product's gathers would have had them written: into the pool, which
+    // deferred.hip materialises the folded parent from -- and into a table of this launch that nothing reads)
+    for (int s = 0; s < 2; ++s)
+    {
+      if (!ga.gx[pos].quad[s]) continue;
+      const FusedOperand * const ab[2] = {&ga.gx[pos].qa[s], &ga.gx[pos].qb[s]};
+      for (int t = 0; t < 2; ++t)
+      {
+        const FusedOperand & g = *ab[t];
+        double * tab = in.pairtab + out.units * per;
+        out.units += 1;
+        if (g.type == FUSED_G_CHERRY_NEW) out.jobs.push_back(FusedPairJob{g.c_lmat, g.c_rmat, tab, 2ull, g.mat, nullptr, ga.gx[pos].qkeep[s][t], 0ull});
+        else out.jobs.push_back(FusedPairJob{nullptr, nullptr, tab, 3ull, g.mat, g.kept, ga.gx[pos].qkeep[s][t], 0ull});
+      }
     }
     // every op with a parent scaler scales the partition's way (and so does a folded product's test)
     if (f.pscaler || (f.prod[0] & 2) || (f.prod[1] & 2)) out.mode = in.rate_scalers ? SCALE_RATE : SCALE_SITE;
@@ -1327,7 +1509,7 @@ static void fused_encode_segment(const FusedEncodeIn & in, const std::vector<Fus
   fused_look_ahead(in, plan, ga, edge, rs[1], -1, out.srcs);
   for (unsigned int pos = 0; pos < n; ++pos)
   {
-    fused_fill_record(in, plan[pos], rs[pos + 2]);
+    fused_fill_record(in, plan[pos], rs[pos + 2], ga.gx[pos].quad[0] != nullptr);
     fused_look_ahead(in, plan, ga, edge, rs[pos + 2], (long)pos, out.srcs);
   }
   rs[n + 2] = rs[n + 1]; // (loaded by the last op, never used)
@@ -1400,6 +1582,11 @@ static int fused_upload(pllhip_ctx * c, const FusedEncoded & enc)
   c->fused_last_jobs_offset = jobs_at;
   c->fused_last_rowtab_offset = rowtab_at;
   c->fused_last_jobs = (unsigned int)enc.jobs.size();
+  c->fused_last_quad_jobs = 0;
+  for (const FusedPairJob & j : enc.jobs) c->fused_last_quad_jobs += j.kind == 4;
+  // (one wide gather per quad: pllhip_quad_list_stats)
+  c->quad_list_stats[0] = c->quad_list_stats[1] = c->fused_last_quad_jobs;
+  c->quad_list_stats[2] += c->fused_last_quad_jobs;
   c->fused_last_longest = enc.longest;
   c->fused_last_nsegs = (unsigned int)enc.segs.size();
   c->fused_last_mode = enc.mode;
@@ -1449,7 +1636,7 @@ static int fused_name_rows(pllhip_ctx * c, FusedAdmitted & adm)
     for (FusedGatherSets & x : sg.gx)
       for (FusedOperand & g : x.g)
       {
-        if (g.type == FUSED_G_NONE) continue;
+        if (g.type == FUSED_G_NONE || g.type == FUSED_G_QUAD) continue; // (a quad's row: fused_pick_quads)
         g.row = g.row1 ? g.row1 : g.row2;
         if (!g.row1 || !g.row2) continue;
         need.push_back(std::make_pair(tip_of(g.row1), tip_of(g.row2)));
@@ -1462,6 +1649,94 @@ static int fused_name_rows(pllhip_ctx * c, FusedAdmitted & adm)
   return 0;
 }
 
+// Which product sides of the admitted plans are quads (partials_fused.hpp: pllhip_fused_quad_rule).  Returns 1 where
+// any is taken (marks: per segment, two per position), 0 where none, else an error.  mats: the matrices whose host
+// bounds the taken quads stand on; *by_bound: quads refused for want of a bound.
+static int fused_pick_quads(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, std::vector<FusedQuadMarks> & marks,
+                            std::vector<unsigned int> & mats, unsigned int * by_bound)
+{
+  *by_bound = 0;
+  const bool instance = c->quad_rows_on && c->sh.pattern_tip && c->sh.rate_cats <= 4 && !c->sh.rate_scalers && c->tipchars;
+  if (!instance) return 0;
+  auto cherry = [](const FusedOperand & g) {
+    return (g.type == FUSED_G_CHERRY_NEW || g.type == FUSED_G_CHERRY_KEPT) && g.row1 && g.row2;
+  };
+  auto tip_of = [&](const unsigned char * row) { return (unsigned int)((size_t)(row - c->tipchars) / c->tip_stride); };
+  // (a class is at least one site: below min_sites_per_class sites no quad can be taken, and none is counted or kept)
+  if (c->sh.sites < c->quad_min_sites_per_class) return 0;
+  std::vector<FusedQuadCand> cands;
+  std::vector<QuadKey> keys;
+  std::vector<int> key_of;
+  for (unsigned int sg = 0; sg < plans.size(); ++sg)
+    for (unsigned int pos = 0; pos < plans[sg].size(); ++pos)
+      for (int s = 0; s < 2; ++s)
+      {
+        const FusedOp & f = plans[sg][pos];
+        if (!f.prod[s]) continue;
+        const bool ch = cherry(f.g[s]) && cherry(f.g2[s]);
+        cands.push_back(FusedQuadCand{sg, pos, s, f.prod[0] && f.prod[1], ch, 0u, (f.prod[s] & 2) != 0, 0.0, 0});
+        key_of.push_back(ch ? (int)keys.size() : -1);
+        if (ch) keys.push_back(QuadKey{{tip_of(f.g[s].row1), tip_of(f.g[s].row2), tip_of(f.g2[s].row1), tip_of(f.g2[s].row2)}});
+      }
+  if (keys.empty()) return 0;
+  std::vector<QuadRowRef> refs;
+  const int rc = pllhip_quad_rows_resolve(c, keys, refs);
+  if (rc) return rc < 0 ? rc : (rc == 1 ? -1 : rc);
+  marks.assign(plans.size(), FusedQuadMarks());
+  for (unsigned int sg = 0; sg < plans.size(); ++sg) marks[sg].assign(2 * plans[sg].size(), FusedQuadSide());
+  // a matrix's host bounds (pmatrix.hip): {entries, row sums}, 0 where the host has none
+  auto bounds_of = [&](const double * m, double & lo, double & rs) {
+    const size_t idx = m && m >= c->pmatrix ? (size_t)(m - c->pmatrix) / c->pmat_elems : ~(size_t)0;
+    lo = idx < c->pmat_min_entry.size() ? c->pmat_min_entry[idx] : 0.0;
+    rs = idx < c->pmat_min_rowsum.size() ? c->pmat_min_rowsum[idx] : 0.0;
+    return (unsigned int)idx;
+  };
+  std::vector<std::vector<unsigned int>> used(cands.size());
+  for (size_t i = 0; i < cands.size(); ++i)
+  {
+    if (key_of[i] < 0) continue;
+    const FusedOp & f = plans[cands[i].seg][cands[i].pos];
+    const int s = cands[i].side;
+    const QuadRowRef & ref = refs[key_of[i]];
+    cands[i].n = ref.n;
+    if (cands[i].scales && !ref.has_zero && f.g[s].type == FUSED_G_CHERRY_NEW && f.g2[s].type == FUSED_G_CHERRY_NEW)
+    {
+      // every entry of the table is at least the product of the four tip matrices' smallest entries -- a character
+      // code names at least one state --, times the row sums of the three matrices the factors are read with
+      const double * const tipm[4] = {f.g[s].c_lmat, f.g[s].c_rmat, f.g2[s].c_lmat, f.g2[s].c_rmat};
+      const double * const inner[3] = {f.g[s].mat, f.g2[s].mat, s == 0 ? f.lmat : f.rmat};
+      double bound = 1.0, lo, rs;
+      for (const double * m : tipm)
+      {
+        used[i].push_back(bounds_of(m, lo, rs));
+        bound *= lo > 0.0 && rs > 0.0 ? lo : 0.0;
+      }
+      for (const double * m : inner)
+      {
+        used[i].push_back(bounds_of(m, lo, rs));
+        bound *= lo > 0.0 && rs > 0.0 ? rs : 0.0;
+      }
+      cands[i].bound = bound;
+    }
+  }
+  const bool any = pllhip_fused_quad_decide(cands.data(), cands.size(), true, c->sh.sites, c->quad_min_sites_per_class) != 0;
+  for (size_t i = 0; i < cands.size(); ++i)
+  {
+    if (key_of[i] < 0) continue; // (a product with a single tip is no quad: not counted as one refused)
+    const int reason = cands[i].reason;
+    // (a bound that was enough, or one that was not, is what a change of the matrices must be weighed against: pmatrix.hip)
+    if (reason == FUSED_QUAD_BOUND) ++*by_bound;
+    if ((reason == FUSED_QUAD_TAKEN || reason == FUSED_QUAD_MIXED) && cands[i].scales) mats.insert(mats.end(), used[i].begin(), used[i].end());
+    if (reason != FUSED_QUAD_TAKEN) ++c->quad_rows.stats[4];
+    FusedQuadSide & q = marks[cands[i].seg][2 * (size_t)cands[i].pos + cands[i].side];
+    q.taken = reason == FUSED_QUAD_TAKEN;
+    q.ref = refs[key_of[i]];
+    q.units = (q.ref.n + 255u) / 256u;
+  }
+  if (!any) mats.clear();
+  return any ? 1 : 0;
+}
+
 // A planned list: admitted, then -- and only then is anything of the device or the context touched -- its buffers,
 // the encoding, the upload, the launch.  Returns 1 if the list is not one the kernel takes.
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
@@ -1469,11 +1744,27 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
 {
   FusedAdmitted adm;
   if (fused_admit(c, plans, nslots, edge, adm)) return 1;
-  int rc = fused_device_buffers(c, adm.ntab * fused_table_doubles(c->sh.rate_cats), edge != nullptr);
+  // Quad rows: which folded products of the admitted list are read from a table of classes.  Their rows are found or
+  // built first (the class counts decide), then the list is admitted once more with them; a list the kernel does not
+  // take that way -- more character batches than it encodes -- runs as it was admitted.
+  std::vector<FusedQuadMarks> quads;
+  std::vector<unsigned int> quad_mats;
+  unsigned int by_bound = 0;
+  int rc = fused_pick_quads(c, plans, quads, quad_mats, &by_bound);
+  if (rc < 0 || rc > 1) return rc;
+  if (rc == 1)
+  {
+    FusedAdmitted with;
+    if (fused_admit(c, plans, nslots, edge, with, &quads) == 0) adm = std::move(with);
+    else quad_mats.clear();
+  }
+  c->fused_last_quad_mats.swap(quad_mats);
+  c->fused_last_quads_refused_by_bound = by_bound;
+  rc = fused_device_buffers(c, adm.ntab * fused_table_doubles(c->sh.rate_cats), edge != nullptr);
   if (rc) return rc;
   if ((rc = fused_name_rows(c, adm))) return rc;
   const FusedEncodeIn in = {c->pmatrix, c->d_pairtab, c->fused_zero_row, pllhip_fused_slot_size(c->sh.rate_cats, c->sh.rate_scalers != 0),
-                            c->sh.rate_cats, c->sh.rate_scalers != 0};
+                            c->sh.rate_cats, c->sh.rate_scalers != 0, c->tip_stride};
   FusedEncoded enc;
   fused_encode(in, plans, adm, keep_jobs, edge, enc);
   if ((rc = fused_upload(c, enc))) return rc;
@@ -1509,6 +1800,19 @@ int pllhip_relaunch_fused(pllhip_ctx * c)
       case 2: k_dna_pair_tables<2><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr); break;
       case 8: k_dna_pair_tables<8><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr); break;
       default: k_dna_pair_tables<4><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr); break;
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  if (c->fused_last_quad_jobs)
+  {
+    // (only the instances that fold have quads: fused_pick_quads)
+    const unsigned int nwg = PLLHIP_QUAD_TABLE_WGS * njobs;
+    switch (c->sh.rate_cats)
+    {
+      case 1: k_dna_quad_tables<1><<<nwg, 256, 0, c->stream>>>(d_jobs, njobs); break;
+      case 2: k_dna_quad_tables<2><<<nwg, 256, 0, c->stream>>>(d_jobs, njobs); break;
+      case 4: k_dna_quad_tables<4><<<nwg, 256, 0, c->stream>>>(d_jobs, njobs); break;
+      default: pllhip_set_error("quad tables: %u categories", c->sh.rate_cats); return -1;
     }
     HIP_TRY(hipGetLastError());
   }

@@ -254,6 +254,120 @@ __host__ __device__ constexpr unsigned int pllhip_fused_row_index(const unsigned
   return pllhip_fused_pick_index<SPS>(shifted, site);
 }
 
+// ---- Quad rows (quad_rows.hip).  A QUAD is a folded pair product whose two factors are both cherries: its value at a
+// site depends on the characters of four tips only, i.e. on the two pair-row bytes (pa, pb) of the site.  The distinct
+// patterns (pa << 8) | pb of an alignment are numbered in ascending order -- the CLASSES -- and a quad row holds each
+// site's class as a 16-bit number; the reader of the product gathers P . (Fa[pa] . Fb[pb]) from a per-call table of one
+// entry per class instead of forming it.  ONE definition for the builder, the list kernel's pick and the host tests.
+#define PLLHIP_QUAD_MAX_CLASSES 1024u
+#define PLLHIP_FUSED_CH_WIDE (1u << 21)                /* the gather names a quad row: 16 bits per site, two lane positions per
+                                                          row granule; in chars2, bits 24-31: tables the first gather takes beyond one */
+__host__ __device__ constexpr unsigned int pllhip_quad_pattern(unsigned char pa, unsigned char pb)
+{
+  return ((unsigned int)pa << 8) | pb;
+}
+// (a character code 0 -- no state at all -- makes the factor 0)
+__host__ __device__ constexpr bool pllhip_quad_pattern_has_zero(unsigned int pattern)
+{
+  return !(pattern & 0xf000u) || !(pattern & 0x0f00u) || !(pattern & 0x00f0u) || !(pattern & 0x000fu);
+}
+// Where site n's 16 bits lie in a quad row of two planes of `stride` bytes each.  A wave fetches its tile's characters
+// as 16-byte granules at row + first site of the tile, whatever the row (partials_fused.hip), so a quad row is laid out
+// to be fetched the same way: granule g of plane 0 holds sites 16 g ... 16 g + 7, granule g of plane 1 sites 16 g + 8 ...
+// 16 g + 15 -- the 32 bytes of sixteen sites are two lane positions of the character batch.
+__host__ __device__ constexpr size_t pllhip_quad_row_offset(size_t n, size_t stride)
+{
+  return ((n >> 3) & 1u) * stride + (n >> 4) * 16u + (n & 7u) * 2u;
+}
+// Word m (two sites) of sub-step j of a tile in a wave's character registers: the lane position behind the row's first
+// (lpr: lanes per plane of a tile) and the word of that lane's four.
+template <unsigned int SPS>
+__host__ __device__ constexpr unsigned int pllhip_quad_word_lane(unsigned int j, unsigned int m, unsigned int lpr)
+{
+  return (((j * SPS + 2u * m) >> 3) & 1u) * lpr + ((j * SPS + 2u * m) >> 4);
+}
+template <unsigned int SPS>
+__host__ __device__ constexpr unsigned int pllhip_quad_word_of_lane(unsigned int j, unsigned int m)
+{
+  return ((j * SPS + 2u * m) & 7u) >> 1;
+}
+// A site's class out of the SPS / 2 words of its sub-step (wave-uniform words; `site` the lane's).
+template <unsigned int SPS>
+__host__ __device__ constexpr unsigned int pllhip_quad_pick(const unsigned int (&w)[SPS / 2], unsigned int site)
+{
+  static_assert(SPS == 4 || SPS == 8 || SPS == 16 || SPS == 32, "sites per sub-step");
+  // (two words at a time, a scalar register pair: four sites are one 64-bit shift by the lane's own amount --
+  // pllhip_fused_pick_index with 16-bit entries)
+  unsigned long long two = 0;
+  for (unsigned int m = 0; m < SPS / 4; ++m)
+  {
+    const unsigned long long d = (unsigned long long)w[2 * m] | ((unsigned long long)w[2 * m + 1] << 32);
+    two = (SPS == 4 || (site >> 2) == m) ? d : two;
+  }
+  return (unsigned int)(two >> ((site & 3u) * 16u)) & 0xffffu;
+}
+// The ONE rule for whether a folded product is read as a quad (pllhip_launch_fused and pllhip_fused_quad_rule_dry).
+// 0: taken; else why not.  n: the classes of its quad row (0: not counted -- beyond the cap); `scales`: the folded op
+// has a scale buffer, and then `bound`, a lower bound on every entry of the table that needs no device (<= 0: none),
+// must prove that the scaling rule cannot fire for any class: a gathered operand inherits no count.
+enum
+{
+  FUSED_QUAD_TAKEN = 0,
+  FUSED_QUAD_NOT_CHERRIES = 1, // a factor is a single tip
+  FUSED_QUAD_INSTANCE = 2,     // quad rows are off, or the instance does not defer and fold
+  FUSED_QUAD_CAP = 3,          // more than PLLHIP_QUAD_MAX_CLASSES classes
+  FUSED_QUAD_RATIO = 4,        // fewer than min_sites_per_class sites per class
+  FUSED_QUAD_BOUND = 5,        // the product might scale
+  FUSED_QUAD_MIXED = 6         // the reader's other side is a folded product that is no quad
+};
+#define PLLHIP_QUAD_BOUND_MIN 0x1p-200
+inline int pllhip_fused_quad_rule(bool cherries, bool instance, unsigned int n, unsigned int sites,
+                                  unsigned int min_sites_per_class, bool scales, double bound)
+{
+  if (!instance) return FUSED_QUAD_INSTANCE;
+  if (!cherries) return FUSED_QUAD_NOT_CHERRIES;
+  if (n == 0 || n > PLLHIP_QUAD_MAX_CLASSES) return FUSED_QUAD_CAP;
+  if ((unsigned long long)n * min_sites_per_class > sites) return FUSED_QUAD_RATIO;
+  if (scales && !(bound >= PLLHIP_QUAD_BOUND_MIN)) return FUSED_QUAD_BOUND;
+  return FUSED_QUAD_TAKEN;
+}
+// The rule over the folded products of a list (the live path's fused_pick_quads and pllhip_fused_plan_dry_quads): one
+// candidate per product side of a walked op.  A reader of two products runs with both as quads or with neither -- the
+// mixed reader is not built --, so a quad whose partner is none is refused as FUSED_QUAD_MIXED.  Returns the quads taken.
+struct FusedQuadCand
+{
+  unsigned int seg, pos;   // the reader: its segment and position in the walk
+  int side;                // 0: its left operand, 1: its right
+  bool both;               // the reader's other operand is a folded product too
+  bool cherries;           // both factors are cherries
+  unsigned int n;          // classes of the quad row (0: not counted)
+  bool scales;             // the folded op has a scale buffer
+  double bound;            // lower bound of the table's entries the host can prove (<= 0: none)
+  int reason;              // out: FUSED_QUAD_*
+};
+inline unsigned int pllhip_fused_quad_decide(FusedQuadCand * cands, size_t count, bool instance, unsigned int sites,
+                                             unsigned int min_sites_per_class)
+{
+  for (size_t i = 0; i < count; ++i)
+    cands[i].reason = pllhip_fused_quad_rule(cands[i].cherries, instance, cands[i].n, sites, min_sites_per_class, cands[i].scales, cands[i].bound);
+  unsigned int taken = 0;
+  for (size_t i = 0; i < count; ++i)
+  {
+    if (cands[i].reason != FUSED_QUAD_TAKEN || !cands[i].both) continue;
+    bool partner = false;
+    for (size_t k = 0; k < count; ++k)
+      if (k != i && cands[k].seg == cands[i].seg && cands[k].pos == cands[i].pos && cands[k].side != cands[i].side)
+        partner = cands[k].reason == FUSED_QUAD_TAKEN || cands[k].reason == -1;
+    if (!partner) cands[i].reason = -1; // (marked: its partner still sees it as taken)
+  }
+  for (size_t i = 0; i < count; ++i)
+  {
+    if (cands[i].reason == -1) cands[i].reason = FUSED_QUAD_MIXED;
+    taken += cands[i].reason == FUSED_QUAD_TAKEN;
+  }
+  return taken;
+}
+
 // sources and LDS destinations of the operands an op reloads (few ops have any: kept out of the records)
 struct FusedSrc
 {

@@ -8,6 +8,9 @@
 // orders of the reference are reproduced exactly, and expm1 is the C library's
 // own sequence (numerics.hpp), so P is bit-identical to the reference's.
 // Traffic is a few KB per branch: launch-latency bound, not HBM bound.
+#include <algorithm>
+#include <math.h>
+
 #include "ctx.hpp"
 #include "numerics.hpp"
 #include "pmatrix_entry.hpp"
@@ -132,6 +135,76 @@ int pllhip_pmatrices_to(pllhip_ctx * c, double * dst, unsigned int slots, const 
   return 0;
 }
 
+// What the host can say of the matrices about to be written without waiting for the device: a lower bound on the
+// entries and on the row sums of each, from its own copy of the model -- the device's entries in plain double
+// arithmetic, less a margin that covers the difference of the two summation orders and of the two expm1.  4 states, up to
+// four categories (the instances that fold pair products: quad_rows.hip).  A bound that is no longer, or newly, good
+// for a quad ends the kept plan: the list is planned again, without or with the quad.
+void pllhip_pmat_bounds_update(pllhip_ctx * c, const unsigned int * h_params_indices, const unsigned int * h_matrix_indices,
+                               const double * h_branch_lengths, unsigned int count)
+{
+  const unsigned int S = c->sh.states, R = c->sh.rate_cats;
+  if (S != 4 || R > 4 || c->sh.rate_scalers) return;
+  if (c->pmat_min_entry.size() != c->sh.prob_matrices)
+  {
+    c->pmat_min_entry.assign(c->sh.prob_matrices, 0.0);
+    c->pmat_min_rowsum.assign(c->sh.prob_matrices, 0.0);
+  }
+  const bool model = c->h_rates.size() == R && c->h_eigenvals.size() == (size_t)c->sh.rate_matrices * S &&
+                     c->h_eigenvecs.size() == (size_t)c->sh.rate_matrices * S * S && c->h_inv_eigenvecs.size() == c->h_eigenvecs.size();
+  constexpr double MARGIN = 1e-12;
+  bool changed = false;
+  for (unsigned int i = 0; i < count; ++i)
+  {
+    const unsigned int mi = h_matrix_indices[i];
+    if (mi >= c->sh.prob_matrices) continue; // (the call reports it)
+    const double t = h_branch_lengths[i];
+    double lo = 0.0, rs = 0.0;
+    if (model && t > 0.0)
+    {
+      lo = rs = 2.0;
+      for (unsigned int n = 0; n < R; ++n)
+      {
+        const unsigned int pi = h_params_indices[n];
+        if (pi >= c->sh.rate_matrices) { lo = rs = 0.0; break; }
+        const double pinv = c->h_prop_invar[pi];
+        double ex[4];
+        for (unsigned int m = 0; m < 4; ++m)
+        {
+          double arg = (c->h_eigenvals[pi * 4 + m] * c->h_rates[n]) * t;
+          if (pinv > 1e-8) arg = arg / (1.0 - pinv);
+          ex[m] = expm1(arg);
+        }
+        for (unsigned int j = 0; j < 4; ++j)
+        {
+          double sum = 0.0;
+          for (unsigned int k = 0; k < 4; ++k)
+          {
+            double p = j == k ? 1.0 : 0.0;
+            for (unsigned int m = 0; m < 4; ++m)
+              p += (c->h_inv_eigenvecs[pi * 16 + j * 4 + m] * ex[m]) * c->h_eigenvecs[pi * 16 + m * 4 + k];
+            sum += p;
+            if (!(p >= lo)) lo = p; // (a NaN ends up here too)
+          }
+          if (!(sum >= rs)) rs = sum;
+        }
+      }
+      lo -= MARGIN;
+      rs -= MARGIN;
+      if (!(lo > 0.0) || !(rs > 0.0)) lo = rs = 0.0;
+    }
+    // (only a change of what a quad could stand on matters to a kept plan: a bound it uses that fell, or -- a plan that
+    // lost a quad to a bound -- any that rose)
+    const bool used = std::find(c->fused_last_quad_mats.begin(), c->fused_last_quad_mats.end(), mi) != c->fused_last_quad_mats.end();
+    if ((used && (lo < c->pmat_min_entry[mi] || rs < c->pmat_min_rowsum[mi])) ||
+        (c->fused_last_quads_refused_by_bound && lo > c->pmat_min_entry[mi]))
+      changed = true;
+    c->pmat_min_entry[mi] = lo;
+    c->pmat_min_rowsum[mi] = rs;
+  }
+  if (changed) ++c->layout_epoch;
+}
+
 extern "C" int pllhip_update_pmatrices(pllhip_ctx_t * c, const unsigned int * h_params_indices,
                                        const unsigned int * h_matrix_indices,
                                        const double * h_branch_lengths, unsigned int count)
@@ -141,6 +214,8 @@ extern "C" int pllhip_update_pmatrices(pllhip_ctx_t * c, const unsigned int * h_
   if (!count) return 0;
   HIP_TRY(hipSetDevice(c->sh.device));
   PLLHIP_CERT_FIRST(c); // (a list that may have to run again must find the matrices it ran with)
+  // (kept whether quad rows are on or off: a bound must never outlive the matrix it was formed for)
+  pllhip_pmat_bounds_update(c, h_params_indices, h_matrix_indices, h_branch_lengths, count);
   return pllhip_pmatrices_to(c, c->pmatrix, c->sh.prob_matrices, h_params_indices, h_matrix_indices, h_branch_lengths,
                              count);
 }

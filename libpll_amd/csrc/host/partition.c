@@ -931,6 +931,34 @@ int pll_amd_set_pair_row_capacity(pll_partition_t * p, unsigned int rows)
   return PLL_SUCCESS;
 }
 
+int pll_amd_set_quad_rows(pll_partition_t * p, int on, unsigned int min_sites_per_class)
+{
+  int rc = pllhip_set_quad_rows(pll_amd_priv(p)->ctx, on, min_sites_per_class);
+  if (rc) return pll_amd_fail_hip(rc, "set quad rows");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_set_quad_row_capacity(pll_partition_t * p, unsigned int rows)
+{
+  int rc = pllhip_set_quad_row_capacity(pll_amd_priv(p)->ctx, rows);
+  if (rc) return pll_amd_fail_hip(rc, "set quad row capacity");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_quad_list_stats(pll_partition_t * p, unsigned long long * stats3)
+{
+  int rc = pllhip_quad_list_stats(pll_amd_priv(p)->ctx, stats3);
+  if (rc) return pll_amd_fail_hip(rc, "quad list stats");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_quad_row_stats(pll_partition_t * p, unsigned long long * stats5)
+{
+  int rc = pllhip_quad_row_stats(pll_amd_priv(p)->ctx, stats5);
+  if (rc) return pll_amd_fail_hip(rc, "quad row stats");
+  return PLL_SUCCESS;
+}
+
 int pll_amd_pair_row_stats(pll_partition_t * p, unsigned long long * stats4)
 {
   int rc = pllhip_pair_row_stats(pll_amd_priv(p)->ctx, stats4);

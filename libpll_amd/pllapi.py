@@ -293,6 +293,11 @@ class PllLibrary:
             if hasattr(lib, "pll_amd_set_pair_row_capacity"):
                 lib.pll_amd_set_pair_row_capacity.argtypes = [_PP, C.c_uint]
                 lib.pll_amd_pair_row_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
+            if hasattr(lib, "pll_amd_set_quad_rows"):
+                lib.pll_amd_set_quad_rows.argtypes = [_PP, C.c_int, C.c_uint]
+                lib.pll_amd_set_quad_row_capacity.argtypes = [_PP, C.c_uint]
+                lib.pll_amd_quad_row_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
+                lib.pll_amd_quad_list_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
             if hasattr(lib, "pll_amd_set_edge_fold"):
                 lib.pll_amd_set_edge_fold.argtypes = [_PP, C.c_int]
                 lib.pll_amd_edge_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
@@ -1355,6 +1360,26 @@ class Partition:
         buf = (C.c_ulonglong * 4)()
         self._check(self.lib.pll_amd_pair_row_stats(self.ptr, buf), "pll_amd_pair_row_stats")
         return dict(zip(("live", "built", "launches", "evictions"), (int(v) for v in buf)))
+
+    def set_quad_rows(self, on, min_sites_per_class=0):
+        """Quad rows on or off (pll_amd.h); min_sites_per_class: the fewest sites per class a quad is taken at (0: 64)."""
+        self._check(self.lib.pll_amd_set_quad_rows(self.ptr, int(bool(on)), int(min_sites_per_class)), "pll_amd_set_quad_rows")
+
+    def set_quad_row_capacity(self, rows):
+        """Capacity of the pool of cached quad rows (pll_amd.h); 0: the default, a row per four tips."""
+        self._check(self.lib.pll_amd_set_quad_row_capacity(self.ptr, int(rows)), "pll_amd_set_quad_row_capacity")
+
+    def quad_row_stats(self):
+        """{live, built, launches, evictions, refused} of the cached quad rows (pll_amd.h)."""
+        buf = (C.c_ulonglong * 5)()
+        self._check(self.lib.pll_amd_quad_row_stats(self.ptr, buf), "pll_amd_quad_row_stats")
+        return dict(zip(("live", "built", "launches", "evictions", "refused"), (int(v) for v in buf)))
+
+    def quad_list_stats(self):
+        """{taken, wide_gathers, taken_total}: quads the list planned last reads as tables (pll_amd.h)."""
+        buf = (C.c_ulonglong * 3)()
+        self._check(self.lib.pll_amd_quad_list_stats(self.ptr, buf), "pll_amd_quad_list_stats")
+        return dict(zip(("taken", "wide_gathers", "taken_total"), (int(v) for v in buf)))
 
     def unstored_stats(self):
         """{unstored_now, ops_unstored, launches, materialised} of the 4-state pair products (pll_amd.h)."""
