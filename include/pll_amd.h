@@ -1084,7 +1084,9 @@ PLL_EXPORT unsigned int pll_amd_replicates_count(const pll_amd_replicates_t * se
  * the same bits whatever else is in the batch of edges, in whatever order, however the call chunks the batch, on a
  * repeated call, whatever else is in the set (a set made of replicate r alone, or of the replicates in another order,
  * gives replicate r the same bits) and however the set stores its weights; a replicate with weight 1 at one site and 0
- * elsewhere returns that site's persite_lnl bit for bit, an all-zero replicate 0.  persite_lnl of an edge is the same
+ * elsewhere returns that site's persite_lnl bit for bit, an all-zero replicate 0 -- where every site's likelihood is
+ * positive.  A site whose likelihood is zero has persite_lnl -inf, and its term under weight 0 is 0 x -inf: such a
+ * replicate is NaN, as the sequence's sum is (a positive weight there gives -inf).  persite_lnl of an edge is the same
  * bits whether or not lnl is asked for.
  * set may be NULL: then lnl is NULL and only persite_lnl is computed (the unweighted site log-likelihoods of many
  * edges in one call).  With a set, lnl is required and persite_lnl may be NULL.
@@ -1144,7 +1146,9 @@ PLL_EXPORT int pll_amd_replicate_loglikelihood(pll_partition_t * partition,
  * outputs are NULL; arrangement k of (A, B, C, D) is the same bits as arrangement 0 of the edge given with its sides
  * in arrangement k's order; central_lengths equal to the edges' lengths gives the bits of NULL; a replicate with
  * weight 1 at one site and 0 elsewhere returns that site's persite_lnl bit for bit, an all-zero replicate 0, a
- * replicate equal to the partition's own pattern weights lnl[3 e + k] bit for bit.
+ * replicate equal to the partition's own pattern weights lnl[3 e + k] bit for bit.  (The first two where every site's
+ * likelihood is positive: a site whose likelihood is zero has persite_lnl -inf, and under weight 0 its term is
+ * 0 x -inf, so such a replicate is NaN, as in pll_amd_replicate_loglikelihood.)
  * What lives where: P-matrices, the site terms, partial sums, the table and -- for shapes the quartet kernel does
  * not take -- the candidates' CLVs and scale buffers are scratch of the partition on its device, kept until it is
  * destroyed; the call changes nothing of the partition or of the set.  Large batches are worked in chunks of whole
