@@ -872,8 +872,9 @@ typedef struct pll_amd_posterior_edge
  * PLL_ATTRIB_PATTERN_TIP the parent is not a tip (a tip's states are its characters).
  * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
  * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
- * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: joint reconstruction, a builder of the
- * pre-order op list, device-resident outputs.  INTEGRATION.md section 4d. */
+ * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: joint reconstruction, device-resident
+ * outputs.  (pll_amd_utree_directed builds the op list that computes the CLVs of every direction, the pre-order ones
+ * included.)  INTEGRATION.md section 4d. */
 PLL_EXPORT int pll_amd_site_posteriors(pll_partition_t * partition,
                                        const pll_amd_posterior_edge_t * edges, unsigned int edge_count,
                                        const unsigned int * freqs_indices,
@@ -924,7 +925,8 @@ typedef struct pll_amd_nni_edge
  * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
  * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
  * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: optimising the four outer branches,
- * applying a move to a tree, a builder of the all-directions op list.  INTEGRATION.md section 4e. */
+ * applying a move to a tree.  (pll_amd_utree_directed builds the all-directions op list and the edges of a tree.)
+ * INTEGRATION.md section 4e. */
 PLL_EXPORT int pll_amd_nni_loglikelihood(pll_partition_t * partition,
                                          const pll_amd_nni_edge_t * edges, unsigned int edge_count,
                                          const unsigned int * params_indices,
@@ -1357,6 +1359,102 @@ PLL_EXPORT pll_utree_t * pll_amd_distance_tree(pll_partition_t * partition,
 /* Measurement (tools/joining_bench.py): while pll_amd_profile_enable is on, the milliseconds the joining kernels of the
  * partition's last pll_amd_matrix_joins or pll_amd_distance_tree took, first row sum to last join. */
 PLL_EXPORT int pll_amd_joining_kernel_ms(pll_partition_t * partition, float * ms);
+
+/* ---- from a tree to every batched edge call: the all-directions op list, branch derivatives, the tree's gradient
+ * (directed.c, branch_deriv.c, branch_deriv.hip) ----
+ * The batched edge calls (pll_amd_optimize_branch_lengths, pll_amd_nni_*, pll_amd_site_posteriors,
+ * pll_amd_insertion_loglikelihood, pll_amd_branch_derivatives) take an edge as its two sides, each CLV pointing away
+ * from the other.  pll_amd_utree_directed is the way into that state from a pll_utree_t: host only, no device, no
+ * partition.  n = tree->tip_count.
+ * Numbering.  Inner node i (i = 0 .. n - 3) is tree->nodes[n + i]; its ring members are k = 0 (that pointer), k = 1
+ * (->next) and k = 2 (->next->next).  Slot d = 3 i + k belongs to ring member x and holds the CLV of x's side pointing
+ * towards x->back: the CLV computed from x->next->back and x->next->next->back over their edges' pmatrix_index -- what
+ * the reference's traversal leaves in x->clv_index when the virtual root lies across x's edge.  Its CLV index is
+ * first_clv_index + d, its scale buffer first_scaler_index + d (first_scaler_index = PLL_SCALE_BUFFER_NONE: no scale
+ * buffer anywhere).  A tip keeps its own clv_index and has no scale buffer.  The clv_index and scaler_index fields of
+ * inner nodes are not read, and the tree is not modified.
+ * ops [3 (n - 2)]: every slot is written by exactly one op, and an op comes after the ops that write its inner
+ * children; child1 is x->next->back, child2 x->next->next->back.  The order: first the n - 2 ops of the post-order
+ * from tree->nodes[2n - 3] -- the list pll_utree_traverse(tree->nodes[2n - 3], PLL_TREE_TRAVERSE_POSTORDER, ...) and
+ * pll_utree_create_operations give, with slots for the CLV and scaler indices -- then, walking that list backwards
+ * (from the root outwards), for each of its members x the ops of x->next and of x->next->next.
+ * branches, matrix_indices, lengths [2n - 3]: edge t < n is the pendant edge of the tip stored at tree->nodes[t], the
+ * inner side the parent and the tip the child; the n - 3 inner edges follow in ascending order of their lower slot,
+ * the lower slot the parent.  matrix_indices[e] and lengths[e] are the edge's pmatrix_index and length.
+ * nni_edges, nni_branch [n - 3], each may be NULL: inner edge u -- v in the same order, u the lower slot's ring member;
+ * A, B are the sides behind u->next and u->next->next, C, D those behind v->next and v->next->next, each with its own
+ * branch's length; `length` is the central length; nni_branch is the index of the same edge in `branches`.
+ * PLL_ERROR_PARAM_INVALID, outputs untouched: a NULL required array; n < 3; tree->inner_count != n - 2; a ring that is
+ * not three members long; a NULL back, one that is no node of the tree, or x->back->back != x; nodes that do not form
+ * one tree; a tip with clv_index >= n, or two tips with the same one; the two ends of an edge disagreeing in
+ * pmatrix_index or in the bits of length; two edges sharing a pmatrix_index; first_scaler_index negative and not
+ * PLL_SCALE_BUFFER_NONE; index arithmetic that would overflow.  Two calls on the same tree give the same output. */
+PLL_EXPORT int pll_amd_utree_directed(const pll_utree_t * tree,
+                                      unsigned int first_clv_index,
+                                      int first_scaler_index,          /* PLL_SCALE_BUFFER_NONE: no scalers */
+                                      pll_operation_t * ops,            /* out [3 (n - 2)] */
+                                      pll_amd_branch_t * branches,      /* out [2n - 3] */
+                                      unsigned int * matrix_indices,    /* out [2n - 3] */
+                                      double * lengths,                 /* out [2n - 3] */
+                                      pll_amd_nni_edge_t * nni_edges,   /* out [n - 3] or NULL */
+                                      unsigned int * nni_branch);       /* out [n - 3] or NULL: index into branches */
+
+/* The first and second derivative of -lnL with respect to the length of every branch, at the given lengths, all CLVs
+ * held fixed, and the log-likelihood there: one evaluation of what pll_amd_optimize_branch_lengths iterates, handed
+ * back.  (d_f[b], dd_f[b]) is what pll_compute_likelihood_derivatives(partition, parent_scaler, child_scaler,
+ * lengths[b], params_indices, sumtable, &d, &dd) returns after pll_update_sumtable(partition, parent_clv, child_clv,
+ * parent_scaler, child_scaler, params_indices, sumtable) -- the derivatives of -lnL, the reference's convention;
+ * lnl[b] = pll_compute_edge_loglikelihood at length lengths[b] (the tip, if any, as the child; freqs_indices =
+ * params_indices).  There is no Newton rule and there are no bounds.  Both scaling modes, +I, a rate matrix per
+ * category, category weights, pattern tips or tip CLVs and pattern weights behave as in the single calls.  The
+ * device's exp and its order of the site sums differ from the single calls': d_f and dd_f agree with them to about
+ * 1e-13 relative to the sum of the sites' absolute terms, not bit for bit.
+ * With the branches of pll_amd_utree_directed, after the directed op list has run, d_f is the gradient of -lnL of the
+ * whole tree with respect to its branch lengths (pll_amd_tree_gradient does all of it in one call).
+ * What lives where: as for pll_amd_optimize_branch_lengths, whose scratch this call shares -- sumtables (shapes other
+ * than 4 states with 1 or 4 rate categories and no per-rate scale buffers: that shape reads each side once and
+ * builds no table) and partial sums are scratch of the partition on its device; a call never changes a CLV, scale
+ * buffer, P-matrix, sumtable slot or host mirror.  Large batches are worked in chunks of at most about
+ * PLL_AMD_BRANCH_SCRATCH_MB (environment, read at call time, default 2048) of scratch and at most 65,535 branches; a
+ * branch's three values are the same bits whatever else is in the batch, in whatever order, however the call chunks
+ * it, whether or not lnl is asked for, and on a repeated call.  The call is synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, outputs untouched): CLV, scaler and params indices in
+ * range, no tip-tip branch on a PLL_ATTRIB_PATTERN_TIP partition, count >= 1, lengths finite and >= 0, no NULL array
+ * but lnl.  Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias
+ * correction, sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
+ * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  INTEGRATION.md section 4l. */
+PLL_EXPORT int pll_amd_branch_derivatives(pll_partition_t * partition,
+                                          const pll_amd_branch_t * branches, unsigned int count,
+                                          const unsigned int * params_indices,
+                                          const double * lengths,   /* [count] */
+                                          double * d_f,             /* out [count] */
+                                          double * dd_f,            /* out [count] */
+                                          double * lnl);            /* out [count] or NULL */
+
+/* Tree to gradient in one call.  Defined as this sequence, and equal to it bit for bit:
+ *   pll_amd_utree_directed(tree, first_clv_index, first_scaler_index, ops, branches, matrix_indices, lengths,
+ *                          NULL, NULL);
+ *   pll_update_prob_matrices(partition, params_indices, matrix_indices, lengths, 2n - 3);
+ *   pll_update_partials(partition, ops, 3 (n - 2));
+ *   pll_amd_branch_derivatives(partition, branches, 2n - 3, params_indices, lengths, d_f, dd_f, lnl);
+ * branches, matrix_indices and lengths ([2n - 3], each may be NULL) receive the builder's lists.  lnl[e] is the tree's
+ * log-likelihood seen from every edge: the 2n - 3 values agree to rounding.
+ * UNLIKE THE OTHER BATCHED CALLS, THIS ONE CHANGES THE PARTITION, deliberately: afterwards the 2n - 3 P-matrices named
+ * by the tree and all 3 (n - 2) directed CLVs and scale buffers (slots first_clv_index + d, first_scaler_index + d)
+ * are current -- the state every other batched edge call wants.
+ * Checked before anything runs (PLL_ERROR_PARAM_INVALID, nothing changed): everything pll_amd_utree_directed checks;
+ * the slots within the partition's clv_buffers (first_clv_index >= tips) and scale_buffers, the tree's pmatrix_index
+ * values within prob_matrices, tip clv_index values < partition->tips, params indices in range; lengths non-negative
+ * and finite (a neighbour-joining tree can carry negative lengths: clamping them stays the client's decision).
+ * Limits and PLL_ERROR_MEM_ALLOC: as for pll_amd_branch_derivatives. */
+PLL_EXPORT int pll_amd_tree_gradient(pll_partition_t * partition, const pll_utree_t * tree,
+                                     unsigned int first_clv_index, int first_scaler_index,
+                                     const unsigned int * params_indices,
+                                     pll_amd_branch_t * branches,      /* out [2n - 3] or NULL */
+                                     unsigned int * matrix_indices,    /* out [2n - 3] or NULL */
+                                     double * lengths,                 /* out [2n - 3] or NULL */
+                                     double * d_f, double * dd_f,      /* out [2n - 3] */
+                                     double * lnl);                    /* out [2n - 3] or NULL */
 
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets

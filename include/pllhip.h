@@ -549,6 +549,21 @@ PLLHIP_EXPORT int pllhip_optimize_branch_lengths(pllhip_ctx_t * ctx, const pllhi
                                                  unsigned int max_iters, size_t scratch_bytes, double * h_lengths,
                                                  double * h_lnl, unsigned int * h_evals, int * h_status);
 
+/* ---- batched branch derivatives (branch_deriv.hip; host side host/branch_deriv.c) ----
+ * For every branch at its given length, all CLVs fixed: the first and second derivative of -lnL as
+ * pllhip_update_sumtable and pllhip_likelihood_derivatives would return them, and (h_lnl not NULL) lnL as
+ * pllhip_edge_loglikelihood would (freqs indices = params indices); no Newton rule, no bounds (pll_amd_branch_derivatives,
+ * include/pll_amd.h).  route: -1 the library's choice, 0 the general route (sumtables in scratch, k_bo_pass), 1 the
+ * fused kernel where it covers the partition (4 states, 1 or 4 rate categories, no per-rate scale buffers).  Nothing
+ * of the context changes; scratch (kept by the context, shared with pllhip_optimize_branch_lengths) is at most about
+ * scratch_bytes per chunk, at least one branch's worth.  Return codes as for pllhip_optimize_branch_lengths. */
+PLLHIP_EXPORT int pllhip_branch_derivatives(pllhip_ctx_t * ctx, const pllhip_branch_t * h_branches, unsigned int count,
+                                            const unsigned int * h_params_indices, const double * h_lengths, int route,
+                                            size_t scratch_bytes, double * h_df, double * h_ddf, double * h_lnl);
+/* -3 (and the error text) for a context pllhip_branch_derivatives does not take, else 0: for a caller that changes
+ * the context before it gets there (pll_amd_tree_gradient) and must refuse first */
+PLLHIP_EXPORT int pllhip_branch_derivatives_refused(pllhip_ctx_t * ctx);
+
 /* ---- batched per-site posteriors (posteriors.hip; host side host/posteriors.c) ----
  * For every edge and site, how the site likelihood of pllhip_edge_loglikelihood (same five arguments) splits over the
  * states of the parent side and over the rate categories: the definition is written out at pll_amd_site_posteriors

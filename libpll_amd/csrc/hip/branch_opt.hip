@@ -231,26 +231,6 @@ __global__ __launch_bounds__(256) void k_bo_pass(BoPassArgs a)
   }
 }
 
-// a branch's tile pairs (component `comp`, or both) added in tile order by one wave: 64 loads at a time, then every
-// lane adds them in order (the same bits as one lane walking them, without 2 x tiles dependent loads)
-__device__ __forceinline__ void bo_tile_sums(const double * __restrict__ p, unsigned int tiles, double & f, double & g)
-{
-  const unsigned int lane = threadIdx.x & 63u;
-  f = 0.0;
-  g = 0.0;
-  for (unsigned int base = 0; base < tiles; base += 64u)
-  {
-    const unsigned int i = base + lane;
-    const double pf = i < tiles ? p[2 * (size_t)i] : 0.0, pg = i < tiles ? p[2 * (size_t)i + 1] : 0.0;
-    const unsigned int m = min(64u, tiles - base);
-    for (unsigned int j = 0; j < m; ++j)
-    {
-      f += __shfl(pf, (int)j, 64);
-      g += __shfl(pg, (int)j, 64);
-    }
-  }
-}
-
 // one wave per branch: (f, g) = its tile pairs added in tile order, then one step of the rule (include/pll_amd.h)
 __global__ __launch_bounds__(64) void k_bo_step(BoState * __restrict__ st, const double * __restrict__ partial,
                                                 unsigned int tiles, double tol, unsigned int max_iters,
@@ -301,7 +281,7 @@ __global__ __launch_bounds__(64) void k_bo_finish(const double * __restrict__ pa
   if (threadIdx.x == 0) lnl[b] = f;
 }
 
-static int bo_launch_pass(pllhip_ctx * c, const BoPassArgs & a, unsigned int nb)
+int pllhip_bo_launch_pass(pllhip_ctx * c, const BoPassArgs & a, unsigned int nb)
 {
   const dim3 grid(a.tiles, nb);
   const size_t lds = (size_t)a.rate_cats * (3u * a.states + 1u) * sizeof(double);
@@ -365,7 +345,7 @@ int pllhip_bo_newton(pllhip_ctx * c, BoPassArgs & pa, const BoBuffers & bf, unsi
     const unsigned int wn = std::min<unsigned int>(BO_CHECK, max_iters - it);
     for (unsigned int j = 0; j < wn; ++j)
     {
-      if ((rc = bo_launch_pass(c, pa, nb))) return rc;
+      if ((rc = pllhip_bo_launch_pass(c, pa, nb))) return rc;
       const bool last = j + 1 == wn;
       if (last) HIP_TRY(hipMemsetAsync(bf.count, 0, 4, c->stream));
       k_bo_step<<<nb, 64, 0, c->stream>>>(bf.state, bf.partial, tiles, tolerance, max_iters,
@@ -383,7 +363,7 @@ int pllhip_bo_newton(pllhip_ctx * c, BoPassArgs & pa, const BoBuffers & bf, unsi
   if (h_lnl)
   {
     pa.lnl = 1;
-    if ((rc = bo_launch_pass(c, pa, nb))) return rc;
+    if ((rc = pllhip_bo_launch_pass(c, pa, nb))) return rc;
     k_bo_finish<<<nb, 64, 0, c->stream>>>(bf.partial, bf.lnl, tiles);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h_lnl, bf.lnl, nb * 8, hipMemcpyDeviceToHost, c->stream));

@@ -1,5 +1,6 @@
-// branch_opt.hpp -- internal: what branch_opt.hip shares with the other batched Newton caller (nni.hip): the Newton
-// state of a branch, the argument block of k_bo_pass, and the part of a chunk's work that starts once the sumtables
+// branch_opt.hpp -- internal: what branch_opt.hip shares with the other batched Newton caller (nni.hip) and with the
+// call that evaluates without stepping (branch_deriv.hip): the Newton state of a branch, the argument block of
+// k_bo_pass and its launcher, the tile sums of a branch, and the part of a chunk's work that starts once the sumtables
 // and the per-site scaler counts are in scratch.
 #pragma once
 #include "batched.hpp"
@@ -47,6 +48,28 @@ struct BoBuffers
   unsigned int * count;
 };
 
+// a branch's tile pairs (both components) added in tile order by one wave: 64 loads at a time, then every
+// lane adds them in order (the same bits as one lane walking them, without 2 x tiles dependent loads)
+__device__ __forceinline__ void bo_tile_sums(const double * __restrict__ p, unsigned int tiles, double & f, double & g)
+{
+  const unsigned int lane = threadIdx.x & 63u;
+  f = 0.0;
+  g = 0.0;
+  for (unsigned int base = 0; base < tiles; base += 64u)
+  {
+    const unsigned int i = base + lane;
+    const double pf = i < tiles ? p[2 * (size_t)i] : 0.0, pg = i < tiles ? p[2 * (size_t)i + 1] : 0.0;
+    const unsigned int m = min(64u, tiles - base);
+    for (unsigned int j = 0; j < m; ++j)
+    {
+      f += __shfl(pf, (int)j, 64);
+      g += __shfl(pg, (int)j, 64);
+    }
+  }
+}
+
+// one k_bo_pass over nb branches x pa.tiles tiles (pa.lnl: 0 the (d, dd) pairs of the active branches, 1 every branch's lnL)
+int pllhip_bo_launch_pass(pllhip_ctx * c, const BoPassArgs & a, unsigned int nb);
 // per-rate scale buffers: every table of the chunk brought to its sites' smallest counts (k_bo_rescale)
 int pllhip_bo_rescale(pllhip_ctx * c, double * tables, const BoSides * sides, unsigned int nb);
 // everything of `pa` that does not depend on the chunk's scratch or the caller: the model, the shape, the tiles

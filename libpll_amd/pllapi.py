@@ -362,6 +362,36 @@ class PllLibrary:
                 lib.pll_amd_distance_tree.argtypes = [_PP, C.c_void_p, C.c_uint, C.c_void_p, C.c_double, C.c_double,
                                                       C.c_double, C.c_uint, C.c_int] + [C.c_void_p] * 5
                 lib.pll_amd_joining_kernel_ms.argtypes = [_PP, C.POINTER(C.c_float)]
+            if hasattr(lib, "pll_amd_utree_directed"):
+                lib.pll_amd_utree_directed.argtypes = [C.c_void_p, C.c_uint, C.c_int] + [C.c_void_p] * 6
+                lib.pll_amd_branch_derivatives.argtypes = [_PP, C.c_void_p, C.c_uint, _up] + [C.c_void_p] * 4
+                lib.pll_amd_tree_gradient.argtypes = [_PP, C.c_void_p, C.c_uint, C.c_int, _up] + [C.c_void_p] * 6
+
+    def utree_directed(self, tree, first_clv, first_scaler, want_nni=True):
+        """pll_amd_utree_directed (host only): a dict of numpy arrays -- ops (OPS_DTYPE, [3 (n - 2)]), branches
+        (BRANCH_DTYPE), matrix_indices, lengths ([2n - 3]) and, with want_nni, nni_edges (NNI_EDGE_DTYPE) and nni_branch
+        ([n - 3]).  tree: the pointer to a pll_utree_t (tree_from_joins, distance_tree); first_scaler: SCALE_BUFFER_NONE
+        for no scale buffers."""
+        if not hasattr(self.lib, "pll_amd_utree_directed"):
+            raise PllError("this library has no pll_amd_utree_directed")
+        n = int(tree.contents.tip_count)
+        nops, nedges, ninner = 3 * max(n, 2) - 6, 2 * max(n, 2) - 3, max(n, 3) - 3
+        out = {"ops": np.zeros(nops, dtype=OPS_DTYPE), "branches": np.zeros(nedges, dtype=BRANCH_DTYPE),
+               "matrix_indices": np.zeros(nedges, dtype=np.uint32), "lengths": np.zeros(nedges)}
+        if want_nni:
+            out["nni_edges"] = np.zeros(ninner, dtype=NNI_EDGE_DTYPE)
+            out["nni_branch"] = np.zeros(ninner, dtype=np.uint32)
+        # (one spare element behind each: an empty array has no address to give)
+        bufs = {k: np.zeros(len(v) + 1, dtype=v.dtype) for k, v in out.items()}
+        ok = self.lib.pll_amd_utree_directed(
+            C.cast(tree, C.c_void_p), first_clv, first_scaler, bufs["ops"].ctypes.data, bufs["branches"].ctypes.data,
+            bufs["matrix_indices"].ctypes.data, bufs["lengths"].ctypes.data,
+            bufs["nni_edges"].ctypes.data if want_nni else None, bufs["nni_branch"].ctypes.data if want_nni else None)
+        if not ok:
+            raise PllError("pll_amd_utree_directed: errno %d: %s" % (self.errno(), self.errmsg()))
+        for k in out:
+            out[k][:] = bufs[k][:len(out[k])]
+        return out
 
     def joins_from_matrix(self, distances, variances=None, method=JOIN_NJ):
         """pll_amd_joins_from_matrix (host only): (joins, last) -- a JOIN_DTYPE array [n - 3] and a JOIN_LAST_DTYPE
@@ -997,6 +1027,50 @@ class Partition:
             max_iters, _d(t), _d(lnl), _u(evals), status.ctypes.data)
         self._check(ok, "pll_amd_optimize_branch_lengths")
         return t, lnl, evals, status
+
+    def branch_derivatives(self, branches, lengths, params_indices, want_lnl=True):
+        """pll_amd_branch_derivatives: (d_f, dd_f, lnl) as numpy arrays, one entry per branch (lnl None without
+        want_lnl): the first and second derivative of -lnL at the given lengths and lnL there.  branches: rows of
+        (parent_clv, parent_scaler, child_clv, child_scaler) or a BRANCH_DTYPE array."""
+        if not hasattr(self.lib, "pll_amd_branch_derivatives"):
+            raise PllError("this library has no pll_amd_branch_derivatives")
+        b = np.zeros(len(branches), dtype=BRANCH_DTYPE)
+        if isinstance(branches, np.ndarray) and branches.dtype == BRANCH_DTYPE:
+            b[:] = branches
+        else:
+            for i, row in enumerate(branches):
+                b[i] = tuple(row)
+        t = np.array(lengths, dtype=np.float64).reshape(-1)
+        assert len(t) == len(b)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        d, dd = np.zeros(len(b)), np.zeros(len(b))
+        lnl = np.zeros(len(b)) if want_lnl else None
+        ok = self.lib.pll_amd_branch_derivatives(
+            self.ptr, b.ctypes.data if len(b) else None, len(b), _u(pi), t.ctypes.data if len(b) else None,
+            d.ctypes.data if len(b) else None, dd.ctypes.data if len(b) else None,
+            lnl.ctypes.data if want_lnl and len(b) else None)
+        self._check(ok, "pll_amd_branch_derivatives")
+        return d, dd, lnl
+
+    def tree_gradient(self, tree, first_clv, first_scaler, params_indices, want_lnl=True):
+        """pll_amd_tree_gradient: a dict of numpy arrays over the tree's 2n - 3 edges -- branches (BRANCH_DTYPE),
+        matrix_indices, lengths (the lists of pll_amd_utree_directed), d_f, dd_f and, with want_lnl, lnl.  Changes the
+        partition: the tree's P-matrices and all directed CLVs are current afterwards."""
+        if not hasattr(self.lib, "pll_amd_tree_gradient"):
+            raise PllError("this library has no pll_amd_tree_gradient")
+        n = int(tree.contents.tip_count)
+        ne = max(2 * n - 3, 1)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        out = {"branches": np.zeros(ne, dtype=BRANCH_DTYPE), "matrix_indices": np.zeros(ne, dtype=np.uint32),
+               "lengths": np.zeros(ne), "d_f": np.zeros(ne), "dd_f": np.zeros(ne)}
+        if want_lnl:
+            out["lnl"] = np.zeros(ne)
+        ok = self.lib.pll_amd_tree_gradient(
+            self.ptr, C.cast(tree, C.c_void_p), first_clv, first_scaler, _u(pi), out["branches"].ctypes.data,
+            out["matrix_indices"].ctypes.data, out["lengths"].ctypes.data, out["d_f"].ctypes.data,
+            out["dd_f"].ctypes.data, out["lnl"].ctypes.data if want_lnl else None)
+        self._check(ok, "pll_amd_tree_gradient")
+        return out
 
     def nni_loglikelihood(self, edges, params_indices):
         """pll_amd_nni_loglikelihood: an (edges, 3) array, column k the arrangement PLL_AMD_NNI_* = k.  edges: rows of
