@@ -1614,6 +1614,13 @@ PLL_EXPORT int pll_amd_set_quad_row_capacity(pll_partition_t * partition, unsign
 PLL_EXPORT int pll_amd_quad_row_stats(pll_partition_t * partition, unsigned long long * stats5);
 /* {quads read as tables in the list planned last, its wide gathers, quads read as tables by all planned lists} */
 PLL_EXPORT int pll_amd_quad_list_stats(pll_partition_t * partition, unsigned long long * stats3);
+/* Unstored quad products of the same partitions (pllhip.h: pllhip_set_unstored_quad_products): the parent of an op over
+ * two quads is walked but not stored where nothing but its reader's slot needs it; the partition keeps copies of the two
+ * quad tables and stores the CLV, bit for bit, before anything else reads or overwrites it or its scale buffer.  On by
+ * default; 0 stores those there are.  stats4: {live now, ops left unstored in total, materialising launches, CLVs
+ * materialised} -- counted here only, never in the deferred, unstored or pair-fold statistics. */
+PLL_EXPORT int pll_amd_set_unstored_quad_products(pll_partition_t * partition, int on);
+PLL_EXPORT int pll_amd_quad_product_stats(pll_partition_t * partition, unsigned long long * stats4);
 /* Edge log-likelihood terms from the 4-state whole-list launch (pllhip.h: pllhip_set_edge_fold): after
  * pll_compute_edge_loglikelihood at an inner-inner edge, the next pll_update_partials that writes one of the edge's two
  * CLVs also forms the edge's per-site terms, and the same evaluation then only sums them -- bit for bit the value it

@@ -334,6 +334,37 @@ PLLHIP_EXPORT int pllhip_fused_plan_dry_quads(unsigned int tips, unsigned int cl
                                               unsigned int * counts_out);
 PLLHIP_EXPORT int pllhip_fused_quad_rule_dry(int cherries, int instance, unsigned int n, unsigned int sites,
                                              unsigned int min_sites_per_class, int scales, double bound);
+/* Unstored quad products (deferred.hip).  A walked op over two quads -- both its operands folded pair
+ * products read as quads -- has the value Qa[class a] * Qb[class b] at a site, two rows of the launch's two quad tables,
+ * times 2^256 where its own scaling test fired.  Where it passes every condition an unstored pair product passes, the
+ * launch does not store its CLV (its counts it does): the context keeps copies of the two quad tables -- a pool of its
+ * own, a slot per live product, 2 x 1024 classes each, allocated on first use; no memory or no free slot: stored as
+ * before -- and the two quad rows stay as they are while it lives.  Every entry point that reads or overwrites the CLV
+ * or its scale buffer outside a list kernel stores it first, bit for bit what the op would have stored, by a launch of
+ * a kernel of its own; so does whatever changes or evicts a quad row it names.
+ * pllhip_set_unstored_quad_products(ctx, 0): such parents are stored (those unstored now first); 1: the default; off
+ * whenever pllhip_set_quad_rows, pllhip_set_unstored_pairs or pllhip_set_deferral is.
+ * pllhip_quad_product_stats: {live now, ops left unstored in total, materialising launches, CLVs materialised};
+ * pllhip_deferred_stats, pllhip_unstored_stats and pllhip_pair_fold_stats do not count them. */
+PLLHIP_EXPORT int pllhip_set_unstored_quad_products(pllhip_ctx_t * ctx, int on);
+PLLHIP_EXPORT int pllhip_quad_product_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+/* Host logic, no device (tests/test_host_quad_products.py): pllhip_fused_plan_dry_quads, then the rule the launch
+ * applies behind the quads'.  products_out[i] = 1: op i of the list is walked over two taken quads and its parent is not
+ * stored; *bytes_out (may be NULL): the plan's bytes per site -- one write per entry of every stored CLV of the walk and
+ * per count, one read per character of the tips under the list.  And a site's class as the materialising kernel reads
+ * it from a quad row in memory (two planes of `stride` bytes). */
+PLLHIP_EXPORT int pllhip_fused_plan_dry_quad_products(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                                      int pattern_tip, unsigned int rate_cats, int rate_scalers,
+                                                      const pllhip_op_t * ops, unsigned int count, unsigned int nslots,
+                                                      const unsigned char * pinned, const int * edge4, unsigned int sites,
+                                                      int quads_on, unsigned int min_sites_per_class,
+                                                      const unsigned int * classes, const double * bounds,
+                                                      unsigned int * nkept, unsigned int * order_out,
+                                                      unsigned char * folded_out, int * ops_out, int * quads_out,
+                                                      unsigned int * counts_out, unsigned char * products_out,
+                                                      unsigned int * bytes_out);
+PLLHIP_EXPORT unsigned int pllhip_quad_row_class_dry(const unsigned char * row, unsigned long long site,
+                                                     unsigned long long stride);
 /* Host logic, no device (tests/test_host_pair_rows.py): the pair row's byte; the index gather_factor() of the list
  * kernel takes from ONE row's words of a tile (kind 0 a pair row, 1 a single tip that is the table's first character,
  * 2 one that is its second); and the rows every walked op's gathers name, on top of pllhip_fused_plan_dry_folded's

@@ -586,6 +586,7 @@ extern "C" void pllhip_ctx_destroy(pllhip_ctx_t * c)
   pllhip_pair_rows_free(c);
   pllhip_quad_rows_free(c);
   if (c->defer_pool) (void)hipFree(c->defer_pool);
+  if (c->quad_product_pool) (void)hipFree(c->quad_product_pool);
   if (c->cherry_pool) (void)hipFree(c->cherry_pool);
   if (c->cherry_codes) (void)hipFree(c->cherry_codes);
   if (c->cherry_zero) (void)hipFree(c->cherry_zero);

@@ -210,6 +210,14 @@ struct pllhip_ctx
     unsigned int tip1 = 0, tip2 = 0;
     unsigned int rows[4] = {0, 0, 0, 0}; // tip index + 1 of each table's two rows (0: none -- code 0)
     int scaler = -1;
+    // A third kind, the QUAD PRODUCT ("Unstored quad products"): the parent of a walked op over two
+    // quads that the list kernel did not store -- Qa[class a] * Qb[class b], rows of kept copies of the launch's two
+    // quad tables (quad_product_pool, slot qslot), the classes read from the two quad rows (places qrow[] of
+    // quad_rows, tips qtips[] -- the rows stay as they are while the product lives: quad_rows.hip stores it first),
+    // times 2^256 where the op's count (in HBM, in `scaler`) is not 0.
+    bool quad = false;
+    unsigned int qrow[2] = {0, 0}, qslot = 0;
+    unsigned int qtips[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
   };
   std::vector<deferred_clv> deferred;          // per CLV index (sized on first use)
   std::vector<int> deferred_sc_owner;          // per scale buffer: the deferred CLV that owns its (zero) counts, or -1
@@ -227,6 +235,16 @@ struct pllhip_ctx
   struct unstored_product { unsigned int clv; int scaler; unsigned int rows[4]; bool folded; }; // (deferred_clv's fields)
   std::vector<unstored_product> fused_last_unstored; // the kept plan's pair products
   unsigned long long unstored_stats[4] = {0, 0, 0, 0}; // the same four numbers for pair products
+  // ---- quad products (the third kind above).  Counted on their own -- n_deferred includes them, so that every
+  // PLLHIP_DEFERRED_* site serves them; the cherries', pair products' and folded products' statistics do not.
+  struct quad_product { unsigned int clv; int scaler; unsigned int qrow[2], qslot; unsigned int qtips[2][4]; };
+  unsigned int n_quad_products = 0;
+  bool unstored_quad_products = true;          // pllhip_set_unstored_quad_products
+  double * quad_product_pool = nullptr;        // [slot][2 tables][PLLHIP_QUAD_MAX_CLASSES][span]: kept copies of the quad tables
+  std::vector<int> quad_product_owner;         // per slot: the CLV of the live product that has it, or -1
+  bool quad_product_pool_failed = false;       // its allocation failed once: such parents are stored, as before
+  std::vector<quad_product> fused_last_quad_products; // the kept plan's
+  unsigned long long quad_product_stats[4] = {0, 0, 0, 0}; // live now (filled on read), ops left unstored, materialise launches, CLVs materialised
   bool cherry_deferral = true;                        // pllhip_set_deferral (0: the eager path, for A/B and tests)
   unsigned int defer_epoch = 0;                // bumped whenever a deferral ends other than by the list that replaces it
   unsigned int fused_last_defer_epoch = 0;     // ... as it was when the kept plan was launched
@@ -479,6 +497,7 @@ struct QuadRowRef
   bool has_zero = false;                     // a pattern has a character code 0: its entry is 0, no lower bound holds
   const unsigned char * row = nullptr;       // plane 0; plane 1 is tip_stride bytes behind
   const unsigned short * patterns = nullptr; // [n] on the device, ascending
+  unsigned int slot = 0;                     // the row's place in the pool
 };
 struct QuadKey
 {
@@ -490,6 +509,13 @@ struct QuadKey
 int pllhip_quad_rows_resolve(pllhip_ctx * c, const std::vector<QuadKey> & need, std::vector<QuadRowRef> & out);
 void pllhip_quad_rows_tip_written(pllhip_ctx * c, unsigned int tip); // its quad rows are stale, and the kept plan ends
 void pllhip_quad_rows_free(pllhip_ctx * c);
+const unsigned char * pllhip_quad_row_ptr(const pllhip_ctx * c, unsigned int slot, const unsigned int * tips4); // nullptr: the pool's row is no longer that quad's
+// deferred.hip: the quad products -- every live one stored (before a quad row changes or goes: quad_rows.hip), and a
+// product's place in the pool of kept tables (-1: none free, or no pool: the parent is stored); `taken`: places this
+// launch has handed out already
+int pllhip_quad_products_flush(pllhip_ctx * c);
+int pllhip_quad_product_slot(pllhip_ctx * c, unsigned int clv_index, std::vector<unsigned char> & taken);
+double * pllhip_quad_product_table(const pllhip_ctx * c, unsigned int slot, unsigned int which);
 // pmatrix.hip: the host's bounds of the matrices about to be written (pllhip_ctx::pmat_min_entry)
 void pllhip_pmat_bounds_update(pllhip_ctx * c, const unsigned int * h_params_indices, const unsigned int * h_matrix_indices,
                                const double * h_branch_lengths, unsigned int count);

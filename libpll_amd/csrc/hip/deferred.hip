@@ -25,6 +25,7 @@
 
 #include "ctx.hpp"
 #include "numerics.hpp"
+#include "partials_fused.hpp"
 
 #define PLLHIP_DEFER_BATCH 48
 struct DeferredJobs
@@ -103,6 +104,126 @@ __global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs,
       counts[t] = 0u;
 }
 
+// Quad products ("Unstored quad products"): the parent of a walked op over two quads that the list
+// kernel did not store.  Site n's value is Qa[class a of n] * Qb[class b of n] -- the classes from the two quad rows,
+// Qa and Qb the kept copies of the launch's two quad tables ([class][rate][state]) --, times 2^256 where the op's count
+// of the site (in HBM: a quad brings none, so it is the op's own scale bit) is not 0: the list kernel's own two
+// operations in its order (partials_fused.hip, step(): q = x * y, then q *= 2^256 or 1.0).  A launch of its own,
+// never part of a k_deferred_materialise batch: blockIdx.y = CLV, one lane per 16 bytes of the CLV.
+#define PLLHIP_QUAD_PRODUCT_BATCH 64
+struct QuadProductJobs
+{
+  const pll_v2d * qa[PLLHIP_QUAD_PRODUCT_BATCH];
+  const pll_v2d * qb[PLLHIP_QUAD_PRODUCT_BATCH];
+  const unsigned char * row_a[PLLHIP_QUAD_PRODUCT_BATCH];
+  const unsigned char * row_b[PLLHIP_QUAD_PRODUCT_BATCH];
+  pll_v2d * clv[PLLHIP_QUAD_PRODUCT_BATCH];
+  const unsigned int * counts[PLLHIP_QUAD_PRODUCT_BATCH]; // nullptr: none
+};
+static_assert(sizeof(QuadProductJobs) <= 3900, "the jobs travel as kernel arguments");
+
+template <bool NT>
+__global__ __launch_bounds__(256) void k_quad_product_materialise(QuadProductJobs jobs, size_t sites, unsigned int span2,
+                                                                  size_t row_stride)
+{
+  const pll_v2d * __restrict__ qa = jobs.qa[blockIdx.y];
+  const pll_v2d * __restrict__ qb = jobs.qb[blockIdx.y];
+  const unsigned char * __restrict__ row_a = jobs.row_a[blockIdx.y];
+  const unsigned char * __restrict__ row_b = jobs.row_b[blockIdx.y];
+  pll_v2d * __restrict__ clv = jobs.clv[blockIdx.y];
+  const unsigned int * __restrict__ counts = jobs.counts[blockIdx.y];
+  const size_t total = sites * span2;
+  for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+  {
+    const size_t n = t / span2;
+    const unsigned int g = (unsigned int)(t - n * span2);
+    // (a class is below the row's class count, at most PLLHIP_QUAD_MAX_CLASSES: inside the kept table)
+    const unsigned int ca = pllhip_quad_row_class(row_a, n, row_stride) & (PLLHIP_QUAD_MAX_CLASSES - 1u);
+    const unsigned int cb = pllhip_quad_row_class(row_b, n, row_stride) & (PLLHIP_QUAD_MAX_CLASSES - 1u);
+    const pll_v2d a = qa[(size_t)ca * span2 + g], b = qb[(size_t)cb * span2 + g];
+    const bool scale = counts && counts[n];
+    const double factor = __hiloint2double(scale ? 0x4ff00000 : 0x3ff00000, 0);
+    pll_v2d v = {a.x * b.x, a.y * b.y};
+    v.x *= factor;
+    v.y *= factor;
+    if (NT) __builtin_nontemporal_store(v, clv + t);
+    else clv[t] = v;
+  }
+}
+
+// The pool of kept quad tables: a slot per LIVE product, two tables of PLLHIP_QUAD_MAX_CLASSES classes each (4 x 32 KB
+// at four categories).  Allocated on first use for an eighth of the tips' number of products (a product stands over
+// eight tips), 8 at least, 256 MB at most; no memory: such parents are stored as before.
+static size_t quad_product_table_doubles(const pllhip_ctx * c) { return (size_t)PLLHIP_QUAD_MAX_CLASSES * c->span; }
+double * pllhip_quad_product_table(const pllhip_ctx * c, unsigned int slot, unsigned int which)
+{
+  return c->quad_product_pool + ((size_t)slot * 2u + which) * quad_product_table_doubles(c);
+}
+int pllhip_quad_product_slot(pllhip_ctx * c, unsigned int clv, std::vector<unsigned char> & taken)
+{
+  if (!c->quad_product_pool)
+  {
+    if (c->quad_product_pool_failed) return -1;
+    const size_t one = 2u * quad_product_table_doubles(c) * sizeof(double);
+    const size_t slots = std::min<size_t>(std::max<size_t>(8, c->sh.tips / 8u), ((size_t)256 << 20) / one);
+    if (!slots || hipMalloc((void **)&c->quad_product_pool, slots * one) != hipSuccess)
+    {
+      (void)hipGetLastError();
+      c->quad_product_pool = nullptr;
+      c->quad_product_pool_failed = true;
+      return -1;
+    }
+    c->quad_product_owner.assign(slots, -1);
+  }
+  taken.resize(c->quad_product_owner.size(), 0);
+  // (the product this CLV is now keeps its place: whatever reads the old value is served before the tables are written)
+  int slot = -1;
+  for (size_t s = 0; s < c->quad_product_owner.size() && slot < 0; ++s)
+    if (c->quad_product_owner[s] == (int)clv && !taken[s]) slot = (int)s;
+  for (size_t s = 0; s < c->quad_product_owner.size() && slot < 0; ++s)
+    if (c->quad_product_owner[s] < 0 && !taken[s]) slot = (int)s;
+  if (slot >= 0) taken[slot] = 1;
+  return slot;
+}
+
+static int quad_products_materialise(pllhip_ctx * c, const std::vector<unsigned int> & todo)
+{
+  const unsigned int span2 = (unsigned int)(c->span / 2);
+  const size_t total = (size_t)c->sh.sites * span2;
+  const unsigned int gx = (unsigned int)std::min<size_t>(std::max<size_t>(1, (total + 255) / 256), (size_t)c->num_cus * 8);
+  const bool nt = pllhip_use_nt(c);
+  for (size_t first = 0; first < todo.size(); first += PLLHIP_QUAD_PRODUCT_BATCH)
+  {
+    const unsigned int m = (unsigned int)std::min<size_t>(PLLHIP_QUAD_PRODUCT_BATCH, todo.size() - first);
+    QuadProductJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    for (unsigned int k = 0; k < m; ++k)
+    {
+      const unsigned int i = todo[first + k];
+      const pllhip_ctx::deferred_clv & d = c->deferred[i];
+      jobs.row_a[k] = pllhip_quad_row_ptr(c, d.qrow[0], d.qtips[0]);
+      jobs.row_b[k] = pllhip_quad_row_ptr(c, d.qrow[1], d.qtips[1]);
+      // (cannot happen while quad_rows.hip stores every product before a row changes hands: a guard against reading a
+      // row that is another quad's)
+      if (!jobs.row_a[k] || !jobs.row_b[k] || !c->quad_product_pool || d.qslot >= c->quad_product_owner.size())
+      {
+        pllhip_set_error("quad product %u: its quad rows or tables are gone", i);
+        return -1;
+      }
+      jobs.qa[k] = reinterpret_cast<const pll_v2d *>(pllhip_quad_product_table(c, d.qslot, 0));
+      jobs.qb[k] = reinterpret_cast<const pll_v2d *>(pllhip_quad_product_table(c, d.qslot, 1));
+      jobs.clv[k] = reinterpret_cast<pll_v2d *>(c->clv[i]);
+      jobs.counts[k] = pllhip_scaler_ptr(c, d.scaler);
+    }
+    if (nt) k_quad_product_materialise<true><<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, c->tip_stride);
+    else k_quad_product_materialise<false><<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, c->tip_stride);
+    HIP_TRY(hipGetLastError());
+    ++c->quad_product_stats[2];
+  }
+  c->quad_product_stats[3] += todo.size();
+  return 0;
+}
+
 double * pllhip_deferred_table(pllhip_ctx * c, unsigned int idx, unsigned int which)
 {
   if (!c->defer_pool)
@@ -134,7 +255,12 @@ static void deferred_clear(pllhip_ctx * c, unsigned int idx)
   --c->n_deferred;
   if (d.pair) --c->n_unstored;
   if (d.folded) --c->n_folded;
-  d.pair = d.folded = false;
+  if (d.quad)
+  {
+    --c->n_quad_products;
+    if (d.qslot < c->quad_product_owner.size() && c->quad_product_owner[d.qslot] == (int)idx) c->quad_product_owner[d.qslot] = -1;
+  }
+  d.pair = d.folded = d.quad = false;
   ++c->defer_epoch;
 }
 
@@ -159,6 +285,22 @@ int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
         todo.push_back(idx[k]);
   if (todo.empty()) return 0;
   HIP_TRY(hipSetDevice(c->sh.device));
+  // (quad products: a launch of their own kernel, counted on their own -- the batches below are what they were.  They
+  // are served first and are cleared once their launch is enqueued: should a batch below then fail, the call returns
+  // its error with the quad products already stored -- their bytes are in HBM, nothing is lost)
+  if (c->n_quad_products)
+  {
+    std::vector<unsigned int> quads, rest;
+    for (unsigned int i : todo) (c->deferred[i].quad ? quads : rest).push_back(i);
+    if (!quads.empty())
+    {
+      const int rc = quad_products_materialise(c, quads);
+      if (rc) return rc;
+      for (unsigned int i : quads) deferred_clear(c, i);
+      todo.swap(rest);
+      if (todo.empty()) return 0;
+    }
+  }
   const unsigned int span2 = (unsigned int)(c->span / 2);
   const size_t total = (size_t)c->sh.sites * span2;
   const unsigned int gx = (unsigned int)std::min<size_t>(std::max<size_t>(1, (total + 255) / 256), (size_t)c->num_cus * 8);
@@ -237,16 +379,57 @@ extern "C" int pllhip_set_unstored_pairs(pllhip_ctx_t * c, int on)
   pllhip_edge_terms_drop(c);
   PLLHIP_ALL_SHARDS(c, pllhip_set_unstored_pairs(s, on));
   if (c->unstored_pairs == (on != 0)) return 0;
-  if (!on && c->n_unstored)
+  if (!on && (c->n_unstored || c->n_quad_products))
   {
+    // (quad products go with the rest: no list has one while pair products are off)
     std::vector<unsigned int> pairs;
     for (unsigned int i = 0; i < c->deferred.size(); ++i)
-      if (c->deferred[i].on && c->deferred[i].pair) pairs.push_back(i);
+      if (c->deferred[i].on && (c->deferred[i].pair || c->deferred[i].quad)) pairs.push_back(i);
     const int rc = pllhip_deferred_materialise(c, pairs.data(), (int)pairs.size());
     if (rc) return rc;
   }
   c->unstored_pairs = on != 0;
   ++c->defer_epoch;
+  return 0;
+}
+
+int pllhip_quad_products_flush(pllhip_ctx * c)
+{
+  if (!c->n_quad_products) return 0;
+  std::vector<unsigned int> quads;
+  for (unsigned int i = 0; i < c->deferred.size(); ++i)
+    if (c->deferred[i].on && c->deferred[i].quad) quads.push_back(i);
+  return pllhip_deferred_materialise(c, quads.data(), (int)quads.size());
+}
+
+// Quad products (see above) on or off; off stores those there are.  pllhip_set_deferral(ctx, 0) and
+// pllhip_set_unstored_pairs(ctx, 0) turn them off with the rest, and so does pllhip_set_quad_rows(ctx, 0, ...).
+extern "C" int pllhip_set_unstored_quad_products(pllhip_ctx_t * c, int on)
+{
+  pllhip_edge_terms_drop(c);
+  PLLHIP_ALL_SHARDS(c, pllhip_set_unstored_quad_products(s, on));
+  if (c->unstored_quad_products == (on != 0)) return 0;
+  if (!on)
+  {
+    const int rc = pllhip_quad_products_flush(c);
+    if (rc) return rc;
+  }
+  c->unstored_quad_products = on != 0;
+  ++c->defer_epoch;
+  return 0;
+}
+
+// {quad products live now, ops left unstored in total, materialise launches, CLVs materialised}
+extern "C" int pllhip_quad_product_stats(pllhip_ctx_t * c, unsigned long long * out4)
+{
+  for (int t = 0; t < 4; ++t) out4[t] = 0;
+  auto add = [&](const pllhip_ctx * s) {
+    out4[0] += s->n_quad_products;
+    for (int t = 1; t < 4; ++t) out4[t] += s->quad_product_stats[t];
+  };
+  if (!c->shards.empty())
+    for (pllhip_ctx * s : c->shards) add(s);
+  else add(c);
   return 0;
 }
 
@@ -287,12 +470,12 @@ extern "C" int pllhip_deferred_stats(pllhip_ctx_t * c, unsigned long long * out4
   {
     for (pllhip_ctx * s : c->shards)
     {
-      out4[0] += s->n_deferred - s->n_unstored;
+      out4[0] += s->n_deferred - s->n_unstored - s->n_quad_products;
       for (int t = 1; t < 4; ++t) out4[t] += s->defer_stats[t];
     }
     return 0;
   }
-  out4[0] = c->n_deferred - c->n_unstored;
+  out4[0] = c->n_deferred - c->n_unstored - c->n_quad_products;
   for (int t = 1; t < 4; ++t) out4[t] = c->defer_stats[t];
   return 0;
 }

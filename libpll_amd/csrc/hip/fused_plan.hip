@@ -538,68 +538,115 @@ bool pllhip_fused_edge_end_stored(const FusedGeom & geom, const FusedDeferral & 
          std::find(dd.dropped.begin(), dd.dropped.end(), clv) != dd.dropped.end();
 }
 
+// What pllhip_fused_unstored and pllhip_fused_quad_products ask of a walked op alike (partials_fused.hpp): how the list
+// treats its parent and its scale buffer, and what the finished plans reload from HBM.
+namespace
+{
+struct UnstoredConditions
+{
+  static constexpr unsigned int NONE = ~0u;
+  const FusedGeom & geom;
+  const pllhip_op_t * ops;
+  unsigned int count;
+  const FusedEdge * edge;
+  const unsigned char * pinned;
+  // how the list treats every CLV and scale buffer (the cherries' rule: pllhip_fused_deferral)
+  std::vector<unsigned int> nwrites, first_read, sc_nwrites, sc_first_read;
+  std::vector<int> sc_reader; // the one CLV a scale buffer is read with (-1 nobody, -2 several)
+  std::vector<const double *> reloaded; // what some op of the plan copies back from HBM
+
+  UnstoredConditions(const FusedGeom & geom_, const pllhip_op_t * ops_, unsigned int count_,
+                     const std::vector<std::vector<FusedOp>> & plans, const FusedEdge * edge_, const unsigned char * pinned_)
+    : geom(geom_), ops(ops_), count(count_), edge(edge_), pinned(pinned_), nwrites(geom_.nclv, 0), first_read(geom_.nclv, NONE),
+      sc_nwrites(geom_.nsc, 0), sc_first_read(geom_.nsc, NONE), sc_reader(geom_.nsc, -1)
+  {
+    for (unsigned int k = 0; k < count; ++k)
+    {
+      const pllhip_op_t & op = ops[k];
+      ++nwrites[op.parent_clv];
+      if (op.parent_scaler >= 0) ++sc_nwrites[op.parent_scaler];
+      const unsigned int kid[2] = {op.child1_clv, op.child2_clv};
+      const int ksc[2] = {op.child1_scaler, op.child2_scaler};
+      for (int o = 0; o < 2; ++o)
+      {
+        if (first_read[kid[o]] == NONE) first_read[kid[o]] = k;
+        if (ksc[o] < 0) continue;
+        if (sc_first_read[ksc[o]] == NONE) sc_first_read[ksc[o]] = k;
+        if (sc_reader[ksc[o]] == -1) sc_reader[ksc[o]] = (int)kid[o];
+        else if (sc_reader[ksc[o]] != (int)kid[o]) sc_reader[ksc[o]] = -2;
+      }
+    }
+    for (const auto & plan : plans)
+      for (const FusedOp & f : plan)
+      {
+        if ((f.dma_flags & 1) && f.left_hbm) reloaded.push_back(f.left_hbm);
+        if ((f.dma_flags & 2) && f.right_hbm) reloaded.push_back(f.right_hbm);
+      }
+    if (edge)
+    {
+      if ((edge->op.dma_flags & 1) && edge->op.left_hbm) reloaded.push_back(edge->op.left_hbm);
+      if ((edge->op.dma_flags & 2) && edge->op.right_hbm) reloaded.push_back(edge->op.right_hbm);
+    }
+  }
+
+  // a kind-3 op kept in a slot whose parent nothing but its readers' slots needs
+  bool pass(const FusedOp & f) const
+  {
+    if (f.kind != 3 || f.pslot < 0 || f.list_pos < 0 || (unsigned int)f.list_pos >= count) return false;
+    const unsigned int k = (unsigned int)f.list_pos;
+    const pllhip_op_t & op = ops[k];
+    const unsigned int p = op.parent_clv;
+    const int s = op.parent_scaler;
+    if (geom.is_tip(p) || (pinned && pinned[p])) return false;
+    if (edge && (p == edge->parent_clv || p == edge->child_clv)) return false;
+    if (nwrites[p] != 1 || first_read[p] == NONE || first_read[p] <= k) return false;
+    bool foreign = false; // read with counts that are not its own
+    for (unsigned int r = k + 1; r < count && !foreign; ++r)
+      foreign = (ops[r].child1_clv == p && ops[r].child1_scaler != -1 && ops[r].child1_scaler != s) ||
+                (ops[r].child2_clv == p && ops[r].child2_scaler != -1 && ops[r].child2_scaler != s);
+    if (foreign) return false;
+    if (s >= 0 && (sc_nwrites[s] != 1 || (sc_reader[s] != -1 && sc_reader[s] != (int)p) ||
+                   (sc_first_read[s] != NONE && sc_first_read[s] <= k)))
+      return false;
+    return std::find(reloaded.begin(), reloaded.end(), (const double *)f.parent) == reloaded.end();
+  }
+};
+}
+
 // Which gathered-gathered parents of a planned list are left unstored (partials_fused.hpp).
 unsigned int pllhip_fused_unstored(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
                                    std::vector<std::vector<FusedOp>> & plans, const FusedEdge * edge,
                                    const unsigned char * pinned)
 {
-  const size_t nclv = geom.nclv, nsc = geom.nsc;
-  const unsigned int NONE = ~0u;
-  // how the list treats every CLV and scale buffer (the cherries' rule: pllhip_fused_deferral)
-  std::vector<unsigned int> nwrites(nclv, 0), first_read(nclv, NONE), sc_nwrites(nsc, 0), sc_first_read(nsc, NONE);
-  std::vector<int> sc_reader(nsc, -1); // the one CLV a scale buffer is read with (-1 nobody, -2 several)
-  for (unsigned int k = 0; k < count; ++k)
-  {
-    const pllhip_op_t & op = ops[k];
-    ++nwrites[op.parent_clv];
-    if (op.parent_scaler >= 0) ++sc_nwrites[op.parent_scaler];
-    const unsigned int kid[2] = {op.child1_clv, op.child2_clv};
-    const int ksc[2] = {op.child1_scaler, op.child2_scaler};
-    for (int o = 0; o < 2; ++o)
-    {
-      if (first_read[kid[o]] == NONE) first_read[kid[o]] = k;
-      if (ksc[o] < 0) continue;
-      if (sc_first_read[ksc[o]] == NONE) sc_first_read[ksc[o]] = k;
-      if (sc_reader[ksc[o]] == -1) sc_reader[ksc[o]] = (int)kid[o];
-      else if (sc_reader[ksc[o]] != (int)kid[o]) sc_reader[ksc[o]] = -2;
-    }
-  }
-  // what some op of the plan copies back from HBM
-  std::vector<const double *> reloaded;
-  for (const auto & plan : plans)
-    for (const FusedOp & f : plan)
-    {
-      if ((f.dma_flags & 1) && f.left_hbm) reloaded.push_back(f.left_hbm);
-      if ((f.dma_flags & 2) && f.right_hbm) reloaded.push_back(f.right_hbm);
-    }
-  if (edge)
-  {
-    if ((edge->op.dma_flags & 1) && edge->op.left_hbm) reloaded.push_back(edge->op.left_hbm);
-    if ((edge->op.dma_flags & 2) && edge->op.right_hbm) reloaded.push_back(edge->op.right_hbm);
-  }
+  const UnstoredConditions rule(geom, ops, count, plans, edge, pinned);
   unsigned int n = 0;
   for (auto & plan : plans)
     for (FusedOp & f : plan)
     {
       f.unstored = 0;
-      if (f.kind != 3 || f.pslot < 0 || f.list_pos < 0 || (unsigned int)f.list_pos >= count) continue;
       if (f.prod[0] || f.prod[1]) continue; // (a reader of folded products: its value needs the whole mat-vec)
-      const unsigned int k = (unsigned int)f.list_pos;
-      const pllhip_op_t & op = ops[k];
-      const unsigned int p = op.parent_clv;
-      const int s = op.parent_scaler;
-      if (geom.is_tip(p) || (pinned && pinned[p])) continue;
-      if (edge && (p == edge->parent_clv || p == edge->child_clv)) continue;
-      if (nwrites[p] != 1 || first_read[p] == NONE || first_read[p] <= k) continue;
-      bool foreign = false; // read with counts that are not its own
-      for (unsigned int r = k + 1; r < count && !foreign; ++r)
-        foreign = (ops[r].child1_clv == p && ops[r].child1_scaler != -1 && ops[r].child1_scaler != s) ||
-                  (ops[r].child2_clv == p && ops[r].child2_scaler != -1 && ops[r].child2_scaler != s);
-      if (foreign) continue;
-      if (s >= 0 && (sc_nwrites[s] != 1 || (sc_reader[s] != -1 && sc_reader[s] != (int)p) ||
-                     (sc_first_read[s] != NONE && sc_first_read[s] <= k)))
-        continue;
-      if (std::find(reloaded.begin(), reloaded.end(), (const double *)f.parent) != reloaded.end()) continue;
+      if (!rule.pass(f)) continue;
+      f.unstored = 1;
+      ++n;
+    }
+  return n;
+}
+
+// Which parents over two quads are left unstored (partials_fused.hpp).
+unsigned int pllhip_fused_quad_products(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
+                                        std::vector<std::vector<FusedOp>> & plans,
+                                        const std::vector<std::vector<unsigned char>> & taken, const FusedEdge * edge,
+                                        const unsigned char * pinned)
+{
+  const UnstoredConditions rule(geom, ops, count, plans, edge, pinned);
+  unsigned int n = 0;
+  for (size_t sg = 0; sg < plans.size() && sg < taken.size(); ++sg)
+    for (size_t pos = 0; pos < plans[sg].size() && 2 * pos + 1 < taken[sg].size(); ++pos)
+    {
+      FusedOp & f = plans[sg][pos];
+      // (read as quads, the reader's value is the product of two gathered table rows: a pair product's shape)
+      if (f.unstored || !f.prod[0] || !f.prod[1] || !taken[sg][2 * pos] || !taken[sg][2 * pos + 1]) continue;
+      if (!rule.pass(f)) continue;
       f.unstored = 1;
       ++n;
     }
@@ -1075,6 +1122,18 @@ static void dry_slots_out(const FusedOp & f, int * six)
   for (int t = 0; t < 6; ++t) six[t] = v[t];
 }
 
+// (pllhip_fused_plan_dry_quad_products) the final walk as the launch sees it: the plans, the list they were made of --
+// the caller's without the deferred and the folded ops --, each of its ops' place in the caller's list, the gathered CLVs
+struct DryFinal
+{
+  std::vector<std::vector<FusedOp>> plans;
+  std::vector<pllhip_op_t> ops;
+  std::vector<unsigned int> to_list;
+  std::vector<unsigned char> as_tip;
+  bool has_edge = false;
+  FusedEdge edge;
+};
+
 // The planner with deferred cherries, without a device (tests/test_host_deferred_plan.py).  old_deferred / old_scaler /
 // pinned: per CLV index, may be NULL (pllhip_fused_deferral).  Out: *nkept kept ops in walk order as positions in
 // the caller's list (order_out), six numbers per kept op as pllhip_fused_plan_dry gives them (slots_out), two operand
@@ -1083,7 +1142,8 @@ static void dry_slots_out(const FusedOp & f, int * six)
 // (materialise_out, dropped_out: at most clv indices each, counts in *nmaterialise, *ndropped).
 // Returns 0, 1 if the kernel does not take the list, < 0 on error.
 // (edge4 not null: pllhip_fused_plan_dry_edge -- {parent_clv, parent_scaler, child_clv, child_scaler}; `nslots` is then
-// not used: the slot counts are those of 12 and of 8 waves per CU at `rate_cats` categories)
+// not used: the slot counts are those of 12 and of 8 waves per CU at `rate_cats` categories; final_out not null: the
+// final walk as well, DryFinal above)
 static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
                              int pattern_tip, const pllhip_op_t * ops, unsigned int count, unsigned int nslots,
                              const unsigned char * old_deferred, const int * old_scaler,
@@ -1094,7 +1154,7 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
                              const int * edge4, unsigned int rate_cats, int * edge_out,
                              unsigned char * unstored_out = nullptr, unsigned char * folded_out = nullptr,
                              unsigned int * gathers_out = nullptr, unsigned int * batch_out = nullptr,
-                             unsigned int * nbatches_out = nullptr, int * kinds_out = nullptr)
+                             unsigned int * nbatches_out = nullptr, int * kinds_out = nullptr, DryFinal * final_out = nullptr)
 {
   FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0};
   if (dry_ops_in_range("pllhip_fused_plan_dry_deferred", geom, ops, count)) return -1;
@@ -1233,6 +1293,16 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
     }
   }
   if (reloads_out) *reloads_out = w.plan.reloads;
+  if (final_out)
+  {
+    final_out->plans = w.plan.plans;
+    final_out->ops = w.replanned ? w.fl.ops : kept;
+    final_out->to_list.resize(final_out->ops.size());
+    for (unsigned int i = 0; i < final_out->ops.size(); ++i) final_out->to_list[i] = where[w.replanned ? w.fl.where[i] : i];
+    final_out->as_tip = w.replanned ? w.fl.as_tip : d.as_tip;
+    final_out->has_edge = edge4 != nullptr;
+    final_out->edge = w.edge;
+  }
   if (gathers_out)
   {
     // What each walked op gathers, in the order the kernel does (partials_fused.hip: fused_seg_gathers): a reader of
@@ -1301,13 +1371,14 @@ extern "C" int pllhip_fused_plan_dry_rows(unsigned int tips, unsigned int clv_bu
 // ops_out[3 pos ..]: walked op pos's kind, its gathers and how many of them are wide.  quads_out[i]: -1 where op i is no
 // folded product, else the rule's answer (0: read as a quad; else the reason, pllhip.h).  counts_out[2]: quads taken,
 // and refused (of the products over two cherries, as pllhip_quad_row_stats counts them).
-extern "C" int pllhip_fused_plan_dry_quads(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
-                                           int pattern_tip, unsigned int rate_cats, int rate_scalers, const pllhip_op_t * ops,
-                                           unsigned int count, unsigned int nslots, const unsigned char * pinned, const int * edge4,
-                                           unsigned int sites, int quads_on, unsigned int min_sites_per_class,
-                                           const unsigned int * classes, const double * bounds, unsigned int * nkept,
-                                           unsigned int * order_out, unsigned char * folded_out, int * ops_out, int * quads_out,
-                                           unsigned int * counts_out)
+// (products_out / bytes_out: pllhip_fused_plan_dry_quad_products, below)
+static int plan_dry_quads(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                          int pattern_tip, unsigned int rate_cats, int rate_scalers, const pllhip_op_t * ops,
+                          unsigned int count, unsigned int nslots, const unsigned char * pinned, const int * edge4,
+                          unsigned int sites, int quads_on, unsigned int min_sites_per_class,
+                          const unsigned int * classes, const double * bounds, unsigned int * nkept,
+                          unsigned int * order_out, unsigned char * folded_out, int * ops_out, int * quads_out,
+                          unsigned int * counts_out, unsigned char * products_out, unsigned int * bytes_out)
 {
   if (!(rate_cats == 1 || rate_cats == 2 || rate_cats == 4) || !classes || !nkept || !order_out || !folded_out || !ops_out || !quads_out ||
       !counts_out)
@@ -1316,12 +1387,14 @@ extern "C" int pllhip_fused_plan_dry_quads(unsigned int tips, unsigned int clv_b
     return -1;
   }
   int edge_out[8];
+  DryFinal fin;
   std::vector<unsigned char> unstored(count, 0), deferred(count, 0);
   std::vector<unsigned int> gathers(12 * (size_t)count + 12, 0u);
   std::vector<int> kinds(3 * (size_t)count + 3, 0);
   const int rc = plan_dry_deferred(tips, clv_buffers, scale_buffers, pattern_tip, ops, count, nslots, nullptr, nullptr, pinned, nkept,
                                    order_out, nullptr, nullptr, deferred.data(), nullptr, nullptr, nullptr, nullptr, nullptr, edge4,
-                                   rate_cats, edge_out, unstored.data(), folded_out, gathers.data(), nullptr, nullptr, kinds.data());
+                                   rate_cats, edge_out, unstored.data(), folded_out, gathers.data(), nullptr, nullptr, kinds.data(),
+                                   products_out ? &fin : nullptr);
   if (rc) return rc;
   for (unsigned int i = 0; i < count; ++i) quads_out[i] = -1;
   counts_out[0] = counts_out[1] = 0;
@@ -1389,7 +1462,66 @@ extern "C" int pllhip_fused_plan_dry_quads(unsigned int tips, unsigned int clv_b
     ops_out[3 * pos + 1] = ng;
     ops_out[3 * pos + 2] = wide;
   }
+  if (!products_out) return 0;
+  // the launch's step behind the quads' (partials_fused.hip): pllhip_fused_quad_products on the final walk
+  for (unsigned int i = 0; i < count; ++i) products_out[i] = 0;
+  FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0, fin.as_tip.data()};
+  const std::vector<std::vector<unsigned char>> marks(1, taken);
+  pllhip_fused_quad_products(geom, fin.ops.data(), (unsigned int)fin.ops.size(), fin.plans, marks, fin.has_edge ? &fin.edge : nullptr, pinned);
+  // ... and the plan's bytes per site, as DESIGN.md 2.0 counts them: one write per entry of a stored CLV and per count,
+  // one read per character of the tips under the list
+  unsigned int bytes = 0;
+  for (const FusedOp & f : fin.plans[0])
+  {
+    if (f.list_pos < 0 || (size_t)f.list_pos >= fin.to_list.size()) continue;
+    if (f.unstored && f.prod[0] && f.prod[1]) products_out[fin.to_list[f.list_pos]] = 1;
+    bytes += (f.unstored ? 0u : 4u * rate_cats * 8u) + (f.pscaler ? (rate_scalers ? 4u * rate_cats : 4u) : 0u);
+  }
+  std::vector<unsigned char> read(tips, 0);
+  for (unsigned int i = 0; pattern_tip && i < count; ++i)
+  {
+    if (ops[i].child1_clv < tips) read[ops[i].child1_clv] = 1;
+    if (ops[i].child2_clv < tips) read[ops[i].child2_clv] = 1;
+  }
+  for (unsigned int t = 0; t < tips; ++t) bytes += read[t];
+  if (bytes_out) *bytes_out = bytes;
   return 0;
+}
+
+extern "C" int pllhip_fused_plan_dry_quads(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                           int pattern_tip, unsigned int rate_cats, int rate_scalers, const pllhip_op_t * ops,
+                                           unsigned int count, unsigned int nslots, const unsigned char * pinned, const int * edge4,
+                                           unsigned int sites, int quads_on, unsigned int min_sites_per_class,
+                                           const unsigned int * classes, const double * bounds, unsigned int * nkept,
+                                           unsigned int * order_out, unsigned char * folded_out, int * ops_out, int * quads_out,
+                                           unsigned int * counts_out)
+{
+  return plan_dry_quads(tips, clv_buffers, scale_buffers, pattern_tip, rate_cats, rate_scalers, ops, count, nslots, pinned, edge4, sites,
+                        quads_on, min_sites_per_class, classes, bounds, nkept, order_out, folded_out, ops_out, quads_out, counts_out,
+                        nullptr, nullptr);
+}
+
+// Quad products without a device (deferred.hip; tests/test_host_quad_products.py): pllhip_fused_plan_dry_quads, then the
+// rule the launch applies behind the quads' (pllhip_fused_quad_products).  products_out[i] = 1: op i of the caller's
+// list is walked over two taken quads and its parent is not stored.  *bytes_out: the plan's bytes per site -- one write
+// per entry of every stored CLV of the walk and per count, one read per character of the tips under the list.
+extern "C" int pllhip_fused_plan_dry_quad_products(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                                   int pattern_tip, unsigned int rate_cats, int rate_scalers, const pllhip_op_t * ops,
+                                                   unsigned int count, unsigned int nslots, const unsigned char * pinned,
+                                                   const int * edge4, unsigned int sites, int quads_on,
+                                                   unsigned int min_sites_per_class, const unsigned int * classes,
+                                                   const double * bounds, unsigned int * nkept, unsigned int * order_out,
+                                                   unsigned char * folded_out, int * ops_out, int * quads_out,
+                                                   unsigned int * counts_out, unsigned char * products_out, unsigned int * bytes_out)
+{
+  if (!products_out)
+  {
+    pllhip_set_error("pllhip_fused_plan_dry_quad_products: products_out");
+    return -1;
+  }
+  return plan_dry_quads(tips, clv_buffers, scale_buffers, pattern_tip, rate_cats, rate_scalers, ops, count, nslots, pinned, edge4, sites,
+                        quads_on, min_sites_per_class, classes, bounds, nkept, order_out, folded_out, ops_out, quads_out, counts_out,
+                        products_out, bytes_out);
 }
 
 extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,

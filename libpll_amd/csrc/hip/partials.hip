@@ -736,6 +736,7 @@ struct DnaListKept
   std::vector<unsigned int> rows;          // per op of `ops`, four: tip index + 1 of the rows its two gathered factors are
                                            // indexed by (0 none) -- what an unstored pair product is kept with
   std::vector<pllhip_ctx::unstored_product> new_unstored; // per op whose parent the plan being launched leaves unstored
+  FusedQuadProducts quad_products;         // what the launch is to know to leave parents over two quads unstored, and which it left
   // the list's further state, step by step (update_partials_dna_list)
   std::vector<PartialsArgs> args;          // resolve_op's of the ops the kernel runs
   std::vector<int> kinds;
@@ -773,12 +774,13 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
   // (a pair product left unstored by an earlier call has no table a reader could gather from: where a cherry would
   // be read from its kept table, it is stored first -- an ordinary buffer to this list)
   // (read, not written: an index the list writes is a gathered operand because the list defers the cherry it becomes)
-  if (c->n_unstored)
+  // (a quad product likewise)
+  if (c->n_unstored || c->n_quad_products)
   {
     std::vector<unsigned char> written(c->clv.size(), 0);
     for (unsigned int i = 0; i < count; ++i) written[ops[i].parent_clv] = 1;
     for (size_t i = 0; i < c->clv.size(); ++i)
-      if (oldf[i] && c->deferred[i].pair && dd.as_tip[i] && !written[i])
+      if (oldf[i] && (c->deferred[i].pair || c->deferred[i].quad) && dd.as_tip[i] && !written[i])
       {
         dd.as_tip[i] = 0;
         dd.materialise.push_back((unsigned int)i);
@@ -923,6 +925,7 @@ static bool replay_kept_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsig
   pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
   c->defer_stats[1] += c->fused_last_deferred.size();
   c->unstored_stats[1] += c->fused_last_unstored.size();
+  c->quad_product_stats[1] += c->fused_last_quad_products.size();
   c->fold_stats[1] += c->fused_last_nfolded;
   *rc = pllhip_relaunch_fused(c);
   if (*rc == 0 && c->fused_last_edge)
@@ -1054,8 +1057,22 @@ static int launch_list(pllhip_ctx * c, DnaListKept & k)
     }
     attach_tables(c, k);
     c->fused_last_nfolded = w.nfolded; // (the launch sizes its share of counter tiles by the list the caller handed over)
-    rc = pllhip_launch_fused(c, w.plan.plans, w.plan.nslots, keep_jobs, w.plan.folded ? &w.edge : nullptr);
+    // Quad products (deferred.hip): only a folded walk has quads; the rule runs in the launch, once it has picked them,
+    // over the list that walk was planned from
+    FusedQuadProducts * qp = nullptr;
+    if (w.replanned && c->unstored_quad_products && c->unstored_pairs && c->cherry_deferral && c->quad_rows_on)
+    {
+      qp = &k.quad_products;
+      qp->geom = FusedGeom{c->clv.size(), c->sh.scale_buffers, c->sh.tips, c->sh.pattern_tip != 0, w.fl.as_tip.data()};
+      qp->ops = w.fl.ops.data();
+      qp->count = (unsigned int)w.fl.ops.size();
+      qp->edge = k.edge_ok ? &w.edge : nullptr;
+      qp->pinned = c->clv_pinned.data();
+    }
+    k.quad_products.left.clear();
+    rc = pllhip_launch_fused(c, w.plan.plans, w.plan.nslots, keep_jobs, w.plan.folded ? &w.edge : nullptr, qp);
   }
+  if (rc != 0) k.quad_products.left.clear();
   if (rc != 0) c->fused_last_nfolded = 0;
   return rc;
 }
@@ -1097,6 +1114,26 @@ static void commit_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsigned i
     ++c->n_deferred;
     ++c->n_unstored;
   }
+  for (const pllhip_ctx::quad_product & n : k.quad_products.left)
+  {
+    pllhip_deferred_drop(c, n.clv);
+    pllhip_ctx::deferred_clv & d = c->deferred[n.clv];
+    d.on = d.quad = true;
+    d.qslot = n.qslot;
+    for (int s = 0; s < 2; ++s)
+    {
+      d.qrow[s] = n.qrow[s];
+      memcpy(d.qtips[s], n.qtips[s], sizeof(d.qtips[s]));
+    }
+    d.scaler = n.scaler;
+    // (its counts are in HBM and define the CLV, as a pair product's do)
+    if (n.scaler >= 0) c->deferred_sc_owner[n.scaler] = (int)n.clv;
+    c->quad_product_owner[n.qslot] = (int)n.clv;
+    ++c->n_deferred;
+    ++c->n_quad_products;
+  }
+  c->quad_product_stats[1] += k.quad_products.left.size();
+  c->fused_last_quad_products = k.quad_products.left;
   c->defer_stats[1] += k.new_deferred.size();
   c->unstored_stats[1] += k.new_unstored.size();
   c->fold_stats[1] += k.walk.nfolded;

@@ -126,7 +126,8 @@ __device__ __forceinline__ unsigned int rec_pcnt(const Rec & r) { return r.w[15]
 // Fa[pa][rate][k] * Fb[pb][rate][k] -- (pa, pb) the class's pattern; Fa, Fb the two cherries' factors as the jobs of
 // kind 2 / 3 below form them, the multiplication the list kernel's product() does, the dot product its pl.dot() /
 // pr.dot().  Self-contained like kind 2: every factor is formed here from the matrices (or the kept table).  The job
-// takes two records: this one {lmat, rmat: cherry a's tip matrices, pmat: P, kept: the patterns, pad: the classes} and
+// takes two records: this one {lmat, rmat: cherry a's tip matrices, pmat: P, kept: the patterns, pad: the classes,
+// copy: null, or where every entry is written as well -- the kept table of an unstored quad product, deferred.hip} and
 // the next, kind 5 {lmat, rmat: cherry b's, pmat / kept: the matrices Fa / Fb are read with, copy / pad: the kept
 // tables of a / b where they were deferred by an earlier call, else null}.
 // A launch of its own behind k_dna_pair_tables, made only for a list that reads a quad: the lists without one keep
@@ -149,6 +150,7 @@ __global__ __launch_bounds__(256) void k_dna_quad_tables(const FusedPairJob * __
   const PLL_GLOBAL double * side_p[2] = {(const PLL_GLOBAL double *)jb.pmat, (const PLL_GLOBAL double *)jb.kept};
   const PLL_GLOBAL double * side_kept[2] = {(const PLL_GLOBAL double *)jb.copy, (const PLL_GLOBAL double *)jb.pad};
   double * tab = ja.tab;
+  double * copy = ja.copy; // (an unstored quad product's kept table: the same values, deferred.hip)
   double p[4], pf[2][4][4], l[2][4][4], r[2][4][4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) p[k] = pm[ki * 4u + k];
@@ -178,7 +180,9 @@ __global__ __launch_bounds__(256) void k_dna_quad_tables(const FusedPairJob * __
 #pragma unroll
       for (int k = 0; k < 4; ++k) f[s][k] = dot4(pf[s][k], t[0], t[1], t[2], t[3]);
     }
-    tab[cls * ROW + ki] = dot4(p, f[0][0] * f[1][0], f[0][1] * f[1][1], f[0][2] * f[1][2], f[0][3] * f[1][3]);
+    const double q = dot4(p, f[0][0] * f[1][0], f[0][1] * f[1][1], f[0][2] * f[1][2], f[0][3] * f[1][3]);
+    tab[cls * ROW + ki] = q;
+    if (copy) copy[cls * ROW + ki] = q;
   }
 }
 
@@ -1213,9 +1217,11 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
     if (f.prod[0] || f.prod[1])
     {
       // (only what the planner folds: an inner-inner reader, presented as gathered-inner or gathered-gathered)
-      if (!f.prod[0] || (f.kind != 1 && f.kind != 3) || (f.kind == 3) != (f.prod[1] != 0) || f.unstored) return 1;
+      if (!f.prod[0] || (f.kind != 1 && f.kind != 3) || (f.kind == 3) != (f.prod[1] != 0)) return 1;
       // (quads: every product side of the op, or none -- a reader of a quad and a plain product is not built)
       const bool quad = quads && (*quads)[2 * (size_t)pos].taken && (!f.prod[1] || (*quads)[2 * (size_t)pos + 1].taken);
+      // (unstored: a quad product only -- both sides quads, the value two table rows' product: pllhip_fused_quad_products)
+      if (f.unstored && !(quad && f.prod[1])) return 1;
       for (int s = 0; s < (f.prod[1] ? 2 : 1); ++s)
       {
         if (f.g[s].type == FUSED_G_NONE || f.g2[s].type == FUSED_G_NONE || !f.pkeep[s][0] || !f.pkeep[s][1]) return 1;
@@ -1230,6 +1236,7 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
           x.qb[s] = f.g2[s];
           x.qkeep[s][0] = f.pkeep[s][0];
           x.qkeep[s][1] = f.pkeep[s][1];
+          if (f.unstored) x.copy[s] = f.keep[s];
           continue;
         }
         x.g[2 * s] = f.g[s];
@@ -1468,7 +1475,7 @@ static void fused_encode_segment(const FusedEncodeIn & in, const std::vector<Fus
         const FusedOperand & a = ga.gx[pos].qa[k], & b = ga.gx[pos].qb[k];
         for (unsigned int l = 0; l < lpr; ++l)
           out.rowtab[(size_t)ga.batch_of[pos] * 64 + lane0 + lpr + l] = (unsigned long long)(uintptr_t)g.row + in.tip_stride + l * 16u;
-        out.jobs.push_back(FusedPairJob{a.c_lmat, a.c_rmat, tab, 4ull, g.mat, (const double *)q.ref.patterns, nullptr, (unsigned long long)q.ref.n});
+        out.jobs.push_back(FusedPairJob{a.c_lmat, a.c_rmat, tab, 4ull, g.mat, (const double *)q.ref.patterns, ga.gx[pos].copy[k], (unsigned long long)q.ref.n});
         out.jobs.push_back(FusedPairJob{b.c_lmat, b.c_rmat, nullptr, 5ull, a.mat, b.mat,
                                         a.type == FUSED_G_CHERRY_KEPT ? const_cast<double *>(a.kept) : nullptr,
                                         b.type == FUSED_G_CHERRY_KEPT ? (unsigned long long)(uintptr_t)b.kept : 0ull});
@@ -1739,25 +1746,85 @@ static int fused_pick_quads(pllhip_ctx * c, const std::vector<std::vector<FusedO
 
 // A planned list: admitted, then -- and only then is anything of the device or the context touched -- its buffers,
 // the encoding, the upload, the launch.  Returns 1 if the list is not one the kernel takes.
-int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
-                        const std::vector<FusedPairJob> * keep_jobs, const FusedEdge * edge)
+// The parents over two taken quads that stay unstored (fused_plan.hip: pllhip_fused_quad_products), each with a place
+// in the pool of kept quad tables -- one that finds none is stored.  mine: the plans with those marks.  Returns how many.
+static unsigned int fused_mark_quad_products(pllhip_ctx * c, const std::vector<FusedQuadMarks> & quads, FusedQuadProducts & qp,
+                                             std::vector<std::vector<FusedOp>> & mine)
 {
+  std::vector<std::vector<unsigned char>> taken(quads.size());
+  for (size_t sg = 0; sg < quads.size(); ++sg)
+    for (const FusedQuadSide & q : quads[sg]) taken[sg].push_back(q.taken ? 1 : 0);
+  qp.left.clear();
+  if (!pllhip_fused_quad_products(qp.geom, qp.ops, qp.count, mine, taken, qp.edge, qp.pinned)) return 0;
+  std::vector<unsigned char> slots_taken;
+  for (size_t sg = 0; sg < mine.size(); ++sg)
+    for (size_t pos = 0; pos < mine[sg].size(); ++pos)
+    {
+      FusedOp & f = mine[sg][pos];
+      if (!f.unstored || !f.prod[0] || !f.prod[1]) continue;
+      const pllhip_op_t & op = qp.ops[f.list_pos];
+      const int slot = pllhip_quad_product_slot(c, op.parent_clv, slots_taken);
+      if (slot < 0)
+      {
+        f.unstored = 0;
+        continue;
+      }
+      pllhip_ctx::quad_product n;
+      memset(&n, 0, sizeof(n));
+      n.clv = op.parent_clv;
+      n.scaler = op.parent_scaler;
+      n.qslot = (unsigned int)slot;
+      auto tip_of = [&](const unsigned char * row) { return (unsigned int)((size_t)(row - c->tipchars) / c->tip_stride); };
+      for (int s = 0; s < 2; ++s)
+      {
+        f.keep[s] = pllhip_quad_product_table(c, (unsigned int)slot, (unsigned int)s);
+        n.qrow[s] = quads[sg][2 * pos + s].ref.slot;
+        const unsigned int t4[4] = {tip_of(f.g[s].row1), tip_of(f.g[s].row2), tip_of(f.g2[s].row1), tip_of(f.g2[s].row2)};
+        memcpy(n.qtips[s], t4, sizeof(t4));
+      }
+      qp.left.push_back(n);
+    }
+  return (unsigned int)qp.left.size();
+}
+
+int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans_in, unsigned int nslots,
+                        const std::vector<FusedPairJob> * keep_jobs, const FusedEdge * edge, FusedQuadProducts * quad_products)
+{
+  const std::vector<std::vector<FusedOp>> * use = &plans_in;
+  std::vector<std::vector<FusedOp>> mine;
+  if (quad_products) quad_products->left.clear();
   FusedAdmitted adm;
-  if (fused_admit(c, plans, nslots, edge, adm)) return 1;
+  if (fused_admit(c, plans_in, nslots, edge, adm)) return 1;
   // Quad rows: which folded products of the admitted list are read from a table of classes.  Their rows are found or
   // built first (the class counts decide), then the list is admitted once more with them; a list the kernel does not
   // take that way -- more character batches than it encodes -- runs as it was admitted.
   std::vector<FusedQuadMarks> quads;
   std::vector<unsigned int> quad_mats;
   unsigned int by_bound = 0;
-  int rc = fused_pick_quads(c, plans, quads, quad_mats, &by_bound);
+  int rc = fused_pick_quads(c, plans_in, quads, quad_mats, &by_bound);
   if (rc < 0 || rc > 1) return rc;
   if (rc == 1)
   {
+    // (quad products: the rule follows the quads; a list the kernel does not take with them runs with its quads alone)
+    bool taken = false;
+    if (quad_products)
+    {
+      mine = plans_in;
+      FusedAdmitted with;
+      if (fused_mark_quad_products(c, quads, *quad_products, mine) && fused_admit(c, mine, nslots, edge, with, &quads) == 0)
+      {
+        adm = std::move(with);
+        use = &mine;
+        taken = true;
+      }
+      else quad_products->left.clear();
+    }
     FusedAdmitted with;
-    if (fused_admit(c, plans, nslots, edge, with, &quads) == 0) adm = std::move(with);
+    if (taken) {}
+    else if (fused_admit(c, plans_in, nslots, edge, with, &quads) == 0) adm = std::move(with);
     else quad_mats.clear();
   }
+  const std::vector<std::vector<FusedOp>> & plans = *use;
   c->fused_last_quad_mats.swap(quad_mats);
   c->fused_last_quads_refused_by_bound = by_bound;
   rc = fused_device_buffers(c, adm.ntab * fused_table_doubles(c->sh.rate_cats), edge != nullptr);

@@ -279,6 +279,12 @@ __host__ __device__ constexpr size_t pllhip_quad_row_offset(size_t n, size_t str
 {
   return ((n >> 3) & 1u) * stride + (n >> 4) * 16u + (n & 7u) * 2u;
 }
+// Site n's class as read from a quad row in memory (deferred.hip: k_quad_product_materialise, and the host tests):
+// the 16 bits at pllhip_quad_row_offset (an even offset: the builder stores whole granules of unsigned short).
+__host__ __device__ inline unsigned int pllhip_quad_row_class(const unsigned char * row, size_t n, size_t stride)
+{
+  return *reinterpret_cast<const unsigned short *>(row + pllhip_quad_row_offset(n, stride));
+}
 // Word m (two sites) of sub-step j of a tile in a wave's character registers: the lane position behind the row's first
 // (lpr: lanes per plane of a tile) and the word of that lane's four.
 template <unsigned int SPS>
@@ -510,6 +516,17 @@ bool pllhip_fused_edge_end_stored(const FusedGeom & geom, const FusedDeferral & 
 unsigned int pllhip_fused_unstored(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
                                    std::vector<std::vector<FusedOp>> & plans, const FusedEdge * edge,
                                    const unsigned char * pinned);
+// Which parents over two QUADS stay unstored (quad products: deferred.hip).  A walked op qualifies if it is kind 3 with
+// a folded product on both sides, both read as quads (taken[segment][2 pos + side], what pllhip_fused_quad_decide made of
+// the finished plan), and it passes every condition pllhip_fused_unstored puts on a pair product -- the same code.  Its
+// value at a site is Qa[class a] * Qb[class b], two rows of the launch's two quad tables, times 2^256 where its own
+// scaling test fired: no other CLV.  The decision follows the plan and the quads'.  `ops` / `count`: the list `plans`
+// were made of (a folded walk: FusedWalk::fl).  Sets FusedOp::unstored on those ops (no other op's mark is touched),
+// returns how many.  ONE rule for pllhip_launch_fused and pllhip_fused_plan_dry_quad_products.
+unsigned int pllhip_fused_quad_products(const FusedGeom & geom, const pllhip_op_t * ops, unsigned int count,
+                                        std::vector<std::vector<FusedOp>> & plans,
+                                        const std::vector<std::vector<unsigned char>> & taken, const FusedEdge * edge,
+                                        const unsigned char * pinned);
 // Which unstored pair products of a planned list are FOLDED into their reader: not walked at all, the reader forms the
 // product from the two gathered factors itself.  A parent pllhip_fused_unstored marked is folded if
 //   - exactly one op of the list reads it, on one side only;
@@ -695,9 +712,23 @@ int pllhip_aa_list_walk(const FusedGeom & geom, const pllhip_op_t * ops, const P
 void pllhip_aa_list_kinds_of(const int * cls, unsigned int count, bool list_ti_mfma, unsigned int reloads,
                              unsigned int * out8);
 
+// Quad products (deferred.hip): what the launch needs to apply pllhip_fused_quad_products once it has picked the quads
+// -- the list the plans were made of, the hinted edge (folded or not), the pinned CLVs --, and what it left unstored:
+// the CLV and scale buffer of each such op, its two quad rows (their places in the pool of rows) and its place in the
+// pool of kept quad tables.
+struct FusedQuadProducts
+{
+  FusedGeom geom;
+  const pllhip_op_t * ops = nullptr;
+  unsigned int count = 0;
+  const FusedEdge * edge = nullptr;
+  const unsigned char * pinned = nullptr;
+  std::vector<pllhip_ctx::quad_product> left; // out
+};
 // encode and launch: one plan per segment
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
-                        const std::vector<FusedPairJob> * keep_jobs = nullptr, const FusedEdge * edge = nullptr);
+                        const std::vector<FusedPairJob> * keep_jobs = nullptr, const FusedEdge * edge = nullptr,
+                        FusedQuadProducts * quad_products = nullptr);
 int pllhip_relaunch_fused(pllhip_ctx * c); // the same op list as in the previous whole-list call of this context
 
 #endif

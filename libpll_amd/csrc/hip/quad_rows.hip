@@ -201,6 +201,17 @@ void pllhip_quad_rows_tip_written(pllhip_ctx * c, unsigned int tip)
   if (any) ++c->layout_epoch;
 }
 
+// the row at `slot` of the pool, if it still is the quad tips4's and its classes are current (deferred.hip: a quad
+// product names its two rows this way)
+const unsigned char * pllhip_quad_row_ptr(const pllhip_ctx * c, unsigned int slot, const unsigned int * tips4)
+{
+  const pllhip_ctx::quad_row_pool & p = c->quad_rows;
+  if (!p.d || slot >= p.rows.size()) return nullptr;
+  const pllhip_ctx::quad_row & r = p.rows[slot];
+  if (!r.live || r.stale || memcmp(r.t, tips4, sizeof(r.t)) != 0) return nullptr;
+  return quad_row_at(c, slot);
+}
+
 int pllhip_quad_rows_resolve(pllhip_ctx * c, const std::vector<QuadKey> & need, std::vector<QuadRowRef> & out)
 {
   pllhip_ctx::quad_row_pool & p = c->quad_rows;
@@ -243,6 +254,16 @@ int pllhip_quad_rows_resolve(pllhip_ctx * c, const std::vector<QuadKey> & need, 
     }
     if (p.d)
     {
+      // (a live quad product names rows of the pool that goes: stored first)
+      if (const int rc = pllhip_quad_products_flush(c))
+      {
+        (void)hipFree(d);
+        (void)hipFree(dp);
+        (void)hipFree(dc);
+        if (dw) (void)hipFree(dw);
+        (void)hipHostFree(hc);
+        return rc;
+      }
       HIP_TRY(hipStreamSynchronize(c->stream));
       (void)hipFree(p.d);
       (void)hipFree(p.d_patterns);
@@ -272,6 +293,14 @@ int pllhip_quad_rows_resolve(pllhip_ctx * c, const std::vector<QuadKey> & need, 
     it->second = (int)s;
     r.used = p.clock;
   }
+  // (a row will be built -- over an evicted one, or counted again: the quad products, which name rows by their places,
+  // are stored first, on the stream ahead of the builder and before any row changes hands)
+  for (const auto & kv : slot_of)
+    if (kv.second < 0 || p.rows[kv.second].stale)
+    {
+      if (const int rc = pllhip_quad_products_flush(c)) return rc;
+      break;
+    }
   std::vector<unsigned int> build;
   bool evicted = false;
   for (auto & kv : slot_of)
@@ -331,6 +360,7 @@ int pllhip_quad_rows_resolve(pllhip_ctx * c, const std::vector<QuadKey> & need, 
     out[i].has_zero = p.rows[s].has_zero;
     out[i].row = quad_row_at(c, (size_t)s);
     out[i].patterns = p.d_patterns + (size_t)s * PLLHIP_QUAD_MAX_CLASSES;
+    out[i].slot = (unsigned int)s;
   }
   return 0;
 }
@@ -344,6 +374,7 @@ extern "C" int pllhip_set_quad_row_capacity(pllhip_ctx_t * c, unsigned int n)
   p.want = n;
   if (!p.d) return 0;
   HIP_TRY(hipSetDevice(c->sh.device));
+  if (const int rc = pllhip_quad_products_flush(c)) return rc; // (they name rows of the pool that goes)
   HIP_TRY(hipStreamSynchronize(c->stream));
   pllhip_quad_rows_free(c);
   ++c->layout_epoch;
@@ -355,6 +386,12 @@ extern "C" int pllhip_set_quad_rows(pllhip_ctx_t * c, int on, unsigned int min_s
 {
   pllhip_edge_terms_drop(c);
   PLLHIP_ALL_SHARDS(c, pllhip_set_quad_rows(s, on, min_sites_per_class));
+  // (quads off: the quad products there are get their bytes)
+  if (!on)
+  {
+    HIP_TRY(hipSetDevice(c->sh.device));
+    if (const int rc = pllhip_quad_products_flush(c)) return rc;
+  }
   c->quad_rows_on = on != 0;
   c->quad_min_sites_per_class = min_sites_per_class ? min_sites_per_class : 64u;
   ++c->layout_epoch;
@@ -425,6 +462,11 @@ extern "C" int pllhip_quad_row_build_dry(const unsigned char * pa, const unsigne
 extern "C" unsigned long long pllhip_quad_row_offset_dry(unsigned long long site, unsigned long long stride)
 {
   return pllhip_quad_row_offset((size_t)site, (size_t)stride);
+}
+
+extern "C" unsigned int pllhip_quad_row_class_dry(const unsigned char * row, unsigned long long site, unsigned long long stride)
+{
+  return pllhip_quad_row_class(row, (size_t)site, (size_t)stride);
 }
 
 // What gather_factor() of k_dna_fused takes from a quad row: lanes[] the 16-byte character registers of the lanes that

@@ -910,6 +910,20 @@ int pll_amd_set_unstored_pairs(pll_partition_t * p, int on)
   return PLL_SUCCESS;
 }
 
+int pll_amd_quad_product_stats(pll_partition_t * p, unsigned long long * stats4)
+{
+  int rc = pllhip_quad_product_stats(pll_amd_priv(p)->ctx, stats4);
+  if (rc) return pll_amd_fail_hip(rc, "quad product stats");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_set_unstored_quad_products(pll_partition_t * p, int on)
+{
+  int rc = pllhip_set_unstored_quad_products(pll_amd_priv(p)->ctx, on);
+  if (rc) return pll_amd_fail_hip(rc, "set unstored quad products");
+  return PLL_SUCCESS;
+}
+
 int pll_amd_pair_fold_stats(pll_partition_t * p, unsigned long long * stats4)
 {
   int rc = pllhip_pair_fold_stats(pll_amd_priv(p)->ctx, stats4);

@@ -298,6 +298,9 @@ class PllLibrary:
                 lib.pll_amd_set_quad_row_capacity.argtypes = [_PP, C.c_uint]
                 lib.pll_amd_quad_row_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
                 lib.pll_amd_quad_list_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
+            if hasattr(lib, "pll_amd_set_unstored_quad_products"):
+                lib.pll_amd_set_unstored_quad_products.argtypes = [_PP, C.c_int]
+                lib.pll_amd_quad_product_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
             if hasattr(lib, "pll_amd_set_edge_fold"):
                 lib.pll_amd_set_edge_fold.argtypes = [_PP, C.c_int]
                 lib.pll_amd_edge_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
@@ -1454,6 +1457,16 @@ class Partition:
         buf = (C.c_ulonglong * 3)()
         self._check(self.lib.pll_amd_quad_list_stats(self.ptr, buf), "pll_amd_quad_list_stats")
         return dict(zip(("taken", "wide_gathers", "taken_total"), (int(v) for v in buf)))
+
+    def set_unstored_quad_products(self, on):
+        """False: the parent of every op over two quads is stored by the whole-list launch (pll_amd.h); on by default."""
+        self._check(self.lib.pll_amd_set_unstored_quad_products(self.ptr, 1 if on else 0), "pll_amd_set_unstored_quad_products")
+
+    def quad_product_stats(self):
+        """{live, ops_unstored, launches, materialised} of the unstored quad products (pll_amd.h)."""
+        buf = (C.c_ulonglong * 4)()
+        self._check(self.lib.pll_amd_quad_product_stats(self.ptr, buf), "pll_amd_quad_product_stats")
+        return dict(zip(("live", "ops_unstored", "launches", "materialised"), (int(v) for v in buf)))
 
     def unstored_stats(self):
         """{unstored_now, ops_unstored, launches, materialised} of the 4-state pair products (pll_amd.h)."""
