@@ -47,6 +47,17 @@ enum
   BATCH_FAMILIES
 };
 
+// the kinds of CLV a 4-state whole-list launch leaves unstored (pllhip_ctx::deferred_clv)
+enum
+{
+  UNSTORED_NONE,
+  UNSTORED_CHERRY,
+  UNSTORED_PAIR,
+  UNSTORED_FOLDED,
+  UNSTORED_QUAD,
+  UNSTORED_KINDS
+};
+
 // a set of replicate weight vectors on a context's device (replicates.hip): `count` rows of `pitch` bytes, the weights
 // of a row `width` bytes each in site order, the bytes past the last site zero.  Owned by the context's list
 struct pllhip_replicates
@@ -194,63 +205,60 @@ struct pllhip_ctx
   unsigned int fused_last_quads_refused_by_bound = 0; // quads the kept plan lost to a bound: a better one plans again
   unsigned int fused_last_quad_jobs = 0;       // table jobs of kind 4 in the kept plan (0: no k_dna_quad_tables launch)
   unsigned long long quad_list_stats[3] = {0, 0, 0}; // quads read as tables: in the last planned list, its wide gathers, in all
-  // ---- deferred cherries (deferred.hip): a tip-tip op of a 4-state whole-list launch is not run; its
-  // parent CLV is DEFINED by its two tip rows and a kept copy of its pair table T[c1][c2][rate][state] until somebody
-  // other than a list kernel needs the bytes -- every such entry point materialises what it touches first
-  // (PLLHIP_DEFERRED_* below).  deferred[i].on: CLV i is in that state; scaler: the scale buffer cleared with it.
-  // A second kind, the PAIR PRODUCT ("Unstored pair products"): the parent of a gathered-gathered op
-  // that the list kernel walked but did not store -- Fa[rows 0, 1] * Fb[rows 2, 3], the two factor tables the op
-  // gathered from, kept in the pool as well, times 2^256 where the op's count (in HBM, in `scaler`) is not 0.
+  // ---- unstored CLVs (deferred.hip): a parent CLV that a 4-state whole-list launch did not store is
+  // DEFINED by what its record names until somebody other than a list kernel needs the bytes -- every such entry point
+  // materialises what it touches first (PLLHIP_DEFERRED_* below).  ONE record for every kind; the planner fills it
+  // (clv, scaler and its kind's fields), pllhip_deferred_begin makes it deferred[clv], deferred_clear ends it.
+  //   UNSTORED_CHERRY  a tip-tip op that was not run: row (tip1, tip2) of a kept copy of its pair table
+  //                    T[c1][c2][rate][state] (defer_pool); `scaler` is the scale buffer cleared with it.
+  //   UNSTORED_PAIR    the parent of a gathered-gathered op that was walked but not stored: Fa[rows 0, 1] * Fb[rows 2, 3],
+  //                    kept copies of the two factor tables the op gathered from (defer_pool), times 2^256 where the
+  //                    op's count (in HBM, in `scaler`) is not 0.
+  //   UNSTORED_FOLDED  a pair product folded into its reader (not walked): its counts are not in HBM either -- the
+  //                    materialising launch forms the scale bits and writes them.
+  //   UNSTORED_QUAD    the parent of a walked op over two quads: Qa[class a] * Qb[class b], rows of kept copies of the
+  //                    launch's two quad tables (quad_product_pool), the classes read from two quad rows -- which stay
+  //                    as they are while the product lives: quad_rows.hip stores it first --, times 2^256 where the
+  //                    op's count (in HBM, in `scaler`) is not 0.
   struct deferred_clv
   {
-    bool on = false;
-    bool pair = false;                   // a pair product: rows[] and the pool's two tables; else a cherry: tip1, tip2
-    bool folded = false;                 // a pair product FOLDED into its reader (not walked): its counts are not in HBM
-                                         // either -- the materialising launch forms the scale bits and writes them
-    unsigned int tip1 = 0, tip2 = 0;
-    unsigned int rows[4] = {0, 0, 0, 0}; // tip index + 1 of each table's two rows (0: none -- code 0)
-    int scaler = -1;
-    // A third kind, the QUAD PRODUCT ("Unstored quad products"): the parent of a walked op over two
-    // quads that the list kernel did not store -- Qa[class a] * Qb[class b], rows of kept copies of the launch's two
-    // quad tables (quad_product_pool, slot qslot), the classes read from the two quad rows (places qrow[] of
-    // quad_rows, tips qtips[] -- the rows stay as they are while the product lives: quad_rows.hip stores it first),
-    // times 2^256 where the op's count (in HBM, in `scaler`) is not 0.
-    bool quad = false;
-    unsigned int qrow[2] = {0, 0}, qslot = 0;
-    unsigned int qtips[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    unsigned char kind = UNSTORED_NONE;
+    unsigned int clv = 0;                       // its index: deferred[clv]
+    int scaler = -1;                            // the op's scale buffer: owned by the CLV while it lives (deferred_sc_owner)
+    struct { unsigned int tip1 = 0, tip2 = 0; } cherry;
+    struct { unsigned int rows[4] = {0, 0, 0, 0}; } pair; // both pair kinds: tip index + 1 of each table's two rows (0: none -- code 0)
+    struct
+    {
+      unsigned int row[2] = {0, 0};             // the two quad rows: their places in quad_rows ...
+      unsigned int tips[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}; // ... and the quads they must still be
+      unsigned int slot = 0;                    // its two tables' place in quad_product_pool
+    } quad;
+    bool live() const { return kind != UNSTORED_NONE; }
+    bool is_pair() const { return kind == UNSTORED_PAIR || kind == UNSTORED_FOLDED; }
+    bool is_product() const { return kind > UNSTORED_CHERRY; } // no table a list kernel could gather it from
   };
   std::vector<deferred_clv> deferred;          // per CLV index (sized on first use)
-  std::vector<int> deferred_sc_owner;          // per scale buffer: the deferred CLV that owns its (zero) counts, or -1
+  std::vector<int> deferred_sc_owner;          // per scale buffer: the live CLV that owns its counts, or -1
   std::vector<unsigned char> clv_pinned;       // per CLV index: pllhip_dev_clv handed its address out -- never deferred
-  unsigned int n_deferred = 0;                 // cherries and pair products
-  unsigned int n_unstored = 0;                 // ... the pair products among them
+  unsigned int n_live[UNSTORED_KINDS] = {};    // live records per kind ...
+  unsigned int n_deferred = 0;                 // ... and of every kind: what every PLLHIP_DEFERRED_* site tests
+  // per kind {-, ops left unstored, materialising launches, CLVs materialised}, as include/pllhip.h defines them:
+  // UNSTORED_PAIR's row counts every pair product, the folded ones included; UNSTORED_FOLDED's [2]: lists planned twice
+  unsigned long long unstored_stats[UNSTORED_KINDS][4] = {};
+  unsigned int fused_last_unstored_ops[UNSTORED_KINDS] = {}; // what a launch of the kept plan adds to unstored_stats[kind][1]
   double * defer_pool = nullptr;               // [CLV index][defer_pool_tables][256][span]: the kept tables
   unsigned int defer_pool_tables = 0;          // 2: a cherry's T or a pair product's Fa, Fb; 1 (no room for two): cherries only
   bool defer_pool_failed = false;
+  bool cherry_deferral = true;                 // pllhip_set_deferral (0: the eager path, for A/B and tests)
   bool unstored_pairs = true;                  // pllhip_set_unstored_pairs
   bool pair_fold = true;                       // pllhip_set_pair_fold: unstored parents with one reader are not walked
-  unsigned int n_folded = 0;                   // ... the folded ones among the pair products
-  unsigned int fused_last_nfolded = 0;         // ops the kept plan folds (not walked)
-  unsigned long long fold_stats[4] = {0, 0, 0, 0}; // folded now (filled on read), ops folded, lists planned twice, CLVs materialised
-  struct unstored_product { unsigned int clv; int scaler; unsigned int rows[4]; bool folded; }; // (deferred_clv's fields)
-  std::vector<unstored_product> fused_last_unstored; // the kept plan's pair products
-  unsigned long long unstored_stats[4] = {0, 0, 0, 0}; // the same four numbers for pair products
-  // ---- quad products (the third kind above).  Counted on their own -- n_deferred includes them, so that every
-  // PLLHIP_DEFERRED_* site serves them; the cherries', pair products' and folded products' statistics do not.
-  struct quad_product { unsigned int clv; int scaler; unsigned int qrow[2], qslot; unsigned int qtips[2][4]; };
-  unsigned int n_quad_products = 0;
   bool unstored_quad_products = true;          // pllhip_set_unstored_quad_products
+  unsigned int fused_last_nfolded = 0;         // ops the kept plan folds (not walked)
   double * quad_product_pool = nullptr;        // [slot][2 tables][PLLHIP_QUAD_MAX_CLASSES][span]: kept copies of the quad tables
   std::vector<int> quad_product_owner;         // per slot: the CLV of the live product that has it, or -1
   bool quad_product_pool_failed = false;       // its allocation failed once: such parents are stored, as before
-  std::vector<quad_product> fused_last_quad_products; // the kept plan's
-  unsigned long long quad_product_stats[4] = {0, 0, 0, 0}; // live now (filled on read), ops left unstored, materialise launches, CLVs materialised
-  bool cherry_deferral = true;                        // pllhip_set_deferral (0: the eager path, for A/B and tests)
   unsigned int defer_epoch = 0;                // bumped whenever a deferral ends other than by the list that replaces it
   unsigned int fused_last_defer_epoch = 0;     // ... as it was when the kept plan was launched
-  struct deferred_cherry { unsigned int clv, tip1, tip2; int scaler; };
-  std::vector<deferred_cherry> fused_last_deferred; // the kept plan's deferred set
-  unsigned long long defer_stats[4] = {0, 0, 0, 0}; // deferred now (filled on read), ops deferred, materialise launches, CLVs materialised
   // ---- edge lnL terms from the 4-state whole-list launch (partials_fused.hip: EDGE, likelihood.hip)
   // An EDGE_II evaluation is remembered (edge_hint); the next whole-list launch that writes one of its two CLVs also
   // computes that edge's per-site terms (edge_terms), and an evaluation of exactly that request sums them instead of
@@ -717,11 +725,12 @@ static inline void pllhip_edge_terms_drop(pllhip_ctx * c)
     c->edge_hint_on = false;
   }
 }
-// Deferred cherries (pllhip_ctx::deferred, deferred.hip).  An entry point that is about to read or overwrite CLVs or
-// scale buffers outside a 4-state list kernel materialises them first -- bit for bit what the tip-tip op would have
-// stored, and zeros in the scale buffer it cleared.  n < 0 / PLLHIP_DEFERRED_FLUSH: every deferred CLV.
+// Unstored CLVs (pllhip_ctx::deferred, deferred.hip).  An entry point that is about to read or overwrite CLVs or
+// scale buffers outside a 4-state list kernel materialises them first -- bit for bit what the list's op would have
+// stored, counts included.  n < 0 / PLLHIP_DEFERRED_FLUSH: every unstored CLV.
 int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * clv_indices, int n);
 int pllhip_deferred_materialise_scalers(pllhip_ctx * c, const int * scaler_indices, int n);
+void pllhip_deferred_begin(pllhip_ctx * c, const pllhip_ctx::deferred_clv & record); // CLV record.clv is what the record says from here on
 void pllhip_deferred_drop(pllhip_ctx * c, unsigned int clv_index); // the deferral ends without the bytes (overwritten)
 double * pllhip_deferred_table(pllhip_ctx * c, unsigned int clv_index, unsigned int which = 0); // its place in the pool (nullptr: no pool, or no second table)
 #define PLLHIP_DEFERRED_FLUSH(c)                                         \

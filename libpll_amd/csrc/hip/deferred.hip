@@ -1,31 +1,46 @@
-// deferred.hip -- deferred cherries: materialising a CLV that a 4-state whole-list launch did not store.
+// deferred.hip -- unstored CLVs: where the state of a CLV that a 4-state whole-list launch did not store begins and
+// ends, and the launches that materialise it.
 //
-// A tip-tip op's parent at a site is row (c1, c2) of the op's pair table (partials_fused.hip: k_dna_pair_tables), one
-// of 256 values.  The whole-list kernel no longer runs such an op: its readers in the list take what they need from
-// tables, and the CLV is DEFERRED -- defined by its two tip rows and a kept copy T[c1][c2][rate][state] of the pair
-// table (pllhip_ctx::defer_pool; a snapshot: a later pll_update_prob_matrices does not change what the CLV is, just
-// as the reference's CLV keeps its value until an op rewrites it).  Every entry point that reads or overwrites a CLV
-// or a scale buffer outside a list kernel comes through here first (ctx.hpp: PLLHIP_DEFERRED_NEED / _FLUSH): one
-// launch gathers the rows of all the CLVs asked for, blockIdx.y = CLV, and zeroes the scale buffers the ops would
-// have cleared (core_partials_avx.c:598-599) -- the bytes the tip-tip op itself would have stored.
+// The record (pllhip_ctx::deferred_clv, ctx.hpp) says what each kind is defined by.  pllhip_deferred_begin and
+// deferred_clear, next to each other below, are the only code that changes the state: the record, the owner of the
+// scale buffer, the owner of the quad tables' slot, the live counts.  Every entry point that reads or overwrites a CLV
+// or a scale buffer outside a list kernel comes through here first (ctx.hpp: PLLHIP_DEFERRED_NEED / _FLUSH) and gets
+// the bytes the list's op would have stored:
 //
-// Pair products ("Unstored pair products"): the parent of a gathered-gathered op is Fa[rows] * Fb[rows],
-// times 2^256 where the scaling test fired.  The list kernel walks the op -- its reader takes the value from the
-// wave's slot, its counts are stored -- but where nothing else in the list needs the bytes it does not store the CLV
-// (fused_plan.hip: pllhip_fused_unstored).  The CLV is then defined by kept copies of the two factor tables (the
-// table launch writes them next to the ones the kernel gathers from: the same values), their tip rows and the op's
-// counts, which ARE in HBM: a gathered operand inherits none, so a count is 0 or 1 and is the scale bit.  The same
-// launch as for cherries forms it on demand with the kernel's own two multiplications.
+// A cherry is row (c1, c2) of a kept copy T[c1][c2][rate][state] of the op's pair table (partials_fused.hip:
+// k_dna_pair_tables; a snapshot: a later pll_update_prob_matrices does not change what the CLV is, just as the
+// reference's CLV keeps its value until an op rewrites it), one of 256 values, and zeros in the scale buffer the op
+// would have cleared (core_partials_avx.c:598-599).  One launch gathers the rows of all the CLVs asked for.
 //
-// Folded pair products (pllhip_set_pair_fold): such a parent with exactly one reader is not even walked --
-// the reader forms the product in registers (partials_fused.hip, step()).  Its counts were never stored either, so the
-// launch here runs the scaling test itself -- every entry of the site below the threshold, the op's own scale buffer
-// permitting -- and WRITES the counts with the CLV.
+// A pair product ("Unstored pair products") is Fa[rows] * Fb[rows], kept copies of the two factor tables
+// (the table launch writes them next to the ones the kernel gathers from: the same values), times 2^256 where the
+// scaling test fired.  The list kernel walked the op -- its reader took the value from the wave's slot -- and stored
+// its counts: a gathered operand inherits none, so a count is 0 or 1 and is the scale bit.  The cherries' launch forms
+// it with the kernel's own two multiplications.  A FOLDED one (pllhip_set_pair_fold) was not even walked -- its one
+// reader formed the product in registers (partials_fused.hip, step()) --, so the launch runs the scaling test itself
+// -- every entry of the site below the threshold, the op's own scale buffer permitting -- and WRITES the counts.
+//
+// A quad product ("Unstored quad products") is Qa[class a of n] * Qb[class b of n] -- the classes from
+// the two quad rows, Qa and Qb kept copies of the launch's two quad tables ([class][rate][state]) --, times 2^256 where
+// the op's count of the site (in HBM: a quad brings none, so it is the op's own scale bit) is not 0.  A launch of its
+// own kernel, never part of a k_deferred_materialise batch.
 #include <algorithm>
 
 #include "ctx.hpp"
 #include "numerics.hpp"
 #include "partials_fused.hpp"
+
+// The list kernel's own two operations in its order (partials_fused.hip, step(): q = x * y, then q *= 2^256 or 1.0)
+template <bool NT>
+__device__ __forceinline__ void store_product(pll_v2d a, pll_v2d b, bool scale, pll_v2d * dst)
+{
+  const double factor = __hiloint2double(scale ? 0x4ff00000 : 0x3ff00000, 0);
+  pll_v2d v = {a.x * b.x, a.y * b.y};
+  v.x *= factor;
+  v.y *= factor;
+  if (NT) __builtin_nontemporal_store(v, dst);
+  else *dst = v;
+}
 
 #define PLLHIP_DEFER_BATCH 48
 struct DeferredJobs
@@ -44,11 +59,11 @@ struct DeferredJobs
 };
 static_assert(sizeof(DeferredJobs) <= 3900, "the jobs travel as kernel arguments");
 
-// one lane per 16 bytes of the CLV: site n's row is T[(c1[n] & 15) << 4 | (c2[n] & 15)], span2 granules
-// (the list kernels' pair index: partials_fused.hip, gather())
+// blockIdx.y = CLV, one lane per 16 bytes of the CLV: site n's row is T[(c1[n] & 15) << 4 | (c2[n] & 15)], span2 granules
+// (the list kernels' pair index: partials_fused.hip, gather()).  One count per site: nothing is deferred with
+// per-rate scalers
 template <bool NT>
-__global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs, size_t sites, unsigned int span2,
-                                                              unsigned int count_words)
+__global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs, size_t sites, unsigned int span2)
 {
   const pll_v2d * __restrict__ tab = jobs.tab[blockIdx.y];
   const unsigned char * __restrict__ c1 = jobs.c1[blockIdx.y];
@@ -68,7 +83,7 @@ __global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs,
       const unsigned int pa = ((c1 ? (unsigned int)(c1[n] & 15u) : 0u) << 4) | (c2 ? (unsigned int)(c2[n] & 15u) : 0u);
       const unsigned int pb = ((c3 ? (unsigned int)(c3[n] & 15u) : 0u) << 4) | (c4 ? (unsigned int)(c4[n] & 15u) : 0u);
       const pll_v2d a = tab[(size_t)pa * span2 + g], b = tab2[(size_t)pb * span2 + g];
-      bool scale = counts && !folded && counts[n * count_words];
+      bool scale = counts && !folded && counts[n];
       if (folded && counts)
       {
         // (partials_fused.hip, step(): all 2 x span2 entries of the site below the threshold.  The span2 lanes of a site
@@ -78,15 +93,9 @@ __global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs,
         int small = (a.x * b.x < PLLHIP_SCALE_THRESHOLD) && (a.y * b.y < PLLHIP_SCALE_THRESHOLD) ? 1 : 0;
         for (unsigned int m = 1; m < span2; m <<= 1) small &= __shfl_xor(small, (int)m, 64);
         scale = small != 0;
-        if (g == 0) counts[n * count_words] = scale ? 1u : 0u;
+        if (g == 0) counts[n] = scale ? 1u : 0u;
       }
-      // (partials_fused.hip, step(): q = x * y, then q *= 2^256 or 1.0)
-      const double factor = __hiloint2double(scale ? 0x4ff00000 : 0x3ff00000, 0);
-      pll_v2d v = {a.x * b.x, a.y * b.y};
-      v.x *= factor;
-      v.y *= factor;
-      if (NT) __builtin_nontemporal_store(v, clv + t);
-      else clv[t] = v;
+      store_product<NT>(a, b, scale, clv + t);
     }
     return;
   }
@@ -100,16 +109,10 @@ __global__ __launch_bounds__(256) void k_deferred_materialise(DeferredJobs jobs,
     else clv[t] = v;
   }
   if (counts)
-    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < sites * count_words; t += (size_t)gridDim.x * blockDim.x)
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < sites; t += (size_t)gridDim.x * blockDim.x)
       counts[t] = 0u;
 }
 
-// Quad products ("Unstored quad products"): the parent of a walked op over two quads that the list
-// kernel did not store.  Site n's value is Qa[class a of n] * Qb[class b of n] -- the classes from the two quad rows,
-// Qa and Qb the kept copies of the launch's two quad tables ([class][rate][state]) --, times 2^256 where the op's count
-// of the site (in HBM: a quad brings none, so it is the op's own scale bit) is not 0: the list kernel's own two
-// operations in its order (partials_fused.hip, step(): q = x * y, then q *= 2^256 or 1.0).  A launch of its own,
-// never part of a k_deferred_materialise batch: blockIdx.y = CLV, one lane per 16 bytes of the CLV.
 #define PLLHIP_QUAD_PRODUCT_BATCH 64
 struct QuadProductJobs
 {
@@ -122,6 +125,7 @@ struct QuadProductJobs
 };
 static_assert(sizeof(QuadProductJobs) <= 3900, "the jobs travel as kernel arguments");
 
+// blockIdx.y = CLV, one lane per 16 bytes of the CLV
 template <bool NT>
 __global__ __launch_bounds__(256) void k_quad_product_materialise(QuadProductJobs jobs, size_t sites, unsigned int span2,
                                                                   size_t row_stride)
@@ -140,15 +144,22 @@ __global__ __launch_bounds__(256) void k_quad_product_materialise(QuadProductJob
     // (a class is below the row's class count, at most PLLHIP_QUAD_MAX_CLASSES: inside the kept table)
     const unsigned int ca = pllhip_quad_row_class(row_a, n, row_stride) & (PLLHIP_QUAD_MAX_CLASSES - 1u);
     const unsigned int cb = pllhip_quad_row_class(row_b, n, row_stride) & (PLLHIP_QUAD_MAX_CLASSES - 1u);
-    const pll_v2d a = qa[(size_t)ca * span2 + g], b = qb[(size_t)cb * span2 + g];
-    const bool scale = counts && counts[n];
-    const double factor = __hiloint2double(scale ? 0x4ff00000 : 0x3ff00000, 0);
-    pll_v2d v = {a.x * b.x, a.y * b.y};
-    v.x *= factor;
-    v.y *= factor;
-    if (NT) __builtin_nontemporal_store(v, clv + t);
-    else clv[t] = v;
+    store_product<NT>(qa[(size_t)ca * span2 + g], qb[(size_t)cb * span2 + g], counts && counts[n], clv + t);
   }
+}
+
+// One launch of a materialising kernel over m CLVs: as many blocks per CLV as its lanes ask for, eight per CU at most;
+// the stores by the partition's cache policy
+template <class Jobs, class... Extra>
+static int launch_jobs(pllhip_ctx * c, void (*plain)(Jobs, size_t, unsigned int, Extra...),
+                       void (*nt)(Jobs, size_t, unsigned int, Extra...), const Jobs & jobs, unsigned int m, Extra... extra)
+{
+  const unsigned int span2 = (unsigned int)(c->span / 2);
+  const size_t total = (size_t)c->sh.sites * span2;
+  const unsigned int gx = (unsigned int)std::min<size_t>(std::max<size_t>(1, (total + 255) / 256), (size_t)c->num_cus * 8);
+  (pllhip_use_nt(c) ? nt : plain)<<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, extra...);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 // The pool of kept quad tables: a slot per LIVE product, two tables of PLLHIP_QUAD_MAX_CLASSES classes each (4 x 32 KB
@@ -188,10 +199,6 @@ int pllhip_quad_product_slot(pllhip_ctx * c, unsigned int clv, std::vector<unsig
 
 static int quad_products_materialise(pllhip_ctx * c, const std::vector<unsigned int> & todo)
 {
-  const unsigned int span2 = (unsigned int)(c->span / 2);
-  const size_t total = (size_t)c->sh.sites * span2;
-  const unsigned int gx = (unsigned int)std::min<size_t>(std::max<size_t>(1, (total + 255) / 256), (size_t)c->num_cus * 8);
-  const bool nt = pllhip_use_nt(c);
   for (size_t first = 0; first < todo.size(); first += PLLHIP_QUAD_PRODUCT_BATCH)
   {
     const unsigned int m = (unsigned int)std::min<size_t>(PLLHIP_QUAD_PRODUCT_BATCH, todo.size() - first);
@@ -201,26 +208,25 @@ static int quad_products_materialise(pllhip_ctx * c, const std::vector<unsigned 
     {
       const unsigned int i = todo[first + k];
       const pllhip_ctx::deferred_clv & d = c->deferred[i];
-      jobs.row_a[k] = pllhip_quad_row_ptr(c, d.qrow[0], d.qtips[0]);
-      jobs.row_b[k] = pllhip_quad_row_ptr(c, d.qrow[1], d.qtips[1]);
+      jobs.row_a[k] = pllhip_quad_row_ptr(c, d.quad.row[0], d.quad.tips[0]);
+      jobs.row_b[k] = pllhip_quad_row_ptr(c, d.quad.row[1], d.quad.tips[1]);
       // (cannot happen while quad_rows.hip stores every product before a row changes hands: a guard against reading a
       // row that is another quad's)
-      if (!jobs.row_a[k] || !jobs.row_b[k] || !c->quad_product_pool || d.qslot >= c->quad_product_owner.size())
+      if (!jobs.row_a[k] || !jobs.row_b[k] || !c->quad_product_pool || d.quad.slot >= c->quad_product_owner.size())
       {
         pllhip_set_error("quad product %u: its quad rows or tables are gone", i);
         return -1;
       }
-      jobs.qa[k] = reinterpret_cast<const pll_v2d *>(pllhip_quad_product_table(c, d.qslot, 0));
-      jobs.qb[k] = reinterpret_cast<const pll_v2d *>(pllhip_quad_product_table(c, d.qslot, 1));
+      jobs.qa[k] = reinterpret_cast<const pll_v2d *>(pllhip_quad_product_table(c, d.quad.slot, 0));
+      jobs.qb[k] = reinterpret_cast<const pll_v2d *>(pllhip_quad_product_table(c, d.quad.slot, 1));
       jobs.clv[k] = reinterpret_cast<pll_v2d *>(c->clv[i]);
       jobs.counts[k] = pllhip_scaler_ptr(c, d.scaler);
     }
-    if (nt) k_quad_product_materialise<true><<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, c->tip_stride);
-    else k_quad_product_materialise<false><<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, c->tip_stride);
-    HIP_TRY(hipGetLastError());
-    ++c->quad_product_stats[2];
+    const int rc = launch_jobs(c, k_quad_product_materialise<false>, k_quad_product_materialise<true>, jobs, m, c->tip_stride);
+    if (rc) return rc;
+    ++c->unstored_stats[UNSTORED_QUAD][2];
   }
-  c->quad_product_stats[3] += todo.size();
+  c->unstored_stats[UNSTORED_QUAD][3] += todo.size();
   return 0;
 }
 
@@ -245,23 +251,35 @@ double * pllhip_deferred_table(pllhip_ctx * c, unsigned int idx, unsigned int wh
   return c->defer_pool + ((size_t)idx * c->defer_pool_tables + which) * 256 * c->span;
 }
 
+// ---- where the state begins and ends: what one of the two touches, the other undoes
+
+// The state of CLV idx ends, with its bytes in HBM or without.  (defer_epoch: the kept plan stood for the set of
+// unstored CLVs it left; commit_list takes the epoch once the list's own begins and ends are done.)
 static void deferred_clear(pllhip_ctx * c, unsigned int idx)
 {
   pllhip_ctx::deferred_clv & d = c->deferred[idx];
-  if (!d.on) return;
+  if (!d.live()) return;
   if (d.scaler >= 0 && (size_t)d.scaler < c->deferred_sc_owner.size() && c->deferred_sc_owner[d.scaler] == (int)idx)
     c->deferred_sc_owner[d.scaler] = -1;
-  d.on = false;
+  if (d.kind == UNSTORED_QUAD && d.quad.slot < c->quad_product_owner.size() && c->quad_product_owner[d.quad.slot] == (int)idx)
+    c->quad_product_owner[d.quad.slot] = -1;
+  --c->n_live[d.kind];
   --c->n_deferred;
-  if (d.pair) --c->n_unstored;
-  if (d.folded) --c->n_folded;
-  if (d.quad)
-  {
-    --c->n_quad_products;
-    if (d.qslot < c->quad_product_owner.size() && c->quad_product_owner[d.qslot] == (int)idx) c->quad_product_owner[d.qslot] = -1;
-  }
-  d.pair = d.folded = d.quad = false;
+  d.kind = UNSTORED_NONE;
   ++c->defer_epoch;
+}
+
+// A list has left CLV r.clv unstored: whatever the index was before ends, and the record holds from here on.  (The
+// scale buffer: a cherry's would hold zeros; a walked product's counts are in HBM, a folded one's are not, but they
+// define the CLV -- whoever touches the buffer stores the CLV first.)
+void pllhip_deferred_begin(pllhip_ctx * c, const pllhip_ctx::deferred_clv & r)
+{
+  deferred_clear(c, r.clv);
+  c->deferred[r.clv] = r;
+  if (r.scaler >= 0) c->deferred_sc_owner[r.scaler] = (int)r.clv;
+  if (r.kind == UNSTORED_QUAD) c->quad_product_owner[r.quad.slot] = (int)r.clv;
+  ++c->n_live[r.kind];
+  ++c->n_deferred;
 }
 
 void pllhip_deferred_drop(pllhip_ctx * c, unsigned int idx)
@@ -269,18 +287,24 @@ void pllhip_deferred_drop(pllhip_ctx * c, unsigned int idx)
   if (idx < c->deferred.size()) deferred_clear(c, idx);
 }
 
+// every live CLV for which want(record) holds, in index order
+template <class Want>
+static std::vector<unsigned int> live_clvs(const pllhip_ctx * c, Want want)
+{
+  std::vector<unsigned int> out;
+  for (unsigned int i = 0; i < c->deferred.size(); ++i)
+    if (c->deferred[i].live() && want(c->deferred[i])) out.push_back(i);
+  return out;
+}
+
 int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
 {
   if (!c->n_deferred) return 0;
   std::vector<unsigned int> todo;
-  if (n < 0)
-  {
-    for (unsigned int i = 0; i < c->deferred.size(); ++i)
-      if (c->deferred[i].on) todo.push_back(i);
-  }
+  if (n < 0) todo = live_clvs(c, [](const pllhip_ctx::deferred_clv &) { return true; });
   else
     for (int k = 0; k < n; ++k)
-      if (idx[k] < c->deferred.size() && c->deferred[idx[k]].on &&
+      if (idx[k] < c->deferred.size() && c->deferred[idx[k]].live() &&
           std::find(todo.begin(), todo.end(), idx[k]) == todo.end())
         todo.push_back(idx[k]);
   if (todo.empty()) return 0;
@@ -288,10 +312,10 @@ int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
   // (quad products: a launch of their own kernel, counted on their own -- the batches below are what they were.  They
   // are served first and are cleared once their launch is enqueued: should a batch below then fail, the call returns
   // its error with the quad products already stored -- their bytes are in HBM, nothing is lost)
-  if (c->n_quad_products)
+  if (c->n_live[UNSTORED_QUAD])
   {
     std::vector<unsigned int> quads, rest;
-    for (unsigned int i : todo) (c->deferred[i].quad ? quads : rest).push_back(i);
+    for (unsigned int i : todo) (c->deferred[i].kind == UNSTORED_QUAD ? quads : rest).push_back(i);
     if (!quads.empty())
     {
       const int rc = quad_products_materialise(c, quads);
@@ -301,10 +325,6 @@ int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
       if (todo.empty()) return 0;
     }
   }
-  const unsigned int span2 = (unsigned int)(c->span / 2);
-  const size_t total = (size_t)c->sh.sites * span2;
-  const unsigned int gx = (unsigned int)std::min<size_t>(std::max<size_t>(1, (total + 255) / 256), (size_t)c->num_cus * 8);
-  const bool nt = pllhip_use_nt(c);
   size_t npairs = 0, nfolded = 0;
   for (size_t first = 0; first < todo.size(); first += PLLHIP_DEFER_BATCH)
   {
@@ -319,34 +339,33 @@ int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
       jobs.tab[k] = reinterpret_cast<const pll_v2d *>(pllhip_deferred_table(c, i));
       jobs.clv[k] = reinterpret_cast<pll_v2d *>(c->clv[i]);
       jobs.counts[k] = pllhip_scaler_ptr(c, d.scaler);
-      if (d.pair)
+      if (d.is_pair())
       {
         jobs.tab2[k] = reinterpret_cast<const pll_v2d *>(pllhip_deferred_table(c, i, 1));
         const unsigned char * rows[4];
-        for (int r = 0; r < 4; ++r) rows[r] = d.rows[r] ? pllhip_tip_ptr(c, d.rows[r] - 1) : nullptr;
+        for (int r = 0; r < 4; ++r) rows[r] = d.pair.rows[r] ? pllhip_tip_ptr(c, d.pair.rows[r] - 1) : nullptr;
         jobs.c1[k] = rows[0];
         jobs.c2[k] = rows[1];
         jobs.c3[k] = rows[2];
         jobs.c4[k] = rows[3];
-        jobs.folded[k] = d.folded ? 1 : 0;
-        if (d.folded) ++nfolded;
+        jobs.folded[k] = d.kind == UNSTORED_FOLDED ? 1 : 0;
+        nfolded += jobs.folded[k];
         ++npairs;
         continue;
       }
-      jobs.c1[k] = pllhip_tip_ptr(c, d.tip1);
-      jobs.c2[k] = pllhip_tip_ptr(c, d.tip2);
+      jobs.c1[k] = pllhip_tip_ptr(c, d.cherry.tip1);
+      jobs.c2[k] = pllhip_tip_ptr(c, d.cherry.tip2);
     }
-    if (nt) k_deferred_materialise<true><<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, 1u);
-    else k_deferred_materialise<false><<<dim3(gx, m), 256, 0, c->stream>>>(jobs, c->sh.sites, span2, 1u);
-    HIP_TRY(hipGetLastError());
+    const int rc = launch_jobs(c, k_deferred_materialise<false>, k_deferred_materialise<true>, jobs, m);
+    if (rc) return rc;
     // (a launch counts for each kind it serves)
-    if (npairs - pairs_before < m) ++c->defer_stats[2];
-    if (npairs > pairs_before) ++c->unstored_stats[2];
+    if (npairs - pairs_before < m) ++c->unstored_stats[UNSTORED_CHERRY][2];
+    if (npairs > pairs_before) ++c->unstored_stats[UNSTORED_PAIR][2];
   }
   for (unsigned int i : todo) deferred_clear(c, i);
-  c->defer_stats[3] += todo.size() - npairs;
-  c->unstored_stats[3] += npairs;
-  c->fold_stats[3] += nfolded;
+  c->unstored_stats[UNSTORED_CHERRY][3] += todo.size() - npairs;
+  c->unstored_stats[UNSTORED_PAIR][3] += npairs;
+  c->unstored_stats[UNSTORED_FOLDED][3] += nfolded;
   return 0;
 }
 
@@ -372,20 +391,18 @@ extern "C" int pllhip_set_deferral(pllhip_ctx_t * c, int on)
   return 0;
 }
 
-// Pair products (see the top of the file) on or off; off stores those there are.  pllhip_set_deferral(ctx, 0) turns
-// both off: a list that defers no cherry has no gathered-gathered op over one.
+// Pair products on or off; off stores those there are.  pllhip_set_deferral(ctx, 0) turns both off: a list that defers
+// no cherry has no gathered-gathered op over one.
 extern "C" int pllhip_set_unstored_pairs(pllhip_ctx_t * c, int on)
 {
   pllhip_edge_terms_drop(c);
   PLLHIP_ALL_SHARDS(c, pllhip_set_unstored_pairs(s, on));
   if (c->unstored_pairs == (on != 0)) return 0;
-  if (!on && (c->n_unstored || c->n_quad_products))
+  if (!on && c->n_deferred > c->n_live[UNSTORED_CHERRY])
   {
     // (quad products go with the rest: no list has one while pair products are off)
-    std::vector<unsigned int> pairs;
-    for (unsigned int i = 0; i < c->deferred.size(); ++i)
-      if (c->deferred[i].on && (c->deferred[i].pair || c->deferred[i].quad)) pairs.push_back(i);
-    const int rc = pllhip_deferred_materialise(c, pairs.data(), (int)pairs.size());
+    const std::vector<unsigned int> products = live_clvs(c, [](const pllhip_ctx::deferred_clv & d) { return d.is_product(); });
+    const int rc = pllhip_deferred_materialise(c, products.data(), (int)products.size());
     if (rc) return rc;
   }
   c->unstored_pairs = on != 0;
@@ -395,14 +412,12 @@ extern "C" int pllhip_set_unstored_pairs(pllhip_ctx_t * c, int on)
 
 int pllhip_quad_products_flush(pllhip_ctx * c)
 {
-  if (!c->n_quad_products) return 0;
-  std::vector<unsigned int> quads;
-  for (unsigned int i = 0; i < c->deferred.size(); ++i)
-    if (c->deferred[i].on && c->deferred[i].quad) quads.push_back(i);
+  if (!c->n_live[UNSTORED_QUAD]) return 0;
+  const std::vector<unsigned int> quads = live_clvs(c, [](const pllhip_ctx::deferred_clv & d) { return d.kind == UNSTORED_QUAD; });
   return pllhip_deferred_materialise(c, quads.data(), (int)quads.size());
 }
 
-// Quad products (see above) on or off; off stores those there are.  pllhip_set_deferral(ctx, 0) and
+// Quad products on or off; off stores those there are.  pllhip_set_deferral(ctx, 0) and
 // pllhip_set_unstored_pairs(ctx, 0) turn them off with the rest, and so does pllhip_set_quad_rows(ctx, 0, ...).
 extern "C" int pllhip_set_unstored_quad_products(pllhip_ctx_t * c, int on)
 {
@@ -419,20 +434,6 @@ extern "C" int pllhip_set_unstored_quad_products(pllhip_ctx_t * c, int on)
   return 0;
 }
 
-// {quad products live now, ops left unstored in total, materialise launches, CLVs materialised}
-extern "C" int pllhip_quad_product_stats(pllhip_ctx_t * c, unsigned long long * out4)
-{
-  for (int t = 0; t < 4; ++t) out4[t] = 0;
-  auto add = [&](const pllhip_ctx * s) {
-    out4[0] += s->n_quad_products;
-    for (int t = 1; t < 4; ++t) out4[t] += s->quad_product_stats[t];
-  };
-  if (!c->shards.empty())
-    for (pllhip_ctx * s : c->shards) add(s);
-  else add(c);
-  return 0;
-}
-
 // Folding pair products into their readers on or off (A/B, tests); off stores no CLV -- a folded parent stays what
 // it is, an unstored pair product whose counts the materialising launch writes -- but ends the kept plan.
 extern "C" int pllhip_set_pair_fold(pllhip_ctx_t * c, int on)
@@ -445,54 +446,23 @@ extern "C" int pllhip_set_pair_fold(pllhip_ctx_t * c, int on)
   return 0;
 }
 
-// {CLVs folded now, ops folded in total, lists planned a second time, folded CLVs materialised}
-extern "C" int pllhip_pair_fold_stats(pllhip_ctx_t * c, unsigned long long * out4)
+// The four statistics of include/pllhip.h: {live now, unstored_stats[kind][1 .. 3]}, added over a group's shards.
+// `with`: a second kind that counts as live with the first (UNSTORED_NONE: none -- nothing is ever live as that)
+static int kind_stats(const pllhip_ctx * c, int kind, int with, unsigned long long * out4)
 {
   for (int t = 0; t < 4; ++t) out4[t] = 0;
-  if (!c->shards.empty())
-  {
-    for (pllhip_ctx * s : c->shards)
-    {
-      out4[0] += s->n_folded;
-      for (int t = 1; t < 4; ++t) out4[t] += s->fold_stats[t];
-    }
-    return 0;
-  }
-  out4[0] = c->n_folded;
-  for (int t = 1; t < 4; ++t) out4[t] = c->fold_stats[t];
+  auto add = [&](const pllhip_ctx * s) {
+    out4[0] += s->n_live[kind] + s->n_live[with];
+    for (int t = 1; t < 4; ++t) out4[t] += s->unstored_stats[kind][t];
+  };
+  if (c->shards.empty()) add(c);
+  for (const pllhip_ctx * s : c->shards) add(s);
   return 0;
 }
-
-extern "C" int pllhip_deferred_stats(pllhip_ctx_t * c, unsigned long long * out4)
-{
-  for (int t = 0; t < 4; ++t) out4[t] = 0;
-  if (!c->shards.empty())
-  {
-    for (pllhip_ctx * s : c->shards)
-    {
-      out4[0] += s->n_deferred - s->n_unstored - s->n_quad_products;
-      for (int t = 1; t < 4; ++t) out4[t] += s->defer_stats[t];
-    }
-    return 0;
-  }
-  out4[0] = c->n_deferred - c->n_unstored - c->n_quad_products;
-  for (int t = 1; t < 4; ++t) out4[t] = c->defer_stats[t];
-  return 0;
-}
-
-extern "C" int pllhip_unstored_stats(pllhip_ctx_t * c, unsigned long long * out4)
-{
-  for (int t = 0; t < 4; ++t) out4[t] = 0;
-  if (!c->shards.empty())
-  {
-    for (pllhip_ctx * s : c->shards)
-    {
-      out4[0] += s->n_unstored;
-      for (int t = 1; t < 4; ++t) out4[t] += s->unstored_stats[t];
-    }
-    return 0;
-  }
-  out4[0] = c->n_unstored;
-  for (int t = 1; t < 4; ++t) out4[t] = c->unstored_stats[t];
-  return 0;
-}
+// cherries, without the products
+extern "C" int pllhip_deferred_stats(pllhip_ctx_t * c, unsigned long long * out4) { return kind_stats(c, UNSTORED_CHERRY, UNSTORED_NONE, out4); }
+// pair products, the folded ones included
+extern "C" int pllhip_unstored_stats(pllhip_ctx_t * c, unsigned long long * out4) { return kind_stats(c, UNSTORED_PAIR, UNSTORED_FOLDED, out4); }
+// the folded ones; [2]: lists planned a second time
+extern "C" int pllhip_pair_fold_stats(pllhip_ctx_t * c, unsigned long long * out4) { return kind_stats(c, UNSTORED_FOLDED, UNSTORED_NONE, out4); }
+extern "C" int pllhip_quad_product_stats(pllhip_ctx_t * c, unsigned long long * out4) { return kind_stats(c, UNSTORED_QUAD, UNSTORED_NONE, out4); }

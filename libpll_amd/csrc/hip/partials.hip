@@ -732,10 +732,10 @@ struct DnaListKept
   std::vector<pllhip_op_t> ops;            // the ops the kernel runs (empty: the caller's list as it is)
   std::vector<FusedExtra> extras;          // their gathered operands (empty: none -- nothing deferred, now or before)
   std::vector<FusedPairJob> keep_jobs;     // the tables of the cherries this list defers
-  std::vector<pllhip_ctx::deferred_cherry> new_deferred; // per deferred op
+  std::vector<pllhip_ctx::deferred_clv> new_deferred; // per deferred op: its record
   std::vector<unsigned int> rows;          // per op of `ops`, four: tip index + 1 of the rows its two gathered factors are
                                            // indexed by (0 none) -- what an unstored pair product is kept with
-  std::vector<pllhip_ctx::unstored_product> new_unstored; // per op whose parent the plan being launched leaves unstored
+  std::vector<pllhip_ctx::deferred_clv> new_unstored; // per op whose parent the plan being launched leaves unstored, folded or walked
   FusedQuadProducts quad_products;         // what the launch is to know to leave parents over two quads unstored, and which it left
   // the list's further state, step by step (update_partials_dna_list)
   std::vector<PartialsArgs> args;          // resolve_op's of the ops the kernel runs
@@ -764,7 +764,7 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
   std::vector<unsigned char> oldf(c->clv.size(), 0);
   std::vector<int> oldsc(c->clv.size(), -1);
   for (size_t i = 0; c->n_deferred && i < c->clv.size(); ++i)
-    if (c->deferred[i].on)
+    if (c->deferred[i].live())
     {
       oldf[i] = 1;
       oldsc[i] = c->deferred[i].scaler;
@@ -775,12 +775,12 @@ static int defer_cherries(pllhip_ctx * c, const pllhip_op_t * ops, unsigned int 
   // be read from its kept table, it is stored first -- an ordinary buffer to this list)
   // (read, not written: an index the list writes is a gathered operand because the list defers the cherry it becomes)
   // (a quad product likewise)
-  if (c->n_unstored || c->n_quad_products)
+  if (c->n_deferred > c->n_live[UNSTORED_CHERRY])
   {
     std::vector<unsigned char> written(c->clv.size(), 0);
     for (unsigned int i = 0; i < count; ++i) written[ops[i].parent_clv] = 1;
     for (size_t i = 0; i < c->clv.size(); ++i)
-      if (oldf[i] && (c->deferred[i].pair || c->deferred[i].quad) && dd.as_tip[i] && !written[i])
+      if (oldf[i] && c->deferred[i].is_product() && dd.as_tip[i] && !written[i])
       {
         dd.as_tip[i] = 0;
         dd.materialise.push_back((unsigned int)i);
@@ -836,8 +836,8 @@ static FusedOperand gathered_operand(pllhip_ctx * c, const pllhip_op_t * ops, co
   {
     const pllhip_ctx::deferred_clv & d = c->deferred[clv];
     g.type = FUSED_G_CHERRY_KEPT;
-    t1 = d.tip1;
-    t2 = d.tip2;
+    t1 = d.cherry.tip1;
+    t2 = d.cherry.tip2;
     g.kept = pllhip_deferred_table(c, clv);
   }
   g.row1 = pllhip_tip_ptr(c, t1);
@@ -868,7 +868,13 @@ static void keep_undeferred_ops(pllhip_ctx * c, const pllhip_op_t * ops, unsigne
     if (dd.defer[i])
     {
       k.keep_jobs.push_back(FusedPairJob{args[i].lmat, args[i].rmat, pllhip_deferred_table(c, op.parent_clv), 1ull, nullptr, nullptr});
-      k.new_deferred.push_back({op.parent_clv, op.child1_clv, op.child2_clv, op.parent_scaler});
+      pllhip_ctx::deferred_clv r;
+      r.kind = UNSTORED_CHERRY;
+      r.clv = op.parent_clv;
+      r.scaler = op.parent_scaler;
+      r.cherry.tip1 = op.child1_clv;
+      r.cherry.tip2 = op.child2_clv;
+      k.new_deferred.push_back(r);
       continue;
     }
     PartialsArgs a = args[i];
@@ -923,10 +929,7 @@ static bool replay_kept_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsig
       memcmp(c->fused_last_ops.data(), full_ops, (size_t)full_count * sizeof(pllhip_op_t)) != 0)
     return false;
   pllhip_prof_scope prof(c, PLLHIP_PROF_PARTIALS_II);
-  c->defer_stats[1] += c->fused_last_deferred.size();
-  c->unstored_stats[1] += c->fused_last_unstored.size();
-  c->quad_product_stats[1] += c->fused_last_quad_products.size();
-  c->fold_stats[1] += c->fused_last_nfolded;
+  for (int kind = 0; kind < UNSTORED_KINDS; ++kind) c->unstored_stats[kind][1] += c->fused_last_unstored_ops[kind];
   *rc = pllhip_relaunch_fused(c);
   if (*rc == 0 && c->fused_last_edge)
   {
@@ -975,7 +978,7 @@ static void resolve_edge(pllhip_ctx * c, DnaListKept & k)
   const unsigned int ends[2] = {q.parent_clv, q.child_clv};
   for (int t = 0; t < 2; ++t)
   {
-    fedge.deferred_before[t] = ends[t] < c->deferred.size() && c->deferred[ends[t]].on;
+    fedge.deferred_before[t] = ends[t] < c->deferred.size() && c->deferred[ends[t]].live();
     fedge.pinned[t] = ends[t] < c->clv_pinned.size() && c->clv_pinned[ends[t]];
   }
   fedge.parent_clv = q.parent_clv;
@@ -1019,7 +1022,12 @@ static void attach_tables(pllhip_ctx * c, DnaListKept & k)
   FusedWalk & w = k.walk;
   k.new_unstored.clear();
   auto remember = [&](const pllhip_op_t & op, const unsigned int * rows, bool folded) {
-    k.new_unstored.push_back({op.parent_clv, op.parent_scaler, {rows[0], rows[1], rows[2], rows[3]}, folded});
+    pllhip_ctx::deferred_clv r;
+    r.kind = folded ? UNSTORED_FOLDED : UNSTORED_PAIR;
+    r.clv = op.parent_clv;
+    r.scaler = op.parent_scaler;
+    memcpy(r.pair.rows, rows, sizeof(r.pair.rows));
+    k.new_unstored.push_back(r);
   };
   // (a folded parent is an unstored pair product whose counts are not in HBM either)
   for (unsigned int i = 0; w.nfolded && i < k.run_count; ++i)
@@ -1088,58 +1096,15 @@ static void commit_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsigned i
     ++c->edge_stats[0];
   }
   for (unsigned int i : k.dd.dropped) pllhip_deferred_drop(c, i);
-  for (const pllhip_ctx::deferred_cherry & n : k.new_deferred)
-  {
-    pllhip_deferred_drop(c, n.clv);
-    pllhip_ctx::deferred_clv & d = c->deferred[n.clv];
-    d.on = true;
-    d.tip1 = n.tip1;
-    d.tip2 = n.tip2;
-    d.scaler = n.scaler;
-    if (n.scaler >= 0) c->deferred_sc_owner[n.scaler] = (int)n.clv;
-    ++c->n_deferred;
-  }
-  for (const pllhip_ctx::unstored_product & n : k.new_unstored)
-  {
-    pllhip_deferred_drop(c, n.clv);
-    pllhip_ctx::deferred_clv & d = c->deferred[n.clv];
-    d.on = d.pair = true;
-    d.folded = n.folded;
-    if (d.folded) ++c->n_folded;
-    for (int r = 0; r < 4; ++r) d.rows[r] = n.rows[r];
-    d.scaler = n.scaler;
-    // (its counts are in HBM -- a folded product's are not --, but they define the CLV: whoever touches them stores
-    // it first)
-    if (n.scaler >= 0) c->deferred_sc_owner[n.scaler] = (int)n.clv;
-    ++c->n_deferred;
-    ++c->n_unstored;
-  }
-  for (const pllhip_ctx::quad_product & n : k.quad_products.left)
-  {
-    pllhip_deferred_drop(c, n.clv);
-    pllhip_ctx::deferred_clv & d = c->deferred[n.clv];
-    d.on = d.quad = true;
-    d.qslot = n.qslot;
-    for (int s = 0; s < 2; ++s)
-    {
-      d.qrow[s] = n.qrow[s];
-      memcpy(d.qtips[s], n.qtips[s], sizeof(d.qtips[s]));
-    }
-    d.scaler = n.scaler;
-    // (its counts are in HBM and define the CLV, as a pair product's do)
-    if (n.scaler >= 0) c->deferred_sc_owner[n.scaler] = (int)n.clv;
-    c->quad_product_owner[n.qslot] = (int)n.clv;
-    ++c->n_deferred;
-    ++c->n_quad_products;
-  }
-  c->quad_product_stats[1] += k.quad_products.left.size();
-  c->fused_last_quad_products = k.quad_products.left;
-  c->defer_stats[1] += k.new_deferred.size();
-  c->unstored_stats[1] += k.new_unstored.size();
-  c->fold_stats[1] += k.walk.nfolded;
-  if (k.walk.nfolded) ++c->fold_stats[2];
-  c->fused_last_unstored = k.new_unstored;
-  c->fused_last_deferred = k.new_deferred;
+  for (const std::vector<pllhip_ctx::deferred_clv> * records : {&k.new_deferred, &k.new_unstored, &k.quad_products.left})
+    for (const pllhip_ctx::deferred_clv & r : *records) pllhip_deferred_begin(c, r);
+  // (what this launch, and every launch of the kept plan after it, counts as left unstored)
+  c->fused_last_unstored_ops[UNSTORED_CHERRY] = (unsigned int)k.new_deferred.size();
+  c->fused_last_unstored_ops[UNSTORED_PAIR] = (unsigned int)k.new_unstored.size();
+  c->fused_last_unstored_ops[UNSTORED_FOLDED] = k.walk.nfolded;
+  c->fused_last_unstored_ops[UNSTORED_QUAD] = (unsigned int)k.quad_products.left.size();
+  for (int kind = 0; kind < UNSTORED_KINDS; ++kind) c->unstored_stats[kind][1] += c->fused_last_unstored_ops[kind];
+  if (k.walk.nfolded) ++c->unstored_stats[UNSTORED_FOLDED][2];
   c->fused_last_defer_epoch = c->defer_epoch;
   c->fused_last_ops.assign(full_ops, full_ops + full_count);
 }

@@ -1769,18 +1769,18 @@ static unsigned int fused_mark_quad_products(pllhip_ctx * c, const std::vector<F
         f.unstored = 0;
         continue;
       }
-      pllhip_ctx::quad_product n;
-      memset(&n, 0, sizeof(n));
+      pllhip_ctx::deferred_clv n;
+      n.kind = UNSTORED_QUAD;
       n.clv = op.parent_clv;
       n.scaler = op.parent_scaler;
-      n.qslot = (unsigned int)slot;
+      n.quad.slot = (unsigned int)slot;
       auto tip_of = [&](const unsigned char * row) { return (unsigned int)((size_t)(row - c->tipchars) / c->tip_stride); };
       for (int s = 0; s < 2; ++s)
       {
         f.keep[s] = pllhip_quad_product_table(c, (unsigned int)slot, (unsigned int)s);
-        n.qrow[s] = quads[sg][2 * pos + s].ref.slot;
+        n.quad.row[s] = quads[sg][2 * pos + s].ref.slot;
         const unsigned int t4[4] = {tip_of(f.g[s].row1), tip_of(f.g[s].row2), tip_of(f.g2[s].row1), tip_of(f.g2[s].row2)};
-        memcpy(n.qtips[s], t4, sizeof(t4));
+        memcpy(n.quad.tips[s], t4, sizeof(t4));
       }
       qp.left.push_back(n);
     }

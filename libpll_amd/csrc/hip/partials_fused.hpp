@@ -723,7 +723,7 @@ struct FusedQuadProducts
   unsigned int count = 0;
   const FusedEdge * edge = nullptr;
   const unsigned char * pinned = nullptr;
-  std::vector<pllhip_ctx::quad_product> left; // out
+  std::vector<pllhip_ctx::deferred_clv> left; // out: their records
 };
 // encode and launch: one plan per segment
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,

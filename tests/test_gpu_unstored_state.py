@@ -22,6 +22,9 @@ B. 48, 96 and 95 jobs: one batch, two full ones, and a second batch of 47.
 C. 70,001 sites: sites * span / 2 lanes against a grid of multi_processor_count * 8 blocks of 256.
 D. a root that moves (tests/unstored_state_data.py; the lists are checked without a device by
    tests/test_unstored_state_lists.py), 60 moves per tree, the planner's state asserted through six conditions.
+E. cherries, folded pair products and quad products live at once on one partition (balanced 32, the twins of
+   tests/test_gpu_quad_products.py), walked through every way the state ends -- read, overwritten by a list, counts
+   read, the two switches -- with the four statistics asserted as absolute numbers after every step.
 
 Measured on one MI355X (256 CUs), with the trees and seeds of unstored_state_data.WALKS and root edges drawn by
 numpy.random.default_rng(1) -- none had to be replaced.  Conditions 1 - 6 (moves with two or more ops that are not
@@ -742,3 +745,91 @@ def test_moving_root_two_shards(gpu, monkeypatch):
         assert (whole.get_scaler(sc) == split.get_scaler(sc)).all(), sc
     for p in (whole, split):
         p.destroy()
+
+
+# ---- E. every kind live at once, and every way its state ends
+
+def _every_stat(p):
+    return dict(cherries=p.deferred_stats(), pairs=p.unstored_stats(), folded=p.pair_fold_stats(),
+                quads=p.quad_product_stats())
+
+
+def test_every_kind_live_at_once_begins_and_ends(gpu, orc, monkeypatch):
+    """Balanced 32 taxa, 4 rate categories, scale buffers, 40 sites (the environment and twins of
+    tests/test_gpu_quad_products.py): after one full traversal the 16 cherries are deferred, the 8 level-2 parents are
+    folded pair products and the 4 level-3 parents are quad products -- every kind of unstored CLV live at once.  One
+    partition is walked through every way such a state ends; after each step the four statistics are asserted as
+    absolute numbers, derived here from the tree's levels and the rules of partials_fused.hpp:
+
+    (a) get_clv of a CLV stores that CLV alone, in a launch of its kind's (a folded product counts as a pair product too);
+    (b) a list of three ops that do not read each other -- a cherry, a level-2 op, a level-3 op, each below another
+        level-3 parent -- overwrites one live CLV of each kind: all three are dropped without a launch (nothing reads
+        them first; their counts go with them).  The cherry is deferred again; the other two parents have no reader in
+        the list and are stored.  The level-2 op gathers its two cherries from their kept tables: they stay deferred.
+        The level-3 op reads two folded products of the earlier call, which no table serves: one launch stores both;
+    (c) get_scaler of a live quad product's counts stores the product: the counts define it;
+    (d) set_unstored_pairs(False) stores the pair products and the quad products -- a launch each --, no cherry;
+    (e) set_deferral(False) stores the cherries.
+    """
+    import test_gpu_quad_products as QP
+    t = QP._setup(gpu, orc, monkeypatch)
+    plan, p = t.plan, t.p
+    one, two, three = (QP._at_level(plan, n) for n in (1, 2, 3))
+    n1, n2, n3 = len(one), len(two), len(three)
+    assert (n1, n2, n3) == (16, 8, 4)
+    by_parent = {QP._node(op)[0]: op for op in plan.ops}
+    kids = lambda op: [by_parent[k] for k in _kids(op)]    # noqa: E731
+    for op in three:
+        assert all(k in [QP._node(o)[0] for o in two] for k in _kids(op))
+    want = dict(cherries=dict(deferred_now=n1, ops_deferred=n1, launches=0, materialised=0),
+                pairs=dict(unstored_now=n2, ops_unstored=n2, launches=0, materialised=0),
+                folded=dict(folded_now=n2, ops_folded=n2, lists_replanned=1, materialised=0),
+                quads=dict(live=n3, ops_unstored=n3, launches=0, materialised=0))
+
+    def step(what, **changes):
+        for kind, delta in changes.items():
+            for key, d in delta.items():
+                want[kind][key] += d
+        got = _every_stat(p)
+        print(what, got)
+        assert got == want, (what, got, want)
+
+    step("one full traversal")
+    # (a) one CLV of each kind, all below the first level-3 parent
+    mine = kids(three[0])[0]
+    QP._same_value(t, QP._node(kids(mine)[0])[0], -1)
+    step("(a) a cherry read", cherries=dict(deferred_now=-1, launches=1, materialised=1))
+    QP._same_value(t, QP._node(mine)[0], -1)
+    step("(a) a folded product read", pairs=dict(unstored_now=-1, launches=1, materialised=1),
+         folded=dict(folded_now=-1, materialised=1))
+    QP._same_value(t, QP._node(three[0])[0], -1)
+    step("(a) a quad product read", quads=dict(live=-1, launches=1, materialised=1))
+    # (b) a cherry below the second level-3 parent, a level-2 op below the third, the fourth level-3 op
+    part = np.array([kids(kids(three[1])[0])[0], kids(three[2])[0], three[3]], dtype=plan.ops.dtype)
+    written = {QP._node(op)[0] for op in part}
+    assert not any(k in written for op in part for k in _kids(op)), "the three ops were meant not to read each other"
+    t.update(part)
+    step("(b) a list overwrites one of each kind", cherries=dict(ops_deferred=1),
+         pairs=dict(unstored_now=-1 - 2, launches=1, materialised=2), folded=dict(folded_now=-1 - 2, materialised=2),
+         quads=dict(live=-1))
+    # (c) the counts of the second level-3 parent, still a quad product
+    node, sc = QP._node(three[1])
+    assert sc >= 0 and (p.get_scaler(sc) == t.o.scalers[sc]).all()
+    step("(c) a quad product's counts read", quads=dict(live=-1, launches=1, materialised=1))
+    QP._same_value(t, node, sc)
+    step("(c) ... and the product, stored by then")
+    # (d), (e)
+    pairs_left, quads_left, cherries_left = want["pairs"]["unstored_now"], want["quads"]["live"], want["cherries"]["deferred_now"]
+    assert (pairs_left, quads_left, cherries_left) == (n2 - 4, n3 - 3, n1 - 1) and want["folded"]["folded_now"] == pairs_left
+    p.set_unstored_pairs(False)
+    step("(d) pair products off", pairs=dict(unstored_now=-pairs_left, launches=1, materialised=pairs_left),
+         folded=dict(folded_now=-pairs_left, materialised=pairs_left),
+         quads=dict(live=-quads_left, launches=1, materialised=quads_left))
+    p.set_deferral(False)
+    step("(e) deferral off", cherries=dict(deferred_now=-cherries_left, launches=1, materialised=cherries_left))
+    assert [want[k][n] for k, n in (("cherries", "deferred_now"), ("pairs", "unstored_now"), ("folded", "folded_now"),
+                                    ("quads", "live"))] == [0, 0, 0, 0]
+    # every CLV and scale buffer against the per-level twin, the quads-off twin and the oracle
+    t.check()
+    step("everything read")
+    t.destroy()
