@@ -20,7 +20,7 @@ CFLAGS   := -std=gnu11 -O2 -fPIC -g -Wall -Wextra -ffp-contract=off -fvisibility
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -ffp-contract=off -fvisibility=hidden \
             -Wall -Iinclude -Ilibpll_amd/csrc/hip $(EXTRA_HIPFLAGS)
 
-.PHONY: lib oracle all clean asan asan-model-score asan-nni-support
+.PHONY: lib oracle all clean asan asan-model-score asan-nni-support asan-tree-replicates
 lib: $(OUT)
 all: lib oracle
 
@@ -96,7 +96,16 @@ $(ASAN_DIR)/nni_support_args: tools/nni_support_args.c $(ASAN_OBJ) $(HIP_OBJ)
 asan-nni-support: $(ASAN_DIR)/nni_support_args
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/nni_support_args
 
-asan: asan-model-score asan-nni-support $(ASAN_DIR)/libpll_amd.so $(ASAN_DIR)/liboracle.so
+# the refusals of pll_amd_tree_replicate_loglikelihood that come before the partition's device, the same way
+$(ASAN_DIR)/tree_replicates_args: tools/tree_replicates_args.c $(ASAN_OBJ) $(HIP_OBJ)
+	gcc $(filter-out -O2,$(CFLAGS)) $(ASAN_FLAGS) -c $< -o $(ASAN_DIR)/tree_replicates_args.o
+	g++ $(ASAN_FLAGS) -Wl,-rpath,/opt/rocm/lib -o $@ $(ASAN_DIR)/tree_replicates_args.o $(ASAN_OBJ) $(HIP_OBJ) \
+	    -L/opt/rocm/lib -lamdhip64 -lm -ldl
+
+asan-tree-replicates: $(ASAN_DIR)/tree_replicates_args
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/tree_replicates_args
+
+asan: asan-model-score asan-nni-support asan-tree-replicates $(ASAN_DIR)/libpll_amd.so $(ASAN_DIR)/liboracle.so
 	LD_PRELOAD="$$(gcc -print-file-name=libasan.so) $$(gcc -print-file-name=libubsan.so)" \
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1:allocator_may_return_null=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
 	PLL_AMD_LIB=$(abspath $(ASAN_DIR)/libpll_amd.so) PLL_ORACLE_LIB=$(abspath $(ASAN_DIR)/liboracle.so) \

@@ -994,9 +994,10 @@ typedef struct pll_amd_tree_candidate
  * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
  * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
  * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: per-candidate model parameters or category
- * rates (pll_amd_model_loglikelihood below scores models on one tree), per-site outputs (pll_amd_replicate_loglikelihood
- * below returns those of the partition's own edges), applying a candidate to the partition, and lists in which an op reads a CLV that a later op
- * of the same candidate overwrites (they have a meaning in the sequence and no use here).  INTEGRATION.md section 4f. */
+ * rates (pll_amd_model_loglikelihood below scores models on one tree), per-site outputs in this call
+ * (pll_amd_tree_replicate_loglikelihood below returns the candidates' own), applying a candidate to the partition, and
+ * lists in which an op reads a CLV that a later op of the same candidate overwrites (they have a meaning in the
+ * sequence and no use here).  INTEGRATION.md section 4f. */
 PLL_EXPORT int pll_amd_tree_loglikelihood(pll_partition_t * partition,
                                           const pll_amd_tree_candidate_t * candidates, unsigned int count,
                                           const unsigned int * params_indices,
@@ -1105,14 +1106,67 @@ PLL_EXPORT unsigned int pll_amd_replicates_count(const pll_amd_replicates_t * se
  * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
  * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
  * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: generating the resampled weights (the
- * client's random number generator defines them), candidate op lists in the same call (run the list, then ask at its
- * edge), weights of type double.  INTEGRATION.md section 4h. */
+ * client's random number generator defines them), candidate op lists in this call
+ * (pll_amd_tree_replicate_loglikelihood below takes them), weights of type double.  INTEGRATION.md section 4h. */
 PLL_EXPORT int pll_amd_replicate_loglikelihood(pll_partition_t * partition,
                                                const pll_amd_replicates_t * set,   /* may be NULL */
                                                const pll_amd_lnl_edge_t * edges, unsigned int edge_count,
                                                const unsigned int * freqs_indices,
                                                double * lnl,           /* out [edge][count], NULL iff set is NULL */
                                                double * persite_lnl);  /* out [edge][sites], unweighted; may be NULL */
+
+/* ---- candidate trees under a replicate set: RELL over a search's trees (tree_replicates.c, tree_replicates.hip) ----
+ * Many candidate trees (pll_amd_tree_candidate_t, as pll_amd_tree_loglikelihood takes them), each scored against every
+ * replicate of a set, in one call: what a UFBoot loop asks of every tree of a search, and the resampling step of the
+ * KH / SH / AU tests of a set of trees.
+ * persite_lnl[c * sites + n] = the per-site output, under unit pattern weights, of the sequence that defines
+ * pll_amd_tree_loglikelihood for candidate c -- pll_update_prob_matrices(params_indices, its matrix_indices,
+ * branch_lengths, matrix_count); pll_update_partials(its operations, op_count); pll_compute_edge_loglikelihood(its
+ * edge, freqs_indices = params_indices, persite) with every pattern weight set to 1 --: log(terma) + scalings *
+ * log(2^-256).  What a candidate does not list or write is the partition's current content, as there.
+ * lnl[c * count + r] = sum_n (double)w_r[n] * persite_lnl[c][n] with count = pll_amd_replicates_count(set), in the
+ * term formation and the sum order of pll_amd_replicate_loglikelihood, verbatim: a rounded product, added afterwards,
+ * no fused multiply-add; spans of 2048 sites, each added one by one in site order from +0; the spans' sums added one
+ * by one in span order from +0.  It agrees with the sequence under replicate r's weights to about 1e-12 relative
+ * (1e-11 for 20 states), not bit for bit.  A site whose likelihood is zero has persite_lnl -inf: a positive weight there
+ * gives -inf, weight 0 gives 0 x -inf = NaN, as in pll_amd_replicate_loglikelihood.
+ * best_lnl[r] / best_index[r] = the running maximum of lnl[c][r] over the candidates in ascending c.  Nobody holds a
+ * replicate at the start: index UINT_MAX, value NaN.  Candidate c takes over when nobody holds the replicate and its
+ * value is not NaN, or when its value is strictly greater than the held one (plain IEEE comparisons: a NaN never
+ * takes over and, once somebody holds, -inf never does).  Ties therefore keep the lowest index; a replicate where
+ * every value is NaN keeps UINT_MAX / NaN.  The maximum is taken on the device over each chunk's table and carried
+ * from chunk to chunk, so with lnl == NULL the candidates x replicates table never leaves the device.
+ * With set == NULL: lnl, best_index and best_lnl are NULL and persite_lnl is required (the unweighted site
+ * log-likelihoods of many candidate trees).  With a set: at least one of lnl, persite_lnl and the best pair;
+ * best_index and best_lnl come together or not at all.
+ * Bits: a value is the same bits whatever else is in the batch, in whatever order, however the call chunks it, on a
+ * repeated call, whichever outputs are asked for, whatever else is in the set and however the set stores its weights
+ * (best_index names positions in THIS batch); a replicate with weight 1 at one site and 0 elsewhere returns that
+ * site's persite_lnl bit for bit, an all-zero replicate 0 (where every site's likelihood is positive).
+ * What lives where: as for pll_amd_tree_loglikelihood -- for 4 states with 1 or 4 rate categories and no per-rate
+ * scale buffers a candidate's CLVs live on the chip only and the tree kernel stores the site's value itself; for every
+ * other shape and for lists over 16 live values per site they are scratch --, plus a row of site terms per candidate,
+ * per-span partial sums and the chunk's table, scratch of the partition on its device, kept until it is destroyed.
+ * The call changes nothing of the partition (the lazy eigen systems of pll_amd_tree_loglikelihood apart) or of the
+ * set.  Large batches are worked in chunks of whole candidates of at most about PLL_AMD_TREE_REPLICATE_SCRATCH_MB
+ * (environment, read at call time, default 2048, fractions allowed) of scratch, one candidate at least.  The call is
+ * synchronous.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, all outputs untouched): the output rules above; the
+ * set belongs to this partition; everything pll_amd_tree_loglikelihood checks of candidates, count and
+ * params_indices.
+ * Limits (PLL_ERROR_HIP_UNSUPPORTED): partitions with PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction,
+ * sharded over devices (pll_amd_set_devices) or joined to an RCCL communicator (pll_amd_comm_init).
+ * PLL_ERROR_MEM_ALLOC: one chunk's scratch could not be had.  Not offered: per-candidate models, weights of type
+ * double, generating the weights (the client's random number generator defines them), the p-values of the KH / SH / AU
+ * tests (they are functions of the table or of the best pair: the client's).  INTEGRATION.md section 4m. */
+PLL_EXPORT int pll_amd_tree_replicate_loglikelihood(pll_partition_t * partition,
+    const pll_amd_replicates_t * set,                 /* may be NULL */
+    const pll_amd_tree_candidate_t * candidates, unsigned int count,
+    const unsigned int * params_indices,
+    double * lnl,               /* out [candidate][replicates], may be NULL */
+    double * persite_lnl,       /* out [candidate][sites], unweighted; may be NULL */
+    unsigned int * best_index,  /* out [replicates], may be NULL */
+    double * best_lnl);         /* out [replicates], may be NULL */
 
 /* ---- batched branch support: aLRT, aBayes, SH-aLRT and local bootstrap of many inner edges (nni_support.c,
  * nni_support.hip) ----

@@ -717,6 +717,25 @@ PLLHIP_EXPORT int pllhip_replicate_loglikelihood(pllhip_ctx_t * ctx, const pllhi
                                                  const unsigned int * h_freqs_indices, size_t scratch_bytes,
                                                  double * h_lnl, double * h_persite);
 
+/* ---- candidate trees under a replicate set (tree_replicates.hip; host side host/tree_replicates.c) ----
+ * The candidates of pllhip_tree_loglikelihood, each kept per site and resampled: s[c][n] the unweighted per-site
+ * log-likelihood of candidate c at its edge (h_persite [c][sites]), h_lnl[c][r] = sum_n (double)w_r[n] * s[c][n] over
+ * the set in the term formation and sum order of pllhip_replicate_loglikelihood, and the running maximum over the
+ * candidates in ascending c, per replicate: h_best_index[r] / h_best_lnl[r], UINT_MAX / NaN while no candidate holds
+ * it; c takes over when nobody holds it and its value is not NaN, or when its value is strictly greater.  The rule is
+ * written out at pll_amd_tree_replicate_loglikelihood (include/pll_amd.h).  set may be NULL: then h_lnl and the best
+ * pair are NULL too and h_persite is required; with a set any of the three outputs; the best pair comes together.
+ * route, max_slots as for pllhip_tree_loglikelihood: on the kernel route k_tree_score stores the site's value itself
+ * and no CLV is written, on the general route the scratch CLVs' edges go through k_repl_site_terms.  Scratch (kept by
+ * the context) is at most about scratch_bytes per chunk of whole candidates, one candidate's worth at least.  Nothing
+ * of the context or of the set changes.  Returns -1 for a bad argument (nothing launched, outputs untouched), -2 if a
+ * chunk's scratch cannot be had, -3 for a context this call does not take (asc-bias, site repeats, sharded, RCCL). */
+PLLHIP_EXPORT int pllhip_tree_replicate_loglikelihood(pllhip_ctx_t * ctx, const pllhip_replicates_t * set,
+                                                      const pllhip_tree_candidate_t * h_candidates, unsigned int count,
+                                                      const unsigned int * h_params_indices, int route, int max_slots,
+                                                      size_t scratch_bytes, double * h_lnl, double * h_persite,
+                                                      unsigned int * h_best_index, double * h_best_lnl);
+
 /* ---- batched branch support (nni_support.hip; host side host/nni_support.c) ----
  * The three arrangements of pllhip_nni_loglikelihood around every edge, per site and resampled: s[e][k][n] the
  * unweighted per-site log-likelihood of candidate (e, k) -- the central branch h_central[3 e + k] long where

@@ -27,7 +27,9 @@ struct pllhip_rep_work;
 // the candidates' per-site terms, per-span partial sums, the replicate table, centres and counts and, on the general
 // route, candidate CLVs and scale buffers; distances -- the two factors of the bin table, the chunk's count tables, Newton
 // states, start lengths and results, its jobs and the pairs' tips; joining -- the working distance and variance matrices,
-// the row sums, the slots' node numbers, the scan's candidates, the step record and the joins
+// the row sums, the slots' node numbers, the scan's candidates, the step record and the joins; tree replicates -- the
+// chunk's candidates' per-site rows, per-span partial sums, its table and the running best (what the candidates
+// themselves need is tree scoring's)
 struct BatchScratch
 {
   void * p = nullptr;
@@ -44,6 +46,7 @@ enum
   BATCH_NNI_SUPPORT,
   BATCH_DISTANCE,
   BATCH_JOINING,
+  BATCH_TREE_REPLICATES,
   BATCH_FAMILIES
 };
 

@@ -26,6 +26,10 @@
 // planned once, every item has its own matrices, records and model block, and the kernel's and the edge kernel's
 // model variants take the edge term's frequencies, weights and +I proportions from the item's block.
 //
+// And it hands the candidates' site terms to a call that keeps them apart (pllhip_tree_score_run with a sink;
+// tree_replicates.hip): the kernel's SITES variant stores the lane's own site instead of summing the tile, the general
+// route's edge descriptors go to the sink's site-term kernel, and there is no reduction.
+//
 // Determinism: tiles are PLLHIP_BATCH_TILE sites fixed by the site count; a candidate's plan, records and partial sums
 // depend on the candidate alone, every sum runs in a fixed order.  A candidate's value does not depend on the batch, its order or
 // the chunking.  No atomics, no barrier inside the walk, no traffic between waves.
@@ -319,6 +323,8 @@ struct TsArgs
   double * __restrict__ partial;      // [chunk's candidates][tiles]
   unsigned int sites, tiles, nslots;
   BatchModelBlocks mb; // (MODEL only)
+  double * __restrict__ rows;         // (SITES only) [chunk's candidates][spitch]: the sites' own values
+  unsigned int spitch;
 };
 
 // A record is the same for every lane: read through the constant address space it is loaded by the scalar unit into
@@ -448,7 +454,10 @@ __device__ __forceinline__ void ts_product(const TsSide & s, const char * mrow, 
 // MODEL: the edge term's frequencies, category weights and +I proportions are those of the candidate's model block
 // (pllhip_tree_score_run with models).  They are the same for every lane: read through the constant address space, as
 // the records are, every category's values arrive in scalar registers and a lane keeps its own category's.
-template <int R, bool MODEL>
+// SITES: the lane's own site keeps its value -- lk, unweighted, to rows[candidate][site], 0 from the last site to
+// spitch (the tiles cover it: the zero tail of k_repl_site_terms) -- and no tile sum is formed
+// (pllhip_tree_score_run with a sink).
+template <int R, bool MODEL, bool SITES = false>
 __global__ __launch_bounds__(256) void k_tree_score(TsArgs a)
 {
   extern __shared__ __attribute__((aligned(16))) char ts_lds[];
@@ -613,10 +622,15 @@ __global__ __launch_bounds__(256) void k_tree_score(TsArgs a)
   {
     double lk = log(o_t);
     if (o_c) lk += (double)o_c * log(PLLHIP_SCALE_THRESHOLD);
-    acc = lk * (double)a.m.pattern_weights[n_own];
+    acc = SITES ? lk : lk * (double)a.m.pattern_weights[n_own];
   }
-  // the tile's sum: wave trees, then the four waves in order
-  batch_tile_sum(acc, s_wave, a.partial + (size_t)cd.out * a.tiles + tile);
+  if constexpr (SITES)
+  {
+    if (n_own < a.spitch) a.rows[(size_t)cd.out * a.spitch + n_own] = acc;
+  }
+  else
+    // the tile's sum: wave trees, then the four waves in order
+    batch_tile_sum(acc, s_wave, a.partial + (size_t)cd.out * a.tiles + tile);
 }
 
 // ------------------------------------------------------------------------------------------------ the call
@@ -626,10 +640,11 @@ __global__ __launch_bounds__(256) void k_tree_score(TsArgs a)
 // matrices (pllhip_model_pmatrices), records and model block
 int pllhip_tree_score_run(pllhip_ctx * c, const char * what, const pllhip_tree_candidate_t * C, unsigned int count,
                           const unsigned int * params, int route, int max_slots, size_t budget, double * h_lnl,
-                          const TsModels * models)
+                          const TsModels * models, const TsSiteSink * sink)
 {
   pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
-  if (!C || !params || !count || !h_lnl || (models && (count != 1 || !models->count || !models->h_blocks)))
+  if (!C || !params || !count || (!h_lnl && !sink) ||
+      (models && (sink || count != 1 || !models->count || !models->h_blocks)))
   {
     pllhip_set_error("%s: empty batch or NULL array", what);
     return -1;
@@ -731,6 +746,7 @@ int pllhip_tree_score_run(pllhip_ctx * c, const char * what, const pllhip_tree_c
     size_t b = (size_t)C[i].matrix_count * c->pmat_elems * 8 + (size_t)tiles * 8 + 8 + 512;
     b += by_kernel[i] ? nk * sizeof(TsOp) + sizeof(TsCand) : nk * (clv_b + sc_b + 512) + sizeof(BatchEdge);
     if (models) b += (size_t)ml.doubles * 8;
+    if (sink) b += sink->item_bytes;
     return b;
   };
 
@@ -750,7 +766,8 @@ int pllhip_tree_score_run(pllhip_ctx * c, const char * what, const pllhip_tree_c
   {
     // ---- the chunk: whole candidates within `budget` bytes, one at least
     unsigned int cn = 0;
-    size_t used = 8192 + pllhip_batch_align(len_b), nmat = 0, nrec = 0, nkc = 0, ngc = 0, ngen = 0;
+    size_t used = 8192 + pllhip_batch_align(len_b) + (sink ? sink->fixed_bytes : 0);
+    size_t nmat = 0, nrec = 0, nkc = 0, ngc = 0, ngen = 0;
     unsigned int chunk_slots = 1;
     while (c0 + cn < items && cn < 65535u)
     {
@@ -778,8 +795,8 @@ int pllhip_tree_score_run(pllhip_ctx * c, const char * what, const pllhip_tree_c
     const size_t o_ops = L.take(nrec * sizeof(TsOp));
     const size_t o_cand = L.take(nkc * sizeof(TsCand));
     const size_t o_edge = L.take(ngc * sizeof(BatchEdge));
-    const size_t o_part = L.take((size_t)cn * tiles * 8);
-    const size_t o_out = L.take((size_t)cn * 8);
+    const size_t o_part = L.take(sink ? 0 : (size_t)cn * tiles * 8); // (a sink keeps the sites apart: no sums)
+    const size_t o_out = L.take(sink ? 0 : (size_t)cn * 8);
     const size_t o_blk = L.take(models ? (size_t)cn * ml.doubles * 8 : 0);
     const size_t o_len = L.take(len_b);
     const size_t o_zero = L.off; // from here: zeroed on every chunk (the slack behind every scratch CLV reads as zeros)
@@ -798,6 +815,8 @@ int pllhip_tree_score_run(pllhip_ctx * c, const char * what, const pllhip_tree_c
     double * d_clv = (double *)(base + o_clv);
     unsigned int * d_scal = (unsigned int *)(base + o_scal);
     const BatchModelBlocks mb = {(const double *)(base + o_blk), ml.doubles, ml.freqs, ml.pinv, ml.weights};
+    double * d_rows = nullptr;
+    if (sink && (rc = sink->begin(sink->self, cn, &d_rows))) return rc;
 
     // ---- the candidates' own matrices
     if (models)
@@ -963,10 +982,17 @@ int pllhip_tree_score_run(pllhip_ctx * c, const char * what, const pllhip_tree_c
         q.mb = mb;
         q.m.invariant = c->invariant; // (a candidate's proportion may be positive where none of the partition's is)
       }
+      if (sink)
+      {
+        q.rows = d_rows;
+        q.spitch = sink->spitch;
+      }
       const size_t lds = TS_HEAD_BYTES + 4u * TS_STAGE_BYTES + (size_t)chunk_slots * 4u * TS_SLOT_BYTES;
       const dim3 grid(tiles, (unsigned int)nkc);
-      void (*const kernel)(TsArgs) = models ? (R == 4 ? &k_tree_score<4, true> : &k_tree_score<1, true>)
-                                            : (R == 4 ? &k_tree_score<4, false> : &k_tree_score<1, false>);
+      void (*const kernel)(TsArgs) =
+          sink ? (R == 4 ? &k_tree_score<4, false, true> : &k_tree_score<1, false, true>)
+               : models ? (R == 4 ? &k_tree_score<4, true> : &k_tree_score<1, true>)
+                        : (R == 4 ? &k_tree_score<4, false> : &k_tree_score<1, false>);
       if (lds > 65536)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -985,8 +1011,20 @@ int pllhip_tree_score_run(pllhip_ctx * c, const char * what, const pllhip_tree_c
       }
       HIP_TRY(hipMemcpyAsync(d_edges, h_edges.data(), ngc * sizeof(BatchEdge), hipMemcpyHostToDevice, c->stream));
       pllhip_prof_scope prof(c, PLLHIP_PROF_LNL);
-      if ((rc = pllhip_batch_edge_lnl(c, d_edges, (unsigned int)ngc, params, d_part, tiles, models ? &mb : nullptr)))
+      if (sink)
+      {
+        // the descriptors' site terms, kept apart: descriptor i's row is its `out`
+        if ((rc = sink->edge_terms(sink->self, d_edges, (unsigned int)ngc, params))) return rc;
+      }
+      else if ((rc = pllhip_batch_edge_lnl(c, d_edges, (unsigned int)ngc, params, d_part, tiles,
+                                           models ? &mb : nullptr)))
         return rc;
+    }
+    if (sink)
+    {
+      if ((rc = sink->end(sink->self, c0, cn))) return rc; // (waits for the stream)
+      c0 += cn;
+      continue;
     }
     if ((rc = pllhip_batch_reduce(c, d_part, d_out, cn, tiles))) return rc;
     hout.resize(cn);

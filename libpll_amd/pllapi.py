@@ -341,6 +341,9 @@ class PllLibrary:
                 lib.pll_amd_replicates_count.argtypes = [C.c_void_p]
                 lib.pll_amd_replicate_loglikelihood.argtypes = [_PP, C.c_void_p, C.c_void_p, C.c_uint, _up,
                                                                 C.c_void_p, C.c_void_p]
+            if hasattr(lib, "pll_amd_tree_replicate_loglikelihood"):
+                lib.pll_amd_tree_replicate_loglikelihood.argtypes = [_PP, C.c_void_p, C.c_void_p, C.c_uint, _up] + \
+                                                                    [C.c_void_p] * 4
             if hasattr(lib, "pll_amd_nni_support"):
                 lib.pll_amd_nni_support.argtypes = [_PP, C.c_void_p, C.c_void_p, C.c_uint, _up, C.c_void_p,
                                                     C.c_double] + [C.c_void_p] * 7
@@ -1325,6 +1328,32 @@ class Partition:
                                                       persite.ctypes.data if persite is not None and persite.size else None)
         self._check(ok, "pll_amd_replicate_loglikelihood")
         return lnl, persite
+
+    def tree_replicate_loglikelihood(self, rset, candidates, params_indices, want_lnl=True, want_persite=False,
+                                     want_best=False):
+        """pll_amd_tree_replicate_loglikelihood: (lnl [candidates][count], persite [candidates][sites], best_index
+        [count], best_lnl [count]), None where an output was not asked for.  rset: a Replicates of this partition, or
+        None (then only the unweighted per-site log-likelihoods are computed); candidates: rows as tree_loglikelihood
+        takes them."""
+        if not hasattr(self.lib, "pll_amd_tree_replicate_loglikelihood"):
+            raise PllError("this library has no pll_amd_tree_replicate_loglikelihood")
+        arr, keep = tree_candidates(candidates)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        n = len(candidates)
+        reps = rset.count if rset is not None else 0
+        lnl = np.zeros((n, reps)) if (rset is not None and want_lnl) else None
+        persite = np.zeros((n, self.s.sites)) if (want_persite or rset is None) else None
+        best_index = np.zeros(reps, dtype=np.uint32) if (rset is not None and want_best) else None
+        best_lnl = np.zeros(reps) if (rset is not None and want_best) else None
+
+        def ptr(x):
+            return x.ctypes.data if x is not None and x.size else None
+        ok = self.lib.pll_amd_tree_replicate_loglikelihood(self.ptr, rset.ptr if rset is not None else None,
+                                                           C.addressof(arr) if n else None, n, _u(pi), ptr(lnl),
+                                                           ptr(persite), ptr(best_index), ptr(best_lnl))
+        del keep
+        self._check(ok, "pll_amd_tree_replicate_loglikelihood")
+        return lnl, persite, best_index, best_lnl
 
     # -- reading results back ----------------------------------------------------------
     def get_clv(self, idx):
