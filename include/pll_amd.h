@@ -1675,6 +1675,12 @@ PLL_EXPORT int pll_amd_quad_list_stats(pll_partition_t * partition, unsigned lon
  * materialised} -- counted here only, never in the deferred, unstored or pair-fold statistics. */
 PLL_EXPORT int pll_amd_set_unstored_quad_products(pll_partition_t * partition, int on);
 PLL_EXPORT int pll_amd_quad_product_stats(pll_partition_t * partition, unsigned long long * stats4);
+/* Folded quad products (pllhip.h: pllhip_set_quad_fold): an unstored quad product with exactly one reader, an
+ * inner-inner op, is not walked; its reader gathers the two quads and forms the product.  On by default; 0 walks such
+ * parents again (no CLV is stored).  stats4: {folded parents live now, ops folded in total, lists planned once more
+ * for them, folded CLVs materialised}; pll_amd_quad_product_stats counts them with the walked ones. */
+PLL_EXPORT int pll_amd_set_quad_fold(pll_partition_t * partition, int on);
+PLL_EXPORT int pll_amd_quad_fold_stats(pll_partition_t * partition, unsigned long long * stats4);
 /* Edge log-likelihood terms from the 4-state whole-list launch (pllhip.h: pllhip_set_edge_fold): after
  * pll_compute_edge_loglikelihood at an inner-inner edge, the next pll_update_partials that writes one of the edge's two
  * CLVs also forms the edge's per-site terms, and the same evaluation then only sums them -- bit for bit the value it

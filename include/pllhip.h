@@ -348,6 +348,31 @@ PLLHIP_EXPORT int pllhip_fused_quad_rule_dry(int cherries, int instance, unsigne
  * pllhip_deferred_stats, pllhip_unstored_stats and pllhip_pair_fold_stats do not count them. */
 PLLHIP_EXPORT int pllhip_set_unstored_quad_products(pllhip_ctx_t * ctx, int on);
 PLLHIP_EXPORT int pllhip_quad_product_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+/* Folded quad products.  An unstored quad product that exactly one op of the list reads, on one side,
+ * that reader an inner-inner op, is not walked at all: the reader gathers the two quads itself and forms the product,
+ * with the scaling test of the op that is no longer walked, and the launch plans the list once more without such ops.
+ * The parent's counts are then not in HBM either: the launch that stores the CLV forms and writes them.
+ * pllhip_set_quad_fold(ctx, 0): such parents are walked as before (no CLV is stored: those folded now stay what they
+ * are); 1: the default; nothing folds while pllhip_set_unstored_quad_products, pllhip_set_quad_rows,
+ * pllhip_set_unstored_pairs or pllhip_set_deferral is off.
+ * pllhip_quad_fold_stats: {folded parents live now, ops folded in total, lists planned once more for them, folded CLVs
+ * materialised}; pllhip_quad_product_stats counts the folded parents with the walked ones. */
+PLLHIP_EXPORT int pllhip_set_quad_fold(pllhip_ctx_t * ctx, int on);
+PLLHIP_EXPORT int pllhip_quad_fold_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+/* Host logic, no device (tests/test_host_quad_fold.py): pllhip_fused_plan_dry_quad_products, then -- fold_on -- the quad
+ * fold the launch applies behind it.  qfolded_out[i] = 1: op i of the list is a quad product folded into its reader;
+ * *walked_out: the ops the kernel walks; products_out / *bytes_out as there, of the plan that is launched (a folded
+ * parent is a quad product too). */
+PLLHIP_EXPORT int pllhip_fused_plan_dry_quad_fold(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                                  int pattern_tip, unsigned int rate_cats, int rate_scalers,
+                                                  const pllhip_op_t * ops, unsigned int count, unsigned int nslots,
+                                                  const unsigned char * pinned, const int * edge4, unsigned int sites,
+                                                  int quads_on, unsigned int min_sites_per_class,
+                                                  const unsigned int * classes, const double * bounds, int fold_on,
+                                                  unsigned int * nkept, unsigned int * order_out, unsigned char * folded_out,
+                                                  int * ops_out, int * quads_out, unsigned int * counts_out,
+                                                  unsigned char * products_out, unsigned int * bytes_out,
+                                                  unsigned char * qfolded_out, unsigned int * walked_out);
 /* Host logic, no device (tests/test_host_quad_products.py): pllhip_fused_plan_dry_quads, then the rule the launch
  * applies behind the quads'.  products_out[i] = 1: op i of the list is walked over two taken quads and its parent is not
  * stored; *bytes_out (may be NULL): the plan's bytes per site -- one write per entry of every stored CLV of the walk and

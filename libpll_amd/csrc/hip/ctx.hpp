@@ -58,6 +58,7 @@ enum
   UNSTORED_PAIR,
   UNSTORED_FOLDED,
   UNSTORED_QUAD,
+  UNSTORED_QUAD_FOLDED,
   UNSTORED_KINDS
 };
 
@@ -223,6 +224,8 @@ struct pllhip_ctx
   //                    launch's two quad tables (quad_product_pool), the classes read from two quad rows -- which stay
   //                    as they are while the product lives: quad_rows.hip stores it first --, times 2^256 where the
   //                    op's count (in HBM, in `scaler`) is not 0.
+  //   UNSTORED_QUAD_FOLDED  a quad product folded into its reader (not walked): the same record, tables and rows, but its
+  //                    counts are not in HBM either -- the materialising launch forms the scale bits and writes them.
   struct deferred_clv
   {
     unsigned char kind = UNSTORED_NONE;
@@ -238,6 +241,7 @@ struct pllhip_ctx
     } quad;
     bool live() const { return kind != UNSTORED_NONE; }
     bool is_pair() const { return kind == UNSTORED_PAIR || kind == UNSTORED_FOLDED; }
+    bool is_quad() const { return kind == UNSTORED_QUAD || kind == UNSTORED_QUAD_FOLDED; }
     bool is_product() const { return kind > UNSTORED_CHERRY; } // no table a list kernel could gather it from
   };
   std::vector<deferred_clv> deferred;          // per CLV index (sized on first use)
@@ -246,7 +250,8 @@ struct pllhip_ctx
   unsigned int n_live[UNSTORED_KINDS] = {};    // live records per kind ...
   unsigned int n_deferred = 0;                 // ... and of every kind: what every PLLHIP_DEFERRED_* site tests
   // per kind {-, ops left unstored, materialising launches, CLVs materialised}, as include/pllhip.h defines them:
-  // UNSTORED_PAIR's row counts every pair product, the folded ones included; UNSTORED_FOLDED's [2]: lists planned twice
+  // UNSTORED_PAIR's row counts every pair product, the folded ones included; UNSTORED_FOLDED's [2]: lists planned twice;
+  // UNSTORED_QUAD's row counts every quad product likewise; UNSTORED_QUAD_FOLDED's [2]: lists planned once more for them
   unsigned long long unstored_stats[UNSTORED_KINDS][4] = {};
   unsigned int fused_last_unstored_ops[UNSTORED_KINDS] = {}; // what a launch of the kept plan adds to unstored_stats[kind][1]
   double * defer_pool = nullptr;               // [CLV index][defer_pool_tables][256][span]: the kept tables
@@ -256,6 +261,7 @@ struct pllhip_ctx
   bool unstored_pairs = true;                  // pllhip_set_unstored_pairs
   bool pair_fold = true;                       // pllhip_set_pair_fold: unstored parents with one reader are not walked
   bool unstored_quad_products = true;          // pllhip_set_unstored_quad_products
+  bool quad_fold = true;                       // pllhip_set_quad_fold: unstored quad products with one reader are not walked
   unsigned int fused_last_nfolded = 0;         // ops the kept plan folds (not walked)
   double * quad_product_pool = nullptr;        // [slot][2 tables][PLLHIP_QUAD_MAX_CLASSES][span]: kept copies of the quad tables
   std::vector<int> quad_product_owner;         // per slot: the CLV of the live product that has it, or -1

@@ -23,7 +23,9 @@
 // A quad product ("Unstored quad products") is Qa[class a of n] * Qb[class b of n] -- the classes from
 // the two quad rows, Qa and Qb kept copies of the launch's two quad tables ([class][rate][state]) --, times 2^256 where
 // the op's count of the site (in HBM: a quad brings none, so it is the op's own scale bit) is not 0.  A launch of its
-// own kernel, never part of a k_deferred_materialise batch.
+// own kernel, never part of a k_deferred_materialise batch.  A FOLDED one (pllhip_set_quad_fold) was not walked -- its
+// one reader gathered the two quads and formed the product in registers --, so, like a folded pair product's, its
+// counts are formed and WRITTEN by the launch: the same batch, a flag per job.
 #include <algorithm>
 
 #include "ctx.hpp"
@@ -121,7 +123,8 @@ struct QuadProductJobs
   const unsigned char * row_a[PLLHIP_QUAD_PRODUCT_BATCH];
   const unsigned char * row_b[PLLHIP_QUAD_PRODUCT_BATCH];
   pll_v2d * clv[PLLHIP_QUAD_PRODUCT_BATCH];
-  const unsigned int * counts[PLLHIP_QUAD_PRODUCT_BATCH]; // nullptr: none
+  unsigned int * counts[PLLHIP_QUAD_PRODUCT_BATCH]; // nullptr: none
+  unsigned char folded[PLLHIP_QUAD_PRODUCT_BATCH];  // its counts are FORMED and written (never walked)
 };
 static_assert(sizeof(QuadProductJobs) <= 3900, "the jobs travel as kernel arguments");
 
@@ -135,7 +138,8 @@ __global__ __launch_bounds__(256) void k_quad_product_materialise(QuadProductJob
   const unsigned char * __restrict__ row_a = jobs.row_a[blockIdx.y];
   const unsigned char * __restrict__ row_b = jobs.row_b[blockIdx.y];
   pll_v2d * __restrict__ clv = jobs.clv[blockIdx.y];
-  const unsigned int * __restrict__ counts = jobs.counts[blockIdx.y];
+  unsigned int * __restrict__ counts = jobs.counts[blockIdx.y];
+  const bool folded = jobs.folded[blockIdx.y] != 0;
   const size_t total = sites * span2;
   for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
   {
@@ -144,7 +148,18 @@ __global__ __launch_bounds__(256) void k_quad_product_materialise(QuadProductJob
     // (a class is below the row's class count, at most PLLHIP_QUAD_MAX_CLASSES: inside the kept table)
     const unsigned int ca = pllhip_quad_row_class(row_a, n, row_stride) & (PLLHIP_QUAD_MAX_CLASSES - 1u);
     const unsigned int cb = pllhip_quad_row_class(row_b, n, row_stride) & (PLLHIP_QUAD_MAX_CLASSES - 1u);
-    store_product<NT>(qa[(size_t)ca * span2 + g], qb[(size_t)cb * span2 + g], counts && counts[n], clv + t);
+    const pll_v2d a = qa[(size_t)ca * span2 + g], b = qb[(size_t)cb * span2 + g];
+    bool scale = counts && !folded && counts[n];
+    if (folded && counts)
+    {
+      // (the reader's own test, partials_fused.hip, step(): all 2 x span2 products of the site below the threshold; the
+      // site's lanes are joined as k_deferred_materialise joins them, lane 0 of the site stores the count)
+      int small = (a.x * b.x < PLLHIP_SCALE_THRESHOLD) && (a.y * b.y < PLLHIP_SCALE_THRESHOLD) ? 1 : 0;
+      for (unsigned int m = 1; m < span2; m <<= 1) small &= __shfl_xor(small, (int)m, 64);
+      scale = small != 0;
+      if (g == 0) counts[n] = scale ? 1u : 0u;
+    }
+    store_product<NT>(a, b, scale, clv + t);
   }
 }
 
@@ -199,6 +214,7 @@ int pllhip_quad_product_slot(pllhip_ctx * c, unsigned int clv, std::vector<unsig
 
 static int quad_products_materialise(pllhip_ctx * c, const std::vector<unsigned int> & todo)
 {
+  size_t nfolded = 0;
   for (size_t first = 0; first < todo.size(); first += PLLHIP_QUAD_PRODUCT_BATCH)
   {
     const unsigned int m = (unsigned int)std::min<size_t>(PLLHIP_QUAD_PRODUCT_BATCH, todo.size() - first);
@@ -221,12 +237,15 @@ static int quad_products_materialise(pllhip_ctx * c, const std::vector<unsigned 
       jobs.qb[k] = reinterpret_cast<const pll_v2d *>(pllhip_quad_product_table(c, d.quad.slot, 1));
       jobs.clv[k] = reinterpret_cast<pll_v2d *>(c->clv[i]);
       jobs.counts[k] = pllhip_scaler_ptr(c, d.scaler);
+      jobs.folded[k] = d.kind == UNSTORED_QUAD_FOLDED ? 1 : 0;
+      nfolded += jobs.folded[k];
     }
     const int rc = launch_jobs(c, k_quad_product_materialise<false>, k_quad_product_materialise<true>, jobs, m, c->tip_stride);
     if (rc) return rc;
     ++c->unstored_stats[UNSTORED_QUAD][2];
   }
   c->unstored_stats[UNSTORED_QUAD][3] += todo.size();
+  c->unstored_stats[UNSTORED_QUAD_FOLDED][3] += nfolded;
   return 0;
 }
 
@@ -261,7 +280,7 @@ static void deferred_clear(pllhip_ctx * c, unsigned int idx)
   if (!d.live()) return;
   if (d.scaler >= 0 && (size_t)d.scaler < c->deferred_sc_owner.size() && c->deferred_sc_owner[d.scaler] == (int)idx)
     c->deferred_sc_owner[d.scaler] = -1;
-  if (d.kind == UNSTORED_QUAD && d.quad.slot < c->quad_product_owner.size() && c->quad_product_owner[d.quad.slot] == (int)idx)
+  if (d.is_quad() && d.quad.slot < c->quad_product_owner.size() && c->quad_product_owner[d.quad.slot] == (int)idx)
     c->quad_product_owner[d.quad.slot] = -1;
   --c->n_live[d.kind];
   --c->n_deferred;
@@ -277,7 +296,7 @@ void pllhip_deferred_begin(pllhip_ctx * c, const pllhip_ctx::deferred_clv & r)
   deferred_clear(c, r.clv);
   c->deferred[r.clv] = r;
   if (r.scaler >= 0) c->deferred_sc_owner[r.scaler] = (int)r.clv;
-  if (r.kind == UNSTORED_QUAD) c->quad_product_owner[r.quad.slot] = (int)r.clv;
+  if (r.is_quad()) c->quad_product_owner[r.quad.slot] = (int)r.clv;
   ++c->n_live[r.kind];
   ++c->n_deferred;
 }
@@ -312,10 +331,10 @@ int pllhip_deferred_materialise(pllhip_ctx * c, const unsigned int * idx, int n)
   // (quad products: a launch of their own kernel, counted on their own -- the batches below are what they were.  They
   // are served first and are cleared once their launch is enqueued: should a batch below then fail, the call returns
   // its error with the quad products already stored -- their bytes are in HBM, nothing is lost)
-  if (c->n_live[UNSTORED_QUAD])
+  if (c->n_live[UNSTORED_QUAD] + c->n_live[UNSTORED_QUAD_FOLDED])
   {
     std::vector<unsigned int> quads, rest;
-    for (unsigned int i : todo) (c->deferred[i].kind == UNSTORED_QUAD ? quads : rest).push_back(i);
+    for (unsigned int i : todo) (c->deferred[i].is_quad() ? quads : rest).push_back(i);
     if (!quads.empty())
     {
       const int rc = quad_products_materialise(c, quads);
@@ -412,8 +431,8 @@ extern "C" int pllhip_set_unstored_pairs(pllhip_ctx_t * c, int on)
 
 int pllhip_quad_products_flush(pllhip_ctx * c)
 {
-  if (!c->n_live[UNSTORED_QUAD]) return 0;
-  const std::vector<unsigned int> quads = live_clvs(c, [](const pllhip_ctx::deferred_clv & d) { return d.kind == UNSTORED_QUAD; });
+  if (!(c->n_live[UNSTORED_QUAD] + c->n_live[UNSTORED_QUAD_FOLDED])) return 0;
+  const std::vector<unsigned int> quads = live_clvs(c, [](const pllhip_ctx::deferred_clv & d) { return d.is_quad(); });
   return pllhip_deferred_materialise(c, quads.data(), (int)quads.size());
 }
 
@@ -446,6 +465,19 @@ extern "C" int pllhip_set_pair_fold(pllhip_ctx_t * c, int on)
   return 0;
 }
 
+// Folding quad products into their readers on or off (A/B, tests); off stores no CLV -- a folded parent stays what it
+// is, an unstored quad product whose counts the materialising launch writes -- but ends the kept plan.  Nothing is
+// folded while pllhip_set_unstored_quad_products, _unstored_pairs, _deferral or pllhip_set_quad_rows is off.
+extern "C" int pllhip_set_quad_fold(pllhip_ctx_t * c, int on)
+{
+  pllhip_edge_terms_drop(c);
+  PLLHIP_ALL_SHARDS(c, pllhip_set_quad_fold(s, on));
+  if (c->quad_fold == (on != 0)) return 0;
+  c->quad_fold = on != 0;
+  ++c->defer_epoch;
+  return 0;
+}
+
 // The four statistics of include/pllhip.h: {live now, unstored_stats[kind][1 .. 3]}, added over a group's shards.
 // `with`: a second kind that counts as live with the first (UNSTORED_NONE: none -- nothing is ever live as that)
 static int kind_stats(const pllhip_ctx * c, int kind, int with, unsigned long long * out4)
@@ -465,4 +497,7 @@ extern "C" int pllhip_deferred_stats(pllhip_ctx_t * c, unsigned long long * out4
 extern "C" int pllhip_unstored_stats(pllhip_ctx_t * c, unsigned long long * out4) { return kind_stats(c, UNSTORED_PAIR, UNSTORED_FOLDED, out4); }
 // the folded ones; [2]: lists planned a second time
 extern "C" int pllhip_pair_fold_stats(pllhip_ctx_t * c, unsigned long long * out4) { return kind_stats(c, UNSTORED_FOLDED, UNSTORED_NONE, out4); }
-extern "C" int pllhip_quad_product_stats(pllhip_ctx_t * c, unsigned long long * out4) { return kind_stats(c, UNSTORED_QUAD, UNSTORED_NONE, out4); }
+// quad products, the folded ones included
+extern "C" int pllhip_quad_product_stats(pllhip_ctx_t * c, unsigned long long * out4) { return kind_stats(c, UNSTORED_QUAD, UNSTORED_QUAD_FOLDED, out4); }
+// the folded ones; [2]: lists planned once more for them
+extern "C" int pllhip_quad_fold_stats(pllhip_ctx_t * c, unsigned long long * out4) { return kind_stats(c, UNSTORED_QUAD_FOLDED, UNSTORED_NONE, out4); }

@@ -655,7 +655,7 @@ unsigned int pllhip_fused_quad_products(const FusedGeom & geom, const pllhip_op_
 
 // Which unstored pair products are folded into their reader (partials_fused.hpp).
 unsigned int pllhip_fused_fold(const pllhip_op_t * ops, const int * kinds, unsigned int count,
-                               const std::vector<std::vector<FusedOp>> & plans, std::vector<unsigned char> & fold)
+                               const std::vector<std::vector<FusedOp>> & plans, std::vector<unsigned char> & fold, bool quads)
 {
   fold.assign(count, 0);
   // how often each CLV is read in the list, and by whom last: one pass
@@ -675,6 +675,8 @@ unsigned int pllhip_fused_fold(const pllhip_op_t * ops, const int * kinds, unsig
     for (const FusedOp & f : plan)
     {
       if (!f.unstored || f.kind != 3 || f.list_pos < 0 || (unsigned int)f.list_pos >= count) continue;
+      // (a quad product has a product on both sides; a pair product on neither)
+      if (quads != (f.prod[0] && f.prod[1])) continue;
       const unsigned int k = (unsigned int)f.list_pos, p = ops[k].parent_clv;
       // (pllhip_fused_unstored: written once, read only behind op k)
       if (reads[p] != 1 || reader[p] <= (int)k || kinds[reader[p]] != 0) continue;
@@ -692,8 +694,9 @@ unsigned int pllhip_fused_fold(const pllhip_op_t * ops, const int * kinds, unsig
 
 void pllhip_fused_fold_list(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
                             const FusedExtra * extras, const unsigned int * rows4, unsigned int count,
-                            const std::vector<unsigned char> & fold, FusedFoldList & out)
+                            const std::vector<unsigned char> & fold, FusedFoldList & out, bool quads)
 {
+  const unsigned int nrows = quads ? 8u : 4u; // rows an op of the list comes with
   out.where.clear();
   out.ops.clear();
   out.args.clear();
@@ -718,24 +721,26 @@ void pllhip_fused_fold_list(const FusedGeom & geom, const pllhip_op_t * ops, con
     int kind = kinds[i];
     FusedExtra x;
     memset(&x, 0, sizeof(x));
-    if (extras)
+    if (extras && quads) x = extras[i]; // (a folded walk's op keeps its products)
+    else if (extras)
     {
       x.g[0] = extras[i].g[0];
       x.g[1] = extras[i].g[1];
     }
     unsigned int rows[8] = {0, 0, 0, 0, 0, 0, 0, 0}, from[2] = {0, 0};
-    for (int t = 0; rows4 && t < 4; ++t) rows[t] = rows4[4 * (size_t)i + t];
+    for (unsigned int t = 0; rows4 && t < nrows; ++t) rows[t] = rows4[nrows * (size_t)i + t];
     const int f1 = kind == 0 ? folded_by[op.child1_clv] : -1, f2 = kind == 0 ? folded_by[op.child2_clv] : -1;
     // side `to` of the reader becomes the product op f forms; sc: the scale buffer the reader passes with it
     auto product = [&](int to, int f, int sc) {
-      if (extras)
+      if (extras && !quads)
       {
         x.g[to] = extras[f].g[0];
         x.g2[to] = extras[f].g[1];
       }
-      x.prod[to] = 1 | (ops[f].parent_scaler >= 0 ? 2 : 0) | (sc >= 0 ? 4 : 0);
+      x.prod[to] = 1 | (ops[f].parent_scaler >= 0 ? 2 : 0) | (sc >= 0 ? 4 : 0) | (quads ? 8 : 0);
       from[to] = (unsigned int)f + 1;
-      for (int t = 0; rows4 && t < 4; ++t) rows[4 * to + t] = rows4[4 * (size_t)f + t];
+      // (a quad product's factors name quad rows, not tip rows)
+      for (int t = 0; rows4 && !quads && t < 4; ++t) rows[4 * to + t] = rows4[4 * (size_t)f + t];
     };
     if (f1 >= 0 && f2 >= 0)
     {
@@ -889,6 +894,77 @@ int pllhip_fused_plan_walk(const FusedGeom & geom, const pllhip_op_t * ops, cons
   out.replanned = true;
   for (unsigned int i = 0; i < count; ++i) out.nfolded += out.fold[i];
   out.nunstored = pllhip_fused_unstored(geom2, out.fl.ops.data(), n2, out.plan.plans, e, pinned);
+  return 0;
+}
+
+// The quad fold: fold, the list without the folded ops, planned once more (partials_fused.hpp).
+int pllhip_fused_quad_fold_walk(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
+                                const FusedExtra * extras, const unsigned int * rows8, unsigned int count,
+                                const std::vector<std::vector<FusedOp>> & plans, unsigned int max_segments, unsigned int nslots,
+                                const FusedEdge * edge, const FusedDeferral & dd, FusedQuadFold & out)
+{
+  out.nfolded = pllhip_fused_fold(ops, kinds, count, plans, out.fold, true);
+  if (!out.nfolded) return 1;
+  pllhip_fused_fold_list(geom, ops, args, kinds, extras, rows8, count, out.fold, out.fl, true);
+  const unsigned int n2 = (unsigned int)out.fl.ops.size();
+  FusedGeom geom2 = geom;
+  geom2.as_tip = out.fl.as_tip.data();
+  memset(&out.edge, 0, sizeof(out.edge));
+  if (edge) out.edge = *edge;
+  const int rc = pllhip_fused_plan_list(geom2, out.fl.ops.data(), out.fl.args.data(), out.fl.kinds.data(), out.fl.extras.data(), n2,
+                                        max_segments, &nslots, 1, edge ? &out.edge : nullptr, dd, out.plan);
+  if (rc) return rc < 0 ? rc : 1;
+  // (the edge pseudo-op stays where the plan before had it)
+  if (edge && !out.plan.folded) return 1;
+  // what every op was given in the plan before
+  std::vector<const FusedOp *> before(count, nullptr);
+  for (const auto & plan : plans)
+    for (const FusedOp & f : plan)
+      if (f.list_pos >= 0 && (unsigned int)f.list_pos < count) before[f.list_pos] = &f;
+  std::vector<const double *> reloaded;
+  for (const auto & plan : out.plan.plans)
+    for (const FusedOp & f : plan)
+    {
+      if ((f.dma_flags & 1) && f.left_hbm) reloaded.push_back(f.left_hbm);
+      if ((f.dma_flags & 2) && f.right_hbm) reloaded.push_back(f.right_hbm);
+    }
+  if (out.plan.folded)
+  {
+    if ((out.edge.op.dma_flags & 1) && out.edge.op.left_hbm) reloaded.push_back(out.edge.op.left_hbm);
+    if ((out.edge.op.dma_flags & 2) && out.edge.op.right_hbm) reloaded.push_back(out.edge.op.right_hbm);
+  }
+  for (auto & plan : out.plan.plans)
+    for (FusedOp & f : plan)
+    {
+      const FusedOp * const b = f.list_pos >= 0 && (unsigned int)f.list_pos < n2 ? before[out.fl.where[f.list_pos]] : nullptr;
+      if (!b) return 1;
+      f.unstored = b->unstored;
+      // (pllhip_fused_unstored's conditions on the finished plan: held by the plan before, asked of this one again)
+      if (f.unstored && (f.pslot < 0 || std::find(reloaded.begin(), reloaded.end(), (const double *)f.parent) != reloaded.end())) return 1;
+      for (int s = 0; s < 2; ++s)
+      {
+        f.keep[s] = b->keep[s];
+        const unsigned int from = out.fl.prod_op[2 * (size_t)f.list_pos + s];
+        if (!(f.prod[s] & 8))
+        {
+          f.pkeep[s][0] = b->pkeep[s][0];
+          f.pkeep[s][1] = b->pkeep[s][1];
+          continue;
+        }
+        // the op folded into this side: its two sides, folded products both, are the two quads
+        const FusedOp * const q = from ? before[from - 1] : nullptr;
+        if (!q || !q->unstored || !q->prod[0] || !q->prod[1]) return 1;
+        for (int t = 0; t < 2; ++t)
+        {
+          f.q[s][t].a = q->g[t];
+          f.q[s][t].b = q->g2[t];
+          f.q[s][t].mat = t == 0 ? q->lmat : q->rmat;
+          f.q[s][t].pkeep[0] = q->pkeep[t][0];
+          f.q[s][t].pkeep[1] = q->pkeep[t][1];
+          f.qkeep[s][t] = q->keep[t];
+        }
+      }
+    }
   return 0;
 }
 
@@ -1132,6 +1208,14 @@ struct DryFinal
   std::vector<unsigned char> as_tip;
   bool has_edge = false;
   FusedEdge edge;
+  // (pllhip_fused_plan_dry_quad_fold) what the quad fold plans that list with once more
+  std::vector<PartialsArgs> args;
+  std::vector<int> kinds;
+  std::vector<unsigned int> rows8;
+  std::vector<FusedExtra> extras;
+  FusedDeferral dd;
+  unsigned int nslots = 0;
+  bool edge_folded = false;
 };
 
 // The planner with deferred cherries, without a device (tests/test_host_deferred_plan.py).  old_deferred / old_scaler /
@@ -1302,6 +1386,13 @@ static int plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsign
     final_out->as_tip = w.replanned ? w.fl.as_tip : d.as_tip;
     final_out->has_edge = edge4 != nullptr;
     final_out->edge = w.edge;
+    final_out->args = w.replanned ? w.fl.args : args;
+    final_out->kinds = w.replanned ? w.fl.kinds : kinds;
+    if (w.replanned) final_out->rows8 = w.fl.rows8;
+    if (w.replanned) final_out->extras = w.fl.extras; // (no operands without a device; the products of each op)
+    final_out->dd = d;
+    final_out->nslots = w.plan.nslots;
+    final_out->edge_folded = w.plan.folded;
   }
   if (gathers_out)
   {
@@ -1378,7 +1469,8 @@ static int plan_dry_quads(unsigned int tips, unsigned int clv_buffers, unsigned 
                           unsigned int sites, int quads_on, unsigned int min_sites_per_class,
                           const unsigned int * classes, const double * bounds, unsigned int * nkept,
                           unsigned int * order_out, unsigned char * folded_out, int * ops_out, int * quads_out,
-                          unsigned int * counts_out, unsigned char * products_out, unsigned int * bytes_out)
+                          unsigned int * counts_out, unsigned char * products_out, unsigned int * bytes_out,
+                          int fold_on = 0, unsigned char * qfolded_out = nullptr, unsigned int * walked_out = nullptr)
 {
   if (!(rate_cats == 1 || rate_cats == 2 || rate_cats == 4) || !classes || !nkept || !order_out || !folded_out || !ops_out || !quads_out ||
       !counts_out)
@@ -1467,7 +1559,27 @@ static int plan_dry_quads(unsigned int tips, unsigned int clv_buffers, unsigned 
   for (unsigned int i = 0; i < count; ++i) products_out[i] = 0;
   FusedGeom geom = {(size_t)tips + clv_buffers, scale_buffers, tips, pattern_tip != 0, fin.as_tip.data()};
   const std::vector<std::vector<unsigned char>> marks(1, taken);
-  pllhip_fused_quad_products(geom, fin.ops.data(), (unsigned int)fin.ops.size(), fin.plans, marks, fin.has_edge ? &fin.edge : nullptr, pinned);
+  const bool any = pllhip_fused_quad_products(geom, fin.ops.data(), (unsigned int)fin.ops.size(), fin.plans, marks,
+                                              fin.has_edge ? &fin.edge : nullptr, pinned) != 0;
+  // (pllhip_fused_plan_dry_quad_fold) ... and the quad fold behind it: the plan it makes stands in for the walk's
+  for (unsigned int i = 0; qfolded_out && i < count; ++i) qfolded_out[i] = 0;
+  FusedQuadFold qf;
+  if (any && fold_on && !fin.rows8.empty() &&
+      pllhip_fused_quad_fold_walk(geom, fin.ops.data(), fin.args.data(), fin.kinds.data(), fin.extras.data(), fin.rows8.data(),
+                                  (unsigned int)fin.ops.size(), fin.plans, 1, fin.nslots, fin.edge_folded ? &fin.edge : nullptr, fin.dd, qf) == 0)
+  {
+    for (unsigned int i = 0; i < fin.ops.size(); ++i)
+      if (qf.fold[i])
+      {
+        products_out[fin.to_list[i]] = 1;
+        if (qfolded_out) qfolded_out[fin.to_list[i]] = 1;
+      }
+    std::vector<unsigned int> to_list(qf.fl.ops.size());
+    for (unsigned int i = 0; i < to_list.size(); ++i) to_list[i] = fin.to_list[qf.fl.where[i]];
+    fin.to_list.swap(to_list);
+    fin.plans = qf.plan.plans;
+  }
+  if (walked_out) *walked_out = (unsigned int)fin.plans[0].size();
   // ... and the plan's bytes per site, as DESIGN.md 2.0 counts them: one write per entry of a stored CLV and per count,
   // one read per character of the tips under the list
   unsigned int bytes = 0;
@@ -1522,6 +1634,30 @@ extern "C" int pllhip_fused_plan_dry_quad_products(unsigned int tips, unsigned i
   return plan_dry_quads(tips, clv_buffers, scale_buffers, pattern_tip, rate_cats, rate_scalers, ops, count, nslots, pinned, edge4, sites,
                         quads_on, min_sites_per_class, classes, bounds, nkept, order_out, folded_out, ops_out, quads_out, counts_out,
                         products_out, bytes_out);
+}
+
+// The quad fold without a device (tests/test_host_quad_fold.py): pllhip_fused_plan_dry_quad_products, then -- fold_on --
+// the step the launch takes behind it, pllhip_fused_quad_fold_walk.  qfolded_out[i] = 1: op i of the caller's list is a
+// quad product its reader forms; *walked_out: the ops the kernel walks; products_out counts the folded parents with the
+// walked ones, *bytes_out is of the plan that is launched.
+extern "C" int pllhip_fused_plan_dry_quad_fold(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
+                                               int pattern_tip, unsigned int rate_cats, int rate_scalers, const pllhip_op_t * ops,
+                                               unsigned int count, unsigned int nslots, const unsigned char * pinned,
+                                               const int * edge4, unsigned int sites, int quads_on,
+                                               unsigned int min_sites_per_class, const unsigned int * classes,
+                                               const double * bounds, int fold_on, unsigned int * nkept, unsigned int * order_out,
+                                               unsigned char * folded_out, int * ops_out, int * quads_out,
+                                               unsigned int * counts_out, unsigned char * products_out, unsigned int * bytes_out,
+                                               unsigned char * qfolded_out, unsigned int * walked_out)
+{
+  if (!products_out || !qfolded_out || !walked_out)
+  {
+    pllhip_set_error("pllhip_fused_plan_dry_quad_fold: products_out, qfolded_out and walked_out");
+    return -1;
+  }
+  return plan_dry_quads(tips, clv_buffers, scale_buffers, pattern_tip, rate_cats, rate_scalers, ops, count, nslots, pinned, edge4, sites,
+                        quads_on, min_sites_per_class, classes, bounds, nkept, order_out, folded_out, ops_out, quads_out, counts_out,
+                        products_out, bytes_out, fold_on, qfolded_out, walked_out);
 }
 
 extern "C" int pllhip_fused_plan_dry_deferred(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,

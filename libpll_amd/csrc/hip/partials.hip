@@ -745,6 +745,7 @@ struct DnaListKept
   bool edge_wanted = false, edge_ok = false; // the hinted evaluation: asked for by the instance; resolved into `edge`
   FusedEdge edge;
   FusedWalk walk;                          // the plan, what it leaves unstored and folds
+  unsigned int max_segs = 1;               // segments the list was planned with at most (the quad fold plans with as many)
 };
 // Which cherries the list defers (k.dd), with what it cannot read from a table materialised first -- every deferred
 // CLV where nothing may be deferred.  *any = false: the list runs as it is, ordinary buffers, ordinary ops.
@@ -1007,6 +1008,7 @@ static int plan_list(pllhip_ctx * c, size_t fused_tile_sites, DnaListKept & k)
   // PLLHIP_FUSED_SEGMENTS=0 / n: never / up to n whatever the size.
   unsigned int max_segs = (size_t)c->sh.sites / fused_tile_sites < (size_t)c->num_cus * 12 * 8 ? PLLHIP_FUSED_MAX_SEGS : 1u;
   if (const char * e = pllhip_env("PLLHIP_FUSED_SEGMENTS")) max_segs = (unsigned int)std::max(1, atoi(e));
+  k.max_segs = max_segs;
   // Pair products (deferred.hip): gathered-gathered parents may go unstored where the instance defers at all (a kind-3
   // op exists only then) and the pool has the two tables each needs; folded into their reader: pllhip_set_pair_fold.
   const bool may_unstore = extras && c->unstored_pairs && c->cherry_deferral && pllhip_deferred_table(c, 0, 1);
@@ -1076,11 +1078,20 @@ static int launch_list(pllhip_ctx * c, DnaListKept & k)
       qp->count = (unsigned int)w.fl.ops.size();
       qp->edge = k.edge_ok ? &w.edge : nullptr;
       qp->pinned = c->clv_pinned.data();
+      // (the quad fold, pllhip_set_quad_fold: the launch plans the list once more without the parents it folds)
+      qp->fold = c->quad_fold;
+      qp->args = w.fl.args.data();
+      qp->kinds = w.fl.kinds.data();
+      qp->extras = w.fl.extras.data();
+      qp->rows8 = w.fl.rows8.data();
+      qp->max_segments = k.max_segs;
+      qp->dd = &k.dd;
     }
     k.quad_products.left.clear();
     rc = pllhip_launch_fused(c, w.plan.plans, w.plan.nslots, keep_jobs, w.plan.folded ? &w.edge : nullptr, qp);
   }
   if (rc != 0) k.quad_products.left.clear();
+  if (rc != 0) k.quad_products.nfolded = 0;
   if (rc != 0) c->fused_last_nfolded = 0;
   return rc;
 }
@@ -1088,6 +1099,7 @@ static int launch_list(pllhip_ctx * c, DnaListKept & k)
 // The list has run: the deferrals it ends and begins, the pair products it leaves unstored, the kept plan.
 static void commit_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsigned int full_count, const DnaListKept & k)
 {
+  // (a quad fold's plan keeps the edge pseudo-op where the walk's plan had it)
   if (k.walk.plan.folded)
   {
     c->edge_terms_valid = true;
@@ -1103,8 +1115,10 @@ static void commit_list(pllhip_ctx * c, const pllhip_op_t * full_ops, unsigned i
   c->fused_last_unstored_ops[UNSTORED_PAIR] = (unsigned int)k.new_unstored.size();
   c->fused_last_unstored_ops[UNSTORED_FOLDED] = k.walk.nfolded;
   c->fused_last_unstored_ops[UNSTORED_QUAD] = (unsigned int)k.quad_products.left.size();
+  c->fused_last_unstored_ops[UNSTORED_QUAD_FOLDED] = k.quad_products.nfolded;
   for (int kind = 0; kind < UNSTORED_KINDS; ++kind) c->unstored_stats[kind][1] += c->fused_last_unstored_ops[kind];
   if (k.walk.nfolded) ++c->unstored_stats[UNSTORED_FOLDED][2];
+  if (k.quad_products.nfolded) ++c->unstored_stats[UNSTORED_QUAD_FOLDED][2];
   c->fused_last_defer_epoch = c->defer_epoch;
   c->fused_last_ops.assign(full_ops, full_ops + full_count);
 }

@@ -40,6 +40,10 @@
 //             that read it take their factor from a table -- gathered-inner (kind 1) and gathered-gathered (kind 3)
 //   pairs     the parent of a gathered-gathered op that nothing reads from HBM is walked but not stored: its tile stores
 //             go to the wave's sink, and deferred.hip stores the CLV on demand (PLLHIP_FUSED_UNSTORED, see step())
+//   quads     a folded pair product over two cherries is read from a table of one entry per class of its four tips'
+//             characters (quad_rows.hip), by a WIDE gather; the parent of an op over two such quads that one inner-inner
+//             op reads is not walked either: that reader gathers the two quads itself -- up to four wide gathers per op
+//             (fused_plan.hip: pllhip_fused_quad_fold_walk)
 //   limit     a wave's own serial path, not HBM: twelve waves per CU is all the slots allow, so
 //             the order within an op overlaps the wave's latencies with its own work (see step()).
 //             Measured: the vector unit was busy 93 % of the time with three waves per SIMD, but
@@ -536,12 +540,13 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       const unsigned int mask = (ch & PLLHIP_FUSED_CH_NIBBLE) ? 0x0f0f0f0fu : 0xffffffffu;
       const unsigned int shift = (ch / (PLLHIP_FUSED_CH_SHIFT4 / 4u)) & 4u;
       const unsigned long long tab = (unsigned long long)(uintptr_t)bases.pairtab + table_off; // (uniform)
-      // The WIDE form (quad rows, quad_rows.hip; only an op's first two gathers: a reader of quads has no more): the row
-      // holds a 16-bit class per site -- two lane positions per granule of a byte row, pllhip_quad_word_lane --, the table
-      // one entry per class and may be several tables long: a second gather finds its own behind the first's, displaced
-      // by the tables the word's top byte counts.  The same words-then-pick on the scalar side; the two forms differ in
-      // the OFFSET only, an ordinary lane value -- the load is ONE statement for both, so that the gathered registers
-      // have one writer per sub-step and nothing to merge behind it (see gather() below, point 1).
+      // The WIDE form (quad rows, quad_rows.hip; any of an op's gathers: a reader of two folded quad products has four):
+      // the row holds a 16-bit class per site -- two lane positions per granule of a byte row, pllhip_quad_word_lane --,
+      // the table one entry per class and may be several tables long: a gather behind the first finds its own behind all
+      // of those before it, displaced by the tables the word's top byte counts.  The same words-then-pick on the scalar
+      // side; the two forms differ in the OFFSET only, an ordinary lane value -- the load is ONE statement for both, so
+      // that the gathered registers have one writer per sub-step and nothing to merge behind it (see gather() below,
+      // point 1).
       bool wide = false;
       unsigned long long base = tab;
       if constexpr (SECOND && decltype(may_be_wide)::value)
@@ -577,15 +582,16 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
       }
     };
     // (the tables of one op follow each other in the table buffer: gather k reads k tables behind the first; a third
-    // and a fourth factor -- a right-hand operand that is a folded product, see step() -- always come together)
+    // and a fourth factor -- a right-hand operand that is a folded product, see step() -- always come together; where the
+    // factors are quads, tables of several units, each gather's word counts the units the gathers before it took beyond one)
     auto gather = [&](pll_v2d (&pt)[J], pll_v2d (&pt2)[J], pll_v2d (&pt3)[J], pll_v2d (&pt4)[J], const Rec & r) {
       const unsigned int ch = rec_chars(r), ch2 = rec_chars2(r);
       if (ch & PLLHIP_FUSED_CH_LTIP) gather_factor(pt, ch, rec_gather(r), std::true_type(), false);
       if (SECOND && (ch2 & PLLHIP_FUSED_CH_LTIP)) gather_factor(pt2, ch2, rec_gather(r) + TB, std::true_type(), true);
       if (SECOND && (rec_chars3(r) & PLLHIP_FUSED_CH_LTIP))
       {
-        gather_factor(pt3, rec_chars3(r), rec_gather(r) + 2u * TB, std::false_type(), false);
-        gather_factor(pt4, rec_chars4(r), rec_gather(r) + 3u * TB, std::false_type(), false);
+        gather_factor(pt3, rec_chars3(r), rec_gather(r) + 2u * TB, std::true_type(), true);
+        gather_factor(pt4, rec_chars4(r), rec_gather(r) + 3u * TB, std::true_type(), true);
       }
       // the list moves on to rows this batch does not hold (rare: every 1024 / TS tip operands): the lanes'
       // addresses of the next batch, then its rows.  Assembly, like reload(): the compiler counts no load
@@ -1160,7 +1166,8 @@ struct FusedQuadSide
   QuadRowRef ref;
   unsigned int units = 0;
 };
-typedef std::vector<FusedQuadSide> FusedQuadMarks; // two per position of a plan: its sides
+typedef std::vector<FusedQuadSide> FusedQuadMarks; // four per position of a plan: its gathers (a side read as a quad is
+                                                   // gather `side`; quad t of a folded quad product on side s gather 2 s + t)
 struct FusedGatherSets
 {
   FusedOperand g[4];
@@ -1168,9 +1175,9 @@ struct FusedGatherSets
   // g[k] is a quad (type FUSED_G_QUAD; `mat` the reader's matrix on that side): its mark, and the product's two
   // factors, whose tables are still written into the pool -- jobs with no reader in this launch (deferred.hip
   // materialises from them)
-  const FusedQuadSide * quad[2];
-  FusedOperand qa[2], qb[2];
-  double * qkeep[2][2];
+  const FusedQuadSide * quad[4];
+  FusedOperand qa[4], qb[4];
+  double * qkeep[4][2];
 };
 enum { FUSED_G_QUAD = 5 };
 // One segment's gathers and where a wave finds their tip characters: rows in the order the segment uses them, in
@@ -1218,8 +1225,34 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
     {
       // (only what the planner folds: an inner-inner reader, presented as gathered-inner or gathered-gathered)
       if (!f.prod[0] || (f.kind != 1 && f.kind != 3) || (f.kind == 3) != (f.prod[1] != 0)) return 1;
+      // A reader of folded QUAD products (pllhip_fused_quad_fold_walk): every product side is two quads, gathers 2 s and
+      // 2 s + 1 -- each with the table job a quad's reader gives it, the folded op's matrix on that side in it, and the
+      // kept copy of the table where deferred.hip materialises the folded parent from
+      if ((f.prod[0] | f.prod[1]) & 8)
+      {
+        if (!quads || f.unstored || ((f.prod[0] & 8) == 0) || (f.prod[1] && !(f.prod[1] & 8))) return 1;
+        for (int s = 0; s < (f.prod[1] ? 2 : 1); ++s)
+          for (int t = 0; t < 2; ++t)
+          {
+            const int k = 2 * s + t;
+            const FusedOp::Quad & q = f.q[s][t];
+            if (!(*quads)[4 * (size_t)pos + k].taken || q.a.type == FUSED_G_NONE || q.b.type == FUSED_G_NONE || !q.mat ||
+                !q.pkeep[0] || !q.pkeep[1] || !f.qkeep[s][t])
+              return 1;
+            x.g[k].type = FUSED_G_QUAD;
+            x.g[k].mat = q.mat;
+            x.quad[k] = &(*quads)[4 * (size_t)pos + k];
+            x.g[k].row = x.quad[k]->ref.row;
+            x.qa[k] = q.a;
+            x.qb[k] = q.b;
+            x.qkeep[k][0] = q.pkeep[0];
+            x.qkeep[k][1] = q.pkeep[1];
+            x.copy[k] = f.qkeep[s][t];
+          }
+        continue;
+      }
       // (quads: every product side of the op, or none -- a reader of a quad and a plain product is not built)
-      const bool quad = quads && (*quads)[2 * (size_t)pos].taken && (!f.prod[1] || (*quads)[2 * (size_t)pos + 1].taken);
+      const bool quad = quads && (*quads)[4 * (size_t)pos].taken && (!f.prod[1] || (*quads)[4 * (size_t)pos + 1].taken);
       // (unstored: a quad product only -- both sides quads, the value two table rows' product: pllhip_fused_quad_products)
       if (f.unstored && !(quad && f.prod[1])) return 1;
       for (int s = 0; s < (f.prod[1] ? 2 : 1); ++s)
@@ -1230,7 +1263,7 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
           memset(&x.g[s], 0, sizeof(x.g[s]));
           x.g[s].type = FUSED_G_QUAD;
           x.g[s].mat = s == 0 ? f.lmat : f.rmat;
-          x.quad[s] = &(*quads)[2 * (size_t)pos + s];
+          x.quad[s] = &(*quads)[4 * (size_t)pos + s];
           x.g[s].row = x.quad[s]->ref.row;
           x.qa[s] = f.g[s];
           x.qb[s] = f.g2[s];
@@ -1272,19 +1305,19 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
   {
     out.batch_of[pos] += batch0;
     if (out.gx[pos].g[0].type != FUSED_G_NONE) out.table_of[pos] = (unsigned int)(*ntables * fused_table_doubles(R) * sizeof(double));
-    unsigned int first_units = 1;
+    unsigned int extra_units = 0;
     for (int k = 0; k < 4; ++k)
     {
       const FusedOperand & g = out.gx[pos].g[k];
       if (g.type == FUSED_G_QUAD)
       {
-        // (the wide form: one row position, the planes lpr lanes apart; a second gather's table lies behind ALL of the
-        // first's tables -- the word's top byte says how many more than one)
+        // (the wide form: one row position, the planes lpr lanes apart; a later gather's table lies behind ALL the tables
+        // of the gathers before it -- the word's top byte says how many more than one each those took)
         const unsigned int units = out.gx[pos].quad[k]->units;
-        if (k == 0) first_units = units;
         *ntables += units;
         unsigned int & ch = out.chars_of[k][pos];
-        ch = (ch & ~(PLLHIP_FUSED_CH_RTIP | 0xff00u)) | PLLHIP_FUSED_CH_WIDE | (k == 1 ? (first_units - 1u) << 24 : 0u);
+        ch = (ch & ~(PLLHIP_FUSED_CH_RTIP | 0xff00u)) | PLLHIP_FUSED_CH_WIDE | (k >= 1 ? extra_units << 24 : 0u);
+        extra_units += units - 1u;
         if (PLLHIP_FUSED_CH_LPOS(ch) + 2 * lpr > 64) return 1;
         continue;
       }
@@ -1293,8 +1326,8 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
       if ((g.row1 || g.row2) && PLLHIP_FUSED_CH_LPOS(out.chars_of[k][pos]) + lpr > 64) return 1;
     }
     // (the tables of a quad's two factors, written for the pool's sake: behind the op's own)
-    for (int s = 0; s < 2; ++s)
-      if (out.gx[pos].quad[s]) *ntables += 2;
+    for (int k = 0; k < 4; ++k)
+      if (out.gx[pos].quad[k]) *ntables += 2;
   }
   return 0;
 }
@@ -1401,7 +1434,8 @@ static void fused_look_ahead(const FusedEncodeIn & in, const std::vector<FusedOp
   r.gather_off = pos + 1 < n ? ga.table_of[pos + 1] : 0u;
   // (a reader of folded products runs as an inner-inner op: both matrices)
   // (... unless its products are quads: a gathered operand needs no matrix)
-  const bool quad = pos + 1 < n && ga.gx[pos + 1].quad[0] != nullptr;
+  // (... and a reader of folded QUAD products forms them itself, an inner-inner op again: both matrices)
+  const bool quad = pos + 1 < n && ga.gx[pos + 1].quad[0] != nullptr && !(f.prod[0] & 8);
   r.flags |= (f.kind == 0 || (f.prod[0] && !quad) ? 2u : (f.kind == 1 || f.kind == PLLHIP_FUSED_KIND_EDGE) ? 1u : 0u) << PLLHIP_FUSED_STAGE_SHIFT;
   if (!f.dma_flags) return;
   r.flags |= PLLHIP_FUSED_RELOAD_NEXT;
@@ -1491,7 +1525,7 @@ static void fused_encode_segment(const FusedEncodeIn & in, const std::vector<Fus
     }
     // (a quad's two factor tables, as the product's gathers would have had them written: into the pool, which
     // deferred.hip materialises the folded parent from -- and into a table of this launch that nothing reads)
-    for (int s = 0; s < 2; ++s)
+    for (int s = 0; s < 4; ++s)
     {
       if (!ga.gx[pos].quad[s]) continue;
       const FusedOperand * const ab[2] = {&ga.gx[pos].qa[s], &ga.gx[pos].qb[s]};
@@ -1516,7 +1550,7 @@ static void fused_encode_segment(const FusedEncodeIn & in, const std::vector<Fus
   fused_look_ahead(in, plan, ga, edge, rs[1], -1, out.srcs);
   for (unsigned int pos = 0; pos < n; ++pos)
   {
-    fused_fill_record(in, plan[pos], rs[pos + 2], ga.gx[pos].quad[0] != nullptr);
+    fused_fill_record(in, plan[pos], rs[pos + 2], ga.gx[pos].quad[0] != nullptr && !(plan[pos].prod[0] & 8));
     fused_look_ahead(in, plan, ga, edge, rs[pos + 2], (long)pos, out.srcs);
   }
   rs[n + 2] = rs[n + 1]; // (loaded by the last op, never used)
@@ -1690,7 +1724,7 @@ static int fused_pick_quads(pllhip_ctx * c, const std::vector<std::vector<FusedO
   const int rc = pllhip_quad_rows_resolve(c, keys, refs);
   if (rc) return rc < 0 ? rc : (rc == 1 ? -1 : rc);
   marks.assign(plans.size(), FusedQuadMarks());
-  for (unsigned int sg = 0; sg < plans.size(); ++sg) marks[sg].assign(2 * plans[sg].size(), FusedQuadSide());
+  for (unsigned int sg = 0; sg < plans.size(); ++sg) marks[sg].assign(4 * plans[sg].size(), FusedQuadSide());
   // a matrix's host bounds (pmatrix.hip): {entries, row sums}, 0 where the host has none
   auto bounds_of = [&](const double * m, double & lo, double & rs) {
     const size_t idx = m && m >= c->pmatrix ? (size_t)(m - c->pmatrix) / c->pmat_elems : ~(size_t)0;
@@ -1735,7 +1769,7 @@ static int fused_pick_quads(pllhip_ctx * c, const std::vector<std::vector<FusedO
     if (reason == FUSED_QUAD_BOUND) ++*by_bound;
     if ((reason == FUSED_QUAD_TAKEN || reason == FUSED_QUAD_MIXED) && cands[i].scales) mats.insert(mats.end(), used[i].begin(), used[i].end());
     if (reason != FUSED_QUAD_TAKEN) ++c->quad_rows.stats[4];
-    FusedQuadSide & q = marks[cands[i].seg][2 * (size_t)cands[i].pos + cands[i].side];
+    FusedQuadSide & q = marks[cands[i].seg][4 * (size_t)cands[i].pos + cands[i].side];
     q.taken = reason == FUSED_QUAD_TAKEN;
     q.ref = refs[key_of[i]];
     q.units = (q.ref.n + 255u) / 256u;
@@ -1753,7 +1787,8 @@ static unsigned int fused_mark_quad_products(pllhip_ctx * c, const std::vector<F
 {
   std::vector<std::vector<unsigned char>> taken(quads.size());
   for (size_t sg = 0; sg < quads.size(); ++sg)
-    for (const FusedQuadSide & q : quads[sg]) taken[sg].push_back(q.taken ? 1 : 0);
+    for (size_t at = 0; at < quads[sg].size(); at += 4)
+      for (int s = 0; s < 2; ++s) taken[sg].push_back(quads[sg][at + s].taken ? 1 : 0);
   qp.left.clear();
   if (!pllhip_fused_quad_products(qp.geom, qp.ops, qp.count, mine, taken, qp.edge, qp.pinned)) return 0;
   std::vector<unsigned char> slots_taken;
@@ -1778,7 +1813,7 @@ static unsigned int fused_mark_quad_products(pllhip_ctx * c, const std::vector<F
       for (int s = 0; s < 2; ++s)
       {
         f.keep[s] = pllhip_quad_product_table(c, (unsigned int)slot, (unsigned int)s);
-        n.quad.row[s] = quads[sg][2 * pos + s].ref.slot;
+        n.quad.row[s] = quads[sg][4 * pos + s].ref.slot;
         const unsigned int t4[4] = {tip_of(f.g[s].row1), tip_of(f.g[s].row2), tip_of(f.g2[s].row1), tip_of(f.g2[s].row2)};
         memcpy(n.quad.tips[s], t4, sizeof(t4));
       }
@@ -1787,11 +1822,52 @@ static unsigned int fused_mark_quad_products(pllhip_ctx * c, const std::vector<F
   return (unsigned int)qp.left.size();
 }
 
+// The quad fold (fused_plan.hip: pllhip_fused_quad_fold_walk) of the plans fused_mark_quad_products has marked: the
+// list without the folded parents planned once more, every quad's mark moved to the gather that now reads it -- a
+// walked reader's side as before, a folded parent's two sides to gathers 2 s, 2 s + 1 of the reader's side s --, and
+// that plan admitted.  Returns true where it is: qp.folded.plan is what the launch encodes, with marks2 and adm.
+static bool fused_fold_quad_products(const pllhip_ctx * c, const std::vector<FusedQuadMarks> & quads, FusedQuadProducts & qp,
+                                     const std::vector<std::vector<FusedOp>> & mine, unsigned int nslots, const FusedEdge * edge,
+                                     std::vector<FusedQuadMarks> & marks2, FusedAdmitted & adm)
+{
+  FusedQuadFold & qf = qp.folded;
+  if (!qp.dd || pllhip_fused_quad_fold_walk(qp.geom, qp.ops, qp.args, qp.kinds, qp.extras, qp.rows8, qp.count, mine, qp.max_segments,
+                                            nslots, edge, *qp.dd, qf) != 0)
+    return false;
+  std::vector<std::pair<size_t, size_t>> at(qp.count, std::make_pair(~(size_t)0, ~(size_t)0)); // op of the list -> its place in `mine`
+  for (size_t sg = 0; sg < mine.size(); ++sg)
+    for (size_t pos = 0; pos < mine[sg].size(); ++pos)
+      if (mine[sg][pos].list_pos >= 0 && (unsigned int)mine[sg][pos].list_pos < qp.count) at[mine[sg][pos].list_pos] = std::make_pair(sg, pos);
+  const std::vector<std::vector<FusedOp>> & plans2 = qf.plan.plans;
+  marks2.assign(plans2.size(), FusedQuadMarks());
+  for (size_t sg = 0; sg < plans2.size(); ++sg)
+  {
+    marks2[sg].assign(4 * plans2[sg].size(), FusedQuadSide());
+    for (size_t pos = 0; pos < plans2[sg].size(); ++pos)
+    {
+      const FusedOp & f = plans2[sg][pos];
+      for (int s = 0; s < 2; ++s)
+      {
+        if (!f.prod[s]) continue;
+        const unsigned int from = (f.prod[s] & 8) ? qf.fl.prod_op[2 * (size_t)f.list_pos + s] - 1u : qf.fl.where[f.list_pos];
+        if (from >= qp.count || at[from].first >= quads.size()) return false;
+        const FusedQuadSide * const before = &quads[at[from].first][4 * at[from].second];
+        if (f.prod[s] & 8)
+          for (int t = 0; t < 2; ++t) marks2[sg][4 * pos + 2 * s + t] = before[t];
+        else marks2[sg][4 * pos + s] = before[s];
+      }
+    }
+  }
+  return fused_admit(c, plans2, nslots, edge ? &qf.edge : nullptr, adm, &marks2) == 0;
+}
+
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans_in, unsigned int nslots,
                         const std::vector<FusedPairJob> * keep_jobs, const FusedEdge * edge, FusedQuadProducts * quad_products)
 {
   const std::vector<std::vector<FusedOp>> * use = &plans_in;
   std::vector<std::vector<FusedOp>> mine;
+  std::vector<FusedQuadMarks> quads2;
+  if (quad_products) quad_products->nfolded = 0;
   if (quad_products) quad_products->left.clear();
   FusedAdmitted adm;
   if (fused_admit(c, plans_in, nslots, edge, adm)) return 1;
@@ -1810,8 +1886,23 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
     if (quad_products)
     {
       mine = plans_in;
-      FusedAdmitted with;
-      if (fused_mark_quad_products(c, quads, *quad_products, mine) && fused_admit(c, mine, nslots, edge, with, &quads) == 0)
+      FusedAdmitted with, with_fold;
+      const bool marked = fused_mark_quad_products(c, quads, *quad_products, mine) != 0;
+      // (the quad fold: the marked parents with one inner-inner reader are not walked; a plan the planner or the encoder
+      // does not take gives way to the one before it, its parents walked and unstored)
+      if (marked && quad_products->fold && fused_fold_quad_products(c, quads, *quad_products, mine, nslots, edge, quads2, with_fold))
+      {
+        const FusedQuadFold & qf = quad_products->folded;
+        for (pllhip_ctx::deferred_clv & r : quad_products->left)
+          for (unsigned int k = 0; k < quad_products->count; ++k)
+            if (qf.fold[k] && quad_products->ops[k].parent_clv == r.clv) r.kind = UNSTORED_QUAD_FOLDED;
+        quad_products->nfolded = qf.nfolded;
+        adm = std::move(with_fold);
+        use = &qf.plan.plans;
+        if (edge) edge = &qf.edge;
+        taken = true;
+      }
+      else if (marked && fused_admit(c, mine, nslots, edge, with, &quads) == 0)
       {
         adm = std::move(with);
         use = &mine;
@@ -1837,6 +1928,7 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   if ((rc = fused_upload(c, enc))) return rc;
   c->fused_last_count = plans[0].size();
   c->fused_last_ndeferred = keep_jobs ? (unsigned int)keep_jobs->size() : 0u;
+  if (quad_products) c->fused_last_nfolded += quad_products->nfolded; // (not walked either: the caller's list is as long as it was)
   c->fused_last_nslots = nslots;
   c->fused_last_edge = edge != nullptr;
   return pllhip_relaunch_fused(c);

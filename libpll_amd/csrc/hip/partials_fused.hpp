@@ -42,8 +42,10 @@ struct FusedOperand
 // A side of an op may also be the PRODUCT of two gathered factors (prod[side] != 0): a gathered-gathered parent with one
 // reader that is not walked at all but formed by that reader (pllhip_fused_fold).  g[side] and g2[side] are then its
 // two factors; prod[side] is a bit set: 1 a product, | 2 the folded op has a scale buffer (its scaling test can fire),
-// | 4 the reader passes its scale buffer on that side (it inherits the product's scale bit); pkeep[side]: where the two
-// factor tables are kept (the pool: deferred.hip).
+// | 4 the reader passes its scale buffer on that side (it inherits the product's scale bit), | 8 the two factors are
+// QUADS -- the folded op is itself a reader of two folded products, both read as quads, whose parent stays unstored
+// (pllhip_fused_quad_fold_walk; the factors are then in FusedOp::q, filled from the plan before); pkeep[side]: where the
+// two factor tables are kept (the pool: deferred.hip).
 struct FusedExtra
 {
   FusedOperand g[2];
@@ -79,8 +81,19 @@ struct FusedOp
   // planner the op is then gathered-inner (kind 1, the product "left") or gathered-gathered (kind 3); the kernel runs
   // it as an inner-inner op whose operand on that side is formed from registers instead of read from a slot.
   FusedOperand g2[2];
-  int prod[2];                     // 0 no product; else bits: 1 a product, 2 its op has a scale buffer, 4 the reader inherits its count
+  int prod[2];                     // 0 no product; else bits: 1 a product, 2 its op has a scale buffer, 4 the reader inherits its count,
+                                   // 8 a folded QUAD product: its two factors are the quads q[s][0], q[s][1]
   double * pkeep[2][2];            // the pool's places of the two factor tables of side s
+  // a folded quad product on side s (prod[s] & 8): quad t of it is what side t of the folded op was in the plan before
+  // -- a folded pair product over two cherries, a and b, read with the folded op's matrix on that side --, the places
+  // of a's and b's factor tables in the pool; qkeep[s][t]: where the quad's table is kept (the pool of quad tables)
+  struct Quad
+  {
+    FusedOperand a, b;
+    const double * mat;
+    double * pkeep[2];
+  } q[2][2];
+  double * qkeep[2][2];
 };
 
 // The plan as the kernel reads it, through the scalar data cache: ONE 64-byte record per op (one
@@ -261,7 +274,8 @@ __host__ __device__ constexpr unsigned int pllhip_fused_row_index(const unsigned
 // entry per class instead of forming it.  ONE definition for the builder, the list kernel's pick and the host tests.
 #define PLLHIP_QUAD_MAX_CLASSES 1024u
 #define PLLHIP_FUSED_CH_WIDE (1u << 21)                /* the gather names a quad row: 16 bits per site, two lane positions per
-                                                          row granule; in chars2, bits 24-31: tables the first gather takes beyond one */
+                                                          row granule; in chars2 .. chars4, bits 24-31: tables the gathers before
+                                                          it take beyond one each */
 __host__ __device__ constexpr unsigned int pllhip_quad_pattern(unsigned char pa, unsigned char pb)
 {
   return ((unsigned int)pa << 8) | pb;
@@ -535,12 +549,18 @@ unsigned int pllhip_fused_quad_products(const FusedGeom & geom, const pllhip_op_
 // Sets fold[k] = 1 per op of the list to fold, returns how many -- 0 also where fewer than two ops would be left to
 // walk (a list kernel wants two).  ONE rule, applied by pllhip_fused_plan_walk alone, which then plans the list once
 // more without the folded ops (pllhip_fused_fold_list).
+// quads: the same rule for the unstored QUAD products of a folded walk (pllhip_fused_quad_products' marks: kind-3 ops
+// with a product on both sides) -- the pair products walked unstored next to them are left as they are.
 unsigned int pllhip_fused_fold(const pllhip_op_t * ops, const int * kinds, unsigned int count,
-                               const std::vector<std::vector<FusedOp>> & plans, std::vector<unsigned char> & fold);
+                               const std::vector<std::vector<FusedOp>> & plans, std::vector<unsigned char> & fold,
+                               bool quads = false);
 // The list without the ops fold[] marks, as the planner is to see it: `where` (kept op -> op of the list), the kept
 // ops, their args / kinds / extras with every reader's folded side turned into a product operand (FusedExtra::prod --
 // to the planner a gathered side: as_tip[parent] is set for every folded parent), and rows (4 per kept op -> 8: tip
 // index + 1 of the rows of its up to four factors).  extras / rows: of the list (rows may be nullptr: dry).
+// quads: the list is a folded walk's (FusedWalk::fl: rows come eight per op, extras hold products) and the folded ops
+// are quad products: a reader's folded side gets bit 8 and names no rows and no factors (FusedOp::q: filled from the
+// plan before, pllhip_fused_quad_fold_walk).
 struct FusedFoldList
 {
   std::vector<unsigned int> where;
@@ -554,7 +574,7 @@ struct FusedFoldList
 };
 void pllhip_fused_fold_list(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
                             const FusedExtra * extras, const unsigned int * rows4, unsigned int count,
-                            const std::vector<unsigned char> & fold, FusedFoldList & out);
+                            const std::vector<unsigned char> & fold, FusedFoldList & out, bool quads = false);
 // slots per wave with 2 (8 waves per CU) or 3 (12 waves) workgroups per CU
 unsigned int pllhip_fused_slots_for(unsigned int rate_cats, bool rate_scalers, unsigned int workgroups_per_cu);
 unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int workgroups_per_cu);
@@ -643,6 +663,29 @@ int pllhip_fused_plan_walk(const FusedGeom & geom, const pllhip_op_t * ops, cons
                            const FusedEdge * edge, const FusedDeferral & dd, const unsigned char * pinned,
                            bool may_unstore, bool may_fold, FusedWalk & out);
 
+// The quad fold (DESIGN.md 2.0 "Folded quad products"), behind pllhip_fused_plan_walk and the launch's choice of quads:
+// the unstored quad products of a folded walk that exactly one inner-inner op reads are not walked either -- their
+// reader gathers the two quads and forms the product itself (pllhip_fused_fold, quads).  The list without them
+// (pllhip_fused_fold_list) is planned once more by pllhip_fused_plan_list, at the slot count the plan before took.
+// ops / args / kinds / extras / rows8 / count: the list `plans` were made of (FusedWalk::fl); plans: the plan before,
+// with pllhip_fused_quad_products' marks; edge: its edge where it ends in the pseudo-op, else nullptr -- the new plan
+// is taken only if it keeps it.  Every op of the new plan is given what its op had in the plan before (unstored, keep,
+// pkeep) and every folded side the factors of the op folded into it (FusedOp::q, qkeep); a walked op that was
+// unstored must still be kept in a slot and never reloaded.  Returns 0: out.plan is to be launched; 1: nothing folds,
+// or the planner does not take the list -- the plan before stands; < 0 on error.
+struct FusedQuadFold
+{
+  std::vector<unsigned char> fold; // per op of the list: folded, not walked
+  FusedFoldList fl;                // the list `plan` was made of
+  FusedListPlan plan;
+  FusedEdge edge;
+  unsigned int nfolded = 0;
+};
+int pllhip_fused_quad_fold_walk(const FusedGeom & geom, const pllhip_op_t * ops, const PartialsArgs * args, const int * kinds,
+                                const FusedExtra * extras, const unsigned int * rows8, unsigned int count,
+                                const std::vector<std::vector<FusedOp>> & plans, unsigned int max_segments, unsigned int nslots,
+                                const FusedEdge * edge, const FusedDeferral & dd, FusedQuadFold & out);
+
 // ---- The 20-state list (partials_aa_fused.hip) before anything is encoded: what each op is to the kernel, what the
 // scaling certificate makes of it, the list the kernel walks.  Indices and numbers only -- ONE rule for
 // pllhip_aa_fused_update (real addresses) and pllhip_aa_list_plan_dry (fake ones; tests/test_host_aa_list_plan.py).
@@ -724,6 +767,17 @@ struct FusedQuadProducts
   const FusedEdge * edge = nullptr;
   const unsigned char * pinned = nullptr;
   std::vector<pllhip_ctx::deferred_clv> left; // out: their records
+  // the quad fold (pllhip_fused_quad_fold_walk): the rest of the list the plans were made of, and how it was planned;
+  // out: the plan launched in place of the one handed over (nfolded != 0), whose parents `left` has as UNSTORED_QUAD_FOLDED
+  bool fold = false;
+  const PartialsArgs * args = nullptr;
+  const int * kinds = nullptr;
+  const FusedExtra * extras = nullptr;
+  const unsigned int * rows8 = nullptr;
+  unsigned int max_segments = 1;
+  const FusedDeferral * dd = nullptr;
+  FusedQuadFold folded;
+  unsigned int nfolded = 0;
 };
 // encode and launch: one plan per segment
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,

@@ -924,6 +924,20 @@ int pll_amd_set_unstored_quad_products(pll_partition_t * p, int on)
   return PLL_SUCCESS;
 }
 
+int pll_amd_quad_fold_stats(pll_partition_t * p, unsigned long long * stats4)
+{
+  int rc = pllhip_quad_fold_stats(pll_amd_priv(p)->ctx, stats4);
+  if (rc) return pll_amd_fail_hip(rc, "quad fold stats");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_set_quad_fold(pll_partition_t * p, int on)
+{
+  int rc = pllhip_set_quad_fold(pll_amd_priv(p)->ctx, on);
+  if (rc) return pll_amd_fail_hip(rc, "set quad fold");
+  return PLL_SUCCESS;
+}
+
 int pll_amd_pair_fold_stats(pll_partition_t * p, unsigned long long * stats4)
 {
   int rc = pllhip_pair_fold_stats(pll_amd_priv(p)->ctx, stats4);

@@ -301,6 +301,9 @@ class PllLibrary:
             if hasattr(lib, "pll_amd_set_unstored_quad_products"):
                 lib.pll_amd_set_unstored_quad_products.argtypes = [_PP, C.c_int]
                 lib.pll_amd_quad_product_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
+            if hasattr(lib, "pll_amd_set_quad_fold"):
+                lib.pll_amd_set_quad_fold.argtypes = [_PP, C.c_int]
+                lib.pll_amd_quad_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
             if hasattr(lib, "pll_amd_set_edge_fold"):
                 lib.pll_amd_set_edge_fold.argtypes = [_PP, C.c_int]
                 lib.pll_amd_edge_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
@@ -1496,6 +1499,16 @@ class Partition:
         buf = (C.c_ulonglong * 4)()
         self._check(self.lib.pll_amd_quad_product_stats(self.ptr, buf), "pll_amd_quad_product_stats")
         return dict(zip(("live", "ops_unstored", "launches", "materialised"), (int(v) for v in buf)))
+
+    def set_quad_fold(self, on):
+        """False: an unstored quad product with one inner-inner reader is walked, not formed by that reader (pll_amd.h)."""
+        self._check(self.lib.pll_amd_set_quad_fold(self.ptr, 1 if on else 0), "pll_amd_set_quad_fold")
+
+    def quad_fold_stats(self):
+        """{live, ops_folded, plans, materialised} of the quad products folded into their readers (pll_amd.h)."""
+        buf = (C.c_ulonglong * 4)()
+        self._check(self.lib.pll_amd_quad_fold_stats(self.ptr, buf), "pll_amd_quad_fold_stats")
+        return dict(zip(("live", "ops_folded", "plans", "materialised"), (int(v) for v in buf)))
 
     def unstored_stats(self):
         """{unstored_now, ops_unstored, launches, materialised} of the 4-state pair products (pll_amd.h)."""
