@@ -1,5 +1,5 @@
 // batched.hpp -- internal: the device plumbing the batched calls share (insertion.hip, branch_opt.hip, posteriors.hip,
-// nni.hip, tree_score.hip, model_score.hip, replicates.hip, nni_support.hip, distance.hip, joining.hip, branch_deriv.hip, tree_replicates.hip; the code is in batched.hip).  A new batched call starts
+// nni.hip, nni_quartet.hip, tree_score.hip, model_score.hip, replicates.hip, nni_support.hip, distance.hip, joining.hip, branch_deriv.hip, tree_replicates.hip; the code is in batched.hip).  A new batched call starts
 // from these pieces:
 //
 //   opening   pllhip_batch_open: the checks every batched call begins with;

@@ -9,9 +9,10 @@
 //                 three times -- the same bits either way);
 //   site terms    s[(3 e + k) spitch + n], the unweighted per-site log-likelihood of candidate (e, k), rows padded and
 //                 zero-tailed as k_repl_site_terms leaves them.  Quartet route (4 states, 1 or 4 rate categories, no
-//                 per-rate scale buffers): k_support_quartet, k_nni_quartet's log-likelihood path up to the lane's
-//                 own lk -- each side read once, the four products formed once per site, no candidate CLV written.
-//                 General route: u' and v' of every candidate by the partition's own CLV kernels into scratch, then
+//                 per-rate scale buffers): k_nni_quartet with the ending NNI_END_TERMS (nni_quartet.hip), the
+//                 log-likelihood path up to the lane's own lk, arrangement k under its own central matrix -- each side
+//                 read once, the four products formed once per site, no candidate CLV written.  General route: u' and
+//                 v' of every candidate by the partition's own CLV kernels into scratch (pllhip_nni_run_pairs), then
 //                 k_repl_site_terms (batch_edge_site_lnl);
 //   sums          k_support_sums: the loop of k_repl_sums<WT, 3> (replicates.hpp), one edge's three rows per pass over
 //                 the weights, the chunk's edges in the grid's z; k_repl_finish adds the spans in order.  The centres
@@ -30,150 +31,6 @@
 #include <cfloat>
 #include <cmath>
 #include <vector>
-
-#define SUPPORT_MATS 7 // matrices of an edge: sides A..D, then the central branch of arrangements 0, 1, 2
-
-struct SupportQuartetArgs
-{
-  const NniEdge * __restrict__ edges; // [edges]
-  const double * __restrict__ pm;     // [edges][SUPPORT_MATS][R][4][4]
-  BatchModel m;
-  double * __restrict__ s;            // [edges][3][spitch]
-  unsigned int sites, spitch;
-  int scaled;                         // the partition has scale buffers: u' and v' take the op's scaling rule
-};
-
-// k_nni_quartet<R, 0> (nni.hip) up to the lane's own site: the same loads, products, pairings, scaling rule and
-// category sum, the central matrix of arrangement k its own.  The three lk of a site are stored unweighted; past the
-// last site a row is 0 up to spitch.  Grid (tiles, edges), PLLHIP_BATCH_TILE lanes.
-template <int R>
-__global__ __launch_bounds__(256) void k_support_quartet(SupportQuartetArgs a)
-{
-  constexpr unsigned int SPR = 64u / R; // sites per round
-  __shared__ double s_p[4][R][16];      // the sides' matrices
-  __shared__ double s_e[3][R][16];      // the central matrix of each arrangement
-  __shared__ double s_tab[4][16][R][4]; // a pattern tip's product per code: sum of its matrix's columns in the mask
-  __shared__ double s_fr[R][4];
-  const unsigned int e = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
-  const NniEdge ed = a.edges[e];
-  const double * pm = a.pm + (size_t)e * SUPPORT_MATS * R * 16u;
-  for (unsigned int i = tid; i < 4u * R * 16u; i += 256u) (&s_p[0][0][0])[i] = pm[i];
-  for (unsigned int i = tid; i < 3u * R * 16u; i += 256u) (&s_e[0][0][0])[i] = pm[4u * R * 16u + i];
-  for (unsigned int i = tid; i < R * 4u; i += 256u) s_fr[i / 4u][i % 4u] = a.m.freqs[(size_t)a.m.params[i / 4u] * 4u + i % 4u];
-  for (unsigned int i = tid; i < 4u * 16u * R * 4u; i += 256u)
-  {
-    const unsigned int j = i % 4u, k = (i / 4u) % R, code = (i / (4u * R)) % 16u, x = i / (64u * R);
-    double t = 0.0;
-    if (a.edges[e].s[x].tip) // (not `ed`: an index known only at run time would put the copy into private memory)
-    {
-      const double * m = pm + ((size_t)x * R + k) * 16u + j * 4u;
-      for (unsigned int s = 0; s < 4u; ++s)
-        if ((code >> s) & 1u) t += m[s];
-    }
-    s_tab[x][code][k][j] = t;
-  }
-  __syncthreads();
-
-  const unsigned int lane = tid & 63u, wave = tid >> 6;
-  const unsigned int g = lane / R, k = lane - g * R, grp0 = g * R;
-  const unsigned int own_round = lane / SPR;
-  const int own_src = (int)((lane - own_round * SPR) * R);
-  const unsigned int pi = a.m.params[k];
-  const double pinv = a.m.prop_invar[pi];
-  const double wk = a.m.rate_weights[k];
-  const size_t first = (size_t)tile * PLLHIP_BATCH_TILE;
-  const size_t end = std::min<size_t>(first + PLLHIP_BATCH_TILE, a.sites);
-  const size_t sbase = first + (size_t)wave * 64u;
-  double o_t[3] = {1.0, 1.0, 1.0};
-  unsigned int o_c[3] = {0u, 0u, 0u};
-  if (sbase < end)
-  {
-#pragma unroll 1
-    for (unsigned int round = 0; round < (unsigned int)R; ++round)
-    {
-      const size_t pos = sbase + (size_t)round * SPR + g;
-      const bool act = pos < end;
-      const size_t n = act ? pos : 0; // (a lane past the end works on site 0 and stores nothing)
-      // the four products of the site, the lane's category
-      double x[4][4];
-      unsigned int cnt[4];
-#pragma unroll
-      for (int sd = 0; sd < 4; ++sd)
-      {
-        const NniSide & S = ed.s[sd];
-        if (S.tip)
-        {
-          const unsigned int code = S.tip[n] & 15u;
-          const double2 * t2 = reinterpret_cast<const double2 *>(&s_tab[sd][code][k][0]);
-          const double2 lo = t2[0], hi = t2[1];
-          x[sd][0] = lo.x;
-          x[sd][1] = lo.y;
-          x[sd][2] = hi.x;
-          x[sd][3] = hi.y;
-        }
-        else
-        {
-          const double2 * r2 = reinterpret_cast<const double2 *>(S.clv + (n * R + k) * 4u);
-          const double2 lo = r2[0], hi = r2[1];
-          const double row[4] = {lo.x, lo.y, hi.x, hi.y};
-          nni_matvec(&s_p[sd][k][0], row, x[sd]);
-        }
-        cnt[sd] = (a.scaled && S.scaler) ? S.scaler[n] : 0u;
-      }
-      int inv = -1;
-      if (pinv > 0.0 && a.m.invariant) inv = a.m.invariant[n];
-#pragma unroll
-      for (int arr = 0; arr < 3; ++arr)
-      {
-        const int X = 0, Y = arr == 0 ? 1 : arr == 1 ? 2 : 3, Z = arr == 1 ? 1 : 2, W = arr == 2 ? 1 : 3;
-        // (a tip-tip op has no scaling test: partials.c, the lookup-table case)
-        const bool su = a.scaled && !(ed.s[X].tip && ed.s[Y].tip), sv = a.scaled && !(ed.s[Z].tip && ed.s[W].tip);
-        double u[4], v[4];
-        unsigned int count;
-        nni_pair<R>(x[X], x[Y], x[Z], x[W], cnt[X], cnt[Y], cnt[Z], cnt[W], su, sv, grp0, u, v, count);
-        // k_lnl_gen's category term: sum_j u'[j] pi[j] (P_e v')[j], then the weight and +I
-        double tb[4];
-        nni_matvec(&s_e[arr][k][0], v, tb);
-        double terma_r = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) terma_r += u[j] * s_fr[k][j] * tb[j];
-        double contrib;
-        if (pinv > 0.0)
-        {
-          const double inv_lk = (inv == -1) ? 0.0 : s_fr[k][inv];
-          contrib = wk * (terma_r * (1.0 - pinv) + inv_lk * pinv);
-        }
-        else
-          contrib = terma_r * wk;
-        double terma = 0.0;
-#pragma unroll
-        for (int i = 0; i < R; ++i) terma += __shfl(contrib, (int)(grp0 + i), 64);
-        const double t_own = __shfl(terma, own_src, 64);
-        const unsigned int c_own = (unsigned int)__shfl((int)count, own_src, 64);
-        if (own_round == round)
-        {
-          o_t[arr] = t_own;
-          o_c[arr] = c_own;
-        }
-      }
-    }
-  }
-
-  // the lane's own site: three logs and the scaler terms, stored; zeros behind the last site
-  const size_t n_own = sbase + lane;
-  if (n_own >= a.spitch) return;
-#pragma unroll
-  for (int arr = 0; arr < 3; ++arr)
-  {
-    double lk = 0.0;
-    if (n_own < end)
-    {
-      lk = log(o_t[arr]);
-      if (o_c[arr]) lk += (double)o_c[arr] * log(PLLHIP_SCALE_THRESHOLD);
-    }
-    a.s[((size_t)e * 3u + arr) * a.spitch + n_own] = lk;
-  }
-}
 
 // The loop of k_repl_sums<WT, 3> for edge blockIdx.z of the chunk: its rows are s[3 z ..][spitch], its sums go to
 // partial[span][3 z + k][count].  Grid (spans, blocks of 64 replicates, edges), one wave.  (Two edges -- six rows --
@@ -251,39 +108,16 @@ extern "C" int pllhip_nni_support(pllhip_ctx_t * c, const pllhip_replicates_t * 
   }
   int rc = pllhip_batch_open(c, what, BATCH_PLAIN_ONLY, params);
   if (rc) return rc;
-  const unsigned int nodes = (unsigned int)c->clv.size();
-  const int nsc = (int)c->sh.scale_buffers;
   const unsigned int S = c->sh.states, R = c->sh.rate_cats;
   // everything again (the shim's own rule: a binding may call it directly)
-  for (unsigned int i = 0; i < ne; ++i)
-  {
-    if (!(E[i].length >= 0.0 && E[i].length <= DBL_MAX))
+  if ((rc = pllhip_nni_check_edges(c, what, E, ne))) return rc;
+  for (size_t i = 0; h_central && i < 3 * (size_t)ne; ++i)
+    if (!(h_central[i] >= 0.0 && h_central[i] <= DBL_MAX))
     {
-      pllhip_set_error("%s: edge %u: length out of range", what, i);
+      pllhip_set_error("%s: edge %u, arrangement %d: central length out of range", what, (unsigned int)(i / 3),
+                       (int)(i % 3));
       return -1;
     }
-    for (int k = 0; h_central && k < 3; ++k)
-      if (!(h_central[3 * (size_t)i + k] >= 0.0 && h_central[3 * (size_t)i + k] <= DBL_MAX))
-      {
-        pllhip_set_error("%s: edge %u, arrangement %d: central length out of range", what, i, k);
-        return -1;
-      }
-    for (int sd = 0; sd < 4; ++sd)
-    {
-      const pllhip_nni_side_t & s = E[i].side[sd];
-      if (s.clv_index >= nodes || s.scaler_index >= nsc || s.scaler_index < -1 ||
-          !(s.length >= 0.0 && s.length <= DBL_MAX))
-      {
-        pllhip_set_error("%s: edge %u, side %d: index or length out of range", what, i, sd);
-        return -1;
-      }
-      if (!pllhip_is_tip(c, s.clv_index) && !c->clv[s.clv_index])
-      {
-        pllhip_set_error("%s: edge %u, side %d: CLV missing", what, i, sd);
-        return -1;
-      }
-    }
-  }
   if (R > PLLHIP_MAX_RATE_CATS)
   {
     pllhip_set_error("%s: more than %d rate categories", what, PLLHIP_MAX_RATE_CATS);
@@ -292,10 +126,8 @@ extern "C" int pllhip_nni_support(pllhip_ctx_t * c, const pllhip_replicates_t * 
   PLLHIP_CERT_FIRST(c);     // (the CLVs and scaler counts read here are the reference's, or the list runs again first)
   PLLHIP_DEFERRED_FLUSH(c); // (deferred cherries get their bytes before anything but a list kernel touches them)
 
-  const bool scaled = nsc > 0;
-  const bool covers = S == 4 && (R == 1 || R == 4) && !(scaled && c->sh.rate_scalers);
-  const bool quartet = covers && route != 0;
-  const int mode = !scaled ? SCALE_NONE : (c->sh.rate_scalers ? SCALE_RATE : SCALE_SITE);
+  const NniRoute rt = pllhip_nni_route(c, route);
+  const bool scaled = rt.scaled, quartet = rt.quartet;
 
   // ---- chunk size in edges: everything one chunk needs within `budget` bytes (one edge at least)
   const size_t sites = c->sh.sites, spitch = repl_padded_sites(sites);
@@ -304,7 +136,7 @@ extern "C" int pllhip_nni_support(pllhip_ctx_t * c, const pllhip_replicates_t * 
   const size_t reps = set ? set->count : 0;
   const size_t own_pitch = (sites * 4 + REPL_ROW_BYTES - 1) / REPL_ROW_BYTES * REPL_ROW_BYTES;
   const size_t sc_b = scaled ? c->scaler_stride * 4 : 0;
-  size_t per_edge = SUPPORT_MATS * c->pmat_elems * 8 + sizeof(NniEdge) + 3 * spitch * 8 +
+  size_t per_edge = NNI_SUPPORT_MATS * c->pmat_elems * 8 + sizeof(NniEdge) + 3 * spitch * 8 +
                     3 * (size_t)(spans + 1) * (reps + 1) * 8 + 8 + 8 * 256;
   if (!quartet) per_edge += 6 * (c->clv_stride * 8 + sc_b) + 3 * sizeof(BatchEdge);
   const size_t fixed = own_pitch + 4096;
@@ -316,7 +148,7 @@ extern "C" int pllhip_nni_support(pllhip_ctx_t * c, const pllhip_replicates_t * 
   // ---- scratch layout
   BatchLayout L;
   const size_t o_own = L.take(own_pitch);
-  const size_t o_pm = L.take((size_t)SUPPORT_MATS * ec * c->pmat_elems * 8);
+  const size_t o_pm = L.take((size_t)NNI_SUPPORT_MATS * ec * c->pmat_elems * 8);
   const size_t o_desc = L.take((size_t)ec * sizeof(NniEdge));
   const size_t o_s = L.take((size_t)nc * spitch * 8);
   const size_t o_part = L.take((size_t)spans * nc * reps * 8);
@@ -367,8 +199,8 @@ extern "C" int pllhip_nni_support(pllhip_ctx_t * c, const pllhip_replicates_t * 
     sa.count = set->count;
   }
 
-  std::vector<unsigned int> mi(SUPPORT_MATS * (size_t)ec);
-  std::vector<double> bl(SUPPORT_MATS * (size_t)ec);
+  std::vector<unsigned int> mi(NNI_SUPPORT_MATS * (size_t)ec);
+  std::vector<double> bl(NNI_SUPPORT_MATS * (size_t)ec);
   std::vector<NniEdge> hd(quartet ? ec : 0);
   std::vector<BatchOp> ops;
   std::vector<BatchEdge> hge(quartet ? 0 : nc);
@@ -383,79 +215,41 @@ extern "C" int pllhip_nni_support(pllhip_ctx_t * c, const pllhip_replicates_t * 
     {
       for (unsigned int sd = 0; sd < 4; ++sd)
       {
-        mi[SUPPORT_MATS * i + sd] = SUPPORT_MATS * i + sd;
-        bl[SUPPORT_MATS * i + sd] = E[e0 + i].side[sd].length;
+        mi[NNI_SUPPORT_MATS * i + sd] = NNI_SUPPORT_MATS * i + sd;
+        bl[NNI_SUPPORT_MATS * i + sd] = E[e0 + i].side[sd].length;
       }
       for (unsigned int k = 0; k < 3; ++k)
       {
-        mi[SUPPORT_MATS * i + 4 + k] = SUPPORT_MATS * i + 4 + k;
-        bl[SUPPORT_MATS * i + 4 + k] = h_central ? h_central[3 * (size_t)(e0 + i) + k] : E[e0 + i].length;
+        mi[NNI_SUPPORT_MATS * i + 4 + k] = NNI_SUPPORT_MATS * i + 4 + k;
+        bl[NNI_SUPPORT_MATS * i + 4 + k] = h_central ? h_central[3 * (size_t)(e0 + i) + k] : E[e0 + i].length;
       }
     }
-    if ((rc = pllhip_pmatrices_to(c, d_pm, SUPPORT_MATS * ec, params, mi.data(), bl.data(), SUPPORT_MATS * en)))
+    if ((rc = pllhip_pmatrices_to(c, d_pm, NNI_SUPPORT_MATS * ec, params, mi.data(), bl.data(),
+                                  NNI_SUPPORT_MATS * en)))
       return rc;
 
     if (quartet)
     {
-      for (unsigned int i = 0; i < en; ++i)
-        for (unsigned int sd = 0; sd < 4; ++sd)
-        {
-          const pllhip_nni_side_t & s = E[e0 + i].side[sd];
-          const bool t = pllhip_is_tip(c, s.clv_index);
-          hd[i].s[sd].clv = t ? nullptr : c->clv[s.clv_index];
-          hd[i].s[sd].tip = t ? pllhip_tip_ptr(c, s.clv_index) : nullptr;
-          hd[i].s[sd].scaler = t ? nullptr : pllhip_scaler_ptr(c, s.scaler_index);
-        }
-      // (the stream orders this copy behind the previous chunk's kernels; hd is rewritten only after the wait below)
-      HIP_TRY(hipMemcpyAsync(d_desc, hd.data(), en * sizeof(NniEdge), hipMemcpyHostToDevice, c->stream));
-      SupportQuartetArgs q;
+      if ((rc = pllhip_nni_descriptors(c, E + e0, en, hd, d_desc))) return rc;
+      NniQuartetArgs q;
       memset(&q, 0, sizeof(q));
       q.edges = d_desc;
       q.pm = d_pm;
       q.m = model;
-      q.s = d_s;
+      q.terms = d_s;
       q.sites = (unsigned int)sites;
+      q.tiles = tiles;
       q.spitch = (unsigned int)spitch;
       q.scaled = scaled ? 1 : 0;
       pllhip_prof_scope prof(c, PLLHIP_PROF_LNL);
-      const dim3 grid(tiles, en);
-      if (R == 4) k_support_quartet<4><<<grid, 256, 0, c->stream>>>(q);
-      else k_support_quartet<1><<<grid, 256, 0, c->stream>>>(q);
-      HIP_TRY(hipGetLastError());
+      if ((rc = pllhip_nni_quartet_launch(c, q, NNI_END_TERMS, en))) return rc;
     }
     else
     {
-      // u' and v' of every candidate: the ops themselves, by the partition's own CLV kernels
-      ops.resize(2 * (size_t)cn);
-      for (unsigned int i = 0; i < en; ++i)
-        for (unsigned int k = 0; k < 3; ++k)
-          for (unsigned int h = 0; h < 2; ++h)
-          {
-            const unsigned int x = nni_perm[k][2 * h], y = nni_perm[k][2 * h + 1];
-            const size_t slot = ((size_t)i * 3 + k) * 2 + h;
-            const pllhip_nni_side_t & sx = E[e0 + i].side[x], & sy = E[e0 + i].side[y];
-            ops[slot].kind = pllhip_batch_fill_op(
-                c, ops[slot].a,
-                pllhip_batch_operand(c, sx.clv_index, sx.scaler_index,
-                                     d_pm + (size_t)(SUPPORT_MATS * i + x) * c->pmat_elems),
-                pllhip_batch_operand(c, sy.clv_index, sy.scaler_index,
-                                     d_pm + (size_t)(SUPPORT_MATS * i + y) * c->pmat_elems),
-                d_clv + slot * c->clv_stride, d_scal ? d_scal + slot * c->scaler_stride : nullptr);
-            ops[slot].mode = mode;
-          }
-      if ((rc = pllhip_batch_run_ops(c, ops.data(), ops.size()))) return rc;
+      // u' and v' of every candidate
+      if ((rc = pllhip_nni_run_pairs(c, E + e0, en, NNI_SUPPORT_MATS, d_pm, d_clv, d_scal, rt.mode, ops))) return rc;
       // the edge of every candidate: u', v', the arrangement's central matrix; its row of site terms
-      for (unsigned int i = 0; i < cn; ++i)
-      {
-        BatchEdge & g = hge[i];
-        memset(&g, 0, sizeof(g));
-        g.pclv = d_clv + (size_t)(2 * i) * c->clv_stride;
-        g.cclv = g.pclv + c->clv_stride;
-        g.pscal = d_scal ? d_scal + (size_t)(2 * i) * c->scaler_stride : nullptr;
-        g.cscal = d_scal ? g.pscal + c->scaler_stride : nullptr;
-        g.pmat = d_pm + (size_t)(SUPPORT_MATS * (i / 3) + 4 + i % 3) * c->pmat_elems;
-        g.out = i;
-      }
+      pllhip_nni_candidate_edges(c, hge.data(), cn, NNI_SUPPORT_MATS, true, d_pm, d_clv, d_scal);
       // (the stream orders this copy behind the previous chunk's kernels; hge is rewritten only after the wait below)
       HIP_TRY(hipMemcpyAsync(d_gedge, hge.data(), cn * sizeof(BatchEdge), hipMemcpyHostToDevice, c->stream));
       ReplTermArgs ta;

@@ -188,6 +188,29 @@ def test_shapes(gpu, monkeypatch, sites):
         p.destroy()
 
 
+@pytest.mark.parametrize("route", ["quartet", "general"])
+@pytest.mark.parametrize("kw", [dict(rate_cats=4), dict(rate_cats=1), dict(rate_cats=4, pattern_tip=False),
+                                dict(rate_cats=1, pattern_tip=False)], ids=ids_of)
+def test_one_site_equals_nni_loglikelihood(gpu, monkeypatch, kw, route):
+    """an alignment of one site: the sum of pll_amd_nni_loglikelihood and the centre of this call are both the single
+    rounded product of the site's term and its weight (plus zeros), so the site term of the scoring call and the
+    stored one are the same bits"""
+    set_route(monkeypatch, route)
+    case = N.make_case(states=4, tips=10, sites=1, seed=21, scalers=True, **kw)
+    p = N.build(gpu, case)
+    try:
+        edges = N.nni_edges(case)
+        got = p.nni_support(None, edges, case.params, want=("persite_lnl",))
+        lnl = p.nni_loglikelihood(edges, case.params)
+        want = got["persite_lnl"][:, :, 0].astype(np.float64) * np.float64(RD.own_weights(p)[0])
+        print("%s %s: %d edges, weight %d, lnl %s" % (ids_of(kw), route, len(edges), RD.own_weights(p)[0],
+                                                     lnl[0].tolist()))
+        assert bits(got["lnl"]) == bits(lnl)
+        assert bits(lnl) == bits(want)
+    finally:
+        p.destroy()
+
+
 @pytest.mark.parametrize("kw", [dict(), dict(rate_cats=1), dict(pattern_tip=False), dict(scalers=False),
                                 dict(states=20), dict(states=4, rate_scalers=True)], ids=ids_of)
 def test_four_tips(gpu, monkeypatch, kw):
