@@ -395,6 +395,11 @@ PLLHIP_EXPORT unsigned int pllhip_quad_row_class_dry(const unsigned char * row, 
  * 2 one that is its second); and the rows every walked op's gathers name, on top of pllhip_fused_plan_dry_folded's
  * walk: gathers_out[12] per walked op = four gathers x {first tip + 1, second tip + 1, chars word}. */
 PLLHIP_EXPORT unsigned int pllhip_pair_row_byte_dry(unsigned int a, unsigned int b);
+/* The list kernel's index rule (tests/test_host_gather_index.py): for the gather a record's character word `ch`
+ * describes, out3 = {byte offset lane `lane` reads of the wave's 1 KB character batch for sub-step `sub_step`, bytes read
+ * there, table index formed of the value `raw` read there}.  Returns 0, or 1 for arguments no kernel instance has. */
+PLLHIP_EXPORT int pllhip_fused_index_dry(unsigned int ch, unsigned int sps, unsigned int sub_step, unsigned int lane,
+                                         unsigned int raw, unsigned int * out3);
 PLLHIP_EXPORT unsigned int pllhip_fused_row_index_dry(const unsigned int * row, unsigned int kind, unsigned int sps,
                                                       unsigned int sub_step, unsigned int lane);
 PLLHIP_EXPORT int pllhip_fused_plan_dry_rows(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,

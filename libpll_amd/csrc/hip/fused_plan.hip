@@ -47,8 +47,9 @@ unsigned int pllhip_fused_slots_for(unsigned int R, bool rate_scalers, unsigned 
   // (four workgroups -- 16 waves of 128 registers, four slots -- were measured for short lists in round 3 and are
   // slower than three at every list length: 2 / 3 / 5 / 7 / 15 ops 257 / 286 / 335 / 282 / 421 us against 226 / 260 /
   // 310 / 246 / 411; the variant spills seven registers)
+  // (1 KB of it is the wave's character batch: the sixth slot of four rate categories on twelve waves went for it)
   const size_t budget = wgs >= 3 ? 13312 : 16384;
-  return (unsigned int)((budget - pmat) / per_slot);
+  return (unsigned int)((budget - pmat - PLLHIP_FUSED_BATCH_BYTES) / per_slot);
 }
 
 // Slot assignment: every inner operand is read from a slot.  A value whose

@@ -251,14 +251,14 @@ extern "C" unsigned int pllhip_pair_row_byte_dry(unsigned int a, unsigned int b)
 }
 
 // What gather_factor() of k_dna_fused takes from ONE row: row[] the row's words of a tile, kind 0 a pair row, 1 a single
-// tip that is the table's first character, 2 one that is its second (pllhip_fused_gather_bits).
+// tip that is the table's first character, 2 one that is its second (pllhip_fused_gather_bits) -- the index rule
+// (pllhip_fused_index, partials_fused.hpp) on a batch image that holds the row at lane position 0.
 template <unsigned int SPS>
 static unsigned int row_index_dry(const unsigned int * row, unsigned int bits, unsigned int sub_step, unsigned int lane)
 {
-  unsigned int w[SPS / 4];
-  for (unsigned int m = 0; m < SPS / 4; ++m) w[m] = row[sub_step * (SPS / 4) + m];
-  return pllhip_fused_row_index<SPS>(w, (bits & PLLHIP_FUSED_CH_NIBBLE) ? 0x0f0f0f0fu : 0xffffffffu,
-                                     (bits & PLLHIP_FUSED_CH_SHIFT4) ? 4u : 0u, lane / (64u / SPS));
+  unsigned char image[PLLHIP_FUSED_BATCH_BYTES] = {};
+  memcpy(image, row, PLLHIP_FUSED_J * SPS);
+  return pllhip_fused_index_of_image<SPS>(image, bits, sub_step, lane);
 }
 extern "C" unsigned int pllhip_fused_row_index_dry(const unsigned int * row, unsigned int kind, unsigned int sps,
                                                    unsigned int sub_step, unsigned int lane)

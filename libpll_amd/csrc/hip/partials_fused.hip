@@ -371,22 +371,25 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
   const unsigned int h = lane & 1u;
   const unsigned int k = (lane >> 1) & (RC - 1);
   const unsigned int wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // per wave: [nslots][J][64] CLV granules | [MG] matrix granules (one matrix at a time) | counts
-  // (counts: one word per site, or per (site, rate) with per-rate scalers, of a sub-step)
+  // per wave: [nslots][J][64] CLV granules | [MG] matrix granules (one matrix at a time) | counts | the character batch
+  // (counts: one word per site, or per (site, rate) with per-rate scalers, of a sub-step; the batch: 64 lane positions
+  // of 16 bytes, the tile's characters as one load fetched them -- see gather())
   constexpr unsigned int CW = (MODE == SCALE_RATE) ? 32u : (SPS < 4u ? 4u : SPS); // words per sub-step, 16-byte multiple
-  const size_t wave_g = (size_t)nslots * J * 64 + MG + (size_t)nslots * J * CW / 4;
+  constexpr unsigned int BG = PLLHIP_FUSED_BATCH_BYTES / 16u;
+  const size_t wave_g = (size_t)nslots * J * 64 + MG + (size_t)nslots * J * CW / 4 + BG;
   double2 * clv = lds_fused + wave_in_wg * wave_g;
   double2 * pst = clv + (size_t)nslots * J * 64;
   unsigned int * cnt = reinterpret_cast<unsigned int *>(pst + MG);
+  unsigned char * chb = reinterpret_cast<unsigned char *>(clv + (wave_g - BG));
   // the same places as LDS byte addresses (what the LDS-DMA of reload() takes in M0); computed
   // from the array itself: casting a derived generic pointer back to LDS makes the compiler
   // emit a null check it cannot always encode
   const unsigned int clv_lds_b = __builtin_amdgcn_readfirstlane(
       (unsigned int)(uintptr_t)(PLL_LDS char *)lds_fused + (unsigned int)(wave_in_wg * wave_g * 16));
   const unsigned int cnt_lds_b = clv_lds_b + (unsigned int)(((size_t)nslots * J * 64 + MG) * 16);
+  const unsigned int chb_lds_b = clv_lds_b + (unsigned int)((wave_g - BG) * 16);
   // what never changes for a lane: its byte offsets into a tile, a tip row, a pair-table entry, a matrix block
   const unsigned int lane16 = lane * 16u;
-  const unsigned int tip_lane = lane / W;
   const unsigned int gat_lane = (lane & (W - 1)) * 16u;
   const unsigned int pm_lane = (lane & (MG - 1)) * 16u;
   const bool pm_left = lane < MG;
@@ -495,27 +498,16 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     const unsigned int edge_sub = EDGE ? (lane & (W - 1)) % J : 0u, edge_own = EDGE ? edge_sub * SPS + lane / W : 0u;
     unsigned int edge_pw = 0;
     if (EDGE) edge_pw = *(const unsigned int PLL_GLOBAL *)((unsigned long long)(uintptr_t)edge.pattern_weights + (site0 + edge_own) * 4u);
-    pll_v4u cs = *(const pll_v4u PLL_GLOBAL *)(row_first + site0);
+    const pll_v4u cs = *(const pll_v4u PLL_GLOBAL *)(row_first + site0);
     // What an op needs from memory besides is requested TWO ops ahead of it: its 16 bytes of [P_l | P_r].
     auto request = [&](FusedFetch<J> & f, const Rec & r) {
       const unsigned int off = (pm_left ? rec_req_lmat(r) : rec_req_rmat(r)) + pm_lane;
       f.pm = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(bases.pmat) + off);
       if (RC == 8) f.pm2 = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(bases.pmat) + rec_req_rmat(r) + pm_lane);
     };
-    // The characters of sub-step j of a row: bytes j * SPS ... of the row's TS bytes, i.e. the SPS / 4 words that
-    // `readlane` brings from the lane(s) holding them (wave-uniform positions, wave-uniform results: scalar registers).
-    auto row_words = [&](unsigned int pos, unsigned int j, unsigned int (&out)[SPS / 4]) {
-#pragma unroll
-      for (unsigned int m = 0; m < SPS / 4; ++m)
-      {
-        const unsigned int w = j * (SPS / 4) + m; // word of the row
-        const unsigned int v = (w & 3u) == 0 ? cs.x : (w & 3u) == 1 ? cs.y : (w & 3u) == 2 ? cs.z : cs.w;
-        out[m] = (unsigned int)__builtin_amdgcn_readlane((int)v, (int)(pos + w / 4));
-      }
-    };
     // ... and ONE op ahead its entries of the pair table are gathered -- by an op that HAS a gathered factor only (an
-    // absent tip's character is 0).  The characters' readlanes, the address arithmetic and the loads of a factor sit
-    // behind a wave-uniform branch on the record's CH_LTIP | CH_RTIP bits: an inner-inner op ahead costs a scalar test.
+    // absent tip's character is 0).  The index reads, the address arithmetic and the loads of a factor sit
+    // behind a wave-uniform branch on the record's CH_LTIP bits: an inner-inner op ahead costs a scalar test.
     // (deferred cherries: both characters of a pair may belong to ONE operand -- the cherry's two tips -- and an op
     // whose two factors are both gathered, kind 3, takes the second one from a table of its own, behind a branch of
     // its own; the instances that never defer -- 8 categories, per-rate scalers -- have no second gather at all)
@@ -533,77 +525,87 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     // the loads, until both ends of their life were made whole 16-byte operands of an empty asm statement).
     constexpr bool SECOND = RC <= 4 && MODE != SCALE_RATE; // (partials.hip: what may defer a cherry; checked by the launch)
     constexpr unsigned int TB = 256u * W * 16u; // bytes of a table
-    auto gather_factor = [&](pll_v2d (&pt)[J], unsigned int ch, unsigned int table_off, auto may_be_wide, bool displaced) {
-      // (ONE row per factor: a cherry's cached pair row, whose bytes already are the table's index -- pair_rows.hip --, or
-      // a single tip's row, masked and shifted to its place in scalar registers, four characters at a time; a lane then
-      // picks its word and byte: pllhip_fused_row_index, partials_fused.hpp; then one shift-add)
-      const unsigned int mask = (ch & PLLHIP_FUSED_CH_NIBBLE) ? 0x0f0f0f0fu : 0xffffffffu;
-      const unsigned int shift = (ch / (PLLHIP_FUSED_CH_SHIFT4 / 4u)) & 4u;
-      const unsigned long long tab = (unsigned long long)(uintptr_t)bases.pairtab + table_off; // (uniform)
-      // The WIDE form (quad rows, quad_rows.hip; any of an op's gathers: a reader of two folded quad products has four):
-      // the row holds a 16-bit class per site -- two lane positions per granule of a byte row, pllhip_quad_word_lane --,
-      // the table one entry per class and may be several tables long: a gather behind the first finds its own behind all
-      // of those before it, displaced by the tables the word's top byte counts.  The same words-then-pick on the scalar
-      // side; the two forms differ in the OFFSET only, an ordinary lane value -- the load is ONE statement for both, so
-      // that the gathered registers have one writer per sub-step and nothing to merge behind it (see gather() below,
-      // point 1).
-      bool wide = false;
-      unsigned long long base = tab;
-      if constexpr (SECOND && decltype(may_be_wide)::value)
-      {
-        wide = (ch & PLLHIP_FUSED_CH_WIDE) != 0u;
-        if (wide && displaced) base = tab + (unsigned long long)(ch >> 24) * TB;
-      }
+    constexpr unsigned int ENTRY_SHIFT = RC == 1 ? 5u : RC == 2 ? 6u : RC == 4 ? 7u : 8u; // log2 of an entry's W * 16 bytes
+    static_assert((1u << ENTRY_SHIFT) == W * 16u, "an entry of a table: W lanes of 16 bytes");
+    // Index delivery.  The tile's character batch lies in the wave's LDS block `chb` as the load fetched it, lane
+    // position p's 16 bytes at 16 p, and a lane takes the index of ITS site with one LDS read of 16 bits: a quad row's
+    // class (the WIDE form, quad_rows.hip; any of an op's gathers: a reader of two folded quad products has four), or
+    // the pair of bytes that holds its byte -- of a cherry's cached pair row, whose bytes already are the table's index
+    // (pair_rows.hip), or of a single tip's row, masked and shifted to its place.  Where the read is and what becomes of
+    // it: pllhip_fused_index, partials_fused.hpp -- the row's wave-uniform byte offset plus a number of the lane's that
+    // never changes, the second sub-step an immediate offset behind the first; the forms differ in numbers, not in
+    // instructions.  (Until the batch lay in LDS it was four registers, and every gather brought its row's words to
+    // the scalar side with v_readlane and back: some 65 instructions per wide factor.)
+    // The reads of all of an op's factors are issued together, at the top of the op that gathers them (index_reads()
+    // in step()), and waited for once.
+    auto factor_index = [&](unsigned int (&raw)[J], unsigned int ch, auto may_be_wide) {
+      const unsigned int c = (SECOND && decltype(may_be_wide)::value) ? ch : ch & ~PLLHIP_FUSED_CH_WIDE;
 #pragma unroll
       for (unsigned int j = 0; j < J; ++j)
       {
-        unsigned int off;
-        if (wide)
-        {
-          constexpr unsigned int LPR = TS >= 16 ? TS / 16 : 1;
-          const unsigned int pos = PLLHIP_FUSED_CH_LPOS(ch);
-          unsigned int w[SPS / 2];
+        raw[j] = *reinterpret_cast<const unsigned short *>(chb + pllhip_fused_index<SPS>(c, j, lane).offset);
+      }
+    };
+    auto gather_factor = [&](pll_v2d (&pt)[J], const unsigned int (&raw)[J], unsigned int ch, unsigned int table_off, auto may_be_wide,
+                             bool displaced) {
+      const unsigned int c = (SECOND && decltype(may_be_wide)::value) ? ch : ch & ~PLLHIP_FUSED_CH_WIDE;
+      const unsigned long long tab = (unsigned long long)(uintptr_t)bases.pairtab + table_off; // (uniform)
+      // The wide form's table has one entry per class and may be several tables long: a gather behind the first finds
+      // its own behind all of those before it, displaced by the tables the word's top byte counts.  The two forms differ
+      // in the OFFSET only, an ordinary lane value -- the load is ONE statement for both, so that the gathered registers
+      // have one writer per sub-step and nothing to merge behind it (see gather() below, point 1).
+      unsigned long long base = tab;
+      if ((c & PLLHIP_FUSED_CH_WIDE) && displaced) base = tab + (unsigned long long)(ch >> 24) * TB;
 #pragma unroll
-          for (unsigned int m = 0; m < SPS / 2; ++m)
-          {
-            const unsigned int wl = pllhip_quad_word_of_lane<SPS>(j, m);
-            const unsigned int v = wl == 0 ? cs.x : wl == 1 ? cs.y : wl == 2 ? cs.z : cs.w;
-            w[m] = (unsigned int)__builtin_amdgcn_readlane((int)v, (int)(pos + pllhip_quad_word_lane<SPS>(j, m, LPR)));
-          }
-          off = pllhip_quad_pick<SPS>(w, tip_lane) * (W * 16u) + gat_lane;
-        }
-        else
-        {
-          unsigned int w[SPS / 4];
-          row_words(PLLHIP_FUSED_CH_LPOS(ch), j, w);
-          off = pllhip_fused_row_index<SPS>(w, mask, shift, tip_lane) * (W * 16u) + gat_lane;
-        }
+      for (unsigned int j = 0; j < J; ++j)
+      {
+        // (index * bytes of an entry + the lane's 16 of them: the rule's shift and the entry's in one)
+        const FusedIndexRead rd = pllhip_fused_index<SPS>(c, j, lane);
+        const unsigned int off = (rd.field(raw[j]) << (rd.shift + ENTRY_SHIFT)) | gat_lane;
         asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pt[j]) : "v"(off), "s"(base) : "memory");
       }
     };
     // (the tables of one op follow each other in the table buffer: gather k reads k tables behind the first; a third
     // and a fourth factor -- a right-hand operand that is a folded product, see step() -- always come together; where the
     // factors are quads, tables of several units, each gather's word counts the units the gathers before it took beyond one)
-    auto gather = [&](pll_v2d (&pt)[J], pll_v2d (&pt2)[J], pll_v2d (&pt3)[J], pll_v2d (&pt4)[J], const Rec & r) {
-      const unsigned int ch = rec_chars(r), ch2 = rec_chars2(r);
-      if (ch & PLLHIP_FUSED_CH_LTIP) gather_factor(pt, ch, rec_gather(r), std::true_type(), false);
-      if (SECOND && (ch2 & PLLHIP_FUSED_CH_LTIP)) gather_factor(pt2, ch2, rec_gather(r) + TB, std::true_type(), true);
+    struct GatherIndex
+    {
+      unsigned int raw[4][J];
+    };
+    auto index_reads = [&](GatherIndex & gi, const Rec & r) {
+      if (rec_chars(r) & PLLHIP_FUSED_CH_LTIP) factor_index(gi.raw[0], rec_chars(r), std::true_type());
+      if (SECOND && (rec_chars2(r) & PLLHIP_FUSED_CH_LTIP)) factor_index(gi.raw[1], rec_chars2(r), std::true_type());
       if (SECOND && (rec_chars3(r) & PLLHIP_FUSED_CH_LTIP))
       {
-        gather_factor(pt3, rec_chars3(r), rec_gather(r) + 2u * TB, std::true_type(), true);
-        gather_factor(pt4, rec_chars4(r), rec_gather(r) + 3u * TB, std::true_type(), true);
+        factor_index(gi.raw[2], rec_chars3(r), std::true_type());
+        factor_index(gi.raw[3], rec_chars4(r), std::true_type());
+      }
+    };
+    auto gather = [&](pll_v2d (&pt)[J], pll_v2d (&pt2)[J], pll_v2d (&pt3)[J], pll_v2d (&pt4)[J], const GatherIndex & gi, const Rec & r) {
+      const unsigned int ch = rec_chars(r), ch2 = rec_chars2(r);
+      if (ch & PLLHIP_FUSED_CH_LTIP) gather_factor(pt, gi.raw[0], ch, rec_gather(r), std::true_type(), false);
+      if (SECOND && (ch2 & PLLHIP_FUSED_CH_LTIP)) gather_factor(pt2, gi.raw[1], ch2, rec_gather(r) + TB, std::true_type(), true);
+      if (SECOND && (rec_chars3(r) & PLLHIP_FUSED_CH_LTIP))
+      {
+        gather_factor(pt3, gi.raw[2], rec_chars3(r), rec_gather(r) + 2u * TB, std::true_type(), true);
+        gather_factor(pt4, gi.raw[3], rec_chars4(r), rec_gather(r) + 3u * TB, std::true_type(), true);
       }
       // the list moves on to rows this batch does not hold (rare: every 1024 / TS tip operands): the lanes'
-      // addresses of the next batch, then its rows.  Assembly, like reload(): the compiler counts no load
-      // here (a load inside a branch makes it wait for everything in flight on every path), the next op's
-      // first wait -- for a request issued after this -- covers it.
+      // addresses of the next batch, then its rows, copied straight into the wave's batch block by LDS-DMA like a
+      // reload()'s.  Assembly: the compiler counts no load here (a load inside a branch makes it wait for everything in
+      // flight on every path).  The block's reads for op + 1 are behind us -- their values formed the gathers above --
+      // and nothing orders an LDS read behind a pending LDS-DMA but the wave's own wait: the next op's first wait, for a
+      // request issued after this, stands ahead of its index reads and covers it.
       if (ch & PLLHIP_FUSED_CH_LOAD)
       {
         const unsigned long long tab = (unsigned long long)(bases.rowtab + (size_t)(ch >> 24) * 64u);
         unsigned long long a;
         asm volatile("global_load_dwordx2 %0, %1, %2\n\ts_waitcnt vmcnt(0)" : "=v"(a) : "v"(lane * 8u), "s"(tab) : "memory");
         a += site0;
-        asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(cs) : "v"(a) : "memory");
+        unsigned int m0_saved;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(m0_saved) : "s"(chb_lds_b), "v"(a) : "memory");
       }
     };
 
@@ -738,8 +740,15 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     request(fb, h0);
     sink_stores();
     if (rec_flags(h1) & PLLHIP_FUSED_RELOAD_NEXT) reload(rec_src(h1));
-    asm volatile("" ::"v"(cs)); // (the characters are waited for HERE on every path, whether op 0 gathers or not)
-    gather(pta, pta2, ptb, ptb2, h1);
+    // (the characters are waited for HERE on every path, whether op 0 gathers or not, and laid into the wave's batch
+    // block: what a lane reads of it other lanes wrote)
+    *reinterpret_cast<pll_v4u *>(chb + lane16) = cs;
+    asm volatile("" ::: "memory");
+    {
+      GatherIndex g0;
+      index_reads(g0, h1);
+      gather(pta, pta2, ptb, ptb2, g0, h1);
+    }
     if (EDGE) asm volatile("" : "+v"(edge_pw)); // (arrived with the characters, requested ahead of them: not a load any longer)
     request(fa, h1);
     asm volatile("" ::"v"(fb.pm.x), "v"(fb.pm.y) : "memory");
@@ -809,6 +818,13 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
         lc = *reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(cnt) + rec_lcnt(r0) + t * 4u);
         rc = *reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(cnt) + rec_rcnt(r0) + t * 4u);
       }
+      // (the next op's table indices: their LDS reads go out with the operands' and are back when gather() below forms
+      // the offsets -- no scalar load is in flight here: this op's record has arrived, the next is requested behind the
+      // arithmetic.  They MUST stay below the wait for fu's matrix block above: the previous op's gather() may have
+      // refilled the batch block by LDS-DMA, and that wait is the only thing that orders these reads behind it -- moved
+      // above it they would read the old batch, silently)
+      GatherIndex gi;
+      index_reads(gi, r0);
       if (SECOND)
       {
         // The instances that defer: an operand is read from its slot, or taken HERE from the registers the previous op's
@@ -876,7 +892,7 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
         asm volatile("s_mov_b64 exec, 1\n\tglobal_atomic_add %0, %1, %2, off sc0\n\ts_mov_b64 exec, -1"
                      : "=&v"(next_ticket) : "v"(ticket_counter), "v"(1u) : "memory");
       // (the request last: what the next op waits for first is the youngest operation in flight)
-      gather(pf, pf2, p3, p4, r0);
+      gather(pf, pf2, p3, p4, gi, r0);
       request(ff, r0);
       // (this op's gathered entries, as the registers they arrived in: whole 16-byte values on every path, so that the
       // compiler has nothing to re-pack between the op that loaded them and here -- see gather(); the instances that
@@ -1079,7 +1095,8 @@ static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedB
   const unsigned int sites = c->sh.sites;
   const size_t tile_sites = (size_t)J * (64 / (2 * RC));
   const size_t tiles = (sites + tile_sites - 1) / tile_sites;
-  const size_t lds = 4 * ((size_t)nslots * pllhip_fused_slot_size(RC, c->sh.rate_scalers != 0).bytes() + (size_t)RC * 16 * sizeof(double));
+  const size_t lds = 4 * ((size_t)nslots * pllhip_fused_slot_size(RC, c->sh.rate_scalers != 0).bytes() + (size_t)RC * 16 * sizeof(double) +
+                          PLLHIP_FUSED_BATCH_BYTES);
   // three workgroups (12 waves) per CU when the slots leave room for them, else two; each wave
   // walks its share of the tiles
   const size_t nsegs = bases.nsegs; // (work items: (tile, segment) pairs)
@@ -2016,18 +2033,19 @@ extern "C" unsigned int pllhip_fused_entry_bit_dry(unsigned int gw, unsigned lon
   }
 }
 
+// The index from two tip rows, as the pair rows' builder joins them (pllhip_pair_row_word's shift-and-add under the two
+// masks: no byte carries) and the index rule then reads the joined row: a pair row's byte at lane position 0.
 template <unsigned int SPS>
 static unsigned int pair_index_dry(const unsigned int * row_a, const unsigned int * row_b, unsigned int lmask4, unsigned int rmask4,
                                    unsigned int sub_step, unsigned int lane)
 {
-  // as gather_factor() takes them: words sub_step * (SPS / 4) ... of each row, the lane's site lane / W of the sub-step
-  unsigned int a[SPS / 4], b[SPS / 4];
-  for (unsigned int m = 0; m < SPS / 4; ++m)
+  unsigned char image[PLLHIP_FUSED_BATCH_BYTES] = {};
+  for (unsigned int m = 0; m < PLLHIP_FUSED_J * SPS / 4; ++m)
   {
-    a[m] = row_a[sub_step * (SPS / 4) + m];
-    b[m] = row_b[sub_step * (SPS / 4) + m];
+    const unsigned int joined = ((row_a[m] & lmask4) << 4) + (row_b[m] & rmask4);
+    memcpy(image + 4u * m, &joined, 4);
   }
-  return pllhip_fused_pair_index<SPS>(a, b, lmask4, rmask4, lane / (64u / SPS));
+  return pllhip_fused_index_of_image<SPS>(image, 0u, sub_step, lane);
 }
 
 extern "C" unsigned int pllhip_fused_pair_index_dry(const unsigned int * row_a, const unsigned int * row_b, unsigned int lmask4,
@@ -2042,4 +2060,29 @@ extern "C" unsigned int pllhip_fused_pair_index_dry(const unsigned int * row_a, 
     case 32: return pair_index_dry<32>(row_a, row_b, lmask4, rmask4, sub_step, lane);
     default: return ~0u;
   }
+}
+
+// The index rule itself (pllhip_fused_index, partials_fused.hpp; tests/test_host_gather_index.py): for the gather a
+// character word `ch` describes, out3 = {the byte offset lane `lane` reads of the wave's batch block for sub-step
+// `sub_step`, the bytes it reads there, the table index it forms of the value `raw` read there}.  0, or 1 for arguments
+// no kernel instance has (the wide form at 4 sites per sub-step: the instances of 8 rate categories never defer).
+extern "C" int pllhip_fused_index_dry(unsigned int ch, unsigned int sps, unsigned int sub_step, unsigned int lane, unsigned int raw,
+                                      unsigned int * out3)
+{
+  if (!out3 || lane >= 64u || sub_step >= (unsigned int)PLLHIP_FUSED_J) return 1;
+  if ((ch & PLLHIP_FUSED_CH_WIDE) && sps == 4u) return 1;
+  FusedIndexRead rd;
+  switch (sps)
+  {
+    case 4: rd = pllhip_fused_index<4>(ch, sub_step, lane); break;
+    case 8: rd = pllhip_fused_index<8>(ch, sub_step, lane); break;
+    case 16: rd = pllhip_fused_index<16>(ch, sub_step, lane); break;
+    case 32: rd = pllhip_fused_index<32>(ch, sub_step, lane); break;
+    default: return 1;
+  }
+  if (rd.offset + rd.width > PLLHIP_FUSED_BATCH_BYTES) return 1;
+  out3[0] = rd.offset;
+  out3[1] = rd.width;
+  out3[2] = rd.index(raw);
+  return 0;
 }

@@ -162,8 +162,8 @@ inline unsigned int pllhip_fused_gather_bits(bool first, bool second)
   return first && second ? 0u : first ? (PLLHIP_FUSED_CH_SHIFT4 | PLLHIP_FUSED_CH_NIBBLE) : second ? PLLHIP_FUSED_CH_NIBBLE : 0u;
 }
 
-// ---- Pair rows.  Byte n of the pair row of the ordered tip pair (a, b) is the pair-table index of site n: what
-// pllhip_fused_pair_index joins from the two tip rows.  ONE definition for the kernel that builds the rows
+// ---- Pair rows.  Byte n of the pair row of the ordered tip pair (a, b) is the pair-table index of site n, joined
+// from the two tip rows' characters.  ONE definition for the kernel that builds the rows
 // (pair_rows.hip), the list kernel's tests and the host (tests/test_host_pair_rows.py).
 __host__ __device__ constexpr unsigned char pllhip_pair_row_byte(unsigned char a, unsigned char b)
 {
@@ -175,8 +175,8 @@ __host__ __device__ constexpr unsigned int pllhip_pair_row_word(unsigned int a4,
   return ((a4 & 0x0f0f0f0fu) << 4) | (b4 & 0x0f0f0f0fu);
 }
 
-// ---- What k_dna_fused does on the scalar side: integer code on wave masks and on wave-uniform words, no lane values.
-// Plain C++, so the host runs the very functions (pllhip_fused_group_mask_dry, pllhip_fused_pair_index_dry;
+// ---- What k_dna_fused does on the scalar side: integer code on wave masks, no lane values.
+// Plain C++, so the host runs the very functions (pllhip_fused_group_mask_dry, pllhip_fused_entry_bit_dry;
 // tests/test_host_scalar_masks.py).
 
 // The scaling rule's "all entries of the site (of the rate) are below the threshold" as mask arithmetic.  `below`: bit
@@ -219,59 +219,11 @@ __host__ __device__ constexpr unsigned int pllhip_fused_entry_shift(unsigned int
   return (t % (64u / GW)) * GW + t / (64u / GW);
 }
 
-// A site's byte of the SPS / 4 words that hold a sub-step's pair-table indices (wave-uniform words; `site` the lane's).
-template <unsigned int SPS>
-__host__ __device__ constexpr unsigned int pllhip_fused_pick_index(const unsigned int (&joined)[SPS / 4], unsigned int site)
-{
-  static_assert(SPS == 4 || SPS == 8 || SPS == 16 || SPS == 32, "sites per sub-step");
-  if constexpr (SPS == 4) return (joined[0] >> (site * 8u)) & 255u;
-  else
-  {
-    // two words at a time, a scalar register pair: eight sites are one 64-bit shift by the lane's own amount
-    unsigned long long two = 0;
-    for (unsigned int m = 0; m < SPS / 8; ++m)
-    {
-      const unsigned long long d = (unsigned long long)joined[2 * m] | ((unsigned long long)joined[2 * m + 1] << 32);
-      two = (SPS == 8 || (site >> 3) == m) ? d : two;
-    }
-    return (unsigned int)(two >> ((site & 7u) * 8u)) & 255u;
-  }
-}
-
-// The pair-table index of one site of a sub-step.  a[], b[]: the SPS / 4 words of the sub-step in the left and the
-// right tip row, four characters each (wave-uniform: v_readlane results); lmask4 / rmask4: 0x0f0f0f0f where the factor
-// has that row, else 0 (an absent tip's character is 0).  The two rows are joined word by word BEFORE anything depends
-// on the lane -- codes are below 16, so no byte carries into its neighbour --, then the site picks its word and byte
-// ONCE, for the pair.
-template <unsigned int SPS>
-__host__ __device__ constexpr unsigned int pllhip_fused_pair_index(const unsigned int (&a)[SPS / 4], const unsigned int (&b)[SPS / 4],
-                                                                   unsigned int lmask4, unsigned int rmask4, unsigned int site)
-{
-  static_assert(SPS == 4 || SPS == 8 || SPS == 16 || SPS == 32, "sites per sub-step");
-  unsigned int joined[SPS / 4] = {};
-  for (unsigned int m = 0; m < SPS / 4; ++m)
-    joined[m] = ((a[m] & lmask4) << 4) + (b[m] & rmask4); // (no common bit: + is |, and one shift-add)
-  return pllhip_fused_pick_index<SPS>(joined, site);
-}
-
-// The same index from ONE row, as gather_factor() of k_dna_fused takes it since the pair rows (pair_rows.hip): w[] the
-// SPS / 4 words of the sub-step in the row the record names (wave-uniform), mask4 / shift the record's -- 0xffffffff / 0
-// for a pair row, whose bytes already are what the join above gives; 0x0f0f0f0f / 4 for a single tip that is the
-// table's first character, 0x0f0f0f0f / 0 for one that is its second.  All of it before anything depends on the lane.
-template <unsigned int SPS>
-__host__ __device__ constexpr unsigned int pllhip_fused_row_index(const unsigned int (&w)[SPS / 4], unsigned int mask4,
-                                                                  unsigned int shift, unsigned int site)
-{
-  unsigned int shifted[SPS / 4] = {};
-  for (unsigned int m = 0; m < SPS / 4; ++m) shifted[m] = (w[m] & mask4) << shift;
-  return pllhip_fused_pick_index<SPS>(shifted, site);
-}
-
 // ---- Quad rows (quad_rows.hip).  A QUAD is a folded pair product whose two factors are both cherries: its value at a
 // site depends on the characters of four tips only, i.e. on the two pair-row bytes (pa, pb) of the site.  The distinct
 // patterns (pa << 8) | pb of an alignment are numbered in ascending order -- the CLASSES -- and a quad row holds each
 // site's class as a 16-bit number; the reader of the product gathers P . (Fa[pa] . Fb[pb]) from a per-call table of one
-// entry per class instead of forming it.  ONE definition for the builder, the list kernel's pick and the host tests.
+// entry per class instead of forming it.  ONE definition for the builder, the list kernel's index rule (below) and the host tests.
 #define PLLHIP_QUAD_MAX_CLASSES 1024u
 #define PLLHIP_FUSED_CH_WIDE (1u << 21)                /* the gather names a quad row: 16 bits per site, two lane positions per
                                                           row granule; in chars2 .. chars4, bits 24-31: tables the gathers before
@@ -299,33 +251,50 @@ __host__ __device__ inline unsigned int pllhip_quad_row_class(const unsigned cha
 {
   return *reinterpret_cast<const unsigned short *>(row + pllhip_quad_row_offset(n, stride));
 }
-// Word m (two sites) of sub-step j of a tile in a wave's character registers: the lane position behind the row's first
-// (lpr: lanes per plane of a tile) and the word of that lane's four.
-template <unsigned int SPS>
-__host__ __device__ constexpr unsigned int pllhip_quad_word_lane(unsigned int j, unsigned int m, unsigned int lpr)
+
+// ---- The index rule.  A wave keeps its tile's character batch in LDS: PLLHIP_FUSED_BATCH_BYTES, lane position p's 16
+// bytes at byte 16 p, as the one load of a tile fetched them -- so a byte row's TS bytes lie in a piece from 16 pos on,
+// a quad row's two planes as two pieces, the second (lanes per row) x 16 bytes behind the first.  What lane `lane` reads
+// of that block for sub-step j of the gather a record's character word `ch` describes, and the table index it forms of
+// it: ONE definition for gather_factor() of k_dna_fused, the host (pllhip_fused_index_dry, tests/test_host_gather_index.py)
+// and the older dry entry points (pllhip_fused_row_index_dry, pllhip_fused_pair_index_dry, pllhip_fused_quad_pick_dry).
+// Both forms read the ALIGNED 16 bits that hold the lane's entry -- a quad row's class whole, a byte row's byte as one
+// half of them (`drop`: 0 or 8 bits below it) --, so that the kernel has one read instruction and no branch between the
+// forms: they differ in numbers only.  The offset is the row's wave-uniform 16 pos plus a number of the lane's that
+// never changes; the second sub-step's is the first's plus a constant.
+#define PLLHIP_FUSED_BATCH_BYTES 1024u
+struct FusedIndexRead
 {
-  return (((j * SPS + 2u * m) >> 3) & 1u) * lpr + ((j * SPS + 2u * m) >> 4);
-}
+  unsigned int offset;            // byte offset into the wave's batch block (even)
+  unsigned int width;             // bytes the lane reads there (2)
+  unsigned int drop, mask, shift; // index = ((what was read >> drop) & mask) << shift: the entry's field, put in its place
+  __host__ __device__ constexpr unsigned int field(unsigned int raw) const { return (raw >> drop) & mask; }
+  __host__ __device__ constexpr unsigned int index(unsigned int raw) const { return field(raw) << shift; }
+};
 template <unsigned int SPS>
-__host__ __device__ constexpr unsigned int pllhip_quad_word_of_lane(unsigned int j, unsigned int m)
-{
-  return ((j * SPS + 2u * m) & 7u) >> 1;
-}
-// A site's class out of the SPS / 2 words of its sub-step (wave-uniform words; `site` the lane's).
-template <unsigned int SPS>
-__host__ __device__ constexpr unsigned int pllhip_quad_pick(const unsigned int (&w)[SPS / 2], unsigned int site)
+__host__ __device__ constexpr FusedIndexRead pllhip_fused_index(unsigned int ch, unsigned int j, unsigned int lane)
 {
   static_assert(SPS == 4 || SPS == 8 || SPS == 16 || SPS == 32, "sites per sub-step");
-  // (two words at a time, a scalar register pair: four sites are one 64-bit shift by the lane's own amount --
-  // pllhip_fused_pick_index with 16-bit entries)
-  unsigned long long two = 0;
-  for (unsigned int m = 0; m < SPS / 4; ++m)
-  {
-    const unsigned long long d = (unsigned long long)w[2 * m] | ((unsigned long long)w[2 * m + 1] << 32);
-    two = (SPS == 4 || (site >> 2) == m) ? d : two;
-  }
-  return (unsigned int)(two >> ((site & 3u) * 16u)) & 0xffffu;
+  constexpr unsigned int TS = PLLHIP_FUSED_J * SPS, LPR = TS >= 16 ? TS / 16 : 1;
+  // (the lane's site of sub-step 0, and what a sub-step adds: site j SPS + s lies j `step` bytes behind site s in both
+  // forms, and in the same half of its 16 bits -- SPS is even)
+  const unsigned int site = lane / (64u / SPS);
+  const bool wide = (ch & PLLHIP_FUSED_CH_WIDE) != 0u;
+  const unsigned int first = wide ? (unsigned int)pllhip_quad_row_offset(site, LPR * 16u) : site & ~1u;
+  const unsigned int step = wide ? (unsigned int)pllhip_quad_row_offset(SPS, LPR * 16u) : SPS;
+  return {PLLHIP_FUSED_CH_LPOS(ch) * 16u + first + j * step, 2u, wide ? 0u : (site & 1u) * 8u,
+          wide ? 0xffffu : (ch & PLLHIP_FUSED_CH_NIBBLE) ? 15u : 255u, !wide && (ch & PLLHIP_FUSED_CH_SHIFT4) ? 4u : 0u};
 }
+// ... applied to an image of the block (the host's dry entry points; the kernel reads its LDS)
+template <unsigned int SPS>
+inline unsigned int pllhip_fused_index_of_image(const unsigned char * image, unsigned int ch, unsigned int j, unsigned int lane)
+{
+  const FusedIndexRead rd = pllhip_fused_index<SPS>(ch, j, lane);
+  unsigned int raw = 0;
+  for (unsigned int b = 0; b < rd.width; ++b) raw |= (unsigned int)image[rd.offset + b] << (8u * b);
+  return rd.index(raw);
+}
+
 // The ONE rule for whether a folded product is read as a quad (pllhip_launch_fused and pllhip_fused_quad_rule_dry).
 // 0: taken; else why not.  n: the classes of its quad row (0: not counted -- beyond the cap); `scales`: the folded op
 // has a scale buffer, and then `bound`, a lower bound on every entry of the table that needs no device (<= 0: none),

@@ -469,16 +469,16 @@ extern "C" unsigned int pllhip_quad_row_class_dry(const unsigned char * row, uns
   return pllhip_quad_row_class(row, (size_t)site, (size_t)stride);
 }
 
-// What gather_factor() of k_dna_fused takes from a quad row: lanes[] the 16-byte character registers of the lanes that
-// hold the row's tile, plane 0's first (four words each), as the wave fetched them.
+// What gather_factor() of k_dna_fused takes from a quad row: lanes[] the 16-byte character granules of the lane positions
+// that hold the row's tile, plane 0's first (four words each), as the wave fetched them -- the index rule
+// (pllhip_fused_index, partials_fused.hpp) in its wide form, on a batch image that holds them from position 0 on.
 template <unsigned int SPS>
 static unsigned int quad_pick_dry(const unsigned int * lanes, unsigned int sub_step, unsigned int lane)
 {
   constexpr unsigned int TS = PLLHIP_FUSED_J * SPS, LPR = TS >= 16 ? TS / 16 : 1;
-  unsigned int w[SPS / 2];
-  for (unsigned int m = 0; m < SPS / 2; ++m)
-    w[m] = lanes[4u * pllhip_quad_word_lane<SPS>(sub_step, m, LPR) + pllhip_quad_word_of_lane<SPS>(sub_step, m)];
-  return pllhip_quad_pick<SPS>(w, lane / (64u / SPS));
+  unsigned char image[PLLHIP_FUSED_BATCH_BYTES] = {};
+  memcpy(image, lanes, 2u * LPR * 16u);
+  return pllhip_fused_index_of_image<SPS>(image, PLLHIP_FUSED_CH_WIDE, sub_step, lane);
 }
 extern "C" unsigned int pllhip_fused_quad_pick_dry(const unsigned int * lanes, unsigned int sps, unsigned int sub_step, unsigned int lane)
 {
