@@ -1681,6 +1681,17 @@ PLL_EXPORT int pll_amd_quad_product_stats(pll_partition_t * partition, unsigned 
  * for them, folded CLVs materialised}; pll_amd_quad_product_stats counts them with the walked ones. */
 PLL_EXPORT int pll_amd_set_quad_fold(pll_partition_t * partition, int on);
 PLL_EXPORT int pll_amd_quad_fold_stats(pll_partition_t * partition, unsigned long long * stats4);
+/* Table reuse (pllhip.h: pllhip_set_table_reuse): a pll_update_partials with the op list of the call before it -- a
+ * replayed list -- builds a pair or quad table again only where pll_update_prob_matrices or pll_core_update_pmatrix's
+ * upload has written a matrix the table is made of since it was last built; results are bit for bit what they are
+ * without.  On by default; 0 builds every table on every call.  stats4: {table jobs run, table jobs skipped, table
+ * launches made, table launches skipped}. */
+PLL_EXPORT int pll_amd_set_table_reuse(pll_partition_t * partition, int on);
+PLL_EXPORT int pll_amd_table_reuse_stats(pll_partition_t * partition, unsigned long long * stats4);
+/* TEST ONLY, no part of the interface a client builds on: the table jobs of the list that would be replayed and the
+ * matrices each names (pllhip.h: pllhip_table_jobs) */
+PLL_EXPORT int pll_amd_table_jobs(pll_partition_t * partition, unsigned int * kinds, unsigned int * mats,
+                                  unsigned int cap, unsigned int * njobs);
 /* Edge log-likelihood terms from the 4-state whole-list launch (pllhip.h: pllhip_set_edge_fold): after
  * pll_compute_edge_loglikelihood at an inner-inner edge, the next pll_update_partials that writes one of the edge's two
  * CLVs also forms the edge's per-site terms, and the same evaluation then only sums them -- bit for bit the value it

@@ -359,6 +359,36 @@ PLLHIP_EXPORT int pllhip_quad_product_stats(pllhip_ctx_t * ctx, unsigned long lo
  * materialised}; pllhip_quad_product_stats counts the folded parents with the walked ones. */
 PLLHIP_EXPORT int pllhip_set_quad_fold(pllhip_ctx_t * ctx, int on);
 PLLHIP_EXPORT int pllhip_quad_fold_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+/* Table reuse.  The pair and quad tables a 4-state whole-list launch gathers from depend on the
+ * P-matrices their jobs name (and on kept tables and class patterns that cannot change while the kept plan stands), not
+ * on the sites.  The context stamps every write of a matrix (pllhip_update_pmatrices, pllhip_put_pmatrix) with a clock;
+ * a launch of the kept plan -- the same op list again -- builds only the tables of the jobs one of whose matrices was
+ * written since the plan's tables were last built, and makes neither table launch where there is none.  A new plan
+ * builds every table.  The bytes written are those every launch wrote before.
+ * pllhip_set_table_reuse(ctx, 0): every launch builds every table; 1: the default.
+ * pllhip_table_reuse_stats: {table jobs run, table jobs skipped, table launches made, table launches skipped}, added
+ * over a group's shards (a quad's two records are one job). */
+PLLHIP_EXPORT int pllhip_set_table_reuse(pllhip_ctx_t * ctx, int on);
+PLLHIP_EXPORT int pllhip_table_reuse_stats(pllhip_ctx_t * ctx, unsigned long long * out4);
+/* TEST ONLY (tests/test_gpu_table_reuse.py; may change with the plan's encoding): what the table jobs of the kept plan
+ * read, in the form pllhip_table_reuse_dry takes: *njobs records (0: no kept plan), the first `cap` of them into
+ * kinds[cap] and mats[cap][7] (either may be NULL: the count alone).  A group answers for its first shard. */
+PLLHIP_EXPORT int pllhip_table_jobs(pllhip_ctx_t * ctx, unsigned int * kinds, unsigned int * mats, unsigned int cap,
+                                    unsigned int * njobs);
+/* Host logic, no device (tests/test_host_table_reuse.py): the staleness rule a launch of the kept plan applies.
+ * kinds[njobs]: the job records' kinds, 0 - 3 a pair table, 4 a quad with its second record, kind 5, right behind it;
+ * mats[njobs][7]: the matrix indices each names (a pair job: lmat, rmat, pmat; a quad: cherry a's two tip matrices,
+ * cherry b's, the matrices a's and b's factors are read with, the reader's; 0xffffffff: none, 0xfffffffe: a matrix the
+ * clock does not cover -- always stale; a record of kind 5 names none); written[nmats]: the clock at each matrix's last
+ * write; built: the clock the tables were last built at; all: every job is stale (a new plan).  mask_out[16]: bit i
+ * set where job record i runs (1024 records; a longer list runs all or nothing); out4 = {jobs run, jobs skipped, 1:
+ * the pair-table launch is made, 1: the quad-table launch is made}.  Returns 0, or 1 for arguments out of range.
+ * pllhip_pmat_stamp_dry (test only, like every _dry entry point): a write of matrix idx as both writers stamp it (*clock moves on, written[idx] takes it). */
+PLLHIP_EXPORT int pllhip_table_reuse_dry(const unsigned int * kinds, const unsigned int * mats, unsigned int njobs,
+                                         const unsigned long long * written, unsigned int nmats, unsigned long long built,
+                                         int all, unsigned long long * mask_out, unsigned int * out4);
+PLLHIP_EXPORT int pllhip_pmat_stamp_dry(unsigned long long * written, unsigned int nmats, unsigned long long * clock,
+                                        unsigned int idx);
 /* Host logic, no device (tests/test_host_quad_fold.py): pllhip_fused_plan_dry_quad_products, then -- fold_on -- the quad
  * fold the launch applies behind it.  qfolded_out[i] = 1: op i of the list is a quad product folded into its reader;
  * *walked_out: the ops the kernel walks; products_out / *bytes_out as there, of the plan that is launched (a folded

@@ -396,6 +396,7 @@ extern "C" int pllhip_ctx_create(const pllhip_shape_t * shape, pllhip_ctx_t ** o
     c->clv[i] = c->clv_arena + (size_t)(i - first) * c->clv_stride;
   if ((rc = dev_alloc(&c->pmatrix, (size_t)shape->prob_matrices * c->pmat_elems, true,
                       c->stream))) goto fail;
+  c->pmat_written.assign(shape->prob_matrices, 0ull); // (table reuse: no matrix written yet)
   if ((rc = dev_alloc(&c->eigenvals, (size_t)shape->rate_matrices * S, true, c->stream))) goto fail;
   if ((rc = dev_alloc(&c->eigenvecs, (size_t)shape->rate_matrices * S * S, true, c->stream))) goto fail;
   if ((rc = dev_alloc(&c->inv_eigenvecs, (size_t)shape->rate_matrices * S * S, true, c->stream))) goto fail;
@@ -821,6 +822,7 @@ extern "C" int pllhip_put_pmatrix(pllhip_ctx_t * c, unsigned int idx, const doub
   PLLHIP_ALL_SHARDS(c, pllhip_put_pmatrix(s, idx, h));
   PLLHIP_CERT_FIRST(c);
   if (idx >= c->sh.prob_matrices) { pllhip_set_error("pllhip_put_pmatrix: index %u", idx); return -1; }
+  pllhip_pmat_stamp(c, idx); // (table reuse, ctx.hpp: the write clock)
   // (a matrix written by this route: the host claims no bound for it -- no quad stands on it, quad_rows.hip)
   if (idx < c->pmat_min_entry.size() && c->pmat_min_entry[idx] != 0.0)
   {

@@ -72,6 +72,21 @@ struct pllhip_replicates
   unsigned int count, width;
 };
 
+// What a table job of the 4-state whole-list launch reads (table reuse, pllhip_ctx::fused_last_job_reads): its kind
+// (FusedPairJob, partials_fused.hpp; a quad is its record of kind 4 with that of kind 5 behind it, which is no job of
+// its own) and the indices of the P-matrices it names -- a pair job {lmat, rmat, pmat}, a quad {a's two tip matrices,
+// b's two, the matrices a's and b's factors are read with, the reader's}.  PLLHIP_JOB_MAT_NONE: the position names
+// none (a side read from a kept table names no tip matrix); PLLHIP_JOB_MAT_UNKNOWN: a matrix outside the arena, which
+// nobody stamps -- the job is always stale.
+#define PLLHIP_JOB_MATS 7
+#define PLLHIP_JOB_MAT_NONE 0xffffffffu
+#define PLLHIP_JOB_MAT_UNKNOWN 0xfffffffeu
+struct FusedJobReads
+{
+  unsigned int kind;
+  unsigned int mat[PLLHIP_JOB_MATS];
+};
+
 struct pllhip_ctx
 {
   pllhip_shape_t sh;
@@ -209,6 +224,19 @@ struct pllhip_ctx
   unsigned int fused_last_quads_refused_by_bound = 0; // quads the kept plan lost to a bound: a better one plans again
   unsigned int fused_last_quad_jobs = 0;       // table jobs of kind 4 in the kept plan (0: no k_dna_quad_tables launch)
   unsigned long long quad_list_stats[3] = {0, 0, 0}; // quads read as tables: in the last planned list, its wide gathers, in all
+  // ---- table reuse (partials_fused.hpp: pllhip_fused_stale_jobs; DESIGN.md 2.0 "Table reuse", 8.4i): a replay of the
+  // kept plan rebuilds a pair or quad table only where a P-matrix its job names was written since the plan's tables
+  // were last built.  The write clock: pmat_clock counts the writes, pmat_written[m] is its value at matrix m's last
+  // one (0: never) -- stamped by the two writers of the arena, pllhip_update_pmatrices and pllhip_put_pmatrix
+  // (pllhip_pmat_stamp).  The kept plan keeps what each of its jobs reads and the clock its tables were built at;
+  // pllhip_tables_mark_stale: the next launch builds them all.
+  unsigned long long pmat_clock = 0;
+  std::vector<unsigned long long> pmat_written;     // per matrix index (sized with the arena: pllhip_ctx_create)
+  std::vector<FusedJobReads> fused_last_job_reads; // per job record of the kept plan
+  unsigned long long fused_tables_clock = 0;        // pmat_clock when the kept plan's tables were last built
+  bool fused_tables_all_stale = true;
+  bool table_reuse = true;                          // pllhip_set_table_reuse
+  unsigned long long table_reuse_stats[4] = {0, 0, 0, 0}; // jobs run, jobs skipped, table launches made, skipped
   // ---- unstored CLVs (deferred.hip): a parent CLV that a 4-state whole-list launch did not store is
   // DEFINED by what its record names until somebody other than a list kernel needs the bytes -- every such entry point
   // materialises what it touches first (PLLHIP_DEFERRED_* below).  ONE record for every kind; the planner fills it
@@ -556,6 +584,22 @@ static inline double * pllhip_pmat_ptr(const pllhip_ctx * c, unsigned int idx)
 {
   return c->pmatrix + (size_t)idx * c->pmat_elems;
 }
+
+// Table reuse (pllhip_ctx::pmat_clock).  A write of matrix idx: the clock moves on and the matrix takes its value --
+// the rule itself, over arrays (pllhip_pmat_stamp_dry: tests/test_host_table_reuse.py).  An index out of range stamps
+// nothing.
+static inline void pllhip_pmat_stamp_at(unsigned long long * written, unsigned int nmats, unsigned long long * clock, unsigned int idx)
+{
+  if (idx < nmats) written[idx] = ++*clock;
+}
+static inline void pllhip_pmat_stamp(pllhip_ctx * c, unsigned int idx)
+{
+  pllhip_pmat_stamp_at(c->pmat_written.data(), (unsigned int)c->pmat_written.size(), &c->pmat_clock, idx);
+}
+// Every table of the kept plan is built again by the next launch: a new plan, or whatever a plan's validity
+// (layout_epoch, defer_epoch) does not cover may have touched d_pairtab, the pools of kept tables or a quad row's
+// class patterns.
+static inline void pllhip_tables_mark_stale(pllhip_ctx * c) { c->fused_tables_all_stale = true; }
 
 // Cache policy of the streaming kernels.  While all CLVs of the partition together fit
 // the 256 MiB Infinity Cache, the default policy keeps a parent written by one op on die

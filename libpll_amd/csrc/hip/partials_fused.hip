@@ -136,13 +136,15 @@ __device__ __forceinline__ unsigned int rec_pcnt(const Rec & r) { return r.w[15]
 // tables of a / b where they were deferred by an earlier call, else null}.
 // A launch of its own behind k_dna_pair_tables, made only for a list that reads a quad: the lists without one keep
 // their table launch as it was, registers and all.  One thread per (rate, state) of a class, PLLHIP_QUAD_TABLE_WGS
-// workgroups per job over the same job array; a workgroup of any other job ends at once.
+// workgroups per job over the same job array; a workgroup of any other job ends at once, and so does one of a quad
+// whose table is still good (`stale`, partials_fused.hpp: pllhip_fused_stale_jobs -- a scalar test of a kernel argument).
 constexpr unsigned int PLLHIP_QUAD_TABLE_WGS = 16;
 template <int RC>
-__global__ __launch_bounds__(256) void k_dna_quad_tables(const FusedPairJob * __restrict__ jobs, unsigned int njobs)
+__global__ __launch_bounds__(256) void k_dna_quad_tables(const FusedPairJob * __restrict__ jobs, unsigned int njobs,
+                                                         const FusedStaleMask stale)
 {
   const unsigned int i = blockIdx.x / PLLHIP_QUAD_TABLE_WGS, part = blockIdx.x % PLLHIP_QUAD_TABLE_WGS;
-  if (i + 1 >= njobs || jobs[i].kind != 4) return;
+  if (i + 1 >= njobs || !pllhip_fused_job_runs(stale, i) || jobs[i].kind != 4) return;
   constexpr unsigned int ROW = RC * 4u, PER = 256u / ROW;
   const unsigned int ki = threadIdx.x % ROW, sub = threadIdx.x / ROW, rate4 = (ki >> 2) * 4u;
   const FusedPairJob & ja = jobs[i], & jb = jobs[i + 1];
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(256) void k_dna_quad_tables(const FusedPairJob * __
 // the set of counters of the launch BEHIND it, two sets in turn, and this launch no longer does)
 template <int RC>
 __global__ __launch_bounds__(256) void k_dna_pair_tables(const FusedPairJob * __restrict__ jobs, unsigned int njobs,
-                                                         unsigned int * __restrict__ tile_counters)
+                                                         unsigned int * __restrict__ tile_counters, const FusedStaleMask stale)
 {
   // (round 6: four workgroups per job, a quarter of the 256 pairs each -- the launch is a chain of latencies, and
   // thirty-odd workgroups of sixteen rounds each left the device empty for 10 us ahead of every list; a thread reads
@@ -210,6 +212,8 @@ __global__ __launch_bounds__(256) void k_dna_pair_tables(const FusedPairJob * __
   const unsigned int i = blockIdx.x >> 2, quarter = blockIdx.x & 3u;
   if (blockIdx.x == 0 && tile_counters) tile_counters[threadIdx.x * 32u] = 0u;
   if (i >= njobs) return;
+  // (table reuse: a job whose table is still good -- no matrix it names was written since it was built)
+  if (!pllhip_fused_job_runs(stale, i)) return;
   // (kinds 4 and 5, a quad's table: k_dna_quad_tables above)
   if (jobs[i].kind >= 4) return;
   // Deferred cherries: the factor a READER with matrix P takes from a cherry that is not stored,
@@ -1594,6 +1598,42 @@ static void fused_encode(const FusedEncodeIn & in, const std::vector<std::vector
   if (keep_jobs) out.jobs.insert(out.jobs.end(), keep_jobs->begin(), keep_jobs->end());
 }
 
+// What every table job of an encoded plan reads (ctx.hpp: FusedJobReads), for the staleness rule of a replay: a matrix
+// by its index in the arena (the idiom of fused_pick_quads' bounds_of), as the kernels above read them -- a quad's side
+// that comes from a kept table names no tip matrix, a job of kind 3 only the reader's.
+static void fused_job_reads(const pllhip_ctx * c, const std::vector<FusedPairJob> & jobs, std::vector<FusedJobReads> & out)
+{
+  auto index_of = [&](const double * m) {
+    if (!m) return PLLHIP_JOB_MAT_NONE;
+    const size_t idx = m >= c->pmatrix ? (size_t)(m - c->pmatrix) / c->pmat_elems : ~(size_t)0;
+    return idx < c->sh.prob_matrices ? (unsigned int)idx : PLLHIP_JOB_MAT_UNKNOWN;
+  };
+  out.assign(jobs.size(), FusedJobReads());
+  for (size_t i = 0; i < jobs.size(); ++i)
+  {
+    const FusedPairJob & j = jobs[i];
+    FusedJobReads & r = out[i];
+    r.kind = (unsigned int)j.kind;
+    for (unsigned int & m : r.mat) m = PLLHIP_JOB_MAT_NONE;
+    if (j.kind == 5ull) continue; // (read with the record of kind 4 ahead of it)
+    if (j.kind == 4ull)
+    {
+      // (a quad without its second record is never run: k_dna_quad_tables)
+      if (i + 1 >= jobs.size()) continue;
+      const FusedPairJob & b = jobs[i + 1];
+      if (!b.copy) { r.mat[0] = index_of(j.lmat); r.mat[1] = index_of(j.rmat); }
+      if (!b.pad) { r.mat[2] = index_of(b.lmat); r.mat[3] = index_of(b.rmat); }
+      r.mat[4] = index_of(b.pmat);
+      r.mat[5] = index_of(b.kept);
+      r.mat[6] = index_of(j.pmat);
+      continue;
+    }
+    if (j.kind != 3ull) r.mat[0] = index_of(j.lmat);
+    if (j.kind == 1ull || j.kind == 2ull) r.mat[1] = index_of(j.rmat);
+    if (j.kind >= 2ull) r.mat[2] = index_of(j.pmat);
+  }
+}
+
 // (c) Upload: the staging and device buffers grown where they must be, the five arrays at their offsets, and what a
 // repeated call with the same op list needs (pllhip_relaunch_fused).
 static int fused_upload(pllhip_ctx * c, const FusedEncoded & enc)
@@ -1640,6 +1680,8 @@ static int fused_upload(pllhip_ctx * c, const FusedEncoded & enc)
   c->fused_last_jobs_offset = jobs_at;
   c->fused_last_rowtab_offset = rowtab_at;
   c->fused_last_jobs = (unsigned int)enc.jobs.size();
+  fused_job_reads(c, enc.jobs, c->fused_last_job_reads);
+  pllhip_tables_mark_stale(c); // (a new plan: its tables have never been built)
   c->fused_last_quad_jobs = 0;
   for (const FusedPairJob & j : enc.jobs) c->fused_last_quad_jobs += j.kind == 4;
   // (one wide gather per quad: pllhip_quad_list_stats)
@@ -1666,6 +1708,7 @@ static int fused_device_buffers(pllhip_ctx * c, size_t pairtab_elems, bool edge)
     HIP_TRY(hipMalloc((void **)&c->d_pairtab, pairtab_elems * sizeof(double)));
     c->pairtab_elems = pairtab_elems;
     ++c->layout_epoch;
+    pllhip_tables_mark_stale(c);
   }
   if (!c->fused_zero_row)
   {
@@ -1953,7 +1996,9 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
 
 // The device copy of the plan is still that of the previous call (same op list: the plan
 // holds buffer addresses, not values -- P-matrices, tip characters and CLVs are read when the
-// kernels run): tip tables and the list kernel again, no planning, no upload.
+// kernels run): the list kernel again, and ahead of it the tables whose matrices were written since they were last
+// built (all of them for a plan just uploaded; none, and no table launch, where nothing was written) -- no planning,
+// no upload.
 int pllhip_relaunch_fused(pllhip_ctx * c)
 {
   const unsigned int count = c->fused_last_count, nslots = c->fused_last_nslots, njobs = c->fused_last_jobs; // (count: segment 0's)
@@ -1968,30 +2013,47 @@ int pllhip_relaunch_fused(pllhip_ctx * c)
                             (const FusedSrc *)(static_cast<const char *>(c->d_plan) + c->fused_last_srcs_offset),
                             (const FusedSeg *)(static_cast<const char *>(c->d_plan) + c->fused_last_segs_offset),
                             c->fused_last_nsegs};
-  if (njobs)
+  // Table reuse: the jobs whose matrices were written since this plan's tables were last built -- all of them for a new
+  // plan (fused_upload) or with reuse off; a launch none of whose jobs runs is not made.  The tables count as built
+  // at this clock: a later write of a matrix makes its readers stale again.  (Should a launch below fail, everything
+  // is built again by the next one.)
+  FusedStaleMask stale;
+  unsigned int runs[4];
+  pllhip_fused_stale_jobs(c->fused_last_job_reads.data(), njobs, c->pmat_written.data(), (unsigned int)c->pmat_written.size(),
+                          c->fused_tables_clock, c->fused_tables_all_stale || !c->table_reuse, stale, runs);
+  pllhip_tables_mark_stale(c);
+  if (runs[2])
   {
     switch (c->sh.rate_cats)
     {
-      case 1: k_dna_pair_tables<1><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr); break;
-      case 2: k_dna_pair_tables<2><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr); break;
-      case 8: k_dna_pair_tables<8><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr); break;
-      default: k_dna_pair_tables<4><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr); break;
+      case 1: k_dna_pair_tables<1><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr, stale); break;
+      case 2: k_dna_pair_tables<2><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr, stale); break;
+      case 8: k_dna_pair_tables<8><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr, stale); break;
+      default: k_dna_pair_tables<4><<<4 * njobs, 256, 0, c->stream>>>(d_jobs, njobs, nullptr, stale); break;
     }
     HIP_TRY(hipGetLastError());
   }
-  if (c->fused_last_quad_jobs)
+  if (runs[3])
   {
     // (only the instances that fold have quads: fused_pick_quads)
     const unsigned int nwg = PLLHIP_QUAD_TABLE_WGS * njobs;
     switch (c->sh.rate_cats)
     {
-      case 1: k_dna_quad_tables<1><<<nwg, 256, 0, c->stream>>>(d_jobs, njobs); break;
-      case 2: k_dna_quad_tables<2><<<nwg, 256, 0, c->stream>>>(d_jobs, njobs); break;
-      case 4: k_dna_quad_tables<4><<<nwg, 256, 0, c->stream>>>(d_jobs, njobs); break;
+      case 1: k_dna_quad_tables<1><<<nwg, 256, 0, c->stream>>>(d_jobs, njobs, stale); break;
+      case 2: k_dna_quad_tables<2><<<nwg, 256, 0, c->stream>>>(d_jobs, njobs, stale); break;
+      case 4: k_dna_quad_tables<4><<<nwg, 256, 0, c->stream>>>(d_jobs, njobs, stale); break;
       default: pllhip_set_error("quad tables: %u categories", c->sh.rate_cats); return -1;
     }
     HIP_TRY(hipGetLastError());
   }
+  c->fused_tables_all_stale = false;
+  c->fused_tables_clock = c->pmat_clock;
+  // (a launch the plan would make at all: the pair launch where it has a job, the quad launch where it has a quad)
+  const unsigned int would = (njobs > c->fused_last_quad_jobs * 2u ? 1u : 0u) + (c->fused_last_quad_jobs ? 1u : 0u);
+  c->table_reuse_stats[0] += runs[0];
+  c->table_reuse_stats[1] += runs[1];
+  c->table_reuse_stats[2] += runs[2] + runs[3];
+  c->table_reuse_stats[3] += would - (runs[2] + runs[3]);
   switch (c->sh.rate_cats)
   {
     case 1: return launch_fused_rc<1>(c, d_plan, bases, count, nslots, mode, c->fused_last_edge);
@@ -1999,6 +2061,80 @@ int pllhip_relaunch_fused(pllhip_ctx * c)
     case 8: return launch_fused_rc<8>(c, d_plan, bases, count, nslots, mode, c->fused_last_edge);
     default: return launch_fused_rc<4>(c, d_plan, bases, count, nslots, mode, c->fused_last_edge);
   }
+}
+
+// Table reuse on or off (A/B, tests; on by default).  Off: every launch of a kept plan builds every table, as every
+// launch did before.  Either way the next launch builds them all.
+extern "C" int pllhip_set_table_reuse(pllhip_ctx_t * c, int on)
+{
+  pllhip_edge_terms_drop(c);
+  PLLHIP_ALL_SHARDS(c, pllhip_set_table_reuse(s, on));
+  c->table_reuse = on != 0;
+  pllhip_tables_mark_stale(c);
+  return 0;
+}
+
+// {table jobs run, table jobs skipped, table launches made, table launches skipped}, added over a group's shards
+extern "C" int pllhip_table_reuse_stats(pllhip_ctx_t * c, unsigned long long * out4)
+{
+  for (int t = 0; t < 4; ++t) out4[t] = 0;
+  auto add = [&](const pllhip_ctx * s) {
+    for (int t = 0; t < 4; ++t) out4[t] += s->table_reuse_stats[t];
+  };
+  if (c->shards.empty()) add(c);
+  for (const pllhip_ctx * s : c->shards) add(s);
+  return 0;
+}
+
+// What the kept plan's table jobs read, as the rule above is given it (tests: the jobs a write must make stale).  A
+// group answers for its first shard: every shard plans the same list.
+extern "C" int pllhip_table_jobs(pllhip_ctx_t * c, unsigned int * kinds, unsigned int * mats, unsigned int cap, unsigned int * njobs)
+{
+  if (!njobs) return -1;
+  const pllhip_ctx * s = c->shards.empty() ? c : c->shards[0];
+  const unsigned int n = s->fused_last_ops.empty() ? 0u : (unsigned int)s->fused_last_job_reads.size();
+  *njobs = n;
+  for (unsigned int i = 0; i < n && i < cap && kinds && mats; ++i)
+  {
+    kinds[i] = s->fused_last_job_reads[i].kind;
+    memcpy(mats + (size_t)i * PLLHIP_JOB_MATS, s->fused_last_job_reads[i].mat, sizeof(s->fused_last_job_reads[i].mat));
+  }
+  return 0;
+}
+
+// The staleness rule and the write clock without a device (include/pllhip.h; tests/test_host_table_reuse.py)
+extern "C" int pllhip_table_reuse_dry(const unsigned int * kinds, const unsigned int * mats, unsigned int njobs,
+                                      const unsigned long long * written, unsigned int nmats, unsigned long long built,
+                                      int all, unsigned long long * mask_out, unsigned int * out4)
+{
+  if (!out4 || !mask_out || (njobs && (!kinds || !mats)) || (nmats && !written)) return 1;
+  std::vector<FusedJobReads> jobs(njobs);
+  for (unsigned int i = 0; i < njobs; ++i)
+  {
+    if (kinds[i] > 5u || (kinds[i] == 5u && (i == 0 || kinds[i - 1] != 4u)) || (kinds[i] == 4u && (i + 1 >= njobs || kinds[i + 1] != 5u)))
+      return 1;
+    jobs[i].kind = kinds[i];
+    for (unsigned int k = 0; k < PLLHIP_JOB_MATS; ++k)
+    {
+      const unsigned int m = mats[(size_t)i * PLLHIP_JOB_MATS + k];
+      if (m >= nmats && m != PLLHIP_JOB_MAT_NONE && m != PLLHIP_JOB_MAT_UNKNOWN) return 1;
+      jobs[i].mat[k] = m;
+    }
+  }
+  FusedStaleMask mask;
+  pllhip_fused_stale_jobs(jobs.data(), njobs, written, nmats, built, all != 0, mask, out4);
+  // (the mask as the kernels read it: pllhip_fused_job_runs of every record it holds)
+  for (unsigned int w = 0; w < PLLHIP_TABLE_MASK_WORDS; ++w) mask_out[w] = 0ull;
+  for (unsigned int i = 0; i < PLLHIP_TABLE_MASK_JOBS; ++i)
+    if (pllhip_fused_job_runs(mask, i)) mask_out[i >> 6] |= 1ull << (i & 63u);
+  return 0;
+}
+
+extern "C" int pllhip_pmat_stamp_dry(unsigned long long * written, unsigned int nmats, unsigned long long * clock, unsigned int idx)
+{
+  if (!written || !clock || idx >= nmats) return 1;
+  pllhip_pmat_stamp_at(written, nmats, clock, idx);
+  return 0;
 }
 
 // ---------------------------------------------------------------- host: the kernel's scalar-side helpers without a device

@@ -748,6 +748,52 @@ struct FusedQuadProducts
   FusedQuadFold folded;
   unsigned int nfolded = 0;
 };
+// Table reuse (DESIGN.md 2.0 "Table reuse"): which table jobs of the kept plan a launch runs.  THE staleness rule, host
+// logic over arrays (pllhip_table_reuse_dry: tests/test_host_table_reuse.py): a job is stale where `all` says so -- a new
+// plan, pllhip_tables_mark_stale, reuse switched off -- or a matrix it names was written after the tables were last
+// built (written[m] > built; PLLHIP_JOB_MAT_UNKNOWN: always).  A record of kind 5 is the second half of the quad ahead
+// of it: its matrices are in that record's reads, and it is no job.  mask: bit i set where the workgroups of job record
+// i run -- a by-value argument of both table kernels; a list of more records than it holds runs all of them or none
+// (the kernels do not test a record past the mask).  out4 = {jobs that run, jobs skipped, 1 where a job of kinds 0 - 3
+// runs: k_dna_pair_tables is launched, 1 where a quad runs: k_dna_quad_tables is}.
+constexpr unsigned int PLLHIP_TABLE_MASK_WORDS = 16u, PLLHIP_TABLE_MASK_JOBS = 64u * PLLHIP_TABLE_MASK_WORDS;
+struct FusedStaleMask
+{
+  unsigned long long w[PLLHIP_TABLE_MASK_WORDS];
+};
+inline void pllhip_fused_stale_jobs(const FusedJobReads * jobs, unsigned int njobs, const unsigned long long * written,
+                                    unsigned int nmats, unsigned long long built, bool all, FusedStaleMask & mask,
+                                    unsigned int * out4)
+{
+  auto is_stale = [&](const FusedJobReads & j) {
+    for (unsigned int m : j.mat)
+      if (m != PLLHIP_JOB_MAT_NONE && (m >= nmats || written[m] > built)) return true;
+    return false;
+  };
+  bool any = false;
+  for (unsigned int i = 0; i < njobs && !any; ++i) any = jobs[i].kind != 5u && is_stale(jobs[i]);
+  if (any && njobs > PLLHIP_TABLE_MASK_JOBS) all = true;
+  memset(&mask, 0, sizeof(mask));
+  out4[0] = out4[1] = out4[2] = out4[3] = 0u;
+  for (unsigned int i = 0; i < njobs; ++i)
+  {
+    if (jobs[i].kind == 5u) continue;
+    if (!all && !is_stale(jobs[i]))
+    {
+      ++out4[1];
+      continue;
+    }
+    ++out4[0];
+    out4[jobs[i].kind == 4u ? 3 : 2] = 1u;
+    if (i < PLLHIP_TABLE_MASK_JOBS) mask.w[i >> 6] |= 1ull << (i & 63u);
+  }
+}
+// the kernels' side of it: do the workgroups of job record i run (a scalar test of a kernel argument)
+__host__ __device__ __forceinline__ bool pllhip_fused_job_runs(const FusedStaleMask & mask, unsigned int i)
+{
+  return i >= PLLHIP_TABLE_MASK_JOBS || ((mask.w[i >> 6] >> (i & 63u)) & 1ull) != 0ull;
+}
+
 // encode and launch: one plan per segment
 int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> & plans, unsigned int nslots,
                         const std::vector<FusedPairJob> * keep_jobs = nullptr, const FusedEdge * edge = nullptr,

@@ -216,6 +216,9 @@ extern "C" int pllhip_update_pmatrices(pllhip_ctx_t * c, const unsigned int * h_
   PLLHIP_CERT_FIRST(c); // (a list that may have to run again must find the matrices it ran with)
   // (kept whether quad rows are on or off: a bound must never outlive the matrix it was formed for)
   pllhip_pmat_bounds_update(c, h_params_indices, h_matrix_indices, h_branch_lengths, count);
+  // (table reuse, ctx.hpp: the write clock -- behind the certificate's look above, so that a list it runs again is
+  // weighed against the matrices it ran with, and stamped whatever the new length is: a write is a write)
+  for (unsigned int i = 0; i < count; ++i) pllhip_pmat_stamp(c, h_matrix_indices[i]);
   return pllhip_pmatrices_to(c, c->pmatrix, c->sh.prob_matrices, h_params_indices, h_matrix_indices, h_branch_lengths,
                              count);
 }

@@ -938,6 +938,27 @@ int pll_amd_set_quad_fold(pll_partition_t * p, int on)
   return PLL_SUCCESS;
 }
 
+int pll_amd_table_reuse_stats(pll_partition_t * p, unsigned long long * stats4)
+{
+  int rc = pllhip_table_reuse_stats(pll_amd_priv(p)->ctx, stats4);
+  if (rc) return pll_amd_fail_hip(rc, "table reuse stats");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_table_jobs(pll_partition_t * p, unsigned int * kinds, unsigned int * mats, unsigned int cap, unsigned int * njobs)
+{
+  int rc = pllhip_table_jobs(pll_amd_priv(p)->ctx, kinds, mats, cap, njobs);
+  if (rc) return pll_amd_fail_hip(rc, "table jobs");
+  return PLL_SUCCESS;
+}
+
+int pll_amd_set_table_reuse(pll_partition_t * p, int on)
+{
+  int rc = pllhip_set_table_reuse(pll_amd_priv(p)->ctx, on);
+  if (rc) return pll_amd_fail_hip(rc, "set table reuse");
+  return PLL_SUCCESS;
+}
+
 int pll_amd_pair_fold_stats(pll_partition_t * p, unsigned long long * stats4)
 {
   int rc = pllhip_pair_fold_stats(pll_amd_priv(p)->ctx, stats4);

@@ -304,6 +304,10 @@ class PllLibrary:
             if hasattr(lib, "pll_amd_set_quad_fold"):
                 lib.pll_amd_set_quad_fold.argtypes = [_PP, C.c_int]
                 lib.pll_amd_quad_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
+            if hasattr(lib, "pll_amd_set_table_reuse"):
+                lib.pll_amd_set_table_reuse.argtypes = [_PP, C.c_int]
+                lib.pll_amd_table_reuse_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
+                lib.pll_amd_table_jobs.argtypes = [_PP, _up, _up, C.c_uint, _up]
             if hasattr(lib, "pll_amd_set_edge_fold"):
                 lib.pll_amd_set_edge_fold.argtypes = [_PP, C.c_int]
                 lib.pll_amd_edge_fold_stats.argtypes = [_PP, C.POINTER(C.c_ulonglong)]
@@ -1509,6 +1513,25 @@ class Partition:
         buf = (C.c_ulonglong * 4)()
         self._check(self.lib.pll_amd_quad_fold_stats(self.ptr, buf), "pll_amd_quad_fold_stats")
         return dict(zip(("live", "ops_folded", "plans", "materialised"), (int(v) for v in buf)))
+
+    def set_table_reuse(self, on):
+        """False: a replayed op list builds every pair and quad table again, whatever was written since (pll_amd.h)."""
+        self._check(self.lib.pll_amd_set_table_reuse(self.ptr, 1 if on else 0), "pll_amd_set_table_reuse")
+
+    def table_reuse_stats(self):
+        """{jobs_run, jobs_skipped, launches, launches_skipped} of the 4-state list's table launches (pll_amd.h)."""
+        buf = (C.c_ulonglong * 4)()
+        self._check(self.lib.pll_amd_table_reuse_stats(self.ptr, buf), "pll_amd_table_reuse_stats")
+        return dict(zip(("jobs_run", "jobs_skipped", "launches", "launches_skipped"), (int(v) for v in buf)))
+
+    def table_jobs(self):
+        """Test only: (kinds[n], mats[n][7]) of the table jobs of the list a repeated call would replay (pll_amd.h); 0xffffffff: none."""
+        n = C.c_uint(0)
+        self._check(self.lib.pll_amd_table_jobs(self.ptr, None, None, 0, C.byref(n)), "pll_amd_table_jobs")
+        kinds, mats = np.zeros(n.value, dtype=np.uint32), np.zeros((n.value, 7), dtype=np.uint32)
+        self._check(self.lib.pll_amd_table_jobs(self.ptr, kinds.ctypes.data_as(_up), mats.ctypes.data_as(_up), n.value, C.byref(n)),
+                    "pll_amd_table_jobs")
+        return kinds, mats
 
     def unstored_stats(self):
         """{unstored_now, ops_unstored, launches, materialised} of the 4-state pair products (pll_amd.h)."""
