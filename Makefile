@@ -20,7 +20,7 @@ CFLAGS   := -std=gnu11 -O2 -fPIC -g -Wall -Wextra -ffp-contract=off -fvisibility
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -ffp-contract=off -fvisibility=hidden \
             -Wall -Iinclude -Ilibpll_amd/csrc/hip $(EXTRA_HIPFLAGS)
 
-.PHONY: lib oracle all clean asan asan-model-score asan-nni-support asan-tree-replicates
+.PHONY: lib oracle all clean asan asan-model-score asan-nni-support asan-tree-replicates asan-simulate
 lib: $(OUT)
 all: lib oracle
 
@@ -104,6 +104,16 @@ $(ASAN_DIR)/tree_replicates_args: tools/tree_replicates_args.c $(ASAN_OBJ) $(HIP
 
 asan-tree-replicates: $(ASAN_DIR)/tree_replicates_args
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/tree_replicates_args
+
+# pll_amd_simulate_columns -- a small walk, what a byte depends on, the refusals -- the same way (stand-alone: not
+# part of `asan`)
+$(ASAN_DIR)/simulate_args: tools/simulate_args.c $(ASAN_OBJ) $(HIP_OBJ)
+	gcc $(filter-out -O2,$(CFLAGS)) $(ASAN_FLAGS) -c $< -o $(ASAN_DIR)/simulate_args.o
+	g++ $(ASAN_FLAGS) -Wl,-rpath,/opt/rocm/lib -o $@ $(ASAN_DIR)/simulate_args.o $(ASAN_OBJ) $(HIP_OBJ) \
+	    -L/opt/rocm/lib -lamdhip64 -lm -ldl
+
+asan-simulate: $(ASAN_DIR)/simulate_args
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(ASAN_DIR)/simulate_args
 
 asan: asan-model-score asan-nni-support asan-tree-replicates $(ASAN_DIR)/libpll_amd.so $(ASAN_DIR)/liboracle.so
 	LD_PRELOAD="$$(gcc -print-file-name=libasan.so) $$(gcc -print-file-name=libubsan.so)" \

@@ -1510,6 +1510,109 @@ PLL_EXPORT int pll_amd_tree_gradient(pll_partition_t * partition, const pll_utre
                                      double * d_f, double * dd_f,      /* out [2n - 3] */
                                      double * lnl);                    /* out [2n - 3] or NULL */
 
+/* ---- sequence simulation along a tree: parametric bootstrap (host/simulate.c, hip/simulate.hip) ----
+ * A column of an alignment is one walk from the root to the tips over the P-matrices.  The result is defined by the
+ * rule below; pll_amd_simulate_columns implements it in plain C without a device, pll_amd_simulate on the partition's
+ * device, with the same bits.
+ *
+ * Generator.  Philox4x32 with 10 rounds: multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and
+ * 0xBB67AE85; key = (seed low 32 bits, seed high 32 bits); counter = (column low 32, column high 32, draw id,
+ * replicate).  `column` is the 64-bit number first_column + i, `replicate` is first_replicate + r (32 bits, modulo
+ * 2^32).  From the four output words w0..w3 two uniforms in [0, 1) are formed:
+ *   u_a = ((w0 >> 5) * 67108864.0 + (w1 >> 6)) / 9007199254740992.0,  u_b the same expression on w2 and w3;
+ * both are exact in double.  (pll_amd_philox4x32_10 is the generator alone.)
+ *
+ * Pick.  pick(u, p[0..m-1]) is the smallest j with u < c_j, where c_j = ((p[0] + p[1]) + ...) + p[j]: the sum is
+ * sequential in double, one rounding per addition, nothing fused.  If there is no such j, it is the largest j with
+ * p[j] > 0 (0 if no entry is positive).
+ *
+ * A column.  In this order:
+ *   1. draw id 0xFFFFFFFF: the category is k = pick(u_a, rate_weights); the column is invariant exactly when
+ *      prop_invar[params_indices[k]] > 0 and u_b < prop_invar[params_indices[k]];
+ *   2. draw id root_clv_index: the root state is pick(u_a, frequencies[params_indices[k]]);
+ *   3. if there is an edge (edge_clv_index != PLL_AMD_SIMULATE_NO_EDGE): draw id edge_clv_index, the state of that
+ *      node is pick(u_a, row state(root) of category k of P-matrix edge_matrix_index);
+ *   4. for the operations from the last to the first: child 1 -- draw id = its clv index, state = pick(u_a, row
+ *      state(parent) of category k of child1_matrix_index); child 2 the same with its own clv index and matrix;
+ *   5. in an invariant column every node takes the root's state: the draws of 3 and 4 are not used.
+ * The P-matrices are the partition's as they stand, the +I rescaling of pll_update_prob_matrices in them: the
+ * distribution of a column is exactly the site likelihood the library computes for it.  The walk takes what tree
+ * scoring takes: the list of pll_utree_traverse + pll_utree_create_operations at a node with the edge
+ * (node->clv_index, node->back->clv_index, node->pmatrix_index), or a rooted list with no edge.
+ *
+ * Output.  out[((r * node_count) + j) * column_count + i] is one byte: the state number of node node_clv_indices[j]
+ * in column i of replicate r or, where `symbols` is given (`states` characters, e.g. "ACGT"), symbols[state].
+ * Optional: column_categories[r * column_count + i] = k, column_invariant[r * column_count + i] = 0 / 1.
+ *
+ * Bits.  A byte depends on (seed, replicate, column, node, model, matrices) only: not on the range of columns or
+ * replicates asked for, the list or order of nodes, the chunking, which outputs are NULL, a repeated call, host or
+ * device.
+ *
+ * pll_amd_simulate_columns: host only, no device, no partition.  pmatrices[m] ([rate_cats][states][states]) for the
+ * matrix indices m < matrix_count the walk names (others may be NULL); frequencies[k] ([states]), rate_weights[k] and
+ * prop_invar[k] PER CATEGORY (the params indices already applied); clv indices < clv_count.  1 <= states <= 255,
+ * 1 <= rate_cats <= 64.
+ *
+ * pll_amd_simulate: the same on the partition's device with the partition's own model and matrices
+ * (params_indices: [rate_cats]).  Synchronous.  Nothing of the partition changes unless PLL_AMD_SIMULATE_INSTALL is
+ * set; scratch belongs to the partition and is kept until it is destroyed.  The (replicate, column) pairs are worked
+ * in chunks of at most about PLL_AMD_SIMULATE_SCRATCH_MB (environment, read at call time, default 2048) of scratch,
+ * 256 pairs at least.  The node states of a column are bytes in LDS while (nodes of the walk) x 256 bytes fit in 64 KB,
+ * in scratch otherwise.
+ * Flags (both: at most 32 states, a character's mask being 32 bits).  PLL_AMD_SIMULATE_KEEP_GAPS
+ * (PLL_ATTRIB_PATTERN_TIP partitions; column_count == partition->sites, first_column arbitrary; every listed tip's
+ * sequence must have been set): where the partition's current character of a listed tip at site i has all `states`
+ * bits set, the output byte is gap_symbol -- with symbols == NULL it is 255, whatever gap_symbol says -- and an install
+ * keeps the current character: the original gaps imposed on the replicate.
+ * PLL_AMD_SIMULATE_INSTALL (replicate_count == 1, column_count == partition->sites, PLL_ATTRIB_PATTERN_TIP): every
+ * tip among the nodes holds the simulated sequence afterwards, as if pll_set_tip_states had been called with the
+ * output symbols.  The character code of state s is 1 << s for 4 states, otherwise the lowest code c with
+ * tipmap[c] == 1u << s; the code must lie below partition->maxstates (the charmap exists once any tip has been set),
+ * else PLL_ERROR_PARAM_INVALID.  The codes go from the kernel to the tip rows on the device; partition->tipchars and
+ * the "tip was set" marks follow from one device-to-host copy of the codes.  With INSTALL `out` may be NULL.
+ * Checked before anything is launched (PLL_ERROR_PARAM_INVALID, outputs and partition untouched): clv, matrix and
+ * params indices in range; walking the list backwards every operation's parent already has a state, no node receives
+ * a state twice, every requested node receives one; replicate_count, column_count, node_count not 0;
+ * first_column + column_count does not wrap; no NULL array other than operations with count == 0, symbols and the
+ * two optional outputs (and out with INSTALL); the flag conditions.  PLL_ERROR_HIP_UNSUPPORTED: partitions with
+ * PLL_ATTRIB_SITE_REPEATS, with ascertainment-bias correction, sharded over devices or joined to an RCCL
+ * communicator.  PLL_ERROR_MEM_ALLOC: a chunk's scratch could not be had.  Not offered: indels, install into tip-CLV
+ * partitions, device-resident output for other calls without install.  INTEGRATION.md section 4n. */
+#define PLL_AMD_SIMULATE_NO_EDGE 0xFFFFFFFFu
+#define PLL_AMD_SIMULATE_KEEP_GAPS 1u
+#define PLL_AMD_SIMULATE_INSTALL 2u
+PLL_EXPORT void pll_amd_philox4x32_10(const unsigned int * counter /* [4] */, const unsigned int * key /* [2] */,
+                                      unsigned int * out /* [4] */);
+PLL_EXPORT int pll_amd_simulate_columns(unsigned int states, unsigned int rate_cats,
+                                        double * const * pmatrices, unsigned int matrix_count,
+                                        double * const * frequencies,     /* [rate_cats] of [states] */
+                                        const double * rate_weights,      /* [rate_cats] */
+                                        const double * prop_invar,        /* [rate_cats] */
+                                        const pll_operation_t * operations, unsigned int count,
+                                        unsigned int clv_count,
+                                        unsigned int root_clv_index, unsigned int edge_clv_index,
+                                        unsigned int edge_matrix_index,
+                                        unsigned long long seed,
+                                        unsigned int first_replicate, unsigned int replicate_count,
+                                        unsigned long long first_column, unsigned int column_count,
+                                        const unsigned int * node_clv_indices, unsigned int node_count,
+                                        const char * symbols,             /* [states] or NULL */
+                                        unsigned char * out,              /* [replicate_count][node_count][column_count] */
+                                        unsigned int * column_categories, /* [replicate_count][column_count] or NULL */
+                                        unsigned char * column_invariant);/* [replicate_count][column_count] or NULL */
+PLL_EXPORT int pll_amd_simulate(pll_partition_t * partition,
+                                const pll_operation_t * operations, unsigned int count,
+                                unsigned int root_clv_index, unsigned int edge_clv_index,
+                                unsigned int edge_matrix_index,
+                                const unsigned int * params_indices,
+                                unsigned long long seed,
+                                unsigned int first_replicate, unsigned int replicate_count,
+                                unsigned long long first_column, unsigned int column_count,
+                                const unsigned int * node_clv_indices, unsigned int node_count,
+                                unsigned int flags, const char * symbols, unsigned char gap_symbol,
+                                unsigned char * out, unsigned int * column_categories,
+                                unsigned char * column_invariant);
+
 /* Device the NEXT pll_partition_create OF THE CALLING THREAD binds to.  Kept per thread, like pll_errno
  * (pll.c:24-25) -- distinct threads may create partitions on distinct devices concurrently, as the reference lets
  * threads create partitions concurrently -- WITH a process-wide default: a thread that has not set a device uses what

@@ -864,6 +864,35 @@ PLLHIP_EXPORT int pllhip_distance_joins(pllhip_ctx_t * ctx, const unsigned int *
                                         pllhip_join_last_t * h_last);
 PLLHIP_EXPORT int pllhip_joining_kernel_ms(pllhip_ctx_t * ctx, float * ms);
 
+/* ---- sequence simulation along a tree (simulate.hip; host side host/simulate.c) ----
+ * The rule written out at pll_amd_simulate (include/pll_amd.h) on the context's device, one lane per (replicate,
+ * column), over the context's own P-matrices, frequencies, category weights and +I proportions.  The walk comes
+ * checked and compiled by the caller: step s gives node h_steps[s].node (its clv index: the draw id) a state from the
+ * state of step h_steps[s].parent (< s) over P-matrix h_steps[s].matrix; step 0 is the root (parent and matrix not
+ * read).  h_node_slots[j]: the step whose state is output row j.  draw_category 0: one category and no +I proportion,
+ * the category draw is skipped.  A preparation kernel turns the rows the walk uses into the rule's cumulative sums c_j
+ * once per call; a draw is then a search.  A column's states are bytes in LDS while step_count x 256 bytes fit in
+ * 64 KB, in scratch otherwise.  h_symbols ([states]) may be NULL.  keep_gaps: where the current code of a requested
+ * pattern tip at site i equals gap_code, the output byte is gap_symbol and an install keeps the code (column_count ==
+ * sites, the caller's to check).  h_install_codes ([states]; NULL: no install; needs replicate_count == 1,
+ * column_count == sites, pattern tips): every requested tip's row takes the codes of its states on the device, after
+ * the bookkeeping pllhip_put_tipchars does before a row changes, and h_tipchars[tip] receives them from one
+ * device-to-host copy per chunk.  h_out may be NULL with an install; h_categories and h_invariant may always be NULL.
+ * Without an install nothing of the context changes; scratch (kept by the context) is at most about scratch_bytes
+ * per chunk, 256 (replicate, column) pairs at least.  Returns -1 for a bad argument (nothing launched, outputs
+ * untouched), -2 if a chunk's scratch cannot be had, -3 for a context this call does not take (asc-bias, site
+ * repeats, sharded, RCCL). */
+typedef struct pllhip_sim_step { unsigned int node, parent, matrix; } pllhip_sim_step_t;
+PLLHIP_EXPORT int pllhip_simulate(pllhip_ctx_t * ctx, const pllhip_sim_step_t * h_steps, unsigned int step_count,
+                                  const unsigned int * h_params_indices, int draw_category, unsigned long long seed,
+                                  unsigned int first_replicate, unsigned int replicate_count,
+                                  unsigned long long first_column, unsigned int column_count,
+                                  const unsigned int * h_node_slots, unsigned int node_count,
+                                  const unsigned char * h_symbols, int keep_gaps, unsigned int gap_code,
+                                  unsigned char gap_symbol, const unsigned char * h_install_codes,
+                                  size_t scratch_bytes, unsigned char * h_out, unsigned int * h_categories,
+                                  unsigned char * h_invariant, unsigned char * const * h_tipchars);
+
 /* The planner of k_tree_score on its own -- host logic, no device needed.  The ops the edge (parent_clv, child_clv
  * with their scaler indices) does not depend on are dropped; the rest are ordered depth-first from the edge, the
  * operand that needs more live values first, and a parent takes the slot of one of its operands.  Tips (pattern_tip)

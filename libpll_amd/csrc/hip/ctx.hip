@@ -649,19 +649,28 @@ static int d2h(pllhip_ctx * c, void * dst, const void * src, size_t bytes)
   return 0;
 }
 
-extern "C" int pllhip_put_tipchars(pllhip_ctx_t * c, unsigned int tip, const unsigned char * h)
+int pllhip_tip_row_changes(pllhip_ctx * c, unsigned int tip, const char * what)
 {
   pllhip_edge_terms_drop(c); // (ctx.hpp: edge lnL terms are good only while nothing else happened)
-  PLLHIP_ALL_SHARDS(c, pllhip_put_tipchars(s, tip, h + lo));
   PLLHIP_CERT_FIRST(c);
   PLLHIP_DEFERRED_FLUSH(c); // (a deferred cherry is indexed by its tips' rows: it gets its bytes before a row changes)
   if (!c->sh.pattern_tip || tip >= c->sh.tips)
   {
-    pllhip_set_error("pllhip_put_tipchars: tip %u invalid", tip);
+    pllhip_set_error("%s: tip %u invalid", what, tip);
     return -1;
   }
   pllhip_pair_rows_tip_written(c, tip); // (pair_rows.hip: rebuilt in place before the next list launch reads them)
   pllhip_quad_rows_tip_written(c, tip); // (quad_rows.hip: counted again, and the kept plan ends)
+  return 0;
+}
+
+extern "C" int pllhip_put_tipchars(pllhip_ctx_t * c, unsigned int tip, const unsigned char * h)
+{
+  pllhip_edge_terms_drop(c); // (as every entry point that changes device state begins, a sharded context's too; the
+                             // helper's own drop then finds nothing)
+  PLLHIP_ALL_SHARDS(c, pllhip_put_tipchars(s, tip, h + lo));
+  const int rc = pllhip_tip_row_changes(c, tip, "pllhip_put_tipchars");
+  if (rc) return rc;
   return h2d(c, c->tipchars + (size_t)tip * c->tip_stride, h, c->sh.sites);
 }
 

@@ -29,7 +29,8 @@ struct pllhip_rep_work;
 // states, start lengths and results, its jobs and the pairs' tips; joining -- the working distance and variance matrices,
 // the row sums, the slots' node numbers, the scan's candidates, the step record and the joins; tree replicates -- the
 // chunk's candidates' per-site rows, per-span partial sums, its table and the running best (what the candidates
-// themselves need is tree scoring's)
+// themselves need is tree scoring's); simulation -- the cumulative rows, the walk, the chunk's outputs and, for large
+// trees, its columns' node states
 struct BatchScratch
 {
   void * p = nullptr;
@@ -47,6 +48,7 @@ enum
   BATCH_DISTANCE,
   BATCH_JOINING,
   BATCH_TREE_REPLICATES,
+  BATCH_SIMULATE,
   BATCH_FAMILIES
 };
 
@@ -535,6 +537,10 @@ int pllhip_pair_rows_resolve(pllhip_ctx * c, const std::vector<std::pair<unsigne
 int pllhip_pair_rows_refresh(pllhip_ctx * c);                       // stale rows rebuilt in place, on the stream
 void pllhip_pair_rows_tip_written(pllhip_ctx * c, unsigned int tip); // a tip row's bytes change: its pair rows are stale
 void pllhip_pair_rows_free(pllhip_ctx * c);
+// ctx.hip: what goes before the bytes of a pattern tip's row change, whoever changes them (the upload, simulate.hip's
+// install): the edge lnL terms dropped, the certificate resolved, the deferred CLVs given their bytes, the tip's pair
+// and quad rows told.  -1: no such tip row (`what` names the caller in the error text)
+int pllhip_tip_row_changes(pllhip_ctx * c, unsigned int tip, const char * what);
 // quad_rows.hip: the cached quad rows of a context (pllhip_ctx::quad_rows)
 struct QuadRowRef
 {

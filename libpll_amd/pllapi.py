@@ -132,6 +132,9 @@ ERROR_STEPWISE_TIPS = 128
 ERROR_STEPWISE_UNSUPPORTED = 129
 ERROR_HIP_UNSUPPORTED = 202
 
+SIMULATE_NO_EDGE = 0xFFFFFFFF       # pll_amd.h: PLL_AMD_SIMULATE_*
+SIMULATE_KEEP_GAPS, SIMULATE_INSTALL = 1, 2
+
 _PP = C.POINTER(PartitionStruct)
 _PARS = C.POINTER(ParsimonyStruct)
 _UN = C.POINTER(UNode)
@@ -375,6 +378,16 @@ class PllLibrary:
                 lib.pll_amd_distance_tree.argtypes = [_PP, C.c_void_p, C.c_uint, C.c_void_p, C.c_double, C.c_double,
                                                       C.c_double, C.c_uint, C.c_int] + [C.c_void_p] * 5
                 lib.pll_amd_joining_kernel_ms.argtypes = [_PP, C.POINTER(C.c_float)]
+            if hasattr(lib, "pll_amd_simulate"):
+                lib.pll_amd_philox4x32_10.restype = None
+                lib.pll_amd_philox4x32_10.argtypes = [C.c_void_p] * 3
+                lib.pll_amd_simulate_columns.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_uint] + \
+                    [C.c_void_p] * 4 + [C.c_uint] * 5 + [C.c_ulonglong, C.c_uint, C.c_uint, C.c_ulonglong, C.c_uint,
+                                                         C.c_void_p, C.c_uint] + [C.c_void_p] * 4
+                lib.pll_amd_simulate.argtypes = [_PP, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
+                                                 C.c_ulonglong, C.c_uint, C.c_uint, C.c_ulonglong, C.c_uint,
+                                                 C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_ubyte] + \
+                                                [C.c_void_p] * 3
             if hasattr(lib, "pll_amd_utree_directed"):
                 lib.pll_amd_utree_directed.argtypes = [C.c_void_p, C.c_uint, C.c_int] + [C.c_void_p] * 6
                 lib.pll_amd_branch_derivatives.argtypes = [_PP, C.c_void_p, C.c_uint, _up] + [C.c_void_p] * 4
@@ -463,6 +476,62 @@ class PllLibrary:
         if not ok:
             raise PllError("pll_amd_distance_from_counts: errno %d: %s" % (self.errno(), self.errmsg()))
         return d.value, lnl.value, ev.value, st.value
+
+    def philox4x32_10(self, counter, key):
+        """pll_amd_philox4x32_10: the four output words of one block"""
+        c = np.ascontiguousarray(counter, dtype=np.uint32).reshape(4)
+        k = np.ascontiguousarray(key, dtype=np.uint32).reshape(2)
+        out = np.zeros(4, dtype=np.uint32)
+        self.lib.pll_amd_philox4x32_10(c.ctypes.data, k.ctypes.data, out.ctypes.data)
+        return out
+
+    def simulate_columns(self, states, pmatrices, frequencies, rate_weights, prop_invar, ops, root, edge=None, seed=0,
+                         first_replicate=0, replicates=1, first_column=0, columns=1, nodes=(), symbols=None,
+                         clv_count=None, want=("categories", "invariant"), raw=None):
+        """pll_amd_simulate_columns (host only): a dict -- out uint8 [replicates][nodes][columns] and what `want`
+        names of categories (uint32) and invariant (uint8), [replicates][columns].  pmatrices: a dict or list by matrix
+        index of [rate_cats][states][states] arrays (None entries allowed); frequencies: one array per category;
+        edge: (clv index, matrix index) or None; ops: an OPS_DTYPE array.  raw: a dict of prepared output arrays to
+        write into instead (the refusal tests); returns the call's result then."""
+        w = np.ascontiguousarray(rate_weights, dtype=np.float64)
+        pinv = np.ascontiguousarray(prop_invar, dtype=np.float64)
+        R = len(w)
+        if isinstance(pmatrices, dict):
+            pmatrices = [pmatrices.get(m) for m in range(max(pmatrices) + 1)] if pmatrices else []
+        mats = [None if m is None else np.ascontiguousarray(m, dtype=np.float64) for m in pmatrices]
+        mrows = (_dp * max(len(mats), 1))(*[None if m is None else m.ctypes.data_as(_dp) for m in mats])
+        fr = [np.ascontiguousarray(f, dtype=np.float64) for f in frequencies]
+        frows = (_dp * max(R, 1))(*[f.ctypes.data_as(_dp) for f in fr])
+        ops = np.ascontiguousarray(ops, dtype=OPS_DTYPE)
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1)
+        if clv_count is None:
+            seen = [root] + ([] if edge is None else [edge[0]]) + list(nodes)
+            for f in ("parent_clv_index", "child1_clv_index", "child2_clv_index"):
+                seen += list(ops[f])
+            clv_count = int(max(seen)) + 1
+        if raw is None:
+            res = {"out": np.zeros((replicates, len(nodes), columns), dtype=np.uint8)}
+            if "categories" in want:
+                res["categories"] = np.zeros((replicates, columns), dtype=np.uint32)
+            if "invariant" in want:
+                res["invariant"] = np.zeros((replicates, columns), dtype=np.uint8)
+        else:
+            res = raw
+
+        def ptr(name):
+            return res[name].ctypes.data if res.get(name) is not None else None
+        sym = None if symbols is None else C.c_char_p(symbols if isinstance(symbols, bytes) else symbols.encode())
+        ok = self.lib.pll_amd_simulate_columns(
+            states, R, C.addressof(mrows), len(mats), C.addressof(frows), w.ctypes.data, pinv.ctypes.data,
+            ops.ctypes.data if len(ops) else None, len(ops), clv_count, root,
+            SIMULATE_NO_EDGE if edge is None else edge[0], 0 if edge is None else edge[1], seed, first_replicate,
+            replicates, first_column, columns, nodes.ctypes.data if len(nodes) else None, len(nodes),
+            C.cast(sym, C.c_void_p) if sym is not None else None, ptr("out"), ptr("categories"), ptr("invariant"))
+        if raw is not None:
+            return ok
+        if not ok:
+            raise PllError("pll_amd_simulate_columns: errno %d: %s" % (self.errno(), self.errmsg()))
+        return res
 
     def nni_support_counts(self, centre3, replicate_lnl, epsilon=0.0):
         """pll_amd_nni_support_counts (host only): (sh_count, lbp_count) of one edge's table -- centre3 the three
@@ -1192,6 +1261,44 @@ class Partition:
             ptr("evals"), ptr("status"), ptr("counts"))
         self._check(ok, "pll_amd_pairwise_distances")
         return out
+
+    def simulate(self, ops, root, edge, params_indices, seed=0, first_replicate=0, replicates=1, first_column=0,
+                 columns=None, nodes=(), flags=0, symbols=None, gap_symbol=255,
+                 want=("out", "categories", "invariant"), raw=None):
+        """pll_amd_simulate: a dict -- what `want` names of out (uint8 [replicates][nodes][columns]), categories
+        (uint32) and invariant (uint8), both [replicates][columns].  edge: (clv index, matrix index) or None;
+        columns None: the partition's sites.  raw: a dict of prepared output arrays to write into instead (the
+        refusal tests); returns the call's result then."""
+        if not hasattr(self.lib, "pll_amd_simulate"):
+            raise PllError("this library has no pll_amd_simulate")
+        ops = np.ascontiguousarray(ops, dtype=OPS_DTYPE)
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1)
+        pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+        columns = int(self.s.sites) if columns is None else columns
+        if raw is None:
+            res = {}
+            if "out" in want:
+                res["out"] = np.zeros((replicates, len(nodes), columns), dtype=np.uint8)
+            if "categories" in want:
+                res["categories"] = np.zeros((replicates, columns), dtype=np.uint32)
+            if "invariant" in want:
+                res["invariant"] = np.zeros((replicates, columns), dtype=np.uint8)
+        else:
+            res = raw
+
+        def ptr(name):
+            return res[name].ctypes.data if res.get(name) is not None else None
+        sym = None if symbols is None else C.c_char_p(symbols if isinstance(symbols, bytes) else symbols.encode())
+        ok = self.lib.pll_amd_simulate(
+            self.ptr, ops.ctypes.data if len(ops) else None, len(ops), root,
+            SIMULATE_NO_EDGE if edge is None else edge[0], 0 if edge is None else edge[1], pi.ctypes.data, seed,
+            first_replicate, replicates, first_column, columns, nodes.ctypes.data if len(nodes) else None, len(nodes),
+            flags, C.cast(sym, C.c_void_p) if sym is not None else None, gap_symbol, ptr("out"), ptr("categories"),
+            ptr("invariant"))
+        if raw is not None:
+            return ok
+        self._check(ok, "pll_amd_simulate")
+        return res
 
     def matrix_joins(self, distances, variances=None, method=JOIN_NJ):
         """pll_amd_matrix_joins: (joins, last) as PllLibrary.joins_from_matrix returns them, from the device"""
