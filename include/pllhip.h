@@ -432,6 +432,20 @@ PLLHIP_EXPORT int pllhip_fused_index_dry(unsigned int ch, unsigned int sps, unsi
                                          unsigned int raw, unsigned int * out3);
 PLLHIP_EXPORT unsigned int pllhip_fused_row_index_dry(const unsigned int * row, unsigned int kind, unsigned int sps,
                                                       unsigned int sub_step, unsigned int lane);
+/* The list kernel's gather descriptors (tests/test_host_gather_desc.py): the finished numbers the encoder writes per
+ * gathered factor in place of the character word the kernel used to decode.
+ * forms == NULL: desc_out[2] = {table_off, form} of gather `k` (0-3) of an op with character word
+ * `ch` whose first table is `gather_off` bytes into the table buffer; out3 (may be NULL) as pllhip_fused_index_dry's, read
+ * through the descriptor -- out3[2] is the byte offset into the table, the entry's size in the shift.
+ * forms != NULL: a segment of `nops` ops encoded by the launch's own encoder steps; forms[4 pos + k] = what gather k of op
+ * pos is: 0 none, 1 / 2 a single tip's row as the table's first / second character, 3 a cherry's pair row, 256 + u a quad
+ * row over a table of u units; edge: the record behind the last op is the edge pseudo-op's.  recs_out[(nops + 3) x 13]:
+ * per record (two headers first) chars .. chars4, gather_off, four descriptors of two words.
+ * Returns 0, or 1 for arguments no kernel instance has. */
+PLLHIP_EXPORT int pllhip_fused_gather_desc_dry(unsigned int sps, unsigned int ch, unsigned int k, unsigned int gather_off,
+                                               unsigned int sub_step, unsigned int lane, unsigned int raw,
+                                               unsigned int * desc_out, unsigned int * out3, const unsigned int * forms,
+                                               unsigned int nops, int edge, unsigned int * recs_out);
 PLLHIP_EXPORT int pllhip_fused_plan_dry_rows(unsigned int tips, unsigned int clv_buffers, unsigned int scale_buffers,
                                              int pattern_tip, unsigned int rate_cats, const pllhip_op_t * ops,
                                              unsigned int count, unsigned int nslots, unsigned int * nkept,

@@ -35,7 +35,9 @@
 //   tiles     a wave's first rounds by fixed stride, the last third from eight counters (the XCDs
 //             do not write at the same rate), the ticket requested two ops before it is needed
 //   plan      one 64-byte record per op, read through the scalar data cache one op ahead: absolute
-//             addresses and LDS offsets, decoded by the host (FusedRec in partials_fused.hpp)
+//             addresses and LDS offsets, decoded by the host (FusedRec in partials_fused.hpp), and behind it
+//             one descriptor of finished numbers per gathered factor of the op ahead (FusedGatherDesc: the
+//             table's offset, the row's LDS offset, field width, shift and form) -- 128 bytes per op
 //   cherries  a tip-tip op is not run at all where the list allows it: its parent is DEFERRED (deferred.hip), and the ops
 //             that read it take their factor from a table -- gathered-inner (kind 1) and gathered-gathered (kind 3)
 //   pairs     the parent of a gathered-gathered op that nothing reads from HBM is walked but not stored: its tile stores
@@ -51,9 +53,9 @@
 //             pays for is every instruction it issues, vector or scalar; taking instructions OUT (the scaling
 //             test's early exit) bought the rest
 //   scalar    what is wave-uniform, or already a wave mask, stays in scalar registers: the scaling decision is
-//             made on the compares' own 64-bit masks (scale_groups()), the words of the ONE row a gathered factor
-//             names are masked and shifted before a lane picks its byte (gather_factor()) -- partials_fused.hpp has
-//             the integer code, which the host runs as well (tests/test_host_scalar_masks.py, test_host_pair_rows.py)
+//             made on the compares' own 64-bit masks (scale_groups()); what a gather needs of its record is a
+//             descriptor the host has finished, not a word to decode (gather_factor()) -- partials_fused.hpp has
+//             the integer code, which the host runs as well (tests/test_host_scalar_masks.py, test_host_gather_desc.py)
 //   pair rows a cherry's table index (c1 << 4) | c2 depends on its two tip rows only: it is cached, one row of bytes per
 //             ordered tip pair (pair_rows.hip), and a factor over a cherry reads that row instead of joining two
 //
@@ -90,30 +92,36 @@ __device__ __forceinline__ void st16g(unsigned long long base, unsigned int byte
   else *p = v;
 }
 
-// ---- a plan record: sixteen words, one scalar load (all of this is wave-uniform) ----
+// ---- a plan record: sixteen words, one scalar load, and behind them the eight words of its four gather descriptors,
+// a second one issued with it (all of this is wave-uniform) ----
 typedef const unsigned int __attribute__((address_space(4))) * const_words;
 typedef const unsigned long long __attribute__((address_space(4))) * const_quads;
 struct Rec
 {
   unsigned int w[16];
+  unsigned int d[8];
 };
-// (constant address space: a scalar load; adjacent words, the compiler merges them into one)
-__device__ __forceinline__ Rec rec_load(const FusedRec * plan, unsigned int i)
+// (constant address space: scalar loads; adjacent words, the compiler merges them -- and drops the words nobody reads.
+// Of the 64 bytes behind the record only the first 32 are descriptors and are loaded: FusedPlanRec::pad is uploaded
+// and never read, it keeps a record and its descriptors within the cache lines they fill)
+__device__ __forceinline__ Rec rec_load(const FusedPlanRec * plan, unsigned int i)
 {
   const const_words p = (const_words)(unsigned long long)(plan + i);
   Rec r;
 #pragma unroll
   for (int t = 0; t < 16; ++t) r.w[t] = p[t];
+#pragma unroll
+  for (int t = 0; t < 8; ++t) r.d[t] = p[16 + t];
   return r;
 }
+// gather descriptor k of the record (partials_fused.hpp: FusedGatherDesc), as the words the instructions take
+__device__ __forceinline__ unsigned int rec_gd_table(const Rec & r, int k) { return r.d[2 * k]; }
+__device__ __forceinline__ unsigned int rec_gd_form(const Rec & r, int k) { return r.d[2 * k + 1]; }
+__device__ __forceinline__ bool rec_gd_present(const Rec & r, int k) { return (r.d[2 * k + 1] & PLLHIP_FUSED_GD_PRESENT) != 0u; }
 __device__ __forceinline__ unsigned long long rec_quad(const Rec & r, int t) { return (unsigned long long)r.w[t] | ((unsigned long long)r.w[t + 1] << 32); }
 __device__ __forceinline__ unsigned int rec_chars(const Rec & r) { return r.w[0]; }
-__device__ __forceinline__ unsigned int rec_chars2(const Rec & r) { return r.w[1]; }
-__device__ __forceinline__ unsigned int rec_chars3(const Rec & r) { return r.w[2]; }
-__device__ __forceinline__ unsigned int rec_chars4(const Rec & r) { return r.w[3]; }
 __device__ __forceinline__ unsigned int rec_req_lmat(const Rec & r) { return r.w[4]; }
 __device__ __forceinline__ unsigned int rec_req_rmat(const Rec & r) { return r.w[5]; }
-__device__ __forceinline__ unsigned int rec_gather(const Rec & r) { return r.w[6]; }
 __device__ __forceinline__ unsigned int rec_flags(const Rec & r) { return r.w[7]; }
 __device__ __forceinline__ unsigned long long rec_parent(const Rec & r) { return rec_quad(r, 8); }
 __device__ __forceinline__ unsigned long long rec_pscaler(const Rec & r) { return rec_quad(r, 10); }
@@ -354,7 +362,7 @@ __device__ __attribute__((noinline)) double edge_site_loglk(double terma, unsign
 //       in their slots and stored, 8 bytes per site (the epilogue below; one segment, 1 / 2 / 4 rate categories, per-site
 //       or no scale buffers).  Without it the kernel is what it was: every line the flag adds is under `if (EDGE)`.
 template <int RC, int J, int MODE, int NTP, int WPS, bool EDGE>
-__global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restrict__ plan0, FusedBases bases,
+__global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedPlanRec * __restrict__ plan0, FusedBases bases,
                                                         unsigned int nops0, unsigned int sites, unsigned int nslots,
                                                         double2 * sink, unsigned int * next_tile, unsigned int dynamic_rounds,
                                                         unsigned int site_base, unsigned int tile_groups,
@@ -467,7 +475,7 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
   {
     // the item's segment: its records, its length, where its first character rows are
     size_t tile = item;
-    const FusedRec * plan = plan0;
+    const FusedPlanRec * plan = plan0;
     unsigned int nops = nops0;
     unsigned long long row_first = row0;
     if (nsegs > 1u)
@@ -528,71 +536,70 @@ __global__ __launch_bounds__(256, WPS) void k_dna_fused(const FusedRec * __restr
     // destination registers (seen once: the arrays kept as one transposed 8-register value and re-packed right behind
     // the loads, until both ends of their life were made whole 16-byte operands of an empty asm statement).
     constexpr bool SECOND = RC <= 4 && MODE != SCALE_RATE; // (partials.hip: what may defer a cherry; checked by the launch)
-    constexpr unsigned int TB = 256u * W * 16u; // bytes of a table
-    constexpr unsigned int ENTRY_SHIFT = RC == 1 ? 5u : RC == 2 ? 6u : RC == 4 ? 7u : 8u; // log2 of an entry's W * 16 bytes
-    static_assert((1u << ENTRY_SHIFT) == W * 16u, "an entry of a table: W lanes of 16 bytes");
     // Index delivery.  The tile's character batch lies in the wave's LDS block `chb` as the load fetched it, lane
     // position p's 16 bytes at 16 p, and a lane takes the index of ITS site with one LDS read of 16 bits: a quad row's
     // class (the WIDE form, quad_rows.hip; any of an op's gathers: a reader of two folded quad products has four), or
     // the pair of bytes that holds its byte -- of a cherry's cached pair row, whose bytes already are the table's index
     // (pair_rows.hip), or of a single tip's row, masked and shifted to its place.  Where the read is and what becomes of
-    // it: pllhip_fused_index, partials_fused.hpp -- the row's wave-uniform byte offset plus a number of the lane's that
-    // never changes, the second sub-step an immediate offset behind the first; the forms differ in numbers, not in
-    // instructions.  (Until the batch lay in LDS it was four registers, and every gather brought its row's words to
-    // the scalar side with v_readlane and back: some 65 instructions per wide factor.)
+    // it: pllhip_fused_index_of_desc, partials_fused.hpp -- the row's wave-uniform byte offset plus a number of the
+    // lane's that never changes, the second sub-step a wave-uniform stride behind the first; the forms differ in numbers,
+    // not in instructions.  (Until the batch lay in LDS it was four registers, and every gather brought its row's words
+    // to the scalar side with v_readlane and back: some 65 instructions per wide factor.)
     // The reads of all of an op's factors are issued together, at the top of the op that gathers them (index_reads()
     // in step()), and waited for once.
-    auto factor_index = [&](unsigned int (&raw)[J], unsigned int ch, auto may_be_wide) {
-      const unsigned int c = (SECOND && decltype(may_be_wide)::value) ? ch : ch & ~PLLHIP_FUSED_CH_WIDE;
+    // The numbers come FINISHED, in the record's gather descriptors (FusedGatherDesc: the encoder works them out once
+    // per list -- decoded here from the record's character word, once for the reads and once more for the gathers, they
+    // cost 42 instructions per wide factor; from a descriptor 18: 7 for the two reads, 11 for the two gathers).  A lane
+    // adds the descriptor's row offset to ITS offset, one bit field of its constant `pick` (pllhip_fused_lane_pick) that
+    // the descriptor's form word chooses, and the form word is the operand of the extract and the shifts as it stands
+    // or after one scalar shift.
+    const unsigned int pick = pllhip_fused_lane_pick<SPS>(lane);
+    // (the block's LDS address as a lane value: one three-operand add takes one scalar operand)
+    unsigned int chb_lane = chb_lds_b;
+    asm volatile("" : "+v"(chb_lane));
+    auto factor_index = [&](unsigned int (&raw)[J], const Rec & r, int g) {
+      const unsigned int form = rec_gd_form(r, g);
+      const unsigned int first = __builtin_amdgcn_ubfe(pick, form, 8u) + chb_lane + PLLHIP_FUSED_GD_LDS(form);
 #pragma unroll
-      for (unsigned int j = 0; j < J; ++j)
-      {
-        raw[j] = *reinterpret_cast<const unsigned short *>(chb + pllhip_fused_index<SPS>(c, j, lane).offset);
-      }
+      for (unsigned int j = 0; j < J; ++j) raw[j] = *(const unsigned short PLL_LDS *)(uintptr_t)(first + j * pllhip_fused_gather_stride<SPS>(form));
     };
-    auto gather_factor = [&](pll_v2d (&pt)[J], const unsigned int (&raw)[J], unsigned int ch, unsigned int table_off, auto may_be_wide,
-                             bool displaced) {
-      const unsigned int c = (SECOND && decltype(may_be_wide)::value) ? ch : ch & ~PLLHIP_FUSED_CH_WIDE;
-      const unsigned long long tab = (unsigned long long)(uintptr_t)bases.pairtab + table_off; // (uniform)
-      // The wide form's table has one entry per class and may be several tables long: a gather behind the first finds
-      // its own behind all of those before it, displaced by the tables the word's top byte counts.  The two forms differ
-      // in the OFFSET only, an ordinary lane value -- the load is ONE statement for both, so that the gathered registers
-      // have one writer per sub-step and nothing to merge behind it (see gather() below, point 1).
-      unsigned long long base = tab;
-      if ((c & PLLHIP_FUSED_CH_WIDE) && displaced) base = tab + (unsigned long long)(ch >> 24) * TB;
+    auto gather_factor = [&](pll_v2d (&pt)[J], const unsigned int (&raw)[J], const Rec & r, int g) {
+      // (the tables of one op follow each other in the table buffer, a quad's several units long: the descriptor's offset
+      // is the finished one.  The forms differ in NUMBERS only -- the load is ONE statement for all of them, so that the
+      // gathered registers have one writer per sub-step and nothing to merge behind it: see gather() below, point 1)
+      const unsigned long long base = (unsigned long long)(uintptr_t)bases.pairtab + rec_gd_table(r, g); // (uniform)
+      const unsigned int form = rec_gd_form(r, g);
+      const unsigned int drop = form & pick;
 #pragma unroll
       for (unsigned int j = 0; j < J; ++j)
       {
-        // (index * bytes of an entry + the lane's 16 of them: the rule's shift and the entry's in one)
-        const FusedIndexRead rd = pllhip_fused_index<SPS>(c, j, lane);
-        const unsigned int off = (rd.field(raw[j]) << (rd.shift + ENTRY_SHIFT)) | gat_lane;
+        // (the entry's field, times the bytes of an entry -- the rule's shift and the entry's in one -- plus the lane's 16)
+        const unsigned int off = (__builtin_amdgcn_ubfe(raw[j], drop, form >> 8) << ((form >> 16) & 31u)) | gat_lane;
         asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pt[j]) : "v"(off), "s"(base) : "memory");
       }
     };
-    // (the tables of one op follow each other in the table buffer: gather k reads k tables behind the first; a third
-    // and a fourth factor -- a right-hand operand that is a folded product, see step() -- always come together; where the
-    // factors are quads, tables of several units, each gather's word counts the units the gathers before it took beyond one)
+    // (a third and a fourth factor -- a right-hand operand that is a folded product, see step() -- always come together)
     struct GatherIndex
     {
       unsigned int raw[4][J];
     };
     auto index_reads = [&](GatherIndex & gi, const Rec & r) {
-      if (rec_chars(r) & PLLHIP_FUSED_CH_LTIP) factor_index(gi.raw[0], rec_chars(r), std::true_type());
-      if (SECOND && (rec_chars2(r) & PLLHIP_FUSED_CH_LTIP)) factor_index(gi.raw[1], rec_chars2(r), std::true_type());
-      if (SECOND && (rec_chars3(r) & PLLHIP_FUSED_CH_LTIP))
+      if (rec_gd_present(r, 0)) factor_index(gi.raw[0], r, 0);
+      if (SECOND && rec_gd_present(r, 1)) factor_index(gi.raw[1], r, 1);
+      if (SECOND && rec_gd_present(r, 2))
       {
-        factor_index(gi.raw[2], rec_chars3(r), std::true_type());
-        factor_index(gi.raw[3], rec_chars4(r), std::true_type());
+        factor_index(gi.raw[2], r, 2);
+        factor_index(gi.raw[3], r, 3);
       }
     };
     auto gather = [&](pll_v2d (&pt)[J], pll_v2d (&pt2)[J], pll_v2d (&pt3)[J], pll_v2d (&pt4)[J], const GatherIndex & gi, const Rec & r) {
-      const unsigned int ch = rec_chars(r), ch2 = rec_chars2(r);
-      if (ch & PLLHIP_FUSED_CH_LTIP) gather_factor(pt, gi.raw[0], ch, rec_gather(r), std::true_type(), false);
-      if (SECOND && (ch2 & PLLHIP_FUSED_CH_LTIP)) gather_factor(pt2, gi.raw[1], ch2, rec_gather(r) + TB, std::true_type(), true);
-      if (SECOND && (rec_chars3(r) & PLLHIP_FUSED_CH_LTIP))
+      const unsigned int ch = rec_chars(r);
+      if (rec_gd_present(r, 0)) gather_factor(pt, gi.raw[0], r, 0);
+      if (SECOND && rec_gd_present(r, 1)) gather_factor(pt2, gi.raw[1], r, 1);
+      if (SECOND && rec_gd_present(r, 2))
       {
-        gather_factor(pt3, gi.raw[2], rec_chars3(r), rec_gather(r) + 2u * TB, std::true_type(), true);
-        gather_factor(pt4, gi.raw[3], rec_chars4(r), rec_gather(r) + 3u * TB, std::true_type(), true);
+        gather_factor(pt3, gi.raw[2], r, 2);
+        gather_factor(pt4, gi.raw[3], r, 3);
       }
       // the list moves on to rows this batch does not hold (rare: every 1024 / TS tip operands): the lanes'
       // addresses of the next batch, then its rows, copied straight into the wave's batch block by LDS-DMA like a
@@ -1092,7 +1099,7 @@ unsigned int pllhip_fused_slots(const pllhip_ctx * c, unsigned int wgs)
 }
 
 template <int RC>
-static int launch_fused_rc(pllhip_ctx * c, const FusedRec * d_plan, const FusedBases & bases, unsigned int count,
+static int launch_fused_rc(pllhip_ctx * c, const FusedPlanRec * d_plan, const FusedBases & bases, unsigned int count,
                            unsigned int nslots, int mode, bool with_edge)
 {
   constexpr int J = PLLHIP_FUSED_J;
@@ -1226,15 +1233,72 @@ static unsigned int fused_lanes_per_row(unsigned int R)
   return tile_sites >= 16 ? tile_sites / 16 : 1;
 }
 
+// The character words, batches and tables of a segment's gathers, from what each gather IS -- gathered at all, the tip
+// rows it names, the units of its table where it is a quad (0: a byte form): the live path's (fused_seg_gathers below)
+// and the dry encoder's (pllhip_fused_gather_desc_dry).  Four shapes per position.  Returns 1 for rows the kernel
+// cannot address: more than 255 batches, a row beyond lane 63.
+struct FusedGatherShape
+{
+  bool gathered, first, second;
+  unsigned int units;
+};
+static int fused_gather_words(const FusedGatherShape * shapes, unsigned int n, unsigned int R, unsigned int batch0, size_t * ntables,
+                              FusedSegGathers & out)
+{
+  const unsigned int lpr = fused_lanes_per_row(R);
+  out.table_of.assign(n, 0);
+  for (int k = 0; k < 4; ++k) out.chars_of[k].assign(n, 0);
+  out.batch_of.assign(n, 0);
+  out.batch0 = batch0;
+  std::vector<unsigned int> ntips(n, 0);
+  for (unsigned int pos = 0; pos < n; ++pos)
+    for (int k = 0; k < 4; ++k)
+    {
+      // (a quad row is two planes: two rows of the batch, one behind the other)
+      const FusedGatherShape & g = shapes[4 * (size_t)pos + k];
+      ntips[pos] |= (g.units ? 3u : pllhip_fused_gather_rows(g.first, g.second)) << (2 * k);
+    }
+  unsigned int * const chars_out[4] = {out.chars_of[0].data(), out.chars_of[1].data(), out.chars_of[2].data(), out.chars_of[3].data()};
+  out.nbatches = pllhip_fused_char_batches8(ntips.data(), n, lpr, chars_out, out.batch_of.data());
+  if (batch0 + out.nbatches > 255 || 8 * lpr > 64) return 1;
+  for (unsigned int pos = 0; pos < n; ++pos)
+  {
+    out.batch_of[pos] += batch0;
+    if (shapes[4 * (size_t)pos].gathered) out.table_of[pos] = (unsigned int)(*ntables * fused_table_doubles(R) * sizeof(double));
+    unsigned int extra_units = 0, nquads = 0;
+    for (int k = 0; k < 4; ++k)
+    {
+      const FusedGatherShape & g = shapes[4 * (size_t)pos + k];
+      if (g.units)
+      {
+        // (the wide form: one row position, the planes lpr lanes apart; a later gather's table lies behind ALL the tables
+        // of the gathers before it -- the word's top byte says how many more than one each those took)
+        *ntables += g.units;
+        ++nquads;
+        unsigned int & ch = out.chars_of[k][pos];
+        ch = (ch & ~(PLLHIP_FUSED_CH_RTIP | 0xff00u)) | PLLHIP_FUSED_CH_WIDE | (k >= 1 ? extra_units << 24 : 0u);
+        extra_units += g.units - 1u;
+        if (PLLHIP_FUSED_CH_LPOS(ch) + 2 * lpr > 64) return 1;
+        continue;
+      }
+      *ntables += g.gathered;
+      out.chars_of[k][pos] |= pllhip_fused_gather_bits(g.first, g.second);
+      if ((g.first || g.second) && PLLHIP_FUSED_CH_LPOS(out.chars_of[k][pos]) + lpr > 64) return 1;
+    }
+    // (the tables of a quad's two factors, written for the pool's sake: behind the op's own)
+    *ntables += 2 * nquads;
+  }
+  return 0;
+}
+
 // The gathers of one segment, the first of its batches being batch0, of its tables *ntables (counted on).  Returns 1
 // for an op that is not what the planner makes (a malformed product or unstored op, gathers with a gap) or rows the
 // kernel cannot address: more than 255 batches, a row beyond lane 63.
 static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, bool rate_scalers, unsigned int batch0,
                              size_t * ntables, FusedSegGathers & out, const FusedQuadMarks * quads)
 {
-  const unsigned int n = (unsigned int)plan.size(), lpr = fused_lanes_per_row(R);
+  const unsigned int n = (unsigned int)plan.size();
   out.gx.resize(n);
-  out.table_of.assign(n, 0);
   for (unsigned int pos = 0; pos < n; ++pos)
   {
     const FusedOp & f = plan[pos];
@@ -1310,47 +1374,15 @@ static int fused_seg_gathers(const std::vector<FusedOp> & plan, unsigned int R, 
     // (an unstored pair product: its factors are kept, deferred.hip)
     for (int o = 0; f.unstored && o < 2; ++o) x.copy[o] = f.keep[o];
   }
-  for (int k = 0; k < 4; ++k) out.chars_of[k].assign(n, 0);
-  out.batch_of.assign(n, 0);
-  out.batch0 = batch0;
-  std::vector<unsigned int> ntips(n, 0);
+  std::vector<FusedGatherShape> shapes(4 * (size_t)n);
   for (unsigned int pos = 0; pos < n; ++pos)
-    for (int k = 0; k < 4; ++k)
-      // (a quad row is two planes: two rows of the batch, one behind the other)
-      ntips[pos] |= (out.gx[pos].g[k].type == FUSED_G_QUAD ? 3u : pllhip_fused_gather_rows(out.gx[pos].g[k].row1 != nullptr, out.gx[pos].g[k].row2 != nullptr))
-                    << (2 * k);
-  unsigned int * const chars_out[4] = {out.chars_of[0].data(), out.chars_of[1].data(), out.chars_of[2].data(), out.chars_of[3].data()};
-  out.nbatches = pllhip_fused_char_batches8(ntips.data(), n, lpr, chars_out, out.batch_of.data());
-  if (batch0 + out.nbatches > 255 || 8 * lpr > 64) return 1;
-  for (unsigned int pos = 0; pos < n; ++pos)
-  {
-    out.batch_of[pos] += batch0;
-    if (out.gx[pos].g[0].type != FUSED_G_NONE) out.table_of[pos] = (unsigned int)(*ntables * fused_table_doubles(R) * sizeof(double));
-    unsigned int extra_units = 0;
     for (int k = 0; k < 4; ++k)
     {
       const FusedOperand & g = out.gx[pos].g[k];
-      if (g.type == FUSED_G_QUAD)
-      {
-        // (the wide form: one row position, the planes lpr lanes apart; a later gather's table lies behind ALL the tables
-        // of the gathers before it -- the word's top byte says how many more than one each those took)
-        const unsigned int units = out.gx[pos].quad[k]->units;
-        *ntables += units;
-        unsigned int & ch = out.chars_of[k][pos];
-        ch = (ch & ~(PLLHIP_FUSED_CH_RTIP | 0xff00u)) | PLLHIP_FUSED_CH_WIDE | (k >= 1 ? extra_units << 24 : 0u);
-        extra_units += units - 1u;
-        if (PLLHIP_FUSED_CH_LPOS(ch) + 2 * lpr > 64) return 1;
-        continue;
-      }
-      *ntables += g.type != FUSED_G_NONE;
-      out.chars_of[k][pos] |= pllhip_fused_gather_bits(g.row1 != nullptr, g.row2 != nullptr);
-      if ((g.row1 || g.row2) && PLLHIP_FUSED_CH_LPOS(out.chars_of[k][pos]) + lpr > 64) return 1;
+      shapes[4 * (size_t)pos + k] = FusedGatherShape{g.type != FUSED_G_NONE, g.row1 != nullptr, g.row2 != nullptr,
+                                                     g.type == FUSED_G_QUAD ? out.gx[pos].quad[k]->units : 0u};
     }
-    // (the tables of a quad's two factors, written for the pool's sake: behind the op's own)
-    for (int k = 0; k < 4; ++k)
-      if (out.gx[pos].quad[k]) *ntables += 2;
-  }
-  return 0;
+  return fused_gather_words(shapes.data(), n, R, batch0, ntables, out);
 }
 
 // (a) Admission: is this a list the kernel takes?  No HIP call, nothing of the context changed: returns 1 for every
@@ -1414,7 +1446,7 @@ struct FusedEncodeIn
 // reload sources, the pair-table jobs, the character rows' addresses.
 struct FusedEncoded
 {
-  std::vector<FusedRec> recs;
+  std::vector<FusedPlanRec> recs;
   std::vector<FusedSeg> segs;
   std::vector<FusedSrc> srcs;
   std::vector<FusedPairJob> jobs;
@@ -1423,36 +1455,66 @@ struct FusedEncoded
   unsigned int longest = 0;
   size_t units = 0;                       // tables handed out so far (a quad's table takes several)
 };
-// what record `r` says about the ops ahead of position `pos` (pos may be -2, -1: the headers)
-static void fused_look_ahead(const FusedEncodeIn & in, const std::vector<FusedOp> & plan, const FusedSegGathers & ga,
-                             const FusedEdge * edge, FusedRec & r, long pos, std::vector<FusedSrc> & srcs)
+// What record `r` of a segment of n ops says about the GATHERS of the ops ahead of position `pos` (pos may be -2, -1: the
+// headers): the character words and the table of op + 1, the batch switch for op + 2.  The live encoder's and the dry one's.
+static void fused_look_ahead_gathers(const FusedSegGathers & ga, long n, FusedRec & r, long pos)
 {
-  const long n = (long)plan.size();
-  const unsigned int slot_bytes = in.slot.tile_bytes, count_bytes = in.slot.count_bytes;
   r.chars = r.chars2 = r.chars3 = r.chars4 = 0;
-  r.req_lmat = r.req_rmat = 0;
+  r.gather_off = 0;
   if (pos + 1 >= 0 && pos + 1 < n)
   {
     r.chars = ga.chars_of[0][pos + 1];
     r.chars2 = ga.chars_of[1][pos + 1];
     r.chars3 = ga.chars_of[2][pos + 1];
     r.chars4 = ga.chars_of[3][pos + 1];
+    r.gather_off = ga.table_of[pos + 1];
   }
+  if (pos + 2 < n)
+  {
+    // (the rows of op + 2 are fetched once op + 1's characters have been taken from the registers)
+    const unsigned int now = pos + 1 >= 0 ? ga.batch_of[pos + 1] : ga.batch0;
+    if (ga.batch_of[pos + 2] != now) r.chars |= PLLHIP_FUSED_CH_LOAD | ga.batch_of[pos + 2] << 24;
+  }
+}
+// The gather descriptors of a segment's records (partials_fused.hpp: FusedGatherDesc), every one of them -- the headers,
+// the ops, the record behind the last op -- the function of its record's character word, the gather's number and
+// gather_off: what k_dna_fused reads in place of the words.  Returns 1 for a table beyond the descriptor's 32 bits.
+static int fused_fill_descriptors(FusedPlanRec * rs, size_t count, unsigned int rate_cats)
+{
+  const unsigned int w = 2u * rate_cats, table_bytes = 256u * w * 16u;
+  unsigned int entry_shift = 0;
+  while ((1u << entry_shift) < w * 16u) ++entry_shift; // (an entry of a table: W lanes of 16 bytes)
+  for (size_t i = 0; i < count; ++i)
+  {
+    const FusedRec & r = rs[i].rec;
+    const unsigned int ch[4] = {r.chars, r.chars2, r.chars3, r.chars4};
+    for (unsigned int k = 0; k < 4; ++k)
+    {
+      if ((ch[k] & PLLHIP_FUSED_CH_LTIP) && pllhip_fused_gather_table_off(ch[k], k, r.gather_off, table_bytes) > 0xffffffffull) return 1;
+      rs[i].gd[k] = pllhip_fused_gather_desc(ch[k], k, r.gather_off, entry_shift, table_bytes);
+    }
+  }
+  return 0;
+}
+// what record `r` says about the ops ahead of position `pos` (pos may be -2, -1: the headers)
+static void fused_look_ahead(const FusedEncodeIn & in, const std::vector<FusedOp> & plan, const FusedSegGathers & ga,
+                             const FusedEdge * edge, FusedRec & r, long pos, std::vector<FusedSrc> & srcs)
+{
+  const long n = (long)plan.size();
+  const unsigned int slot_bytes = in.slot.tile_bytes, count_bytes = in.slot.count_bytes;
+  fused_look_ahead_gathers(ga, n, r, pos);
+  r.req_lmat = r.req_rmat = 0;
   // (the edge pseudo-op at position n: its matrix is requested and staged as a right-hand one, like a tip-inner op's)
   if (edge && pos + 2 == n) r.req_rmat = (unsigned int)((edge->pmat - in.pmatrix) * sizeof(double));
   if (pos + 2 < n)
   {
     const FusedOp & f = plan[pos + 2];
-    // (the rows of op + 2 are fetched once op + 1's characters have been taken from the registers)
-    const unsigned int now = pos + 1 >= 0 ? ga.batch_of[pos + 1] : ga.batch0;
-    if (ga.batch_of[pos + 2] != now) r.chars |= PLLHIP_FUSED_CH_LOAD | ga.batch_of[pos + 2] << 24;
     r.req_lmat = (unsigned int)((f.lmat - in.pmatrix) * sizeof(double));
     r.req_rmat = (unsigned int)((f.rmat - in.pmatrix) * sizeof(double));
   }
   r.src = 0;
   if (pos + 1 < 0 || pos + 1 >= n + (edge ? 1 : 0)) return;
   const FusedOp & f = pos + 1 < n ? plan[pos + 1] : edge->op;
-  r.gather_off = pos + 1 < n ? ga.table_of[pos + 1] : 0u;
   // (a reader of folded products runs as an inner-inner op: both matrices)
   // (... unless its products are quads: a gathered operand needs no matrix)
   // (... and a reader of folded QUAD products forms them itself, an inner-inner op again: both matrices)
@@ -1504,7 +1566,7 @@ static void fused_fill_record(const FusedEncodeIn & in, const FusedOp & f, Fused
 }
 
 // one segment: its rows' addresses, its pair-table jobs, its records
-static void fused_encode_segment(const FusedEncodeIn & in, const std::vector<FusedOp> & plan, const FusedSegGathers & ga,
+static int fused_encode_segment(const FusedEncodeIn & in, const std::vector<FusedOp> & plan, const FusedSegGathers & ga,
                                  const FusedEdge * edge, FusedEncoded & out)
 {
   const unsigned int n = (unsigned int)plan.size(), lpr = fused_lanes_per_row(in.rate_cats);
@@ -1565,37 +1627,42 @@ static void fused_encode_segment(const FusedEncodeIn & in, const std::vector<Fus
   const size_t first = out.recs.size();
   out.segs.push_back(FusedSeg{(unsigned int)first, n, ga.batch0, 0u});
   out.recs.resize(first + n + 3);
-  FusedRec * rs = out.recs.data() + first;
-  memset(rs, 0, (n + 3) * sizeof(FusedRec));
-  fused_look_ahead(in, plan, ga, edge, rs[0], -2, out.srcs);
-  fused_look_ahead(in, plan, ga, edge, rs[1], -1, out.srcs);
+  FusedPlanRec * rs = out.recs.data() + first;
+  memset(rs, 0, (n + 3) * sizeof(FusedPlanRec));
+  fused_look_ahead(in, plan, ga, edge, rs[0].rec, -2, out.srcs);
+  fused_look_ahead(in, plan, ga, edge, rs[1].rec, -1, out.srcs);
   for (unsigned int pos = 0; pos < n; ++pos)
   {
-    fused_fill_record(in, plan[pos], rs[pos + 2], ga.gx[pos].quad[0] != nullptr && !(plan[pos].prod[0] & 8));
-    fused_look_ahead(in, plan, ga, edge, rs[pos + 2], (long)pos, out.srcs);
+    fused_fill_record(in, plan[pos], rs[pos + 2].rec, ga.gx[pos].quad[0] != nullptr && !(plan[pos].prod[0] & 8));
+    fused_look_ahead(in, plan, ga, edge, rs[pos + 2].rec, (long)pos, out.srcs);
   }
   rs[n + 2] = rs[n + 1]; // (loaded by the last op, never used)
-  rs[n + 2].flags &= ~PLLHIP_FUSED_RELOAD_NEXT;
-  if (!edge) return;
-  // ... but by the edge epilogue: where the two CLVs and their counts are
-  FusedRec & e = rs[n + 2];
-  const FusedOp & f = edge->op;
-  memset(&e, 0, sizeof(e));
-  if (f.lsc_slot >= 0) e.flags |= PLLHIP_FUSED_LCNT;
-  if (f.rsc_slot >= 0) e.flags |= PLLHIP_FUSED_RCNT;
-  e.lslot_b = (unsigned short)(f.lslot * in.slot.tile_bytes);
-  e.rslot_b = (unsigned short)(f.rslot * in.slot.tile_bytes);
-  e.lcnt_b = (unsigned short)((f.lsc_slot > 0 ? f.lsc_slot : 0) * in.slot.count_bytes);
-  e.rcnt_b = (unsigned short)((f.rsc_slot > 0 ? f.rsc_slot : 0) * in.slot.count_bytes);
+  rs[n + 2].rec.flags &= ~PLLHIP_FUSED_RELOAD_NEXT;
+  if (edge)
+  {
+    // ... but by the edge epilogue: where the two CLVs and their counts are
+    FusedRec & e = rs[n + 2].rec;
+    const FusedOp & f = edge->op;
+    memset(&e, 0, sizeof(e));
+    if (f.lsc_slot >= 0) e.flags |= PLLHIP_FUSED_LCNT;
+    if (f.rsc_slot >= 0) e.flags |= PLLHIP_FUSED_RCNT;
+    e.lslot_b = (unsigned short)(f.lslot * in.slot.tile_bytes);
+    e.rslot_b = (unsigned short)(f.rslot * in.slot.tile_bytes);
+    e.lcnt_b = (unsigned short)((f.lsc_slot > 0 ? f.lsc_slot : 0) * in.slot.count_bytes);
+    e.rcnt_b = (unsigned short)((f.rsc_slot > 0 ? f.rsc_slot : 0) * in.slot.count_bytes);
+  }
+  return fused_fill_descriptors(rs, n + 3, in.rate_cats);
 }
 
-static void fused_encode(const FusedEncodeIn & in, const std::vector<std::vector<FusedOp>> & plans, const FusedAdmitted & adm,
-                         const std::vector<FusedPairJob> * keep_jobs, const FusedEdge * edge, FusedEncoded & out)
+static int fused_encode(const FusedEncodeIn & in, const std::vector<std::vector<FusedOp>> & plans, const FusedAdmitted & adm,
+                        const std::vector<FusedPairJob> * keep_jobs, const FusedEdge * edge, FusedEncoded & out)
 {
   out.longest = adm.longest;
-  for (size_t sg = 0; sg < plans.size(); ++sg) fused_encode_segment(in, plans[sg], adm.segs[sg], edge, out);
+  for (size_t sg = 0; sg < plans.size(); ++sg)
+    if (fused_encode_segment(in, plans[sg], adm.segs[sg], edge, out)) return 1;
   // the kept tables T of the cherries this list defers: written straight into their places in the pool
   if (keep_jobs) out.jobs.insert(out.jobs.end(), keep_jobs->begin(), keep_jobs->end());
+  return 0;
 }
 
 // What every table job of an encoded plan reads (ctx.hpp: FusedJobReads), for the staleness rule of a replay: a matrix
@@ -1638,7 +1705,7 @@ static void fused_job_reads(const pllhip_ctx * c, const std::vector<FusedPairJob
 // repeated call with the same op list needs (pllhip_relaunch_fused).
 static int fused_upload(pllhip_ctx * c, const FusedEncoded & enc)
 {
-  const size_t rec_bytes = enc.recs.size() * sizeof(FusedRec);
+  const size_t rec_bytes = enc.recs.size() * sizeof(FusedPlanRec);
   const size_t seg_bytes = (size_t)PLLHIP_FUSED_MAX_SEGS * sizeof(FusedSeg);
   const size_t src_bytes = (enc.srcs.size() + 1) * sizeof(FusedSrc);
   const size_t job_bytes = (enc.jobs.size() + 1) * sizeof(FusedPairJob);
@@ -1984,7 +2051,11 @@ int pllhip_launch_fused(pllhip_ctx * c, const std::vector<std::vector<FusedOp>> 
   const FusedEncodeIn in = {c->pmatrix, c->d_pairtab, c->fused_zero_row, pllhip_fused_slot_size(c->sh.rate_cats, c->sh.rate_scalers != 0),
                             c->sh.rate_cats, c->sh.rate_scalers != 0, c->tip_stride};
   FusedEncoded enc;
-  fused_encode(in, plans, adm, keep_jobs, edge, enc);
+  if (fused_encode(in, plans, adm, keep_jobs, edge, enc))
+  {
+    pllhip_set_error("whole-list launch: a gather's table lies beyond the descriptor's 32 bits");
+    return -1;
+  }
   if ((rc = fused_upload(c, enc))) return rc;
   c->fused_last_count = plans[0].size();
   c->fused_last_ndeferred = keep_jobs ? (unsigned int)keep_jobs->size() : 0u;
@@ -2006,7 +2077,7 @@ int pllhip_relaunch_fused(pllhip_ctx * c)
   static_assert(PLLHIP_TILE_COUNTER_BYTES == 256 * 128, "one counter per thread of k_dna_pair_tables' first workgroup");
   // (pair rows whose tip rows were written since: rebuilt in place before this launch reads them)
   if (const int rc = pllhip_pair_rows_refresh(c)) return rc;
-  const FusedRec * d_plan = (const FusedRec *)c->d_plan;
+  const FusedPlanRec * d_plan = (const FusedPlanRec *)c->d_plan;
   const FusedPairJob * d_jobs = (const FusedPairJob *)(static_cast<const char *>(c->d_plan) + c->fused_last_jobs_offset);
   const FusedBases bases = {c->pmatrix, c->d_pairtab,
                             (const unsigned long long *)(static_cast<const char *>(c->d_plan) + c->fused_last_rowtab_offset),
@@ -2220,5 +2291,77 @@ extern "C" int pllhip_fused_index_dry(unsigned int ch, unsigned int sps, unsigne
   out3[0] = rd.offset;
   out3[1] = rd.width;
   out3[2] = rd.index(raw);
+  return 0;
+}
+
+// The gather descriptors without a device (partials_fused.hpp: FusedGatherDesc; tests/test_host_gather_desc.py).
+// forms == NULL: ONE descriptor.  desc_out[2] = the descriptor of gather `k` of an op whose character word is `ch` and
+// whose first table is at `gather_off`, for the instance of `sps` sites per sub-step; out3 (may be NULL) = what lane
+// `lane` makes of it for sub-step `sub_step`: {the byte offset it reads of the wave's batch block, the bytes it reads
+// there, the BYTE offset into the table it forms of the value `raw` read there: the entry's size is in the shift}.
+// forms != NULL: an ENCODED segment of `nops` ops.  forms[4 pos + k] says what gather k of op pos is -- 0 none, 1 a
+// single tip's row as the table's first character, 2 as its second, 3 a cherry's pair row, 256 + u a quad row with a
+// table of u units -- and the segment is encoded by the live encoder's own steps (fused_gather_words,
+// fused_look_ahead_gathers, fused_fill_descriptors; edge != 0: the record behind the last op is the pseudo-op's).
+// recs_out[(nops + 3) x 13]: per record, headers first, chars .. chars4, gather_off and the eight descriptor words.
+// Returns 0; 1 for arguments no kernel instance has, or a list the encoder refuses.
+extern "C" int pllhip_fused_gather_desc_dry(unsigned int sps, unsigned int ch, unsigned int k, unsigned int gather_off,
+                                            unsigned int sub_step, unsigned int lane, unsigned int raw, unsigned int * desc_out,
+                                            unsigned int * out3, const unsigned int * forms, unsigned int nops, int edge,
+                                            unsigned int * recs_out)
+{
+  if (!(sps == 4u || sps == 8u || sps == 16u || sps == 32u)) return 1;
+  const unsigned int w = 64u / sps, rate_cats = w / 2u, table_bytes = 256u * w * 16u;
+  unsigned int entry_shift = 0;
+  while ((1u << entry_shift) < w * 16u) ++entry_shift;
+  if (!forms)
+  {
+    if (!desc_out || k >= 4u || lane >= 64u || sub_step >= (unsigned int)PLLHIP_FUSED_J) return 1;
+    if ((ch & PLLHIP_FUSED_CH_WIDE) && sps == 4u) return 1;
+    if (pllhip_fused_gather_table_off(ch, k, gather_off, table_bytes) > 0xffffffffull) return 1;
+    const FusedGatherDesc d = pllhip_fused_gather_desc(ch, k, gather_off, entry_shift, table_bytes);
+    memcpy(desc_out, &d, sizeof(d));
+    if (!out3) return 0;
+    FusedIndexRead rd;
+    switch (sps)
+    {
+      case 4: rd = pllhip_fused_index_of_desc<4>(d, sub_step, lane); break;
+      case 8: rd = pllhip_fused_index_of_desc<8>(d, sub_step, lane); break;
+      case 16: rd = pllhip_fused_index_of_desc<16>(d, sub_step, lane); break;
+      default: rd = pllhip_fused_index_of_desc<32>(d, sub_step, lane); break;
+    }
+    if (rd.offset + rd.width > PLLHIP_FUSED_BATCH_BYTES) return 1;
+    out3[0] = rd.offset;
+    out3[1] = rd.width;
+    out3[2] = rd.index(raw);
+    return 0;
+  }
+  if (!recs_out || nops < 2u || nops > PLLHIP_FUSED_MAX_OPS) return 1;
+  std::vector<FusedGatherShape> shapes(4 * (size_t)nops);
+  for (size_t i = 0; i < shapes.size(); ++i)
+  {
+    const unsigned int f = forms[i];
+    if (!(f <= 3u || (f > 256u && f <= 256u + PLLHIP_QUAD_MAX_CLASSES / 256u)) || (f > 256u && sps == 4u)) return 1;
+    // (gathers are numbered without gaps)
+    if (f && (i & 3u) && !forms[i - 1]) return 1;
+    shapes[i] = FusedGatherShape{f != 0u, f == 1u || f == 3u, f == 2u || f == 3u, f > 256u ? f - 256u : 0u};
+  }
+  FusedSegGathers ga;
+  size_t ntables = 0;
+  if (fused_gather_words(shapes.data(), nops, rate_cats, 0u, &ntables, ga)) return 1;
+  if (ntables * (size_t)table_bytes > 0xffffffffull) return 1;
+  std::vector<FusedPlanRec> rs((size_t)nops + 3);
+  memset(rs.data(), 0, rs.size() * sizeof(FusedPlanRec));
+  for (long pos = -2; pos < (long)nops; ++pos) fused_look_ahead_gathers(ga, (long)nops, rs[pos + 2].rec, pos);
+  rs[nops + 2] = rs[nops + 1];
+  if (edge) memset(&rs[nops + 2], 0, sizeof(FusedPlanRec));
+  if (fused_fill_descriptors(rs.data(), rs.size(), rate_cats)) return 1;
+  for (size_t i = 0; i < rs.size(); ++i)
+  {
+    unsigned int * o = recs_out + 13 * i;
+    const unsigned int five[5] = {rs[i].rec.chars, rs[i].rec.chars2, rs[i].rec.chars3, rs[i].rec.chars4, rs[i].rec.gather_off};
+    memcpy(o, five, sizeof(five));
+    memcpy(o + 5, rs[i].gd, sizeof(rs[i].gd));
+  }
   return 0;
 }

@@ -1,5 +1,6 @@
 // partials_fused.hpp -- plan of the site-blocked whole-list kernels: planner and the 20-state list's classes, certificate
-// bounds and walk (fused_plan.hip), kernels (partials_fused.hip, 4 states; partials_aa_fused.hip, 20)
+// bounds and walk (fused_plan.hip), kernels (partials_fused.hip, 4 states; partials_aa_fused.hip, 20); the 4-state
+// list's record, index rule and gather descriptors, one definition each for the kernel, the encoder and the host
 #ifndef PLLHIP_PARTIALS_FUSED_HPP_
 #define PLLHIP_PARTIALS_FUSED_HPP_
 
@@ -97,7 +98,8 @@ struct FusedOp
 };
 
 // The plan as the kernel reads it, through the scalar data cache: ONE 64-byte record per op (one
-// scalar load, one cache line), holding everything the wave does WHILE that op runs, ready
+// scalar load, one cache line; the gather descriptors of FusedPlanRec below lie behind it, a second
+// load issued with it), holding everything the wave does WHILE that op runs, ready
 // to use -- absolute addresses and LDS byte offsets, no indices to multiply out:
 //   - what it requests for the op two ahead (P-matrix offsets),
 //   - the pair table it gathers from for the op one ahead and where that op's tip characters are
@@ -108,7 +110,9 @@ struct FusedOp
 // a wave-op then cost 124 scalar + 124 vector instructions of which 30 were arithmetic, and that
 // the wave, not HBM, was the limit (tools/pmc_instmix.sh) -- so the
 // host now does the decoding once per list.  The records hold addresses: they are rebuilt when an
-// arena moves (layout_epoch).
+// arena moves (layout_epoch).  (The gathers added since brought a packed word back, chars .. chars4:
+// the kernel no longer reads it but for CH_LOAD and its batch -- FusedGatherDesc holds the same,
+// finished; the words are still written, for the host's tests and the batch switch.)
 struct FusedRec
 {
   unsigned int chars;                    // tip characters of op + 1, PLLHIP_FUSED_CH_* below
@@ -256,8 +260,9 @@ __host__ __device__ inline unsigned int pllhip_quad_row_class(const unsigned cha
 // bytes at byte 16 p, as the one load of a tile fetched them -- so a byte row's TS bytes lie in a piece from 16 pos on,
 // a quad row's two planes as two pieces, the second (lanes per row) x 16 bytes behind the first.  What lane `lane` reads
 // of that block for sub-step j of the gather a record's character word `ch` describes, and the table index it forms of
-// it: ONE definition for gather_factor() of k_dna_fused, the host (pllhip_fused_index_dry, tests/test_host_gather_index.py)
-// and the older dry entry points (pllhip_fused_row_index_dry, pllhip_fused_pair_index_dry, pllhip_fused_quad_pick_dry).
+// it: ONE definition for gather_factor() of k_dna_fused (through the gather descriptor below, which is what the kernel
+// reads), the host (pllhip_fused_index_dry, tests/test_host_gather_index.py; pllhip_fused_gather_desc_dry) and the older
+// dry entry points (pllhip_fused_row_index_dry, pllhip_fused_pair_index_dry, pllhip_fused_quad_pick_dry).
 // Both forms read the ALIGNED 16 bits that hold the lane's entry -- a quad row's class whole, a byte row's byte as one
 // half of them (`drop`: 0 or 8 bits below it) --, so that the kernel has one read instruction and no branch between the
 // forms: they differ in numbers only.  The offset is the row's wave-uniform 16 pos plus a number of the lane's that
@@ -271,19 +276,112 @@ struct FusedIndexRead
   __host__ __device__ constexpr unsigned int field(unsigned int raw) const { return (raw >> drop) & mask; }
   __host__ __device__ constexpr unsigned int index(unsigned int raw) const { return field(raw) << shift; }
 };
+
+// ---- Gather descriptors.  Everything the rule above makes of a record's character word is a constant of the LIST -- the
+// same for every tile and every wave --, so the encoder works it out once and the kernel reads FINISHED numbers: one
+// descriptor per gathered factor of an op, up to four, behind the op's FusedRec (FusedPlanRec below).  The kernel tests
+// no flag of the character word and derives nothing from it; what is left to a lane is one constant of its own
+// (pllhip_fused_lane_pick) and the descriptor's numbers as operands.
+//   table_off    the factor's table, in bytes from FusedBases::pairtab: gather_off + (k + displaced units) tables
+//   form         PLLHIP_FUSED_GD_*: the other numbers, each where the instruction that takes it finds it -- the vector
+//                unit's bit-field extract and its shifts read the low five bits of their operand only, so a number at
+//                bit 0 IS an operand, and one at bit 8 or 16 after one scalar shift of the word
+// Two words, not four: sixteen words of descriptors live across the op boundary did not fit the scalar registers of the
+// instance with an edge epilogue and per-site scaling (reads of spilled registers inside the op loop); eight do.
+struct FusedGatherDesc
+{
+  unsigned int table_off;
+  unsigned int form;
+};
+static_assert(sizeof(FusedGatherDesc) == 8, "two words per factor");
+// FusedGatherDesc::form
+//   bits 0-4   PICK: 8 the byte forms, 16 the wide form.  Three uses: the bit at which the form's read offset begins in
+//              the lane's constant; and-ed with that constant, the lane's `drop` (bit 3: a byte form's odd sites drop 8
+//              bits); and, at 8 sites per sub-step, the bytes between the two sub-steps' reads -- at 4, 16 and 32 sites the
+//              two forms have the same stride, the sites per sub-step (pllhip_fused_gather_stride)
+//   bit 7      the factor is gathered at all
+//   bits 8-12  BITS: the field's width, 16, 8 or 4 (FusedIndexRead::mask is (1 << BITS) - 1)
+//   bits 16-19 SHIFT: the rule's shift plus the instance's log2 of a table entry's bytes, in one (12 at most)
+//   bits 20-31 LDS: the byte offset of the row in the wave's batch block, 16 CH_LPOS (bits 20-23 are 0: what reads
+//              SHIFT as five bits reads SHIFT)
+#define PLLHIP_FUSED_GD_PICK(f) ((f) & 31u)
+#define PLLHIP_FUSED_GD_PRESENT (1u << 7)
+#define PLLHIP_FUSED_GD_BITS(f) (((f) >> 8) & 31u)
+#define PLLHIP_FUSED_GD_SHIFT(f) (((f) >> 16) & 31u)
+#define PLLHIP_FUSED_GD_LDS(f) ((f) >> 20)
+#define PLLHIP_FUSED_GD_PICK_BYTE 8u
+#define PLLHIP_FUSED_GD_PICK_WIDE 16u
+// The record and its descriptors as the device reads them: 128 bytes per op, the descriptors a scalar load of their own
+// behind the record (the rest is padding: a record and its descriptors never straddle more cache lines than they fill).
+struct FusedPlanRec
+{
+  FusedRec rec;
+  FusedGatherDesc gd[4];
+  unsigned int pad[8];
+};
+static_assert(sizeof(FusedPlanRec) == 128, "a record, four descriptors, padding");
+// (the vector unit's v_bfe_u32: offset and width are the low five bits of their operands)
+__host__ __device__ constexpr unsigned int pllhip_fused_bfe(unsigned int x, unsigned int offset, unsigned int width)
+{
+  return (width & 31u) == 0u ? 0u : (x >> (offset & 31u)) & ((1u << (width & 31u)) - 1u);
+}
+// The bytes between the reads of sub-step 0 and sub-step 1: site SPS + s lies that far behind site s in both forms, and
+// in the same half of its 16 bits (SPS is even).
 template <unsigned int SPS>
-__host__ __device__ constexpr FusedIndexRead pllhip_fused_index(unsigned int ch, unsigned int j, unsigned int lane)
+__host__ __device__ constexpr unsigned int pllhip_fused_gather_stride(unsigned int form)
 {
   static_assert(SPS == 4 || SPS == 8 || SPS == 16 || SPS == 32, "sites per sub-step");
   constexpr unsigned int TS = PLLHIP_FUSED_J * SPS, LPR = TS >= 16 ? TS / 16 : 1;
-  // (the lane's site of sub-step 0, and what a sub-step adds: site j SPS + s lies j `step` bytes behind site s in both
-  // forms, and in the same half of its 16 bits -- SPS is even)
-  const unsigned int site = lane / (64u / SPS);
+  static_assert(SPS == 4 || pllhip_quad_row_offset(SPS, LPR * 16u) == (SPS == 8 ? PLLHIP_FUSED_GD_PICK_WIDE : SPS), "the wide form's stride");
+  static_assert(SPS != 8 || SPS == PLLHIP_FUSED_GD_PICK_BYTE, "the byte forms' stride at 8 sites");
+  return SPS == 8 ? PLLHIP_FUSED_GD_PICK(form) : SPS;
+}
+// The descriptor of gather `k` of an op, from what the encoder has: the gather's character word, the op's gather_off
+// and the instance's numbers -- log2 of an entry's bytes, bytes of a table.  (A gather behind the first finds its table
+// behind all the tables of those before it: k of them, and what a wide gather's word counts in its top byte -- the
+// first word's top byte is the batch of CH_LOAD.)  The 64-bit offset is for the encoder's check.
+__host__ __device__ constexpr unsigned long long pllhip_fused_gather_table_off(unsigned int ch, unsigned int k, unsigned int gather_off,
+                                                                                unsigned int table_bytes)
+{
+  const unsigned int units = (k >= 1u && (ch & PLLHIP_FUSED_CH_WIDE)) ? ch >> 24 : 0u;
+  return (unsigned long long)gather_off + (unsigned long long)(k + units) * table_bytes;
+}
+__host__ __device__ constexpr FusedGatherDesc pllhip_fused_gather_desc(unsigned int ch, unsigned int k, unsigned int gather_off,
+                                                                       unsigned int entry_shift, unsigned int table_bytes)
+{
   const bool wide = (ch & PLLHIP_FUSED_CH_WIDE) != 0u;
-  const unsigned int first = wide ? (unsigned int)pllhip_quad_row_offset(site, LPR * 16u) : site & ~1u;
-  const unsigned int step = wide ? (unsigned int)pllhip_quad_row_offset(SPS, LPR * 16u) : SPS;
-  return {PLLHIP_FUSED_CH_LPOS(ch) * 16u + first + j * step, 2u, wide ? 0u : (site & 1u) * 8u,
-          wide ? 0xffffu : (ch & PLLHIP_FUSED_CH_NIBBLE) ? 15u : 255u, !wide && (ch & PLLHIP_FUSED_CH_SHIFT4) ? 4u : 0u};
+  const unsigned int bits = wide ? 16u : (ch & PLLHIP_FUSED_CH_NIBBLE) ? 4u : 8u;
+  const unsigned int shift = (!wide && (ch & PLLHIP_FUSED_CH_SHIFT4) ? 4u : 0u) + entry_shift;
+  return {(unsigned int)pllhip_fused_gather_table_off(ch, k, gather_off, table_bytes),
+          (wide ? PLLHIP_FUSED_GD_PICK_WIDE : PLLHIP_FUSED_GD_PICK_BYTE) | ((ch & PLLHIP_FUSED_CH_LTIP) ? PLLHIP_FUSED_GD_PRESENT : 0u) |
+              bits << 8 | shift << 16 | (PLLHIP_FUSED_CH_LPOS(ch) * 16u) << 20};
+}
+// The lane's constant: its site of sub-step 0 as each form reads it -- the byte forms' offset (the aligned 16 bits that
+// hold the site's byte) from bit 8, the wide form's (pllhip_quad_row_offset) from bit 16 -- and in bit 3 the 8 bits a
+// byte form drops below an odd site's byte.
+template <unsigned int SPS>
+__host__ __device__ constexpr unsigned int pllhip_fused_lane_pick(unsigned int lane)
+{
+  static_assert(SPS == 4 || SPS == 8 || SPS == 16 || SPS == 32, "sites per sub-step");
+  constexpr unsigned int TS = PLLHIP_FUSED_J * SPS, LPR = TS >= 16 ? TS / 16 : 1;
+  const unsigned int site = lane / (64u / SPS);
+  return (site & 1u) * 8u | (site & ~1u) << PLLHIP_FUSED_GD_PICK_BYTE |
+         (unsigned int)pllhip_quad_row_offset(site, LPR * 16u) << PLLHIP_FUSED_GD_PICK_WIDE;
+}
+// What lane `lane` reads for sub-step j of the gather a descriptor describes, and what becomes of it: the statements of
+// index_reads() and gather() of k_dna_fused, written out (shift: the descriptor's, the entry's bytes included).
+template <unsigned int SPS>
+__host__ __device__ constexpr FusedIndexRead pllhip_fused_index_of_desc(const FusedGatherDesc & d, unsigned int j, unsigned int lane)
+{
+  const unsigned int pick = pllhip_fused_lane_pick<SPS>(lane);
+  return {PLLHIP_FUSED_GD_LDS(d.form) + pllhip_fused_bfe(pick, d.form, 8u) + j * pllhip_fused_gather_stride<SPS>(d.form), 2u,
+          (d.form & pick) & 31u, (1u << PLLHIP_FUSED_GD_BITS(d.form)) - 1u, PLLHIP_FUSED_GD_SHIFT(d.form)};
+}
+// The rule of a character word: its descriptor's (no table, no entry size: the index as a number of entries).
+template <unsigned int SPS>
+__host__ __device__ constexpr FusedIndexRead pllhip_fused_index(unsigned int ch, unsigned int j, unsigned int lane)
+{
+  return pllhip_fused_index_of_desc<SPS>(pllhip_fused_gather_desc(ch, 0u, 0u, 0u, 0u), j, lane);
 }
 // ... applied to an image of the block (the host's dry entry points; the kernel reads its LDS)
 template <unsigned int SPS>
